@@ -89,7 +89,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-pe", action="store_true", help="skip the paired-end leg (mate rescue + pairing; reported beside, never `value`)")
     ap.add_argument("--no-hard-genome", action="store_true", help="skip the beside leg that repeats the steps on the grch38_like genome profile")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: rendezvous (gloo), barriers and the JSON line only")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed for rank 0's reads — the final regions of a fixed, "
+                         "seeded sample of reads and every read's region count — as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -221,6 +227,63 @@ def ert_report(st, mean, CHn, n_bases, ert_info, pmc=None):
 
 
 
+# --dump-outputs: the fields of the final regions the project pins to the oracle (tests/test_golden.py FINAL_F)
+DUMP_FIELDS = ("rb", "re", "qb", "qe", "rid", "chain", "score", "truesc", "sub", "csub", "w", "seedcov", "seedlen0", "n_comp_is_alt",
+               "frac_rep")
+DUMP_LIMIT = 64 << 20
+DUMP_SAMPLE_READS = 65536
+
+
+def dump_outputs(out_dir, batch, run_chunk, chunk_sizes, first):
+    """What the timed step hands its caller — bwams_dedup_fetch's final regions and per-read offsets — written as .npy files.
+    The last chunk's regions are still in the batch; the earlier chunks are run again (the path is deterministic) and the last
+    one last, so the batch is left as the timed steps left it.  Regions are kept for a fixed, seeded sample of reads, trimmed in
+    read order to stay within DUMP_LIMIT; every read's region count is kept as well when that fits in a quarter of it."""
+    R = int(sum(chunk_sizes))
+    bounds = np.r_[0, np.cumsum(chunk_sizes)].astype(np.int64)
+    pick = np.sort(np.random.default_rng(0).choice(R, min(R, DUMP_SAMPLE_READS), replace=False))
+    counts = np.empty(R, np.int64)
+    rows = []
+    n_chunks = len(chunk_sizes)
+    for c in [n_chunks - 1] + list(range(n_chunks - 1)):
+        if c != n_chunks - 1:
+            run_chunk(c)
+            batch.sync()
+        regs, off = batch.dedup_fetch()
+        counts[bounds[c]:bounds[c + 1]] = np.diff(off)
+        loc = pick[(pick >= bounds[c]) & (pick < bounds[c + 1])] - bounds[c]
+        lens = off[loc + 1] - off[loc]
+        idx = np.repeat(off[loc], lens) + np.arange(lens.sum()) - np.repeat(np.cumsum(lens) - lens, lens)
+        rows.append((c, regs[idx]))
+    if n_chunks > 1:
+        run_chunk(n_chunks - 1)
+        batch.sync()
+    regs = np.concatenate([r for _, r in sorted(rows, key=lambda t: t[0])])
+    lens = counts[pick]
+    per_region = sum(np.dtype(np.float32 if f == "frac_rep" else np.float64).itemsize for f in DUMP_FIELDS)
+    hdr = 128 * (len(DUMP_FIELDS) + 3)                          # an .npy header per file
+    all_counts = 4 * R <= DUMP_LIMIT // 4
+    budget = DUMP_LIMIT - hdr - (4 * R if all_counts else 0)
+    k = int(np.searchsorted(np.cumsum(8 + 4 + per_region * lens), budget, side="right"))
+    pick, lens = pick[:k], lens[:k]
+    regs = regs[:int(lens.sum())]
+    out = {"read_index": (first + pick).astype(np.float64), "read_regions": lens.astype(np.float32)}
+    if all_counts:
+        out["regions_per_read"] = counts.astype(np.float32)
+    for f in DUMP_FIELDS:
+        out["region_" + f] = regs[f].astype(np.float32 if f == "frac_rep" else np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in out.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"[bench] --dump-outputs wrote {total} bytes, more than {DUMP_LIMIT}")
+    return {"dir": out_dir, "files": len(out), "bytes": total, "reads": R, "sampled_reads": k, "sampled_regions": len(regs),
+            "regions": int(counts.sum())}
+
+
 def fastq_rows(rd, first):
     """One four-line FASTQ record per row: '@r%08d' names, the bases of `rd`, '+', a constant quality string."""
     n, RL = rd.shape
@@ -249,9 +312,6 @@ def main():
     if args.dry_run:
         return dry_run(args, rank, world)
 
-    # the library forks its size classes onto auxiliary streams; HIP's default of four hardware queues makes some of them
-    # share a queue and run one after the other (chaining 44 -> 40 ms with eight)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
 
@@ -377,6 +437,10 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, batch, run_chunk, chunk_sizes, first)
+        log(f"outputs of the last timed step: {dumped['files']} files, {dumped['bytes'] / 2**20:.1f} MiB in {args.dump_outputs}")
 
     # ---------------- the same steps with seeding over the ERT (reported beside, never `value`; N = 1 only) ----------------
     ert_side = None
@@ -1009,6 +1073,8 @@ def main():
                           "algorithmic_bytes": int(emf_bytes),
                           "achieved_GBps": round(emf_bytes / (emf_ms * 1e-3) / 1e9, 1) if emf_ms > 0 else None}
         out["sam_side"] = sam_side
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if pe_out is not None:
             out["paired_end"] = pe_out
         if args.pcie:

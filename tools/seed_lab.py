@@ -30,7 +30,6 @@ def main():
     ap.add_argument("--step", action="store_true", help="run the whole step (seed .. dedup), not just seeding")
     ap.add_argument("variants", nargs="*")
     args = ap.parse_args()
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
 
     from bwams import capi, simulate

@@ -14,7 +14,6 @@ ap.add_argument("--extra-batch", action="store_true", help="an idle batch beside
 ap.add_argument("--depths", default="1,2,3")
 ap.add_argument("--leave-free-gib", type=float, default=0.0, help="hog HBM so that only this much is free when the worker is made (memory-exhaustion rehearsal)")
 args = ap.parse_args()
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from bwams import capi, simulate, stream
 torch.cuda.set_device(0)
