@@ -33,7 +33,6 @@ void knobs_reload() {
     k.bwd_late_list = env_int("BWAMS_BWD_LATE_LIST", k.bwd_late_list);
     k.bwd_dry_min_list = env_int("BWAMS_BWD_DRY_MIN_LIST", k.bwd_dry_min_list); k.bwd_dry_cols = env_int("BWAMS_BWD_DRY_COLS", k.bwd_dry_cols);
     k.bwd_dry_late_list = env_int("BWAMS_BWD_DRY_LATE_LIST", k.bwd_dry_late_list);
-    k.bwd_fused = env_int("BWAMS_BWD_FUSED", 1); k.bwd_cap_mul = std::max(1, env_int("BWAMS_BWD_CAP_MUL", 1));
     k.r3_beside = env_int("BWAMS_SEED_R3_BESIDE", 1);
     k.ext_max_rounds = env_int("BWAMS_EXT_MAX_ROUNDS", 0); k.ext_all_rounds = getenv("BWAMS_EXT_ALL_ROUNDS") != nullptr;
     k.ext_inplace = env_int("BWAMS_EXT_INPLACE", 1);
@@ -42,9 +41,6 @@ void knobs_reload() {
     k.trace_pair = env_int("BWAMS_TRACE_PAIR", 0);
     k.bsw_pk = env_int("BWAMS_BSW_PK", 1);
     k.chain_batch = env_int("BWAMS_CHAIN_BATCH", 1);
-    k.cp2 = env_int("BWAMS_CP2", 2);
-    k.seed_split = env_int("BWAMS_SEED_SPLIT", 0);
-    k.fwd_bpc = std::max(1, env_int("BWAMS_FWD_BPC", 8)); k.bwdl_bpc = std::max(1, env_int("BWAMS_BWDL_BPC", 6));
     k.ert_ticket = env_int("BWAMS_ERT_TICKET", 1); k.ert_grid = env_int("BWAMS_ERT_GRID", -1); k.ert_fat = env_int("BWAMS_ERT_FAT", 1);
     g_knobs = k;
 }
@@ -131,7 +127,6 @@ int bwams_device_count(int *n) {
 static int index_finish(bwams_index *ix, const bwams_fmi_desc_t *d) {
     ix->fmi.cp = reinterpret_cast<const uint4 *>(ix->d_cp);
     ix->fmi.cp2 = nullptr;
-    ix->fmi.tab_kind = 0;
     ix->fmi.sa_ms = reinterpret_cast<const int8_t *>(ix->d_ms);
     ix->fmi.sa_ls = reinterpret_cast<const uint32_t *>(ix->d_ls);
     ix->fmi.ref = reinterpret_cast<const uint8_t *>(ix->d_ref);
@@ -475,7 +470,7 @@ int bwams_index_fetch_fma(bwams_index_t *ix, void *all_smem, void *last_smem) {
 
 // (re)allocate every buffer whose size follows max_smem; the batch grows them when a chunk needs more
 static int alloc_smem_buffers(bwams_batch *b, int64_t max_smem) {
-    void **ptrs[] = {(void **)&b->d_pool, (void **)&b->d_pool3, (void **)&b->d_sorted, (void **)&b->d_keys, (void **)&b->d_keys2, (void **)&b->d_vals,
+    void **ptrs[] = {(void **)&b->d_pool, (void **)&b->d_sorted, (void **)&b->d_keys, (void **)&b->d_keys2, (void **)&b->d_vals,
                      (void **)&b->d_vals2, (void **)&b->d_work2, (void **)&b->d_sa_off, (void **)&b->d_sa_cnt};
     for (void **p : ptrs)
         if (*p) { (void)hipFree(*p); *p = nullptr; }
@@ -484,10 +479,6 @@ static int alloc_smem_buffers(bwams_batch *b, int64_t max_smem) {
     // of each of the five emitting launches on top of the max_smem real records
     b->pool_cap = b->max_smem + seed_pool_slack(b->cu_count);
     BWAMS_HIP(dev_malloc(&b->d_pool, (size_t)b->pool_cap * sizeof(bwams_smem_t)));
-    // round 3's own pool (it runs from the start of the stage): it may hold most of a chunk's records (a clean unique read has one
-    // SMEM and half a dozen round-3 seeds), so it is as large as the main one's record part + one launch's chunk tails
-    b->pool3_cap = b->max_smem + seed_pool_slack(b->cu_count) / 5;
-    if (knobs().r3_beside == 2) BWAMS_HIP(dev_malloc(&b->d_pool3, (size_t)b->pool3_cap * sizeof(bwams_smem_t)));      // the experiment's buffer: only on demand
     BWAMS_HIP(dev_malloc(&b->d_sorted, (size_t)b->max_smem * sizeof(bwams_smem_t)));
     BWAMS_HIP(dev_malloc(&b->d_keys, (size_t)b->pool_cap * 8));
     BWAMS_HIP(dev_malloc(&b->d_keys2, (size_t)b->pool_cap * 8));
@@ -523,7 +514,6 @@ static int batch_create_fill(bwams_batch *b, bwams_index_t *ix, int64_t max_read
     if (int arc = alloc_smem_buffers(b, b->max_smem)) return arc;
     BWAMS_HIP(dev_malloc(&b->d_sa_coord, (size_t)b->max_sa * 8));
     BWAMS_HIP(dev_malloc(&b->d_ctr, sizeof(DevCounters)));
-    BWAMS_HIP(dev_malloc(&b->d_ctr3, sizeof(DevCounters)));
     BWAMS_HIP(hipHostMalloc(&b->h_ctr, sizeof(DevCounters)));
     BWAMS_HIP(hipMemset(b->d_ctr, 0, sizeof(DevCounters)));
 
@@ -558,7 +548,7 @@ int bwams_batch_destroy(bwams_batch_t *b) {
     (void)hipSetDevice(b->idx->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     void *ptrs[] = {b->d_enc, b->d_cum, b->d_skip, b->d_pool, b->d_sorted, b->d_keys, b->d_keys2, b->d_vals,
-                    b->d_vals2, b->d_work2, b->d_sa_off, b->d_sa_cnt, b->d_sa_coord, b->d_tmp, b->d_ctr, b->d_ctr3, b->d_pool3, b->d_prev, b->d_packed, b->d_emf_out, b->d_emf_code, b->d_ksw_out, b->d_bsw_list, b->d_pairs, b->d_ref, b->d_qer, b->d_ert_prof, b->d_ert_stk, b->d_ert_redo, b->d_bwd_items, b->d_bwd_ent, b->d_f_items, b->d_fl_ent};
+                    b->d_vals2, b->d_work2, b->d_sa_off, b->d_sa_cnt, b->d_sa_coord, b->d_tmp, b->d_ctr, b->d_prev, b->d_packed, b->d_emf_out, b->d_emf_code, b->d_ksw_out, b->d_bsw_list, b->d_pairs, b->d_ref, b->d_qer, b->d_ert_prof, b->d_ert_stk, b->d_ert_redo, b->d_bwd_items, b->d_bwd_ent};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (b->h_ctr) (void)hipHostFree(b->h_ctr);
@@ -648,27 +638,7 @@ int bwams_seed_upload(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, 
     // what uniform and repeat-rich genomes produce several times over; when they are full a pivot simply stays on its lane
     // (two item arrays of bi slots in one allocation: long lists, short lists; once a launch drains every backward phase leaves its
     // lane, about half a pivot per read in flight, profiles/r04_notes.md)
-    const int64_t cap_mul = knobs().bwd_cap_mul;                // lab: room for EVERY backward phase
-    const int64_t bi = std::max<int64_t>(nseq, 4096) * 2 * cap_mul, be = std::max<int64_t>(nseq, 4096) * 24 * cap_mul;
-    if (knobs().seed_split) {
-        // lists: round 1 needs 2 (bases + reads) entries, round 2 (max_len + 2) per work item — room for two items per read; items: six per read
-        const int64_t fl = std::max<int64_t>(2 * (nb + nseq) + 64, 2 * std::max<int64_t>(nseq, 4096) * (int64_t)(mx + 2));
-        const int64_t fi = 6 * std::max<int64_t>(nseq, 4096) + 4096;
-        const int dbl = knobs().seed_split == 2 ? 2 : 1;       // lab: two halves (the forward kernel writes one while the backward kernel reads the other)
-        if (dbl > b->split_dbl) { b->fl_cap = 0; b->f_items_cap = 0; b->split_dbl = dbl; }      // (the lab's doubled buffers: allocate again)
-        if (fl > b->fl_cap) {
-            if (b->d_fl_ent) (void)hipFree(b->d_fl_ent);
-            b->d_fl_ent = nullptr; b->fl_cap = 0;
-            BWAMS_HIP(dev_malloc(&b->d_fl_ent, (size_t)fl * 16 * dbl));
-            b->fl_cap = fl;
-        }
-        if (fi > b->f_items_cap) {
-            if (b->d_f_items) (void)hipFree(b->d_f_items);
-            b->d_f_items = nullptr; b->f_items_cap = 0;
-            BWAMS_HIP(dev_malloc(&b->d_f_items, (size_t)fi * sizeof(BwdItem) * dbl));
-            b->f_items_cap = fi;
-        }
-    }
+    const int64_t bi = std::max<int64_t>(nseq, 4096) * 2, be = std::max<int64_t>(nseq, 4096) * 24;
     if (bi > b->bwd_items_cap) {
         if (b->d_bwd_items) (void)hipFree(b->d_bwd_items);
         if (b->d_bwd_ent) (void)hipFree(b->d_bwd_ent);
@@ -710,16 +680,28 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     b->with_sa = with_sa != 0;
     b->n_smem = b->n_sa = 0;
 
-    if (knobs().cp2 && b->idx->cp2_kind != knobs().cp2 && b->idx->d_cp && b->idx->n_blk > 0) {     // the search kernels' own table, once per index
-        if (b->idx->d_cp2) { BWAMS_HIP(hipStreamSynchronize(st)); (void)hipFree(b->idx->d_cp2); b->idx->d_cp2 = nullptr; }
-        BWAMS_HIP(dev_malloc(&b->idx->d_cp2, cp2_bytes(b->idx->n_blk, knobs().cp2)));
-        launch_cp2_build(reinterpret_cast<const uint4 *>(b->idx->d_cp), b->idx->n_blk, reinterpret_cast<uint4 *>(b->idx->d_cp2), knobs().cp2, st);
-        b->idx->cp2_kind = knobs().cp2;
+    // the search kernels' table, built once per index at its first FM-index seeding (ERT-only jobs never pay for it).  Batches of other
+    // threads may seed the same index: it is published only after its build has finished, and nothing frees it before bwams_index_close.
+    const uint4 *cp2 = nullptr;
+    {
+        bwams_index *ix = b->idx;
+        std::lock_guard<std::mutex> lock(ix->cp2_mu);
+        if (!ix->d_cp2) {
+            void *t = nullptr;
+            hipError_t e = dev_malloc(&t, cp2_bytes(ix->n_blk));
+            if (e == hipSuccess) {
+                launch_cp2_build(reinterpret_cast<const uint4 *>(ix->d_cp), ix->n_blk, reinterpret_cast<uint4 *>(t), st);
+                e = hipStreamSynchronize(st);
+                if (e != hipSuccess) (void)hipFree(t);
+            }
+            BWAMS_HIP(e);
+            ix->d_cp2 = t;
+        }
+        cp2 = reinterpret_cast<const uint4 *>(ix->d_cp2);
     }
     SeedLaunch a;
     a.fmi = b->idx->fmi;
-    a.fmi.cp2 = knobs().cp2 ? reinterpret_cast<const uint4 *>(b->idx->d_cp2) : nullptr;
-    a.fmi.tab_kind = knobs().cp2 ? b->idx->cp2_kind : 0;
+    a.fmi.cp2 = cp2;
     a.enc = b->d_enc;
     a.cum = b->d_cum;
     a.skip = b->has_skip ? b->d_skip : nullptr;
@@ -736,16 +718,6 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     a.prev = b->d_prev;
     a.prev_cap = b->prev_cap;
     a.prev_threads = b->prev_threads;
-    const bool split = knobs().seed_split && !b->seed_split_failed && b->d_fl_ent && b->d_f_items;
-    const bool lab_overlap = split && knobs().seed_split == 2;
-    if (lab_overlap) b->split_parity ^= 1;
-    const int par = lab_overlap ? b->split_parity : 0;
-    a.f_items = b->d_f_items + (int64_t)par * b->f_items_cap;
-    a.f_items_cap = b->f_items_cap;
-    a.f_items_fixed = -1;
-    a.fl_ent = b->d_fl_ent + (int64_t)par * b->fl_cap;
-    a.fl_cap = b->fl_cap;
-    a.fl_item_stride = b->max_read_len + 2;
     a.bwd_items = b->d_bwd_items;
     a.bwd_items_s = b->d_bwd_items + b->bwd_items_cap;
     a.bwd_ent = b->d_bwd_ent;
@@ -769,43 +741,8 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     BWAMS_HIP(hipEventRecord(b->ev[0], st));
     launch_pack_reads(b->d_enc, b->d_cum, b->nseq, b->read_w, b->read_cw, b->d_packed, st);
     launch_mark(b->d_ctr, 0, st);
-    // Round 3 reads nothing of rounds 1 and 2 (bwtSeedStrategyAllPosOneThread walks every read from position 0).  BWAMS_SEED_R3_BESIDE=2
-    // (an experiment, kept behind the switch and under the parity test): it is launched HERE, on the stream of its own, with a pool and
-    // counters of its own (round 2's work list is cut from the main pool's prefix); behind round 2 its records are appended to the main
-    // pool and its counts folded in (append_r3_kernel + mark 3).  The hope was that its workgroups would only find room where round 1
-    // drains; they are placed beside round 1's throughout: round 1 16.1 -> 18.3 ms, round 2 12.5 -> 10.7, the stage 35.3 -> 35.8 ms.
-    const int r3_mode = (b->nseq > 0 && opt->max_mem_intv > 0 && !split && !lab_overlap) ? knobs().r3_beside : 0;
-    SeedLaunch a3 = a;
-    a3.min_seed_len = opt->min_seed_len + 1;
-    if (r3_mode == 2) {
-        if (!b->d_pool3) BWAMS_HIP(dev_malloc(&b->d_pool3, (size_t)b->pool3_cap * sizeof(bwams_smem_t)));
-        a3.pool = b->d_pool3; a3.pool_cap = b->pool3_cap; a3.ctr = b->d_ctr3;
-        BWAMS_HIP(hipMemsetAsync(b->d_ctr3, 0, sizeof(DevCounters), st));
-        BWAMS_HIP(hipEventRecord(b->seed_fork, st));
-        BWAMS_HIP(hipStreamWaitEvent(b->seed_aux, b->seed_fork, 0));
-        BWAMS_HIP(hipEventRecord(b->ev[12], b->seed_aux));
-        launch_smem_round3(a3, opt->max_mem_intv, b->cu_count, b->seed_aux);
-        BWAMS_HIP(hipEventRecord(b->ev[13], b->seed_aux));
-        BWAMS_HIP(hipEventRecord(b->seed_join, b->seed_aux));
-    }
     BWAMS_HIP(hipEventRecord(b->ev[8], st));
-    if (b->nseq > 0) {
-        if (lab_overlap && b->f_items_prev[par ^ 1][0] >= 0) {
-            // LAB ONLY: the backward kernel over the items the PREVIOUS run left in the other half (the same reads: the same SMEMs), beside
-            // this run's forward kernel — what a perfect overlap of the two would take
-            SeedLaunch ab = a;
-            ab.f_items = b->d_f_items + (int64_t)(par ^ 1) * b->f_items_cap;
-            ab.fl_ent = b->d_fl_ent + (int64_t)(par ^ 1) * b->fl_cap;
-            ab.f_items_fixed = b->f_items_prev[par ^ 1][0];
-            BWAMS_HIP(hipEventRecord(b->seed_fork, st));
-            BWAMS_HIP(hipStreamWaitEvent(b->seed_aux, b->seed_fork, 0));
-            launch_smem_fwd(a, nullptr, b->cu_count, st);
-            launch_smem_bwdl(ab, b->cu_count, b->seed_aux);
-            BWAMS_HIP(hipEventRecord(b->seed_join, b->seed_aux));
-            BWAMS_HIP(hipStreamWaitEvent(st, b->seed_join, 0));
-        } else if (split) { launch_smem_fwd(a, nullptr, b->cu_count, st); launch_smem_bwdl(a, b->cu_count, st); }
-        else launch_smem_round1(a, b->cu_count, st);
-    }
+    if (b->nseq > 0) launch_smem_round1(a, b->cu_count, st);
 #ifdef BWAMS_BWDDBG
     static hipEvent_t dbg_ev = nullptr;
     if (!dbg_ev) BWAMS_HIP(hipEventCreate(&dbg_ev));
@@ -818,28 +755,25 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     // Round 3 reads nothing of rounds 1 and 2 (bwtSeedStrategyAllPosOneThread walks every read from position 0): it runs beside
     // round 2 on a stream of its own and fills the tail in which round 2's slowest reads keep few lanes busy.  Its extensions and
     // SMEMs are counted apart (n_ext3 / n_blk3 / n_smem3), so that the per-round figures stay exact.
-    const bool r3_beside = knobs().r3_beside != 0 && r3_mode != 2;
-    const bool r3 = b->nseq > 0 && opt->max_mem_intv > 0 && r3_mode != 2;
-    hipStream_t st3 = r3_beside ? b->seed_aux : st;
-    if (r3 && r3_beside) {
+    SeedLaunch a3 = a;
+    a3.min_seed_len = opt->min_seed_len + 1;
+    const bool r3 = b->nseq > 0 && opt->max_mem_intv > 0;
+    const bool r3_beside = r3 && knobs().r3_beside != 0;
+    if (r3_beside) {
         BWAMS_HIP(hipEventRecord(b->seed_fork, st));
-        BWAMS_HIP(hipStreamWaitEvent(st3, b->seed_fork, 0));
-        BWAMS_HIP(hipEventRecord(b->ev[12], st3));
-        launch_smem_round3(a3, opt->max_mem_intv, b->cu_count, st3);
-        BWAMS_HIP(hipEventRecord(b->ev[13], st3));
-        BWAMS_HIP(hipEventRecord(b->seed_join, st3));
+        BWAMS_HIP(hipStreamWaitEvent(b->seed_aux, b->seed_fork, 0));
+        BWAMS_HIP(hipEventRecord(b->ev[12], b->seed_aux));
+        launch_smem_round3(a3, opt->max_mem_intv, b->cu_count, b->seed_aux);
+        BWAMS_HIP(hipEventRecord(b->ev[13], b->seed_aux));
+        BWAMS_HIP(hipEventRecord(b->seed_join, b->seed_aux));
     }
     BWAMS_HIP(hipEventRecord(b->ev[10], st));
-    if (b->nseq > 0) {
-        if (split && !lab_overlap) { launch_smem_fwd(a, b->d_work2, b->cu_count, st); launch_smem_bwdl(a, b->cu_count, st); }
-        else launch_smem_round2(a, b->d_work2, b->cu_count, st);       // (the lab's overlap run keeps round 1's items intact for the next run)
-    }
+    if (b->nseq > 0) launch_smem_round2(a, b->d_work2, b->cu_count, st);
     if (b->nseq > 0) launch_smem_bwd_wave(a, b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[11], st));
-    if ((r3 && r3_beside) || r3_mode == 2) BWAMS_HIP(hipStreamWaitEvent(st, b->seed_join, 0));
+    if (r3_beside) BWAMS_HIP(hipStreamWaitEvent(st, b->seed_join, 0));
     launch_mark(b->d_ctr, 2, st);
-    if (r3_mode == 2) launch_append_r3(b->d_pool, b->pool_cap, b->d_pool3, b->pool3_cap, b->d_ctr, b->d_ctr3, st);
-    if (!(r3 && r3_beside) && r3_mode != 2) {
+    if (!r3_beside) {
         BWAMS_HIP(hipEventRecord(b->ev[12], st));
         if (r3) launch_smem_round3(a3, opt->max_mem_intv, b->cu_count, st);
         BWAMS_HIP(hipEventRecord(b->ev[13], st));
@@ -871,13 +805,6 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
         fprintf(stderr, "\n[smem_r1] wave-iterations after the wave first saw the queue dry: %llu, with one lane extending %llu (max per wave %llu), with 2-4 lanes %llu\n", d[64], d[65], d[67], d[66]);
     }
 #endif
-    if (lab_overlap) { b->f_items_prev[par][0] = (int64_t)b->h_ctr->f_items_r[0]; b->f_items_prev[par][1] = (int64_t)b->h_ctr->f_items_r[1]; }
-    if (knobs().verbose && split) fprintf(stderr, "[bwams_seed_run] split search: items r1 %llu r2 %llu, overflow %llu%s\n", b->h_ctr->f_items_r[0], b->h_ctr->f_items_r[1],
-                                          b->h_ctr->f_overflow, lab_overlap ? " (lab: backward kernel beside the forward kernel)" : "");
-    if (split && b->h_ctr->f_overflow) {         // pivots that found no room between the two kernels: this batch searches unsplit from now on
-        b->seed_split_failed = true;
-        return seed_run_once(b, opt, with_sa);
-    }
     const int64_t n_slots = (int64_t)b->h_ctr->n_smem_total;      // pool slots handed out (holes included)
     const int64_t n = (int64_t)b->h_ctr->n_smem_valid;           // real SMEMs
     b->n_smem = n;

@@ -3,6 +3,7 @@
 
 #include <cstdlib>
 #include <hip/hip_runtime.h>
+#include <mutex>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -25,10 +26,7 @@ struct Knobs {
     int poison = 0;                // BWAMS_POISON: fresh device allocations are filled with 0xAB
     int bwd_min_list = 40, bwd_cols = 24, bwd_late_list = 8;                     // BWAMS_BWD_MIN_LIST / _COLS / _LATE_LIST   (fmi_seed.hip: bwd_hand_over)
     int bwd_dry_min_list = 24, bwd_dry_cols = 8, bwd_dry_late_list = 12;         // BWAMS_BWD_DRY_*: the same once the work queue is dry
-    int bwd_fused = 1;             // BWAMS_BWD_FUSED=0: the two roles behind a search kernel as two launches
-    int bwd_cap_mul = 1;           // BWAMS_BWD_CAP_MUL: hand-over buffers x this (experiments that hand every backward phase over)
-    int r3_beside = 1;             // BWAMS_SEED_R3_BESIDE: 1 (default) = SMEM round 3 beside round 2; 0 = behind it; 2 = from the START of the stage into a
-                                   // pool of its own (measured: its workgroups do get placed beside round 1's — round 1 16.1 -> 18.3 ms, stage 35.3 -> 35.8)
+    int r3_beside = 1;             // BWAMS_SEED_R3_BESIDE: 1 (default) = SMEM round 3 beside round 2 on a stream of its own; 0 = behind it
     int ext_max_rounds = 0;        // BWAMS_EXT_MAX_ROUNDS: cap of the extension rounds (tests force the extend-the-rest fallback)
     int ext_all_rounds = 0;        // BWAMS_EXT_ALL_ROUNDS: never cut the rounds short
     int ext_inplace = 1;           // BWAMS_EXT_INPLACE=0: extension tasks copied into flat buffers
@@ -37,11 +35,6 @@ struct Knobs {
     int trace_pair = 0;            // BWAMS_TRACE_PAIR: a synchronisation and a line per launch of the paired-end tail
     int bsw_pk = 1;                // BWAMS_BSW_PK=0: the 32-bit eight-task banded-SW kernel
     int chain_batch = 1;           // BWAMS_CHAIN_BATCH=0: chaining's wave tier takes one seed at a time (chain.hip: chain_seeds_batch)
-    int fwd_bpc = 8, bwdl_bpc = 6; // BWAMS_FWD_BPC / BWAMS_BWDL_BPC: workgroups per CU of the forward / backward lane kernels (lab)
-    int seed_split = 0;            // BWAMS_SEED_SPLIT=1: SMEM rounds 1 and 2 as a forward kernel + a backward kernel (fmi_seed.hip)
-    int cp2 = 2;                   // BWAMS_CP2: the table the SMEM search kernels read — 2 (default): the INTERLEAVED form of CP_OCC (piece b = count and
-                                   // string of base b: an extension reads half a block per end, fetched by a pair of lanes); 1: the compact 128-rows-per-block
-                                   // form (measured: no gain); 0: CP_OCC itself
     int ert_fat = 1;               // BWAMS_ERT_FAT=0: the ERT walk reads the reference's two tables only (no entry + tree-head table)
     int ert_grid = -1, ert_ticket = 1;   // BWAMS_ERT_GRID (blocks per CU, 0 = one block per 256 bases) / BWAMS_ERT_TICKET=0 (round robin)
 };
@@ -75,8 +68,7 @@ template <class T> static inline hipError_t dev_malloc(T **p, size_t bytes) {
 // 16-byte pieces  [cnt0 cnt1] [cnt2 cnt3] [hot0 hot1] [hot2 hot3].
 struct DevFmi {
     const uint4 *cp;
-    const uint4 *cp2;          // the search kernels' resident form of cp (fmi_seed.hip; BWAMS_CP2), or nullptr
-    int32_t tab_kind;          // ... 1: compact, 128 rows per block; 2: interleaved, piece b = count and string of base b
+    const uint4 *cp2;          // the search kernels' interleaved form of cp (fmi_seed.hip: piece b = count and string of base b), built at the first seeding
     const int8_t *sa_ms;
     const uint32_t *sa_ls;
     const uint8_t *ref;        // .0123 or nullptr
@@ -146,7 +138,6 @@ struct DevCounters {
     unsigned long long n_rest;           // extension: slots behind the requests of the last selection (an upper bound of the undecided seeds)
     unsigned long long ert_ticket;       // ERT walk: work cursor of ert_profile_kernel (groups of 64 read positions)
     unsigned long long bwd_items, bwd_entries, bwd_ticket;   // SMEM search: backward phases handed to the wave kernel, their list entries, its work cursor
-    unsigned long long f_items, f_ticket, f_overflow, f_items_r[2];        // SMEM search split by role: item slots handed out, the backward kernel's cursor, pivots without room (the caller re-runs unsplit)
     unsigned long long bwd_items_s, bwd_ticket_s;            // ... the short lists (smem_bwd_group_kernel): slots handed out, work cursor
     unsigned long long pair_full, pair_fail;   // mate rescue: reads redone with every orientation planned; reads the second pass could not finish (never expected)
 };
@@ -205,8 +196,8 @@ struct bwams_index {
     int64_t bytes = 0;
     int64_t n_blk = 0, n_sa = 0;
     void *d_cp = nullptr, *d_ms = nullptr, *d_ls = nullptr, *d_ref = nullptr;
-    int cp2_kind = 0;
-    void *d_cp2 = nullptr;                       // compact search table derived from d_cp on first use (BWAMS_CP2=1; always owned)
+    void *d_cp2 = nullptr;                       // the search kernels' table derived from d_cp at the first FM-index seeding (always owned);
+    std::mutex cp2_mu;                           // ... published under this lock once built, freed only by bwams_index_close
     void *d_all = nullptr, *d_last = nullptr;    // FMA tables (owned)
     void *d_contigs = nullptr;                   // bwams_contig_t[n_seqs] (owned); null = one sequence [0, l_pac)
     int32_t n_seqs = 0;
@@ -262,9 +253,6 @@ struct bwams_batch {
 
     // seeding buffers
     bwams_smem_t *d_pool = nullptr;      // unsorted SMEM pool (append order)
-    bwams_smem_t *d_pool3 = nullptr;     // round 3's own pool while it runs from the start of the stage (appended to d_pool behind round 2)
-    int64_t pool3_cap = 0;
-    bwams::DevCounters *d_ctr3 = nullptr;   // ... and its own counters
     bwams_smem_t *d_sorted = nullptr;    // (rid, m, n) order
     uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
     uint32_t *d_vals = nullptr, *d_vals2 = nullptr;
@@ -278,12 +266,6 @@ struct bwams_batch {
     bwams::DevCounters *h_ctr = nullptr;  // pinned host mirror
     // per-lane scratch of the SMEM search (previous-interval lists)
     uint4 *d_prev = nullptr;
-    bwams::BwdItem *d_f_items = nullptr;        // SMEM search split by role: pivots between the forward and the backward kernel ...
-    uint4 *d_fl_ent = nullptr;                  // ... and their interval lists
-    int64_t f_items_cap = 0, fl_cap = 0;
-    int split_parity = 0, split_dbl = 1;                       // lab (BWAMS_SEED_SPLIT=2): which half of the doubled buffers the forward kernel writes
-    int64_t f_items_prev[2][2] = {{-1, -1}, {-1, -1}};   // ... items per round the previous runs left in each half
-    bool seed_split_failed = false;             // a chunk whose pivots did not fit: this batch searches with the one-kernel form from then on
     bwams::BwdItem *d_bwd_items = nullptr;      // SMEM search: backward phases with long interval lists (wave-per-pivot kernel)
     uint4 *d_bwd_ent = nullptr;
     int64_t bwd_items_cap = 0, bwd_ent_cap = 0;

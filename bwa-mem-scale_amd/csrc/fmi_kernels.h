@@ -22,13 +22,6 @@ struct SeedLaunch {
     int prev_cap;                 // entries per lane
     int64_t prev_threads;         // lanes the scratch was sized for
     // backward phases whose interval list has at least bwd_min_list entries go to smem_bwd_wave_kernel (0 = never)
-    // rounds 1 and 2 as a forward kernel and a backward kernel (smem_fwd_kernel / smem_bwdl_kernel): the pivots between them and their lists
-    BwdItem *f_items;             // f_items_cap slots, reserved 64 at a time per wave (num_prev = 0: unused)
-    int64_t f_items_cap;
-    int64_t f_items_fixed;        // >= 0: the backward kernel takes this many items instead of the counter (lab: overlap experiment)
-    uint4 *fl_ent;                // the lists: fl_cap 16-byte entries
-    int64_t fl_cap;
-    int32_t fl_item_stride;       // round 2: entries per work item (max read length + 2)
     BwdItem *bwd_items, *bwd_items_s;   // lists beyond / up to kBwdShortMax entries; bwd_items_cap slots each
     uint4 *bwd_ent;
     int64_t bwd_items_cap, bwd_ent_cap;
@@ -40,8 +33,6 @@ struct SeedLaunch {
 // grid sizing shared by batch_create (scratch) and the launches
 int seed_block_threads();
 int64_t seed_max_threads(int cu_count);
-// round 3's records (a pool and counters of its own while it ran from the start of the stage) behind the main pool's, its counts into n_smem3 / n_ext3 / n_blk3
-void launch_append_r3(bwams_smem_t *pool, int64_t pool_cap, const bwams_smem_t *pool3, int64_t pool3_cap, DevCounters *ctr, const DevCounters *ctr3, hipStream_t st);
 int64_t seed_pool_slack(int cu_count);   // pool slots the launches of one seeding pass can leave unused in partly filled chunks
 
 // enc_qdb bytes -> 2-bit codes + N mask, W words per read
@@ -55,9 +46,6 @@ void launch_smem_round1(const SeedLaunch &a, int cu_count, hipStream_t st);
 void launch_round2_work(const SeedLaunch &a, Round2Work *work, int64_t work_cap, int split_len,
                         int split_width, int cu_count, hipStream_t st);
 void launch_smem_round2(const SeedLaunch &a, const Round2Work *work, int cu_count, hipStream_t st);
-// rounds 1 / 2 split by role: forward phases of every read (work == nullptr) or work item, then the backward phase of every pivot
-void launch_smem_fwd(const SeedLaunch &a, const Round2Work *work, int cu_count, hipStream_t st);
-void launch_smem_bwdl(const SeedLaunch &a, int cu_count, hipStream_t st);
 // the backward phases rounds 1 / 2 set aside (lists of bwd_min_list entries and more): one wavefront per pivot, one lane per entry
 void launch_smem_bwd_wave(const SeedLaunch &a, int cu_count, hipStream_t st);
 // round 3: forward-only seeds (bwtSeedStrategyAllPosOneThread)
@@ -75,8 +63,8 @@ void launch_sa_lookup(const DevFmi &f, const bwams_smem_t *sorted, int64_t n_sme
                       int64_t *coord, int64_t coord_cap, int max_occ, DevCounters *ctr, int cu_count,
                       hipStream_t st);
 
-// the search kernels' compact Occ table (CpOcc2, BWAMS_CP2=1): (n_blk + 1) / 2 blocks of 64 B
-size_t cp2_bytes(int64_t n_blk, int kind);          // kind 1: compact (128 rows per block); 2: interleaved (piece b = count and string of base b)
-void launch_cp2_build(const uint4 *cp, int64_t n_blk, uint4 *cp2, int kind, hipStream_t st);
+// the search kernels' table: the interleaved form of CP_OCC (piece b of a block = count and string of base b), n_blk blocks of 64 B
+size_t cp2_bytes(int64_t n_blk);
+void launch_cp2_build(const uint4 *cp, int64_t n_blk, uint4 *cp2, hipStream_t st);
 
 }  // namespace bwams

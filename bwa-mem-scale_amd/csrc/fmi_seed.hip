@@ -35,48 +35,13 @@ struct Occ4 {
     int64_t v[4];
 };
 
-// ---- quad-cooperative block fetch --------------------------------------------------
-// A lane that reads its own 64-byte block with four 16-byte loads costs four L2 requests
-// per block; the memory system then tops out at ~28 G blocks/s (tools/ubench_gather, mode 0).
-// Instead the four lanes of a quad fetch four blocks together: in load j every lane of the
-// quad reads the 16-byte piece (lane & 3) of quad member j's block, so one wave instruction
-// is 16 fully used 64-byte requests; a 4x4 register transpose inside the quad (DPP
-// quad_perm, no LDS) then hands every lane the whole block it asked for.  This shape
-// reaches the random-line ceiling of HBM (~50 G blocks/s, mode 1 of the same benchmark).
+// DPP quad_perm: a value from another lane of the quad, without LDS
 template <int CTRL>
 __device__ __forceinline__ uint32_t qdpp(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
 }
-template <int J>
-__device__ __forceinline__ int64_t quad_bcast64(int64_t v) {
-    const uint32_t lo = qdpp<J * 0x55>((uint32_t)v), hi = qdpp<J * 0x55>((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)mk64(lo, hi);
-}
 
-// In place 4x4 transpose across the quad: on entry lane q holds m[j] = element (q, j);
-// on exit lane q holds m[j] = element (j, q).
-__device__ __forceinline__ void quad_transpose(uint32_t &m0, uint32_t &m1, uint32_t &m2, uint32_t &m3, int q) {
-    const bool hi2 = (q & 2) != 0, hi1 = (q & 1) != 0;
-    // exchange 2x2 blocks with lane ^ 2
-    uint32_t t0 = hi2 ? m0 : m2, t1 = hi2 ? m1 : m3;
-    t0 = qdpp<0x4E>(t0);           // quad_perm [2,3,0,1]
-    t1 = qdpp<0x4E>(t1);
-    if (hi2) { m0 = t0; m1 = t1; } else { m2 = t0; m3 = t1; }
-    // exchange inside the 2x2 blocks with lane ^ 1
-    t0 = hi1 ? m0 : m1;
-    t1 = hi1 ? m2 : m3;
-    t0 = qdpp<0xB1>(t0);           // quad_perm [1,0,3,2]
-    t1 = qdpp<0xB1>(t1);
-    if (hi1) { m0 = t0; m2 = t1; } else { m1 = t0; m3 = t1; }
-}
-
-__device__ __forceinline__ void quad_transpose4(uint4 &a0, uint4 &a1, uint4 &a2, uint4 &a3, int q) {
-    quad_transpose(a0.x, a1.x, a2.x, a3.x, q);
-    quad_transpose(a0.y, a1.y, a2.y, a3.y, q);
-    quad_transpose(a0.z, a1.z, a2.z, a3.z, q);
-    quad_transpose(a0.w, a1.w, a2.w, a3.w, q);
-}
-
+// Occ of the four bases at row pos from a CP_OCC block (the FMA table builders' per-lane reads)
 __device__ __forceinline__ void occ_from_block(const uint4 &c01, const uint4 &c23, const uint4 &h01,
                                                const uint4 &h23, int64_t pos, Occ4 &o) {
     const int y = (int)(pos & 63);
@@ -87,47 +52,18 @@ __device__ __forceinline__ void occ_from_block(const uint4 &c01, const uint4 &c2
     o.v[3] = (int64_t)mk64(c23.z, c23.w) + __popcll(mk64(h23.z, h23.w) & mask);
 }
 
-// ---- the compact table (BWAMS_CP2=1: a resident layout for the search kernels; the files and every other kernel keep CP_OCC) -----
-// CpOcc2: the same information as two adjacent CP_OCC blocks in 64 bytes — the four counts at the start of a 128-base block and the
-// bases as two bit planes (bit 63 - j of word 0 = base j, of word 1 = base 64 + j; hi: G or T, lo: C or T):
-//     piece 0 = {count A, count C}, piece 1 = {count G, count T}, piece 2 = {hi word 0, hi word 1}, piece 3 = {lo word 0, lo word 1}.
-// k and k + s then share a block whenever s < 128 (one request instead of two), and the table is half as large.  The row of the sentinel
-// has no bit in any one-hot string; in the planes it reads as an A: Occ(A) is corrected in its block.  Algorithmic bytes stay the
-// reference layout's count: the kernels count blocks of 64 rows whatever table they read.
-__device__ __forceinline__ void occ_from_block2(const uint4 &c01, const uint4 &c23, const uint4 &hp, const uint4 &lp, int64_t pos,
-                                                int64_t sentinel, Occ4 &o) {
-    const int y = (int)(pos & 127);
-    const int y0 = y < 64 ? y : 64, y1 = y - y0;
-    const uint64_t m0 = y0 ? (~0ull << (64 - y0)) : 0ull, m1 = y1 ? (~0ull << (64 - y1)) : 0ull;
-    const uint64_t h0 = mk64(hp.x, hp.y) & m0, h1 = mk64(hp.z, hp.w) & m1;
-    const uint64_t l0 = mk64(lp.x, lp.y), l1 = mk64(lp.z, lp.w);
-    const int nt = __popcll(h0 & l0) + __popcll(h1 & l1);
-    const int ng = __popcll(h0 & ~l0) + __popcll(h1 & ~l1);
-    const int nc = __popcll(~mk64(hp.x, hp.y) & l0 & m0) + __popcll(~mk64(hp.z, hp.w) & l1 & m1);
-    int na = y - nt - ng - nc;
-    if ((pos >> 7) == (sentinel >> 7) && y > (int)(sentinel & 127)) --na;
-    o.v[0] = (int64_t)mk64(c01.x, c01.y) + na;
-    o.v[1] = (int64_t)mk64(c01.z, c01.w) + nc;
-    o.v[2] = (int64_t)mk64(c23.x, c23.y) + ng;
-    o.v[3] = (int64_t)mk64(c23.z, c23.w) + nt;
-}
-template <int TAB>
-__device__ __forceinline__ void occ_any(const DevFmi &f, const uint4 &p0, const uint4 &p1, const uint4 &p2, const uint4 &p3, int64_t pos, Occ4 &o) {
-    if (TAB == 1) occ_from_block2(p0, p1, p2, p3, pos, f.sentinel, o);
-    else occ_from_block(p0, p1, p2, p3, pos, o);
-}
-
-// ---- the interleaved table (TAB == 2; BWAMS_CP2=2, the default) ---------------------------------------------------------------------
+// ---- the interleaved table: what the search kernels read -----------------------------------------------------------------------------
 // The same 64 bytes per 64 rows as CP_OCC, the fields permuted: piece b (16 bytes) = {cp_count[b], one_hot_bwt_str[b]}, b = A, C, G, T.
 // backwardExt(a) needs Occ of base a at both ends (k' and s') and, for l', the sizes of the bases ABOVE a — or, because the four sizes add
 // up to s minus the sentinel, the bases up to a:
 //     l'[0] = l + s - s0        l'[1] = l + s - s0 - s1        l'[2] = l + [sentinel] + s3        l'[3] = l + [sentinel]
 // (FMI_search.cpp:2029-2056 with s0 + s1 + s2 + s3 = s - [sentinel in range]: exact integer identities).  So an extension by a reads only
 // the HALF of each block that holds a's pair of bases — {A, C} or {G, T}: 32 bytes — fetched by a PAIR of lanes (lane q of the pair
-// reads piece q of both members' halves; one exchange with the neighbour gives a lane both pieces of its own half).  Against the
-// quad-cooperative whole-block fetch: half the load instructions, a 2 x 2 exchange of 4 words instead of a 4 x 4 transpose of 16, two
-// masked popcounts per end instead of four: 5.74 G -> 4.27 G vector instructions per round-1 launch, 16.8 -> 15.9 ms (profiles/r04_notes.md).
-// The files and every other kernel keep the reference layout; the algorithmic byte count stays the reference layout's.
+// reads piece q of both members' halves; one exchange with the neighbour gives a lane both pieces of its own half).  Against a
+// quad-cooperative whole-block fetch over CP_OCC itself: half the load instructions, a 2 x 2 exchange of 4 words instead of a 4 x 4
+// transpose of 16, two masked popcounts per end instead of four: 5.74 G -> 4.27 G vector instructions per round-1 launch, 16.8 -> 15.9 ms
+// (profiles/r04_notes.md).  The files and every other kernel keep the reference layout; the algorithmic byte count stays the reference
+// layout's.
 __device__ __forceinline__ int64_t cnt_at4(const DevFmi &f, int i) { return i == 0 ? f.count[0] : i == 1 ? f.count[1] : i == 2 ? f.count[2] : f.count[3]; }
 struct HalfBlk { uint4 x, y; };            // piece (lane & 1) and piece 1 - (lane & 1) of the lane's half: bases 2h + q, 2h + 1 - q
 template <int J>
@@ -169,11 +105,8 @@ __device__ __forceinline__ void pair_finish(const DevFmi &f, int q, int64_t k, i
     ns = s_a;
     nl = a == 0 ? l + s - s_a : a == 1 ? l + s - s_a - s_o : a == 2 ? l + sent + s_o : l + sent;
 }
-struct HalfCache {
-    HalfBlk a, b;
-    int32_t ta, tb;                     // (block << 1 | half) held, -1 = none
-};
-// backwardExt over the interleaved table for every lane of the wave.  MUST be called by all 64 lanes.
+// backwardExt over the interleaved table for every lane of the wave at once.  MUST be called by all 64 lanes (wave-uniform control
+// flow); lanes without work pass need = false.
 __device__ __forceinline__ void backward_ext_pair(const DevFmi &f, bool need, int64_t k, int64_t l, int64_t s, int a,
                                                   int64_t &nk, int64_t &nl, int64_t &ns) {
     const int q = (int)(threadIdx.x & 1);
@@ -190,7 +123,22 @@ __device__ __forceinline__ void backward_ext_pair(const DevFmi &f, bool need, in
     occ_pair(two ? B : A, ep, oxe, oye);
     pair_finish(f, q, k, l, s, a, oxs, oys, oxe, oye, nk, nl, ns);
 }
-// ... with the lane's two most recent half blocks kept in registers (BlkCache's rule: start against previous start, end against previous end)
+
+// backwardExt with the lane's two most recent half blocks kept in registers.  Four extensions in five belong to the backward
+// phase (642 M of 818 M per million reads in rounds 1-2), where the entries of a column are NESTED intervals visited from the
+// innermost outwards: the block holding k is one of the previous entry's blocks for 43 % of them, the block holding k + s for
+// 35 % of those that need a second block (counted on the bench reads, profiles/r03_notes.md).  Those fetches were L1 / L2 hits,
+// but requests all the same, and requests per second — not bytes, not lines — are what the memory system runs out of under this
+// kernel.  The cache is role-bound (start half block against the previous start, end half block against the previous end), so
+// a hit moves no data: the lane simply takes no part in the pair's fetch of its own half block.  MUST be called by all 64 lanes.
+struct HalfCache {
+    HalfBlk a, b;
+    int32_t ta, tb;                     // (block << 1 | half) held, -1 = none
+};
+__device__ __forceinline__ void cache_init(HalfCache &c) {
+    c.a.x = c.a.y = c.b.x = c.b.y = make_uint4(0, 0, 0, 0);
+    c.ta = c.tb = -1;
+}
 __device__ __forceinline__ void backward_ext_pair_cached(const DevFmi &f, HalfCache &c, bool need, int64_t k, int64_t l, int64_t s, int a,
                                                          int64_t &nk, int64_t &nl, int64_t &ns) {
     const int q = (int)(threadIdx.x & 1);
@@ -205,133 +153,6 @@ __device__ __forceinline__ void backward_ext_pair_cached(const DevFmi &f, HalfCa
     occ_pair(c.a, sp, oxs, oys);
     occ_pair(two ? c.b : c.a, ep, oxe, oye);
     pair_finish(f, q, k, l, s, a, oxs, oys, oxe, oye, nk, nl, ns);
-}
-
-// backwardExt for every lane of the wave at once.  MUST be called by all 64 lanes
-// (wave-uniform control flow); lanes without work pass need = false.
-template <int TAB = 0>
-__device__ __forceinline__ void backward_ext_coop(const DevFmi &f, bool need, int64_t k, int64_t l, int64_t s,
-                                                  int a, int64_t &nk, int64_t &nl, int64_t &ns) {
-    if (TAB == 2) { backward_ext_pair(f, need, k, l, s, a, nk, nl, ns); return; }
-    constexpr int BS = TAB == 1 ? 7 : 6;
-    const uint4 *const tab = TAB ? f.cp2 : f.cp;
-    const int q = (int)(threadIdx.x & 3);
-    const int64_t sp = need ? k : 0, ep = need ? k + s : 0;
-    const bool two = need && ((sp >> BS) != (ep >> BS));
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    uint4 A0 = zero, A1 = zero, A2 = zero, A3 = zero;
-    {
-        const int64_t b0 = quad_bcast64<0>(sp) >> BS, b1 = quad_bcast64<1>(sp) >> BS;
-        const int64_t b2 = quad_bcast64<2>(sp) >> BS, b3 = quad_bcast64<3>(sp) >> BS;
-        const uint32_t n = need ? 1u : 0u;
-        if (qdpp<0x00>(n)) A0 = tab[(b0 << 2) + q];
-        if (qdpp<0x55>(n)) A1 = tab[(b1 << 2) + q];
-        if (qdpp<0xAA>(n)) A2 = tab[(b2 << 2) + q];
-        if (qdpp<0xFF>(n)) A3 = tab[(b3 << 2) + q];
-    }
-    uint4 B0 = zero, B1 = zero, B2 = zero, B3 = zero;
-    const bool any_two = __any(two);
-    if (any_two) {
-        const int64_t b0 = quad_bcast64<0>(ep) >> BS, b1 = quad_bcast64<1>(ep) >> BS;
-        const int64_t b2 = quad_bcast64<2>(ep) >> BS, b3 = quad_bcast64<3>(ep) >> BS;
-        const uint32_t n = two ? 1u : 0u;
-        if (qdpp<0x00>(n)) B0 = tab[(b0 << 2) + q];
-        if (qdpp<0x55>(n)) B1 = tab[(b1 << 2) + q];
-        if (qdpp<0xAA>(n)) B2 = tab[(b2 << 2) + q];
-        if (qdpp<0xFF>(n)) B3 = tab[(b3 << 2) + q];
-    }
-    // after the transpose A0..A3 are pieces 0..3 of this lane's own block
-    quad_transpose4(A0, A1, A2, A3, q);
-    if (any_two) quad_transpose4(B0, B1, B2, B3, q);
-    if (!two) { B0 = A0; B1 = A1; B2 = A2; B3 = A3; }
-    Occ4 osp, oep;
-    occ_any<TAB>(f, A0, A1, A2, A3, sp, osp);
-    occ_any<TAB>(f, B0, B1, B2, B3, ep, oep);
-    const int64_t s0 = oep.v[0] - osp.v[0], s1 = oep.v[1] - osp.v[1];
-    const int64_t s2 = oep.v[2] - osp.v[2], s3 = oep.v[3] - osp.v[3];
-    const int64_t l3 = l + ((k <= f.sentinel && k + s > f.sentinel) ? 1 : 0);
-    const int64_t l2 = l3 + s3, l1 = l2 + s2, l0 = l1 + s1;
-    nk = (a == 0 ? f.count[0] + osp.v[0] : a == 1 ? f.count[1] + osp.v[1]
-          : a == 2 ? f.count[2] + osp.v[2] : f.count[3] + osp.v[3]);
-    ns = a == 0 ? s0 : a == 1 ? s1 : a == 2 ? s2 : s3;
-    nl = a == 0 ? l0 : a == 1 ? l1 : a == 2 ? l2 : l3;
-}
-
-// backwardExt with the lane's two most recent blocks kept in registers.  Four extensions in five belong to the backward
-// phase (642 M of 818 M per million reads in rounds 1-2), where the entries of a column are NESTED intervals visited from the
-// innermost outwards: the block holding k is one of the previous entry's blocks for 43 % of them, the block holding k + s for
-// 35 % of those that need a second block (counted on the bench reads, profiles/r03_notes.md).  Those fetches were L1 / L2 hits,
-// but requests all the same, and requests per second — not bytes, not lines — are what the memory system runs out of under this
-// kernel.  The cache is role-bound (start block against the previous start block, end block against the previous end block), so
-// a hit moves no data: the lane simply takes no part in the quad's fetch of its own block.  MUST be called by all 64 lanes.
-struct BlkCache {
-    uint4 a0, a1, a2, a3, b0, b1, b2, b3;
-    int32_t ta, tb;                     // block numbers held (rows >> 6 < 2^30), -1 = none
-};
-template <int TAB = 0>
-__device__ __forceinline__ void backward_ext_cached(const DevFmi &f, BlkCache &c, bool need, int64_t k, int64_t l, int64_t s,
-                                                    int a, int64_t &nk, int64_t &nl, int64_t &ns) {
-    constexpr int BS = TAB == 1 ? 7 : 6;
-    const uint4 *const tab = TAB ? f.cp2 : f.cp;
-    const int q = (int)(threadIdx.x & 3);
-    const int64_t sp = need ? k : 0, ep = need ? k + s : 0;
-    const int32_t bs = (int32_t)(sp >> BS), be = (int32_t)(ep >> BS);
-    const bool two = need && bs != be;
-    const bool fa = need && bs != c.ta, fb = two && be != c.tb;
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    if (__any(fa)) {
-        uint4 A0 = zero, A1 = zero, A2 = zero, A3 = zero;
-        const int64_t b0 = quad_bcast64<0>(sp) >> BS, b1 = quad_bcast64<1>(sp) >> BS;
-        const int64_t b2 = quad_bcast64<2>(sp) >> BS, b3 = quad_bcast64<3>(sp) >> BS;
-        const uint32_t n = fa ? 1u : 0u;
-        if (qdpp<0x00>(n)) A0 = tab[(b0 << 2) + q];
-        if (qdpp<0x55>(n)) A1 = tab[(b1 << 2) + q];
-        if (qdpp<0xAA>(n)) A2 = tab[(b2 << 2) + q];
-        if (qdpp<0xFF>(n)) A3 = tab[(b3 << 2) + q];
-        quad_transpose4(A0, A1, A2, A3, q);
-        if (fa) { c.a0 = A0; c.a1 = A1; c.a2 = A2; c.a3 = A3; c.ta = bs; }
-    }
-    if (__any(fb)) {
-        uint4 B0 = zero, B1 = zero, B2 = zero, B3 = zero;
-        const int64_t b0 = quad_bcast64<0>(ep) >> BS, b1 = quad_bcast64<1>(ep) >> BS;
-        const int64_t b2 = quad_bcast64<2>(ep) >> BS, b3 = quad_bcast64<3>(ep) >> BS;
-        const uint32_t n = fb ? 1u : 0u;
-        if (qdpp<0x00>(n)) B0 = tab[(b0 << 2) + q];
-        if (qdpp<0x55>(n)) B1 = tab[(b1 << 2) + q];
-        if (qdpp<0xAA>(n)) B2 = tab[(b2 << 2) + q];
-        if (qdpp<0xFF>(n)) B3 = tab[(b3 << 2) + q];
-        quad_transpose4(B0, B1, B2, B3, q);
-        if (fb) { c.b0 = B0; c.b1 = B1; c.b2 = B2; c.b3 = B3; c.tb = be; }
-    }
-    Occ4 osp, oep;
-    occ_any<TAB>(f, c.a0, c.a1, c.a2, c.a3, sp, osp);
-    occ_any<TAB>(f, two ? c.b0 : c.a0, two ? c.b1 : c.a1, two ? c.b2 : c.a2, two ? c.b3 : c.a3, ep, oep);
-    const int64_t s0 = oep.v[0] - osp.v[0], s1 = oep.v[1] - osp.v[1];
-    const int64_t s2 = oep.v[2] - osp.v[2], s3 = oep.v[3] - osp.v[3];
-    const int64_t l3 = l + ((k <= f.sentinel && k + s > f.sentinel) ? 1 : 0);
-    const int64_t l2 = l3 + s3, l1 = l2 + s2, l0 = l1 + s1;
-    nk = (a == 0 ? f.count[0] + osp.v[0] : a == 1 ? f.count[1] + osp.v[1]
-          : a == 2 ? f.count[2] + osp.v[2] : f.count[3] + osp.v[3]);
-    ns = a == 0 ? s0 : a == 1 ? s1 : a == 2 ? s2 : s3;
-    nl = a == 0 ? l0 : a == 1 ? l1 : a == 2 ? l2 : l3;
-}
-
-// the register cache that goes with a table kind, and the cached extension over it
-template <int TAB> struct CacheOf { using type = BlkCache; };
-template <> struct CacheOf<2> { using type = HalfCache; };
-__device__ __forceinline__ void cache_init(BlkCache &c) {
-    c.a0 = c.a1 = c.a2 = c.a3 = c.b0 = c.b1 = c.b2 = c.b3 = make_uint4(0, 0, 0, 0);
-    c.ta = c.tb = -1;
-}
-__device__ __forceinline__ void cache_init(HalfCache &c) {
-    c.a.x = c.a.y = c.b.x = c.b.y = make_uint4(0, 0, 0, 0);
-    c.ta = c.tb = -1;
-}
-template <int TAB>
-__device__ __forceinline__ void ext_cached(const DevFmi &f, typename CacheOf<TAB>::type &c, bool need, int64_t k, int64_t l, int64_t s, int a,
-                                           int64_t &nk, int64_t &nl, int64_t &ns) {
-    if constexpr (TAB == 2) backward_ext_pair_cached(f, c, need, k, l, s, a, nk, nl, ns);
-    else backward_ext_cached<TAB>(f, c, need, k, l, s, a, nk, nl, ns);
 }
 
 // count[i] without dynamic indexing of the kernel argument (keeps it in SGPRs)
@@ -581,7 +402,7 @@ __device__ __forceinline__ long long ho_item_slot(const SeedLaunch &a, HoState &
 // Returns true for the lanes whose pivot has left; false (run the backward phase here) when the buffers are full.
 // MUST be called by all 64 lanes.
 __device__ __forceinline__ bool bwd_hand_over(const SeedLaunch &a, HoState &h, const PrevList &pl, bool req, int base, int num_prev,
-                                              uint32_t rid, int x, int min_intv, bool dry, const uint4 *src_list = nullptr) {
+                                              uint32_t rid, int x, int min_intv, bool dry) {
     if (!__any(req)) return false;
     const int lane = (int)(threadIdx.x & 63);
     const bool is_short = num_prev <= kBwdShortMax;
@@ -610,8 +431,7 @@ __device__ __forceinline__ bool bwd_hand_over(const SeedLaunch &a, HoState &h, c
         BwdItem w;
         w.rid = rid; w.x = x; w.min_intv = min_intv; w.num_prev = 0; w.off = 0;
         if (fits) {
-            if (src_list) { for (int p = 0; p < num_prev; ++p) a.bwd_ent[eo + p] = src_list[num_prev - 1 - p]; }     // a forward kernel's list: push order
-            else for (int p = 0; p < num_prev; ++p) a.bwd_ent[eo + p] = prev_raw(pl, base, p);
+            for (int p = 0; p < num_prev; ++p) a.bwd_ent[eo + p] = prev_raw(pl, base, p);
             w.num_prev = num_prev;
             w.off = (int64_t)eo;
         }
@@ -746,8 +566,8 @@ enum : int { PH_FETCH = 0, PH_LOAD, PH_HOLD, PH_PIVOT, PH_FWD, PH_FWD_END, PH_BW
 
 // Rounds 1 and 2.  ALL_POS: work item = read, walk every pivot (round 1).
 // !ALL_POS: work item = (read, pivot, min_intv), one pivot (round 2).
-template <bool ALL_POS, int TAB = 0>
-__global__ __launch_bounds__(kBlock, TAB == 1 ? 3 : BWAMS_SEARCH_MIN_BLOCKS) void smem_search_kernel(SeedLaunch a, const Round2Work *work) {
+template <bool ALL_POS>
+__global__ __launch_bounds__(kBlock, BWAMS_SEARCH_MIN_BLOCKS) void smem_search_kernel(SeedLaunch a, const Round2Work *work) {
     const DevFmi &f = a.fmi;
     const int64_t slot = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int cap = a.prev_cap;
@@ -793,12 +613,8 @@ __global__ __launch_bounds__(kBlock, TAB == 1 ? 3 : BWAMS_SEARCH_MIN_BLOCKS) voi
     wo.base = -1; wo.used = 0; wo.emitted = 0;
     WaveTickets wt;
     wt.next = 0; wt.left = 0; wt.seen = 0;
-    typename CacheOf<TAB>::type bc;
+    HalfCache bc;
     cache_init(bc);
-#ifdef BWAMS_LIST_PREFETCH                   // (measured: no gain, 17.1 against 16.9 ms — the entry's round trip is not what an iteration waits for; profiles/r04_notes.md)
-    uint4 pf_ent = make_uint4(0, 0, 0, 0);    // the list entry requested one iteration ahead (logical index pf_p of the current column, -1: none)
-    int pf_p = -1;
-#endif
 
     while (true) {
         // at most one SMEM per lane and iteration; written at the wave-uniform point below
@@ -989,18 +805,7 @@ __global__ __launch_bounds__(kBlock, TAB == 1 ? 3 : BWAMS_SEARCH_MIN_BLOCKS) voi
             if (!go) {
                 phase = PH_BWD_END;
             } else {
-                // an entry beyond the LDS ring comes from the lane's HBM list: a memory round trip IN FRONT of the block fetch that depends
-                // on it — two dependent round trips in one iteration, for the whole wave.  The entry the lane will need NEXT (p + 1: the
-                // compaction writes at most index p) is requested here, together with this iteration's blocks, and is in registers when
-                // the next iteration asks for it
-#ifdef BWAMS_LIST_PREFETCH
-                if (pf_p == p) prev_unpack(pf_ent, pk, pl, ps, pn);
-                else prev_get(prev, base, p, pk, pl, ps, pn);
-                pf_p = -1;
-                if (p + 1 < num_prev && p + 1 >= kPrevLds) { pf_ent = prev.glob[base + p + 1]; pf_p = p + 1; }
-#else
                 prev_get(prev, base, p, pk, pl, ps, pn);
-#endif
                 do_ext = true;
                 ek = pk; el = pl; es = ps; ea = bwd_a;
             }
@@ -1008,11 +813,7 @@ __global__ __launch_bounds__(kBlock, TAB == 1 ? 3 : BWAMS_SEARCH_MIN_BLOCKS) voi
 
         // ---- the one extension of this iteration -------------------------------------
         int64_t nk = 0, nl = 0, ns = 0;
-#ifdef BWAMS_NO_BLKCACHE
-        backward_ext_coop<TAB>(f, do_ext, ek, el, es, ea, nk, nl, ns);
-#else
-        ext_cached<TAB>(f, bc, do_ext, ek, el, es, ea, nk, nl, ns);
-#endif
+        backward_ext_pair_cached(f, bc, do_ext, ek, el, es, ea, nk, nl, ns);
         if (do_ext) {
             n_ext++;
             n_blk += ((ek >> 6) == ((ek + es) >> 6)) ? 1 : 2;
@@ -1166,328 +967,6 @@ __global__ __launch_bounds__(kBlock, TAB == 1 ? 3 : BWAMS_SEARCH_MIN_BLOCKS) voi
     flush_counters(a.ctr, n_ext, n_blk);
 }
 
-// ---- rounds 1 and 2 as TWO lane kernels (round 4) ------------------------------------------------------------------------------
-// smem_search_kernel runs forward and backward phases of different lanes in one loop: every iteration executes the forward lanes'
-// code AND the backward lanes' code (the wave diverges), about 700 vector + 290 scalar instructions for one extension per lane — the
-// launch is bound by instruction issue (profiles/r04_notes.md), not by the memory round trip.  Split by role, each loop carries one
-// role's code and state:
-//   smem_fwd_kernel   a lane owns a read (round 1) or a pivot (round 2) and runs FORWARD phases only; every interval the reference
-//                     would push on prevArray goes straight to the pivot's list in HBM (no ring, no copy); at the end of a forward
-//                     phase the pivot becomes an item (rid, x, min_intv, entries, list) and the lane opens the read's next pivot at once.
-//                     Forward phases cost the same for every read (149 extensions): no tail.
-//   smem_bwdl_kernel  a lane owns an item and runs its BACKWARD phase: the first column reads the list where the forward kernel left
-//                     it, the survivors are compacted into the lane's LDS ring / HBM list as before.  Long phases leave the lane for
-//                     the kernels behind (bwd_hand_over), as in the one-kernel form.
-// Lists in HBM: round 1, pivot x of read r at 2 (cum[r] + r) + 2 x (a read's forward phases tile it: list i ends before list i + 1
-// begins); round 2, work item t at t (max_len + 2).  Same extensions, same SMEMs, same counts as smem_search_kernel.
-enum : int { FW_FETCH = 0, FW_PIVOT, FW_FWD, FW_EXIT };
-
-template <bool ALL_POS, int TAB>
-__global__ __launch_bounds__(kBlock) void smem_fwd_kernel(SeedLaunch a, const Round2Work *work) {
-    const DevFmi &f = a.fmi;
-    extern __shared__ uint32_t lds_reads[];
-    uint32_t *const lds_col = a.reads_in_lds ? lds_reads + threadIdx.x : nullptr;
-    ReadView rv;
-    rv.lds_col = lds_col;
-    rv.gl = a.packed;
-    rv.cw = a.read_cw;
-    const int64_t n_work = ALL_POS ? a.nseq : (int64_t)a.ctr->n_work2;
-    const unsigned long long lanes_below = (1ull << (threadIdx.x & 63)) - 1ull;
-    int phase = FW_FETCH;
-    uint32_t rid = 0;
-    int len = 0, x = 0, next_x = 0, min_intv = 1;
-    int64_t ck = 0, cl = 0, cs = 0;
-    int cn = 0, j = 0, num_prev = 0;
-    int64_t lbase = 0;                    // round 1: 2 (cum[rid] + rid); round 2: the item's list
-    int64_t fl = 0;                       // the list of the pivot in progress
-    bool lst_ok = true;                   // its list lies inside the buffer (round 2 beyond the buffer: counted, the caller re-runs unsplit)
-    unsigned long long n_ext = 0, n_blk = 0;
-    WaveTickets wt;
-    wt.next = 0; wt.left = 0; wt.seen = 0;
-    long long it_base = -1;               // the wave's chunk of item slots
-    int it_used = 0;
-
-    auto push = [&](int64_t k, int64_t l, int64_t s_, int n) {
-        if (lst_ok) a.fl_ent[fl + num_prev] = prev_pack(k, l, s_, n);
-        num_prev++;
-    };
-    while (true) {
-        {
-            unsigned long long t = 0;
-            if (take_ticket(&a.ctr->work_head, wt, phase == FW_FETCH, t, n_work, ALL_POS)) {
-                if ((int64_t)t >= n_work) phase = FW_EXIT;
-                else {
-                    if (ALL_POS) {
-                        rid = (uint32_t)t; x = 0; min_intv = 1;
-                    } else {
-                        const Round2Work wk = work[t];
-                        rid = wk.rid; x = wk.x; min_intv = wk.min_intv;
-                    }
-                    const int64_t qoff = a.cum[rid];
-                    len = (int)(a.cum[rid + 1] - qoff);
-                    lbase = ALL_POS ? 2 * (qoff + (int64_t)rid) : (int64_t)t * (int64_t)(a.fl_item_stride);
-                    lst_ok = ALL_POS || lbase + a.fl_item_stride <= a.fl_cap;
-                    phase = FW_PIVOT;
-                    if (ALL_POS && a.skip && a.skip[rid]) phase = FW_FETCH;
-                    else if (!lst_ok) { atomicAdd(&a.ctr->f_overflow, 1ull); phase = FW_FETCH; }
-                    else read_take(rv, lds_col, a.packed, a.read_w, rid);
-                }
-            }
-        }
-        if (__all(phase == FW_EXIT)) break;
-
-        if (phase == FW_PIVOT) {
-            if (x >= len) phase = FW_FETCH;
-            else {
-                const int c = base_at(rv, x);
-                if (c >= 4) {
-                    x = x + 1;
-                    if (!ALL_POS) phase = FW_FETCH;
-                } else {
-                    ck = cnt_at(f, c);
-                    cl = cnt_at(f, 3 - c);
-                    cs = cnt_at(f, c + 1) - ck;
-                    cn = x;
-                    j = x + 1;
-                    next_x = x + 1;
-                    num_prev = 0;
-                    fl = ALL_POS ? lbase + 2 * (int64_t)x : lbase;
-                    phase = FW_FWD;
-                    if (f.all_smem && len - x >= f.all_bp) {
-                        // FMA: the first forward steps come from one all_smem entry (FMI_search.cpp:1414-1463)
-                        const int bp = f.all_bp;
-                        uint32_t tix = 0;
-                        int kk = 0;
-                        for (; kk < bp; ++kk) {
-                            const int bb = base_at(rv, x + kk);
-                            if (bb >= 4) break;
-                            tix |= (uint32_t)bb << ((bp - 1 - kk) * 2);
-                        }
-                        const uint32_t *ent = f.all_smem + (int64_t)tix * 32;
-                        const int last_avail = (int)ent[0];
-                        const int last_idx = (kk > last_avail ? last_avail : kk) - 1;
-                        for (int t = 0; t < last_idx; ++t, ++j) {
-                            const int bb = base_at(rv, j);
-                            next_x = j + 1;
-                            const int64_t tk = ck + ent[1 + 3 * t];
-                            const int64_t tl = cnt_at(f, 3 - bb) + ent[2 + 3 * t];
-                            const int64_t ts = ent[3 + 3 * t];
-                            if (ts != cs) push(ck, cl, cs, cn);
-                            if (ts < min_intv) {
-                                next_x = j;
-                                j = len;                       // no further forward steps
-                                break;
-                            }
-                            ck = tk; cl = tl; cs = ts; cn = j;
-                        }
-                        if (kk < bp) {                         // an N inside the window (reference quirk kept)
-                            next_x = j + 1;
-                            j = len;
-                        }
-                    }
-                }
-            }
-        }
-        // ---- one forward extension ----------------------------------------------------------------
-        bool do_ext = false, fin = false;
-        int ea = 0;
-        if (phase == FW_FWD) {
-            fin = true;
-            if (j < len) {
-                const int c = base_at(rv, j);
-                next_x = j + 1;
-                if (c < 4) { fin = false; do_ext = true; ea = 3 - c; }
-            }
-        }
-        int64_t nk = 0, nl = 0, ns = 0;
-        backward_ext_coop<TAB>(f, do_ext, cl, ck, cs, ea, nk, nl, ns);          // forward = backward on the other strand
-        if (do_ext) {
-            n_ext++;
-            n_blk += ((cl >> 6) == ((cl + cs) >> 6)) ? 1 : 2;
-            if (ns != cs) push(ck, cl, cs, cn);
-            if (ns < min_intv) {
-                next_x = j;
-                fin = true;                                   // cur is still the old interval
-            } else {
-                ck = nl; cl = nk; cs = ns; cn = j;
-                j++;
-            }
-        }
-        bool item = false;
-        if (phase == FW_FWD && fin) {
-            if (cs >= min_intv) push(ck, cl, cs, cn);
-            item = num_prev > 0;                              // an empty list leaves nothing for the backward phase to do
-        }
-        // ---- the pivots whose forward phase ended become items (slots reserved per wave, 64 at a time) --------
-        {
-            const unsigned long long m = __ballot(item);
-            if (m) {
-                const int cnt = __popcll(m);
-                if (it_base < 0 || it_used + cnt > 64) {
-                    const int lane = (int)(threadIdx.x & 63);
-                    if (it_base >= 0) { const long long sl = it_base + it_used + lane; if (it_used + lane < 64 && sl < a.f_items_cap) a.f_items[sl].num_prev = 0; }
-                    it_base = (long long)wave_ticket(&a.ctr->f_items, 64ull);
-                    it_used = 0;
-                }
-                const long long sl = it_base + it_used + __popcll(m & lanes_below);
-                if (item) {
-                    if (sl < a.f_items_cap) {
-                        BwdItem w;
-                        w.rid = rid; w.x = x; w.min_intv = min_intv; w.num_prev = num_prev; w.off = fl;
-                        a.f_items[sl] = w;
-                    } else atomicAdd(&a.ctr->f_overflow, 1ull);
-                }
-                it_used += cnt;
-            }
-        }
-        if (phase == FW_FWD && fin) {
-            x = next_x;
-            phase = ALL_POS ? FW_PIVOT : FW_FETCH;
-        }
-    }
-    {   // the unused slots of the wave's last chunk
-        const int lane = (int)(threadIdx.x & 63);
-        if (it_base >= 0) { const long long sl = it_base + it_used + lane; if (it_used + lane < 64 && sl < a.f_items_cap) a.f_items[sl].num_prev = 0; }
-    }
-    flush_counters(a.ctr, n_ext, n_blk);
-}
-
-enum : int { BL_FETCH = 0, BL_BWD, BL_BWD_END, BL_HO, BL_HO_LATE, BL_EXIT };
-
-template <int TAB>
-__global__ __launch_bounds__(kBlock, TAB == 1 ? 3 : BWAMS_SEARCH_MIN_BLOCKS) void smem_bwdl_kernel(SeedLaunch a) {
-    const DevFmi &f = a.fmi;
-    const int64_t slot = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    extern __shared__ uint32_t lds_reads[];
-    uint32_t *const lds_col = a.reads_in_lds ? lds_reads + threadIdx.x : nullptr;
-    PrevList prev;
-    prev.glob = a.prev + slot * (int64_t)a.prev_cap;
-    prev.ring = reinterpret_cast<uint4 *>(lds_reads + (a.reads_in_lds ? a.read_w * kBlock : 0)) + threadIdx.x;
-    ReadView rv;
-    rv.lds_col = lds_col;
-    rv.gl = a.packed;
-    rv.cw = a.read_cw;
-    unsigned long long n_items = a.f_items_fixed >= 0 ? (unsigned long long)a.f_items_fixed : a.ctr->f_items;
-    if ((int64_t)n_items > a.f_items_cap) n_items = (unsigned long long)a.f_items_cap;
-    int phase = BL_FETCH;
-    uint32_t rid = 0;
-    int x = 0, min_intv = 1, j = 0, num_prev = 0, p = 0, num_curr = 0, cur_m = 0, bwd_a = 0, ho_x = 0;
-    int32_t curr_s = -1;
-    bool first = true, dry = false, ho_tried = false;
-    const uint4 *src = nullptr;           // the forward kernel's list while the first column reads it (push order: shortest match first)
-    unsigned long long n_ext = 0, n_blk = 0;
-    WaveOut wo;
-    wo.base = -1; wo.used = 0; wo.emitted = 0;
-    WaveTickets wt;
-    wt.next = 0; wt.left = 0; wt.seen = 0;
-    typename CacheOf<TAB>::type bc;
-    cache_init(bc);
-    HoState ho;
-    ho_init(ho);
-
-    auto entry = [&](int q, int64_t &k, int64_t &l, int64_t &s_, int &n) {
-        if (src) prev_unpack(src[num_prev - 1 - q], k, l, s_, n);
-        else prev_get(prev, 0, q, k, l, s_, n);
-    };
-    while (true) {
-        bool em = false;
-        uint32_t em_m = 0, em_n = 0;
-        int64_t em_k = 0, em_l = 0, em_s = 0;
-        if (phase == BL_BWD_END) {
-            if (num_prev != 0) {
-                int64_t qk, ql, qs;
-                int qn;
-                entry(0, qk, ql, qs, qn);
-                if (qn - cur_m + 1 >= a.min_seed_len) { em = true; em_m = (uint32_t)cur_m; em_n = (uint32_t)qn; em_k = qk; em_l = ql; em_s = qs; }
-            }
-            phase = BL_FETCH;
-        }
-        wave_emit(a, wo, em, rid, em_m, em_n, em_k, em_l, em_s);
-        em = false;
-        {
-            unsigned long long t = 0;
-            if (take_ticket(&a.ctr->f_ticket, wt, phase == BL_FETCH, t, (int64_t)n_items, true)) {
-                if (t >= n_items) phase = BL_EXIT;
-                else {
-                    const BwdItem it = a.f_items[t];
-                    if (it.num_prev > 0) {
-                        rid = it.rid; x = it.x; min_intv = it.min_intv; num_prev = it.num_prev;
-                        src = a.fl_ent + it.off;
-                        read_take(rv, lds_col, a.packed, a.read_w, rid);
-                        j = x - 1; p = 0; num_curr = 0; curr_s = -1; first = true; cur_m = x; ho_tried = false;
-                        phase = BL_BWD;
-                        if (a.bwd_min_list > 0 && num_prev >= (dry ? a.bwd_dry_min_list : a.bwd_min_list) && num_prev <= kBwdMaxList) { ho_x = x; phase = BL_HO; }
-                    }
-                }
-            }
-        }
-        if (__all(phase == BL_EXIT)) break;
-        if (!dry && __any(phase == BL_EXIT)) { dry = true; ho_tried = false; }
-
-        bool do_ext = false;
-        int64_t pk = 0, pl = 0, ps = 0;
-        int pn = 0;
-        if (phase == BL_BWD) {
-            bool go = true;
-            if (p == 0) {
-                go = false;
-                if (num_prev != 0 && j >= 0) { bwd_a = base_at(rv, j); go = bwd_a < 4; }
-            }
-            if (!go) phase = BL_BWD_END;
-            else { entry(p, pk, pl, ps, pn); do_ext = true; }
-        }
-        int64_t nk = 0, nl = 0, ns = 0;
-#ifdef BWAMS_NO_BLKCACHE
-        backward_ext_coop<TAB>(f, do_ext, pk, pl, ps, bwd_a, nk, nl, ns);
-#else
-        ext_cached<TAB>(f, bc, do_ext, pk, pl, ps, bwd_a, nk, nl, ns);
-#endif
-        if (do_ext) {
-            n_ext++;
-            n_blk += ((pk >> 6) == ((pk + ps) >> 6)) ? 1 : 2;
-            bool keep = false;
-            if (first) {
-                if (ns < min_intv && (pn - cur_m + 1) >= a.min_seed_len) {
-                    em = true; em_m = (uint32_t)cur_m; em_n = (uint32_t)pn; em_k = pk; em_l = pl; em_s = ps;
-                    first = false;
-                } else if (ns >= min_intv && ns != (int64_t)curr_s) { keep = true; first = false; }
-            } else keep = ns >= min_intv && ns != (int64_t)curr_s;
-            if (keep) {
-                curr_s = (int32_t)ns;
-                prev_put(prev, 0, num_curr, nk, nl, ns, pn);
-                num_curr++;
-            }
-            p++;
-            if (p == num_prev) {                         // this column is done: the list now lives in the lane's ring / HBM list
-                src = nullptr;
-                num_prev = num_curr;
-                if (num_curr == 0) phase = BL_BWD_END;
-                else {
-                    cur_m = j;
-                    j--;
-                    p = 0; num_curr = 0; curr_s = -1; first = true;
-                    if (!ho_tried && x - cur_m >= (dry ? a.bwd_dry_cols : a.bwd_cols)) {
-                        ho_tried = true;
-                        if (a.bwd_min_list > 0 && num_prev >= (dry ? a.bwd_dry_late_list : a.bwd_late_list) && num_prev <= kBwdMaxList) { ho_x = cur_m; phase = BL_HO_LATE; }
-                    }
-                }
-            }
-        }
-        {
-            const bool rq = phase == BL_HO || phase == BL_HO_LATE;
-            if (__any(rq)) {
-                const bool gone = bwd_hand_over(a, ho, prev, rq, 0, num_prev, rid, ho_x, min_intv, dry, phase == BL_HO ? src : nullptr);
-                if (rq) phase = gone ? BL_FETCH : BL_BWD;       // the buffers are full: the backward phase runs (on) here, its state untouched
-            }
-        }
-        wave_emit(a, wo, em, rid, em_m, em_n, em_k, em_l, em_s);
-    }
-    ho_close_items<0>(a, ho);
-    ho_close_items<1>(a, ho);
-    wave_emit_finish(a, wo);
-    flush_counters(a.ctr, n_ext, n_blk);
-}
-
 // The backward phase of one pivot per wavefront (see bwd_hand_over): the list lives in LDS, lane p of a batch of 64 owns entry
 // p, every column is one cooperative extension of all entries followed by the reference's in-order decisions
 // (FMI_search.cpp:1529-1590) taken with ballots:
@@ -1506,7 +985,6 @@ constexpr int kBwdReadLds = 256;
 __device__ __forceinline__ int bwd_read_words(const SeedLaunch &a) { return a.read_w <= kBwdReadLds ? a.read_w : 0; }
 __device__ __forceinline__ int bwd_wave_words(const SeedLaunch &a) { return kBwdMaxList * 4 + 4 * bwd_read_words(a); }
 
-template <int TAB>
 __device__ __forceinline__ void bwd_wave_role(const SeedLaunch &a, uint32_t *lds_reads, WaveOut &wo, unsigned long long &n_ext_io,
                                               unsigned long long &n_blk_io) {
     const DevFmi &f = a.fmi;
@@ -1573,7 +1051,7 @@ __device__ __forceinline__ void bwd_wave_role(const SeedLaunch &a, uint32_t *lds
                     int64_t pk = 0, pl = 0, ps = 0, nk = 0, nl = 0, ns = 0;
                     int pn = 0;
                     if (need) prev_unpack(lst[p], pk, pl, ps, pn);
-                    backward_ext_coop<TAB>(f, need, pk, pl, ps, ba, nk, nl, ns);
+                    backward_ext_pair(f, need, pk, pl, ps, ba, nk, nl, ns);
                     if (need) {
                         n_ext++;
                         n_blk += ((pk >> 6) == ((pk + ps) >> 6)) ? 1 : 2;
@@ -1637,7 +1115,6 @@ __device__ __forceinline__ void bwd_wave_role(const SeedLaunch &a, uint32_t *lds
 // are the ones above, taken on the group's sixteen bits of each ballot.
 constexpr int kGrp = 16;
 constexpr int kGroupItemsPerTicket = 16;
-template <int TAB>
 __device__ __forceinline__ void bwd_group_role(const SeedLaunch &a, uint32_t *lds_reads, WaveOut &wo, unsigned long long &n_ext_io,
                                                unsigned long long &n_blk_io) {
     const DevFmi &f = a.fmi;
@@ -1738,7 +1215,7 @@ __device__ __forceinline__ void bwd_group_role(const SeedLaunch &a, uint32_t *ld
         int64_t pk = 0, pl = 0, ps = 0, nk = 0, nl = 0, ns = 0;
         int pn = 0;
         if (need) prev_unpack(lst[p], pk, pl, ps, pn);
-        backward_ext_coop<TAB>(f, need, pk, pl, ps, ba & 3, nk, nl, ns);
+        backward_ext_pair(f, need, pk, pl, ps, ba & 3, nk, nl, ns);
         if (need) {
             n_ext++;
             n_blk += ((pk >> 6) == ((pk + ps) >> 6)) ? 1 : 2;
@@ -1805,31 +1282,18 @@ __device__ __forceinline__ void bwd_group_role(const SeedLaunch &a, uint32_t *ld
 
 // The launch behind rounds 1 and 2: every wavefront first takes pivots with long lists (a wavefront each, the longest-running
 // items), then pivots with short lists (four at a time) — one launch, one tail.
-template <int TAB>
 __global__ __launch_bounds__(kBlock) void smem_bwd_kernel(SeedLaunch a) {
     extern __shared__ uint32_t lds_reads[];
     unsigned long long n_ext = 0, n_blk = 0;
     WaveOut wo;
     wo.base = -1; wo.used = 0; wo.emitted = 0;
-    bwd_wave_role<TAB>(a, lds_reads, wo, n_ext, n_blk);
+    bwd_wave_role(a, lds_reads, wo, n_ext, n_blk);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    bwd_group_role<TAB>(a, lds_reads, wo, n_ext, n_blk);
+    bwd_group_role(a, lds_reads, wo, n_ext, n_blk);
     wave_emit_finish(a, wo);
     flush_counters(a.ctr, n_ext, n_blk);
 }
-template <int ROLE, int TAB>
-__global__ __launch_bounds__(kBlock) void smem_bwd_role_kernel(SeedLaunch a) {
-    extern __shared__ uint32_t lds_reads[];
-    unsigned long long n_ext = 0, n_blk = 0;
-    WaveOut wo;
-    wo.base = -1; wo.used = 0; wo.emitted = 0;
-    if (ROLE == 0) bwd_wave_role<TAB>(a, lds_reads, wo, n_ext, n_blk);
-    else bwd_group_role<TAB>(a, lds_reads, wo, n_ext, n_blk);
-    wave_emit_finish(a, wo);
-    flush_counters(a.ctr, n_ext, n_blk);
-}
-
 // Select round-2 pivots from the round-1 SMEMs (src/bwamem.cpp:721-738).
 __global__ void round2_work_kernel(const bwams_smem_t *pool, DevCounters *ctr, Round2Work *work,
                                    int64_t work_cap, int split_len, int split_width) {
@@ -1851,24 +1315,6 @@ __global__ void round2_work_kernel(const bwams_smem_t *pool, DevCounters *ctr, R
     }
 }
 
-// round 3 ran with a pool and counters of its own: its slots (chunk holes included) go behind the main pool's ...
-__global__ void append_r3_kernel(bwams_smem_t *__restrict__ pool, int64_t pool_cap, const bwams_smem_t *__restrict__ pool3, int64_t pool3_cap,
-                                 const DevCounters *ctr, const DevCounters *ctr3) {
-    const int64_t n12 = (int64_t)ctr->n_smem_total;
-    int64_t n3 = (int64_t)ctr3->n_smem_total;
-    if (n3 > pool3_cap) n3 = pool3_cap;                   // (the overflow is reported by the finish kernel)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x)
-        if (n12 + i < pool_cap) pool[n12 + i] = pool3[i];
-}
-// ... and its counts into the fields mark_kernel(3) folds in.  A pool that could not hold round 3's records shows as a slot count
-// beyond the main pool's capacity: the host grows the pools and runs the stage again.
-__global__ void append_r3_finish_kernel(int64_t pool_cap, int64_t pool3_cap, DevCounters *ctr, const DevCounters *ctr3) {
-    const unsigned long long n3 = ctr3->n_smem_total;
-    ctr->n_smem_total += n3;
-    if ((int64_t)n3 > pool3_cap && (int64_t)ctr->n_smem_total <= pool_cap) ctr->n_smem_total = (unsigned long long)pool_cap + (n3 - (unsigned long long)pool3_cap);
-    ctr->n_smem3 += ctr3->n_smem3; ctr->n_ext3 += ctr3->n_ext3; ctr->n_blk3 += ctr3->n_blk3;
-}
-
 // bookkeeping between rounds (single thread): snapshot the pool cursor, reset the queue
 __global__ void mark_kernel(DevCounters *ctr, int which) {
     if (which == 1) { ctr->n_after_r1 = ctr->n_smem_total; ctr->valid_after[0] = ctr->n_smem_valid; }
@@ -1885,14 +1331,10 @@ __global__ void mark_kernel(DevCounters *ctr, int which) {
     ctr->work_head = 0;
     ctr->bwd_items = ctr->bwd_entries = ctr->bwd_ticket = 0;
     ctr->bwd_items_s = ctr->bwd_ticket_s = 0;
-    if (which == 1) ctr->f_items_r[0] = ctr->f_items;
-    if (which == 2) ctr->f_items_r[1] = ctr->f_items;
-    ctr->f_items = ctr->f_ticket = 0;
     if (which != 2) ctr->work_head3 = 0;       // (mark 2 may run while round 3 is in flight on its own stream... it has joined; kept for symmetry)
 }
 
 // Round 3: forward-only seeds.
-template <int TAB>
 __global__ __launch_bounds__(kBlock) void seed_strategy_kernel(SeedLaunch a, int max_intv) {
     const DevFmi &f = a.fmi;
     extern __shared__ uint32_t lds_reads[];
@@ -1995,7 +1437,7 @@ __global__ __launch_bounds__(kBlock) void seed_strategy_kernel(SeedLaunch a, int
             }
         }
         int64_t nk = 0, nl = 0, ns = 0;
-        backward_ext_coop<TAB>(f, do_ext, cl, ck, cs, ea, nk, nl, ns);
+        backward_ext_pair(f, do_ext, cl, ck, cs, ea, nk, nl, ns);
         if (do_ext) {
             n_ext++;
             n_blk += ((cl >> 6) == ((cl + cs) >> 6)) ? 1 : 2;
@@ -2039,24 +1481,6 @@ __global__ void gather_sorted_kernel(const bwams_smem_t *pool, const uint32_t *o
     }
 }
 
-// CpOcc2 from CP_OCC: compact block B = reference blocks 2B and 2B + 1 (the second may not exist)
-__global__ void cp2_build_kernel(const uint4 *__restrict__ cp, int64_t n_blk, uint4 *__restrict__ cp2) {
-    const int64_t n2 = (n_blk + 1) >> 1;
-    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < n2; b += (int64_t)gridDim.x * blockDim.x) {
-        const uint4 *p = cp + (2 * b) * 4;
-        const uint4 c01 = p[0], c23 = p[1], ac = p[2], gt = p[3];         // one-hot strings: {A, C}, {G, T}
-        uint4 ac2 = make_uint4(0, 0, 0, 0), gt2 = make_uint4(0, 0, 0, 0);
-        if (2 * b + 1 < n_blk) { ac2 = p[6]; gt2 = p[7]; }
-        uint4 hp, lp;
-        hp.x = gt.x | gt.z; hp.y = gt.y | gt.w;            // G | T of bases 0-63
-        hp.z = gt2.x | gt2.z; hp.w = gt2.y | gt2.w;
-        lp.x = ac.z | gt.z; lp.y = ac.w | gt.w;            // C | T
-        lp.z = ac2.z | gt2.z; lp.w = ac2.w | gt2.w;
-        uint4 *o = cp2 + b * 4;
-        o[0] = c01; o[1] = c23; o[2] = hp; o[3] = lp;
-    }
-}
-
 // the interleaved table from CP_OCC: piece b = {cp_count[b], one_hot_bwt_str[b]}
 __global__ void cpi_build_kernel(const uint4 *__restrict__ cp, int64_t n_blk, uint4 *__restrict__ out) {
     for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < n_blk; b += (int64_t)gridDim.x * blockDim.x) {
@@ -2080,11 +1504,10 @@ int grid_for(int64_t n_items, int cu_count) {
 
 }  // namespace
 
-size_t cp2_bytes(int64_t n_blk, int kind) { return kind == 2 ? (size_t)n_blk * 64 + 64 : (size_t)((n_blk + 1) >> 1) * 64 + 64; }
-void launch_cp2_build(const uint4 *cp, int64_t n_blk, uint4 *cp2, int kind, hipStream_t st) {
+size_t cp2_bytes(int64_t n_blk) { return (size_t)n_blk * 64 + 64; }
+void launch_cp2_build(const uint4 *cp, int64_t n_blk, uint4 *cp2, hipStream_t st) {
     if (n_blk <= 0) return;
-    if (kind == 2) cpi_build_kernel<<<256 * 16, 256, 0, st>>>(cp, n_blk, cp2);
-    else cp2_build_kernel<<<256 * 16, 256, 0, st>>>(cp, n_blk, cp2);
+    cpi_build_kernel<<<256 * 16, 256, 0, st>>>(cp, n_blk, cp2);
 }
 
 static size_t lds_bytes(const SeedLaunch &a) { return a.reads_in_lds ? (size_t)a.read_w * kBlock * 4 : 0; }
@@ -2113,17 +1536,9 @@ int64_t seed_pool_slack(int cu_count) {
 }
 
 void launch_mark(DevCounters *ctr, int which, hipStream_t st) { mark_kernel<<<1, 1, 0, st>>>(ctr, which); }
-void launch_append_r3(bwams_smem_t *pool, int64_t pool_cap, const bwams_smem_t *pool3, int64_t pool3_cap, DevCounters *ctr, const DevCounters *ctr3,
-                      hipStream_t st) {
-    append_r3_kernel<<<256, 256, 0, st>>>(pool, pool_cap, pool3, pool3_cap, ctr, ctr3);
-    append_r3_finish_kernel<<<1, 1, 0, st>>>(pool_cap, pool3_cap, ctr, ctr3);
-}
 
 void launch_smem_round1(const SeedLaunch &a, int cu_count, hipStream_t st) {
-    const int tab = a.fmi.cp2 ? a.fmi.tab_kind : 0;
-    if (tab == 2) smem_search_kernel<true, 2><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, nullptr);
-    else if (tab == 1) smem_search_kernel<true, 1><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, nullptr);
-    else smem_search_kernel<true, 0><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, nullptr);
+    smem_search_kernel<true><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, nullptr);
 }
 
 void launch_round2_work(const SeedLaunch &a, Round2Work *work, int64_t work_cap, int split_len,
@@ -2133,59 +1548,18 @@ void launch_round2_work(const SeedLaunch &a, Round2Work *work, int64_t work_cap,
 
 void launch_smem_round2(const SeedLaunch &a, const Round2Work *work, int cu_count, hipStream_t st) {
     // the number of items is only known on the device: launch the persistent grid at chip size
-    const int tab = a.fmi.cp2 ? a.fmi.tab_kind : 0;
-    if (tab == 2) smem_search_kernel<false, 2><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, work);
-    else if (tab == 1) smem_search_kernel<false, 1><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, work);
-    else smem_search_kernel<false, 0><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, work);
-}
-
-void launch_smem_fwd(const SeedLaunch &a, const Round2Work *work, int cu_count, hipStream_t st) {
-    const int grid = cu_count * knobs().fwd_bpc;
-    const int tab = a.fmi.cp2 ? a.fmi.tab_kind : 0;
-    if (!work) {
-        if (tab == 2) smem_fwd_kernel<true, 2><<<grid, kBlock, lds_bytes(a), st>>>(a, nullptr);
-        else if (tab == 1) smem_fwd_kernel<true, 1><<<grid, kBlock, lds_bytes(a), st>>>(a, nullptr);
-        else smem_fwd_kernel<true, 0><<<grid, kBlock, lds_bytes(a), st>>>(a, nullptr);
-    } else {
-        if (tab == 2) smem_fwd_kernel<false, 2><<<grid, kBlock, lds_bytes(a), st>>>(a, work);
-        else if (tab == 1) smem_fwd_kernel<false, 1><<<grid, kBlock, lds_bytes(a), st>>>(a, work);
-        else smem_fwd_kernel<false, 0><<<grid, kBlock, lds_bytes(a), st>>>(a, work);
-    }
-}
-
-void launch_smem_bwdl(const SeedLaunch &a, int cu_count, hipStream_t st) {
-    const size_t lds = lds_bytes(a) + (size_t)kPrevLds * kBlock * 16;
-    const int tab = a.fmi.cp2 ? a.fmi.tab_kind : 0;
-    if (tab == 2) smem_bwdl_kernel<2><<<cu_count * knobs().bwdl_bpc, kBlock, lds, st>>>(a);
-    else if (tab == 1) smem_bwdl_kernel<1><<<cu_count * knobs().bwdl_bpc, kBlock, lds, st>>>(a);
-    else smem_bwdl_kernel<0><<<cu_count * knobs().bwdl_bpc, kBlock, lds, st>>>(a);
+    smem_search_kernel<false><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes_search(a), st>>>(a, work);
 }
 
 void launch_smem_bwd_wave(const SeedLaunch &a, int cu_count, hipStream_t st) {
     if (a.bwd_min_list <= 0) return;
     // the number of items is only known on the device; waves without an item leave at their first ticket
     const size_t lds = (size_t)(kBlock / 64) * (kBwdMaxList * 16 + 16 * (size_t)(a.read_w <= kBwdReadLds ? a.read_w : 0));
-    const size_t lds_g = lds;
-    const bool fused = knobs().bwd_fused != 0;
-    const int tab = a.fmi.cp2 ? a.fmi.tab_kind : 0;
-    if (fused) {
-        if (tab == 2) smem_bwd_kernel<2><<<cu_count * 8, kBlock, lds > lds_g ? lds : lds_g, st>>>(a);
-        else if (tab == 1) smem_bwd_kernel<1><<<cu_count * 8, kBlock, lds > lds_g ? lds : lds_g, st>>>(a);
-        else smem_bwd_kernel<0><<<cu_count * 8, kBlock, lds > lds_g ? lds : lds_g, st>>>(a);
-    } else if (tab == 2) {                     // (A-B switch: the two roles as two launches)
-        smem_bwd_role_kernel<0, 2><<<cu_count * 8, kBlock, lds, st>>>(a);
-        smem_bwd_role_kernel<1, 2><<<cu_count * 8, kBlock, lds_g, st>>>(a);
-    } else {
-        smem_bwd_role_kernel<0, 0><<<cu_count * 8, kBlock, lds, st>>>(a);
-        smem_bwd_role_kernel<1, 0><<<cu_count * 8, kBlock, lds_g, st>>>(a);
-    }
+    smem_bwd_kernel<<<cu_count * 8, kBlock, lds, st>>>(a);
 }
 
 void launch_smem_round3(const SeedLaunch &a, int max_intv, int cu_count, hipStream_t st) {
-    const int tab = a.fmi.cp2 ? a.fmi.tab_kind : 0;
-    if (tab == 2) seed_strategy_kernel<2><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes(a), st>>>(a, max_intv);
-    else if (tab == 1) seed_strategy_kernel<1><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes(a), st>>>(a, max_intv);
-    else seed_strategy_kernel<0><<<grid_for(a.nseq, cu_count), kBlock, lds_bytes(a), st>>>(a, max_intv);
+    seed_strategy_kernel<<<grid_for(a.nseq, cu_count), kBlock, lds_bytes(a), st>>>(a, max_intv);
 }
 
 void launch_make_keys(const bwams_smem_t *pool, int64_t n, uint64_t *keys, uint32_t *vals, uint32_t hole_key_rid,

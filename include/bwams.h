@@ -48,7 +48,7 @@ const char *bwams_last_error(void);
  *   BWAMS_VERBOSE=1 stage times / counters on stderr    BWAMS_POISON=1 fresh device allocations filled with 0xAB
  *   BWAMS_BWD_MIN_LIST / _COLS / _LATE_LIST, BWAMS_BWD_DRY_MIN_LIST / _DRY_COLS / _DRY_LATE_LIST  when a backward phase of the SMEM search
  *     leaves its lane (entries at the forward end; columns run and entries alive; the same once the read queue is dry; MIN_LIST=0: never)
- *   BWAMS_BWD_FUSED=0, BWAMS_BWD_CAP_MUL, BWAMS_SEED_R3_BESIDE=0, BWAMS_DEBUG   SMEM search launch variants / ablations
+ *   BWAMS_SEED_R3_BESIDE=0 (SMEM round 3 behind round 2 instead of beside it), BWAMS_DEBUG (SMEM search ablations)
  *   BWAMS_EXT_MAX_ROUNDS, BWAMS_EXT_ALL_ROUNDS, BWAMS_EXT_INPLACE=0, BWAMS_BSW_PK=0, BWAMS_CHAIN_BATCH=0   extension rounds and kernel variants
  *   BWAMS_DEDUP_SEQ=1, BWAMS_PAIR_DROP_PLAN, BWAMS_TRACE_PAIR   fallback paths forced by tests; a line per launch of the paired-end tail
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */

@@ -172,10 +172,10 @@ def test_resident_buffers_grow_on_demand(gpu_toy):
     b.close()
 
 
-@pytest.mark.parametrize("mode", ["0", "1", "2"])
-def test_round3_behind_beside_or_from_the_start(gpu_toy, monkeypatch, mode):
-    """BWAMS_SEED_R3_BESIDE: round 3 behind round 2 (0), beside it (1), or from the start of the stage with a pool and counters of its
-    own, appended behind round 2's records (2): schedules, not algorithms — the same SMEMs, coordinates and counts."""
+@pytest.mark.parametrize("mode", ["0", "1"])
+def test_round3_behind_or_beside(gpu_toy, monkeypatch, mode):
+    """BWAMS_SEED_R3_BESIDE: round 3 behind round 2 (0) or beside it on a stream of its own (1): schedules, not algorithms — the
+    same SMEMs, coordinates and counts."""
     g, idx, ix = gpu_toy
     monkeypatch.setenv("BWAMS_SEED_R3_BESIDE", mode)
     capi.debug_reload()
