@@ -35,6 +35,7 @@ SYMBOLS = [
     "bwams_bsw_extend", "bwams_bsw_upload", "bwams_bsw_run", "bwams_bsw_fetch",
     "bwams_batch_stats", "bwams_batch_sync", "bwams_ksw_align",
     "bwams_index_build_fma", "bwams_index_set_fma", "bwams_index_fetch_fma",
+    "bwams_index_from_fasta", "bwams_index_from_fasta_file", "bwams_index_load_bns",
     "bwams_emf_open", "bwams_emf_from_host", "bwams_emf_close", "bwams_emf_probe",
     "bwams_emf_from_device", "bwams_emf_run", "bwams_emf_fetch",
     "bwams_index_set_contigs", "bwams_chain_run", "bwams_chain_fetch", "bwams_chain_upload",
@@ -183,6 +184,12 @@ class BuildStats(C.Structure):
                 ("ms_first_pass", C.c_float), ("ms_outputs", C.c_float)]
 
 
+class FastaStats(C.Structure):
+    _fields_ = [("l_pac", C.c_int64), ("n_seqs", C.c_int32), ("n_holes", C.c_int32), ("n_ambig_bases", C.c_int64),
+                ("ms_host_read", C.c_float), ("ms_upload", C.c_float), ("ms_device_pack", C.c_float), ("ms_fm_build", C.c_float),
+                ("build", BuildStats)]
+
+
 def pestat_from_keys(keys) -> np.ndarray:
     """mem_pestat's arithmetic over the insert-size keys of a whole chunk (host only; keys in any order)."""
     keys = np.ascontiguousarray(keys, np.uint64)
@@ -256,6 +263,9 @@ def lib():
         L.bwams_index_build.argtypes = [vp, i64, C.c_int, C.c_int, C.c_int, i64, vp, vp]
         L.bwams_index_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
         L.bwams_index_save.argtypes = [vp, C.c_char_p]
+        L.bwams_index_from_fasta.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, i64, vp, vp]
+        L.bwams_index_from_fasta_file.argtypes = [C.c_char_p, C.c_int, C.c_int, i64, vp, vp]
+        L.bwams_index_load_bns.argtypes = [vp, C.c_char_p]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
@@ -385,6 +395,39 @@ class Index:
         ix = cls(h)
         ix.build_stats = st
         return ix
+
+    @classmethod
+    def from_fasta(cls, text, device: int = 0, keep_ref: bool = True, chunk_rows: int = 0) -> "Index":
+        """bns_fasta2bntseq + the FM-index build on the GPU (bwams_index_from_fasta).  text: FASTA bytes, or a torch uint8 tensor
+        already on `device`.  The handle carries its contigs, names and annotations and writes .ann / .amb / .pac on save."""
+        h = C.c_void_p()
+        st = FastaStats()
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            t = bytes(text)
+            _chk(lib().bwams_index_from_fasta(device, t, len(t), 0, int(keep_ref), chunk_rows, C.byref(st), C.byref(h)),
+                 "bwams_index_from_fasta")
+        else:
+            t = text.contiguous()
+            _chk(lib().bwams_index_from_fasta(device, t.data_ptr(), t.numel(), 1, int(keep_ref), chunk_rows, C.byref(st), C.byref(h)),
+                 "bwams_index_from_fasta")
+        ix = cls(h)
+        ix.fasta_stats = st
+        return ix
+
+    @classmethod
+    def from_fasta_file(cls, path: str, device: int = 0, keep_ref: bool = True, chunk_rows: int = 0) -> "Index":
+        """The same from a plain or gzip FASTA file (bwams_index_from_fasta_file)."""
+        h = C.c_void_p()
+        st = FastaStats()
+        _chk(lib().bwams_index_from_fasta_file(path.encode(), device, int(keep_ref), chunk_rows, C.byref(st), C.byref(h)),
+             "bwams_index_from_fasta_file")
+        ix = cls(h)
+        ix.fasta_stats = st
+        return ix
+
+    def load_bns(self, prefix: str):
+        """bns_restore onto this handle: contigs (with .alt flags), names and annotations from <prefix>.ann / .amb / .alt."""
+        _chk(lib().bwams_index_load_bns(self.h, prefix.encode()), "bwams_index_load_bns")
 
     def fetch(self, with_ref: bool = True):
         """The resident arrays as a bwams.fmindex.FMIndex of numpy arrays (for the file writer / the CPU oracle)."""

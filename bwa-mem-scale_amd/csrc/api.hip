@@ -369,11 +369,13 @@ int bwams_index_save(bwams_index_t *ix, const char *prefix) {
         }
     }
     if (rc == BWAMS_ERR_IO) set_last_error("write failed: " + path);
+    if (!rc && ix->bns) rc = bns_save(ix, prefix);
     return rc;
 }
 
 int bwams_index_close(bwams_index_t *ix) {
     if (!ix) return BWAMS_OK;
+    bns_free(ix);
     if (ix->d_cp2) { (void)hipSetDevice(ix->device); (void)hipFree(ix->d_cp2); ix->d_cp2 = nullptr; }
     if (ix->owns) {
         (void)hipSetDevice(ix->device);

@@ -181,6 +181,21 @@ int launch_ksw(const bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, cons
 // read input helpers shared with the outer boundary (fastq.hip)
 struct SegMove { const char *src; char *dst; int64_t len; };     // one contiguous piece of device memory to copy
 int segment_copy(const std::vector<SegMove> &moves, hipStream_t st);
+// positions of the '\n' bytes of d_text[0, n_bytes) in HBM (rocPRIM select over a counting iterator, sized by a count first);
+// *ends (n_nl + 16 slots) is the caller's to free
+int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, int64_t **ends, int64_t *n_nl);
+
+// The reference metadata of an index made from FASTA (fasta_ref.hip): what bns_fasta2bntseq keeps and bns_dump writes.
+struct BnsMeta {
+    int64_t l_pac = 0;
+    std::vector<std::string> names, comments;           // comments: kseq's, empty = none (add1 stores "(null)")
+    std::vector<int64_t> ctg_off;
+    std::vector<int32_t> ctg_len, ctg_ambs;
+    std::vector<int64_t> hole_off;                       // bntamb1_t: offset, len, amb
+    std::vector<int32_t> hole_len;
+    std::vector<char> hole_amb;
+    void *d_pac = nullptr;                               // the 2-bit .pac, ceil(l_pac / 4) bytes in HBM (owned)
+};
 }  // namespace bwams
 struct bwams_fastq;
 namespace bwams {
@@ -203,7 +218,13 @@ struct bwams_index {
     int32_t n_seqs = 0;
     void *d_ctg_annos = nullptr, *d_ctg_anno_off = nullptr;   // bntann1_t.anno for MEM_F_REF_HDR (bwams_index_set_contig_annos)
     void *d_ctg_names = nullptr, *d_ctg_off = nullptr;   // sequence names for the SAM text (bwams_index_set_contig_names)
+    bwams::BnsMeta *bns = nullptr;               // .ann / .amb / .pac of an index made from FASTA (bwams_index_from_fasta), else null
 };
+
+namespace bwams {
+int bns_save(bwams_index *ix, const char *prefix);     // fasta_ref.hip: writes <prefix>.ann, .amb, .pac
+void bns_free(bwams_index *ix);
+}
 
 namespace bwams {
 int bsw_list_ensure(bwams_batch *b, int64_t n_tasks);   // grows b->d_bsw_list (synchronises the stream when it must reallocate)

@@ -404,6 +404,38 @@ __global__ __launch_bounds__(256) void fq_wrapped_emit_kernel(const char *__rest
 using namespace bwams;
 
 namespace bwams {
+int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, int64_t **ends, int64_t *n_nl) {
+    *ends = nullptr;
+    *n_nl = 0;
+    if (n_bytes <= 0) return BWAMS_OK;
+    int64_t *d_ends = nullptr, *d_cnt = nullptr;
+    void *d_tmp = nullptr;
+    struct Free {
+        void **p[2];
+        ~Free() { for (auto q : p) if (*q) (void)hipFree(*q); }
+    } fr{{reinterpret_cast<void **>(&d_cnt), &d_tmp}};
+    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_cnt), 64));
+    // count first: the array of line ends is sized exactly
+    BWAMS_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
+    fastq_count_kernel<<<256 * 8, 256, 0, st>>>(d_text, n_bytes, reinterpret_cast<unsigned long long *>(d_cnt));
+    int64_t n = 0;
+    BWAMS_HIP(hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    size_t tb = 0;
+    rocprim::counting_iterator<int64_t> it(0);
+    IsLineEnd pred{d_text};
+    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_ends), (size_t)(n + 16) * 8));
+    hipError_t e = rocprim::select(nullptr, tb, it, d_ends, d_cnt, (size_t)n_bytes, pred, st);
+    if (e == hipSuccess) e = dev_malloc(&d_tmp, tb + 16);
+    if (e == hipSuccess) e = rocprim::select(d_tmp, tb, it, d_ends, d_cnt, (size_t)n_bytes, pred, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(d_ends); BWAMS_HIP(e); }
+    *ends = d_ends;
+    *n_nl = n;
+    return BWAMS_OK;
+}
+
 int segment_copy(const std::vector<SegMove> &moves, hipStream_t st) {
     if (moves.empty()) return BWAMS_OK;
     SegMove *d = nullptr;
@@ -569,24 +601,10 @@ int bwams_fastq_decode(int device, const char *text, int64_t n_bytes, bwams_fast
     int64_t n_nl = 0;
     char last = '\n';
     if (n_bytes) {
-        // count first: the array of line ends is sized exactly
-        BWAMS_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
-        fastq_count_kernel<<<256 * 8, 256, 0, st>>>(d_text, n_bytes, reinterpret_cast<unsigned long long *>(d_cnt));
-        BWAMS_HIP(hipMemcpyAsync(&n_nl, d_cnt, 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
-        size_t tb = 0;
-        rocprim::counting_iterator<int64_t> it(0);
-        IsLineEnd pred{d_text};
-        BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_ends), (size_t)(n_nl + 16) * 8)); scr.p.push_back(d_ends);
-        BWAMS_HIP(rocprim::select(nullptr, tb, it, d_ends, d_cnt, (size_t)n_bytes, pred, st));
-        void *d_tmp = nullptr;
-        BWAMS_HIP(dev_malloc(&d_tmp, tb + 16)); scr.p.push_back(d_tmp);
-        std::vector<char> tail(1);
-        BWAMS_HIP(hipMemcpy(tail.data(), d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost));
-        last = tail[0];
-        BWAMS_HIP(rocprim::select(d_tmp, tb, it, d_ends, d_cnt, (size_t)n_bytes, pred, st));
-        BWAMS_HIP(hipMemcpyAsync(&n_nl, d_cnt, 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
+        int rc = line_ends(d_text, n_bytes, st, &d_ends, &n_nl);
+        if (rc) return rc;
+        scr.p.push_back(d_ends);
+        BWAMS_HIP(hipMemcpy(&last, d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost));
     }
     const int64_t n_lines = n_nl + (n_bytes && last != '\n' ? 1 : 0);
     char first = '@';

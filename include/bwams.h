@@ -113,8 +113,37 @@ int bwams_index_build(const uint8_t *fw, int64_t l_pac, int fw_on_device, int de
 int bwams_index_fetch(bwams_index_t *idx, bwams_cp_occ_t *cp_occ, int8_t *sa_ms_byte, uint32_t *sa_ls_word,
                       uint8_t *ref_0123, bwams_fmi_desc_t *desc);
 /* Writes <prefix>.bwt.2bit.64 (and <prefix>.0123 when the index holds the text) in the reference's format
- * (src/FMI_search.cpp:629-763, :796-829), streaming from HBM. */
+ * (src/FMI_search.cpp:629-763, :796-829), streaming from HBM; on a handle from bwams_index_from_fasta also <prefix>.ann, .amb
+ * and .pac (bns_dump and bns_fasta2bntseq's .pac, src/bntseq.cpp:83-112, :356-366). */
 int bwams_index_save(bwams_index_t *idx, const char *prefix);
+
+/* Indexing a reference FASTA on the GPU.  Replaces bns_fasta2bntseq (src/bntseq.cpp:269-372) + FMI_search::build_index as
+ * bwa_idx_build_mem2 chains them (src/bwtindex.cpp:377-394): the text (plain FASTA, in host memory or — text_on_device != 0 — in
+ * this GPU's memory) is parsed as kseq_read parses it, every base code >= 4 becomes lrand48() & 3 after srand48(11) in global base
+ * order, and the 2-bit codes go to bwams_index_build's builder without leaving HBM.  The handle carries its sequences as
+ * bwams_index_set_contigs / _set_contig_names / _set_contig_annos would set them (annotations as bns_restore reads them back), and
+ * the .ann / .amb / .pac content, which bwams_index_save then writes besides .bwt.2bit.64 and .0123 — byte for byte what
+ * `bwa-mem2.scale index` writes.  Refused: a line starting with '+' (FASTQ) and a sequence over INT32_MAX bases
+ * (BWAMS_ERR_UNSUPPORTED); text without a '>' / '@' header or without bases (BWAMS_ERR_ARG).  No handle is left on an error. */
+typedef struct bwams_fasta_stats {
+    int64_t l_pac;                     /* bases of the forward strand */
+    int32_t n_seqs, n_holes;           /* sequences; runs of one ambiguous byte (the .amb records) */
+    int64_t n_ambig_bases;             /* bases with an nst_nt4_table code >= 4 (each took one lrand48 draw) */
+    float ms_host_read;                /* file read and inflate (bwams_index_from_fasta_file; 0 otherwise) */
+    float ms_upload;                   /* host text to HBM (0 when the text was already on the device) */
+    float ms_device_pack;              /* text in HBM -> codes, .pac and holes, headers to the host */
+    float ms_fm_build;                 /* the FM-index build from the codes */
+    bwams_build_stats_t build;
+} bwams_fasta_stats_t;
+int bwams_index_from_fasta(int device, const char *text, int64_t n_bytes, int text_on_device, int keep_ref, int64_t chunk_rows,
+                           bwams_fasta_stats_t *stats, bwams_index_t **out);
+/* The same from a plain or gzip file (zlib, inflated into page-locked memory). */
+int bwams_index_from_fasta_file(const char *path, int device, int keep_ref, int64_t chunk_rows, bwams_fasta_stats_t *stats,
+                                bwams_index_t **out);
+/* bns_restore (src/bntseq.cpp:114-246) onto a handle, e.g. one from bwams_index_open: reads <prefix>.ann, checks the .amb header
+ * against it (a mismatched pair is BWAMS_ERR_IO), reads <prefix>.alt when present, and sets the sequences (with is_alt), their
+ * names and annotations.  The .ann must describe the index's l_pac (BWAMS_ERR_ARG otherwise). */
+int bwams_index_load_bns(bwams_index_t *idx, const char *prefix);
 
 int bwams_index_close(bwams_index_t *idx);
 int64_t bwams_index_bytes(const bwams_index_t *idx);
