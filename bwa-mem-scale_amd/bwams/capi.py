@@ -42,6 +42,7 @@ SYMBOLS = [
     "bwams_extend_build", "bwams_extend_run", "bwams_extend_fetch", "bwams_extend_tasks_fetch",
     "bwams_process_reads", "bwams_process_reads_stage1", "bwams_process_reads_stage2", "bwams_host_alloc", "bwams_host_free",
     "bwams_reader_open", "bwams_reader_next", "bwams_reader_release", "bwams_reader_error", "bwams_reader_close",
+    "bwams_inflater_create", "bwams_inflater_run", "bwams_inflater_destroy", "bwams_reader_open_device", "bwams_reader_info",
     "bwams_writer_open", "bwams_writer_put", "bwams_writer_close",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
@@ -190,6 +191,69 @@ class FastaStats(C.Structure):
                 ("build", BuildStats)]
 
 
+class InflateStats(C.Structure):
+    _fields_ = [("members", C.c_int64), ("in_bytes", C.c_int64), ("out_bytes", C.c_int64),
+                ("ms_upload", C.c_float), ("ms_kernel", C.c_float), ("ms_download", C.c_float)]
+
+
+class ReaderStats(C.Structure):
+    _fields_ = [("device_inflate", C.c_int32), ("in_bytes", C.c_int64), ("out_bytes", C.c_int64),
+                ("ms_read", C.c_float), ("ms_inflate", C.c_float)]
+
+
+class Inflater:
+    """BGZF inflated on one GPU (bwams_inflater_t)."""
+
+    def __init__(self, device: int = 0, max_in_bytes: int = 32 << 20, max_out_bytes: int = 64 << 20):
+        self.h = C.c_void_p()
+        self.max_out = max_out_bytes
+        _chk(lib().bwams_inflater_create(device, max_in_bytes, max_out_bytes, C.byref(self.h)), "bwams_inflater_create")
+
+    def run_raw(self, gz, out, out_cap: int, on_device: bool):
+        """bwams_inflater_run as is: gz bytes (or an address with its length as (addr, n)), out an address.  Returns
+        (rc, n_consumed, n_out, InflateStats)."""
+        used, n_out, st = C.c_int64(0), C.c_int64(0), InflateStats()
+        ptr, n = (C.c_void_p(gz[0]), gz[1]) if isinstance(gz, tuple) else (gz, len(gz))
+        rc = lib().bwams_inflater_run(self.h, ptr, n, C.c_void_p(out), out_cap, int(on_device), C.byref(used), C.byref(n_out),
+                                      C.byref(st))
+        return rc, used.value, n_out.value, st
+
+    def run(self, gz: bytes, out_cap: int | None = None):
+        """The whole members at the front of gz, inflated to host memory (out_cap: default max_out_bytes): (text bytes, n_consumed,
+        InflateStats)."""
+        cap = out_cap if out_cap is not None else self.max_out
+        buf = C.create_string_buffer(max(cap, 1))
+        rc, used, n, st = self.run_raw(gz, C.addressof(buf), cap, False)
+        _chk(rc, "bwams_inflater_run")
+        return buf.raw[:n], used, st
+
+    def close(self):
+        if self.h:
+            lib().bwams_inflater_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def reader_open_device(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0,
+                       n_buffers: int = 2) -> C.c_void_p:
+    """bwams_reader_open_device: a bwams_reader_t handle (bwams_reader_next / _release / _close as for bwams_reader_open)."""
+    r = C.c_void_p()
+    _chk(lib().bwams_reader_open_device(path.encode(), device, chunk_bases, int(paired), buffer_bytes, n_buffers, C.byref(r)),
+         "bwams_reader_open_device")
+    return r
+
+
+def reader_info(r) -> ReaderStats:
+    st = ReaderStats()
+    _chk(lib().bwams_reader_info(r, C.byref(st)), "bwams_reader_info")
+    return st
+
+
 def pestat_from_keys(keys) -> np.ndarray:
     """mem_pestat's arithmetic over the insert-size keys of a whole chunk (host only; keys in any order)."""
     keys = np.ascontiguousarray(keys, np.uint64)
@@ -266,6 +330,11 @@ def lib():
         L.bwams_index_from_fasta.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, i64, vp, vp]
         L.bwams_index_from_fasta_file.argtypes = [C.c_char_p, C.c_int, C.c_int, i64, vp, vp]
         L.bwams_index_load_bns.argtypes = [vp, C.c_char_p]
+        L.bwams_inflater_create.argtypes = [C.c_int, i64, i64, vp]
+        L.bwams_inflater_run.argtypes = [vp, vp, i64, vp, i64, C.c_int, vp, vp, vp]
+        L.bwams_inflater_destroy.argtypes = [vp]
+        L.bwams_reader_open_device.argtypes = [C.c_char_p, C.c_int, i64, i32, i64, i32, vp]
+        L.bwams_reader_info.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]

@@ -1,0 +1,559 @@
+// inflate.hip — BGZF input inflated on the device: RFC 1951 DEFLATE, one wave per member.
+//
+// Replaces the gzread() behind kseq (the reference inflates every compressed input with zlib on one thread) for BGZF files, the
+// blocked gzip of SAMv1 §4.1: a chain of independent gzip members, each at most 64 KiB in and out, whose header carries the member's
+// compressed size (the 'BC' extra subfield).  The host walks that header chain (O(members), ~26 bytes read per 64 KiB), reads BSIZE,
+// CRC32 and ISIZE, and gives every member its output offset by an exclusive scan of the ISIZEs.  The device does the rest.
+//
+// Mapping.  One 64-lane workgroup per member, every lane running the same decoder on the same (wave-uniform) state:
+//   * the member's compressed bytes come through a 4 KiB LDS window that the 64 lanes reload together; the bit buffer is 64 bits;
+//   * its output is built in a 64 KiB LDS buffer (a member never inflates to more), so back-references read LDS only;
+//   * code tables are built in LDS by all lanes: a first-level table of 2^10 (literal/length) or 2^8 (distance) entries, and for the
+//     rare longer code the canonical count/symbol walk; validity follows zlib's inflate_table (over-subscribed and incomplete codes
+//     refused, except the single code of length 1; symbols 286/287 and distances 30/31 refused when decoded);
+//   * a literal is one lane's LDS byte store; a match is copied 64 bytes per step (an overlap, distance < length, reads i % distance);
+//   * CRC32 is wave-parallel: a lane per 1/64 of the output with a byte table in LDS, the lanes' remainders joined by x^(8n) mod P;
+//   * only a member whose CRC32 and ISIZE check out is written to HBM, in dwords, inside [out_off, out_off + ISIZE).
+// Every read stays inside the member's input range (bytes past it read as 0 and count as an overrun) and every write inside its
+// output range, so damaged input gives a status per member, never a fault.  LDS ~73 KiB: two members per CU.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+using namespace bwams;
+
+namespace {
+
+constexpr int kOutMax = 65536;           // a BGZF member inflates to at most 64 KiB
+constexpr int kInWin = 4096;             // LDS window over the member's compressed bytes
+constexpr int kLRoot = 10, kDRoot = 8;   // first-level table bits: literal/length, distance
+constexpr uint32_t kPoly = 0xEDB88320u;  // CRC-32 (reflected)
+
+struct Member {                          // one BGZF member as the kernel sees it (32 bytes)
+    int64_t in_off;                      // its DEFLATE data in the input buffer
+    int64_t out_off;                     // where its ISIZE bytes go
+    int32_t in_len, isize;
+    uint32_t crc;
+    int32_t pad_;
+};
+
+enum Status : int32_t {
+    ST_OK = 0, ST_BTYPE, ST_STORED_LEN, ST_COUNTS, ST_CODE_LENS, ST_REPEAT, ST_NO_EOB, ST_OVERSUB, ST_INCOMPLETE, ST_BAD_LITLEN,
+    ST_BAD_DIST, ST_FAR, ST_OVERFLOW, ST_OVERRUN, ST_TRAILING, ST_ISIZE, ST_CRC,
+};
+
+const char *status_text(int s) {
+    switch (s) {
+        case ST_BTYPE: return "invalid block type";
+        case ST_STORED_LEN: return "stored block LEN is not ~NLEN";
+        case ST_COUNTS: return "too many length or distance symbols";
+        case ST_CODE_LENS: return "invalid code lengths code";
+        case ST_REPEAT: return "invalid bit length repeat";
+        case ST_NO_EOB: return "missing end-of-block code";
+        case ST_OVERSUB: return "over-subscribed Huffman code";
+        case ST_INCOMPLETE: return "incomplete Huffman code";
+        case ST_BAD_LITLEN: return "invalid literal/length code";
+        case ST_BAD_DIST: return "invalid distance code";
+        case ST_FAR: return "distance too far back";
+        case ST_OVERFLOW: return "more output than ISIZE";
+        case ST_OVERRUN: return "DEFLATE data runs past the member";
+        case ST_TRAILING: return "bytes between the end of the DEFLATE data and the trailer";
+        case ST_ISIZE: return "ISIZE does not match the inflated size";
+        case ST_CRC: return "CRC32 mismatch";
+    }
+    return "unknown status";
+}
+
+__constant__ uint16_t kLenBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131,
+                                      163, 195, 227, 258};
+__constant__ uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+__constant__ uint16_t kDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537,
+                                       2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+__constant__ uint8_t kDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+__constant__ uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+// A canonical Huffman code in LDS: cnt[len], the symbols sorted by (length, value), the first-level table (entry = symbol | len << 9;
+// len 0: the code is longer than the table's bits, or no code has that prefix).
+struct Code {
+    uint16_t *tab, *cnt, *sym;
+    int root;
+};
+
+struct Lds {
+    uint8_t out[kOutMax];
+    uint8_t in[kInWin];
+    uint16_t ltab[1 << kLRoot], dtab[1 << kDRoot];
+    uint16_t lsym[288], dsym[32], lcnt[16], dcnt[16], off[16], next[16];
+    uint8_t lens[320];
+    uint32_t crc_tab[256], part[64];
+};
+
+// The bit reader: wave-uniform.  ip: next byte of the member's data to enter bb; [base, base + kInWin) is in the LDS window.
+struct Bits {
+    uint64_t bb;
+    int bc, ip, base;
+};
+
+__device__ __forceinline__ void window_load(Lds &s, const uint8_t *__restrict__ in, int in_len, int base, int lane) {
+    __syncthreads();
+    for (int j = lane; j < kInWin; j += 64) s.in[j] = base + j < in_len ? in[base + j] : 0;
+    __syncthreads();
+}
+
+// at least 57 bits in bb
+__device__ __forceinline__ void refill(Bits &b, Lds &s, const uint8_t *__restrict__ in, int in_len, int lane) {
+    while (b.bc <= 56) {
+        if (b.ip - b.base >= kInWin) {
+            b.base = b.ip;
+            window_load(s, in, in_len, b.base, lane);
+        }
+        b.bb |= (uint64_t)s.in[b.ip - b.base] << b.bc;
+        b.bc += 8;
+        ++b.ip;
+    }
+}
+
+__device__ __forceinline__ uint32_t take(Bits &b, int n) {
+    const uint32_t v = (uint32_t)(b.bb & ((1ull << n) - 1));
+    b.bb >>= n;
+    b.bc -= n;
+    return v;
+}
+
+// one symbol (needs 15 bits in bb); -1: no code of this code has that bit string
+__device__ __forceinline__ int decode(Bits &b, const Code &c) {
+    const uint32_t e = c.tab[b.bb & ((1u << c.root) - 1)];
+    if (e >> 9) {
+        take(b, (int)(e >> 9));
+        return (int)(e & 511);
+    }
+    uint64_t bits = b.bb;                             // canonical walk, one bit at a time (codes longer than the table's bits)
+    int code = 0, first = 0, index = 0;
+    for (int len = 1; len <= 15; ++len) {
+        code |= (int)(bits & 1);
+        bits >>= 1;
+        const int count = c.cnt[len];
+        if (code - count < first) {
+            take(b, len);
+            return c.sym[index + (code - first)];
+        }
+        index += count;
+        first = (first + count) << 1;
+        code <<= 1;
+    }
+    return -1;
+}
+
+// the code of lens[0, n) into c; `cl`: the code lengths code (an incomplete code is refused even with one code of length 1)
+__device__ int build(Lds &s, const uint8_t *lens, int n, const Code &c, bool cl, int lane) {
+    __syncthreads();
+    for (int i = lane; i < (1 << c.root); i += 64) c.tab[i] = 0;
+    int k = 0;
+    if (lane < 16)
+        for (int i = 0; i < n; ++i) k += lens[i] == lane;
+    if (lane < 16) c.cnt[lane] = (uint16_t)(lane ? k : 0);
+    __syncthreads();
+    int left = 1, max = 0, code = 0, off = 0;
+    for (int len = 1; len <= 15; ++len) {
+        const int m = c.cnt[len];
+        left = (left << 1) - m;
+        if (left < 0) return ST_OVERSUB;
+        if (m) max = len;
+        code = (code + (len > 1 ? c.cnt[len - 1] : 0)) << 1;
+        if (lane == len) { s.off[len] = (uint16_t)off; s.next[len] = (uint16_t)code; }
+        off += m;
+    }
+    if (max == 0) return ST_OK;                       // no symbols at all (zlib accepts it; any decode then fails)
+    if (left > 0 && (cl || max != 1)) return ST_INCOMPLETE;
+    __syncthreads();
+    if (lane >= 1 && lane < 16) {                     // lane = length: its symbols in value order
+        int at = s.off[lane];
+        for (int i = 0; i < n; ++i)
+            if (lens[i] == lane) c.sym[at++] = (uint16_t)i;
+    }
+    __syncthreads();
+    for (int i = lane; i < off; i += 64) {            // every code that fits the table: all its entries
+        int len = 1;
+        while (len < 15 && i >= s.off[len] + c.cnt[len]) ++len;
+        if (len > c.root) continue;
+        const uint32_t cd = s.next[len] + (uint32_t)(i - s.off[len]);
+        const uint32_t rev = __builtin_bitreverse32(cd) >> (32 - len);
+        const uint16_t e = (uint16_t)(c.sym[i] | len << 9);
+        for (uint32_t j = rev; j < (1u << c.root); j += 1u << len) c.tab[j] = e;
+    }
+    __syncthreads();
+    return ST_OK;
+}
+
+__device__ __forceinline__ uint32_t gf2_mul(uint32_t a, uint32_t b) {     // a * b mod P (reflected: bit 31 is x^0)
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b & 1) ? (b >> 1) ^ kPoly : b >> 1;
+    }
+    return p;
+}
+
+__device__ uint32_t x8n(uint32_t n) {                // x^(8n) mod P
+    uint32_t sq = 0x40000000u, r = 0x80000000u;      // x^1, x^0
+    for (int i = 0; i < 3; ++i) sq = gf2_mul(sq, sq);  // x^8
+    for (; n; n >>= 1) {
+        if (n & 1) r = gf2_mul(r, sq);
+        sq = gf2_mul(sq, sq);
+    }
+    return r;
+}
+
+__device__ int inflate_member(Lds &s, const uint8_t *__restrict__ in, int in_len, int isize, int lane) {
+    Bits b{0, 0, 0, 0};
+    window_load(s, in, in_len, 0, lane);
+    const Code lc{s.ltab, s.lcnt, s.lsym, kLRoot}, dc{s.dtab, s.dcnt, s.dsym, kDRoot}, cc{s.ltab, s.lcnt, s.lsym, 7};
+    int pos = 0, last = 0;
+    while (!last) {
+        refill(b, s, in, in_len, lane);
+        if ((int64_t)b.ip * 8 - b.bc > (int64_t)in_len * 8) return ST_OVERRUN;
+        last = (int)take(b, 1);
+        const int type = (int)take(b, 2);
+        if (type == 0) {                              // stored
+            take(b, b.bc & 7);
+            const uint32_t len = take(b, 16), nlen = take(b, 16);
+            if (len != (~nlen & 0xffffu)) return ST_STORED_LEN;
+            const int p = b.ip - b.bc / 8;            // the byte behind NLEN
+            if (p + (int)len > in_len) return ST_OVERRUN;
+            if (pos + (int)len > isize) return ST_OVERFLOW;
+            __syncthreads();
+            for (int i = lane; i < (int)len; i += 64) s.out[pos + i] = in[p + i];
+            pos += (int)len;
+            b.bb = 0; b.bc = 0; b.ip = p + (int)len;
+            continue;
+        }
+        if (type == 3) return ST_BTYPE;
+        int rc;
+        if (type == 1) {                              // fixed codes
+            __syncthreads();
+            for (int i = lane; i < 320; i += 64) s.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5;
+            if ((rc = build(s, s.lens, 288, lc, false, lane))) return rc;
+            if ((rc = build(s, s.lens + 288, 32, dc, false, lane))) return rc;
+        } else {                                      // dynamic codes
+            const int nlen = (int)take(b, 5) + 257, ndist = (int)take(b, 5) + 1, ncode = (int)take(b, 4) + 4;
+            if (nlen > 286 || ndist > 30) return ST_COUNTS;
+            refill(b, s, in, in_len, lane);
+            __syncthreads();
+            if (lane < 19) s.lens[lane] = 0;
+            __syncthreads();
+            for (int i = 0; i < ncode; ++i) {
+                const uint8_t v = (uint8_t)take(b, 3);
+                if (lane == 0) s.lens[kClOrder[i]] = v;
+            }
+            if (build(s, s.lens, 19, cc, true, lane)) return ST_CODE_LENS;
+            int n = 0, prev = 0;
+            while (n < nlen + ndist) {
+                if (b.bc < 32) refill(b, s, in, in_len, lane);
+                if ((int64_t)b.ip * 8 - b.bc > (int64_t)in_len * 8) return ST_OVERRUN;
+                const int sym = decode(b, cc);
+                if (sym < 0) return ST_CODE_LENS;
+                if (sym < 16) {
+                    if (lane == 0) s.lens[n] = (uint8_t)sym;
+                    prev = sym;
+                    ++n;
+                    continue;
+                }
+                int v, rep;
+                if (sym == 16) {
+                    if (n == 0) return ST_REPEAT;
+                    v = prev; rep = 3 + (int)take(b, 2);
+                } else if (sym == 17) {
+                    v = 0; rep = 3 + (int)take(b, 3);
+                } else {
+                    v = 0; rep = 11 + (int)take(b, 7);
+                }
+                if (n + rep > nlen + ndist) return ST_REPEAT;
+                for (int i = lane; i < rep; i += 64) s.lens[n + i] = (uint8_t)v;
+                prev = v;
+                n += rep;
+            }
+            __syncthreads();
+            if (s.lens[256] == 0) return ST_NO_EOB;
+            if ((rc = build(s, s.lens, nlen, lc, false, lane))) return rc;
+            if ((rc = build(s, s.lens + nlen, ndist, dc, false, lane))) return rc;
+        }
+        for (;;) {                                    // the block's symbols
+            if (b.bc < 48) refill(b, s, in, in_len, lane);
+            if ((int64_t)b.ip * 8 - b.bc > (int64_t)in_len * 8) return ST_OVERRUN;
+            int sym = decode(b, lc);
+            if (sym < 0) return ST_BAD_LITLEN;
+            if (sym < 256) {
+                if (pos >= isize) return ST_OVERFLOW;
+                if (lane == 0) s.out[pos] = (uint8_t)sym;
+                ++pos;
+                continue;
+            }
+            if (sym == 256) break;
+            sym -= 257;
+            if (sym >= 29) return ST_BAD_LITLEN;
+            const int len = kLenBase[sym] + (int)take(b, kLenExtra[sym]);
+            const int dsym = decode(b, dc);
+            if (dsym < 0 || dsym >= 30) return ST_BAD_DIST;
+            const int dist = kDistBase[dsym] + (int)take(b, kDistExtra[dsym]);
+            if (dist > pos) return ST_FAR;
+            if (pos + len > isize) return ST_OVERFLOW;
+            __syncthreads();                          // the literals and matches before this one are in LDS
+            const int from = pos - dist;
+            if (dist >= len) {
+                for (int i = lane; i < len; i += 64) s.out[pos + i] = s.out[from + i];
+            } else {
+                for (int i = lane; i < len; i += 64) s.out[pos + i] = s.out[from + i % dist];
+            }
+            pos += len;
+        }
+    }
+    take(b, b.bc & 7);
+    const int64_t used = (int64_t)b.ip - b.bc / 8;
+    if (used > in_len) return ST_OVERRUN;
+    if (used < in_len) return ST_TRAILING;
+    if (pos != isize) return ST_ISIZE;
+    return ST_OK;
+}
+
+__global__ __launch_bounds__(64) void inflate_kernel(const uint8_t *__restrict__ in, const Member *__restrict__ mem,
+                                                     uint8_t *__restrict__ out, int32_t *__restrict__ status) {
+    __shared__ Lds s;
+    const int lane = (int)threadIdx.x;
+    const Member m = mem[blockIdx.x];
+    for (int i = lane; i < 256; i += 64) {
+        uint32_t c = (uint32_t)i;
+        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ kPoly : c >> 1;
+        s.crc_tab[i] = c;
+    }
+    int st = inflate_member(s, in + m.in_off, m.in_len, m.isize, lane);
+    if (st == ST_OK) {
+        __syncthreads();
+        const int L = (m.isize + 63) / 64, a = min(lane * L, m.isize), e = min(a + L, m.isize);
+        uint32_t c = 0;                                // the raw remainder of the lane's slice (register starting at 0)
+        for (int i = a; i < e; ++i) c = s.crc_tab[(c ^ s.out[i]) & 255] ^ (c >> 8);
+        s.part[lane] = c;
+        __syncthreads();
+        const uint32_t xl = x8n((uint32_t)L);
+        uint32_t acc = 0xFFFFFFFFu;                    // register after slice k = (register before) * x^(8 len_k) + slice k's remainder
+        for (int k = 0; k < 64; ++k) {
+            const int ka = min(k * L, m.isize), ke = min(ka + L, m.isize);
+            if (ke == ka) break;
+            acc = gf2_mul(ke - ka == L ? xl : x8n((uint32_t)(ke - ka)), acc) ^ s.part[k];
+        }
+        if (~acc != m.crc) st = ST_CRC;
+    }
+    if (st == ST_OK) {                                 // to HBM: bytes up to a 4-byte boundary, then dwords, then the tail
+        uint8_t *o = out + m.out_off;
+        const int n = m.isize;
+        const int head = min((int)((4 - ((uintptr_t)o & 3)) & 3), n);
+        if (lane < head) o[lane] = s.out[lane];
+        const int nw = (n - head) >> 2;
+        uint32_t *ow = reinterpret_cast<uint32_t *>(o + head);
+        for (int w = lane; w < nw; w += 64) {
+            const int q = head + 4 * w;
+            ow[w] = (uint32_t)s.out[q] | (uint32_t)s.out[q + 1] << 8 | (uint32_t)s.out[q + 2] << 16 | (uint32_t)s.out[q + 3] << 24;
+        }
+        const int t = head + 4 * nw;
+        if (t + lane < n) o[t + lane] = s.out[t + lane];
+    }
+    if (lane == 0) status[blockIdx.x] = st;
+}
+
+inline uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+enum Hdr { HDR_OK, HDR_SHORT, HDR_NOT_BGZF, HDR_BAD };
+
+// A BGZF member header at p (n bytes there): *hdr = bytes of the header, *total = BSIZE + 1.  HDR_SHORT: the bytes there could be the
+// start of one, more are needed.
+Hdr bgzf_header(const uint8_t *p, int64_t n, int *hdr, int *total) {
+    static const uint8_t magic[4] = {31, 139, 8, 4};      // ID1 ID2 CM FLG (FEXTRA only)
+    for (int i = 0; i < 4; ++i) {
+        if (i >= n) return HDR_SHORT;
+        if (p[i] != magic[i]) return HDR_NOT_BGZF;
+    }
+    if (n < 12) return HDR_SHORT;
+    const int xlen = p[10] | p[11] << 8;
+    if (xlen < 6) return HDR_NOT_BGZF;
+    if (n < 12 + xlen) return HDR_SHORT;
+    int bsize = -1;
+    for (int q = 12; q + 4 <= 12 + xlen;) {
+        const int slen = p[q + 2] | p[q + 3] << 8;
+        if (p[q] == 'B' && p[q + 1] == 'C' && slen == 2 && q + 6 <= 12 + xlen) bsize = p[q + 4] | p[q + 5] << 8;
+        q += 4 + slen;
+    }
+    if (bsize < 0) return HDR_NOT_BGZF;
+    *hdr = 12 + xlen;
+    *total = bsize + 1;
+    return *total < *hdr + 8 ? HDR_BAD : HDR_OK;
+}
+
+int device_ok(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) {
+        (void)hipGetLastError();
+        set_last_error("no usable HIP device");
+        return BWAMS_ERR_DEVICE;
+    }
+    hipDeviceProp_t p;
+    BWAMS_HIP(hipGetDeviceProperties(&p, device));
+    if (std::string(p.gcnArchName).rfind("gfx950", 0) != 0) {
+        set_last_error(std::string("device is ") + p.gcnArchName + ", this library is built for gfx950 only");
+        return BWAMS_ERR_DEVICE;
+    }
+    return BWAMS_OK;
+}
+
+}  // namespace
+
+struct bwams_inflater {
+    int device = 0;
+    int64_t max_in = 0, max_out = 0, max_members = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[4] = {};
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    Member *d_mem = nullptr, *h_mem = nullptr;        // h_mem / h_status page-locked
+    int32_t *d_status = nullptr, *h_status = nullptr;
+    int64_t members_done = 0, bytes_done = 0;         // over every call: a handle fed one file in order names the file's members
+    std::vector<int64_t> at;                          // this call's members: where each starts in gz
+};
+
+extern "C" {
+
+int bwams_inflater_destroy(bwams_inflater_t *f) {
+    if (!f) return BWAMS_OK;
+    (void)hipSetDevice(f->device);
+    if (f->st) (void)hipStreamSynchronize(f->st);
+    for (auto e : f->ev) if (e) (void)hipEventDestroy(e);
+    if (f->d_in) (void)hipFree(f->d_in);
+    if (f->d_out) (void)hipFree(f->d_out);
+    if (f->d_mem) (void)hipFree(f->d_mem);
+    if (f->d_status) (void)hipFree(f->d_status);
+    if (f->h_mem) (void)hipHostFree(f->h_mem);
+    if (f->h_status) (void)hipHostFree(f->h_status);
+    if (f->st) (void)hipStreamDestroy(f->st);
+    delete f;
+    return BWAMS_OK;
+}
+
+int bwams_inflater_create(int device, int64_t max_in_bytes, int64_t max_out_bytes, bwams_inflater_t **out) {
+    if (!out) return BWAMS_ERR_ARG;
+    *out = nullptr;
+    if (max_in_bytes < kOutMax || max_out_bytes < kOutMax || max_in_bytes > ((int64_t)1 << 40) || max_out_bytes > ((int64_t)1 << 40)) {
+        set_last_error("bwams_inflater_create: max_in_bytes and max_out_bytes must be at least 65536 (one BGZF member)");
+        return BWAMS_ERR_ARG;
+    }
+    if (int rc = device_ok(device)) return rc;
+    BWAMS_HIP(hipSetDevice(device));
+    auto *f = new bwams_inflater();
+    f->device = device;
+    f->max_in = max_in_bytes;
+    f->max_out = max_out_bytes;
+    f->max_members = max_in_bytes / 28 + 1;           // a member takes at least 28 bytes (the EOF member's size)
+    auto fail = [&](hipError_t e) {
+        set_last_error(std::string("bwams_inflater_create: ") + hipGetErrorString(e));
+        bwams_inflater_destroy(f);
+        return e == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&f->st, hipStreamNonBlocking)) != hipSuccess) return fail(e);
+    for (auto &x : f->ev)
+        if ((e = hipEventCreate(&x)) != hipSuccess) return fail(e);
+    if ((e = dev_malloc(&f->d_in, (size_t)max_in_bytes)) != hipSuccess) return fail(e);
+    if ((e = dev_malloc(&f->d_out, (size_t)max_out_bytes)) != hipSuccess) return fail(e);
+    if ((e = dev_malloc(&f->d_mem, sizeof(Member) * (size_t)f->max_members)) != hipSuccess) return fail(e);
+    if ((e = dev_malloc(&f->d_status, sizeof(int32_t) * (size_t)f->max_members)) != hipSuccess) return fail(e);
+    if ((e = hipHostMalloc(reinterpret_cast<void **>(&f->h_mem), sizeof(Member) * (size_t)f->max_members, hipHostMallocDefault)) != hipSuccess) return fail(e);
+    if ((e = hipHostMalloc(reinterpret_cast<void **>(&f->h_status), sizeof(int32_t) * (size_t)f->max_members, hipHostMallocDefault)) != hipSuccess) return fail(e);
+    *out = f;
+    return BWAMS_OK;
+}
+
+int bwams_inflater_run(bwams_inflater_t *f, const uint8_t *gz, int64_t n_bytes, void *out, int64_t out_cap, int out_on_device,
+                       int64_t *n_consumed, int64_t *n_out, bwams_inflate_stats_t *stats) {
+    if (!f || (!gz && n_bytes) || n_bytes < 0 || out_cap < 0 || (!out && out_cap)) return BWAMS_ERR_ARG;
+    if (n_consumed) *n_consumed = 0;
+    if (n_out) *n_out = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    BWAMS_HIP(hipSetDevice(f->device));
+    // the header chain: whole members that fit max_in, out_cap and (host output) the staging buffer
+    const int64_t out_lim = out_on_device ? out_cap : std::min(out_cap, f->max_out);
+    int64_t p = 0, o = 0, nm = 0;
+    auto where = [&](int64_t i, int64_t at) {
+        return "BGZF member " + std::to_string(f->members_done + i) + " at byte " + std::to_string(f->bytes_done + at) + ": ";
+    };
+    while (p < n_bytes && nm < f->max_members) {
+        int hdr = 0, total = 0;
+        const Hdr h = bgzf_header(gz + p, n_bytes - p, &hdr, &total);
+        if (h == HDR_SHORT) break;
+        if (h == HDR_NOT_BGZF) {
+            if (nm) break;                            // the members in front of it still go
+            set_last_error(where(0, p) + "not BGZF (a gzip header with FEXTRA only and a 'BC' extra subfield)");
+            return BWAMS_ERR_UNSUPPORTED;
+        }
+        if (h == HDR_BAD) {
+            set_last_error(where(nm, p) + "BSIZE smaller than its header and trailer");
+            return BWAMS_ERR_IO;
+        }
+        if (p + total > n_bytes) break;               // cut off by the end of the buffer
+        const uint32_t isize = rd32(gz + p + total - 4);
+        if (isize > (uint32_t)kOutMax) {
+            set_last_error(where(nm, p) + "ISIZE " + std::to_string(isize) + " is over 65536");
+            return BWAMS_ERR_IO;
+        }
+        if (o + (int64_t)isize > out_lim || p + total > f->max_in) {
+            if (nm) break;
+            set_last_error("bwams_inflater_run: the first member (" + std::to_string(isize) + " bytes) does not fit out_cap " +
+                           std::to_string(out_cap));
+            return BWAMS_ERR_CAPACITY;
+        }
+        if ((int64_t)f->at.size() <= nm) f->at.resize((size_t)nm + 1);
+        f->at[(size_t)nm] = p;
+        Member &m = f->h_mem[nm];
+        m.in_off = p + hdr;
+        m.in_len = total - hdr - 8;
+        m.out_off = o;
+        m.isize = (int32_t)isize;
+        m.crc = rd32(gz + p + total - 8);
+        m.pad_ = 0;
+        p += total;
+        o += isize;
+        ++nm;
+    }
+    if (nm == 0) return BWAMS_OK;
+    uint8_t *d_out = out_on_device ? static_cast<uint8_t *>(out) : f->d_out;
+    BWAMS_HIP(hipEventRecord(f->ev[0], f->st));
+    BWAMS_HIP(hipMemcpyAsync(f->d_in, gz, (size_t)p, hipMemcpyHostToDevice, f->st));
+    BWAMS_HIP(hipMemcpyAsync(f->d_mem, f->h_mem, sizeof(Member) * (size_t)nm, hipMemcpyHostToDevice, f->st));
+    BWAMS_HIP(hipEventRecord(f->ev[1], f->st));
+    hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)nm), dim3(64), 0, f->st, f->d_in, f->d_mem, d_out, f->d_status);
+    BWAMS_HIP(hipGetLastError());
+    BWAMS_HIP(hipEventRecord(f->ev[2], f->st));
+    BWAMS_HIP(hipMemcpyAsync(f->h_status, f->d_status, sizeof(int32_t) * (size_t)nm, hipMemcpyDeviceToHost, f->st));
+    BWAMS_HIP(hipStreamSynchronize(f->st));
+    for (int64_t i = 0; i < nm; ++i)
+        if (f->h_status[i] != ST_OK) {
+            set_last_error(where(i, f->at[(size_t)i]) + status_text(f->h_status[i]));
+            return BWAMS_ERR_IO;
+        }
+    if (!out_on_device && o) BWAMS_HIP(hipMemcpyAsync(out, f->d_out, (size_t)o, hipMemcpyDeviceToHost, f->st));
+    BWAMS_HIP(hipEventRecord(f->ev[3], f->st));
+    BWAMS_HIP(hipEventSynchronize(f->ev[3]));
+    if (stats) {
+        stats->members = nm;
+        stats->in_bytes = p;
+        stats->out_bytes = o;
+        BWAMS_HIP(hipEventElapsedTime(&stats->ms_upload, f->ev[0], f->ev[1]));
+        BWAMS_HIP(hipEventElapsedTime(&stats->ms_kernel, f->ev[1], f->ev[2]));
+        BWAMS_HIP(hipEventElapsedTime(&stats->ms_download, f->ev[2], f->ev[3]));
+    }
+    f->members_done += nm;
+    f->bytes_done += p;
+    if (n_consumed) *n_consumed = p;
+    if (n_out) *n_out = o;
+    return BWAMS_OK;
+}
+
+}  // extern "C"

@@ -12,15 +12,22 @@
 //   * bwams_writer: one output stream per shard (per GPU: "<prefix>.<s>.sam", or a single file), each with a thread that writes the
 //     texts handed to it in sequence-number order — a shard's file is in read order; concatenating the shards' files of a job that gave
 //     shard s the s-th contiguous slice of every chunk is NOT read order across chunks (that is what the single-stream form is for).
+//   * where the text comes from is a Source: zlib's gzread (bwams_reader_open, and bwams_reader_open_device on any file that is not
+//     BGZF), or BGZF members inflated on a GPU (bwams_reader_open_device: read(2) into page-locked staging, bwams_inflater_run into
+//     the chunk buffer behind the carried bytes).  The cut loop is the same for both, so their chunks are the same bytes.
 // Host C++ only.  zlib is the reference's own dependency for this step (Makefile: -lz).
+#include <fcntl.h>
+#include <unistd.h>
 #include <zlib.h>
 
+#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -86,10 +93,110 @@ int64_t one_record(const char *t, int64_t p, int64_t end, bool final, int64_t *b
     return a;
 }
 
+using Clock = std::chrono::steady_clock;
+float ms_since(Clock::time_point t0) { return std::chrono::duration<float, std::milli>(Clock::now() - t0).count(); }
+
+// The reader's text: read() puts up to `want` bytes at dst and returns how many, 0 at the end of the file, < 0 on an error (err says
+// what).  `step`: the most one read() is asked for.
+struct Source {
+    int64_t step = 8 << 20;
+    bwams_reader_stats_t st{};
+    virtual ~Source() {}
+    virtual int64_t read(char *dst, int64_t want, std::string &err) = 0;
+};
+
+struct ZlibSource : Source {
+    gzFile fp = nullptr;
+    ~ZlibSource() override { if (fp) gzclose(fp); }
+    int64_t read(char *dst, int64_t want, std::string &err) override {
+        const auto t0 = Clock::now();
+        const int got = gzread(fp, dst, (unsigned)want);
+        st.ms_inflate += ms_since(t0);
+        if (got < 0) { int e_ = 0; err = gzerror(fp, &e_); return BWAMS_ERR_IO; }
+        st.out_bytes += got;
+        st.in_bytes = gzoffset(fp);
+        return got;
+    }
+};
+
+// BGZF: compressed bytes by read(2) into page-locked staging, whole members inflated on the GPU into the chunk buffer.  A request
+// smaller than a member (the chunk buffer's last bytes) is served from one member inflated into `spill`.
+struct BgzfSource : Source {
+    std::string path;
+    int fd = -1;
+    bwams_inflater_t *inf = nullptr;
+    char *zbuf = nullptr;                                  // page-locked
+    int64_t zcap = 0, zpos = 0, zend = 0;
+    bool file_end = false;
+    std::vector<char> spill = std::vector<char>(65536);
+    int64_t spill_pos = 0, spill_end = 0;
+    ~BgzfSource() override {
+        if (inf) bwams_inflater_destroy(inf);
+        if (zbuf) bwams_host_free(zbuf);
+        if (fd >= 0) close(fd);
+    }
+    int64_t read(char *dst, int64_t want, std::string &err) override {
+        if (spill_pos < spill_end) {
+            const int64_t n = std::min(want, spill_end - spill_pos);
+            memcpy(dst, spill.data() + spill_pos, (size_t)n);
+            spill_pos += n;
+            return n;
+        }
+        for (;;) {
+            if (zend > zpos) {
+                const bool direct = want >= (int64_t)spill.size();
+                int64_t used = 0, n_out = 0;
+                const auto t0 = Clock::now();
+                const int rc = bwams_inflater_run(inf, reinterpret_cast<const uint8_t *>(zbuf + zpos), zend - zpos, direct ? dst : spill.data(),
+                                                  direct ? want : (int64_t)spill.size(), 0, &used, &n_out, nullptr);
+                st.ms_inflate += ms_since(t0);
+                if (rc) { err = path + ": " + bwams_last_error(); return rc; }
+                if (used) {
+                    zpos += used;
+                    st.out_bytes += n_out;
+                    if (n_out == 0) continue;                      // EOF members only
+                    if (direct) return n_out;
+                    spill_pos = 0;
+                    spill_end = n_out;
+                    return read(dst, want, err);
+                }
+            }
+            if (file_end) {
+                if (zend > zpos) { err = path + ": the file ends inside a BGZF member"; return BWAMS_ERR_IO; }
+                return 0;
+            }
+            memmove(zbuf, zbuf + zpos, (size_t)(zend - zpos));
+            zend -= zpos;
+            zpos = 0;
+            const auto t0 = Clock::now();
+            const ssize_t got = ::read(fd, zbuf + zend, (size_t)(zcap - zend));
+            st.ms_read += ms_since(t0);
+            if (got < 0) { err = path + ": read failed"; return BWAMS_ERR_IO; }
+            if (got == 0) file_end = true;
+            zend += got;
+            st.in_bytes += got;
+        }
+    }
+};
+
+// the first bytes of a BGZF file: a gzip header with FEXTRA only and a 'BC' subfield
+bool is_bgzf(const char *path) {
+    unsigned char h[64];
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return false;
+    const size_t n = fread(h, 1, sizeof h, fp);
+    fclose(fp);
+    if (n < 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || h[3] != 4) return false;
+    const size_t xend = 12 + (size_t)(h[10] | h[11] << 8);
+    for (size_t q = 12; q + 4 <= xend && q + 6 <= n; q += 4 + (size_t)(h[q + 2] | h[q + 3] << 8))
+        if (h[q] == 'B' && h[q + 1] == 'C' && (h[q + 2] | h[q + 3] << 8) == 2) return true;
+    return false;
+}
+
 }  // namespace
 
 struct bwams_reader {
-    gzFile fp = nullptr;
+    std::unique_ptr<Source> src;
     int64_t chunk_bases = 0;
     int paired = 0;
     std::vector<Chunk> ring;
@@ -102,6 +209,8 @@ struct bwams_reader {
     std::string err;
     // carry: bytes inflated but not yet part of a chunk
     std::vector<char> carry;
+    bwams_reader_stats_t stats{};                       // src->st as of the last read, under stat_mu
+    mutable std::mutex stat_mu;
 };
 
 static void reader_main(bwams_reader *r) {
@@ -139,9 +248,15 @@ static void reader_main(bwams_reader *r) {
                 break;
             }
             if (have >= c.cap - 1) { r->rc = BWAMS_ERR_CAPACITY; r->err = "chunk buffer too small for " + std::to_string(r->chunk_bases) + " bases of records"; break; }
-            const int64_t want = std::min<int64_t>(c.cap - 1 - have, 8 << 20);      // one byte of slack: bwams_bseq_parse may put a NUL behind the text
-            const int got = gzread(r->fp, c.buf + have, (unsigned)want);
-            if (got < 0) { int e_ = 0; r->rc = BWAMS_ERR_IO; r->err = gzerror(r->fp, &e_); break; }
+            const int64_t want = std::min<int64_t>(c.cap - 1 - have, r->src->step);      // one byte of slack: bwams_bseq_parse may put a NUL behind the text
+            int64_t got;
+            {
+                std::string e_;
+                got = r->src->read(c.buf + have, want, e_);
+                std::lock_guard<std::mutex> g(r->stat_mu);
+                r->stats = r->src->st;
+                if (got < 0) { r->rc = (int)got; r->err = e_; break; }
+            }
             if (got == 0) file_end = true;
             have += got;
         }
@@ -167,8 +282,33 @@ int bwams_reader_close(bwams_reader_t *r) {
     r->cv.notify_all();
     if (r->th.joinable()) r->th.join();
     for (Chunk &c : r->ring) if (c.buf) bwams_host_free(c.buf);
-    if (r->fp) gzclose(r->fp);
     delete r;
+    return BWAMS_OK;
+}
+
+static int reader_start(bwams_reader *r, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes, int32_t n_buffers) {
+    r->chunk_bases = chunk_bases;
+    r->paired = paired;
+    // a record of 150 bases is ~ 320 bytes of text: 2.6 bytes per base and room for the record that crosses the limit
+    const int64_t cap = buffer_bytes > 0 ? buffer_bytes : chunk_bases * 3 + (64 << 20);
+    r->ring.resize((size_t)n_buffers);
+    for (int i = 0; i < n_buffers; ++i) {
+        void *p = nullptr;
+        if (int rc = bwams_host_alloc((size_t)cap, &p)) return rc;
+        r->ring[(size_t)i].buf = static_cast<char *>(p);
+        r->ring[(size_t)i].cap = cap;
+        r->free_q.push_back(i);
+    }
+    r->th = std::thread(reader_main, r);
+    return BWAMS_OK;
+}
+
+static int zlib_source(const char *path, std::unique_ptr<Source> *out) {
+    auto z = std::unique_ptr<ZlibSource>(new ZlibSource());
+    z->fp = gzopen(path, "rb");
+    if (!z->fp) return BWAMS_ERR_IO;
+    gzbuffer(z->fp, 1 << 20);
+    *out = std::move(z);
     return BWAMS_OK;
 }
 
@@ -178,27 +318,52 @@ int bwams_reader_open(const char *path, int64_t chunk_bases, int32_t paired, int
     bwams_reader *r = nullptr;
     try {
         r = new bwams_reader();
-        r->fp = gzopen(path, "rb");
-        if (!r->fp) { delete r; return BWAMS_ERR_IO; }
-        gzbuffer(r->fp, 1 << 20);
-        r->chunk_bases = chunk_bases;
-        r->paired = paired;
-        // a record of 150 bases is ~ 320 bytes of text: 2.6 bytes per base and room for the record that crosses the limit
-        const int64_t cap = buffer_bytes > 0 ? buffer_bytes : chunk_bases * 3 + (64 << 20);
-        r->ring.resize((size_t)n_buffers);
-        for (int i = 0; i < n_buffers; ++i) {
-            void *p = nullptr;
-            if (int rc = bwams_host_alloc((size_t)cap, &p)) { bwams_reader_close(r); return rc; }
-            r->ring[(size_t)i].buf = static_cast<char *>(p);
-            r->ring[(size_t)i].cap = cap;
-            r->free_q.push_back(i);
-        }
-        r->th = std::thread(reader_main, r);
+        if (int rc = zlib_source(path, &r->src)) { delete r; return rc; }
+        if (int rc = reader_start(r, chunk_bases, paired, buffer_bytes, n_buffers)) { bwams_reader_close(r); return rc; }
     } catch (...) {
         if (r) bwams_reader_close(r);
         return BWAMS_ERR_NOMEM;
     }
     *out = r;
+    return BWAMS_OK;
+}
+
+int bwams_reader_open_device(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes,
+                             int32_t n_buffers, bwams_reader_t **out) {
+    if (!path || !out || chunk_bases <= 0 || n_buffers < 1 || n_buffers > 16) return BWAMS_ERR_ARG;
+    *out = nullptr;
+    bwams_reader *r = nullptr;
+    try {
+        r = new bwams_reader();
+        if (!is_bgzf(path)) {
+            if (int rc = zlib_source(path, &r->src)) { delete r; return rc; }
+        } else {
+            constexpr int64_t kIn = 32 << 20, kOut = 64 << 20;     // one call: up to 32 MiB of members, 64 MiB of text
+            auto b = std::unique_ptr<BgzfSource>(new BgzfSource());
+            b->path = path;
+            b->st.device_inflate = 1;
+            b->step = kOut;
+            b->fd = open(path, O_RDONLY);
+            if (b->fd < 0) { delete r; return BWAMS_ERR_IO; }
+            if (int rc = bwams_host_alloc((size_t)kIn, reinterpret_cast<void **>(&b->zbuf))) { delete r; return rc; }
+            b->zcap = kIn;
+            if (int rc = bwams_inflater_create(device, kIn, kOut, &b->inf)) { delete r; return rc; }
+            r->src = std::move(b);
+        }
+        if (int rc = reader_start(r, chunk_bases, paired, buffer_bytes, n_buffers)) { bwams_reader_close(r); return rc; }
+    } catch (...) {
+        if (r) bwams_reader_close(r);
+        return BWAMS_ERR_NOMEM;
+    }
+    *out = r;
+    return BWAMS_OK;
+}
+
+int bwams_reader_info(const bwams_reader_t *r, bwams_reader_stats_t *out) {
+    if (!r || !out) return BWAMS_ERR_ARG;
+    std::lock_guard<std::mutex> g(r->stat_mu);
+    *out = r->stats;
+    out->device_inflate = r->src->st.device_inflate;
     return BWAMS_OK;
 }
 

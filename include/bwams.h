@@ -140,6 +140,25 @@ int bwams_index_from_fasta(int device, const char *text, int64_t n_bytes, int te
 /* The same from a plain or gzip file (zlib, inflated into page-locked memory). */
 int bwams_index_from_fasta_file(const char *path, int device, int keep_ref, int64_t chunk_rows, bwams_fasta_stats_t *stats,
                                 bwams_index_t **out);
+/* BGZF (blocked gzip, SAMv1 §4.1: what bgzip writes) inflated on the GPU — replaces gzread() for such input.  The host walks the
+ * member headers (BSIZE, CRC32, ISIZE); each member is inflated (RFC 1951: stored, fixed and dynamic blocks, with zlib's checks of
+ * the codes) by one wave, and its CRC32 and ISIZE are checked, always.  max_in_bytes / max_out_bytes (each >= 65536): the compressed
+ * bytes and the host-output bytes one call takes at most.  The handle is bound to `device`; one caller at a time. */
+typedef struct bwams_inflater bwams_inflater_t;
+typedef struct bwams_inflate_stats {
+    int64_t members, in_bytes, out_bytes;
+    float ms_upload, ms_kernel, ms_download;     /* device events */
+} bwams_inflate_stats_t;
+int bwams_inflater_create(int device, int64_t max_in_bytes, int64_t max_out_bytes, bwams_inflater_t **out);
+/* Inflates the whole BGZF members at the front of gz[0, n_bytes) into out (host memory, or this device's memory when out_on_device)
+ * in file order. It stops at a member cut off by the end of the buffer and at the first member that would not fit out_cap (or
+ * max_in_bytes / max_out_bytes). *n_consumed / *n_out say how far it got (0 / 0: give it more bytes). BWAMS_ERR_UNSUPPORTED: not
+ * BGZF (a later member that is not BGZF ends the call in front of it). BWAMS_ERR_CAPACITY: the first member does not fit.
+ * BWAMS_ERR_IO: damaged data; bwams_last_error names the member (index and byte offset, counted over every call on this handle),
+ * nothing is consumed, and out is written only in the ranges of the members that checked out. */
+int bwams_inflater_run(bwams_inflater_t *f, const uint8_t *gz, int64_t n_bytes, void *out, int64_t out_cap, int out_on_device,
+                       int64_t *n_consumed, int64_t *n_out, bwams_inflate_stats_t *stats);
+int bwams_inflater_destroy(bwams_inflater_t *f);
 /* bns_restore (src/bntseq.cpp:114-246) onto a handle, e.g. one from bwams_index_open: reads <prefix>.ann, checks the .amb header
  * against it (a mismatched pair is BWAMS_ERR_IO), reads <prefix>.alt when present, and sets the sequences (with is_alt), their
  * names and annotations.  The .ann must describe the index's l_pac (BWAMS_ERR_ARG otherwise). */
@@ -647,6 +666,17 @@ int bwams_reader_next(bwams_reader_t *r, const char **text, int64_t *n_bytes, in
 int bwams_reader_release(bwams_reader_t *r, const char *text);
 const char *bwams_reader_error(const bwams_reader_t *r);
 int bwams_reader_close(bwams_reader_t *r);
+/* The same reader, with a BGZF file inflated on `device` (bwams_inflater_run into the chunk buffer; read(2) into page-locked
+ * staging): chunks byte-identical to bwams_reader_open's.  Any other file (plain gzip, uncompressed) is read exactly as
+ * bwams_reader_open reads it, and bwams_reader_info says device_inflate = 0.  The reader's own thread sets the device. */
+int bwams_reader_open_device(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes,
+                             int32_t n_buffers, bwams_reader_t **out);
+typedef struct bwams_reader_stats {
+    int32_t device_inflate;                      /* 1: BGZF on the GPU; 0: zlib on the reader's thread */
+    int64_t in_bytes, out_bytes;                 /* file bytes read so far, text bytes inflated so far */
+    float ms_read, ms_inflate;                   /* reader thread: read(2) (device path only), inflate */
+} bwams_reader_stats_t;
+int bwams_reader_info(const bwams_reader_t *r, bwams_reader_stats_t *out);
 int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out);
 int bwams_writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *text, int64_t n_bytes);
 int bwams_writer_close(bwams_writer_t *w);       /* waits until everything handed over in order is on disk */
