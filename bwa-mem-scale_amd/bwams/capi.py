@@ -43,6 +43,8 @@ SYMBOLS = [
     "bwams_process_reads", "bwams_process_reads_stage1", "bwams_process_reads_stage2", "bwams_host_alloc", "bwams_host_free",
     "bwams_reader_open", "bwams_reader_next", "bwams_reader_release", "bwams_reader_error", "bwams_reader_close",
     "bwams_inflater_create", "bwams_inflater_run", "bwams_inflater_destroy", "bwams_reader_open_device", "bwams_reader_info",
+    "bwams_deflate_bound", "bwams_deflater_create", "bwams_deflater_run", "bwams_deflater_destroy", "bwams_sam_fetch_bgzf",
+    "bwams_writer_open_bgzf", "bwams_writer_put_bgzf",
     "bwams_writer_open", "bwams_writer_put", "bwams_writer_close",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
@@ -239,6 +241,57 @@ class Inflater:
             pass
 
 
+class DeflateStats(C.Structure):
+    _fields_ = [("members", C.c_int64), ("in_bytes", C.c_int64), ("out_bytes", C.c_int64),
+                ("ms_upload", C.c_float), ("ms_kernel", C.c_float), ("ms_download", C.c_float)]
+
+
+DEFLATE_EOF = 0x1                # BWAMS_DEFLATE_EOF: append the BGZF EOF member
+
+
+def deflate_bound(n_bytes: int) -> int:
+    """bwams_deflate_bound: the most bwams_deflater_run writes for n_bytes of input."""
+    return lib().bwams_deflate_bound(n_bytes)
+
+
+class Deflater:
+    """BGZF written on one GPU (bwams_deflater_t)."""
+
+    def __init__(self, device: int = 0, max_in_bytes: int = 32 << 20):
+        self.h = C.c_void_p()
+        self.device = device
+        _chk(lib().bwams_deflater_create(device, max_in_bytes, C.byref(self.h)), "bwams_deflater_create")
+
+    def run_raw(self, data, out, out_cap: int, in_on_device: bool = False, out_on_device: bool = False, flags: int = 0):
+        """bwams_deflater_run as is: data bytes (or an address with its length as (addr, n)), out an address.  Returns
+        (rc, n_out, DeflateStats)."""
+        n_out, st = C.c_int64(0), DeflateStats()
+        ptr, n = (C.c_void_p(data[0]), data[1]) if isinstance(data, tuple) else (data, len(data))
+        rc = lib().bwams_deflater_run(self.h, ptr, n, int(in_on_device), C.c_void_p(out), out_cap, int(out_on_device), flags,
+                                      C.byref(n_out), C.byref(st))
+        return rc, n_out.value, st
+
+    def run(self, data, eof: bool = False):
+        """data (bytes, or (device address, n)) as BGZF members in host memory: (bytes, DeflateStats)."""
+        n = data[1] if isinstance(data, tuple) else len(data)
+        cap = deflate_bound(n)
+        buf = C.create_string_buffer(cap)
+        rc, got, st = self.run_raw(data, C.addressof(buf), cap, isinstance(data, tuple), False, DEFLATE_EOF if eof else 0)
+        _chk(rc, "bwams_deflater_run")
+        return buf.raw[:got], st
+
+    def close(self):
+        if self.h:
+            lib().bwams_deflater_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def reader_open_device(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0,
                        n_buffers: int = 2) -> C.c_void_p:
     """bwams_reader_open_device: a bwams_reader_t handle (bwams_reader_next / _release / _close as for bwams_reader_open)."""
@@ -335,6 +388,14 @@ def lib():
         L.bwams_inflater_destroy.argtypes = [vp]
         L.bwams_reader_open_device.argtypes = [C.c_char_p, C.c_int, i64, i32, i64, i32, vp]
         L.bwams_reader_info.argtypes = [vp, vp]
+        L.bwams_deflate_bound.restype = i64
+        L.bwams_deflate_bound.argtypes = [i64]
+        L.bwams_deflater_create.argtypes = [C.c_int, i64, vp]
+        L.bwams_deflater_run.argtypes = [vp, vp, i64, C.c_int, vp, i64, C.c_int, i32, vp, vp]
+        L.bwams_deflater_destroy.argtypes = [vp]
+        L.bwams_sam_fetch_bgzf.argtypes = [vp, vp, vp, i64, i32, vp]
+        L.bwams_writer_open_bgzf.argtypes = [C.c_char_p, i32, C.c_int, vp]
+        L.bwams_writer_put_bgzf.argtypes = [vp, i32, i64, vp, i64]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
@@ -1010,6 +1071,15 @@ class Batch:
         mq = np.zeros(max(n_regs, 1), np.int32)
         _chk(lib().bwams_sam_fetch(self.h, _p(buf), len(buf), _p(off), _p(mq) if n_regs else None, len(mq)), "bwams_sam_fetch")
         return bytes(buf[:self._sam_bytes]), off, mq[:n_regs]
+
+    def sam_fetch_bgzf(self, deflater: "Deflater", eof: bool = False) -> bytes:
+        """The SAM text of the last SAM run as BGZF members, compressed on the device where it lies (bwams_sam_fetch_bgzf)."""
+        cap = deflate_bound(getattr(self, "_sam_bytes", 0))
+        buf = C.create_string_buffer(cap)
+        n = C.c_int64(0)
+        _chk(lib().bwams_sam_fetch_bgzf(self.h, deflater.h, C.addressof(buf), cap, DEFLATE_EOF if eof else 0, C.byref(n)),
+             "bwams_sam_fetch_bgzf")
+        return buf.raw[:n.value]
 
     def reg2aln_sam(self, opt: MemOpt | None = None, sopt=None, pes=None, fetch: bool = True):
         """mem_reg2aln of the regions the SAM text needs only (after mark_primary_se, or pair_run with its pes) ->

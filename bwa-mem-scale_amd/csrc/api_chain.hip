@@ -1516,6 +1516,20 @@ int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off,
     return BWAMS_OK;
 }
 
+int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out) {
+    if (!b || !d || !b->chain || !b->chain->sm_done) {
+        set_last_error("bwams_sam_fetch_bgzf: run bwams_sam_run first");
+        return BWAMS_ERR_ARG;
+    }
+    if (deflater_device(d) != b->idx->device) {
+        set_last_error("bwams_sam_fetch_bgzf: the deflater is on device " + std::to_string(deflater_device(d)) + ", the batch on device " +
+                       std::to_string(b->idx->device));
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    return deflater_run_after(d, b->stream, s->sm_out.p, s->sm_bytes, 1, out, cap, 0, flags, n_out, nullptr);
+}
+
 /* ------------------------------------------------------------ mem_process_seqs ---- */
 
 // The outer boundary for one chunk, text to text: what kt_pipeline's step 0 parsing and step 1 (mem_process_seqs, src/bwamem.cpp:1850-1980)

@@ -145,6 +145,11 @@ struct DevCounters {
 struct ChainState;                       // chain / extension buffers of a batch (api_chain.hip)
 void chain_state_free(ChainState *s);
 
+// deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
+int deflater_device(const bwams_deflater *d);
+int deflater_run_after(bwams_deflater *d, hipStream_t after, const void *in, int64_t n_bytes, int in_on_device, void *out, int64_t out_cap,
+                       int out_on_device, int32_t flags, int64_t *n_out, bwams_deflate_stats_t *stats);
+
 // banded-SW parameters in kernel form (max_sc = max entry of mat)
 struct SwParams {
     int o_del, e_del, o_ins, e_ins, zdrop, end_bonus, max_sc;

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "crc32.h"
 
 using namespace bwams;
 
@@ -30,7 +31,6 @@ namespace {
 constexpr int kOutMax = 65536;           // a BGZF member inflates to at most 64 KiB
 constexpr int kInWin = 4096;             // LDS window over the member's compressed bytes
 constexpr int kLRoot = 10, kDRoot = 8;   // first-level table bits: literal/length, distance
-constexpr uint32_t kPoly = 0xEDB88320u;  // CRC-32 (reflected)
 
 struct Member {                          // one BGZF member as the kernel sees it (32 bytes)
     int64_t in_off;                      // its DEFLATE data in the input buffer
@@ -188,25 +188,6 @@ __device__ int build(Lds &s, const uint8_t *lens, int n, const Code &c, bool cl,
     return ST_OK;
 }
 
-__device__ __forceinline__ uint32_t gf2_mul(uint32_t a, uint32_t b) {     // a * b mod P (reflected: bit 31 is x^0)
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b & 1) ? (b >> 1) ^ kPoly : b >> 1;
-    }
-    return p;
-}
-
-__device__ uint32_t x8n(uint32_t n) {                // x^(8n) mod P
-    uint32_t sq = 0x40000000u, r = 0x80000000u;      // x^1, x^0
-    for (int i = 0; i < 3; ++i) sq = gf2_mul(sq, sq);  // x^8
-    for (; n; n >>= 1) {
-        if (n & 1) r = gf2_mul(r, sq);
-        sq = gf2_mul(sq, sq);
-    }
-    return r;
-}
-
 __device__ int inflate_member(Lds &s, const uint8_t *__restrict__ in, int in_len, int isize, int lane) {
     Bits b{0, 0, 0, 0};
     window_load(s, in, in_len, 0, lane);
@@ -323,27 +304,11 @@ __global__ __launch_bounds__(64) void inflate_kernel(const uint8_t *__restrict__
     __shared__ Lds s;
     const int lane = (int)threadIdx.x;
     const Member m = mem[blockIdx.x];
-    for (int i = lane; i < 256; i += 64) {
-        uint32_t c = (uint32_t)i;
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ kPoly : c >> 1;
-        s.crc_tab[i] = c;
-    }
+    crc32_table<64>(s.crc_tab, lane);
     int st = inflate_member(s, in + m.in_off, m.in_len, m.isize, lane);
     if (st == ST_OK) {
         __syncthreads();
-        const int L = (m.isize + 63) / 64, a = min(lane * L, m.isize), e = min(a + L, m.isize);
-        uint32_t c = 0;                                // the raw remainder of the lane's slice (register starting at 0)
-        for (int i = a; i < e; ++i) c = s.crc_tab[(c ^ s.out[i]) & 255] ^ (c >> 8);
-        s.part[lane] = c;
-        __syncthreads();
-        const uint32_t xl = x8n((uint32_t)L);
-        uint32_t acc = 0xFFFFFFFFu;                    // register after slice k = (register before) * x^(8 len_k) + slice k's remainder
-        for (int k = 0; k < 64; ++k) {
-            const int ka = min(k * L, m.isize), ke = min(ka + L, m.isize);
-            if (ke == ka) break;
-            acc = gf2_mul(ke - ka == L ? xl : x8n((uint32_t)(ke - ka)), acc) ^ s.part[k];
-        }
-        if (~acc != m.crc) st = ST_CRC;
+        if (crc32_lds<64>(s.out, m.isize, s.crc_tab, s.part, lane) != m.crc) st = ST_CRC;
     }
     if (st == ST_OK) {                                 // to HBM: bytes up to a 4-byte boundary, then dwords, then the tail
         uint8_t *o = out + m.out_off;

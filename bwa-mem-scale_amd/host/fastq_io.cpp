@@ -407,32 +407,55 @@ const char *bwams_reader_error(const bwams_reader_t *r) { return r ? r->err.c_st
 
 // ------------------------------------------------------------------------------------------------------------------------- writer
 struct bwams_writer {
+    struct Piece {
+        std::string bytes;
+        bool members = false;                         // BGZF members already made (bwams_writer_put_bgzf): written as they are
+    };
     struct Shard {
         FILE *fp = nullptr;
         std::thread th;
         std::mutex mu;
         std::condition_variable cv;
-        std::map<int64_t, std::string> pending;       // sequence number -> text (written when its turn comes)
+        std::map<int64_t, Piece> pending;             // sequence number -> text (written when its turn comes)
         int64_t next = 0;
         bool stop = false;
         int rc = BWAMS_OK;
+        bwams_deflater_t *def = nullptr;              // BGZF writer: text is compressed on this shard's thread
+        std::string gz;                               // its output buffer
     };
     std::vector<Shard *> sh;
+    bool bgzf = false;
 };
+
+static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0,
+                                     0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 static void writer_main(bwams_writer::Shard *s) {
     for (;;) {
-        std::string text;
+        bwams_writer::Piece p;
         {
             std::unique_lock<std::mutex> g(s->mu);
             s->cv.wait(g, [s] { return s->stop || s->pending.count(s->next); });
             auto it = s->pending.find(s->next);
             if (it == s->pending.end()) { if (s->stop) return; continue; }
-            text.swap(it->second);
+            p.bytes.swap(it->second.bytes);
+            p.members = it->second.members;
             s->pending.erase(it);
             ++s->next;
         }
-        if (!text.empty() && fwrite(text.data(), 1, text.size(), s->fp) != text.size()) s->rc = BWAMS_ERR_IO;
+        const std::string *out = &p.bytes;
+        if (s->def && !p.members && !p.bytes.empty()) {
+            const int64_t n = (int64_t)p.bytes.size();
+            int64_t got = 0;
+            s->gz.resize((size_t)bwams_deflate_bound(n));
+            if (int rc = bwams_deflater_run(s->def, p.bytes.data(), n, 0, &s->gz[0], (int64_t)s->gz.size(), 0, 0, &got, nullptr)) {
+                s->rc = rc;
+                got = 0;
+            }
+            s->gz.resize((size_t)got);
+            out = &s->gz;
+        }
+        if (!out->empty() && fwrite(out->data(), 1, out->size(), s->fp) != out->size()) s->rc = BWAMS_ERR_IO;
         s->cv.notify_all();
     }
 }
@@ -449,7 +472,9 @@ int bwams_writer_close(bwams_writer_t *w) {
         }
         s->cv.notify_all();
         if (s->th.joinable()) s->th.join();
+        if (s->fp && w->bgzf && !s->rc && fwrite(kBgzfEof, 1, sizeof kBgzfEof, s->fp) != sizeof kBgzfEof) s->rc = BWAMS_ERR_IO;
         if (s->fp && fclose(s->fp)) rc = BWAMS_ERR_IO;
+        if (s->def) bwams_deflater_destroy(s->def);
         if (s->rc) rc = s->rc;
         delete s;
     }
@@ -457,17 +482,22 @@ int bwams_writer_close(bwams_writer_t *w) {
     return rc;
 }
 
-// n_shards == 1: `path` is the file.  n_shards > 1: "<path>.<s>.sam", s = 0 .. n_shards - 1 (one per GPU).
-int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out) {
+// n_shards == 1: `path` is the file.  n_shards > 1: "<path>.<s>.sam" (BGZF: ".sam.gz"), s = 0 .. n_shards - 1 (one per GPU).
+// device >= 0: a BGZF writer, each shard with a deflater on that device.
+static int writer_open(const char *path, int32_t n_shards, int device, bwams_writer_t **out) {
     if (!path || !out || n_shards < 1 || n_shards > 64) return BWAMS_ERR_ARG;
     *out = nullptr;
     bwams_writer *w = nullptr;
     try {
         w = new bwams_writer();
+        w->bgzf = device >= 0;
         for (int s = 0; s < n_shards; ++s) {
             auto *x = new bwams_writer::Shard();
             w->sh.push_back(x);
-            const std::string name = n_shards == 1 ? std::string(path) : std::string(path) + "." + std::to_string(s) + ".sam";
+            if (w->bgzf)
+                if (int rc = bwams_deflater_create(device, 32 << 20, &x->def)) { bwams_writer_close(w); return rc; }
+            const std::string name = n_shards == 1 ? std::string(path)
+                                                   : std::string(path) + "." + std::to_string(s) + (w->bgzf ? ".sam.gz" : ".sam");
             x->fp = fopen(name.c_str(), "wb");
             if (!x->fp) { bwams_writer_close(w); return BWAMS_ERR_IO; }
             setvbuf(x->fp, nullptr, _IOFBF, 8 << 20);
@@ -481,21 +511,40 @@ int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out) 
     return BWAMS_OK;
 }
 
+int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out) { return writer_open(path, n_shards, -1, out); }
+
+int bwams_writer_open_bgzf(const char *path, int32_t n_shards, int device, bwams_writer_t **out) {
+    if (device < 0) return BWAMS_ERR_ARG;
+    return writer_open(path, n_shards, device, out);
+}
+
 // Hand shard `shard` the text with sequence number `seq` (0, 1, 2 ... per shard, any arrival order); the bytes are copied, the call
 // returns at once, the shard's thread writes seq 0, 1, 2 ... in that order.
-int bwams_writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *text, int64_t n_bytes) {
-    if (!w || shard < 0 || shard >= (int32_t)w->sh.size() || seq < 0 || n_bytes < 0 || (n_bytes && !text)) return BWAMS_ERR_ARG;
+static int writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *bytes, int64_t n_bytes, bool members) {
+    if (!w || shard < 0 || shard >= (int32_t)w->sh.size() || seq < 0 || n_bytes < 0 || (n_bytes && !bytes)) return BWAMS_ERR_ARG;
     auto *s = w->sh[(size_t)shard];
     try {
-        std::string t(text ? text : "", (size_t)n_bytes);
+        bwams_writer::Piece p;
+        p.bytes.assign(bytes ? bytes : "", (size_t)n_bytes);
+        p.members = members;
         std::lock_guard<std::mutex> g(s->mu);
         if (seq < s->next || s->pending.count(seq)) return BWAMS_ERR_ARG;
-        s->pending.emplace(seq, std::move(t));
+        s->pending.emplace(seq, std::move(p));
     } catch (...) {
         return BWAMS_ERR_NOMEM;
     }
     s->cv.notify_all();
     return s->rc;
+}
+
+int bwams_writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *text, int64_t n_bytes) {
+    return writer_put(w, shard, seq, text, n_bytes, false);
+}
+
+// Members already made go to a BGZF writer's shard as they are, in the same sequence order as the text of bwams_writer_put.
+int bwams_writer_put_bgzf(bwams_writer_t *w, int32_t shard, int64_t seq, const uint8_t *members, int64_t n_bytes) {
+    if (w && !w->bgzf) return BWAMS_ERR_ARG;
+    return writer_put(w, shard, seq, reinterpret_cast<const char *>(members), n_bytes, true);
 }
 
 // ------------------------------------------------------------------------------------------------- step 0 for mem_process_seqs()

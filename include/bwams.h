@@ -159,6 +159,28 @@ int bwams_inflater_create(int device, int64_t max_in_bytes, int64_t max_out_byte
 int bwams_inflater_run(bwams_inflater_t *f, const uint8_t *gz, int64_t n_bytes, void *out, int64_t out_cap, int out_on_device,
                        int64_t *n_consumed, int64_t *n_out, bwams_inflate_stats_t *stats);
 int bwams_inflater_destroy(bwams_inflater_t *f);
+/* BGZF written on the GPU: the output side's counterpart of the inflater.  The text is cut every 65280 bytes from its byte 0 (bgzip's
+ * and htslib's cut; the last member is partial) and each piece becomes one standalone gzip member with bgzip's header: one RFC 1951
+ * block, stored, fixed or dynamic Huffman, whichever has the fewest bits (input that does not compress is stored: its length + 31
+ * bytes), LZ77 matches inside the member only, CRC32 and ISIZE computed on the device.  Members come out contiguous and in input order,
+ * and their bytes depend only on the input bytes (not on max_in_bytes, the number of launches or where input and output lie).
+ * max_in_bytes (>= 65280): the input one launch takes; larger input runs in several launches with the same output.  The handle is
+ * bound to `device`; one caller at a time. */
+typedef struct bwams_deflater bwams_deflater_t;
+typedef struct bwams_deflate_stats {
+    int64_t members, in_bytes, out_bytes;
+    float ms_upload, ms_kernel, ms_download;     /* device events */
+} bwams_deflate_stats_t;
+#define BWAMS_DEFLATE_EOF 0x1                    /* append the 28-byte BGZF EOF member */
+int64_t bwams_deflate_bound(int64_t n_bytes);    /* n + 31 * ceil(n / 65280) + 28: the most bwams_deflater_run can write */
+int bwams_deflater_create(int device, int64_t max_in_bytes, bwams_deflater_t **out);
+/* Compresses all of in[0, n_bytes) (host memory, or this device's memory when in_on_device) into out (host, or this device's memory
+ * when out_on_device); *n_out: the bytes written.  Members never span two calls, so the outputs of consecutive calls concatenate into one
+ * BGZF stream.  n_bytes = 0 writes nothing (or only the EOF member).  BWAMS_ERR_CAPACITY, with nothing written and *n_out = the bound:
+ * out_cap < bwams_deflate_bound(n_bytes).  BWAMS_ERR_ARG: a null handle, in or out, or unknown flags. */
+int bwams_deflater_run(bwams_deflater_t *d, const void *in, int64_t n_bytes, int in_on_device, void *out, int64_t out_cap,
+                       int out_on_device, int32_t flags, int64_t *n_out, bwams_deflate_stats_t *stats);
+int bwams_deflater_destroy(bwams_deflater_t *d);
 /* bns_restore (src/bntseq.cpp:114-246) onto a handle, e.g. one from bwams_index_open: reads <prefix>.ann, checks the .amb header
  * against it (a mismatched pair is BWAMS_ERR_IO), reads <prefix>.alt when present, and sets the sequences (with is_alt), their
  * names and annotations.  The .ann must describe the index's l_pac (BWAMS_ERR_ARG otherwise). */
@@ -328,6 +350,10 @@ int bwams_sam_run_pe(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_s
 /* sam: the text of all reads in read order (cap >= sam_bytes); read_off[nseq + 1]: where a read's lines start; mapq: the
  * device-side mem_approx_mapq_se of every region (region order of bwams_reg2aln_fetch).  Any of the three may be NULL. */
 int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off, int32_t *mapq, int64_t mapq_cap);
+/* The batch's SAM text (after bwams_sam_run / _run_pe / _run_emf or bwams_process_chunk*) compressed where it lies by `d`, after the
+ * work queued on the batch's stream: BGZF members into host memory out[0, cap), as bwams_deflater_run writes them (flags:
+ * BWAMS_DEFLATE_EOF).  They inflate to exactly what bwams_sam_fetch returns.  BWAMS_ERR_ARG: no SAM run yet, or d on another device. */
+int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out);
 
 /* ------------------------------------------------------------- read input ---- *
  * A buffer of FASTQ text (host or this GPU's memory) becomes the arrays bwams_seed_upload and bwams_sam_upload take: replaces, per
@@ -680,6 +706,12 @@ int bwams_reader_info(const bwams_reader_t *r, bwams_reader_stats_t *out);
 int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out);
 int bwams_writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *text, int64_t n_bytes);
 int bwams_writer_close(bwams_writer_t *w);       /* waits until everything handed over in order is on disk */
+/* A BGZF writer: shards named as bwams_writer_open names them, with ".sam.gz" in place of ".sam".  Every shard's thread owns a deflater
+ * on `device` and compresses the text of each bwams_writer_put (a put's members never span into the next put);
+ * bwams_writer_put_bgzf hands over members already made (e.g. by bwams_sam_fetch_bgzf, without the EOF member), written in the same
+ * sequence order.  bwams_writer_close appends the EOF member to every shard. */
+int bwams_writer_open_bgzf(const char *path, int32_t n_shards, int device, bwams_writer_t **out);
+int bwams_writer_put_bgzf(bwams_writer_t *w, int32_t shard, int64_t seq, const uint8_t *members, int64_t n_bytes);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);
