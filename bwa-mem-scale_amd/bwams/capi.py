@@ -45,6 +45,7 @@ SYMBOLS = [
     "bwams_inflater_create", "bwams_inflater_run", "bwams_inflater_destroy", "bwams_reader_open_device", "bwams_reader_info",
     "bwams_deflate_bound", "bwams_deflater_create", "bwams_deflater_run", "bwams_deflater_destroy", "bwams_sam_fetch_bgzf",
     "bwams_writer_open_bgzf", "bwams_writer_put_bgzf",
+    "bwams_bam_run", "bwams_bam_fetch", "bwams_bam_fetch_bgzf", "bwams_sam_header", "bwams_bam_header", "bwams_writer_open_bam",
     "bwams_writer_open", "bwams_writer_put", "bwams_writer_close",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
@@ -292,6 +293,14 @@ class Deflater:
             pass
 
 
+def writer_open_bam(path: str, n_shards: int, device: int, bam_header: bytes) -> C.c_void_p:
+    """bwams_writer_open_bam: a bwams_writer_t handle (bwams_writer_put_bgzf / _close as for bwams_writer_open_bgzf)."""
+    w = C.c_void_p()
+    _chk(lib().bwams_writer_open_bam(path.encode(), n_shards, device, bytes(bam_header), len(bam_header), C.byref(w)),
+         "bwams_writer_open_bam")
+    return w
+
+
 def reader_open_device(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0,
                        n_buffers: int = 2) -> C.c_void_p:
     """bwams_reader_open_device: a bwams_reader_t handle (bwams_reader_next / _release / _close as for bwams_reader_open)."""
@@ -396,6 +405,12 @@ def lib():
         L.bwams_sam_fetch_bgzf.argtypes = [vp, vp, vp, i64, i32, vp]
         L.bwams_writer_open_bgzf.argtypes = [C.c_char_p, i32, C.c_int, vp]
         L.bwams_writer_put_bgzf.argtypes = [vp, i32, i64, vp, i64]
+        L.bwams_bam_run.argtypes = [vp, vp, vp]
+        L.bwams_bam_fetch.argtypes = [vp, vp, i64, vp]
+        L.bwams_bam_fetch_bgzf.argtypes = [vp, vp, vp, i64, i32, vp]
+        L.bwams_sam_header.argtypes = [vp, C.c_char_p, C.c_char_p, vp, i64, vp]
+        L.bwams_bam_header.argtypes = [vp, C.c_char_p, i64, vp, i64, vp]
+        L.bwams_writer_open_bam.argtypes = [C.c_char_p, i32, C.c_int, C.c_char_p, i64, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
@@ -607,6 +622,24 @@ class Index:
         off.append(len(blob))
         off = np.asarray(off, np.int32)
         _chk(lib().bwams_index_set_contig_names(self.h, bytes(blob), _p(off)), "bwams_index_set_contig_names")
+
+    def _header(self, fn, name, *args) -> bytes:
+        n = C.c_int64(0)
+        rc = fn(self.h, *args, None, 0, C.byref(n))
+        if rc != -4:                                       # BWAMS_ERR_CAPACITY gives the size
+            _chk(rc, name)
+        buf = C.create_string_buffer(max(n.value, 1))
+        _chk(fn(self.h, *args, buf, n.value, C.byref(n)), name)
+        return buf.raw[:n.value]
+
+    def sam_header(self, hdr_line=None, pg_line=None) -> bytes:
+        """bwa_print_sam_hdr as bytes (bwams_sam_header): @SQ lines (unless hdr_line has its own), hdr_line + newline, pg_line."""
+        enc = lambda x: x.encode() if isinstance(x, str) else x
+        return self._header(lib().bwams_sam_header, "bwams_sam_header", enc(hdr_line), enc(pg_line))
+
+    def bam_header(self, text: bytes) -> bytes:
+        """The BAM header block of `text` and the index's sequences (bwams_bam_header)."""
+        return self._header(lib().bwams_bam_header, "bwams_bam_header", bytes(text), len(text))
 
     def set_contig_annos(self, annos):
         """bntann1_t.anno of every sequence (b"" = none): the XR:Z: tags of MEM_F_REF_HDR (0x100)."""
@@ -1079,6 +1112,30 @@ class Batch:
         n = C.c_int64(0)
         _chk(lib().bwams_sam_fetch_bgzf(self.h, deflater.h, C.addressof(buf), cap, DEFLATE_EOF if eof else 0, C.byref(n)),
              "bwams_sam_fetch_bgzf")
+        return buf.raw[:n.value]
+
+    def bam_run(self) -> tuple[int, int]:
+        """The SAM text of the last SAM run as BAM records on the device (bwams_bam_run): (bytes, records)."""
+        nb, nr = C.c_int64(0), C.c_int64(0)
+        _chk(lib().bwams_bam_run(self.h, C.byref(nb), C.byref(nr)), "bwams_bam_run")
+        self._bam_bytes = nb.value
+        return nb.value, nr.value
+
+    def bam_fetch(self, n_reads: int | None = None):
+        """(records of the last bam_run, n + 1 per-read offsets); n_reads defaults to the reads of the last SAM run."""
+        n = self._nseq if n_reads is None else n_reads
+        buf = np.empty(max(self._bam_bytes, 1), np.uint8)
+        off = np.zeros(n + 1, np.int64)
+        _chk(lib().bwams_bam_fetch(self.h, _p(buf), len(buf), _p(off)), "bwams_bam_fetch")
+        return buf[:self._bam_bytes].tobytes(), off
+
+    def bam_fetch_bgzf(self, deflater: "Deflater", eof: bool = False) -> bytes:
+        """The records of the last bam_run as BGZF members, compressed where they lie (bwams_bam_fetch_bgzf)."""
+        cap = deflate_bound(getattr(self, "_bam_bytes", 0))
+        buf = C.create_string_buffer(cap)
+        n = C.c_int64(0)
+        _chk(lib().bwams_bam_fetch_bgzf(self.h, deflater.h, C.addressof(buf), cap, DEFLATE_EOF if eof else 0, C.byref(n)),
+             "bwams_bam_fetch_bgzf")
         return buf.raw[:n.value]
 
     def reg2aln_sam(self, opt: MemOpt | None = None, sopt=None, pes=None, fetch: bool = True):

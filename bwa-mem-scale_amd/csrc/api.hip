@@ -397,6 +397,10 @@ int bwams_index_close(bwams_index_t *ix) {
         (void)hipFree(ix->d_ctg_names);
         (void)hipFree(ix->d_ctg_off);
     }
+    if (ix->d_ctg_sorted) {
+        (void)hipSetDevice(ix->device);
+        (void)hipFree(ix->d_ctg_sorted);
+    }
     if (ix->d_all || ix->d_last) {
         (void)hipSetDevice(ix->device);
         if (ix->d_all) (void)hipFree(ix->d_all);

@@ -61,6 +61,9 @@ struct ChainState {
     int64_t sm_bytes = 0, sm_nseq = 0, sm_nregs = 0;
     int64_t sm_merged_n = -1;            // >= 0: sm_out / sm_off hold that many reads' text merged from two runs (bwams_process_chunk_smart)
     bool sm_up = false, sm_has_qual = false, sm_has_comm = false, sm_done = false, sm_log_ok = false;
+    DevBuf bm_size, bm_roff, bm_off, bm_out, bm_bad;   // BAM records of the SAM text (bwams_bam_run)
+    int64_t bm_bytes = 0, bm_nrec = 0, bm_nseq = 0;
+    bool bm_done = false;                // bm_* hold the BAM of the current SAM text (every change of sm_done clears it)
     int64_t n_final = 0;
     bool dedup_done = false;
     int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_chain_redo = 0;
@@ -116,7 +119,7 @@ void chain_state_free(ChainState *s) {
                      &s->chain_off, &s->chains, &s->seeds, &s->seeds2, &s->sw_qb, &s->sw_rb, &s->sw_read, &s->sw_newn, &s->sw_res, &s->dd_regs, &s->dd_ord, &s->dd_srt, &s->dd_eh,
                      &s->dd_nout, &s->dd_wide, &s->dd_off, &s->dd_out, &s->dd_light, &s->pe_keys, &s->pe_keys2, &s->pr_na, &s->pr_wide, &s->pr_offs, &s->pr_anchor, &s->pr_slot, &s->pr_task, &s->pr_trb, &s->pr_tl1, &s->pr_twide, &s->pr_toffs,
                      &s->pr_pairs, &s->pr_tref, &s->pr_tqer, &s->pr_aln, &s->pr_pool, &s->pr_ord, &s->pr_srt, &s->pr_z, &s->pr_nfin, &s->pr_npri, &s->pr_nsw, &s->pr_full, &s->pr_owide,
-                     &s->pr_ooff, &s->pr_out, &s->pr_res, &s->et_mems, &s->et_moff, &s->et_hits, &s->et_hoff, &s->et_smem, &s->et_cnt, &s->et_off, &s->et_coord, &s->et_srt, &s->er_wide, &s->er_off, &s->er_scr, &s->er_n, &s->er_rev, &s->er_out, &s->er_ooff, &s->mg_wide, &s->mg_off, &s->mg_out, &s->al_need, &s->al_cls, &s->al_off, &s->al_scr, &s->al_list, &s->al_rec, &s->al_wide, &s->al_offs, &s->al_cig, &s->al_md, &s->al_cnt, &s->al_only, &s->sm_names, &s->sm_noff, &s->sm_qual, &s->sm_comm, &s->sm_coff, &s->sm_mapq, &s->sm_len, &s->sm_off, &s->sm_out, &s->sm_logtab, &s->sm_bad, &s->regs, &s->srt, &s->rmax, &s->cnt, &s->state, &s->kreg, &s->cur, &s->lim,
+                     &s->pr_ooff, &s->pr_out, &s->pr_res, &s->et_mems, &s->et_moff, &s->et_hits, &s->et_hoff, &s->et_smem, &s->et_cnt, &s->et_off, &s->et_coord, &s->et_srt, &s->er_wide, &s->er_off, &s->er_scr, &s->er_n, &s->er_rev, &s->er_out, &s->er_ooff, &s->mg_wide, &s->mg_off, &s->mg_out, &s->al_need, &s->al_cls, &s->al_off, &s->al_scr, &s->al_list, &s->al_rec, &s->al_wide, &s->al_offs, &s->al_cig, &s->al_md, &s->al_cnt, &s->al_only, &s->sm_names, &s->sm_noff, &s->sm_qual, &s->sm_comm, &s->sm_coff, &s->sm_mapq, &s->sm_len, &s->sm_off, &s->sm_out, &s->sm_logtab, &s->sm_bad, &s->bm_size, &s->bm_roff, &s->bm_off, &s->bm_out, &s->bm_bad, &s->regs, &s->srt, &s->rmax, &s->cnt, &s->state, &s->kreg, &s->cur, &s->lim,
                      &s->ewide, &s->eoffs, &s->lpairs, &s->lref, &s->lqer, &s->rpairs, &s->rref, &s->rqer, &s->retry};
     for (DevBuf *d : all)
         if (d->p) (void)hipFree(d->p);
@@ -1308,7 +1311,7 @@ int bwams_index_set_contig_names(bwams_index_t *ix, const char *names, const int
     BWAMS_HIP(dev_malloc(&ix->d_ctg_off, (size_t)(n + 1) * 4));
     BWAMS_HIP(hipMemcpy(ix->d_ctg_names, names, (size_t)name_off[n], hipMemcpyHostToDevice));
     BWAMS_HIP(hipMemcpy(ix->d_ctg_off, name_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
-    return BWAMS_OK;
+    return bam_names_index(ix, names, name_off, n);
 }
 
 int bwams_index_set_contig_annos(bwams_index_t *ix, const char *annos, const int32_t *anno_off) {
@@ -1351,7 +1354,7 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
         set_last_error("bwams_sam_upload: offsets start at 0");
         return BWAMS_ERR_ARG;
     }
-    s->sm_up = s->sm_done = false;
+    s->sm_up = s->sm_done = s->bm_done = false;
     BWAMS_HIP(s->sm_names.ensure((size_t)name_off[nseq] + 16));
     BWAMS_HIP(s->sm_noff.ensure((size_t)n1 * 8));
     BWAMS_HIP(hipMemcpyAsync(s->sm_names.p, names, (size_t)name_off[nseq], hipMemcpyDefault, st));
@@ -1407,7 +1410,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     if (!memchr(sopt->rg_id, 0, sizeof sopt->rg_id)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    s->sm_done = false; s->sm_merged_n = -1;
+    s->sm_done = s->bm_done = false; s->sm_merged_n = -1;
     const int64_t nseq = s->nseq, n1 = nseq + 1, n = s->al_n;
     constexpr int kLogN = 1 << 16;
     if (!s->sm_log_ok) {                                   // log(i) with the C library's log, as the reference's host code computes it
@@ -1479,7 +1482,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     launch_sam_text(A, true, b->cu_count, st);
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
-    s->sm_bytes = total; s->sm_nregs = n; s->sm_done = true;
+    s->sm_bytes = total; s->sm_nregs = n; s->sm_done = true; s->bm_done = false;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
 }
@@ -1530,6 +1533,114 @@ int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64
     return deflater_run_after(d, b->stream, s->sm_out.p, s->sm_bytes, 1, out, cap, 0, flags, n_out, nullptr);
 }
 
+/* ------------------------------------------------------------ BAM records (bam.hip) ---- */
+
+int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
+    if (!b || !b->chain || !b->chain->sm_done) {
+        set_last_error("bwams_bam_run: run bwams_sam_run first");
+        return BWAMS_ERR_ARG;
+    }
+    bwams_index *ix = b->idx;
+    if (!ix->d_ctg_sorted || (int64_t)ix->h_ctg_names.size() != ix->n_seqs) {
+        set_last_error("bwams_bam_run: the index has no sequence names (bwams_index_set_contig_names)");
+        return BWAMS_ERR_ARG;
+    }
+    if (ix->ctg_dup) {
+        set_last_error("bwams_bam_run: two of the index's sequences have the same name; BAM cannot tell them apart");
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    BWAMS_HIP(hipSetDevice(ix->device));
+    hipStream_t st = b->stream;
+    s->bm_done = false;
+    const int64_t nseq = s->sm_merged_n >= 0 ? s->sm_merged_n : s->nseq;
+    int64_t *ends = nullptr, n_rec = 0;
+    struct Free {
+        int64_t **p;
+        ~Free() { if (*p) (void)hipFree(*p); }
+    } fr{&ends};
+    int rc = line_ends(s->sm_out.as<char>(), s->sm_bytes, st, &ends, &n_rec);
+    if (rc) return rc;
+    BWAMS_HIP(s->bm_size.ensure((size_t)(n_rec + 1) * 8));
+    BWAMS_HIP(s->bm_roff.ensure((size_t)(n_rec + 1) * 8));
+    BWAMS_HIP(s->bm_off.ensure((size_t)(nseq + 1) * 8));
+    BWAMS_HIP(s->bm_bad.ensure(64));
+    if (n_rec == 0) {                                         // no text (a chunk of no reads): no records
+        BWAMS_HIP(hipMemsetAsync(s->bm_off.p, 0, (size_t)(nseq + 1) * 8, st));
+        BWAMS_HIP(hipStreamSynchronize(st));
+        s->bm_bytes = 0; s->bm_nrec = 0; s->bm_nseq = nseq; s->bm_done = true;
+        if (bam_bytes) *bam_bytes = 0;
+        if (n_records) *n_records = 0;
+        return BWAMS_OK;
+    }
+    BamArgs A;
+    memset(&A, 0, sizeof A);
+    A.text = s->sm_out.as<char>();
+    A.line_end = ends; A.read_off = s->sm_off.as<int64_t>();
+    A.n_rec = n_rec; A.nseq = nseq;
+    A.ctg_names = reinterpret_cast<const char *>(ix->d_ctg_names);
+    A.ctg_off = reinterpret_cast<const int32_t *>(ix->d_ctg_off);
+    A.ctg_sorted = reinterpret_cast<const int32_t *>(ix->d_ctg_sorted);
+    A.n_ctg = ix->n_seqs;
+    A.size = s->bm_size.as<int64_t>(); A.rec_off = s->bm_roff.as<int64_t>();
+    A.bad = s->bm_bad.as<unsigned long long>();
+    BWAMS_HIP(hipMemsetAsync(s->bm_bad.p, 0xFF, 8, st));
+    BWAMS_HIP(hipMemsetAsync(A.size + n_rec, 0, 8, st));
+    launch_bam_count(A, b->cu_count, st);
+    if ((rc = scan_rows(b, A.size, s->bm_roff.as<int64_t>(), 1, n_rec + 1))) return rc;
+    int64_t total = 0;
+    unsigned long long bad = 0;
+    BWAMS_HIP(hipMemcpyAsync(&total, s->bm_roff.as<int64_t>() + n_rec, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(&bad, s->bm_bad.p, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    if (bad != ~0ULL) {
+        static const char *why[] = {"", "a line that is not a SAM record BAM can hold", "a read name longer than 254 bytes",
+                                    "an optional field that is not TG:T:value of type A, i, f, Z or H (a copied FASTQ comment?)",
+                                    "an integer field outside int32 / uint32", "more than 65535 CIGAR operations", "SEQ and QUAL of different lengths"};
+        const unsigned r = (unsigned)(bad & 0xFF);
+        set_last_error("bwams_bam_run: read " + std::to_string(bad >> 8) + ": " + (r < 7 ? why[r] : "?"));
+        return BWAMS_ERR_UNSUPPORTED;
+    }
+    BWAMS_HIP(s->bm_out.ensure((size_t)total + 16));
+    A.out = s->bm_out.as<uint8_t>();
+    launch_bam_write(A, s->bm_off.as<int64_t>(), b->cu_count, st);
+    BWAMS_HIP(hipGetLastError());
+    BWAMS_HIP(hipStreamSynchronize(st));
+    s->bm_bytes = total; s->bm_nrec = n_rec; s->bm_nseq = nseq; s->bm_done = true;
+    if (bam_bytes) *bam_bytes = total;
+    if (n_records) *n_records = n_rec;
+    return BWAMS_OK;
+}
+
+int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off) {
+    if (!b || !b->chain || !b->chain->bm_done) {
+        set_last_error("bwams_bam_fetch: run bwams_bam_run first");
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    if (bam && s->bm_bytes > cap) return BWAMS_ERR_CAPACITY;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t st = b->stream;
+    if (bam && s->bm_bytes) BWAMS_HIP(hipMemcpyAsync(bam, s->bm_out.p, (size_t)s->bm_bytes, hipMemcpyDeviceToHost, st));
+    if (read_off) BWAMS_HIP(hipMemcpyAsync(read_off, s->bm_off.p, (size_t)(s->bm_nseq + 1) * 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    return BWAMS_OK;
+}
+
+int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out) {
+    if (!b || !d || !b->chain || !b->chain->bm_done) {
+        set_last_error("bwams_bam_fetch_bgzf: run bwams_bam_run first");
+        return BWAMS_ERR_ARG;
+    }
+    if (deflater_device(d) != b->idx->device) {
+        set_last_error("bwams_bam_fetch_bgzf: the deflater is on device " + std::to_string(deflater_device(d)) + ", the batch on device " +
+                       std::to_string(b->idx->device));
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    return deflater_run_after(d, b->stream, s->bm_out.p, s->bm_bytes, 1, out, cap, 0, flags, n_out, nullptr);
+}
+
 /* ------------------------------------------------------------ mem_process_seqs ---- */
 
 // The outer boundary for one chunk, text to text: what kt_pipeline's step 0 parsing and step 1 (mem_process_seqs, src/bwamem.cpp:1850-1980)
@@ -1568,7 +1679,7 @@ static int process_stage2(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, 
 }
 
 static void process_empty(bwams_batch_t *b, int64_t *sam_bytes) {      // an empty chunk: no reads, no text
-    if (b->chain) { b->chain->sm_done = true; b->chain->sm_bytes = 0; b->chain->sm_nregs = 0; b->chain->nseq = 0; b->chain->sm_merged_n = -1; }
+    if (b->chain) { b->chain->sm_done = true; b->chain->bm_done = false; b->chain->sm_bytes = 0; b->chain->sm_nregs = 0; b->chain->nseq = 0; b->chain->sm_merged_n = -1; }
     b->nseq = 0;
     if (sam_bytes) *sam_bytes = 0;
 }
@@ -1809,7 +1920,7 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     if ((rc = segment_copy(mv, st))) return rc;
     BWAMS_HIP(hipMemcpyAsync(s->sm_off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->sm_bytes = total; s->sm_nregs = 0; s->sm_merged_n = n; s->sm_done = true;
+    s->sm_bytes = total; s->sm_nregs = 0; s->sm_merged_n = n; s->sm_done = true; s->bm_done = false;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
 }
@@ -1880,7 +1991,7 @@ int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
     std::swap(s->dd_off, s->mg_off);
     s->n_final = total;
     s->er_done = false;                                   // merged: a second call would add them again
-    s->pair_done = s->al_done = s->sm_done = false;
+    s->pair_done = s->al_done = s->sm_done = s->bm_done = false;
     if (n_regs) *n_regs = total;
     return BWAMS_OK;
 }

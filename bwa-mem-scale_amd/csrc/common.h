@@ -145,6 +145,24 @@ struct DevCounters {
 struct ChainState;                       // chain / extension buffers of a batch (api_chain.hip)
 void chain_state_free(ChainState *s);
 
+// bam.hip: a batch's SAM text as BAM records.  Record r is the line that ends at line_end[r]; the counting pass writes size[r]
+// (block_size + 4) and, for a line BAM cannot hold, bad[0] = min(read << 8 | reason); the writing pass fills out from rec_off
+// (the exclusive scan of size, n_rec + 1 entries) and bam_off[nseq + 1], where each read's records start.
+struct BamArgs {
+    const char *text;
+    const int64_t *line_end, *read_off;
+    int64_t n_rec, nseq;
+    const char *ctg_names;
+    const int32_t *ctg_off, *ctg_sorted;
+    int32_t n_ctg;
+    int64_t *size;
+    const int64_t *rec_off;
+    uint8_t *out;
+    unsigned long long *bad;
+};
+void launch_bam_count(const BamArgs &A, int cu_count, hipStream_t st);
+void launch_bam_write(const BamArgs &A, int64_t *bam_off, int cu_count, hipStream_t st);
+
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);
 int deflater_run_after(bwams_deflater *d, hipStream_t after, const void *in, int64_t n_bytes, int in_on_device, void *out, int64_t out_cap,
@@ -224,11 +242,15 @@ struct bwams_index {
     void *d_ctg_annos = nullptr, *d_ctg_anno_off = nullptr;   // bntann1_t.anno for MEM_F_REF_HDR (bwams_index_set_contig_annos)
     void *d_ctg_names = nullptr, *d_ctg_off = nullptr;   // sequence names for the SAM text (bwams_index_set_contig_names)
     bwams::BnsMeta *bns = nullptr;               // .ann / .amb / .pac of an index made from FASTA (bwams_index_from_fasta), else null
+    std::vector<std::string> h_ctg_names;        // host copy of the sequence names (the SAM / BAM headers)
+    void *d_ctg_sorted = nullptr;                // int32 permutation of the names in strcmp order: the BAM encoder's RNAME lookup
+    bool ctg_dup = false;                        // two sequences share a name (the BAM entry points refuse the index)
 };
 
 namespace bwams {
 int bns_save(bwams_index *ix, const char *prefix);     // fasta_ref.hip: writes <prefix>.ann, .amb, .pac
 void bns_free(bwams_index *ix);
+int bam_names_index(bwams_index *ix, const char *names, const int32_t *name_off, int32_t n);   // bam.hip, from set_contig_names
 }
 
 namespace bwams {

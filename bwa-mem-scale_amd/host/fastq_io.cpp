@@ -425,6 +425,7 @@ struct bwams_writer {
     };
     std::vector<Shard *> sh;
     bool bgzf = false;
+    bool bam = false;                                 // a BAM writer: members only (bwams_writer_put refuses text)
 };
 
 static const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0,
@@ -482,25 +483,40 @@ int bwams_writer_close(bwams_writer_t *w) {
     return rc;
 }
 
-// n_shards == 1: `path` is the file.  n_shards > 1: "<path>.<s>.sam" (BGZF: ".sam.gz"), s = 0 .. n_shards - 1 (one per GPU).
-// device >= 0: a BGZF writer, each shard with a deflater on that device.
-static int writer_open(const char *path, int32_t n_shards, int device, bwams_writer_t **out) {
+// n_shards == 1: `path` is the file.  n_shards > 1: "<path>.<s>.sam" (BGZF: ".sam.gz", BAM: ".bam"), s = 0 .. n_shards - 1 (one per
+// GPU).  device >= 0: a BGZF writer, each shard with a deflater on that device.  bam_header: a BAM writer; every shard starts with
+// the header block compressed into members of its own, so that the first record starts a member.
+static int writer_open(const char *path, int32_t n_shards, int device, bwams_writer_t **out, const void *bam_header = nullptr,
+                       int64_t n_header = 0) {
     if (!path || !out || n_shards < 1 || n_shards > 64) return BWAMS_ERR_ARG;
     *out = nullptr;
     bwams_writer *w = nullptr;
     try {
         w = new bwams_writer();
         w->bgzf = device >= 0;
+        w->bam = bam_header != nullptr;
+        std::string hdr;
+        if (w->bam && n_header > 0) {
+            bwams_deflater_t *d = nullptr;
+            if (int rc = bwams_deflater_create(device, 32 << 20, &d)) { delete w; return rc; }
+            hdr.resize((size_t)bwams_deflate_bound(n_header));
+            int64_t got = 0;
+            const int rc = bwams_deflater_run(d, bam_header, n_header, 0, &hdr[0], (int64_t)hdr.size(), 0, 0, &got, nullptr);
+            bwams_deflater_destroy(d);
+            if (rc) { delete w; return rc; }
+            hdr.resize((size_t)got);
+        }
         for (int s = 0; s < n_shards; ++s) {
             auto *x = new bwams_writer::Shard();
             w->sh.push_back(x);
             if (w->bgzf)
                 if (int rc = bwams_deflater_create(device, 32 << 20, &x->def)) { bwams_writer_close(w); return rc; }
             const std::string name = n_shards == 1 ? std::string(path)
-                                                   : std::string(path) + "." + std::to_string(s) + (w->bgzf ? ".sam.gz" : ".sam");
+                                                   : std::string(path) + "." + std::to_string(s) + (w->bam ? ".bam" : w->bgzf ? ".sam.gz" : ".sam");
             x->fp = fopen(name.c_str(), "wb");
             if (!x->fp) { bwams_writer_close(w); return BWAMS_ERR_IO; }
             setvbuf(x->fp, nullptr, _IOFBF, 8 << 20);
+            if (!hdr.empty() && fwrite(hdr.data(), 1, hdr.size(), x->fp) != hdr.size()) { bwams_writer_close(w); return BWAMS_ERR_IO; }
             x->th = std::thread(writer_main, x);
         }
     } catch (...) {
@@ -516,6 +532,11 @@ int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out) 
 int bwams_writer_open_bgzf(const char *path, int32_t n_shards, int device, bwams_writer_t **out) {
     if (device < 0) return BWAMS_ERR_ARG;
     return writer_open(path, n_shards, device, out);
+}
+
+int bwams_writer_open_bam(const char *path, int32_t n_shards, int device, const void *bam_header, int64_t n, bwams_writer_t **out) {
+    if (device < 0 || !bam_header || n < 4 || memcmp(bam_header, "BAM\1", 4) != 0) return BWAMS_ERR_ARG;
+    return writer_open(path, n_shards, device, out, bam_header, n);
 }
 
 // Hand shard `shard` the text with sequence number `seq` (0, 1, 2 ... per shard, any arrival order); the bytes are copied, the call
@@ -538,6 +559,7 @@ static int writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char 
 }
 
 int bwams_writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *text, int64_t n_bytes) {
+    if (w && w->bam) return BWAMS_ERR_ARG;           // text would corrupt a BAM stream
     return writer_put(w, shard, seq, text, n_bytes, false);
 }
 

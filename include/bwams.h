@@ -355,6 +355,32 @@ int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off,
  * BWAMS_DEFLATE_EOF).  They inflate to exactly what bwams_sam_fetch returns.  BWAMS_ERR_ARG: no SAM run yet, or d on another device. */
 int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out);
 
+/* ------------------------------------------------------------- BAM ---- *
+ * The batch's SAM text, whichever run made it (bwams_sam_run / _run_pe / _run_emf, bwams_process_chunk / _chunk2 / _chunk_smart), as
+ * BAM alignment records (SAMv1 §4.2), one per line in text order, encoded on the device where the text lies, with htslib's rules
+ * (sam_parse1 + bam_write1): refID / next_refID = the sequence's index in the index's order (-1 for '*', RNEXT '=' is refID), 0-based
+ * POS / PNEXT, bin = reg2bin(pos, end) with end = pos + the CIGAR's reference length (pos + 1 when unmapped, CIGAR '*' or length 0),
+ * read name + one NUL, SEQ in 4-bit codes (high nibble first), QUAL - 33 (0xFF bytes when '*'), aux fields in text order with the
+ * smallest integer type (c / s / i when negative, C / S / I otherwise), f as (float)strtod.  bwams/bam.py restates the rules.
+ * BWAMS_ERR_UNSUPPORTED, nothing kept, bwams_last_error naming the earliest read concerned: text BAM cannot hold, all of it from the
+ * user — a read name over 254 bytes, a copied FASTQ comment (BWAMS_CHUNK_COPY_COMMENT, mem -C) that is not TG:T:value fields of type
+ * A, i, f, Z or H (Illumina's "1:N:0:ACGT"; B arrays are refused too), an integer outside int32 / uint32, more than 65535 CIGAR
+ * operations.  BWAMS_ERR_ARG: no SAM run yet, an index without sequence names, or one where two sequences share a name. */
+int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records);
+/* bam: the records of the last bwams_bam_run (cap >= bam_bytes, BWAMS_ERR_CAPACITY otherwise); read_off[n + 1]: where each read's
+ * records start (n = the reads of the SAM text, as for bwams_sam_fetch).  Either may be NULL. */
+int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off);
+/* The records compressed where they lie, as bwams_sam_fetch_bgzf compresses the text (BWAMS_DEFLATE_EOF; a record may span two
+ * members, which SAMv1 §4.1 allows). */
+int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out);
+/* bwa_print_sam_hdr into out[0, cap): "@SQ\tSN:<name>\tLN:<len>" per sequence ("\tAH:*" for ALT sequences) unless hdr_line holds @SQ
+ * lines of its own; then hdr_line and a newline (mem -H text and the @RG line, as main_mem builds it); then pg_line as given (it carries
+ * its own newline).  hdr_line / pg_line may be NULL.  *n_out: the bytes written, or needed with BWAMS_ERR_CAPACITY. */
+int bwams_sam_header(const bwams_index_t *idx, const char *hdr_line, const char *pg_line, char *out, int64_t cap, int64_t *n_out);
+/* The BAM header block (SAMv1 §4.2): "BAM\1", l_text, the header text (n_text bytes, no NUL added), n_ref and, per sequence of the
+ * index in index order (what refID counts), l_name (with its NUL), the name and l_ref.  *n_out as for bwams_sam_header. */
+int bwams_bam_header(const bwams_index_t *idx, const char *text, int64_t n_text, void *out, int64_t cap, int64_t *n_out);
+
 /* ------------------------------------------------------------- read input ---- *
  * A buffer of FASTQ text (host or this GPU's memory) becomes the arrays bwams_seed_upload and bwams_sam_upload take: replaces, per
  * record, kseq_read (src/kseq.h:358-400), trim_readno and kseq2bseq1 (src/bwa.cpp:74-153) as bseq_read_orig (src/bwa.cpp:266-335)
@@ -712,6 +738,11 @@ int bwams_writer_close(bwams_writer_t *w);       /* waits until everything hande
  * sequence order.  bwams_writer_close appends the EOF member to every shard. */
 int bwams_writer_open_bgzf(const char *path, int32_t n_shards, int device, bwams_writer_t **out);
 int bwams_writer_put_bgzf(bwams_writer_t *w, int32_t shard, int64_t seq, const uint8_t *members, int64_t n_bytes);
+/* A BAM writer: shards named as bwams_writer_open names them, with ".bam" in place of ".sam".  Every shard starts with bam_header
+ * (bwams_bam_header's block, n bytes) compressed into members of its own on `device`, so that the first record starts a member; then
+ * the members of bwams_writer_put_bgzf (e.g. from bwams_bam_fetch_bgzf, without the EOF member) in sequence order; bwams_writer_close
+ * appends the EOF member.  bwams_writer_put (text) on a BAM writer is BWAMS_ERR_ARG. */
+int bwams_writer_open_bam(const char *path, int32_t n_shards, int device, const void *bam_header, int64_t n, bwams_writer_t **out);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);
