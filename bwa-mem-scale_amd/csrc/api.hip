@@ -1333,8 +1333,8 @@ int bwams_bsw_upload(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n, 
         if (p.len2 > qmax) qmax = p.len2;
         if (p.len1 > tmax) tmax = p.len1;
     }
-    if (bsw_lds_bytes(qmax) > 160 * 1024) {
-        set_last_error("bwams_bsw_upload: query longer than the LDS-resident kernel supports");
+    if (bsw_lds_waves(qmax) < 1) {                    // the limit launch_bsw has: one wave's row within a CU's LDS
+        set_last_error("bwams_bsw_upload: query of " + std::to_string(qmax) + " bases, longer than the LDS-resident kernel supports (18196)");
         return BWAMS_ERR_UNSUPPORTED;
     }
     auto grow = [](void **p, int64_t *cap, int64_t need, size_t elem) -> hipError_t {

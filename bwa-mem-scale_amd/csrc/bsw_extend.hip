@@ -27,6 +27,12 @@ namespace {
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kTaskChunk = 8;      // tasks a wave reserves per atomic (one word serves ~90 M tickets/s)
+constexpr size_t kBswLdsMax = 160 * 1024;      // LDS of one CU: the most a block of bsw_kernel may take
+
+// LDS of one wave of bsw_kernel: the (h, e) row of qmax + 1 columns, then the query, 16-byte aligned
+__host__ __device__ __forceinline__ size_t bsw_row_bytes(int qmax) {
+    return (((size_t)(qmax + 1) * 8 + (size_t)qmax + 64 + 15) / 16) * 16;
+}
 
 __device__ __forceinline__ int wave_incl_prefix_max(int v, int lane) {
 #pragma unroll
@@ -50,7 +56,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void bsw_kernel(
     extern __shared__ __align__(16) unsigned char lds[];
     n = (int64_t)*n_list;                              // this kernel walks the list of tasks left to the one-task-per-wave kernels
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t per_wave = (((size_t)(qmax + 1) * 8 + (size_t)qmax + 64 + 15) / 16) * 16;
+    const size_t per_wave = bsw_row_bytes(qmax);
     int2 *eh = reinterpret_cast<int2 *>(lds + wave * per_wave);
     uint8_t *qs = reinterpret_cast<uint8_t *>(eh + (qmax + 1));
 
@@ -994,11 +1000,9 @@ int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint
     {
         // what neither packed form can take: (h, e) row + query of one task per wave in LDS, fewer waves per block for very long queries.
         // Last on the main stream, persistent waves on a small grid: the class is usually empty.
-        const size_t per_wave = (((size_t)(qmax + 1) * 8 + (size_t)qmax + 64 + 15) / 16) * 16;
-        int waves = (int)((size_t)160 * 1024 / per_wave);
-        if (waves < 1) return -2;                  // a query of more than ~18 k bases does not fit a CU's LDS
-        waves = waves < kWavesPerBlock ? waves : kWavesPerBlock;
-        const size_t lds = per_wave * (size_t)waves;
+        const int waves = bsw_lds_waves(qmax);
+        if (waves < 1) return -2;                  // a query of more than 18196 bases does not fit a CU's LDS
+        const size_t lds = bsw_row_bytes(qmax) * (size_t)waves;
         if (lds > 48 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1016,9 +1020,9 @@ int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint
 }
 size_t bsw_list_bytes(int64_t n) { return (size_t)kNumBswClass * (size_t)(n > 0 ? n : 1) * sizeof(int32_t); }
 
-size_t bsw_lds_bytes(int qmax) {
-    const size_t per_wave = (((size_t)(qmax + 1) * 8 + (size_t)qmax + 64 + 15) / 16) * 16;
-    return per_wave * kWavesPerBlock;
+int bsw_lds_waves(int qmax) {
+    const size_t waves = kBswLdsMax / bsw_row_bytes(qmax);
+    return waves < (size_t)kWavesPerBlock ? (int)waves : kWavesPerBlock;
 }
 
 }  // namespace bwams

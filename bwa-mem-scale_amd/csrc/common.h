@@ -194,7 +194,7 @@ int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint
                DevCounters *ctr, int cu_count, hipStream_t st, int32_t *list, hipStream_t *aux = nullptr, hipEvent_t fork = nullptr,
                hipEvent_t *join = nullptr, const int64_t *src = nullptr, int dir = 1);
 size_t bsw_list_bytes(int64_t n_tasks);          // scratch `list` of launch_bsw
-size_t bsw_lds_bytes(int qmax);
+int bsw_lds_waves(int qmax);                     // waves per block of launch_bsw's one-task-per-wave kernel; 0: qmax does not fit
 void launch_emf_probe(const DevEmf &t, const uint8_t *enc, const int64_t *cum, int64_t nseq, uint32_t *out,
                       uint8_t *code, uint8_t *skip, DevCounters *ctr, hipStream_t st);
 constexpr int kKswMaxTarget = 20000;     // longest local-SW target: its row-maxima list must fit the LDS of a 4-wave block

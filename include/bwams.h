@@ -246,7 +246,10 @@ int bwams_bsw_extend(bwams_batch_t *b, bwams_seqpair_t *pairs, int64_t n,
                      const uint8_t *qer, int64_t qer_bytes,
                      int32_t w, const bwams_sw_opt_t *opt);
 
-/* Resident form: upload once, run (async), fetch. */
+/* Resident form: upload once, run (async), fetch.  A query (len2) of more than 18196 bases
+ * is refused with BWAMS_ERR_UNSUPPORTED: the tasks the packed kernels cannot take run one
+ * per wavefront with the query's row in LDS, and one wavefront's row must fit a CU's 160 KiB
+ * (the bound of the extension inside bwams_extend_run too). */
 int bwams_bsw_upload(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n,
                      const uint8_t *ref, int64_t ref_bytes, const uint8_t *qer, int64_t qer_bytes);
 int bwams_bsw_run(bwams_batch_t *b, int32_t w, const bwams_sw_opt_t *opt);

@@ -237,13 +237,11 @@ def test_extension_tasks_match_oracle(rep_toy):
     b.close()
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(extend_all=1), dict(w=12, zdrop=30), dict(w=12, zdrop=30, extend_all=1),
-                                dict(pen_clip5=0, pen_clip3=11), dict(e_del=2, e_ins=3, o_del=4), dict(a=2), dict(a=2, extend_all=1)])
-def test_regions_match_oracle(rep_toy, kw):
-    g, idx, ix = rep_toy
+def _indel_reads(g):
+    """reads with long indels: band retries and clipping decisions"""
     extra = []
     rng = np.random.default_rng(41)
-    for _ in range(200):                          # reads with long indels: band retries and clipping decisions
+    for _ in range(200):
         st = int(rng.integers(0, len(g) - 600))
         a = g[st:st + 70]
         gap = int(rng.integers(5, 60))
@@ -252,11 +250,39 @@ def test_regions_match_oracle(rep_toy, kw):
         else:
             r = np.concatenate([a, rng.integers(0, 4, size=gap, dtype=np.uint8), g[st + 70:st + 150]])
         extra.append(r)
-    b, want, got, ctx = _run(idx, ix, g, _reads(g, 1500, 29, extra), **kw)
+    return extra
+
+
+def _edge_reads(g, edges):
+    """Reads whose alignment starts at one of `edges` (a first base) or ends just before it (a last base), on both strands, with a
+    mismatch or an indel some 20-60 bases in: the seeds begin behind it, and the extension toward the edge reaches it, so the
+    left side's backward in-place read runs down to the edge's offset."""
+    rng = np.random.default_rng(43)
+    out = []
+    for e in edges:
+        for k in range(12):
+            L = int(rng.integers(90, 160))
+            at_start = k % 2 == 0
+            if at_start and e + L > len(g) or not at_start and e - L < 0:
+                continue
+            r = g[e:e + L].copy() if at_start else g[e - L:e].copy()
+            d = int(rng.integers(20, 60))
+            p = d if at_start else L - 1 - d
+            if k % 4 < 2:
+                r[p] = (r[p] + 1) & 3
+            else:
+                r = np.delete(r, p)
+            out.append(simulate.revcomp(r) if k % 3 == 0 else r)
+    return out
+
+
+def _regions_case(rep_toy, kw, extra=(), contigs=None):
+    g, idx, ix = rep_toy
+    b, want, got, ctx = _run(idx, ix, g, _reads(g, 1500, 29, _indel_reads(g) + list(extra)), contigs=contigs, **kw)
     n = b.extend_run(ctx["gopt"])
     regs, reg_off, aln = b.extend_fetch()
     wregs, wreg_off, wseeds, tasks_all = loader.chain2aln(want["chains"], want["seeds"], want["chain_off"], ctx["enc"], ctx["cum"],
-                                                          ctx["ref"], ctx["l_pac"], opt=ctx["oopt"], want_tasks=True)
+                                                          ctx["ref"], ctx["l_pac"], contigs=contigs, opt=ctx["oopt"], want_tasks=True)
     assert n == len(wregs) and np.array_equal(reg_off, wreg_off) and np.array_equal(aln, wseeds["aln"])
     _assert_regs(regs, wregs, bool(kw.get("extend_all")))
     st = b.stats()
@@ -271,6 +297,50 @@ def test_regions_match_oracle(rep_toy, kw):
         purged = (regs["qb"] == -1) & (regs["qe"] == -1)
         assert purged.sum() > 0 and (~purged).sum() > 0
     b.close()
+    if contigs is not None:
+        c = np.zeros(1, capi.CONTIG_DTYPE)
+        c["len"] = ctx["l_pac"]
+        ix.set_contigs(c)
+    return wregs
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(extend_all=1), dict(w=12, zdrop=30), dict(w=12, zdrop=30, extend_all=1),
+                                dict(pen_clip5=0, pen_clip3=11), dict(e_del=2, e_ins=3, o_del=4), dict(a=2), dict(a=2, extend_all=1)])
+def test_regions_match_oracle(rep_toy, kw):
+    _regions_case(rep_toy, kw)
+
+
+@pytest.mark.parametrize("inplace,pk", [("0", "1"), ("1", "0"), ("0", "0"), ("1", "1")])
+@pytest.mark.parametrize("kw", [dict(), dict(w=12, zdrop=30), dict(e_del=2, e_ins=3, o_del=4)])
+def test_regions_under_extension_knobs(rep_toy, monkeypatch, kw, inplace, pk):
+    """BWAMS_EXT_INPLACE=0 (the tasks' bytes copied into flat buffers) and BWAMS_BSW_PK=0 (the eight-task banded-SW kernel) are
+    result-neutral; reads that align from the reference's first base or up to its last one take the in-place left extension
+    down to offset 0 (forward strand) and its right extension up to the end of the text."""
+    monkeypatch.setenv("BWAMS_EXT_INPLACE", inplace)
+    monkeypatch.setenv("BWAMS_BSW_PK", pk)
+    capi.debug_reload()                                       # the switches are read once: say that they changed
+    g = rep_toy[0]
+    wregs = _regions_case(rep_toy, kw, _edge_reads(g, [0, len(g)]))
+    l_pac = len(g)
+    assert ((wregs["rb"] == 0) | (wregs["re"] == 2 * l_pac) | (wregs["re"] == l_pac) | (wregs["rb"] == l_pac)).sum() >= 4
+
+
+@pytest.mark.parametrize("inplace,pk", [("0", "0"), ("1", "1")])
+def test_regions_at_contig_edges(rep_toy, monkeypatch, inplace, pk):
+    """Extension windows clipped to the contig of the chain, with reads that align from a contig's first base or up to its last."""
+    monkeypatch.setenv("BWAMS_EXT_INPLACE", inplace)
+    monkeypatch.setenv("BWAMS_BSW_PK", pk)
+    capi.debug_reload()
+    g = rep_toy[0]
+    l_pac = len(g)
+    contigs = np.zeros(4, capi.CONTIG_DTYPE)
+    contigs["offset"] = [0, 30000, 30150, 90000]
+    contigs["len"] = [30000, 150, 59850, l_pac - 90000]
+    contigs["is_alt"] = [0, 0, 1, 0]
+    wregs = _regions_case(rep_toy, dict(), _edge_reads(g, [0, 30000, 30150, 90000, l_pac]), contigs=contigs)
+    edges = np.array([0, 30000, 30150, 90000, l_pac])
+    edges = np.concatenate([edges, 2 * l_pac - edges])
+    assert (np.isin(wregs["rb"], edges) | np.isin(wregs["re"], edges)).sum() >= 8
 
 
 def test_round_cap_extends_the_rest(rep_toy, monkeypatch):

@@ -7,7 +7,8 @@ import pytest
 
 from oracle import loader
 from ref_answers import Answers
-from util import OUT_FIELDS, assert_pairs_equal, make_pairs
+from util import (BSW_SCORING_EDGES, BSW_WIDE_W, OUT_FIELDS, assert_pairs_equal, bsw_class_edge_tasks, bsw_n_run_tasks, bsw_score_limit_tasks,
+                  bsw_scoring_edge_tasks, bsw_sw_opt, bsw_wide_band_tasks, make_pairs)
 
 REF = loader.ref_lib()
 
@@ -23,6 +24,45 @@ def test_restatement_equals_reference_scalar(w, end_bonus, zdrop):
     assert_pairs_equal(ours, theirs, "scalar")
     assert cells > 0
 
+
+
+def _outputs(p):
+    return np.stack([p[f] for f in OUT_FIELDS], axis=1)
+
+
+def _pin(tasks, w, opt):
+    """the restatement equals scalarBandedSWA on these tasks (the answers are stored as the six output fields)"""
+    pairs, ref, qer = tasks
+    ours, _ = loader.bsw_pairs(pairs, ref, qer, w, opt)
+    theirs = Answers(REF is not None)(lambda: _outputs(loader.ref_bsw(REF, "scalar", pairs, ref, qer, w, opt))).reshape(-1, len(OUT_FIELDS))
+    bad = np.flatnonzero((_outputs(ours) != theirs).any(axis=1))
+    assert bad.size == 0, f"{bad.size} tasks differ, first {pairs[bad[0]]}: ours {_outputs(ours)[bad[0]]}, reference {theirs[bad[0]]}"
+
+
+# The edge families of tests/test_gpu_bsw.py: the GPU kernels are compared with the restatement on exactly these inputs.
+@pytest.mark.parametrize("a", [1, 5])
+def test_reference_scalar_at_the_score_limits(a):
+    """scores up to 2^14 + 1 at every class edge, h0 up to 10^6, h0 = 0 and h0 < 0"""
+    _pin(bsw_score_limit_tasks(a), 100, bsw_sw_opt(loader, a=a))
+
+
+@pytest.mark.parametrize("w", [100, 5])
+def test_reference_scalar_at_the_class_edges(w):
+    _pin(bsw_class_edge_tasks(w), w, bsw_sw_opt(loader))
+
+
+@pytest.mark.parametrize("w", BSW_WIDE_W)
+def test_reference_scalar_in_wide_bands(w):
+    _pin(bsw_wide_band_tasks(), w, bsw_sw_opt(loader))
+
+
+def test_reference_scalar_with_runs_of_n():
+    _pin(bsw_n_run_tasks(), 100, bsw_sw_opt(loader))
+
+
+@pytest.mark.parametrize("a,gaps,n_score", BSW_SCORING_EDGES, ids=lambda v: str(v).replace(" ", ""))
+def test_reference_scalar_at_the_scoring_edges(a, gaps, n_score):
+    _pin(bsw_scoring_edge_tasks(a, seed=sum(gaps) + a), 100, bsw_sw_opt(loader, a=a, gaps=gaps, n_score=n_score))
 
 def _ref_ksw_extend2(opt, q, t, w, h0):
     o = [C.c_int() for _ in range(5)]
