@@ -74,13 +74,12 @@ static int check_device(int device) {
 
 void chain_state_stats(const ChainState *s, bwams_stats_t *out);   // api_chain.hip
 
-int bsw_list_ensure(bwams_batch *b, int64_t n_tasks) {
-    if (n_tasks <= b->cap_bsw_list) return BWAMS_OK;
-    BWAMS_HIP(hipStreamSynchronize(b->stream));
-    if (b->d_bsw_list) (void)hipFree(b->d_bsw_list);
-    b->d_bsw_list = nullptr;
-    b->cap_bsw_list = n_tasks + n_tasks / 4 + 1024;
-    BWAMS_HIP(dev_malloc(&b->d_bsw_list, bsw_list_bytes(b->cap_bsw_list)));
+int tmp_reserve(bwams_batch *b, size_t &tb) {
+    if (tb > b->d_tmp.cap) {
+        BWAMS_HIP(hipStreamSynchronize(b->stream));
+        BWAMS_HIP(b->d_tmp.alloc(tb));
+    }
+    tb = b->d_tmp.cap;
     return BWAMS_OK;
 }
 int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int keep_ref, int64_t chunk_rows, int verbose,
@@ -124,12 +123,12 @@ int bwams_device_count(int *n) {
 
 /* ------------------------------------------------------------------ index -- */
 
-static int index_finish(bwams_index *ix, const bwams_fmi_desc_t *d) {
-    ix->fmi.cp = reinterpret_cast<const uint4 *>(ix->d_cp);
+static int index_finish(bwams_index *ix, const bwams_fmi_desc_t *d, const void *cp, const void *ms, const void *ls, const void *ref) {
+    ix->fmi.cp = reinterpret_cast<const uint4 *>(cp);
     ix->fmi.cp2 = nullptr;
-    ix->fmi.sa_ms = reinterpret_cast<const int8_t *>(ix->d_ms);
-    ix->fmi.sa_ls = reinterpret_cast<const uint32_t *>(ix->d_ls);
-    ix->fmi.ref = reinterpret_cast<const uint8_t *>(ix->d_ref);
+    ix->fmi.sa_ms = reinterpret_cast<const int8_t *>(ms);
+    ix->fmi.sa_ls = reinterpret_cast<const uint32_t *>(ls);
+    ix->fmi.ref = reinterpret_cast<const uint8_t *>(ref);
     if (d->ref_seq_len >= ((int64_t)1 << 36)) {
         set_last_error("text longer than 2^36 rows is not supported by the 36-bit interval packing");
         return BWAMS_ERR_UNSUPPORTED;
@@ -155,9 +154,9 @@ int bwams_index_from_host(const bwams_fmi_desc_t *d, int device, bwams_index_t *
     const size_t b_cp = (size_t)ix->n_blk * 64, b_ms = (size_t)ix->n_sa, b_ls = (size_t)ix->n_sa * 4;
     const size_t b_ref = d->ref_0123 ? (size_t)(d->ref_seq_len - 1) : 0;
     // a failed allocation or copy must not strand the multi-GB buffers already made: close the handle on the way out
-    auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = dev_malloc(dst, bytes + 64);          // slack: kernels read whole aligned words
-        return e != hipSuccess ? e : hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    auto up = [&](DevBuf<> *dst, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = dst->alloc(bytes + 64);               // slack: kernels read whole aligned words
+        return e != hipSuccess ? e : hipMemcpy(dst->p, src, bytes, hipMemcpyHostToDevice);
     };
     hipError_t ue = up(&ix->d_cp, d->cp_occ, b_cp);
     if (ue == hipSuccess) ue = up(&ix->d_ms, d->sa_ms_byte, b_ms);
@@ -168,7 +167,7 @@ int bwams_index_from_host(const bwams_fmi_desc_t *d, int device, bwams_index_t *
         BWAMS_HIP(ue);
     }
     ix->bytes = (int64_t)(b_cp + b_ms + b_ls + b_ref);
-    int frc = index_finish(ix, d);
+    int frc = index_finish(ix, d, ix->d_cp.p, ix->d_ms.p, ix->d_ls.p, ix->d_ref.p);
     if (frc) { bwams_index_close(ix); return frc; }
     *out = ix;
     return BWAMS_OK;
@@ -183,15 +182,10 @@ int bwams_index_from_device(const bwams_fmi_desc_t *d, int device, bwams_index_t
     if (rc) return rc;
     bwams_index *ix = new bwams_index();
     ix->device = device;
-    ix->owns = false;
     ix->n_blk = (d->ref_seq_len >> 6) + 1;
     ix->n_sa = (d->ref_seq_len >> 3) + 1;
-    ix->d_cp = const_cast<bwams_cp_occ_t *>(d->cp_occ);
-    ix->d_ms = const_cast<int8_t *>(d->sa_ms_byte);
-    ix->d_ls = const_cast<uint32_t *>(d->sa_ls_word);
-    ix->d_ref = const_cast<uint8_t *>(d->ref_0123);
     ix->bytes = ix->n_blk * 64 + ix->n_sa * 5 + (d->ref_0123 ? d->ref_seq_len - 1 : 0);
-    int frc = index_finish(ix, d);
+    int frc = index_finish(ix, d, d->cp_occ, d->sa_ms_byte, d->sa_ls_word, d->ref_0123);
     if (frc) { bwams_index_close(ix); return frc; }
     *out = ix;
     return BWAMS_OK;
@@ -292,16 +286,15 @@ int bwams_index_build(const uint8_t *fw, int64_t l_pac, int fw_on_device, int de
     int rc = check_device(device);
     if (rc) return rc;
     BWAMS_HIP(hipSetDevice(device));
-    void *staged = nullptr;
+    DevBuf<uint8_t> staged;
     if (!fw_on_device) {
-        BWAMS_HIP(dev_malloc(&staged, (size_t)l_pac));
-        hipError_t e = hipMemcpy(staged, fw, (size_t)l_pac, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(staged); BWAMS_HIP(e); }
+        BWAMS_HIP(staged.alloc((size_t)l_pac));
+        BWAMS_HIP(hipMemcpy(staged.p, fw, (size_t)l_pac, hipMemcpyHostToDevice));
     }
     bwams_index *ix = new bwams_index();
     ix->device = device;
-    rc = fmi_build_device(ix, staged ? (const uint8_t *)staged : fw, l_pac, keep_ref, chunk_rows, knobs().verbose != 0, stats);
-    if (staged) (void)hipFree(staged);
+    rc = fmi_build_device(ix, staged.p ? staged.p : fw, l_pac, keep_ref, chunk_rows, knobs().verbose != 0, stats);
+    staged.release();
     if (rc) { bwams_index_close(ix); return rc; }
     *out = ix;
     return BWAMS_OK;
@@ -311,15 +304,15 @@ int bwams_index_fetch(bwams_index_t *ix, bwams_cp_occ_t *cp_occ, int8_t *sa_ms_b
                       bwams_fmi_desc_t *d) {
     if (!ix) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (cp_occ) BWAMS_HIP(hipMemcpy(cp_occ, ix->d_cp, (size_t)ix->n_blk * 64, hipMemcpyDeviceToHost));
-    if (sa_ms_byte) BWAMS_HIP(hipMemcpy(sa_ms_byte, ix->d_ms, (size_t)ix->n_sa, hipMemcpyDeviceToHost));
-    if (sa_ls_word) BWAMS_HIP(hipMemcpy(sa_ls_word, ix->d_ls, (size_t)ix->n_sa * 4, hipMemcpyDeviceToHost));
+    if (cp_occ) BWAMS_HIP(hipMemcpy(cp_occ, ix->fmi.cp, (size_t)ix->n_blk * 64, hipMemcpyDeviceToHost));
+    if (sa_ms_byte) BWAMS_HIP(hipMemcpy(sa_ms_byte, ix->fmi.sa_ms, (size_t)ix->n_sa, hipMemcpyDeviceToHost));
+    if (sa_ls_word) BWAMS_HIP(hipMemcpy(sa_ls_word, ix->fmi.sa_ls, (size_t)ix->n_sa * 4, hipMemcpyDeviceToHost));
     if (ref_0123) {
-        if (!ix->d_ref) {
+        if (!ix->fmi.ref) {
             set_last_error("bwams_index_fetch: the index holds no .0123 text");
             return BWAMS_ERR_ARG;
         }
-        BWAMS_HIP(hipMemcpy(ref_0123, ix->d_ref, (size_t)(ix->fmi.ref_seq_len - 1), hipMemcpyDeviceToHost));
+        BWAMS_HIP(hipMemcpy(ref_0123, ix->fmi.ref, (size_t)(ix->fmi.ref_seq_len - 1), hipMemcpyDeviceToHost));
     }
     if (d) {
         memset(d, 0, sizeof *d);
@@ -353,18 +346,18 @@ int bwams_index_save(bwams_index_t *ix, const char *prefix) {
     hdr[0] = ix->fmi.ref_seq_len;
     for (int i = 0; i < 5; ++i) hdr[1 + i] = ix->fmi.count[i] - 1;          // the file holds them without the loader's +1
     int rc = fwrite(hdr, 8, 6, f) == 6 ? BWAMS_OK : BWAMS_ERR_IO;
-    if (!rc) rc = stream_out(f, ix->d_cp, (size_t)ix->n_blk * 64);
-    if (!rc) rc = stream_out(f, ix->d_ms, (size_t)ix->n_sa);
-    if (!rc) rc = stream_out(f, ix->d_ls, (size_t)ix->n_sa * 4);
+    if (!rc) rc = stream_out(f, ix->fmi.cp, (size_t)ix->n_blk * 64);
+    if (!rc) rc = stream_out(f, ix->fmi.sa_ms, (size_t)ix->n_sa);
+    if (!rc) rc = stream_out(f, ix->fmi.sa_ls, (size_t)ix->n_sa * 4);
     const int64_t sent = ix->fmi.sentinel;
     if (!rc && fwrite(&sent, 8, 1, f) != 1) rc = BWAMS_ERR_IO;
     if (fclose(f) != 0 && !rc) rc = BWAMS_ERR_IO;
-    if (!rc && ix->d_ref) {
+    if (!rc && ix->fmi.ref) {
         path = std::string(prefix) + ".0123";
         f = fopen(path.c_str(), "wb");
         if (!f) rc = BWAMS_ERR_IO;
         else {
-            rc = stream_out(f, ix->d_ref, (size_t)(ix->fmi.ref_seq_len - 1));
+            rc = stream_out(f, ix->fmi.ref, (size_t)(ix->fmi.ref_seq_len - 1));
             if (fclose(f) != 0 && !rc) rc = BWAMS_ERR_IO;
         }
     }
@@ -375,37 +368,8 @@ int bwams_index_save(bwams_index_t *ix, const char *prefix) {
 
 int bwams_index_close(bwams_index_t *ix) {
     if (!ix) return BWAMS_OK;
-    bns_free(ix);
-    if (ix->d_cp2) { (void)hipSetDevice(ix->device); (void)hipFree(ix->d_cp2); ix->d_cp2 = nullptr; }
-    if (ix->owns) {
-        (void)hipSetDevice(ix->device);
-        (void)hipFree(ix->d_cp);
-        (void)hipFree(ix->d_ms);
-        (void)hipFree(ix->d_ls);
-        if (ix->d_ref) (void)hipFree(ix->d_ref);
-    }
-    if (ix->d_contigs) {
-        (void)hipSetDevice(ix->device);
-        (void)hipFree(ix->d_contigs);
-    }
-    if (ix->d_ctg_annos) {
-        (void)hipFree(ix->d_ctg_annos);
-        (void)hipFree(ix->d_ctg_anno_off);
-    }
-    if (ix->d_ctg_names) {
-        (void)hipSetDevice(ix->device);
-        (void)hipFree(ix->d_ctg_names);
-        (void)hipFree(ix->d_ctg_off);
-    }
-    if (ix->d_ctg_sorted) {
-        (void)hipSetDevice(ix->device);
-        (void)hipFree(ix->d_ctg_sorted);
-    }
-    if (ix->d_all || ix->d_last) {
-        (void)hipSetDevice(ix->device);
-        if (ix->d_all) (void)hipFree(ix->d_all);
-        if (ix->d_last) (void)hipFree(ix->d_last);
-    }
+    (void)hipSetDevice(ix->device);
+    delete ix->bns;
     delete ix;
     return BWAMS_OK;
 }
@@ -420,19 +384,18 @@ static int fma_alloc(bwams_index *ix, int all_bp, int last_bp) {
         return BWAMS_ERR_ARG;
     }
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (ix->d_all) (void)hipFree(ix->d_all);
-    if (ix->d_last) (void)hipFree(ix->d_last);
-    ix->d_all = ix->d_last = nullptr;
+    ix->d_all.release();
+    ix->d_last.release();
     ix->fmi.all_smem = nullptr;
     ix->fmi.last_smem = nullptr;
-    BWAMS_HIP(dev_malloc(&ix->d_all, ((size_t)1 << (2 * all_bp)) * 128));
-    BWAMS_HIP(dev_malloc(&ix->d_last, ((size_t)1 << (2 * last_bp)) * 16));
+    BWAMS_HIP(ix->d_all.alloc(((size_t)1 << (2 * all_bp)) * 128));
+    BWAMS_HIP(ix->d_last.alloc(((size_t)1 << (2 * last_bp)) * 16));
     return BWAMS_OK;
 }
 
 static void fma_attach(bwams_index *ix, int all_bp, int last_bp) {
-    ix->fmi.all_smem = reinterpret_cast<const uint32_t *>(ix->d_all);
-    ix->fmi.last_smem = reinterpret_cast<const uint4 *>(ix->d_last);
+    ix->fmi.all_smem = ix->d_all.as<const uint32_t>();
+    ix->fmi.last_smem = ix->d_last.as<const uint4>();
     ix->fmi.all_bp = all_bp;
     ix->fmi.last_bp = last_bp;
 }
@@ -441,8 +404,7 @@ int bwams_index_build_fma(bwams_index_t *ix, int all_bp, int last_bp) {
     if (!ix) return BWAMS_ERR_ARG;
     int rc = fma_alloc(ix, all_bp, last_bp);
     if (rc) return rc;
-    launch_build_fma(ix->fmi, all_bp, reinterpret_cast<uint32_t *>(ix->d_all), last_bp,
-                     reinterpret_cast<uint4 *>(ix->d_last), nullptr);
+    launch_build_fma(ix->fmi, all_bp, ix->d_all.as<uint32_t>(), last_bp, ix->d_last.as<uint4>(), nullptr);
     BWAMS_HIP(hipGetLastError());
     BWAMS_HIP(hipDeviceSynchronize());
     fma_attach(ix, all_bp, last_bp);
@@ -458,17 +420,17 @@ int bwams_index_set_fma(bwams_index_t *ix, const void *all_smem, int all_bp, con
     }
     int rc = fma_alloc(ix, all_bp, last_bp);
     if (rc) return rc;
-    BWAMS_HIP(hipMemcpy(ix->d_all, all_smem, ((size_t)1 << (2 * all_bp)) * 128, hipMemcpyHostToDevice));
-    BWAMS_HIP(hipMemcpy(ix->d_last, last_smem, ((size_t)1 << (2 * last_bp)) * 16, hipMemcpyHostToDevice));
+    BWAMS_HIP(hipMemcpy(ix->d_all.p, all_smem, ((size_t)1 << (2 * all_bp)) * 128, hipMemcpyHostToDevice));
+    BWAMS_HIP(hipMemcpy(ix->d_last.p, last_smem, ((size_t)1 << (2 * last_bp)) * 16, hipMemcpyHostToDevice));
     fma_attach(ix, all_bp, last_bp);
     return BWAMS_OK;
 }
 
 int bwams_index_fetch_fma(bwams_index_t *ix, void *all_smem, void *last_smem) {
-    if (!ix || !ix->d_all || !ix->d_last) return BWAMS_ERR_ARG;
+    if (!ix || !ix->d_all.p || !ix->d_last.p) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (all_smem) BWAMS_HIP(hipMemcpy(all_smem, ix->d_all, ((size_t)1 << (2 * ix->fmi.all_bp)) * 128, hipMemcpyDeviceToHost));
-    if (last_smem) BWAMS_HIP(hipMemcpy(last_smem, ix->d_last, ((size_t)1 << (2 * ix->fmi.last_bp)) * 16, hipMemcpyDeviceToHost));
+    if (all_smem) BWAMS_HIP(hipMemcpy(all_smem, ix->d_all.p, ((size_t)1 << (2 * ix->fmi.all_bp)) * 128, hipMemcpyDeviceToHost));
+    if (last_smem) BWAMS_HIP(hipMemcpy(last_smem, ix->d_last.p, ((size_t)1 << (2 * ix->fmi.last_bp)) * 16, hipMemcpyDeviceToHost));
     return BWAMS_OK;
 }
 
@@ -476,23 +438,21 @@ int bwams_index_fetch_fma(bwams_index_t *ix, void *all_smem, void *last_smem) {
 
 // (re)allocate every buffer whose size follows max_smem; the batch grows them when a chunk needs more
 static int alloc_smem_buffers(bwams_batch *b, int64_t max_smem) {
-    void **ptrs[] = {(void **)&b->d_pool, (void **)&b->d_sorted, (void **)&b->d_keys, (void **)&b->d_keys2, (void **)&b->d_vals,
-                     (void **)&b->d_vals2, (void **)&b->d_work2, (void **)&b->d_sa_off, (void **)&b->d_sa_cnt};
-    for (void **p : ptrs)
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    b->d_pool.release(); b->d_sorted.release(); b->d_keys.release(); b->d_keys2.release(); b->d_vals.release();   // all of the old set
+    b->d_vals2.release(); b->d_work2.release(); b->d_sa_off.release(); b->d_sa_cnt.release();                     // goes first
     b->max_smem = max_smem;
     // the pool is handed out in per-wave chunks: room for every wave's partly filled last chunk
     // of each of the five emitting launches on top of the max_smem real records
     b->pool_cap = b->max_smem + seed_pool_slack(b->cu_count);
-    BWAMS_HIP(dev_malloc(&b->d_pool, (size_t)b->pool_cap * sizeof(bwams_smem_t)));
-    BWAMS_HIP(dev_malloc(&b->d_sorted, (size_t)b->max_smem * sizeof(bwams_smem_t)));
-    BWAMS_HIP(dev_malloc(&b->d_keys, (size_t)b->pool_cap * 8));
-    BWAMS_HIP(dev_malloc(&b->d_keys2, (size_t)b->pool_cap * 8));
-    BWAMS_HIP(dev_malloc(&b->d_vals, (size_t)b->pool_cap * 4));
-    BWAMS_HIP(dev_malloc(&b->d_vals2, (size_t)b->pool_cap * 4));
-    BWAMS_HIP(dev_malloc(&b->d_work2, (size_t)b->pool_cap * sizeof(Round2Work)));
-    BWAMS_HIP(dev_malloc(&b->d_sa_off, (size_t)(b->max_smem + 1) * 8));
-    BWAMS_HIP(dev_malloc(&b->d_sa_cnt, (size_t)(b->max_smem + 1) * 8));
+    BWAMS_HIP(b->d_pool.alloc((size_t)b->pool_cap * sizeof(bwams_smem_t)));
+    BWAMS_HIP(b->d_sorted.alloc((size_t)b->max_smem * sizeof(bwams_smem_t)));
+    BWAMS_HIP(b->d_keys.alloc((size_t)b->pool_cap * 8));
+    BWAMS_HIP(b->d_keys2.alloc((size_t)b->pool_cap * 8));
+    BWAMS_HIP(b->d_vals.alloc((size_t)b->pool_cap * 4));
+    BWAMS_HIP(b->d_vals2.alloc((size_t)b->pool_cap * 4));
+    BWAMS_HIP(b->d_work2.alloc((size_t)b->pool_cap * sizeof(Round2Work)));
+    BWAMS_HIP(b->d_sa_off.alloc((size_t)(b->max_smem + 1) * 8));
+    BWAMS_HIP(b->d_sa_cnt.alloc((size_t)(b->max_smem + 1) * 8));
     return BWAMS_OK;
 }
 
@@ -514,23 +474,22 @@ static int batch_create_fill(bwams_batch *b, bwams_index_t *ix, int64_t max_read
     for (auto &e : b->ev) BWAMS_HIP(hipEventCreate(&e));
     for (auto &e : b->ev_emf) BWAMS_HIP(hipEventCreate(&e));
 
-    BWAMS_HIP(dev_malloc(&b->d_enc, (size_t)max_bases + 64));
-    BWAMS_HIP(dev_malloc(&b->d_cum, (size_t)(max_reads + 1) * 8));
-    BWAMS_HIP(dev_malloc(&b->d_skip, (size_t)max_reads));
+    BWAMS_HIP(b->d_enc.alloc((size_t)max_bases + 64));
+    BWAMS_HIP(b->d_cum.alloc((size_t)(max_reads + 1) * 8));
+    BWAMS_HIP(b->d_skip.alloc((size_t)max_reads));
     if (int arc = alloc_smem_buffers(b, b->max_smem)) return arc;
-    BWAMS_HIP(dev_malloc(&b->d_sa_coord, (size_t)b->max_sa * 8));
-    BWAMS_HIP(dev_malloc(&b->d_ctr, sizeof(DevCounters)));
-    BWAMS_HIP(hipHostMalloc(&b->h_ctr, sizeof(DevCounters)));
-    BWAMS_HIP(hipMemset(b->d_ctr, 0, sizeof(DevCounters)));
+    BWAMS_HIP(b->d_sa_coord.alloc((size_t)b->max_sa * 8));
+    BWAMS_HIP(b->d_ctr.alloc(sizeof(DevCounters)));
+    BWAMS_HIP(b->h_ctr.alloc(sizeof(DevCounters)));
+    BWAMS_HIP(hipMemset(b->d_ctr.p, 0, sizeof(DevCounters)));
 
     // rocPRIM temporary storage for the largest sort / scan this batch can issue
     size_t t1 = 0, t2 = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, t1, b->d_keys, b->d_keys2, b->d_vals, b->d_vals2,
+    (void)rocprim::radix_sort_pairs(nullptr, t1, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p,
                               (size_t)b->max_smem, 0, 64, b->stream);
-    (void)rocprim::exclusive_scan(nullptr, t2, b->d_sa_cnt, b->d_sa_off, (int64_t)0, (size_t)b->max_smem + 1,
+    (void)rocprim::exclusive_scan(nullptr, t2, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)b->max_smem + 1,
                             rocprim::plus<int64_t>(), b->stream);
-    b->tmp_bytes = std::max(t1, t2);
-    BWAMS_HIP(dev_malloc(&b->d_tmp, b->tmp_bytes));
+    BWAMS_HIP(b->d_tmp.alloc(std::max(t1, t2)));
     return BWAMS_OK;
 }
 
@@ -553,11 +512,6 @@ int bwams_batch_destroy(bwams_batch_t *b) {
     if (!b) return BWAMS_OK;
     (void)hipSetDevice(b->idx->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    void *ptrs[] = {b->d_enc, b->d_cum, b->d_skip, b->d_pool, b->d_sorted, b->d_keys, b->d_keys2, b->d_vals,
-                    b->d_vals2, b->d_work2, b->d_sa_off, b->d_sa_cnt, b->d_sa_coord, b->d_tmp, b->d_ctr, b->d_prev, b->d_packed, b->d_emf_out, b->d_emf_code, b->d_ksw_out, b->d_bsw_list, b->d_pairs, b->d_ref, b->d_qer, b->d_ert_prof, b->d_ert_stk, b->d_ert_redo, b->d_bwd_items, b->d_bwd_ent};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (b->h_ctr) (void)hipHostFree(b->h_ctr);
     if (b->chain) chain_state_free(b->chain);
     for (auto &e : b->ev)
         if (e) (void)hipEventDestroy(e);
@@ -608,9 +562,9 @@ int bwams_seed_upload(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, 
     b->has_skip = skip != nullptr;
     b->seed_done = false;
     // enc may already live in this GPU's memory (a caller that keeps several chunks resident): the copy kind is inferred
-    if (nb) BWAMS_HIP(hipMemcpyAsync(b->d_enc, enc, (size_t)nb, hipMemcpyDefault, b->stream));
-    BWAMS_HIP(hipMemcpyAsync(b->d_cum, cum, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, b->stream));
-    if (skip && nseq) BWAMS_HIP(hipMemcpyAsync(b->d_skip, skip, (size_t)nseq, hipMemcpyHostToDevice, b->stream));
+    if (nb) BWAMS_HIP(hipMemcpyAsync(b->d_enc.p, enc, (size_t)nb, hipMemcpyDefault, b->stream));
+    BWAMS_HIP(hipMemcpyAsync(b->d_cum.p, cum, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    if (skip && nseq) BWAMS_HIP(hipMemcpyAsync(b->d_skip.p, skip, (size_t)nseq, hipMemcpyHostToDevice, b->stream));
     // the source buffers belong to the caller: do not return before they are consumed
     BWAMS_HIP(hipStreamSynchronize(b->stream));
 
@@ -622,21 +576,14 @@ int bwams_seed_upload(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, 
         b->read_w = W;
         b->read_cw = cw;
         const int64_t need = (int64_t)W * (nseq > 0 ? nseq : 1);
-        if (need > b->packed_cap) {
-            if (b->d_packed) (void)hipFree(b->d_packed);
-            b->d_packed = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_packed, (size_t)need * 4));
-            b->packed_cap = need;
-        }
+        BWAMS_HIP(b->d_packed.ensure((size_t)need * 4, (size_t)need * 4));
     }
     // per-lane scratch for the previous-interval lists: (longest read + 1) entries per lane
     const int cap = mx + 1;
     const int64_t threads = seed_max_threads(b->cu_count);
     if (cap > b->prev_cap || threads > b->prev_threads) {
-        if (b->d_prev) (void)hipFree(b->d_prev);
-        b->d_prev = nullptr;
         const size_t n = (size_t)cap * (size_t)threads;
-        BWAMS_HIP(dev_malloc(&b->d_prev, n * 16));
+        BWAMS_HIP(b->d_prev.alloc(n * 16));
         b->prev_cap = cap;
         b->prev_threads = threads;
     }
@@ -646,11 +593,9 @@ int bwams_seed_upload(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, 
     // lane, about half a pivot per read in flight, profiles/r04_notes.md)
     const int64_t bi = std::max<int64_t>(nseq, 4096) * 2, be = std::max<int64_t>(nseq, 4096) * 24;
     if (bi > b->bwd_items_cap) {
-        if (b->d_bwd_items) (void)hipFree(b->d_bwd_items);
-        if (b->d_bwd_ent) (void)hipFree(b->d_bwd_ent);
-        b->d_bwd_items = nullptr; b->d_bwd_ent = nullptr; b->bwd_items_cap = b->bwd_ent_cap = 0;
-        BWAMS_HIP(dev_malloc(&b->d_bwd_items, (size_t)bi * 2 * sizeof(BwdItem)));
-        BWAMS_HIP(dev_malloc(&b->d_bwd_ent, (size_t)be * 16));
+        b->d_bwd_items.release(); b->d_bwd_ent.release(); b->bwd_items_cap = b->bwd_ent_cap = 0;
+        BWAMS_HIP(b->d_bwd_items.alloc((size_t)bi * 2 * sizeof(BwdItem)));
+        BWAMS_HIP(b->d_bwd_ent.alloc((size_t)be * 16));
         b->bwd_items_cap = bi;
         b->bwd_ent_cap = be;
     }
@@ -672,8 +617,7 @@ int bwams_seed_run(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with_sa) {
         const int64_t seen = std::max(b->n_smem, b->n_pool_slots - seed_pool_slack(b->cu_count));
         const int64_t need = std::max(seen, b->max_smem) + seen / 4 + 1024;
         if ((rc = alloc_smem_buffers(b, need))) return rc;
-        b->tmp_bytes = 0;                           // rocPRIM scratch is re-queried per call
-        if (b->d_tmp) { (void)hipFree(b->d_tmp); b->d_tmp = nullptr; }
+        b->d_tmp.release();                         // rocPRIM scratch is re-queried per call
         rc = seed_run_once(b, opt, with_sa);
     }
     return rc;
@@ -692,41 +636,37 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     {
         bwams_index *ix = b->idx;
         std::lock_guard<std::mutex> lock(ix->cp2_mu);
-        if (!ix->d_cp2) {
-            void *t = nullptr;
-            hipError_t e = dev_malloc(&t, cp2_bytes(ix->n_blk));
-            if (e == hipSuccess) {
-                launch_cp2_build(reinterpret_cast<const uint4 *>(ix->d_cp), ix->n_blk, reinterpret_cast<uint4 *>(t), st);
-                e = hipStreamSynchronize(st);
-                if (e != hipSuccess) (void)hipFree(t);
-            }
-            BWAMS_HIP(e);
-            ix->d_cp2 = t;
+        if (!ix->d_cp2.p) {
+            DevBuf<> t;
+            BWAMS_HIP(t.alloc(cp2_bytes(ix->n_blk)));
+            launch_cp2_build(ix->fmi.cp, ix->n_blk, t.as<uint4>(), st);
+            BWAMS_HIP(hipStreamSynchronize(st));
+            ix->d_cp2 = std::move(t);
         }
-        cp2 = reinterpret_cast<const uint4 *>(ix->d_cp2);
+        cp2 = ix->d_cp2.as<const uint4>();
     }
     SeedLaunch a;
     a.fmi = b->idx->fmi;
     a.fmi.cp2 = cp2;
-    a.enc = b->d_enc;
-    a.cum = b->d_cum;
-    a.skip = b->has_skip ? b->d_skip : nullptr;
+    a.enc = b->d_enc.p;
+    a.cum = b->d_cum.p;
+    a.skip = b->has_skip ? b->d_skip.p : nullptr;
     a.nseq = b->nseq;
-    a.packed = b->d_packed;
+    a.packed = b->d_packed.p;
     a.read_w = b->read_w;
     a.read_cw = b->read_cw;
     a.reads_in_lds = b->read_w <= 40;      // 40 words x 256 lanes x 4 B = 40 KB per workgroup
     a.debug = knobs().debug;
     a.min_seed_len = opt->min_seed_len;
-    a.pool = b->d_pool;
+    a.pool = b->d_pool.p;
     a.pool_cap = b->pool_cap;
-    a.ctr = b->d_ctr;
-    a.prev = b->d_prev;
+    a.ctr = b->d_ctr.p;
+    a.prev = b->d_prev.p;
     a.prev_cap = b->prev_cap;
     a.prev_threads = b->prev_threads;
-    a.bwd_items = b->d_bwd_items;
-    a.bwd_items_s = b->d_bwd_items + b->bwd_items_cap;
-    a.bwd_ent = b->d_bwd_ent;
+    a.bwd_items = b->d_bwd_items.p;
+    a.bwd_items_s = b->d_bwd_items.p + b->bwd_items_cap;
+    a.bwd_ent = b->d_bwd_ent.p;
     a.bwd_items_cap = b->bwd_items_cap;
     a.bwd_ent_cap = b->bwd_ent_cap;
     {   // hand-over thresholds (fmi_seed.hip, bwd_hand_over; profiles/r03_notes.md 86): 40 entries at the forward end, or 8 still alive
@@ -743,10 +683,10 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     const int split_len = (int)(opt->min_seed_len * opt->split_factor + .499);
 
     // events: 0 start | 8,9 round-1 kernel | 10,11 round-2 kernel | 12,13 round-3 kernel | 3 rounds done
-    BWAMS_HIP(hipMemsetAsync(b->d_ctr, 0, sizeof(DevCounters), st));
+    BWAMS_HIP(hipMemsetAsync(b->d_ctr.p, 0, sizeof(DevCounters), st));
     BWAMS_HIP(hipEventRecord(b->ev[0], st));
-    launch_pack_reads(b->d_enc, b->d_cum, b->nseq, b->read_w, b->read_cw, b->d_packed, st);
-    launch_mark(b->d_ctr, 0, st);
+    launch_pack_reads(b->d_enc.p, b->d_cum.p, b->nseq, b->read_w, b->read_cw, b->d_packed.p, st);
+    launch_mark(b->d_ctr.p, 0, st);
     BWAMS_HIP(hipEventRecord(b->ev[8], st));
     if (b->nseq > 0) launch_smem_round1(a, b->cu_count, st);
 #ifdef BWAMS_BWDDBG
@@ -756,8 +696,8 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
 #endif
     if (b->nseq > 0) launch_smem_bwd_wave(a, b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[9], st));
-    launch_mark(b->d_ctr, 1, st);
-    if (b->nseq > 0) launch_round2_work(a, b->d_work2, b->pool_cap, split_len, opt->split_width, b->cu_count, st);
+    launch_mark(b->d_ctr.p, 1, st);
+    if (b->nseq > 0) launch_round2_work(a, b->d_work2.p, b->pool_cap, split_len, opt->split_width, b->cu_count, st);
     // Round 3 reads nothing of rounds 1 and 2 (bwtSeedStrategyAllPosOneThread walks every read from position 0): it runs beside
     // round 2 on a stream of its own and fills the tail in which round 2's slowest reads keep few lanes busy.  Its extensions and
     // SMEMs are counted apart (n_ext3 / n_blk3 / n_smem3), so that the per-round figures stay exact.
@@ -774,25 +714,25 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
         BWAMS_HIP(hipEventRecord(b->seed_join, b->seed_aux));
     }
     BWAMS_HIP(hipEventRecord(b->ev[10], st));
-    if (b->nseq > 0) launch_smem_round2(a, b->d_work2, b->cu_count, st);
+    if (b->nseq > 0) launch_smem_round2(a, b->d_work2.p, b->cu_count, st);
     if (b->nseq > 0) launch_smem_bwd_wave(a, b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[11], st));
     if (r3_beside) BWAMS_HIP(hipStreamWaitEvent(st, b->seed_join, 0));
-    launch_mark(b->d_ctr, 2, st);
+    launch_mark(b->d_ctr.p, 2, st);
     if (!r3_beside) {
         BWAMS_HIP(hipEventRecord(b->ev[12], st));
         if (r3) launch_smem_round3(a3, opt->max_mem_intv, b->cu_count, st);
         BWAMS_HIP(hipEventRecord(b->ev[13], st));
     }
-    launch_mark(b->d_ctr, 3, st);
+    launch_mark(b->d_ctr.p, 3, st);
     BWAMS_HIP(hipEventRecord(b->ev[3], st));
     BWAMS_HIP(hipGetLastError());
     // the SMEM count sizes the sort: one small read-back
-    BWAMS_HIP(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
 #ifdef BWAMS_BWDDBG
     if (knobs().verbose) {
-        const unsigned long long *d = b->h_ctr->dbg;
+        const unsigned long long *d = b->h_ctr.p->dbg;
         { float m1 = 0, m2 = 0; (void)hipEventElapsedTime(&m1, b->ev[8], dbg_ev); (void)hipEventElapsedTime(&m2, dbg_ev, b->ev[9]);
           fprintf(stderr, "[smem_r1] search kernel %.3f ms, the two backward kernels behind it %.3f ms\n", m1, m2); }
         fprintf(stderr, "[bwd_wave] rounds 1+2: items %llu, column batches %llu (%.1f per item), waves with work %llu: busy mean %.3f ms max %.3f ms, "
@@ -801,7 +741,7 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
         fprintf(stderr, "[bwd_group] rounds 1+2: items %llu, wave-iterations %llu (groups live per iteration %.2f), waves with work %llu: busy mean %.3f ms max %.3f ms; "
                 "first in %.3f last out %.3f ms after round 1's start; [bwd_wave] first in %.3f last out %.3f\n", d[68], d[69], d[69] ? (double)d[70] / d[69] : 0.0, d[72],
                 d[72] ? d[71] * 1e-5 / d[72] : 0.0, d[73] * 1e-5, (~d[75] - ~d[8]) * 1e-5, (d[74] - ~d[8]) * 1e-5, (~d[7] - ~d[8]) * 1e-5, (d[6] - ~d[8]) * 1e-5);
-        fprintf(stderr, "[bwd_group] extensions %llu of %llu (rounds 1+2)\n", d[76], (unsigned long long)b->h_ctr->ext_after[1]);
+        fprintf(stderr, "[bwd_group] extensions %llu of %llu (rounds 1+2)\n", d[76], (unsigned long long)b->h_ctr.p->ext_after[1]);
         const unsigned long long t0 = ~d[8], tdry = ~d[9];
         fprintf(stderr, "[smem_r1] waves %llu: read queue dry at %.3f ms, last wave out at %.3f ms, mean wave life %.3f ms (%.3f ms of it after the queue ran dry); "
                 "iterations %llu, lanes extending per iteration %.1f\n", d[12], (tdry - t0) * 1e-5, (d[10] - t0) * 1e-5, d[12] ? d[11] * 1e-5 / d[12] : 0.0,
@@ -811,8 +751,8 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
         fprintf(stderr, "\n[smem_r1] wave-iterations after the wave first saw the queue dry: %llu, with one lane extending %llu (max per wave %llu), with 2-4 lanes %llu\n", d[64], d[65], d[67], d[66]);
     }
 #endif
-    const int64_t n_slots = (int64_t)b->h_ctr->n_smem_total;      // pool slots handed out (holes included)
-    const int64_t n = (int64_t)b->h_ctr->n_smem_valid;           // real SMEMs
+    const int64_t n_slots = (int64_t)b->h_ctr.p->n_smem_total;      // pool slots handed out (holes included)
+    const int64_t n = (int64_t)b->h_ctr.p->n_smem_valid;           // real SMEMs
     b->n_smem = n;
     b->n_pool_slots = n_slots;
     if (n > b->max_smem || n_slots > b->pool_cap) {
@@ -822,43 +762,29 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     }
     if (n_slots > 0) {
         // key = rid << 32 | m << 16 | n; chunk holes carry rid = nseq and sort behind every read
-        launch_make_keys(b->d_pool, n_slots, b->d_keys, b->d_vals, (uint32_t)b->nseq, st);
+        launch_make_keys(b->d_pool.p, n_slots, b->d_keys.p, b->d_vals.p, (uint32_t)b->nseq, st);
         int rid_bits = 1;
         while (((int64_t)1 << rid_bits) <= b->nseq) rid_bits++;
         size_t tb = 0;      // the temporary size depends on the size / bit range: ask for this call
-        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, b->d_keys, b->d_keys2, b->d_vals, b->d_vals2,
+        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p,
                                             (size_t)n_slots, 0, 32 + rid_bits, st));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(st));
-            (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp, tb, b->d_keys, b->d_keys2, b->d_vals, b->d_vals2,
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp.p, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p,
                                             (size_t)n_slots, 0, 32 + rid_bits, st));
-        launch_gather_sorted(b->d_pool, b->d_vals2, n, b->d_sorted, with_sa ? b->d_sa_cnt : nullptr,
+        launch_gather_sorted(b->d_pool.p, b->d_vals2.p, n, b->d_sorted.p, with_sa ? b->d_sa_cnt.p : nullptr,
                              opt->max_occ, st);
     }
     BWAMS_HIP(hipEventRecord(b->ev[4], st));
     if (with_sa && n > 0) {
         size_t tb = 0;
-        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, b->d_sa_cnt, b->d_sa_off, (int64_t)0, (size_t)n + 1,
+        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
                                           rocprim::plus<int64_t>(), st));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(st));
-            (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(hipMemsetAsync(b->d_sa_cnt + n, 0, 8, st));
-        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp, tb, b->d_sa_cnt, b->d_sa_off, (int64_t)0, (size_t)n + 1,
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(hipMemsetAsync(b->d_sa_cnt.p + n, 0, 8, st));
+        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp.p, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
                                           rocprim::plus<int64_t>(), st));
-        launch_sa_lookup(b->idx->fmi, b->d_sorted, n, b->d_sa_off, b->d_sa_coord, b->max_sa, opt->max_occ,
-                         b->d_ctr, b->cu_count, st);
+        launch_sa_lookup(b->idx->fmi, b->d_sorted.p, n, b->d_sa_off.p, b->d_sa_coord.p, b->max_sa, opt->max_occ,
+                         b->d_ctr.p, b->cu_count, st);
     }
     BWAMS_HIP(hipEventRecord(b->ev[5], st));
     BWAMS_HIP(hipGetLastError());
@@ -866,46 +792,41 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     return BWAMS_OK;
 }
 
-static int ert_redo_ensure(bwams_batch_t *b, int64_t n) {
-    if (n <= b->cap_ert_redo) return BWAMS_OK;
-    if (b->d_ert_redo) (void)hipFree(b->d_ert_redo);
-    b->d_ert_redo = nullptr;
-    b->cap_ert_redo = n + n / 4 + 1024;
-    BWAMS_HIP(dev_malloc(&b->d_ert_redo, (size_t)((b->cap_ert_redo + 31) / 32) * 4));
+static int ert_redo_ensure(bwams_batch_t *b, int64_t n) {           // a bit per seed
+    const int64_t cap = n + n / 4 + 1024;
+    BWAMS_HIP(b->d_ert_redo.ensure((size_t)((n + 31) / 32) * 4, (size_t)((cap + 31) / 32) * 4));
     return BWAMS_OK;
 }
 
 int bwams_seed_counts(bwams_batch_t *b, int64_t *n_smem, int64_t *n_sa) {
     if (!b || !b->seed_done) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    BWAMS_HIP(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
+    BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
     BWAMS_HIP(hipStreamSynchronize(b->stream));
-    b->n_sa = b->with_sa ? (int64_t)b->h_ctr->n_sa_lookups : 0;
+    b->n_sa = b->with_sa ? (int64_t)b->h_ctr.p->n_sa_lookups : 0;
     if (n_smem) *n_smem = b->n_smem;
     if (n_sa) *n_sa = b->n_sa;
     if (b->n_smem > b->max_smem) return BWAMS_ERR_CAPACITY;
     if (b->n_sa > b->max_sa) {
         // the lookup kernel counted every coordinate but stored only max_sa of them: grow and run it again
-        (void)hipFree(b->d_sa_coord);
-        b->d_sa_coord = nullptr;
         b->max_sa = b->n_sa + b->n_sa / 8 + 1024;
-        BWAMS_HIP(dev_malloc(&b->d_sa_coord, (size_t)b->max_sa * 8));
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr->n_sa_lookups, 0, 2 * sizeof(unsigned long long), b->stream));   // + n_lf_steps
+        BWAMS_HIP(b->d_sa_coord.alloc((size_t)b->max_sa * 8));
+        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->n_sa_lookups, 0, 2 * sizeof(unsigned long long), b->stream));   // + n_lf_steps
         if (b->seed_ert) {
-            launch_ert_locate(b->seed_ert->t, b->d_enc, b->d_cum, b->d_sorted, b->n_smem, b->d_sa_cnt, b->last_seed_opt.max_occ,
-                              b->d_ctr, b->d_ert_stk, b->ert_stk_frames, b->cu_count, b->stream);
+            launch_ert_locate(b->seed_ert->t, b->d_enc.p, b->d_cum.p, b->d_sorted.p, b->n_smem, b->d_sa_cnt.p, b->last_seed_opt.max_occ,
+                              b->d_ctr.p, b->d_ert_stk.p, b->ert_stk_frames, b->cu_count, b->stream);
             if (int rrc = ert_redo_ensure(b, b->n_smem)) return rrc;
-            launch_ert_gather(b->seed_ert->t, b->d_sorted, b->n_smem, b->d_sa_off, b->d_sa_coord, b->max_sa,
-                              b->last_seed_opt.max_occ, b->d_ctr, b->d_ert_stk, b->ert_stk_frames, b->d_ert_redo, b->max_sa,
+            launch_ert_gather(b->seed_ert->t, b->d_sorted.p, b->n_smem, b->d_sa_off.p, b->d_sa_coord.p, b->max_sa,
+                              b->last_seed_opt.max_occ, b->d_ctr.p, b->d_ert_stk.p, b->ert_stk_frames, b->d_ert_redo.p, b->max_sa,
                               b->cu_count, b->stream);
-            launch_ert_clear(b->d_sorted, b->n_smem, b->stream);
+            launch_ert_clear(b->d_sorted.p, b->n_smem, b->stream);
         } else
-        launch_sa_lookup(b->idx->fmi, b->d_sorted, b->n_smem, b->d_sa_off, b->d_sa_coord, b->max_sa, b->last_seed_opt.max_occ,
-                         b->d_ctr, b->cu_count, b->stream);
+        launch_sa_lookup(b->idx->fmi, b->d_sorted.p, b->n_smem, b->d_sa_off.p, b->d_sa_coord.p, b->max_sa, b->last_seed_opt.max_occ,
+                         b->d_ctr.p, b->cu_count, b->stream);
         BWAMS_HIP(hipEventRecord(b->ev[5], b->stream));
-        BWAMS_HIP(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
+        BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
         BWAMS_HIP(hipStreamSynchronize(b->stream));
-        b->n_sa = (int64_t)b->h_ctr->n_sa_lookups;
+        b->n_sa = (int64_t)b->h_ctr.p->n_sa_lookups;
         if (n_sa) *n_sa = b->n_sa;
         if (b->n_sa > b->max_sa) {
             set_last_error("SA coordinate buffer overflow: need " + std::to_string(b->n_sa));
@@ -926,13 +847,13 @@ int bwams_seed_fetch(bwams_batch_t *b, bwams_smem_t *smem_out, int64_t smem_cap,
         return BWAMS_ERR_CAPACITY;
     }
     if (smem_out && ns)
-        BWAMS_HIP(hipMemcpyAsync(smem_out, b->d_sorted, (size_t)ns * sizeof(bwams_smem_t), hipMemcpyDeviceToHost,
+        BWAMS_HIP(hipMemcpyAsync(smem_out, b->d_sorted.p, (size_t)ns * sizeof(bwams_smem_t), hipMemcpyDeviceToHost,
                                  b->stream));
     if (sa_coord && sa_off && b->with_sa) {
         if (ns) {
-            BWAMS_HIP(hipMemcpyAsync(sa_off, b->d_sa_off, (size_t)(ns + 1) * 8, hipMemcpyDeviceToHost, b->stream));
+            BWAMS_HIP(hipMemcpyAsync(sa_off, b->d_sa_off.p, (size_t)(ns + 1) * 8, hipMemcpyDeviceToHost, b->stream));
             if (na)
-                BWAMS_HIP(hipMemcpyAsync(sa_coord, b->d_sa_coord, (size_t)na * 8, hipMemcpyDeviceToHost, b->stream));
+                BWAMS_HIP(hipMemcpyAsync(sa_coord, b->d_sa_coord.p, (size_t)na * 8, hipMemcpyDeviceToHost, b->stream));
         } else {
             sa_off[0] = 0;
         }
@@ -965,20 +886,20 @@ int bwams_seed_fmi(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, con
 static int ert_fat_table(bwams_ert *e) {
     if (!knobs().ert_fat) return BWAMS_OK;
     const size_t bytes = (size_t)64 << (2 * e->t.K);
-    BWAMS_HIP(dev_malloc(&e->d_fat, bytes));
-    launch_ert_fat(e->t, e->mlt_bytes, (uint8_t *)e->d_fat, 0);
+    BWAMS_HIP(e->d_fat.alloc(bytes));
+    launch_ert_fat(e->t, e->mlt_bytes, e->d_fat.as<uint8_t>(), 0);
     BWAMS_HIP(hipDeviceSynchronize());
     BWAMS_HIP(hipGetLastError());
-    e->t.fat = (const uint8_t *)e->d_fat;
+    e->t.fat = e->d_fat.as<const uint8_t>();
     e->bytes += (int64_t)bytes;
     return BWAMS_OK;
 }
 static int ert_count_table(bwams_ert *e) {
     int bits = 16;
     while (bits < 26 && ((int64_t)1 << bits) < e->mlt_bytes / 256) bits++;
-    BWAMS_HIP(dev_malloc(&e->d_cnt, (size_t)16 << bits));
-    BWAMS_HIP(hipMemset(e->d_cnt, 0, (size_t)16 << bits));
-    e->t.cnt_tab = (uint64_t *)e->d_cnt;
+    BWAMS_HIP(e->d_cnt.alloc((size_t)16 << bits));
+    BWAMS_HIP(hipMemset(e->d_cnt.p, 0, (size_t)16 << bits));
+    e->t.cnt_tab = e->d_cnt.as<uint64_t>();
     e->t.cnt_bits = bits;
     e->bytes += (int64_t)16 << bits;
     return BWAMS_OK;
@@ -991,7 +912,7 @@ int bwams_ert_from_host(bwams_index_t *ix, const uint64_t *kmer_table, int32_t k
         set_last_error("bwams_ert_from_host: k-mer size must be in [2, 15], x-mer size in [1, 8]");
         return BWAMS_ERR_ARG;
     }
-    if (!ix->d_ref) {
+    if (!ix->fmi.ref) {
         set_last_error("bwams_ert_from_host: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -999,18 +920,18 @@ int bwams_ert_from_host(bwams_index_t *ix, const uint64_t *kmer_table, int32_t k
     bwams_ert *e = new bwams_ert();
     e->idx = ix;
     const size_t nk = (size_t)1 << (2 * kmer_size);
-    hipError_t he = dev_malloc(&e->d_kmer, nk * 8);
-    if (he == hipSuccess) he = dev_malloc(&e->d_mlt, (size_t)mlt_bytes + 16);
-    if (he == hipSuccess) he = hipMemcpy(e->d_kmer, kmer_table, nk * 8, hipMemcpyHostToDevice);
-    if (he == hipSuccess && mlt_bytes) he = hipMemcpy(e->d_mlt, mlt_table, (size_t)mlt_bytes, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemset((uint8_t *)e->d_mlt + mlt_bytes, 0, 16);
+    hipError_t he = e->d_kmer.alloc(nk * 8);
+    if (he == hipSuccess) he = e->d_mlt.alloc((size_t)mlt_bytes + 16);
+    if (he == hipSuccess) he = hipMemcpy(e->d_kmer.p, kmer_table, nk * 8, hipMemcpyHostToDevice);
+    if (he == hipSuccess && mlt_bytes) he = hipMemcpy(e->d_mlt.p, mlt_table, (size_t)mlt_bytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemset(e->d_mlt.as<uint8_t>() + mlt_bytes, 0, 16);
     if (he != hipSuccess) {
         set_last_error(std::string("bwams_ert_from_host: ") + hipGetErrorString(he));
         bwams_ert_close(e);
         return he == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
     }
-    e->t.kmer = (const uint64_t *)e->d_kmer;
-    e->t.mlt = (const uint8_t *)e->d_mlt;
+    e->t.kmer = e->d_kmer.as<const uint64_t>();
+    e->t.mlt = e->d_mlt.as<const uint8_t>();
     e->t.ref = ix->fmi.ref;
     e->t.ref_len = ix->fmi.ref_seq_len - 1;
     e->t.K = kmer_size; e->t.X = xmer_size; e->t.read_len = read_len;
@@ -1024,7 +945,7 @@ int bwams_ert_from_host(bwams_index_t *ix, const uint64_t *kmer_table, int32_t k
 
 int bwams_ert_open(bwams_index_t *ix, const char *prefix, int32_t read_len, bwams_ert_t **out) {
     if (!ix || !prefix || !out) return BWAMS_ERR_ARG;
-    if (!ix->d_ref) {
+    if (!ix->fmi.ref) {
         set_last_error("bwams_ert_open: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -1046,32 +967,32 @@ int bwams_ert_open(bwams_index_t *ix, const char *prefix, int32_t read_len, bwam
     const size_t nk = (size_t)1 << (2 * K);
     int rc = BWAMS_OK;
     const size_t chunk = (size_t)256 << 20;          // streamed through one pinned staging buffer
-    void *stage = nullptr;
-    hipError_t he = dev_malloc(&e->d_kmer, nk * 8);
-    if (he == hipSuccess) he = dev_malloc(&e->d_mlt, (size_t)mlt_bytes + 16);
-    if (he == hipSuccess) he = hipHostMalloc(&stage, chunk);
+    HostBuf<uint8_t> stage;
+    hipError_t he = e->d_kmer.alloc(nk * 8);
+    if (he == hipSuccess) he = e->d_mlt.alloc((size_t)mlt_bytes + 16);
+    if (he == hipSuccess) he = stage.alloc(chunk);
     if (he != hipSuccess) rc = he == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
     auto stream_in = [&](FILE *f, void *dst, size_t total) {
         size_t done = 0;
         while (rc == BWAMS_OK && done < total) {
             const size_t n = total - done < chunk ? total - done : chunk;
-            if (fread(stage, 1, n, f) != n) { rc = BWAMS_ERR_IO; break; }
-            if (hipMemcpy((uint8_t *)dst + done, stage, n, hipMemcpyHostToDevice) != hipSuccess) { rc = BWAMS_ERR_DEVICE; break; }
+            if (fread(stage.p, 1, n, f) != n) { rc = BWAMS_ERR_IO; break; }
+            if (hipMemcpy((uint8_t *)dst + done, stage.p, n, hipMemcpyHostToDevice) != hipSuccess) { rc = BWAMS_ERR_DEVICE; break; }
             done += n;
         }
     };
-    if (rc == BWAMS_OK) stream_in(f1, e->d_kmer, nk * 8);
-    if (rc == BWAMS_OK) stream_in(f2, e->d_mlt, (size_t)mlt_bytes);
-    if (rc == BWAMS_OK && hipMemset((uint8_t *)e->d_mlt + mlt_bytes, 0, 16) != hipSuccess) rc = BWAMS_ERR_DEVICE;
+    if (rc == BWAMS_OK) stream_in(f1, e->d_kmer.p, nk * 8);
+    if (rc == BWAMS_OK) stream_in(f2, e->d_mlt.p, (size_t)mlt_bytes);
+    if (rc == BWAMS_OK && hipMemset(e->d_mlt.as<uint8_t>() + mlt_bytes, 0, 16) != hipSuccess) rc = BWAMS_ERR_DEVICE;
     fclose(f1); fclose(f2);
-    if (stage) (void)hipHostFree(stage);
+    stage.release();
     if (rc != BWAMS_OK) {
         set_last_error("bwams_ert_open: reading " + fk + " / " + fm + " failed");
         bwams_ert_close(e);
         return rc;
     }
-    e->t.kmer = (const uint64_t *)e->d_kmer;
-    e->t.mlt = (const uint8_t *)e->d_mlt;
+    e->t.kmer = e->d_kmer.as<const uint64_t>();
+    e->t.mlt = e->d_mlt.as<const uint8_t>();
     e->t.ref = ix->fmi.ref;
     e->t.ref_len = ix->fmi.ref_seq_len - 1;
     e->t.K = K; e->t.X = X; e->t.read_len = read_len;
@@ -1091,7 +1012,7 @@ int bwams_ert_build(bwams_index_t *ix, int32_t kmer_size, int32_t xmer_size, int
         set_last_error("bwams_ert_build: k-mer size must be in [2, 15], x-mer size in [1, 8], read length in [k + x, 255]");
         return BWAMS_ERR_ARG;
     }
-    if (!ix->d_ref) {
+    if (!ix->fmi.ref) {
         set_last_error("bwams_ert_build: the index holds no .0123 reference (leaf expansion reads it)");
         return BWAMS_ERR_ARG;
     }
@@ -1122,8 +1043,8 @@ int bwams_ert_info(const bwams_ert_t *e, int32_t *kmer_size, int32_t *xmer_size,
 int bwams_ert_fetch(bwams_ert_t *e, uint64_t *kmer_table, uint8_t *mlt_table) {
     if (!e) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(e->idx->device));
-    if (kmer_table) BWAMS_HIP(hipMemcpy(kmer_table, e->d_kmer, ((size_t)1 << (2 * e->t.K)) * 8, hipMemcpyDeviceToHost));
-    if (mlt_table && e->mlt_bytes) BWAMS_HIP(hipMemcpy(mlt_table, e->d_mlt, (size_t)e->mlt_bytes, hipMemcpyDeviceToHost));
+    if (kmer_table) BWAMS_HIP(hipMemcpy(kmer_table, e->d_kmer.p, ((size_t)1 << (2 * e->t.K)) * 8, hipMemcpyDeviceToHost));
+    if (mlt_table && e->mlt_bytes) BWAMS_HIP(hipMemcpy(mlt_table, e->d_mlt.p, (size_t)e->mlt_bytes, hipMemcpyDeviceToHost));
     return BWAMS_OK;
 }
 
@@ -1131,8 +1052,8 @@ int bwams_ert_save(bwams_ert_t *e, const char *prefix) {
     if (!e || !prefix) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(e->idx->device));
     const size_t chunk = (size_t)256 << 20;
-    void *stage = nullptr;
-    BWAMS_HIP(hipHostMalloc(&stage, chunk));
+    HostBuf<uint8_t> stage;
+    BWAMS_HIP(stage.alloc(chunk));
     int rc = BWAMS_OK;
     auto stream_out = [&](const std::string &path, const void *src, size_t total) {
         FILE *f = fopen(path.c_str(), "wb");
@@ -1140,25 +1061,20 @@ int bwams_ert_save(bwams_ert_t *e, const char *prefix) {
         size_t done = 0;
         while (rc == BWAMS_OK && done < total) {
             const size_t n = total - done < chunk ? total - done : chunk;
-            if (hipMemcpy(stage, (const uint8_t *)src + done, n, hipMemcpyDeviceToHost) != hipSuccess) { rc = BWAMS_ERR_DEVICE; break; }
-            if (fwrite(stage, 1, n, f) != n) { rc = BWAMS_ERR_IO; set_last_error("bwams_ert_save: short write to " + path); break; }
+            if (hipMemcpy(stage.p, (const uint8_t *)src + done, n, hipMemcpyDeviceToHost) != hipSuccess) { rc = BWAMS_ERR_DEVICE; break; }
+            if (fwrite(stage.p, 1, n, f) != n) { rc = BWAMS_ERR_IO; set_last_error("bwams_ert_save: short write to " + path); break; }
             done += n;
         }
         fclose(f);
     };
-    stream_out(std::string(prefix) + ".kmer_table", e->d_kmer, ((size_t)1 << (2 * e->t.K)) * 8);
-    if (rc == BWAMS_OK) stream_out(std::string(prefix) + ".mlt_table", e->d_mlt, (size_t)e->mlt_bytes);
-    (void)hipHostFree(stage);
+    stream_out(std::string(prefix) + ".kmer_table", e->d_kmer.p, ((size_t)1 << (2 * e->t.K)) * 8);
+    if (rc == BWAMS_OK) stream_out(std::string(prefix) + ".mlt_table", e->d_mlt.p, (size_t)e->mlt_bytes);
     return rc;
 }
 
 int bwams_ert_close(bwams_ert_t *e) {
     if (!e) return BWAMS_OK;
     (void)hipSetDevice(e->idx->device);
-    if (e->d_kmer) (void)hipFree(e->d_kmer);
-    if (e->d_mlt) (void)hipFree(e->d_mlt);
-    if (e->d_cnt) (void)hipFree(e->d_cnt);
-    if (e->d_fat) (void)hipFree(e->d_fat);
     delete e;
     return BWAMS_OK;
 }
@@ -1170,18 +1086,17 @@ int bwams_ert_set_fat(bwams_ert_t *e, int32_t on) {
     BWAMS_HIP(hipSetDevice(e->idx->device));
     BWAMS_HIP(hipDeviceSynchronize());                   // no walk is reading it
     if (on) {
-        if (e->d_fat) return BWAMS_OK;
+        if (e->d_fat.p) return BWAMS_OK;
         const size_t bytes = (size_t)64 << (2 * e->t.K);
-        BWAMS_HIP(dev_malloc(&e->d_fat, bytes));
-        launch_ert_fat(e->t, e->mlt_bytes, (uint8_t *)e->d_fat, 0);
+        BWAMS_HIP(e->d_fat.alloc(bytes));
+        launch_ert_fat(e->t, e->mlt_bytes, e->d_fat.as<uint8_t>(), 0);
         BWAMS_HIP(hipDeviceSynchronize());
-        e->t.fat = (const uint8_t *)e->d_fat;
+        e->t.fat = e->d_fat.as<const uint8_t>();
         e->bytes += (int64_t)bytes;
         return BWAMS_OK;
     }
-    if (e->d_fat) {
-        (void)hipFree(e->d_fat);
-        e->d_fat = nullptr;
+    if (e->d_fat.p) {
+        e->d_fat.release();
         e->t.fat = nullptr;
         e->bytes -= (int64_t)64 << (2 * e->t.K);
     }
@@ -1193,41 +1108,34 @@ static int ert_run_once(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t
     hipStream_t st = b->stream;
     b->with_sa = with_sa != 0;
     b->n_smem = b->n_sa = 0;
-    const int64_t need = (int64_t)ert_prof_bytes(b->nbases);
-    if (need > b->cap_ert_prof) {
-        if (b->d_ert_prof) (void)hipFree(b->d_ert_prof);
-        b->d_ert_prof = nullptr;
-        b->cap_ert_prof = need + need / 8;
-        BWAMS_HIP(dev_malloc(&b->d_ert_prof, (size_t)b->cap_ert_prof));
-    }
+    const size_t need = ert_prof_bytes(b->nbases);
+    BWAMS_HIP(b->d_ert_prof.ensure(need, need + need / 8));
     const int frames = 2 * (e->t.read_len + 2);      // the counting walk keeps two words per level
     const size_t part_bytes = ert_count_bytes();      // partial counters sit behind the stacks
     if (frames > b->ert_stk_frames) {
-        if (b->d_ert_stk) (void)hipFree(b->d_ert_stk);
-        b->d_ert_stk = nullptr;
-        BWAMS_HIP(dev_malloc(&b->d_ert_stk, (size_t)ert_walk_threads(b->cu_count) * (size_t)frames * 8 + part_bytes));
+        BWAMS_HIP(b->d_ert_stk.alloc((size_t)ert_walk_threads(b->cu_count) * (size_t)frames * 8 + part_bytes));
         b->ert_stk_frames = frames;
-        BWAMS_HIP(hipMemsetAsync(b->d_ert_stk + (size_t)ert_walk_threads(b->cu_count) * (size_t)frames, 0, part_bytes, b->stream));
+        BWAMS_HIP(hipMemsetAsync(b->d_ert_stk.p + (size_t)ert_walk_threads(b->cu_count) * (size_t)frames, 0, part_bytes, b->stream));
     }
-    const uint8_t *skip = b->has_skip ? b->d_skip : nullptr;
+    const uint8_t *skip = b->has_skip ? b->d_skip.p : nullptr;
     // events: 0 start | 8,9 match profiles | 10,11 the three rounds | 3,4 sort | 12,13 locate | 4,5 locate + hits
-    BWAMS_HIP(hipMemsetAsync(b->d_ctr, 0, sizeof(DevCounters), st));
+    BWAMS_HIP(hipMemsetAsync(b->d_ctr.p, 0, sizeof(DevCounters), st));
     BWAMS_HIP(hipEventRecord(b->ev[0], st));
     BWAMS_HIP(hipEventRecord(b->ev[8], st));
-    launch_ert_profile(e->t, b->d_enc, b->d_cum, skip, b->nseq, b->nbases, M, b->d_ert_prof, b->d_ctr,
-                       (unsigned long long *)(b->d_ert_stk + (size_t)ert_walk_threads(b->cu_count) * (size_t)b->ert_stk_frames), b->cu_count, st);
+    launch_ert_profile(e->t, b->d_enc.p, b->d_cum.p, skip, b->nseq, b->nbases, M, b->d_ert_prof.p, b->d_ctr.p,
+                       (unsigned long long *)(b->d_ert_stk.p + (size_t)ert_walk_threads(b->cu_count) * (size_t)b->ert_stk_frames), b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[9], st));
     BWAMS_HIP(hipEventRecord(b->ev[10], st));
-    launch_ert_select(b->d_ert_prof, b->d_cum, skip, b->nseq, b->nbases, M, *opt, b->d_pool, b->pool_cap, b->d_ctr, b->cu_count, st);
+    launch_ert_select(b->d_ert_prof.p, b->d_cum.p, skip, b->nseq, b->nbases, M, *opt, b->d_pool.p, b->pool_cap, b->d_ctr.p, b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[11], st));
     BWAMS_HIP(hipEventRecord(b->ev[3], st));
     BWAMS_HIP(hipGetLastError());
-    BWAMS_HIP(hipMemcpyAsync(&b->d_ctr->n_smem_valid, &b->d_ctr->n_smem_total, 8, hipMemcpyDeviceToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(&b->d_ctr.p->n_smem_valid, &b->d_ctr.p->n_smem_total, 8, hipMemcpyDeviceToDevice, st));
     for (int k = 0; k < 3; ++k)      // the rounds are not separate launches here: all seeds are reported under round 1
-        BWAMS_HIP(hipMemcpyAsync(&b->d_ctr->valid_after[k], &b->d_ctr->n_smem_total, 8, hipMemcpyDeviceToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(&b->d_ctr.p->valid_after[k], &b->d_ctr.p->n_smem_total, 8, hipMemcpyDeviceToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    const int64_t n = (int64_t)b->h_ctr->n_smem_total;
+    const int64_t n = (int64_t)b->h_ctr.p->n_smem_total;
     b->n_smem = n;
     if (n > b->max_smem || n > b->pool_cap) {
         set_last_error("SMEM pool overflow: need " + std::to_string(n) + " slots");
@@ -1235,49 +1143,35 @@ static int ert_run_once(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t
         return BWAMS_ERR_CAPACITY;
     }
     if (n > 0) {
-        launch_make_keys(b->d_pool, n, b->d_keys, b->d_vals, (uint32_t)b->nseq, st);
+        launch_make_keys(b->d_pool.p, n, b->d_keys.p, b->d_vals.p, (uint32_t)b->nseq, st);
         int rid_bits = 1;
         while (((int64_t)1 << rid_bits) <= b->nseq) rid_bits++;
         size_t tb = 0;
-        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, b->d_keys, b->d_keys2, b->d_vals, b->d_vals2, (size_t)n, 0,
+        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p, (size_t)n, 0,
                                             32 + rid_bits, st));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(st));
-            (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp, tb, b->d_keys, b->d_keys2, b->d_vals, b->d_vals2, (size_t)n, 0,
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp.p, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p, (size_t)n, 0,
                                             32 + rid_bits, st));
-        launch_gather_sorted(b->d_pool, b->d_vals2, n, b->d_sorted, nullptr, opt->max_occ, st);
+        launch_gather_sorted(b->d_pool.p, b->d_vals2.p, n, b->d_sorted.p, nullptr, opt->max_occ, st);
     }
     BWAMS_HIP(hipEventRecord(b->ev[4], st));
     BWAMS_HIP(hipEventRecord(b->ev[12], st));
-    launch_ert_locate(e->t, b->d_enc, b->d_cum, b->d_sorted, n, with_sa ? b->d_sa_cnt : nullptr, opt->max_occ, b->d_ctr, b->d_ert_stk,
+    launch_ert_locate(e->t, b->d_enc.p, b->d_cum.p, b->d_sorted.p, n, with_sa ? b->d_sa_cnt.p : nullptr, opt->max_occ, b->d_ctr.p, b->d_ert_stk.p,
                       b->ert_stk_frames, b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[13], st));
     if (with_sa && n > 0) {
         size_t tb = 0;
-        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, b->d_sa_cnt, b->d_sa_off, (int64_t)0, (size_t)n + 1,
+        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
                                           rocprim::plus<int64_t>(), st));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(st));
-            (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(hipMemsetAsync(b->d_sa_cnt + n, 0, 8, st));
-        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp, tb, b->d_sa_cnt, b->d_sa_off, (int64_t)0, (size_t)n + 1,
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(hipMemsetAsync(b->d_sa_cnt.p + n, 0, 8, st));
+        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp.p, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
                                           rocprim::plus<int64_t>(), st));
         if (int rrc = ert_redo_ensure(b, n)) return rrc;
-        launch_ert_gather(e->t, b->d_sorted, n, b->d_sa_off, b->d_sa_coord, b->max_sa, opt->max_occ, b->d_ctr, b->d_ert_stk,
-                          b->ert_stk_frames, b->d_ert_redo, b->max_sa, b->cu_count, st);
+        launch_ert_gather(e->t, b->d_sorted.p, n, b->d_sa_off.p, b->d_sa_coord.p, b->max_sa, opt->max_occ, b->d_ctr.p, b->d_ert_stk.p,
+                          b->ert_stk_frames, b->d_ert_redo.p, b->max_sa, b->cu_count, st);
     }
-    launch_ert_clear(b->d_sorted, n, st);
+    launch_ert_clear(b->d_sorted.p, n, st);
     BWAMS_HIP(hipEventRecord(b->ev[5], st));
     BWAMS_HIP(hipGetLastError());
     b->seed_done = true;
@@ -1309,8 +1203,7 @@ int bwams_seed_run_ert(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t 
         const int64_t seen = std::max(b->n_smem, b->n_pool_slots - seed_pool_slack(b->cu_count));
         const int64_t need = std::max(seen, b->max_smem) + seen / 4 + 1024;
         if ((rc = alloc_smem_buffers(b, need))) return rc;
-        b->tmp_bytes = 0;
-        if (b->d_tmp) { (void)hipFree(b->d_tmp); b->d_tmp = nullptr; }
+        b->d_tmp.release();
         rc = ert_run_once(b, e, opt, with_sa, M);
     }
     return rc;
@@ -1337,20 +1230,14 @@ int bwams_bsw_upload(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n, 
         set_last_error("bwams_bsw_upload: query of " + std::to_string(qmax) + " bases, longer than the LDS-resident kernel supports (18196)");
         return BWAMS_ERR_UNSUPPORTED;
     }
-    auto grow = [](void **p, int64_t *cap, int64_t need, size_t elem) -> hipError_t {
-        if (need <= *cap) return hipSuccess;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        *cap = need + need / 4 + 1024;
-        return dev_malloc(p, (size_t)*cap * elem);
-    };
-    BWAMS_HIP(grow((void **)&b->d_pairs, &b->cap_pairs, n, sizeof(bwams_seqpair_t)));
-    BWAMS_HIP(grow((void **)&b->d_ref, &b->cap_ref, ref_bytes + 64, 1));
-    BWAMS_HIP(grow((void **)&b->d_qer, &b->cap_qer, qer_bytes + 64, 1));
+    auto grow = [](auto &buf, int64_t need, size_t elem) { return buf.ensure((size_t)need * elem, (size_t)(need + need / 4 + 1024) * elem); };
+    BWAMS_HIP(grow(b->d_pairs, n, sizeof(bwams_seqpair_t)));
+    BWAMS_HIP(grow(b->d_ref, ref_bytes + 64, 1));
+    BWAMS_HIP(grow(b->d_qer, qer_bytes + 64, 1));
     if (n) {
-        BWAMS_HIP(hipMemcpyAsync(b->d_pairs, pairs, (size_t)n * sizeof(bwams_seqpair_t), hipMemcpyHostToDevice, b->stream));
-        BWAMS_HIP(hipMemcpyAsync(b->d_ref, ref, (size_t)ref_bytes, hipMemcpyHostToDevice, b->stream));
-        BWAMS_HIP(hipMemcpyAsync(b->d_qer, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, b->stream));
+        BWAMS_HIP(hipMemcpyAsync(b->d_pairs.p, pairs, (size_t)n * sizeof(bwams_seqpair_t), hipMemcpyHostToDevice, b->stream));
+        BWAMS_HIP(hipMemcpyAsync(b->d_ref.p, ref, (size_t)ref_bytes, hipMemcpyHostToDevice, b->stream));
+        BWAMS_HIP(hipMemcpyAsync(b->d_qer.p, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, b->stream));
         BWAMS_HIP(hipStreamSynchronize(b->stream));
     }
     b->n_pairs = n;
@@ -1375,10 +1262,12 @@ int bwams_bsw_run(bwams_batch_t *b, int32_t w, const bwams_sw_opt_t *o) {
         mx = mx > o->mat[i] ? mx : o->mat[i];
     }
     prm.max_sc = mx;
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->bsw_cells, 0, sizeof(unsigned long long), b->stream));
-    if (int lrc = bsw_list_ensure(b, b->n_pairs)) return lrc;
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->bsw_cells, 0, sizeof(unsigned long long), b->stream));
+    const size_t list_bytes = b->n_pairs > 0 ? bsw_list_bytes(b->n_pairs) : 0;
+    if (list_bytes > b->d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(b->stream));     // the last launch may still read the lists
+    BWAMS_HIP(b->d_bsw_list.ensure(list_bytes, bsw_list_bytes(b->n_pairs + b->n_pairs / 4 + 1024)));
     BWAMS_HIP(hipEventRecord(b->ev[6], b->stream));
-    if (launch_bsw(b->d_pairs, b->n_pairs, b->d_ref, b->d_qer, w, prm, b->max_qlen, b->d_ctr, b->cu_count, b->stream, b->d_bsw_list)) {
+    if (launch_bsw(b->d_pairs.p, b->n_pairs, b->d_ref.p, b->d_qer.p, w, prm, b->max_qlen, b->d_ctr.p, b->cu_count, b->stream, b->d_bsw_list.p)) {
         set_last_error("bwams_bsw_run: a query longer than ~18000 bases does not fit the LDS kernel");
         return BWAMS_ERR_UNSUPPORTED;
     }
@@ -1390,7 +1279,7 @@ int bwams_bsw_run(bwams_batch_t *b, int32_t w, const bwams_sw_opt_t *o) {
 int bwams_bsw_fetch(bwams_batch_t *b, bwams_seqpair_t *pairs, int64_t n) {
     if (!b || n != b->n_pairs) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    if (n) BWAMS_HIP(hipMemcpyAsync(pairs, b->d_pairs, (size_t)n * sizeof(bwams_seqpair_t), hipMemcpyDeviceToHost, b->stream));
+    if (n) BWAMS_HIP(hipMemcpyAsync(pairs, b->d_pairs.p, (size_t)n * sizeof(bwams_seqpair_t), hipMemcpyDeviceToHost, b->stream));
     BWAMS_HIP(hipStreamSynchronize(b->stream));
     return BWAMS_OK;
 }
@@ -1410,7 +1299,7 @@ int bwams_emf_from_host(bwams_index_t *ix, int32_t seed_len, uint32_t seq_len, c
                         uint32_t num_loc_entry, const bwams_seed_entry_t *seed_table, uint32_t num_seed_entry,
                         bwams_emf_t **out) {
     if (!ix || !out || !seed_table || !num_seed_entry || seed_len <= 0 || (num_loc_entry && !loc_table)) return BWAMS_ERR_ARG;
-    if (!ix->d_ref) {
+    if (!ix->fmi.ref) {
         set_last_error("bwams_emf_from_host: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -1418,17 +1307,17 @@ int bwams_emf_from_host(bwams_index_t *ix, int32_t seed_len, uint32_t seq_len, c
     bwams_emf *e = new bwams_emf();
     e->idx = ix;
     const size_t bs = (size_t)num_seed_entry * 16, bl = (size_t)(num_loc_entry ? num_loc_entry : 1) * 4;
-    hipError_t he = dev_malloc(&e->d_seeds, bs);
-    if (he == hipSuccess) he = dev_malloc(&e->d_loc, bl);
-    if (he == hipSuccess) he = hipMemcpy(e->d_seeds, seed_table, bs, hipMemcpyHostToDevice);
-    if (he == hipSuccess && num_loc_entry) he = hipMemcpy(e->d_loc, loc_table, (size_t)num_loc_entry * 4, hipMemcpyHostToDevice);
+    hipError_t he = e->d_seeds.alloc(bs);
+    if (he == hipSuccess) he = e->d_loc.alloc(bl);
+    if (he == hipSuccess) he = hipMemcpy(e->d_seeds.p, seed_table, bs, hipMemcpyHostToDevice);
+    if (he == hipSuccess && num_loc_entry) he = hipMemcpy(e->d_loc.p, loc_table, (size_t)num_loc_entry * 4, hipMemcpyHostToDevice);
     if (he != hipSuccess) {                     // a table is tens of GiB: do not strand the half that was made
         set_last_error(std::string("bwams_emf_from_host: ") + hipGetErrorString(he));
         bwams_emf_close(e);
         return he == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
     }
-    e->t.seed_table = reinterpret_cast<const uint4 *>(e->d_seeds);
-    e->t.loc_table = reinterpret_cast<const uint32_t *>(e->d_loc);
+    e->t.seed_table = e->d_seeds.as<const uint4>();
+    e->t.loc_table = e->d_loc.as<const uint32_t>();
     e->t.ref = ix->fmi.ref;
     e->t.num_seed_entry = num_seed_entry;
     e->t.num_loc_entry = num_loc_entry;
@@ -1473,10 +1362,9 @@ int bwams_emf_open(bwams_index_t *ix, const char *path, bwams_emf_t **out) {
 int bwams_emf_from_device(bwams_index_t *ix, int32_t seed_len, uint32_t seq_len, const uint32_t *loc_table_dev,
                           uint32_t num_loc_entry, const bwams_seed_entry_t *seed_table_dev, uint32_t num_seed_entry,
                           bwams_emf_t **out) {
-    if (!ix || !out || !seed_table_dev || !num_seed_entry || seed_len <= 0 || !ix->d_ref) return BWAMS_ERR_ARG;
+    if (!ix || !out || !seed_table_dev || !num_seed_entry || seed_len <= 0 || !ix->fmi.ref) return BWAMS_ERR_ARG;
     bwams_emf *e = new bwams_emf();
     e->idx = ix;
-    e->owns = false;
     e->t.seed_table = reinterpret_cast<const uint4 *>(seed_table_dev);
     e->t.loc_table = loc_table_dev;
     e->t.ref = ix->fmi.ref;
@@ -1489,41 +1377,45 @@ int bwams_emf_from_device(bwams_index_t *ix, int32_t seed_len, uint32_t seq_len,
     return BWAMS_OK;
 }
 
+// the probe's per-read results: a word pair and a code byte per read
+static int emf_out_ensure(bwams_batch_t *b, int64_t nseq) {
+    if ((size_t)nseq <= b->d_emf_code.cap) return BWAMS_OK;
+    b->d_emf_out.release();
+    b->d_emf_code.release();
+    const size_t cap = (size_t)(nseq + nseq / 8 + 256);
+    BWAMS_HIP(b->d_emf_out.alloc(cap * 8));
+    BWAMS_HIP(b->d_emf_code.alloc(cap));
+    return BWAMS_OK;
+}
+
 /* Resident form: probe the reads uploaded by bwams_seed_upload and set the batch's skip flags on the
  * device, so that the following bwams_seed_run leaves the matched reads out. */
 int bwams_emf_run(bwams_batch_t *b, bwams_emf_t *e) {
     if (!b || !e || e->idx != b->idx) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     const int64_t nseq = b->nseq;
-    if (nseq > b->cap_emf) {
-        if (b->d_emf_out) (void)hipFree(b->d_emf_out);
-        if (b->d_emf_code) (void)hipFree(b->d_emf_code);
-        b->d_emf_out = nullptr; b->d_emf_code = nullptr;
-        b->cap_emf = nseq + nseq / 8 + 256;
-        BWAMS_HIP(dev_malloc(&b->d_emf_out, (size_t)b->cap_emf * 8));
-        BWAMS_HIP(dev_malloc(&b->d_emf_code, (size_t)b->cap_emf));
-    }
+    if (int rc = emf_out_ensure(b, nseq)) return rc;
     hipStream_t st = b->stream;
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->emf_nodes, 0, 16, st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->emf_nodes, 0, 16, st));
     BWAMS_HIP(hipEventRecord(b->ev_emf[0], st));
-    launch_emf_probe(e->t, b->d_enc, b->d_cum, nseq, b->d_emf_out, b->d_emf_code, b->d_skip, b->d_ctr, st);
+    launch_emf_probe(e->t, b->d_enc.p, b->d_cum.p, nseq, b->d_emf_out.p, b->d_emf_code.p, b->d_skip.p, b->d_ctr.p, st);
     BWAMS_HIP(hipEventRecord(b->ev_emf[1], st));
     // seed_run clears the counters: keep the probe's own
-    BWAMS_HIP(hipMemcpyAsync(&b->h_ctr->emf_nodes, &b->d_ctr->emf_nodes, 16, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(&b->h_ctr.p->emf_nodes, &b->d_ctr.p->emf_nodes, 16, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    b->emf_nodes = b->h_ctr->emf_nodes;
-    b->emf_cmp_bytes = b->h_ctr->emf_cmp_bytes;
+    b->emf_nodes = b->h_ctr.p->emf_nodes;
+    b->emf_cmp_bytes = b->h_ctr.p->emf_cmp_bytes;
     BWAMS_HIP(hipGetLastError());
     b->has_skip = true;
     return BWAMS_OK;
 }
 
 int bwams_emf_fetch(bwams_batch_t *b, bwams_perfect_t *out, uint8_t *code) {
-    if (!b || !b->d_emf_out) return BWAMS_ERR_ARG;
+    if (!b || !b->d_emf_out.p) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     if (b->nseq) {
-        if (out) BWAMS_HIP(hipMemcpyAsync(out, b->d_emf_out, (size_t)b->nseq * 8, hipMemcpyDeviceToHost, b->stream));
-        if (code) BWAMS_HIP(hipMemcpyAsync(code, b->d_emf_code, (size_t)b->nseq, hipMemcpyDeviceToHost, b->stream));
+        if (out) BWAMS_HIP(hipMemcpyAsync(out, b->d_emf_out.p, (size_t)b->nseq * 8, hipMemcpyDeviceToHost, b->stream));
+        if (code) BWAMS_HIP(hipMemcpyAsync(code, b->d_emf_code.p, (size_t)b->nseq, hipMemcpyDeviceToHost, b->stream));
     }
     BWAMS_HIP(hipStreamSynchronize(b->stream));
     return BWAMS_OK;
@@ -1534,7 +1426,7 @@ int bwams_emf_build(bwams_index_t *ix, int32_t seed_len, double slack, bwams_emf
         set_last_error("bwams_emf_build: seed length must be in [16, 255], slack in [1, 4]");
         return BWAMS_ERR_ARG;
     }
-    if (!ix->d_ref) {
+    if (!ix->fmi.ref) {
         set_last_error("bwams_emf_build: the index holds no .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -1549,7 +1441,7 @@ int bwams_emf_build(bwams_index_t *ix, int32_t seed_len, double slack, bwams_emf
     bwams_emf *e = new bwams_emf();
     e->idx = ix;
     int64_t st[4] = {0, 0, 0, 0};
-    const int rc = emf_build_device(e, (const uint8_t *)ix->d_ref, l_pac, seed_len, slack, prop.multiProcessorCount, knobs().verbose != 0, st);
+    const int rc = emf_build_device(e, ix->fmi.ref, l_pac, seed_len, slack, prop.multiProcessorCount, knobs().verbose != 0, st);
     if (rc) { bwams_emf_close(e); return rc; }
     e->n_used = st[0]; e->n_key = st[1]; e->n_other = st[2]; e->build_ms = st[3];
     *out = e;
@@ -1590,20 +1482,20 @@ int bwams_emf_save(bwams_emf_t *e, const char *path) {
     memcpy(hdr, &sl, 4); memcpy(hdr + 4, a, 12); memcpy(hdr + 40, b3, 12);
     int rc = fwrite(hdr, 1, 64, f) == 64 ? BWAMS_OK : BWAMS_ERR_IO;
     const size_t chunk = (size_t)256 << 20;
-    void *stage = nullptr;
-    if (rc == BWAMS_OK && hipHostMalloc(&stage, chunk) != hipSuccess) rc = BWAMS_ERR_NOMEM;
+    HostBuf<uint8_t> stage;
+    if (rc == BWAMS_OK && stage.alloc(chunk) != hipSuccess) rc = BWAMS_ERR_NOMEM;
     auto stream_out = [&](const void *src, size_t total) {
         size_t done = 0;
         while (rc == BWAMS_OK && done < total) {
             const size_t n = total - done < chunk ? total - done : chunk;
-            if (hipMemcpy(stage, (const uint8_t *)src + done, n, hipMemcpyDeviceToHost) != hipSuccess) { rc = BWAMS_ERR_DEVICE; break; }
-            if (fwrite(stage, 1, n, f) != n) { rc = BWAMS_ERR_IO; break; }
+            if (hipMemcpy(stage.p, (const uint8_t *)src + done, n, hipMemcpyDeviceToHost) != hipSuccess) { rc = BWAMS_ERR_DEVICE; break; }
+            if (fwrite(stage.p, 1, n, f) != n) { rc = BWAMS_ERR_IO; break; }
             done += n;
         }
     };
     if (rc == BWAMS_OK) stream_out(e->t.loc_table, (size_t)e->t.num_loc_entry * 4);
     if (rc == BWAMS_OK) stream_out(e->t.seed_table, (size_t)e->t.num_seed_entry * 16);
-    if (stage) (void)hipHostFree(stage);
+    stage.release();
     fclose(f);
     if (rc) set_last_error(std::string("bwams_emf_save: writing ") + path + " failed");
     return rc;
@@ -1611,10 +1503,7 @@ int bwams_emf_save(bwams_emf_t *e, const char *path) {
 
 int bwams_emf_close(bwams_emf_t *e) {
     if (!e) return BWAMS_OK;
-    if (!e->owns) { delete e; return BWAMS_OK; }
     (void)hipSetDevice(e->idx->device);
-    if (e->d_seeds) (void)hipFree(e->d_seeds);
-    if (e->d_loc) (void)hipFree(e->d_loc);
     delete e;
     return BWAMS_OK;
 }
@@ -1629,22 +1518,15 @@ int bwams_emf_probe(bwams_batch_t *b, bwams_emf_t *e, const uint8_t *enc, const 
     const int64_t nb = cum[nseq] - cum[0];
     if (cum[0] != 0 || nseq > b->max_reads || nb > b->max_bases) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    if (nseq > b->cap_emf) {
-        if (b->d_emf_out) (void)hipFree(b->d_emf_out);
-        if (b->d_emf_code) (void)hipFree(b->d_emf_code);
-        b->d_emf_out = nullptr; b->d_emf_code = nullptr;
-        b->cap_emf = nseq + nseq / 8 + 256;
-        BWAMS_HIP(dev_malloc(&b->d_emf_out, (size_t)b->cap_emf * 8));
-        BWAMS_HIP(dev_malloc(&b->d_emf_code, (size_t)b->cap_emf));
-    }
+    if (int rc = emf_out_ensure(b, nseq)) return rc;
     hipStream_t st = b->stream;
-    if (nb) BWAMS_HIP(hipMemcpyAsync(b->d_enc, enc, (size_t)nb, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(b->d_cum, cum, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, st));
-    launch_emf_probe(e->t, b->d_enc, b->d_cum, nseq, b->d_emf_out, b->d_emf_code, nullptr, nullptr, st);
+    if (nb) BWAMS_HIP(hipMemcpyAsync(b->d_enc.p, enc, (size_t)nb, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(b->d_cum.p, cum, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, st));
+    launch_emf_probe(e->t, b->d_enc.p, b->d_cum.p, nseq, b->d_emf_out.p, b->d_emf_code.p, nullptr, nullptr, st);
     BWAMS_HIP(hipGetLastError());
     if (nseq) {
-        BWAMS_HIP(hipMemcpyAsync(out, b->d_emf_out, (size_t)nseq * 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipMemcpyAsync(code, b->d_emf_code, (size_t)nseq, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(out, b->d_emf_out.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(code, b->d_emf_code.p, (size_t)nseq, hipMemcpyDeviceToHost, st));
     }
     BWAMS_HIP(hipStreamSynchronize(st));
     b->seed_done = false;            // the resident reads were replaced
@@ -1675,25 +1557,20 @@ int bwams_ksw_align(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n, c
         return BWAMS_ERR_UNSUPPORTED;
     }
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    if (n > b->cap_ksw) {
-        if (b->d_ksw_out) (void)hipFree(b->d_ksw_out);
-        b->d_ksw_out = nullptr;
-        b->cap_ksw = n + n / 4 + 256;
-        BWAMS_HIP(dev_malloc(&b->d_ksw_out, (size_t)b->cap_ksw * sizeof(bwams_kswr_t)));
-    }
+    BWAMS_HIP(b->d_ksw_out.ensure((size_t)n * sizeof(bwams_kswr_t), (size_t)(n + n / 4 + 256) * sizeof(bwams_kswr_t)));
     SwParams prm;
     prm.o_del = o->o_del; prm.e_del = o->e_del; prm.o_ins = o->o_ins; prm.e_ins = o->e_ins;
     prm.zdrop = o->zdrop; prm.end_bonus = o->end_bonus; prm.max_sc = mx;
     for (int i = 0; i < 25; ++i) prm.mat[i] = o->mat[i];
     BWAMS_HIP(hipEventRecord(b->ev[14], b->stream));
-    if (launch_ksw(b->d_pairs, n, b->d_ref, b->d_qer, prm, ((b->max_qlen + 15) / 16) * 16, b->max_tlen, b->d_ksw_out,
-                   b->d_ctr, b->cu_count, b->stream)) {
+    if (launch_ksw(b->d_pairs.p, n, b->d_ref.p, b->d_qer.p, prm, ((b->max_qlen + 15) / 16) * 16, b->max_tlen, b->d_ksw_out.p,
+                   b->d_ctr.p, b->cu_count, b->stream)) {
         set_last_error("bwams_ksw_align: target too long for the LDS of one block");
         return BWAMS_ERR_UNSUPPORTED;
     }
     BWAMS_HIP(hipEventRecord(b->ev[15], b->stream));
     BWAMS_HIP(hipGetLastError());
-    if (n) BWAMS_HIP(hipMemcpyAsync(out, b->d_ksw_out, (size_t)n * sizeof(bwams_kswr_t), hipMemcpyDeviceToHost, b->stream));
+    if (n) BWAMS_HIP(hipMemcpyAsync(out, b->d_ksw_out.p, (size_t)n * sizeof(bwams_kswr_t), hipMemcpyDeviceToHost, b->stream));
     BWAMS_HIP(hipStreamSynchronize(b->stream));
     return BWAMS_OK;
 }
@@ -1703,11 +1580,11 @@ int bwams_ksw_align(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n, c
 int bwams_batch_stats(bwams_batch_t *b, bwams_stats_t *out) {
     if (!b || !out) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    BWAMS_HIP(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
+    BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
     BWAMS_HIP(hipStreamSynchronize(b->stream));
     bwams_stats_t s;
     memset(&s, 0, sizeof s);
-    const DevCounters &c = *b->h_ctr;
+    const DevCounters &c = *b->h_ctr.p;
     s.n_ext = (int64_t)c.n_ext;
     s.n_ext_blocks = (int64_t)c.n_ext_blocks;
     s.n_sa_lookups = (int64_t)c.n_sa_lookups;

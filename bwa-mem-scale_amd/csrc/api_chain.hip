@@ -19,22 +19,8 @@
 
 namespace bwams {
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = bytes + bytes / 8 + 4096;
-        hipError_t e = dev_malloc(&p, cap);
-        if (e != hipSuccess) { cap = 0; return e; }
-        return e;
-    }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 struct ChainState {
+    using DevBuf = bwams::DevBuf<>;
     // chaining scratch (per SA hit)
     DevBuf s_next, s_ql, crec, flt, f_rec, f_first, f_kept, f_sel, nodes;
     // per read
@@ -114,15 +100,6 @@ static void aux_release(int device) {
 
 void chain_state_free(ChainState *s) {
     if (!s) return;
-    DevBuf *all[] = {&s->lsrc, &s->rsrc, &s->s_next, &s->s_ql, &s->crec, &s->flt, &s->f_rec, &s->f_first, &s->f_kept, &s->f_sel,
-                     &s->nodes, &s->n_kept, &s->n_kept_seeds, &s->n_chn, &s->heavy, &s->redo, &s->slice, &s->okeys, &s->okeys2, &s->ovals, &s->ovals2, &s->read_base, &s->frac, &s->wide,
-                     &s->chain_off, &s->chains, &s->seeds, &s->seeds2, &s->sw_qb, &s->sw_rb, &s->sw_read, &s->sw_newn, &s->sw_res, &s->dd_regs, &s->dd_ord, &s->dd_srt, &s->dd_eh,
-                     &s->dd_nout, &s->dd_wide, &s->dd_off, &s->dd_out, &s->dd_light, &s->pe_keys, &s->pe_keys2, &s->pr_na, &s->pr_wide, &s->pr_offs, &s->pr_anchor, &s->pr_slot, &s->pr_task, &s->pr_trb, &s->pr_tl1, &s->pr_twide, &s->pr_toffs,
-                     &s->pr_pairs, &s->pr_tref, &s->pr_tqer, &s->pr_aln, &s->pr_pool, &s->pr_ord, &s->pr_srt, &s->pr_z, &s->pr_nfin, &s->pr_npri, &s->pr_nsw, &s->pr_full, &s->pr_owide,
-                     &s->pr_ooff, &s->pr_out, &s->pr_res, &s->et_mems, &s->et_moff, &s->et_hits, &s->et_hoff, &s->et_smem, &s->et_cnt, &s->et_off, &s->et_coord, &s->et_srt, &s->er_wide, &s->er_off, &s->er_scr, &s->er_n, &s->er_rev, &s->er_out, &s->er_ooff, &s->mg_wide, &s->mg_off, &s->mg_out, &s->al_need, &s->al_cls, &s->al_off, &s->al_scr, &s->al_list, &s->al_rec, &s->al_wide, &s->al_offs, &s->al_cig, &s->al_md, &s->al_cnt, &s->al_only, &s->sm_names, &s->sm_noff, &s->sm_qual, &s->sm_comm, &s->sm_coff, &s->sm_mapq, &s->sm_len, &s->sm_off, &s->sm_out, &s->sm_logtab, &s->sm_bad, &s->bm_size, &s->bm_roff, &s->bm_off, &s->bm_out, &s->bm_bad, &s->regs, &s->srt, &s->rmax, &s->cnt, &s->state, &s->kreg, &s->cur, &s->lim,
-                     &s->ewide, &s->eoffs, &s->lpairs, &s->lref, &s->lqer, &s->rpairs, &s->rref, &s->rqer, &s->retry};
-    for (DevBuf *d : all)
-        if (d->p) (void)hipFree(d->p);
     if (s->ev_ok) {
         for (auto &e : s->ev) (void)hipEventDestroy(e);
         for (auto &e : s->join) (void)hipEventDestroy(e);
@@ -146,15 +123,8 @@ int scan_rows(bwams_batch *b, const int64_t *in, int64_t *out, int rows, int64_t
         size_t tb = 0;
         BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, in + r * n1, out + r * n1, (int64_t)0, (size_t)n1,
                                           rocprim::plus<int64_t>(), b->stream));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(b->stream));
-            if (b->d_tmp) (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp, tb, in + r * n1, out + r * n1, (int64_t)0, (size_t)n1,
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp.p, tb, in + r * n1, out + r * n1, (int64_t)0, (size_t)n1,
                                           rocprim::plus<int64_t>(), b->stream));
     }
     return BWAMS_OK;
@@ -184,18 +154,18 @@ int check_opt(const bwams_mem_opt_t *o, const char *who) {
 
 int dev_bns(bwams_index *ix, DevBns *out) {
     const int64_t l_pac = (ix->fmi.ref_seq_len - 1) / 2;
-    if (!ix->d_contigs) {                       // default: one sequence spanning the whole text
+    if (!ix->d_contigs.p) {                     // default: one sequence spanning the whole text
         bwams_contig_t c;
         c.offset = 0; c.len = (int32_t)l_pac; c.is_alt = 0;
         if (l_pac > 0x7fffffffLL) {
             set_last_error("the index holds more than 2^31 bases: call bwams_index_set_contigs with the real sequences");
             return BWAMS_ERR_ARG;
         }
-        BWAMS_HIP(dev_malloc(&ix->d_contigs, sizeof c));
-        BWAMS_HIP(hipMemcpy(ix->d_contigs, &c, sizeof c, hipMemcpyHostToDevice));
+        BWAMS_HIP(ix->d_contigs.alloc(sizeof c));
+        BWAMS_HIP(hipMemcpy(ix->d_contigs.p, &c, sizeof c, hipMemcpyHostToDevice));
         ix->n_seqs = 1;
     }
-    out->contigs = reinterpret_cast<const bwams_contig_t *>(ix->d_contigs);
+    out->contigs = ix->d_contigs.as<const bwams_contig_t>();
     out->n_seqs = ix->n_seqs;
     out->l_pac = l_pac;
     return BWAMS_OK;
@@ -235,10 +205,8 @@ int bwams_index_set_contigs(bwams_index_t *ix, const bwams_contig_t *contigs, in
         return BWAMS_ERR_ARG;
     }
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (ix->d_contigs) (void)hipFree(ix->d_contigs);
-    ix->d_contigs = nullptr;
-    BWAMS_HIP(dev_malloc(&ix->d_contigs, (size_t)n_seqs * sizeof(bwams_contig_t)));
-    BWAMS_HIP(hipMemcpy(ix->d_contigs, contigs, (size_t)n_seqs * sizeof(bwams_contig_t), hipMemcpyHostToDevice));
+    BWAMS_HIP(ix->d_contigs.alloc((size_t)n_seqs * sizeof(bwams_contig_t)));
+    BWAMS_HIP(hipMemcpy(ix->d_contigs.p, contigs, (size_t)n_seqs * sizeof(bwams_contig_t), hipMemcpyHostToDevice));
     ix->n_seqs = n_seqs;
     return BWAMS_OK;
 }
@@ -246,7 +214,7 @@ int bwams_index_set_contigs(bwams_index_t *ix, const bwams_contig_t *contigs, in
 // mem_flt_chained_seeds for the chunk's long reads (seed_sw.hip): re-score short seeds with the local-SW
 // kernel, drop the weak ones, re-pack the seed array
 static int flt_chained_seeds(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt, const DevBns &bns) {
-    if (!b->idx->d_ref) {
+    if (!b->idx->fmi.ref) {
         set_last_error("bwams_chain_run: reads of ~1100 bases and more need the .0123 reference (mem_flt_chained_seeds)");
         return BWAMS_ERR_ARG;
     }
@@ -267,7 +235,7 @@ static int flt_chained_seeds(bwams_batch *b, ChainState *s, const bwams_mem_opt_
     SeedSwArgs W;
     W.chains = s->chains.as<bwams_chain_t>(); W.n_chains = C;
     W.seeds = s->seeds.as<bwams_chain_seed_t>(); W.n_seeds = N;
-    W.enc = b->d_enc; W.cum = b->d_cum; W.nseq = s->nseq; W.ref = b->idx->fmi.ref; W.bns = bns; W.opt = *opt;
+    W.enc = b->d_enc.p; W.cum = b->d_cum.p; W.nseq = s->nseq; W.ref = b->idx->fmi.ref; W.bns = bns; W.opt = *opt;
     W.cnt = s->cnt.as<int32_t>(); W.win_qb = s->sw_qb.as<int32_t>(); W.win_rb = s->sw_rb.as<int64_t>();
     W.seed_read = s->sw_read.as<int32_t>();
     launch_seedsw_plan(W, s->ewide.as<int64_t>(), st);
@@ -290,7 +258,7 @@ static int flt_chained_seeds(bwams_batch *b, ChainState *s, const bwams_mem_opt_
         SwParams prm;
         sw_params(*opt, 0, &prm);
         (void)launch_ksw(s->lpairs.as<bwams_seqpair_t>(), tot[0], s->lref.as<uint8_t>(), s->lqer.as<uint8_t>(), prm, 208, 200,
-                         s->sw_res.p, b->d_ctr, b->cu_count, st);
+                         s->sw_res.p, b->d_ctr.p, b->cu_count, st);
     }
     // keep / drop, new chain lengths, packed offsets (eoffs row 0 still holds the task index of each seed)
     int64_t *cw = s->ewide.as<int64_t>();                // reused: C + 1 entries
@@ -327,7 +295,7 @@ int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_cha
     if (rc) return rc;
     if ((rc = bwams_seed_counts(b, nullptr, nullptr))) return rc;     // sizes of the seed stage (and its overflow check)
     SeedView sv;
-    sv.smem = b->d_sorted; sv.n_smem = b->n_smem; sv.sa_off = b->d_sa_off; sv.sa_coord = b->d_sa_coord; sv.n_sa = b->n_sa;
+    sv.smem = b->d_sorted.p; sv.n_smem = b->n_smem; sv.sa_off = b->d_sa_off.p; sv.sa_coord = b->d_sa_coord.p; sv.n_sa = b->n_sa;
     sv.one_smem_quirk = true;
     return chain_common(b, opt, sv, n_chains, n_seeds);
 }
@@ -416,7 +384,7 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
 
     ChainArgs A;
     A.smem = sv.smem; A.n_smem = sv.n_smem; A.sa_off = sv.sa_off; A.sa_coord = sv.sa_coord;
-    A.cum = b->d_cum; A.nseq = nseq;
+    A.cum = b->d_cum.p; A.nseq = nseq;
     if ((rc = dev_bns(b->idx, &A.bns))) return rc;
     A.opt = *opt;
     A.s_next = s->s_next.as<int32_t>(); A.s_ql = s->s_ql.as<int2>();
@@ -427,12 +395,12 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
     A.n_chn = s->n_chn.as<int32_t>(); A.heavy = s->heavy.as<int32_t>(); A.redo = s->redo.as<int32_t>();
     A.slice = s->slice.as<int64_t>(); A.order = s->ovals2.as<uint32_t>();
     A.read_base = s->read_base.as<int64_t>(); A.frac_rep = s->frac.as<float>();
-    A.ctr = b->d_ctr;
+    A.ctr = b->d_ctr.p;
     A.seed_batch = knobs().chain_batch;
 
     BWAMS_HIP(hipEventRecord(s->ev[0], st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->chain_redo, 0, 2 * sizeof(unsigned long long), st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->chain_overflow, 0, 29 * sizeof(unsigned long long), st));   // overflow, longread, n_heavy, chain_class[10], chain_ticket[10], heavy_tickets[6]
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_redo, 0, 2 * sizeof(unsigned long long), st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_overflow, 0, 29 * sizeof(unsigned long long), st));   // overflow, longread, n_heavy, chain_class[10], chain_ticket[10], heavy_tickets[6]
     // mem_chain_seeds' loop guard `pos < num_smem - 1` (bwamem.cpp:819) makes a work item with exactly
     // one SMEM produce no chain at all
     if ((sv.one_smem_quirk ? sv.n_smem <= 1 : sv.n_smem <= 0) || n_sa == 0) {
@@ -444,15 +412,8 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
         size_t tb = 0;
         BWAMS_HIP(rocprim::radix_sort_pairs_desc(nullptr, tb, s->okeys.as<uint32_t>(), s->okeys2.as<uint32_t>(),
                                                  s->ovals.as<uint32_t>(), s->ovals2.as<uint32_t>(), (size_t)nseq, 0, 32, st));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(st));
-            if (b->d_tmp) (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(rocprim::radix_sort_pairs_desc(b->d_tmp, tb, s->okeys.as<uint32_t>(), s->okeys2.as<uint32_t>(),
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(rocprim::radix_sort_pairs_desc(b->d_tmp.p, tb, s->okeys.as<uint32_t>(), s->okeys2.as<uint32_t>(),
                                                  s->ovals.as<uint32_t>(), s->ovals2.as<uint32_t>(), (size_t)nseq, 0, 32, st));
         if (launch_chain(A, s->okeys.as<uint32_t>(), b->cu_count, st, s->aux, s->fork, s->join)) {
             set_last_error("bwams_chain_run: stream fork/join failed");
@@ -469,12 +430,12 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
     } else {
         BWAMS_HIP(hipMemsetAsync(s->chain_off.p, 0, (size_t)n1 * 16, st));       // no reads: both offset rows are {0}
     }
-    BWAMS_HIP(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     {
         const bool vb = knobs().verbose != 0;
         if (vb) {
-            const unsigned long long *d = b->h_ctr->dbg;
+            const unsigned long long *d = b->h_ctr.p->dbg;
             fprintf(stderr, "[bwams_chain_run] filter wave tier: reads by chains <=32 %llu <=64 %llu <=128 %llu <=256 %llu <=512 %llu <=960 %llu more %llu; "
                             "Mcycles: sequential(HBM) %.1f sort %.1f filter %.1f; chains %llu selected %llu; longest read: sort %.2f filter %.2f Mcycles, most chains %llu, most selected %llu\n",
                     d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7] / 1e6, d[8] / 1e6, d[9] / 1e6, d[11], d[10], d[12] / 1e6, d[13] / 1e6, d[14], d[15]);
@@ -488,12 +449,12 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
 #endif
         }
     }
-    if (b->h_ctr->chain_overflow) {
+    if (b->h_ctr.p->chain_overflow) {
         set_last_error("bwams_chain_run: internal B-tree node region exhausted");
         return BWAMS_ERR_CAPACITY;
     }
-    const bool has_long = b->h_ctr->chain_longread != 0;
-    s->n_chain_redo = (int64_t)b->h_ctr->chain_redo;
+    const bool has_long = b->h_ctr.p->chain_longread != 0;
+    s->n_chain_redo = (int64_t)b->h_ctr.p->chain_redo;
     s->n_chains = tot[0]; s->n_seeds = tot[1]; s->nseq = nseq;
     BWAMS_HIP(s->chains.ensure((size_t)(tot[0] + 1) * sizeof(bwams_chain_t)));
     BWAMS_HIP(s->seeds.ensure((size_t)(tot[1] + 1) * sizeof(bwams_chain_seed_t)));
@@ -583,16 +544,16 @@ static int ext_args(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt, E
     A->chains = s->chains.as<bwams_chain_t>(); A->n_chains = s->n_chains;
     A->seeds = s->seeds.as<bwams_chain_seed_t>(); A->n_seeds = s->n_seeds;
     A->chain_off = s->chain_off.as<int64_t>(); A->seed_off = s->chain_off.as<int64_t>() + n1;
-    A->enc = b->d_enc; A->cum = b->d_cum; A->nseq = s->nseq;
+    A->enc = b->d_enc.p; A->cum = b->d_cum.p; A->nseq = s->nseq;
     A->ref = b->idx->fmi.ref;
     int rc = dev_bns(b->idx, &A->bns);
     if (rc) return rc;
     A->opt = *opt;
     A->regs = s->regs.as<bwams_alnreg_t>(); A->srt = s->srt.as<uint32_t>(); A->rmax = s->rmax.as<int64_t>();
-    A->cnt = s->cnt.as<int32_t>(); A->ctr = b->d_ctr;
+    A->cnt = s->cnt.as<int32_t>(); A->ctr = b->d_ctr.p;
     A->state = s->state.as<int32_t>(); A->kreg = s->kreg.p;
     A->cur = s->cur.as<int32_t>(); A->lim = s->lim.as<int32_t>();
-    A->sel_heavy = s->heavy.as<int32_t>(); A->n_sel_heavy = &b->d_ctr->sel_heavy; A->sel_ticket = &b->d_ctr->sel_ticket;
+    A->sel_heavy = s->heavy.as<int32_t>(); A->n_sel_heavy = &b->d_ctr.p->sel_heavy; A->sel_ticket = &b->d_ctr.p->sel_ticket;
     return BWAMS_OK;
 }
 
@@ -612,7 +573,7 @@ static int ext_plan(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt, i
     BWAMS_HIP(s->heavy.ensure((size_t)n1 * 4));
     int rc = ext_args(b, s, opt, A);
     if (rc) return rc;
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->sel_heavy, 0, 4 * sizeof(unsigned long long), b->stream));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->sel_heavy, 0, 4 * sizeof(unsigned long long), b->stream));
     launch_ext_heavy_list(*A, b->stream);
     BWAMS_HIP(hipMemsetAsync(s->cur.p, 0, (size_t)n1 * 4, b->stream));
     BWAMS_HIP(hipMemsetAsync(s->lim.p, 0, (size_t)n1 * 4, b->stream));
@@ -660,7 +621,7 @@ int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_
         set_last_error("bwams_extend_build: run bwams_chain_run (or bwams_chain_upload) first");
         return BWAMS_ERR_ARG;
     }
-    if (!b->idx->d_ref) {
+    if (!b->idx->fmi.ref) {
         set_last_error("bwams_extend_build: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -699,10 +660,11 @@ static int run_side(bwams_batch *b, ChainState *s, const ExtArgs &A, int right, 
     sw_params(A.opt, right ? A.opt.pen_clip3 : A.opt.pen_clip5, &prm);
     const int qmax = b->max_read_len > 1 ? b->max_read_len : 1;
     if (n == 0) return BWAMS_OK;
-    unsigned long long *d_nretry = &b->d_ctr->n_retry;
+    unsigned long long *d_nretry = &b->d_ctr.p->n_retry;
     BWAMS_HIP(hipMemsetAsync(d_nretry, 0, sizeof(unsigned long long), st));
-    if (int erc = bsw_list_ensure(b, n)) return erc;
-    if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr, b->cu_count, st, b->d_bsw_list, s->aux, s->fork, s->join, src, dir)) {
+    if (bsw_list_bytes(n) > b->d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(st));   // the last launch may still read the lists
+    BWAMS_HIP(b->d_bsw_list.ensure(bsw_list_bytes(n), bsw_list_bytes(n + n / 4 + 1024)));
+    if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr.p, b->cu_count, st, b->d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) {
         set_last_error(lrc == -2 ? "banded SW: a query longer than ~18000 bases does not fit the LDS kernel" : "banded SW: stream fork/join failed");
         return lrc == -2 ? BWAMS_ERR_UNSUPPORTED : BWAMS_ERR_DEVICE;
     }
@@ -711,7 +673,7 @@ static int run_side(bwams_batch *b, ChainState *s, const ExtArgs &A, int right, 
     BWAMS_HIP(hipMemcpyAsync(&nr, d_nretry, sizeof nr, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     if (nr) {
-        if (launch_bsw(s->retry.as<bwams_seqpair_t>(), (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr, b->cu_count, st, b->d_bsw_list, s->aux, s->fork, s->join, src, dir)) return BWAMS_ERR_DEVICE;
+        if (launch_bsw(s->retry.as<bwams_seqpair_t>(), (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr.p, b->cu_count, st, b->d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) return BWAMS_ERR_DEVICE;
         launch_ext_post(A, right, s->retry.as<bwams_seqpair_t>(), (int64_t)nr, A.opt.w << 1, 1, nullptr, d_nretry, st);
     }
     *n_retry_out += (int64_t)nr;
@@ -726,7 +688,7 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
         set_last_error("bwams_extend_run: run bwams_chain_run (or bwams_chain_upload) first");
         return BWAMS_ERR_ARG;
     }
-    if (!b->idx->d_ref) {
+    if (!b->idx->fmi.ref) {
         set_last_error("bwams_extend_run: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -742,7 +704,7 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
     s->built = s->ext_done = s->dedup_done = s->pair_done = false;
     ExtArgs A;
     BWAMS_HIP(hipEventRecord(s->ev[10], st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->bsw_cells, 0, sizeof(unsigned long long), st));      // DP cells of this run, all rounds
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->bsw_cells, 0, sizeof(unsigned long long), st));      // DP cells of this run, all rounds
     BWAMS_HIP(hipEventRecord(s->ev[2], st));
     if ((rc = ext_plan(b, s, opt, opt->extend_all != 0, &A))) return rc;
     int64_t tot_left = 0, tot_right = 0;
@@ -758,19 +720,19 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
         launch_ext_right_h0(A, s->rpairs.as<bwams_seqpair_t>(), s->n_right, st);
         if ((rc = run_side(b, s, A, 1, &s->n_retry_right))) return rc;
         if (round == 0) { BWAMS_HIP(hipEventRecord(s->ev[7], st)); BWAMS_HIP(hipEventRecord(s->ev[8], st)); }
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr->n_req, 0, sizeof(unsigned long long), st));
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr->sel_ticket, 0, 3 * sizeof(unsigned long long), st));
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr->n_rest, 0, sizeof(unsigned long long), st));
+        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->n_req, 0, sizeof(unsigned long long), st));
+        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->sel_ticket, 0, 3 * sizeof(unsigned long long), st));
+        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->n_rest, 0, sizeof(unsigned long long), st));
         const bool vb_sel = knobs().verbose != 0;
         const bool verbose_sel = vb_sel;
-        if (verbose_sel) BWAMS_HIP(hipMemsetAsync(b->d_ctr->dbg, 0, sizeof b->d_ctr->dbg, st));
+        if (verbose_sel) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg, 0, sizeof b->d_ctr.p->dbg, st));
         if (s->n_seeds && launch_ext_select(A, b->cu_count, st, s->aux, s->fork, s->join)) {
             set_last_error("bwams_extend_run: stream fork/join failed");
             return BWAMS_ERR_DEVICE;
         }
         if (verbose_sel) {           // filled only by a build of ext_aln.hip with -DBWAMS_SELDBG
             unsigned long long d[16];
-            BWAMS_HIP(hipMemcpyAsync(d, b->d_ctr->dbg, sizeof d, hipMemcpyDeviceToHost, st));
+            BWAMS_HIP(hipMemcpyAsync(d, b->d_ctr.p->dbg, sizeof d, hipMemcpyDeviceToHost, st));
             BWAMS_HIP(hipStreamSynchronize(st));
             if (d[0])
                 fprintf(stderr, "[bwams_extend_run] selection walk, round %d: %llu reads, Mticks total %.2f fetch %.2f scan %.2f keep-anyway %.2f; %llu slots, %llu chunks, "
@@ -779,8 +741,8 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
         }
         if (round == 0) BWAMS_HIP(hipEventRecord(s->ev[9], st));
         unsigned long long n_req = 0, n_rest = 0;
-        BWAMS_HIP(hipMemcpyAsync(&n_req, &b->d_ctr->n_req, sizeof n_req, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipMemcpyAsync(&n_rest, &b->d_ctr->n_rest, sizeof n_rest, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(&n_req, &b->d_ctr.p->n_req, sizeof n_req, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(&n_rest, &b->d_ctr.p->n_rest, sizeof n_rest, hipMemcpyDeviceToHost, st));
         BWAMS_HIP(hipStreamSynchronize(st));
         if (n_req == 0) break;
         // A round costs about as much as ~10^5 extensions whatever it holds (launches, the selection's walk of the heaviest
@@ -848,7 +810,7 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
     DedupArgs D;
     D.regs = s->dd_regs.as<bwams_alnreg_t>();
     D.seed_off = s->chain_off.as<int64_t>() + n1;
-    D.enc = b->d_enc; D.cum = b->d_cum; D.nseq = s->nseq; D.ref = b->idx->fmi.ref;
+    D.enc = b->d_enc.p; D.cum = b->d_cum.p; D.nseq = s->nseq; D.ref = b->idx->fmi.ref;
     if ((rc = dev_bns(b->idx, &D.bns))) return rc;
     D.opt = *opt;
     D.ord = s->dd_ord.as<int32_t>(); D.srt = s->dd_srt.p; D.eh = s->dd_eh.as<int2>(); D.eh_lanes = n_lanes;
@@ -857,14 +819,14 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
     D.force_seq = knobs().dedup_seq;      // 1: every read through the one-lane form (tests)
     BWAMS_HIP(s->dd_light.ensure((size_t)n1 * 4));
     D.heavy = s->heavy.as<int32_t>(); D.light = s->dd_light.as<int32_t>();
-    D.n_heavy_ctr = &b->d_ctr->dedup_heavy; D.ticket = &b->d_ctr->dedup_ticket; D.n_light_ctr = &b->d_ctr->dedup_light;
-    D.ticket2 = &b->d_ctr->dedup_ticket2; D.ticket3 = &b->d_ctr->dedup_ticket3;
+    D.n_heavy_ctr = &b->d_ctr.p->dedup_heavy; D.ticket = &b->d_ctr.p->dedup_ticket; D.n_light_ctr = &b->d_ctr.p->dedup_light;
+    D.ticket2 = &b->d_ctr.p->dedup_ticket2; D.ticket3 = &b->d_ctr.p->dedup_ticket3;
     const bool vb_dd = knobs().verbose != 0;
     const bool verbose_dd = vb_dd;
-    D.dbg = verbose_dd ? b->d_ctr->dbg : nullptr;
-    if (verbose_dd) BWAMS_HIP(hipMemsetAsync(b->d_ctr->dbg, 0, sizeof b->d_ctr->dbg, st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->dedup_heavy, 0, 3 * sizeof(unsigned long long), st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->dedup_ticket2, 0, 2 * sizeof(unsigned long long), st));
+    D.dbg = verbose_dd ? b->d_ctr.p->dbg : nullptr;
+    if (verbose_dd) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg, 0, sizeof b->d_ctr.p->dbg, st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->dedup_heavy, 0, 3 * sizeof(unsigned long long), st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->dedup_ticket2, 0, 2 * sizeof(unsigned long long), st));
     BWAMS_HIP(hipEventRecord(s->ev[12], st));
     // work on a copy: bwams_extend_fetch stays valid
     if (N) BWAMS_HIP(hipMemcpyAsync(D.regs, s->regs.p, (size_t)N * sizeof(bwams_alnreg_t), hipMemcpyDeviceToDevice, st));
@@ -883,11 +845,11 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
         BWAMS_HIP(hipMemsetAsync(s->dd_off.p, 0, 8, st));          // an empty chunk: reg_off = {0}
     }
     BWAMS_HIP(hipEventRecord(s->ev[13], st));
-    if (verbose_dd) BWAMS_HIP(hipMemcpyAsync(b->h_ctr->dbg, b->d_ctr->dbg, sizeof b->d_ctr->dbg, hipMemcpyDeviceToHost, st));
+    if (verbose_dd) BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p->dbg, b->d_ctr.p->dbg, sizeof b->d_ctr.p->dbg, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
     if (verbose_dd) {
-        const unsigned long long *d = b->h_ctr->dbg;
+        const unsigned long long *d = b->h_ctr.p->dbg;
         fprintf(stderr, "[bwams_dedup_run] largest wave instance: %llu reads, %llu slots, %llu alive; Mcycles: load %.1f sort(end) %.1f pairs %.1f reload %.1f sort(score) %.1f store %.1f; "
                         "longest read: sort(end) %.2f pairs %.2f sort(score) %.2f, whole %.2f (read %llu, %llu regions; %llu patch alignments in %.2f, %llu scan trips); all reads: %llu patch alignments in %.1f\n",
                 d[0], d[1], d[2], d[3] / 1e6, d[4] / 1e6, d[5] / 1e6, d[6] / 1e6, d[7] / 1e6, d[8] / 1e6, d[9] / 1e6, d[10] / 1e6, d[11] / 1e6, d[12] / 1e6, d[13], d[14],
@@ -973,7 +935,7 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     BWAMS_HIP(s->pr_res.ensure((size_t)(nseq / 2 + 1) * sizeof(bwams_pair_t)));
     PairArgs A;
     A.regs = s->dd_out.as<bwams_alnreg_t>(); A.reg_off = s->dd_off.as<int64_t>();
-    A.enc = b->d_enc; A.cum = b->d_cum; A.nseq = nseq; A.ref = b->idx->fmi.ref;
+    A.enc = b->d_enc.p; A.cum = b->d_cum.p; A.nseq = nseq; A.ref = b->idx->fmi.ref;
     if ((rc = dev_bns(b->idx, &A.bns))) return rc;
     A.opt = *opt;
     for (int k = 0; k < 4; ++k) A.pes[k] = pes[k];
@@ -986,12 +948,12 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     int64_t *aoff = s->pr_offs.as<int64_t>(), *ooff = aoff + n1;
     A.aoff = aoff; A.ooff = ooff;
     A.n_fin = s->pr_nfin.as<int32_t>(); A.n_pri = s->pr_npri.as<int32_t>(); A.n_sw = s->pr_nsw.as<int32_t>();
-    A.full = s->pr_full.as<uint8_t>(); A.ctr = b->d_ctr;
+    A.full = s->pr_full.as<uint8_t>(); A.ctr = b->d_ctr.p;
     A.anchor = nullptr; A.slot_read = nullptr; A.n_slots = 0; A.task = nullptr; A.trb = nullptr; A.tl1 = nullptr; A.aln = nullptr;
     A.pool = nullptr; A.ord = nullptr; A.zbuf = nullptr; A.srt = nullptr; A.heavy = nullptr;
     BWAMS_HIP(hipEventRecord(s->ev[14], st));
     BWAMS_HIP(hipMemsetAsync(A.full, 0, (size_t)n1, st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->pair_full, 0, 2 * sizeof(unsigned long long), st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->pair_full, 0, 2 * sizeof(unsigned long long), st));
     // anchors per read, pool capacities
     launch_pair_count(A, s->pr_wide.as<int64_t>(), st);
     if ((rc = scan_rows(b, s->pr_wide.as<int64_t>(), aoff, 1, n1))) return rc;
@@ -1043,28 +1005,28 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
                           b->cu_count, st);
         PR_TRACE("build done");
         if (tot[0] > 0 && launch_ksw(s->pr_pairs.as<bwams_seqpair_t>(), tot[0], s->pr_tref.as<uint8_t>(), s->pr_tqer.as<uint8_t>(), prm,
-                                     ((b->max_read_len + 15) / 16) * 16, tmax, s->pr_aln.p, b->d_ctr, b->cu_count, st)) {
+                                     ((b->max_read_len + 15) / 16) * 16, tmax, s->pr_aln.p, b->d_ctr.p, b->cu_count, st)) {
             set_last_error("bwams_pair_run: rescue window too long for the local-SW kernel");
             return BWAMS_ERR_UNSUPPORTED;
         }
         PR_TRACE("ksw done");
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr->pair_heavy, 0, 2 * sizeof(unsigned long long), st));
+        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->pair_heavy, 0, 2 * sizeof(unsigned long long), st));
         launch_pair_post(A, b->cu_count, st);
 #ifdef BWAMS_PAIRDBG
         if (knobs().verbose) {
             unsigned long long d[80];
             BWAMS_HIP(hipStreamSynchronize(st));
-            BWAMS_HIP(hipMemcpy(d, b->d_ctr->dbg, sizeof d, hipMemcpyDeviceToHost));
+            BWAMS_HIP(hipMemcpy(d, b->d_ctr.p->dbg, sizeof d, hipMemcpyDeviceToHost));
             fprintf(stderr, "[pair_post_wave] reads %llu (mean %.0f regions at the end, %.1f anchors, %.1f rescues), %.3f ms of a wave per read (longest %.3f ms); sorts %llu = %.1f per read, %.3f ms per read; "
                     "with equal keys %llu, %.3f ms per read in them\n", d[20], d[20] ? (double)d[27] / d[20] : 0.0, d[20] ? (double)d[28] / d[20] : 0.0, d[20] ? (double)d[29] / d[20] : 0.0,
                     d[20] ? d[24] * 1e-5 / d[20] : 0.0, d[25] * 1e-5, d[21], d[20] ? (double)d[21] / d[20] : 0.0, d[20] ? d[26] * 1e-5 / d[20] : 0.0, d[22], d[20] ? d[23] * 1e-5 / d[20] : 0.0);
-            BWAMS_HIP(hipMemsetAsync(b->d_ctr->dbg + 20, 0, 10 * sizeof(unsigned long long), st));
+            BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg + 20, 0, 10 * sizeof(unsigned long long), st));
         }
 #endif
         PR_TRACE("post done");
         s->pr_tasks += tot[0];
         unsigned long long flags[2] = {0, 0};
-        BWAMS_HIP(hipMemcpyAsync(flags, &b->d_ctr->pair_full, sizeof flags, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(flags, &b->d_ctr.p->pair_full, sizeof flags, hipMemcpyDeviceToHost, st));
         BWAMS_HIP(hipStreamSynchronize(st));
         if (flags[1]) {
             set_last_error("bwams_pair_run: internal error, a rescue alignment was missing in the second pass");
@@ -1074,8 +1036,8 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
         if (pass == 1 || flags[0] == 0) break;
     }
     // mem_mark_primary_se of every read, regions in final order, then mem_pair
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->pair_heavy, 0, 2 * sizeof(unsigned long long), st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr->pair_ticket2, 0, sizeof(unsigned long long), st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->pair_heavy, 0, 2 * sizeof(unsigned long long), st));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->pair_ticket2, 0, sizeof(unsigned long long), st));
     launch_pair_mark(A, b->cu_count, st);
     PR_TRACE("mark done");
     launch_pair_widen(A, s->pr_owide.as<int64_t>(), st);
@@ -1153,7 +1115,7 @@ static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t so
     }
     int rc = check_opt(opt, "bwams_reg2aln_run");
     if (rc) return rc;
-    if (!b->idx->d_ref) {
+    if (!b->idx->fmi.ref) {
         set_last_error("bwams_reg2aln_run: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
@@ -1167,7 +1129,7 @@ static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t so
     A.regs = source ? s->pr_out.as<bwams_alnreg_t>() : s->dd_out.as<bwams_alnreg_t>();
     A.reg_off = source ? s->pr_ooff.as<int64_t>() : s->dd_off.as<int64_t>();
     A.n_regs = n; A.nseq = s->nseq;
-    A.enc = b->d_enc; A.cum = b->d_cum; A.ref = b->idx->fmi.ref;
+    A.enc = b->d_enc.p; A.cum = b->d_cum.p; A.ref = b->idx->fmi.ref;
     if ((rc = dev_bns(b->idx, &A.bns))) return rc;
     A.opt = *opt;
     A.only = only;
@@ -1255,15 +1217,8 @@ int bwams_reg2aln_run_sam(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bw
         BWAMS_HIP(s->sm_bad.ensure(64));
         int64_t *d_sum = s->sm_bad.as<int64_t>() + 1;
         BWAMS_HIP(rocprim::reduce(nullptr, tb, s->al_only.as<uint8_t>(), d_sum, (int64_t)0, (size_t)(n > 0 ? n : 0), rocprim::plus<int64_t>(), st));
-        if (tb > b->tmp_bytes) {
-            BWAMS_HIP(hipStreamSynchronize(st));
-            if (b->d_tmp) (void)hipFree(b->d_tmp);
-            b->d_tmp = nullptr;
-            BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-            b->tmp_bytes = tb;
-        }
-        tb = b->tmp_bytes;
-        BWAMS_HIP(rocprim::reduce(b->d_tmp, tb, s->al_only.as<uint8_t>(), d_sum, (int64_t)0, (size_t)(n > 0 ? n : 0), rocprim::plus<int64_t>(), st));
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(rocprim::reduce(b->d_tmp.p, tb, s->al_only.as<uint8_t>(), d_sum, (int64_t)0, (size_t)(n > 0 ? n : 0), rocprim::plus<int64_t>(), st));
         BWAMS_HIP(hipMemcpyAsync(n_needed, d_sum, 8, hipMemcpyDeviceToHost, st));
     }
     return reg2aln_impl(b, opt, 1, s->al_only.as<uint8_t>(), n_aln, n_cigar_ops, md_bytes);
@@ -1306,11 +1261,11 @@ int bwams_index_set_contig_names(bwams_index_t *ix, const char *names, const int
             return BWAMS_ERR_ARG;
         }
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (ix->d_ctg_names) { (void)hipFree(ix->d_ctg_names); (void)hipFree(ix->d_ctg_off); ix->d_ctg_names = ix->d_ctg_off = nullptr; }
-    BWAMS_HIP(dev_malloc(&ix->d_ctg_names, (size_t)name_off[n]));
-    BWAMS_HIP(dev_malloc(&ix->d_ctg_off, (size_t)(n + 1) * 4));
-    BWAMS_HIP(hipMemcpy(ix->d_ctg_names, names, (size_t)name_off[n], hipMemcpyHostToDevice));
-    BWAMS_HIP(hipMemcpy(ix->d_ctg_off, name_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
+    ix->d_ctg_names.release(); ix->d_ctg_off.release();
+    BWAMS_HIP(ix->d_ctg_names.alloc((size_t)name_off[n]));
+    BWAMS_HIP(ix->d_ctg_off.alloc((size_t)(n + 1) * 4));
+    BWAMS_HIP(hipMemcpy(ix->d_ctg_names.p, names, (size_t)name_off[n], hipMemcpyHostToDevice));
+    BWAMS_HIP(hipMemcpy(ix->d_ctg_off.p, name_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
     return bam_names_index(ix, names, name_off, n);
 }
 
@@ -1326,11 +1281,11 @@ int bwams_index_set_contig_annos(bwams_index_t *ix, const char *annos, const int
             return BWAMS_ERR_ARG;
         }
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (ix->d_ctg_annos) { (void)hipFree(ix->d_ctg_annos); (void)hipFree(ix->d_ctg_anno_off); ix->d_ctg_annos = ix->d_ctg_anno_off = nullptr; }
-    BWAMS_HIP(dev_malloc(&ix->d_ctg_annos, (size_t)anno_off[n]));
-    BWAMS_HIP(dev_malloc(&ix->d_ctg_anno_off, (size_t)(n + 1) * 4));
-    BWAMS_HIP(hipMemcpy(ix->d_ctg_annos, annos, (size_t)anno_off[n], hipMemcpyHostToDevice));
-    BWAMS_HIP(hipMemcpy(ix->d_ctg_anno_off, anno_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
+    ix->d_ctg_annos.release(); ix->d_ctg_anno_off.release();
+    BWAMS_HIP(ix->d_ctg_annos.alloc((size_t)anno_off[n]));
+    BWAMS_HIP(ix->d_ctg_anno_off.alloc((size_t)(n + 1) * 4));
+    BWAMS_HIP(hipMemcpy(ix->d_ctg_annos.p, annos, (size_t)anno_off[n], hipMemcpyHostToDevice));
+    BWAMS_HIP(hipMemcpy(ix->d_ctg_anno_off.p, anno_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
     return BWAMS_OK;
 }
 
@@ -1340,7 +1295,7 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
         set_last_error("bwams_sam_upload: names and their offsets are required; comments come with offsets");
         return BWAMS_ERR_ARG;
     }
-    if (b->nseq <= 0 || !b->d_cum) {
+    if (b->nseq <= 0 || !b->d_cum.p) {
         set_last_error("bwams_sam_upload: upload the reads first (bwams_seed_upload)");
         return BWAMS_ERR_ARG;
     }
@@ -1391,7 +1346,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
         set_last_error("bwams_sam_run: run bwams_sam_upload for this chunk first");
         return BWAMS_ERR_ARG;
     }
-    if (!b->idx->d_ctg_names) {
+    if (!b->idx->d_ctg_names.p) {
         set_last_error("bwams_sam_run: the index has no sequence names (bwams_index_set_contig_names)");
         return BWAMS_ERR_ARG;
     }
@@ -1403,7 +1358,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
         set_last_error("bwams_sam_run: MEM_F_PE / MEM_F_SMARTPE (the caller's business) and MEM_F_XB are not built");
         return BWAMS_ERR_UNSUPPORTED;
     }
-    if ((sopt->flag & BWAMS_MEM_F_REF_HDR) && !b->idx->d_ctg_annos) {
+    if ((sopt->flag & BWAMS_MEM_F_REF_HDR) && !b->idx->d_ctg_annos.p) {
         set_last_error("bwams_sam_run: MEM_F_REF_HDR needs the sequences' annotations (bwams_index_set_contig_annos)");
         return BWAMS_ERR_ARG;
     }
@@ -1429,15 +1384,15 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     A.regs = s->pr_out.as<bwams_alnreg_t>(); A.reg_off = s->pr_ooff.as<int64_t>();
     A.n_regs = n; A.nseq = nseq;
     A.rec = s->al_rec.as<bwams_aln_t>(); A.cig = s->al_cig.as<uint32_t>(); A.md = s->al_md.as<char>();
-    A.enc = b->d_enc; A.cum = b->d_cum;
+    A.enc = b->d_enc.p; A.cum = b->d_cum.p;
     A.names = s->sm_names.as<char>(); A.name_off = s->sm_noff.as<int64_t>();
     A.quals = s->sm_has_qual ? s->sm_qual.as<char>() : nullptr;
     A.comments = s->sm_has_comm ? s->sm_comm.as<char>() : nullptr;
     A.comment_off = s->sm_has_comm ? s->sm_coff.as<int64_t>() : nullptr;
-    A.ctg_names = reinterpret_cast<const char *>(b->idx->d_ctg_names);
-    A.ctg_off = reinterpret_cast<const int32_t *>(b->idx->d_ctg_off);
-    A.ctg_annos = reinterpret_cast<const char *>(b->idx->d_ctg_annos);
-    A.ctg_anno_off = reinterpret_cast<const int32_t *>(b->idx->d_ctg_anno_off);
+    A.ctg_names = b->idx->d_ctg_names.as<const char>();
+    A.ctg_off = b->idx->d_ctg_off.as<const int32_t>();
+    A.ctg_annos = b->idx->d_ctg_annos.as<const char>();
+    A.ctg_anno_off = b->idx->d_ctg_anno_off.as<const int32_t>();
     A.opt = *opt; A.sopt = *sopt;
     A.logtab = s->sm_logtab.as<double>(); A.logtab_n = kLogN;
     A.coef_fac = opt->mapq_coef_len > 0 ? log((double)opt->mapq_coef_len) : 0.;
@@ -1541,7 +1496,7 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
         return BWAMS_ERR_ARG;
     }
     bwams_index *ix = b->idx;
-    if (!ix->d_ctg_sorted || (int64_t)ix->h_ctg_names.size() != ix->n_seqs) {
+    if (!ix->d_ctg_sorted.p || (int64_t)ix->h_ctg_names.size() != ix->n_seqs) {
         set_last_error("bwams_bam_run: the index has no sequence names (bwams_index_set_contig_names)");
         return BWAMS_ERR_ARG;
     }
@@ -1554,11 +1509,8 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     hipStream_t st = b->stream;
     s->bm_done = false;
     const int64_t nseq = s->sm_merged_n >= 0 ? s->sm_merged_n : s->nseq;
-    int64_t *ends = nullptr, n_rec = 0;
-    struct Free {
-        int64_t **p;
-        ~Free() { if (*p) (void)hipFree(*p); }
-    } fr{&ends};
+    DevBuf<int64_t> ends;
+    int64_t n_rec = 0;
     int rc = line_ends(s->sm_out.as<char>(), s->sm_bytes, st, &ends, &n_rec);
     if (rc) return rc;
     BWAMS_HIP(s->bm_size.ensure((size_t)(n_rec + 1) * 8));
@@ -1576,11 +1528,11 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     BamArgs A;
     memset(&A, 0, sizeof A);
     A.text = s->sm_out.as<char>();
-    A.line_end = ends; A.read_off = s->sm_off.as<int64_t>();
+    A.line_end = ends.p; A.read_off = s->sm_off.as<int64_t>();
     A.n_rec = n_rec; A.nseq = nseq;
-    A.ctg_names = reinterpret_cast<const char *>(ix->d_ctg_names);
-    A.ctg_off = reinterpret_cast<const int32_t *>(ix->d_ctg_off);
-    A.ctg_sorted = reinterpret_cast<const int32_t *>(ix->d_ctg_sorted);
+    A.ctg_names = ix->d_ctg_names.as<const char>();
+    A.ctg_off = ix->d_ctg_off.as<const int32_t>();
+    A.ctg_sorted = ix->d_ctg_sorted.as<const int32_t>();
     A.n_ctg = ix->n_seqs;
     A.size = s->bm_size.as<int64_t>(); A.rec_off = s->bm_roff.as<int64_t>();
     A.bad = s->bm_bad.as<unsigned long long>();
@@ -1870,14 +1822,11 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     if ((rc = fastq_classify(fq, &which))) { bwams_fastq_close(fq); return rc; }
     std::vector<int64_t> ids[2];
     for (int64_t i = 0; i < n; ++i) ids[which[(size_t)i]].push_back(i);
-    struct Held {                                        // the text of one run, kept while the batch does the other
-        char *text = nullptr;
-        std::vector<int64_t> off;
-        ~Held() { if (text) (void)hipFree(text); }
-    } held[2];
+    DevBuf<char> held[2];                                // the text of each run, kept while the batch does the other,
+    std::vector<int64_t> held_off[2];                    // and where its reads start
     hipStream_t st = b->stream;
     for (int k = 0; k < 2; ++k) {
-        held[k].off.assign(ids[k].size() + 1, 0);
+        held_off[k].assign(ids[k].size() + 1, 0);
         if (ids[k].empty()) continue;
         bwams_fastq_t *sub = nullptr;
         if ((rc = fastq_subset(fq, ids[k], &sub))) { bwams_fastq_close(fq); return rc; }
@@ -1886,9 +1835,9 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
                              n_processed + (k ? (int64_t)ids[0].size() : 0), flags, &bytes);
         if (rc) { bwams_fastq_close(fq); return rc; }
         ChainState *s = b->chain;
-        hipError_t e = dev_malloc(reinterpret_cast<void **>(&held[k].text), (size_t)bytes + 16);
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(held[k].text, s->sm_out.p, (size_t)bytes, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(held[k].off.data(), s->sm_off.p, held[k].off.size() * 8, hipMemcpyDeviceToHost, st);
+        hipError_t e = held[k].alloc((size_t)bytes + 16);
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(held[k].p, s->sm_out.p, (size_t)bytes, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(held_off[k].data(), s->sm_off.p, held_off[k].size() * 8, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) { bwams_fastq_close(fq); BWAMS_HIP(e); }
     }
@@ -1903,9 +1852,9 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     for (int k = 0; k < 2; ++k)
         for (size_t j = 0; j < ids[k].size(); ++j) rank[(size_t)ids[k][j]] = (int64_t)j;
     for (int64_t i = 0; i < n; ++i) {
-        const Held &h = held[which[(size_t)i]];
+        const std::vector<int64_t> &h = held_off[which[(size_t)i]];
         const size_t j = (size_t)rank[(size_t)i];
-        off[(size_t)i + 1] = off[(size_t)i] + (h.off[j + 1] - h.off[j]);
+        off[(size_t)i + 1] = off[(size_t)i] + (h[j + 1] - h[j]);
     }
     const int64_t total = off[(size_t)n];
     BWAMS_HIP(s->sm_out.ensure((size_t)total + 16));
@@ -1913,9 +1862,9 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     std::vector<SegMove> mv;
     mv.reserve((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
-        const Held &h = held[which[(size_t)i]];
+        const int k = which[(size_t)i];
         const size_t j = (size_t)rank[(size_t)i];
-        mv.push_back({h.text + h.off[j], s->sm_out.as<char>() + off[(size_t)i], h.off[j + 1] - h.off[j]});
+        mv.push_back({held[k].p + held_off[k][j], s->sm_out.as<char>() + off[(size_t)i], held_off[k][j + 1] - held_off[k][j]});
     }
     if ((rc = segment_copy(mv, st))) return rc;
     BWAMS_HIP(hipMemcpyAsync(s->sm_off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
@@ -1928,7 +1877,7 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
 /* ------------------------------------------------------------ mem_perfect2reg ---- */
 
 int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !e || !b->d_emf_out || !b->d_emf_code) {
+    if (!b || !e || !b->d_emf_out.p || !b->d_emf_code.p) {
         set_last_error("bwams_emf_regs_run: run bwams_emf_run first");
         return BWAMS_ERR_ARG;
     }
@@ -1944,7 +1893,7 @@ int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *
     BWAMS_HIP(s->er_ooff.ensure((size_t)n1 * 8));
     BWAMS_HIP(s->er_n.ensure((size_t)n1 * 4)); BWAMS_HIP(s->er_rev.ensure((size_t)n1));
     EmfRegArgs A;
-    A.t = e->t; A.perfect = b->d_emf_out; A.code = b->d_emf_code; A.enc = b->d_enc; A.cum = b->d_cum; A.nseq = nseq;
+    A.t = e->t; A.perfect = b->d_emf_out.p; A.code = b->d_emf_code.p; A.enc = b->d_enc.p; A.cum = b->d_cum.p; A.nseq = nseq;
     if ((rc = dev_bns(b->idx, &A.bns))) return rc;
     A.opt = *opt;
     A.scratch = nullptr;
@@ -2028,15 +1977,8 @@ static int pestat_keys(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt
     size_t tb = 0;
     BWAMS_HIP(rocprim::radix_sort_keys(nullptr, tb, s->pe_keys.as<unsigned long long>(), s->pe_keys2.as<unsigned long long>(),
                                        (size_t)n_pairs, 0, 64, st));
-    if (tb > b->tmp_bytes) {
-        BWAMS_HIP(hipStreamSynchronize(st));
-        if (b->d_tmp) (void)hipFree(b->d_tmp);
-        b->d_tmp = nullptr;
-        BWAMS_HIP(dev_malloc(&b->d_tmp, tb));
-        b->tmp_bytes = tb;
-    }
-    tb = b->tmp_bytes;
-    BWAMS_HIP(rocprim::radix_sort_keys(b->d_tmp, tb, s->pe_keys.as<unsigned long long>(), s->pe_keys2.as<unsigned long long>(),
+    if (int rc = tmp_reserve(b, tb)) return rc;
+    BWAMS_HIP(rocprim::radix_sort_keys(b->d_tmp.p, tb, s->pe_keys.as<unsigned long long>(), s->pe_keys2.as<unsigned long long>(),
                                        (size_t)n_pairs, 0, 64, st));
     BWAMS_HIP(hipMemcpyAsync(keys->data(), s->pe_keys2.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));

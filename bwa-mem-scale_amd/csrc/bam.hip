@@ -349,11 +349,10 @@ int bam_names_index(bwams_index *ix, const char *names, const int32_t *name_off,
     std::sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return strcmp(names + name_off[a], names + name_off[b]) < 0; });
     bool dup = false;
     for (int32_t i = 1; i < n; ++i) dup |= strcmp(names + name_off[perm[(size_t)i - 1]], names + name_off[perm[(size_t)i]]) == 0;
-    if (ix->d_ctg_sorted) (void)hipFree(ix->d_ctg_sorted);
-    ix->d_ctg_sorted = nullptr;
+    ix->d_ctg_sorted.release();
     ix->h_ctg_names.clear();
-    BWAMS_HIP(dev_malloc(&ix->d_ctg_sorted, (size_t)n * 4));
-    BWAMS_HIP(hipMemcpy(ix->d_ctg_sorted, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    BWAMS_HIP(ix->d_ctg_sorted.alloc((size_t)n * 4));
+    BWAMS_HIP(hipMemcpy(ix->d_ctg_sorted.p, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     for (int32_t i = 0; i < n; ++i) ix->h_ctg_names.emplace_back(names + name_off[i]);
     ix->ctg_dup = dup;
     return BWAMS_OK;
@@ -367,13 +366,13 @@ namespace {
 
 // the index's sequences as the header needs them: names (host copy), lengths and is_alt (from the device table)
 int header_seqs(const bwams_index_t *idx, const char *who, std::vector<bwams_contig_t> *c) {
-    if (!idx || !idx->d_contigs || (int64_t)idx->h_ctg_names.size() != idx->n_seqs) {
+    if (!idx || !idx->d_contigs.p || (int64_t)idx->h_ctg_names.size() != idx->n_seqs) {
         set_last_error(std::string(who) + ": the index has no sequence names (bwams_index_set_contig_names)");
         return BWAMS_ERR_ARG;
     }
     c->resize((size_t)idx->n_seqs);
     BWAMS_HIP(hipSetDevice(idx->device));
-    BWAMS_HIP(hipMemcpy(c->data(), idx->d_contigs, c->size() * sizeof(bwams_contig_t), hipMemcpyDeviceToHost));
+    BWAMS_HIP(hipMemcpy(c->data(), idx->d_contigs.p, c->size() * sizeof(bwams_contig_t), hipMemcpyDeviceToHost));
     return BWAMS_OK;
 }
 

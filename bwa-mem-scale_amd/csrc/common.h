@@ -51,6 +51,37 @@ template <class T> static inline hipError_t dev_malloc(T **p, size_t bytes) {
     return e;
 }
 
+// The one owner of a block of device memory (through dev_malloc) or, Host = true, of pinned host memory: move-only, freed by its
+// destructor.  alloc() frees and allocates exactly `bytes`; ensure() reallocates only to grow, to `new_cap` bytes or by default to
+// `bytes + bytes/8 + 4096`; cap is in bytes.  Growing does not synchronise: a caller whose stream may still read the old block does.
+template <class T = void, bool Host = false> struct Buf {
+    T *p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~Buf() { release(); }
+    template <class U> U *as() const { return reinterpret_cast<U *>(p); }
+    void release() {
+        if (p) (void)(Host ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    hipError_t alloc(size_t bytes) {
+        release();
+        hipError_t e = Host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : dev_malloc(&p, bytes);
+        cap = p ? bytes : 0;
+        return e;
+    }
+    hipError_t ensure(size_t bytes, size_t new_cap) { return bytes <= cap ? hipSuccess : alloc(new_cap); }
+    hipError_t ensure(size_t bytes) { return ensure(bytes, bytes + bytes / 8 + 4096); }
+};
+template <class T = void> using DevBuf = Buf<T, false>;
+template <class T = void> using HostBuf = Buf<T, true>;
+
 #define BWAMS_HIP(call)                                                                  \
     do {                                                                                 \
         hipError_t e_ = (call);                                                          \
@@ -204,9 +235,9 @@ int launch_ksw(const bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, cons
 // read input helpers shared with the outer boundary (fastq.hip)
 struct SegMove { const char *src; char *dst; int64_t len; };     // one contiguous piece of device memory to copy
 int segment_copy(const std::vector<SegMove> &moves, hipStream_t st);
-// positions of the '\n' bytes of d_text[0, n_bytes) in HBM (rocPRIM select over a counting iterator, sized by a count first);
-// *ends (n_nl + 16 slots) is the caller's to free
-int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, int64_t **ends, int64_t *n_nl);
+// positions of the '\n' bytes of d_text[0, n_bytes) in HBM (rocPRIM select over a counting iterator, sized by a count first),
+// into *ends (allocated here: n_nl + 16 slots)
+int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, DevBuf<int64_t> *ends, int64_t *n_nl);
 
 // The reference metadata of an index made from FASTA (fasta_ref.hip): what bns_fasta2bntseq keeps and bns_dump writes.
 struct BnsMeta {
@@ -217,7 +248,7 @@ struct BnsMeta {
     std::vector<int64_t> hole_off;                       // bntamb1_t: offset, len, amb
     std::vector<int32_t> hole_len;
     std::vector<char> hole_amb;
-    void *d_pac = nullptr;                               // the 2-bit .pac, ceil(l_pac / 4) bytes in HBM (owned)
+    DevBuf<> d_pac;                                      // the 2-bit .pac, ceil(l_pac / 4) bytes in HBM
 };
 }  // namespace bwams
 struct bwams_fastq;
@@ -229,47 +260,40 @@ int fastq_interleave(bwams_fastq *f1, bwams_fastq *f2, bwams_fastq **out);      
 
 struct bwams_index {
     int device = 0;
-    bwams::DevFmi fmi{};
-    bool owns = true;
+    bwams::DevFmi fmi{};                         // points at d_cp .. d_ref, or at the caller's memory (bwams_index_from_device: they stay empty)
     int64_t bytes = 0;
     int64_t n_blk = 0, n_sa = 0;
-    void *d_cp = nullptr, *d_ms = nullptr, *d_ls = nullptr, *d_ref = nullptr;
-    void *d_cp2 = nullptr;                       // the search kernels' table derived from d_cp at the first FM-index seeding (always owned);
+    bwams::DevBuf<> d_cp, d_ms, d_ls, d_ref;
+    bwams::DevBuf<> d_cp2;                       // the search kernels' table derived from the CP_OCC array at the first FM-index seeding;
     std::mutex cp2_mu;                           // ... published under this lock once built, freed only by bwams_index_close
-    void *d_all = nullptr, *d_last = nullptr;    // FMA tables (owned)
-    void *d_contigs = nullptr;                   // bwams_contig_t[n_seqs] (owned); null = one sequence [0, l_pac)
+    bwams::DevBuf<> d_all, d_last;               // FMA tables
+    bwams::DevBuf<> d_contigs;                   // bwams_contig_t[n_seqs]; empty = one sequence [0, l_pac)
     int32_t n_seqs = 0;
-    void *d_ctg_annos = nullptr, *d_ctg_anno_off = nullptr;   // bntann1_t.anno for MEM_F_REF_HDR (bwams_index_set_contig_annos)
-    void *d_ctg_names = nullptr, *d_ctg_off = nullptr;   // sequence names for the SAM text (bwams_index_set_contig_names)
+    bwams::DevBuf<> d_ctg_annos, d_ctg_anno_off;   // bntann1_t.anno for MEM_F_REF_HDR (bwams_index_set_contig_annos)
+    bwams::DevBuf<> d_ctg_names, d_ctg_off;      // sequence names for the SAM text (bwams_index_set_contig_names)
     bwams::BnsMeta *bns = nullptr;               // .ann / .amb / .pac of an index made from FASTA (bwams_index_from_fasta), else null
     std::vector<std::string> h_ctg_names;        // host copy of the sequence names (the SAM / BAM headers)
-    void *d_ctg_sorted = nullptr;                // int32 permutation of the names in strcmp order: the BAM encoder's RNAME lookup
+    bwams::DevBuf<> d_ctg_sorted;                // int32 permutation of the names in strcmp order: the BAM encoder's RNAME lookup
     bool ctg_dup = false;                        // two sequences share a name (the BAM entry points refuse the index)
 };
 
 namespace bwams {
 int bns_save(bwams_index *ix, const char *prefix);     // fasta_ref.hip: writes <prefix>.ann, .amb, .pac
-void bns_free(bwams_index *ix);
 int bam_names_index(bwams_index *ix, const char *names, const int32_t *name_off, int32_t n);   // bam.hip, from set_contig_names
-}
-
-namespace bwams {
-int bsw_list_ensure(bwams_batch *b, int64_t n_tasks);   // grows b->d_bsw_list (synchronises the stream when it must reallocate)
 }
 
 struct bwams_ert {
     bwams_index *idx = nullptr;
     bwams::DevErt t{};
-    void *d_kmer = nullptr, *d_mlt = nullptr, *d_cnt = nullptr, *d_fat = nullptr;
+    bwams::DevBuf<> d_kmer, d_mlt, d_cnt, d_fat;
     int64_t bytes = 0, mlt_bytes = 0, n_big = 0;
     float build_ms[3] = {0, 0, 0};       // bwams_ert_build: sizes, scan + allocation, bytes
 };
 
 struct bwams_emf {
     bwams_index *idx = nullptr;
-    bwams::DevEmf t{};
-    bool owns = true;
-    void *d_seeds = nullptr, *d_loc = nullptr;
+    bwams::DevEmf t{};                   // points at d_seeds / d_loc, or at the caller's table (bwams_emf_from_device: they stay empty)
+    bwams::DevBuf<> d_seeds, d_loc;
     int64_t bytes = 0;
     int64_t n_used = 0, n_key = 0, n_other = 0, build_ms = 0;     // bwams_emf_build: distinct L-mers, buckets used, nodes outside their bucket
 };
@@ -280,6 +304,7 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
 }
 
 struct bwams_batch {
+    template <class T = void> using DevBuf = bwams::DevBuf<T>;
     bwams_index *idx = nullptr;
     hipStream_t stream = nullptr;
     hipStream_t seed_aux = nullptr;      // SMEM round 3 runs beside round 2
@@ -289,33 +314,31 @@ struct bwams_batch {
     int cu_count = 0;
 
     // reads
-    uint8_t *d_enc = nullptr;
-    int64_t *d_cum = nullptr;
-    uint8_t *d_skip = nullptr;
+    DevBuf<uint8_t> d_enc;
+    DevBuf<int64_t> d_cum;
+    DevBuf<uint8_t> d_skip;
     bool has_skip = false;
     int64_t nseq = 0, nbases = 0;
     int max_read_len = 0;
-    uint32_t *d_packed = nullptr;        // packed reads (2-bit codes + N mask)
-    int64_t packed_cap = 0;              // words
+    DevBuf<uint32_t> d_packed;           // packed reads (2-bit codes + N mask)
     int read_w = 0, read_cw = 0;
 
     // seeding buffers
-    bwams_smem_t *d_pool = nullptr;      // unsorted SMEM pool (append order)
-    bwams_smem_t *d_sorted = nullptr;    // (rid, m, n) order
-    uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
-    uint32_t *d_vals = nullptr, *d_vals2 = nullptr;
-    bwams::Round2Work *d_work2 = nullptr;
-    int64_t *d_sa_off = nullptr;         // max_smem + 1
-    int64_t *d_sa_cnt = nullptr;         // max_smem + 1
-    int64_t *d_sa_coord = nullptr;
-    void *d_tmp = nullptr;               // rocPRIM temporary storage
-    size_t tmp_bytes = 0;
-    bwams::DevCounters *d_ctr = nullptr;
-    bwams::DevCounters *h_ctr = nullptr;  // pinned host mirror
+    DevBuf<bwams_smem_t> d_pool;         // unsorted SMEM pool (append order)
+    DevBuf<bwams_smem_t> d_sorted;       // (rid, m, n) order
+    DevBuf<uint64_t> d_keys, d_keys2;
+    DevBuf<uint32_t> d_vals, d_vals2;
+    DevBuf<bwams::Round2Work> d_work2;
+    DevBuf<int64_t> d_sa_off;            // max_smem + 1
+    DevBuf<int64_t> d_sa_cnt;            // max_smem + 1
+    DevBuf<int64_t> d_sa_coord;
+    DevBuf<> d_tmp;                      // rocPRIM temporary storage
+    DevBuf<bwams::DevCounters> d_ctr;
+    bwams::HostBuf<bwams::DevCounters> h_ctr;   // pinned host mirror
     // per-lane scratch of the SMEM search (previous-interval lists)
-    uint4 *d_prev = nullptr;
-    bwams::BwdItem *d_bwd_items = nullptr;      // SMEM search: backward phases with long interval lists (wave-per-pivot kernel)
-    uint4 *d_bwd_ent = nullptr;
+    DevBuf<uint4> d_prev;
+    DevBuf<bwams::BwdItem> d_bwd_items;  // SMEM search: backward phases with long interval lists (wave-per-pivot kernel)
+    DevBuf<uint4> d_bwd_ent;
     int64_t bwd_items_cap = 0, bwd_ent_cap = 0;
     int64_t prev_threads = 0;
     int prev_cap = 0;
@@ -324,26 +347,21 @@ struct bwams_batch {
     int64_t n_pool_slots = 0;            // SMEM pool slots the last seeding pass handed out (holes included)
     bool seed_done = false, with_sa = false;
     bwams_ert *seed_ert = nullptr;       // the last seed run went over this ERT (nullptr: FM-index)
-    uint8_t *d_ert_prof = nullptr;       // ERT seeding: match-length planes, (M + 1) x nbases bytes
-    int64_t cap_ert_prof = 0;
-    uint64_t *d_ert_stk = nullptr;       // ERT seeding: stacks of the leaf walks (ert_walk_threads x frames words)
+    DevBuf<uint8_t> d_ert_prof;          // ERT seeding: match-length planes, (M + 1) x nbases bytes
+    DevBuf<uint64_t> d_ert_stk;          // ERT seeding: stacks of the leaf walks (ert_walk_threads x frames words)
     int ert_stk_frames = 0;
-    uint32_t *d_ert_redo = nullptr;      // ERT seeding: seeds whose hits the rank descent could not list (bit per seed)
-    int64_t cap_ert_redo = 0;            // seeds it is sized for
+    DevBuf<uint32_t> d_ert_redo;         // ERT seeding: seeds whose hits the rank descent could not list (bit per seed)
     bwams_seed_opt_t last_seed_opt{};    // of the last bwams_seed_run (a grown SA buffer re-runs the lookup)
 
     // extension buffers
-    bwams_seqpair_t *d_pairs = nullptr;
-    uint8_t *d_ref = nullptr, *d_qer = nullptr;
-    int64_t cap_pairs = 0, cap_ref = 0, cap_qer = 0, n_pairs = 0;
+    DevBuf<bwams_seqpair_t> d_pairs;
+    DevBuf<uint8_t> d_ref, d_qer;
+    int64_t n_pairs = 0;
     int max_qlen = 0, max_tlen = 0;
-    uint32_t *d_emf_out = nullptr;
-    uint8_t *d_emf_code = nullptr;
-    int64_t cap_emf = 0;
-    void *d_ksw_out = nullptr;
-    int64_t cap_ksw = 0;
-    int32_t *d_bsw_list = nullptr;       // task lists of the banded-SW length classes (launch_bsw)
-    int64_t cap_bsw_list = 0;            // tasks it is sized for
+    DevBuf<uint32_t> d_emf_out;
+    DevBuf<uint8_t> d_emf_code;
+    DevBuf<> d_ksw_out;
+    DevBuf<int32_t> d_bsw_list;          // task lists of the banded-SW length classes (launch_bsw)
 
     bwams::ChainState *chain = nullptr;
 
@@ -352,3 +370,7 @@ struct bwams_batch {
     unsigned long long emf_nodes = 0, emf_cmp_bytes = 0;
     bwams_stats_t stats{};
 };
+
+namespace bwams {
+int tmp_reserve(bwams_batch *b, size_t &tb);   // grows b->d_tmp to tb bytes (the stream drained first) and sets tb to its size (api.hip)
+}

@@ -756,18 +756,17 @@ int launch_sort_test(const int64_t *k, const int32_t *s_, const int32_t *q, int 
     if (n < 0 || n > kTestN) return -1;
     SortRec *h = (SortRec *)malloc(sizeof(SortRec) * (size_t)(n + 1));
     for (int i = 0; i < n; ++i) { h[i].k = k[i]; h[i].s = s_[i]; h[i].q = q[i]; h[i].idx = i; h[i].pad_ = 0; }
-    SortRec *d_in = nullptr, *d_scr = nullptr;
-    int32_t *d_ord = nullptr;
     int rc = -1;
-    if (dev_malloc(&d_in, sizeof(SortRec) * (size_t)(n + 1)) == hipSuccess && dev_malloc(&d_ord, 4 * (size_t)(n + 1)) == hipSuccess &&
-        dev_malloc(&d_scr, sizeof(SortRec) * (size_t)(n + 1)) == hipSuccess &&
-        hipMemcpy(d_in, h, sizeof(SortRec) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
-        sort_test_kernel<<<1, 64>>>(d_in, n, by_score, mode, d_ord, d_scr);
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(order, d_ord, 4 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    {
+        DevBuf<SortRec> d_in, d_scr;
+        DevBuf<int32_t> d_ord;
+        if (d_in.alloc(sizeof(SortRec) * (size_t)(n + 1)) == hipSuccess && d_ord.alloc(4 * (size_t)(n + 1)) == hipSuccess &&
+            d_scr.alloc(sizeof(SortRec) * (size_t)(n + 1)) == hipSuccess &&
+            hipMemcpy(d_in.p, h, sizeof(SortRec) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
+            sort_test_kernel<<<1, 64>>>(d_in.p, n, by_score, mode, d_ord.p, d_scr.p);
+            if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(order, d_ord.p, 4 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+        }
     }
-    if (d_in) (void)hipFree(d_in);
-    if (d_scr) (void)hipFree(d_scr);
-    if (d_ord) (void)hipFree(d_ord);
     free(h);
     return rc;
 }

@@ -550,11 +550,12 @@ struct bwams_deflater {
     int grid = 0;                                     // workgroups (workspace slots)
     hipStream_t st = nullptr;
     hipEvent_t ev[4] = {}, after = nullptr;
-    uint8_t *d_in = nullptr, *d_out = nullptr;        // host input / host output staging
-    uint16_t *d_prev = nullptr;
-    uint32_t *d_match = nullptr, *d_slots = nullptr;
-    int32_t *d_size = nullptr;
-    int64_t *d_off = nullptr, *h_total = nullptr;     // h_total page-locked
+    bwams::DevBuf<uint8_t> d_in, d_out;               // host input / host output staging
+    bwams::DevBuf<uint16_t> d_prev;
+    bwams::DevBuf<uint32_t> d_match, d_slots;
+    bwams::DevBuf<int32_t> d_size;
+    bwams::DevBuf<int64_t> d_off;
+    bwams::HostBuf<int64_t> h_total;                  // page-locked
 };
 
 namespace bwams {
@@ -591,23 +592,23 @@ int deflater_run_after(bwams_deflater *d, hipStream_t after, const void *in, int
         const uint8_t *src = static_cast<const uint8_t *>(in) + a;
         BWAMS_HIP(hipEventRecord(d->ev[0], d->st));
         if (!in_on_device) {
-            BWAMS_HIP(hipMemcpyAsync(d->d_in, src, (size_t)len, hipMemcpyHostToDevice, d->st));
-            src = d->d_in;
+            BWAMS_HIP(hipMemcpyAsync(d->d_in.p, src, (size_t)len, hipMemcpyHostToDevice, d->st));
+            src = d->d_in.p;
         }
         BWAMS_HIP(hipEventRecord(d->ev[1], d->st));
-        hipLaunchKernelGGL(deflate_kernel, dim3((unsigned)std::min(nm, d->grid)), dim3(kNT), 0, d->st, src, len, nm, d->d_prev, d->d_match,
-                           d->d_slots, d->d_size);
+        hipLaunchKernelGGL(deflate_kernel, dim3((unsigned)std::min(nm, d->grid)), dim3(kNT), 0, d->st, src, len, nm, d->d_prev.p, d->d_match.p,
+                           d->d_slots.p, d->d_size.p);
         BWAMS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(deflate_scan, dim3(1), dim3(kNT), 0, d->st, d->d_size, nm, d->d_off);
+        hipLaunchKernelGGL(deflate_scan, dim3(1), dim3(kNT), 0, d->st, d->d_size.p, nm, d->d_off.p);
         BWAMS_HIP(hipGetLastError());
-        uint8_t *dst = out_on_device ? static_cast<uint8_t *>(out) + pos : d->d_out;
-        hipLaunchKernelGGL(deflate_copy, dim3((unsigned)nm), dim3(kNT), 0, d->st, d->d_slots, d->d_size, d->d_off, dst);
+        uint8_t *dst = out_on_device ? static_cast<uint8_t *>(out) + pos : d->d_out.p;
+        hipLaunchKernelGGL(deflate_copy, dim3((unsigned)nm), dim3(kNT), 0, d->st, d->d_slots.p, d->d_size.p, d->d_off.p, dst);
         BWAMS_HIP(hipGetLastError());
         BWAMS_HIP(hipEventRecord(d->ev[2], d->st));
-        BWAMS_HIP(hipMemcpyAsync(d->h_total, d->d_off + nm, sizeof(int64_t), hipMemcpyDeviceToHost, d->st));
+        BWAMS_HIP(hipMemcpyAsync(d->h_total.p, d->d_off.p + nm, sizeof(int64_t), hipMemcpyDeviceToHost, d->st));
         BWAMS_HIP(hipStreamSynchronize(d->st));
-        const int64_t got = *d->h_total;
-        if (!out_on_device) BWAMS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(out) + pos, d->d_out, (size_t)got, hipMemcpyDeviceToHost, d->st));
+        const int64_t got = *d->h_total.p;
+        if (!out_on_device) BWAMS_HIP(hipMemcpyAsync(static_cast<uint8_t *>(out) + pos, d->d_out.p, (size_t)got, hipMemcpyDeviceToHost, d->st));
         BWAMS_HIP(hipEventRecord(d->ev[3], d->st));
         BWAMS_HIP(hipEventSynchronize(d->ev[3]));
         float t;
@@ -653,14 +654,6 @@ int bwams_deflater_destroy(bwams_deflater_t *d) {
     if (d->st) (void)hipStreamSynchronize(d->st);
     for (auto e : d->ev) if (e) (void)hipEventDestroy(e);
     if (d->after) (void)hipEventDestroy(d->after);
-    if (d->d_in) (void)hipFree(d->d_in);
-    if (d->d_out) (void)hipFree(d->d_out);
-    if (d->d_prev) (void)hipFree(d->d_prev);
-    if (d->d_match) (void)hipFree(d->d_match);
-    if (d->d_slots) (void)hipFree(d->d_slots);
-    if (d->d_size) (void)hipFree(d->d_size);
-    if (d->d_off) (void)hipFree(d->d_off);
-    if (d->h_total) (void)hipHostFree(d->h_total);
     if (d->st) (void)hipStreamDestroy(d->st);
     delete d;
     return BWAMS_OK;
@@ -693,14 +686,14 @@ int bwams_deflater_create(int device, int64_t max_in_bytes, bwams_deflater_t **o
     for (auto &x : d->ev)
         if ((e = hipEventCreate(&x)) != hipSuccess) return fail(e);
     if ((e = hipEventCreateWithFlags(&d->after, hipEventDisableTiming)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_in, (size_t)step)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_out, (size_t)(step + 31 * d->per_launch))) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_prev, sizeof(uint16_t) * kBlock * (size_t)d->grid)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_match, sizeof(uint32_t) * kBlock * (size_t)d->grid)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_slots, (size_t)kSlot * (size_t)d->per_launch)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_size, sizeof(int32_t) * (size_t)d->per_launch)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&d->d_off, sizeof(int64_t) * (size_t)(d->per_launch + 1))) != hipSuccess) return fail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void **>(&d->h_total), sizeof(int64_t), hipHostMallocDefault)) != hipSuccess) return fail(e);
+    if ((e = d->d_in.alloc((size_t)step)) != hipSuccess) return fail(e);
+    if ((e = d->d_out.alloc((size_t)(step + 31 * d->per_launch))) != hipSuccess) return fail(e);
+    if ((e = d->d_prev.alloc(sizeof(uint16_t) * kBlock * (size_t)d->grid)) != hipSuccess) return fail(e);
+    if ((e = d->d_match.alloc(sizeof(uint32_t) * kBlock * (size_t)d->grid)) != hipSuccess) return fail(e);
+    if ((e = d->d_slots.alloc((size_t)kSlot * (size_t)d->per_launch)) != hipSuccess) return fail(e);
+    if ((e = d->d_size.alloc(sizeof(int32_t) * (size_t)d->per_launch)) != hipSuccess) return fail(e);
+    if ((e = d->d_off.alloc(sizeof(int64_t) * (size_t)(d->per_launch + 1))) != hipSuccess) return fail(e);
+    if ((e = d->h_total.alloc(sizeof(int64_t))) != hipSuccess) return fail(e);
     *out = d;
     return BWAMS_OK;
 }

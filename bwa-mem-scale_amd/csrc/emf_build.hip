@@ -413,60 +413,54 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
         set_last_error("emf_build: the table's 32-bit locations and slots hold references of fewer than 2^32 / slack bases");
         return BWAMS_ERR_UNSUPPORTED;
     }
-    void *d_k = nullptr, *d_k2 = nullptr, *d_v = nullptr, *d_v2 = nullptr, *d_tmp = nullptr, *d_used = nullptr, *d_free = nullptr, *d_ctr = nullptr,
-         *d_nsel = nullptr, *d_big = nullptr, *d_runs = nullptr, *d_ord = nullptr;
-    auto cleanup = [&]() {
-        for (void *p : {d_k, d_k2, d_v, d_v2, d_tmp, d_used, d_free, d_ctr, d_nsel, d_big, d_runs, d_ord})
-            if (p) (void)hipFree(p);
-    };
+    DevBuf<> d_k, d_k2, d_v, d_v2, d_tmp, d_used, d_free, d_ctr, d_nsel, d_big, d_runs, d_ord;     // freed when the build returns
 #define EMF_HIP(call)                                                       \
     do {                                                                    \
         hipError_t e_ = (call);                                             \
         if (e_ != hipSuccess) {                                             \
             set_last_error(std::string("emf_build: " #call " -> ") + hipGetErrorString(e_)); \
-            cleanup();                                                      \
             return e_ == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE; \
         }                                                                   \
     } while (0)
     const size_t n = (size_t)B.n_win;
     hipEvent_t e0, e1, e2, e3;
     EMF_HIP(hipEventCreate(&e0)); EMF_HIP(hipEventCreate(&e1)); EMF_HIP(hipEventCreate(&e2)); EMF_HIP(hipEventCreate(&e3));
-    EMF_HIP(dev_malloc(&d_k, n * 8)); EMF_HIP(dev_malloc(&d_k2, n * 8));
-    EMF_HIP(dev_malloc(&d_v, n * 4)); EMF_HIP(dev_malloc(&d_v2, n * 4));
-    EMF_HIP(dev_malloc(&d_ctr, 8 * 8));
-    EMF_HIP(hipMemsetAsync(d_ctr, 0, 8 * 8, st));
+    EMF_HIP(d_k.alloc(n * 8)); EMF_HIP(d_k2.alloc(n * 8));
+    EMF_HIP(d_v.alloc(n * 4)); EMF_HIP(d_v2.alloc(n * 4));
+    EMF_HIP(d_ctr.alloc(8 * 8));
+    EMF_HIP(hipMemsetAsync(d_ctr.p, 0, 8 * 8, st));
     const unsigned grid = (unsigned)std::min<int64_t>((int64_t)((n + 255) / 256), (int64_t)cu_count * 32);
     EMF_HIP(hipEventRecord(e0, st));
-    hipLaunchKernelGGL(emf_key_kernel, dim3(grid), dim3(256), 0, st, B, (uint64_t *)d_k, (uint32_t *)d_v);
+    hipLaunchKernelGGL(emf_key_kernel, dim3(grid), dim3(256), 0, st, B, (uint64_t *)d_k.p, (uint32_t *)d_v.p);
     EMF_HIP(hipGetLastError());
     {
-        rocprim::double_buffer<uint64_t> kb((uint64_t *)d_k, (uint64_t *)d_k2);
-        rocprim::double_buffer<uint32_t> vb((uint32_t *)d_v, (uint32_t *)d_v2);
+        rocprim::double_buffer<uint64_t> kb((uint64_t *)d_k.p, (uint64_t *)d_k2.p);
+        rocprim::double_buffer<uint32_t> vb((uint32_t *)d_v.p, (uint32_t *)d_v2.p);
         size_t tb = 0;
         EMF_HIP(rocprim::radix_sort_pairs(nullptr, tb, kb, vb, n, 0, 64, st));
-        EMF_HIP(dev_malloc(&d_tmp, tb ? tb : 8));
-        EMF_HIP(rocprim::radix_sort_pairs(d_tmp, tb, kb, vb, n, 0, 64, st));
+        EMF_HIP(d_tmp.alloc(tb ? tb : 8));
+        EMF_HIP(rocprim::radix_sort_pairs(d_tmp.p, tb, kb, vb, n, 0, 64, st));
         EMF_HIP(hipStreamSynchronize(st));
-        if (kb.current() != (uint64_t *)d_k) std::swap(d_k, d_k2);
-        if (vb.current() != (uint32_t *)d_v) std::swap(d_v, d_v2);
-        (void)hipFree(d_tmp); d_tmp = nullptr;
-        (void)hipFree(d_k2); d_k2 = nullptr;
-        (void)hipFree(d_v2); d_v2 = nullptr;
+        if (kb.current() != (uint64_t *)d_k.p) std::swap(d_k, d_k2);
+        if (vb.current() != (uint32_t *)d_v.p) std::swap(d_v, d_v2);
+        d_tmp.release();
+        d_k2.release();
+        d_v2.release();
     }
     EMF_HIP(hipEventRecord(e1, st));
     const size_t used_words = (size_t)((B.n_entry + 31) / 32);
-    EMF_HIP(dev_malloc(&d_used, used_words * 4 + 4));
-    EMF_HIP(hipMemsetAsync(d_used, 0, used_words * 4 + 4, st));
+    EMF_HIP(d_used.alloc(used_words * 4 + 4));
+    EMF_HIP(hipMemsetAsync(d_used.p, 0, used_words * 4 + 4, st));
     BucketArgs A;
     memset(&A, 0, sizeof A);
-    A.B = B; A.keys = (const uint64_t *)d_k; A.pos = (const uint32_t *)d_v; A.used = (uint32_t *)d_used;
-    A.ctr = (unsigned long long *)d_ctr;
-    EMF_HIP(dev_malloc(&d_big, kBigCap * sizeof(ulonglong2)));
-    A.big = (ulonglong2 *)d_big; A.big_cap = kBigCap;
+    A.B = B; A.keys = (const uint64_t *)d_k.p; A.pos = (const uint32_t *)d_v.p; A.used = (uint32_t *)d_used.p;
+    A.ctr = (unsigned long long *)d_ctr.p;
+    EMF_HIP(d_big.alloc(kBigCap * sizeof(ulonglong2)));
+    A.big = (ulonglong2 *)d_big.p; A.big_cap = kBigCap;
     hipLaunchKernelGGL(emf_bucket_kernel<1>, dim3(grid), dim3(256), 0, st, A);
     EMF_HIP(hipGetLastError());
     unsigned long long c[8];
-    EMF_HIP(hipMemcpyAsync(c, d_ctr, sizeof c, hipMemcpyDeviceToHost, st));
+    EMF_HIP(hipMemcpyAsync(c, d_ctr.p, sizeof c, hipMemcpyDeviceToHost, st));
     EMF_HIP(hipStreamSynchronize(st));
     // runs with more distinct L-mers than a lane keeps: sorted and counted by their own kernels
     const unsigned long long n_big = c[6];
@@ -475,20 +469,18 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
     if (n_big > kBigCap) {
         set_last_error("emf_build: " + std::to_string(n_big) + " hash buckets hold more than " + std::to_string(kMaxU) + " distinct L-mers (the builder lists " +
                        std::to_string(kBigCap) + " of them)");
-        cleanup();
         return BWAMS_ERR_UNSUPPORTED;
     }
     unsigned long long big_windows = 0;
     if (n_big) {
         std::vector<ulonglong2> lst(n_big);
-        EMF_HIP(hipMemcpy(lst.data(), d_big, n_big * sizeof(ulonglong2), hipMemcpyDeviceToHost));
+        EMF_HIP(hipMemcpy(lst.data(), d_big.p, n_big * sizeof(ulonglong2), hipMemcpyDeviceToHost));
         std::sort(lst.begin(), lst.end(), [](const ulonglong2 &a, const ulonglong2 &b) { return a.x < b.x; });
         std::vector<BigRun> runs(n_big);
         unsigned long long off = 0;
         for (size_t t = 0; t < n_big; ++t) {
             if (lst[t].y >= (1ull << 30)) {
                 set_last_error("emf_build: a hash bucket holds 2^30 windows or more");
-                cleanup();
                 return BWAMS_ERR_UNSUPPORTED;
             }
             unsigned int pad = 2;
@@ -497,38 +489,38 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
             off += pad;
             big_windows += lst[t].y;
         }
-        EMF_HIP(dev_malloc(&d_runs, n_big * sizeof(BigRun)));
-        EMF_HIP(dev_malloc(&d_ord, off * 4));
-        EMF_HIP(hipMemcpyAsync(d_runs, runs.data(), n_big * sizeof(BigRun), hipMemcpyHostToDevice, st));
-        G.A = A; G.runs = (const BigRun *)d_runs; G.ord = (uint32_t *)d_ord;
+        EMF_HIP(d_runs.alloc(n_big * sizeof(BigRun)));
+        EMF_HIP(d_ord.alloc(off * 4));
+        EMF_HIP(hipMemcpyAsync(d_runs.p, runs.data(), n_big * sizeof(BigRun), hipMemcpyHostToDevice, st));
+        G.A = A; G.runs = (const BigRun *)d_runs.p; G.ord = (uint32_t *)d_ord.p;
         hipLaunchKernelGGL(emf_big_sort_kernel, dim3((unsigned)n_big), dim3(256), 0, st, G);
         hipLaunchKernelGGL(emf_big_emit_kernel<1>, dim3((unsigned)n_big), dim3(64), 0, st, G);
         EMF_HIP(hipGetLastError());
-        EMF_HIP(hipMemcpyAsync(c, d_ctr, sizeof c, hipMemcpyDeviceToHost, st));
+        EMF_HIP(hipMemcpyAsync(c, d_ctr.p, sizeof c, hipMemcpyDeviceToHost, st));
         EMF_HIP(hipStreamSynchronize(st));                  // (runs[] stays alive until here)
     }
     const unsigned long long n_other = c[0], n_loc = c[1] + 1, n_used = c[2], n_key = c[3];
     // the free slots, ascending
     const size_t n_free = (size_t)(B.n_entry - n_key);
-    EMF_HIP(dev_malloc(&d_free, (n_free ? n_free : 1) * 4));
-    EMF_HIP(dev_malloc(&d_nsel, 8));
+    EMF_HIP(d_free.alloc((n_free ? n_free : 1) * 4));
+    EMF_HIP(d_nsel.alloc(8));
     {
         IsFree pred;
-        pred.used = (const uint32_t *)d_used;
+        pred.used = (const uint32_t *)d_used.p;
         rocprim::counting_iterator<uint32_t> it(0u);
         size_t tb = 0;
-        EMF_HIP(rocprim::select(nullptr, tb, it, (uint32_t *)d_free, (size_t *)d_nsel, (size_t)B.n_entry, pred, st));
-        EMF_HIP(dev_malloc(&d_tmp, tb ? tb : 8));
-        EMF_HIP(rocprim::select(d_tmp, tb, it, (uint32_t *)d_free, (size_t *)d_nsel, (size_t)B.n_entry, pred, st));
+        EMF_HIP(rocprim::select(nullptr, tb, it, (uint32_t *)d_free.p, (size_t *)d_nsel.p, (size_t)B.n_entry, pred, st));
+        EMF_HIP(d_tmp.alloc(tb ? tb : 8));
+        EMF_HIP(rocprim::select(d_tmp.p, tb, it, (uint32_t *)d_free.p, (size_t *)d_nsel.p, (size_t)B.n_entry, pred, st));
     }
     EMF_HIP(hipEventRecord(e2, st));
-    EMF_HIP(dev_malloc(&e->d_seeds, (size_t)B.n_entry * 16));
-    EMF_HIP(dev_malloc(&e->d_loc, (size_t)n_loc * 4));
-    EMF_HIP(hipMemsetAsync(e->d_loc, 0, (size_t)n_loc * 4, st));
-    hipLaunchKernelGGL(emf_fill_kernel, dim3((unsigned)cu_count * 32), dim3(256), 0, st, (uint4 *)e->d_seeds, B.n_entry);
+    EMF_HIP(e->d_seeds.alloc((size_t)B.n_entry * 16));
+    EMF_HIP(e->d_loc.alloc((size_t)n_loc * 4));
+    EMF_HIP(hipMemsetAsync(e->d_loc.p, 0, (size_t)n_loc * 4, st));
+    hipLaunchKernelGGL(emf_fill_kernel, dim3((unsigned)cu_count * 32), dim3(256), 0, st, (uint4 *)e->d_seeds.p, B.n_entry);
     const unsigned long long init[8] = {0, 1, 0, 0, 0, 0, 0, 0};        // loc_table[0] is unused
-    EMF_HIP(hipMemcpyAsync(d_ctr, init, sizeof init, hipMemcpyHostToDevice, st));
-    A.free_list = (const uint32_t *)d_free; A.seeds = (uint4 *)e->d_seeds; A.loc = (uint32_t *)e->d_loc;
+    EMF_HIP(hipMemcpyAsync(d_ctr.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    A.free_list = (const uint32_t *)d_free.p; A.seeds = (uint4 *)e->d_seeds.p; A.loc = (uint32_t *)e->d_loc.p;
     A.free_cap = n_free; A.loc_cap = n_loc;
     hipLaunchKernelGGL(emf_bucket_kernel<2>, dim3(grid), dim3(256), 0, st, A);
     if (n_big) {
@@ -537,11 +529,10 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
     }
     EMF_HIP(hipGetLastError());
     EMF_HIP(hipEventRecord(e3, st));
-    EMF_HIP(hipMemcpyAsync(c, d_ctr, sizeof c, hipMemcpyDeviceToHost, st));
+    EMF_HIP(hipMemcpyAsync(c, d_ctr.p, sizeof c, hipMemcpyDeviceToHost, st));
     EMF_HIP(hipStreamSynchronize(st));
     if (c[4] || c[5] != n_other || c[1] != n_loc) {
         set_last_error("emf_build: internal error, the two passes disagree");
-        cleanup();
         return BWAMS_ERR_DEVICE;
     }
     float ms1 = 0, ms2 = 0, ms3 = 0;
@@ -551,10 +542,9 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
                         "%llu location words, %llu buckets (%llu windows) beyond %d L-mers; keys + sort %.1f ms, count + free list %.1f ms, table %.1f ms\n",
                 seed_len, (unsigned long long)n, n_used, n_key, (unsigned long long)B.n_entry, n_other, n_loc, n_big, big_windows, kMaxU, ms1, ms2, ms3);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
-    cleanup();
 #undef EMF_HIP
-    e->t.seed_table = reinterpret_cast<const uint4 *>(e->d_seeds);
-    e->t.loc_table = reinterpret_cast<const uint32_t *>(e->d_loc);
+    e->t.seed_table = reinterpret_cast<const uint4 *>(e->d_seeds.p);
+    e->t.loc_table = reinterpret_cast<const uint32_t *>(e->d_loc.p);
     e->t.ref = ref;
     e->t.num_seed_entry = (uint32_t)B.n_entry;
     e->t.num_loc_entry = (uint32_t)n_loc;

@@ -427,78 +427,70 @@ int ert_build_device(bwams_ert *e, const DevFmi &f, int K, int X, int read_len, 
     if ((uint64_t)blocks * 256 > n_kmers) blocks = (int64_t)((n_kmers + 255) / 256);
     A.n_threads = blocks * 256;
     A.max_frames = read_len - K + 2;
-    void *d_meta = nullptr, *d_off = nullptr, *d_stk = nullptr, *d_err = nullptr, *d_tmp = nullptr;
-    auto cleanup = [&]() {
-        for (void *p : {d_meta, d_off, d_stk, d_err, d_tmp})
-            if (p) (void)hipFree(p);
-    };
+    DevBuf<> d_meta, d_off, d_stk, d_err, d_tmp;                          // freed when the build returns
 #define ERT_HIP(call)                                                       \
     do {                                                                    \
         hipError_t e_ = (call);                                             \
         if (e_ != hipSuccess) {                                             \
             set_last_error(std::string("ert_build: " #call " -> ") + hipGetErrorString(e_)); \
-            cleanup();                                                      \
             return e_ == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE; \
         }                                                                   \
     } while (0)
     hipEvent_t e0, e1, e2, e3;
     ERT_HIP(hipEventCreate(&e0)); ERT_HIP(hipEventCreate(&e1)); ERT_HIP(hipEventCreate(&e2)); ERT_HIP(hipEventCreate(&e3));
-    ERT_HIP(dev_malloc(&e->d_kmer, n_kmers * 8));
-    ERT_HIP(dev_malloc(&d_meta, n_kmers * 8));
-    ERT_HIP(dev_malloc(&d_off, n_kmers * 8));
-    ERT_HIP(dev_malloc(&d_stk, (size_t)A.n_threads * (size_t)A.max_frames * 40));
-    ERT_HIP(dev_malloc(&d_err, 32));
-    ERT_HIP(hipMemsetAsync(d_err, 0, 32, st));
-    A.kmer = (uint64_t *)e->d_kmer;
-    A.meta = (uint64_t *)d_meta;
-    A.off = (const uint64_t *)d_off;
+    ERT_HIP(e->d_kmer.alloc(n_kmers * 8));
+    ERT_HIP(d_meta.alloc(n_kmers * 8));
+    ERT_HIP(d_off.alloc(n_kmers * 8));
+    ERT_HIP(d_stk.alloc((size_t)A.n_threads * (size_t)A.max_frames * 40));
+    ERT_HIP(d_err.alloc(32));
+    ERT_HIP(hipMemsetAsync(d_err.p, 0, 32, st));
+    A.kmer = (uint64_t *)e->d_kmer.p;
+    A.meta = (uint64_t *)d_meta.p;
+    A.off = (const uint64_t *)d_off.p;
     A.mlt = nullptr;
-    A.stk = (uint64_t *)d_stk;
-    A.err = (unsigned long long *)d_err;
+    A.stk = (uint64_t *)d_stk.p;
+    A.err = (unsigned long long *)d_err.p;
     ERT_HIP(hipEventRecord(e0, st));
     hipLaunchKernelGGL(ert_size_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
     ERT_HIP(hipGetLastError());
     ERT_HIP(hipEventRecord(e1, st));
     {
-        auto in = rocprim::make_transform_iterator((const uint64_t *)d_meta, LowWord());
+        auto in = rocprim::make_transform_iterator((const uint64_t *)d_meta.p, LowWord());
         size_t tb = 0;
-        ERT_HIP(rocprim::exclusive_scan(nullptr, tb, in, (uint64_t *)d_off, (uint64_t)0, (size_t)n_kmers, rocprim::plus<uint64_t>(), st));
-        ERT_HIP(dev_malloc(&d_tmp, tb ? tb : 8));
-        ERT_HIP(rocprim::exclusive_scan(d_tmp, tb, in, (uint64_t *)d_off, (uint64_t)0, (size_t)n_kmers, rocprim::plus<uint64_t>(), st));
+        ERT_HIP(rocprim::exclusive_scan(nullptr, tb, in, (uint64_t *)d_off.p, (uint64_t)0, (size_t)n_kmers, rocprim::plus<uint64_t>(), st));
+        ERT_HIP(d_tmp.alloc(tb ? tb : 8));
+        ERT_HIP(rocprim::exclusive_scan(d_tmp.p, tb, in, (uint64_t *)d_off.p, (uint64_t)0, (size_t)n_kmers, rocprim::plus<uint64_t>(), st));
     }
     uint64_t last_off = 0, last_meta = 0;
     unsigned long long err[4] = {0, 0, 0, 0};
-    ERT_HIP(hipMemcpyAsync(&last_off, (uint64_t *)d_off + (n_kmers - 1), 8, hipMemcpyDeviceToHost, st));
-    ERT_HIP(hipMemcpyAsync(&last_meta, (uint64_t *)d_meta + (n_kmers - 1), 8, hipMemcpyDeviceToHost, st));
-    ERT_HIP(hipMemcpyAsync(err, d_err, 32, hipMemcpyDeviceToHost, st));
+    ERT_HIP(hipMemcpyAsync(&last_off, (uint64_t *)d_off.p + (n_kmers - 1), 8, hipMemcpyDeviceToHost, st));
+    ERT_HIP(hipMemcpyAsync(&last_meta, (uint64_t *)d_meta.p + (n_kmers - 1), 8, hipMemcpyDeviceToHost, st));
+    ERT_HIP(hipMemcpyAsync(err, d_err.p, 32, hipMemcpyDeviceToHost, st));
     ERT_HIP(hipStreamSynchronize(st));
     if (err[2]) {
         set_last_error("ert_build: " + std::to_string(err[2]) + " k-mer tree(s) hold a string of read_len bases that occurs 65536 times or more; the ERT format "
                        "counts the hits of such a leaf in 16 bits (src/ertindex.cpp:336-352), so this text has no ERT index");
-        cleanup();
         return BWAMS_ERR_UNSUPPORTED;
     }
     if (err[3]) {
         set_last_error("ert_build: the trees of " + std::to_string(err[3]) + " k-mer(s) reach 64 MiB; child pointers carry 26 bits of offset and the reference's "
                        "writer asserts every k-mer's bytes below 2^26 (src/ertindex.cpp:452, :607, :651), so this text has no ERT index with this k");
-        cleanup();
         return BWAMS_ERR_UNSUPPORTED;
     }
     if (err[0]) {
         set_last_error("ert_build: a radix tree is deeper than the read length allows (corrupt index?)");
-        cleanup();
         return BWAMS_ERR_UNSUPPORTED;
     }
     const int64_t mlt_bytes = (int64_t)(last_off + (last_meta & 0xffffffffull));
-    ERT_HIP(dev_malloc(&e->d_mlt, (size_t)mlt_bytes + 16));
-    ERT_HIP(hipMemsetAsync(e->d_mlt, 0, (size_t)mlt_bytes + 16, st));
-    A.mlt = (uint8_t *)e->d_mlt;
+    ERT_HIP(e->d_mlt.alloc((size_t)mlt_bytes + 16));
+    ERT_HIP(hipMemsetAsync(e->d_mlt.p, 0, (size_t)mlt_bytes + 16, st));
+    A.mlt = (uint8_t *)e->d_mlt.p;
     int bits = 10;
     while (((uint64_t)1 << bits) < 2 * err[1] + 16) bits++;
-    ERT_HIP(dev_malloc(&e->d_cnt, ((size_t)16) << bits));
-    ERT_HIP(hipMemsetAsync(e->d_cnt, 0, ((size_t)16) << bits, st));
+    ERT_HIP(e->d_cnt.alloc(((size_t)16) << bits));
+    ERT_HIP(hipMemsetAsync(e->d_cnt.p, 0, ((size_t)16) << bits, st));
     memset(&A.cnt, 0, sizeof A.cnt);
-    A.cnt.cnt_tab = (uint64_t *)e->d_cnt;
+    A.cnt.cnt_tab = (uint64_t *)e->d_cnt.p;
     A.cnt.cnt_bits = bits;
     ERT_HIP(hipEventRecord(e2, st));
     hipLaunchKernelGGL(ert_emit_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
@@ -513,14 +505,13 @@ int ert_build_device(bwams_ert *e, const DevFmi &f, int K, int X, int read_len, 
         fprintf(stderr, "[bwams] ert_build: %llu k-mers, trees %.3f GB, %llu nodes with 20+ hits (count table 2^%d); sizes %.1f ms, scan + alloc %.1f ms, bytes %.1f ms\n",
                 (unsigned long long)n_kmers, mlt_bytes / 1e9, err[1], bits, msB, msS, msC);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
-    cleanup();
 #undef ERT_HIP
-    e->t.kmer = (const uint64_t *)e->d_kmer;
-    e->t.mlt = (const uint8_t *)e->d_mlt;
+    e->t.kmer = (const uint64_t *)e->d_kmer.p;
+    e->t.mlt = (const uint8_t *)e->d_mlt.p;
     e->t.ref = f.ref;
     e->t.ref_len = f.ref_seq_len - 1;
     e->t.K = K; e->t.X = X; e->t.read_len = read_len;
-    e->t.cnt_tab = (uint64_t *)e->d_cnt;
+    e->t.cnt_tab = (uint64_t *)e->d_cnt.p;
     e->t.cnt_bits = bits;
     e->n_big = (int64_t)err[1];
     e->bytes = (int64_t)(n_kmers * 8) + mlt_bytes + 16 + ((int64_t)16 << bits);

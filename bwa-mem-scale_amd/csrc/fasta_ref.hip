@@ -248,28 +248,14 @@ __global__ __launch_bounds__(256) void fa_emit_kernel(const uint8_t *__restrict_
     *reinterpret_cast<uint32_t *>(pac + k * 4) = pk;
 }
 
-struct DevBuf {                                  // device temporaries of one call, freed on every way out
-    std::vector<void *> p;
-    template <class T> hipError_t get(T **q, size_t bytes) {
-        hipError_t e = dev_malloc(q, bytes);
-        if (e == hipSuccess) p.push_back(*q);
-        return e;
-    }
-    void drop(void *q) {
-        for (auto &r : p) if (r == q) { (void)hipFree(r); r = nullptr; }
-    }
-    ~DevBuf() { for (void *q : p) if (q) (void)hipFree(q); }
-};
-
-template <class In, class Out> hipError_t exscan(In in, Out out, size_t n, hipStream_t st, DevBuf &scr) {
+template <class In, class Out> hipError_t exscan(In in, Out out, size_t n, hipStream_t st) {
     using T = typename std::iterator_traits<Out>::value_type;
     size_t tb = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, (T)0, n, rocprim::plus<T>(), st);
-    void *tmp = nullptr;
-    if (e == hipSuccess) e = scr.get(&tmp, tb + 16);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, tb, in, out, (T)0, n, rocprim::plus<T>(), st);
+    DevBuf<> tmp;
+    if (e == hipSuccess) e = tmp.alloc(tb + 16);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.p, tb, in, out, (T)0, n, rocprim::plus<T>(), st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    scr.drop(tmp);
     return e;
 }
 
@@ -305,16 +291,22 @@ void cut_header(const char *h, int64_t len, std::string *name, std::string *comm
     }
 }
 
-// text already in HBM -> codes in HBM (returned in *d_fw, l_pac + 16 bytes) and the bns in *m (its .pac in HBM)
-int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *m, uint8_t **d_fw, int64_t *n_ambig) {
-    DevBuf scr;
-    *d_fw = nullptr;
+// text already in HBM -> codes in HBM (into *fw, l_pac + 16 bytes) and the bns in *m (its .pac in HBM)
+int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *m, DevBuf<uint8_t> *fw, int64_t *n_ambig) {
     if (n_bytes <= 0) {
         set_last_error("bwams_index_from_fasta: empty text");
         return BWAMS_ERR_ARG;
     }
-    unsigned long long *d_flag = nullptr;
-    BWAMS_HIP(scr.get(&d_flag, 64));
+    // the device temporaries of the pack, freed when it returns (the line tables once the bytes are placed)
+    DevBuf<unsigned long long> flag;
+    DevBuf<int64_t> ends, contrib, offs, hdrs, cnt, ctg, hole_b, hole_e;
+    DevBuf<uint8_t> kind, raw, hole_amb;
+    DevBuf<HeaderPos> hps;
+    DevBuf<char> hdr_bytes;
+    DevBuf<uint32_t> cnt16;
+    DevBuf<uint64_t> ra, rs, re;
+    BWAMS_HIP(flag.alloc(64));
+    unsigned long long *d_flag = flag.p;
     // where the first record begins
     uint8_t b0 = 0;
     BWAMS_HIP(hipMemcpy(&b0, d_text, 1, hipMemcpyDeviceToHost));
@@ -336,26 +328,26 @@ int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *
     const uint8_t *t = d_text + p0;
     const int64_t n = n_bytes - p0;
     // (1) lines
-    int64_t *d_ends = nullptr, n_nl = 0;
+    int64_t n_nl = 0;
     {
-        int rc = line_ends(reinterpret_cast<const char *>(t), n, st, &d_ends, &n_nl);
+        int rc = line_ends(reinterpret_cast<const char *>(t), n, st, &ends, &n_nl);
         if (rc) return rc;
-        scr.p.push_back(d_ends);
     }
+    const int64_t *d_ends = ends.p;
     uint8_t last = 0;
     BWAMS_HIP(hipMemcpy(&last, t + n - 1, 1, hipMemcpyDeviceToHost));
     const int64_t n_lines = n_nl + (last != '\n' ? 1 : 0);
     // (2) kinds and contributions, (3) base positions
-    int64_t *d_contrib = nullptr, *d_off = nullptr;
-    uint8_t *d_kind = nullptr;
-    BWAMS_HIP(scr.get(&d_contrib, (size_t)(n_lines + 1) * 8));
-    BWAMS_HIP(scr.get(&d_off, (size_t)(n_lines + 1) * 8));
-    BWAMS_HIP(scr.get(&d_kind, (size_t)n_lines + 16));
+    BWAMS_HIP(contrib.alloc((size_t)(n_lines + 1) * 8));
+    BWAMS_HIP(offs.alloc((size_t)(n_lines + 1) * 8));
+    BWAMS_HIP(kind.alloc((size_t)n_lines + 16));
+    int64_t *d_contrib = contrib.p, *d_off = offs.p;
+    uint8_t *d_kind = kind.p;
     BWAMS_HIP(hipMemsetAsync(d_flag, 0, 8, st));
     fa_line_kernel<<<(unsigned)((n_lines + 255) / 256), 256, 0, st>>>(t, n, d_ends, n_nl, n_lines, d_contrib, d_kind, d_flag);
     BWAMS_HIP(hipGetLastError());
     BWAMS_HIP(hipMemsetAsync(d_contrib + n_lines, 0, 8, st));
-    BWAMS_HIP(exscan(d_contrib, d_off, (size_t)n_lines + 1, st, scr));
+    BWAMS_HIP(exscan(d_contrib, d_off, (size_t)n_lines + 1, st));
     unsigned long long bad = 0;
     int64_t l_pac = 0;
     BWAMS_HIP(hipMemcpy(&bad, d_flag, 8, hipMemcpyDeviceToHost));
@@ -366,20 +358,19 @@ int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *
     }
     // headers: positions on the device, bytes to the host
     int64_t n_seqs = 0;
-    int64_t *d_hdr = nullptr, *d_cnt = nullptr;
-    BWAMS_HIP(scr.get(&d_cnt, 64));
+    BWAMS_HIP(cnt.alloc(64));
+    BWAMS_HIP(hdrs.alloc((size_t)n_lines * 8 + 16));
+    int64_t *d_hdr = hdrs.p, *d_cnt = cnt.p;
     {
         rocprim::counting_iterator<int64_t> it(0);
         IsHeader pred{d_kind};
         size_t tb = 0;
-        BWAMS_HIP(scr.get(&d_hdr, (size_t)n_lines * 8 + 16));
         BWAMS_HIP(rocprim::select(nullptr, tb, it, d_hdr, d_cnt, (size_t)n_lines, pred, st));
-        void *tmp = nullptr;
-        BWAMS_HIP(scr.get(&tmp, tb + 16));
-        BWAMS_HIP(rocprim::select(tmp, tb, it, d_hdr, d_cnt, (size_t)n_lines, pred, st));
+        DevBuf<> tmp;
+        BWAMS_HIP(tmp.alloc(tb + 16));
+        BWAMS_HIP(rocprim::select(tmp.p, tb, it, d_hdr, d_cnt, (size_t)n_lines, pred, st));
         BWAMS_HIP(hipMemcpyAsync(&n_seqs, d_cnt, 8, hipMemcpyDeviceToHost, st));
         BWAMS_HIP(hipStreamSynchronize(st));
-        scr.drop(tmp);
     }
     if (n_seqs > 0x7fffffffLL) {
         set_last_error("bwams_index_from_fasta: more than 2^31 - 1 sequences");
@@ -387,8 +378,8 @@ int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *
     }
     std::vector<HeaderPos> hp((size_t)n_seqs);
     {
-        HeaderPos *d_hp = nullptr;
-        BWAMS_HIP(scr.get(&d_hp, (size_t)n_seqs * sizeof(HeaderPos)));
+        BWAMS_HIP(hps.alloc((size_t)n_seqs * sizeof(HeaderPos)));
+        HeaderPos *d_hp = hps.p;
         fa_header_kernel<<<(unsigned)((n_seqs + 255) / 256), 256, 0, st>>>(d_hdr, n_seqs, d_ends, n_nl, n, d_off, d_hp);
         BWAMS_HIP(hipGetLastError());
         BWAMS_HIP(hipMemcpyAsync(hp.data(), d_hp, (size_t)n_seqs * sizeof(HeaderPos), hipMemcpyDeviceToHost, st));
@@ -400,8 +391,8 @@ int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *
     std::vector<int64_t> hoff((size_t)n_seqs + 1, 0);
     {
         for (int64_t i = 0; i < n_seqs; ++i) hoff[(size_t)i + 1] = hoff[(size_t)i] + (hp[(size_t)i].e - hp[(size_t)i].b);
-        char *d_hb = nullptr;
-        BWAMS_HIP(scr.get(&d_hb, (size_t)hoff[(size_t)n_seqs] + 16));
+        BWAMS_HIP(hdr_bytes.alloc((size_t)hoff[(size_t)n_seqs] + 16));
+        char *d_hb = hdr_bytes.p;
         std::vector<SegMove> mv;
         mv.reserve((size_t)n_seqs);
         for (int64_t i = 0; i < n_seqs; ++i)
@@ -433,33 +424,33 @@ int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *
         return BWAMS_ERR_ARG;
     }
     // (4) the kept bytes, at their base positions
-    uint8_t *d_raw = nullptr;
-    BWAMS_HIP(scr.get(&d_raw, (size_t)l_pac + 16));
+    BWAMS_HIP(raw.alloc((size_t)l_pac + 16));
+    const uint8_t *d_raw = raw.p;
     {
         const int64_t lanes = (n + 15) / 16;
-        fa_raw_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, st>>>(t, n, d_ends, n_nl, d_contrib, d_off, d_raw);
+        fa_raw_kernel<<<(unsigned)((lanes + 255) / 256), 256, 0, st>>>(t, n, d_ends, n_nl, d_contrib, d_off, raw.p);
         BWAMS_HIP(hipGetLastError());
         BWAMS_HIP(hipStreamSynchronize(st));
     }
-    scr.drop(d_ends); scr.drop(d_contrib); scr.drop(d_off); scr.drop(d_kind); scr.drop(d_hdr);
+    ends.release(); contrib.release(); offs.release(); kind.release(); hdrs.release();
     // (5) ambiguous bases and holes per 16 bases, three scans
-    int64_t *d_ctg = nullptr;
-    BWAMS_HIP(scr.get(&d_ctg, (size_t)n_seqs * 8 + 8));
-    BWAMS_HIP(hipMemcpy(d_ctg, m->ctg_off.data(), (size_t)n_seqs * 8, hipMemcpyHostToDevice));
+    BWAMS_HIP(ctg.alloc((size_t)n_seqs * 8 + 8));
+    const int64_t *d_ctg = ctg.p;
+    BWAMS_HIP(hipMemcpy(ctg.p, m->ctg_off.data(), (size_t)n_seqs * 8, hipMemcpyHostToDevice));
     const int64_t n16 = (l_pac + 15) / 16;
     const unsigned grid = (unsigned)((n16 + 255) / 256);
-    uint32_t *d_cnt16 = nullptr;
-    uint64_t *d_ra = nullptr, *d_rs = nullptr, *d_re = nullptr;
-    BWAMS_HIP(scr.get(&d_cnt16, (size_t)(n16 + 1) * 4));
-    BWAMS_HIP(scr.get(&d_ra, (size_t)(n16 + 1) * 8));
-    BWAMS_HIP(scr.get(&d_rs, (size_t)(n16 + 1) * 8));
-    BWAMS_HIP(scr.get(&d_re, (size_t)(n16 + 1) * 8));
+    BWAMS_HIP(cnt16.alloc((size_t)(n16 + 1) * 4));
+    BWAMS_HIP(ra.alloc((size_t)(n16 + 1) * 8));
+    BWAMS_HIP(rs.alloc((size_t)(n16 + 1) * 8));
+    BWAMS_HIP(re.alloc((size_t)(n16 + 1) * 8));
+    uint32_t *d_cnt16 = cnt16.p;
+    uint64_t *d_ra = ra.p, *d_rs = rs.p, *d_re = re.p;
     fa_count_kernel<<<grid, 256, 0, st>>>(d_raw, l_pac, d_ctg, n_seqs, d_cnt16);
     BWAMS_HIP(hipGetLastError());
     BWAMS_HIP(hipMemsetAsync(d_cnt16 + n16, 0, 4, st));
-    BWAMS_HIP(exscan(rocprim::make_transform_iterator(d_cnt16, CountField{0}), d_ra, (size_t)n16 + 1, st, scr));
-    BWAMS_HIP(exscan(rocprim::make_transform_iterator(d_cnt16, CountField{8}), d_rs, (size_t)n16 + 1, st, scr));
-    BWAMS_HIP(exscan(rocprim::make_transform_iterator(d_cnt16, CountField{16}), d_re, (size_t)n16 + 1, st, scr));
+    BWAMS_HIP(exscan(rocprim::make_transform_iterator(d_cnt16, CountField{0}), d_ra, (size_t)n16 + 1, st));
+    BWAMS_HIP(exscan(rocprim::make_transform_iterator(d_cnt16, CountField{8}), d_rs, (size_t)n16 + 1, st));
+    BWAMS_HIP(exscan(rocprim::make_transform_iterator(d_cnt16, CountField{16}), d_re, (size_t)n16 + 1, st));
     uint64_t tot[3] = {0, 0, 0};
     BWAMS_HIP(hipMemcpy(&tot[0], d_ra + n16, 8, hipMemcpyDeviceToHost));
     BWAMS_HIP(hipMemcpy(&tot[1], d_rs + n16, 8, hipMemcpyDeviceToHost));
@@ -471,16 +462,15 @@ int fasta_pack(const uint8_t *d_text, int64_t n_bytes, hipStream_t st, BnsMeta *
     }
     const int64_t n_holes = (int64_t)tot[1];
     // (6) codes, .pac, holes
-    uint8_t *d_pac = nullptr, *d_hamb = nullptr;
-    int64_t *d_hb = nullptr, *d_he = nullptr;
-    BWAMS_HIP(dev_malloc(d_fw, (size_t)n16 * 16 + 16));
-    BWAMS_HIP(dev_malloc(&d_pac, (size_t)n16 * 4 + 16));
-    m->d_pac = d_pac;
-    BWAMS_HIP(scr.get(&d_hb, (size_t)n_holes * 8 + 8));
-    BWAMS_HIP(scr.get(&d_he, (size_t)n_holes * 8 + 8));
-    BWAMS_HIP(scr.get(&d_hamb, (size_t)n_holes + 16));
-    fa_emit_kernel<<<grid, 256, 0, st>>>(d_raw, l_pac, d_ctg, n_seqs, d_cnt16, d_ra, d_rs, d_re, make_jump(), *d_fw, d_pac, d_hb, d_he,
-                                         d_hamb);
+    BWAMS_HIP(fw->alloc((size_t)n16 * 16 + 16));
+    BWAMS_HIP(m->d_pac.alloc((size_t)n16 * 4 + 16));
+    BWAMS_HIP(hole_b.alloc((size_t)n_holes * 8 + 8));
+    BWAMS_HIP(hole_e.alloc((size_t)n_holes * 8 + 8));
+    BWAMS_HIP(hole_amb.alloc((size_t)n_holes + 16));
+    int64_t *d_hb = hole_b.p, *d_he = hole_e.p;
+    uint8_t *d_hamb = hole_amb.p;
+    fa_emit_kernel<<<grid, 256, 0, st>>>(d_raw, l_pac, d_ctg, n_seqs, d_cnt16, d_ra, d_rs, d_re, make_jump(), fw->p, m->d_pac.as<uint8_t>(), d_hb,
+                                         d_he, d_hamb);
     BWAMS_HIP(hipGetLastError());
     std::vector<int64_t> hb((size_t)n_holes), he((size_t)n_holes);
     m->hole_amb.resize((size_t)n_holes);
@@ -510,10 +500,8 @@ int attach_contigs(bwams_index *ix, const std::vector<int64_t> &off, const std::
     std::vector<bwams_contig_t> c(n);
     for (size_t i = 0; i < n; ++i) { c[i].offset = off[i]; c[i].len = len[i]; c[i].is_alt = alt.empty() ? 0 : alt[i]; }
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (ix->d_contigs) (void)hipFree(ix->d_contigs);
-    ix->d_contigs = nullptr;
-    BWAMS_HIP(dev_malloc(&ix->d_contigs, n * sizeof(bwams_contig_t)));
-    BWAMS_HIP(hipMemcpy(ix->d_contigs, c.data(), n * sizeof(bwams_contig_t), hipMemcpyHostToDevice));
+    BWAMS_HIP(ix->d_contigs.alloc(n * sizeof(bwams_contig_t)));
+    BWAMS_HIP(hipMemcpy(ix->d_contigs.p, c.data(), n * sizeof(bwams_contig_t), hipMemcpyHostToDevice));
     ix->n_seqs = (int32_t)n;
     auto blob = [&](const std::vector<std::string> &s, std::string *b, std::vector<int32_t> *o) {
         o->assign(n + 1, 0);
@@ -530,13 +518,6 @@ int attach_contigs(bwams_index *ix, const std::vector<int64_t> &off, const std::
 }
 
 }  // namespace
-
-void bns_free(bwams_index *ix) {
-    if (!ix->bns) return;
-    if (ix->bns->d_pac) { (void)hipSetDevice(ix->device); (void)hipFree(ix->bns->d_pac); }
-    delete ix->bns;
-    ix->bns = nullptr;
-}
 
 // bns_dump's .ann and .amb, and the .pac of bns_fasta2bntseq (always l_pac/4 + 2 bytes, the last one l_pac % 4)
 int bns_save(bwams_index *ix, const char *prefix) {
@@ -577,7 +558,7 @@ int bns_save(bwams_index *ix, const char *prefix) {
             std::vector<uint8_t> slab(std::min(kSlab, body) + 2);
             for (size_t o = 0; o < body && !rc; o += kSlab) {
                 const size_t k = std::min(kSlab, body - o);
-                if (hipMemcpy(slab.data(), (const uint8_t *)m.d_pac + o, k, hipMemcpyDeviceToHost) != hipSuccess) rc = BWAMS_ERR_DEVICE;
+                if (hipMemcpy(slab.data(), m.d_pac.as<const uint8_t>() + o, k, hipMemcpyDeviceToHost) != hipSuccess) rc = BWAMS_ERR_DEVICE;
                 else if (fwrite(slab.data(), 1, k, f) != k) rc = BWAMS_ERR_IO;
             }
             uint8_t tail[2] = {0, (uint8_t)(m.l_pac % 4)};
@@ -618,34 +599,27 @@ static int from_fasta(int device, const char *text, int64_t n_bytes, int text_on
         ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
     } ev;
     for (auto &x : ev.e) BWAMS_HIP(hipEventCreate(&x));
-    void *d_own = nullptr;
+    DevBuf<uint8_t> own;
     BWAMS_HIP(hipEventRecord(ev.e[0], st));
     const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
     if (!text_on_device) {
-        BWAMS_HIP(dev_malloc(&d_own, (size_t)n_bytes + 16));
-        hipError_t e = hipMemcpy(d_own, text, (size_t)n_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d_own); BWAMS_HIP(e); }
-        d_text = reinterpret_cast<const uint8_t *>(d_own);
+        BWAMS_HIP(own.alloc((size_t)n_bytes + 16));
+        BWAMS_HIP(hipMemcpy(own.p, text, (size_t)n_bytes, hipMemcpyHostToDevice));
+        d_text = own.p;
     }
     BWAMS_HIP(hipEventRecord(ev.e[1], st));
     std::unique_ptr<BnsMeta> m(new BnsMeta());
-    uint8_t *d_fw = nullptr;
+    DevBuf<uint8_t> fw;
     int64_t n_ambig = 0;
-    int rc = fasta_pack(d_text, n_bytes, st, m.get(), &d_fw, &n_ambig);
-    if (d_own) (void)hipFree(d_own);                               // the text goes before suffix sorting starts
-    auto drop = [&]() {
-        if (d_fw) (void)hipFree(d_fw);
-        if (m->d_pac) (void)hipFree(m->d_pac);
-        m->d_pac = nullptr;
-    };
-    if (rc) { drop(); return rc; }
+    int rc = fasta_pack(d_text, n_bytes, st, m.get(), &fw, &n_ambig);
+    own.release();                                                 // the text goes before suffix sorting starts
+    if (rc) return rc;
     BWAMS_HIP(hipEventRecord(ev.e[2], st));
     bwams_index *ix = new bwams_index();
     ix->device = device;
-    rc = fmi_build_device(ix, d_fw, m->l_pac, keep_ref, chunk_rows, knobs().verbose != 0, &S.build);
-    (void)hipFree(d_fw);
-    d_fw = nullptr;
-    if (rc) { drop(); bwams_index_close(ix); return rc; }
+    rc = fmi_build_device(ix, fw.p, m->l_pac, keep_ref, chunk_rows, knobs().verbose != 0, &S.build);
+    fw.release();
+    if (rc) { bwams_index_close(ix); return rc; }
     BWAMS_HIP(hipEventRecord(ev.e[3], st));
     BWAMS_HIP(hipEventSynchronize(ev.e[3]));
     std::vector<std::string> annos(m->comments.size());
@@ -692,8 +666,8 @@ int bwams_index_from_fasta_file(const char *path, int device, int keep_ref, int6
     gzbuffer(fp, 1 << 20);
     // page-locked, grown by doubling (a gzip file's inflated size is not known up front)
     size_t cap = std::max<size_t>((size_t)sb.st_size + 16, (size_t)1 << 20), have = 0;
-    char *buf = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&buf), cap) != hipSuccess) {
+    HostBuf<char> buf;
+    if (buf.alloc(cap) != hipSuccess) {
         gzclose(fp);
         set_last_error("bwams_index_from_fasta_file: page-locked allocation failed");
         return BWAMS_ERR_NOMEM;
@@ -701,15 +675,14 @@ int bwams_index_from_fasta_file(const char *path, int device, int keep_ref, int6
     int rc = BWAMS_OK;
     for (;;) {
         if (have == cap) {
-            char *nb = nullptr;
-            if (hipHostMalloc(reinterpret_cast<void **>(&nb), cap * 2) != hipSuccess) { rc = BWAMS_ERR_NOMEM; break; }
-            memcpy(nb, buf, have);
-            (void)hipHostFree(buf);
-            buf = nb;
+            HostBuf<char> nb;
+            if (nb.alloc(cap * 2) != hipSuccess) { rc = BWAMS_ERR_NOMEM; break; }
+            memcpy(nb.p, buf.p, have);
+            buf = std::move(nb);
             cap *= 2;
         }
         const unsigned want = (unsigned)std::min<size_t>(cap - have, (size_t)1 << 30);
-        const int got = gzread(fp, buf + have, want);
+        const int got = gzread(fp, buf.p + have, want);
         if (got < 0) {
             int e_ = 0;
             set_last_error(std::string(path) + ": " + gzerror(fp, &e_));
@@ -725,8 +698,7 @@ int bwams_index_from_fasta_file(const char *path, int device, int keep_ref, int6
         rc = BWAMS_ERR_ARG;
     }
     const float ms_read = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (!rc) rc = from_fasta(device, buf, (int64_t)have, 0, keep_ref, chunk_rows, ms_read, stats, out);
-    (void)hipHostFree(buf);
+    if (!rc) rc = from_fasta(device, buf.p, (int64_t)have, 0, keep_ref, chunk_rows, ms_read, stats, out);
     return rc;
 }
 

@@ -30,17 +30,14 @@
 struct bwams_fastq {
     int device = 0;
     int64_t n_reads = 0, n_bases = 0, name_bytes = 0, comment_bytes = 0;
-    void *d_enc = nullptr, *d_qual = nullptr, *d_names = nullptr, *d_comments = nullptr;
+    bwams::DevBuf<uint8_t> d_enc;
+    bwams::DevBuf<char> d_qual, d_names, d_comments;
     std::vector<int64_t> cum, name_off, comment_off;       // host copies of the three offset arrays
     float ms = 0;
     bool has_qual = true;                                  // false: FASTA text
     // a decode that fails half way (an allocation, a kernel) drops the handle: whatever it had allocated goes with it
     ~bwams_fastq() {
-        if (d_enc || d_qual || d_names || d_comments) (void)hipSetDevice(device);
-        if (d_enc) (void)hipFree(d_enc);
-        if (d_qual) (void)hipFree(d_qual);
-        if (d_names) (void)hipFree(d_names);
-        if (d_comments) (void)hipFree(d_comments);
+        if (d_enc.p || d_qual.p || d_names.p || d_comments.p) (void)hipSetDevice(device);
     }
 };
 
@@ -404,51 +401,40 @@ __global__ __launch_bounds__(256) void fq_wrapped_emit_kernel(const char *__rest
 using namespace bwams;
 
 namespace bwams {
-int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, int64_t **ends, int64_t *n_nl) {
-    *ends = nullptr;
+int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, DevBuf<int64_t> *ends, int64_t *n_nl) {
     *n_nl = 0;
     if (n_bytes <= 0) return BWAMS_OK;
-    int64_t *d_ends = nullptr, *d_cnt = nullptr;
-    void *d_tmp = nullptr;
-    struct Free {
-        void **p[2];
-        ~Free() { for (auto q : p) if (*q) (void)hipFree(*q); }
-    } fr{{reinterpret_cast<void **>(&d_cnt), &d_tmp}};
-    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_cnt), 64));
+    DevBuf<int64_t> cnt;
+    DevBuf<> tmp;
+    BWAMS_HIP(cnt.alloc(64));
     // count first: the array of line ends is sized exactly
-    BWAMS_HIP(hipMemsetAsync(d_cnt, 0, 8, st));
-    fastq_count_kernel<<<256 * 8, 256, 0, st>>>(d_text, n_bytes, reinterpret_cast<unsigned long long *>(d_cnt));
+    BWAMS_HIP(hipMemsetAsync(cnt.p, 0, 8, st));
+    fastq_count_kernel<<<256 * 8, 256, 0, st>>>(d_text, n_bytes, cnt.as<unsigned long long>());
     int64_t n = 0;
-    BWAMS_HIP(hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(&n, cnt.p, 8, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     size_t tb = 0;
     rocprim::counting_iterator<int64_t> it(0);
     IsLineEnd pred{d_text};
-    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_ends), (size_t)(n + 16) * 8));
-    hipError_t e = rocprim::select(nullptr, tb, it, d_ends, d_cnt, (size_t)n_bytes, pred, st);
-    if (e == hipSuccess) e = dev_malloc(&d_tmp, tb + 16);
-    if (e == hipSuccess) e = rocprim::select(d_tmp, tb, it, d_ends, d_cnt, (size_t)n_bytes, pred, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(d_ends); BWAMS_HIP(e); }
-    *ends = d_ends;
+    BWAMS_HIP(ends->alloc((size_t)(n + 16) * 8));
+    BWAMS_HIP(rocprim::select(nullptr, tb, it, ends->p, cnt.p, (size_t)n_bytes, pred, st));
+    BWAMS_HIP(tmp.alloc(tb + 16));
+    BWAMS_HIP(rocprim::select(tmp.p, tb, it, ends->p, cnt.p, (size_t)n_bytes, pred, st));
+    BWAMS_HIP(hipMemcpyAsync(&n, cnt.p, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
     *n_nl = n;
     return BWAMS_OK;
 }
 
 int segment_copy(const std::vector<SegMove> &moves, hipStream_t st) {
     if (moves.empty()) return BWAMS_OK;
-    SegMove *d = nullptr;
-    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d), moves.size() * sizeof(SegMove)));
-    hipError_t e = hipMemcpyAsync(d, moves.data(), moves.size() * sizeof(SegMove), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        int64_t blocks = ((int64_t)moves.size() + 3) / 4;
-        if (blocks > 256 * 64) blocks = 256 * 64;
-        segment_copy_kernel<<<(unsigned)blocks, 256, 0, st>>>(d, (int64_t)moves.size());
-        e = hipStreamSynchronize(st);
-    }
-    (void)hipFree(d);
-    BWAMS_HIP(e);
+    DevBuf<SegMove> d;
+    BWAMS_HIP(d.alloc(moves.size() * sizeof(SegMove)));
+    BWAMS_HIP(hipMemcpyAsync(d.p, moves.data(), moves.size() * sizeof(SegMove), hipMemcpyHostToDevice, st));
+    int64_t blocks = ((int64_t)moves.size() + 3) / 4;
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    segment_copy_kernel<<<(unsigned)blocks, 256, 0, st>>>(d.p, (int64_t)moves.size());
+    BWAMS_HIP(hipStreamSynchronize(st));
     return BWAMS_OK;
 }
 
@@ -459,18 +445,16 @@ int fastq_classify(bwams_fastq *f, std::vector<uint8_t> *which) {
     which->assign((size_t)n, 0);
     if (n == 0) return BWAMS_OK;
     BWAMS_HIP(hipSetDevice(f->device));
-    uint8_t *d_eq = nullptr;
-    int64_t *d_off = nullptr;
-    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_eq), (size_t)n));
-    hipError_t e = dev_malloc(reinterpret_cast<void **>(&d_off), (size_t)(n + 1) * 8);
     std::vector<uint8_t> eq((size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(d_off, f->name_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        fastq_same_name_kernel<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(reinterpret_cast<const char *>(f->d_names), d_off, n, d_eq);
-        e = hipMemcpy(eq.data(), d_eq, (size_t)n, hipMemcpyDeviceToHost);
+    {
+        DevBuf<uint8_t> d_eq;
+        DevBuf<int64_t> d_off;
+        BWAMS_HIP(d_eq.alloc((size_t)n));
+        BWAMS_HIP(d_off.alloc((size_t)(n + 1) * 8));
+        BWAMS_HIP(hipMemcpy(d_off.p, f->name_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+        fastq_same_name_kernel<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(f->d_names.p, d_off.p, n, d_eq.p);
+        BWAMS_HIP(hipMemcpy(eq.data(), d_eq.p, (size_t)n, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d_eq); (void)hipFree(d_off);
-    BWAMS_HIP(e);
     int has_last = 1;                                    // the reference's loop, on the comparison results
     int64_t i;
     for (i = 1; i < n; ++i) {
@@ -497,22 +481,22 @@ int fastq_subset(bwams_fastq *f, const std::vector<int64_t> &ids, bwams_fastq **
     }
     g->n_reads = (int64_t)m; g->n_bases = g->cum[m]; g->name_bytes = g->name_off[m]; g->comment_bytes = g->comment_off[m];
     auto fail = [&](hipError_t e) { bwams_fastq *p = g.release(); bwams_fastq_close(p); return e; };
-    hipError_t e = dev_malloc(&g->d_enc, (size_t)g->n_bases + 64);
-    if (e == hipSuccess) e = dev_malloc(&g->d_qual, (size_t)g->n_bases + 64);
-    if (e == hipSuccess) e = dev_malloc(&g->d_names, (size_t)g->name_bytes + 64);
-    if (e == hipSuccess) e = dev_malloc(&g->d_comments, (size_t)g->comment_bytes + 64);
+    hipError_t e = g->d_enc.alloc((size_t)g->n_bases + 64);
+    if (e == hipSuccess) e = g->d_qual.alloc((size_t)g->n_bases + 64);
+    if (e == hipSuccess) e = g->d_names.alloc((size_t)g->name_bytes + 64);
+    if (e == hipSuccess) e = g->d_comments.alloc((size_t)g->comment_bytes + 64);
     if (e != hipSuccess) { BWAMS_HIP(fail(e)); }
     std::vector<SegMove> mv;
     mv.reserve(4 * m);
     for (size_t k = 0; k < m; ++k) {
         const size_t r = (size_t)ids[k];
-        const char *se = reinterpret_cast<const char *>(f->d_enc) + f->cum[r], *sq = reinterpret_cast<const char *>(f->d_qual) + f->cum[r];
-        mv.push_back({se, reinterpret_cast<char *>(g->d_enc) + g->cum[k], f->cum[r + 1] - f->cum[r]});
-        if (f->has_qual) mv.push_back({sq, reinterpret_cast<char *>(g->d_qual) + g->cum[k], f->cum[r + 1] - f->cum[r]});
-        mv.push_back({reinterpret_cast<const char *>(f->d_names) + f->name_off[r], reinterpret_cast<char *>(g->d_names) + g->name_off[k],
+        const char *se = f->d_enc.as<const char>() + f->cum[r], *sq = f->d_qual.p + f->cum[r];
+        mv.push_back({se, g->d_enc.as<char>() + g->cum[k], f->cum[r + 1] - f->cum[r]});
+        if (f->has_qual) mv.push_back({sq, g->d_qual.p + g->cum[k], f->cum[r + 1] - f->cum[r]});
+        mv.push_back({f->d_names.p + f->name_off[r], g->d_names.p + g->name_off[k],
                       f->name_off[r + 1] - f->name_off[r]});
         if (f->comment_off[r + 1] > f->comment_off[r])
-            mv.push_back({reinterpret_cast<const char *>(f->d_comments) + f->comment_off[r], reinterpret_cast<char *>(g->d_comments) + g->comment_off[k],
+            mv.push_back({f->d_comments.p + f->comment_off[r], g->d_comments.p + g->comment_off[k],
                           f->comment_off[r + 1] - f->comment_off[r]});
     }
     int rc = segment_copy(mv, nullptr);
@@ -539,10 +523,10 @@ int fastq_interleave(bwams_fastq *f1, bwams_fastq *f2, bwams_fastq **out) {
         g->comment_off[k + 1] = g->comment_off[k] + (f->comment_off[r + 1] - f->comment_off[r]);
     }
     g->n_reads = (int64_t)m; g->n_bases = g->cum[m]; g->name_bytes = g->name_off[m]; g->comment_bytes = g->comment_off[m];
-    hipError_t e = dev_malloc(&g->d_enc, (size_t)g->n_bases + 64);
-    if (e == hipSuccess) e = dev_malloc(&g->d_qual, (size_t)g->n_bases + 64);
-    if (e == hipSuccess) e = dev_malloc(&g->d_names, (size_t)g->name_bytes + 64);
-    if (e == hipSuccess) e = dev_malloc(&g->d_comments, (size_t)g->comment_bytes + 64);
+    hipError_t e = g->d_enc.alloc((size_t)g->n_bases + 64);
+    if (e == hipSuccess) e = g->d_qual.alloc((size_t)g->n_bases + 64);
+    if (e == hipSuccess) e = g->d_names.alloc((size_t)g->name_bytes + 64);
+    if (e == hipSuccess) e = g->d_comments.alloc((size_t)g->comment_bytes + 64);
     if (e != hipSuccess) { bwams_fastq_close(g.release()); BWAMS_HIP(e); }
     std::vector<SegMove> mv;
     mv.reserve(4 * m);
@@ -550,10 +534,10 @@ int fastq_interleave(bwams_fastq *f1, bwams_fastq *f2, bwams_fastq **out) {
         const bwams_fastq *f = src[k & 1];
         const size_t r = k >> 1;
         const int64_t ls = f->cum[r + 1] - f->cum[r], ln = f->name_off[r + 1] - f->name_off[r], lc = f->comment_off[r + 1] - f->comment_off[r];
-        mv.push_back({reinterpret_cast<const char *>(f->d_enc) + f->cum[r], reinterpret_cast<char *>(g->d_enc) + g->cum[k], ls});
-        if (f->has_qual) mv.push_back({reinterpret_cast<const char *>(f->d_qual) + f->cum[r], reinterpret_cast<char *>(g->d_qual) + g->cum[k], ls});
-        mv.push_back({reinterpret_cast<const char *>(f->d_names) + f->name_off[r], reinterpret_cast<char *>(g->d_names) + g->name_off[k], ln});
-        if (lc) mv.push_back({reinterpret_cast<const char *>(f->d_comments) + f->comment_off[r], reinterpret_cast<char *>(g->d_comments) + g->comment_off[k], lc});
+        mv.push_back({f->d_enc.as<const char>() + f->cum[r], g->d_enc.as<char>() + g->cum[k], ls});
+        if (f->has_qual) mv.push_back({f->d_qual.p + f->cum[r], g->d_qual.p + g->cum[k], ls});
+        mv.push_back({f->d_names.p + f->name_off[r], g->d_names.p + g->name_off[k], ln});
+        if (lc) mv.push_back({f->d_comments.p + f->comment_off[r], g->d_comments.p + g->comment_off[k], lc});
     }
     int rc = segment_copy(mv, nullptr);
     if (rc) { bwams_fastq_close(g.release()); return rc; }
@@ -582,50 +566,51 @@ int bwams_fastq_decode(int device, const char *text, int64_t n_bytes, bwams_fast
     hipPointerAttribute_t attr;
     const bool on_dev = hipPointerGetAttributes(&attr, text) == hipSuccess && attr.type == hipMemoryTypeDevice;
     (void)hipGetLastError();
-    void *d_own = nullptr;
+    // the device temporaries of the decode, all freed when it returns
+    DevBuf<char> own;                                      // the text, when it came from the host
+    DevBuf<int64_t> ends, cnt, hdr, up, fc;
+    DevBuf<unsigned long long> bad_flags;
+    DevBuf<> sel_tmp, scan_tmp[3];
+    DevBuf<Rec> recs[2];                                   // [1]: records over several lines, when the four-line attempt gave up on [0]
+    DevBuf<int64_t> wides[2], offss[2];
     if (on_dev) d_text = const_cast<char *>(text);
     else {
-        BWAMS_HIP(dev_malloc(&d_own, (size_t)n_bytes + 16));
-        d_text = reinterpret_cast<char *>(d_own);
+        BWAMS_HIP(own.alloc((size_t)n_bytes + 16));
+        d_text = own.p;
         if (n_bytes) BWAMS_HIP(hipMemcpy(d_text, text, (size_t)n_bytes, hipMemcpyHostToDevice));
     }
-    struct Scratch {
-        std::vector<void *> p;
-        ~Scratch() { for (void *q : p) if (q) (void)hipFree(q); }
-    } scr;
-    scr.p.push_back(d_own);
     BWAMS_HIP(hipEventRecord(e0, st));
     // (1) line ends
-    int64_t *d_ends = nullptr, *d_cnt = nullptr;
-    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_cnt), 64)); scr.p.push_back(d_cnt);
+    BWAMS_HIP(cnt.alloc(64));
+    int64_t *d_ends = nullptr, *d_cnt = cnt.p;
     int64_t n_nl = 0;
     char last = '\n';
     if (n_bytes) {
-        int rc = line_ends(d_text, n_bytes, st, &d_ends, &n_nl);
+        int rc = line_ends(d_text, n_bytes, st, &ends, &n_nl);
         if (rc) return rc;
-        scr.p.push_back(d_ends);
+        d_ends = ends.p;
         BWAMS_HIP(hipMemcpy(&last, d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost));
     }
     const int64_t n_lines = n_nl + (n_bytes && last != '\n' ? 1 : 0);
     char first = '@';
     if (n_bytes) BWAMS_HIP(hipMemcpy(&first, d_text, 1, hipMemcpyDeviceToHost));
     const bool fasta = n_bytes && first == '>';
-    unsigned long long *d_bad = nullptr;
-    BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_bad), 64)); scr.p.push_back(d_bad);
+    BWAMS_HIP(bad_flags.alloc(64));
+    unsigned long long *d_bad = bad_flags.p;
     BWAMS_HIP(hipMemsetAsync(d_bad, 0, 16, st));
     int64_t n = 0;
     int64_t *d_hdr = nullptr;
     if (fasta) {
         // the records: the lines that start with '>'; no line may start with '+' or '@'
         fasta_check_kernel<<<(unsigned)((n_lines + 255) / 256), 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n_lines, d_bad);
-        BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_hdr), (size_t)(n_lines + 16) * 8)); scr.p.push_back(d_hdr);
+        BWAMS_HIP(hdr.alloc((size_t)(n_lines + 16) * 8));
+        d_hdr = hdr.p;
         size_t tb = 0;
         rocprim::counting_iterator<int64_t> it(0);
         IsHeaderLine pred{d_text, d_ends, n_nl, n_bytes};
         BWAMS_HIP(rocprim::select(nullptr, tb, it, d_hdr, d_cnt, (size_t)n_lines, pred, st));
-        void *d_tmp = nullptr;
-        BWAMS_HIP(dev_malloc(&d_tmp, tb + 16)); scr.p.push_back(d_tmp);
-        BWAMS_HIP(rocprim::select(d_tmp, tb, it, d_hdr, d_cnt, (size_t)n_lines, pred, st));
+        BWAMS_HIP(sel_tmp.alloc(tb + 16));
+        BWAMS_HIP(rocprim::select(sel_tmp.p, tb, it, d_hdr, d_cnt, (size_t)n_lines, pred, st));
         unsigned long long bad0 = 0;
         BWAMS_HIP(hipMemcpyAsync(&n, d_cnt, 8, hipMemcpyDeviceToHost, st));
         BWAMS_HIP(hipMemcpyAsync(&bad0, d_bad, 8, hipMemcpyDeviceToHost, st));
@@ -642,14 +627,15 @@ int bwams_fastq_decode(int device, const char *text, int64_t n_bytes, bwams_fast
     // (2) measure + validate
     Rec *d_rec = nullptr;
     int64_t *d_wide = nullptr, *d_offs = nullptr;
-    auto alloc_records = [&]() -> hipError_t {
-        hipError_t e_ = dev_malloc(reinterpret_cast<void **>(&d_rec), (size_t)n1 * sizeof(Rec)); scr.p.push_back(d_rec);
-        if (e_ == hipSuccess) { e_ = dev_malloc(reinterpret_cast<void **>(&d_wide), (size_t)n1 * 3 * 8); scr.p.push_back(d_wide); }
-        if (e_ == hipSuccess) { e_ = dev_malloc(reinterpret_cast<void **>(&d_offs), (size_t)n1 * 3 * 8); scr.p.push_back(d_offs); }
+    auto alloc_records = [&](int k) -> hipError_t {
+        hipError_t e_ = recs[k].alloc((size_t)n1 * sizeof(Rec));
+        if (e_ == hipSuccess) e_ = wides[k].alloc((size_t)n1 * 3 * 8);
+        if (e_ == hipSuccess) e_ = offss[k].alloc((size_t)n1 * 3 * 8);
+        d_rec = recs[k].p; d_wide = wides[k].p; d_offs = offss[k].p;
         return e_;
     };
     if (!wrapped) {
-        BWAMS_HIP(alloc_records());
+        BWAMS_HIP(alloc_records(0));
         if (fasta) fasta_measure_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n_lines, d_hdr, n, d_rec, d_wide);
         else {
             fastq_measure_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n, d_rec, d_wide, d_bad);
@@ -669,33 +655,31 @@ int bwams_fastq_decode(int device, const char *text, int64_t n_bytes, bwams_fast
         while (((int64_t)1 << levels) <= n_lines) ++levels;
         if (levels > kFqLevels) levels = kFqLevels;
         const int64_t stride = n_lines + 2;
-        int64_t *d_up = nullptr, *d_fc = nullptr;
-        BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_up), (size_t)levels * (size_t)stride * 8)); scr.p.push_back(d_up);
-        BWAMS_HIP(dev_malloc(reinterpret_cast<void **>(&d_fc), 64)); scr.p.push_back(d_fc);
+        BWAMS_HIP(up.alloc((size_t)levels * (size_t)stride * 8));
+        BWAMS_HIP(fc.alloc(64));
+        int64_t *d_up = up.p, *d_fc = fc.p;
         const unsigned gb = (unsigned)((stride + 255) / 256);
         fq_succ_kernel<<<gb, 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n_lines, d_up);
         for (int k = 1; k < levels; ++k) fq_double_kernel<<<gb, 256, 0, st>>>(d_up + (int64_t)(k - 1) * stride, d_up + (int64_t)k * stride, stride);
         fq_count_kernel<<<1, 1, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n_lines, d_up, levels, d_fc);
-        int64_t fc[2] = {0, 0};
-        BWAMS_HIP(hipMemcpyAsync(fc, d_fc, 16, hipMemcpyDeviceToHost, st));
+        int64_t h_fc[2] = {0, 0};
+        BWAMS_HIP(hipMemcpyAsync(h_fc, d_fc, 16, hipMemcpyDeviceToHost, st));
         BWAMS_HIP(hipStreamSynchronize(st));
-        if (fc[1] < 0) {
+        if (h_fc[1] < 0) {
             set_last_error("bwams_fastq_decode: FASTQ text the device path does not take: text before the first '@' header or between records, a record "
                            "without a '+' line, or a quality string of another length than its sequence (read this input on the host)");
             return BWAMS_ERR_UNSUPPORTED;
         }
-        n = fc[1];
+        n = h_fc[1];
         n1 = n + 1;
-        if (d_rec) { d_rec = nullptr; d_wide = nullptr; d_offs = nullptr; }      // (the four-line attempt's arrays stay in scr until the end)
-        BWAMS_HIP(alloc_records());
-        fq_wrapped_measure_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n_lines, d_up, levels, fc[0], n, d_rec, d_wide, d_bad);
+        BWAMS_HIP(alloc_records(1));                      // (the four-line attempt's arrays stay until the end)
+        fq_wrapped_measure_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, n_lines, d_up, levels, h_fc[0], n, d_rec, d_wide, d_bad);
     }
     for (int row = 0; row < 3; ++row) {
         size_t tb = 0;
         BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, d_wide + row * n1, d_offs + row * n1, (int64_t)0, (size_t)n1, rocprim::plus<int64_t>(), st));
-        void *d_tmp = nullptr;
-        BWAMS_HIP(dev_malloc(&d_tmp, tb + 16)); scr.p.push_back(d_tmp);
-        BWAMS_HIP(rocprim::exclusive_scan(d_tmp, tb, d_wide + row * n1, d_offs + row * n1, (int64_t)0, (size_t)n1, rocprim::plus<int64_t>(), st));
+        BWAMS_HIP(scan_tmp[row].alloc(tb + 16));
+        BWAMS_HIP(rocprim::exclusive_scan(scan_tmp[row].p, tb, d_wide + row * n1, d_offs + row * n1, (int64_t)0, (size_t)n1, rocprim::plus<int64_t>(), st));
     }
     f->cum.resize((size_t)n1); f->name_off.resize((size_t)n1); f->comment_off.resize((size_t)n1);
     unsigned long long bad[2] = {0, 0};
@@ -711,24 +695,24 @@ int bwams_fastq_decode(int device, const char *text, int64_t n_bytes, bwams_fast
     f->has_qual = !fasta;
     f->n_reads = n; f->n_bases = f->cum[(size_t)n]; f->name_bytes = f->name_off[(size_t)n]; f->comment_bytes = f->comment_off[(size_t)n];
     // (3) emit
-    BWAMS_HIP(dev_malloc(&f->d_enc, (size_t)f->n_bases + 64));
-    BWAMS_HIP(dev_malloc(&f->d_qual, (size_t)f->n_bases + 64));
-    BWAMS_HIP(dev_malloc(&f->d_names, (size_t)f->name_bytes + 64));
-    BWAMS_HIP(dev_malloc(&f->d_comments, (size_t)f->comment_bytes + 64));
+    BWAMS_HIP(f->d_enc.alloc((size_t)f->n_bases + 64));
+    BWAMS_HIP(f->d_qual.alloc((size_t)f->n_bases + 64));
+    BWAMS_HIP(f->d_names.alloc((size_t)f->name_bytes + 64));
+    BWAMS_HIP(f->d_comments.alloc((size_t)f->comment_bytes + 64));
     if (n) {
         int64_t blocks = (n + 3) / 4;
         if (blocks > 256 * 64) blocks = 256 * 64;
         if (fasta)
-            fasta_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, d_rec, n, d_offs, reinterpret_cast<char *>(f->d_names),
-                                                                reinterpret_cast<char *>(f->d_comments), reinterpret_cast<uint8_t *>(f->d_enc), d_bad + 1);
+            fasta_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, d_rec, n, d_offs, f->d_names.p,
+                                                                f->d_comments.p, f->d_enc.p, d_bad + 1);
         else if (wrapped)
-            fq_wrapped_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, d_rec, n, d_offs, reinterpret_cast<char *>(f->d_names),
-                                                                     reinterpret_cast<char *>(f->d_comments), reinterpret_cast<uint8_t *>(f->d_enc),
-                                                                     reinterpret_cast<char *>(f->d_qual), d_bad + 1);
+            fq_wrapped_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d_text, n_bytes, d_ends, n_nl, d_rec, n, d_offs, f->d_names.p,
+                                                                     f->d_comments.p, f->d_enc.p,
+                                                                     f->d_qual.p, d_bad + 1);
         else
-            fastq_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d_text, d_rec, n, d_offs, reinterpret_cast<char *>(f->d_names),
-                                                                reinterpret_cast<char *>(f->d_comments), reinterpret_cast<uint8_t *>(f->d_enc),
-                                                                reinterpret_cast<char *>(f->d_qual), d_bad + 1);
+            fastq_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d_text, d_rec, n, d_offs, f->d_names.p,
+                                                                f->d_comments.p, f->d_enc.p,
+                                                                f->d_qual.p, d_bad + 1);
     }
     BWAMS_HIP(hipEventRecord(e1, st));
     BWAMS_HIP(hipMemcpyAsync(bad + 1, d_bad + 1, 8, hipMemcpyDeviceToHost, st));
@@ -762,10 +746,10 @@ int bwams_fastq_fetch(bwams_fastq_t *f, uint8_t *enc, int64_t *cum, char *names,
     if (!f) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(f->device));
     const size_t n1 = (size_t)f->n_reads + 1;
-    if (enc && f->n_bases) BWAMS_HIP(hipMemcpy(enc, f->d_enc, (size_t)f->n_bases, hipMemcpyDeviceToHost));
-    if (quals && f->n_bases && f->has_qual) BWAMS_HIP(hipMemcpy(quals, f->d_qual, (size_t)f->n_bases, hipMemcpyDeviceToHost));
-    if (names && f->name_bytes) BWAMS_HIP(hipMemcpy(names, f->d_names, (size_t)f->name_bytes, hipMemcpyDeviceToHost));
-    if (comments && f->comment_bytes) BWAMS_HIP(hipMemcpy(comments, f->d_comments, (size_t)f->comment_bytes, hipMemcpyDeviceToHost));
+    if (enc && f->n_bases) BWAMS_HIP(hipMemcpy(enc, f->d_enc.p, (size_t)f->n_bases, hipMemcpyDeviceToHost));
+    if (quals && f->n_bases && f->has_qual) BWAMS_HIP(hipMemcpy(quals, f->d_qual.p, (size_t)f->n_bases, hipMemcpyDeviceToHost));
+    if (names && f->name_bytes) BWAMS_HIP(hipMemcpy(names, f->d_names.p, (size_t)f->name_bytes, hipMemcpyDeviceToHost));
+    if (comments && f->comment_bytes) BWAMS_HIP(hipMemcpy(comments, f->d_comments.p, (size_t)f->comment_bytes, hipMemcpyDeviceToHost));
     if (cum) memcpy(cum, f->cum.data(), n1 * 8);
     if (name_off) memcpy(name_off, f->name_off.data(), n1 * 8);
     if (comment_off) memcpy(comment_off, f->comment_off.data(), n1 * 8);
@@ -774,12 +758,12 @@ int bwams_fastq_fetch(bwams_fastq_t *f, uint8_t *enc, int64_t *cum, char *names,
 
 int bwams_fastq_to_batch_opt(bwams_fastq_t *f, bwams_batch_t *b, int32_t copy_comment) {
     if (!f || !b) return BWAMS_ERR_ARG;
-    int rc = bwams_seed_upload(b, reinterpret_cast<const uint8_t *>(f->d_enc), f->cum.data(), nullptr, f->n_reads);
+    int rc = bwams_seed_upload(b, f->d_enc.p, f->cum.data(), nullptr, f->n_reads);
     if (rc) return rc;
     const bool cm = copy_comment && f->comment_bytes;
-    return bwams_sam_upload(b, reinterpret_cast<const char *>(f->d_names), f->name_off.data(),
-                            f->has_qual ? reinterpret_cast<const char *>(f->d_qual) : nullptr,
-                            cm ? reinterpret_cast<const char *>(f->d_comments) : nullptr, cm ? f->comment_off.data() : nullptr);
+    return bwams_sam_upload(b, f->d_names.p, f->name_off.data(),
+                            f->has_qual ? f->d_qual.p : nullptr,
+                            cm ? f->d_comments.p : nullptr, cm ? f->comment_off.data() : nullptr);
 }
 
 int bwams_fastq_to_batch(bwams_fastq_t *f, bwams_batch_t *b) { return bwams_fastq_to_batch_opt(f, b, 1); }

@@ -299,17 +299,6 @@ __global__ void sa_sample_kernel(const int64_t *__restrict__ sa, int64_t L, int6
     ls[t] = (uint32_t)(v & 0xffffffff);
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        return dev_malloc(&p, bytes ? bytes : 8);
-    }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; } }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // blocks of `per` threads covering n items; every caller keeps n below 2^32 (HIP's bound on the threads of one launch)
 inline unsigned int nblk(int64_t n, int per) { return (unsigned int)((n + per - 1) / per); }
 
@@ -338,7 +327,7 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
     BWAMS_HIP(hipEventRecord(e0, st));
 
     // ---- text: fw || rc, packed form, base counts
-    DevBuf ref, packed, small;
+    DevBuf<> ref, packed, small;
     BWAMS_HIP(ref.alloc((size_t)N + 64));
     const int64_t nwords = (N >> 5) + 3;
     BWAMS_HIP(packed.alloc((size_t)nwords * 8));
@@ -389,19 +378,18 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
         max_chunk = std::max(max_chunk, c);
     }
 
-    DevBuf sa, isa, bm;
+    DevBuf<> sa, isa, bm;
     const int64_t bm_words = (L >> 6) + 2;
     BWAMS_HIP(sa.alloc((size_t)L * 8));
     BWAMS_HIP(isa.alloc((size_t)(L + 1) * 8));
     BWAMS_HIP(bm.alloc((size_t)bm_words * 8));
     BWAMS_HIP(hipMemsetAsync(bm.p, 0, (size_t)bm_words * 8, st));
 
-    DevBuf k0, k1, v0, v1, tmp;
-    size_t tmp_bytes = 0;
-    auto need_tmp = [&](size_t b) -> hipError_t {
-        if (b <= tmp_bytes) return hipSuccess;
-        tmp_bytes = b + b / 8 + 256;
-        return tmp.alloc(tmp_bytes);
+    DevBuf<> k0, k1, v0, v1, tmp;
+    auto need_tmp = [&](size_t &b) -> hipError_t {         // rocPRIM scratch, grown as the passes need; b becomes its size
+        hipError_t e = tmp.ensure(b, b + b / 8 + 256);
+        b = tmp.cap;
+        return e;
     };
     {
         BWAMS_HIP(k0.alloc((size_t)max_chunk * 8));
@@ -423,7 +411,6 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
             // the chunk's keys differ from bit 0 (length field) up to the top of the bin field
             BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, dk, dv, (size_t)cnt, 0u, 64u, st));
             BWAMS_HIP(need_tmp(tb));
-            tb = tmp_bytes;
             BWAMS_HIP(rocprim::radix_sort_pairs(tmp.p, tb, dk, dv, (size_t)cnt, 0u, 64u, st));
             // rank of every element = row of its group's head: inclusive max-scan of the head rows, into the free key buffer
             int64_t *rank = reinterpret_cast<int64_t *>(dk.alternate());
@@ -431,7 +418,6 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
             tb = 0;
             BWAMS_HIP(rocprim::inclusive_scan(nullptr, tb, in, rank, (size_t)cnt, MaxOp(), st));
             BWAMS_HIP(need_tmp(tb));
-            tb = tmp_bytes;
             BWAMS_HIP(rocprim::inclusive_scan(tmp.p, tb, in, rank, (size_t)cnt, MaxOp(), st));
             hipLaunchKernelGGL(chunk_finish_kernel, dim3(nblk(cnt, kBlk)), dim3(kBlk), 0, st, dk.current(), dv.current(), rank, cnt, base,
                                sa.as<int64_t>(), isa.as<int64_t>(), bm.as<unsigned long long>());
@@ -452,7 +438,7 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
     BWAMS_HIP(hipEventElapsedTime(&ms_first, e0, e1));
 
     // ---- doubling rounds
-    DevBuf wcnt, woff, upos, gsum;
+    DevBuf<> wcnt, woff, upos, gsum;
     BWAMS_HIP(wcnt.alloc((size_t)bm_words * 8));
     BWAMS_HIP(woff.alloc((size_t)(bm_words + 1) * 8));
     int64_t cap_m = 0;
@@ -466,7 +452,6 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
         BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, wcnt.as<int64_t>(), woff.as<int64_t>(), (int64_t)0, (size_t)nw + 1,
                                           rocprim::plus<int64_t>(), st));
         BWAMS_HIP(need_tmp(tb));
-        tb = tmp_bytes;
         // (one element past the counts is read: wcnt has bm_words >= nw + 1 entries; its value does not matter)
         BWAMS_HIP(rocprim::exclusive_scan(tmp.p, tb, wcnt.as<int64_t>(), woff.as<int64_t>(), (int64_t)0, (size_t)nw + 1,
                                           rocprim::plus<int64_t>(), st));
@@ -500,7 +485,6 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
         tb = 0;
         BWAMS_HIP(rocprim::inclusive_scan(nullptr, tb, v1.as<int64_t>(), gsum.as<int64_t>(), (size_t)M, rocprim::plus<int64_t>(), st));
         BWAMS_HIP(need_tmp(tb));
-        tb = tmp_bytes;
         BWAMS_HIP(rocprim::inclusive_scan(tmp.p, tb, v1.as<int64_t>(), gsum.as<int64_t>(), (size_t)M, rocprim::plus<int64_t>(), st));
         int64_t n_groups = 0;
         BWAMS_HIP(hipMemcpyAsync(&n_groups, gsum.as<int64_t>() + (M - 1), 8, hipMemcpyDeviceToHost, st));
@@ -518,14 +502,12 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
         tb = 0;
         BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, dk, dv, (size_t)M, 0u, (unsigned)(rbits + gbits), st));
         BWAMS_HIP(need_tmp(tb));
-        tb = tmp_bytes;
         BWAMS_HIP(rocprim::radix_sort_pairs(tmp.p, tb, dk, dv, (size_t)M, 0u, (unsigned)(rbits + gbits), st));
         int64_t *rank = reinterpret_cast<int64_t *>(dk.alternate());
         auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0), RoundHeadPos{dk.current(), upos.as<int64_t>()});
         tb = 0;
         BWAMS_HIP(rocprim::inclusive_scan(nullptr, tb, in, rank, (size_t)M, MaxOp(), st));
         BWAMS_HIP(need_tmp(tb));
-        tb = tmp_bytes;
         BWAMS_HIP(rocprim::inclusive_scan(tmp.p, tb, in, rank, (size_t)M, MaxOp(), st));
         hipLaunchKernelGGL(round_finish_kernel, dim3(nblk(M, kBlk)), dim3(kBlk), 0, st, dk.current(), dv.current(), upos.as<int64_t>(), rank,
                            M, sa.as<int64_t>(), isa.as<int64_t>(), bm.as<unsigned long long>());
@@ -541,7 +523,7 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
 
     // ---- BWT -> CP_OCC, SA samples
     const int64_t n_blk = (L >> 6) + 1, filled = (L + 63) >> 6, n_sa = (L >> 3) + 1;
-    DevBuf cp, ms, ls, blkcnt;
+    DevBuf<> cp, ms, ls, blkcnt;
     BWAMS_HIP(cp.alloc((size_t)n_blk * 64));
     BWAMS_HIP(ms.alloc((size_t)n_sa));
     BWAMS_HIP(ls.alloc((size_t)n_sa * 4));
@@ -554,7 +536,6 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
         Cnt4 zero{{0, 0, 0, 0}};
         BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, blkcnt.as<Cnt4>(), blkcnt.as<Cnt4>(), zero, (size_t)filled, Cnt4Add(), st));
         BWAMS_HIP(need_tmp(tb));
-        tb = tmp_bytes;
         BWAMS_HIP(rocprim::exclusive_scan(tmp.p, tb, blkcnt.as<Cnt4>(), blkcnt.as<Cnt4>(), zero, (size_t)filled, Cnt4Add(), st));
     }
     hipLaunchKernelGGL(cp_counts_kernel, dim3(nblk(filled * 4, kBlk)), dim3(kBlk), 0, st, blkcnt.as<Cnt4>(), filled, cp.as<uint64_t>());
@@ -568,18 +549,17 @@ int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int ke
     (void)hipEventDestroy(e1);
     sa.release(); blkcnt.release(); tmp.release();
 
-    ix->owns = true;
     ix->n_blk = n_blk;
     ix->n_sa = n_sa;
-    ix->d_cp = cp.p; cp.p = nullptr;
-    ix->d_ms = ms.p; ms.p = nullptr;
-    ix->d_ls = ls.p; ls.p = nullptr;
-    if (keep_ref) { ix->d_ref = ref.p; ref.p = nullptr; }
+    ix->d_cp = std::move(cp);
+    ix->d_ms = std::move(ms);
+    ix->d_ls = std::move(ls);
+    if (keep_ref) ix->d_ref = std::move(ref);
     ix->bytes = n_blk * 64 + n_sa * 5 + (keep_ref ? N : 0);
-    ix->fmi.cp = reinterpret_cast<const uint4 *>(ix->d_cp);
-    ix->fmi.sa_ms = reinterpret_cast<const int8_t *>(ix->d_ms);
-    ix->fmi.sa_ls = reinterpret_cast<const uint32_t *>(ix->d_ls);
-    ix->fmi.ref = reinterpret_cast<const uint8_t *>(ix->d_ref);
+    ix->fmi.cp = ix->d_cp.as<const uint4>();
+    ix->fmi.sa_ms = ix->d_ms.as<const int8_t>();
+    ix->fmi.sa_ls = ix->d_ls.as<const uint32_t>();
+    ix->fmi.ref = ix->d_ref.as<const uint8_t>();
     for (int k = 0; k < 5; ++k) ix->fmi.count[k] = count[k] + 1;           // as the loader leaves them (FMI_search.cpp:880-883)
     ix->fmi.sentinel = sentinel;
     ix->fmi.ref_seq_len = L;

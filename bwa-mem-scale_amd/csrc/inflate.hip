@@ -378,9 +378,11 @@ struct bwams_inflater {
     int64_t max_in = 0, max_out = 0, max_members = 0;
     hipStream_t st = nullptr;
     hipEvent_t ev[4] = {};
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    Member *d_mem = nullptr, *h_mem = nullptr;        // h_mem / h_status page-locked
-    int32_t *d_status = nullptr, *h_status = nullptr;
+    bwams::DevBuf<uint8_t> d_in, d_out;
+    bwams::DevBuf<Member> d_mem;
+    bwams::HostBuf<Member> h_mem;                     // h_mem / h_status page-locked
+    bwams::DevBuf<int32_t> d_status;
+    bwams::HostBuf<int32_t> h_status;
     int64_t members_done = 0, bytes_done = 0;         // over every call: a handle fed one file in order names the file's members
     std::vector<int64_t> at;                          // this call's members: where each starts in gz
 };
@@ -392,12 +394,6 @@ int bwams_inflater_destroy(bwams_inflater_t *f) {
     (void)hipSetDevice(f->device);
     if (f->st) (void)hipStreamSynchronize(f->st);
     for (auto e : f->ev) if (e) (void)hipEventDestroy(e);
-    if (f->d_in) (void)hipFree(f->d_in);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->d_mem) (void)hipFree(f->d_mem);
-    if (f->d_status) (void)hipFree(f->d_status);
-    if (f->h_mem) (void)hipHostFree(f->h_mem);
-    if (f->h_status) (void)hipHostFree(f->h_status);
     if (f->st) (void)hipStreamDestroy(f->st);
     delete f;
     return BWAMS_OK;
@@ -426,12 +422,12 @@ int bwams_inflater_create(int device, int64_t max_in_bytes, int64_t max_out_byte
     if ((e = hipStreamCreateWithFlags(&f->st, hipStreamNonBlocking)) != hipSuccess) return fail(e);
     for (auto &x : f->ev)
         if ((e = hipEventCreate(&x)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&f->d_in, (size_t)max_in_bytes)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&f->d_out, (size_t)max_out_bytes)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&f->d_mem, sizeof(Member) * (size_t)f->max_members)) != hipSuccess) return fail(e);
-    if ((e = dev_malloc(&f->d_status, sizeof(int32_t) * (size_t)f->max_members)) != hipSuccess) return fail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void **>(&f->h_mem), sizeof(Member) * (size_t)f->max_members, hipHostMallocDefault)) != hipSuccess) return fail(e);
-    if ((e = hipHostMalloc(reinterpret_cast<void **>(&f->h_status), sizeof(int32_t) * (size_t)f->max_members, hipHostMallocDefault)) != hipSuccess) return fail(e);
+    if ((e = f->d_in.alloc((size_t)max_in_bytes)) != hipSuccess) return fail(e);
+    if ((e = f->d_out.alloc((size_t)max_out_bytes)) != hipSuccess) return fail(e);
+    if ((e = f->d_mem.alloc(sizeof(Member) * (size_t)f->max_members)) != hipSuccess) return fail(e);
+    if ((e = f->d_status.alloc(sizeof(int32_t) * (size_t)f->max_members)) != hipSuccess) return fail(e);
+    if ((e = f->h_mem.alloc(sizeof(Member) * (size_t)f->max_members)) != hipSuccess) return fail(e);
+    if ((e = f->h_status.alloc(sizeof(int32_t) * (size_t)f->max_members)) != hipSuccess) return fail(e);
     *out = f;
     return BWAMS_OK;
 }
@@ -476,7 +472,7 @@ int bwams_inflater_run(bwams_inflater_t *f, const uint8_t *gz, int64_t n_bytes, 
         }
         if ((int64_t)f->at.size() <= nm) f->at.resize((size_t)nm + 1);
         f->at[(size_t)nm] = p;
-        Member &m = f->h_mem[nm];
+        Member &m = f->h_mem.p[nm];
         m.in_off = p + hdr;
         m.in_len = total - hdr - 8;
         m.out_off = o;
@@ -488,22 +484,22 @@ int bwams_inflater_run(bwams_inflater_t *f, const uint8_t *gz, int64_t n_bytes, 
         ++nm;
     }
     if (nm == 0) return BWAMS_OK;
-    uint8_t *d_out = out_on_device ? static_cast<uint8_t *>(out) : f->d_out;
+    uint8_t *d_out = out_on_device ? static_cast<uint8_t *>(out) : f->d_out.p;
     BWAMS_HIP(hipEventRecord(f->ev[0], f->st));
-    BWAMS_HIP(hipMemcpyAsync(f->d_in, gz, (size_t)p, hipMemcpyHostToDevice, f->st));
-    BWAMS_HIP(hipMemcpyAsync(f->d_mem, f->h_mem, sizeof(Member) * (size_t)nm, hipMemcpyHostToDevice, f->st));
+    BWAMS_HIP(hipMemcpyAsync(f->d_in.p, gz, (size_t)p, hipMemcpyHostToDevice, f->st));
+    BWAMS_HIP(hipMemcpyAsync(f->d_mem.p, f->h_mem.p, sizeof(Member) * (size_t)nm, hipMemcpyHostToDevice, f->st));
     BWAMS_HIP(hipEventRecord(f->ev[1], f->st));
-    hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)nm), dim3(64), 0, f->st, f->d_in, f->d_mem, d_out, f->d_status);
+    hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)nm), dim3(64), 0, f->st, f->d_in.p, f->d_mem.p, d_out, f->d_status.p);
     BWAMS_HIP(hipGetLastError());
     BWAMS_HIP(hipEventRecord(f->ev[2], f->st));
-    BWAMS_HIP(hipMemcpyAsync(f->h_status, f->d_status, sizeof(int32_t) * (size_t)nm, hipMemcpyDeviceToHost, f->st));
+    BWAMS_HIP(hipMemcpyAsync(f->h_status.p, f->d_status.p, sizeof(int32_t) * (size_t)nm, hipMemcpyDeviceToHost, f->st));
     BWAMS_HIP(hipStreamSynchronize(f->st));
     for (int64_t i = 0; i < nm; ++i)
-        if (f->h_status[i] != ST_OK) {
-            set_last_error(where(i, f->at[(size_t)i]) + status_text(f->h_status[i]));
+        if (f->h_status.p[i] != ST_OK) {
+            set_last_error(where(i, f->at[(size_t)i]) + status_text(f->h_status.p[i]));
             return BWAMS_ERR_IO;
         }
-    if (!out_on_device && o) BWAMS_HIP(hipMemcpyAsync(out, f->d_out, (size_t)o, hipMemcpyDeviceToHost, f->st));
+    if (!out_on_device && o) BWAMS_HIP(hipMemcpyAsync(out, f->d_out.p, (size_t)o, hipMemcpyDeviceToHost, f->st));
     BWAMS_HIP(hipEventRecord(f->ev[3], f->st));
     BWAMS_HIP(hipEventSynchronize(f->ev[3]));
     if (stats) {
