@@ -16,6 +16,10 @@ is unset), every rank holding a replica of the index and its own shard of reads,
 (`--scaling weak`: --reads per rank; `--scaling strong`: --reads-total split over the ranks, BASELINE config 4's shape).
 
 Prints ONE JSON line (rank 0).  DESIGN.md "Measurement" defines roofline.achieved (algorithmic bytes) and cpu_baseline.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` adds what is measured
+beside the headline: the steps seeded over the ERT and configs[2]'s index set, the SAM side, the paired-end leg, the harder
+genome and the CPU oracle (cpu_baseline).
 """
 from __future__ import annotations
 
@@ -79,6 +83,9 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--reads-total", type=int, default=8_000_000, help="reads of the whole job (strong scaling)")
     ap.add_argument("--chunk-reads", type=int, default=1_000_000, help="reads per resident chunk (one bwams batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs reported beside `value`: ERT and configs[2] legs, SAM side, "
+                         "paired-end leg, harder genome, CPU oracle (each can be skipped with its --no-* option)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fma", action="store_true", help="build and use the FMA tables (all_smem.11 / last_smem.13)")
@@ -442,9 +449,9 @@ def main():
         dumped = dump_outputs(args.dump_outputs, batch, run_chunk, chunk_sizes, first)
         log(f"outputs of the last timed step: {dumped['files']} files, {dumped['bytes'] / 2**20:.1f} MiB in {args.dump_outputs}")
 
-    # ---------------- the same steps with seeding over the ERT (reported beside, never `value`; N = 1 only) ----------------
+    # ---------------- the same steps with seeding over the ERT (--full; reported beside, never `value`; N = 1 only) ----------------
     ert_side = None
-    if not args.ert and not args.no_ert_leg and world == 1 and not (args.fma or args.emf):
+    if args.full and not args.ert and not args.no_ert_leg and world == 1 and not (args.fma or args.emf):
         t0 = time.time()
         ert_h = capi.Ert.build(ix)
         ert_info = ert_h.info()
@@ -552,184 +559,186 @@ def main():
         step()                                  # leave the batch as the timed configuration left it (the legs below read it)
         batch.sync()
 
-    # ---------------- SAM-side alignment of the last chunk's final regions (reported beside, never `value`) ----------------
-    batch.mark_primary_se(mem_opt, id_base=first)
-    batch.sync()
-    t0 = time.perf_counter()
-    batch.mark_primary_se(mem_opt, id_base=first)           # mem_mark_primary_se of every read (mem_reg2sam's first step)
-    batch.sync()
-    mark_ms = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    aln_, cig_, md_ = batch.reg2aln(mem_opt, 1)
-    reg2aln_ms = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    n_aln = capi.C.c_int64(0); n_cig = capi.C.c_int64(0); n_md = capi.C.c_int64(0)
-    capi._chk(capi.lib().bwams_reg2aln_run(batch.h, capi.C.byref(mem_opt), 1, capi.C.byref(n_aln), capi.C.byref(n_cig), capi.C.byref(n_md)), "bwams_reg2aln_run")
-    reg2aln_run_ms = (time.perf_counter() - t0) * 1e3
-    sam_side = {"regions": int(n_aln.value), "cigar_ops": int(n_cig.value), "md_bytes": int(n_md.value),
-                "gapped_fraction": round(float(np.mean([(int(c) & 0xf) in (1, 2) for c in cig_[:200000]])), 4) if len(cig_) else 0.0,
-                "ms_mark_primary_se": round(mark_ms, 2), "mean_mapq": round(float(aln_["mapq"].mean()), 2) if len(aln_) else None,
-                "ms_run": round(reg2aln_run_ms, 2), "ms_run_plus_fetch": round(reg2aln_ms, 2),
-                "Malignments_per_s": round(n_aln.value / (reg2aln_run_ms * 1e-3) / 1e6, 2) if reg2aln_run_ms > 0 else None,
-                "note": "single-end SAM side of one chunk on the device: mem_mark_primary_se of every read, then mem_reg2aln (band inference, "
-                        "banded global alignment with traceback, CIGAR / NM / MD, position) of every final region; mapping quality on the host "
-                        "side of the library"}
-    # mem_reg2aln restricted to what the SAM text reads (the reference aligns only what it prints)
-    sopt_ = capi.default_sam_opt()
-    batch.reg2aln_sam(mem_opt, sopt_, fetch=False)
-    t0 = time.perf_counter()
-    _, n_needed_ = batch.reg2aln_sam(mem_opt, sopt_, fetch=False)
-    reg2aln_sam_ms = (time.perf_counter() - t0) * 1e3
-    aln_r_ = batch.reg2aln_sam(mem_opt, sopt_)[0]
-    done_ = aln_r_["rid"] >= 0
-    sam_side["reg2aln_for_sam"] = {"regions_aligned": int(n_needed_), "of": int(n_aln.value), "ms_run": round(reg2aln_sam_ms, 2),
-                                   "note": "bwams_reg2aln_run_sam: the records mem_reg2sam prints and the members of their XA strings only; "
-                                           "the SAM text below is produced from this run"}
-    # the SAM text of the chunk (mem_reg2sam + mem_gen_alt + mem_aln2sam on the device), with size-independent checks
-    cum_ = cums[n_chunks - 1]
-    n_seq_ = len(cum_) - 1
-    names_ = [b"r%08d" % (first + i) for i in range(n_seq_)]          # the names the FASTQ text below carries
-    quals_ = np.full(int(cum_[-1]), ord("I"), np.uint8)
-    ix.set_contig_names([b"chr%d" % (i + 1) for i in range(len(contigs) if contigs is not None else 1)])
-    t0 = time.perf_counter()
-    batch.sam_upload(names_, quals_)
-    sam_up_ms = (time.perf_counter() - t0) * 1e3
-    batch.sam_run(mem_opt, sopt_)
-    t0 = time.perf_counter()
-    sam_bytes = batch.sam_run(mem_opt, sopt_)
-    sam_ms = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    text_, roff_, mq_ = batch.sam_fetch(len(aln_))
-    sam_fetch_ms = (time.perf_counter() - t0) * 1e3
-    tb = np.frombuffer(text_, np.uint8)
-    n_lines = int((tb == 10).sum())
-    n_tabs = int((tb == 9).sum())
-    checks = {
-        "device_mapq_equals_host_mapq": bool(np.array_equal(mq_[done_], aln_["mapq"][done_])),
-        "restricted_records_equal_full_run": bool(all(np.array_equal(aln_r_[f_][done_], aln_[f_][done_]) for f_ in ("pos", "rid", "NM", "n_cigar", "md_len", "score"))
-                                                  and int(done_.sum()) == int(n_needed_)),
-        "one_block_per_read": bool(roff_[0] == 0 and roff_[-1] == sam_bytes and np.all(np.diff(roff_) > 0)),
-        "every_block_ends_a_line": bool(np.all(tb[roff_[1:] - 1] == 10)),
-        "lines_at_least_reads": n_lines >= n_seq_,
-        "eleven_fields_per_line": n_tabs >= 10 * n_lines,
-    }
-    sam_side["sam_text"] = {"bytes": int(sam_bytes), "lines": n_lines, "ms_run": round(sam_ms, 2), "ms_upload_names_quals": round(sam_up_ms, 2),
-                            "ms_fetch": round(sam_fetch_ms, 2), "Mreads_per_s": round(n_seq_ / (sam_ms * 1e-3) / 1e6, 2) if sam_ms > 0 else None,
-                            "GBps_written": round(sam_bytes / (sam_ms * 1e-3) / 1e9, 2) if sam_ms > 0 else None,
-                            "xa_tags": int(text_.count(b"\tXA:Z:")), "unaligned_records": int(text_.count(b"\t4\t*\t0\t0\t*\t")),
-                            "checks": checks,
-                            "note": "mem_reg2sam + mem_gen_alt + mem_aln2sam (single-end) and mem_approx_mapq_se on the device, names "
-                                    "and qualities already in HBM when timed; byte-equal to the oracle in tests/test_gpu_sam.py"}
-    if not all(checks.values()):
-        raise SystemExit(f"[bench] SAM text property check failed: {checks}")
-    # read input: the chunk as FASTQ text -> encoded bases, names, qualities on the device (kseq_read + trim_readno + base encoding)
-    rd_ = reads_l[n_chunks - 1]
-    row = fastq_rows(rd_, first)
-    fq_text = row.tobytes()
-    d_fq = torch.from_numpy(row.reshape(-1)).to(dev)               # the text resident in HBM, as the other inputs are
-    fq = capi.Fastq(d_fq.data_ptr(), device=local, n_bytes=len(fq_text)); fq.close()
-    t0 = time.perf_counter()
-    fq = capi.Fastq(d_fq.data_ptr(), device=local, n_bytes=len(fq_text))
-    fq_wall_ms = (time.perf_counter() - t0) * 1e3
-    fqi = fq.info()
-    got_ = fq.fetch()
-    fq_checks = {"bases_equal_the_reads": bool(np.array_equal(got_["enc"], rd_.reshape(-1))),
-                 "cum_is_regular": bool(np.array_equal(got_["cum"], cum_)),
-                 "names_round_trip": bool(got_["names"][0] == b"r%08d" % first and got_["names"][-1] == b"r%08d" % (first + n_seq_ - 1)),
-                 "qualities_round_trip": bool((got_["quals"] == ord("I")).all())}
-    fq.close()
-    sam_side["fastq_decode"] = {"bytes": len(fq_text), "reads": int(fqi["n_reads"]), "ms_kernels": round(fqi["ms"], 3), "ms_call": round(fq_wall_ms, 2),
-                                "GBps_text": round(len(fq_text) / (fqi["ms"] * 1e-3) / 1e9, 1) if fqi["ms"] > 0 else None,
-                                "Mreads_per_s": round(fqi["n_reads"] / (fqi["ms"] * 1e-3) / 1e6, 1) if fqi["ms"] > 0 else None,
-                                "checks": fq_checks,
-                                "note": "four-line FASTQ text already in HBM -> encoded bases + cum, names (trim_readno), comments, qualities: line "
-                                        "ends (count + rocPRIM select), a lane per record to validate and measure, a wave per record to copy / encode; "
-                                        "ms_call adds the allocations, three scans and the offset arrays' copy to the host"}
-    if not all(fq_checks.values()):
-        raise SystemExit(f"[bench] FASTQ decode property check failed: {fq_checks}")
-    # the whole single-end path in one go, text to text: FASTQ bytes (in HBM) -> ... -> SAM bytes (in HBM)
-    def fastq_to_sam():                                  # bwams_process_chunk: the outer boundary, one call
-        return batch.process_chunk((d_fq.data_ptr(), len(fq_text)), seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first, fetch=False)
-    fastq_to_sam()
-    batch.sync()
-    t0 = time.perf_counter()
-    for _ in range(2):
-        e2e_bytes = fastq_to_sam()
-    batch.sync()
-    e2e_ms = (time.perf_counter() - t0) / 2 * 1e3
-    sam_side["fastq_to_sam"] = {"ms_per_chunk": round(e2e_ms, 2), "Mreads_per_s": round(n_seq_ / (e2e_ms * 1e-3) / 1e6, 3), "sam_bytes": int(e2e_bytes),
-                                "note": "bwams_process_chunk — single-end, FM-index seeding, one chunk end to end on the device: FASTQ decode, seed -> chain -> extend -> dedup, "
-                                        "mem_mark_primary_se, mem_reg2aln of what the text needs, SAM text; FASTQ text resident in HBM at the start, "
-                                        "SAM text left in HBM at the end (host transfers and gz excluded); never `value`"}
-    if e2e_bytes != sam_bytes:
-        raise SystemExit(f"[bench] FASTQ -> SAM run produced {e2e_bytes} bytes of text, the staged run {sam_bytes}")
-    # the same call with the text in pageable host memory on both sides (what a caller without device buffers pays): never `value`
-    sam_h = np.empty(int(sam_bytes) + 16, np.uint8)
-    off_h = np.empty(n_seq_ + 1, np.int64)
-    t0 = time.perf_counter()
-    hb_ = batch.process_chunk(fq_text, seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first, fetch=False)
-    capi._chk(capi.lib().bwams_sam_fetch(batch.h, capi._p(sam_h), len(sam_h), capi._p(off_h), None, 0), "bwams_sam_fetch")
-    pcie_ms = (time.perf_counter() - t0) * 1e3
-    sam_side["fastq_to_sam"]["pcie_inclusive"] = {
-        "ms_per_chunk": round(pcie_ms, 2), "Mreads_per_s": round(n_seq_ / (pcie_ms * 1e-3) / 1e6, 3),
-        "host_bytes_up": len(fq_text), "host_bytes_down": int(hb_) + 8 * (n_seq_ + 1),
-        "note": "FASTQ text in pageable host memory -> SAM text and its per-read offsets in pageable host memory, one call + bwams_sam_fetch"}
-    del sam_h, off_h
-    # ... and in PAGE-LOCKED host memory (bwams_host_alloc), which is what the compiled caller at the reference's boundary stages
-    # through (bwa-mem-scale_amd/host/mem_process_seqs_hip.cpp): never `value`
-    fq_pin = capi.pinned_array(len(fq_text))
-    fq_pin[:] = np.frombuffer(fq_text, np.uint8)
-    sam_pin = capi.pinned_array(int(sam_bytes) + 16)
-    off_pin = capi.pinned_array(n_seq_ + 1, np.int64)
-    pin_ms = []
-    for _ in range(2):
+    # ---------------- SAM-side alignment of the last chunk's final regions (--full; reported beside, never `value`) ----------------
+    sam_side = None
+    if args.full:
+        batch.mark_primary_se(mem_opt, id_base=first)
+        batch.sync()
         t0 = time.perf_counter()
-        hb_ = batch.process_chunk((fq_pin.ctypes.data, len(fq_text)), seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first, fetch=False)
-        capi._chk(capi.lib().bwams_sam_fetch(batch.h, capi._p(sam_pin), len(sam_pin), capi._p(off_pin), None, 0), "bwams_sam_fetch")
-        pin_ms.append((time.perf_counter() - t0) * 1e3)
-    sam_side["fastq_to_sam"]["pcie_inclusive_pinned"] = {
-        "ms_per_chunk": round(min(pin_ms), 2), "Mreads_per_s": round(n_seq_ / (min(pin_ms) * 1e-3) / 1e6, 3),
-        "ratio_to_resident": round(min(pin_ms) / e2e_ms, 3),
-        "note": "the same call with both texts in page-locked host memory (bwams_host_alloc): what the compiled mem_process_seqs() pays per chunk"}
-    # ... and the chunk over TWO batches on this GPU behind one call (host/chunk_multi.cpp: the N-GPU form of the outer boundary with
-    # both shards on one device): parsed records in page-locked memory -> SAM text in page-locked memory, in read order
-    try:
-        b2 = [capi.Batch(ix, n_seq_, n_seq_ * RL) for _ in range(2)]
-        multi = capi.Multi(b2)
-        nm_pin = capi.pinned_array(9 * n_seq_)
-        nm_pin[:] = np.frombuffer(b"".join(b"r%08d" % (first + i) for i in range(n_seq_)), np.uint8)
-        noff_ = (np.arange(n_seq_ + 1, dtype=np.int64) * 9)
-        enc_pin = capi.pinned_array(n_seq_ * RL)
-        enc_pin[:] = rd_.reshape(-1)
-        q_pin = capi.pinned_array(n_seq_ * RL)
-        q_pin[:] = ord("I")
-        mt = []
+        batch.mark_primary_se(mem_opt, id_base=first)           # mem_mark_primary_se of every read (mem_reg2sam's first step)
+        batch.sync()
+        mark_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        aln_, cig_, md_ = batch.reg2aln(mem_opt, 1)
+        reg2aln_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        n_aln = capi.C.c_int64(0); n_cig = capi.C.c_int64(0); n_md = capi.C.c_int64(0)
+        capi._chk(capi.lib().bwams_reg2aln_run(batch.h, capi.C.byref(mem_opt), 1, capi.C.byref(n_aln), capi.C.byref(n_cig), capi.C.byref(n_md)), "bwams_reg2aln_run")
+        reg2aln_run_ms = (time.perf_counter() - t0) * 1e3
+        sam_side = {"regions": int(n_aln.value), "cigar_ops": int(n_cig.value), "md_bytes": int(n_md.value),
+                    "gapped_fraction": round(float(np.mean([(int(c) & 0xf) in (1, 2) for c in cig_[:200000]])), 4) if len(cig_) else 0.0,
+                    "ms_mark_primary_se": round(mark_ms, 2), "mean_mapq": round(float(aln_["mapq"].mean()), 2) if len(aln_) else None,
+                    "ms_run": round(reg2aln_run_ms, 2), "ms_run_plus_fetch": round(reg2aln_ms, 2),
+                    "Malignments_per_s": round(n_aln.value / (reg2aln_run_ms * 1e-3) / 1e6, 2) if reg2aln_run_ms > 0 else None,
+                    "note": "single-end SAM side of one chunk on the device: mem_mark_primary_se of every read, then mem_reg2aln (band inference, "
+                            "banded global alignment with traceback, CIGAR / NM / MD, position) of every final region; mapping quality on the host "
+                            "side of the library"}
+        # mem_reg2aln restricted to what the SAM text reads (the reference aligns only what it prints)
+        sopt_ = capi.default_sam_opt()
+        batch.reg2aln_sam(mem_opt, sopt_, fetch=False)
+        t0 = time.perf_counter()
+        _, n_needed_ = batch.reg2aln_sam(mem_opt, sopt_, fetch=False)
+        reg2aln_sam_ms = (time.perf_counter() - t0) * 1e3
+        aln_r_ = batch.reg2aln_sam(mem_opt, sopt_)[0]
+        done_ = aln_r_["rid"] >= 0
+        sam_side["reg2aln_for_sam"] = {"regions_aligned": int(n_needed_), "of": int(n_aln.value), "ms_run": round(reg2aln_sam_ms, 2),
+                                       "note": "bwams_reg2aln_run_sam: the records mem_reg2sam prints and the members of their XA strings only; "
+                                               "the SAM text below is produced from this run"}
+        # the SAM text of the chunk (mem_reg2sam + mem_gen_alt + mem_aln2sam on the device), with size-independent checks
+        cum_ = cums[n_chunks - 1]
+        n_seq_ = len(cum_) - 1
+        names_ = [b"r%08d" % (first + i) for i in range(n_seq_)]          # the names the FASTQ text below carries
+        quals_ = np.full(int(cum_[-1]), ord("I"), np.uint8)
+        ix.set_contig_names([b"chr%d" % (i + 1) for i in range(len(contigs) if contigs is not None else 1)])
+        t0 = time.perf_counter()
+        batch.sam_upload(names_, quals_)
+        sam_up_ms = (time.perf_counter() - t0) * 1e3
+        batch.sam_run(mem_opt, sopt_)
+        t0 = time.perf_counter()
+        sam_bytes = batch.sam_run(mem_opt, sopt_)
+        sam_ms = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        text_, roff_, mq_ = batch.sam_fetch(len(aln_))
+        sam_fetch_ms = (time.perf_counter() - t0) * 1e3
+        tb = np.frombuffer(text_, np.uint8)
+        n_lines = int((tb == 10).sum())
+        n_tabs = int((tb == 9).sum())
+        checks = {
+            "device_mapq_equals_host_mapq": bool(np.array_equal(mq_[done_], aln_["mapq"][done_])),
+            "restricted_records_equal_full_run": bool(all(np.array_equal(aln_r_[f_][done_], aln_[f_][done_]) for f_ in ("pos", "rid", "NM", "n_cigar", "md_len", "score"))
+                                                      and int(done_.sum()) == int(n_needed_)),
+            "one_block_per_read": bool(roff_[0] == 0 and roff_[-1] == sam_bytes and np.all(np.diff(roff_) > 0)),
+            "every_block_ends_a_line": bool(np.all(tb[roff_[1:] - 1] == 10)),
+            "lines_at_least_reads": n_lines >= n_seq_,
+            "eleven_fields_per_line": n_tabs >= 10 * n_lines,
+        }
+        sam_side["sam_text"] = {"bytes": int(sam_bytes), "lines": n_lines, "ms_run": round(sam_ms, 2), "ms_upload_names_quals": round(sam_up_ms, 2),
+                                "ms_fetch": round(sam_fetch_ms, 2), "Mreads_per_s": round(n_seq_ / (sam_ms * 1e-3) / 1e6, 2) if sam_ms > 0 else None,
+                                "GBps_written": round(sam_bytes / (sam_ms * 1e-3) / 1e9, 2) if sam_ms > 0 else None,
+                                "xa_tags": int(text_.count(b"\tXA:Z:")), "unaligned_records": int(text_.count(b"\t4\t*\t0\t0\t*\t")),
+                                "checks": checks,
+                                "note": "mem_reg2sam + mem_gen_alt + mem_aln2sam (single-end) and mem_approx_mapq_se on the device, names "
+                                        "and qualities already in HBM when timed; byte-equal to the oracle in tests/test_gpu_sam.py"}
+        if not all(checks.values()):
+            raise SystemExit(f"[bench] SAM text property check failed: {checks}")
+        # read input: the chunk as FASTQ text -> encoded bases, names, qualities on the device (kseq_read + trim_readno + base encoding)
+        rd_ = reads_l[n_chunks - 1]
+        row = fastq_rows(rd_, first)
+        fq_text = row.tobytes()
+        d_fq = torch.from_numpy(row.reshape(-1)).to(dev)               # the text resident in HBM, as the other inputs are
+        fq = capi.Fastq(d_fq.data_ptr(), device=local, n_bytes=len(fq_text)); fq.close()
+        t0 = time.perf_counter()
+        fq = capi.Fastq(d_fq.data_ptr(), device=local, n_bytes=len(fq_text))
+        fq_wall_ms = (time.perf_counter() - t0) * 1e3
+        fqi = fq.info()
+        got_ = fq.fetch()
+        fq_checks = {"bases_equal_the_reads": bool(np.array_equal(got_["enc"], rd_.reshape(-1))),
+                     "cum_is_regular": bool(np.array_equal(got_["cum"], cum_)),
+                     "names_round_trip": bool(got_["names"][0] == b"r%08d" % first and got_["names"][-1] == b"r%08d" % (first + n_seq_ - 1)),
+                     "qualities_round_trip": bool((got_["quals"] == ord("I")).all())}
+        fq.close()
+        sam_side["fastq_decode"] = {"bytes": len(fq_text), "reads": int(fqi["n_reads"]), "ms_kernels": round(fqi["ms"], 3), "ms_call": round(fq_wall_ms, 2),
+                                    "GBps_text": round(len(fq_text) / (fqi["ms"] * 1e-3) / 1e9, 1) if fqi["ms"] > 0 else None,
+                                    "Mreads_per_s": round(fqi["n_reads"] / (fqi["ms"] * 1e-3) / 1e6, 1) if fqi["ms"] > 0 else None,
+                                    "checks": fq_checks,
+                                    "note": "four-line FASTQ text already in HBM -> encoded bases + cum, names (trim_readno), comments, qualities: line "
+                                            "ends (count + rocPRIM select), a lane per record to validate and measure, a wave per record to copy / encode; "
+                                            "ms_call adds the allocations, three scans and the offset arrays' copy to the host"}
+        if not all(fq_checks.values()):
+            raise SystemExit(f"[bench] FASTQ decode property check failed: {fq_checks}")
+        # the whole single-end path in one go, text to text: FASTQ bytes (in HBM) -> ... -> SAM bytes (in HBM)
+        def fastq_to_sam():                                  # bwams_process_chunk: the outer boundary, one call
+            return batch.process_chunk((d_fq.data_ptr(), len(fq_text)), seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first, fetch=False)
+        fastq_to_sam()
+        batch.sync()
+        t0 = time.perf_counter()
+        for _ in range(2):
+            e2e_bytes = fastq_to_sam()
+        batch.sync()
+        e2e_ms = (time.perf_counter() - t0) / 2 * 1e3
+        sam_side["fastq_to_sam"] = {"ms_per_chunk": round(e2e_ms, 2), "Mreads_per_s": round(n_seq_ / (e2e_ms * 1e-3) / 1e6, 3), "sam_bytes": int(e2e_bytes),
+                                    "note": "bwams_process_chunk — single-end, FM-index seeding, one chunk end to end on the device: FASTQ decode, seed -> chain -> extend -> dedup, "
+                                            "mem_mark_primary_se, mem_reg2aln of what the text needs, SAM text; FASTQ text resident in HBM at the start, "
+                                            "SAM text left in HBM at the end (host transfers and gz excluded); never `value`"}
+        if e2e_bytes != sam_bytes:
+            raise SystemExit(f"[bench] FASTQ -> SAM run produced {e2e_bytes} bytes of text, the staged run {sam_bytes}")
+        # the same call with the text in pageable host memory on both sides (what a caller without device buffers pays): never `value`
+        sam_h = np.empty(int(sam_bytes) + 16, np.uint8)
+        off_h = np.empty(n_seq_ + 1, np.int64)
+        t0 = time.perf_counter()
+        hb_ = batch.process_chunk(fq_text, seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first, fetch=False)
+        capi._chk(capi.lib().bwams_sam_fetch(batch.h, capi._p(sam_h), len(sam_h), capi._p(off_h), None, 0), "bwams_sam_fetch")
+        pcie_ms = (time.perf_counter() - t0) * 1e3
+        sam_side["fastq_to_sam"]["pcie_inclusive"] = {
+            "ms_per_chunk": round(pcie_ms, 2), "Mreads_per_s": round(n_seq_ / (pcie_ms * 1e-3) / 1e6, 3),
+            "host_bytes_up": len(fq_text), "host_bytes_down": int(hb_) + 8 * (n_seq_ + 1),
+            "note": "FASTQ text in pageable host memory -> SAM text and its per-read offsets in pageable host memory, one call + bwams_sam_fetch"}
+        del sam_h, off_h
+        # ... and in PAGE-LOCKED host memory (bwams_host_alloc), which is what the compiled caller at the reference's boundary stages
+        # through (bwa-mem-scale_amd/host/mem_process_seqs_hip.cpp): never `value`
+        fq_pin = capi.pinned_array(len(fq_text))
+        fq_pin[:] = np.frombuffer(fq_text, np.uint8)
+        sam_pin = capi.pinned_array(int(sam_bytes) + 16)
+        off_pin = capi.pinned_array(n_seq_ + 1, np.int64)
+        pin_ms = []
         for _ in range(2):
             t0 = time.perf_counter()
-            mtext, moff = multi.process_reads(enc_pin, cum_, nm_pin, noff_, quals=q_pin, seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first)
-            mt.append((time.perf_counter() - t0) * 1e3)
-        sam_side["fastq_to_sam"]["two_batches_one_call"] = {
-            "ms_per_chunk": round(min(mt), 2), "Mreads_per_s": round(n_seq_ / (min(mt) * 1e-3) / 1e6, 3), "same_text": bool(len(mtext) == sam_bytes),
-            "note": "bwams_multi_process_reads + bwams_multi_fetch with 2 batches on ONE GPU (parsed records up, text down, page-locked; the fetch "
-                    "lands in a pageable numpy buffer here): the code path `N GPUs behind one C call` takes, byte-identical to one batch "
-                    "(tests/test_host_boundary.py); no N > 1 hardware run exists for it"}
-        multi.close()
-        for b_ in b2:
-            b_.close()
-        for a_ in (nm_pin, enc_pin, q_pin):
+            hb_ = batch.process_chunk((fq_pin.ctypes.data, len(fq_text)), seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first, fetch=False)
+            capi._chk(capi.lib().bwams_sam_fetch(batch.h, capi._p(sam_pin), len(sam_pin), capi._p(off_pin), None, 0), "bwams_sam_fetch")
+            pin_ms.append((time.perf_counter() - t0) * 1e3)
+        sam_side["fastq_to_sam"]["pcie_inclusive_pinned"] = {
+            "ms_per_chunk": round(min(pin_ms), 2), "Mreads_per_s": round(n_seq_ / (min(pin_ms) * 1e-3) / 1e6, 3),
+            "ratio_to_resident": round(min(pin_ms) / e2e_ms, 3),
+            "note": "the same call with both texts in page-locked host memory (bwams_host_alloc): what the compiled mem_process_seqs() pays per chunk"}
+        # ... and the chunk over TWO batches on this GPU behind one call (host/chunk_multi.cpp: the N-GPU form of the outer boundary with
+        # both shards on one device): parsed records in page-locked memory -> SAM text in page-locked memory, in read order
+        try:
+            b2 = [capi.Batch(ix, n_seq_, n_seq_ * RL) for _ in range(2)]
+            multi = capi.Multi(b2)
+            nm_pin = capi.pinned_array(9 * n_seq_)
+            nm_pin[:] = np.frombuffer(b"".join(b"r%08d" % (first + i) for i in range(n_seq_)), np.uint8)
+            noff_ = (np.arange(n_seq_ + 1, dtype=np.int64) * 9)
+            enc_pin = capi.pinned_array(n_seq_ * RL)
+            enc_pin[:] = rd_.reshape(-1)
+            q_pin = capi.pinned_array(n_seq_ * RL)
+            q_pin[:] = ord("I")
+            mt = []
+            for _ in range(2):
+                t0 = time.perf_counter()
+                mtext, moff = multi.process_reads(enc_pin, cum_, nm_pin, noff_, quals=q_pin, seed_opt=seed_opt, opt=mem_opt, sopt=sopt_, n_processed=first)
+                mt.append((time.perf_counter() - t0) * 1e3)
+            sam_side["fastq_to_sam"]["two_batches_one_call"] = {
+                "ms_per_chunk": round(min(mt), 2), "Mreads_per_s": round(n_seq_ / (min(mt) * 1e-3) / 1e6, 3), "same_text": bool(len(mtext) == sam_bytes),
+                "note": "bwams_multi_process_reads + bwams_multi_fetch with 2 batches on ONE GPU (parsed records up, text down, page-locked; the fetch "
+                        "lands in a pageable numpy buffer here): the code path `N GPUs behind one C call` takes, byte-identical to one batch "
+                        "(tests/test_host_boundary.py); no N > 1 hardware run exists for it"}
+            multi.close()
+            for b_ in b2:
+                b_.close()
+            for a_ in (nm_pin, enc_pin, q_pin):
+                capi.pinned_free(a_)
+            del b2, multi, nm_pin, enc_pin, q_pin, mtext, moff
+        except capi.BwamsError as e:
+            sam_side["fastq_to_sam"]["two_batches_one_call"] = {"error": str(e)}
+        for a_ in (fq_pin, sam_pin, off_pin):
             capi.pinned_free(a_)
-        del b2, multi, nm_pin, enc_pin, q_pin, mtext, moff
-    except capi.BwamsError as e:
-        sam_side["fastq_to_sam"]["two_batches_one_call"] = {"error": str(e)}
-    for a_ in (fq_pin, sam_pin, off_pin):
-        capi.pinned_free(a_)
-    del fq_pin, sam_pin, off_pin
-    del row, fq_text, d_fq, got_
-    del aln_, cig_, md_, text_, tb, mq_, aln_r_
+        del fq_pin, sam_pin, off_pin
+        del row, fq_text, d_fq, got_
+        del aln_, cig_, md_, text_, tb, mq_, aln_r_
 
-    # ---------------- paired-end leg (every rank: the pestat exchange is a collective) ----------------
+    # ---------------- paired-end leg (--full; every rank: the pestat exchange is a collective) ----------------
     pe_out = None
-    if not args.no_pe:
+    if args.full and not args.no_pe:
         t0 = time.time()
         n_pairs = chunk_sizes[0] // 2
         pr = simulate.make_read_pairs_bulk(genome, n_pairs, seed=4242 + rank, contig_bounds=cb)
@@ -837,9 +846,9 @@ def main():
                                               "mem_pestat inferred from the chunk, mate rescue, pairing, mem_reg2aln of what is printed, mem_sam_pe's text)"}
             del prow, d_pfq
 
-    # ---------------- the same steps on the harder genome (reported beside, never `value`; N = 1 only) ----------------
+    # ---------------- the same steps on the harder genome (--full; reported beside, never `value`; N = 1 only) ----------------
     hard_side = None
-    if world == 1 and not args.no_hard_genome and not (args.fma or args.emf or args.ert):
+    if args.full and world == 1 and not args.no_hard_genome and not (args.fma or args.emf or args.ert):
         t0 = time.time()
         genome_h = simulate.make_genome(G, seed=2024, profile="grch38_like")
         ix_h = capi.Index.build(genome_h, local)
@@ -936,7 +945,7 @@ def main():
             "vs_baseline": None,
             "dtype": "int64 intervals / int16 DP (two columns per register; int32 for queries beyond 191 bases or scores beyond 2^14)",
             "data": "synthetic",
-            "not_included": ["mem_mark_primary_se + mem_reg2aln / ksw_global2 traceback / CIGAR + XA + SAM text (timed beside: sam_side)", "FASTQ decode and host I/O",
+            "not_included": ["mem_mark_primary_se + mem_reg2aln / ksw_global2 traceback / CIGAR + XA + SAM text (timed beside with --full: sam_side)", "FASTQ decode and host I/O",
                              "PCIe transfers (see pcie_inclusive with --pcie)"],
             "config": {
                 "workload": f"{total_reads} synthetic 150bp SE reads ({R} per GPU, {n_chunks} resident chunk(s) of <= {CH}) vs a synthetic {G} bp genome "
@@ -1060,7 +1069,8 @@ def main():
         if pe_out is not None:
             legs["paired_end_Mreads_per_s"] = pe_out.get("value")
             legs["paired_end_fastq_to_sam_Mreads_per_s"] = (pe_out.get("fastq_to_sam") or {}).get("Mreads_per_s")
-        legs["fastq_to_sam_Mreads_per_s"] = (sam_side.get("fastq_to_sam") or {}).get("Mreads_per_s")
+        if sam_side is not None:
+            legs["fastq_to_sam_Mreads_per_s"] = (sam_side.get("fastq_to_sam") or {}).get("Mreads_per_s")
         out["config"]["legs"] = legs
         if emf_h is not None:
             _, codes = batch.emf_fetch(CHn)
@@ -1072,7 +1082,8 @@ def main():
                           "launch_ms": round(emf_ms, 3), "nodes_per_read": round(st.emf_nodes / CHn, 3),
                           "algorithmic_bytes": int(emf_bytes),
                           "achieved_GBps": round(emf_bytes / (emf_ms * 1e-3) / 1e9, 1) if emf_ms > 0 else None}
-        out["sam_side"] = sam_side
+        if sam_side is not None:
+            out["sam_side"] = sam_side
         if dumped is not None:
             out["dumped_outputs"] = dumped
         if pe_out is not None:
@@ -1091,7 +1102,7 @@ def main():
             dt = (time.perf_counter() - t0) / 2
             out["pcie_inclusive"] = {"value": round(len(reads) / dt / 1e6, 4), "unit": "Mreads/s", "ms_per_batch": round(dt * 1e3, 2),
                                      "note": "pageable host buffers: reads up; SMEMs, SA coordinates, chains and final regions down; includes numpy copies"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             log("timing the CPU oracle on a sample (cpu_baseline)...")
             threads = min(16, os.cpu_count() or 1)
             n_s = min(args.cpu_sample, len(reads))

@@ -129,7 +129,7 @@ alg = bench["roofline"]["bytes_per_launch"]
 with open(f"profiles/{rnd}_summary.md", "w") as f:
     f.write(f"# Round {rnd} — rocprofv3 summary (MI355X, gfx950, ROCm 7.2)\n\n")
     f.write(f"Collected by `bash profiles/run_profiles_{rnd}.sh <tag>` at the metric's configuration (synthetic genome of GRCh38's size, 6.4 G index rows): "
-            "`rocprofv3 --kernel-trace --stats -- python3 bench.py "
+            "`rocprofv3 --kernel-trace --stats -- python3 bench.py --full "
             "--steps 2 --warmup 1 --no-cpu-baseline --no-pe --no-ert-leg --no-hard-genome` plus one `--pmc` pass per counter group (never combined "
             f"with tracing); summarised by `profiles/make_summary.py`.  Raw: `profiles/{rnd}_kernel_stats.csv`.\n\n")
     f.write("## Kernel time (library kernels; rocPRIM kernels omitted; the index-build kernels run once, untimed by bench.py)\n\n"
@@ -152,7 +152,7 @@ with open(f"profiles/{rnd}_summary.md", "w") as f:
     te = newest(src + "/trace_ert/*/*_kernel_stats.csv")
     if te:
         shutil.copy(te[0], f"profiles/{rnd}_ert_kernel_stats.csv")
-        f.write("\n### Seeding over the ERT (`bench.py --ert --steps 2 --warmup 1 --no-cpu-baseline --no-pe`; the build kernels run once)\n\n"
+        f.write("\n### Seeding over the ERT (`bench.py --full --ert --steps 2 --warmup 1 --no-cpu-baseline --no-pe`; the build kernels run once)\n\n"
                 "| kernel | calls | avg ms |\n|---|---|---|\n")
         for r in csv.DictReader(open(te[0])):
             s_ = short(r["Name"])

@@ -5,7 +5,7 @@ GMBP=${2:-512}
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
-ARGS="bench.py --genome-mbp $GMBP --steps 1 --warmup 0 --no-cpu-baseline"
+ARGS="bench.py --full --genome-mbp $GMBP --steps 1 --warmup 0 --no-cpu-baseline"
 i=0
 while read -r line; do
   [ -z "$line" ] && continue

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT
 mkdir -p $OUT
-ARGS="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pe --no-ert-leg --no-hard-genome"
+ARGS="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pe --no-ert-leg --no-hard-genome"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace.log 2>&1
 echo "trace done" > $OUT/progress.txt
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $ARGS > $OUT/pmc_fetch.log 2>&1
@@ -20,7 +20,7 @@ echo "l2 done" >> $OUT/progress.txt
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq -- python3 $ARGS > $OUT/pmc_sq.log 2>&1 || true
 echo "sq done" >> $OUT/progress.txt
 # the same with seeding over the ERT (bench.py --ert): kernel trace + the walk kernel's HBM bytes
-EARGS="bench.py --ert --steps 2 --warmup 1 --no-cpu-baseline --no-pe --no-hard-genome"
+EARGS="bench.py --full --ert --steps 2 --warmup 1 --no-cpu-baseline --no-pe --no-hard-genome"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ert -- python3 $EARGS > $OUT/trace_ert.log 2>&1
 echo "trace_ert done" >> $OUT/progress.txt
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_ert -- python3 $EARGS > $OUT/pmc_fetch_ert.log 2>&1

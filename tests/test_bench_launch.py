@@ -29,3 +29,9 @@ def test_gpus_flag_must_match_the_launcher():
     e.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], env=e, capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
+
+
+def test_plain_run_leaves_the_beside_legs_to_full():
+    import bench                                                 # the repository root is on sys.path (tests/conftest.py)
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--full"]).full is True
