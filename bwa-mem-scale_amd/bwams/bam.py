@@ -2,7 +2,8 @@
 
 encode_records(sam_text, ref_names) turns SAM lines into BAM alignment records with htslib's rules (sam_parse1 + bam_write1),
 refusing what csrc/bam.hip refuses (BamRefusal, with the line's index); header_block(text, names, lengths) is the header block;
-decode(bam_bytes) reads an uncompressed BAM stream (header block and records) back, records as SAM lines.
+decode(bam_bytes) reads an uncompressed BAM stream (header block and records) back, records as SAM lines.  coord_key / coord_sort
+restate the coordinate order of csrc/bam_sort.hip (samtools sort's default), record_end the end its coords carry.
 """
 from __future__ import annotations
 
@@ -195,6 +196,29 @@ def split_records(data: bytes, p: int = 0) -> list[bytes]:
         p += 4 + bs
     assert p == len(data), "truncated record"
     return out
+
+
+def record_end(rec: bytes) -> int:
+    """The end reg2bin takes of one record (block_size included): POS + the CIGAR's reference length (M/D/N/=/X), or POS + 1 when
+    unmapped, without CIGAR or of reference length 0 — wrapped to int32, as bwams_bam_coord_t.end holds it."""
+    (pos, l_name, n_cig, flag) = struct.unpack_from("<iBxxxHH", rec, 8)
+    ops = struct.unpack_from("<%dI" % n_cig, rec, 36 + l_name)
+    rlen = sum(c >> 4 for c in ops if c & 15 in (0, 2, 3, 7, 8))
+    end = pos + 1 if (flag & 4) or not ops or rlen == 0 else pos + rlen
+    return (end + (1 << 31)) % (1 << 32) - (1 << 31)
+
+
+def coord_key(rec: bytes) -> int:
+    """The coordinate order's key of one record (block_size included): (uint32)refID << 32 | (uint32)(POS + 1) << 1 | reverse
+    strand — samtools sort's default order, refID -1 (unplaced) last.  include/bwams_types.h (bwams_bam_coord_t) defines it."""
+    (refid, pos, flag) = struct.unpack_from("<ii6xH", rec, 4)
+    return (refid & 0xFFFFFFFF) << 32 | ((pos + 1) & 0xFFFFFFFF) << 1 | (flag >> 4 & 1)
+
+
+def coord_sort(records: bytes) -> bytes:
+    """The records of `records` (block_size included, back to back) in coordinate order: a stable sort by coord_key."""
+    recs = split_records(records)
+    return b"".join(sorted(recs, key=coord_key))
 
 
 def decode(bam_bytes: bytes, names=None):

@@ -47,6 +47,8 @@ SYMBOLS = [
     "bwams_writer_open_bgzf", "bwams_writer_put_bgzf",
     "bwams_bam_run", "bwams_bam_fetch", "bwams_bam_fetch_bgzf", "bwams_sam_header", "bwams_bam_header", "bwams_writer_open_bam",
     "bwams_writer_open", "bwams_writer_put", "bwams_writer_close",
+    "bwams_bam_upload", "bwams_bam_sort", "bwams_bam_sorted_fetch",
+    "bwams_sorter_open", "bwams_sorter_put", "bwams_sorter_put_batch", "bwams_sorter_close",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
@@ -76,6 +78,7 @@ ALN_DTYPE = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("flag", "<i4"), ("is_rev"
                       ("NM", "<i4"), ("n_cigar", "<i4"), ("md_len", "<i4"), ("cigar_off", "<i8"), ("md_off", "<i8"),
                       ("score", "<i4"), ("sub", "<i4"), ("alt_sc", "<i4"), ("pad_", "<i4")])
 assert ALN_DTYPE.itemsize == 72
+BAM_COORD_DTYPE = np.dtype([("key", "<u8"), ("end", "<i4"), ("size", "<i4")])      # bwams_bam_coord_t
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
 
@@ -301,6 +304,47 @@ def writer_open_bam(path: str, n_shards: int, device: int, bam_header: bytes) ->
     return w
 
 
+SORT_BAI = 0x1                   # BWAMS_SORT_BAI: also write <path>.bai
+
+
+class SorterStats(C.Structure):
+    _fields_ = [("runs", C.c_int64), ("records", C.c_int64), ("spilled_runs", C.c_int64), ("spilled_bytes", C.c_int64),
+                ("out_bytes", C.c_int64), ("ms_merge", C.c_float), ("ms_deflate", C.c_float), ("ms_write", C.c_float)]
+
+
+class Sorter:
+    """A coordinate-sorted BAM file (and its .bai) from sorted runs (bwams_sorter_t)."""
+
+    def __init__(self, path: str, device: int, bam_header: bytes, tmp_prefix: str | None = None, mem_bytes: int = 4 << 30,
+                 bai: bool = True):
+        self.h = C.c_void_p()
+        hdr = bytes(bam_header)
+        _chk(lib().bwams_sorter_open(path.encode(), device, hdr, len(hdr), tmp_prefix.encode() if tmp_prefix else None, mem_bytes,
+                                     SORT_BAI if bai else 0, C.byref(self.h)), "bwams_sorter_open")
+
+    def put(self, seq: int, records: bytes, coords) -> None:
+        """One sorted run: records (bytes) and their coords (BAM_COORD_DTYPE)."""
+        records = bytes(records)
+        coords = np.ascontiguousarray(coords, BAM_COORD_DTYPE)
+        _chk(lib().bwams_sorter_put(self.h, seq, records, len(records), _p(coords), len(coords)), "bwams_sorter_put")
+
+    def put_batch(self, seq: int, batch: "Batch") -> None:
+        _chk(lib().bwams_sorter_put_batch(self.h, seq, batch.h), "bwams_sorter_put_batch")
+
+    def close(self) -> SorterStats:
+        st = SorterStats()
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_sorter_close(h, C.byref(st)), "bwams_sorter_close")
+        return st
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def reader_open_device(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0,
                        n_buffers: int = 2) -> C.c_void_p:
     """bwams_reader_open_device: a bwams_reader_t handle (bwams_reader_next / _release / _close as for bwams_reader_open)."""
@@ -411,6 +455,13 @@ def lib():
         L.bwams_sam_header.argtypes = [vp, C.c_char_p, C.c_char_p, vp, i64, vp]
         L.bwams_bam_header.argtypes = [vp, C.c_char_p, i64, vp, i64, vp]
         L.bwams_writer_open_bam.argtypes = [C.c_char_p, i32, C.c_int, C.c_char_p, i64, vp]
+        L.bwams_bam_upload.argtypes = [vp, vp, i64, vp]
+        L.bwams_bam_sort.argtypes = [vp, vp]
+        L.bwams_bam_sorted_fetch.argtypes = [vp, vp, i64, vp]
+        L.bwams_sorter_open.argtypes = [C.c_char_p, C.c_int, vp, i64, C.c_char_p, i64, i32, vp]
+        L.bwams_sorter_put.argtypes = [vp, i64, vp, i64, vp, i64]
+        L.bwams_sorter_put_batch.argtypes = [vp, i64, vp]
+        L.bwams_sorter_close.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
@@ -1119,10 +1170,37 @@ class Batch:
         nb, nr = C.c_int64(0), C.c_int64(0)
         _chk(lib().bwams_bam_run(self.h, C.byref(nb), C.byref(nr)), "bwams_bam_run")
         self._bam_bytes = nb.value
+        self._bam_uploaded = None
         return nb.value, nr.value
 
+    def bam_upload(self, records: bytes) -> int:
+        """Host BAM records (block_size included, back to back) become the batch's records (bwams_bam_upload): their number."""
+        records = bytes(records)
+        n = C.c_int64(0)
+        _chk(lib().bwams_bam_upload(self.h, records, len(records), C.byref(n)), "bwams_bam_upload")
+        self._bam_bytes = len(records)
+        self._bam_uploaded = n.value
+        return n.value
+
+    def bam_sort(self) -> int:
+        """The batch's BAM records in coordinate order, on the device (bwams_bam_sort): their number."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_bam_sort(self.h, C.byref(n)), "bwams_bam_sort")
+        self._bam_sorted = n.value
+        return n.value
+
+    def bam_sorted_fetch(self):
+        """(sorted records as bytes, their coords as a BAM_COORD_DTYPE array) of the last bam_sort."""
+        buf = np.empty(max(self._bam_bytes, 1), np.uint8)
+        coords = np.zeros(max(self._bam_sorted, 1), BAM_COORD_DTYPE)
+        _chk(lib().bwams_bam_sorted_fetch(self.h, _p(buf), len(buf), _p(coords)), "bwams_bam_sorted_fetch")
+        return buf[:self._bam_bytes].tobytes(), coords[:self._bam_sorted]
+
     def bam_fetch(self, n_reads: int | None = None):
-        """(records of the last bam_run, n + 1 per-read offsets); n_reads defaults to the reads of the last SAM run."""
+        """(records of the last bam_run, n + 1 per-read offsets); n_reads defaults to the reads of the last SAM run (after a
+        bam_upload: its records, each counted as one read)."""
+        if n_reads is None and getattr(self, "_bam_uploaded", None) is not None:
+            n_reads = self._bam_uploaded
         n = self._nseq if n_reads is None else n_reads
         buf = np.empty(max(self._bam_bytes, 1), np.uint8)
         off = np.zeros(n + 1, np.int64)

@@ -50,6 +50,10 @@ struct ChainState {
     DevBuf bm_size, bm_roff, bm_off, bm_out, bm_bad;   // BAM records of the SAM text (bwams_bam_run)
     int64_t bm_bytes = 0, bm_nrec = 0, bm_nseq = 0;
     bool bm_done = false;                // bm_* hold the BAM of the current SAM text (every change of sm_done clears it)
+    uint32_t bm_nref = 0;                // refIDs of bm_* lie in [-1, bm_nref): the index's sequences, or what bwams_bam_upload found
+    DevBuf bs_out, bs_coord, bs_coord0, bs_keys, bs_keys2, bs_idx, bs_idx2, bs_size, bs_off;   // the records sorted (bwams_bam_sort)
+    int64_t bs_bytes = 0, bs_nrec = 0;
+    bool bs_done = false;                // bs_* hold the sort of the current bm_* (cleared wherever bm_done is)
     int64_t n_final = 0;
     bool dedup_done = false;
     int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_chain_redo = 0;
@@ -1309,7 +1313,7 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
         set_last_error("bwams_sam_upload: offsets start at 0");
         return BWAMS_ERR_ARG;
     }
-    s->sm_up = s->sm_done = s->bm_done = false;
+    s->sm_up = s->sm_done = s->bm_done = s->bs_done = false;
     BWAMS_HIP(s->sm_names.ensure((size_t)name_off[nseq] + 16));
     BWAMS_HIP(s->sm_noff.ensure((size_t)n1 * 8));
     BWAMS_HIP(hipMemcpyAsync(s->sm_names.p, names, (size_t)name_off[nseq], hipMemcpyDefault, st));
@@ -1365,7 +1369,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     if (!memchr(sopt->rg_id, 0, sizeof sopt->rg_id)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    s->sm_done = s->bm_done = false; s->sm_merged_n = -1;
+    s->sm_done = s->bm_done = s->bs_done = false; s->sm_merged_n = -1;
     const int64_t nseq = s->nseq, n1 = nseq + 1, n = s->al_n;
     constexpr int kLogN = 1 << 16;
     if (!s->sm_log_ok) {                                   // log(i) with the C library's log, as the reference's host code computes it
@@ -1437,7 +1441,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     launch_sam_text(A, true, b->cu_count, st);
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
-    s->sm_bytes = total; s->sm_nregs = n; s->sm_done = true; s->bm_done = false;
+    s->sm_bytes = total; s->sm_nregs = n; s->sm_done = true; s->bm_done = s->bs_done = false;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
 }
@@ -1507,7 +1511,8 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     ChainState *s = b->chain;
     BWAMS_HIP(hipSetDevice(ix->device));
     hipStream_t st = b->stream;
-    s->bm_done = false;
+    s->bm_done = s->bs_done = false;
+    s->bm_nref = (uint32_t)ix->n_seqs;
     const int64_t nseq = s->sm_merged_n >= 0 ? s->sm_merged_n : s->nseq;
     DevBuf<int64_t> ends;
     int64_t n_rec = 0;
@@ -1593,6 +1598,122 @@ int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64
     return deflater_run_after(d, b->stream, s->bm_out.p, s->bm_bytes, 1, out, cap, 0, flags, n_out, nullptr);
 }
 
+/* ------------------------------------------------------------ BAM coordinate sort (bam_sort.hip) ---- */
+
+int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t *n_records) {
+    if (!b || n_bytes < 0 || (n_bytes && !bam)) {
+        set_last_error("bwams_bam_upload: a batch and host records are required");
+        return BWAMS_ERR_ARG;
+    }
+    const uint8_t *p = static_cast<const uint8_t *>(bam);
+    auto i32 = [&](int64_t at) { int32_t v; memcpy(&v, p + at, 4); return v; };
+    std::vector<int64_t> off(1, 0);
+    int32_t max_rid = -1;
+    for (int64_t at = 0; at < n_bytes;) {                   // the block_size chain, and what the key kernel reads inside it
+        const int64_t k = (int64_t)off.size() - 1;
+        if (n_bytes - at < 4) { set_last_error("bwams_bam_upload: record " + std::to_string(k) + " is cut off"); return BWAMS_ERR_ARG; }
+        const int64_t bs = (uint32_t)i32(at);
+        if (bs < 32 || bs > n_bytes - at - 4) {
+            set_last_error("bwams_bam_upload: record " + std::to_string(k) + ": block_size " + std::to_string(bs) +
+                           (bs < 32 ? " < 32" : " runs past n_bytes"));
+            return BWAMS_ERR_ARG;
+        }
+        const int32_t rid = i32(at + 4), pos = i32(at + 8);
+        const int64_t l_name = p[at + 12], n_cig = (int64_t)p[at + 16] | (int64_t)p[at + 17] << 8;
+        if (rid < -1 || pos < -1 || pos > 0x7FFFFFFE || 32 + l_name + 4 * n_cig > bs) {
+            set_last_error("bwams_bam_upload: record " + std::to_string(k) + ": refID < -1, POS outside [-1, 2^31 - 2], or its name and CIGAR "
+                           "run past block_size");
+            return BWAMS_ERR_ARG;
+        }
+        max_rid = std::max(max_rid, rid);
+        at += 4 + bs;
+        off.push_back(at);
+    }
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    ChainState *s;
+    int rc = get_state(b, &s);
+    if (rc) return rc;
+    hipStream_t st = b->stream;
+    const int64_t n_rec = (int64_t)off.size() - 1;
+    s->bm_done = s->bs_done = false;
+    BWAMS_HIP(hipStreamSynchronize(st));                     // the buffers below may still be read by queued work
+    BWAMS_HIP(s->bm_out.ensure((size_t)n_bytes + 16));
+    BWAMS_HIP(s->bm_roff.ensure((size_t)(n_rec + 1) * 8));
+    BWAMS_HIP(s->bm_off.ensure((size_t)(n_rec + 1) * 8));
+    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(s->bm_out.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(s->bm_roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(s->bm_off.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    s->bm_bytes = n_bytes; s->bm_nrec = n_rec; s->bm_nseq = n_rec; s->bm_nref = (uint32_t)(max_rid + 1); s->bm_done = true;
+    if (n_records) *n_records = n_rec;
+    return BWAMS_OK;
+}
+
+int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records) {
+    if (!b || !b->chain || !b->chain->bm_done) {
+        set_last_error("bwams_bam_sort: run bwams_bam_run or bwams_bam_upload first");
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    if (s->bs_done) {
+        if (n_records) *n_records = s->bs_nrec;
+        return BWAMS_OK;
+    }
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t st = b->stream;
+    const int64_t n = s->bm_nrec;
+    if (n > 0xFFFFFFFFLL) {
+        set_last_error("bwams_bam_sort: more than 2^32 records");
+        return BWAMS_ERR_UNSUPPORTED;
+    }
+    BWAMS_HIP(s->bs_out.ensure((size_t)s->bm_bytes + 16));
+    BWAMS_HIP(s->bs_coord.ensure((size_t)(n + 1) * sizeof(bwams_bam_coord_t)));
+    BWAMS_HIP(s->bs_coord0.ensure((size_t)(n + 1) * sizeof(bwams_bam_coord_t)));
+    BWAMS_HIP(s->bs_keys.ensure((size_t)(n + 1) * 8)); BWAMS_HIP(s->bs_keys2.ensure((size_t)(n + 1) * 8));
+    BWAMS_HIP(s->bs_idx.ensure((size_t)(n + 1) * 4)); BWAMS_HIP(s->bs_idx2.ensure((size_t)(n + 1) * 4));
+    BWAMS_HIP(s->bs_size.ensure((size_t)(n + 1) * 8)); BWAMS_HIP(s->bs_off.ensure((size_t)(n + 1) * 8));
+    if (n > 0) {
+        const uint8_t *src = s->bm_out.as<const uint8_t>();
+        const int64_t *roff = s->bm_roff.as<const int64_t>();
+        launch_bam_sort_keys(src, roff, n, s->bm_nref, s->bs_coord0.as<bwams_bam_coord_t>(), s->bs_keys.as<uint64_t>(),
+                             s->bs_idx.as<uint32_t>(), b->cu_count, st);
+        const unsigned bits = (unsigned)bam_sort_bits(s->bm_nref);
+        size_t tb = 0;
+        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, s->bs_keys.as<uint64_t>(), s->bs_keys2.as<uint64_t>(), s->bs_idx.as<uint32_t>(),
+                                            s->bs_idx2.as<uint32_t>(), (size_t)n, 0u, bits, st));
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp.p, tb, s->bs_keys.as<uint64_t>(), s->bs_keys2.as<uint64_t>(), s->bs_idx.as<uint32_t>(),
+                                            s->bs_idx2.as<uint32_t>(), (size_t)n, 0u, bits, st));
+        const uint32_t *idx = s->bs_idx2.as<const uint32_t>();
+        BWAMS_HIP(hipMemsetAsync(s->bs_size.as<int64_t>() + n, 0, 8, st));
+        launch_bam_sort_permute(s->bs_coord0.as<const bwams_bam_coord_t>(), idx, n, s->bs_coord.as<bwams_bam_coord_t>(),
+                                s->bs_size.as<int64_t>(), b->cu_count, st);
+        if (int rc = scan_rows(b, s->bs_size.as<int64_t>(), s->bs_off.as<int64_t>(), 1, n + 1)) return rc;
+        launch_bam_sort_gather(src, roff, idx, s->bs_off.as<const int64_t>(), n, s->bs_out.as<uint8_t>(), b->cu_count, st);
+        BWAMS_HIP(hipGetLastError());
+    }
+    BWAMS_HIP(hipStreamSynchronize(st));
+    s->bs_bytes = s->bm_bytes; s->bs_nrec = n; s->bs_done = true;
+    if (n_records) *n_records = n;
+    return BWAMS_OK;
+}
+
+int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_coord_t *coords) {
+    if (!b || !b->chain || !b->chain->bm_done || !b->chain->bs_done) {
+        set_last_error("bwams_bam_sorted_fetch: run bwams_bam_sort first");
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    if (bam && s->bs_bytes > cap) return BWAMS_ERR_CAPACITY;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t st = b->stream;
+    if (bam && s->bs_bytes) BWAMS_HIP(hipMemcpyAsync(bam, s->bs_out.p, (size_t)s->bs_bytes, hipMemcpyDeviceToHost, st));
+    if (coords && s->bs_nrec)
+        BWAMS_HIP(hipMemcpyAsync(coords, s->bs_coord.p, (size_t)s->bs_nrec * sizeof(bwams_bam_coord_t), hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    return BWAMS_OK;
+}
+
 /* ------------------------------------------------------------ mem_process_seqs ---- */
 
 // The outer boundary for one chunk, text to text: what kt_pipeline's step 0 parsing and step 1 (mem_process_seqs, src/bwamem.cpp:1850-1980)
@@ -1631,7 +1752,7 @@ static int process_stage2(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, 
 }
 
 static void process_empty(bwams_batch_t *b, int64_t *sam_bytes) {      // an empty chunk: no reads, no text
-    if (b->chain) { b->chain->sm_done = true; b->chain->bm_done = false; b->chain->sm_bytes = 0; b->chain->sm_nregs = 0; b->chain->nseq = 0; b->chain->sm_merged_n = -1; }
+    if (b->chain) { b->chain->sm_done = true; b->chain->bm_done = b->chain->bs_done = false; b->chain->sm_bytes = 0; b->chain->sm_nregs = 0; b->chain->nseq = 0; b->chain->sm_merged_n = -1; }
     b->nseq = 0;
     if (sam_bytes) *sam_bytes = 0;
 }
@@ -1869,7 +1990,7 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     if ((rc = segment_copy(mv, st))) return rc;
     BWAMS_HIP(hipMemcpyAsync(s->sm_off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->sm_bytes = total; s->sm_nregs = 0; s->sm_merged_n = n; s->sm_done = true; s->bm_done = false;
+    s->sm_bytes = total; s->sm_nregs = 0; s->sm_merged_n = n; s->sm_done = true; s->bm_done = s->bs_done = false;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
 }
@@ -1940,7 +2061,7 @@ int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
     std::swap(s->dd_off, s->mg_off);
     s->n_final = total;
     s->er_done = false;                                   // merged: a second call would add them again
-    s->pair_done = s->al_done = s->sm_done = s->bm_done = false;
+    s->pair_done = s->al_done = s->sm_done = s->bm_done = s->bs_done = false;
     if (n_regs) *n_regs = total;
     return BWAMS_OK;
 }

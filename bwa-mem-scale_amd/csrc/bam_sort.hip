@@ -1,0 +1,129 @@
+// bam_sort.hip — a batch's BAM records in coordinate order, sorted where they lie (bwams_bam_sort).
+//
+// The order is bwams_bam_coord_t's key (include/bwams_types.h): refID (-1 last), POS, the reverse-strand bit; ties keep their input
+// order.  Three launches and a rocPRIM sort, all memory-bound:
+//   bam_sort_key_kernel     lane per record: reads refID, POS, FLAG and the CIGAR at rec_off[r], writes the published coord (key,
+//                           end, size) and the DEVICE key, in which refID -1 is n_ref, so that the radix sort runs over
+//                           32 + bit_width(n_ref) bits instead of 64 (the published key keeps 0xFFFFFFFF);
+//   rocprim::radix_sort_pairs (device key, record index): stable, as the order needs;
+//   bam_sort_permute_kernel lane per sorted slot: the coord of its record, and its size for the exclusive scan (scan_rows);
+//   bam_sort_gather_kernel  sixteen lanes per record copy it from rec_off[idx[i]] to new_off[i]: its head bytes up to the next
+//                           16-byte boundary of the destination and its tail bytes one a lane; the body as aligned 16-byte stores,
+//                           each built from aligned dword loads of the source shifted into place (v_alignbyte), since records are
+//                           not 4-byte aligned in general.  Every byte is read once and written once.
+// A record's bytes are only written inside its own range, so the head and tail bytes, which share a dword with the next record,
+// never race.  The source buffer holds 16 bytes of slack past its last record (bwams_bam_run / _upload allocate it), so the
+// aligned loads that reach past a record's end stay in bounds.
+#include <algorithm>
+#include <cstring>
+#include "common.h"
+
+namespace bwams {
+namespace {
+
+constexpr int kGroup = 16;
+
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) {          // little-endian, any alignment
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+__global__ void __launch_bounds__(256) bam_sort_key_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, uint32_t n_ref,
+                                                           bwams_bam_coord_t *coord, uint64_t *dkey, uint32_t *idx) {
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
+        const uint8_t *p = bam + rec_off[r];
+        const uint32_t block_size = ld_u32(p);
+        const int32_t rid = (int32_t)ld_u32(p + 4), pos = (int32_t)ld_u32(p + 8);
+        const uint32_t l_name = p[12];
+        const uint32_t n_cig = (uint32_t)p[16] | (uint32_t)p[17] << 8;
+        const uint32_t flag = (uint32_t)p[18] | (uint32_t)p[19] << 8;
+        int64_t rlen = 0;
+        const uint8_t *c = p + 36 + l_name;
+        for (uint32_t k = 0; k < n_cig; ++k) {
+            const uint32_t op = ld_u32(c + 4 * k);
+            const uint32_t o = op & 15;
+            if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rlen += op >> 4;
+        }
+        const int64_t end = ((flag & 4) || n_cig == 0 || rlen == 0) ? (int64_t)pos + 1 : (int64_t)pos + rlen;
+        const uint64_t low = (uint64_t)(uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1);
+        bwams_bam_coord_t cd;
+        cd.key = (uint64_t)(uint32_t)rid << 32 | low;
+        cd.end = (int32_t)end;
+        cd.size = (int32_t)(block_size + 4);
+        coord[r] = cd;
+        dkey[r] = (uint64_t)(rid < 0 ? n_ref : (uint32_t)rid) << 32 | low;
+        idx[r] = (uint32_t)r;
+    }
+}
+
+__global__ void __launch_bounds__(256) bam_sort_permute_kernel(const bwams_bam_coord_t *coord, const uint32_t *idx, int64_t n_rec,
+                                                               bwams_bam_coord_t *coord_out, int64_t *size) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += (int64_t)gridDim.x * blockDim.x) {
+        const bwams_bam_coord_t cd = coord[idx[i]];
+        coord_out[i] = cd;
+        size[i] = cd.size;
+    }
+}
+
+__global__ void __launch_bounds__(256) bam_sort_gather_kernel(const uint8_t *src, const int64_t *rec_off, const uint32_t *idx,
+                                                              const int64_t *new_off, int64_t n_rec, uint8_t *dst) {
+    const int g = (int)(threadIdx.x & (kGroup - 1));
+    const int64_t n_groups = (int64_t)gridDim.x * (blockDim.x / kGroup);
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroup; i < n_rec; i += n_groups) {
+        const int64_t s = rec_off[idx[i]], d = new_off[i], n = new_off[i + 1] - d;
+        const int64_t head = std::min<int64_t>((16 - (d & 15)) & 15, n);
+        const int64_t body = (n - head) & ~(int64_t)15;
+        const int64_t tail = n - head - body;
+        if (g < head) dst[d + g] = src[s + g];
+        if (g < tail) dst[d + head + body + g] = src[s + head + body + g];
+        const int64_t s0 = s + head;                         // source of the body's first byte
+        const unsigned a = (unsigned)(s0 & 3);
+        const uint32_t *sw = reinterpret_cast<const uint32_t *>(src + (s0 - a));
+        uint4 *dw = reinterpret_cast<uint4 *>(dst + d + head);
+        for (int64_t k = g; k < body / 16; k += kGroup) {
+            const uint32_t *q = sw + 4 * k;
+            uint4 v;
+            if (a == 0) {
+                v.x = q[0]; v.y = q[1]; v.z = q[2]; v.w = q[3];
+            } else {
+                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4];
+                v.x = __builtin_amdgcn_alignbyte(w1, w0, a);
+                v.y = __builtin_amdgcn_alignbyte(w2, w1, a);
+                v.z = __builtin_amdgcn_alignbyte(w3, w2, a);
+                v.w = __builtin_amdgcn_alignbyte(w4, w3, a);
+            }
+            dw[k] = v;
+        }
+    }
+}
+
+unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
+    int64_t g = (items + per_block - 1) / per_block;
+    const int64_t cap = (int64_t)cu_count * 16;
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+}  // namespace
+
+int bam_sort_bits(uint32_t n_ref) {                          // bits of the device key: POS + 1 and the strand, then refID in [0, n_ref]
+    int w = 0;
+    while (w < 32 && (n_ref >> w) != 0) ++w;
+    return 32 + w;
+}
+
+void launch_bam_sort_keys(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, uint32_t n_ref, bwams_bam_coord_t *coord,
+                          uint64_t *dkey, uint32_t *idx, int cu_count, hipStream_t st) {
+    if (n_rec > 0) bam_sort_key_kernel<<<grid_of(n_rec, 256, cu_count), 256, 0, st>>>(bam, rec_off, n_rec, n_ref, coord, dkey, idx);
+}
+
+void launch_bam_sort_permute(const bwams_bam_coord_t *coord, const uint32_t *idx, int64_t n_rec, bwams_bam_coord_t *coord_out,
+                             int64_t *size, int cu_count, hipStream_t st) {
+    if (n_rec > 0) bam_sort_permute_kernel<<<grid_of(n_rec, 256, cu_count), 256, 0, st>>>(coord, idx, n_rec, coord_out, size);
+}
+
+void launch_bam_sort_gather(const uint8_t *src, const int64_t *rec_off, const uint32_t *idx, const int64_t *new_off, int64_t n_rec,
+                            uint8_t *dst, int cu_count, hipStream_t st) {
+    if (n_rec > 0)
+        bam_sort_gather_kernel<<<grid_of(n_rec, 256 / kGroup, cu_count), 256, 0, st>>>(src, rec_off, idx, new_off, n_rec, dst);
+}
+
+}  // namespace bwams

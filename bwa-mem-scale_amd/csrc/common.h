@@ -194,6 +194,18 @@ struct BamArgs {
 void launch_bam_count(const BamArgs &A, int cu_count, hipStream_t st);
 void launch_bam_write(const BamArgs &A, int64_t *bam_off, int cu_count, hipStream_t st);
 
+// bam_sort.hip: coordinate sort of n_rec records at bam + rec_off[r] (the buffer holds 16 bytes of slack past the last record).
+// keys: coord[r] (the published order) and dkey[r] (refID -1 as n_ref: bam_sort_bits(n_ref) significant bits), idx[r] = r; then,
+// after the radix sort of (dkey, idx), permute: coord_out[i] = coord[idx[i]], size[i] its size (scan it into new_off[n_rec + 1]);
+// gather: the record idx[i] to dst + new_off[i].
+int bam_sort_bits(uint32_t n_ref);
+void launch_bam_sort_keys(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, uint32_t n_ref, bwams_bam_coord_t *coord,
+                          uint64_t *dkey, uint32_t *idx, int cu_count, hipStream_t st);
+void launch_bam_sort_permute(const bwams_bam_coord_t *coord, const uint32_t *idx, int64_t n_rec, bwams_bam_coord_t *coord_out,
+                             int64_t *size, int cu_count, hipStream_t st);
+void launch_bam_sort_gather(const uint8_t *src, const int64_t *rec_off, const uint32_t *idx, const int64_t *new_off, int64_t n_rec,
+                            uint8_t *dst, int cu_count, hipStream_t st);
+
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);
 int deflater_run_after(bwams_deflater *d, hipStream_t after, const void *in, int64_t n_bytes, int in_on_device, void *out, int64_t out_cap,

@@ -376,6 +376,19 @@ int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off)
 /* The records compressed where they lie, as bwams_sam_fetch_bgzf compresses the text (BWAMS_DEFLATE_EOF; a record may span two
  * members, which SAMv1 §4.1 allows). */
 int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out);
+/* Coordinate sort of the batch's BAM records where they lie (csrc/bam_sort.hip), in the order bwams_bam_coord_t's key defines
+ * (include/bwams_types.h; bwams/bam.py restates it).
+ * _upload: host records bam[0, n_bytes) become the batch's records, as if bwams_bam_run had made them (any BAM, e.g. another
+ * aligner's; a fresh batch will do).  The block_size chain is checked: every record has block_size >= 32, its name and CIGAR
+ * inside it, refID >= -1 and -1 <= POS <= 2^31 - 2, and the chain ends exactly at n_bytes; BWAMS_ERR_ARG otherwise, nothing kept.
+ * After an upload each record counts as one read: bwams_bam_fetch's read_off holds n_records + 1 entries, the records' offsets.
+ * _sort: BWAMS_ERR_ARG before any bwams_bam_run or _upload.  The unsorted records (bwams_bam_fetch, _fetch_bgzf) stay as they are;
+ * a second call on records it has sorted already returns at once.  *n_records may be NULL.
+ * _sorted_fetch: the sorted records (cap >= the bytes of bwams_bam_run / _upload, BWAMS_ERR_CAPACITY otherwise) and their
+ * n_records coords in sorted order; either pointer may be NULL.  BWAMS_ERR_ARG before a _sort of the current records. */
+int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t *n_records);
+int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records);
+int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_coord_t *coords);
 /* bwa_print_sam_hdr into out[0, cap): "@SQ\tSN:<name>\tLN:<len>" per sequence ("\tAH:*" for ALT sequences) unless hdr_line holds @SQ
  * lines of its own; then hdr_line and a newline (mem -H text and the @RG line, as main_mem builds it); then pg_line as given (it carries
  * its own newline).  hdr_line / pg_line may be NULL.  *n_out: the bytes written, or needed with BWAMS_ERR_CAPACITY. */
@@ -746,6 +759,26 @@ int bwams_writer_put_bgzf(bwams_writer_t *w, int32_t shard, int64_t seq, const u
  * the members of bwams_writer_put_bgzf (e.g. from bwams_bam_fetch_bgzf, without the EOF member) in sequence order; bwams_writer_close
  * appends the EOF member.  bwams_writer_put (text) on a BAM writer is BWAMS_ERR_ARG. */
 int bwams_writer_open_bam(const char *path, int32_t n_shards, int device, const void *bam_header, int64_t n, bwams_writer_t **out);
+/* A coordinate-sorted BAM file and, with BWAMS_SORT_BAI, its index <path>.bai (SAMv1 §5.2): what `samtools sort` and
+ * `samtools index` make of the unsorted stream (host/bam_sort.cpp).  Each put is one sorted run tagged with its sequence number
+ * `seq` (the run's place in input order); any thread may put, in any order.  Runs stay in host memory up to mem_bytes and are
+ * spilled raw beyond that to "<tmp_prefix>.<n>.run" (tmp_prefix NULL: "<path>.tmp"); close removes them, on success and on error.
+ * _put: records[0, n_bytes) with their coords (as bwams_bam_sorted_fetch returns them); BWAMS_ERR_ARG for keys out of order, sizes
+ * that do not chain the records to n_bytes, a refID >= the header's n_ref, an end past 2^29 with BWAMS_SORT_BAI, or a seq put before.
+ * _put_batch: bwams_bam_sort on the batch (at once when it is sorted already), its records fetched straight into the run.
+ * _close: k-way merge by (key, seq, index in the run); the header block (bwams_bam_header's) in members of its own, then the merged
+ * records cut every 65280 bytes from their first byte into members made by a deflater on `device`, then the EOF member.  The
+ * bytes of the file and of the index depend only on the records and their seq numbers (not on put order, threads, mem_bytes or
+ * spilling); bwams/bai.py restates the index.  BWAMS_SORT_BAI with a reference longer than 2^29 bases: BWAMS_ERR_UNSUPPORTED at
+ * open (BAI cannot hold it). */
+typedef struct bwams_sorter bwams_sorter_t;
+#define BWAMS_SORT_BAI 0x1                       /* also write <path>.bai */
+int bwams_sorter_open(const char *path, int device, const void *bam_header, int64_t n_header, const char *tmp_prefix, int64_t mem_bytes,
+                      int32_t flags, bwams_sorter_t **out);
+int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_t n_bytes, const bwams_bam_coord_t *coords,
+                     int64_t n_records);
+int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b);
+int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats);   /* stats may be NULL */
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -239,6 +239,23 @@ typedef struct bwams_sam_opt {
     char    rg_id[256];         /* "" = no RG:Z tag */
 } bwams_sam_opt_t;
 
+/* One BAM record's place in coordinate order (samtools sort's default): key = (uint64)(uint32)refID << 32 |
+ * (uint64)(uint32)(pos + 1) << 1 | (FLAG & 0x10 ? 1 : 0) — refID -1 (unplaced) last, then POS, then the reverse-strand bit; records
+ * of equal key keep their input order.  end = pos + the CIGAR's reference length (M/D/N/=/X), or pos + 1 when the record is
+ * unmapped, has no CIGAR or a reference length of 0 (the end reg2bin takes); size = block_size + 4. */
+typedef struct bwams_bam_coord {
+    uint64_t key;
+    int32_t  end;
+    int32_t  size;
+} bwams_bam_coord_t;
+
+/* What bwams_sorter_close did: runs put, records merged, runs (and their bytes: records + coords) spilled to temporary files,
+ * the output's bytes, and host-clock milliseconds of the k-way merge, the deflate calls and the file writes. */
+typedef struct bwams_sorter_stats {
+    int64_t runs, records, spilled_runs, spilled_bytes, out_bytes;
+    float   ms_merge, ms_deflate, ms_write;
+} bwams_sorter_stats_t;
+
 #ifdef __cplusplus
 }
 #endif
