@@ -48,7 +48,8 @@ SYMBOLS = [
     "bwams_bam_run", "bwams_bam_fetch", "bwams_bam_fetch_bgzf", "bwams_sam_header", "bwams_bam_header", "bwams_writer_open_bam",
     "bwams_writer_open", "bwams_writer_put", "bwams_writer_close",
     "bwams_bam_upload", "bwams_bam_sort", "bwams_bam_sorted_fetch",
-    "bwams_sorter_open", "bwams_sorter_put", "bwams_sorter_put_batch", "bwams_sorter_close",
+    "bwams_sorter_open", "bwams_sorter_put", "bwams_sorter_put_batch", "bwams_sorter_close", "bwams_sorter_close2",
+    "bwams_bam_templates", "bwams_bam_templates_fetch", "bwams_dup_decide", "bwams_bam_markdup",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
@@ -79,6 +80,9 @@ ALN_DTYPE = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("flag", "<i4"), ("is_rev"
                       ("score", "<i4"), ("sub", "<i4"), ("alt_sc", "<i4"), ("pad_", "<i4")])
 assert ALN_DTYPE.itemsize == 72
 BAM_COORD_DTYPE = np.dtype([("key", "<u8"), ("end", "<i4"), ("size", "<i4")])      # bwams_bam_coord_t
+DUP_END_DTYPE = np.dtype([("tmpl", "<i8"), ("ref1", "<i4"), ("pos1", "<i4"), ("ref2", "<i4"), ("pos2", "<i4"), ("score", "<i4"),
+                          ("strands", "<i4")])                                    # bwams_dup_end_t
+assert DUP_END_DTYPE.itemsize == 32
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
 
@@ -305,6 +309,27 @@ def writer_open_bam(path: str, n_shards: int, device: int, bam_header: bytes) ->
 
 
 SORT_BAI = 0x1                   # BWAMS_SORT_BAI: also write <path>.bai
+SORT_MARKDUP = 0x2               # BWAMS_SORT_MARKDUP: mark duplicates over all puts
+
+
+class DupStats(C.Structure):
+    """bwams_dup_stats_t (rule 8 of duplicate marking)."""
+    _fields_ = [("templates", C.c_int64), ("unpaired_examined", C.c_int64), ("unpaired_duplicates", C.c_int64),
+                ("pairs_examined", C.c_int64), ("pair_duplicates", C.c_int64), ("records_marked", C.c_int64),
+                ("ms_decide", C.c_float), ("pad_", C.c_int32)]
+
+    def counts(self) -> dict:
+        """the counts as a dict (without ms_decide), to compare with bwams.markdup's stats"""
+        return {f: getattr(self, f) for f, _ in self._fields_ if f not in ("ms_decide", "pad_")}
+
+
+def dup_decide(device: int, ends, n_templates: int):
+    """Rule 6 on the device over ends (DUP_END_DTYPE) of n_templates templates (bwams_dup_decide) -> (dup: uint8 per template, DupStats)."""
+    ends = np.ascontiguousarray(ends, DUP_END_DTYPE)
+    dup = np.zeros(max(n_templates, 1), np.uint8)
+    st = DupStats()
+    _chk(lib().bwams_dup_decide(device, _p(ends), len(ends), n_templates, _p(dup), C.byref(st)), "bwams_dup_decide")
+    return dup[:n_templates], st
 
 
 class SorterStats(C.Structure):
@@ -316,11 +341,12 @@ class Sorter:
     """A coordinate-sorted BAM file (and its .bai) from sorted runs (bwams_sorter_t)."""
 
     def __init__(self, path: str, device: int, bam_header: bytes, tmp_prefix: str | None = None, mem_bytes: int = 4 << 30,
-                 bai: bool = True):
+                 bai: bool = True, markdup: bool = False):
         self.h = C.c_void_p()
         hdr = bytes(bam_header)
+        flags = (SORT_BAI if bai else 0) | (SORT_MARKDUP if markdup else 0)
         _chk(lib().bwams_sorter_open(path.encode(), device, hdr, len(hdr), tmp_prefix.encode() if tmp_prefix else None, mem_bytes,
-                                     SORT_BAI if bai else 0, C.byref(self.h)), "bwams_sorter_open")
+                                     flags, C.byref(self.h)), "bwams_sorter_open")
 
     def put(self, seq: int, records: bytes, coords) -> None:
         """One sorted run: records (bytes) and their coords (BAM_COORD_DTYPE)."""
@@ -332,10 +358,12 @@ class Sorter:
         _chk(lib().bwams_sorter_put_batch(self.h, seq, batch.h), "bwams_sorter_put_batch")
 
     def close(self) -> SorterStats:
-        st = SorterStats()
+        """bwams_sorter_close2: the sorter's stats, with the duplicate-marking counts as .dup (a DupStats, zeros without markdup)."""
+        st, dup = SorterStats(), DupStats()
         h, self.h = self.h, C.c_void_p()
         if h:
-            _chk(lib().bwams_sorter_close(h, C.byref(st)), "bwams_sorter_close")
+            _chk(lib().bwams_sorter_close2(h, C.byref(st), C.byref(dup)), "bwams_sorter_close2")
+        st.dup = dup
         return st
 
     def __del__(self):
@@ -462,6 +490,11 @@ def lib():
         L.bwams_sorter_put.argtypes = [vp, i64, vp, i64, vp, i64]
         L.bwams_sorter_put_batch.argtypes = [vp, i64, vp]
         L.bwams_sorter_close.argtypes = [vp, vp]
+        L.bwams_sorter_close2.argtypes = [vp, vp, vp]
+        L.bwams_bam_templates.argtypes = [vp, vp, vp]
+        L.bwams_bam_templates_fetch.argtypes = [vp, vp, i64, vp, i32]
+        L.bwams_dup_decide.argtypes = [C.c_int, vp, i64, i64, vp, vp]
+        L.bwams_bam_markdup.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
@@ -1171,6 +1204,7 @@ class Batch:
         _chk(lib().bwams_bam_run(self.h, C.byref(nb), C.byref(nr)), "bwams_bam_run")
         self._bam_bytes = nb.value
         self._bam_uploaded = None
+        self._bam_nrec = nr.value
         return nb.value, nr.value
 
     def bam_upload(self, records: bytes) -> int:
@@ -1180,6 +1214,7 @@ class Batch:
         _chk(lib().bwams_bam_upload(self.h, records, len(records), C.byref(n)), "bwams_bam_upload")
         self._bam_bytes = len(records)
         self._bam_uploaded = n.value
+        self._bam_nrec = n.value
         return n.value
 
     def bam_sort(self) -> int:
@@ -1195,6 +1230,29 @@ class Batch:
         coords = np.zeros(max(self._bam_sorted, 1), BAM_COORD_DTYPE)
         _chk(lib().bwams_bam_sorted_fetch(self.h, _p(buf), len(buf), _p(coords)), "bwams_bam_sorted_fetch")
         return buf[:self._bam_bytes].tobytes(), coords[:self._bam_sorted]
+
+    def bam_templates(self) -> tuple[int, int]:
+        """The batch's BAM records grouped into templates, their duplicate-marking ends on the device (bwams_bam_templates):
+        (templates, ends)."""
+        nt, ne = C.c_int64(0), C.c_int64(0)
+        _chk(lib().bwams_bam_templates(self.h, C.byref(nt), C.byref(ne)), "bwams_bam_templates")
+        self._md_ends = ne.value
+        return nt.value, ne.value
+
+    def bam_templates_fetch(self, sorted: bool = False):
+        """(ends as DUP_END_DTYPE, each record's template ordinal: in record order, or in bam_sort's order with sorted=True) of the
+        last bam_templates (bwams_bam_templates_fetch)."""
+        n_rec = self._bam_nrec
+        ends = np.zeros(max(self._md_ends, 1), DUP_END_DTYPE)
+        rt = np.zeros(max(n_rec, 1), np.uint32)
+        _chk(lib().bwams_bam_templates_fetch(self.h, _p(ends), len(ends), _p(rt), 1 if sorted else 0), "bwams_bam_templates_fetch")
+        return ends[:self._md_ends], rt[:n_rec]
+
+    def bam_markdup(self) -> "DupStats":
+        """Duplicate marking of the batch's BAM records where they lie, the unsorted records and the sorted copy (bwams_bam_markdup)."""
+        st = DupStats()
+        _chk(lib().bwams_bam_markdup(self.h, C.byref(st)), "bwams_bam_markdup")
+        return st
 
     def bam_fetch(self, n_reads: int | None = None):
         """(records of the last bam_run, n + 1 per-read offsets); n_reads defaults to the reads of the last SAM run (after a

@@ -1,6 +1,7 @@
 // api_chain.hip — C-ABI entry points of the chaining and chain-to-alignment stages
 // (include/bwams.h): launch sequences over chain.hip, ext_aln.hip and bsw_extend.hip on the
 // batch's stream.  No CPU fallback: every entry point runs HIP kernels or returns an error.
+#include <chrono>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -54,6 +55,10 @@ struct ChainState {
     DevBuf bs_out, bs_coord, bs_coord0, bs_keys, bs_keys2, bs_idx, bs_idx2, bs_size, bs_off;   // the records sorted (bwams_bam_sort)
     int64_t bs_bytes = 0, bs_nrec = 0;
     bool bs_done = false;                // bs_* hold the sort of the current bm_* (cleared wherever bm_done is)
+    MdTemplates md;                      // templates and ends of the current bm_* (bwams_bam_templates)
+    MdDecide mdd;                        // the decision's buffers (bwams_bam_markdup)
+    DevBuf md_dup, md_cnt, md_sorted;
+    bool md_done = false;                // md holds the templates of the current bm_* (cleared wherever bm_done is)
     int64_t n_final = 0;
     bool dedup_done = false;
     int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_chain_redo = 0;
@@ -1313,7 +1318,7 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
         set_last_error("bwams_sam_upload: offsets start at 0");
         return BWAMS_ERR_ARG;
     }
-    s->sm_up = s->sm_done = s->bm_done = s->bs_done = false;
+    s->sm_up = s->sm_done = s->bm_done = s->bs_done = s->md_done = false;
     BWAMS_HIP(s->sm_names.ensure((size_t)name_off[nseq] + 16));
     BWAMS_HIP(s->sm_noff.ensure((size_t)n1 * 8));
     BWAMS_HIP(hipMemcpyAsync(s->sm_names.p, names, (size_t)name_off[nseq], hipMemcpyDefault, st));
@@ -1369,7 +1374,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     if (!memchr(sopt->rg_id, 0, sizeof sopt->rg_id)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    s->sm_done = s->bm_done = s->bs_done = false; s->sm_merged_n = -1;
+    s->sm_done = s->bm_done = s->bs_done = s->md_done = false; s->sm_merged_n = -1;
     const int64_t nseq = s->nseq, n1 = nseq + 1, n = s->al_n;
     constexpr int kLogN = 1 << 16;
     if (!s->sm_log_ok) {                                   // log(i) with the C library's log, as the reference's host code computes it
@@ -1441,7 +1446,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     launch_sam_text(A, true, b->cu_count, st);
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
-    s->sm_bytes = total; s->sm_nregs = n; s->sm_done = true; s->bm_done = s->bs_done = false;
+    s->sm_bytes = total; s->sm_nregs = n; s->sm_done = true; s->bm_done = s->bs_done = s->md_done = false;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
 }
@@ -1511,7 +1516,7 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     ChainState *s = b->chain;
     BWAMS_HIP(hipSetDevice(ix->device));
     hipStream_t st = b->stream;
-    s->bm_done = s->bs_done = false;
+    s->bm_done = s->bs_done = s->md_done = false;
     s->bm_nref = (uint32_t)ix->n_seqs;
     const int64_t nseq = s->sm_merged_n >= 0 ? s->sm_merged_n : s->nseq;
     DevBuf<int64_t> ends;
@@ -1635,7 +1640,7 @@ int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t
     if (rc) return rc;
     hipStream_t st = b->stream;
     const int64_t n_rec = (int64_t)off.size() - 1;
-    s->bm_done = s->bs_done = false;
+    s->bm_done = s->bs_done = s->md_done = false;
     BWAMS_HIP(hipStreamSynchronize(st));                     // the buffers below may still be read by queued work
     BWAMS_HIP(s->bm_out.ensure((size_t)n_bytes + 16));
     BWAMS_HIP(s->bm_roff.ensure((size_t)(n_rec + 1) * 8));
@@ -1714,6 +1719,138 @@ int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_c
     return BWAMS_OK;
 }
 
+/* ------------------------------------------------------------ duplicate marking (markdup.hip) ---- */
+
+int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends) {
+    if (!b || !b->chain || !b->chain->bm_done) {
+        set_last_error("bwams_bam_templates: run bwams_bam_run or bwams_bam_upload first");
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    if (!s->md_done) {
+        if (s->bm_nrec > 0xFFFFFFFFLL) {
+            set_last_error("bwams_bam_templates: more than 2^32 - 1 records");
+            return BWAMS_ERR_UNSUPPORTED;
+        }
+        BWAMS_HIP(hipSetDevice(b->idx->device));
+        BWAMS_HIP(hipStreamSynchronize(b->stream));          // the buffers below may still be read by queued work
+        if (int rc = md_templates(s->md, s->bm_out.as<const uint8_t>(), s->bm_roff.as<const int64_t>(), s->bm_nrec, b->cu_count, b->stream))
+            return rc;
+        s->md_done = true;
+    }
+    if (n_templates) *n_templates = s->md.n_t;
+    if (n_ends) *n_ends = s->md.n_e;
+    return BWAMS_OK;
+}
+
+int bwams_bam_templates_fetch(bwams_batch_t *b, bwams_dup_end_t *ends, int64_t cap, uint32_t *rec_tmpl, int32_t sorted) {
+    if (!b || !b->chain || !b->chain->bm_done || !b->chain->md_done || (sorted && !b->chain->bs_done)) {
+        set_last_error("bwams_bam_templates_fetch: run bwams_bam_templates (and bwams_bam_sort for sorted = 1) on the current records first");
+        return BWAMS_ERR_ARG;
+    }
+    ChainState *s = b->chain;
+    if (ends && s->md.n_e > cap) return BWAMS_ERR_CAPACITY;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t st = b->stream;
+    const int64_t n = s->bm_nrec;
+    if (ends && s->md.n_e)
+        BWAMS_HIP(hipMemcpyAsync(ends, s->md.ends.p, (size_t)s->md.n_e * sizeof(bwams_dup_end_t), hipMemcpyDeviceToHost, st));
+    if (rec_tmpl && n) {
+        const uint32_t *src = s->md.rtmpl.as<const uint32_t>();
+        if (sorted) {
+            BWAMS_HIP(s->md_sorted.ensure((size_t)n * 4));
+            launch_md_gather32(src, s->bs_idx2.as<const uint32_t>(), n, s->md_sorted.as<uint32_t>(), b->cu_count, st);
+            src = s->md_sorted.as<const uint32_t>();
+        }
+        BWAMS_HIP(hipMemcpyAsync(rec_tmpl, src, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    }
+    BWAMS_HIP(hipStreamSynchronize(st));
+    BWAMS_HIP(hipGetLastError());
+    return BWAMS_OK;
+}
+
+int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, int64_t n_templates, uint8_t *dup, bwams_dup_stats_t *st) {
+    if (n_ends < 0 || n_templates < 0 || (n_ends && !ends) || (n_templates && !dup)) {
+        set_last_error("bwams_dup_decide: host ends and a dup array of n_templates bytes are required");
+        return BWAMS_ERR_ARG;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
+        set_last_error("bwams_dup_decide: no device " + std::to_string(device));
+        return BWAMS_ERR_DEVICE;
+    }
+    BWAMS_HIP(hipSetDevice(device));
+    int cus = 0;
+    BWAMS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    int64_t cnt[3] = {0, 0, 0};
+    {
+        hipStream_t q = nullptr;
+        BWAMS_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+        struct StreamGuard { hipStream_t q; ~StreamGuard() { (void)hipStreamDestroy(q); } } guard{q};
+        MdDecide w;
+        DevBuf<bwams_dup_end_t> d_ends;
+        DevBuf<uint8_t> d_dup;
+        BWAMS_HIP(d_ends.alloc((size_t)std::max<int64_t>(n_ends, 1) * sizeof(bwams_dup_end_t)));
+        BWAMS_HIP(d_dup.alloc((size_t)std::max<int64_t>(n_templates, 1)));
+        if (n_ends) BWAMS_HIP(hipMemcpyAsync(d_ends.p, ends, (size_t)n_ends * sizeof(bwams_dup_end_t), hipMemcpyHostToDevice, q));
+        if (int rc = md_decide(w, d_ends.p, n_ends, n_templates, d_dup.p, cnt, cus, q)) {
+            (void)hipStreamSynchronize(q);
+            return rc;
+        }
+        if (n_templates) BWAMS_HIP(hipMemcpyAsync(dup, d_dup.p, (size_t)n_templates, hipMemcpyDeviceToHost, q));
+        BWAMS_HIP(hipStreamSynchronize(q));
+    }
+    if (st) {
+        memset(st, 0, sizeof *st);
+        st->templates = n_templates;
+        st->pairs_examined = cnt[0];
+        st->unpaired_examined = n_ends - cnt[0];
+        st->pair_duplicates = cnt[1];
+        st->unpaired_duplicates = cnt[2];
+        st->ms_decide = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return BWAMS_OK;
+}
+
+int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st) {
+    int64_t n_t = 0, n_e = 0;
+    if (int rc = bwams_bam_templates(b, &n_t, &n_e)) return rc;
+    ChainState *s = b->chain;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t q = b->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    BWAMS_HIP(s->md_dup.ensure((size_t)std::max<int64_t>(n_t, 1)));
+    BWAMS_HIP(s->md_cnt.ensure(16));
+    int64_t cnt[3] = {0, 0, 0};
+    if (int rc = md_decide(s->mdd, s->md.ends.as<const bwams_dup_end_t>(), n_e, n_t, s->md_dup.as<uint8_t>(), cnt, b->cu_count, q)) return rc;
+    const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    unsigned long long *marked = s->md_cnt.as<unsigned long long>();
+    BWAMS_HIP(hipMemsetAsync(marked, 0, 16, q));
+    const int64_t n = s->bm_nrec;
+    const uint32_t *rt = s->md.rtmpl.as<const uint32_t>();
+    const uint8_t *dup = s->md_dup.as<const uint8_t>();
+    launch_md_apply(s->bm_out.as<uint8_t>(), s->bm_roff.as<const int64_t>(), nullptr, rt, dup, n, marked, b->cu_count, q);
+    if (s->bs_done)                                          // the sorted copy: record i is the unsorted record bs_idx2[i]
+        launch_md_apply(s->bs_out.as<uint8_t>(), s->bs_off.as<const int64_t>(), s->bs_idx2.as<const uint32_t>(), rt, dup, n, marked + 1,
+                        b->cu_count, q);
+    unsigned long long h[2] = {0, 0};
+    BWAMS_HIP(hipMemcpyAsync(h, marked, 16, hipMemcpyDeviceToHost, q));
+    BWAMS_HIP(hipStreamSynchronize(q));
+    BWAMS_HIP(hipGetLastError());
+    if (st) {
+        memset(st, 0, sizeof *st);
+        st->templates = n_t;
+        st->pairs_examined = cnt[0];
+        st->unpaired_examined = n_e - cnt[0];
+        st->pair_duplicates = cnt[1];
+        st->unpaired_duplicates = cnt[2];
+        st->records_marked = (int64_t)h[0];
+        st->ms_decide = ms;
+    }
+    return BWAMS_OK;
+}
+
 /* ------------------------------------------------------------ mem_process_seqs ---- */
 
 // The outer boundary for one chunk, text to text: what kt_pipeline's step 0 parsing and step 1 (mem_process_seqs, src/bwamem.cpp:1850-1980)
@@ -1752,7 +1889,7 @@ static int process_stage2(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, 
 }
 
 static void process_empty(bwams_batch_t *b, int64_t *sam_bytes) {      // an empty chunk: no reads, no text
-    if (b->chain) { b->chain->sm_done = true; b->chain->bm_done = b->chain->bs_done = false; b->chain->sm_bytes = 0; b->chain->sm_nregs = 0; b->chain->nseq = 0; b->chain->sm_merged_n = -1; }
+    if (b->chain) { b->chain->sm_done = true; b->chain->bm_done = b->chain->bs_done = b->chain->md_done = false; b->chain->sm_bytes = 0; b->chain->sm_nregs = 0; b->chain->nseq = 0; b->chain->sm_merged_n = -1; }
     b->nseq = 0;
     if (sam_bytes) *sam_bytes = 0;
 }
@@ -1990,7 +2127,7 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     if ((rc = segment_copy(mv, st))) return rc;
     BWAMS_HIP(hipMemcpyAsync(s->sm_off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->sm_bytes = total; s->sm_nregs = 0; s->sm_merged_n = n; s->sm_done = true; s->bm_done = s->bs_done = false;
+    s->sm_bytes = total; s->sm_nregs = 0; s->sm_merged_n = n; s->sm_done = true; s->bm_done = s->bs_done = s->md_done = false;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
 }
@@ -2061,7 +2198,7 @@ int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
     std::swap(s->dd_off, s->mg_off);
     s->n_final = total;
     s->er_done = false;                                   // merged: a second call would add them again
-    s->pair_done = s->al_done = s->sm_done = s->bm_done = s->bs_done = false;
+    s->pair_done = s->al_done = s->sm_done = s->bm_done = s->bs_done = s->md_done = false;
     if (n_regs) *n_regs = total;
     return BWAMS_OK;
 }

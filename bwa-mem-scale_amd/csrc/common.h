@@ -206,6 +206,31 @@ void launch_bam_sort_permute(const bwams_bam_coord_t *coord, const uint32_t *idx
 void launch_bam_sort_gather(const uint8_t *src, const int64_t *rec_off, const uint32_t *idx, const int64_t *new_off, int64_t n_rec,
                             uint8_t *dst, int cu_count, hipStream_t st);
 
+// markdup.hip: duplicate marking (rules in include/bwams.h above bwams_bam_templates).  md_templates groups n_rec records (at
+// bam + rec_off[r], 16 bytes of slack past the last) into templates: m.n_t templates, m.rtmpl[r] each record's, and the m.n_e ends
+// of the templates that have one, in template order, at m.ends; BWAMS_ERR_UNSUPPORTED (last error: the first record concerned) for
+// rules 2-3.  md_decide: rule 6 over device ends[0, n_e) into device dup[0, n_t) (zeroed first); counts = pairs, pair duplicates,
+// fragment duplicates.  launch_md_apply: FLAG 0x400 of the record at rec_off[i] from dup[rtmpl[perm ? perm[i] : i]] (*n_marked counts
+// the records set).  launch_md_gather32: dst[i] = src[idx[i]].
+struct MdRec {                           // one record as the template kernel reads it
+    int64_t c;                           // unclipped 5' coordinate of a mapped primary (rule 3), else 0
+    int32_t rid;
+    uint16_t flag, score;                // score: rule 4's, of a mapped primary
+};
+struct MdTemplates {
+    DevBuf<> head, tid, rtmpl, tstart, rec, tend, has, ends, info, tmp;
+    int64_t n_t = 0, n_e = 0;
+};
+struct MdDecide {
+    DevBuf<> k1, k2, ka, kb, i1, i2, info, tmp;
+};
+int md_templates(MdTemplates &m, const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, int cu_count, hipStream_t st);
+int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t, uint8_t *dup, int64_t counts[3], int cu_count,
+              hipStream_t st);
+void launch_md_apply(uint8_t *bam, const int64_t *rec_off, const uint32_t *perm, const uint32_t *rtmpl, const uint8_t *dup, int64_t n_rec,
+                     unsigned long long *n_marked, int cu_count, hipStream_t st);
+void launch_md_gather32(const uint32_t *src, const uint32_t *idx, int64_t n, uint32_t *dst, int cu_count, hipStream_t st);
+
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);
 int deflater_run_after(bwams_deflater *d, hipStream_t after, const void *in, int64_t n_bytes, int in_on_device, void *out, int64_t out_cap,

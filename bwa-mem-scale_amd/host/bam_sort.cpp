@@ -16,6 +16,10 @@
 //   * bins in ascending order; references without records have no bins and no linear index; n_no_coor at the end.
 // Virtual offsets: a record starting at record-stream byte x is at (member of x) << 16 | x % 65280; one ending before byte y at
 // (member of y - 1) << 16 | ((y - 1) % 65280 + 1), the end of that member's data rather than the start of the next member.
+// With BWAMS_SORT_MARKDUP every put_batch also keeps its batch's duplicate-marking ends (host memory, outside mem_bytes) and each
+// record's template ordinal in sorted order (with the run: in memory, or spilled after its records).  Close offsets each run's
+// ordinals by the templates of the runs before it in seq order, runs one bwams_dup_decide over all the ends, and sets or clears
+// FLAG 0x400 (bit 2 of the record's byte 19) in the merge buffer as each record is copied; the index does not read that bit.
 // Plain C++ over the C-ABI (no HIP header), like fastq_io.cpp.
 #include <fcntl.h>
 #include <unistd.h>
@@ -54,7 +58,10 @@ struct Run {
     int64_t seq = 0, n_rec = 0, n_bytes = 0;
     std::unique_ptr<uint8_t[]> recs;                  // in memory; empty when spilled
     std::vector<bwams_bam_coord_t> coords;
-    std::string path;                                 // spilled: coords, then records
+    std::string path;                                 // spilled: coords, then records (then, with markdup, template ordinals)
+    std::vector<uint32_t> tmpl;                       // markdup: each record's template ordinal, in sorted order (empty when spilled)
+    std::vector<bwams_dup_end_t> ends;                // markdup: the batch's ends, tmpl local to the run
+    int64_t n_tmpl = 0;
 };
 
 // One run's records in order: from memory, or from its spill file through bounded buffers.
@@ -66,6 +73,8 @@ struct Cursor {
     int64_t c0 = 0;
     std::vector<uint8_t> rb;                          // spilled: record bytes [b0, b0 + bn)
     int64_t b0 = 0, bn = 0;
+    std::vector<uint32_t> tb;                         // spilled, markdup: template ordinals [t0, t0 + tb.size())
+    int64_t t0 = 0;
 
     bool pread_all(void *dst, int64_t n, int64_t off) {
         for (int64_t got = 0; got < n;) {
@@ -94,6 +103,16 @@ struct Cursor {
             if (!pread_all(rb.data(), bn, r->n_rec * 16 + at)) return nullptr;
         }
         return rb.data() + (at - b0);
+    }
+    bool tmpl(uint32_t *t) {
+        if (r->recs) { *t = r->tmpl[(size_t)i]; return true; }
+        if (i < t0 || i >= t0 + (int64_t)tb.size()) {
+            t0 = i;
+            tb.resize((size_t)std::min(kSpillCoords, r->n_rec - i));
+            if (!pread_all(tb.data(), (int64_t)tb.size() * 4, r->n_rec * 16 + r->n_bytes + i * 4)) return false;
+        }
+        *t = tb[(size_t)(i - t0)];
+        return true;
     }
 };
 
@@ -242,7 +261,7 @@ int check_run(const bwams_sorter *s, const uint8_t *rec, int64_t n_bytes, const 
 
 // hand a checked run over: refused for a seq put before; kept in memory within mem_bytes, else spilled
 int take_run(bwams_sorter *s, std::unique_ptr<Run> r) {
-    const int64_t need = r->n_bytes + r->n_rec * 16;
+    const int64_t need = r->n_bytes + r->n_rec * 16 + (int64_t)r->tmpl.size() * 4;
     int64_t spill = -1;
     {
         std::lock_guard<std::mutex> g(s->mu);
@@ -253,10 +272,12 @@ int take_run(bwams_sorter *s, std::unique_ptr<Run> r) {
     if (spill >= 0) {
         r->path = s->tmp_prefix + "." + std::to_string(spill) + ".run";
         const int fd = ::open(r->path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0600);
-        const bool ok = fd >= 0 && write_all(fd, r->coords.data(), r->n_rec * 16) && write_all(fd, r->recs.get(), r->n_bytes);
+        const bool ok = fd >= 0 && write_all(fd, r->coords.data(), r->n_rec * 16) && write_all(fd, r->recs.get(), r->n_bytes) &&
+                        write_all(fd, r->tmpl.data(), (int64_t)r->tmpl.size() * 4);
         if (fd >= 0) ::close(fd);
         r->recs.reset();
         r->coords = std::vector<bwams_bam_coord_t>();
+        r->tmpl = std::vector<uint32_t>();
         std::lock_guard<std::mutex> g(s->mu);
         s->spilled_bytes += need;
         s->runs.push_back(std::move(r));               // its file is removed at close even when the write failed
@@ -291,7 +312,7 @@ extern "C" {
 
 int bwams_sorter_open(const char *path, int device, const void *bam_header, int64_t n_header, const char *tmp_prefix, int64_t mem_bytes,
                       int32_t flags, bwams_sorter_t **out) {
-    if (!path || !out || !bam_header || n_header < 12 || mem_bytes < 0 || (flags & ~BWAMS_SORT_BAI) || device < 0) return BWAMS_ERR_ARG;
+    if (!path || !out || !bam_header || n_header < 12 || mem_bytes < 0 || (flags & ~(BWAMS_SORT_BAI | BWAMS_SORT_MARKDUP)) || device < 0) return BWAMS_ERR_ARG;
     *out = nullptr;
     const uint8_t *h = static_cast<const uint8_t *>(bam_header);
     if (memcmp(h, "BAM\1", 4) != 0) return BWAMS_ERR_ARG;
@@ -346,6 +367,7 @@ int bwams_sorter_open(const char *path, int device, const void *bam_header, int6
 int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_t n_bytes, const bwams_bam_coord_t *coords,
                      int64_t n_records) {
     if (!s || seq < 0 || n_bytes < 0 || n_records < 0 || (n_bytes && !records) || (n_records && !coords)) return BWAMS_ERR_ARG;
+    if (s->flags & BWAMS_SORT_MARKDUP) return BWAMS_ERR_ARG;            // sorted host records carry no template grouping
     const uint8_t *rec = static_cast<const uint8_t *>(records);
     if (int rc = check_run(s, rec, n_bytes, coords, n_records)) return rc;
     try {
@@ -362,8 +384,11 @@ int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_
 
 int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b) {
     if (!s || !b || seq < 0) return BWAMS_ERR_ARG;
-    int64_t n = 0;
+    int64_t n = 0, n_t = 0, n_e = 0;
     if (int rc = bwams_bam_sort(b, &n)) return rc;
+    const bool md = (s->flags & BWAMS_SORT_MARKDUP) != 0;
+    if (md)
+        if (int rc = bwams_bam_templates(b, &n_t, &n_e)) return rc;
     try {
         auto r = std::make_unique<Run>();
         r->seq = seq; r->n_rec = n;
@@ -373,19 +398,48 @@ int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b) {
         r->recs.reset(new uint8_t[(size_t)std::max<int64_t>(r->n_bytes, 1)]);
         if (int rc = bwams_bam_sorted_fetch(b, r->recs.get(), r->n_bytes, nullptr)) return rc;
         if (int rc = check_run(s, r->recs.get(), r->n_bytes, r->coords.data(), n)) return rc;
+        if (md) {
+            r->n_tmpl = n_t;
+            r->ends.resize((size_t)n_e);
+            r->tmpl.resize((size_t)n);
+            if (int rc = bwams_bam_templates_fetch(b, r->ends.data(), n_e, r->tmpl.data(), 1)) return rc;
+        }
         return take_run(s, std::move(r));
     } catch (...) {
         return BWAMS_ERR_NOMEM;
     }
 }
 
-int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats) {
+int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats) { return bwams_sorter_close2(s, stats, nullptr); }
+
+int bwams_sorter_close2(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats) {
     if (!s) return BWAMS_ERR_ARG;
     const Clock::time_point t_all = Clock::now();
-    float ms_deflate = 0, ms_write = 0;
+    float ms_deflate = 0, ms_write = 0, ms_decide = 0;
     int rc = BWAMS_OK;
-    int64_t n_records = 0, file_pos = 0;
+    int64_t n_records = 0, file_pos = 0, n_marked = 0;
+    const bool md = (s->flags & BWAMS_SORT_MARKDUP) != 0;
+    bwams_dup_stats_t dst;
+    memset(&dst, 0, sizeof dst);
     try {
+        std::vector<int64_t> base(s->runs.size(), 0);                           // markdup: each run's first template ordinal
+        std::vector<uint8_t> dup;
+        if (md) {
+            const Clock::time_point t0 = Clock::now();
+            std::vector<size_t> by_seq(s->runs.size());
+            for (size_t k = 0; k < by_seq.size(); ++k) by_seq[k] = k;
+            std::sort(by_seq.begin(), by_seq.end(), [&](size_t a, size_t b) { return s->runs[a]->seq < s->runs[b]->seq; });
+            int64_t n_t = 0, n_e = 0;
+            for (size_t k : by_seq) { base[k] = n_t; n_t += s->runs[k]->n_tmpl; n_e += (int64_t)s->runs[k]->ends.size(); }
+            std::vector<bwams_dup_end_t> ends;
+            ends.reserve((size_t)n_e);
+            for (size_t k : by_seq)
+                for (bwams_dup_end_t e : s->runs[k]->ends) { e.tmpl += base[k]; ends.push_back(e); }
+            dup.resize((size_t)std::max<int64_t>(n_t, 1));
+            rc = bwams_dup_decide(s->device, ends.data(), n_e, n_t, dup.data(), &dst);
+            dst.templates = n_t;
+            ms_decide = ms_since(t0);
+        }
         Clock::time_point t = Clock::now();
         if (fwrite(s->header_gz.data(), 1, s->header_gz.size(), s->fp) != s->header_gz.size()) rc = BWAMS_ERR_IO;
         ms_write += ms_since(t);
@@ -447,9 +501,20 @@ int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats) {
             const uint8_t *p = nullptr;
             if (!c.coord(&cd) || !(p = c.bytes(cd.size))) { rc = BWAMS_ERR_IO; break; }
             if (s->flags & BWAMS_SORT_BAI) pend.push_back({cd.key, cd.end, (uint32_t)(p[18] | p[19] << 8), x, cd.size});
+            bool d = false;
+            if (md) {
+                uint32_t t = 0;
+                if (!c.tmpl(&t)) { rc = BWAMS_ERR_IO; break; }
+                d = dup[(size_t)(base[k] + t)] != 0;
+                n_marked += d;
+            }
             for (int64_t done = 0; done < cd.size && !rc;) {                   // a record larger than the piece goes in parts
                 const int64_t k2 = std::min<int64_t>(cd.size - done, kPiece - fill);
                 memcpy(buf.data() + fill, p + done, (size_t)k2);
+                if (md && done <= 19 && 19 < done + k2) {                      // FLAG's high byte: 0x400 is its bit 2
+                    uint8_t &f = buf[(size_t)(fill + 19 - done)];
+                    f = (uint8_t)((f & ~4u) | (d ? 4u : 0u));
+                }
                 fill += k2;
                 done += k2;
                 if (fill == kPiece) rc = flush();
@@ -489,7 +554,11 @@ int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats) {
         stats->out_bytes = file_pos;
         stats->ms_deflate = ms_deflate;
         stats->ms_write = ms_write;
-        stats->ms_merge = std::max(0.f, ms_since(t_all) - ms_deflate - ms_write);
+        stats->ms_merge = std::max(0.f, ms_since(t_all) - ms_deflate - ms_write - ms_decide);
+    }
+    if (dup_stats) {
+        *dup_stats = dst;
+        if (md) { dup_stats->records_marked = n_marked; dup_stats->ms_decide = ms_decide; }
     }
     cleanup(s);
     return rc;

@@ -389,6 +389,56 @@ int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64
 int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t *n_records);
 int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records);
 int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_coord_t *coords);
+/* Duplicate marking (csrc/markdup.hip): Picard MarkDuplicates' rules for query-grouped input — default SUM_OF_BASE_QUALITIES scoring,
+ * one library, no optical duplicate detection, no barcodes.  bwams/markdup.py restates them.
+ *  1. Template: a maximal run of consecutive records with byte-equal read names, in the batch's unsorted order.  This is the order
+ *     bwams_bam_run produces, and the order an uploaded BAM is given in.  A template never spans two batches or two sorter puts.
+ *  2. Primary: FLAG has neither 0x100 nor 0x800.  A primary's segment is "only" when 0x1 is clear.  When 0x1 is set, it is "first"
+ *     for 0x40 and "last" for 0x80.  A template is refused with BWAMS_ERR_UNSUPPORTED in any of these cases, and bwams_last_error
+ *     names the first record concerned: two primaries of one segment (for example, two adjacent single-end reads that share a
+ *     name); a paired primary with neither or both of 0x40/0x80; paired and unpaired primaries mixed.  (The record concerned is
+ *     the one at which a walk over the template in order meets the fault: the second primary of a segment, the paired primary
+ *     without a single segment bit, the first primary whose 0x1 differs from the template's first primary's.)
+ *  3. Unclipped 5' coordinate of a mapped primary (0x4 clear), 0-based: forward: POS - (the S and H lengths before the first other
+ *     op); reverse (0x10): POS + rlen - 1 + (the S and H lengths after the last other op), where rlen is the sum of the M/D/N/=/X
+ *     lengths, taken as 1 when it is 0.  A coordinate outside [-2^31, 2^31) is refused as in rule 2, and so is a mapped primary
+ *     with refID -1.
+ *  4. Score of a mapped primary: the sum of its QUAL values that are >= 15, capped at 16383 (Picard's Short.MAX_VALUE / 2).  It is 0
+ *     when QUAL is absent (0xFF).  A pair's score is the sum of its two ends' scores.
+ *  5. Ends: Pair: a template whose two primaries ("first" and "last") are both mapped.  End 1 is the end with the smaller (refID,
+ *     coordinate); on a tie it is the earlier record.  The pair key is (ref1, c1, strand1, ref2, c2, strand2), so FR and RF at the
+ *     same places are different keys.  Fragment: any other template with exactly one mapped primary.  The fragment key is (ref, c,
+ *     strand).  Each end of a pair is also a paired fragment under its own fragment key, for rule 6 only.
+ *  6. Decision.  The tie-break "earlier" below means input order: the batch's record order, and across sorter puts, seq first.
+ *     Pairs with equal keys: the pair with the highest score is kept.  Ties go to the earlier template.  Every other pair is a
+ *     duplicate.  Fragments with equal keys: if the group holds any paired fragment, every unpaired fragment in it is a duplicate.
+ *     Otherwise the highest score is kept, ties go to the earlier template, and the rest are duplicates.
+ *  7. Marking: every record of a duplicate template gets FLAG 0x400.  That includes its primaries, its secondary and supplementary
+ *     records, and the unmapped mate of a duplicate fragment.  This is what Picard does on query-grouped input.  Every other record
+ *     has 0x400 cleared.  Templates with no mapped primary are never duplicates.  Nothing but that one FLAG bit changes, so sizes,
+ *     bins and the BAI stay the same.
+ *  8. Counts (bwams_dup_stats_t): templates: all templates; unpaired_examined / unpaired_duplicates: fragments, and the fragments
+ *     marked; pairs_examined / pair_duplicates: pairs (not reads), and the pairs marked; records_marked: records that end up with
+ *     0x400 set; ms_decide: host clock around the decision.  Picard's PERCENT_DUPLICATION is (unpaired_duplicates +
+ *     2 pair_duplicates) / (unpaired_examined + 2 pairs_examined).
+ * _templates: groups the batch's current records (bwams_bam_run / _upload) into templates and computes their ends on the device:
+ * *n_templates, and *n_ends (one per template with a mapped primary, in template order); either may be NULL.  Rules 1-3 refuse here
+ * (BWAMS_ERR_UNSUPPORTED).  BWAMS_ERR_ARG before any bwams_bam_run or _upload.  More than 2^32 - 1 records: BWAMS_ERR_UNSUPPORTED.
+ * _templates_fetch (after _templates on the current records): the n_ends ends (cap >= n_ends, BWAMS_ERR_CAPACITY otherwise) and each
+ * record's template ordinal, in record order, or with sorted = 1 in the order of bwams_bam_sort (BWAMS_ERR_ARG before a sort of the
+ * current records); either pointer may be NULL.
+ * bwams_dup_decide: rule 6 on `device` over host ends[0, n_ends) of templates [0, n_templates): dup[t] = 1 for every duplicate
+ * template, 0 otherwise (n_templates bytes, host memory).  Each template has at most one end.  Every tmpl must lie in
+ * [0, n_templates), ref1 in [0, 2^30), ref2 in [-1, 2^30), score in [0, 32767] and strands in [0, 3] (bit 1 only with an end 2):
+ * BWAMS_ERR_ARG otherwise, with the first bad end in bwams_last_error.  The decision's device buffers (about 110 B per end) that do
+ * not fit: BWAMS_ERR_NOMEM.  *st (may be NULL): rule 8's counts, records_marked 0.
+ * _markdup: the batch alone is the whole input: _templates, the decision and the marking, all in HBM.  The unsorted records and the
+ * sorted copy, when the current records have one, are marked, so bwams_bam_fetch, _fetch_bgzf, _sort and _sorted_fetch all see the
+ * flags.  A second call gives the same records.  *st may be NULL. */
+int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends);
+int bwams_bam_templates_fetch(bwams_batch_t *b, bwams_dup_end_t *ends, int64_t cap, uint32_t *rec_tmpl, int32_t sorted);
+int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, int64_t n_templates, uint8_t *dup, bwams_dup_stats_t *st);
+int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st);
 /* bwa_print_sam_hdr into out[0, cap): "@SQ\tSN:<name>\tLN:<len>" per sequence ("\tAH:*" for ALT sequences) unless hdr_line holds @SQ
  * lines of its own; then hdr_line and a newline (mem -H text and the @RG line, as main_mem builds it); then pg_line as given (it carries
  * its own newline).  hdr_line / pg_line may be NULL.  *n_out: the bytes written, or needed with BWAMS_ERR_CAPACITY. */
@@ -770,15 +820,26 @@ int bwams_writer_open_bam(const char *path, int32_t n_shards, int device, const 
  * records cut every 65280 bytes from their first byte into members made by a deflater on `device`, then the EOF member.  The
  * bytes of the file and of the index depend only on the records and their seq numbers (not on put order, threads, mem_bytes or
  * spilling); bwams/bai.py restates the index.  BWAMS_SORT_BAI with a reference longer than 2^29 bases: BWAMS_ERR_UNSUPPORTED at
- * open (BAI cannot hold it). */
+ * open (BAI cannot hold it).
+ * With BWAMS_SORT_MARKDUP the file is also duplicate-marked (the rules above bwams_bam_templates), over every put as one input:
+ * _put is BWAMS_ERR_ARG (sorted host records carry no template grouping); _put_batch also runs bwams_bam_templates on the batch
+ * (its refusals pass through) and keeps the batch's ends and each record's template ordinal in sorted order (4 B per record, kept
+ * and spilled with the run).  The ends (32 B per template) stay in host memory and are not counted in mem_bytes.  At close the
+ * runs' template ordinals are offset by a base taken in seq order, one bwams_dup_decide runs on `device` (BWAMS_ERR_NOMEM when it
+ * does not fit in HBM), and the merge sets or clears 0x400 in each record as it copies it.  Without the flag FLAG passes through
+ * (a batch marked with bwams_bam_markdup keeps its marks).  0x400 changes no size, bin or index byte.
+ * _close2: _close, and the marking's counts in *dup (zeros without BWAMS_SORT_MARKDUP); either stats pointer may be NULL.
+ * _close(s, st) is _close2(s, st, NULL). */
 typedef struct bwams_sorter bwams_sorter_t;
 #define BWAMS_SORT_BAI 0x1                       /* also write <path>.bai */
+#define BWAMS_SORT_MARKDUP 0x2                   /* mark duplicates over all puts (FLAG 0x400) */
 int bwams_sorter_open(const char *path, int device, const void *bam_header, int64_t n_header, const char *tmp_prefix, int64_t mem_bytes,
                       int32_t flags, bwams_sorter_t **out);
 int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_t n_bytes, const bwams_bam_coord_t *coords,
                      int64_t n_records);
 int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b);
 int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats);   /* stats may be NULL */
+int bwams_sorter_close2(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -256,6 +256,23 @@ typedef struct bwams_sorter_stats {
     float   ms_merge, ms_deflate, ms_write;
 } bwams_sorter_stats_t;
 
+/* One template's duplicate-marking end (include/bwams.h, "Duplicate marking"): tmpl is the template's ordinal in input order;
+ * (ref1, pos1) is end 1's refID and unclipped 5' coordinate (0-based), (ref2, pos2) end 2's, ref2 = -1 for a fragment (pos2 = 0);
+ * score is the template's score (a pair's: both ends' summed); strands: bit 0 end 1 reverse, bit 1 end 2 reverse. */
+typedef struct bwams_dup_end {
+    int64_t tmpl;
+    int32_t ref1, pos1, ref2, pos2;
+    int32_t score, strands;
+} bwams_dup_end_t;
+
+/* What duplicate marking found (rule 8): templates; fragments examined and marked; pairs (not reads) examined and marked; records
+ * that end up with FLAG 0x400; host-clock milliseconds around the decision. */
+typedef struct bwams_dup_stats {
+    int64_t templates, unpaired_examined, unpaired_duplicates, pairs_examined, pair_duplicates, records_marked;
+    float   ms_decide;
+    int32_t pad_;
+} bwams_dup_stats_t;
+
 #ifdef __cplusplus
 }
 #endif
