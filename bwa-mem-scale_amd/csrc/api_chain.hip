@@ -67,6 +67,7 @@ struct ChainState {
     DevBuf regs, srt, rmax, cnt, ewide, eoffs, state, kreg, cur, lim;
     DevBuf lpairs, lref, lqer, rpairs, rref, rqer, retry;
     DevBuf lsrc, rsrc;           // in-place extension (bwams_extend_run): per task the start offsets {query, target} instead of copied bytes
+    DevBuf req_list, rtask;      // bwams_extend_run: the slots requested for the next build (appended by whoever requests); per slot its right task
     bool tasks_inplace = false;
     int64_t n_left = 0, n_right = 0, lref_b = 0, lqer_b = 0, rref_b = 0, rqer_b = 0;
     int64_t n_retry_left = 0, n_retry_right = 0, n_rounds = 0;
@@ -562,27 +563,46 @@ static int ext_args(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt, E
     A->cnt = s->cnt.as<int32_t>(); A->ctr = b->d_ctr.p;
     A->state = s->state.as<int32_t>(); A->kreg = s->kreg.p;
     A->cur = s->cur.as<int32_t>(); A->lim = s->lim.as<int32_t>();
-    A->sel_heavy = s->heavy.as<int32_t>(); A->n_sel_heavy = &b->d_ctr.p->sel_heavy; A->sel_ticket = &b->d_ctr.p->sel_ticket;
+    A->sel_heavy = s->heavy.as<int32_t>(); A->n_sel_heavy = &b->d_ctr.p->sel_heavy; A->sel_ticket = b->d_ctr.p->ext_sel_ticket;
+    A->req_list = s->req_list.as<int32_t>(); A->rtask = nullptr;
     return BWAMS_OK;
 }
 
-// allocate the per-seed arrays and run the plan kernel (windows, seed order, regions, task sizes)
+// The counters of one round (DevCounters: ext_n_req .. ext_n_retry) are one block: one memset clears them.
+static hipError_t ext_round_clear(bwams_batch *b) {
+    DevCounters *c = b->d_ctr.p;
+    return hipMemsetAsync(&c->ext_n_req, 0, (size_t)((char *)(c->ext_n_retry + 2) - (char *)&c->ext_n_req), b->stream);
+}
+// ... and what the host needs of them — requests, slots behind them, the requests' left and right tasks — is one copy.
+static int ext_round_fetch(bwams_batch *b, int64_t *n_req, int64_t *n_rest, int64_t *n_l, int64_t *n_r) {
+    DevCounters *h = b->h_ctr.p;
+    BWAMS_HIP(hipMemcpyAsync(&h->ext_n_req, &b->d_ctr.p->ext_n_req, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+    BWAMS_HIP(hipStreamSynchronize(b->stream));
+    *n_req = (int64_t)h->ext_n_req; *n_rest = (int64_t)h->ext_n_rest;
+    *n_l = (int64_t)(h->ext_n_tasks & 0xffffffffull); *n_r = (int64_t)(h->ext_n_tasks >> 32);
+    return BWAMS_OK;
+}
+
+// allocate the per-seed arrays and run the plan kernel (windows, seed order, regions, task sizes, the first requests)
 static int ext_plan(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt, int extend_all, ExtArgs *A) {
     const int64_t N1 = s->n_seeds + 1, n1 = s->nseq + 1;
     BWAMS_HIP(s->regs.ensure((size_t)N1 * sizeof(bwams_alnreg_t)));
     BWAMS_HIP(s->srt.ensure((size_t)N1 * 4));
     BWAMS_HIP(s->rmax.ensure((size_t)(s->n_chains + 1) * 16));
     BWAMS_HIP(s->cnt.ensure((size_t)N1 * 6 * 4));
-    BWAMS_HIP(s->ewide.ensure((size_t)N1 * 6 * 8));
-    BWAMS_HIP(s->eoffs.ensure((size_t)N1 * 6 * 8));
     BWAMS_HIP(s->state.ensure((size_t)N1 * 4));
     BWAMS_HIP(s->kreg.ensure((size_t)N1 * 32));
     BWAMS_HIP(s->cur.ensure((size_t)n1 * 4));
     BWAMS_HIP(s->lim.ensure((size_t)n1 * 4));
     BWAMS_HIP(s->heavy.ensure((size_t)n1 * 4));
+    // the request list: a slot is requested at most once in a run, so every slot fits; entries beyond the cursor of the round in
+    // hand (a larger chunk's, an earlier round's) are never read
+    BWAMS_HIP(s->req_list.ensure((size_t)N1 * 4));
+    BWAMS_HIP(s->rtask.ensure((size_t)N1 * 4));
     int rc = ext_args(b, s, opt, A);
     if (rc) return rc;
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->sel_heavy, 0, 4 * sizeof(unsigned long long), b->stream));
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->sel_heavy, 0, sizeof(unsigned long long), b->stream));
+    BWAMS_HIP(ext_round_clear(b));
     launch_ext_heavy_list(*A, b->stream);
     BWAMS_HIP(hipMemsetAsync(s->cur.p, 0, (size_t)n1 * 4, b->stream));
     BWAMS_HIP(hipMemsetAsync(s->lim.p, 0, (size_t)n1 * 4, b->stream));
@@ -590,18 +610,21 @@ static int ext_plan(bwams_batch *b, ChainState *s, const bwams_mem_opt_t *opt, i
     return BWAMS_OK;
 }
 
-// build the task lists of the seeds requested this round
-static int ext_build_round(bwams_batch *b, ChainState *s, const ExtArgs &A, int64_t tot[6], bool inplace) {
+// Tasks in flat buffers (the SeqPair boundary): the six rows of task sizes of n slots — list[i], or with list == nullptr the requested
+// ones among all n = n_seeds slots — are scanned for task indices and byte offsets, so the tasks come in the order of the slots given.
+static int ext_build_flat(bwams_batch *b, ChainState *s, const ExtArgs &A, const int32_t *list, int64_t n, int64_t tot[6]) {
     hipStream_t st = b->stream;
-    const int64_t N = s->n_seeds, N1 = N + 1;
-    launch_ext_widen(A, s->ewide.as<int64_t>(), st);
-    int rc = scan_rows(b, s->ewide.as<int64_t>(), s->eoffs.as<int64_t>(), 6, N1);
+    const int64_t n1 = n + 1;
+    BWAMS_HIP(s->ewide.ensure((size_t)n1 * 6 * 8));
+    BWAMS_HIP(s->eoffs.ensure((size_t)n1 * 6 * 8));
+    launch_ext_widen(A, list, n, s->ewide.as<int64_t>(), st);
+    int rc = scan_rows(b, s->ewide.as<int64_t>(), s->eoffs.as<int64_t>(), 6, n1);
     if (rc) return rc;
     for (int r = 0; r < 6; ++r)
-        BWAMS_HIP(hipMemcpyAsync(&tot[r], s->eoffs.as<int64_t>() + r * N1 + N, 8, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipMemcpyAsync(&tot[r], s->eoffs.as<int64_t>() + r * n1 + n, 8, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     for (int r : {1, 2, 4, 5})
-        if (!inplace && tot[r] >= ((int64_t)1 << 31)) {
+        if (tot[r] >= ((int64_t)1 << 31)) {
             set_last_error("extension task buffers exceed the 31-bit offsets of SeqPair; use smaller chunks");
             return BWAMS_ERR_CAPACITY;
         }
@@ -611,17 +634,39 @@ static int ext_build_round(bwams_batch *b, ChainState *s, const ExtArgs &A, int6
     BWAMS_HIP(s->rpairs.ensure((size_t)(tot[3] + 1) * sizeof(bwams_seqpair_t)));
     const int64_t mx = tot[0] > tot[3] ? tot[0] : tot[3];
     BWAMS_HIP(s->retry.ensure((size_t)(mx + 1) * sizeof(bwams_seqpair_t)));
-    s->tasks_inplace = inplace;
-    if (inplace) {               // no bytes are copied: 16 bytes of offsets per task
-        BWAMS_HIP(s->lsrc.ensure((size_t)(tot[0] + 1) * 16)); BWAMS_HIP(s->rsrc.ensure((size_t)(tot[3] + 1) * 16));
-    } else {
-        BWAMS_HIP(s->lqer.ensure((size_t)tot[1] + 64)); BWAMS_HIP(s->lref.ensure((size_t)tot[2] + 64));
-        BWAMS_HIP(s->rqer.ensure((size_t)tot[4] + 64)); BWAMS_HIP(s->rref.ensure((size_t)tot[5] + 64));
-    }
+    s->tasks_inplace = false;
+    BWAMS_HIP(s->lqer.ensure((size_t)tot[1] + 64)); BWAMS_HIP(s->lref.ensure((size_t)tot[2] + 64));
+    BWAMS_HIP(s->rqer.ensure((size_t)tot[4] + 64)); BWAMS_HIP(s->rref.ensure((size_t)tot[5] + 64));
     if (tot[0] + tot[3] > 0)
-        launch_ext_build(A, s->eoffs.as<int64_t>(), s->lpairs.as<bwams_seqpair_t>(), s->lref.as<uint8_t>(), s->lqer.as<uint8_t>(),
-                         s->rpairs.as<bwams_seqpair_t>(), s->rref.as<uint8_t>(), s->rqer.as<uint8_t>(),
-                         inplace ? s->lsrc.as<int64_t>() : nullptr, inplace ? s->rsrc.as<int64_t>() : nullptr, b->cu_count, st);
+        launch_ext_build(A, list, n, s->eoffs.as<int64_t>(), s->lpairs.as<bwams_seqpair_t>(), s->lref.as<uint8_t>(), s->lqer.as<uint8_t>(),
+                         s->rpairs.as<bwams_seqpair_t>(), s->rref.as<uint8_t>(), s->rqer.as<uint8_t>(), nullptr, nullptr, st);
+    return BWAMS_OK;
+}
+
+// One round's tasks, built from the request list: n_req slots with n_l left and n_r right tasks, all three known to the host from the
+// round trip that ended the previous round (or followed the plan).  In place nothing is scanned and nothing but the list is read:
+// the build reserves task indices as it goes.  BWAMS_EXT_INPLACE=0 scans the requested slots' sizes for the flat buffers' offsets.
+static int ext_build_round(bwams_batch *b, ChainState *s, const ExtArgs &A, int64_t n_req, int64_t n_l, int64_t n_r, bool inplace) {
+    if (!inplace) {
+        int64_t tot[6] = {0, 0, 0, 0, 0, 0};
+        if (int rc = ext_build_flat(b, s, A, A.req_list, n_req, tot)) return rc;
+        if (tot[0] != n_l || tot[3] != n_r) {
+            set_last_error("bwams_extend_run: the request list and its task counters disagree");
+            return BWAMS_ERR_DEVICE;
+        }
+        return BWAMS_OK;
+    }
+    s->n_left = n_l; s->n_right = n_r;
+    s->lqer_b = s->lref_b = s->rqer_b = s->rref_b = 0;
+    BWAMS_HIP(s->lpairs.ensure((size_t)(n_l + 1) * sizeof(bwams_seqpair_t)));
+    BWAMS_HIP(s->rpairs.ensure((size_t)(n_r + 1) * sizeof(bwams_seqpair_t)));
+    const int64_t mx = n_l > n_r ? n_l : n_r;
+    BWAMS_HIP(s->retry.ensure((size_t)(mx + 1) * sizeof(bwams_seqpair_t)));
+    s->tasks_inplace = true;               // no bytes are copied: 16 bytes of offsets per task
+    BWAMS_HIP(s->lsrc.ensure((size_t)(n_l + 1) * 16)); BWAMS_HIP(s->rsrc.ensure((size_t)(n_r + 1) * 16));
+    if (n_l + n_r > 0)
+        launch_ext_build(A, A.req_list, n_req, nullptr, s->lpairs.as<bwams_seqpair_t>(), nullptr, nullptr, s->rpairs.as<bwams_seqpair_t>(),
+                         nullptr, nullptr, s->lsrc.as<int64_t>(), s->rsrc.as<int64_t>(), b->stream);
     return BWAMS_OK;
 }
 
@@ -644,7 +689,7 @@ int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_
     BWAMS_HIP(hipEventRecord(s->ev[2], st));
     if ((rc = ext_plan(b, s, opt, 1, &A))) return rc;           // every seed, as the reference builds them
     int64_t tot[6];
-    if ((rc = ext_build_round(b, s, A, tot, false))) return rc;
+    if ((rc = ext_build_flat(b, s, A, nullptr, s->n_seeds, tot))) return rc;
     BWAMS_HIP(hipEventRecord(s->ev[3], st));
     BWAMS_HIP(hipGetLastError());
     s->built = true;
@@ -669,21 +714,21 @@ static int run_side(bwams_batch *b, ChainState *s, const ExtArgs &A, int right, 
     sw_params(A.opt, right ? A.opt.pen_clip3 : A.opt.pen_clip5, &prm);
     const int qmax = b->max_read_len > 1 ? b->max_read_len : 1;
     if (n == 0) return BWAMS_OK;
-    unsigned long long *d_nretry = &b->d_ctr.p->n_retry;
-    BWAMS_HIP(hipMemsetAsync(d_nretry, 0, sizeof(unsigned long long), st));
+    unsigned long long *d_nretry = &b->d_ctr.p->ext_n_retry[right], *h_nretry = &b->h_ctr.p->ext_n_retry[right];   // cleared with the round's counters
+    bwams_seqpair_t *rp = A.rtask ? s->rpairs.as<bwams_seqpair_t>() : nullptr;       // a settled left task hands its score to the slot's right task
     if (bsw_list_bytes(n) > b->d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(st));   // the last launch may still read the lists
     BWAMS_HIP(b->d_bsw_list.ensure(bsw_list_bytes(n), bsw_list_bytes(n + n / 4 + 1024)));
     if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr.p, b->cu_count, st, b->d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) {
         set_last_error(lrc == -2 ? "banded SW: a query longer than ~18000 bases does not fit the LDS kernel" : "banded SW: stream fork/join failed");
         return lrc == -2 ? BWAMS_ERR_UNSUPPORTED : BWAMS_ERR_DEVICE;
     }
-    launch_ext_post(A, right, pairs, n, A.opt.w, 0, s->retry.as<bwams_seqpair_t>(), d_nretry, st);
-    unsigned long long nr = 0;
-    BWAMS_HIP(hipMemcpyAsync(&nr, d_nretry, sizeof nr, hipMemcpyDeviceToHost, st));
+    launch_ext_post(A, right, pairs, n, A.opt.w, 0, s->retry.as<bwams_seqpair_t>(), d_nretry, rp, st);
+    BWAMS_HIP(hipMemcpyAsync(h_nretry, d_nretry, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
+    const unsigned long long nr = *h_nretry;
     if (nr) {
         if (launch_bsw(s->retry.as<bwams_seqpair_t>(), (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr.p, b->cu_count, st, b->d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) return BWAMS_ERR_DEVICE;
-        launch_ext_post(A, right, s->retry.as<bwams_seqpair_t>(), (int64_t)nr, A.opt.w << 1, 1, nullptr, d_nretry, st);
+        launch_ext_post(A, right, s->retry.as<bwams_seqpair_t>(), (int64_t)nr, A.opt.w << 1, 1, nullptr, d_nretry, rp, st);
     }
     *n_retry_out += (int64_t)nr;
     return BWAMS_OK;
@@ -692,6 +737,15 @@ static int run_side(bwams_batch *b, ChainState *s, const ExtArgs &A, int right, 
 // Rounds of (build the requested tasks, extend left, extend right, select).  Round 0 extends the first
 // seed visited of every chain; a later round extends the seeds the selection found it must keep but
 // that had not been extended yet.  After kMaxRounds everything still undecided is extended at once.
+//
+// A round costs what it extends, not what the chunk holds: whoever requests a slot (the plan, the selection, the
+// extend-the-rest kernel) appends it to the request list and adds its task counts to the round's counters, the build
+// starts a lane per list entry and reserves task indices as it goes (the order of the tasks inside a round is
+// unspecified; results go back by (seqid, regid)), and one copy of three words after the selection tells the host
+// whether another round runs and how large its buffers must be.  The host waits three times per round: after each
+// side for the retry count (the right side starts from the left side's settled scores), after the selection for
+// the next round's sizes — and once after the plan, once more when the rest is requested.  One list serves every
+// round: a round's build has consumed it before that round's selection, which alone appends, clears its cursor.
 int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_regs) {
     if (!b || !b->chain || !b->chain->chain_done) {
         set_last_error("bwams_extend_run: run bwams_chain_run (or bwams_chain_upload) first");
@@ -716,22 +770,21 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->bsw_cells, 0, sizeof(unsigned long long), st));      // DP cells of this run, all rounds
     BWAMS_HIP(hipEventRecord(s->ev[2], st));
     if ((rc = ext_plan(b, s, opt, opt->extend_all != 0, &A))) return rc;
+    A.rtask = s->rtask.as<int32_t>();
     int64_t tot_left = 0, tot_right = 0;
     s->n_retry_left = s->n_retry_right = 0;
+    int64_t n_req = 0, n_rest = 0, n_l = 0, n_r = 0;          // what the round in hand builds: known before it starts
+    if ((rc = ext_round_fetch(b, &n_req, &n_rest, &n_l, &n_r))) return rc;
     int round = 0;
     for (;; ++round) {
-        int64_t tot[6];
-        if ((rc = ext_build_round(b, s, A, tot, inplace_on))) return rc;
+        if ((rc = ext_build_round(b, s, A, n_req, n_l, n_r, inplace_on))) return rc;
         if (round == 0) { BWAMS_HIP(hipEventRecord(s->ev[3], st)); BWAMS_HIP(hipEventRecord(s->ev[4], st)); }
-        tot_left += tot[0]; tot_right += tot[3];
+        tot_left += n_l; tot_right += n_r;
         if ((rc = run_side(b, s, A, 0, &s->n_retry_left))) return rc;
         if (round == 0) { BWAMS_HIP(hipEventRecord(s->ev[5], st)); BWAMS_HIP(hipEventRecord(s->ev[6], st)); }
-        launch_ext_right_h0(A, s->rpairs.as<bwams_seqpair_t>(), s->n_right, st);
         if ((rc = run_side(b, s, A, 1, &s->n_retry_right))) return rc;
         if (round == 0) { BWAMS_HIP(hipEventRecord(s->ev[7], st)); BWAMS_HIP(hipEventRecord(s->ev[8], st)); }
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->n_req, 0, sizeof(unsigned long long), st));
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->sel_ticket, 0, 3 * sizeof(unsigned long long), st));
-        BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->n_rest, 0, sizeof(unsigned long long), st));
+        BWAMS_HIP(ext_round_clear(b));                         // the list's cursor, the task counts, the build's and the walk's cursors, the retry counts
         const bool vb_sel = knobs().verbose != 0;
         const bool verbose_sel = vb_sel;
         if (verbose_sel) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg, 0, sizeof b->d_ctr.p->dbg, st));
@@ -749,17 +802,17 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
                         round, d[0], d[1] / 1e6, d[2] / 1e6, d[3] / 1e6, d[4] / 1e6, d[5], d[6], d[7], d[8] / 1e6, d[9] / 1e6, d[10] / 1e6, d[11] / 1e6, d[12], d[13], d[14], d[15]);
         }
         if (round == 0) BWAMS_HIP(hipEventRecord(s->ev[9], st));
-        unsigned long long n_req = 0, n_rest = 0;
-        BWAMS_HIP(hipMemcpyAsync(&n_req, &b->d_ctr.p->n_req, sizeof n_req, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipMemcpyAsync(&n_rest, &b->d_ctr.p->n_rest, sizeof n_rest, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
+        if ((rc = ext_round_fetch(b, &n_req, &n_rest, &n_l, &n_r))) return rc;
         if (n_req == 0) break;
-        // A round costs about as much as ~10^5 extensions whatever it holds (launches, the selection's walk of the heaviest
-        // reads).  When the seeds still undecided — at most n_rest, the slots behind this round's requests — are few beside what
+        // A round costs the launches and the selection's walk of the heaviest reads whatever it holds.  When the seeds still
+        // undecided — at most n_rest, the slots behind this round's requests — are few beside what
         // has been extended already, extending them all now (as the reference does with every seed) is cheaper than the rounds
         // that would sort out which of them are dead.
-        const bool few_left = !adaptive_off && (int64_t)(n_req + n_rest) * 32 < tot_left + tot_right;
-        if (round + 1 >= kMaxRounds || few_left) launch_ext_request_rest(A, st);
+        const bool few_left = !adaptive_off && (n_req + n_rest) * 32 < tot_left + tot_right;
+        if (round + 1 >= kMaxRounds || few_left) {
+            launch_ext_request_rest(A, st);                    // appends behind the selection's requests
+            if ((rc = ext_round_fetch(b, &n_req, &n_rest, &n_l, &n_r))) return rc;
+        }
     }
     BWAMS_HIP(hipEventRecord(s->ev[11], st));
     BWAMS_HIP(hipGetLastError());

@@ -976,16 +976,26 @@ int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint
     }
     const unsigned B = (unsigned)blocks, T = kWavesPerBlock * 64;
     unsigned long long *cnt = ctr->bsw_cls_cnt, *hd = ctr->bsw_cls_head;
-    // per launch: the attribute belongs to the current device (a batch on a second GPU of the process needs it too)
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_qwin_kernel<kBswLpt, kBswWin>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((size_t)kWavesPerBlock * (64 / kBswLpt) * 192 * 4)) != hipSuccess) return -1;
+    // once per device: the attribute belongs to the device that is current (a batch on a second GPU of the process needs it too)
+    auto pk_lds = [](int cols) { return (size_t)64 + (size_t)kPkWaves * 16 * ((size_t)(cols / 2) * 10 + 24); };
+    {
+        static std::mutex mu;
+        static bool done[64] = {};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return -1;
+        std::lock_guard<std::mutex> g(mu);
+        if (dev < 0 || dev >= 64 || !done[dev]) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_qwin_kernel<kBswLpt, kBswWin>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((size_t)kWavesPerBlock * (64 / kBswLpt) * 192 * 4)) != hipSuccess) return -1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_pk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds(192)) != hipSuccess) return -1;
+            if (dev >= 0 && dev < 64) done[dev] = true;
+        }
+    }
     // every class on a stream of its own, the classes of the longest queries first.  (With two classes per stream and the
     // one-task-per-wave kernel — usually without a single task, but 2048 blocks that wait for a free CU slot — in front of one
     // of them, the kernel trace showed two class launches starting 14 ms late.)
     const bool pk_env = knobs().bsw_pk != 0;       // A-B knob: the 32-bit eight-task kernel
     if (pk_env && bsw_pk_eligible(prm)) {
-        auto pk_lds = [](int cols) { return (size_t)64 + (size_t)kPkWaves * 16 * ((size_t)(cols / 2) * 10 + 24); };
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_pk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds(192)) != hipSuccess) return -1;
         static const int kCols[5] = {32, 64, 96, 144, 192};
         const unsigned Bp = (unsigned)((int64_t)B * kWavesPerBlock / kPkWaves);
         for (int c = 4; c >= 0; --c)

@@ -76,16 +76,22 @@ struct ExtArgs {
     int32_t *cur, *lim;            // per read: seeds decided so far, regions kept so far
     int32_t *sel_heavy;            // reads with many regions (the selection's wave tier)
     unsigned long long *n_sel_heavy, *sel_ticket;     // sel_ticket[0..2]: the small class, the big class' two passes
+    int32_t *req_list;             // the slots requested for the next build, in no particular order: entries [0, ctr->ext_n_req) are this round's
+    int32_t *rtask;                // per slot, written by the build of bwams_extend_run: index of the slot's right task or -1 (nullptr: not kept)
     DevCounters *ctr;
 };
 void launch_ext_plan(const ExtArgs &A, int extend_all, hipStream_t st);
-void launch_ext_widen(const ExtArgs &A, int64_t *wide, hipStream_t st);
-void launch_ext_build(const ExtArgs &A, const int64_t *offs, bwams_seqpair_t *left, uint8_t *lref, uint8_t *lqer,
-                      bwams_seqpair_t *right, uint8_t *rref, uint8_t *rqer, int64_t *lsrc, int64_t *rsrc, int cu_count, hipStream_t st);
-// after one extension attempt at band width w: settle finished tasks, queue the others for the next width
+// task sizes (the six rows of cnt) of n slots — list[i], or slot i where it is requested when list is null — widened for the scans
+void launch_ext_widen(const ExtArgs &A, const int32_t *list, int64_t n, int64_t *wide, hipStream_t st);
+// SeqPair records (and, without lsrc / rsrc, sequence copies) of n slots: list[i], or the requested ones among slots [0, n) when list is
+// null.  offs (six scanned rows of n + 1) fixes task indices and byte offsets; offs == nullptr (in-place tasks only): task indices
+// are reserved from ctr->ext_head, so the order of the tasks is unspecified.
+void launch_ext_build(const ExtArgs &A, const int32_t *list, int64_t n, const int64_t *offs, bwams_seqpair_t *left, uint8_t *lref, uint8_t *lqer,
+                      bwams_seqpair_t *right, uint8_t *rref, uint8_t *rqer, int64_t *lsrc, int64_t *rsrc, hipStream_t st);
+// after one extension attempt at band width w: settle finished tasks, queue the others for the next width.  A settled left task hands
+// its score to the slot's right task (rpairs[A.rtask[slot]].h0) when rpairs is given.
 void launch_ext_post(const ExtArgs &A, int right, const bwams_seqpair_t *pairs, int64_t n, int w, int last_try,
-                     bwams_seqpair_t *retry, unsigned long long *n_retry, hipStream_t st);
-void launch_ext_right_h0(const ExtArgs &A, bwams_seqpair_t *right, int64_t n, hipStream_t st);
+                     bwams_seqpair_t *retry, unsigned long long *n_retry, bwams_seqpair_t *rpairs, hipStream_t st);
 void launch_ext_heavy_list(const ExtArgs &A, hipStream_t st);
 int launch_ext_select(const ExtArgs &A, int cu_count, hipStream_t st, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join);
 void launch_ext_request_rest(const ExtArgs &A, hipStream_t st);

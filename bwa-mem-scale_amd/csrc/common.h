@@ -155,9 +155,15 @@ struct DevCounters {
     unsigned long long chain_class[10];  // chaining: reads with more seeds than the L, L1, M, M1, S, lane-tier, XL, L2, M2 and XL2 limits
     unsigned long long chain_ticket[10]; // chaining: work cursors of the wave kernels
     unsigned long long heavy_tickets[6]; // chaining: work cursors of chain_heavy_kernel's size classes (five used)
-    unsigned long long n_retry;          // extension: tasks queued for the next band width
-    unsigned long long n_req;            // extension: seeds requested by the last selection
-    unsigned long long sel_heavy, sel_ticket, sel_ticket2, sel_ticket3;   // extension: reads of the selection's wave tier; work cursors: the small class, the big class' two passes
+    unsigned long long sel_heavy;        // extension: reads of the selection's wave tier
+    // extension, the counters of ONE round (bwams_extend_run clears the block with one memset before whoever requests — the plan,
+    // then each selection — and copies its first three words back in one copy):
+    unsigned long long ext_n_req;        // slots appended to the request list (its cursor)
+    unsigned long long ext_n_rest;       // slots behind the requests of the last selection (an upper bound of the undecided seeds)
+    unsigned long long ext_n_tasks;      // tasks of the requested slots: left in the low, right in the high 32 bits
+    unsigned long long ext_head[2];      // task indices handed out by the build (left, right)
+    unsigned long long ext_sel_ticket[3];   // work cursors of the selection's wave tier: the small class, the big class' two passes
+    unsigned long long ext_n_retry[2];   // tasks queued for the next band width (left, right)
     unsigned long long dedup_heavy, dedup_ticket, dedup_light;   // dedup: reads for the wave tier, its work cursor, reads for the lane tier
     unsigned long long chain_redo, chain_redo_ticket;   // chaining: reads the ordered-array attempt gave up on, work cursor
     unsigned long long pair_heavy, pair_ticket;   // mem_mark_primary_se: reads of the wave tier, its work cursor
@@ -166,7 +172,6 @@ struct DevCounters {
     unsigned long long dedup_ticket2, dedup_ticket3;    // dedup: work cursors of the wave tier's smaller instances
     unsigned long long ert_kmer, ert_nodes, ert_ref;   // ERT profile kernel: k-mer entries read, tree records decoded, text bytes compared
     unsigned long long work_head3, n_ext3, n_blk3, n_smem3;   // SMEM round 3 (it may run beside round 2): its own cursor and counts, folded in by mark_kernel(3)
-    unsigned long long n_rest;           // extension: slots behind the requests of the last selection (an upper bound of the undecided seeds)
     unsigned long long ert_ticket;       // ERT walk: work cursor of ert_profile_kernel (groups of 64 read positions)
     unsigned long long bwd_items, bwd_entries, bwd_ticket;   // SMEM search: backward phases handed to the wave kernel, their list entries, its work cursor
     unsigned long long bwd_items_s, bwd_ticket_s;            // ... the short lists (smem_bwd_group_kernel): slots handed out, work cursor

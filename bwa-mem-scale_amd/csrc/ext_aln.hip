@@ -51,51 +51,86 @@ __device__ __forceinline__ int seedcov(const bwams_alnreg_t &a, const bwams_chai
     return cov;
 }
 
-// lane per chain: window, seed order, regions, task sizes
-__global__ void ext_plan_kernel(ExtArgs A, int extend_all) {
+// Requests are APPENDED, never searched for: whoever sets kExtReq on a slot puts the slot on A.req_list and adds its left / right
+// task counts to ctr->ext_n_tasks, so that the build starts a lane per requested slot and the host learns the next round's sizes
+// from three words.  Every thread of the block calls this once (n_mine = 0: nothing to append); one global atomic pair per block.
+__device__ __forceinline__ unsigned long long ext_block_reserve(unsigned n_mine, unsigned nl, unsigned nr, DevCounters *ctr) {
+    __shared__ unsigned int l_n[3];
+    __shared__ unsigned long long l_base;
+    if (threadIdx.x < 3) l_n[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned off = 0;
+    if (n_mine) {
+        off = atomicAdd(&l_n[0], n_mine);
+        if (nl) atomicAdd(&l_n[1], nl);
+        if (nr) atomicAdd(&l_n[2], nr);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && l_n[0]) {
+        l_base = atomicAdd(&ctr->ext_n_req, (unsigned long long)l_n[0]);
+        atomicAdd(&ctr->ext_n_tasks, (unsigned long long)l_n[1] | ((unsigned long long)l_n[2] << 32));
+    }
+    __syncthreads();
+    return l_base + off;
+}
+
+// lane per chain: window, seed order, regions, task sizes, the first round's requests
+__global__ __launch_bounds__(256) void ext_plan_kernel(ExtArgs A, int extend_all) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= A.n_chains) return;
-    const bwams_chain_t c = A.chains[j];
-    const int r = c.seqid;
-    const int l_query = (int)(A.cum[r + 1] - A.cum[r]);
+    bwams_chain_t c;
+    c.n = 0;
+    if (j < A.n_chains) c = A.chains[j];
+    const bool live = j < A.n_chains && c.n > 0;
+    const int r = live ? c.seqid : 0;
+    const int l_query = live ? (int)(A.cum[r + 1] - A.cum[r]) : 0;
     const int64_t l_pac = A.bns.l_pac;
-    bwams_chain_seed_t *cs = A.seeds + c.seed_off;
-    if (c.n == 0) return;
-
+    bwams_chain_seed_t *cs = A.seeds + (live ? c.seed_off : 0);
+    uint32_t *srt = A.srt + (live ? c.seed_off : 0);
     int64_t r0 = l_pac << 1, r1 = 0;
-    for (int i = 0; i < c.n; ++i) {
-        const int64_t rb = cs[i].rbeg;
-        const int qb = cs[i].qbeg, ln = cs[i].len;
-        const int64_t b = rb - (qb + cal_max_gap(A.opt, qb));
-        const int64_t e = rb + ln + ((l_query - qb - ln) + cal_max_gap(A.opt, l_query - qb - ln));
-        r0 = r0 < b ? r0 : b;
-        r1 = r1 > e ? r1 : e;
-    }
-    r0 = r0 > 0 ? r0 : 0;
-    r1 = r1 < (l_pac << 1) ? r1 : (l_pac << 1);
-    const int64_t rbeg0 = cs[0].rbeg;
-    if (r0 < l_pac && l_pac < r1) {
-        if (rbeg0 < l_pac) r1 = l_pac;
-        else r0 = l_pac;
-    }
-    {   // bns_fetch_seq_v2: clip to the reference sequence holding the first seed
-        const bool is_rev = rbeg0 >= l_pac;
-        const int rid = pos2rid(A.bns, is_rev ? (l_pac << 1) - 1 - rbeg0 : rbeg0);
-        int64_t far_beg = A.bns.contigs[rid].offset, far_end = far_beg + A.bns.contigs[rid].len;
-        if (is_rev) { const int64_t t0 = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - t0; }
-        r0 = r0 > far_beg ? r0 : far_beg;
-        r1 = r1 < far_end ? r1 : far_end;
-    }
-    A.rmax[2 * j] = r0; A.rmax[2 * j + 1] = r1;
+    unsigned my_req = 0, my_nl = 0, my_nr = 0;
+    if (live) {
+        for (int i = 0; i < c.n; ++i) {
+            const int64_t rb = cs[i].rbeg;
+            const int qb = cs[i].qbeg, ln = cs[i].len;
+            const int64_t b = rb - (qb + cal_max_gap(A.opt, qb));
+            const int64_t e = rb + ln + ((l_query - qb - ln) + cal_max_gap(A.opt, l_query - qb - ln));
+            r0 = r0 < b ? r0 : b;
+            r1 = r1 > e ? r1 : e;
+        }
+        r0 = r0 > 0 ? r0 : 0;
+        r1 = r1 < (l_pac << 1) ? r1 : (l_pac << 1);
+        const int64_t rbeg0 = cs[0].rbeg;
+        if (r0 < l_pac && l_pac < r1) {
+            if (rbeg0 < l_pac) r1 = l_pac;
+            else r0 = l_pac;
+        }
+        {   // bns_fetch_seq_v2: clip to the reference sequence holding the first seed
+            const bool is_rev = rbeg0 >= l_pac;
+            const int rid = pos2rid(A.bns, is_rev ? (l_pac << 1) - 1 - rbeg0 : rbeg0);
+            int64_t far_beg = A.bns.contigs[rid].offset, far_end = far_beg + A.bns.contigs[rid].len;
+            if (is_rev) { const int64_t t0 = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - t0; }
+            r0 = r0 > far_beg ? r0 : far_beg;
+            r1 = r1 < far_end ? r1 : far_end;
+        }
+        A.rmax[2 * j] = r0; A.rmax[2 * j + 1] = r1;
 
-    // srt: seed indices by ascending (score, index) — ks_introsort_64 over distinct keys
-    uint32_t *srt = A.srt + c.seed_off;
-    for (int i = 0; i < c.n; ++i) {
-        const int sc = cs[i].score;
-        int p = i;
-        while (p > 0 && cs[srt[p - 1]].score > sc) { srt[p] = srt[p - 1]; --p; }
-        srt[p] = (uint32_t)i;
+        // srt: seed indices by ascending (score, index) — ks_introsort_64 over distinct keys
+        for (int i = 0; i < c.n; ++i) {
+            const int sc = cs[i].score;
+            int p = i;
+            while (p > 0 && cs[srt[p - 1]].score > sc) { srt[p] = srt[p - 1]; --p; }
+            srt[p] = (uint32_t)i;
+        }
+        // the first round extends the first seed visited of every chain (every seed when extend_all): those are the seeds most
+        // likely to survive the containment test.  Counted here, appended below once the block has its place in the list.
+        for (int k = c.n - 1; k >= (extend_all ? 0 : c.n - 1); --k) {
+            const bwams_chain_seed_t *s = &cs[srt[k]];
+            const unsigned nl = s->qbeg != 0, nr = s->qbeg + s->len != l_query;
+            my_req += nl | nr; my_nl += nl; my_nr += nr;
+        }
     }
+    unsigned long long at = ext_block_reserve(my_req, my_nl, my_nr, A.ctr);
+    if (!live) return;
 
     const int64_t reg0 = A.seed_off[r];
     const int64_t N = A.n_seeds;
@@ -131,28 +166,32 @@ __global__ void ext_plan_kernel(ExtArgs A, int extend_all) {
         A.regs[p] = a;
         A.cnt[0 * N + p] = nl; A.cnt[1 * N + p] = lq; A.cnt[2 * N + p] = lr;
         A.cnt[3 * N + p] = nr; A.cnt[4 * N + p] = rq; A.cnt[5 * N + p] = rr;
-        // the first round extends the first seed visited of every chain (every seed when extend_all):
-        // those are the seeds most likely to survive the containment test
         int st = 0;
         if (!nl && !nr) st = kExtDone;                       // nothing to extend
-        else if (extend_all || k == c.n - 1) st = kExtReq;
+        else if (extend_all || k == c.n - 1) { st = kExtReq; A.req_list[at++] = (int32_t)p; }
         A.state[p] = st;
     }
 }
 
-// task sizes of the seeds requested this round, widened for the scans
-__global__ void ext_widen_kernel(const int32_t *cnt, const int32_t *state, int64_t n, int64_t *wide) {
+// task sizes of n slots — list[i], or slot i where it is requested — widened for the scans
+__global__ void ext_widen_kernel(const int32_t *cnt, const int32_t *state, const int32_t *list, int64_t n_seeds, int64_t n, int64_t *wide) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= 6 * (n + 1)) return;
     const int64_t row = g / (n + 1), i = g - row * (n + 1);
-    wide[g] = (i < n && (state[i] & kExtReq)) ? (int64_t)cnt[row * n + i] : 0;
+    int64_t v = 0;
+    if (i < n) {
+        const int64_t p = list ? list[i] : i;
+        if (list || (state[p] & kExtReq)) v = cnt[row * n_seeds + p];
+    }
+    wide[g] = v;
 }
 
-// SeqPair records and sequence copies.  A wavefront takes 64 slots at a time: every lane looks at one slot's state (most slots are
-// not requested in a round), a requested slot's lane fetches what the slot needs — chain, place in the chain's order, seed, offsets:
-// dependent loads, in flight for all the requested slots of the 64 together — and writes its SeqPair records; then the wave copies
-// the bytes of one requested slot after the other, the slot's fields broadcast from its lane.  (A wave per slot paid the chain of
-// dependent loads once per slot: 5.2 ms per step for 3.6 M tasks among 21.9 M slots.)
+// SeqPair records and sequence copies: a lane per slot of the round — list[i], the slots that were requested (bwams_extend_run: a
+// later round holds a few thousand of the chunk's millions), or with list == nullptr every slot, of which the requested ones are
+// taken (bwams_extend_build).  The slot's lane fetches what the slot needs — chain, place in the chain's order, seed: dependent
+// loads, in flight for the 64 slots of a wave together — and writes its SeqPair records; then the wave copies the bytes of one slot
+// after the other, the slot's fields broadcast from its lane.  (A wave per slot paid the chain of dependent loads once per slot:
+// 5.2 ms per step for 3.6 M tasks among 21.9 M slots.)
 __device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
     return ((int64_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)v, src);
 }
@@ -160,82 +199,118 @@ __device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
 // chunk's base codes and the window in the resident .0123 text, read backwards for a left extension; what is written per task is the two
 // start offsets {query, target} and no byte is copied (the copies were 2.2 of the 3.9 ms this stage took per million reads).  The flat
 // buffers of the SeqPair boundary are still built for bwams_extend_build / bwams_extend_tasks_fetch.
-__global__ __launch_bounds__(256) void ext_build_kernel(ExtArgs A, const int64_t *__restrict__ offs, bwams_seqpair_t *left,
-                                                        uint8_t *lref, uint8_t *lqer, bwams_seqpair_t *right, uint8_t *rref,
-                                                        uint8_t *rqer, int64_t *lsrc, int64_t *rsrc) {
+// offs != nullptr: six scanned rows of n + 1 give task indices and byte offsets, so tasks are in the order of the slots given.
+// offs == nullptr (in place only, nothing needs a byte offset): the block reserves its task indices from ctr->ext_head — waves count
+// into LDS, one global atomic per side and block — and the order of the tasks is whatever the blocks' atomics made it.
+constexpr int kBuildBlock = 1024;
+__global__ __launch_bounds__(kBuildBlock) void ext_build_kernel(ExtArgs A, const int32_t *__restrict__ list, int64_t n, const int64_t *__restrict__ offs,
+                                                               bwams_seqpair_t *left, uint8_t *lref, uint8_t *lqer, bwams_seqpair_t *right,
+                                                               uint8_t *rref, uint8_t *rqer, int64_t *lsrc, int64_t *rsrc) {
+    __shared__ unsigned int l_cnt[2];
+    __shared__ unsigned long long l_base[2];
     const int lane = threadIdx.x & 63;
-    const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    const int64_t N = A.n_seeds, n1 = N + 1;
-    for (int64_t p0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 64; p0 < N; p0 += n_waves * 64) {
-        const int64_t p = p0 + lane;
-        const int st = p < N ? A.state[p] : 0;
-        const bool req = (st & kExtReq) != 0;
-        // left: query bytes enc[l_qsrc - t], t < l_ql, to lqer[l_qo + t]; reference bytes ref[l_rsrc - t], t < l_rl, to lref[l_ro + t]
-        int64_t l_qsrc = 0, l_rsrc = 0, l_qo = 0, l_ro = 0, r_qsrc = 0, r_rsrc = 0, r_qo = 0, r_ro = 0;
-        int l_ql = 0, l_rl = 0, r_ql = 0, r_rl = 0;
-        if (req) {
-            const int nl = A.cnt[0 * N + p], nr = A.cnt[3 * N + p];
-            A.state[p] = (st & ~kExtReq) | kExtDone;      // extended by the time the next selection runs
-            const int64_t j = A.regs[p].chain;
-            const bwams_chain_t c = A.chains[j];
-            const int k = c.n - 1 - (int)(p - c.seed_off);
-            const bwams_chain_seed_t sd = A.seeds[c.seed_off + A.srt[c.seed_off + k]];
-            const int r = c.seqid;
-            const int64_t qoff = A.cum[r];
-            const int l_query = (int)(A.cum[r + 1] - qoff);
-            const int64_t r0 = A.rmax[2 * j];
-            if (nl) {
-                const int64_t ti = offs[0 * n1 + p];
-                l_qo = offs[1 * n1 + p]; l_ro = offs[2 * n1 + p];
-                l_ql = sd.qbeg; l_rl = (int)(sd.rbeg - r0);
-                l_qsrc = qoff + sd.qbeg - 1; l_rsrc = sd.rbeg - 1;
-                bwams_seqpair_t sp;
-                sp.idr = (int32_t)l_ro; sp.idq = (int32_t)l_qo; sp.id = (int32_t)ti;
-                sp.len1 = l_rl; sp.len2 = l_ql; sp.h0 = sd.len * A.opt.a; sp.seqid = r; sp.regid = sd.aln;
-                sp.score = sp.tle = sp.gtle = sp.qle = sp.gscore = sp.max_off = 0;
-                left[ti] = sp;
-                if (lsrc) { lsrc[2 * ti] = l_qsrc; lsrc[2 * ti + 1] = l_rsrc; }
-            }
-            if (nr) {
-                const int64_t ti = offs[3 * n1 + p];
-                r_qo = offs[4 * n1 + p]; r_ro = offs[5 * n1 + p];
-                const int qe = sd.qbeg + sd.len;
-                r_ql = l_query - qe; r_rl = A.cnt[5 * N + p];
-                r_qsrc = qoff + qe; r_rsrc = sd.rbeg + sd.len;
-                bwams_seqpair_t sp;
-                sp.idr = (int32_t)r_ro; sp.idq = (int32_t)r_qo; sp.id = (int32_t)ti;
-                sp.len1 = r_rl; sp.len2 = r_ql; sp.h0 = H0_; sp.seqid = r; sp.regid = sd.aln;
-                sp.score = sp.tle = sp.gtle = sp.qle = sp.gscore = sp.max_off = 0;
-                right[ti] = sp;
-                if (rsrc) { rsrc[2 * ti] = r_qsrc; rsrc[2 * ti + 1] = r_rsrc; }
-            }
+    const int64_t N = A.n_seeds, n1 = n + 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = i < n ? (list ? (int64_t)list[i] : i) : 0;
+    const int st = i < n ? A.state[p] : 0;
+    const bool req = (st & kExtReq) != 0;
+    const int nl = req ? A.cnt[0 * N + p] : 0, nr = req ? A.cnt[3 * N + p] : 0;
+    int64_t ti_l = 0, ti_r = 0;
+    if (offs) {
+        if (nl) ti_l = offs[0 * n1 + i];
+        if (nr) ti_r = offs[3 * n1 + i];
+    } else {
+        if (threadIdx.x < 2) l_cnt[threadIdx.x] = 0;
+        __syncthreads();
+        unsigned int off_l = 0, off_r = 0;
+        const unsigned long long ml = __ballot(nl != 0), mr = __ballot(nr != 0);
+        if (ml) {
+            const int leader = __ffsll((long long)ml) - 1;
+            unsigned int wbase = 0;
+            if (lane == leader) wbase = atomicAdd(&l_cnt[0], (unsigned int)__popcll(ml));
+            off_l = (unsigned int)__shfl((int)wbase, leader) + (unsigned int)__popcll(ml & ((1ull << lane) - 1ull));
         }
-        unsigned long long m = lsrc ? 0ull : __ballot(req);
-        while (m) {
-            const int src = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const int ql = __shfl(l_ql, src), rl = __shfl(l_rl, src), qr = __shfl(r_ql, src), rr = __shfl(r_rl, src);
-            if (ql | rl) {
-                const int64_t qs = shfl64(l_qsrc, src), rs = shfl64(l_rsrc, src), qo = shfl64(l_qo, src), ro = shfl64(l_ro, src);
-                for (int t = lane; t < ql; t += 64) lqer[qo + t] = A.enc[qs - t];
-                for (int t = lane; t < rl; t += 64) lref[ro + t] = A.ref[rs - t];
-            }
-            if (qr | rr) {
-                const int64_t qs = shfl64(r_qsrc, src), rs = shfl64(r_rsrc, src), qo = shfl64(r_qo, src), ro = shfl64(r_ro, src);
-                for (int t = lane; t < qr; t += 64) rqer[qo + t] = A.enc[qs + t];
-                for (int t = lane; t < rr; t += 64) rref[ro + t] = A.ref[rs + t];
-            }
+        if (mr) {
+            const int leader = __ffsll((long long)mr) - 1;
+            unsigned int wbase = 0;
+            if (lane == leader) wbase = atomicAdd(&l_cnt[1], (unsigned int)__popcll(mr));
+            off_r = (unsigned int)__shfl((int)wbase, leader) + (unsigned int)__popcll(mr & ((1ull << lane) - 1ull));
+        }
+        __syncthreads();
+        if (threadIdx.x < 2 && l_cnt[threadIdx.x]) l_base[threadIdx.x] = atomicAdd(&A.ctr->ext_head[threadIdx.x], (unsigned long long)l_cnt[threadIdx.x]);
+        __syncthreads();
+        if (nl) ti_l = (int64_t)l_base[0] + off_l;
+        if (nr) ti_r = (int64_t)l_base[1] + off_r;
+    }
+    // left: query bytes enc[l_qsrc - t], t < l_ql, to lqer[l_qo + t]; reference bytes ref[l_rsrc - t], t < l_rl, to lref[l_ro + t]
+    int64_t l_qsrc = 0, l_rsrc = 0, l_qo = 0, l_ro = 0, r_qsrc = 0, r_rsrc = 0, r_qo = 0, r_ro = 0;
+    int l_ql = 0, l_rl = 0, r_ql = 0, r_rl = 0;
+    if (req) {
+        A.state[p] = (st & ~kExtReq) | kExtDone;      // extended by the time the next selection runs
+        const int64_t j = A.regs[p].chain;
+        const bwams_chain_t c = A.chains[j];
+        const int k = c.n - 1 - (int)(p - c.seed_off);
+        const bwams_chain_seed_t sd = A.seeds[c.seed_off + A.srt[c.seed_off + k]];
+        const int r = c.seqid;
+        const int64_t qoff = A.cum[r];
+        const int l_query = (int)(A.cum[r + 1] - qoff);
+        const int64_t r0 = A.rmax[2 * j];
+        if (A.rtask) A.rtask[p] = nr ? (int32_t)ti_r : -1;
+        if (nl) {
+            if (offs) { l_qo = offs[1 * n1 + i]; l_ro = offs[2 * n1 + i]; }
+            l_ql = sd.qbeg; l_rl = (int)(sd.rbeg - r0);
+            l_qsrc = qoff + sd.qbeg - 1; l_rsrc = sd.rbeg - 1;
+            bwams_seqpair_t sp;
+            sp.idr = (int32_t)l_ro; sp.idq = (int32_t)l_qo; sp.id = (int32_t)ti_l;
+            sp.len1 = l_rl; sp.len2 = l_ql; sp.h0 = sd.len * A.opt.a; sp.seqid = r; sp.regid = sd.aln;
+            sp.score = sp.tle = sp.gtle = sp.qle = sp.gscore = sp.max_off = 0;
+            left[ti_l] = sp;
+            if (lsrc) { lsrc[2 * ti_l] = l_qsrc; lsrc[2 * ti_l + 1] = l_rsrc; }
+        }
+        if (nr) {
+            if (offs) { r_qo = offs[4 * n1 + i]; r_ro = offs[5 * n1 + i]; }
+            const int qe = sd.qbeg + sd.len;
+            r_ql = l_query - qe; r_rl = A.cnt[5 * N + p];
+            r_qsrc = qoff + qe; r_rsrc = sd.rbeg + sd.len;
+            bwams_seqpair_t sp;
+            sp.idr = (int32_t)r_ro; sp.idq = (int32_t)r_qo; sp.id = (int32_t)ti_r;
+            // the right extension starts from the score the left one reached (bwamem.cpp:3425-3430): written by the left task's
+            // ext_post_kernel when there is one, and known already — the seed's own score, as the plan set it — when there is none
+            sp.len1 = r_rl; sp.len2 = r_ql; sp.h0 = (A.rtask && !nl) ? sd.len * A.opt.a : H0_; sp.seqid = r; sp.regid = sd.aln;
+            sp.score = sp.tle = sp.gtle = sp.qle = sp.gscore = sp.max_off = 0;
+            right[ti_r] = sp;
+            if (rsrc) { rsrc[2 * ti_r] = r_qsrc; rsrc[2 * ti_r + 1] = r_rsrc; }
+        }
+    }
+    unsigned long long m = lsrc ? 0ull : __ballot(req);
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int ql = __shfl(l_ql, src), rl = __shfl(l_rl, src), qr = __shfl(r_ql, src), rr = __shfl(r_rl, src);
+        if (ql | rl) {
+            const int64_t qs = shfl64(l_qsrc, src), rs = shfl64(l_rsrc, src), qo = shfl64(l_qo, src), ro = shfl64(l_ro, src);
+            for (int t = lane; t < ql; t += 64) lqer[qo + t] = A.enc[qs - t];
+            for (int t = lane; t < rl; t += 64) lref[ro + t] = A.ref[rs - t];
+        }
+        if (qr | rr) {
+            const int64_t qs = shfl64(r_qsrc, src), rs = shfl64(r_rsrc, src), qo = shfl64(r_qo, src), ro = shfl64(r_ro, src);
+            for (int t = lane; t < qr; t += 64) rqer[qo + t] = A.enc[qs + t];
+            for (int t = lane; t < rr; t += 64) rref[ro + t] = A.ref[rs + t];
         }
     }
 }
 
 // lane per task, after one extension attempt
-__global__ void ext_post_kernel(ExtArgs A, int right, const bwams_seqpair_t *__restrict__ pairs, int64_t n, int w, int last_try,
-                                bwams_seqpair_t *retry, unsigned long long *n_retry) {
+__global__ __launch_bounds__(256) void ext_post_kernel(ExtArgs A, int right, const bwams_seqpair_t *__restrict__ pairs, int64_t n, int w, int last_try,
+                                bwams_seqpair_t *__restrict__ retry, unsigned long long *n_retry, bwams_seqpair_t *__restrict__ rpairs) {
     const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= n) return;
-    const bwams_seqpair_t sp = pairs[l];
-    bwams_alnreg_t *ap = &A.regs[A.seed_off[sp.seqid] + sp.regid];
+    // the fields the bookkeeping reads, not a copy of the record: a retried task's record is copied from where it lies
+    struct { int32_t seqid, regid, h0, score, tle, gtle, qle, gscore, max_off; } sp;
+    sp.seqid = pairs[l].seqid; sp.regid = pairs[l].regid; sp.h0 = pairs[l].h0; sp.score = pairs[l].score; sp.tle = pairs[l].tle;
+    sp.gtle = pairs[l].gtle; sp.qle = pairs[l].qle; sp.gscore = pairs[l].gscore; sp.max_off = pairs[l].max_off;
+    const int64_t slot = A.seed_off[sp.seqid] + sp.regid;
+    bwams_alnreg_t *ap = &A.regs[slot];
     bwams_alnreg_t a = *ap;
     const int prev = a.score;
     a.score = sp.score;
@@ -248,6 +323,8 @@ __global__ void ext_post_kernel(ExtArgs A, int right, const bwams_seqpair_t *__r
                 a.qb = 0; a.rb -= sp.gtle;
                 a.truesc = sp.gscore;
             }
+            // the right extension starts from the score the left one reached (bwamem.cpp:3425-3430)
+            if (rpairs) { const int32_t rt = A.rtask[slot]; if (rt >= 0) rpairs[rt].h0 = a.score; }
         } else {
             if (sp.gscore <= 0 || sp.gscore <= a.score - A.opt.pen_clip3) {
                 a.qe += sp.qle; a.re += sp.tle;
@@ -262,16 +339,8 @@ __global__ void ext_post_kernel(ExtArgs A, int right, const bwams_seqpair_t *__r
         *ap = a;
     } else {
         ap->score = a.score;
-        const unsigned long long slot = atomicAdd(n_retry, 1ull);
-        retry[slot] = sp;
+        retry[atomicAdd(n_retry, 1ull)] = pairs[l];
     }
-}
-
-// the right extension starts from the score the left one reached (bwamem.cpp:3425-3430)
-__global__ void ext_right_h0_kernel(ExtArgs A, bwams_seqpair_t *right, int64_t n) {
-    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= n) return;
-    right[l].h0 = A.regs[A.seed_off[right[l].seqid] + right[l].regid].score;
 }
 
 // ---- purge: drop seeds (and their regions) that an earlier region already explains ----------
@@ -333,6 +402,7 @@ __global__ __launch_bounds__(64) void ext_select_kernel(ExtArgs A) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool req = false;
     int rest = 0;
+    int64_t req_p = 0;
     if (r < A.nseq) {
         const int64_t reg0 = A.seed_off[r];
         const int av_n = (int)(A.seed_off[r + 1] - reg0);
@@ -359,7 +429,7 @@ __global__ __launch_bounds__(64) void ext_select_kernel(ExtArgs A) {
                     A.state[p] = st | kExtPurged;
                     continue;
                 }
-                if (!(st & kExtDone)) { A.state[p] = st | kExtReq; req = true; rest = av_n - t - 1; break; }
+                if (!(st & kExtDone)) { A.state[p] = st | kExtReq; req = true; req_p = p; rest = av_n - t - 1; break; }
                 const bwams_alnreg_t *a = &A.regs[p];
                 KReg q;
                 q.rb = a->rb; q.re = a->re; q.qb = a->qb; q.qe = a->qe; q.seedlen0 = a->seedlen0; q.w = a->w;
@@ -370,13 +440,20 @@ __global__ __launch_bounds__(64) void ext_select_kernel(ExtArgs A) {
             A.lim[r] = lim;
         }
     }
+    // the wave's requests go onto the list together: one atomic for their places, one for their task counts
     const unsigned long long m = __ballot(req);
     if (m) {
-        for (int o = 32; o > 0; o >>= 1) rest += __shfl_xor(rest, o);
-        if ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) {
-            atomicAdd(&A.ctr->n_req, (unsigned long long)__popcll(m));
-            if (rest) atomicAdd(&A.ctr->n_rest, (unsigned long long)rest);
+        const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
+        int nl = req ? A.cnt[0 * A.n_seeds + req_p] : 0, nr = req ? A.cnt[3 * A.n_seeds + req_p] : 0;
+        for (int o = 32; o > 0; o >>= 1) { rest += __shfl_xor(rest, o); nl += __shfl_xor(nl, o); nr += __shfl_xor(nr, o); }
+        unsigned long long base = 0;
+        if (lane == leader) {
+            base = atomicAdd(&A.ctr->ext_n_req, (unsigned long long)__popcll(m));
+            atomicAdd(&A.ctr->ext_n_tasks, (unsigned long long)(unsigned)nl | ((unsigned long long)(unsigned)nr << 32));
+            if (rest) atomicAdd(&A.ctr->ext_n_rest, (unsigned long long)rest);
         }
+        base = (unsigned long long)shfl64((int64_t)base, leader);
+        if (req) A.req_list[base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = (int32_t)req_p;
     }
 }
 
@@ -423,6 +500,7 @@ __device__ __forceinline__ bool purge_keep_anyway_w(const bwams_chain_seed_t &s,
 // The top class holds a few dozen reads per million on a genome like the bench's, so its longest walk starts when the kernel does; on
 // a repeat-heavy genome (27 k reads per million beyond 128 regions) the middle class is what keeps enough wavefronts on them.
 constexpr int kSelCap[3] = {256, 640, 1280};
+constexpr int kSelSteps = 4;             // steps of the wave tier's region scan taken together
 __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, int cap, unsigned long long *ticket) {
     extern __shared__ __align__(16) unsigned char l_sel_raw[];
     KReg *lk = reinterpret_cast<KReg *>(l_sel_raw);
@@ -475,16 +553,28 @@ __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, 
                 const unsigned long long Tb = __builtin_amdgcn_s_memtime();
                 ++n_slots;
 #endif
-                for (int base = 0; base < lim && !brk; base += 64) {          // the kept regions, 64 at a time
-                    const int i = base + lane;
-                    int cls = 0;
-                    if (i < lim) {
-                        const KReg q = in_lds ? lk[i] : kreg[i];
-                        cls = purge_class(A.opt, s, l_query, q.rb, q.re, q.qb, q.qe, q.seedlen0, q.w);
+                // The kept regions, 64 per step, kSelSteps steps together (`brk` is an "any" over the regions, so the steps do not depend
+                // on one another): their loads and the containment test — integer compares, which almost every region fails — are in
+                // flight at once and without a branch; the gap arithmetic (cal_max_gap: two double divisions) runs as before, and
+                // only in a step where some region contains the seed.  One ballot per kSelSteps steps.
+                for (int base = 0; base < lim && !brk; base += 64 * kSelSteps) {
+                    KReg q[kSelSteps];
+                    bool go[kSelSteps];
+#pragma unroll
+                    for (int u = 0; u < kSelSteps; ++u) {
+                        const int i = base + u * 64 + lane;
+                        const int ii = i < lim ? i : lim - 1;                 // a valid region for every lane
+                        q[u] = in_lds ? lk[ii] : kreg[ii];
+                        go[u] = (i < lim) & !((q[u].qb == -1) & (q[u].qe == -1)) &
+                                !((s.rbeg < q[u].rb) | (s.rbeg + s.len > q[u].re) | (s.qbeg < q[u].qb) | (s.qbeg + s.len > q[u].qe));
                     }
-                    brk = __ballot(cls == 2) != 0;
+                    bool hit = false;
+#pragma unroll
+                    for (int u = 0; u < kSelSteps; ++u)
+                        if (go[u]) hit |= purge_class(A.opt, s, l_query, q[u].rb, q[u].re, q[u].qb, q[u].qe, q[u].seedlen0, q[u].w) == 2;
+                    brk = __ballot(hit) != 0;
 #ifdef BWAMS_SELDBG
-                    ++n_chunks;
+                    n_chunks += kSelSteps;
 #endif
                 }
 #ifdef BWAMS_SELDBG
@@ -502,8 +592,10 @@ __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, 
                 if (!(st & kExtDone)) {
                     if (lane == 0) {
                         A.state[p] = st | kExtReq;
-                        atomicAdd(&A.ctr->n_req, 1ull);
-                        if (av_n - (t + j) - 1 > 0) atomicAdd(&A.ctr->n_rest, (unsigned long long)(av_n - (t + j) - 1));
+                        A.req_list[atomicAdd(&A.ctr->ext_n_req, 1ull)] = (int32_t)p;
+                        atomicAdd(&A.ctr->ext_n_tasks, (unsigned long long)(unsigned)A.cnt[0 * A.n_seeds + p] |
+                                                           ((unsigned long long)(unsigned)A.cnt[3 * A.n_seeds + p] << 32));
+                        if (av_n - (t + j) - 1 > 0) atomicAdd(&A.ctr->ext_n_rest, (unsigned long long)(av_n - (t + j) - 1));
                     }
                     stop = true;
                     break;
@@ -534,56 +626,54 @@ __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, 
 }
 
 // after too many rounds: request every seed that is still undecided and unextended
-__global__ void ext_request_rest_kernel(ExtArgs A) {
+__global__ __launch_bounds__(256) void ext_request_rest_kernel(ExtArgs A) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= A.n_seeds) return;
-    const int st = A.state[p];
-    if (!(st & (kExtKept | kExtPurged | kExtDone | kExtReq))) A.state[p] = st | kExtReq;
+    const int st = p < A.n_seeds ? A.state[p] : kExtDone;
+    const bool want = !(st & (kExtKept | kExtPurged | kExtDone | kExtReq));
+    const unsigned nl = want ? (unsigned)A.cnt[0 * A.n_seeds + p] : 0u, nr = want ? (unsigned)A.cnt[3 * A.n_seeds + p] : 0u;
+    const unsigned long long at = ext_block_reserve(want ? 1u : 0u, nl, nr, A.ctr);
+    if (want) { A.state[p] = st | kExtReq; A.req_list[at] = (int32_t)p; }
 }
 
 }  // namespace
 
 void launch_ext_plan(const ExtArgs &A, int extend_all, hipStream_t st) {
-    if (A.n_chains > 0) ext_plan_kernel<<<(unsigned)((A.n_chains + 63) / 64), 64, 0, st>>>(A, extend_all);
+    if (A.n_chains > 0) ext_plan_kernel<<<(unsigned)((A.n_chains + 255) / 256), 256, 0, st>>>(A, extend_all);
 }
-void launch_ext_widen(const ExtArgs &A, int64_t *wide, hipStream_t st) {
-    const int64_t g = 6 * (A.n_seeds + 1);
-    ext_widen_kernel<<<(unsigned)((g + 255) / 256), 256, 0, st>>>(A.cnt, A.state, A.n_seeds, wide);
+void launch_ext_widen(const ExtArgs &A, const int32_t *list, int64_t n, int64_t *wide, hipStream_t st) {
+    const int64_t g = 6 * (n + 1);
+    ext_widen_kernel<<<(unsigned)((g + 255) / 256), 256, 0, st>>>(A.cnt, A.state, list, A.n_seeds, n, wide);
 }
 
-void launch_ext_build(const ExtArgs &A, const int64_t *offs, bwams_seqpair_t *left, uint8_t *lref, uint8_t *lqer,
-                      bwams_seqpair_t *right, uint8_t *rref, uint8_t *rqer, int64_t *lsrc, int64_t *rsrc, int cu_count, hipStream_t st) {
-    if (A.n_seeds <= 0) return;
-    int64_t blocks = (A.n_seeds + 255) / 256;              // a wave per 64 slots
-    if (blocks > (int64_t)cu_count * 16) blocks = (int64_t)cu_count * 16;
-    ext_build_kernel<<<(unsigned)blocks, 256, 0, st>>>(A, offs, left, lref, lqer, right, rref, rqer, lsrc, rsrc);
+void launch_ext_build(const ExtArgs &A, const int32_t *list, int64_t n, const int64_t *offs, bwams_seqpair_t *left, uint8_t *lref, uint8_t *lqer,
+                      bwams_seqpair_t *right, uint8_t *rref, uint8_t *rqer, int64_t *lsrc, int64_t *rsrc, hipStream_t st) {
+    if (n <= 0) return;
+    ext_build_kernel<<<(unsigned)((n + kBuildBlock - 1) / kBuildBlock), kBuildBlock, 0, st>>>(A, list, n, offs, left, lref, lqer, right, rref, rqer,
+                                                                                              lsrc, rsrc);
 }
 
 void launch_ext_post(const ExtArgs &A, int right, const bwams_seqpair_t *pairs, int64_t n, int w, int last_try,
-                     bwams_seqpair_t *retry, unsigned long long *n_retry, hipStream_t st) {
+                     bwams_seqpair_t *retry, unsigned long long *n_retry, bwams_seqpair_t *rpairs, hipStream_t st) {
     if (n <= 0) return;
-    ext_post_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(A, right, pairs, n, w, last_try, retry, n_retry);
-}
-
-void launch_ext_right_h0(const ExtArgs &A, bwams_seqpair_t *right, int64_t n, hipStream_t st) {
-    if (n <= 0) return;
-    ext_right_h0_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(A, right, n);
+    ext_post_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(A, right, pairs, n, w, last_try, retry, n_retry, right ? nullptr : rpairs);
 }
 
 void launch_ext_heavy_list(const ExtArgs &A, hipStream_t st) {
     if (A.nseq <= 0) return;
     ext_heavy_list_kernel<<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A);
 }
+// The top class goes first and beside the rest, on a stream of its own: its longest read is its duration.  The lane tier and the
+// two smaller classes follow one another on the main stream — together they take about as long as the top class alone, and a third
+// stream bought nothing where the process has four hardware queues: the middle class then sat in the top class's queue and started
+// when that ended (kernel trace: 1.2 ms per round).
 int launch_ext_select(const ExtArgs &A, int cu_count, hipStream_t st, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join) {
     if (A.nseq <= 0) return 0;
-    if (hipEventRecord(fork, st) != hipSuccess || hipStreamWaitEvent(aux[0], fork, 0) != hipSuccess ||
-        hipStreamWaitEvent(aux[1], fork, 0) != hipSuccess) return -1;
+    if (hipEventRecord(fork, st) != hipSuccess || hipStreamWaitEvent(aux[0], fork, 0) != hipSuccess) return -1;
     ext_select_wave_kernel<<<(unsigned)(cu_count * 3), 64, kSelCap[2] * sizeof(KReg), aux[0]>>>(A, kSelCap[1], kSelCap[2], A.sel_ticket + 2);
-    ext_select_wave_kernel<<<(unsigned)(cu_count * 7), 64, kSelCap[1] * sizeof(KReg), aux[1]>>>(A, kSelCap[0], kSelCap[1], A.sel_ticket + 1);
     ext_select_kernel<<<(unsigned)((A.nseq + 63) / 64), 64, 0, st>>>(A);
+    ext_select_wave_kernel<<<(unsigned)(cu_count * 7), 64, kSelCap[1] * sizeof(KReg), st>>>(A, kSelCap[0], kSelCap[1], A.sel_ticket + 1);
     ext_select_wave_kernel<<<(unsigned)(cu_count * 16), 64, kSelCap[0] * sizeof(KReg), st>>>(A, kLightRegs, kSelCap[0], A.sel_ticket);
-    for (int i = 0; i < 2; ++i)
-        if (hipEventRecord(join[i], aux[i]) != hipSuccess || hipStreamWaitEvent(st, join[i], 0) != hipSuccess) return -1;
+    if (hipEventRecord(join[0], aux[0]) != hipSuccess || hipStreamWaitEvent(st, join[0], 0) != hipSuccess) return -1;
     return 0;
 }
 void launch_ext_request_rest(const ExtArgs &A, hipStream_t st) {
