@@ -18,6 +18,7 @@
 
 #include "fmi_kernels.h"
 #include "ert_kernels.h"
+#include "stage_state.h"
 
 namespace bwams {
 
@@ -71,8 +72,6 @@ static int check_device(int device) {
     }
     return BWAMS_OK;
 }
-
-void chain_state_stats(const ChainState *s, bwams_stats_t *out);   // api_chain.hip
 
 int tmp_reserve(bwams_batch *b, size_t &tb) {
     if (tb > b->d_tmp.cap) {
@@ -765,24 +764,16 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
         launch_make_keys(b->d_pool.p, n_slots, b->d_keys.p, b->d_vals.p, (uint32_t)b->nseq, st);
         int rid_bits = 1;
         while (((int64_t)1 << rid_bits) <= b->nseq) rid_bits++;
-        size_t tb = 0;      // the temporary size depends on the size / bit range: ask for this call
-        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p,
-                                            (size_t)n_slots, 0, 32 + rid_bits, st));
-        if (int rc = tmp_reserve(b, tb)) return rc;
-        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp.p, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p,
-                                            (size_t)n_slots, 0, 32 + rid_bits, st));
+        if (int rc = with_tmp(b, "bwams_seed_run: radix_sort_pairs", [&](void *tmp, size_t &tb) {     // the temporary size depends on the size / bit range: ask for this call
+                return rocprim::radix_sort_pairs(tmp, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p, (size_t)n_slots, 0, 32 + rid_bits, st);
+            })) return rc;
         launch_gather_sorted(b->d_pool.p, b->d_vals2.p, n, b->d_sorted.p, with_sa ? b->d_sa_cnt.p : nullptr,
                              opt->max_occ, st);
     }
     BWAMS_HIP(hipEventRecord(b->ev[4], st));
     if (with_sa && n > 0) {
-        size_t tb = 0;
-        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
-                                          rocprim::plus<int64_t>(), st));
-        if (int rc = tmp_reserve(b, tb)) return rc;
         BWAMS_HIP(hipMemsetAsync(b->d_sa_cnt.p + n, 0, 8, st));
-        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp.p, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
-                                          rocprim::plus<int64_t>(), st));
+        if (int rc = scan_rows(b, b->d_sa_cnt.p, b->d_sa_off.p, 1, n + 1)) return rc;
         launch_sa_lookup(b->idx->fmi, b->d_sorted.p, n, b->d_sa_off.p, b->d_sa_coord.p, b->max_sa, opt->max_occ,
                          b->d_ctr.p, b->cu_count, st);
     }
@@ -1146,12 +1137,9 @@ static int ert_run_once(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t
         launch_make_keys(b->d_pool.p, n, b->d_keys.p, b->d_vals.p, (uint32_t)b->nseq, st);
         int rid_bits = 1;
         while (((int64_t)1 << rid_bits) <= b->nseq) rid_bits++;
-        size_t tb = 0;
-        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p, (size_t)n, 0,
-                                            32 + rid_bits, st));
-        if (int rc = tmp_reserve(b, tb)) return rc;
-        BWAMS_HIP(rocprim::radix_sort_pairs(b->d_tmp.p, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p, (size_t)n, 0,
-                                            32 + rid_bits, st));
+        if (int rc = with_tmp(b, "bwams_seed_run_ert: radix_sort_pairs", [&](void *tmp, size_t &tb) {
+                return rocprim::radix_sort_pairs(tmp, tb, b->d_keys.p, b->d_keys2.p, b->d_vals.p, b->d_vals2.p, (size_t)n, 0, 32 + rid_bits, st);
+            })) return rc;
         launch_gather_sorted(b->d_pool.p, b->d_vals2.p, n, b->d_sorted.p, nullptr, opt->max_occ, st);
     }
     BWAMS_HIP(hipEventRecord(b->ev[4], st));
@@ -1160,13 +1148,8 @@ static int ert_run_once(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t
                       b->ert_stk_frames, b->cu_count, st);
     BWAMS_HIP(hipEventRecord(b->ev[13], st));
     if (with_sa && n > 0) {
-        size_t tb = 0;
-        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
-                                          rocprim::plus<int64_t>(), st));
-        if (int rc = tmp_reserve(b, tb)) return rc;
         BWAMS_HIP(hipMemsetAsync(b->d_sa_cnt.p + n, 0, 8, st));
-        BWAMS_HIP(rocprim::exclusive_scan(b->d_tmp.p, tb, b->d_sa_cnt.p, b->d_sa_off.p, (int64_t)0, (size_t)n + 1,
-                                          rocprim::plus<int64_t>(), st));
+        if (int rc = scan_rows(b, b->d_sa_cnt.p, b->d_sa_off.p, 1, n + 1)) return rc;
         if (int rrc = ert_redo_ensure(b, n)) return rrc;
         launch_ert_gather(e->t, b->d_sorted.p, n, b->d_sa_off.p, b->d_sa_coord.p, b->max_sa, opt->max_occ, b->d_ctr.p, b->d_ert_stk.p,
                           b->ert_stk_frames, b->d_ert_redo.p, b->max_sa, b->cu_count, st);

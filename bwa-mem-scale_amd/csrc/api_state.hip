@@ -1,0 +1,166 @@
+// api_state.hip — the stage state of a batch (stage_state.h) and what the entry-point files share: the per-device auxiliary
+// stream set, state creation (get_state) and release (chain_state_free), the invalidation function (outdated), check_opt, dev_bns,
+// sw_params, scan_rows with widen2_kernel behind launch_widen2, and chain_state_stats for bwams_batch_stats.
+#include <cstring>
+#include <map>
+
+#include <rocprim/rocprim.hpp>
+
+#include "stage_state.h"
+
+namespace bwams {
+
+// The auxiliary streams are ONE set per device, shared by its batches (reference-counted).  A batch of its own set made 9 streams per
+// batch; the runtime maps streams onto GPU_MAX_HW_QUEUES (8) hardware queues and a queue completes its packets in order, so with
+// three batches on a device (two chunks in flight + the caller's) a slot's copies landed behind another slot's kernels or not,
+// depending on the order in which the process had created its streams (bench.py: 4.5 .. 5.6 Mreads/s streaming in a process that had
+// created other batches before, 7.3 .. 7.6 in a fresh one).  Sharing is safe: every use is fork event -> launches -> join event, and
+// a stream is a total order.
+struct AuxSet { hipStream_t q[7] = {}; int refs = 0; };
+static std::mutex g_aux_mu;
+static std::map<int, AuxSet> g_aux;
+static int aux_acquire(int device, hipStream_t *out) {
+    std::lock_guard<std::mutex> g(g_aux_mu);
+    AuxSet &a = g_aux[device];
+    if (a.refs == 0)
+        for (auto &q : a.q) BWAMS_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+    ++a.refs;
+    for (int i = 0; i < 7; ++i) out[i] = a.q[i];
+    return BWAMS_OK;
+}
+static void aux_release(int device) {
+    std::lock_guard<std::mutex> g(g_aux_mu);
+    auto it = g_aux.find(device);
+    if (it == g_aux.end()) return;
+    if (--it->second.refs == 0) {
+        for (auto &q : it->second.q) if (q) (void)hipStreamDestroy(q);
+        g_aux.erase(it);
+    }
+}
+
+void chain_state_free(StageState *s) {
+    if (!s) return;
+    if (s->ev_ok) {
+        for (auto &e : s->ev) (void)hipEventDestroy(e);
+        for (auto &e : s->join) (void)hipEventDestroy(e);
+        (void)hipEventDestroy(s->fork);
+        if (s->aux_device >= 0) aux_release(s->aux_device);
+    }
+    delete s;
+}
+
+namespace {
+
+__global__ void widen2_kernel(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= 2 * (n + 1)) return;
+    const int64_t row = g / (n + 1), i = g - row * (n + 1);
+    wide[g] = i < n ? (int64_t)(row ? b[i] : a[i]) : 0;
+}
+
+}  // namespace
+
+void launch_widen2(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide, hipStream_t st) {
+    widen2_kernel<<<(unsigned)((2 * (n + 1) + 255) / 256), 256, 0, st>>>(a, b, n, wide);
+}
+
+int scan_rows(bwams_batch *b, const int64_t *in, int64_t *out, int rows, int64_t n1) {
+    for (int r = 0; r < rows; ++r)
+        if (int rc = with_tmp(b, "scan_rows: exclusive_scan", [&](void *tmp, size_t &tb) {
+                return rocprim::exclusive_scan(tmp, tb, in + r * n1, out + r * n1, (int64_t)0, (size_t)n1, rocprim::plus<int64_t>(), b->stream);
+            })) return rc;
+    return BWAMS_OK;
+}
+
+void outdated(StageState *s, From first) {
+    switch (first) {
+    case From::chain: s->ch.done = false; [[fallthrough]];
+    case From::built: s->ext.built = s->ext.done = false; [[fallthrough]];
+    case From::dedup: s->dd.done = false; [[fallthrough]];
+    case From::pair: s->pr.done = false; break;
+    case From::al: s->al.done = false; break;
+    case From::er: s->er.done = false; break;
+    case From::sam_upload: s->sm.up = false; [[fallthrough]];
+    case From::sam: s->sm.done = false; [[fallthrough]];
+    case From::bam: s->bm.done = s->bs.done = s->md.done = false; break;
+    }
+}
+
+int get_state(bwams_batch *b, StageState **out) {
+    if (!b->chain) {
+        b->chain = new StageState();
+        for (auto &e : b->chain->ev) BWAMS_HIP(hipEventCreate(&e));
+        for (auto &e : b->chain->join) BWAMS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        BWAMS_HIP(hipEventCreateWithFlags(&b->chain->fork, hipEventDisableTiming));
+        b->chain->ev_ok = true;
+        if (int rc = aux_acquire(b->idx->device, b->chain->aux)) return rc;
+        b->chain->aux_device = b->idx->device;
+    }
+    *out = b->chain;
+    return BWAMS_OK;
+}
+
+int check_opt(const bwams_mem_opt_t *o, const char *who) {
+    if (!o || o->e_del <= 0 || o->e_ins <= 0 || o->max_occ <= 0 || o->w < 0) {
+        set_last_error(std::string(who) + ": null options, non-positive gap extension penalty or max_occ");
+        return BWAMS_ERR_ARG;
+    }
+    return BWAMS_OK;
+}
+
+int dev_bns(bwams_index *ix, DevBns *out) {
+    const int64_t l_pac = (ix->fmi.ref_seq_len - 1) / 2;
+    if (!ix->d_contigs.p) {                     // default: one sequence spanning the whole text
+        bwams_contig_t c;
+        c.offset = 0; c.len = (int32_t)l_pac; c.is_alt = 0;
+        if (l_pac > 0x7fffffffLL) {
+            set_last_error("the index holds more than 2^31 bases: call bwams_index_set_contigs with the real sequences");
+            return BWAMS_ERR_ARG;
+        }
+        BWAMS_HIP(ix->d_contigs.alloc(sizeof c));
+        BWAMS_HIP(hipMemcpy(ix->d_contigs.p, &c, sizeof c, hipMemcpyHostToDevice));
+        ix->n_seqs = 1;
+    }
+    out->contigs = ix->d_contigs.as<const bwams_contig_t>();
+    out->n_seqs = ix->n_seqs;
+    out->l_pac = l_pac;
+    return BWAMS_OK;
+}
+
+void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm) {
+    prm->o_del = o.o_del; prm->e_del = o.e_del; prm->o_ins = o.o_ins; prm->e_ins = o.e_ins;
+    prm->zdrop = o.zdrop; prm->end_bonus = end_bonus;
+    int mx = 0;
+    for (int i = 0; i < 25; ++i) {
+        prm->mat[i] = o.mat[i];
+        mx = mx > o.mat[i] ? mx : o.mat[i];
+    }
+    prm->max_sc = mx;
+}
+
+void chain_state_stats(const StageState *s, bwams_stats_t *out) {
+    if (!s) return;
+    out->n_chains = s->ch.n_chains; out->n_chain_seeds = s->ch.n_seeds; out->n_chain_redo = s->ch.n_redo;
+    out->n_left = s->ext.n_left; out->n_right = s->ext.n_right;
+    out->n_retry_left = s->ext.n_retry_left; out->n_retry_right = s->ext.n_retry_right;
+    auto el = [&](int a, int b, float *dst) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, s->ev[a], s->ev[b]) == hipSuccess) *dst = ms;
+    };
+    el(0, 1, &out->ms_chain);
+    el(2, 3, &out->ms_ext_plan);
+    if (s->ext.done) {
+        el(4, 5, &out->ms_ext_left);
+        el(6, 7, &out->ms_ext_right);
+        el(8, 9, &out->ms_ext_purge);
+        el(10, 11, &out->ms_ext_total);
+        out->n_ext_rounds = s->ext.n_rounds;
+    }
+    if (s->dd.done) { el(12, 13, &out->ms_dedup); out->n_final_regs = s->dd.n_final; }
+    if (s->pr.done) {
+        el(14, 15, &out->ms_pair);
+        out->n_pair_tasks = s->pr.tasks; out->n_pair_redone = s->pr.redone; out->n_pair_regs = s->pr.total;
+    }
+    (void)hipGetLastError();
+}
+}  // namespace bwams

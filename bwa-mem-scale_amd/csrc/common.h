@@ -78,6 +78,7 @@ template <class T = void, bool Host = false> struct Buf {
     }
     hipError_t ensure(size_t bytes, size_t new_cap) { return bytes <= cap ? hipSuccess : alloc(new_cap); }
     hipError_t ensure(size_t bytes) { return ensure(bytes, bytes + bytes / 8 + 4096); }
+    hipError_t ensure_n(size_t n) { return ensure(n * sizeof(T)); }     // n elements (a typed buffer): the same call, the same growth
 };
 template <class T = void> using DevBuf = Buf<T, false>;
 template <class T = void> using HostBuf = Buf<T, true>;
@@ -178,8 +179,8 @@ struct DevCounters {
     unsigned long long pair_full, pair_fail;   // mate rescue: reads redone with every orientation planned; reads the second pass could not finish (never expected)
 };
 
-struct ChainState;                       // chain / extension buffers of a batch (api_chain.hip)
-void chain_state_free(ChainState *s);
+struct StageState;                       // a batch's state behind seeding, stage by stage (stage_state.h)
+void chain_state_free(StageState *s);
 
 // bam.hip: a batch's SAM text as BAM records.  Record r is the line that ends at line_end[r]; the counting pass writes size[r]
 // (block_size + 4) and, for a line BAM cannot hold, bad[0] = min(read << 8 | reason); the writing pass fills out from rec_off
@@ -405,7 +406,7 @@ struct bwams_batch {
     DevBuf<> d_ksw_out;
     DevBuf<int32_t> d_bsw_list;          // task lists of the banded-SW length classes (launch_bsw)
 
-    bwams::ChainState *chain = nullptr;
+    bwams::StageState *chain = nullptr;
 
     hipEvent_t ev[16] = {};
     hipEvent_t ev_emf[2] = {};
@@ -415,4 +416,17 @@ struct bwams_batch {
 
 namespace bwams {
 int tmp_reserve(bwams_batch *b, size_t &tb);   // grows b->d_tmp to tb bytes (the stream drained first) and sets tb to its size (api.hip)
+// A rocPRIM call with the batch's temporary storage: call(nullptr, bytes) asks for the size, call(storage, bytes) runs.  who names
+// the entry point and the call in the error text.
+template <class F> int with_tmp(bwams_batch *b, const char *who, F &&call) {    // call(void *tmp, size_t &bytes) -> hipError_t
+    size_t tb = 0;
+    hipError_t e = call(nullptr, tb);
+    if (e == hipSuccess) {
+        if (int rc = tmp_reserve(b, tb)) return rc;
+        e = call(b->d_tmp.p, tb);
+    }
+    if (e == hipSuccess) return BWAMS_OK;
+    set_last_error(std::string(who) + " -> " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
+}
 }
