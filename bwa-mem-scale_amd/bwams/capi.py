@@ -50,6 +50,8 @@ SYMBOLS = [
     "bwams_bam_upload", "bwams_bam_sort", "bwams_bam_sorted_fetch",
     "bwams_sorter_open", "bwams_sorter_put", "bwams_sorter_put_batch", "bwams_sorter_close", "bwams_sorter_close2",
     "bwams_bam_templates", "bwams_bam_templates_fetch", "bwams_dup_decide", "bwams_bam_markdup",
+    "bwams_bam_reads_decode", "bwams_bam_reads_info", "bwams_process_chunk_bam", "bwams_process_chunk_bam_smart",
+    "bwams_reader_open_bam", "bwams_reader_bam_header",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
@@ -126,6 +128,9 @@ class Fastq:
     def __init__(self, text, device: int = 0, n_bytes: int | None = None):
         """text: bytes (host) or an int device address with n_bytes."""
         self.h = C.c_void_p()
+        self.n_records = None
+        if text is None:                              # bam_reads_decode fills the handle in
+            return
         n, nb = C.c_int64(0), C.c_int64(0)
         if isinstance(text, int):
             rc = lib().bwams_fastq_decode(device, C.c_void_p(text), C.c_int64(n_bytes), C.byref(self.h), C.byref(n), C.byref(nb))
@@ -382,6 +387,71 @@ def reader_open_device(path: str, device: int, chunk_bases: int, paired: bool = 
     return r
 
 
+def bam_reads_decode(device: int, records, tags: bytes = b"", n_bytes: int | None = None) -> Fastq:
+    """bwams_bam_reads_decode: BAM records (bytes, or an int device address with n_bytes) as a decoded chunk.  The Fastq also carries
+    n_records (skipped records included)."""
+    fq = Fastq(None)
+    n, nb, nr = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    if isinstance(records, int):
+        src = C.c_void_p(records)
+    else:
+        src, n_bytes = C.cast(C.c_char_p(records), C.c_void_p), len(records)
+        fq._keep = records
+    _chk(lib().bwams_bam_reads_decode(device, src, n_bytes, tags or None, C.byref(fq.h), C.byref(n), C.byref(nb), C.byref(nr)),
+         "bwams_bam_reads_decode")
+    fq.n_reads, fq.n_bases, fq.n_records = n.value, nb.value, nr.value
+    return fq
+
+
+def bam_reads_info(fq: Fastq) -> dict:
+    """bwams_bam_reads_info: device ms of the record search and of what follows it, the filter's candidates, the records."""
+    a, b, nc, nr = C.c_float(0), C.c_float(0), C.c_int64(0), C.c_int64(0)
+    _chk(lib().bwams_bam_reads_info(fq.h, C.byref(a), C.byref(b), C.byref(nc), C.byref(nr)), "bwams_bam_reads_info")
+    return dict(ms_discover=a.value, ms_emit=b.value, n_candidates=nc.value, n_records=nr.value)
+
+
+def reader_open_bam(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0,
+                    n_buffers: int = 2) -> C.c_void_p:
+    """bwams_reader_open_bam: a bwams_reader_t handle over a BAM file (device < 0: zlib); chunks of whole BAM records."""
+    r = C.c_void_p()
+    _chk(lib().bwams_reader_open_bam(path.encode(), device, chunk_bases, int(paired), buffer_bytes, n_buffers, C.byref(r)),
+         "bwams_reader_open_bam")
+    return r
+
+
+def reader_bam_header(r) -> tuple[bytes, int]:
+    """bwams_reader_bam_header: (header text, number of references)."""
+    text, n, n_ref = C.c_void_p(), C.c_int64(0), C.c_int32(0)
+    _chk(lib().bwams_reader_bam_header(r, C.byref(text), C.byref(n), C.byref(n_ref)), "bwams_reader_bam_header")
+    return C.string_at(text, n.value) if n.value else b"", n_ref.value
+
+
+def reader_open(path: str, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0, n_buffers: int = 2) -> C.c_void_p:
+    """bwams_reader_open: a bwams_reader_t handle over a gz or plain FASTQ / FASTA file."""
+    r = C.c_void_p()
+    _chk(lib().bwams_reader_open(path.encode(), chunk_bases, int(paired), buffer_bytes, n_buffers, C.byref(r)), "bwams_reader_open")
+    return r
+
+
+def reader_chunks(r):
+    """Every chunk of a reader as (bytes, n_reads, n_bases), each buffer released at once; closes the reader.  A reader's error
+    raises BwamsError with bwams_reader_error's text."""
+    L = lib()
+    out = []
+    try:
+        while True:
+            text, nb, n, bases = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            rc = L.bwams_reader_next(r, C.byref(text), C.byref(nb), C.byref(n), C.byref(bases))
+            if rc == 1:
+                return out
+            if rc:
+                raise BwamsError(rc, "bwams_reader_next", L.bwams_reader_error(r).decode())
+            out.append((C.string_at(text, nb.value), n.value, bases.value))
+            L.bwams_reader_release(r, text)
+    finally:
+        L.bwams_reader_close(r)
+
+
 def reader_info(r) -> ReaderStats:
     st = ReaderStats()
     _chk(lib().bwams_reader_info(r, C.byref(st)), "bwams_reader_info")
@@ -469,6 +539,18 @@ def lib():
         L.bwams_inflater_destroy.argtypes = [vp]
         L.bwams_reader_open_device.argtypes = [C.c_char_p, C.c_int, i64, i32, i64, i32, vp]
         L.bwams_reader_info.argtypes = [vp, vp]
+        L.bwams_reader_open.argtypes = [C.c_char_p, i64, i32, i64, i32, vp]
+        L.bwams_reader_next.argtypes = [vp, vp, vp, vp, vp]
+        L.bwams_reader_release.argtypes = [vp, vp]
+        L.bwams_reader_error.restype = C.c_char_p
+        L.bwams_reader_error.argtypes = [vp]
+        L.bwams_reader_close.argtypes = [vp]
+        L.bwams_reader_open_bam.argtypes = [C.c_char_p, C.c_int, i64, i32, i64, i32, vp]
+        L.bwams_reader_bam_header.argtypes = [vp, vp, vp, vp]
+        L.bwams_bam_reads_decode.argtypes = [C.c_int, vp, i64, C.c_char_p, vp, vp, vp, vp]
+        L.bwams_bam_reads_info.argtypes = [vp, vp, vp, vp, vp]
+        L.bwams_process_chunk_bam.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, C.c_char_p, i32, vp, i64, i32, vp, vp]
+        L.bwams_process_chunk_bam_smart.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, C.c_char_p, vp, i64, i32, vp, vp, vp]
         L.bwams_deflate_bound.restype = i64
         L.bwams_deflate_bound.argtypes = [i64]
         L.bwams_deflater_create.argtypes = [C.c_int, i64, vp]
@@ -1158,6 +1240,42 @@ class Batch:
                                              C.byref(opt), C.byref(sopt), src, C.c_int64(nbytes), pp, C.c_int64(n_processed),
                                              flags | (0x100 if copy_comment else 0), C.byref(n), C.byref(n0), C.byref(nb)),
              "bwams_process_chunk_smart")
+        self._nseq, self._sam_bytes = n.value, nb.value
+        text, off, _ = self.sam_fetch()
+        return text, off, n0.value
+
+    def process_chunk_bam(self, records, tags: bytes = b"", paired: bool = False, emf=None, ert=None, seed_opt=None, opt: MemOpt | None = None,
+                          sopt=None, pes=None, n_processed: int = 0, flags: int = 0, copy_comment: bool = False, fetch: bool = True):
+        """bwams_process_chunk_bam: process_chunk for a chunk of BAM records (bytes, or (device address, n_bytes)); tags as for
+        bam_reads_decode -> (SAM text, read_off), or the byte count with fetch=False."""
+        seed_opt = seed_opt or default_seed_opt()
+        opt = opt or default_mem_opt()
+        sopt = sopt or default_sam_opt()
+        n, nb = C.c_int64(0), C.c_int64(0)
+        pp = _p(np.ascontiguousarray(pes, PESTAT_DTYPE)) if pes is not None else None
+        src, nbytes = (C.c_void_p(records[0]), records[1]) if isinstance(records, tuple) else (C.cast(C.c_char_p(records), C.c_void_p), len(records))
+        _chk(lib().bwams_process_chunk_bam(self.h, emf.h if emf is not None else None, ert.h if ert is not None else None, C.byref(seed_opt),
+                                           C.byref(opt), C.byref(sopt), src, nbytes, tags or None, 1 if paired else 0, pp, n_processed,
+                                           flags | (0x100 if copy_comment else 0), C.byref(n), C.byref(nb)), "bwams_process_chunk_bam")
+        self._nseq, self._sam_bytes = n.value, nb.value
+        if not fetch:
+            return nb.value
+        text, off, _ = self.sam_fetch()
+        return text, off
+
+    def process_chunk_bam_smart(self, records, tags: bytes = b"", emf=None, ert=None, seed_opt=None, opt: MemOpt | None = None, sopt=None,
+                                pes=None, n_processed: int = 0, flags: int = 0, copy_comment: bool = False):
+        """bwams_process_chunk_bam_smart: process_chunk_smart for BAM records -> (SAM text, read_off, number of single reads)."""
+        seed_opt = seed_opt or default_seed_opt()
+        opt = opt or default_mem_opt()
+        sopt = sopt or default_sam_opt()
+        n, n0, nb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        pp = _p(np.ascontiguousarray(pes, PESTAT_DTYPE)) if pes is not None else None
+        src, nbytes = (C.c_void_p(records[0]), records[1]) if isinstance(records, tuple) else (C.cast(C.c_char_p(records), C.c_void_p), len(records))
+        _chk(lib().bwams_process_chunk_bam_smart(self.h, emf.h if emf is not None else None, ert.h if ert is not None else None,
+                                                 C.byref(seed_opt), C.byref(opt), C.byref(sopt), src, nbytes, tags or None, pp, n_processed,
+                                                 flags | (0x100 if copy_comment else 0), C.byref(n), C.byref(n0), C.byref(nb)),
+             "bwams_process_chunk_bam_smart")
         self._nseq, self._sam_bytes = n.value, nb.value
         text, off, _ = self.sam_fetch()
         return text, off, n0.value

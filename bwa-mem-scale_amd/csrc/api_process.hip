@@ -1,5 +1,5 @@
 // api_process.hip — mem_process_seqs through the public C-ABI (include/bwams.h): the process_* stage sequences, bwams_process_reads*
-// and bwams_process_chunk*, and beside them bwams_host_alloc, _free and bwams_batch_device.  The stage state is touched only for an
+// and bwams_process_chunk* (FASTQ text or BAM records), and beside them bwams_host_alloc, _free and bwams_batch_device.  The stage state is touched only for an
 // empty chunk (process_empty) and for the merged text of bwams_process_chunk_smart.
 #include <cstring>
 
@@ -168,6 +168,20 @@ int bwams_host_free(void *p) {
     return BWAMS_OK;
 }
 
+// bwams_process_chunk behind its decode (fq is closed here): `who` names the entry point in the error text
+static int chunk_decoded(const char *who, bwams_batch_t *b, bwams_fastq_t *fq, int64_t n, bwams_emf_t *emf, bwams_ert_t *ert,
+                         const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo, const bwams_sam_opt_t *sam_opt, int32_t paired,
+                         const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes) {
+    if (paired && (n & 1)) {
+        bwams_fastq_close(fq);
+        set_last_error(std::string(who) + ": a paired-end chunk holds an even number of reads (ends interleaved)");
+        return BWAMS_ERR_ARG;
+    }
+    const int rc = process_decoded(b, fq, n, emf, ert, so, mo, sam_opt, paired, pes0, n_processed, flags, sam_bytes);
+    if (!rc && n_reads) *n_reads = n;
+    return rc;
+}
+
 int bwams_process_chunk(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
                         const bwams_sam_opt_t *sam_opt, const char *fastq, int64_t n_bytes, int32_t paired, const bwams_pestat_t *pes0,
                         int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes) {
@@ -179,14 +193,22 @@ int bwams_process_chunk(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, co
     int64_t n = 0, nb = 0;
     int rc = bwams_fastq_decode(b->idx->device, fastq, n_bytes, &fq, &n, &nb);
     if (rc) return rc;
-    if (paired && (n & 1)) {
-        bwams_fastq_close(fq);
-        set_last_error("bwams_process_chunk: a paired-end chunk holds an even number of reads (ends interleaved)");
+    return chunk_decoded("bwams_process_chunk", b, fq, n, emf, ert, so, mo, sam_opt, paired, pes0, n_processed, flags, n_reads, sam_bytes);
+}
+
+// The same chunk given as BAM records (bam_reads.hip decodes them to the same handle)
+int bwams_process_chunk_bam(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                            const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags, int32_t paired,
+                            const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes) {
+    if (!b || !so || !mo || !sam_opt || !bam || n_bytes < 0) {
+        set_last_error("bwams_process_chunk_bam: batch, options and records are required");
         return BWAMS_ERR_ARG;
     }
-    rc = process_decoded(b, fq, n, emf, ert, so, mo, sam_opt, paired, pes0, n_processed, flags, sam_bytes);
-    if (!rc && n_reads) *n_reads = n;
-    return rc;
+    bwams_fastq_t *fq = nullptr;
+    int64_t n = 0, nb = 0;
+    int rc = bwams_bam_reads_decode(b->idx->device, bam, n_bytes, tags, &fq, &n, &nb, nullptr);
+    if (rc) return rc;
+    return chunk_decoded("bwams_process_chunk_bam", b, fq, n, emf, ert, so, mo, sam_opt, paired, pes0, n_processed, flags, n_reads, sam_bytes);
 }
 
 // A paired-end chunk read from two files (bseq_read_orig with ks2, src/bwa.cpp:275-318): record k of the first text and record k of the
@@ -219,18 +241,12 @@ int bwams_process_chunk2(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, c
 
 // process()'s MEM_F_SMARTPE branch (src/fastmap.cpp:378-414): bseq_classify splits the chunk into the reads that stand alone and the
 // interleaved pairs; mem_process_seqs runs on the first set as single-end (ids from n_processed) and on the second as paired-end (ids
-// from n_processed + the number of single reads, pes0); every read's text returns to its place in the chunk.
-int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
-                              const bwams_sam_opt_t *sam_opt, const char *fastq, int64_t n_bytes, const bwams_pestat_t *pes0,
-                              int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *n_single, int64_t *sam_bytes) {
-    if (!b || !so || !mo || !sam_opt || !fastq || n_bytes < 0) {
-        set_last_error("bwams_process_chunk_smart: batch, options and text are required");
-        return BWAMS_ERR_ARG;
-    }
-    bwams_fastq_t *fq = nullptr;
-    int64_t n = 0, nb = 0;
-    int rc = bwams_fastq_decode(b->idx->device, fastq, n_bytes, &fq, &n, &nb);
-    if (rc) return rc;
+// from n_processed + the number of single reads, pes0); every read's text returns to its place in the chunk.  Behind the decode
+// (fq is closed here), shared by the text and the BAM entry points.
+static int chunk_smart_decoded(bwams_batch_t *b, bwams_fastq_t *fq, int64_t n, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so,
+                               const bwams_mem_opt_t *mo, const bwams_sam_opt_t *sam_opt, const bwams_pestat_t *pes0, int64_t n_processed,
+                               int32_t flags, int64_t *n_reads, int64_t *n_single, int64_t *sam_bytes) {
+    int rc;
     std::vector<uint8_t> which;
     if ((rc = fastq_classify(fq, &which))) { bwams_fastq_close(fq); return rc; }
     std::vector<int64_t> ids[2];
@@ -285,5 +301,34 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
     s->sm.bytes = total; s->sm.nregs = 0; s->sm.merged_n = n; s->sm.done = true;
     if (sam_bytes) *sam_bytes = total;
     return BWAMS_OK;
+}
+
+int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                              const bwams_sam_opt_t *sam_opt, const char *fastq, int64_t n_bytes, const bwams_pestat_t *pes0,
+                              int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *n_single, int64_t *sam_bytes) {
+    if (!b || !so || !mo || !sam_opt || !fastq || n_bytes < 0) {
+        set_last_error("bwams_process_chunk_smart: batch, options and text are required");
+        return BWAMS_ERR_ARG;
+    }
+    bwams_fastq_t *fq = nullptr;
+    int64_t n = 0, nb = 0;
+    int rc = bwams_fastq_decode(b->idx->device, fastq, n_bytes, &fq, &n, &nb);
+    if (rc) return rc;
+    return chunk_smart_decoded(b, fq, n, emf, ert, so, mo, sam_opt, pes0, n_processed, flags, n_reads, n_single, sam_bytes);
+}
+
+int bwams_process_chunk_bam_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                                  const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags,
+                                  const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *n_single,
+                                  int64_t *sam_bytes) {
+    if (!b || !so || !mo || !sam_opt || !bam || n_bytes < 0) {
+        set_last_error("bwams_process_chunk_bam_smart: batch, options and records are required");
+        return BWAMS_ERR_ARG;
+    }
+    bwams_fastq_t *fq = nullptr;
+    int64_t n = 0, nb = 0;
+    int rc = bwams_bam_reads_decode(b->idx->device, bam, n_bytes, tags, &fq, &n, &nb, nullptr);
+    if (rc) return rc;
+    return chunk_smart_decoded(b, fq, n, emf, ert, so, mo, sam_opt, pes0, n_processed, flags, n_reads, n_single, sam_bytes);
 }
 }  // extern "C"

@@ -1,0 +1,580 @@
+// bam_reads.hip — BAM as read input: a buffer of BAM alignment records becomes the decoded chunk (bwams_fastq_t) that FASTQ text
+// becomes in fastq.hip.  The reference reads FASTQ / FASTA only; the behaviour reproduced is `samtools fastq` (htslib's bam2fq) in
+// front of `bwa mem`, with the rules written out in include/bwams.h above bwams_bam_reads_decode and restated in bwams/bam_reads.py.
+//
+// Record discovery.  Where record k + 1 starts follows from record k's block_size, so the records are a linked list through the
+// bytes.  As for FASTQ records over several lines (fastq.hip), every position is parsed as if a record began there and the real
+// records are the chain of successors from byte 0, found by binary lifting — but over the few positions that can be a record at all:
+//   (1) br_filter_kernel: a lane per byte offset, the bytes staged through LDS in 16-byte loads, tests rule 1 (sizes consistent,
+//       the name's NUL in place, the end inside the buffer).  The wave's ballot is one word of a bitmap; its population count goes
+//       into a second array whose exclusive scan gives, for any offset q, "index of the candidate at q" in O(1).
+//   (2) br_succ_kernel: a lane per bitmap word lists its candidates' offsets and their successors — the candidate index at
+//       q + 4 + block_size, END when that is n_bytes, BAD when nothing well formed starts there.
+//   (3) br_double_kernel, ceil(log2(candidates)) + 1 levels; br_count_kernel (one lane) descends them from candidate 0: the number
+//       of records, or the ordinal and offset of the first position the chain reaches where no record starts.
+// Quality and aux bytes do give false candidates (a Z value may hold a whole record); the chain from byte 0 never visits them.
+// Scratch: 1/8 byte (bitmap) + 1/16 byte (ranks) per input byte, 8 + 4 * levels bytes per candidate — about 0.75 byte per input
+// byte for a million 150-base reads.
+// Behind it: br_measure_kernel, a lane per record (its offset by lifting; FLAG, lengths, the aux walk, rules 4 and 6), four exclusive
+// scans, br_compact_kernel (the offsets of the kept reads), br_emit_kernel, 16 lanes per record: the packed SEQ in 4-byte loads, a
+// nibble to its code by shifts of a constant, qualities, names and comments lane by lane.
+// All kernels stream: the filter reads the input once (HBM bound), the emit reads ~0.8 and writes ~1.1 of it; the lifting's
+// `levels` dependent 4-byte gathers per record are latency bound and small beside them.
+#include <algorithm>
+#include <cstring>
+#include <rocprim/rocprim.hpp>
+#include <memory>
+#include <string>
+#include <vector>
+#include "common.h"
+
+namespace bwams {
+namespace {
+
+constexpr int kTile = 4096;                   // bytes per block of br_filter_kernel: 64 bitmap words
+constexpr int kHalo = 48;                     // a record's fixed part (36 bytes) behind the tile's last offset, in 16-byte pieces
+constexpr int kMaxTags = 32;
+constexpr int kGroup = 16;                    // lanes per record of br_emit_kernel
+
+struct Tags {                                 // the listed tags, by value in the kernel arguments
+    int32_t n;
+    uint8_t t[2 * kMaxTags];
+};
+
+__device__ __forceinline__ uint32_t ld16(const uint8_t *__restrict__ d, int64_t p) { return (uint32_t)d[p] | (uint32_t)d[p + 1] << 8; }
+__device__ __forceinline__ uint32_t ld32(const uint8_t *__restrict__ d, int64_t p) {
+    return (uint32_t)d[p] | (uint32_t)d[p + 1] << 8 | (uint32_t)d[p + 2] << 16 | (uint32_t)d[p + 3] << 24;
+}
+// the aligned word w of the buffer (d is 16-byte aligned): one load when it lies inside [0, n), its bytes inside otherwise
+__device__ __forceinline__ uint32_t ld_word(const uint8_t *__restrict__ d, int64_t w, int64_t n) {
+    const int64_t p = w * 4;
+    if (p + 4 <= n) return *reinterpret_cast<const uint32_t *>(d + p);
+    uint32_t v = 0;
+    for (int k = 0; k < 4; ++k)
+        if (p + k < n) v |= (uint32_t)d[p + k] << (8 * k);
+    return v;
+}
+// the four bytes at p (any alignment), bytes outside [0, n) as zeros
+__device__ __forceinline__ uint32_t ld_wide(const uint8_t *__restrict__ d, int64_t p, int64_t n) {
+    const int64_t w = p >> 2;
+    const int sh = (int)(p & 3) * 8;
+    const uint32_t lo = ld_word(d, w, n);
+    if (!sh) return lo;
+    return lo >> sh | ld_word(d, w + 1, n) << (32 - sh);
+}
+
+// rule 1 at offset q from the fields of the fixed part: everything but the name's NUL
+__device__ __forceinline__ bool fixed_ok(int64_t q, int64_t n, uint32_t block_size, uint32_t l_name, uint32_t n_cig, int32_t l_seq) {
+    if (block_size < 32 || l_name < 1 || l_seq < 0) return false;
+    if (q + 4 + (int64_t)block_size > n) return false;
+    const int64_t need = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq;
+    return need <= (int64_t)block_size;
+}
+
+// (1) a lane per offset.  Block b takes offsets [b * kTile, (b + 1) * kTile); bm: one bit per offset, cnt[w] = popcount(bm[w]).
+__global__ __launch_bounds__(256) void br_filter_kernel(const uint8_t *__restrict__ d, int64_t n, unsigned long long *__restrict__ bm,
+                                                        uint32_t *__restrict__ cnt) {
+    __shared__ uint32_t lds[(kTile + kHalo) / 4 + 1];
+    const int64_t t0 = (int64_t)blockIdx.x * kTile;
+    for (int piece = threadIdx.x; piece < (kTile + kHalo) / 16; piece += 256) {
+        const int64_t p = t0 + (int64_t)piece * 16;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (p + 16 <= n) v = *reinterpret_cast<const uint4 *>(d + p);
+        else if (p < n) { v.x = ld_word(d, p >> 2, n); v.y = ld_word(d, (p >> 2) + 1, n); v.z = ld_word(d, (p >> 2) + 2, n); v.w = ld_word(d, (p >> 2) + 3, n); }
+        lds[piece * 4] = v.x; lds[piece * 4 + 1] = v.y; lds[piece * 4 + 2] = v.z; lds[piece * 4 + 3] = v.w;
+    }
+    if (threadIdx.x == 0) lds[(kTile + kHalo) / 4] = 0;
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = 0; k < kTile / 256; ++k) {
+        const int t = k * 256 + threadIdx.x;                     // consecutive lanes, consecutive offsets: four lanes share a word
+        const int64_t q = t0 + t;
+        const int sh = (t & 3) * 8, w = t >> 2;
+        auto u32_at = [&](int word) -> uint32_t {
+            const uint32_t lo = lds[word], hi = lds[word + 1];
+            return sh ? (lo >> sh | hi << (32 - sh)) : lo;
+        };
+        bool ok = false;
+        if (q + 36 <= n) {
+            const uint32_t block_size = u32_at(w);
+            if (block_size >= 32 && q + 4 + (int64_t)block_size <= n) {
+                const uint32_t l_name = u32_at(w + 3) & 0xFF, n_cig = u32_at(w + 4) & 0xFFFF;
+                const int32_t l_seq = (int32_t)u32_at(w + 5);
+                ok = fixed_ok(q, n, block_size, l_name, n_cig, l_seq) && d[q + 35 + l_name] == 0;     // the name's last byte: inside the record
+            }
+        }
+        const unsigned long long m = __ballot(ok);
+        if (lane == 0) {
+            const int64_t word = (t0 >> 6) + k * 4 + wave;
+            bm[word] = m;
+            cnt[word] = (uint32_t)__popcll(m);
+        }
+    }
+}
+
+// (2) a lane per bitmap word: offsets and successors of its candidates.  END = n_cand, BAD = n_cand + 1 (both map to themselves).
+__global__ __launch_bounds__(256) void br_succ_kernel(const uint8_t *__restrict__ d, int64_t n, const unsigned long long *__restrict__ bm,
+                                                      const uint32_t *__restrict__ rank, int64_t n_words, uint32_t n_cand,
+                                                      int64_t *__restrict__ cand_off, uint32_t *__restrict__ up0) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w == 0) { up0[n_cand] = n_cand; up0[n_cand + 1] = n_cand + 1; }
+    if (w >= n_words) return;
+    unsigned long long bits = bm[w];
+    uint32_t idx = rank[w];
+    while (bits) {
+        const int b = __ffsll((long long)bits) - 1;
+        bits &= bits - 1;
+        const int64_t q = w * 64 + b;
+        const int64_t q2 = q + 4 + (int64_t)ld32(d, q);           // <= n: the filter saw to it
+        uint32_t nx = n_cand + 1;
+        if (q2 == n) nx = n_cand;
+        else {
+            const unsigned long long m = bm[q2 >> 6];
+            const int s = (int)(q2 & 63);
+            if ((m >> s) & 1) nx = rank[q2 >> 6] + (uint32_t)__popcll(m & ((1ull << s) - 1));
+        }
+        cand_off[idx] = q;
+        up0[idx] = nx;
+        ++idx;
+    }
+}
+
+// (3) up[k + 1] = up[k] o up[k]
+__global__ __launch_bounds__(256) void br_double_kernel(const uint32_t *__restrict__ a, uint32_t *__restrict__ b, int64_t n) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) b[j] = a[a[j]];
+}
+
+// one lane: out[0] = records of the chain from byte 0, or -1 with out[1] / out[2] = ordinal / offset of the first bad record
+__global__ void br_count_kernel(const uint8_t *__restrict__ d, const unsigned long long *__restrict__ bm, const uint32_t *__restrict__ up,
+                                int levels, uint32_t n_cand, const int64_t *__restrict__ cand_off, int64_t *__restrict__ out) {
+    if (!(bm[0] & 1)) { out[0] = -1; out[1] = 0; out[2] = 0; return; }
+    const int64_t stride = (int64_t)n_cand + 2;
+    uint32_t cur = 0;
+    int64_t cnt = 0;
+    for (int k = levels - 1; k >= 0; --k) {
+        const uint32_t nx = up[(int64_t)k * stride + cur];
+        if (nx < n_cand) { cur = nx; cnt += (int64_t)1 << k; }
+    }
+    if (up[cur] == n_cand) { out[0] = cnt + 1; out[1] = out[2] = 0; return; }
+    out[0] = -1;
+    out[1] = cnt + 1;
+    out[2] = cand_off[cur] + 4 + (int64_t)ld32(d, cand_off[cur]);
+}
+
+struct BrRec {                                // a record as the emit kernel reads it
+    int64_t name_at, seq_at, end;             // end: one past the record
+    int32_t l_name, l_seq;
+    uint32_t flag;                            // FLAG | kept << 16
+    int32_t pad_;
+};
+
+// ---- aux fields ----
+// the field at p in [p, end): the position behind it; -1: it runs past the record, -2: a type SAMv1 does not know.  *val / *type
+// receive where its value starts and its type
+__device__ int64_t aux_next(const uint8_t *__restrict__ d, int64_t p, int64_t end, int64_t *val, int *type) {
+    if (p + 3 > end) return -1;
+    const int ty = d[p + 2];
+    int64_t v = p + 3, e;
+    *type = ty; *val = v;
+    switch (ty) {
+    case 'A': case 'c': case 'C': e = v + 1; break;
+    case 's': case 'S': e = v + 2; break;
+    case 'i': case 'I': case 'f': e = v + 4; break;
+    case 'Z': case 'H':
+        for (e = v; e < end && d[e]; ++e) {}
+        if (e >= end) return -1;                                 // no NUL inside the record
+        ++e;
+        break;
+    case 'B': {
+        if (v + 5 > end) return -1;
+        const int sub = d[v];
+        const int64_t cnt = ld32(d, v + 1);
+        const int sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+        if (!sz) return -2;
+        e = v + 5 + cnt * sz;
+        break;
+    }
+    default: return -2;
+    }
+    return e <= end ? e : -1;
+}
+// the record's first field with tag (t0, t1) in [a, end) (already validated): its value position and type, or -1
+__device__ int64_t aux_find(const uint8_t *__restrict__ d, int64_t a, int64_t end, uint8_t t0, uint8_t t1, int *type) {
+    while (a < end) {
+        int64_t val;
+        int ty;
+        const int64_t nx = aux_next(d, a, end, &val, &ty);
+        if (nx < 0) return -1;
+        if (d[a] == t0 && d[a + 1] == t1) { *type = ty; return val; }
+        a = nx;
+    }
+    return -1;
+}
+__device__ __forceinline__ int64_t aux_int(const uint8_t *__restrict__ d, int64_t v, int ty) {
+    switch (ty) {
+    case 'c': return (int8_t)d[v];
+    case 'C': return d[v];
+    case 's': return (int16_t)ld16(d, v);
+    case 'S': return ld16(d, v);
+    case 'i': return (int32_t)ld32(d, v);
+    default:  return ld32(d, v);
+    }
+}
+__device__ __forceinline__ int dec_len(int64_t x) {
+    int l = x < 0 ? 1 : 0;
+    unsigned long long u = x < 0 ? (unsigned long long)(-x) : (unsigned long long)x;
+    do { ++l; u /= 10; } while (u);
+    return l;
+}
+// bytes of "TG:T:value" for the field whose value starts at v
+__device__ int aux_text_len(const uint8_t *__restrict__ d, int64_t v, int ty) {
+    if (ty == 'A') return 6;
+    if (ty == 'Z' || ty == 'H') { int l = 0; while (d[v + l]) ++l; return 5 + l; }
+    return 5 + dec_len(aux_int(d, v, ty));
+}
+__device__ void aux_text_write(const uint8_t *__restrict__ d, int64_t v, int ty, uint8_t t0, uint8_t t1, char *__restrict__ out) {
+    out[0] = (char)t0; out[1] = (char)t1; out[2] = ':'; out[4] = ':';
+    if (ty == 'A') { out[3] = 'A'; out[5] = (char)d[v]; return; }
+    if (ty == 'Z' || ty == 'H') {
+        out[3] = (char)ty;
+        for (int l = 0; d[v + l]; ++l) out[5 + l] = (char)d[v + l];
+        return;
+    }
+    out[3] = 'i';
+    const int64_t x = aux_int(d, v, ty);
+    int l = dec_len(x);
+    unsigned long long u = x < 0 ? (unsigned long long)(-x) : (unsigned long long)x;
+    if (x < 0) out[5] = '-';
+    do { out[5 + --l] = (char)('0' + u % 10); u /= 10; } while (u);
+}
+
+// what br_measure_kernel reports: err = min over records of (ordinal << 8 | reason); first_q / first_n = the first kept record with /
+// without qualities (~0: none)
+struct BrFlags {
+    unsigned long long err, first_q, first_n;
+};
+enum { kErrLseq0 = 1, kErrMixed = 2, kErrAuxType = 3, kErrAuxBad = 4 };
+
+// a lane per record: its offset by lifting, then FLAG, the lengths, rules 4 and 6.  wide: 4 rows of n_rec + 1 (name, comment, bases, kept)
+__global__ __launch_bounds__(256) void br_measure_kernel(const uint8_t *__restrict__ d, const uint32_t *__restrict__ up, int levels, uint32_t n_cand,
+                                                         const int64_t *__restrict__ cand_off, int64_t n_rec, Tags tags, BrRec *__restrict__ rec,
+                                                         int64_t *__restrict__ wide, BrFlags *__restrict__ fl) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n_rec) return;
+    const int64_t n1 = n_rec + 1;
+    if (r == n_rec) { wide[r] = wide[n1 + r] = wide[2 * n1 + r] = wide[3 * n1 + r] = 0; return; }
+    const int64_t stride = (int64_t)n_cand + 2;
+    uint32_t cur = 0;
+    for (int k = 0; k < levels; ++k)
+        if ((r >> k) & 1) cur = up[(int64_t)k * stride + cur];
+    const int64_t q = cand_off[cur];
+    const uint32_t block_size = ld32(d, q), l_name = d[q + 12], n_cig = ld16(d, q + 16), flag = ld16(d, q + 18);
+    const int32_t l_seq = (int32_t)ld32(d, q + 20);
+    const bool kept = !(flag & 0x900);
+    BrRec R;
+    R.name_at = q + 36; R.seq_at = q + 36 + l_name + 4 * (int64_t)n_cig; R.end = q + 4 + (int64_t)block_size;
+    R.l_name = (int32_t)l_name - 1; R.l_seq = l_seq; R.flag = flag | (kept ? 1u << 16 : 0u); R.pad_ = 0;
+    int l_comment = 0;
+    if (kept) {
+        unsigned long long err = 0;
+        const int64_t qual_at = R.seq_at + ((int64_t)l_seq + 1) / 2, aux_at = qual_at + l_seq;
+        if (l_seq == 0) err = kErrLseq0;
+        else {
+            // the first kept record of either kind: the minimum settles with the first blocks, so look before the atomic (a stale
+            // value only costs an atomic; a million of them on one address cost 10 ms)
+            unsigned long long *first = d[qual_at] == 0xFF ? &fl->first_n : &fl->first_q;
+            if ((unsigned long long)r < __atomic_load_n(first, __ATOMIC_RELAXED)) atomicMin(first, (unsigned long long)r);
+            if (tags.n) {
+                for (int64_t a = aux_at; a < R.end && !err;) {          // every field inside the record, of a known type
+                    int64_t val;
+                    int ty;
+                    const int64_t nx = aux_next(d, a, R.end, &val, &ty);
+                    if (nx < 0) { err = kErrAuxBad; break; }
+                    if (ty == 'f' || ty == 'B') {                          // refused when it is a listed tag's first field
+                        for (int t = 0; t < tags.n; ++t)
+                            if (d[a] == tags.t[2 * t] && d[a + 1] == tags.t[2 * t + 1]) {
+                                int ty1;
+                                if (aux_find(d, aux_at, a, tags.t[2 * t], tags.t[2 * t + 1], &ty1) < 0) err = kErrAuxType;     // no earlier field of this tag
+                                break;
+                            }
+                    }
+                    a = nx;
+                }
+                if (!err)
+                    for (int t = 0; t < tags.n; ++t) {
+                        int ty;
+                        const int64_t v = aux_find(d, aux_at, R.end, tags.t[2 * t], tags.t[2 * t + 1], &ty);
+                        if (v >= 0) l_comment += aux_text_len(d, v, ty) + (l_comment ? 1 : 0);
+                    }
+            }
+        }
+        if (err) atomicMin(&fl->err, (unsigned long long)r << 8 | err);
+    }
+    rec[r] = R;
+    wide[r] = kept ? R.l_name : 0;
+    wide[n1 + r] = l_comment;
+    wide[2 * n1 + r] = kept ? l_seq : 0;
+    wide[3 * n1 + r] = kept ? 1 : 0;
+}
+
+// the offsets of the kept reads: comp = 3 rows of n_rec + 1 (name, comment, bases), entry k of a row = the kept read k's offset
+__global__ __launch_bounds__(256) void br_compact_kernel(const int64_t *__restrict__ wide, const int64_t *__restrict__ offs, int64_t n_rec,
+                                                         int64_t *__restrict__ comp) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n_rec) return;
+    const int64_t n1 = n_rec + 1;
+    if (r < n_rec && !wide[3 * n1 + r]) return;
+    const int64_t k = offs[3 * n1 + r];
+    for (int row = 0; row < 3; ++row) comp[row * n1 + k] = offs[row * n1 + r];
+}
+
+// a nibble's base code (1, 2, 4, 8 -> 0 .. 3, anything else 4): digit c of a constant
+__device__ __forceinline__ uint32_t nib_code(uint32_t c) { return (uint32_t)(0x4444444344424104ull >> (4 * c)) & 15; }
+
+// kGroup lanes per record
+__global__ __launch_bounds__(256) void br_emit_kernel(const uint8_t *__restrict__ d, int64_t n, const BrRec *__restrict__ rec, int64_t n_rec,
+                                                      const int64_t *__restrict__ offs, Tags tags, int has_qual, char *__restrict__ names,
+                                                      char *__restrict__ comments, uint8_t *__restrict__ enc, char *__restrict__ qual) {
+    const int lane = threadIdx.x & (kGroup - 1);
+    const int64_t n1 = n_rec + 1;
+    const int64_t group = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroup, n_groups = ((int64_t)gridDim.x * blockDim.x) / kGroup;
+    for (int64_t r = group; r < n_rec; r += n_groups) {
+        const BrRec R = rec[r];
+        if (!(R.flag >> 16)) continue;
+        const bool rev = R.flag & 0x10;
+        const int64_t no = offs[r], co = offs[n1 + r], so = offs[2 * n1 + r];
+        const int l = R.l_seq;
+        for (int i = lane; i < R.l_name; i += kGroup) names[no + i] = (char)d[R.name_at + i];
+        // bases: 4 packed bytes = 8 bases per lane and step
+        for (int s = lane * 8; s < l; s += kGroup * 8) {
+            const uint32_t w = ld_wide(d, R.seq_at + (s >> 1), n);
+            for (int k = 0; k < 8 && s + k < l; ++k) {
+                uint32_t c = nib_code((w >> (8 * (k >> 1) + ((k & 1) ? 0 : 4))) & 15);
+                if (rev && c < 4) c = 3 - c;
+                enc[so + (rev ? l - 1 - (s + k) : s + k)] = (uint8_t)c;
+            }
+        }
+        if (has_qual) {
+            const int64_t qual_at = R.seq_at + ((int64_t)l + 1) / 2;
+            for (int i = lane; i < l; i += kGroup) qual[so + i] = (char)(d[qual_at + (rev ? l - 1 - i : i)] + 33);
+        }
+        // comment: lanes take the listed tags, a prefix sum over the group places each field
+        if (tags.n) {
+            const int64_t aux_at = R.seq_at + ((int64_t)l + 1) / 2 + l;
+            int before = 0;                                                   // bytes of the fields of the rounds before
+            for (int t0 = 0; t0 < tags.n; t0 += kGroup) {
+                const int t = t0 + lane;
+                int ty = 0, len = 0;
+                int64_t v = -1;
+                if (t < tags.n) {
+                    v = aux_find(d, aux_at, R.end, tags.t[2 * t], tags.t[2 * t + 1], &ty);
+                    if (v >= 0) len = aux_text_len(d, v, ty) + 1;             // with the tab in front of it
+                }
+                int incl = len;
+                for (int o = 1; o < kGroup; o <<= 1) {
+                    const int x = __shfl_up(incl, o, kGroup);
+                    if (lane >= o) incl += x;
+                }
+                const int excl = before + incl - len;
+                if (v >= 0) {
+                    char *out = comments + co + excl - 1;                     // the first field has no tab
+                    if (excl) out[0] = '\t';
+                    aux_text_write(d, v, ty, tags.t[2 * t], tags.t[2 * t + 1], out + 1);
+                }
+                before += __shfl(incl, kGroup - 1, kGroup);
+            }
+        }
+    }
+}
+
+}  // namespace
+}  // namespace bwams
+
+using namespace bwams;
+
+extern "C" {
+
+int bwams_bam_reads_decode(int device, const void *bam, int64_t n_bytes, const char *tags, bwams_fastq_t **out, int64_t *n_reads,
+                           int64_t *n_bases, int64_t *n_records) {
+    if (!bam || n_bytes < 0 || !out) return BWAMS_ERR_ARG;
+    *out = nullptr;
+    Tags tg;
+    memset(&tg, 0, sizeof tg);
+    if (tags) {
+        const size_t lt = strlen(tags);
+        if ((lt & 1) || lt > 2 * kMaxTags) {
+            set_last_error("bwams_bam_reads_decode: tags must be two-letter tags back to back, at most 32 of them");
+            return BWAMS_ERR_ARG;
+        }
+        tg.n = (int32_t)(lt / 2);
+        memcpy(tg.t, tags, lt);
+    }
+    if (n_bytes >= ((int64_t)1 << 36)) {
+        set_last_error("bwams_bam_reads_decode: a buffer of 2^36 bytes or more (cut the records into chunks)");
+        return BWAMS_ERR_UNSUPPORTED;
+    }
+    BWAMS_HIP(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    std::unique_ptr<bwams_fastq> f(new bwams_fastq());
+    f->device = device;
+    auto finish = [&](int64_t n_rec) {
+        if (n_reads) *n_reads = f->n_reads;
+        if (n_bases) *n_bases = f->n_bases;
+        if (n_records) *n_records = n_rec;
+        f->n_records = n_rec;
+        *out = f.release();
+        return BWAMS_OK;
+    };
+    auto empty = [&](int64_t n_rec) -> int {          // rule 7: the handle of a text without records
+        f->cum.assign(1, 0); f->name_off.assign(1, 0); f->comment_off.assign(1, 0);
+        BWAMS_HIP(f->d_enc.alloc(64)); BWAMS_HIP(f->d_qual.alloc(64)); BWAMS_HIP(f->d_names.alloc(64)); BWAMS_HIP(f->d_comments.alloc(64));
+        return finish(n_rec);
+    };
+    if (n_bytes == 0) return empty(0);
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr, c = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); if (c) (void)hipEventDestroy(c); }
+    } evs;
+    BWAMS_HIP(hipEventCreate(&evs.a)); BWAMS_HIP(hipEventCreate(&evs.b)); BWAMS_HIP(hipEventCreate(&evs.c));
+    // the records may already be in this GPU's memory; the kernels want them 16-byte aligned
+    hipPointerAttribute_t attr;
+    const bool on_dev = hipPointerGetAttributes(&attr, bam) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();
+    DevBuf<uint8_t> own;
+    DevBuf<unsigned long long> bm;
+    DevBuf<uint32_t> rank, up;
+    DevBuf<int64_t> cand_off, res, wide, offs, comp;
+    DevBuf<BrRec> recs;
+    DevBuf<BrFlags> flags;
+    DevBuf<> scan_tmp;
+    const uint8_t *d = static_cast<const uint8_t *>(bam);
+    if (!on_dev || (reinterpret_cast<uintptr_t>(bam) & 15)) {
+        BWAMS_HIP(own.alloc((size_t)n_bytes + 16));
+        BWAMS_HIP(hipMemcpy(own.p, bam, (size_t)n_bytes, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        d = own.p;
+    }
+    BWAMS_HIP(hipEventRecord(evs.a, st));
+    // (1) the filter, the ranks
+    const int64_t n_tiles = (n_bytes + kTile - 1) / kTile, n_words = n_tiles * (kTile / 64);
+    BWAMS_HIP(bm.alloc((size_t)n_words * 8));
+    BWAMS_HIP(rank.alloc((size_t)(n_words + 1) * 4));
+    br_filter_kernel<<<(unsigned)n_tiles, 256, 0, st>>>(d, n_bytes, bm.p, rank.p);
+    BWAMS_HIP(hipMemsetAsync(rank.p + n_words, 0, 4, st));
+    {
+        size_t tb = 0;
+        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, rank.p, rank.p, 0u, (size_t)(n_words + 1), rocprim::plus<uint32_t>(), st));
+        BWAMS_HIP(scan_tmp.alloc(tb + 16));
+        BWAMS_HIP(rocprim::exclusive_scan(scan_tmp.p, tb, rank.p, rank.p, 0u, (size_t)(n_words + 1), rocprim::plus<uint32_t>(), st));
+    }
+    uint32_t n_cand = 0;
+    BWAMS_HIP(hipMemcpyAsync(&n_cand, rank.p + n_words, 4, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    auto bad_record = [&](int64_t ordinal, int64_t at) {
+        set_last_error("bwams_bam_reads_decode: record " + std::to_string(ordinal) + " at byte " + std::to_string(at) +
+                       " is not a well-formed BAM record inside the buffer (block_size, l_read_name, l_seq, the name's NUL), or the "
+                       "records do not end at n_bytes");
+        return BWAMS_ERR_ARG;
+    };
+    if (n_cand == 0) return bad_record(0, 0);
+    // (2) successors, (3) lifting
+    int levels = 1;
+    while (((int64_t)1 << (levels - 1)) < (int64_t)n_cand) ++levels;
+    const int64_t stride = (int64_t)n_cand + 2;
+    BWAMS_HIP(cand_off.alloc((size_t)n_cand * 8));
+    BWAMS_HIP(up.alloc((size_t)levels * (size_t)stride * 4));
+    BWAMS_HIP(res.alloc(64));
+    br_succ_kernel<<<(unsigned)((n_words + 255) / 256), 256, 0, st>>>(d, n_bytes, bm.p, rank.p, n_words, n_cand, cand_off.p, up.p);
+    for (int k = 1; k < levels; ++k)
+        br_double_kernel<<<(unsigned)((stride + 255) / 256), 256, 0, st>>>(up.p + (int64_t)(k - 1) * stride, up.p + (int64_t)k * stride, stride);
+    br_count_kernel<<<1, 1, 0, st>>>(d, bm.p, up.p, levels, n_cand, cand_off.p, res.p);
+    int64_t h_res[3] = {0, 0, 0};
+    BWAMS_HIP(hipMemcpyAsync(h_res, res.p, 24, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipEventRecord(evs.b, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    if (h_res[0] < 0) return bad_record(h_res[1], h_res[2]);
+    const int64_t n_rec = h_res[0], n1 = n_rec + 1;
+    f->n_cand = n_cand;
+    // measure, scans, the kept reads' offsets
+    BWAMS_HIP(recs.alloc((size_t)n1 * sizeof(BrRec)));
+    BWAMS_HIP(wide.alloc((size_t)n1 * 4 * 8));
+    BWAMS_HIP(offs.alloc((size_t)n1 * 4 * 8));
+    BWAMS_HIP(comp.alloc((size_t)n1 * 3 * 8));
+    BWAMS_HIP(flags.alloc(sizeof(BrFlags)));
+    BWAMS_HIP(hipMemsetAsync(flags.p, 0xFF, sizeof(BrFlags), st));
+    br_measure_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(d, up.p, levels, n_cand, cand_off.p, n_rec, tg, recs.p, wide.p, flags.p);
+    {
+        size_t tb = 0;                                // the four rows are scans of one size
+        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, wide.p, offs.p, (int64_t)0, (size_t)n1, rocprim::plus<int64_t>(), st));
+        BWAMS_HIP(scan_tmp.ensure(tb + 16));
+        for (int row = 0; row < 4; ++row)
+            BWAMS_HIP(rocprim::exclusive_scan(scan_tmp.p, tb, wide.p + row * n1, offs.p + row * n1, (int64_t)0, (size_t)n1, rocprim::plus<int64_t>(), st));
+    }
+    br_compact_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(wide.p, offs.p, n_rec, comp.p);
+    BrFlags h_fl;
+    int64_t tot[4] = {0, 0, 0, 0};
+    BWAMS_HIP(hipMemcpyAsync(&h_fl, flags.p, sizeof h_fl, hipMemcpyDeviceToHost, st));
+    for (int row = 0; row < 4; ++row) BWAMS_HIP(hipMemcpyAsync(&tot[row], offs.p + row * n1 + n_rec, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    // rules 4 and 6: the earliest record decides; within one record l_seq 0, then mixed qualities, then the aux fields
+    unsigned long long err = h_fl.err;
+    if (h_fl.first_q != ~0ull && h_fl.first_n != ~0ull) {
+        const unsigned long long mixed = std::max(h_fl.first_q, h_fl.first_n) << 8 | kErrMixed;
+        if (mixed < err) err = mixed;
+    }
+    if (err != ~0ull) {
+        const int64_t ordinal = (int64_t)(err >> 8);
+        int64_t at = 0;
+        BrRec R;
+        BWAMS_HIP(hipMemcpy(&R, recs.p + ordinal, sizeof R, hipMemcpyDeviceToHost));
+        at = R.name_at - 36;
+        const std::string where = "bwams_bam_reads_decode: record " + std::to_string(ordinal) + " at byte " + std::to_string(at) + ": ";
+        switch (err & 0xFF) {
+        case kErrLseq0: set_last_error(where + "a read without bases (l_seq 0)"); return BWAMS_ERR_UNSUPPORTED;
+        case kErrMixed:
+            set_last_error(where + (h_fl.first_q < h_fl.first_n ? "no qualities, while record " + std::to_string(h_fl.first_q) + " has them"
+                                                                : "qualities, while record " + std::to_string(h_fl.first_n) + " has none"));
+            return BWAMS_ERR_UNSUPPORTED;
+        case kErrAuxType: set_last_error(where + "a listed tag of type f or B"); return BWAMS_ERR_UNSUPPORTED;
+        default: set_last_error(where + "an aux field of unknown type, or one that runs past its record"); return BWAMS_ERR_ARG;
+        }
+    }
+    const int64_t n_kept = tot[3];
+    if (n_kept == 0) return empty(n_rec);
+    const size_t k1 = (size_t)n_kept + 1;
+    f->name_off.resize(k1); f->comment_off.resize(k1); f->cum.resize(k1);
+    BWAMS_HIP(hipMemcpyAsync(f->name_off.data(), comp.p, k1 * 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(f->comment_off.data(), comp.p + n1, k1 * 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(f->cum.data(), comp.p + 2 * n1, k1 * 8, hipMemcpyDeviceToHost, st));
+    f->has_qual = h_fl.first_q != ~0ull;
+    f->n_reads = n_kept; f->name_bytes = tot[0]; f->comment_bytes = tot[1]; f->n_bases = tot[2];
+    BWAMS_HIP(f->d_enc.alloc((size_t)f->n_bases + 64));
+    BWAMS_HIP(f->d_qual.alloc((size_t)f->n_bases + 64));
+    BWAMS_HIP(f->d_names.alloc((size_t)f->name_bytes + 64));
+    BWAMS_HIP(f->d_comments.alloc((size_t)f->comment_bytes + 64));
+    {
+        int64_t blocks = (n_rec + 256 / kGroup - 1) / (256 / kGroup);
+        if (blocks > 256 * 256) blocks = 256 * 256;
+        br_emit_kernel<<<(unsigned)blocks, 256, 0, st>>>(d, n_bytes, recs.p, n_rec, offs.p, tg, f->has_qual ? 1 : 0, f->d_names.p,
+                                                         f->d_comments.p, f->d_enc.p, f->d_qual.p);
+    }
+    BWAMS_HIP(hipEventRecord(evs.c, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    BWAMS_HIP(hipGetLastError());
+    float ms_emit = 0;
+    (void)hipEventElapsedTime(&f->ms_discover, evs.a, evs.b);
+    (void)hipEventElapsedTime(&ms_emit, evs.b, evs.c);
+    f->ms = f->ms_discover + ms_emit;
+    return finish(n_rec);
+}
+
+int bwams_bam_reads_info(const bwams_fastq_t *f, float *ms_discover, float *ms_emit, int64_t *n_candidates, int64_t *n_records) {
+    if (!f) return BWAMS_ERR_ARG;
+    if (ms_discover) *ms_discover = f->ms_discover;
+    if (ms_emit) *ms_emit = f->ms - f->ms_discover;
+    if (n_candidates) *n_candidates = f->n_cand;
+    if (n_records) *n_records = f->n_records;
+    return BWAMS_OK;
+}
+
+}  // extern "C"

@@ -294,7 +294,22 @@ struct BnsMeta {
     DevBuf<> d_pac;                                      // the 2-bit .pac, ceil(l_pac / 4) bytes in HBM
 };
 }  // namespace bwams
-struct bwams_fastq;
+// a decoded chunk of reads (fastq.hip: FASTQ / FASTA text; bam_reads.hip: BAM records), resident on its device
+struct bwams_fastq {
+    int device = 0;
+    int64_t n_reads = 0, n_bases = 0, name_bytes = 0, comment_bytes = 0;
+    bwams::DevBuf<uint8_t> d_enc;
+    bwams::DevBuf<char> d_qual, d_names, d_comments;
+    std::vector<int64_t> cum, name_off, comment_off;       // host copies of the three offset arrays
+    float ms = 0;
+    bool has_qual = true;                                  // false: FASTA text, or BAM records without qualities
+    float ms_discover = 0;                                 // bam_reads.hip: the part of ms spent finding the records,
+    int64_t n_cand = 0, n_records = 0;                     // the offsets that passed its filter, the records (skipped ones included)
+    // a decode that fails half way (an allocation, a kernel) drops the handle: whatever it had allocated goes with it
+    ~bwams_fastq() {
+        if (d_enc.p || d_qual.p || d_names.p || d_comments.p) (void)hipSetDevice(device);
+    }
+};
 namespace bwams {
 int fastq_classify(bwams_fastq *f, std::vector<uint8_t> *which);                       // bseq_classify: 1 = an end of a pair
 int fastq_subset(bwams_fastq *f, const std::vector<int64_t> &ids, bwams_fastq **out);  // those reads as a chunk of their own

@@ -27,20 +27,6 @@
 #include <vector>
 #include "common.h"
 
-struct bwams_fastq {
-    int device = 0;
-    int64_t n_reads = 0, n_bases = 0, name_bytes = 0, comment_bytes = 0;
-    bwams::DevBuf<uint8_t> d_enc;
-    bwams::DevBuf<char> d_qual, d_names, d_comments;
-    std::vector<int64_t> cum, name_off, comment_off;       // host copies of the three offset arrays
-    float ms = 0;
-    bool has_qual = true;                                  // false: FASTA text
-    // a decode that fails half way (an allocation, a kernel) drops the handle: whatever it had allocated goes with it
-    ~bwams_fastq() {
-        if (d_enc.p || d_qual.p || d_names.p || d_comments.p) (void)hipSetDevice(device);
-    }
-};
-
 namespace bwams {
 namespace {
 

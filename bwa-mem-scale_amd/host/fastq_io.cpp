@@ -15,11 +15,15 @@
 //   * where the text comes from is a Source: zlib's gzread (bwams_reader_open, and bwams_reader_open_device on any file that is not
 //     BGZF), or BGZF members inflated on a GPU (bwams_reader_open_device: read(2) into page-locked staging, bwams_inflater_run into
 //     the chunk buffer behind the carried bytes).  The cut loop is the same for both, so their chunks are the same bytes.
+//   * bwams_reader_open_bam: the same Sources under a BAM file.  Open parses the header block on the caller's thread; the reader's
+//     thread then cuts chunks of whole BAM records, hopping along block_size where the text loop scans lines (one_bam_record), with
+//     the same cut.  Such chunks go to bwams_process_chunk_bam; bwams_bseq_parse below stays FASTQ-only.
 // Host C++ only.  zlib is the reference's own dependency for this step (Makefile: -lz).
 #include <fcntl.h>
 #include <unistd.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -91,6 +95,27 @@ int64_t one_record(const char *t, int64_t p, int64_t end, bool final, int64_t *b
     while (a < end && (t[a] == '\n' || (t[a] == '\r' && a + 1 < end && t[a + 1] == '\n'))) a += t[a] == '\n' ? 1 : 2;   // blank lines
     if (a >= end && !final) return -1;                  // (whether blank lines or the next header follow is not known yet)
     return a;
+}
+
+// One BAM record at p in [p, end) (rule 1 of bwams_bam_reads_decode, include/bwams.h): the position behind it, -1 when more input is
+// needed, -2 when no well-formed record starts here.  *kept: FLAG has neither 0x100 nor 0x800; *bases: its l_seq; *size: 4 + block_size
+// once that is known (the caller tells a record larger than its buffer from one the file cuts off).
+int64_t one_bam_record(const char *t, int64_t p, int64_t end, bool *kept, int64_t *bases, int64_t *size) {
+    const unsigned char *u = reinterpret_cast<const unsigned char *>(t) + p;
+    auto u32 = [&](int at) { return (uint32_t)u[at] | (uint32_t)u[at + 1] << 8 | (uint32_t)u[at + 2] << 16 | (uint32_t)u[at + 3] << 24; };
+    *size = 0;
+    if (p + 4 > end) return -1;
+    const int64_t block_size = u32(0);
+    if (block_size < 32) return -2;
+    *size = 4 + block_size;
+    if (p + 36 > end) return -1;
+    const int64_t l_name = u[12], n_cig = u[16] | u[17] << 8, flag = u[18] | u[19] << 8, l_seq = (int32_t)u32(20);
+    if (l_name < 1 || l_seq < 0 || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > block_size) return -2;
+    if (p + 4 + block_size > end) return -1;
+    if (u[35 + l_name] != 0) return -2;
+    *kept = !(flag & 0x900);
+    *bases = l_seq;
+    return p + 4 + block_size;
 }
 
 using Clock = std::chrono::steady_clock;
@@ -210,6 +235,10 @@ struct bwams_reader {
     // carry: bytes inflated but not yet part of a chunk
     std::vector<char> carry;
     bwams_reader_stats_t stats{};                       // src->st as of the last read, under stat_mu
+    bool bam = false;                                   // bwams_reader_open_bam: chunks of BAM records
+    std::string bam_text;                               // its header text,
+    int32_t bam_n_ref = 0;                              // the number of references,
+    int64_t bam_records = 0;                            // and the records cut so far (the ordinal in an error text)
     mutable std::mutex stat_mu;
 };
 
@@ -233,7 +262,21 @@ static void reader_main(bwams_reader *r) {
         bool full = false;
         while (!full && !r->rc) {
             // parse what is there
-            while (pos < have) {
+            while (r->bam && pos < have) {                                   // BAM: hop along block_size
+                bool kept = false;
+                int64_t b = 0, size = 0;
+                const int64_t nx = one_bam_record(c.buf, pos, have, &kept, &b, &size);
+                if (nx == -1) {
+                    if (size > c.cap - 1) { r->rc = BWAMS_ERR_CAPACITY; r->err = "a record larger than the chunk buffer"; }
+                    break;
+                }
+                if (nx == -2) { r->rc = BWAMS_ERR_IO; r->err = "BAM record " + std::to_string(r->bam_records) + " is not well formed"; break; }
+                pos = nx; ++r->bam_records;
+                if (!kept) continue;
+                ++reads; bases += b;
+                if (bases >= r->chunk_bases && (!r->paired || (reads & 1) == 0)) { full = true; break; }     // the same cut, after a kept record
+            }
+            while (!r->bam && pos < have) {
                 if (c.buf[pos] == '\n') { ++pos; continue; }                 // blank lines in front of a header
                 int64_t b = 0;
                 const int64_t nx = one_record(c.buf, pos, have, file_end, &b);
@@ -312,6 +355,23 @@ static int zlib_source(const char *path, std::unique_ptr<Source> *out) {
     return BWAMS_OK;
 }
 
+// The Source of bwams_reader_open_device: BGZF members inflated on `device`, anything else through zlib
+static int device_source(const char *path, int device, std::unique_ptr<Source> *out) {
+    if (device < 0 || !is_bgzf(path)) return zlib_source(path, out);
+    constexpr int64_t kIn = 32 << 20, kOut = 64 << 20;     // one call: up to 32 MiB of members, 64 MiB of text
+    auto b = std::unique_ptr<BgzfSource>(new BgzfSource());
+    b->path = path;
+    b->st.device_inflate = 1;
+    b->step = kOut;
+    b->fd = open(path, O_RDONLY);
+    if (b->fd < 0) return BWAMS_ERR_IO;
+    if (int rc = bwams_host_alloc((size_t)kIn, reinterpret_cast<void **>(&b->zbuf))) return rc;
+    b->zcap = kIn;
+    if (int rc = bwams_inflater_create(device, kIn, kOut, &b->inf)) return rc;
+    *out = std::move(b);
+    return BWAMS_OK;
+}
+
 int bwams_reader_open(const char *path, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes, int32_t n_buffers, bwams_reader_t **out) {
     if (!path || !out || chunk_bases <= 0 || n_buffers < 1 || n_buffers > 16) return BWAMS_ERR_ARG;
     *out = nullptr;
@@ -335,27 +395,87 @@ int bwams_reader_open_device(const char *path, int device, int64_t chunk_bases, 
     bwams_reader *r = nullptr;
     try {
         r = new bwams_reader();
-        if (!is_bgzf(path)) {
-            if (int rc = zlib_source(path, &r->src)) { delete r; return rc; }
-        } else {
-            constexpr int64_t kIn = 32 << 20, kOut = 64 << 20;     // one call: up to 32 MiB of members, 64 MiB of text
-            auto b = std::unique_ptr<BgzfSource>(new BgzfSource());
-            b->path = path;
-            b->st.device_inflate = 1;
-            b->step = kOut;
-            b->fd = open(path, O_RDONLY);
-            if (b->fd < 0) { delete r; return BWAMS_ERR_IO; }
-            if (int rc = bwams_host_alloc((size_t)kIn, reinterpret_cast<void **>(&b->zbuf))) { delete r; return rc; }
-            b->zcap = kIn;
-            if (int rc = bwams_inflater_create(device, kIn, kOut, &b->inf)) { delete r; return rc; }
-            r->src = std::move(b);
-        }
+        if (int rc = device_source(path, device, &r->src)) { delete r; return rc; }
         if (int rc = reader_start(r, chunk_bases, paired, buffer_bytes, n_buffers)) { bwams_reader_close(r); return rc; }
     } catch (...) {
         if (r) bwams_reader_close(r);
         return BWAMS_ERR_NOMEM;
     }
     *out = r;
+    return BWAMS_OK;
+}
+
+// The BAM header block from the start of the stream: magic, l_text, text, n_ref, then l_name / name / l_ref per reference.  What was
+// inflated behind it becomes the reader's carry.
+static int bam_header_parse(bwams_reader *r) {
+    std::vector<char> hb;
+    bool file_end = false;
+    auto need = [&](size_t n) -> int {                       // 0: hb holds n bytes
+        while (hb.size() < n) {
+            if (file_end) { r->err = "the file ends inside the BAM header"; return BWAMS_ERR_IO; }
+            const size_t have = hb.size();
+            const int64_t want = std::max<int64_t>(1 << 20, (int64_t)std::min<size_t>(n - have, (size_t)r->src->step));
+            hb.resize(have + (size_t)want);
+            std::string e_;
+            const int64_t got = r->src->read(hb.data() + have, want, e_);
+            r->stats = r->src->st;
+            hb.resize(have + (size_t)std::max<int64_t>(got, 0));
+            if (got < 0) { r->err = e_; return (int)got; }
+            if (got == 0) file_end = true;
+        }
+        return BWAMS_OK;
+    };
+    auto i32 = [&](size_t at) {
+        const unsigned char *u = reinterpret_cast<const unsigned char *>(hb.data()) + at;
+        return (int32_t)((uint32_t)u[0] | (uint32_t)u[1] << 8 | (uint32_t)u[2] << 16 | (uint32_t)u[3] << 24);
+    };
+    if (int rc = need(4)) return rc;
+    if (memcmp(hb.data(), "BAM\1", 4) != 0) { r->err = "not a BAM file (no BAM\\1 magic)"; return BWAMS_ERR_UNSUPPORTED; }
+    if (int rc = need(8)) return rc;
+    const int64_t l_text = i32(4);
+    if (l_text < 0) { r->err = "BAM header: negative l_text"; return BWAMS_ERR_IO; }
+    if (int rc = need((size_t)(12 + l_text))) return rc;
+    r->bam_text.assign(hb.data() + 8, (size_t)l_text);
+    const int32_t n_ref = i32((size_t)(8 + l_text));
+    if (n_ref < 0) { r->err = "BAM header: negative n_ref"; return BWAMS_ERR_IO; }
+    size_t p = (size_t)(12 + l_text);
+    for (int32_t k = 0; k < n_ref; ++k) {
+        if (int rc = need(p + 4)) return rc;
+        const int64_t l_name = i32(p);
+        if (l_name < 1) { r->err = "BAM header: reference " + std::to_string(k) + " without a name"; return BWAMS_ERR_IO; }
+        if (int rc = need(p + 8 + (size_t)l_name)) return rc;
+        p += 8 + (size_t)l_name;
+    }
+    r->bam_n_ref = n_ref;
+    r->carry.assign(hb.begin() + (std::ptrdiff_t)p, hb.end());
+    return BWAMS_OK;
+}
+
+int bwams_reader_open_bam(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes, int32_t n_buffers,
+                          bwams_reader_t **out) {
+    if (!path || !out || chunk_bases <= 0 || n_buffers < 1 || n_buffers > 16) return BWAMS_ERR_ARG;
+    *out = nullptr;
+    bwams_reader *r = nullptr;
+    try {
+        r = new bwams_reader();
+        r->bam = true;
+        if (int rc = device_source(path, device, &r->src)) { delete r; return rc; }
+        if (int rc = bam_header_parse(r)) { delete r; return rc; }
+        // a BAM record of 150 bases is ~ 1.6 bytes per base; the text reader's default (3 per base + 64 MiB) is room enough
+        if (int rc = reader_start(r, chunk_bases, paired, buffer_bytes, n_buffers)) { bwams_reader_close(r); return rc; }
+    } catch (...) {
+        if (r) bwams_reader_close(r);
+        return BWAMS_ERR_NOMEM;
+    }
+    *out = r;
+    return BWAMS_OK;
+}
+
+int bwams_reader_bam_header(const bwams_reader_t *r, const char **text, int64_t *n_text, int32_t *n_ref) {
+    if (!r || !r->bam) return BWAMS_ERR_ARG;
+    if (text) *text = r->bam_text.data();
+    if (n_text) *n_text = (int64_t)r->bam_text.size();
+    if (n_ref) *n_ref = r->bam_n_ref;
     return BWAMS_OK;
 }
 

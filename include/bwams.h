@@ -469,6 +469,39 @@ int bwams_fastq_to_batch(bwams_fastq_t *f, bwams_batch_t *b);
 int bwams_fastq_to_batch_opt(bwams_fastq_t *f, bwams_batch_t *b, int32_t copy_comment);
 int bwams_fastq_close(bwams_fastq_t *f);
 
+/* ------------------------------------------------------------- BAM as read input ---- *
+ * BAM alignment records (SAMv1 §4.2, back to back, no header block; host or this device's memory) as a decoded chunk: what
+ * `samtools fastq` (htslib's bam2fq) hands to `bwa mem`, computed on the device (csrc/bam_reads.hip).  bwams/bam_reads.py restates
+ * the rules.  The result is an ordinary bwams_fastq_t: bwams_fastq_info / _has_qual / _fetch / _to_batch / _to_batch_opt / _close
+ * work on it unchanged.
+ *  1. Records.  Record 0 starts at byte 0, record k + 1 at start_k + 4 + block_size_k.  A record is well formed when block_size >= 32,
+ *     l_read_name >= 1, l_seq >= 0, 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= block_size, the name's last byte is
+ *     NUL and the record ends at or before n_bytes; the chain must end exactly at n_bytes.  Anything else is BWAMS_ERR_ARG, no handle
+ *     is left, and bwams_last_error names the earliest bad record's ordinal and byte offset ("record K at byte Q").  refID, POS, bin,
+ *     MAPQ, the mate fields and the CIGAR's content are not looked at.  The records are checked before anything of rules 2-6.
+ *  2. Kept records.  Records with FLAG 0x100 or 0x800 are skipped (`samtools fastq`'s default -F 0x900); all others become reads, in
+ *     record order.  *n_records counts all records, *n_reads the kept ones.
+ *  3. Bases.  The 4-bit codes 1, 2, 4, 8 (A, C, G, T) become 0, 1, 2, 3, every other code 4 (nst_nt4_table of the letter).  With FLAG
+ *     0x10 the read is reverse-complemented: base i of the read is 3 - c of base l_seq - 1 - i when c < 4, and 4 otherwise.
+ *  4. Qualities.  QUAL + 33, reversed with 0x10.  A record whose first QUAL byte is 0xFF has none.  No kept record with qualities:
+ *     bwams_fastq_has_qual = 0, as for FASTA text.  Some with and some without: BWAMS_ERR_UNSUPPORTED, naming the first kept record
+ *     that differs from the first kept record.  A kept record with l_seq == 0: BWAMS_ERR_UNSUPPORTED.
+ *  5. Names.  The name bytes as stored, without the NUL.  No "/<digit>" trimming (samtools would append "/1" or "/2", and bwa would
+ *     strip just that).
+ *  6. Comments.  tags: NULL, "", or two-letter tags back to back ("RGBCRX"); an odd length or more than 32 tags is BWAMS_ERR_ARG.
+ *     For each listed tag, in list order, the record's first aux field with that tag becomes TG:T:value; the fields are joined by
+ *     tabs — the form `mem -C` appends and bwams_bam_run accepts.  Types A, Z, H are copied; c / C / s / S / i / I are printed as :i:
+ *     decimal.  A listed tag of type f or B is BWAMS_ERR_UNSUPPORTED.  With a non-empty list every aux field of a kept record is
+ *     walked: a field of an unknown type, or one that runs past its record, is BWAMS_ERR_ARG.  No listed tag present: no comment.
+ *     Within one record rule 4 is checked before rule 6; among records the earliest one decides, and bwams_last_error names it.
+ *  7. No kept read at all (n_bytes == 0, or everything skipped): what bwams_fastq_decode returns for a text without records.
+ * Scratch memory that does not fit is BWAMS_ERR_NOMEM and leaves nothing behind.  Inputs of 2^36 bytes or more: BWAMS_ERR_UNSUPPORTED.
+ * bwams_bam_reads_info (a handle of bwams_bam_reads_decode; BWAMS_ERR_ARG otherwise): the device time of finding the records and of
+ * everything behind it (measure, scans, emit), the offsets that passed the filter of the record search, and the records found. */
+int bwams_bam_reads_decode(int device, const void *bam, int64_t n_bytes, const char *tags, bwams_fastq_t **out, int64_t *n_reads,
+                           int64_t *n_bases, int64_t *n_records);
+int bwams_bam_reads_info(const bwams_fastq_t *f, float *ms_discover, float *ms_emit, int64_t *n_candidates, int64_t *n_records);
+
 /* ----------------------------------------------------------- mate rescue ---- */
 
 /* Local Smith-Waterman of mate rescue over n tasks: out[i] = ksw_align2(len2, qer + idq,
@@ -721,6 +754,17 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
                               const bwams_sam_opt_t *sam_opt, const char *fastq, int64_t n_bytes, const bwams_pestat_t *pes0,
                               int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *n_single, int64_t *sam_bytes);
 #define BWAMS_CHUNK_COPY_COMMENT 0x100
+/* bwams_process_chunk / _chunk_smart with bwams_bam_reads_decode in place of bwams_fastq_decode: bam[0, n_bytes) are whole BAM records
+ * (host or device memory, no header block), tags as for bwams_bam_reads_decode (the comments reach the SAM text only with
+ * BWAMS_CHUNK_COPY_COMMENT).  With paired, kept reads 2k and 2k + 1 are the two ends, in file order — what `samtools fastq | bwa mem -p`
+ * does; collating a coordinate-sorted BAM (`samtools collate`) is the caller's job.  Everything behind the decode is bwams_process_chunk's. */
+int bwams_process_chunk_bam(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                            const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags, int32_t paired,
+                            const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes);
+int bwams_process_chunk_bam_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                                  const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags,
+                                  const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *n_single,
+                                  int64_t *sam_bytes);
 
 /* mem_process_seqs (src/bwamem.cpp:1850-1903) for a chunk that arrives the way the reference hands it over: parsed records (bseq1_t:
  * name, comment, seq, qual — src/bwa.h:76-86), here as flat arrays — enc_qdb / cum_len as bwams_seed_upload takes them, names (NUL
@@ -795,6 +839,19 @@ typedef struct bwams_reader_stats {
     float ms_read, ms_inflate;                   /* reader thread: read(2) (device path only), inflate */
 } bwams_reader_stats_t;
 int bwams_reader_info(const bwams_reader_t *r, bwams_reader_stats_t *out);
+/* A BAM file as read input: BGZF inflated on `device` as bwams_reader_open_device inflates it (device < 0: zlib on the reader's thread,
+ * gzread reads BGZF).  Open parses the header block (magic, l_text, text, n_ref, the references; it may span many members) before the
+ * reader's thread starts: a wrong magic is BWAMS_ERR_UNSUPPORTED, a header cut off by the end of the file BWAMS_ERR_IO.
+ * bwams_reader_next returns whole BAM records (no header) for bwams_process_chunk_bam / bwams_bam_reads_decode; n_reads counts the
+ * kept records (neither 0x100 nor 0x800), n_bases is the sum of their l_seq.  The cut is bwams_reader_open's, evaluated right after
+ * each kept record (skipped records that follow go to the next chunk): chunk i holds exactly the reads of chunk i of
+ * bwams_reader_open over the equivalent FASTQ.  A record that is not well formed (rule 1 of bwams_bam_reads_decode) is BWAMS_ERR_IO,
+ * with its ordinal in bwams_reader_error.  bwams_reader_bam_header: the header text (not NUL terminated; it lives as long as the
+ * reader — its @RG lines may go into bwams_sam_header's hdr_line) and the number of references; BWAMS_ERR_ARG for a reader of text.
+ * The mem_process_seqs / bwams_bseq_parse path stays FASTQ-only. */
+int bwams_reader_open_bam(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes, int32_t n_buffers,
+                          bwams_reader_t **out);
+int bwams_reader_bam_header(const bwams_reader_t *r, const char **text, int64_t *n_text, int32_t *n_ref);
 int bwams_writer_open(const char *path, int32_t n_shards, bwams_writer_t **out);
 int bwams_writer_put(bwams_writer_t *w, int32_t shard, int64_t seq, const char *text, int64_t n_bytes);
 int bwams_writer_close(bwams_writer_t *w);       /* waits until everything handed over in order is on disk */
