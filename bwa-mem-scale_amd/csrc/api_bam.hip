@@ -15,7 +15,7 @@ extern "C" {
 /* ------------------------------------------------------------ BAM records (bam.hip) ---- */
 
 int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
-    if (!b || !b->chain || !b->chain->sm.done) {
+    if (!b || !b->stages || !b->stages->sm.done) {
         set_last_error("bwams_bam_run: run bwams_sam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -28,7 +28,7 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
         set_last_error("bwams_bam_run: two of the index's sequences have the same name; BAM cannot tell them apart");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(ix->device));
     hipStream_t st = b->stream;
     outdated(s, From::bam);
@@ -82,11 +82,11 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
 }
 
 int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off) {
-    if (!b || !b->chain || !b->chain->bm.done) {
+    if (!b || !b->stages || !b->stages->bm.done) {
         set_last_error("bwams_bam_fetch: run bwams_bam_run first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (bam && s->bm.bytes > cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -97,7 +97,7 @@ int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off)
 }
 
 int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out) {
-    if (!b || !d || !b->chain || !b->chain->bm.done) {
+    if (!b || !d || !b->stages || !b->stages->bm.done) {
         set_last_error("bwams_bam_fetch_bgzf: run bwams_bam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -106,7 +106,7 @@ int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64
                        std::to_string(b->idx->device));
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     return deflater_run_after(d, b->stream, s->bm.out.p, s->bm.bytes, 1, out, cap, 0, flags, n_out, nullptr);
 }
 
@@ -161,11 +161,11 @@ int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t
 }
 
 int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records) {
-    if (!b || !b->chain || !b->chain->bm.done) {
+    if (!b || !b->stages || !b->stages->bm.done) {
         set_last_error("bwams_bam_sort: run bwams_bam_run or bwams_bam_upload first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->bs.done) {
         if (n_records) *n_records = s->bs.nrec;
         return BWAMS_OK;
@@ -203,11 +203,11 @@ int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records) {
 }
 
 int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_coord_t *coords) {
-    if (!b || !b->chain || !b->chain->bm.done || !b->chain->bs.done) {
+    if (!b || !b->stages || !b->stages->bm.done || !b->stages->bs.done) {
         set_last_error("bwams_bam_sorted_fetch: run bwams_bam_sort first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (bam && s->bs.bytes > cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -221,11 +221,11 @@ int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_c
 /* ------------------------------------------------------------ duplicate marking (markdup.hip) ---- */
 
 int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends) {
-    if (!b || !b->chain || !b->chain->bm.done) {
+    if (!b || !b->stages || !b->stages->bm.done) {
         set_last_error("bwams_bam_templates: run bwams_bam_run or bwams_bam_upload first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (!s->md.done) {
         if (s->bm.nrec > 0xFFFFFFFFLL) {
             set_last_error("bwams_bam_templates: more than 2^32 - 1 records");
@@ -242,11 +242,11 @@ int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends)
 }
 
 int bwams_bam_templates_fetch(bwams_batch_t *b, bwams_dup_end_t *ends, int64_t cap, uint32_t *rec_tmpl, int32_t sorted) {
-    if (!b || !b->chain || !b->chain->bm.done || !b->chain->md.done || (sorted && !b->chain->bs.done)) {
+    if (!b || !b->stages || !b->stages->bm.done || !b->stages->md.done || (sorted && !b->stages->bs.done)) {
         set_last_error("bwams_bam_templates_fetch: run bwams_bam_templates (and bwams_bam_sort for sorted = 1) on the current records first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (ends && s->md.t.n_e > cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -317,7 +317,7 @@ int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, in
 int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st) {
     int64_t n_t = 0, n_e = 0;
     if (int rc = bwams_bam_templates(b, &n_t, &n_e)) return rc;
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t q = b->stream;
     const auto t0 = std::chrono::steady_clock::now();

@@ -100,7 +100,7 @@ struct SeedView {
 static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedView &sv, int64_t *n_chains, int64_t *n_seeds);
 
 int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_chains, int64_t *n_seeds) {
-    if (!b || !b->seed_done || !b->with_sa) {
+    if (!b || !b->sd.done || !b->sd.with_sa) {
         set_last_error("bwams_chain_run: run bwams_seed_run(with_sa = 1) first");
         return BWAMS_ERR_ARG;
     }
@@ -108,7 +108,7 @@ int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_cha
     if (rc) return rc;
     if ((rc = bwams_seed_counts(b, nullptr, nullptr))) return rc;     // sizes of the seed stage (and its overflow check)
     SeedView sv;
-    sv.smem = b->d_sorted.p; sv.n_smem = b->n_smem; sv.sa_off = b->d_sa_off.p; sv.sa_coord = b->d_sa_coord.p; sv.n_sa = b->n_sa;
+    sv.smem = b->sd.d_sorted.p; sv.n_smem = b->sd.n_smem; sv.sa_off = b->sd.d_sa_off.p; sv.sa_coord = b->sd.d_sa_coord.p; sv.n_sa = b->sd.n_sa;
     sv.one_smem_quirk = true;
     return chain_common(b, opt, sv, n_chains, n_seeds);
 }
@@ -263,11 +263,11 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
 
 int bwams_chain_fetch(bwams_batch_t *b, bwams_chain_t *chains, int64_t chain_cap, bwams_chain_seed_t *seeds,
                       int64_t seed_cap, int64_t *chain_off) {
-    if (!b || !b->chain || !b->chain->ch.done) {
+    if (!b || !b->stages || !b->stages->ch.done) {
         set_last_error("bwams_chain_fetch: no chains on the device");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->ch.n_chains > chain_cap || s->ch.n_seeds > seed_cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;

@@ -113,7 +113,7 @@ static int ext_build_round(bwams_batch *b, StageState *s, const ExtArgs &A, int6
 }
 
 int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_left, int64_t *n_right) {
-    if (!b || !b->chain || !b->chain->ch.done) {
+    if (!b || !b->stages || !b->stages->ch.done) {
         set_last_error("bwams_extend_build: run bwams_chain_run (or bwams_chain_upload) first");
         return BWAMS_ERR_ARG;
     }
@@ -124,7 +124,7 @@ int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_
     int rc = check_opt(opt, "bwams_extend_build");
     if (rc) return rc;
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     outdated(s, From::built);
     hipStream_t st = b->stream;
     ExtArgs A;
@@ -158,9 +158,9 @@ static int run_side(bwams_batch *b, StageState *s, const ExtArgs &A, int right, 
     if (n == 0) return BWAMS_OK;
     unsigned long long *d_nretry = &b->d_ctr.p->ext_n_retry[right], *h_nretry = &b->h_ctr.p->ext_n_retry[right];   // cleared with the round's counters
     bwams_seqpair_t *rp = A.rtask ? s->ext.rpairs.p : nullptr;       // a settled left task hands its score to the slot's right task
-    if (bsw_list_bytes(n) > b->d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(st));   // the last launch may still read the lists
-    BWAMS_HIP(b->d_bsw_list.ensure(bsw_list_bytes(n), bsw_list_bytes(n + n / 4 + 1024)));
-    if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr.p, b->cu_count, st, b->d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) {
+    if (bsw_list_bytes(n) > b->sw.d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(st));   // the last launch may still read the lists
+    BWAMS_HIP(b->sw.d_bsw_list.ensure(bsw_list_bytes(n), bsw_list_bytes(n + n / 4 + 1024)));
+    if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr.p, b->cu_count, st, b->sw.d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) {
         set_last_error(lrc == -2 ? "banded SW: a query longer than ~18000 bases does not fit the LDS kernel" : "banded SW: stream fork/join failed");
         return lrc == -2 ? BWAMS_ERR_UNSUPPORTED : BWAMS_ERR_DEVICE;
     }
@@ -169,7 +169,7 @@ static int run_side(bwams_batch *b, StageState *s, const ExtArgs &A, int right, 
     BWAMS_HIP(hipStreamSynchronize(st));
     const unsigned long long nr = *h_nretry;
     if (nr) {
-        if (launch_bsw(s->ext.retry.p, (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr.p, b->cu_count, st, b->d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) return BWAMS_ERR_DEVICE;
+        if (launch_bsw(s->ext.retry.p, (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr.p, b->cu_count, st, b->sw.d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) return BWAMS_ERR_DEVICE;
         launch_ext_post(A, right, s->ext.retry.p, (int64_t)nr, A.opt.w << 1, 1, nullptr, d_nretry, rp, st);
     }
     *n_retry_out += (int64_t)nr;
@@ -189,7 +189,7 @@ static int run_side(bwams_batch *b, StageState *s, const ExtArgs &A, int right, 
 // the next round's sizes — and once after the plan, once more when the rest is requested.  One list serves every
 // round: a round's build has consumed it before that round's selection, which alone appends, clears its cursor.
 int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !b->chain || !b->chain->ch.done) {
+    if (!b || !b->stages || !b->stages->ch.done) {
         set_last_error("bwams_extend_run: run bwams_chain_run (or bwams_chain_upload) first");
         return BWAMS_ERR_ARG;
     }
@@ -203,7 +203,7 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
     if (knobs().ext_max_rounds > 0) kMaxRounds = knobs().ext_max_rounds;      // test knob: force the extend-the-rest fallback
     const bool adaptive_off = knobs().ext_all_rounds != 0;                    // test knob: never cut the rounds short
     const bool inplace_on = knobs().ext_inplace != 0;                          // A-B knob: 0 = copy the tasks' bytes into flat buffers
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
     outdated(s, From::built);
@@ -266,11 +266,11 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
 }
 
 int bwams_extend_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off, int32_t *seed_aln) {
-    if (!b || !b->chain || !(b->chain->ext.done || b->chain->ext.built)) {
+    if (!b || !b->stages || !(b->stages->ext.done || b->stages->ext.built)) {
         set_last_error("bwams_extend_fetch: no regions on the device");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->ch.n_seeds > reg_cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -286,15 +286,15 @@ int bwams_extend_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, 
 int bwams_extend_tasks_fetch(bwams_batch_t *b, int32_t side, bwams_seqpair_t *pairs, int64_t pair_cap, uint8_t *ref,
                              int64_t ref_cap, uint8_t *qer, int64_t qer_cap, int64_t *n_pairs, int64_t *ref_bytes,
                              int64_t *qer_bytes) {
-    if (!b || !b->chain || !(b->chain->ext.built || b->chain->ext.done) || (side != 0 && side != 1)) {
+    if (!b || !b->stages || !(b->stages->ext.built || b->stages->ext.done) || (side != 0 && side != 1)) {
         set_last_error("bwams_extend_tasks_fetch: no task lists on the device");
         return BWAMS_ERR_ARG;
     }
-    if (b->chain->ext.tasks_inplace) {
+    if (b->stages->ext.tasks_inplace) {
         set_last_error("bwams_extend_tasks_fetch: bwams_extend_run extends in place and builds no flat task buffers; bwams_extend_build does");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     const int64_t n = side ? s->ext.n_right : s->ext.n_left, rb = side ? s->ext.rref_b : s->ext.lref_b, qb = side ? s->ext.rqer_b : s->ext.lqer_b;
     if (n_pairs) *n_pairs = n;
     if (ref_bytes) *ref_bytes = rb;

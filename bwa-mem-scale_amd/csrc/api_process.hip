@@ -43,7 +43,7 @@ static int process_stage2(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, 
 }
 
 static void process_empty(bwams_batch_t *b, int64_t *sam_bytes) {      // an empty chunk: no reads, no text
-    if (StageState *s = b->chain) { outdated(s, From::bam); s->sm.done = true; s->sm.bytes = 0; s->sm.nregs = 0; s->ch.nseq = 0; s->sm.merged_n = -1; }
+    if (StageState *s = b->stages) { outdated(s, From::bam); s->sm.done = true; s->sm.bytes = 0; s->sm.nregs = 0; s->ch.nseq = 0; s->sm.merged_n = -1; }
     b->nseq = 0;
     if (sam_bytes) *sam_bytes = 0;
 }
@@ -263,7 +263,7 @@ static int chunk_smart_decoded(bwams_batch_t *b, bwams_fastq_t *fq, int64_t n, b
         rc = process_decoded(b, sub, (int64_t)ids[k].size(), emf, ert, so, mo, sam_opt, k, k ? pes0 : nullptr,
                              n_processed + (k ? (int64_t)ids[0].size() : 0), flags, &bytes);
         if (rc) { bwams_fastq_close(fq); return rc; }
-        StageState *s = b->chain;
+        StageState *s = b->stages;
         hipError_t e = held[k].alloc((size_t)bytes + 16);
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(held[k].p, s->sm.out.p, (size_t)bytes, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(held_off[k].data(), s->sm.off.p, held_off[k].size() * 8, hipMemcpyDeviceToHost, st);

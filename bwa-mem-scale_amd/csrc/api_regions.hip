@@ -17,13 +17,13 @@ extern "C" {
 /* ---------------------------------------------- the tail of mem_kernel2_core ---- */
 
 int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !b->chain || !b->chain->ext.done) {
+    if (!b || !b->stages || !b->stages->ext.done) {
         set_last_error("bwams_dedup_run: run bwams_extend_run first");
         return BWAMS_ERR_ARG;
     }
     int rc = check_opt(opt, "bwams_dedup_run");
     if (rc) return rc;
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
     outdated(s, From::dedup);
@@ -88,11 +88,11 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
 }
 
 int bwams_dedup_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off) {
-    if (!b || !b->chain || !b->chain->dd.done) {
+    if (!b || !b->stages || !b->stages->dd.done) {
         set_last_error("bwams_dedup_fetch: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->dd.n_final > reg_cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -130,13 +130,13 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     const int no_rescue = (flags & BWAMS_PAIR_NO_RESCUE) || single_end, use_ert = (flags & BWAMS_PAIR_USE_ERT) != 0;
     static const bwams_pestat_t no_pes[4] = {{0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}};
     if (single_end && !pes) pes = no_pes;
-    if (!b || !b->chain || !b->chain->dd.done) {
+    if (!b || !b->stages || !b->stages->dd.done) {
         set_last_error("bwams_pair_run: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
     int rc = check_opt(opt, "bwams_pair_run");
     if (rc) return rc;
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (!pes || (!single_end && (s->ch.nseq & 1))) {
         set_last_error("bwams_pair_run: needs the insert-size statistics and an even number of reads (ends of pair p at 2p, 2p + 1)");
         return BWAMS_ERR_ARG;
@@ -276,11 +276,11 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
 }
 
 int bwams_pair_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off, bwams_pair_t *pairs) {
-    if (!b || !b->chain || !b->chain->pr.done) {
+    if (!b || !b->stages || !b->stages->pr.done) {
         set_last_error("bwams_pair_fetch: run bwams_pair_run first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->pr.total > reg_cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -294,7 +294,7 @@ int bwams_pair_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, in
 /* ------------------------------------------------------------ mem_perfect2reg ---- */
 
 int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !e || !b->d_emf_out.p || !b->d_emf_code.p) {
+    if (!b || !e || !b->emf.d_emf_out.p || !b->emf.d_emf_code.p) {
         set_last_error("bwams_emf_regs_run: run bwams_emf_run first");
         return BWAMS_ERR_ARG;
     }
@@ -309,7 +309,7 @@ int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *
     BWAMS_HIP(s->er.wide.ensure_n((size_t)n1)); BWAMS_HIP(s->er.off.ensure_n((size_t)n1)); BWAMS_HIP(s->er.ooff.ensure_n((size_t)n1));
     BWAMS_HIP(s->er.n.ensure_n((size_t)n1)); BWAMS_HIP(s->er.rev.ensure_n((size_t)n1));
     EmfRegArgs A;
-    A.t = e->t; A.perfect = b->d_emf_out.p; A.code = b->d_emf_code.p; A.enc = b->d_enc.p; A.cum = b->d_cum.p; A.nseq = nseq;
+    A.t = e->t; A.perfect = b->emf.d_emf_out.p; A.code = b->emf.d_emf_code.p; A.enc = b->d_enc.p; A.cum = b->d_cum.p; A.nseq = nseq;
     if ((rc = dev_bns(b->idx, &A.bns))) return rc;
     A.opt = *opt; A.scratch = nullptr;
     launch_emfregs_count(A, s->er.wide.p, st);
@@ -333,11 +333,11 @@ int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *
 }
 
 int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
-    if (!b || !b->chain || !b->chain->er.done || !b->chain->dd.done || b->chain->er.nseq != b->chain->ch.nseq) {
+    if (!b || !b->stages || !b->stages->er.done || !b->stages->dd.done || b->stages->er.nseq != b->stages->ch.nseq) {
         set_last_error("bwams_emf_regs_merge: run bwams_emf_regs_run and bwams_dedup_run of this chunk first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
     const int64_t nseq = s->ch.nseq, n1 = nseq + 1;
@@ -360,11 +360,11 @@ int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
 }
 
 int bwams_emf_regs_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off, uint8_t *first_is_rev) {
-    if (!b || !b->chain || !b->chain->er.done) {
+    if (!b || !b->stages || !b->stages->er.done) {
         set_last_error("bwams_emf_regs_fetch: run bwams_emf_regs_run first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->er.total > reg_cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -445,7 +445,7 @@ static void pestat_from_sorted(const unsigned long long *keys, size_t n, bwams_p
 }
 
 int bwams_pestat(bwams_batch_t *b, const bwams_mem_opt_t *opt, bwams_pestat_t pes[4]) {
-    if (!b || !b->chain || !b->chain->dd.done || !pes) {
+    if (!b || !b->stages || !b->stages->dd.done || !pes) {
         set_last_error("bwams_pestat: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
@@ -453,13 +453,13 @@ int bwams_pestat(bwams_batch_t *b, const bwams_mem_opt_t *opt, bwams_pestat_t pe
     if (rc) return rc;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     std::vector<unsigned long long> keys;
-    if ((rc = pestat_keys(b, b->chain, opt, &keys))) return rc;
+    if ((rc = pestat_keys(b, b->stages, opt, &keys))) return rc;
     pestat_from_sorted(keys.data(), keys.size(), pes);
     return BWAMS_OK;
 }
 
 int bwams_pestat_keys(bwams_batch_t *b, const bwams_mem_opt_t *opt, uint64_t *keys_out, int64_t cap, int64_t *n_keys) {
-    if (!b || !b->chain || !b->chain->dd.done || !n_keys) {
+    if (!b || !b->stages || !b->stages->dd.done || !n_keys) {
         set_last_error("bwams_pestat_keys: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
@@ -467,7 +467,7 @@ int bwams_pestat_keys(bwams_batch_t *b, const bwams_mem_opt_t *opt, uint64_t *ke
     if (rc) return rc;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     std::vector<unsigned long long> keys;
-    if ((rc = pestat_keys(b, b->chain, opt, &keys))) return rc;
+    if ((rc = pestat_keys(b, b->stages, opt, &keys))) return rc;
     *n_keys = (int64_t)keys.size();
     if ((int64_t)keys.size() > cap) return BWAMS_ERR_CAPACITY;
     if (!keys.empty()) memcpy(keys_out, keys.data(), keys.size() * 8);

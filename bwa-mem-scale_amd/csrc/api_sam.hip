@@ -41,7 +41,7 @@ static int approx_mapq_se(const bwams_mem_opt_t *opt, const bwams_alnreg_t *a) {
 
 static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t source, const uint8_t *only, int64_t *n_aln,
                         int64_t *n_cigar_ops, int64_t *md_bytes) {
-    if (!b || !b->chain || (source == 0 && !b->chain->dd.done) || (source == 1 && !b->chain->pr.done) || source < 0 || source > 1) {
+    if (!b || !b->stages || (source == 0 && !b->stages->dd.done) || (source == 1 && !b->stages->pr.done) || source < 0 || source > 1) {
         set_last_error("bwams_reg2aln_run: run bwams_dedup_run (source 0) or bwams_pair_run (source 1) first");
         return BWAMS_ERR_ARG;
     }
@@ -51,7 +51,7 @@ static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t so
         set_last_error("bwams_reg2aln_run: the index was opened without its .0123 reference");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
     outdated(s, From::al);
@@ -114,13 +114,13 @@ int bwams_reg2aln_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t sour
 
 int bwams_reg2aln_run_sam(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_sam_opt_t *sopt, const bwams_pestat_t *pes,
                           int64_t *n_aln, int64_t *n_needed, int64_t *n_cigar_ops, int64_t *md_bytes) {
-    if (!b || !sopt || !b->chain || !b->chain->pr.done || b->chain->pr.single == (pes != nullptr)) {
+    if (!b || !sopt || !b->stages || !b->stages->pr.done || b->stages->pr.single == (pes != nullptr)) {
         set_last_error("bwams_reg2aln_run_sam: run bwams_pair_run first (BWAMS_PAIR_SINGLE_END and pes = NULL, or the paired-end form and its pes)");
         return BWAMS_ERR_ARG;
     }
     int rc = check_opt(opt, "bwams_reg2aln_run_sam");
     if (rc) return rc;
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
     const int64_t n = s->pr.total;
@@ -145,11 +145,11 @@ int bwams_reg2aln_run_sam(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bw
 }
 
 int bwams_reg2aln_fetch(bwams_batch_t *b, bwams_aln_t *aln, int64_t aln_cap, uint32_t *cigar, int64_t cigar_cap, char *md, int64_t md_cap) {
-    if (!b || !b->chain || !b->chain->al.done) {
+    if (!b || !b->stages || !b->stages->al.done) {
         set_last_error("bwams_reg2aln_fetch: run bwams_reg2aln_run first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (s->al.n > aln_cap || s->al.ncig > cigar_cap || s->al.nmd > md_cap) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -253,12 +253,12 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
 static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_sam_opt_t *sopt, const bwams_pestat_t *pes,
                         int64_t *sam_bytes, bwams_emf_t *emf = nullptr) {
     const bool pe = pes != nullptr;
-    if (!b || !sopt || !b->chain || !b->chain->al.done || b->chain->al.source != 1 || b->chain->pr.single == pe) {
+    if (!b || !sopt || !b->stages || !b->stages->al.done || b->stages->al.source != 1 || b->stages->pr.single == pe) {
         set_last_error(pe ? "bwams_sam_run_pe: run bwams_pair_run (paired-end) and bwams_reg2aln_run(source 1) first"
                           : "bwams_sam_run: run bwams_pair_run(BWAMS_PAIR_SINGLE_END) and bwams_reg2aln_run(source 1) first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if (pe && (s->ch.nseq & 1)) return BWAMS_ERR_ARG;
     if (!s->sm.up || s->sm.nseq != s->ch.nseq) {
         set_last_error("bwams_sam_run: run bwams_sam_upload for this chunk first");
@@ -364,11 +364,11 @@ int bwams_sam_run_pe(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_s
 }
 
 int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off, int32_t *mapq, int64_t mapq_cap) {
-    if (!b || !b->chain || !b->chain->sm.done) {
+    if (!b || !b->stages || !b->stages->sm.done) {
         set_last_error("bwams_sam_fetch: run bwams_sam_run first");
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     if ((sam && s->sm.bytes > cap) || (mapq && s->sm.nregs > mapq_cap)) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
@@ -381,7 +381,7 @@ int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off,
 }
 
 int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out) {
-    if (!b || !d || !b->chain || !b->chain->sm.done) {
+    if (!b || !d || !b->stages || !b->stages->sm.done) {
         set_last_error("bwams_sam_fetch_bgzf: run bwams_sam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -390,7 +390,7 @@ int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64
                        std::to_string(b->idx->device));
         return BWAMS_ERR_ARG;
     }
-    StageState *s = b->chain;
+    StageState *s = b->stages;
     return deflater_run_after(d, b->stream, s->sm.out.p, s->sm.bytes, 1, out, cap, 0, flags, n_out, nullptr);
 }
 }  // extern "C"

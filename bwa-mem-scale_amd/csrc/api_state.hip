@@ -1,6 +1,6 @@
 // api_state.hip — the stage state of a batch (stage_state.h) and what the entry-point files share: the per-device auxiliary
-// stream set, state creation (get_state) and release (chain_state_free), the invalidation function (outdated), check_opt, dev_bns,
-// sw_params, scan_rows with widen2_kernel behind launch_widen2, and chain_state_stats for bwams_batch_stats.
+// stream set, state creation (get_state) and release (stage_state_free), the invalidation function (outdated), check_opt, dev_bns,
+// sw_params, scan_rows with widen2_kernel behind launch_widen2, and stage_state_stats for bwams_batch_stats.
 #include <cstring>
 #include <map>
 
@@ -38,7 +38,7 @@ static void aux_release(int device) {
     }
 }
 
-void chain_state_free(StageState *s) {
+void stage_state_free(StageState *s) {
     if (!s) return;
     if (s->ev_ok) {
         for (auto &e : s->ev) (void)hipEventDestroy(e);
@@ -87,16 +87,16 @@ void outdated(StageState *s, From first) {
 }
 
 int get_state(bwams_batch *b, StageState **out) {
-    if (!b->chain) {
-        b->chain = new StageState();
-        for (auto &e : b->chain->ev) BWAMS_HIP(hipEventCreate(&e));
-        for (auto &e : b->chain->join) BWAMS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        BWAMS_HIP(hipEventCreateWithFlags(&b->chain->fork, hipEventDisableTiming));
-        b->chain->ev_ok = true;
-        if (int rc = aux_acquire(b->idx->device, b->chain->aux)) return rc;
-        b->chain->aux_device = b->idx->device;
+    if (!b->stages) {
+        b->stages = new StageState();
+        for (auto &e : b->stages->ev) BWAMS_HIP(hipEventCreate(&e));
+        for (auto &e : b->stages->join) BWAMS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        BWAMS_HIP(hipEventCreateWithFlags(&b->stages->fork, hipEventDisableTiming));
+        b->stages->ev_ok = true;
+        if (int rc = aux_acquire(b->idx->device, b->stages->aux)) return rc;
+        b->stages->aux_device = b->idx->device;
     }
-    *out = b->chain;
+    *out = b->stages;
     return BWAMS_OK;
 }
 
@@ -127,7 +127,7 @@ int dev_bns(bwams_index *ix, DevBns *out) {
     return BWAMS_OK;
 }
 
-void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm) {
+template <class Opt> static void sw_fill(const Opt &o, int end_bonus, SwParams *prm) {
     prm->o_del = o.o_del; prm->e_del = o.e_del; prm->o_ins = o.o_ins; prm->e_ins = o.e_ins;
     prm->zdrop = o.zdrop; prm->end_bonus = end_bonus;
     int mx = 0;
@@ -137,8 +137,10 @@ void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm) {
     }
     prm->max_sc = mx;
 }
+void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm) { sw_fill(o, end_bonus, prm); }
+void sw_params(const bwams_sw_opt_t &o, SwParams *prm) { sw_fill(o, o.end_bonus, prm); }
 
-void chain_state_stats(const StageState *s, bwams_stats_t *out) {
+void stage_state_stats(const StageState *s, bwams_stats_t *out) {
     if (!s) return;
     out->n_chains = s->ch.n_chains; out->n_chain_seeds = s->ch.n_seeds; out->n_chain_redo = s->ch.n_redo;
     out->n_left = s->ext.n_left; out->n_right = s->ext.n_right;

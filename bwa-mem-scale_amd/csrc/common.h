@@ -180,7 +180,7 @@ struct DevCounters {
 };
 
 struct StageState;                       // a batch's state behind seeding, stage by stage (stage_state.h)
-void chain_state_free(StageState *s);
+void stage_state_free(StageState *s);
 
 // bam.hip: a batch's SAM text as BAM records.  Record r is the line that ends at line_end[r]; the counting pass writes size[r]
 // (block_size + 4) and, for a line BAM cannot hold, bad[0] = min(read << 8 | reason); the writing pass fills out from rec_off
@@ -363,74 +363,96 @@ int emf_build_device(bwams_emf *e, const uint8_t *ref, int64_t l_pac, int seed_l
 
 struct bwams_batch {
     template <class T = void> using DevBuf = bwams::DevBuf<T>;
+    // what every stage reads
     bwams_index *idx = nullptr;
     hipStream_t stream = nullptr;
-    hipStream_t seed_aux = nullptr;      // SMEM round 3 runs beside round 2
-    hipEvent_t seed_fork = nullptr, seed_join = nullptr;
+    int cu_count = 0;
     int64_t max_reads = 0, max_bases = 0, max_smem = 0, max_sa = 0;
     int64_t pool_cap = 0;                // max_smem + chunk slack
-    int cu_count = 0;
-
-    // reads
-    DevBuf<uint8_t> d_enc;
+    DevBuf<uint8_t> d_enc;               // the resident reads
     DevBuf<int64_t> d_cum;
     DevBuf<uint8_t> d_skip;
     bool has_skip = false;
     int64_t nseq = 0, nbases = 0;
     int max_read_len = 0;
-    DevBuf<uint32_t> d_packed;           // packed reads (2-bit codes + N mask)
-    int read_w = 0, read_cw = 0;
-
-    // seeding buffers
-    DevBuf<bwams_smem_t> d_pool;         // unsorted SMEM pool (append order)
-    DevBuf<bwams_smem_t> d_sorted;       // (rid, m, n) order
-    DevBuf<uint64_t> d_keys, d_keys2;
-    DevBuf<uint32_t> d_vals, d_vals2;
-    DevBuf<bwams::Round2Work> d_work2;
-    DevBuf<int64_t> d_sa_off;            // max_smem + 1
-    DevBuf<int64_t> d_sa_cnt;            // max_smem + 1
-    DevBuf<int64_t> d_sa_coord;
-    DevBuf<> d_tmp;                      // rocPRIM temporary storage
     DevBuf<bwams::DevCounters> d_ctr;
     bwams::HostBuf<bwams::DevCounters> h_ctr;   // pinned host mirror
-    // per-lane scratch of the SMEM search (previous-interval lists)
-    DevBuf<uint4> d_prev;
-    DevBuf<bwams::BwdItem> d_bwd_items;  // SMEM search: backward phases with long interval lists (wave-per-pivot kernel)
-    DevBuf<uint4> d_bwd_ent;
-    int64_t bwd_items_cap = 0, bwd_ent_cap = 0;
-    int64_t prev_threads = 0;
-    int prev_cap = 0;
-
-    int64_t n_smem = 0, n_sa = 0;
-    int64_t n_pool_slots = 0;            // SMEM pool slots the last seeding pass handed out (holes included)
-    bool seed_done = false, with_sa = false;
-    bwams_ert *seed_ert = nullptr;       // the last seed run went over this ERT (nullptr: FM-index)
-    DevBuf<uint8_t> d_ert_prof;          // ERT seeding: match-length planes, (M + 1) x nbases bytes
-    DevBuf<uint64_t> d_ert_stk;          // ERT seeding: stacks of the leaf walks (ert_walk_threads x frames words)
-    int ert_stk_frames = 0;
-    DevBuf<uint32_t> d_ert_redo;         // ERT seeding: seeds whose hits the rank descent could not list (bit per seed)
-    bwams_seed_opt_t last_seed_opt{};    // of the last bwams_seed_run (a grown SA buffer re-runs the lookup)
-
-    // extension buffers
-    DevBuf<bwams_seqpair_t> d_pairs;
-    DevBuf<uint8_t> d_ref, d_qer;
-    int64_t n_pairs = 0;
-    int max_qlen = 0, max_tlen = 0;
-    DevBuf<uint32_t> d_emf_out;
-    DevBuf<uint8_t> d_emf_code;
-    DevBuf<> d_ksw_out;
-    DevBuf<int32_t> d_bsw_list;          // task lists of the banded-SW length classes (launch_bsw)
-
-    bwams::StageState *chain = nullptr;
-
-    hipEvent_t ev[16] = {};
-    hipEvent_t ev_emf[2] = {};
-    unsigned long long emf_nodes = 0, emf_cmp_bytes = 0;
+    DevBuf<> d_tmp;                      // rocPRIM temporary storage
     bwams_stats_t stats{};
+
+    struct Seed {                        // seeding over the FM-index or the ERT (api_seed.hip); chaining reads the sorted SMEMs and the SA buffers
+        DevBuf<bwams_smem_t> d_pool;     // unsorted SMEM pool (append order)
+        DevBuf<bwams_smem_t> d_sorted;   // (rid, m, n) order
+        DevBuf<uint64_t> d_keys, d_keys2;
+        DevBuf<uint32_t> d_vals, d_vals2;
+        DevBuf<bwams::Round2Work> d_work2;
+        DevBuf<int64_t> d_sa_off, d_sa_cnt;   // max_smem + 1 each
+        DevBuf<int64_t> d_sa_coord;      // max_sa
+        DevBuf<uint32_t> d_packed;       // packed reads (2-bit codes + N mask)
+        int read_w = 0, read_cw = 0;
+        DevBuf<uint4> d_prev;            // per-lane scratch of the SMEM search (previous-interval lists)
+        int64_t prev_threads = 0;
+        int prev_cap = 0;
+        DevBuf<bwams::BwdItem> d_bwd_items;   // SMEM search: backward phases with long interval lists (wave-per-pivot kernel)
+        DevBuf<uint4> d_bwd_ent;
+        int64_t bwd_items_cap = 0, bwd_ent_cap = 0;
+        DevBuf<uint8_t> d_ert_prof;      // ERT seeding: match-length planes, (M + 1) x nbases bytes
+        DevBuf<uint64_t> d_ert_stk;      // ERT seeding: stacks of the leaf walks (ert_walk_threads x frames words)
+        int ert_stk_frames = 0;
+        DevBuf<uint32_t> d_ert_redo;     // ERT seeding: seeds whose hits the rank descent could not list (bit per seed)
+        hipStream_t seed_aux = nullptr;  // SMEM round 3 runs beside round 2
+        hipEvent_t seed_fork = nullptr, seed_join = nullptr;
+        int64_t n_smem = 0, n_sa = 0;
+        int64_t n_pool_slots = 0;        // SMEM pool slots the last seeding pass handed out (holes included)
+        bool done = false, with_sa = false;
+        bwams_ert *ert = nullptr;        // the last seed run went over this ERT (nullptr: FM-index)
+        bwams_seed_opt_t last_opt{};     // of the last seed run (a grown SA buffer re-runs the lookup)
+    } sd;
+    struct Sw {                          // banded SW and ksw on uploaded pairs (api_sw.hip); the extension stage borrows d_bsw_list
+        DevBuf<bwams_seqpair_t> d_pairs;
+        DevBuf<uint8_t> d_ref, d_qer;
+        DevBuf<int32_t> d_bsw_list;      // task lists of the banded-SW length classes (launch_bsw)
+        DevBuf<> d_ksw_out;              // bwams_kswr_t per pair (launch_ksw's output)
+        int64_t n_pairs = 0;
+        int max_qlen = 0, max_tlen = 0;
+    } sw;
+    struct Emf {                         // the EMF probe's results (api_emf.hip); mem_perfect2reg reads them
+        DevBuf<uint32_t> d_emf_out;      // a word pair per read
+        DevBuf<uint8_t> d_emf_code;
+        hipEvent_t ev[2] = {};           // around the probe of bwams_emf_run
+        unsigned long long emf_nodes = 0, emf_cmp_bytes = 0;
+    } emf;
+    bwams::StageState *stages = nullptr; // everything behind seeding, created at its first use (get_state)
+
+    enum Ev {                            // the timing events: of a seeding pass (FM-index | ERT), of the two SW entry points
+        kEvSeedStart = 0, kEvRoundsDone = 3, kEvSorted = 4, kEvSeedEnd = 5,   // 3-4 the sort, 4-5 the lookup | locate + hits
+        kEvR1Start = 8, kEvR1End = 9,    // round-1 kernel | match profiles
+        kEvR2Start = 10, kEvR2End = 11,  // round-2 kernel | the three rounds
+        kEvR3Start = 12, kEvR3End = 13,  // round-3 kernel | locate
+        kEvBswStart = 6, kEvBswEnd = 7, kEvKswStart = 14, kEvKswEnd = 15, kEvCount = 16
+    };
+    hipEvent_t ev[kEvCount] = {};
 };
 
 namespace bwams {
+int check_device(int device);                  // api.hip: the ordinal names a gfx950 device
 int tmp_reserve(bwams_batch *b, size_t &tb);   // grows b->d_tmp to tb bytes (the stream drained first) and sets tb to its size (api.hip)
+int alloc_smem_buffers(bwams_batch *b, int64_t max_smem);   // api_seed.hip: (re)allocates every buffer sized by max_smem
+int alloc_seed_tmp(bwams_batch *b);            // api_seed.hip: d_tmp for the largest sort / scan the batch can issue
+// api.hip: `bytes` of device memory to / from a file through the caller's staging buffer of `chunk` bytes
+int dev_to_file(FILE *f, const void *dev, size_t bytes, uint8_t *stage, size_t chunk);
+int file_to_dev(FILE *f, void *dev, size_t bytes, uint8_t *stage, size_t chunk);
+// A file mapped read-only while the object lives (api.hip).  p stays null when the file cannot be opened (!opened), is shorter than
+// min_size or cannot be mapped.
+struct MappedFile {
+    const uint8_t *p = nullptr;
+    size_t size = 0;
+    bool opened = false;
+    explicit MappedFile(const std::string &path, size_t min_size = 1);
+    ~MappedFile();
+    MappedFile(const MappedFile &) = delete;
+    MappedFile &operator=(const MappedFile &) = delete;
+};
 // A rocPRIM call with the batch's temporary storage: call(nullptr, bytes) asks for the size, call(storage, bytes) runs.  who names
 // the entry point and the call in the error text.
 template <class F> int with_tmp(bwams_batch *b, const char *who, F &&call) {    // call(void *tmp, size_t &bytes) -> hipError_t

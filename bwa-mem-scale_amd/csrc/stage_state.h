@@ -1,4 +1,4 @@
-// stage_state.h — a batch's state behind seeding (bwams_batch::chain), one member per stage, and the host helpers the
+// stage_state.h — a batch's state behind seeding (bwams_batch::stages), one member per stage, and the host helpers the
 // entry-point files share (defined in api_state.hip).  A DevBuf<T> is read as T everywhere; a DevBuf<> holds several
 // rows or types and names its layout.
 #pragma once
@@ -107,12 +107,13 @@ struct StageState {
 enum class From { chain, built, dedup, pair, al, er, sam_upload, sam, bam };
 void outdated(StageState *s, From first);
 
-int get_state(bwams_batch *b, StageState **out);                  // creates b->chain at the first call
+int get_state(bwams_batch *b, StageState **out);                  // creates b->stages at the first call
 int check_opt(const bwams_mem_opt_t *o, const char *who);
 int dev_bns(bwams_index *ix, DevBns *out);                         // materialises the one-sequence default
 void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm);
+void sw_params(const bwams_sw_opt_t &o, SwParams *prm);
 void launch_widen2(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide, hipStream_t st);   // rows a | b of n + 1 as int64, the last of each 0
 int scan_rows(bwams_batch *b, const int64_t *in, int64_t *out, int rows, int64_t n1);               // exclusive scan of each row of n1
-void chain_state_stats(const StageState *s, bwams_stats_t *out);   // timing and counts for bwams_batch_stats (api.hip)
+void stage_state_stats(const StageState *s, bwams_stats_t *out);   // timing and counts for bwams_batch_stats (api.hip)
 
 }  // namespace bwams
