@@ -30,7 +30,7 @@ SYMBOLS = [
     "bwams_process_chunk", "bwams_process_chunk_smart", "bwams_process_chunk2", "bwams_emf_regs_merge", "bwams_fastq_decode", "bwams_fastq_info", "bwams_fastq_has_qual", "bwams_fastq_fetch", "bwams_fastq_to_batch", "bwams_fastq_to_batch_opt", "bwams_fastq_close", "bwams_batch_create", "bwams_batch_destroy", "bwams_seed_fmi",
     "bwams_seed_upload", "bwams_seed_run", "bwams_seed_counts", "bwams_seed_fetch",
     "bwams_ert_from_host", "bwams_ert_open", "bwams_ert_close", "bwams_ert_bytes", "bwams_ert_set_fat", "bwams_seed_run_ert",
-    "bwams_ert_build", "bwams_ert_info", "bwams_ert_fetch", "bwams_ert_save", "bwams_debug_sort",
+    "bwams_ert_build", "bwams_ert_info", "bwams_ert_fetch", "bwams_ert_save", "bwams_debug_sort", "bwams_debug_regs_upload", "bwams_debug_aln_lists",
     "bwams_emf_build", "bwams_emf_info", "bwams_emf_table_fetch", "bwams_emf_save",
     "bwams_bsw_extend", "bwams_bsw_upload", "bwams_bsw_run", "bwams_bsw_fetch",
     "bwams_batch_stats", "bwams_batch_sync", "bwams_ksw_align",
@@ -579,6 +579,8 @@ def lib():
         L.bwams_bam_markdup.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
+        L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]
+        L.bwams_debug_aln_lists.argtypes = [vp, vp]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
         L.bwams_index_set_fma.argtypes = [vp, vp, C.c_int, vp, C.c_int]
         L.bwams_index_fetch_fma.argtypes = [vp, vp, vp]
@@ -1145,6 +1147,19 @@ class Batch:
         md = np.zeros(max(nm.value, 1), np.uint8)
         _chk(lib().bwams_reg2aln_fetch(self.h, _p(aln), len(aln), _p(cig), len(cig), _p(md), len(md)), "bwams_reg2aln_fetch")
         return aln[:n.value], cig[:nc.value], md[:nm.value]
+
+    def debug_regs_upload(self, regs, reg_off):
+        """Test hook: regs (ALNREG_DTYPE, grouped by read through reg_off) become the final regions reg2aln(opt, 0) runs on."""
+        regs = np.ascontiguousarray(regs, ALNREG_DTYPE)
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        _chk(lib().bwams_debug_regs_upload(self.h, _p(regs), len(regs), _p(reg_off), len(reg_off) - 1), "bwams_debug_regs_upload")
+        self._n_final = len(regs)
+
+    def debug_aln_lists(self):
+        """Test hook: regions per launch of the last reg2aln (ring, wave 1, wave 2 with the requeued ones, row in global memory)."""
+        cnt = np.zeros(4, np.int64)
+        _chk(lib().bwams_debug_aln_lists(self.h, _p(cnt)), "bwams_debug_aln_lists")
+        return cnt
 
     def sam_upload(self, names, quals=None, comments=None):
         """Names (list of bytes), qualities (uint8 array laid out like the reads, or None), comments (list of bytes / None, or

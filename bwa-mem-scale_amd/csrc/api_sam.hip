@@ -1,6 +1,6 @@
 // api_sam.hip — C-ABI entry points of the SAM side (include/bwams.h): bwams_reg2aln_* (mem_reg2aln, the host's mem_approx_mapq_se),
-// bwams_index_set_contig_names and _annos, bwams_sam_upload, _run, _run_emf, _run_pe, _fetch and _fetch_bgzf, over reg2aln.hip and
-// sam_text.hip.  No CPU fallback: every entry point runs HIP kernels or returns an error.
+// the test hooks bwams_debug_regs_upload and bwams_debug_aln_lists, bwams_index_set_contig_names and _annos, bwams_sam_upload, _run,
+// _run_emf, _run_pe, _fetch and _fetch_bgzf, over reg2aln.hip and sam_text.hip.  No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <cmath>
 #include <cstring>
 
@@ -164,6 +164,66 @@ int bwams_reg2aln_fetch(bwams_batch_t *b, bwams_aln_t *aln, int64_t aln_cap, uin
     BWAMS_HIP(hipStreamSynchronize(st));
     for (int64_t k = 0; k < s->al.n; ++k)
         if (aln[k].rid >= 0) aln[k].mapq = regs[(size_t)k].secondary < 0 ? approx_mapq_se(&s->opt, &regs[(size_t)k]) : 0;
+    return BWAMS_OK;
+}
+
+/* Test hook: caller-given regions take the place of the de-duplication stage's final regions (include/bwams.h).  Only what
+ * would make a kernel read outside the reads is refused; the reference side of a region is aln_plan_kernel's to judge. */
+int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
+    if (!b || n_regs < 0 || n_reads < 0 || !reg_off || (n_regs && !regs)) return BWAMS_ERR_ARG;
+    if (!b->d_cum.p || n_reads != b->nseq) {
+        set_last_error("bwams_debug_regs_upload: n_reads is not the number of reads of the last bwams_seed_upload");
+        return BWAMS_ERR_ARG;
+    }
+    if (reg_off[0] != 0 || reg_off[n_reads] != n_regs) {
+        set_last_error("bwams_debug_regs_upload: reg_off must run from 0 to n_regs");
+        return BWAMS_ERR_ARG;
+    }
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (reg_off[r + 1] < reg_off[r]) {
+            set_last_error("bwams_debug_regs_upload: reg_off decreases at read " + std::to_string(r));
+            return BWAMS_ERR_ARG;
+        }
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t st = b->stream;
+    std::vector<int64_t> cum((size_t)n_reads + 1);
+    BWAMS_HIP(hipMemcpyAsync(cum.data(), b->d_cum.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const int64_t len = cum[(size_t)r + 1] - cum[(size_t)r];
+        for (int64_t k = reg_off[r]; k < reg_off[r + 1]; ++k)
+            if (regs[k].qb < 0 || regs[k].qe > len || regs[k].qb > regs[k].qe) {
+                set_last_error("bwams_debug_regs_upload: region " + std::to_string(k) + " has a query span outside its read");
+                return BWAMS_ERR_ARG;
+            }
+    }
+    StageState *s;
+    int rc = get_state(b, &s);
+    if (rc) return rc;
+    outdated(s, From::dedup); outdated(s, From::al); outdated(s, From::er); outdated(s, From::sam);
+    BWAMS_HIP(s->dd.out.ensure_n((size_t)n_regs + 1)); BWAMS_HIP(s->dd.off.ensure_n((size_t)n_reads + 1));
+    if (n_regs) BWAMS_HIP(hipMemcpyAsync(s->dd.out.p, regs, (size_t)n_regs * sizeof(bwams_alnreg_t), hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(s->dd.off.p, reg_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    s->dd.n_final = n_regs; s->ch.nseq = n_reads; s->dd.done = true;
+    return BWAMS_OK;
+}
+
+/* Test hook: the lengths of the four region lists of the last bwams_reg2aln_run (include/bwams.h). */
+int bwams_debug_aln_lists(bwams_batch_t *b, int64_t counts[4]) {
+    if (!b || !counts || !b->stages || !b->stages->al.done) {
+        set_last_error("bwams_debug_aln_lists: run bwams_reg2aln_run first");
+        return BWAMS_ERR_ARG;
+    }
+    StageState *s = b->stages;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (s->al.n > 0) {                                     // a run over no regions launches nothing and leaves the counters alone
+        BWAMS_HIP(hipSetDevice(b->idx->device));
+        unsigned long long c[4];
+        BWAMS_HIP(hipMemcpyAsync(c, s->al.cnt.p, sizeof c, hipMemcpyDeviceToHost, b->stream));
+        BWAMS_HIP(hipStreamSynchronize(b->stream));
+        for (int i = 0; i < 4; ++i) counts[i] = (int64_t)c[i];
+    }
     return BWAMS_OK;
 }
 

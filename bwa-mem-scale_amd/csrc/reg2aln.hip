@@ -9,12 +9,18 @@
 // (sam_text.hip: sam_mapq_kernel) with equal results — both so that the last bit is the reference's.)
 //
 // Mapping.  Regions are independent.  Most need no dynamic programming at all (equal lengths and an inferred band of 0:
-// the reference's "no gap" shortcut) — aln_simple_kernel finishes those, one lane per region, and lists the rest.
-// aln_dp_kernel runs the banded global alignment for the listed regions, one lane per region, dense waves: the (h, e) row
-// of ksw_global2 only ever holds 2w + 2 live columns (the band slides by one column per row and eh[end] is rewritten
-// every row), so it lives in an LDS ring of the band's size class (32 / 128 columns per lane); wider bands fall back
-// to a row in HBM scratch.  The direction matrix z goes to HBM packed four cells to a word; the traceback reads it back.
-// CIGAR and MD are written to per-region scratch and compacted into the flat pools afterwards.
+// the reference's "no gap" shortcut) — aln_simple_kernel finishes those, one lane per region, and lists the rest by the band
+// of their first try.  The (h, e) row of ksw_global2 only ever holds 2w + 2 live columns (the band slides by one column per
+// row and eh[end] is rewritten every row).  Four launches follow, each over its own list:
+//   list 0  aln_dp_kernel<32>    bands up to 15: a lane per region, dense waves, the row in an LDS ring of 32 columns per lane;
+//                                a region whose retry outgrows the ring is appended to list 2 and redone there from the start
+//   list 1  aln_dp_wave_kernel   bands 16 to 63: a wave per region, the row whole in LDS (queries up to 511 bases)
+//   list 2  aln_dp_wave_kernel   bands of 64 and more, and the regions requeued from list 0
+//   list 3  aln_dp_kernel<0>     queries of 512 bases and more that came through list 1 or 2 (the wave kernel appends them):
+//                                a lane per region, the row in HBM scratch
+// The direction matrix z goes to HBM (four cells to a word from the lane kernels, a byte per cell from the wave kernel, the same
+// layout); the traceback reads it back.  CIGAR and MD are written to per-region scratch and compacted into the flat pools
+// afterwards.  bwams_debug_aln_lists returns the four lists' lengths; tests/test_gpu_aln_limits.py drives every path to its limits.
 #include "common.h"
 #include "chain_kernels.h"
 #include "wave_ops.h"
@@ -164,7 +170,8 @@ __global__ void aln_plan_kernel(RegAlnArgs A) {
     const bool skip = A.only && !A.only[k];            // not needed by the SAM text: the record stays an unmapped one
     const bool bad = skip || ar.rb < 0 || ar.re < 0 || lq <= 0 || lr64 <= 0 || (ar.rb < l_pac && ar.re > l_pac) || ar.re > 2 * l_pac || lr64 > (1 << 20);
     int64_t need = 64;
-    int cls = -1;                                     // -1: no DP; 0 / 1: LDS ring of 32 / 128 columns; 2: HBM row
+    int cls = -1;                                     // -1: no DP; the list of the first launch: 0 ring of 32 columns (aln_dp_kernel<32>),
+                                                      // 1 / 2 wave per region (aln_dp_wave_kernel, bands up to 63 / beyond)
     if (!bad) {
         const int lr = (int)lr64;
         need = (int64_t)(lq + lr + 4) * 4 + (int64_t)md_cap(lr);
@@ -180,7 +187,8 @@ __global__ void aln_plan_kernel(RegAlnArgs A) {
             wmax = wmax > d + 3 ? wmax : d + 3;
             const int64_t n_col = lq < 2 * wmax + 1 ? lq : 2 * wmax + 1;
             // the class follows the band of the FIRST try (bwa.cpp:414-423); a retry that outgrows the ring — rare: the
-            // global score fell short of the local one — sends the region to the HBM-row launch, which runs last
+            // global score fell short of the local one — sends the region to list 2, the second wave launch; from lists 1 and 2
+            // a query beyond the wave kernel's LDS row goes on to list 3, the HBM-row launch (aln_dp_kernel<0>), which runs last
             {
                 const int8_t m0 = A.opt.mat[0];
                 const int max_ins = (int)((double)(((lq + 1) >> 1) * m0 - A.opt.o_ins) / A.opt.e_ins + 1.);
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(64) void aln_dp_kernel(RegAlnArgs A, int cls) {
             last_sc = score;
             w2 <<= 1;
         } while (++it < 3 && score < ar.truesc - A.opt.a);
-        if (requeue) {                                   // redone from the start by the HBM-row launch
+        if (requeue) {                                   // redone from the start by the second wave launch (list 2)
             A.list[2 * A.n_regs + (int64_t)atomicAdd(&A.n_list[2], 1ull)] = (int32_t)k;
             continue;
         }

@@ -524,6 +524,22 @@ int bwams_ksw_align(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n,
 int bwams_debug_sort(bwams_index_t *idx, const int64_t *k, const int32_t *s, const int32_t *q, int32_t n, int32_t which,
                      int32_t mode, int32_t *order_out);
 
+/* Test hook (not part of the drop-in surface): caller-given regions take the place of the batch's final regions of the
+ * de-duplication stage.  Called after bwams_seed_upload of the reads; bwams_reg2aln_run(b, opt, 0, ...) and
+ * bwams_reg2aln_fetch then run on these regions as on real ones, and the results of later stages (pairing, alignment
+ * records, the EMF's regions, SAM text, BAM) count as outdated.  The chains and extension results of an earlier run stay as
+ * they are: they no longer belong to these regions, and the hook is not to be mixed with entry points that read them.  regs[reg_off[r] .. reg_off[r + 1]) belong to read r.  Returns BWAMS_ERR_ARG and
+ * launches nothing when n_reads is not the uploaded read count, when reg_off does not run non-decreasing from 0 to n_regs,
+ * or when a region has qb < 0, qe beyond its read or qb > qe (a kernel would read outside the reads).  The reference side
+ * (rb, re) and every other field go through untouched: what mem_reg2aln / bwa_gen_cigar2 reject becomes the unmapped record. */
+int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads);
+
+/* Test hook (not part of the drop-in surface): how many regions the last bwams_reg2aln_run gave to each of its four
+ * dynamic-programming launches.  counts[0]: lane per region with a 32-column ring in LDS; counts[1]: wave per region, bands
+ * of at most 63 on the first try; counts[2]: wave per region, wider bands and the regions whose retry outgrew the ring;
+ * counts[3]: lane per region with the row in global memory (queries of 512 bases and more that came through 1 or 2). */
+int bwams_debug_aln_lists(bwams_batch_t *b, int64_t counts[4]);
+
 /* ------------------------------------------------------------- counters ---- */
 
 /* Event counts of the last seed run on this batch (the same events the oracle

@@ -7,9 +7,12 @@
  *   mem_reg2aln                         /root/reference/src/bwamem.cpp:2533-2628 (orc_reg2aln)
  *
  * PINNING: ksw_global2 with its CIGAR is pinned against the reference's own ksw.cpp object (oracle/_ref/libref_sw_*.so,
- * tests/test_oracle_aln.py).  bwa_gen_cigar2 / mem_reg2aln live in bwa.cpp / bwamem.cpp (safestringlib: not buildable
- * here): PARITY UNPINNED, checked through properties (the CIGAR consumes exactly the query and reference spans, NM and MD
- * recomputed independently from the two sequences and the CIGAR).
+ * tests/test_oracle_aln.py), also at the shapes the device kernels are tested at (queries of 511, 512 and 1 500 bases, bands up
+ * to 703, gap runs of 31 to 64, tandem repeats).  bwa_gen_cigar2 / mem_reg2aln live in bwa.cpp / bwamem.cpp (safestringlib: not
+ * buildable here): PARITY UNPINNED.  They are checked through properties (the CIGAR consumes exactly the query and reference
+ * spans, NM and MD recomputed independently from the two sequences and the CIGAR) and, for the band inference, the retry loop,
+ * the squeeze and the clips, against a second restatement written from the reference's lines over the pinned ksw_global2
+ * (tests/aln_cases.py, test_reg2aln_retry_loop_against_pinned_alignment).
  *
  * The reference reads the reference bases from the 2-bit .pac through bns_get_seq; for coordinates on the reverse strand
  * (rb >= l_pac) that yields text[rb, re) of the fw || rc text, i.e. the .0123 array this restatement reads directly.
@@ -33,8 +36,11 @@ static int push_cigar(int n, uint32_t *cigar, int op, int len)
 }
 
 /* cigar must hold qlen + tlen + 2 entries */
-int orc_ksw_global2_cigar(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
-                          int e_del, int o_ins, int e_ins, int w, int *n_cigar_, uint32_t *cigar)
+/* flip: for the tests that ask which CIGARs hang on a tie, each bit turns one comparison of the direction byte the other way
+ * where its two sides are equal (1: M against E, 2: H against F, 4: extending a deletion against opening one, 8: the same for
+ * an insertion).  The scores do not change with it; 0 is ksw_global2. */
+static int global2_cigar(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
+                         int e_del, int o_ins, int e_ins, int w, int *n_cigar_, uint32_t *cigar, int flip)
 {
     const int m = 5, oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
     int i, j, k, score;
@@ -62,19 +68,19 @@ int orc_ksw_global2_cigar(int qlen, const uint8_t *query, int tlen, const uint8_
             uint8_t d;
             p->h = h1;
             mm += q[j];
-            d = mm >= e ? 0 : 1;
+            d = (flip & 1 ? mm > e : mm >= e) ? 0 : 1;
             h = mm >= e ? mm : e;
-            d = h >= f ? d : 2;
+            d = (flip & 2 ? h > f : h >= f) ? d : 2;
             h = h >= f ? h : f;
             h1 = h;
             t = mm - oe_del;
             e -= e_del;
-            d |= e > t ? 1 << 2 : 0;
+            d |= (flip & 4 ? e >= t : e > t) ? 1 << 2 : 0;
             e = e > t ? e : t;
             p->e = e;
             t = mm - oe_ins;
             f -= e_ins;
-            d |= f > t ? 2 << 4 : 0;
+            d |= (flip & 8 ? f >= t : f > t) ? 2 << 4 : 0;
             f = f > t ? f : t;
             zi[j - beg] = d;
         }
@@ -98,6 +104,18 @@ int orc_ksw_global2_cigar(int qlen, const uint8_t *query, int tlen, const uint8_
     }
     free(eh); free(qp); free(z);
     return score;
+}
+
+int orc_ksw_global2_cigar(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
+                          int e_del, int o_ins, int e_ins, int w, int *n_cigar_, uint32_t *cigar)
+{
+    return global2_cigar(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, w, n_cigar_, cigar, 0);
+}
+
+int orc_ksw_global2_cigar_flip(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
+                               int e_del, int o_ins, int e_ins, int w, int *n_cigar_, uint32_t *cigar, int flip)
+{
+    return global2_cigar(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, w, n_cigar_, cigar, flip);
 }
 
 static int put_num(char *s, int l, int x)          /* kputw */
@@ -232,13 +250,19 @@ static int pos2rid(const orc_bns_t *b, int64_t pos_f)      /* bns_pos2rid (bntse
 }
 
 /* mem_reg2aln for one region.  cigar: l_query + (re - rb) + 4 entries; md: 3 * (re - rb) + 16 bytes.  Returns 0 for the
- * unmapped record (ar with rb < 0 or re < 0), 1 otherwise. */
-int orc_reg2aln(const bwams_mem_opt_t *opt, const orc_bns_t *bns, const uint8_t *ref_string, int l_query, const uint8_t *query,
-                const bwams_alnreg_t *ar, bwams_aln_t *a, uint32_t *cigar, char *md)
+ * unmapped record, 1 otherwise.  The unmapped record is the reference's for ar with rb < 0 or re < 0.  A region that
+ * bwa_gen_cigar2 rejects (no query, no reference span, a span across the strands' junction or beyond the text) stops the
+ * reference at its assert(a.cigar != NULL), bwamem.cpp:2568: there is no answer to restate, and the library's answer, the
+ * unmapped record, is taken here too.  last_score / n_tries (either may be NULL): the global score of the last try and the
+ * number of tries of the loop at bwamem.cpp:2558-2567, for the tests of that loop. */
+int orc_reg2aln_tries(const bwams_mem_opt_t *opt, const orc_bns_t *bns, const uint8_t *ref_string, int l_query, const uint8_t *query,
+                      const bwams_alnreg_t *ar, bwams_aln_t *a, uint32_t *cigar, char *md, int *last_score, int *n_tries)
 {
-    int i, w2, tmp, qb, qe, NM = -1, score = 0, is_rev, last_sc = -(1 << 30), n_cigar = 0, l_MD = 0;
+    int i, w2, tmp, qb, qe, NM = -1, score = 0, is_rev, last_sc = -(1 << 30), n_cigar = 0, l_MD = 0, ok = 1;
     int64_t pos, rb, re;
     memset(a, 0, sizeof *a);
+    if (last_score) *last_score = 0;
+    if (n_tries) *n_tries = 0;
     if (ar == 0 || ar->rb < 0 || ar->re < 0) {
         a->rid = -1; a->pos = -1; a->flag |= 0x4;
         return 0;
@@ -253,11 +277,19 @@ int orc_reg2aln(const bwams_mem_opt_t *opt, const orc_bns_t *bns, const uint8_t 
     i = 0;
     do {
         w2 = w2 < opt->w << 2 ? w2 : opt->w << 2;
-        gen_cigar2(opt, w2, bns->l_pac, ref_string, qe - qb, query + qb, rb, re, &score, &n_cigar, cigar, &NM, md, &l_MD);
+        ok = gen_cigar2(opt, w2, bns->l_pac, ref_string, qe - qb, query + qb, rb, re, &score, &n_cigar, cigar, &NM, md, &l_MD);
+        if (n_tries) ++*n_tries;
+        if (!ok) break;
         if (score == last_sc || w2 == opt->w << 2) break;
         last_sc = score;
         w2 <<= 1;
     } while (++i < 3 && score < ar->truesc - opt->a);
+    if (!ok) {
+        memset(a, 0, sizeof *a);
+        a->rid = -1; a->pos = -1; a->flag |= 0x4;
+        return 0;
+    }
+    if (last_score) *last_score = score;
     a->NM = NM;
     {
         const int64_t p0 = rb < bns->l_pac ? rb : re - 1;
@@ -290,4 +322,10 @@ int orc_reg2aln(const bwams_mem_opt_t *opt, const orc_bns_t *bns, const uint8_t 
     a->score = ar->score; a->sub = ar->sub > ar->csub ? ar->sub : ar->csub;
     a->is_alt = ((uint32_t)ar->n_comp_is_alt >> 30) & 1; a->alt_sc = ar->alt_sc;      /* is_alt:2 of the region, :1 of the record */
     return 1;
+}
+
+int orc_reg2aln(const bwams_mem_opt_t *opt, const orc_bns_t *bns, const uint8_t *ref_string, int l_query, const uint8_t *query,
+                const bwams_alnreg_t *ar, bwams_aln_t *a, uint32_t *cigar, char *md)
+{
+    return orc_reg2aln_tries(opt, bns, ref_string, l_query, query, ar, a, cigar, md, 0, 0);
 }

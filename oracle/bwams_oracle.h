@@ -162,9 +162,13 @@ typedef struct orc_bns {            /* the fields of bntseq_t the path reads */
 /* SAM-side alignment (aln_oracle.c): ksw_global2 with traceback (pinned), mem_approx_mapq_se, mem_reg2aln (unpinned) */
 int orc_ksw_global2_cigar(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
                           int e_del, int o_ins, int e_ins, int w, int *n_cigar, uint32_t *cigar);
+int orc_ksw_global2_cigar_flip(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
+                               int e_del, int o_ins, int e_ins, int w, int *n_cigar, uint32_t *cigar, int flip);   /* ties turned: tests only */
 int orc_approx_mapq_se(const bwams_mem_opt_t *opt, const bwams_alnreg_t *a);
 int orc_reg2aln(const bwams_mem_opt_t *opt, const struct orc_bns *bns, const uint8_t *ref_string, int l_query, const uint8_t *query,
                 const bwams_alnreg_t *ar, bwams_aln_t *a, uint32_t *cigar, char *md);
+int orc_reg2aln_tries(const bwams_mem_opt_t *opt, const struct orc_bns *bns, const uint8_t *ref_string, int l_query, const uint8_t *query,
+                      const bwams_alnreg_t *ar, bwams_aln_t *a, uint32_t *cigar, char *md, int *last_score, int *n_tries);
 /* single-end SAM text (sam_oracle.c): mem_reg2sam + mem_gen_alt + mem_aln2sam for one read (PARITY UNPINNED).  ctg_names:
  * NUL-terminated names back to back, ctg_off[rid] = start of a name.  Returns the text length, or -1 - length if cap was short. */
 void orc_set_contig_annos(const char *annos, const int32_t *anno_off);      /* MEM_F_REF_HDR: bntann1_t.anno table, NULL = none */

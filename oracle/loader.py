@@ -661,18 +661,20 @@ ALN_DTYPE = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("flag", "<i4"), ("is_rev"
 assert ALN_DTYPE.itemsize == 72
 
 
-def ksw_global2_cigar(query, target, w: int, opt: SwOpt | None = None, L=None):
-    """(score, cigar uint32[]) of ksw_global2 with traceback; L = a reference library from ref_lib() to run the real one."""
+def ksw_global2_cigar(query, target, w: int, opt: SwOpt | None = None, L=None, flip: int = 0):
+    """(score, cigar uint32[]) of ksw_global2 with traceback; L = a reference library from ref_lib() to run the real one.
+    flip (the restatement only): bits that turn a comparison of the direction byte the other way where its sides are equal
+    (1 M | E, 2 H | F, 4 deletion extended | opened, 8 insertion extended | opened), to find the CIGARs that hang on a tie."""
     opt = opt or default_sw_opt()
     q = np.ascontiguousarray(query, np.uint8)
     t = np.ascontiguousarray(target, np.uint8)
     cig = np.zeros(len(q) + len(t) + 4, np.uint32)
     n = C.c_int(0)
     if L is None:
-        f = lib().orc_ksw_global2_cigar
+        f = lib().orc_ksw_global2_cigar_flip
         f.restype = C.c_int
         sc = f(len(q), _p(q), len(t), _p(t), C.byref(opt, SwOpt.mat.offset), opt.o_del, opt.e_del, opt.o_ins, opt.e_ins, w,
-               C.byref(n), _p(cig))
+               C.byref(n), _p(cig), flip)
     else:
         L.ref_ksw_global2_cigar.restype = C.c_int
         L.ref_ksw_global2_cigar.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
@@ -680,8 +682,9 @@ def ksw_global2_cigar(query, target, w: int, opt: SwOpt | None = None, L=None):
     return sc, cig[:n.value].copy()
 
 
-def reg2aln(regs, reg_off, enc, cum, ref_string, l_pac, contigs=None, opt: MemOpt | None = None):
-    """mem_reg2aln over every region (regions grouped by read): (aln records, cigar pool, md pool as bytes)."""
+def reg2aln(regs, reg_off, enc, cum, ref_string, l_pac, contigs=None, opt: MemOpt | None = None, tries=None):
+    """mem_reg2aln over every region (regions grouped by read): (aln records, cigar pool, md pool as bytes).
+    tries: an int32 array of (n regions, 2) that receives the global score of the last try and the number of tries."""
     opt = opt or default_mem_opt()
     bns, keep = _bns(l_pac, contigs if contigs is not None else single_contig(l_pac))
     regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
@@ -690,8 +693,9 @@ def reg2aln(regs, reg_off, enc, cum, ref_string, l_pac, contigs=None, opt: MemOp
     out = np.zeros(len(regs), ALN_DTYPE)
     cigs, mds = [], []
     co = mo = 0
-    f = lib().orc_reg2aln
+    f = lib().orc_reg2aln_tries
     f.restype = C.c_int
+    sc, nt = C.c_int(0), C.c_int(0)
     for r in range(len(reg_off) - 1):
         q = enc[cum[r]:cum[r + 1]]
         for k in range(int(reg_off[r]), int(reg_off[r + 1])):
@@ -699,7 +703,9 @@ def reg2aln(regs, reg_off, enc, cum, ref_string, l_pac, contigs=None, opt: MemOp
             span = max(int(ar["re"][0] - ar["rb"][0]), 0)
             cig = np.zeros(len(q) + span + 8, np.uint32)
             md = np.zeros(3 * span + 32, np.uint8)
-            f(C.byref(opt), C.byref(bns), _p(ref_string), len(q), _p(q), _p(ar), _p(out[k:k + 1]), _p(cig), _p(md))
+            f(C.byref(opt), C.byref(bns), _p(ref_string), len(q), _p(q), _p(ar), _p(out[k:k + 1]), _p(cig), _p(md), C.byref(sc), C.byref(nt))
+            if tries is not None:
+                tries[k] = sc.value, nt.value
             out[k]["cigar_off"], out[k]["md_off"] = co, mo
             cigs.append(cig[:out[k]["n_cigar"]]); mds.append(md[:out[k]["md_len"]])
             co += int(out[k]["n_cigar"]); mo += int(out[k]["md_len"])
