@@ -820,7 +820,8 @@ class Index:
         _chk(lib().bwams_index_set_contig_annos(self.h, bytes(blob), _p(off)), "bwams_index_set_contig_annos")
 
     def debug_sort(self, k, s, q, which: int, mode: int = 0):
-        """order of the wave tier's region sort (test hook)"""
+        """order of a device sort (test hook).  which 0, 1: the region sorts of the de-duplication's wave tier (keys k, s, q);
+        2: the chain filter's (k = weight in [0, 2^30), descending; s and q ignored).  mode: see bwams.h"""
         k = np.ascontiguousarray(k, np.int64); s = np.ascontiguousarray(s, np.int32); q = np.ascontiguousarray(q, np.int32)
         out = np.zeros(len(k), np.int32)
         _chk(lib().bwams_debug_sort(self.h, _p(k), _p(s), _p(q), len(k), which, mode, _p(out)), "bwams_debug_sort")

@@ -482,14 +482,17 @@ int bwams_pestat_from_keys(const uint64_t *keys_in, int64_t n, bwams_pestat_t pe
     return BWAMS_OK;
 }
 
-/* Test hook: the region sorts of the de-duplication's wave tier on caller-given keys (order_out[i] = index of the i-th
- * record after the sort).  which: 0 = mem_ars2 (key k), 1 = mem_ars (s descending, k, q).  mode: 0 = as the kernels run
- * it, 1 = the operation-exact wave-parallel introsort even without ties, 2 = the sequential introsort on lane 0. */
+/* Test hook: the device sorts on caller-given keys (order_out[i] = index of the i-th record after the sort).  which:
+ * 0 = mem_ars2 (key k), 1 = mem_ars (s descending, k, q), 2 = the chain filter's (k = weight in [0, 2^30), descending).
+ * mode: see bwams.h. */
 int bwams_debug_sort(bwams_index_t *ix, const int64_t *k, const int32_t *s, const int32_t *q, int32_t n, int32_t which,
                      int32_t mode, int32_t *order_out) {
     if (!ix || n < 0 || (n && (!k || !s || !q || !order_out))) return BWAMS_ERR_ARG;
+    if (which == 2)
+        for (int32_t i = 0; i < n; ++i)
+            if (k[i] < 0 || k[i] >= (1 << 30)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(ix->device));
-    if (launch_sort_test(k, s, q, n, which, mode, order_out)) {
+    if (which == 2 ? launch_flt_sort_test(k, n, mode, order_out) : launch_sort_test(k, s, q, n, which, mode, order_out)) {
         set_last_error("bwams_debug_sort: n must be at most 1024");
         return BWAMS_ERR_ARG;
     }

@@ -15,8 +15,8 @@
 //                       in lockstep by 64 lanes (uniform loads = one request; lane 0 stores), the
 //                       chain records and an ordered array of chain positions in LDS; a read in
 //                       which a chain position repeats goes to chain_redo_kernel (B-tree, HBM).
-//   chain_heavy_kernel  one wave per read with many chains: the sort runs on lane 0 over an LDS
-//                       copy, the quadratic pairwise filter runs 64 kept chains at a time.
+//   chain_heavy_kernel  one wave per read with many chains: the sort runs on the whole wave over an
+//                       LDS copy, the quadratic pairwise filter runs 64 candidates at a time.
 // All state lives in HBM scratch indexed by the read's slice of the SA-coordinate array: a seed
 // IS an SA hit, so every per-seed array shares the index space of sa_coord, and a chain is named
 // by its first seed.  The latency of dependent loads is what a lane pays for, so the hot records
@@ -35,6 +35,7 @@
 #include "common.h"
 #include "chain_kernels.h"
 #include "wave_ops.h"
+#include "ksort.h"
 
 namespace bwams {
 namespace {
@@ -299,201 +300,69 @@ __device__ __forceinline__ int32_t kbt_traverse(const ReadCtx &c, int32_t *out) 
     return n;
 }
 
-// ---- ksort.h introsort over {w, id} pairs, descending w --------------------------------------
-__device__ __forceinline__ bool flt_lt(uint2 a, uint2 b) { return a.x > b.x; }
-__device__ __forceinline__ void swp(uint2 *a, int i, int j) { const uint2 t = a[i]; a[i] = a[j]; a[j] = t; }
+// ---- the chain filter's sort: ksort.h's introsort (csrc/ksort.h) over {w, id} pairs, descending w ---------------------
+// The sequential form, ks_introsort(fl, n, FltLt()), runs on HBM arrays only; reads with many chains are sorted by a whole
+// wavefront over an LDS copy (wave_flt_sort).  Equal weights are common and the sort is not stable: both forms are the
+// reference's sequence of operations.
+struct FltLt { __device__ __forceinline__ bool operator()(const uint2 &a, const uint2 &b) const { return a.x > b.x; } };
 
-__device__ __forceinline__ void flt_insertsort(uint2 *a, int s, int t) {
-    for (int i = s + 1; i < t; ++i)
-        for (int j = i; j > s && flt_lt(a[j], a[j - 1]); --j) swp(a, j, j - 1);
-}
-__device__ __forceinline__ void flt_combsort(uint2 *a, int n) {
-    const double shrink = 1.2473309501039786540366528676643;
-    bool do_swap;
-    unsigned long long gap = (unsigned long long)n;
-    do {
-        if (gap > 2) {
-            gap = (unsigned long long)((double)gap / shrink);
-            if (gap == 9 || gap == 10) gap = 11;
-        }
-        do_swap = false;
-        for (long long i = 0; i < (long long)n - (long long)gap; ++i) {
-            const long long j = i + (long long)gap;
-            if (flt_lt(a[j], a[i])) { swp(a, (int)i, (int)j); do_swap = true; }
-        }
-    } while (do_swap || gap > 2);
-    if (gap != 1) flt_insertsort(a, 0, n);
-}
-__device__ __forceinline__ void flt_introsort(uint2 *a, int n) {
-    if (n < 1) return;
-    if (n == 2) { if (flt_lt(a[1], a[0])) swp(a, 0, 1); return; }
-    int d;
-    for (d = 2; (1ul << d) < (unsigned long)n; ++d);
-    int stk_l[40], stk_r[40], stk_d[40], top = 0;
-    int s = 0, t = n - 1;
-    d <<= 1;
-    for (;;) {
-        if (s < t) {
-            if (--d == 0) { flt_combsort(a + s, t - s + 1); t = s; continue; }
-            int i = s, j = t, k = i + ((j - i) >> 1) + 1;
-            if (flt_lt(a[k], a[i])) { if (flt_lt(a[k], a[j])) k = j; }
-            else k = flt_lt(a[j], a[i]) ? i : j;
-            const uint2 rp = a[k];
-            if (k != t) swp(a, k, t);
-            for (;;) {
-                do ++i; while (flt_lt(a[i], rp));
-                do --j; while (i <= j && flt_lt(rp, a[j]));
-                if (j <= i) break;
-                swp(a, i, j);
-            }
-            swp(a, i, t);
-            if (i - s > t - i) {
-                if (i - s > 16) { stk_l[top] = s; stk_r[top] = i - 1; stk_d[top] = d; ++top; }
-                s = t - i > 16 ? i + 1 : t;
-            } else {
-                if (t - i > 16) { stk_l[top] = i + 1; stk_r[top] = t; stk_d[top] = d; ++top; }
-                t = i - s > 16 ? i - 1 : s;
-            }
-        } else {
-            if (top == 0) { flt_insertsort(a, 0, n); return; }
-            --top; s = stk_l[top]; t = stk_r[top]; d = stk_d[top];
-        }
-    }
-}
-
-// ---- the same introsort, run by a whole wavefront over an LDS array -----------------------------------------
-// ksort.h's introsort is not stable, so ties (equal weights are common) come out in an order that only the same
-// sequence of operations reproduces — but that sequence need not be EXECUTED sequentially:
-//   * Hoare's partition is a function of two flag vectors over the untouched range — "stops the upward scan"
-//     (!lt(a[x], pivot)) and "stops the downward scan" (!lt(pivot, a[x])): its k-th swap exchanges the k-th upward stopper
-//     with the k-th downward stopper for as long as the former lies left of the latter (positions already swapped are never
-//     scanned again), and the pivot lands on the next upward stopper or on the last swapped downward position, whichever
-//     comes first.  The stoppers are listed with ballots, the swaps are independent;
-//   * the final insertion sort over the whole array is a STABLE sort, whose result is unique: a rank sort gives it.
-// The control flow between partitions (median of three, explicit stack, depth budget, comb-sort fallback on lane 0) is
-// ksort's own.  tmp: 2 * n uint16 (the stopper lists), stk: 3 * 40 ints, both LDS.  All 64 lanes call this.
-__device__ void wave_flt_introsort(uint2 *a, int n, uint16_t *tmp, int *stk, int lane) {
-    if (n < 2) return;
-    if (n == 2) {
-        if (lane == 0 && flt_lt(a[1], a[0])) swp(a, 0, 1);
-        __syncthreads();
-        return;
-    }
-    uint16_t *ls = tmp, *rs = tmp + n;
-    int d;
-    for (d = 2; (1ul << d) < (unsigned long)n; ++d);
-    int top = 0, s = 0, t = n - 1;
-    d <<= 1;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (;;) {
-        if (s < t) {
-            if (--d == 0) {
-                if (lane == 0) flt_combsort(a + s, t - s + 1);
-                __syncthreads();
-                t = s;
-                continue;
-            }
-            int i = s, j = t, k = i + ((j - i) >> 1) + 1;
-            {
-                const uint2 ak = a[k], ai = a[i], aj = a[j];
-                if (flt_lt(ak, ai)) { if (flt_lt(ak, aj)) k = j; }
-                else k = flt_lt(aj, ai) ? i : j;
-            }
-            const uint2 rp = a[k];
+// wave_ks_introsort's closing stable sort for this order.  Stable = unique: up to 64 chains a rank sort (every lane counts,
+// from uniform LDS reads, the elements that sort before its own); beyond, a sorting network over the 64-bit keys (weight
+// descending, position ascending — no two equal), n log^2 n / 128 compare-exchanges per lane instead of n^2 / 64
+// comparisons.  The network is the bitonic sorter in its standard form (every comparator leaves the smaller key at the lower
+// index), so the pads of a power of two are virtual: a comparator whose upper end lies at or beyond n does nothing.
+// scratch: 16 * n bytes (keys, then the output copy).
+struct FltClose {
+    __device__ __forceinline__ void operator()(uint2 *a, int n, void *scratch, int lane, FltLt) const {
+        uint2 *out = reinterpret_cast<uint2 *>(scratch);
+        if (n > 64) {
+            unsigned long long *key = reinterpret_cast<unsigned long long *>(scratch);
+            out = reinterpret_cast<uint2 *>(key + n);
+            for (int x = lane; x < n; x += 64) key[x] = ((unsigned long long)(0x7fffffffu - a[x].x) << 32) | (unsigned long long)(unsigned)x;
             __syncthreads();
-            if (lane == 0 && k != t) { a[k] = a[t]; a[t] = rp; }
-            __syncthreads();
-            int NL = 0, NR = 0;
-            for (int x0 = s + 1; x0 <= t; x0 += 64) {
-                const int x = x0 + lane;
-                const bool f = x <= t && !flt_lt(a[x], rp);
-                const unsigned long long m = __ballot(f);
-                if (f) ls[NL + __popcll(m & below)] = (uint16_t)x;
-                NL += __popcll(m);
-            }
-            for (int x0 = t - 1; x0 >= s + 1; x0 -= 64) {
-                const int x = x0 - lane;
-                const bool f = x >= s + 1 && !flt_lt(rp, a[x]);
-                const unsigned long long m = __ballot(f);
-                if (f) rs[NR + __popcll(m & below)] = (uint16_t)x;
-                NR += __popcll(m);
-            }
-            __syncthreads();
-            const int np = NL < NR ? NL : NR;
-            int m_sw = 0;
-            for (int k0 = 0; k0 < np; k0 += 64) {
-                const int kk = k0 + lane;
-                m_sw += __popcll(__ballot(kk < np && ls[kk] < rs[kk]));
-            }
-            for (int k0 = 0; k0 < m_sw; k0 += 64) {
-                const int kk = k0 + lane;
-                if (kk < m_sw) swp(a, ls[kk], rs[kk]);
-            }
-            int i_f = ls[m_sw];
-            if (m_sw >= 1 && (int)rs[m_sw - 1] < i_f) i_f = rs[m_sw - 1];
-            __syncthreads();
-            if (lane == 0) swp(a, i_f, t);
-            __syncthreads();
-            i = i_f;
-            if (i - s > t - i) {
-                if (i - s > 16) { stk[3 * top] = s; stk[3 * top + 1] = i - 1; stk[3 * top + 2] = d; ++top; }
-                s = t - i > 16 ? i + 1 : t;
-            } else {
-                if (t - i > 16) { stk[3 * top] = i + 1; stk[3 * top + 1] = t; stk[3 * top + 2] = d; ++top; }
-                t = i - s > 16 ? i - 1 : s;
-            }
-            __syncthreads();                         // the stack entries were written by every lane (same values)
-        } else {
-            if (top == 0) break;
-            --top; s = stk[3 * top]; t = stk[3 * top + 1]; d = stk[3 * top + 2];
-        }
-    }
-    // the closing insertion sort = THE stable sort of what the partitions left.  (Not a local clean-up: ksort's median of
-    // three never examines a[s], which may lie beyond the pivot and then travels a long way in the insertion sort.)  Stable =
-    // unique: up to 64 chains a rank sort (every lane counts, from uniform LDS reads, the elements that sort before its own);
-    // beyond, a sorting network over the 64-bit keys (weight descending, position ascending — no two equal), n log^2 n / 128
-    // compare-exchanges per lane instead of n^2 / 64 comparisons.  The network is the bitonic sorter in its standard form (every
-    // comparator leaves the smaller key at the lower index), so the pads of a power of two are virtual: a comparator whose upper
-    // end lies at or beyond n does nothing.  tmp: 16 * n bytes (keys, then the output copy).
-    __syncthreads();
-    uint2 *out = reinterpret_cast<uint2 *>(tmp);          // n * 8 bytes: the stopper lists are dead by now
-    if (n > 64) {
-        unsigned long long *key = reinterpret_cast<unsigned long long *>(tmp);
-        out = reinterpret_cast<uint2 *>(key + n);
-        for (int x = lane; x < n; x += 64) key[x] = ((unsigned long long)(0x7fffffffu - a[x].x) << 32) | (unsigned long long)(unsigned)x;
-        __syncthreads();
-        int P = 128;
-        while (P < n) P <<= 1;
-        for (int k = 2; k <= P; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const bool flip = j == (k >> 1);
-                for (int c0 = 0; c0 < (P >> 1); c0 += 64) {
-                    const int c = c0 + lane;
-                    const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));        // j is a power of two
-                    const int l = flip ? (i ^ (k - 1)) : i + j;
-                    if (l < n) {
-                        const unsigned long long x = key[i], y = key[l];
-                        if (y < x) { key[i] = y; key[l] = x; }
+            int P = 128;
+            while (P < n) P <<= 1;
+            for (int k = 2; k <= P; k <<= 1) {
+                for (int j = k >> 1; j > 0; j >>= 1) {
+                    const bool flip = j == (k >> 1);
+                    for (int c0 = 0; c0 < (P >> 1); c0 += 64) {
+                        const int c = c0 + lane;
+                        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));        // j is a power of two
+                        const int l = flip ? (i ^ (k - 1)) : i + j;
+                        if (l < n) {
+                            const unsigned long long x = key[i], y = key[l];
+                            if (y < x) { key[i] = y; key[l] = x; }
+                        }
                     }
+                    __syncthreads();
                 }
-                __syncthreads();
             }
+            for (int x = lane; x < n; x += 64) out[x] = a[(uint32_t)key[x]];
+            __syncthreads();
+        } else {
+            const int x = lane;
+            const uint2 v = x < n ? a[x] : make_uint2(0u, 0u);
+            int pos = 0;
+            for (int y = 0; y < n; ++y) {
+                const uint32_t wy = a[y].x;
+                pos += (wy > v.x || (wy == v.x && y < x)) ? 1 : 0;
+            }
+            if (x < n) out[pos] = v;
+            __syncthreads();
         }
-        for (int x = lane; x < n; x += 64) out[x] = a[(uint32_t)key[x]];
-        __syncthreads();
-    } else {
-        const int x = lane;
-        const uint2 v = x < n ? a[x] : make_uint2(0u, 0u);
-        int pos = 0;
-        for (int y = 0; y < n; ++y) {
-            const uint32_t wy = a[y].x;
-            pos += (wy > v.x || (wy == v.x && y < x)) ? 1 : 0;
-        }
-        if (x < n) out[pos] = v;
+        for (int x = lane; x < n; x += 64) a[x] = out[x];
         __syncthreads();
     }
-    for (int x = lane; x < n; x += 64) a[x] = out[x];
-    __syncthreads();
+};
+
+// The wave form over a[0 .. n) in LDS.  All 64 lanes call this.  scratch: 16 n bytes of LDS, at least 8 n + 480, used as
+//   [0, 4 n)          the stopper lists of a partition (dead during a depth-limit fallback and at the closing sort)
+//   [0, 8 n)          the output of the comb-sort fallback's closing rank sort (at most n records of 8 B)
+//   [8 n, 8 n + 480)  the partition stack (3 * 40 ints), which the fallback therefore leaves alone
+//   [0, 16 n)         FltClose's keys and output copy, when the stack is dead too
+// depth0: see ks_introsort (the test hook's)
+__device__ __forceinline__ void wave_flt_sort(uint2 *a, int n, void *scratch, int lane, int depth0 = 0) {
+    wave_ks_introsort(a, n, scratch, reinterpret_cast<int *>(reinterpret_cast<char *>(scratch) + (size_t)n * 8), lane, FltLt(), FltClose(), depth0);
 }
 
 // ---- the pairwise filter of mem_chain_flt, sequential form --------------------------------------
@@ -1191,7 +1060,7 @@ __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int la
         A.heavy[slot] = (int32_t)r;
         return true;
     }
-    flt_introsort(fl, n_chn);
+    ks_introsort(fl, n_chn, FltLt());
     uint4 *rec = A.f_rec + base;
     int32_t *kept = A.f_kept + base;
     for (int i = 0; i < n_chn; ++i) {
@@ -1267,6 +1136,7 @@ __global__ __launch_bounds__(64) void chain_redo_kernel(ChainArgs A) {
 constexpr int kHeavyCap[6] = {64, 128, 256, 512, 960, 3840};         // 2.7 / 5 / 10.5 / 21 / 39 / 157 KB of LDS
 __host__ __device__ constexpr size_t heavy_lds_bytes(int cap) { return (size_t)cap * 41 + 64; }
 static_assert(heavy_lds_bytes(kHeavyCap[5]) <= 160 * 1024, "the largest class must fit one CU's LDS");
+static_assert(160 * 1024 / 41 <= 65535, "wave_ks_introsort's stopper lists are uint16_t: no LDS class may hold more chains");
 
 // one read's sort, pairwise filter and totals by a whole wavefront.  lds: heavy_lds_bytes(cap) bytes, n_chn <= cap; fl[0 .. n_chn) in HBM
 // holds the {weight, chain id} pairs in B-tree order.  All 64 lanes call this.
@@ -1287,9 +1157,9 @@ __device__ void heavy_read(const ChainArgs &A, int64_t r, int64_t base, int n_ch
         __syncthreads();
         for (int i = lane; i < n_chn; i += 64) l_fl[i] = fl[i];
         __syncthreads();
-        // ksort's introsort, operation for operation, by the whole wave; l_sel is free until the filter: it lends the sort
-        // its stopper lists / output copy (8 B per chain) and, behind them, the partition stack
-        wave_flt_introsort(l_fl, n_chn, reinterpret_cast<uint16_t *>(l_sel), reinterpret_cast<int *>(reinterpret_cast<char *>(l_sel) + (size_t)n_chn * 8), lane);
+        // ksort's introsort, operation for operation, by the whole wave; l_sel (16 B per chain, cap >= 64) is free until the
+        // filter: it lends the sort its scratch, laid out as wave_flt_sort states
+        wave_flt_sort(l_fl, n_chn, l_sel, lane);
         const unsigned long long t_1 = __builtin_amdgcn_s_memtime();
         for (int i = lane; i < n_chn; i += 64) {
             const uint2 f = l_fl[i];
@@ -1449,7 +1319,7 @@ __global__ __launch_bounds__(64) void chain_heavy_kernel(ChainArgs A, const unsi
             const unsigned long long t_0 = __builtin_amdgcn_s_memtime();
             if (lane == 0) {
                 atomicAdd(&A.ctr->dbg[6], 1ull);
-                flt_introsort(fl, n_chn);
+                ks_introsort(fl, n_chn, FltLt());
                 for (int i = 0; i < n_chn; ++i) { rec[i] = make_rec(A, crec[fl[i].y], fl[i].x); kept[i] = 0; }
                 filter_seq(A.opt, n_chn, rec, kept, A.f_sel + base);
                 finish_read(A, r, base, n_chn, L);
@@ -1521,6 +1391,29 @@ __global__ __launch_bounds__(256) void chain_emit_kernel(ChainArgs A, const int6
         }
         so0 += total;
     }
+}
+
+// test hook (bwams_debug_sort, which = 2): one wavefront sorts n {weight, index} pairs as the chain filter does, with LDS
+// laid out like heavy_read's.  mode 0, 1: wave_flt_sort; 2: the sequential form by lane 0 on a copy in GLOBAL memory; 3 / 4:
+// modes 1 / 2 with a depth budget of 2, so that the comb-sort fallback sorts nearly everything
+constexpr int kFltTestN = 1024;
+__global__ __launch_bounds__(64) void flt_sort_test_kernel(const uint2 *__restrict__ in, int n, int mode, int32_t *__restrict__ order,
+                                                           uint2 *__restrict__ scratch) {
+    __shared__ uint2 l_a[kFltTestN];
+    __shared__ uint4 l_scr[kFltTestN];
+    const int lane = threadIdx.x;
+    if (mode == 2 || mode == 4) {
+        for (int i = lane; i < n; i += 64) scratch[i] = in[i];
+        __syncthreads();
+        if (lane == 0) ks_introsort(scratch, n, FltLt(), mode == 4 ? 2 : 0);
+        __syncthreads();
+        for (int i = lane; i < n; i += 64) order[i] = (int32_t)scratch[i].y;
+        return;
+    }
+    for (int i = lane; i < n; i += 64) l_a[i] = in[i];
+    __syncthreads();
+    wave_flt_sort(l_a, n, l_scr, lane, mode == 3 ? 2 : 0);
+    for (int i = lane; i < n; i += 64) order[i] = (int32_t)l_a[i].y;
 }
 
 }  // namespace
@@ -1604,6 +1497,19 @@ void launch_chain_emit(const ChainArgs &A, const int64_t *chain_off, const int64
                        bwams_chain_seed_t *seeds, hipStream_t st) {
     if (A.nseq <= 0) return;
     chain_emit_kernel<<<(unsigned)((A.nseq * 16 + 255) / 256), 256, 0, st>>>(A, chain_off, seed_off, chains, seeds);
+}
+
+int launch_flt_sort_test(const int64_t *w, int n, int mode, int32_t *order) {
+    if (n < 0 || n > kFltTestN) return -1;
+    std::vector<uint2> h((size_t)n + 1);
+    for (int i = 0; i < n; ++i) h[i] = make_uint2((unsigned)w[i], (unsigned)i);
+    DevBuf<uint2> d_in, d_scr;
+    DevBuf<int32_t> d_ord;
+    if (d_in.alloc(8 * (size_t)(n + 1)) != hipSuccess || d_scr.alloc(8 * (size_t)(n + 1)) != hipSuccess || d_ord.alloc(4 * (size_t)(n + 1)) != hipSuccess ||
+        hipMemcpy(d_in.p, h.data(), 8 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    flt_sort_test_kernel<<<1, 64>>>(d_in.p, n, mode, d_ord.p, d_scr.p);
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(order, d_ord.p, 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return 0;
 }
 
 }  // namespace bwams

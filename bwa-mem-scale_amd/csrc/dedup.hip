@@ -731,7 +731,7 @@ constexpr int kTestN = 1024;
 // test hook: one wavefront sorts n records held in LDS, as the wave tier does (mode 0: rank sort, or beyond 96 records the bitonic
 // network, with the exact fallback on ties, 1: the operation-exact wave introsort always, 2: lane 0 alone through sort_records on a copy in GLOBAL memory — the
 // sequential statement of the same sort; 3 / 4: modes 1 / 2 with a depth budget of 2, so that the comb-sort fallback
-// (wave_combsort / r_combsort) sorts nearly everything)
+// (wave_ks_combsort / ks_combsort) sorts nearly everything)
 __global__ __launch_bounds__(64) void sort_test_kernel(const SortRec *__restrict__ in, int n, int by_score, int mode, int32_t *__restrict__ order,
                                                        SortRec *__restrict__ scratch) {
     __shared__ SortRec l_a[kTestN], l_t[kTestN];

@@ -516,23 +516,16 @@ __global__ __launch_bounds__(64) void pair_post_wave_kernel(PairArgs A) {
                     else { l_k64[i] = INT64_MAX; l_ks[i] = INT32_MIN; l_kq[i] = INT32_MAX; l_tmp[i] = -1; }
                 }
                 __syncthreads();
-                for (int k = 2; k <= P; k <<= 1) {
-                    for (int j = k >> 1; j > 0; j >>= 1) {
-                        for (int t = lane; t < (P >> 1); t += 64) {
-                            const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                            const int64_t ka = l_k64[i], kb = l_k64[l];
-                            const int sa = l_ks[i], sb = l_ks[l], qa = l_kq[i], qb = l_kq[l];
-                            const bool b_lt_a = sb > sa || (sb == sa && (kb < ka || (kb == ka && qb < qa)));
-                            const bool a_lt_b = sa > sb || (sa == sb && (ka < kb || (ka == kb && qa < qb)));
-                            const bool up = (i & k) == 0;
-                            if (up ? b_lt_a : a_lt_b) {
-                                l_k64[i] = kb; l_k64[l] = ka; l_ks[i] = sb; l_ks[l] = sa; l_kq[i] = qb; l_kq[l] = qa;
-                                const int ta = l_tmp[i]; l_tmp[i] = l_tmp[l]; l_tmp[l] = ta;
-                            }
-                        }
-                        __syncthreads();
+                wave_bitonic_net(P, lane, [&](int i, int l, bool up) {
+                    const int64_t ka = l_k64[i], kb = l_k64[l];
+                    const int sa = l_ks[i], sb = l_ks[l], qa = l_kq[i], qb = l_kq[l];
+                    const bool b_lt_a = sb > sa || (sb == sa && (kb < ka || (kb == ka && qb < qa)));
+                    const bool a_lt_b = sa > sb || (sa == sb && (ka < kb || (ka == kb && qa < qb)));
+                    if (up ? b_lt_a : a_lt_b) {
+                        l_k64[i] = kb; l_k64[l] = ka; l_ks[i] = sb; l_ks[l] = sa; l_kq[i] = qb; l_kq[l] = qa;
+                        const int ta = l_tmp[i]; l_tmp[i] = l_tmp[l]; l_tmp[l] = ta;
                     }
-                }
+                });
                 for (int ib = 0; ib < n; ib += 64) {
                     const int i = ib + lane;
                     const bool eq = i >= 1 && i < n && l_k64[i] == l_k64[i - 1] && l_ks[i] == l_ks[i - 1] && l_kq[i] == l_kq[i - 1];
@@ -808,21 +801,15 @@ __global__ __launch_bounds__(64) void pair_mark_wave_kernel(PairArgs A, unsigned
                 else { k1[i] = ~0ull; k2[i] = ~0ull; pay[i] = -1; }
             }
             __syncthreads();
-            for (int k = 2; k <= P; k <<= 1) {
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int t = lane; t < (P >> 1); t += 64) {
-                        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                        const uint64_t a1 = k1[i], b1 = k1[l], a2 = k2[i], b2 = k2[l];
-                        const bool b_lt_a = b1 < a1 || (b1 == a1 && b2 < a2);
-                        const bool a_lt_b = a1 < b1 || (a1 == b1 && a2 < b2);
-                        if (((i & k) == 0) ? b_lt_a : a_lt_b) {
-                            k1[i] = b1; k1[l] = a1; k2[i] = b2; k2[l] = a2;
-                            const int ta = pay[i]; pay[i] = pay[l]; pay[l] = ta;
-                        }
-                    }
-                    __syncthreads();
+            wave_bitonic_net(P, lane, [&](int i, int l, bool up) {
+                const uint64_t a1 = k1[i], b1 = k1[l], a2 = k2[i], b2 = k2[l];
+                const bool b_lt_a = b1 < a1 || (b1 == a1 && b2 < a2);
+                const bool a_lt_b = a1 < b1 || (a1 == b1 && a2 < b2);
+                if (up ? b_lt_a : a_lt_b) {
+                    k1[i] = b1; k1[l] = a1; k2[i] = b2; k2[l] = a2;
+                    const int ta = pay[i]; pay[i] = pay[l]; pay[l] = ta;
                 }
-            }
+            });
             for (int r = lane; r < n; r += 64) l_at[r] = pay[r];
             __syncthreads();
         } else {

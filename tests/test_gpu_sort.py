@@ -1,4 +1,5 @@
-"""The region sorts of mem_sort_dedup_patch as the wave tier runs them (bwams_debug_sort): ksort.h's introsort is not
+"""The device sorts (csrc/ksort.h) as the wave tiers run them (bwams_debug_sort) — the region sorts of mem_sort_dedup_patch
+(which = 0, 1) and the chain filter's sort by weight (which = 2): ksort.h's introsort is not
 stable, so on tied keys only the same sequence of comparisons and swaps gives the reference's order.  Checked against
 the reference's own ks_introsort (oracle/_ref/libref_chain.so when present, else the restatement pinned to it) on inputs
 with heavy ties, including every small size (the six-record case of profiles/r01_notes.md item 20 among them), sorted /
@@ -53,6 +54,21 @@ def test_wave_tier_sorts_equal_ksort(ix):
                 got = ix.debug_sort(k, s, q, which, mode)
                 assert np.array_equal(got, want), (len(k), which, mode, k[:12], got[:12], want[:12])
             n_tied += len(k) > len(np.unique(k))
+    assert n_tied > 100
+
+
+def test_chain_filter_sort_equals_ksort(ix):
+    """which = 2: weights descending, as heavy_read (wave form, modes 0 and 1) and chain_read (sequential form, mode 2) sort a
+    read's chains; 64 / 65 is where the wave form's closing sort changes from the rank sort to the key network, 129 the first
+    size whose network (P = 256) has virtual pads."""
+    L = loader.ref_chain_lib()
+    n_tied = 0
+    for w, _, _ in _cases():
+        want = loader.flt_sort(w, L)
+        for mode in (0, 1, 2):
+            got = ix.debug_sort(w, w, w, 2, mode)
+            assert np.array_equal(got, want), (len(w), mode, w[:12], got[:12], want[:12])
+        n_tied += len(w) > len(np.unique(w))
     assert n_tied > 100
 
 
@@ -142,7 +158,7 @@ def _antiquicksort(n):
 
 
 def test_depth_limit_fallback(ix):
-    """The comb-sort fallback of ks_introsort's depth limit in the wave tiers (wave_combsort: the whole wavefront, no lane
+    """The comb-sort fallback of ks_introsort's depth limit in the wave tiers (wave_ks_combsort: the whole wavefront, no lane
     sorting alone on LDS): (a) an adversarial permutation on which ksort.h itself exhausts its depth budget — the order must be
     the pinned ks_introsort's; (b) a depth budget of 2 on inputs of every kind — the wave form must equal the sequential form
     operation for operation (ties included)."""
@@ -168,3 +184,23 @@ def test_depth_limit_fallback(ix):
                 keys = k[a] if which == 0 else np.stack([-s[a], k[a], q[a]], 1)
                 srt = np.all(np.diff(keys) >= 0) if which == 0 else all(tuple(keys[i]) <= tuple(keys[i + 1]) for i in range(n - 1))
                 assert srt
+
+
+def test_chain_filter_sort_depth_limit_fallback(ix):
+    """The same two checks for which = 2 (the adversary turned for the descending order: weight = n - 1 - key, so that the
+    sort makes the comparisons the adversary answered)."""
+    L = loader.ref_chain_lib()
+    for n in (200, 700, 1024):
+        k, hit = _antiquicksort(n)
+        assert hit, n
+        w = n - 1 - k
+        want = loader.flt_sort(w, L)
+        for mode in (0, 1, 2):
+            assert np.array_equal(ix.debug_sort(w, w, w, 2, mode), want), (n, mode)
+    rng = np.random.default_rng(11)
+    for n in (3, 17, 18, 40, 65, 130, 500, 1024):
+        for spread in (1, 2, 5, 1 << 20):
+            w = rng.integers(0, spread, size=n)
+            a, b = ix.debug_sort(w, w, w, 2, 3), ix.debug_sort(w, w, w, 2, 4)
+            assert np.array_equal(a, b), (n, spread)
+            assert np.array_equal(np.sort(a), np.arange(n)) and np.all(np.diff(w[a]) <= 0), (n, spread)
