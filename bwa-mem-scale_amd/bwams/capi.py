@@ -43,6 +43,7 @@ SYMBOLS = [
     "bwams_process_reads", "bwams_process_reads_stage1", "bwams_process_reads_stage2", "bwams_host_alloc", "bwams_host_free",
     "bwams_reader_open", "bwams_reader_next", "bwams_reader_release", "bwams_reader_error", "bwams_reader_close",
     "bwams_inflater_create", "bwams_inflater_run", "bwams_inflater_destroy", "bwams_reader_open_device", "bwams_reader_info",
+    "bwams_gunzip_create", "bwams_gunzip_run", "bwams_gunzip_destroy", "bwams_reader_open_device2",
     "bwams_deflate_bound", "bwams_deflater_create", "bwams_deflater_run", "bwams_deflater_destroy", "bwams_sam_fetch_bgzf",
     "bwams_writer_open_bgzf", "bwams_writer_put_bgzf",
     "bwams_bam_run", "bwams_bam_fetch", "bwams_bam_fetch_bgzf", "bwams_sam_header", "bwams_bam_header", "bwams_writer_open_bam",
@@ -209,6 +210,11 @@ class FastaStats(C.Structure):
 class InflateStats(C.Structure):
     _fields_ = [("members", C.c_int64), ("in_bytes", C.c_int64), ("out_bytes", C.c_int64),
                 ("ms_upload", C.c_float), ("ms_kernel", C.c_float), ("ms_download", C.c_float)]
+
+
+class GunzipStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("members", "pieces", "pieces_dropped", "recounts", "in_bytes", "out_bytes", "trailing_bytes")] + \
+               [(n, C.c_float) for n in ("ms_upload", "ms_find", "ms_count", "ms_decode", "ms_window", "ms_resolve", "ms_download")]
 
 
 class ReaderStats(C.Structure):
@@ -378,12 +384,60 @@ class Sorter:
             pass
 
 
+class Gunzipper:
+    """Plain gzip inflated on one GPU (bwams_gunzip_t): one file, fed in order."""
+
+    def __init__(self, device: int = 0, max_in_bytes: int = 32 << 20, max_out_bytes: int = 64 << 20, piece_bytes: int = 0):
+        self.h = C.c_void_p()
+        self.max_out = max_out_bytes
+        _chk(lib().bwams_gunzip_create(device, max_in_bytes, max_out_bytes, piece_bytes, C.byref(self.h)), "bwams_gunzip_create")
+
+    def run_raw(self, gz, last: bool, out, out_cap: int, on_device: bool):
+        """bwams_gunzip_run as is: gz bytes (or (addr, n)), out an address.  Returns (rc, n_consumed, n_out, GunzipStats)."""
+        used, n_out, st = C.c_int64(0), C.c_int64(0), GunzipStats()
+        ptr, n = (C.c_void_p(gz[0]), gz[1]) if isinstance(gz, tuple) else (gz, len(gz))
+        rc = lib().bwams_gunzip_run(self.h, ptr, n, int(last), C.c_void_p(out), out_cap, int(on_device), C.byref(used),
+                                    C.byref(n_out), C.byref(st))
+        return rc, used.value, n_out.value, st
+
+    def run(self, gz: bytes, last: bool = True, out_cap: int | None = None):
+        """One call with a host output (out_cap: default max_out_bytes): (text bytes, n_consumed, GunzipStats)."""
+        cap = out_cap if out_cap is not None else self.max_out
+        buf = C.create_string_buffer(max(cap, 1))
+        rc, used, n, st = self.run_raw(gz, last, C.addressof(buf), cap, False)
+        _chk(rc, "bwams_gunzip_run")
+        return buf.raw[:n], used, st
+
+    def close(self):
+        if self.h:
+            lib().bwams_gunzip_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def reader_open_device(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0,
                        n_buffers: int = 2) -> C.c_void_p:
     """bwams_reader_open_device: a bwams_reader_t handle (bwams_reader_next / _release / _close as for bwams_reader_open)."""
     r = C.c_void_p()
     _chk(lib().bwams_reader_open_device(path.encode(), device, chunk_bases, int(paired), buffer_bytes, n_buffers, C.byref(r)),
          "bwams_reader_open_device")
+    return r
+
+
+READER_GUNZIP = 0x1          # BWAMS_READER_GUNZIP
+
+
+def reader_open_device2(path: str, device: int, chunk_bases: int, paired: bool = False, buffer_bytes: int = 0, n_buffers: int = 2,
+                        flags: int = 0) -> C.c_void_p:
+    """bwams_reader_open_device2: bwams_reader_open_device with flags (READER_GUNZIP: plain gzip inflated on the device too)."""
+    r = C.c_void_p()
+    _chk(lib().bwams_reader_open_device2(path.encode(), device, chunk_bases, int(paired), buffer_bytes, n_buffers, flags, C.byref(r)),
+         "bwams_reader_open_device2")
     return r
 
 
@@ -539,6 +593,10 @@ def lib():
         L.bwams_inflater_destroy.argtypes = [vp]
         L.bwams_reader_open_device.argtypes = [C.c_char_p, C.c_int, i64, i32, i64, i32, vp]
         L.bwams_reader_info.argtypes = [vp, vp]
+        L.bwams_gunzip_create.argtypes = [C.c_int, i64, i64, i32, vp]
+        L.bwams_gunzip_run.argtypes = [vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp]
+        L.bwams_gunzip_destroy.argtypes = [vp]
+        L.bwams_reader_open_device2.argtypes = [C.c_char_p, C.c_int, i64, i32, i64, i32, C.c_uint32, vp]
         L.bwams_reader_open.argtypes = [C.c_char_p, i64, i32, i64, i32, vp]
         L.bwams_reader_next.argtypes = [vp, vp, vp, vp, vp]
         L.bwams_reader_release.argtypes = [vp, vp]

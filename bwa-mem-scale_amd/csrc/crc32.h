@@ -1,6 +1,6 @@
 // crc32.h — gzip's CRC-32 (reflected polynomial 0xEDB88320) of bytes in LDS, computed by a whole workgroup: a lane per 1/NT of the
 // bytes with a byte table in LDS, the lanes' remainders joined by x^(8n) mod P.  Shared by inflate.hip (checks a member's output) and
-// deflate.hip (writes a member's trailer).
+// deflate.hip (writes a member's trailer); gunzip.hip computes one per tile of output and joins them on the host.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -13,7 +13,8 @@
 //     texts handed to it in sequence-number order — a shard's file is in read order; concatenating the shards' files of a job that gave
 //     shard s the s-th contiguous slice of every chunk is NOT read order across chunks (that is what the single-stream form is for).
 //   * where the text comes from is a Source: zlib's gzread (bwams_reader_open, and bwams_reader_open_device on any file that is not
-//     BGZF), or BGZF members inflated on a GPU (bwams_reader_open_device: read(2) into page-locked staging, bwams_inflater_run into
+//     BGZF), plain gzip inflated on a GPU (bwams_reader_open_device2 with BWAMS_READER_GUNZIP: bwams_gunzip_run), or BGZF members
+//     inflated on a GPU (bwams_reader_open_device: read(2) into page-locked staging, bwams_inflater_run into
 //     the chunk buffer behind the carried bytes).  The cut loop is the same for both, so their chunks are the same bytes.
 //   * bwams_reader_open_bam: the same Sources under a BAM file.  Open parses the header block on the caller's thread; the reader's
 //     thread then cuts chunks of whole BAM records, hopping along block_size where the text loop scans lines (one_bam_record), with
@@ -204,6 +205,92 @@ struct BgzfSource : Source {
     }
 };
 
+// Plain gzip: compressed bytes by read(2) into page-locked staging, bwams_gunzip_run into the chunk buffer.  A call consumes whole
+// bytes up to a block boundary; the rest is presented again with what the file gives next.  A request smaller than a piece may
+// inflate to (kSpill bytes) is served from `spill`.
+struct GunzipSource : Source {
+    static constexpr int64_t kSpill = 4 << 20;
+    std::string path;
+    int fd = -1;
+    bwams_gunzip_t *gun = nullptr;
+    char *zbuf = nullptr;                                  // page-locked
+    int64_t zcap = 0, zpos = 0, zend = 0;
+    bool file_end = false, done = false;
+    std::vector<char> spill = std::vector<char>((size_t)kSpill);
+    int64_t spill_pos = 0, spill_end = 0;
+    ~GunzipSource() override {
+        if (gun) bwams_gunzip_destroy(gun);
+        if (zbuf) bwams_host_free(zbuf);
+        if (fd >= 0) close(fd);
+    }
+    int64_t read(char *dst, int64_t want, std::string &err) override {
+        if (spill_pos < spill_end) {
+            const int64_t n = std::min(want, spill_end - spill_pos);
+            memcpy(dst, spill.data() + spill_pos, (size_t)n);
+            spill_pos += n;
+            return n;
+        }
+        for (;;) {
+            if (done) return 0;
+            if (zend > zpos || file_end) {
+                const bool direct = want >= kSpill;
+                int64_t used = 0, n_out = 0;
+                const auto t0 = Clock::now();
+                int rc = bwams_gunzip_run(gun, reinterpret_cast<const uint8_t *>(zbuf + zpos), zend - zpos, file_end, direct ? dst : spill.data(),
+                                          direct ? want : kSpill, 0, &used, &n_out, nullptr);
+                st.ms_inflate += ms_since(t0);
+                if (rc == BWAMS_ERR_CAPACITY && direct && want < step) {       // the chunk buffer's last bytes: through the spill
+                    rc = bwams_gunzip_run(gun, reinterpret_cast<const uint8_t *>(zbuf + zpos), zend - zpos, file_end, spill.data(), kSpill, 0,
+                                          &used, &n_out, nullptr);
+                    if (!rc && n_out) {
+                        zpos += used;
+                        st.out_bytes += n_out;
+                        spill_pos = 0;
+                        spill_end = n_out;
+                        return read(dst, want, err);
+                    }
+                }
+                if (rc) {
+                    err = path + ": " + bwams_last_error();
+                    if (rc == BWAMS_ERR_CAPACITY) err += " (open the file without BWAMS_READER_GUNZIP)";
+                    return rc;
+                }
+                zpos += used;
+                st.out_bytes += n_out;
+                if (n_out) {
+                    if (direct) return n_out;
+                    spill_pos = 0;
+                    spill_end = n_out;
+                    return read(dst, want, err);
+                }
+                if (file_end && used == 0) { done = true; return 0; }
+                if (used) continue;
+            }
+            if (zpos == 0 && zend == zcap) { err = path + ": no DEFLATE block boundary inside the staging buffer (open the file without BWAMS_READER_GUNZIP)"; return BWAMS_ERR_CAPACITY; }
+            memmove(zbuf, zbuf + zpos, (size_t)(zend - zpos));
+            zend -= zpos;
+            zpos = 0;
+            const auto t0 = Clock::now();
+            const ssize_t got = ::read(fd, zbuf + zend, (size_t)(zcap - zend));
+            st.ms_read += ms_since(t0);
+            if (got < 0) { err = path + ": read failed"; return BWAMS_ERR_IO; }
+            if (got == 0) file_end = true;
+            zend += got;
+            st.in_bytes += got;
+        }
+    }
+};
+
+// the first two bytes of a gzip file
+bool is_gzip(const char *path) {
+    unsigned char h[2];
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return false;
+    const size_t n = fread(h, 1, sizeof h, fp);
+    fclose(fp);
+    return n == 2 && h[0] == 31 && h[1] == 139;
+}
+
 // the first bytes of a BGZF file: a gzip header with FEXTRA only and a 'BC' subfield
 bool is_bgzf(const char *path) {
     unsigned char h[64];
@@ -356,9 +443,26 @@ static int zlib_source(const char *path, std::unique_ptr<Source> *out) {
 }
 
 // The Source of bwams_reader_open_device: BGZF members inflated on `device`, anything else through zlib
-static int device_source(const char *path, int device, std::unique_ptr<Source> *out) {
-    if (device < 0 || !is_bgzf(path)) return zlib_source(path, out);
+static int device_source(const char *path, int device, std::unique_ptr<Source> *out, uint32_t flags = 0) {
     constexpr int64_t kIn = 32 << 20, kOut = 64 << 20;     // one call: up to 32 MiB of members, 64 MiB of text
+    if (device >= 0 && (flags & BWAMS_READER_GUNZIP) && !is_bgzf(path) && is_gzip(path)) {
+        // a call's parallelism is its pieces: 32 MiB of gzip in pieces of 32 KiB (a zlib block of FASTQ is some 20 KB) is a
+        // thousand decoders, and some 60 MiB of FASTQ text (a call takes the pieces whose text fits kOut)
+        constexpr int64_t kGzIn = 32 << 20;
+        constexpr int32_t kPiece = 32 << 10;
+        auto b = std::unique_ptr<GunzipSource>(new GunzipSource());
+        b->path = path;
+        b->st.device_inflate = 2;
+        b->step = kOut;
+        b->fd = open(path, O_RDONLY);
+        if (b->fd < 0) return BWAMS_ERR_IO;
+        if (int rc = bwams_host_alloc((size_t)kGzIn, reinterpret_cast<void **>(&b->zbuf))) return rc;
+        b->zcap = kGzIn;
+        if (int rc = bwams_gunzip_create(device, kGzIn, kOut, kPiece, &b->gun)) return rc;
+        *out = std::move(b);
+        return BWAMS_OK;
+    }
+    if (device < 0 || !is_bgzf(path)) return zlib_source(path, out);
     auto b = std::unique_ptr<BgzfSource>(new BgzfSource());
     b->path = path;
     b->st.device_inflate = 1;
@@ -390,12 +494,17 @@ int bwams_reader_open(const char *path, int64_t chunk_bases, int32_t paired, int
 
 int bwams_reader_open_device(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes,
                              int32_t n_buffers, bwams_reader_t **out) {
-    if (!path || !out || chunk_bases <= 0 || n_buffers < 1 || n_buffers > 16) return BWAMS_ERR_ARG;
+    return bwams_reader_open_device2(path, device, chunk_bases, paired, buffer_bytes, n_buffers, 0, out);
+}
+
+int bwams_reader_open_device2(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes,
+                              int32_t n_buffers, uint32_t flags, bwams_reader_t **out) {
+    if (!path || !out || chunk_bases <= 0 || n_buffers < 1 || n_buffers > 16 || (flags & ~(uint32_t)BWAMS_READER_GUNZIP)) return BWAMS_ERR_ARG;
     *out = nullptr;
     bwams_reader *r = nullptr;
     try {
         r = new bwams_reader();
-        if (int rc = device_source(path, device, &r->src)) { delete r; return rc; }
+        if (int rc = device_source(path, device, &r->src, flags)) { delete r; return rc; }
         if (int rc = reader_start(r, chunk_bases, paired, buffer_bytes, n_buffers)) { bwams_reader_close(r); return rc; }
     } catch (...) {
         if (r) bwams_reader_close(r);

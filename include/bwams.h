@@ -159,6 +159,31 @@ int bwams_inflater_create(int device, int64_t max_in_bytes, int64_t max_out_byte
 int bwams_inflater_run(bwams_inflater_t *f, const uint8_t *gz, int64_t n_bytes, void *out, int64_t out_cap, int out_on_device,
                        int64_t *n_consumed, int64_t *n_out, bwams_inflate_stats_t *stats);
 int bwams_inflater_destroy(bwams_inflater_t *f);
+/* Plain gzip (RFC 1952: one DEFLATE stream, or a few members, with no table of member sizes — what `gzip` writes) inflated on the GPU
+ * (csrc/gunzip.hip).  The compressed bytes of a call are cut into pieces of piece_bytes (>= 4096; 0: 256 KiB); a block start is
+ * searched in each piece, every piece is decoded at once with the unknown 32 KiB in front of it as markers, and the markers are
+ * resolved afterwards.  The candidates are hints: a piece is used only when its predecessor's decode ended exactly on its start, so the
+ * output is a sequential decoder's on any input.  max_in_bytes (>= piece_bytes) / max_out_bytes (>= 65536): the compressed bytes one
+ * call looks at and the text bytes one call produces at most.  BGZF is gzip: this handle inflates it too.  One caller at a time. */
+typedef struct bwams_gunzip bwams_gunzip_t;
+typedef struct bwams_gunzip_stats {
+    int64_t members, pieces, pieces_dropped, recounts, in_bytes, out_bytes, trailing_bytes;   /* members: those that ended in this call */
+    float ms_upload, ms_find, ms_count, ms_decode, ms_window, ms_resolve, ms_download;        /* device events */
+} bwams_gunzip_stats_t;
+int bwams_gunzip_create(int device, int64_t max_in_bytes, int64_t max_out_bytes, int32_t piece_bytes, bwams_gunzip_t **out);
+/* A handle is fed one file in order, in calls of any size; it keeps where in the stream it is (a header, DEFLATE data at bit 0-7 of
+ * the first unconsumed byte, a trailer), the 32 KiB window (on the device) and the current member's CRC32 and length.  A call inflates
+ * gz[0, n_bytes) into out (host memory, or this device's memory when out_on_device) up to the last block boundary of the confirmed
+ * chain of pieces whose output fits out_cap and max_out_bytes.  *n_consumed counts whole bytes: the caller presents the rest again,
+ * followed by more; `last` = 1 says that no bytes follow.  0 with 0 / 0: give it more bytes.  BWAMS_ERR_UNSUPPORTED: the first bytes
+ * are no gzip header.  BWAMS_ERR_CAPACITY: not even the first piece's output fits, or no block boundary lies inside max_in_bytes.
+ * BWAMS_ERR_IO: damaged data (a refused code, a distance too far back, CRC32 or ISIZE that do not match, a bad member header), or a
+ * stream that ends inside a member when `last` is set; bwams_last_error names the member and the byte offset, counted over all
+ * calls, and nothing of that call is consumed.  Bytes behind a member that are no gzip header are ignored, as gzread ignores them,
+ * and counted in trailing_bytes. */
+int bwams_gunzip_run(bwams_gunzip_t *g, const uint8_t *gz, int64_t n_bytes, int32_t last, void *out, int64_t out_cap,
+                     int out_on_device, int64_t *n_consumed, int64_t *n_out, bwams_gunzip_stats_t *stats);
+int bwams_gunzip_destroy(bwams_gunzip_t *g);
 /* BGZF written on the GPU: the output side's counterpart of the inflater.  The text is cut every 65280 bytes from its byte 0 (bgzip's
  * and htslib's cut; the last member is partial) and each piece becomes one standalone gzip member with bgzip's header: one RFC 1951
  * block, stored, fixed or dynamic Huffman, whichever has the fewest bits (input that does not compress is stored: its length + 31
@@ -851,8 +876,14 @@ int bwams_reader_close(bwams_reader_t *r);
  * bwams_reader_open reads it, and bwams_reader_info says device_inflate = 0.  The reader's own thread sets the device. */
 int bwams_reader_open_device(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes,
                              int32_t n_buffers, bwams_reader_t **out);
+/* bwams_reader_open_device with flags.  BWAMS_READER_GUNZIP: a gzip file that is not BGZF is inflated on `device` too
+ * (bwams_gunzip_run into the chunk buffer), and bwams_reader_info says device_inflate = 2; the chunks are the same bytes.  flags = 0:
+ * bwams_reader_open_device exactly. */
+#define BWAMS_READER_GUNZIP 0x1
+int bwams_reader_open_device2(const char *path, int device, int64_t chunk_bases, int32_t paired, int64_t buffer_bytes,
+                              int32_t n_buffers, uint32_t flags, bwams_reader_t **out);
 typedef struct bwams_reader_stats {
-    int32_t device_inflate;                      /* 1: BGZF on the GPU; 0: zlib on the reader's thread */
+    int32_t device_inflate;                      /* 1: BGZF on the GPU; 2: plain gzip on the GPU; 0: zlib on the reader's thread */
     int64_t in_bytes, out_bytes;                 /* file bytes read so far, text bytes inflated so far */
     float ms_read, ms_inflate;                   /* reader thread: read(2) (device path only), inflate */
 } bwams_reader_stats_t;
