@@ -31,6 +31,7 @@ SYMBOLS = [
     "bwams_seed_upload", "bwams_seed_run", "bwams_seed_counts", "bwams_seed_fetch",
     "bwams_ert_from_host", "bwams_ert_open", "bwams_ert_close", "bwams_ert_bytes", "bwams_ert_set_fat", "bwams_seed_run_ert",
     "bwams_ert_build", "bwams_ert_info", "bwams_ert_fetch", "bwams_ert_save", "bwams_debug_sort", "bwams_debug_regs_upload", "bwams_debug_aln_lists",
+    "bwams_debug_ext_regs_upload", "bwams_debug_dedup_counts",
     "bwams_emf_build", "bwams_emf_info", "bwams_emf_table_fetch", "bwams_emf_save",
     "bwams_bsw_extend", "bwams_bsw_upload", "bwams_bsw_run", "bwams_bsw_fetch",
     "bwams_batch_stats", "bwams_batch_sync", "bwams_ksw_align",
@@ -639,6 +640,8 @@ def lib():
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]
         L.bwams_debug_aln_lists.argtypes = [vp, vp]
+        L.bwams_debug_ext_regs_upload.argtypes = [vp, vp, i64, vp, i64]
+        L.bwams_debug_dedup_counts.argtypes = [vp, vp]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
         L.bwams_index_set_fma.argtypes = [vp, vp, C.c_int, vp, C.c_int]
         L.bwams_index_fetch_fma.argtypes = [vp, vp, vp]
@@ -1213,6 +1216,21 @@ class Batch:
         reg_off = np.ascontiguousarray(reg_off, np.int64)
         _chk(lib().bwams_debug_regs_upload(self.h, _p(regs), len(regs), _p(reg_off), len(reg_off) - 1), "bwams_debug_regs_upload")
         self._n_final = len(regs)
+
+    DEDUP_COUNTS = ("triage", "lane", "wave128", "wave512", "wave2048", "one_lane", "shortcut", "hbm", "lds", "reg1", "reg2", "reg3", "reg4", "early")
+
+    def debug_ext_regs_upload(self, regs, reg_off):
+        """Test hook: regs (ALNREG_DTYPE, a read's slots grouped through reg_off) become the regions dedup_run runs on."""
+        regs = np.ascontiguousarray(regs, ALNREG_DTYPE)
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        _chk(lib().bwams_debug_ext_regs_upload(self.h, _p(regs), len(regs), _p(reg_off), len(reg_off) - 1), "bwams_debug_ext_regs_upload")
+
+    def debug_dedup_counts(self):
+        """Test hook: what the last dedup_run under BWAMS_DEDUP_COUNT=1 did, as a dict over DEDUP_COUNTS (reads per tier, patch
+        alignments per variant, early exits)."""
+        cnt = np.zeros(len(self.DEDUP_COUNTS), np.int64)
+        _chk(lib().bwams_debug_dedup_counts(self.h, _p(cnt)), "bwams_debug_dedup_counts")
+        return dict(zip(self.DEDUP_COUNTS, cnt.tolist()))
 
     def debug_aln_lists(self):
         """Test hook: regions per launch of the last reg2aln (ring, wave 1, wave 2 with the requeued ones, row in global memory)."""

@@ -29,6 +29,7 @@ void knobs_reload() {
     k.ext_max_rounds = env_int("BWAMS_EXT_MAX_ROUNDS", 0); k.ext_all_rounds = getenv("BWAMS_EXT_ALL_ROUNDS") != nullptr;
     k.ext_inplace = env_int("BWAMS_EXT_INPLACE", 1);
     k.dedup_seq = env_int("BWAMS_DEDUP_SEQ", 0) == 1;
+    k.dedup_count = env_int("BWAMS_DEDUP_COUNT", 0) == 1;
     k.pair_drop_plan = getenv("BWAMS_PAIR_DROP_PLAN") != nullptr;
     k.trace_pair = env_int("BWAMS_TRACE_PAIR", 0);
     k.bsw_pk = env_int("BWAMS_BSW_PK", 1);

@@ -1,6 +1,7 @@
 // api_regions.hip — C-ABI entry points of the stages that finish a chunk's regions (include/bwams.h): bwams_dedup_*
 // (mem_sort_dedup_patch), bwams_pair_* (mate rescue, mem_mark_primary_se, mem_pair), bwams_emf_regs_* (mem_perfect2reg and its
-// merge), bwams_pestat* (mem_pestat) and the test hook bwams_debug_sort, over dedup.hip, pair.hip, ksw_local.hip and emf_regs.hip.
+// merge), bwams_pestat* (mem_pestat) and the test hooks bwams_debug_sort, bwams_debug_ext_regs_upload and
+// bwams_debug_dedup_counts, over dedup.hip, pair.hip, ksw_local.hip and emf_regs.hip.
 // No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <algorithm>
 #include <cmath>
@@ -51,6 +52,13 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
     const bool verbose_dd = knobs().verbose != 0;
     D.dbg = verbose_dd ? b->d_ctr.p->dbg : nullptr;
     if (verbose_dd) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg, 0, sizeof b->d_ctr.p->dbg, st));
+    const bool count_dd = knobs().dedup_count != 0;       // tests: reads per tier, patch alignments per variant (bwams_debug_dedup_counts)
+    if (count_dd) {
+        BWAMS_HIP(s->dd.cnt.ensure_n((size_t)kDedupCounts));
+        BWAMS_HIP(hipMemsetAsync(s->dd.cnt.p, 0, kDedupCounts * sizeof(unsigned long long), st));
+    }
+    D.cnt = count_dd ? s->dd.cnt.p : nullptr;
+    s->dd.counted = false;
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->dedup_heavy, 0, 3 * sizeof(unsigned long long), st));
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->dedup_ticket2, 0, 2 * sizeof(unsigned long long), st));
     BWAMS_HIP(hipEventRecord(s->ev[12], st));
@@ -72,8 +80,12 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
     }
     BWAMS_HIP(hipEventRecord(s->ev[13], st));
     if (verbose_dd) BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p->dbg, b->d_ctr.p->dbg, sizeof b->d_ctr.p->dbg, hipMemcpyDeviceToHost, st));
+    unsigned long long cnt_dd[kDedupCounts] = {};
+    if (count_dd) BWAMS_HIP(hipMemcpyAsync(cnt_dd, s->dd.cnt.p, sizeof cnt_dd, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
+    for (int i = 0; i < kDedupCounts; ++i) s->dd.counts[i] = (int64_t)cnt_dd[i];
+    s->dd.counted = count_dd;
     if (verbose_dd) {
         const unsigned long long *d = b->h_ctr.p->dbg;
         fprintf(stderr, "[bwams_dedup_run] largest wave instance: %llu reads, %llu slots, %llu alive; Mcycles: load %.1f sort(end) %.1f pairs %.1f reload %.1f sort(score) %.1f store %.1f; "
@@ -99,6 +111,76 @@ int bwams_dedup_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, i
     if (s->dd.n_final) BWAMS_HIP(hipMemcpyAsync(regs, s->dd.out.p, (size_t)s->dd.n_final * sizeof(bwams_alnreg_t), hipMemcpyDeviceToHost, st));
     if (reg_off) BWAMS_HIP(hipMemcpyAsync(reg_off, s->dd.off.p, (size_t)(s->ch.nseq + 1) * 8, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
+    return BWAMS_OK;
+}
+
+/* Test hook: what the last bwams_dedup_run counted (include/bwams.h). */
+int bwams_debug_dedup_counts(bwams_batch_t *b, int64_t counts[14]) {
+    static_assert(kDedupCounts == 14, "include/bwams.h documents 14 counters");
+    if (!b || !counts || !b->stages || !b->stages->dd.done || !b->stages->dd.counted) {
+        set_last_error("bwams_debug_dedup_counts: no bwams_dedup_run with BWAMS_DEDUP_COUNT=1 on this batch");
+        return BWAMS_ERR_ARG;
+    }
+    for (int i = 0; i < kDedupCounts; ++i) counts[i] = b->stages->dd.counts[i];
+    return BWAMS_OK;
+}
+
+/* Test hook: caller-given regions take the place of the extension stage's regions (include/bwams.h).  Refused: what would make a
+ * kernel read outside the reads or the text, and the values on which mem_patch_reg itself divides by zero or converts NaN to int. */
+int bwams_debug_ext_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
+    if (!b || n_regs < 0 || n_reads < 0 || !reg_off || (n_regs && !regs)) return BWAMS_ERR_ARG;
+    if (!b->d_cum.p || n_reads != b->nseq) {
+        set_last_error("bwams_debug_ext_regs_upload: n_reads is not the number of reads of the last bwams_seed_upload");
+        return BWAMS_ERR_ARG;
+    }
+    if (reg_off[0] != 0 || reg_off[n_reads] != n_regs) {
+        set_last_error("bwams_debug_ext_regs_upload: reg_off must run from 0 to n_regs");
+        return BWAMS_ERR_ARG;
+    }
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (reg_off[r + 1] < reg_off[r]) {
+            set_last_error("bwams_debug_ext_regs_upload: reg_off decreases at read " + std::to_string(r));
+            return BWAMS_ERR_ARG;
+        }
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t st = b->stream;
+    DevBns bns;
+    int rc = dev_bns(b->idx, &bns);
+    if (rc) return rc;
+    std::vector<int64_t> cum((size_t)n_reads + 1);
+    BWAMS_HIP(hipMemcpyAsync(cum.data(), b->d_cum.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const int64_t len = cum[(size_t)r + 1] - cum[(size_t)r];
+        for (int64_t k = reg_off[r]; k < reg_off[r + 1]; ++k) {
+            const bwams_alnreg_t &a = regs[k];
+            const char *why = nullptr;
+            if (a.rid < -1 || a.rid >= bns.n_seqs) why = " has rid outside [-1, number of sequences)";
+            else if (a.qe <= a.qb) continue;                   // a purged slot: dropped before anything reads it
+            else if (a.qb < 0 || a.qe > len) why = " has a query span outside its read";
+            else if (a.rb < 0 || a.re > 2 * bns.l_pac || a.re <= a.rb) why = " has a reference span that is empty or outside the text";
+            else if (a.score < 1) why = " has a score below 1";
+            if (why) {
+                set_last_error("bwams_debug_ext_regs_upload: region " + std::to_string(k) + why);
+                return BWAMS_ERR_ARG;
+            }
+        }
+    }
+    StageState *s;
+    if ((rc = get_state(b, &s))) return rc;
+    // the chains and seeds of an earlier run no longer belong to these regions: nothing may extend them again
+    outdated(s, From::chain); outdated(s, From::al); outdated(s, From::er); outdated(s, From::sam);
+    const int64_t n1 = n_reads + 1;
+    BWAMS_HIP(s->ext.regs.ensure_n((size_t)n_regs + 1)); BWAMS_HIP(s->ch.chain_off.ensure((size_t)n1 * 16));
+    BWAMS_HIP(s->ch.seeds.ensure_n((size_t)n_regs + 1));     // bwams_extend_fetch reads a word per region from here: zeros
+    BWAMS_HIP(hipMemsetAsync(s->ch.seeds.p, 0, ((size_t)n_regs + 1) * sizeof(bwams_chain_seed_t), st));
+    if (n_regs) BWAMS_HIP(hipMemcpyAsync(s->ext.regs.p, regs, (size_t)n_regs * sizeof(bwams_alnreg_t), hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemsetAsync(s->ch.chain_off.p, 0, (size_t)n1 * 8, st));
+    BWAMS_HIP(hipMemcpyAsync(s->ch.chain_off.as<int64_t>() + n1, reg_off, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    s->ch.n_chains = 0; s->ch.n_seeds = n_regs; s->ch.nseq = n_reads;
+    s->ext.n_left = s->ext.n_right = 0; s->ext.tasks_inplace = true;      // no task lists belong to these regions: bwams_extend_tasks_fetch refuses
+    s->ext.done = true;
     return BWAMS_OK;
 }
 
@@ -493,7 +575,7 @@ int bwams_debug_sort(bwams_index_t *ix, const int64_t *k, const int32_t *s, cons
             if (k[i] < 0 || k[i] >= (1 << 30)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(ix->device));
     if (which == 2 ? launch_flt_sort_test(k, n, mode, order_out) : launch_sort_test(k, s, q, n, which, mode, order_out)) {
-        set_last_error("bwams_debug_sort: n must be at most 1024");
+        set_last_error("bwams_debug_sort: n must be at most 2048 (which = 0, 1) or 1024 (which = 2)");
         return BWAMS_ERR_ARG;
     }
     return BWAMS_OK;

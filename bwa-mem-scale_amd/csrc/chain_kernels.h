@@ -144,14 +144,17 @@ struct DedupArgs {
     int32_t force_seq;             // debug: lane 0 runs the one-lane form for every read
     unsigned long long *ticket2, *ticket3;   // work cursors of the wave tier's smaller instances
     unsigned long long *dbg;       // BWAMS_VERBOSE: cycles per phase of the largest wave instance (8 words), else nullptr
+    unsigned long long *cnt;       // BWAMS_DEDUP_COUNT=1: kDedupCounts words, reads per tier and patch alignments per variant (bwams_debug_dedup_counts) through kernel
+                                   // instances of their own, else nullptr: a production launch holds no counting code
 };
+constexpr int kDedupCounts = 14;
 size_t dedup_sortrec_bytes(int64_t n);
 int launch_dedup(const DedupArgs &A, int64_t n_lanes, int64_t n_waves, int64_t n_waves_small, hipStream_t st, hipStream_t aux,
                  hipStream_t aux2, hipStream_t aux3, hipEvent_t fork, hipEvent_t join, hipEvent_t join2, hipEvent_t join3);
 void launch_pestat(const bwams_alnreg_t *regs, const int64_t *reg_off, int64_t n_pairs, int64_t l_pac, const bwams_mem_opt_t &opt,
                    unsigned long long *keys, hipStream_t st);
 void launch_dedup_gather(const DedupArgs &A, const int64_t *out_off, bwams_alnreg_t *out, hipStream_t st);
-// test hook (bwams_debug_sort, which = 0, 1): the wave tier's sort of n <= 1024 records on the current device
+// test hook (bwams_debug_sort, which = 0, 1): the wave tier's sort of n <= 2048 records (its LDS budget) on the current device
 int launch_sort_test(const int64_t *k, const int32_t *s, const int32_t *q, int n, int by_score, int mode, int32_t *order);
 
 // ---- regions of the reads the exact-match filter resolved (emf_regs.hip) ----

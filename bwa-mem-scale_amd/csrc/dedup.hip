@@ -21,6 +21,10 @@ constexpr int kLightN = 16;          // regions per read handled by a single lan
 constexpr int kSmallN = 128, kMidN = 512;      // regions per read of the wave tier's smaller instances
 constexpr int kLdsN = 2048;          // sort records a wavefront keeps in LDS (largest instance of the wave tier)
 constexpr int MINUS_INF = -0x40000000;
+// DedupArgs::cnt (bwams_debug_dedup_counts, include/bwams.h): reads finished per tier, patch alignments per variant
+enum { kCntTriage = 0, kCntLane, kCntWaveSmall, kCntWaveMid, kCntWaveLarge, kCntOneLane, kCntShortcut, kCntHbm, kCntLds, kCntReg1, kCntReg2, kCntReg3,
+       kCntReg4, kCntEarly };
+static_assert(kCntEarly + 1 == kDedupCounts, "one word per counter");
 constexpr int kEhLdsLen = 1000;      // reads up to this length align their patch candidates with the row in LDS (9 bytes per base)
 __host__ __device__ constexpr size_t dd_lds_bytes(int cap, int max_read_len) {
     return (size_t)60 * cap + (max_read_len <= kEhLdsLen ? (size_t)(max_read_len + 2) * 8 + (((size_t)max_read_len + 2 + 15) & ~(size_t)15) : 0);
@@ -262,9 +266,18 @@ __device__ __forceinline__ bool patch_geom(const bwams_mem_opt_t &opt, int64_t l
     return true;
 }
 
+// mem_patch_reg's predicted score of the merged pair from one side's spans (q_s, r_s: bwamem.cpp:236-237): the product is rounded before
+// .499 is added, as the reference's build does; one fused multiply-add is one off where the exact value is an integer
+// (tests/test_gpu_dedup_limits.py::test_rounding_edge)
+__device__ __forceinline__ int patch_pred(int64_t merged_span, int64_t span_sum, int score_sum) {
+#pragma clang fp contract(off)
+    return (int)((double)merged_span / (double)span_sum * (double)score_sum + .499);
+}
+
 // mem_patch_reg (bwamem.cpp:199-250): score of the merged alignment, or 0
-// WAVE: called by all 64 lanes with equal arguments, eh and qbuf in LDS
-template <bool WAVE>
+// WAVE: called by all 64 lanes with equal arguments, eh and qbuf in LDS; COUNT: A.cnt counts the alignment (tests: the production
+// instances hold no counting code)
+template <bool WAVE, bool COUNT>
 __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_alnreg_t &a, const bwams_alnreg_t &b, int *w_out, int2 *eh,
                          uint8_t *qbuf = nullptr, int lane = 0) {
     const bwams_mem_opt_t &opt = A.opt;
@@ -284,8 +297,10 @@ __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_a
         const uint8_t *qseq = rev ? query + a.qb + l_query - 1 : query + a.qb;
         const uint8_t *tseq = rev ? A.ref + rb + rlen - 1 : A.ref + rb;
         const int st = rev ? -1 : 1;
+        int route;
         if (l_query == rlen && w == 0) {
             for (int i = 0; i < l_query; ++i) score += opt.mat[tseq[(int64_t)st * i] * 5 + qseq[(int64_t)st * i]];
+            route = kCntShortcut;
         } else if (WAVE) {
             int max_ins = (int)((double)(((l_query + 1) >> 1) * opt.mat[0] - opt.o_ins) / opt.e_ins + 1.);
             int max_del = (int)((double)(((l_query + 1) >> 1) * opt.mat[0] - opt.o_del) / opt.e_del + 1.);
@@ -297,8 +312,8 @@ __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_a
             const int min_w = dl + 3;
             ww = ww > min_w ? ww : min_w;
             // what the pair must reach (the acceptance test below): lets the alignment stop once it cannot
-            const int q_s0 = (int)((double)(b.qe - a.qb) / (double)((b.qe - b.qb) + (a.qe - a.qb)) * (double)(b.score + a.score) + .499);
-            const int r_s0 = (int)((double)(b.re - a.rb) / (double)((b.re - b.rb) + (a.re - a.rb)) * (double)(b.score + a.score) + .499);
+            const int q_s0 = patch_pred(b.qe - a.qb, (b.qe - b.qb) + (a.qe - a.qb), b.score + a.score);
+            const int r_s0 = patch_pred(b.re - a.rb, (b.re - b.rb) + (a.re - a.rb), b.score + a.score);
             const int mx0 = q_s0 > r_s0 ? q_s0 : r_s0;
             int need = MINUS_INF;
             if (mx0 > 0) {
@@ -310,6 +325,7 @@ __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_a
             else if (l_query < 192) score = global_score_wave_reg<3>(opt, l_query, qseq, st, (int)rlen, tseq, st, ww, lane, need);
             else if (l_query < 256) score = global_score_wave_reg<4>(opt, l_query, qseq, st, (int)rlen, tseq, st, ww, lane, need);
             else score = global_score_wave(opt, l_query, qseq, st, (int)rlen, tseq, st, ww, eh, qbuf, lane);
+            route = l_query < 256 ? kCntReg1 + (l_query >> 6) : kCntLds;
         } else {
             int max_ins = (int)((double)(((l_query + 1) >> 1) * opt.mat[0] - opt.o_ins) / opt.e_ins + 1.);
             int max_del = (int)((double)(((l_query + 1) >> 1) * opt.mat[0] - opt.o_del) / opt.e_del + 1.);
@@ -321,16 +337,24 @@ __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_a
             const int min_w = dl + 3;
             ww = ww > min_w ? ww : min_w;
             score = global_score(opt, l_query, qseq, st, (int)rlen, tseq, st, ww, eh);
+            route = kCntHbm;
+        }
+        if (COUNT && lane == 0) {
+            atomicAdd(&A.cnt[route], 1ull);
+            // global_score_wave_reg gave up.  A finished alignment never returns this value: the band is at least dl + 3, so the last
+            // cell lies inside it and holds a reachable score (the tests pin it: no early exit is counted under BWAMS_DEDUP_SEQ=1)
+            if (score == MINUS_INF) atomicAdd(&A.cnt[kCntEarly], 1ull);
         }
     }
-    const int q_s = (int)((double)(b.qe - a.qb) / (double)((b.qe - b.qb) + (a.qe - a.qb)) * (double)(b.score + a.score) + .499);
-    const int r_s = (int)((double)(b.re - a.rb) / (double)((b.re - b.rb) + (a.re - a.rb)) * (double)(b.score + a.score) + .499);
+    const int q_s = patch_pred(b.qe - a.qb, (b.qe - b.qb) + (a.qe - a.qb), b.score + a.score);
+    const int r_s = patch_pred(b.re - a.rb, (b.re - b.rb) + (a.re - a.rb), b.score + a.score);
     if ((double)score / (double)(q_s > r_s ? q_s : r_s) < (double)0.90f) return 0;
     *w_out = w;
     return score;
 }
 
 // The whole per-read procedure, run by one lane.  srt: room for the read's sort records (HBM strip or LDS).
+template <bool COUNT>
 __device__ int dedup_read(const DedupArgs &A, int64_t r, SortRec *srt, int2 *eh) {
     const int64_t reg0 = A.seed_off[r];
     const int av_n = (int)(A.seed_off[r + 1] - reg0);
@@ -360,7 +384,7 @@ __device__ int dedup_read(const DedupArgs &A, int64_t r, SortRec *srt, int2 *eh)
                 if ((float)or_ > A.opt.mask_level_redun * (float)mr && (float)oq > A.opt.mask_level_redun * (float)mq) {
                     if (p->score < q->score) { p->qe = p->qb; break; }
                     else q->qe = q->qb;
-                } else if (q->rb < p->rb && (score = patch_reg<false>(A, query, *q, *p, &w, eh)) > 0) {
+                } else if (q->rb < p->rb && (score = patch_reg<false, COUNT>(A, query, *q, *p, &w, eh)) > 0) {
                     p->n_comp_is_alt = (p->n_comp_is_alt + q->n_comp_is_alt + 1) & 0x3fffffff;
                     p->seedcov = p->seedcov > q->seedcov ? p->seedcov : q->seedcov;
                     p->sub = p->sub > q->sub ? p->sub : q->sub;
@@ -402,6 +426,7 @@ __device__ int dedup_read(const DedupArgs &A, int64_t r, SortRec *srt, int2 *eh)
 
 // lane per read: reads left with at most one region are finished here; the others are listed for the
 // lane tier (few regions) or the wave tier (many)
+template <bool COUNT>
 __global__ void dedup_triage_kernel(DedupArgs A) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= A.nseq) return;
@@ -417,6 +442,7 @@ __global__ void dedup_triage_kernel(DedupArgs A) {
             if (a[last].rid >= 0 && A.bns.contigs[a[last].rid].is_alt) a[last].n_comp_is_alt = (a[last].n_comp_is_alt & 0x3fffffff) | (1 << 30);
         }
         A.n_out[r] = n;
+        if (COUNT) atomicAdd(&A.cnt[kCntTriage], 1ull);
         return;
     }
     if (av_n > kLightN) A.heavy[atomicAdd(A.n_heavy_ctr, 1ull)] = (int32_t)r;
@@ -424,6 +450,7 @@ __global__ void dedup_triage_kernel(DedupArgs A) {
 }
 
 // lane tier: one lane per listed read (each lane owns a strip for the global alignment)
+template <bool COUNT>
 __global__ __launch_bounds__(64) void dedup_kernel(DedupArgs A, int64_t n_lanes) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_lanes) return;
@@ -431,7 +458,8 @@ __global__ __launch_bounds__(64) void dedup_kernel(DedupArgs A, int64_t n_lanes)
     const int64_t n_light = (int64_t)*A.n_light_ctr;
     for (int64_t t = g; t < n_light; t += n_lanes) {
         const int64_t r = A.light[t];
-        A.n_out[r] = dedup_read(A, r, reinterpret_cast<SortRec *>(A.srt) + A.seed_off[r], eh);
+        A.n_out[r] = dedup_read<COUNT>(A, r, reinterpret_cast<SortRec *>(A.srt) + A.seed_off[r], eh);
+        if (COUNT) atomicAdd(&A.cnt[kCntLane], 1ull);
     }
 }
 
@@ -469,7 +497,7 @@ __device__ __forceinline__ int wave_compact_alive(const bwams_alnreg_t *a, int32
 // LO < regions <= CAP for (32, 128] (7.7 KB per wave, ~20 waves per CU), (128, 512] (30 KB, five per CU) and
 // (512, 2048] (120 KB, one per CU; 355 reads per million on the bench workload).  One 1024-region instance left two waves
 // per CU for every heavy read, and the four reads beyond it sorted 1100 records through HBM on a single lane: 14.9 ms.
-template <int CAP, int LO>
+template <int CAP, int LO, bool COUNT>
 __global__ __launch_bounds__(64) void dedup_wave_kernel(DedupArgs A, int64_t n_waves, int64_t eh_base, unsigned long long *ticket) {
     extern __shared__ __align__(16) unsigned char lds_dd[];
     SortRec *l_srt = reinterpret_cast<SortRec *>(lds_dd), *l_srt2 = l_srt + CAP;
@@ -494,9 +522,13 @@ __global__ __launch_bounds__(64) void dedup_wave_kernel(DedupArgs A, int64_t n_w
         const uint8_t *query = A.enc + A.cum[r];
         __syncthreads();
         if (av_n > kLdsN || A.force_seq == 1) {                              // beyond the LDS budget: the one-lane form
-            if (lane == 0) A.n_out[r] = dedup_read(A, r, reinterpret_cast<SortRec *>(A.srt) + reg0, eh);
+            if (lane == 0) {
+                A.n_out[r] = dedup_read<COUNT>(A, r, reinterpret_cast<SortRec *>(A.srt) + reg0, eh);
+                if (COUNT) atomicAdd(&A.cnt[kCntOneLane], 1ull);
+            }
             continue;
         }
+        if (COUNT && lane == 0) atomicAdd(&A.cnt[CAP == kSmallN ? kCntWaveSmall : CAP == kMidN ? kCntWaveMid : kCntWaveLarge], 1ull);
         const bool prof = CAP == kLdsN && A.dbg != nullptr;
         unsigned long long n_al = 0, t_al = 0, n_it = 0;       // patch alignments of the read, their time, scan trips (diagnostics)
         unsigned long long tk0 = prof ? wall_clock64() : 0ull, tk1 = tk0, tk2 = tk0, tk3 = tk0, tk4 = tk0, tk5 = tk0;
@@ -584,8 +616,8 @@ __global__ __launch_bounds__(64) void dedup_wave_kernel(DedupArgs A, int64_t n_w
                         const unsigned long long ta0 = prof ? wall_clock64() : 0ull;
                         if (lds_eh) {
                             const bwams_alnreg_t qa = *qq, pa = *pp;       // written through by lane 0 only, read back behind a barrier
-                            score = patch_reg<true>(A, query, qa, pa, &w, lds_eh, lds_q, lane);
-                        } else if (lane == 0) score = patch_reg<false>(A, query, *qq, *pp, &w, eh);
+                            score = patch_reg<true, COUNT>(A, query, qa, pa, &w, lds_eh, lds_q, lane);
+                        } else if (lane == 0) score = patch_reg<false, COUNT>(A, query, *qq, *pp, &w, eh);
                         if (prof) { t_al += wall_clock64() - ta0; ++n_al; }
                         score = __builtin_amdgcn_readfirstlane(score);
                         w = __builtin_amdgcn_readfirstlane(w);
@@ -728,13 +760,15 @@ __global__ void pestat_kernel(const bwams_alnreg_t *__restrict__ regs, const int
 }
 
 constexpr int kTestN = 1024;
-// test hook: one wavefront sorts n records held in LDS, as the wave tier does (mode 0: rank sort, or beyond 96 records the bitonic
+// test hook: one wavefront sorts n records held in LDS (dynamic: two arrays of cap records, cap = kTestN, or kLdsN for the sizes only the
+// largest instance of the wave tier takes), as the wave tier does (mode 0: rank sort, or beyond 96 records the bitonic
 // network, with the exact fallback on ties, 1: the operation-exact wave introsort always, 2: lane 0 alone through sort_records on a copy in GLOBAL memory — the
 // sequential statement of the same sort; 3 / 4: modes 1 / 2 with a depth budget of 2, so that the comb-sort fallback
 // (wave_ks_combsort / ks_combsort) sorts nearly everything)
 __global__ __launch_bounds__(64) void sort_test_kernel(const SortRec *__restrict__ in, int n, int by_score, int mode, int32_t *__restrict__ order,
-                                                       SortRec *__restrict__ scratch) {
-    __shared__ SortRec l_a[kTestN], l_t[kTestN];
+                                                       SortRec *__restrict__ scratch, int cap) {
+    extern __shared__ __align__(16) unsigned char lds_dd[];
+    SortRec *l_a = reinterpret_cast<SortRec *>(lds_dd), *l_t = l_a + cap;
     const int lane = threadIdx.x;
     if (mode == 2 || mode == 4) {
         for (int i = lane; i < n; i += 64) scratch[i] = in[i];
@@ -746,14 +780,16 @@ __global__ __launch_bounds__(64) void sort_test_kernel(const SortRec *__restrict
     }
     for (int i = lane; i < n; i += 64) l_a[i] = in[i];
     __syncthreads();
-    wave_sort_records(l_a, l_t, n, by_score, lane, mode == 1 || mode == 3, mode == 3 ? 2 : 0, kTestN);
+    wave_sort_records(l_a, l_t, n, by_score, lane, mode == 1 || mode == 3, mode == 3 ? 2 : 0, cap);
     for (int i = lane; i < n; i += 64) order[i] = l_a[i].idx;
 }
 
 }  // namespace
 
 int launch_sort_test(const int64_t *k, const int32_t *s_, const int32_t *q, int n, int by_score, int mode, int32_t *order) {
-    if (n < 0 || n > kTestN) return -1;
+    if (n < 0 || n > kLdsN) return -1;
+    const int cap = n > kTestN ? kLdsN : kTestN;
+    const size_t lds = 2 * (size_t)cap * sizeof(SortRec);
     SortRec *h = (SortRec *)malloc(sizeof(SortRec) * (size_t)(n + 1));
     for (int i = 0; i < n; ++i) { h[i].k = k[i]; h[i].s = s_[i]; h[i].q = q[i]; h[i].idx = i; h[i].pad_ = 0; }
     int rc = -1;
@@ -762,8 +798,10 @@ int launch_sort_test(const int64_t *k, const int32_t *s_, const int32_t *q, int 
         DevBuf<int32_t> d_ord;
         if (d_in.alloc(sizeof(SortRec) * (size_t)(n + 1)) == hipSuccess && d_ord.alloc(4 * (size_t)(n + 1)) == hipSuccess &&
             d_scr.alloc(sizeof(SortRec) * (size_t)(n + 1)) == hipSuccess &&
-            hipMemcpy(d_in.p, h, sizeof(SortRec) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
-            sort_test_kernel<<<1, 64>>>(d_in.p, n, by_score, mode, d_ord.p, d_scr.p);
+            hipMemcpy(d_in.p, h, sizeof(SortRec) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+            // beyond 64 KB of dynamic LDS a kernel needs the opt-in, as launch_dedup's largest instance does
+            hipFuncSetAttribute(reinterpret_cast<const void *>(sort_test_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) {
+            sort_test_kernel<<<1, 64, lds>>>(d_in.p, n, by_score, mode, d_ord.p, d_scr.p, cap);
             if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(order, d_ord.p, 4 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
         }
     }
@@ -780,25 +818,32 @@ void launch_pestat(const bwams_alnreg_t *regs, const int64_t *reg_off, int64_t n
 size_t dedup_sortrec_bytes(int64_t n) { return (size_t)(n + 1) * sizeof(SortRec); }
 
 // triage, then the lane tier and the wave tier side by side (they work on disjoint reads)
-int launch_dedup(const DedupArgs &A, int64_t n_lanes, int64_t n_waves, int64_t n_waves_small, hipStream_t st, hipStream_t aux,
+// COUNT: the instances that count into A.cnt (bwams_debug_dedup_counts); a production launch runs the ones without any counting code
+template <bool COUNT>
+static int launch_dedup_t(const DedupArgs &A, int64_t n_lanes, int64_t n_waves, int64_t n_waves_small, hipStream_t st, hipStream_t aux,
                  hipStream_t aux2, hipStream_t aux3, hipEvent_t fork, hipEvent_t join, hipEvent_t join2, hipEvent_t join3) {
     if (A.nseq <= 0) return 0;
-    dedup_triage_kernel<<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A);
+    dedup_triage_kernel<COUNT><<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A);
     if (hipEventRecord(fork, st) != hipSuccess || hipStreamWaitEvent(aux, fork, 0) != hipSuccess) return -1;
     // the reads with the most regions first (one wave per CU), the bulk beside them on the auxiliary streams
     // the 120 KB of dynamic LDS of the largest instance need the opt-in on EVERY device a batch runs on (the attribute belongs to the
     // device that is current when it is set); cheap enough to repeat per launch, and checked
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(dedup_wave_kernel<kLdsN, kMidN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dd_lds_bytes(kLdsN, A.max_read_len)) != hipSuccess) return -1;
-    dedup_wave_kernel<kLdsN, kMidN><<<(unsigned)n_waves, 64, dd_lds_bytes(kLdsN, A.max_read_len), st>>>(A, n_waves, A.eh_lanes, A.ticket);
-    dedup_kernel<<<(unsigned)((n_lanes + 63) / 64), 64, 0, aux>>>(A, n_lanes);
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(dedup_wave_kernel<kLdsN, kMidN, COUNT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dd_lds_bytes(kLdsN, A.max_read_len)) != hipSuccess) return -1;
+    dedup_wave_kernel<kLdsN, kMidN, COUNT><<<(unsigned)n_waves, 64, dd_lds_bytes(kLdsN, A.max_read_len), st>>>(A, n_waves, A.eh_lanes, A.ticket);
+    dedup_kernel<COUNT><<<(unsigned)((n_lanes + 63) / 64), 64, 0, aux>>>(A, n_lanes);
     if (hipEventRecord(join, aux) != hipSuccess || hipStreamWaitEvent(st, join, 0) != hipSuccess) return -1;
     if (hipStreamWaitEvent(aux3, fork, 0) != hipSuccess) return -1;
-    dedup_wave_kernel<kMidN, kSmallN><<<(unsigned)n_waves, 64, dd_lds_bytes(kMidN, A.max_read_len), aux3>>>(A, n_waves, A.eh_lanes + n_waves, A.ticket3);
+    dedup_wave_kernel<kMidN, kSmallN, COUNT><<<(unsigned)n_waves, 64, dd_lds_bytes(kMidN, A.max_read_len), aux3>>>(A, n_waves, A.eh_lanes + n_waves, A.ticket3);
     if (hipEventRecord(join3, aux3) != hipSuccess || hipStreamWaitEvent(st, join3, 0) != hipSuccess) return -1;
     if (hipStreamWaitEvent(aux2, fork, 0) != hipSuccess) return -1;
-    dedup_wave_kernel<kSmallN, kLightN><<<(unsigned)n_waves_small, 64, dd_lds_bytes(kSmallN, A.max_read_len), aux2>>>(A, n_waves_small, A.eh_lanes + 2 * n_waves, A.ticket2);
+    dedup_wave_kernel<kSmallN, kLightN, COUNT><<<(unsigned)n_waves_small, 64, dd_lds_bytes(kSmallN, A.max_read_len), aux2>>>(A, n_waves_small, A.eh_lanes + 2 * n_waves, A.ticket2);
     if (hipEventRecord(join2, aux2) != hipSuccess || hipStreamWaitEvent(st, join2, 0) != hipSuccess) return -1;
     return 0;
+}
+int launch_dedup(const DedupArgs &A, int64_t n_lanes, int64_t n_waves, int64_t n_waves_small, hipStream_t st, hipStream_t aux,
+                 hipStream_t aux2, hipStream_t aux3, hipEvent_t fork, hipEvent_t join, hipEvent_t join2, hipEvent_t join3) {
+    return A.cnt ? launch_dedup_t<true>(A, n_lanes, n_waves, n_waves_small, st, aux, aux2, aux3, fork, join, join2, join3)
+                 : launch_dedup_t<false>(A, n_lanes, n_waves, n_waves_small, st, aux, aux2, aux3, fork, join, join2, join3);
 }
 void launch_dedup_gather(const DedupArgs &A, const int64_t *out_off, bwams_alnreg_t *out, hipStream_t st) {
     if (A.nseq <= 0) return;

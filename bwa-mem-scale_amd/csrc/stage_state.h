@@ -40,7 +40,9 @@ struct StageState {
         DevBuf<> eh;                         // int2 (h, e) rows: lanes and waves x (longest read + 2)
         DevBuf<> wide;                       // 2 int64 rows of nseq + 1 (widen2), the first scanned
         DevBuf<int64_t> off; DevBuf<unsigned long long> pe_keys, pe_keys2;
-        int64_t n_final = 0; bool done = false;
+        DevBuf<unsigned long long> cnt;      // kDedupCounts words, written only when a run counts (BWAMS_DEDUP_COUNT=1)
+        int64_t counts[kDedupCounts] = {};   // ... of the last run
+        int64_t n_final = 0; bool done = false, counted = false;
     } dd;
     struct PairStage {                       // mate rescue + mem_mark_primary_se + mem_pair
         DevBuf<int32_t> na, anchor, slot, task, tl1, ord, z, nfin, npri, nsw; DevBuf<int64_t> wide, trb, owide, ooff;

@@ -50,7 +50,9 @@ const char *bwams_last_error(void);
  *     leaves its lane (entries at the forward end; columns run and entries alive; the same once the read queue is dry; MIN_LIST=0: never)
  *   BWAMS_SEED_R3_BESIDE=0 (SMEM round 3 behind round 2 instead of beside it), BWAMS_DEBUG (SMEM search ablations)
  *   BWAMS_EXT_MAX_ROUNDS, BWAMS_EXT_ALL_ROUNDS, BWAMS_EXT_INPLACE=0, BWAMS_BSW_PK=0, BWAMS_CHAIN_BATCH=0   extension rounds and kernel variants
- *   BWAMS_DEDUP_SEQ=1, BWAMS_PAIR_DROP_PLAN, BWAMS_TRACE_PAIR   fallback paths forced by tests; a line per launch of the paired-end tail
+ *   BWAMS_DEDUP_SEQ=1, BWAMS_PAIR_DROP_PLAN, BWAMS_TRACE_PAIR   fallback paths forced by tests (tests/test_gpu_dedup_limits.py runs its batches under
+ *     BWAMS_DEDUP_SEQ=1 as well); a line per launch of the paired-end tail
+ *   BWAMS_DEDUP_COUNT=1   bwams_dedup_run counts its reads per tier and its patch alignments per variant (bwams_debug_dedup_counts)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
 int bwams_device_count(int *n);
@@ -541,7 +543,8 @@ int bwams_ksw_align(bwams_batch_t *b, const bwams_seqpair_t *pairs, int64_t n,
                     const bwams_sw_opt_t *opt, bwams_kswr_t *out);
 
 /* Test hook (not part of the drop-in surface): the device sorts (ksort.h's introsort, csrc/ksort.h) as the wave tiers run
- * them, on caller-given keys of n <= 1024 records; order_out[i] = index of the i-th record after the sort.  which: 0 = mem_ars2
+ * them, on caller-given keys of n <= 2048 records (which = 0, 1: what the largest instance of de-duplication's wave tier keeps in
+ * LDS) or n <= 1024 (which = 2); order_out[i] = index of the i-th record after the sort.  which: 0 = mem_ars2
  * (key k = re), 1 = mem_ars (s = score descending, k = rb, q = qb), both as the de-duplication kernel's wave tier sorts; 2 =
  * the chain filter's order (k = weight in [0, 2^30), descending; s and q ignored) as the many-chain reads are sorted.  mode: 0
  * = as the kernels choose (which 0, 1: rank sort, operation-exact introsort when keys tie; which 2 has no such shortcut: as
@@ -560,6 +563,29 @@ int bwams_debug_sort(bwams_index_t *idx, const int64_t *k, const int32_t *s, con
  * or when a region has qb < 0, qe beyond its read or qb > qe (a kernel would read outside the reads).  The reference side
  * (rb, re) and every other field go through untouched: what mem_reg2aln / bwa_gen_cigar2 reject becomes the unmapped record. */
 int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads);
+
+/* Test hook (not part of the drop-in surface): caller-given regions take the place of the batch's regions of the extension
+ * stage, in front of de-duplication.  Called after bwams_seed_upload of the reads; bwams_dedup_run and bwams_dedup_fetch then run
+ * on these regions as on real ones.  The chains of an earlier run and everything downstream (final regions, pairing, alignment
+ * records, the EMF's regions, SAM text, BAM) count as outdated; of the extension's own results bwams_extend_fetch returns the
+ * uploaded regions with a seed_aln of zeros, and bwams_extend_tasks_fetch refuses (no task lists belong to them).  regs[reg_off[r] .. reg_off[r + 1]) are the slots of read r; a
+ * slot with qe <= qb is a purged one and passes as it is (qb = qe = -1 included).  Returns BWAMS_ERR_ARG, launches nothing and
+ * leaves the batch as it was when n_reads is not the uploaded read count, when reg_off does not run non-decreasing from 0 to
+ * n_regs, when a live region (qe > qb) has qb < 0, qe beyond its read, rb < 0, re > 2 l_pac, re <= rb or score < 1, or when any
+ * region has rid outside [-1, number of sequences).  Besides what would make a kernel read outside the reads or the text, the
+ * excluded values are those on which the reference itself divides by zero or converts NaN to int (mem_patch_reg's expected
+ * scores: a sum of two spans that is zero, a ratio against an expected score of zero). */
+int bwams_debug_ext_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads);
+
+/* Test hook (not part of the drop-in surface): what the last bwams_dedup_run on this batch did, when it ran with
+ * BWAMS_DEDUP_COUNT=1 (BWAMS_ERR_ARG otherwise; a run without the variable launches kernel instances that hold no counting code).
+ * Reads: counts[0] finished by the triage kernel (at most one live region), [1] by the lane tier (up to 16 slots), [2], [3],
+ * [4] by the wave tier's instances for (16, 128], (128, 512] and (512, 2048] slots across the wavefront, [5] by the one-lane
+ * form inside the wave kernels (more than 2048 slots, or BWAMS_DEDUP_SEQ=1).  Patch alignments (mem_patch_reg candidates that
+ * pass the coordinate tests): [6] the gap-free shortcut, [7] one lane with the row in global memory, [8] the wavefront with the
+ * row in LDS (queries of 256 bases and more), [9] .. [12] the wavefront with the row in registers, queries below 64, 128, 192
+ * and 256 bases; [13] how many of [9] .. [12] the early exit ended. */
+int bwams_debug_dedup_counts(bwams_batch_t *b, int64_t counts[14]);
 
 /* Test hook (not part of the drop-in surface): how many regions the last bwams_reg2aln_run gave to each of its four
  * dynamic-programming launches.  counts[0]: lane per region with a 32-column ring in LDS; counts[1]: wave per region, bands

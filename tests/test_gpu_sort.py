@@ -3,7 +3,8 @@
 stable, so on tied keys only the same sequence of comparisons and swaps gives the reference's order.  Checked against
 the reference's own ks_introsort (oracle/_ref/libref_chain.so when present, else the restatement pinned to it) on inputs
 with heavy ties, including every small size (the six-record case of profiles/r01_notes.md item 20 among them), sorted /
-reversed / organ-pipe inputs that reach the comb-sort depth fallback, and sizes up to the LDS limit."""
+reversed / organ-pipe inputs that reach the comb-sort depth fallback, and sizes up to the LDS limit of the largest instance
+of de-duplication's wave tier (2048 records)."""
 import numpy as np
 import pytest
 
@@ -55,6 +56,25 @@ def test_wave_tier_sorts_equal_ksort(ix):
                 assert np.array_equal(got, want), (len(k), which, mode, k[:12], got[:12], want[:12])
             n_tied += len(k) > len(np.unique(k))
     assert n_tied > 100
+
+
+def test_largest_instance_sizes(ix):
+    """1025 to 2048 records — what only the largest instance of de-duplication's wave tier sorts, two arrays of 2048 records in
+    dynamic LDS: hardly any tie, keys that tie by the hundred, keys that are all equal; both orders, the three modes."""
+    L = loader.ref_chain_lib()
+    rng = np.random.default_rng(13)
+    for n in (1025, 1537, 2047, 2048):
+        for spread in (1 << 20, max(n // 100, 2), 1):
+            k = rng.integers(0, spread, size=n)
+            s = rng.integers(0, spread, size=n) if spread > 1 else np.zeros(n, np.int64)
+            q = rng.integers(0, 2 if spread > 1 else 1, size=n)
+            for which in (0, 1):
+                want = _want(which, k, s, q, L)
+                for mode in (0, 1, 2):
+                    got = ix.debug_sort(k, s, q, which, mode)
+                    assert np.array_equal(got, want), (n, spread, which, mode, got[:12], want[:12])
+    with pytest.raises(capi.BwamsError):
+        ix.debug_sort(np.zeros(2049, np.int64), np.zeros(2049, np.int64), np.zeros(2049, np.int64), 0, 0)
 
 
 def test_chain_filter_sort_equals_ksort(ix):
