@@ -52,6 +52,9 @@ SYMBOLS = [
     "bwams_bam_upload", "bwams_bam_sort", "bwams_bam_sorted_fetch",
     "bwams_sorter_open", "bwams_sorter_put", "bwams_sorter_put_batch", "bwams_sorter_close", "bwams_sorter_close2",
     "bwams_bam_templates", "bwams_bam_templates_fetch", "bwams_dup_decide", "bwams_bam_markdup",
+    "bwams_dup_groups_create", "bwams_dup_groups_info", "bwams_dup_groups_library", "bwams_dup_groups_destroy",
+    "bwams_bam_templates2", "bwams_bam_templates_fetch_loc", "bwams_bam_lib_record_counts", "bwams_dup_decide2", "bwams_bam_markdup2",
+    "bwams_dup_library_size", "bwams_dup_metrics_text", "bwams_sorter_set_markdup", "bwams_sorter_close3",
     "bwams_bam_reads_decode", "bwams_bam_reads_info", "bwams_process_chunk_bam", "bwams_process_chunk_bam_smart",
     "bwams_reader_open_bam", "bwams_reader_bam_header",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
@@ -87,6 +90,11 @@ BAM_COORD_DTYPE = np.dtype([("key", "<u8"), ("end", "<i4"), ("size", "<i4")])   
 DUP_END_DTYPE = np.dtype([("tmpl", "<i8"), ("ref1", "<i4"), ("pos1", "<i4"), ("ref2", "<i4"), ("pos2", "<i4"), ("score", "<i4"),
                           ("strands", "<i4")])                                    # bwams_dup_end_t
 assert DUP_END_DTYPE.itemsize == 32
+DUP_LOC_DTYPE = np.dtype([(n, "<i4") for n in ("lib", "rg", "tile", "x", "y", "has")])                      # bwams_dup_loc_t
+DUP_LIB_STATS_DTYPE = np.dtype([(n, "<i8") for n in ("unpaired_examined", "pairs_examined", "secondary_or_supplementary", "unmapped",
+                                                     "unpaired_duplicates", "pair_duplicates", "pair_optical_duplicates",
+                                                     "estimated_library_size")] + [("percent_duplication", "<f8")])   # bwams_dup_lib_stats_t
+assert DUP_LOC_DTYPE.itemsize == 24 and DUP_LIB_STATS_DTYPE.itemsize == 72
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
 
@@ -344,6 +352,89 @@ def dup_decide(device: int, ends, n_templates: int):
     return dup[:n_templates], st
 
 
+class DupOpt(C.Structure):
+    """bwams_dup_opt_t: optical_distance 0 turns optical duplicate detection off; max_optical_set 0 means 300000."""
+    _fields_ = [("optical_distance", C.c_int32), ("pad_", C.c_int32), ("max_optical_set", C.c_int64)]
+
+
+class DupGroups:
+    """The read groups and libraries of SAM header text (bwams_dup_groups_t, rule 9 of duplicate marking)."""
+
+    def __init__(self, header_text):
+        text = header_text.encode() if isinstance(header_text, str) else bytes(header_text)
+        self.h = C.c_void_p()
+        _chk(lib().bwams_dup_groups_create(text, len(text), C.byref(self.h)), "bwams_dup_groups_create")
+        n_rg, n_lib = C.c_int64(0), C.c_int64(0)
+        _chk(lib().bwams_dup_groups_info(self.h, C.byref(n_rg), C.byref(n_lib)), "bwams_dup_groups_info")
+        self.n_rg, self.n_lib = n_rg.value, n_lib.value
+
+    def library(self, k: int):
+        name = lib().bwams_dup_groups_library(self.h, k)
+        return None if name is None else name.decode("latin-1")
+
+    @property
+    def libraries(self) -> list:
+        return [self.library(k) for k in range(self.n_lib)]
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            lib().bwams_dup_groups_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _groups_h(groups):
+    return groups.h if groups is not None else None
+
+
+def _dup_opt(distance: int, max_set: int):
+    return DupOpt(distance, 0, max_set)
+
+
+def lib_rows(lib_stats) -> list:
+    """DUP_LIB_STATS_DTYPE rows as the dicts bwams.markdup's decide2 / mark2 give"""
+    return [{k: (float(r[k]) if k == "percent_duplication" else int(r[k])) for k in DUP_LIB_STATS_DTYPE.names} for r in lib_stats]
+
+
+def dup_decide2(device: int, ends, locs, n_templates: int, n_lib: int = 1, distance: int = 0, max_set: int = 0, opt=True):
+    """bwams_dup_decide2 over ends (DUP_END_DTYPE) and locs (DUP_LOC_DTYPE, or None) -> (dup, optical: uint8 per template, rows:
+    DUP_LIB_STATS_DTYPE per library).  opt=False passes a NULL bwams_dup_opt_t."""
+    ends = np.ascontiguousarray(ends, DUP_END_DTYPE)
+    if locs is not None:
+        locs = np.ascontiguousarray(locs, DUP_LOC_DTYPE)
+        assert len(locs) == len(ends)
+    dup, optical = np.zeros(max(n_templates, 1), np.uint8), np.zeros(max(n_templates, 1), np.uint8)
+    rows = np.zeros(max(n_lib, 1), DUP_LIB_STATS_DTYPE)
+    o = _dup_opt(distance, max_set)
+    _chk(lib().bwams_dup_decide2(device, _p(ends), _p(locs) if locs is not None else None, len(ends), n_templates, n_lib,
+                                 C.byref(o) if opt else None, _p(dup), _p(optical), _p(rows)), "bwams_dup_decide2")
+    return dup[:n_templates], optical[:n_templates], rows[:n_lib]
+
+
+def dup_library_size(n: int, c: int):
+    """Rule 14 (bwams_dup_library_size): the estimate, or None."""
+    v = lib().bwams_dup_library_size(n, c)
+    return None if v < 0 else v
+
+
+def dup_metrics_text(groups, lib_stats, comment: str = "") -> str:
+    """Rule 15 (bwams_dup_metrics_text) of DUP_LIB_STATS_DTYPE rows."""
+    rows = np.ascontiguousarray(lib_stats, DUP_LIB_STATS_DTYPE)
+    n = C.c_int64(0)
+    rc = lib().bwams_dup_metrics_text(_groups_h(groups), _p(rows), len(rows), comment.encode(), None, 0, C.byref(n))
+    if rc != -4:
+        _chk(rc, "bwams_dup_metrics_text")
+    buf = C.create_string_buffer(max(n.value, 1))
+    _chk(lib().bwams_dup_metrics_text(_groups_h(groups), _p(rows), len(rows), comment.encode(), buf, n.value, C.byref(n)),
+         "bwams_dup_metrics_text")
+    return buf.raw[:n.value].decode("latin-1")
+
+
 class SorterStats(C.Structure):
     _fields_ = [("runs", C.c_int64), ("records", C.c_int64), ("spilled_runs", C.c_int64), ("spilled_bytes", C.c_int64),
                 ("out_bytes", C.c_int64), ("ms_merge", C.c_float), ("ms_deflate", C.c_float), ("ms_write", C.c_float)]
@@ -368,6 +459,22 @@ class Sorter:
 
     def put_batch(self, seq: int, batch: "Batch") -> None:
         _chk(lib().bwams_sorter_put_batch(self.h, seq, batch.h), "bwams_sorter_put_batch")
+
+    def set_markdup(self, groups=None, distance: int = 0, max_set: int = 0) -> None:
+        """bwams_sorter_set_markdup: the groups table (a DupGroups or None; copied) and the optical options, before the first put."""
+        o = _dup_opt(distance, max_set)
+        _chk(lib().bwams_sorter_set_markdup(self.h, _groups_h(groups), C.byref(o)), "bwams_sorter_set_markdup")
+        self._n_lib = groups.n_lib if groups is not None else 1
+
+    def close3(self) -> SorterStats:
+        """bwams_sorter_close3: close()'s stats, .dup, and rule 13's rows as .lib (DUP_LIB_STATS_DTYPE)."""
+        st, dup = SorterStats(), DupStats()
+        rows = np.zeros(getattr(self, "_n_lib", 1), DUP_LIB_STATS_DTYPE)
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_sorter_close3(h, C.byref(st), C.byref(dup), _p(rows), len(rows)), "bwams_sorter_close3")
+        st.dup, st.lib = dup, rows
+        return st
 
     def close(self) -> SorterStats:
         """bwams_sorter_close2: the sorter's stats, with the duplicate-marking counts as .dup (a DupStats, zeros without markdup)."""
@@ -636,6 +743,22 @@ def lib():
         L.bwams_bam_templates_fetch.argtypes = [vp, vp, i64, vp, i32]
         L.bwams_dup_decide.argtypes = [C.c_int, vp, i64, i64, vp, vp]
         L.bwams_bam_markdup.argtypes = [vp, vp]
+        L.bwams_dup_groups_create.argtypes = [C.c_char_p, i64, vp]
+        L.bwams_dup_groups_info.argtypes = [vp, vp, vp]
+        L.bwams_dup_groups_library.argtypes = [vp, i64]
+        L.bwams_dup_groups_library.restype = C.c_char_p
+        L.bwams_dup_groups_destroy.argtypes = [vp]
+        L.bwams_dup_groups_destroy.restype = None
+        L.bwams_bam_templates2.argtypes = [vp, vp, vp, vp]
+        L.bwams_bam_templates_fetch_loc.argtypes = [vp, vp, i64]
+        L.bwams_bam_lib_record_counts.argtypes = [vp, vp, vp, i64]
+        L.bwams_dup_decide2.argtypes = [C.c_int, vp, vp, i64, i64, i64, vp, vp, vp, vp]
+        L.bwams_bam_markdup2.argtypes = [vp, vp, vp, vp, vp, i64]
+        L.bwams_dup_library_size.argtypes = [i64, i64]
+        L.bwams_dup_library_size.restype = i64
+        L.bwams_dup_metrics_text.argtypes = [vp, vp, i64, C.c_char_p, vp, i64, vp]
+        L.bwams_sorter_set_markdup.argtypes = [vp, vp, vp]
+        L.bwams_sorter_close3.argtypes = [vp, vp, vp, vp, i64]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]
@@ -1463,6 +1586,36 @@ class Batch:
         st = DupStats()
         _chk(lib().bwams_bam_markdup(self.h, C.byref(st)), "bwams_bam_markdup")
         return st
+
+    def bam_templates2(self, groups=None) -> tuple[int, int]:
+        """bam_templates, and each template's read group, library and location on the device (bwams_bam_templates2); groups is a
+        DupGroups or None."""
+        nt, ne = C.c_int64(0), C.c_int64(0)
+        _chk(lib().bwams_bam_templates2(self.h, _groups_h(groups), C.byref(nt), C.byref(ne)), "bwams_bam_templates2")
+        self._md_ends = ne.value
+        return nt.value, ne.value
+
+    def bam_templates_fetch_loc(self):
+        """One DUP_LOC_DTYPE row per end of the last bam_templates2 (bwams_bam_templates_fetch_loc)."""
+        loc = np.zeros(max(self._md_ends, 1), DUP_LOC_DTYPE)
+        _chk(lib().bwams_bam_templates_fetch_loc(self.h, _p(loc), len(loc)), "bwams_bam_templates_fetch_loc")
+        return loc[:self._md_ends]
+
+    def bam_lib_record_counts(self, n_lib: int = 1):
+        """(secondary_or_supplementary, unmapped) records per library of the last bam_templates / bam_templates2."""
+        a, u = np.zeros(n_lib, np.int64), np.zeros(n_lib, np.int64)
+        _chk(lib().bwams_bam_lib_record_counts(self.h, _p(a), _p(u), n_lib), "bwams_bam_lib_record_counts")
+        return a, u
+
+    def bam_markdup2(self, groups=None, distance: int = 0, max_set: int = 0, opt=True, cap_lib: int | None = None):
+        """bwams_bam_markdup2 -> (DupStats, rows: DUP_LIB_STATS_DTYPE per library).  opt=False passes a NULL bwams_dup_opt_t."""
+        st = DupStats()
+        n_lib = groups.n_lib if groups is not None else 1
+        rows = np.zeros(max(n_lib if cap_lib is None else cap_lib, 1), DUP_LIB_STATS_DTYPE)
+        o = _dup_opt(distance, max_set)
+        _chk(lib().bwams_bam_markdup2(self.h, _groups_h(groups), C.byref(o) if opt else None, C.byref(st), _p(rows),
+                                      n_lib if cap_lib is None else cap_lib), "bwams_bam_markdup2")
+        return st, rows[:n_lib]
 
     def bam_fetch(self, n_reads: int | None = None):
         """(records of the last bam_run, n + 1 per-read offsets); n_reads defaults to the reads of the last SAM run (after a

@@ -1,6 +1,6 @@
 // api_bam.hip — C-ABI entry points of the BAM side (include/bwams.h): bwams_bam_run, _fetch, _fetch_bgzf and _upload, the
-// coordinate sort (bwams_bam_sort, _sorted_fetch) and duplicate marking (bwams_bam_templates, _templates_fetch, _markdup,
-// bwams_dup_decide), over bam.hip, bam_sort.hip and markdup.hip.  No CPU fallback: every entry point runs HIP kernels or returns an error.
+// coordinate sort (bwams_bam_sort, _sorted_fetch) and duplicate marking (bwams_bam_templates / _templates2, _templates_fetch / _fetch_loc,
+// _lib_record_counts, _markdup / _markdup2, bwams_dup_decide / _decide2), over bam.hip, bam_sort.hip and markdup.hip.  No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -8,6 +8,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "stage_state.h"
+#include "../host/dup_groups.h"
 
 using namespace bwams;
 
@@ -233,6 +234,7 @@ int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends)
         }
         BWAMS_HIP(hipSetDevice(b->idx->device));
         BWAMS_HIP(hipStreamSynchronize(b->stream));          // the buffers below may still be read by queued work
+        s->md.loc_done = false;
         if (int rc = md_templates(s->md.t, s->bm.out.p, s->bm.roff.p, s->bm.nrec, b->cu_count, b->stream)) return rc;
         s->md.done = true;
     }
@@ -278,12 +280,37 @@ static void dup_stats(bwams_dup_stats_t *st, int64_t n_t, int64_t n_e, const int
     st->ms_decide = ms;
 }
 
-int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, int64_t n_templates, uint8_t *dup, bwams_dup_stats_t *st) {
+// rule 13's rows from the device's counts (md_decide's and md_lib_recs': 7 words per library), rule 14 and the percentage added
+static void lib_rows(bwams_dup_lib_stats_t *rows, int64_t n_lib, const unsigned long long *c) {
+    for (int64_t k = 0; k < n_lib; ++k, c += 7) {
+        bwams_dup_lib_stats_t &r = rows[k];
+        memset(&r, 0, sizeof r);
+        r.unpaired_examined = (int64_t)c[0]; r.pairs_examined = (int64_t)c[1]; r.unpaired_duplicates = (int64_t)c[2];
+        r.pair_duplicates = (int64_t)c[3]; r.pair_optical_duplicates = (int64_t)c[4]; r.secondary_or_supplementary = (int64_t)c[5];
+        r.unmapped = (int64_t)c[6];
+        dup_lib_finish(&r);
+    }
+}
+
+// opt as md_decide takes it: d (0: off) and the largest group examined; false for a negative value
+static bool opt_values(const bwams_dup_opt_t *opt, int64_t *d, int64_t *max_set) {
+    *d = opt ? opt->optical_distance : 0;
+    *max_set = opt && opt->max_optical_set ? opt->max_optical_set : 300000;
+    return *d >= 0 && *max_set > 0;
+}
+
+static int decide_host(int device, const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_ends, int64_t n_templates,
+                       int64_t n_lib, const bwams_dup_opt_t *opt, uint8_t *dup, uint8_t *optical, bwams_dup_lib_stats_t *lib_stats,
+                       int64_t cnt[3]) {
+    int64_t d = 0, max_set = 0;
     if (n_ends < 0 || n_templates < 0 || (n_ends && !ends) || (n_templates && !dup)) {
         set_last_error("bwams_dup_decide: host ends and a dup array of n_templates bytes are required");
         return BWAMS_ERR_ARG;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    if (n_lib < 1 || n_lib > 0x7FFFFFFF || !opt_values(opt, &d, &max_set)) {
+        set_last_error("bwams_dup_decide: n_lib >= 1, optical_distance >= 0 and max_optical_set >= 0 are required");
+        return BWAMS_ERR_ARG;
+    }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
         set_last_error("bwams_dup_decide: no device " + std::to_string(device));
@@ -292,38 +319,176 @@ int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, in
     BWAMS_HIP(hipSetDevice(device));
     int cus = 0;
     BWAMS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    int64_t cnt[3] = {0, 0, 0};
-    {
-        hipStream_t q = nullptr;
-        BWAMS_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-        struct StreamGuard { hipStream_t q; ~StreamGuard() { (void)hipStreamDestroy(q); } } guard{q};
-        MdDecide w;
-        DevBuf<bwams_dup_end_t> d_ends;
-        DevBuf<uint8_t> d_dup;
-        BWAMS_HIP(d_ends.alloc((size_t)std::max<int64_t>(n_ends, 1) * sizeof(bwams_dup_end_t)));
-        BWAMS_HIP(d_dup.alloc((size_t)std::max<int64_t>(n_templates, 1)));
-        if (n_ends) BWAMS_HIP(hipMemcpyAsync(d_ends.p, ends, (size_t)n_ends * sizeof(bwams_dup_end_t), hipMemcpyHostToDevice, q));
-        if (int rc = md_decide(w, d_ends.p, n_ends, n_templates, d_dup.p, cnt, cus, q)) {
-            (void)hipStreamSynchronize(q);
-            return rc;
+    hipStream_t q = nullptr;
+    BWAMS_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t q; ~StreamGuard() { (void)hipStreamDestroy(q); } } guard{q};
+    MdDecide w;
+    DevBuf<bwams_dup_end_t> d_ends;
+    DevBuf<bwams_dup_loc_t> d_loc;
+    DevBuf<uint8_t> d_dup, d_opt;
+    DevBuf<unsigned long long> d_cnt;
+    BWAMS_HIP(d_ends.alloc((size_t)std::max<int64_t>(n_ends, 1) * sizeof(bwams_dup_end_t)));
+    BWAMS_HIP(d_dup.alloc((size_t)std::max<int64_t>(n_templates, 1)));
+    if (n_ends) BWAMS_HIP(hipMemcpyAsync(d_ends.p, ends, (size_t)n_ends * sizeof(bwams_dup_end_t), hipMemcpyHostToDevice, q));
+    MdDecideMore more{nullptr, (int32_t)n_lib, d, max_set, nullptr, nullptr};
+    const bool any_more = loc || lib_stats;
+    if (loc && n_ends) {
+        BWAMS_HIP(d_loc.alloc((size_t)n_ends * sizeof(bwams_dup_loc_t)));
+        BWAMS_HIP(hipMemcpyAsync(d_loc.p, loc, (size_t)n_ends * sizeof(bwams_dup_loc_t), hipMemcpyHostToDevice, q));
+        more.loc = d_loc.p;
+        if (d > 0 && n_templates) {
+            BWAMS_HIP(d_opt.alloc((size_t)n_templates));
+            BWAMS_HIP(hipMemsetAsync(d_opt.p, 0, (size_t)n_templates, q));
+            more.optical = d_opt.p;
         }
-        if (n_templates) BWAMS_HIP(hipMemcpyAsync(dup, d_dup.p, (size_t)n_templates, hipMemcpyDeviceToHost, q));
-        BWAMS_HIP(hipStreamSynchronize(q));
     }
+    if (lib_stats) {
+        BWAMS_HIP(d_cnt.alloc((size_t)n_lib * 7 * 8));
+        BWAMS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_lib * 7 * 8, q));
+        more.lib_counts = d_cnt.p;
+    }
+    if (int rc = md_decide(w, d_ends.p, n_ends, n_templates, d_dup.p, cnt, cus, q, any_more ? &more : nullptr)) {
+        (void)hipStreamSynchronize(q);
+        return rc;
+    }
+    if (n_templates) BWAMS_HIP(hipMemcpyAsync(dup, d_dup.p, (size_t)n_templates, hipMemcpyDeviceToHost, q));
+    if (optical && n_templates) {
+        if (more.optical) BWAMS_HIP(hipMemcpyAsync(optical, d_opt.p, (size_t)n_templates, hipMemcpyDeviceToHost, q));
+        else memset(optical, 0, (size_t)n_templates);
+    }
+    std::vector<unsigned long long> c;
+    if (lib_stats) {
+        c.resize((size_t)n_lib * 7);
+        BWAMS_HIP(hipMemcpyAsync(c.data(), d_cnt.p, c.size() * 8, hipMemcpyDeviceToHost, q));
+    }
+    BWAMS_HIP(hipStreamSynchronize(q));
+    if (lib_stats) lib_rows(lib_stats, n_lib, c.data());
+    return BWAMS_OK;
+}
+
+int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, int64_t n_templates, uint8_t *dup, bwams_dup_stats_t *st) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int64_t cnt[3] = {0, 0, 0};
+    if (int rc = decide_host(device, ends, nullptr, n_ends, n_templates, 1, nullptr, dup, nullptr, nullptr, cnt)) return rc;
     if (st) dup_stats(st, n_templates, n_ends, cnt, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return BWAMS_OK;
 }
 
-int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st) {
-    int64_t n_t = 0, n_e = 0;
-    if (int rc = bwams_bam_templates(b, &n_t, &n_e)) return rc;
+int bwams_dup_decide2(int device, const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_ends, int64_t n_templates,
+                      int64_t n_lib, const bwams_dup_opt_t *opt, uint8_t *dup, uint8_t *optical, bwams_dup_lib_stats_t *lib_stats) {
+    int64_t cnt[3] = {0, 0, 0};
+    return decide_host(device, ends, loc, n_ends, n_templates, n_lib, opt, dup, optical, lib_stats, cnt);
+}
+
+// the groups table as md_loc_kernel reads it: IDs sorted by bytes, uploaded into the stage's buffers (null: no table)
+static int groups_upload(StageState *s, const bwams_dup_groups_t *g, MdGroupsDev *G, hipStream_t st) {
+    memset(G, 0, sizeof *G);
+    G->n_lib = 1;
+    if (!g) return BWAMS_OK;
+    const size_t n = g->ids.size();
+    std::vector<int32_t> ord(n);
+    for (size_t k = 0; k < n; ++k) ord[k] = (int32_t)k;
+    std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return g->ids[(size_t)a] < g->ids[(size_t)b]; });   // by unsigned bytes
+    std::vector<int64_t> off(n + 1, 0);
+    std::string ids;
+    for (size_t k = 0; k < n; ++k) { ids += g->ids[(size_t)ord[k]]; off[k + 1] = (int64_t)ids.size(); }
+    BWAMS_HIP(s->md.g_ids.ensure_n(ids.size() + 1)); BWAMS_HIP(s->md.g_off.ensure_n(n + 1));
+    BWAMS_HIP(s->md.g_ord.ensure_n(n + 1)); BWAMS_HIP(s->md.g_lib.ensure_n(n + 1));
+    if (!ids.empty()) BWAMS_HIP(hipMemcpyAsync(s->md.g_ids.p, ids.data(), ids.size(), hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(s->md.g_off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n) {
+        BWAMS_HIP(hipMemcpyAsync(s->md.g_ord.p, ord.data(), n * 4, hipMemcpyHostToDevice, st));
+        BWAMS_HIP(hipMemcpyAsync(s->md.g_lib.p, g->rg_lib.data(), n * 4, hipMemcpyHostToDevice, st));
+    }
+    BWAMS_HIP(hipStreamSynchronize(st));                       // the host vectors above end here
+    G->ids = s->md.g_ids.p; G->id_off = s->md.g_off.p; G->id_ord = s->md.g_ord.p; G->rg_lib = s->md.g_lib.p;
+    G->n_rg = (int32_t)n; G->n_lib = (int32_t)g->libs.size(); G->walk = 1;
+    return BWAMS_OK;
+}
+
+int bwams_bam_templates2(bwams_batch_t *b, const bwams_dup_groups_t *groups, int64_t *n_templates, int64_t *n_ends) {
+    if (int rc = bwams_bam_templates(b, n_templates, n_ends)) return rc;
+    StageState *s = b->stages;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    s->md.loc_done = false;
+    MdGroupsDev G;
+    if (int rc = groups_upload(s, groups, &G, b->stream)) return rc;
+    if (int rc = md_locs(s->md.t, s->bm.out.p, s->bm.roff.p, s->bm.nrec, G, b->cu_count, b->stream)) return rc;
+    s->md.n_lib = G.n_lib;
+    s->md.loc_done = true;
+    return BWAMS_OK;
+}
+
+int bwams_bam_templates_fetch_loc(bwams_batch_t *b, bwams_dup_loc_t *loc, int64_t cap) {
+    if (!b || !b->stages || !b->stages->bm.done || !b->stages->md.done || !b->stages->md.loc_done) {
+        set_last_error("bwams_bam_templates_fetch_loc: run bwams_bam_templates2 on the current records first");
+        return BWAMS_ERR_ARG;
+    }
+    StageState *s = b->stages;
+    if (loc && s->md.t.n_e > cap) return BWAMS_ERR_CAPACITY;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    if (loc && s->md.t.n_e)
+        BWAMS_HIP(hipMemcpyAsync(loc, s->md.t.locs.p, (size_t)s->md.t.n_e * sizeof(bwams_dup_loc_t), hipMemcpyDeviceToHost, b->stream));
+    BWAMS_HIP(hipStreamSynchronize(b->stream));
+    return BWAMS_OK;
+}
+
+int bwams_bam_lib_record_counts(bwams_batch_t *b, int64_t *secondary_or_supplementary, int64_t *unmapped, int64_t cap_lib) {
+    if (!b || !b->stages || !b->stages->bm.done || !b->stages->md.done) {
+        set_last_error("bwams_bam_lib_record_counts: run bwams_bam_templates or _templates2 on the current records first");
+        return BWAMS_ERR_ARG;
+    }
+    StageState *s = b->stages;
+    const int64_t n_lib = s->md.loc_done ? s->md.n_lib : 1;
+    if (cap_lib < n_lib) return BWAMS_ERR_CAPACITY;
+    BWAMS_HIP(hipSetDevice(b->idx->device));
+    hipStream_t q = b->stream;
+    BWAMS_HIP(s->md.lib_counts.ensure_n((size_t)n_lib * 7));
+    BWAMS_HIP(hipMemsetAsync(s->md.lib_counts.p, 0, (size_t)n_lib * 7 * 8, q));
+    launch_md_lib_recs(s->md.t, s->bm.nrec, s->md.loc_done && s->md.t.n_t ? s->md.t.tloc.as<const bwams_dup_loc_t>() : nullptr,
+                       (int)n_lib, s->md.lib_counts.p, b->cu_count, q);
+    std::vector<unsigned long long> c((size_t)n_lib * 7);
+    BWAMS_HIP(hipMemcpyAsync(c.data(), s->md.lib_counts.p, c.size() * 8, hipMemcpyDeviceToHost, q));
+    BWAMS_HIP(hipStreamSynchronize(q));
+    BWAMS_HIP(hipGetLastError());
+    for (int64_t k = 0; k < n_lib; ++k) {
+        if (secondary_or_supplementary) secondary_or_supplementary[k] = (int64_t)c[(size_t)k * 7 + 5];
+        if (unmapped) unmapped[k] = (int64_t)c[(size_t)k * 7 + 6];
+    }
+    return BWAMS_OK;
+}
+
+int bwams_bam_markdup2(bwams_batch_t *b, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt, bwams_dup_stats_t *st,
+                       bwams_dup_lib_stats_t *lib_stats, int64_t cap_lib) {
+    int64_t n_t = 0, n_e = 0, d = 0, max_set = 0;
+    if (!opt_values(opt, &d, &max_set)) {
+        set_last_error("bwams_bam_markdup2: optical_distance >= 0 and max_optical_set >= 0 are required");
+        return BWAMS_ERR_ARG;
+    }
+    const int64_t n_lib = groups ? (int64_t)groups->libs.size() : 1;
+    if (lib_stats && cap_lib < n_lib) return BWAMS_ERR_CAPACITY;
+    const bool locs = groups || d > 0;                       // without either: one library, no location, and bwams_bam_markdup's kernels
+    if (int rc = locs ? bwams_bam_templates2(b, groups, &n_t, &n_e) : bwams_bam_templates(b, &n_t, &n_e)) return rc;
     StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t q = b->stream;
     const auto t0 = std::chrono::steady_clock::now();
     BWAMS_HIP(s->md.dup.ensure_n((size_t)std::max<int64_t>(n_t, 1))); BWAMS_HIP(s->md.cnt.ensure_n(2));
+    MdDecideMore more{locs && n_e ? s->md.t.locs.as<const bwams_dup_loc_t>() : nullptr, (int32_t)n_lib, d, max_set, nullptr, nullptr};
+    if (more.loc && d > 0) {
+        BWAMS_HIP(s->md.optical.ensure_n((size_t)std::max<int64_t>(n_t, 1)));
+        BWAMS_HIP(hipMemsetAsync(s->md.optical.p, 0, (size_t)n_t, q));
+        more.optical = s->md.optical.p;
+    }
+    if (lib_stats) {
+        BWAMS_HIP(s->md.lib_counts.ensure_n((size_t)n_lib * 7));
+        BWAMS_HIP(hipMemsetAsync(s->md.lib_counts.p, 0, (size_t)n_lib * 7 * 8, q));
+        more.lib_counts = s->md.lib_counts.p;
+    }
     int64_t cnt[3] = {0, 0, 0};
-    if (int rc = md_decide(s->md.decide, s->md.t.ends.as<const bwams_dup_end_t>(), n_e, n_t, s->md.dup.p, cnt, b->cu_count, q)) return rc;
+    if (int rc = md_decide(s->md.decide, s->md.t.ends.as<const bwams_dup_end_t>(), n_e, n_t, s->md.dup.p, cnt, b->cu_count, q,
+                           more.loc || lib_stats ? &more : nullptr))
+        return rc;
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     unsigned long long *marked = s->md.cnt.p;
     BWAMS_HIP(hipMemsetAsync(marked, 0, 16, q));
@@ -333,14 +498,24 @@ int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st) {
     launch_md_apply(s->bm.out.p, s->bm.roff.p, nullptr, rt, dup, n, marked, b->cu_count, q);
     if (s->bs.done)                                          // the sorted copy: record i is the unsorted record bs.idx2[i]
         launch_md_apply(s->bs.out.p, s->bs.off.p, s->bs.idx2.p, rt, dup, n, marked + 1, b->cu_count, q);
+    std::vector<unsigned long long> c;
+    if (lib_stats) {
+        launch_md_lib_recs(s->md.t, n, locs && n_t ? s->md.t.tloc.as<const bwams_dup_loc_t>() : nullptr, (int)n_lib, more.lib_counts,
+                           b->cu_count, q);
+        c.resize((size_t)n_lib * 7);
+        BWAMS_HIP(hipMemcpyAsync(c.data(), more.lib_counts, c.size() * 8, hipMemcpyDeviceToHost, q));
+    }
     unsigned long long h[2] = {0, 0};
     BWAMS_HIP(hipMemcpyAsync(h, marked, 16, hipMemcpyDeviceToHost, q));
     BWAMS_HIP(hipStreamSynchronize(q));
     BWAMS_HIP(hipGetLastError());
+    if (lib_stats) lib_rows(lib_stats, n_lib, c.data());
     if (st) {
         dup_stats(st, n_t, n_e, cnt, ms);
         st->records_marked = (int64_t)h[0];
     }
     return BWAMS_OK;
 }
+
+int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st) { return bwams_bam_markdup2(b, nullptr, nullptr, st, nullptr, 0); }
 }  // extern "C"

@@ -226,14 +226,37 @@ struct MdRec {                           // one record as the template kernel re
 };
 struct MdTemplates {
     DevBuf<> head, tid, rtmpl, tstart, rec, tend, has, ends, info, tmp;
+    DevBuf<> tloc, locs;                 // md_locs: bwams_dup_loc_t per template, and per end (parallel to ends)
     int64_t n_t = 0, n_e = 0;
 };
 struct MdDecide {
     DevBuf<> k1, k2, ka, kb, i1, i2, info, tmp;
+    DevBuf<> e2, opt;                    // the ends with their libraries folded into the refIDs; optical clustering's slot arrays
+};
+// The groups table on the device (rule 9): the read groups' IDs sorted by bytes, ids[id_off[k], id_off[k + 1]) the k-th of them and
+// id_ord[k] its ordinal; rg_lib by ordinal.  walk = 0: no table, no aux walk, every template read group -1 of library n_lib - 1 = 0.
+struct MdGroupsDev {
+    const uint8_t *ids;
+    const int64_t *id_off;
+    const int32_t *id_ord, *rg_lib;
+    int32_t n_rg, n_lib, walk;
+};
+// What md_decide does beyond rule 6 when given: loc per end (device; null: one library, no location), d > 0 and optical (device,
+// n_t bytes, zeroed by the caller) for rule 12, lib_counts (device, n_lib * 7 words, zeroed by the caller: unpaired and pairs
+// examined, unpaired, pair and optical duplicates, then md_lib_recs' two) for rule 13.
+struct MdDecideMore {
+    const bwams_dup_loc_t *loc;
+    int32_t n_lib;
+    int64_t d, max_set;
+    uint8_t *optical;
+    unsigned long long *lib_counts;
 };
 int md_templates(MdTemplates &m, const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, int cu_count, hipStream_t st);
+int md_locs(MdTemplates &m, const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const MdGroupsDev &G, int cu_count, hipStream_t st);
+void launch_md_lib_recs(const MdTemplates &m, int64_t n_rec, const bwams_dup_loc_t *tloc, int n_lib, unsigned long long *counts,
+                        int cu_count, hipStream_t st);
 int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t, uint8_t *dup, int64_t counts[3], int cu_count,
-              hipStream_t st);
+              hipStream_t st, const MdDecideMore *more = nullptr);
 void launch_md_apply(uint8_t *bam, const int64_t *rec_off, const uint32_t *perm, const uint32_t *rtmpl, const uint8_t *dup, int64_t n_rec,
                      unsigned long long *n_marked, int cu_count, hipStream_t st);
 void launch_md_gather32(const uint32_t *src, const uint32_t *idx, int64_t n, uint32_t *dst, int cu_count, hipStream_t st);

@@ -23,7 +23,29 @@
 //   md_mark_pairs / md_mark_frags  lane per sorted slot: a pair slot that is not its group's first, an unpaired fragment slot that is
 //                    not its group's first, writes dup[tmpl] = 1 (each template has one end, so no slot races another's byte).
 // md_apply_kernel: lane per record, sets or clears 0x400 in FLAG's high byte (byte 19 of the record) from dup[rtmpl[r]].
-// Every kernel is memory-bound; none uses LDS or scratch.
+// Rules 9-13 (bwams_bam_templates2, bwams_dup_decide2, bwams_bam_markdup2); none of this is launched by the calls of rules 1-8:
+//   md_loc_kernel    lane per template, a pass of its own behind md_tmpl_kernel (md_rec_kernel's sixteen lanes and 45 VGPRs stay as
+//                    they are): the record rule 9 names; with a table its aux fields walked by type to block_size (atomicMin of the
+//                    first record that does not chain), the RG:Z value looked up by binary search in the table's IDs sorted by
+//                    bytes; the name's colons counted and its three fields parsed (rule 10); one bwams_dup_loc_t per template, and
+//                    rocprim::select with the ends' flags gives one per end;
+//   md_check_loc / md_lib_ends_fold  the ends' libraries checked; with n_lib > 1 a copy of the ends whose refIDs are
+//                    library * (largest refID + 1) + refID, so that the position keys above carry the library as their most
+//                    significant part (rule 11) and the sorts and mark kernels run unchanged (the product must stay below 2^31);
+//   optical clustering (rule 12), after md_mark_pairs while the pairs' slots lie sorted, a group's slots adjacent, its kept pair first:
+//     md_opt_head / scan / md_opt_start   each slot's group and each group's first slot, so its size;
+//     md_opt_keys      the slots of groups of 2..max_set members that have a location are keyed by (tile, x) and by (group, read
+//                      group); two stable 64-bit radix sorts order them by (group, read group, tile, x), the others behind them;
+//     md_opt_pts / md_opt_link   lane per sorted point: forward while the (group, read group) and tile are its own and x' - x <= d,
+//                      joining the points also within d in y by union-find (find without compression, hook the larger root under
+//                      the smaller with atomicMin).  A tree's root is its smallest slot whatever the schedule, in a group the
+//                      best-ranked member, so the kept pair when the cluster holds it.  The scan is quadratic for many points at one
+//                      x of one tile: Picard's own worst case, which max_set bounds;
+//     md_opt_root / md_opt_mark  every slot's root; a cluster without the kept pair collects its smallest template ordinal
+//                      (atomicMin); every member but the representative writes optical[tmpl] = 1;
+//   md_lib_ends / md_lib_recs  rule 13's counts per library, lane per end and lane per record: a workgroup counts in 64 x 7 LDS words
+//                    (1792 B) when n_lib <= 64 and adds what is not zero to global memory at its end; global atomics otherwise.
+// Every kernel is memory-bound; none uses scratch, and only the two md_lib kernels use LDS.
 #include <algorithm>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -279,6 +301,280 @@ __global__ void __launch_bounds__(256) md_apply_kernel(uint8_t *bam, const int64
     }
 }
 
+// ---- rules 9-10: a template's read group, library and location, lane per template ----
+
+__device__ __forceinline__ int aux_size(uint32_t t) {        // bytes of a fixed-size aux value of type t, 0 for any other
+    return (t == 'A' || t == 'c' || t == 'C') ? 1 : (t == 's' || t == 'S') ? 2 : (t == 'i' || t == 'I' || t == 'f') ? 4 : 0;
+}
+
+// one field of a read name from s[at, n): an optional '-', then digits up to the first other byte; *ok cleared outside int32
+__device__ __forceinline__ int32_t name_value(const uint8_t *s, uint32_t at, uint32_t n, bool *ok) {
+    const bool neg = at < n && s[at] == '-';
+    if (neg) ++at;
+    int64_t v = 0;
+    for (; at < n && s[at] >= '0' && s[at] <= '9'; ++at) v = min(v * 10 + (s[at] - '0'), (int64_t)1 << 40);
+    if (neg) v = -v;
+    if (v < -(1LL << 31) || v >= (1LL << 31)) *ok = false;
+    return (int32_t)v;
+}
+
+__global__ void __launch_bounds__(256) md_loc_kernel(const uint8_t *bam, const int64_t *rec_off, const MdRec *rec, const uint32_t *tstart,
+                                                     int64_t n_t, int64_t n_rec, MdGroupsDev G, bwams_dup_loc_t *tloc,
+                                                     unsigned long long *bad) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_t; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r0 = tstart[t], r1 = t + 1 < n_t ? (int64_t)tstart[t + 1] : n_rec;
+        int64_t r = r0;
+        while (r < r1 && (rec[r].flag & 0x900)) ++r;         // the first primary, else the first record
+        if (r == r1) r = r0;
+        const uint8_t *p = bam + rec_off[r];
+        const uint32_t l_name = p[12];
+        bwams_dup_loc_t L;
+        L.rg = -1; L.lib = G.n_lib - 1; L.tile = L.x = L.y = 0; L.has = 0;
+        if (G.walk) {                                         // rule 9: the aux fields by their types, to the record's end
+            const int64_t n = (int64_t)ld_u32(p) + 4;         // the record with its block_size
+            const int64_t l_seq = (int32_t)ld_u32(p + 20);
+            int64_t a = 36 + (int64_t)l_name + 4 * (int64_t)((uint32_t)p[16] | (uint32_t)p[17] << 8) + (l_seq + 1) / 2 + l_seq;
+            bool ok = l_seq >= 0 && a <= n, found = false;
+            int64_t v0 = 0, v1 = 0;                           // RG's value: p[v0, v1)
+            while (ok && a < n) {
+                if (a + 3 > n) { ok = false; break; }
+                const uint32_t c0 = p[a], c1 = p[a + 1], ty = p[a + 2];
+                a += 3;
+                if (ty == 'Z' || ty == 'H') {
+                    const int64_t s = a;
+                    while (a < n && p[a] != 0) ++a;
+                    if (a >= n) { ok = false; break; }
+                    if (ty == 'Z' && c0 == 'R' && c1 == 'G' && !found) { found = true; v0 = s; v1 = a; }
+                    ++a;
+                } else if (ty == 'B') {
+                    if (a + 5 > n) { ok = false; break; }
+                    const int sz = aux_size(p[a]);
+                    if (!sz || p[a] == 'A') { ok = false; break; }
+                    a += 5 + (int64_t)sz * (int64_t)ld_u32(p + a + 1);
+                } else {
+                    const int sz = aux_size(ty);
+                    if (!sz) { ok = false; break; }
+                    a += sz;
+                }
+                if (a > n) ok = false;
+            }
+            if (!ok) atomicMin(bad, (unsigned long long)r);
+            if (ok && found) {                                // the ID among the table's, sorted by bytes
+                int lo = 0, hi = G.n_rg;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    const uint8_t *id = G.ids + G.id_off[mid];
+                    const int64_t ln = G.id_off[mid + 1] - G.id_off[mid], lv = v1 - v0;
+                    int64_t k = 0;
+                    while (k < ln && k < lv && id[k] == p[v0 + k]) ++k;
+                    const int cmp = k < ln && k < lv ? (id[k] < p[v0 + k] ? -1 : 1) : ln < lv ? -1 : ln > lv ? 1 : 0;
+                    if (cmp == 0) { L.rg = G.id_ord[mid]; L.lib = G.rg_lib[L.rg]; break; }
+                    if (cmp < 0) lo = mid + 1;
+                    else hi = mid;
+                }
+            }
+        }
+        const uint8_t *s = p + 36;                            // rule 10: the name without its NUL
+        const uint32_t n = l_name ? l_name - 1 : 0;
+        uint32_t colons = 0;
+        for (uint32_t k = 0; k < n; ++k) colons += s[k] == ':';
+        const int first = colons == 4 ? 2 : (colons == 6 || colons == 7) ? 4 : -1;
+        if (first >= 0) {
+            uint32_t at = 0;
+            for (int f = 0; f < first; ++at) f += s[at] == ':';
+            bool ok = true;
+            int32_t v[3];
+#pragma unroll
+            for (int f = 0; f < 3; ++f) {
+                v[f] = name_value(s, at, n, &ok);
+                while (at < n && s[at] != ':') ++at;
+                ++at;
+            }
+            if (ok) { L.tile = v[0]; L.x = v[1]; L.y = v[2]; L.has = 1; }
+        }
+        tloc[t] = L;
+    }
+}
+
+// ---- rule 13: counts per library.  counts[lib * kLibCounts + which]; a workgroup counts in LDS when the libraries fit ----
+
+constexpr int kLibCounts = 7, kLdsLibs = 64;
+enum { kUnpEx = 0, kPairEx = 1, kUnpDup = 2, kPairDup = 3, kOptical = 4, kSecSup = 5, kUnmapped = 6 };
+
+struct LibCounter {
+    unsigned int *lds;                                        // kLdsLibs * kLibCounts words, or null: straight to global memory
+    unsigned long long *out;
+    __device__ void init(unsigned int *sh, int n_lib, unsigned long long *counts) {
+        lds = n_lib <= kLdsLibs ? sh : nullptr;
+        out = counts;
+        if (lds) {
+            for (int k = threadIdx.x; k < n_lib * kLibCounts; k += blockDim.x) lds[k] = 0;
+            __syncthreads();
+        }
+    }
+    __device__ void add(int lib, int which) {
+        if (lds) atomicAdd(lds + lib * kLibCounts + which, 1u);
+        else atomicAdd(out + (int64_t)lib * kLibCounts + which, 1ULL);
+    }
+    __device__ void flush(int n_lib) {
+        if (!lds) return;
+        __syncthreads();
+        for (int k = threadIdx.x; k < n_lib * kLibCounts; k += blockDim.x)
+            if (lds[k]) atomicAdd(out + k, (unsigned long long)lds[k]);
+    }
+};
+
+// lane per end: its template's kind and what the decision made of it, to the end's library (loc null: library 0)
+__global__ void __launch_bounds__(256) md_lib_ends_kernel(const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_e,
+                                                          const uint8_t *dup, const uint8_t *optical, int n_lib,
+                                                          unsigned long long *counts) {
+    __shared__ unsigned int sh[kLdsLibs * kLibCounts];
+    LibCounter c;
+    c.init(sh, n_lib, counts);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_e; i += (int64_t)gridDim.x * blockDim.x) {
+        const bwams_dup_end_t e = ends[i];
+        const int lib = loc ? loc[i].lib : 0;
+        const bool pair = e.ref2 >= 0;
+        c.add(lib, pair ? kPairEx : kUnpEx);
+        if (dup[e.tmpl]) c.add(lib, pair ? kPairDup : kUnpDup);
+        if (optical && optical[e.tmpl]) c.add(lib, kOptical);
+    }
+    c.flush(n_lib);
+}
+
+// lane per record: secondary or supplementary and mapped, or unmapped, to its template's library (tloc null: library 0)
+__global__ void __launch_bounds__(256) md_lib_recs_kernel(const MdRec *rec, const uint32_t *rtmpl, const bwams_dup_loc_t *tloc, int64_t n_rec,
+                                                          int n_lib, unsigned long long *counts) {
+    __shared__ unsigned int sh[kLdsLibs * kLibCounts];
+    LibCounter c;
+    c.init(sh, n_lib, counts);
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t f = rec[r].flag;
+        if (!(f & 4) && !(f & 0x900)) continue;
+        c.add(tloc ? tloc[rtmpl[r]].lib : 0, (f & 4) ? kUnmapped : kSecSup);
+    }
+    c.flush(n_lib);
+}
+
+// ---- the ends' libraries checked, and folded into the refIDs of the keys (rule 11) ----
+
+// info[0]: the first end whose loc is out of range (atomicMin)
+__global__ void __launch_bounds__(256) md_check_loc_kernel(const bwams_dup_loc_t *loc, int64_t n_e, int n_lib, unsigned long long *info) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_e; i += (int64_t)gridDim.x * blockDim.x) {
+        const bwams_dup_loc_t L = loc[i];
+        if (L.lib < 0 || L.lib >= n_lib || (L.has != 0 && L.has != 1)) atomicMin(info, (unsigned long long)i);
+    }
+}
+
+// ends2[i] = ends[i] with refID + lib * stride for each refID: equal places in two libraries become different places
+__global__ void __launch_bounds__(256) md_lib_ends_fold_kernel(const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_e,
+                                                               int32_t stride, bwams_dup_end_t *ends2) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_e; i += (int64_t)gridDim.x * blockDim.x) {
+        bwams_dup_end_t e = ends[i];
+        const int32_t add = loc[i].lib * stride;
+        e.ref1 += add;
+        if (e.ref2 >= 0) e.ref2 += add;
+        ends2[i] = e;
+    }
+}
+
+// ---- rule 12: optical duplicates, over the pairs' slots as the pair sort left them (a group's slots adjacent, the kept pair first) ----
+
+// head[i] = 1 where slot i opens a group (a slot that holds no pair is a group of its own)
+__global__ void __launch_bounds__(256) md_opt_head_kernel(const uint64_t *ks, const uint64_t *k2, const uint32_t *idx, int64_t n,
+                                                          uint64_t none_key, uint32_t *head) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        head[i] = !(i > 0 && ks[i] != none_key && ks[i] == ks[i - 1] && k2[idx[i]] == k2[idx[i - 1]]);
+}
+
+__global__ void __launch_bounds__(256) md_opt_start_kernel(const uint32_t *head, const uint32_t *gid, int64_t n, uint32_t *gstart) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        if (head[i]) gstart[gid[i] - 1] = (uint32_t)i;
+}
+
+// per slot: the two sort keys of the eligible slots, (tile, x) and (group, read group); others take ~0 as the second and sort last.
+// Every slot starts as a cluster of its own.
+__global__ void __launch_bounds__(256) md_opt_keys_kernel(const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, const uint32_t *idx,
+                                                          const uint32_t *gid, const uint32_t *gstart, int64_t n, int64_t max_set,
+                                                          uint64_t *key_a, uint64_t *key_b, uint32_t *slot, uint32_t *parent) {
+    const int64_t n_g = gid[n - 1];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t e = idx[i];
+        const bwams_dup_loc_t L = loc[e];
+        const int64_t g = (int64_t)gid[i] - 1;
+        const int64_t size = (g + 1 < n_g ? (int64_t)gstart[g + 1] : n) - (int64_t)gstart[g];
+        const bool el = L.has == 1 && ends[e].ref2 >= 0 && size >= 2 && size <= max_set;
+        key_a[i] = (uint64_t)((uint32_t)L.tile ^ 0x80000000u) << 32 | (uint64_t)((uint32_t)L.x ^ 0x80000000u);
+        key_b[i] = el ? (uint64_t)g << 32 | (uint64_t)(uint32_t)(L.rg + 1) : ~0ULL;
+        slot[i] = (uint32_t)i;
+        parent[i] = (uint32_t)i;
+    }
+}
+
+struct OptPt { int32_t tile, x, y; uint32_t slot; };
+
+__global__ void __launch_bounds__(256) md_opt_pts_kernel(const bwams_dup_loc_t *loc, const uint32_t *idx, const uint32_t *slot, int64_t n,
+                                                         OptPt *pts) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+        const bwams_dup_loc_t L = loc[idx[slot[j]]];
+        pts[j] = OptPt{L.tile, L.x, L.y, slot[j]};
+    }
+}
+
+__device__ __forceinline__ uint32_t opt_find(const uint32_t *parent, uint32_t x) {
+    for (uint32_t p = parent[x]; p != x; p = parent[x]) x = p;
+    return x;
+}
+
+// parent[] only ever decreases and parent[x] <= x, so every tree's root is its smallest slot: in a group, the best-ranked member
+__device__ __forceinline__ void opt_union(uint32_t *parent, uint32_t a, uint32_t b) {
+    volatile uint32_t *vp = parent;
+    for (;;) {
+        while (vp[a] != a) a = vp[a];
+        while (vp[b] != b) b = vp[b];
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = atomicMin(parent + a, b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// lane per sorted point: forward over the points of its (group, read group) and tile while x' - x <= d; joins those close in y too
+__global__ void __launch_bounds__(256) md_opt_link_kernel(const uint64_t *kb, const OptPt *pts, int64_t n, int64_t d, uint32_t *parent) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = kb[j];
+        if (key == ~0ULL) continue;
+        const OptPt a = pts[j];
+        for (int64_t k = j + 1; k < n && kb[k] == key; ++k) {
+            const OptPt b = pts[k];
+            if (b.tile != a.tile || (int64_t)b.x - (int64_t)a.x > d) break;
+            const int64_t dy = (int64_t)b.y - (int64_t)a.y;
+            if (dy <= d && -dy <= d) opt_union(parent, a.slot, b.slot);
+        }
+    }
+}
+
+// lane per slot: root[i]; a cluster whose root is not its group's kept pair collects its smallest template ordinal
+__global__ void __launch_bounds__(256) md_opt_root_kernel(const bwams_dup_end_t *ends, const uint32_t *idx, const uint32_t *head,
+                                                          const uint32_t *parent, int64_t n, uint32_t *root, unsigned long long *min_t) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = opt_find(parent, (uint32_t)i);
+        root[i] = r;
+        if (!head[r]) atomicMin(min_t + r, (unsigned long long)ends[idx[i]].tmpl);
+    }
+}
+
+__global__ void __launch_bounds__(256) md_opt_mark_kernel(const bwams_dup_end_t *ends, const uint32_t *idx, const uint32_t *head,
+                                                          const uint32_t *root, const unsigned long long *min_t, int64_t n,
+                                                          uint8_t *optical) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = root[i];
+        const int64_t t = ends[idx[i]].tmpl;
+        if (head[r] ? r != (uint32_t)i : (unsigned long long)t != min_t[r]) optical[t] = 1;
+    }
+}
+
 unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
     int64_t g = (items + per_block - 1) / per_block;
     const int64_t cap = (int64_t)cu_count * 16;
@@ -293,6 +589,7 @@ int bit_width(uint64_t x) {
 
 const char *kReason[4] = {"two primaries of one segment", "a paired primary with neither or both of 0x40 / 0x80",
                           "paired and unpaired primaries mixed", "a mapped primary's unclipped 5' coordinate outside [-2^31, 2^31) or its refID -1"};
+const char *kReasonAux = "aux fields do not chain to the record's end";
 
 }  // namespace
 
@@ -341,8 +638,43 @@ int md_templates(MdTemplates &m, const uint8_t *bam, const int64_t *rec_off, int
     return BWAMS_OK;
 }
 
+// rules 9-10 over the templates md_templates left in m: m.tloc per template, m.locs per end (parallel to m.ends)
+int md_locs(MdTemplates &m, const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const MdGroupsDev &G, int cu_count, hipStream_t st) {
+    if (m.n_t == 0) return BWAMS_OK;
+    const size_t n_t = (size_t)m.n_t;
+    BWAMS_HIP(m.tloc.ensure(n_t * sizeof(bwams_dup_loc_t))); BWAMS_HIP(m.locs.ensure(n_t * sizeof(bwams_dup_loc_t)));
+    BWAMS_HIP(m.info.ensure(16));
+    const unsigned long long init[2] = {~0ULL, 0};
+    BWAMS_HIP(hipMemcpyAsync(m.info.p, init, 16, hipMemcpyHostToDevice, st));
+    md_loc_kernel<<<grid_of(m.n_t, 256, cu_count), 256, 0, st>>>(bam, rec_off, m.rec.as<const MdRec>(), m.tstart.as<const uint32_t>(), m.n_t,
+                                                                 n_rec, G, m.tloc.as<bwams_dup_loc_t>(), m.info.as<unsigned long long>());
+    size_t tb = 0;
+    BWAMS_HIP(rocprim::select(nullptr, tb, m.tloc.as<const bwams_dup_loc_t>(), m.has.as<const uint8_t>(), m.locs.as<bwams_dup_loc_t>(),
+                              m.info.as<unsigned long long>() + 1, n_t, st));
+    BWAMS_HIP(m.tmp.ensure(tb));
+    BWAMS_HIP(rocprim::select(m.tmp.p, tb, m.tloc.as<const bwams_dup_loc_t>(), m.has.as<const uint8_t>(), m.locs.as<bwams_dup_loc_t>(),
+                              m.info.as<unsigned long long>() + 1, n_t, st));
+    unsigned long long bad = 0;
+    BWAMS_HIP(hipMemcpyAsync(&bad, m.info.p, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    BWAMS_HIP(hipGetLastError());
+    if (bad != ~0ULL) {
+        set_last_error("bwams_bam_templates: record " + std::to_string(bad) + ": " + kReasonAux);
+        return BWAMS_ERR_UNSUPPORTED;
+    }
+    return BWAMS_OK;
+}
+
+// rule 13's two record-level counts of the templates in m, added to counts[lib * 7 + 5 .. 6] (device); tloc null: library 0
+void launch_md_lib_recs(const MdTemplates &m, int64_t n_rec, const bwams_dup_loc_t *tloc, int n_lib, unsigned long long *counts,
+                        int cu_count, hipStream_t st) {
+    if (n_rec > 0)
+        md_lib_recs_kernel<<<grid_of(n_rec, 256, cu_count), 256, 0, st>>>(m.rec.as<const MdRec>(), m.rtmpl.as<const uint32_t>(), tloc, n_rec,
+                                                                          n_lib, counts);
+}
+
 int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t, uint8_t *dup, int64_t counts[3], int cu_count,
-              hipStream_t st) {
+              hipStream_t st, const MdDecideMore *x) {
     counts[0] = counts[1] = counts[2] = 0;                   // pairs, pair duplicates, fragment duplicates
     if (n_t > 0) BWAMS_HIP(hipMemsetAsync(dup, 0, (size_t)n_t, st));
     if (n_e == 0) return BWAMS_OK;
@@ -352,12 +684,14 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
     }
     const size_t n2 = 2 * (size_t)n_e;
     BWAMS_HIP(w.info.ensure(32));
-    const unsigned long long init[4] = {~0ULL, 0, 0, 0};
+    const unsigned long long init[4] = {~0ULL, 0, 0, ~0ULL};
     BWAMS_HIP(hipMemcpyAsync(w.info.p, init, 32, hipMemcpyHostToDevice, st));
     unsigned long long *info = w.info.as<unsigned long long>();
+    const bwams_dup_loc_t *loc = x ? x->loc : nullptr;
     md_check_kernel<<<grid_of(n_e, 256, cu_count), 256, 0, st>>>(ends, n_e, n_t, info);
-    unsigned long long h[3];
-    BWAMS_HIP(hipMemcpyAsync(h, info, 24, hipMemcpyDeviceToHost, st));
+    if (loc) md_check_loc_kernel<<<grid_of(n_e, 256, cu_count), 256, 0, st>>>(loc, n_e, x->n_lib, info + 3);
+    unsigned long long h[4];
+    BWAMS_HIP(hipMemcpyAsync(h, info, 32, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
     if (h[0] != ~0ULL) {
@@ -365,7 +699,24 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
                        "(ref2: -1 too), score outside [0, 32767] or strands outside [0, 3] (bit 1 without end 2)");
         return BWAMS_ERR_ARG;
     }
-    const int32_t none_ref = (int32_t)h[1];                  // the largest refID + 1: slots that hold nothing
+    if (h[3] != ~0ULL) {
+        set_last_error("bwams_dup_decide: end " + std::to_string(h[3]) + ": loc.lib outside [0, n_lib) or loc.has outside {0, 1}");
+        return BWAMS_ERR_ARG;
+    }
+    const bwams_dup_end_t *ends0 = ends;                     // as given: ends may become their folded copy
+    int32_t none_ref = (int32_t)h[1];                        // the largest refID + 1: slots that hold nothing
+    if (loc && x->n_lib > 1) {                               // rule 11: library l's refIDs become l * stride + refID
+        const int32_t stride = none_ref;
+        if ((int64_t)x->n_lib * stride >= (1LL << 31)) {
+            set_last_error("bwams_dup_decide: n_lib * (the largest refID + 1) must stay below 2^31");
+            return BWAMS_ERR_UNSUPPORTED;
+        }
+        BWAMS_HIP(w.e2.ensure((size_t)n_e * sizeof(bwams_dup_end_t)));
+        md_lib_ends_fold_kernel<<<grid_of(n_e, 256, cu_count), 256, 0, st>>>(ends, loc, n_e, stride, w.e2.as<bwams_dup_end_t>());
+        ends = w.e2.as<const bwams_dup_end_t>();
+        none_ref = x->n_lib * stride;
+    }
+    const bool optical = loc && x->d > 0 && x->optical && h[2] > 0;
     const uint64_t none_key = (uint64_t)(uint32_t)none_ref << 33 | (uint64_t)0x80000000u << 1;
     const unsigned kb = (unsigned)(33 + bit_width((uint64_t)none_ref)), tb = (unsigned)std::max(1, bit_width((uint64_t)n_t));
     counts[0] = (int64_t)h[2];
@@ -381,6 +732,15 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
         BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, t, ka, kbuf, i1, i2, q.first, 0u, q.second, st));
         need = std::max(need, t);
     }
+    if (optical) {
+        size_t t = 0;
+        BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, t, ka, kbuf, i1, i2, (size_t)n_e, 0u, 64u, st));
+        need = std::max(need, t);
+        t = 0;
+        BWAMS_HIP(rocprim::inclusive_scan(nullptr, t, i1, i2, (size_t)n_e, rocprim::plus<uint32_t>(), st));
+        need = std::max(need, t);
+        BWAMS_HIP(w.opt.ensure(5 * (size_t)n_e * 4));
+    }
     BWAMS_HIP(w.tmp.ensure(need));
     auto sort = [&](uint64_t *kin, uint32_t *vin, uint32_t *vout, size_t n, unsigned bits) {
         size_t t = need;
@@ -395,12 +755,34 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
     md_gather64_kernel<<<g1, 256, 0, st>>>(k1, i1, n_e, ka);
     BWAMS_HIP(sort(ka, i1, i2, (size_t)n_e, kb));
     md_mark_pairs_kernel<<<g1, 256, 0, st>>>(kbuf, k2, i2, n_e, none_key, ends, dup, info + 2);
+    if (optical) {                                           // rule 12, while kbuf / i2 hold the pairs' sorted key 1 and each slot's end
+        uint32_t *head = w.opt.as<uint32_t>(), *gid = head + n_e, *gstart = gid + n_e, *parent = gstart + n_e, *v2 = parent + n_e;
+        uint64_t *key_b = k1;                                // k1's first half; its second: every cluster's smallest template ordinal
+        unsigned long long *min_t = reinterpret_cast<unsigned long long *>(k1 + n_e);
+        OptPt *pts = reinterpret_cast<OptPt *>(k2);          // 16 bytes per end, as k2 has
+        md_opt_head_kernel<<<g1, 256, 0, st>>>(kbuf, k2, i2, n_e, none_key, head);
+        size_t t = need;
+        BWAMS_HIP(rocprim::inclusive_scan(w.tmp.p, t, head, gid, (size_t)n_e, rocprim::plus<uint32_t>(), st));
+        md_opt_start_kernel<<<g1, 256, 0, st>>>(head, gid, n_e, gstart);
+        md_opt_keys_kernel<<<g1, 256, 0, st>>>(ends, loc, i2, gid, gstart, n_e, x->max_set, ka, key_b, i1, parent);
+        BWAMS_HIP(sort(ka, i1, v2, (size_t)n_e, 64));
+        md_gather64_kernel<<<g1, 256, 0, st>>>(key_b, v2, n_e, ka);
+        BWAMS_HIP(sort(ka, v2, i1, (size_t)n_e, 64));
+        md_opt_pts_kernel<<<g1, 256, 0, st>>>(loc, i2, i1, n_e, pts);
+        md_opt_link_kernel<<<g1, 256, 0, st>>>(kbuf, pts, n_e, x->d, parent);
+        BWAMS_HIP(hipMemsetAsync(min_t, 0xFF, (size_t)n_e * 8, st));
+        uint32_t *root = gid;                                // the group ordinals are done with
+        md_opt_root_kernel<<<g1, 256, 0, st>>>(ends, i2, head, parent, n_e, root, min_t);
+        md_opt_mark_kernel<<<g1, 256, 0, st>>>(ends, i2, head, root, min_t, n_e, x->optical);
+    }
     // fragments: by (unpaired, rank), then the key
     md_frag_keys_kernel<<<g1, 256, 0, st>>>(ends, n_e, none_ref, (int)tb, k1, ka, i1);
     BWAMS_HIP(sort(ka, i1, i2, n2, 16 + tb));
     md_gather64_kernel<<<g2, 256, 0, st>>>(k1, i2, (int64_t)n2, ka);
     BWAMS_HIP(sort(ka, i2, i1, n2, kb));
     md_mark_frags_kernel<<<g2, 256, 0, st>>>(kbuf, i1, (int64_t)n2, none_key, ends, dup, info + 3);
+    if (x && x->lib_counts)
+        md_lib_ends_kernel<<<g1, 256, 0, st>>>(ends0, loc, n_e, dup, x->optical, x->n_lib, x->lib_counts);
     BWAMS_HIP(hipMemcpyAsync(h, info + 2, 16, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());

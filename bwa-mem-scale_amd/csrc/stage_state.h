@@ -91,7 +91,10 @@ struct StageState {
         MdTemplates t;                       // templates and ends of the current records (bwams_bam_templates)
         MdDecide decide;                     // the decision's buffers (bwams_bam_markdup)
         DevBuf<uint8_t> dup; DevBuf<unsigned long long> cnt; DevBuf<uint32_t> sorted;
-        bool done = false;
+        DevBuf<uint8_t> optical, g_ids; DevBuf<unsigned long long> lib_counts;      // rule 12's marks, the groups table, rule 13's counts
+        DevBuf<int64_t> g_off; DevBuf<int32_t> g_ord, g_lib;
+        int32_t n_lib = 1;                   // of the last bwams_bam_templates2
+        bool done = false, loc_done = false; // loc_done: t.tloc / t.locs hold the current templates' (bwams_bam_templates2)
     } md;
     DevBuf<int32_t> heavy;        // per read: the wave tier's read list of whichever stage runs (chaining, selection, de-duplication, pairing)
     bwams_mem_opt_t opt{};

@@ -20,6 +20,9 @@
 // record's template ordinal in sorted order (with the run: in memory, or spilled after its records).  Close offsets each run's
 // ordinals by the templates of the runs before it in seq order, runs one bwams_dup_decide over all the ends, and sets or clears
 // FLAG 0x400 (bit 2 of the record's byte 19) in the merge buffer as each record is copied; the index does not read that bit.
+// After bwams_sorter_set_markdup a put_batch runs bwams_bam_templates2 with the sorter's copy of the groups table and also keeps the
+// put's bwams_dup_loc_t per end and its two record-level counts per library; close3 hands ends and locs to bwams_dup_decide2 and adds
+// the puts' record-level counts to its rows.
 // Plain C++ over the C-ABI (no HIP header), like fastq_io.cpp.
 #include <fcntl.h>
 #include <unistd.h>
@@ -37,6 +40,7 @@
 #include <vector>
 
 #include "bwams.h"
+#include "dup_groups.h"
 
 namespace {
 
@@ -62,6 +66,8 @@ struct Run {
     std::vector<uint32_t> tmpl;                       // markdup: each record's template ordinal, in sorted order (empty when spilled)
     std::vector<bwams_dup_end_t> ends;                // markdup: the batch's ends, tmpl local to the run
     int64_t n_tmpl = 0;
+    std::vector<bwams_dup_loc_t> loc;                 // after set_markdup: parallel to ends
+    std::vector<int64_t> rec_counts;                  // after set_markdup: secondary_or_supplementary[n_lib], then unmapped[n_lib]
 };
 
 // One run's records in order: from memory, or from its spill file through bounded buffers.
@@ -221,6 +227,11 @@ struct bwams_sorter {
     std::set<int64_t> seqs;
     std::vector<std::unique_ptr<Run>> runs;
     int64_t n_spill = 0, spilled_bytes = 0;
+    bool any_put = false;                             // a put or put_batch was called
+    bool md_set = false, has_groups = false;          // bwams_sorter_set_markdup: its table (copied) and options
+    bwams_dup_groups groups;
+    bwams_dup_opt_t opt{};
+    int64_t n_lib() const { return has_groups ? (int64_t)groups.libs.size() : 1; }
 };
 
 namespace {
@@ -367,6 +378,7 @@ int bwams_sorter_open(const char *path, int device, const void *bam_header, int6
 int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_t n_bytes, const bwams_bam_coord_t *coords,
                      int64_t n_records) {
     if (!s || seq < 0 || n_bytes < 0 || n_records < 0 || (n_bytes && !records) || (n_records && !coords)) return BWAMS_ERR_ARG;
+    { std::lock_guard<std::mutex> g(s->mu); s->any_put = true; }
     if (s->flags & BWAMS_SORT_MARKDUP) return BWAMS_ERR_ARG;            // sorted host records carry no template grouping
     const uint8_t *rec = static_cast<const uint8_t *>(records);
     if (int rc = check_run(s, rec, n_bytes, coords, n_records)) return rc;
@@ -385,10 +397,12 @@ int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_
 int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b) {
     if (!s || !b || seq < 0) return BWAMS_ERR_ARG;
     int64_t n = 0, n_t = 0, n_e = 0;
+    { std::lock_guard<std::mutex> g(s->mu); s->any_put = true; }
     if (int rc = bwams_bam_sort(b, &n)) return rc;
     const bool md = (s->flags & BWAMS_SORT_MARKDUP) != 0;
     if (md)
-        if (int rc = bwams_bam_templates(b, &n_t, &n_e)) return rc;
+        if (int rc = s->md_set ? bwams_bam_templates2(b, s->has_groups ? &s->groups : nullptr, &n_t, &n_e) : bwams_bam_templates(b, &n_t, &n_e))
+            return rc;
     try {
         auto r = std::make_unique<Run>();
         r->seq = seq; r->n_rec = n;
@@ -403,6 +417,13 @@ int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b) {
             r->ends.resize((size_t)n_e);
             r->tmpl.resize((size_t)n);
             if (int rc = bwams_bam_templates_fetch(b, r->ends.data(), n_e, r->tmpl.data(), 1)) return rc;
+            if (s->md_set) {
+                const int64_t n_lib = s->n_lib();
+                r->loc.resize((size_t)n_e);
+                r->rec_counts.resize((size_t)(2 * n_lib));
+                if (int rc = bwams_bam_templates_fetch_loc(b, r->loc.data(), n_e)) return rc;
+                if (int rc = bwams_bam_lib_record_counts(b, r->rec_counts.data(), r->rec_counts.data() + n_lib, n_lib)) return rc;
+            }
         }
         return take_run(s, std::move(r));
     } catch (...) {
@@ -413,7 +434,33 @@ int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b) {
 int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats) { return bwams_sorter_close2(s, stats, nullptr); }
 
 int bwams_sorter_close2(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats) {
+    return bwams_sorter_close3(s, stats, dup_stats, nullptr, 0);
+}
+
+int bwams_sorter_set_markdup(bwams_sorter_t *s, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt) {
+    if (!s || !(s->flags & BWAMS_SORT_MARKDUP)) return BWAMS_ERR_ARG;
+    if (opt && (opt->optical_distance < 0 || opt->max_optical_set < 0)) return BWAMS_ERR_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->any_put) return BWAMS_ERR_ARG;
+    try {
+        s->has_groups = groups != nullptr;
+        s->groups = groups ? *groups : bwams_dup_groups();
+    } catch (...) {
+        return BWAMS_ERR_NOMEM;
+    }
+    s->opt = opt ? *opt : bwams_dup_opt_t{};
+    s->md_set = true;
+    return BWAMS_OK;
+}
+
+int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats, bwams_dup_lib_stats_t *lib_stats,
+                        int64_t cap_lib) {
     if (!s) return BWAMS_ERR_ARG;
+    if (lib_stats && cap_lib < s->n_lib()) return BWAMS_ERR_CAPACITY;
+    for (int64_t l = 0; lib_stats && l < s->n_lib(); ++l) {                      // without BWAMS_SORT_MARKDUP the rows stay like this
+        memset(&lib_stats[l], 0, sizeof lib_stats[l]);
+        lib_stats[l].estimated_library_size = -1;
+    }
     const Clock::time_point t_all = Clock::now();
     float ms_deflate = 0, ms_write = 0, ms_decide = 0;
     int rc = BWAMS_OK;
@@ -432,11 +479,32 @@ int bwams_sorter_close2(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
             int64_t n_t = 0, n_e = 0;
             for (size_t k : by_seq) { base[k] = n_t; n_t += s->runs[k]->n_tmpl; n_e += (int64_t)s->runs[k]->ends.size(); }
             std::vector<bwams_dup_end_t> ends;
+            std::vector<bwams_dup_loc_t> loc;
             ends.reserve((size_t)n_e);
-            for (size_t k : by_seq)
+            if (s->md_set) loc.reserve((size_t)n_e);
+            for (size_t k : by_seq) {
                 for (bwams_dup_end_t e : s->runs[k]->ends) { e.tmpl += base[k]; ends.push_back(e); }
+                if (s->md_set) loc.insert(loc.end(), s->runs[k]->loc.begin(), s->runs[k]->loc.end());
+            }
             dup.resize((size_t)std::max<int64_t>(n_t, 1));
-            rc = bwams_dup_decide(s->device, ends.data(), n_e, n_t, dup.data(), &dst);
+            if (!s->md_set && !lib_stats) {
+                rc = bwams_dup_decide(s->device, ends.data(), n_e, n_t, dup.data(), &dst);
+            } else {                                                             // rules 11-13: the rows, and the totals from them
+                const int64_t n_lib = s->n_lib();
+                std::vector<bwams_dup_lib_stats_t> own((size_t)n_lib);
+                bwams_dup_lib_stats_t *rows = lib_stats ? lib_stats : own.data();
+                rc = bwams_dup_decide2(s->device, ends.data(), s->md_set ? loc.data() : nullptr, n_e, n_t, n_lib, &s->opt, dup.data(), nullptr,
+                                       rows);
+                for (int64_t l = 0; l < n_lib && !rc; ++l) {
+                    for (auto &r : s->runs)
+                        if (!r->rec_counts.empty()) {
+                            rows[l].secondary_or_supplementary += r->rec_counts[(size_t)l];
+                            rows[l].unmapped += r->rec_counts[(size_t)(n_lib + l)];
+                        }
+                    dst.unpaired_examined += rows[l].unpaired_examined; dst.unpaired_duplicates += rows[l].unpaired_duplicates;
+                    dst.pairs_examined += rows[l].pairs_examined; dst.pair_duplicates += rows[l].pair_duplicates;
+                }
+            }
             dst.templates = n_t;
             ms_decide = ms_since(t0);
         }

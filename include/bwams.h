@@ -417,7 +417,8 @@ int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t
 int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records);
 int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_coord_t *coords);
 /* Duplicate marking (csrc/markdup.hip): Picard MarkDuplicates' rules for query-grouped input — default SUM_OF_BASE_QUALITIES scoring,
- * one library, no optical duplicate detection, no barcodes.  bwams/markdup.py restates them.
+ * no barcodes.  Rules 1-8 are one library without optical duplicate detection (the calls without a 2 or 3 in their names); rules 9-15
+ * below them add read groups, libraries, optical duplicates and the metrics file.  bwams/markdup.py restates all of them.
  *  1. Template: a maximal run of consecutive records with byte-equal read names, in the batch's unsorted order.  This is the order
  *     bwams_bam_run produces, and the order an uploaded BAM is given in.  A template never spans two batches or two sorter puts.
  *  2. Primary: FLAG has neither 0x100 nor 0x800.  A primary's segment is "only" when 0x1 is clear.  When 0x1 is set, it is "first"
@@ -461,8 +462,85 @@ int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_c
  * not fit: BWAMS_ERR_NOMEM.  *st (may be NULL): rule 8's counts, records_marked 0.
  * _markdup: the batch alone is the whole input: _templates, the decision and the marking, all in HBM.  The unsorted records and the
  * sorted copy, when the current records have one, are marked, so bwams_bam_fetch, _fetch_bgzf, _sort and _sorted_fetch all see the
- * flags.  A second call gives the same records.  *st may be NULL. */
+ * flags.  A second call gives the same records.  *st may be NULL.
+ *
+ * Read groups, libraries, optical duplicates and the metrics (Picard where Picard is definite; where a choice was made the rule says so):
+ *  9. Read groups and libraries.  A groups table (bwams_dup_groups_t) is made from SAM header text.  Every @RG line gives a read group
+ *     whose ordinal is the line's place among the @RG lines.  Its ID is required: a line without one, or two lines with one ID, is
+ *     BWAMS_ERR_ARG.  Its LB is optional.  Libraries are the distinct LB values in order of first appearance, ordinals from 0; after
+ *     them comes one more, "Unknown Library", which always exists, so n_lib = distinct LBs + 1.  With no table n_lib = 1 and
+ *     everything is "Unknown Library".  A record's read group is the value of its first aux field with tag RG and type Z, found by
+ *     walking the aux fields by their types (SAMv1 §4.2.4: A c C s S i I f Z H B) to the record's end.  A field of unknown type
+ *     (or a B array of unknown element type), or one that runs past block_size, refuses the batch as rules 2-3 do, with a fifth
+ *     reason, "aux fields do not chain to the record's end"; rules 2-3 are checked over the whole batch first, so this
+ *     reason names the first such record of a batch they accept.  Only one record per template is walked: its first primary in record order, or its first record
+ *     when it has no primary; and only when a table is given (choice: without one no read group can be looked up, and the calls of
+ *     rules 1-8 keep accepting what they accept).  That record's read group is the template's; ordinal -1 means no RG field or a
+ *     value not in the table.  The template's library is its read group's; ordinal -1 and read groups without LB belong to
+ *     "Unknown Library".
+ * 10. Location, from the name of the record rule 9 names (without its NUL), split at ':'.  Exactly 5 fields: tile, x, y are fields
+ *     2, 3, 4 (from 0).  Exactly 7 or 8 fields: fields 4, 5, 6.  Any other count: no location.  A field's value is an optional '-',
+ *     then the decimal digits up to the first byte that is not a digit; the rest is ignored and no digits gives 0.  A value outside
+ *     int32 means no location.
+ * 11. Keys.  The library ordinal is the most significant part of the pair key and of the fragment key of rules 5-6: equal places in
+ *     two libraries are not duplicates of each other.  (The decision folds it into the refIDs, library * (largest refID + 1) + refID,
+ *     which must stay below 2^31: BWAMS_ERR_UNSUPPORTED otherwise.)
+ * 12. Optical duplicates, for a distance d > 0 (Picard's default is 100, and 2500 for patterned flow cells; 0 turns it off).  Only
+ *     pairs are examined.  In a group of pairs with equal key that holds between 2 and max_set members (Picard: 300000), two members
+ *     are close when both have a location, their read-group ordinals are equal (-1 equals -1), their tiles are equal, and
+ *     |x - x'| <= d and |y - y'| <= d, the differences taken in 64 bits.  Clusters are the connected components of "close"; a member
+ *     with no location is a cluster of its own.  A cluster's representative is the group's kept pair (rule 6) if it is in the
+ *     cluster, otherwise the member with the smallest template ordinal.  Every other member is an optical duplicate, so a group's
+ *     optical count is the sum over its clusters of (size - 1).  (Picard switches between two algorithms at a group size of 4; both
+ *     give this count.)  Nothing is written into the records: Picard's default TAGGING_POLICY is DontTag.
+ * 13. Per-library counts (bwams_dup_lib_stats_t), each attributed to the template's library: unpaired_examined, pairs_examined,
+ *     unpaired_duplicates, pair_duplicates as in rule 8; pair_optical_duplicates: rule 12; secondary_or_supplementary: records with
+ *     0x100 or 0x800 set and 0x4 clear; unmapped: records with 0x4 set; percent_duplication: rule 8's formula, 0 when the denominator
+ *     is 0; estimated_library_size: rule 14, -1 for none.  Summed over libraries, the first four equal bwams_dup_stats_t's.
+ * 14. Estimated library size: Picard's estimateLibrarySize, on the host in doubles with the C library's exp.  n = pairs_examined -
+ *     pair_optical_duplicates, c = pairs_examined - pair_duplicates.  None if n <= 0, n - c <= 0 or c <= 0.  Otherwise, with
+ *     f(x) = c/x - 1 + exp(-n/x): m = 1.0, M = 100.0; while f(M*c) > 0: M *= 10.0; 40 times: r = (m + M) / 2, u = f(r*c), stop if
+ *     u == 0, m = r if u > 0 else M = r; the result is (int64)(c * (m + M) / 2.0).  (1000, 900) gives 4660 and (2, 1) gives 1.
+ * 15. Metrics text, Picard's layout: a line "## htsjdk.samtools.metrics.StringHeader"; a line "# " and the caller's text; a line
+ *     "## METRICS CLASS\tpicard.sam.DuplicationMetrics"; the column line LIBRARY UNPAIRED_READS_EXAMINED READ_PAIRS_EXAMINED
+ *     SECONDARY_OR_SUPPLEMENTARY_RDS UNMAPPED_READS UNPAIRED_READ_DUPLICATES READ_PAIR_DUPLICATES READ_PAIR_OPTICAL_DUPLICATES
+ *     PERCENT_DUPLICATION ESTIMATED_LIBRARY_SIZE, tab-separated; one row per library that has any count above zero, in ordinal order;
+ *     an empty line.  PERCENT_DUPLICATION is printed as %.6f; ESTIMATED_LIBRARY_SIZE is left empty when there is none.  Picard's
+ *     histogram section is not written.
+ * The DT tag, REMOVE_DUPLICATES and barcode / UMI keys are out of scope.
+ * bwams_dup_groups_create: the table of header_text[0, n_text) (lines end at '\n', a '\r' before it dropped; fields are split at
+ * tabs); _info: its read groups and libraries (either pointer may be NULL); _library: library lib's name, owned by the table (NULL
+ * table: "Unknown Library" for 0), NULL outside [0, n_lib); _destroy (NULL allowed).  A host object; calls that take one only read it.
+ * _templates2: _templates, then rules 9-10 on the device for every template: the template's read group, library and location.
+ * groups may be NULL.  _templates_fetch_loc (after _templates2 on the current records, BWAMS_ERR_ARG otherwise): one bwams_dup_loc_t
+ * per end, parallel to _templates_fetch's ends (cap >= n_ends, BWAMS_ERR_CAPACITY otherwise).  _lib_record_counts (after _templates
+ * or _templates2): rule 13's two record-level counts of the batch per library (one library after _templates), n_lib values each;
+ * either pointer may be NULL; cap_lib < n_lib is BWAMS_ERR_CAPACITY.
+ * bwams_dup_decide2: bwams_dup_decide with rules 11-13.  loc: one per end, or NULL for library 0 and no location; every loc.lib must
+ * lie in [0, n_lib) and has in {0, 1} (BWAMS_ERR_ARG naming the first such end).  opt may be NULL: optical detection off;
+ * max_optical_set 0 means 300000; a negative value is BWAMS_ERR_ARG.  optical (n_templates bytes, may be NULL): 1 for every optical
+ * duplicate.  lib_stats (n_lib rows, may be NULL): rule 13, the two record-level counts 0.
+ * _markdup2: _markdup with a table and options: everything in HBM, *st and lib_stats[0, n_lib) (either may be NULL; cap_lib < n_lib
+ * is BWAMS_ERR_CAPACITY) with all counts filled.  With groups NULL and optical detection off it is _markdup: the same kernels, the
+ * same records, the same *st.
+ * bwams_dup_library_size: rule 14, -1 for none.  bwams_dup_metrics_text: rule 15 into out[0, cap) for lib_stats[0, n_lib) (n_lib must
+ * be the table's, 1 for a NULL table: BWAMS_ERR_ARG otherwise); comment may be NULL; *n_out: the bytes written, or needed with
+ * BWAMS_ERR_CAPACITY, as bwams_sam_header. */
 int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends);
+int bwams_dup_groups_create(const char *header_text, int64_t n_text, bwams_dup_groups_t **out);
+int bwams_dup_groups_info(const bwams_dup_groups_t *g, int64_t *n_rg, int64_t *n_lib);
+const char *bwams_dup_groups_library(const bwams_dup_groups_t *g, int64_t lib);
+void bwams_dup_groups_destroy(bwams_dup_groups_t *g);
+int bwams_bam_templates2(bwams_batch_t *b, const bwams_dup_groups_t *groups, int64_t *n_templates, int64_t *n_ends);
+int bwams_bam_templates_fetch_loc(bwams_batch_t *b, bwams_dup_loc_t *loc, int64_t cap);
+int bwams_bam_lib_record_counts(bwams_batch_t *b, int64_t *secondary_or_supplementary, int64_t *unmapped, int64_t cap_lib);
+int bwams_dup_decide2(int device, const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_ends, int64_t n_templates,
+                      int64_t n_lib, const bwams_dup_opt_t *opt, uint8_t *dup, uint8_t *optical, bwams_dup_lib_stats_t *lib_stats);
+int bwams_bam_markdup2(bwams_batch_t *b, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt, bwams_dup_stats_t *st,
+                       bwams_dup_lib_stats_t *lib_stats, int64_t cap_lib);
+int64_t bwams_dup_library_size(int64_t n, int64_t c);
+int bwams_dup_metrics_text(const bwams_dup_groups_t *g, const bwams_dup_lib_stats_t *lib_stats, int64_t n_lib, const char *comment,
+                           char *out, int64_t cap, int64_t *n_out);
 int bwams_bam_templates_fetch(bwams_batch_t *b, bwams_dup_end_t *ends, int64_t cap, uint32_t *rec_tmpl, int32_t sorted);
 int bwams_dup_decide(int device, const bwams_dup_end_t *ends, int64_t n_ends, int64_t n_templates, uint8_t *dup, bwams_dup_stats_t *st);
 int bwams_bam_markdup(bwams_batch_t *b, bwams_dup_stats_t *st);
@@ -972,6 +1050,16 @@ int bwams_sorter_put(bwams_sorter_t *s, int64_t seq, const void *records, int64_
 int bwams_sorter_put_batch(bwams_sorter_t *s, int64_t seq, bwams_batch_t *b);
 int bwams_sorter_close(bwams_sorter_t *s, bwams_sorter_stats_t *stats);   /* stats may be NULL */
 int bwams_sorter_close2(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup);
+/* _set_markdup: the groups table (copied; may be NULL) and the options (may be NULL: optical detection off) of a sorter opened with
+ * BWAMS_SORT_MARKDUP, before its first put: BWAMS_ERR_ARG otherwise.  Every put_batch then runs bwams_bam_templates2 with the table
+ * and keeps the put's bwams_dup_loc_t beside its ends (24 B per end, host memory, outside mem_bytes) and its two record-level counts
+ * per library; a library ordinal means the same in every put, the table being the sorter's.
+ * _close3: _close2 through bwams_dup_decide2 over all the puts, with rule 13's rows in lib_stats[0, n_lib) (may be NULL; cap_lib <
+ * n_lib is BWAMS_ERR_CAPACITY and leaves the sorter open).  Without _set_markdup: one library, no optical duplicates, the two record-level counts 0,
+ * _close2's file. */
+int bwams_sorter_set_markdup(bwams_sorter_t *s, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt);
+int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup, bwams_dup_lib_stats_t *lib_stats,
+                        int64_t cap_lib);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

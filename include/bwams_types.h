@@ -273,6 +273,30 @@ typedef struct bwams_dup_stats {
     int32_t pad_;
 } bwams_dup_stats_t;
 
+/* Options of the decision (rule 12): optical_distance is d, 0 for no optical duplicate detection (Picard: 100, 2500 for patterned
+ * flow cells); max_optical_set is the largest group examined, 0 for Picard's 300000. */
+typedef struct bwams_dup_opt {
+    int32_t optical_distance;
+    int32_t pad_;
+    int64_t max_optical_set;
+} bwams_dup_opt_t;
+
+/* One end's library, read group and flow-cell location (rules 9-10), parallel to bwams_dup_end_t: lib in [0, n_lib), rg the read
+ * group's ordinal or -1; has is 1 when the read name gives a location (tile, x, y) and 0 otherwise, and then tile, x and y are 0. */
+typedef struct bwams_dup_loc {
+    int32_t lib, rg, tile, x, y, has;
+} bwams_dup_loc_t;
+
+/* One library's row of the metrics (rule 13).  estimated_library_size is -1 when rule 14 gives none. */
+typedef struct bwams_dup_lib_stats {
+    int64_t unpaired_examined, pairs_examined, secondary_or_supplementary, unmapped, unpaired_duplicates, pair_duplicates,
+            pair_optical_duplicates, estimated_library_size;
+    double  percent_duplication;
+} bwams_dup_lib_stats_t;
+
+/* The read groups and libraries of a SAM header (rule 9): a host object. */
+typedef struct bwams_dup_groups bwams_dup_groups_t;
+
 #ifdef __cplusplus
 }
 #endif
