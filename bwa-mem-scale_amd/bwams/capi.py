@@ -59,6 +59,9 @@ SYMBOLS = [
     "bwams_reader_open_bam", "bwams_reader_bam_header",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
+    "bwams_depth_open", "bwams_depth_close", "bwams_depth_reset", "bwams_depth_add_batch", "bwams_depth_add_records", "bwams_depth_finish",
+    "bwams_depth_summary", "bwams_depth_hist", "bwams_depth_windows", "bwams_depth_runs", "bwams_depth_fetch", "bwams_depth_text",
+    "bwams_sorter_set_depth",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -94,6 +97,8 @@ DUP_LOC_DTYPE = np.dtype([(n, "<i4") for n in ("lib", "rg", "tile", "x", "y", "h
 DUP_LIB_STATS_DTYPE = np.dtype([(n, "<i8") for n in ("unpaired_examined", "pairs_examined", "secondary_or_supplementary", "unmapped",
                                                      "unpaired_duplicates", "pair_duplicates", "pair_optical_duplicates",
                                                      "estimated_library_size")] + [("percent_duplication", "<f8")])   # bwams_dup_lib_stats_t
+DEPTH_REF_DTYPE = np.dtype([("length", "<i8"), ("bases", "<i8"), ("min", "<i4"), ("max", "<i4")])         # bwams_depth_ref_t
+assert DEPTH_REF_DTYPE.itemsize == 24
 assert DUP_LOC_DTYPE.itemsize == 24 and DUP_LIB_STATS_DTYPE.itemsize == 72
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
@@ -466,6 +471,10 @@ class Sorter:
         _chk(lib().bwams_sorter_set_markdup(self.h, _groups_h(groups), C.byref(o)), "bwams_sorter_set_markdup")
         self._n_lib = groups.n_lib if groups is not None else 1
 
+    def set_depth(self, depth: "Depth") -> None:
+        """bwams_sorter_set_depth: close adds the merged stream, as written, to the handle; before the first put."""
+        _chk(lib().bwams_sorter_set_depth(self.h, depth.h), "bwams_sorter_set_depth")
+
     def close3(self) -> SorterStats:
         """bwams_sorter_close3: close()'s stats, .dup, and rule 13's rows as .lib (DUP_LIB_STATS_DTYPE)."""
         st, dup = SorterStats(), DupStats()
@@ -484,6 +493,96 @@ class Sorter:
             _chk(lib().bwams_sorter_close2(h, C.byref(st), C.byref(dup)), "bwams_sorter_close2")
         st.dup = dup
         return st
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DepthOpt(C.Structure):
+    _fields_ = [("exclude", C.c_uint32), ("min_mapq", C.c_int32), ("count_deletions", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Depth:
+    """Per-base depth of coverage on one GPU (bwams_depth_t): add, finish once, query."""
+
+    def __init__(self, l_ref, device: int = 0, exclude: int = 0x704, min_mapq: int = 0, count_deletions: bool = False):
+        self.h = C.c_void_p()
+        self.l_ref = np.ascontiguousarray(l_ref, np.int32)
+        o = DepthOpt(exclude, min_mapq, int(count_deletions), 0)
+        _chk(lib().bwams_depth_open(device, _p(self.l_ref), len(self.l_ref), C.byref(o), C.byref(self.h)), "bwams_depth_open")
+
+    def add_batch(self, batch: "Batch") -> int:
+        """The batch's current BAM records, read in HBM; -> the records that counted."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_depth_add_batch(self.h, batch.h, C.byref(n)), "bwams_depth_add_batch")
+        return n.value
+
+    def add_records(self, records: bytes) -> int:
+        records = bytes(records)
+        n = C.c_int64(0)
+        _chk(lib().bwams_depth_add_records(self.h, records, len(records), C.byref(n)), "bwams_depth_add_records")
+        return n.value
+
+    def finish(self) -> "Depth":
+        _chk(lib().bwams_depth_finish(self.h), "bwams_depth_finish")
+        return self
+
+    def reset(self) -> None:
+        _chk(lib().bwams_depth_reset(self.h), "bwams_depth_reset")
+
+    def summary(self) -> np.ndarray:
+        rows = np.zeros(len(self.l_ref), DEPTH_REF_DTYPE)
+        _chk(lib().bwams_depth_summary(self.h, _p(rows), len(rows)), "bwams_depth_summary")
+        return rows
+
+    def hist(self, ref: int, n_bins: int) -> np.ndarray:
+        h = np.zeros(max(n_bins, 1), np.int64)
+        _chk(lib().bwams_depth_hist(self.h, ref, _p(h), n_bins), "bwams_depth_hist")
+        return h
+
+    def windows(self, w: int) -> np.ndarray:
+        n = C.c_int64(0)
+        _chk(lib().bwams_depth_windows(self.h, w, None, 0, C.byref(n)), "bwams_depth_windows")
+        sums = np.zeros(n.value, np.int64)
+        _chk(lib().bwams_depth_windows(self.h, w, _p(sums), len(sums), C.byref(n)), "bwams_depth_windows")
+        return sums
+
+    def runs(self, ref: int, beg: int, end: int, cap: int | None = None):
+        """(start, depth) of rule 10; cap: the arrays' size (default: asked for first)."""
+        n = C.c_int64(0)
+        if cap is None:
+            _chk(lib().bwams_depth_runs(self.h, ref, beg, end, None, None, 0, C.byref(n)), "bwams_depth_runs")
+            cap = n.value
+        start, depth = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        rc = lib().bwams_depth_runs(self.h, ref, beg, end, _p(start), _p(depth), cap, C.byref(n))
+        self.n_runs = n.value
+        _chk(rc, "bwams_depth_runs")
+        return start[:n.value], depth[:n.value]
+
+    def fetch(self, ref: int, beg: int = 0, end: int | None = None) -> np.ndarray:
+        end = int(self.l_ref[ref]) if end is None else end
+        out = np.zeros(max(end - beg, 1), np.int32)
+        _chk(lib().bwams_depth_fetch(self.h, ref, beg, end, _p(out)), "bwams_depth_fetch")
+        return out[:max(end - beg, 0)]
+
+    def text(self, names, what: int, arg: int = 0) -> str:
+        """bwams_depth_text: what = 0 summary, 1 distribution (arg: n_bins), 2 windows BED (arg: w)."""
+        flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
+        n = C.c_int64(0)
+        rc = lib().bwams_depth_text(self.h, flat, what, arg, None, 0, C.byref(n))
+        if rc != -4:
+            _chk(rc, "bwams_depth_text")
+        buf = C.create_string_buffer(max(n.value, 1))
+        _chk(lib().bwams_depth_text(self.h, flat, what, arg, buf, n.value, C.byref(n)), "bwams_depth_text")
+        return buf.raw[:n.value].decode("latin-1")
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_depth_close(h), "bwams_depth_close")
 
     def __del__(self):
         try:
@@ -759,6 +858,19 @@ def lib():
         L.bwams_dup_metrics_text.argtypes = [vp, vp, i64, C.c_char_p, vp, i64, vp]
         L.bwams_sorter_set_markdup.argtypes = [vp, vp, vp]
         L.bwams_sorter_close3.argtypes = [vp, vp, vp, vp, i64]
+        L.bwams_depth_open.argtypes = [C.c_int, vp, i32, vp, vp]
+        L.bwams_depth_close.argtypes = [vp]
+        L.bwams_depth_reset.argtypes = [vp]
+        L.bwams_depth_add_batch.argtypes = [vp, vp, vp]
+        L.bwams_depth_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_depth_finish.argtypes = [vp]
+        L.bwams_depth_summary.argtypes = [vp, vp, i64]
+        L.bwams_depth_hist.argtypes = [vp, i32, vp, i32]
+        L.bwams_depth_windows.argtypes = [vp, i32, vp, i64, vp]
+        L.bwams_depth_runs.argtypes = [vp, i32, i32, i32, vp, vp, i64, vp]
+        L.bwams_depth_fetch.argtypes = [vp, i32, i32, i32, vp]
+        L.bwams_depth_text.argtypes = [vp, vp, i32, i32, vp, i64, vp]
+        L.bwams_sorter_set_depth.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]

@@ -12,6 +12,35 @@
 
 using namespace bwams;
 
+namespace bwams {
+int bam_record_offsets(const char *who, const void *bam, int64_t n_bytes, std::vector<int64_t> *offsets, int32_t *max_rid) {
+    const uint8_t *p = static_cast<const uint8_t *>(bam);
+    auto i32 = [&](int64_t at) { int32_t v; memcpy(&v, p + at, 4); return v; };
+    std::vector<int64_t> &off = *offsets;
+    off.assign(1, 0);
+    *max_rid = -1;
+    auto rec = [&]() { return std::string(who) + ": record " + std::to_string(off.size() - 1); };       // built on an error only
+    for (int64_t at = 0; at < n_bytes;) {                   // the block_size chain, and what the kernels read inside it
+        if (n_bytes - at < 4) { set_last_error(rec() + " is cut off"); return BWAMS_ERR_ARG; }
+        const int64_t bs = (uint32_t)i32(at);
+        if (bs < 32 || bs > n_bytes - at - 4) {
+            set_last_error(rec() + ": block_size " + std::to_string(bs) + (bs < 32 ? " < 32" : " runs past n_bytes"));
+            return BWAMS_ERR_ARG;
+        }
+        const int32_t rid = i32(at + 4), pos = i32(at + 8);
+        const int64_t l_name = p[at + 12], n_cig = (int64_t)p[at + 16] | (int64_t)p[at + 17] << 8;
+        if (rid < -1 || pos < -1 || pos > 0x7FFFFFFE || 32 + l_name + 4 * n_cig > bs) {
+            set_last_error(rec() + ": refID < -1, POS outside [-1, 2^31 - 2], or its name and CIGAR run past block_size");
+            return BWAMS_ERR_ARG;
+        }
+        *max_rid = std::max(*max_rid, rid);
+        at += 4 + bs;
+        off.push_back(at);
+    }
+    return BWAMS_OK;
+}
+}  // namespace bwams
+
 extern "C" {
 /* ------------------------------------------------------------ BAM records (bam.hip) ---- */
 
@@ -118,30 +147,9 @@ int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t
         set_last_error("bwams_bam_upload: a batch and host records are required");
         return BWAMS_ERR_ARG;
     }
-    const uint8_t *p = static_cast<const uint8_t *>(bam);
-    auto i32 = [&](int64_t at) { int32_t v; memcpy(&v, p + at, 4); return v; };
-    std::vector<int64_t> off(1, 0);
+    std::vector<int64_t> off;
     int32_t max_rid = -1;
-    for (int64_t at = 0; at < n_bytes;) {                   // the block_size chain, and what the key kernel reads inside it
-        const int64_t k = (int64_t)off.size() - 1;
-        if (n_bytes - at < 4) { set_last_error("bwams_bam_upload: record " + std::to_string(k) + " is cut off"); return BWAMS_ERR_ARG; }
-        const int64_t bs = (uint32_t)i32(at);
-        if (bs < 32 || bs > n_bytes - at - 4) {
-            set_last_error("bwams_bam_upload: record " + std::to_string(k) + ": block_size " + std::to_string(bs) +
-                           (bs < 32 ? " < 32" : " runs past n_bytes"));
-            return BWAMS_ERR_ARG;
-        }
-        const int32_t rid = i32(at + 4), pos = i32(at + 8);
-        const int64_t l_name = p[at + 12], n_cig = (int64_t)p[at + 16] | (int64_t)p[at + 17] << 8;
-        if (rid < -1 || pos < -1 || pos > 0x7FFFFFFE || 32 + l_name + 4 * n_cig > bs) {
-            set_last_error("bwams_bam_upload: record " + std::to_string(k) + ": refID < -1, POS outside [-1, 2^31 - 2], or its name and CIGAR "
-                           "run past block_size");
-            return BWAMS_ERR_ARG;
-        }
-        max_rid = std::max(max_rid, rid);
-        at += 4 + bs;
-        off.push_back(at);
-    }
+    if (int rc = bam_record_offsets("bwams_bam_upload", bam, n_bytes, &off, &max_rid)) return rc;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     StageState *s;
     int rc = get_state(b, &s);

@@ -37,6 +37,7 @@ struct Knobs {
     int bsw_pk = 1;                // BWAMS_BSW_PK=0: the 32-bit eight-task banded-SW kernel
     int chain_batch = 1;           // BWAMS_CHAIN_BATCH=0: chaining's wave tier takes one seed at a time (chain.hip: chain_seeds_batch)
     int ert_fat = 1;               // BWAMS_ERT_FAT=0: the ERT walk reads the reference's two tables only (no entry + tree-head table)
+    int depth_combine = 1;         // BWAMS_DEPTH_COMBINE=0: the depth add issues one atomic per lane (no folding of equal slots inside a wave)
     int ert_grid = -1, ert_ticket = 1;   // BWAMS_ERT_GRID (blocks per CU, 0 = one block per 256 bases) / BWAMS_ERT_TICKET=0 (round robin)
 };
 const Knobs &knobs();
@@ -260,6 +261,28 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
 void launch_md_apply(uint8_t *bam, const int64_t *rec_off, const uint32_t *perm, const uint32_t *rtmpl, const uint8_t *dup, int64_t n_rec,
                      unsigned long long *n_marked, int cu_count, hipStream_t st);
 void launch_md_gather32(const uint32_t *src, const uint32_t *idx, int64_t n, uint32_t *dst, int cu_count, hipStream_t st);
+
+// api_bam.hip: the offsets of host BAM records bam[0, n_bytes) (n + 1 of them) from their block_size chain, with the checks of
+// bwams_bam_upload (every record whole, block_size >= 32, refID >= -1, POS in [-1, 2^31 - 2], name and CIGAR inside the record) and
+// the largest refID; BWAMS_ERR_ARG with `who` and the first bad record in the last error.
+int bam_record_offsets(const char *who, const void *bam, int64_t n_bytes, std::vector<int64_t> *offsets, int32_t *max_rid);
+
+// depth.hip: depth of coverage (rules in include/bwams.h above bwams_depth_open).  slots: l_ref[r] + 1 int32 per reference from
+// slot_off[r] (n_ref + 1 entries, device); differences while records are added, depths after the scan.  check: *bad = min(*bad, index
+// of a record with an op code above 8).  add: rule 2's filter and rule 3's stretches of the records at bam + rec_off[r]; *n_counted +=
+// the records that passed.  summary: sum / mn / mx per reference (zeroed / INT_MAX / 0 by the caller).  windows: sums[win_off[r] +
+// pos / w] (zeroed by the caller).  hist: slots [lo, hi) into hist[0, n_bins) (zeroed by the caller), the last bin open-ended.
+// gather: depth[k] = slots[base + start[k]].
+constexpr int kDepthHistLds = 4096;      // depths below this are counted in LDS
+void launch_depth_check(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, unsigned long long *bad, int cu_count, hipStream_t st);
+void launch_depth_add(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const bwams_depth_opt_t &opt, int32_t n_ref,
+                      const int64_t *slot_off, int32_t *slots, unsigned long long *n_counted, int combine, int cu_count, hipStream_t st);
+void launch_depth_summary(const int32_t *slots, const int64_t *slot_off, int32_t n_ref, int64_t n_slots, unsigned long long *sum,
+                          int32_t *mn, int32_t *mx, int cu_count, hipStream_t st);
+void launch_depth_windows(const int32_t *slots, const int64_t *slot_off, int32_t n_ref, int64_t n_slots, const int64_t *win_off, int32_t w,
+                          unsigned long long *sums, int cu_count, hipStream_t st);
+void launch_depth_hist(const int32_t *slots, int64_t lo, int64_t hi, int32_t n_bins, unsigned long long *hist, int cu_count, hipStream_t st);
+void launch_depth_gather(const int32_t *slots, int64_t base, const int32_t *start, int64_t n, int32_t *depth, int cu_count, hipStream_t st);
 
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);
@@ -485,6 +508,22 @@ template <class F> int with_tmp(bwams_batch *b, const char *who, F &&call) {    
     if (e == hipSuccess) {
         if (int rc = tmp_reserve(b, tb)) return rc;
         e = call(b->d_tmp.p, tb);
+    }
+    if (e == hipSuccess) return BWAMS_OK;
+    set_last_error(std::string(who) + " -> " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
+}
+// The same for a handle that is no batch: its own temporary storage, grown once `st` has drained.
+template <class F> int with_tmp(DevBuf<> &tmp, hipStream_t st, const char *who, F &&call) {
+    size_t tb = 0;
+    hipError_t e = call(nullptr, tb);
+    if (e == hipSuccess && (tb > tmp.cap || !tmp.p)) {           // never null: rocPRIM reads a null pointer as the size query
+        e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = tmp.alloc(tb > 256 ? tb : 256);
+    }
+    if (e == hipSuccess) {
+        tb = tmp.cap;
+        e = call(tmp.p, tb);
     }
     if (e == hipSuccess) return BWAMS_OK;
     set_last_error(std::string(who) + " -> " + hipGetErrorString(e));

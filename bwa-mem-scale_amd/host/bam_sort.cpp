@@ -23,6 +23,9 @@
 // After bwams_sorter_set_markdup a put_batch runs bwams_bam_templates2 with the sorter's copy of the groups table and also keeps the
 // put's bwams_dup_loc_t per end and its two record-level counts per library; close3 hands ends and locs to bwams_dup_decide2 and adds
 // the puts' record-level counts to its rows.
+// After bwams_sorter_set_depth close also hands the merged stream, as written, to the depth handle: every flushed piece goes to
+// bwams_depth_add_records in whole records; the bytes of a record that the piece's end cuts wait in a carry buffer for the next piece, so
+// the record is added once, with its final flag, wherever the pieces cut.
 // Plain C++ over the C-ABI (no HIP header), like fastq_io.cpp.
 #include <fcntl.h>
 #include <unistd.h>
@@ -40,6 +43,7 @@
 #include <vector>
 
 #include "bwams.h"
+#include "depth_host.h"
 #include "dup_groups.h"
 
 namespace {
@@ -231,6 +235,7 @@ struct bwams_sorter {
     bool md_set = false, has_groups = false;          // bwams_sorter_set_markdup: its table (copied) and options
     bwams_dup_groups groups;
     bwams_dup_opt_t opt{};
+    bwams_depth_t *depth = nullptr;                   // bwams_sorter_set_depth: close adds the merged stream to it (the caller's handle)
     int64_t n_lib() const { return has_groups ? (int64_t)groups.libs.size() : 1; }
 };
 
@@ -453,6 +458,23 @@ int bwams_sorter_set_markdup(bwams_sorter_t *s, const bwams_dup_groups_t *groups
     return BWAMS_OK;
 }
 
+int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d) {
+    const char *why = !s || !d ? "a sorter and a depth handle are required"
+                      : bwams::depth_device(d) != s->device ? "the depth handle is on another device than the sorter"
+                      : bwams::depth_l_ref(d) != s->l_ref ? "the depth handle's reference lengths are not the sorter header's" : nullptr;
+    if (why) {
+        bwams::set_last_error(std::string("bwams_sorter_set_depth: ") + why);
+        return BWAMS_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->any_put) {
+        bwams::set_last_error("bwams_sorter_set_depth: called after the sorter's first put");
+        return BWAMS_ERR_ARG;
+    }
+    s->depth = d;
+    return BWAMS_OK;
+}
+
 int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats, bwams_dup_lib_stats_t *lib_stats,
                         int64_t cap_lib) {
     if (!s) return BWAMS_ERR_ARG;
@@ -534,8 +556,34 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         std::vector<uint8_t> gz((size_t)bwams_deflate_bound(kPiece));
         std::vector<int64_t> sizes;
         int64_t fill = 0, flushed = 0;                                           // bytes in buf, record-stream bytes flushed
+        // set_depth: the stream up to depth_at is added; whole_end is the end of the last record copied whole and open_end that of
+        // the record being copied; carry holds stream bytes [depth_at, flushed) of the record that the last piece's end cut
+        int64_t depth_at = 0, whole_end = 0, open_end = 0, carry_end = 0;
+        std::vector<uint8_t> carry;
+        auto depth_add = [&]() -> int {
+            if (whole_end > depth_at) {
+                int64_t from = depth_at;
+                if (from < flushed) {                                            // the cut record ends in this piece
+                    carry.insert(carry.end(), buf.data(), buf.data() + (carry_end - flushed));
+                    if (int e = bwams_depth_add_records(s->depth, carry.data(), (int64_t)carry.size(), nullptr)) return e;
+                    carry.clear();
+                    from = carry_end;
+                }
+                if (whole_end > from)
+                    if (int e = bwams_depth_add_records(s->depth, buf.data() + (from - flushed), whole_end - from, nullptr)) return e;
+                depth_at = whole_end;
+            }
+            if (flushed + fill > depth_at) {                                     // the piece ends inside a record
+                const int64_t from = std::max(depth_at, flushed);
+                carry.insert(carry.end(), buf.data() + (from - flushed), buf.data() + fill);
+                carry_end = open_end;
+            }
+            return BWAMS_OK;
+        };
         auto flush = [&]() -> int {
             if (fill == 0) return BWAMS_OK;
+            if (s->depth)
+                if (int e = depth_add()) return e;
             Clock::time_point t0 = Clock::now();
             int64_t got = 0;
             if (int e = bwams_deflater_run(s->def, buf.data(), fill, 0, gz.data(), (int64_t)gz.size(), 0, 0, &got, nullptr)) return e;
@@ -576,6 +624,7 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
                 d = dup[(size_t)(base[k] + t)] != 0;
                 n_marked += d;
             }
+            open_end = x + cd.size;
             for (int64_t done = 0; done < cd.size && !rc;) {                   // a record larger than the piece goes in parts
                 const int64_t k2 = std::min<int64_t>(cd.size - done, kPiece - fill);
                 memcpy(buf.data() + fill, p + done, (size_t)k2);
@@ -585,6 +634,7 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
                 }
                 fill += k2;
                 done += k2;
+                if (done == cd.size) whole_end = open_end;
                 if (fill == kPiece) rc = flush();
             }
             x += cd.size;

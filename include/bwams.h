@@ -53,6 +53,7 @@ const char *bwams_last_error(void);
  *   BWAMS_DEDUP_SEQ=1, BWAMS_PAIR_DROP_PLAN, BWAMS_TRACE_PAIR   fallback paths forced by tests (tests/test_gpu_dedup_limits.py runs its batches under
  *     BWAMS_DEDUP_SEQ=1 as well); a line per launch of the paired-end tail
  *   BWAMS_DEDUP_COUNT=1   bwams_dedup_run counts its reads per tier and its patch alignments per variant (bwams_debug_dedup_counts)
+ *   BWAMS_DEPTH_COMBINE=0   the depth add issues one atomic per lane instead of folding equal slots inside a wave (tools/depth_rate.py)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
 int bwams_device_count(int *n);
@@ -1060,6 +1061,84 @@ int bwams_sorter_close2(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
 int bwams_sorter_set_markdup(bwams_sorter_t *s, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt);
 int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup, bwams_dup_lib_stats_t *lib_stats,
                         int64_t cap_lib);
+/* Depth of coverage (csrc/depth.hip, csrc/api_depth.hip, host/depth_text.cpp): per-base depth accumulated on the device from a
+ * batch's BAM records, from host records, or from the sorted BAM writer's merged stream; finished once, then queried.  The rules
+ * are this library's own, modelled on `samtools depth` without -s and on `mosdepth --fast-mode`; no byte parity with either is
+ * claimed.  bwams/depth.py restates them in numpy and is what the tests compare against.
+ *  1. References.  The handle is made from n_ref lengths, l_ref[r] >= 0.  Depth is defined for positions [0, l_ref[r]) of each
+ *     reference.  The handle holds sum(l_ref) + n_ref 32-bit counters in HBM (12.4 GB at GRCh38 size); when they do not fit the
+ *     open returns BWAMS_ERR_NOMEM.
+ *  2. Which records count.  A record counts when (FLAG & exclude) == 0 (default exclude 0x704: unmapped, secondary, QC-fail,
+ *     duplicate), MAPQ >= min_mapq (default 0), 0 <= refID < n_ref, and n_cigar_op > 0.  Supplementary records count unless the
+ *     caller excludes 0x800.  A record that does not count is skipped; it does not refuse the call.
+ *  3. What a record covers.  The CIGAR is walked from POS: M, = and X cover their length and advance; D advances, and covers only
+ *     with count_deletions; N advances without covering; I, S, H and P do neither.  Positions below 0 or at or past l_ref[refID] are
+ *     clipped, not refused: a record that runs off the end of its reference covers up to the end.  Only the CIGAR field counts; a
+ *     long CIGAR parked in a CG tag is not looked up.  A record with an op code above 8 refuses the whole call with BWAMS_ERR_ARG,
+ *     whether it would count or not (choice: the check does not depend on the filter); bwams_last_error names the first such
+ *     record; nothing of that call is added (all records are checked first, then added).
+ *  4. No mate-overlap correction: every record counts by itself, as in `samtools depth` without -s.  Correcting for overlapping
+ *     mates is out of scope.
+ *  5. Accumulation.  Depth is the sum over all added records, in any order, over any number of calls.  More than 2^31 - 1 records
+ *     added in total (counted or not): BWAMS_ERR_UNSUPPORTED, and nothing of that call is added.
+ *  6. State.  _finish turns the accumulated counters into depths, in place (a second _finish does nothing).  After it an add is
+ *     BWAMS_ERR_ARG; before it a query is BWAMS_ERR_ARG.  _reset zeroes the handle for reuse, finished or not.
+ *  7. Summary per reference: length; bases, the sum of the depth as int64; min; max.  min and max are 0 for a reference of length 0.
+ *  8. Histogram for one reference, or for ref = -1 all references: hist[v] is the number of positions of depth v for v < n_bins - 1,
+ *     hist[n_bins - 1] the number of positions at or above n_bins - 1.  Counts are int64; 2 <= n_bins <= 2^20.
+ *  9. Windows of w >= 1 bases: reference r has ceil(l_ref[r] / w) windows, the references' windows follow each other in reference
+ *     order, a reference's last window may be short, a reference of length 0 has none.  A window's value is the int64 sum of the
+ *     depth in it; the mean exists in the text only.
+ * 10. Runs over [beg, end) of one reference (0 <= beg <= end <= l_ref[ref]): a run is a maximal stretch of equal depth inside the
+ *     range; start[k] is its first position and depth[k] its depth.  Zero-depth runs are included.  The first run starts at beg,
+ *     also when beg lies inside a longer run.  When the runs do not fit cap: BWAMS_ERR_CAPACITY with *n the number needed.
+ * 11. Text (bwams_depth_text; names: n_ref names, each ending in NUL, back to back).  Three texts:
+ *     BWAMS_DEPTH_TEXT_SUMMARY: a header line, one row per reference, a `total` row; chrom, length, bases, mean, min, max separated by
+ *       tabs; mean = bases / length printed with %.2f, 0.00 for length 0; the total row's min and max are over the references of
+ *       length > 0 (0 when there is none).  Two references c1 (10 bases, depths 2 2 2 2 2 0 0 0 0 1) and c2 (length 0):
+ *         "chrom\tlength\tbases\tmean\tmin\tmax\n" "c1\t10\t11\t1.10\t0\t2\n" "c2\t0\t0\t0.00\t0\t0\n" "total\t10\t11\t1.10\t0\t2\n"
+ *     BWAMS_DEPTH_TEXT_DIST (arg: n_bins of rule 8, 0 for 1024): chrom, depth, and the fraction of positions at or above that depth
+ *       printed with %.4f; rows from the largest occupied bin down to 0; a `total` block first, then a block per reference; a
+ *       reference (or a total) of length 0 has no rows.  The same handle:
+ *         "total\t2\t0.5000\n" "total\t1\t0.6000\n" "total\t0\t1.0000\n" "c1\t2\t0.5000\n" "c1\t1\t0.6000\n" "c1\t0\t1.0000\n"
+ *     BWAMS_DEPTH_TEXT_WINDOWS (arg: w of rule 9): a BED line per window: chrom, start, end, mean = sum / (end - start) with %.2f.
+ *       The same handle, w = 4: "c1\t0\t4\t2.00\n" "c1\t4\t8\t0.50\n" "c1\t8\t10\t0.50\n"
+ *     A per-base BED file is out of scope (tens of gigabytes of text at 30x); rule 10's arrays are the interface for that.
+ * bwams_depth_open: a zeroed handle on `device` (opt may be NULL; exclude above 0xFFFF, reserved != 0, n_ref < 0 or a negative
+ * length: BWAMS_ERR_ARG).  _close (NULL allowed).  _add_batch: the batch's current BAM records (bwams_bam_run / _upload left them,
+ * BWAMS_ERR_ARG before either), read in HBM; the batch must be on the handle's device (BWAMS_ERR_ARG); after bwams_bam_markdup the
+ * records carry 0x400, so duplicates drop out by rule 2.  _add_records: host records bam[0, n_bytes), uploaded; their block_size
+ * chain is checked as bwams_bam_upload checks it (BWAMS_ERR_ARG).  *n_counted (may be NULL): the records of this call that rule 2
+ * let through.  _summary: n_ref rows (cap < n_ref: BWAMS_ERR_CAPACITY).  _hist: ref in [-1, n_ref).  _windows: *n (may be NULL) the
+ * number of windows, needed or written; sums may be NULL to ask for it; cap too small: BWAMS_ERR_CAPACITY.  _runs: start and depth
+ * may both be NULL to ask for *n.  _fetch: the depths of [beg, end) of one reference, for tests and small regions.  _text: `what`
+ * of rule 11 into out[0, cap); *n: the bytes written, or needed with BWAMS_ERR_CAPACITY, as bwams_sam_header.
+ * bwams_sorter_set_depth: before the sorter's first put (BWAMS_ERR_ARG later, for a handle on another device, or when the handle's
+ * lengths differ from the sorter header's).  The close then adds every record of the merged stream AS WRITTEN, that is after the
+ * merge has set or cleared 0x400, so a sorter with BWAMS_SORT_MARKDUP gives duplicate-free depth.  The records are uploaded a second
+ * time, in whole records: one that straddles two deflate pieces is counted once, with its final flag, so the result does not
+ * depend on where the pieces cut the stream.  Close does not call _finish: the caller may add further files.  The file and the
+ * index are byte for byte what they are without the call.  An add that fails ends the close with its error (rule 3: a record of
+ * the merged stream with an op code above 8 is BWAMS_ERR_ARG), with the file written up to the piece before it and no index: a
+ * sorter without a handle would have written those records; check them first when they come from elsewhere.
+ * bwams_depth_text with BWAMS_DEPTH_TEXT_DIST runs one histogram per reference and holds (n_ref + 1) * n_bins int64 on the host:
+ * meant for tens to thousands of references; for an assembly of 100 000 contigs ask bwams_depth_hist for the references wanted. */
+#define BWAMS_DEPTH_TEXT_SUMMARY 0
+#define BWAMS_DEPTH_TEXT_DIST 1
+#define BWAMS_DEPTH_TEXT_WINDOWS 2
+int bwams_depth_open(int device, const int32_t *l_ref, int32_t n_ref, const bwams_depth_opt_t *opt, bwams_depth_t **out);
+int bwams_depth_close(bwams_depth_t *d);
+int bwams_depth_reset(bwams_depth_t *d);
+int bwams_depth_add_batch(bwams_depth_t *d, bwams_batch_t *b, int64_t *n_counted);
+int bwams_depth_add_records(bwams_depth_t *d, const void *bam, int64_t n_bytes, int64_t *n_counted);
+int bwams_depth_finish(bwams_depth_t *d);
+int bwams_depth_summary(bwams_depth_t *d, bwams_depth_ref_t *rows, int64_t cap);
+int bwams_depth_hist(bwams_depth_t *d, int32_t ref, int64_t *hist, int32_t n_bins);
+int bwams_depth_windows(bwams_depth_t *d, int32_t w, int64_t *sums, int64_t cap, int64_t *n);
+int bwams_depth_runs(bwams_depth_t *d, int32_t ref, int32_t beg, int32_t end, int32_t *start, int32_t *depth, int64_t cap, int64_t *n);
+int bwams_depth_fetch(bwams_depth_t *d, int32_t ref, int32_t beg, int32_t end, int32_t *depth);
+int bwams_depth_text(bwams_depth_t *d, const char *names, int32_t what, int32_t arg, char *out, int64_t cap, int64_t *n);
+int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -297,6 +297,24 @@ typedef struct bwams_dup_lib_stats {
 /* The read groups and libraries of a SAM header (rule 9): a host object. */
 typedef struct bwams_dup_groups bwams_dup_groups_t;
 
+/* Depth of coverage (include/bwams.h, "Depth of coverage").  A depth handle lives on one device. */
+typedef struct bwams_depth bwams_depth_t;
+
+/* Rule 2's filter and rule 3's choice: records with any bit of exclude set in FLAG, or MAPQ below min_mapq, do not count;
+ * count_deletions != 0 makes D cover.  reserved must be 0.  A NULL pointer means {0x704, 0, 0, 0}. */
+typedef struct bwams_depth_opt {
+    uint32_t exclude;
+    int32_t  min_mapq;
+    int32_t  count_deletions;
+    int32_t  reserved;
+} bwams_depth_opt_t;
+
+/* One reference's row of the summary (rule 7): its length, the sum of its depths, and the smallest and largest depth. */
+typedef struct bwams_depth_ref {
+    int64_t length, bases;
+    int32_t min, max;
+} bwams_depth_ref_t;
+
 #ifdef __cplusplus
 }
 #endif
