@@ -238,9 +238,11 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
             BWAMS_HIP(hipMemcpyAsync(d, b->d_ctr.p->dbg, sizeof d, hipMemcpyDeviceToHost, st));
             BWAMS_HIP(hipStreamSynchronize(st));
             if (d[0])
-                fprintf(stderr, "[bwams_extend_run] selection walk, round %d: %llu reads, Mticks total %.2f fetch %.2f scan %.2f keep-anyway %.2f; %llu slots, %llu chunks, "
-                                "%llu keep-anyway calls; longest read: %.3f Mticks (fetch %.3f scan %.3f keep %.3f), %llu slots %llu chunks %llu calls, %llu regions\n",
-                        round, d[0], d[1] / 1e6, d[2] / 1e6, d[3] / 1e6, d[4] / 1e6, d[5], d[6], d[7], d[8] / 1e6, d[9] / 1e6, d[10] / 1e6, d[11] / 1e6, d[12], d[13], d[14], d[15]);
+                fprintf(stderr, "[bwams_extend_run] selection walk, round %d: %llu reads, Mticks total %.2f fetch %.2f bulk scan %.2f ordered part %.2f (of it keep-anyway %.2f); "
+                                "%llu slots, %llu keep-anyway calls; longest read: %.3f Mticks (fetch %.3f bulk %.3f ordered %.3f, of it keep-anyway %.3f), %llu slots "
+                                "%llu calls, %llu kept regions\n",
+                        round, d[0], d[1] / 1e6, d[2] / 1e6, d[3] / 1e6, d[4] / 1e6, d[5] / 1e6, d[6], d[7], d[8] / 1e6, d[9] / 1e6, d[10] / 1e6, d[11] / 1e6,
+                        d[12] / 1e6, d[13], d[14], d[15]);
         }
         if (round == 0) BWAMS_HIP(hipEventRecord(s->ev[9], st));
         if ((rc = ext_round_fetch(b, &n_req, &n_rest, &n_l, &n_r))) return rc;

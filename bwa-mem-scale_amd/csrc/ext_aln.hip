@@ -487,20 +487,67 @@ __device__ __forceinline__ bool purge_keep_anyway_w(const bwams_chain_seed_t &s,
     return found;
 }
 
-// Wave per read.  The decisions are sequential in the visiting order, but what a slot needs to be decided — its chain, its place
-// in the chain's order, its seed, its state — depends on no decision (a purge rewrites only the purged slot's own entries), so the
-// wave fetches 64 slots at once, one per lane (four dependent loads each, in flight together), and then walks them with the
-// slot's fields broadcast from its lane.  (One slot at a time, every slot paid the four load latencies: the kernel's duration was
-// the ~1000 seeds of the heaviest read times ~3 us, the same at any chunk size.)
-// Round 3: the kept regions a slot is tested against (KReg, 32 B; 64 per step) live in LDS while a read is walked.  Instrumented
-// (-DBWAMS_SELDBG, BWAMS_VERBOSE): the kernel's 3.2 ms were ONE read — 1191 slots, 10.8 k steps of that scan at ~650 cycles each, i.e.
-// the L2 round trip of the kreg load, 79 % of its 8.9 M cycles.  The copy in HBM stays the state between rounds (loaded at the start
-// of a read, written through).  Three size classes, each its own launch with its own work cursor over the same list: up to 256 regions
-// (8 KB of LDS per wave: sixteen waves per CU), up to 640 (20 KB: seven), up to 1280 (40 KB: three; the reads beyond fall back to HBM).
-// The top class holds a few dozen reads per million on a genome like the bench's, so its longest walk starts when the kernel does; on
-// a repeat-heavy genome (27 k reads per million beyond 128 regions) the middle class is what keeps enough wavefronts on them.
+// Wave per read, 64 slots per batch, lane j owning slot t + j.  What a slot needs to be decided — its chain, its place in the chain's
+// order, its seed, its state, and (should it be kept) the six fields of its own region — depends on no decision: a purge rewrites
+// only the purged slot's own entries, and only a slot with kExtDone can be kept, whose region ext_post_kernel wrote in an earlier
+// launch.  So the wave fetches all of it at once, one slot per lane, the dependent loads of 64 slots in flight together.
+//
+// The test of a seed against a kept region depends on no other slot either: what the sequential walk computes per slot is an "any"
+// over the regions kept before it, and those are the lim0 regions kept when the batch starts plus the regions kept at slots
+// t .. t + j - 1 of the same batch.  The batch is therefore decided in two parts:
+//  * bulk scan: for i in [0, lim0), a wave-uniform index, every lane tests its own seed against region i (LDS broadcast read, or
+//    one address in HBM for the reads beyond the top class) and keeps a sticky `hit`.  The containment test — integer compares,
+//    which almost every region fails — is branch-free; the gap arithmetic (cal_max_gap: two double divisions) runs only in the
+//    lanes whose seed the region contains.  kSelUnroll regions are loaded together to cover the load latency.
+//  * ordered part: j = 0 .. nb - 1 with wave-uniform control flow.  `hit` of lane j set: the overlap rescue (purge_keep_anyway_w,
+//    wave-wide as before; the purge marks of earlier slots it reads are final by then), and without a rescue the slot is purged.
+//    Otherwise a slot that is not extended yet is requested and the walk stops there; an extended one is kept: lane j appends its
+//    prefetched region to kreg / lk, the region is broadcast from lane j (v_readlane), and every lane behind j tests its own seed
+//    against it and ORs the result into its `hit`.
+// The decisions are those of the sequential walk: a slot's `hit` when its turn comes is an OR over exactly the regions kept before
+// it (the bulk scan's lim0, then one term per slot kept earlier in the batch); purged regions never enter kreg; the rescue test and
+// the request / stop rule are the sequential ones; slots behind a stop are not written and are fetched and scanned again by the next
+// round.  One barrier per batch (the next bulk scan reads what the ordered part appended) replaces one per kept slot.
+//
+// The kept regions (KReg, 32 B) live in LDS while a read is walked; the copy in HBM stays the state between rounds (loaded at the
+// start of a read, written through).  Three size classes, each its own launch with its own work cursor over the same list: up to 256
+// regions (8 KB of LDS per wave: sixteen waves per CU), up to 640 (20 KB: seven), up to 1280 (40 KB: three; the reads beyond fall back
+// to HBM).  The top class holds a few dozen reads per million on a genome like the bench's, so its longest walk starts when the kernel
+// does; on a repeat-heavy genome (27 k reads per million beyond 128 regions) the middle class is what keeps enough wavefronts on them.
 constexpr int kSelCap[3] = {256, 640, 1280};
-constexpr int kSelSteps = 4;             // steps of the wave tier's region scan taken together
+constexpr int kSelUnroll = 6;            // regions of the bulk scan loaded together
+
+__device__ __forceinline__ int64_t readlane64(int64_t v, int j) {
+    return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, j);
+}
+
+// purge_class's first two returns (a purged region, a region that does not contain the seed) without a branch
+__device__ __forceinline__ bool sel_contains(const KReg &q, const bwams_chain_seed_t &s) {
+    return !((q.qb == -1) & (q.qe == -1)) & !((s.rbeg < q.rb) | (s.rbeg + s.len > q.re) | (s.qbeg < q.qb) | (s.qbeg + s.len > q.qe));
+}
+
+// every lane's own seed against src[0 .. n), the same region in every lane; returns hit | "some region explains the seed"
+__device__ __forceinline__ bool sel_bulk_scan(const bwams_mem_opt_t &opt, const KReg *src, int n, const bwams_chain_seed_t &s, int l_query, bool own,
+                                              bool hit) {
+    for (int base = 0; base < n; base += kSelUnroll) {
+        KReg q[kSelUnroll];
+        bool go[kSelUnroll], any = false;
+#pragma unroll
+        for (int u = 0; u < kSelUnroll; ++u) {
+            const int i = base + u;
+            q[u] = src[i < n ? i : n - 1];                                    // past the end: the last region again (an OR)
+            go[u] = own & sel_contains(q[u], s);
+            any |= go[u];
+        }
+        if (any & !hit) {                                                     // rare: one branch over the whole group
+#pragma unroll
+            for (int u = 0; u < kSelUnroll; ++u)
+                if (go[u] && !hit) hit = purge_class(opt, s, l_query, q[u].rb, q[u].re, q[u].qb, q[u].qe, q[u].seedlen0, q[u].w) == 2;
+        }
+    }
+    return hit;
+}
+
 __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, int cap, unsigned long long *ticket) {
     extern __shared__ __align__(16) unsigned char l_sel_raw[];
     KReg *lk = reinterpret_cast<KReg *>(l_sel_raw);
@@ -526,68 +573,67 @@ __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, 
         bool stop = false;
 #ifdef BWAMS_SELDBG                 // phase timers of the walk (printed by bwams_extend_run under BWAMS_VERBOSE)
         const unsigned long long T0 = __builtin_amdgcn_s_memtime();
-        unsigned long long t_scan = 0, n_slots = 0, n_chunks = 0;
+        unsigned long long t_fetch = 0, t_bulk = 0, t_ord = 0, t_keep = 0, n_slots = 0, n_calls = 0;
 #endif
         while (t < av_n && !stop) {
             const int nb = av_n - t < 64 ? av_n - t : 64;
-            int64_t my_off = 0, my_rbeg = 0;
-            int my_n = 0, my_k = 0, my_st = 0, my_qbeg = 0, my_len = 0;
-            if (lane < nb) {
+            const bool own = lane < nb;
+#ifdef BWAMS_SELDBG
+            const unsigned long long Ta = __builtin_amdgcn_s_memtime();
+#endif
+            // fetch: the slot's seed, chain, state and region, one slot per lane
+            bwams_chain_seed_t s;
+            s.rbeg = 0; s.qbeg = 0; s.len = 0;
+            KReg mine;
+            mine.rb = mine.re = 0; mine.qb = mine.qe = mine.seedlen0 = mine.w = 0;
+            int64_t my_off = 0;
+            int my_n = 0, my_k = 0, my_st = 0;
+            if (own) {
                 const int64_t p = reg0 + t + lane;
                 bwams_chain_t c;
                 bwams_chain_seed_t sd;
                 select_seed_of_slot(A, p, c, my_k, sd);
-                my_off = c.seed_off; my_n = c.n; my_rbeg = sd.rbeg; my_qbeg = sd.qbeg; my_len = sd.len;
+                my_off = c.seed_off; my_n = c.n; s.rbeg = sd.rbeg; s.qbeg = sd.qbeg; s.len = sd.len;
                 my_st = A.state[p];
+                const bwams_alnreg_t *a = &A.regs[p];
+                mine.rb = a->rb; mine.re = a->re; mine.qb = a->qb; mine.qe = a->qe; mine.seedlen0 = a->seedlen0; mine.w = a->w;
             }
+#ifdef BWAMS_SELDBG
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const unsigned long long Tb = __builtin_amdgcn_s_memtime();
+#endif
+            // bulk scan: the regions kept before the batch
+            bool hit = in_lds ? sel_bulk_scan(A.opt, lk, lim, s, l_query, own, false) : sel_bulk_scan(A.opt, kreg, lim, s, l_query, own, false);
+#ifdef BWAMS_SELDBG
+            const unsigned long long Tc = __builtin_amdgcn_s_memtime();
+#endif
+            // ordered part
             int j = 0;
             for (; j < nb; ++j) {
                 const int64_t p = reg0 + t + j;
-                const int64_t c_off = ((int64_t)__shfl((int)(my_off >> 32), j) << 32) | (uint32_t)__shfl((int)my_off, j);
-                bwams_chain_seed_t s;
-                s.rbeg = ((int64_t)__shfl((int)(my_rbeg >> 32), j) << 32) | (uint32_t)__shfl((int)my_rbeg, j);
-                s.qbeg = __shfl(my_qbeg, j); s.len = __shfl(my_len, j);
-                const int c_n = __shfl(my_n, j), k = __shfl(my_k, j), st = __shfl(my_st, j);
-                bool brk = false;
+                const int st = __builtin_amdgcn_readlane(my_st, j);
+                if ((__ballot(hit) >> j) & 1ull) {
+                    bwams_chain_seed_t sj;
+                    sj.rbeg = readlane64(s.rbeg, j); sj.qbeg = __builtin_amdgcn_readlane(s.qbeg, j); sj.len = __builtin_amdgcn_readlane(s.len, j);
+                    const int64_t c_off = readlane64(my_off, j);
+                    const int c_n = __builtin_amdgcn_readlane(my_n, j), k = __builtin_amdgcn_readlane(my_k, j);
 #ifdef BWAMS_SELDBG
-                const unsigned long long Tb = __builtin_amdgcn_s_memtime();
-                ++n_slots;
+                    const unsigned long long Tk = __builtin_amdgcn_s_memtime();
+                    ++n_calls;
 #endif
-                // The kept regions, 64 per step, kSelSteps steps together (`brk` is an "any" over the regions, so the steps do not depend
-                // on one another): their loads and the containment test — integer compares, which almost every region fails — are in
-                // flight at once and without a branch; the gap arithmetic (cal_max_gap: two double divisions) runs as before, and
-                // only in a step where some region contains the seed.  One ballot per kSelSteps steps.
-                for (int base = 0; base < lim && !brk; base += 64 * kSelSteps) {
-                    KReg q[kSelSteps];
-                    bool go[kSelSteps];
-#pragma unroll
-                    for (int u = 0; u < kSelSteps; ++u) {
-                        const int i = base + u * 64 + lane;
-                        const int ii = i < lim ? i : lim - 1;                 // a valid region for every lane
-                        q[u] = in_lds ? lk[ii] : kreg[ii];
-                        go[u] = (i < lim) & !((q[u].qb == -1) & (q[u].qe == -1)) &
-                                !((s.rbeg < q[u].rb) | (s.rbeg + s.len > q[u].re) | (s.qbeg < q[u].qb) | (s.qbeg + s.len > q[u].qe));
+                    const bool rescued = purge_keep_anyway_w(sj, A.seeds + c_off, A.srt + c_off, k, c_n, lane);
+#ifdef BWAMS_SELDBG
+                    t_keep += __builtin_amdgcn_s_memtime() - Tk;
+#endif
+                    if (!rescued) {
+                        if (lane == 0) {
+                            __hip_atomic_store(reinterpret_cast<unsigned long long *>(&A.regs[p].qb), 0xffffffffffffffffull,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // qb = qe = -1
+                            __hip_atomic_store(&A.srt[c_off + k], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            A.state[p] = st | kExtPurged;
+                        }
+                        continue;
                     }
-                    bool hit = false;
-#pragma unroll
-                    for (int u = 0; u < kSelSteps; ++u)
-                        if (go[u]) hit |= purge_class(A.opt, s, l_query, q[u].rb, q[u].re, q[u].qb, q[u].qe, q[u].seedlen0, q[u].w) == 2;
-                    brk = __ballot(hit) != 0;
-#ifdef BWAMS_SELDBG
-                    n_chunks += kSelSteps;
-#endif
-                }
-#ifdef BWAMS_SELDBG
-                t_scan += __builtin_amdgcn_s_memtime() - Tb;
-#endif
-                if (brk && !purge_keep_anyway_w(s, A.seeds + c_off, A.srt + c_off, k, c_n, lane)) {
-                    if (lane == 0) {
-                        __hip_atomic_store(reinterpret_cast<unsigned long long *>(&A.regs[p].qb), 0xffffffffffffffffull,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // qb = qe = -1
-                        __hip_atomic_store(&A.srt[c_off + k], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        A.state[p] = st | kExtPurged;
-                    }
-                    continue;
                 }
                 if (!(st & kExtDone)) {
                     if (lane == 0) {
@@ -600,26 +646,36 @@ __global__ __launch_bounds__(64) void ext_select_wave_kernel(ExtArgs A, int lo, 
                     stop = true;
                     break;
                 }
-                if (lane == 0) {
-                    const bwams_alnreg_t *a = &A.regs[p];
-                    KReg q;
-                    q.rb = a->rb; q.re = a->re; q.qb = a->qb; q.qe = a->qe; q.seedlen0 = a->seedlen0; q.w = a->w;
-                    kreg[lim] = q;
-                    if (in_lds) lk[lim] = q;
+                // keep: lane j appends its region; the lanes behind it get it by broadcast, not through LDS
+                KReg q;
+                q.rb = readlane64(mine.rb, j); q.re = readlane64(mine.re, j);
+                q.qb = __builtin_amdgcn_readlane(mine.qb, j); q.qe = __builtin_amdgcn_readlane(mine.qe, j);
+                q.seedlen0 = __builtin_amdgcn_readlane(mine.seedlen0, j); q.w = __builtin_amdgcn_readlane(mine.w, j);
+                if (lane == j) {
+                    kreg[lim] = mine;
+                    if (in_lds) lk[lim] = mine;
                     A.state[p] = st | kExtKept;
                 }
+                if (own & (lane > j) & !hit & sel_contains(q, s)) hit = purge_class(A.opt, s, l_query, q.rb, q.re, q.qb, q.qe, q.seedlen0, q.w) == 2;
                 ++lim;
-                __syncthreads();                                              // the appended region is read by every lane from the next slot on
             }
+#ifdef BWAMS_SELDBG
+            n_slots += (unsigned long long)(j < nb ? j + 1 : j);
+            t_fetch += Tb - Ta; t_bulk += Tc - Tb; t_ord += __builtin_amdgcn_s_memtime() - Tc;
+#endif
             t += j;                                                          // a request leaves t at the requested slot
+            __syncthreads();                                                 // the next bulk scan reads what this batch appended
         }
         if (lane == 0) { A.cur[r] = t; A.lim[r] = lim; }
 #ifdef BWAMS_SELDBG
-        if (lane == 0) {
+        if (lane == 0) {                                                     // d[4], d[11]: the ordered part with its keep-anyway calls
             const unsigned long long tot = __builtin_amdgcn_s_memtime() - T0;
             unsigned long long *d = A.ctr->dbg;
-            atomicAdd(&d[0], 1ull); atomicAdd(&d[1], tot); atomicAdd(&d[3], t_scan); atomicAdd(&d[5], n_slots); atomicAdd(&d[6], n_chunks);
-            if (atomicMax(&d[8], tot) < tot) { d[10] = t_scan; d[12] = n_slots; d[13] = n_chunks; d[15] = (unsigned long long)av_n; }
+            atomicAdd(&d[0], 1ull); atomicAdd(&d[1], tot); atomicAdd(&d[2], t_fetch); atomicAdd(&d[3], t_bulk); atomicAdd(&d[4], t_ord);
+            atomicAdd(&d[5], t_keep); atomicAdd(&d[6], n_slots); atomicAdd(&d[7], n_calls);
+            if (atomicMax(&d[8], tot) < tot) {
+                d[9] = t_fetch; d[10] = t_bulk; d[11] = t_ord; d[12] = t_keep; d[13] = n_slots; d[14] = n_calls; d[15] = (unsigned long long)lim;
+            }
         }
 #endif
     }
@@ -663,9 +719,11 @@ void launch_ext_heavy_list(const ExtArgs &A, hipStream_t st) {
     ext_heavy_list_kernel<<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A);
 }
 // The top class goes first and beside the rest, on a stream of its own: its longest read is its duration.  The lane tier and the
-// two smaller classes follow one another on the main stream — together they take about as long as the top class alone, and a third
-// stream bought nothing where the process has four hardware queues: the middle class then sat in the top class's queue and started
-// when that ended (kernel trace: 1.2 ms per round).
+// two smaller classes follow one another on the main stream.  Kernel trace of the batch walk (profiles/ext_rounds.md): round 0 top
+// class 1.59 ms beside 0.64 + 0.76 + 0.47 = 1.87 ms, round 1 1.28 beside 0.28 + 0.65 + 0.38 = 1.32 ms, so the main stream now ends
+// last, by 0.3 and 0.05 ms.  The layout stays: no other split of these four over two streams has a shorter longer side (the small
+// class behind the top class: 2.06 | 1.39), and a third stream bought nothing where the process has four hardware queues: the
+// middle class then sat in the top class's queue and started when that ended (kernel trace of the earlier walk: 1.2 ms per round).
 int launch_ext_select(const ExtArgs &A, int cu_count, hipStream_t st, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join) {
     if (A.nseq <= 0) return 0;
     if (hipEventRecord(fork, st) != hipSuccess || hipStreamWaitEvent(aux[0], fork, 0) != hipSuccess) return -1;
