@@ -1,6 +1,6 @@
 // api_state.hip — the stage state of a batch (stage_state.h) and what the entry-point files share: the per-device auxiliary
 // stream set, state creation (get_state) and release (stage_state_free), the invalidation function (outdated), check_opt, dev_bns,
-// sw_params, scan_rows with widen2_kernel behind launch_widen2, and stage_state_stats for bwams_batch_stats.
+// sw_params, scan_rows with the widen kernels behind launch_widen1 / launch_widen2, and stage_state_stats for bwams_batch_stats.
 #include <cstring>
 #include <map>
 
@@ -51,6 +51,11 @@ void stage_state_free(StageState *s) {
 
 namespace {
 
+__global__ void widen1_kernel(const int32_t *a, int64_t n, int64_t *wide) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g > n) return;
+    wide[g] = g < n ? (int64_t)a[g] : 0;
+}
 __global__ void widen2_kernel(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= 2 * (n + 1)) return;
@@ -60,6 +65,9 @@ __global__ void widen2_kernel(const int32_t *a, const int32_t *b, int64_t n, int
 
 }  // namespace
 
+void launch_widen1(const int32_t *a, int64_t n, int64_t *wide, hipStream_t st) {
+    widen1_kernel<<<(unsigned)((n + 256) / 256), 256, 0, st>>>(a, n, wide);
+}
 void launch_widen2(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide, hipStream_t st) {
     widen2_kernel<<<(unsigned)((2 * (n + 1) + 255) / 256), 256, 0, st>>>(a, b, n, wide);
 }

@@ -13,11 +13,10 @@
 #include <algorithm>
 #include <cstring>
 #include "common.h"
+#include "bam_rec.h"
 
 namespace bwams {
 namespace {
-
-constexpr int kGroup = 16;
 
 enum BamRefusal : unsigned { kBadLine = 1, kLongName = 2, kBadAux = 3, kBadInt = 4, kManyOps = 5, kSeqQual = 6 };
 

@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "bam_rec.h"
 
 namespace bwams {
 namespace {
@@ -34,17 +35,12 @@ namespace {
 constexpr int kTile = 4096;                   // bytes per block of br_filter_kernel: 64 bitmap words
 constexpr int kHalo = 48;                     // a record's fixed part (36 bytes) behind the tile's last offset, in 16-byte pieces
 constexpr int kMaxTags = 32;
-constexpr int kGroup = 16;                    // lanes per record of br_emit_kernel
 
 struct Tags {                                 // the listed tags, by value in the kernel arguments
     int32_t n;
     uint8_t t[2 * kMaxTags];
 };
 
-__device__ __forceinline__ uint32_t ld16(const uint8_t *__restrict__ d, int64_t p) { return (uint32_t)d[p] | (uint32_t)d[p + 1] << 8; }
-__device__ __forceinline__ uint32_t ld32(const uint8_t *__restrict__ d, int64_t p) {
-    return (uint32_t)d[p] | (uint32_t)d[p + 1] << 8 | (uint32_t)d[p + 2] << 16 | (uint32_t)d[p + 3] << 24;
-}
 // the aligned word w of the buffer (d is 16-byte aligned): one load when it lies inside [0, n), its bytes inside otherwise
 __device__ __forceinline__ uint32_t ld_word(const uint8_t *__restrict__ d, int64_t w, int64_t n) {
     const int64_t p = w * 4;
@@ -67,7 +63,7 @@ __device__ __forceinline__ uint32_t ld_wide(const uint8_t *__restrict__ d, int64
 __device__ __forceinline__ bool fixed_ok(int64_t q, int64_t n, uint32_t block_size, uint32_t l_name, uint32_t n_cig, int32_t l_seq) {
     if (block_size < 32 || l_name < 1 || l_seq < 0) return false;
     if (q + 4 + (int64_t)block_size > n) return false;
-    const int64_t need = 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq;
+    const int64_t need = bam_aux_at(l_name, n_cig, l_seq) - 4;
     return need <= (int64_t)block_size;
 }
 
@@ -95,12 +91,12 @@ __global__ __launch_bounds__(256) void br_filter_kernel(const uint8_t *__restric
             return sh ? (lo >> sh | hi << (32 - sh)) : lo;
         };
         bool ok = false;
-        if (q + 36 <= n) {
+        if (q + kBamName <= n) {
             const uint32_t block_size = u32_at(w);
             if (block_size >= 32 && q + 4 + (int64_t)block_size <= n) {
                 const uint32_t l_name = u32_at(w + 3) & 0xFF, n_cig = u32_at(w + 4) & 0xFFFF;
                 const int32_t l_seq = (int32_t)u32_at(w + 5);
-                ok = fixed_ok(q, n, block_size, l_name, n_cig, l_seq) && d[q + 35 + l_name] == 0;     // the name's last byte: inside the record
+                ok = fixed_ok(q, n, block_size, l_name, n_cig, l_seq) && d[q + kBamName - 1 + l_name] == 0;     // the name's last byte: inside the record
             }
         }
         const unsigned long long m = __ballot(ok);
@@ -125,7 +121,7 @@ __global__ __launch_bounds__(256) void br_succ_kernel(const uint8_t *__restrict_
         const int b = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
         const int64_t q = w * 64 + b;
-        const int64_t q2 = q + 4 + (int64_t)ld32(d, q);           // <= n: the filter saw to it
+        const int64_t q2 = q + 4 + (int64_t)bam_block_size(d + q);           // <= n: the filter saw to it
         uint32_t nx = n_cand + 1;
         if (q2 == n) nx = n_cand;
         else {
@@ -159,7 +155,7 @@ __global__ void br_count_kernel(const uint8_t *__restrict__ d, const unsigned lo
     if (up[cur] == n_cand) { out[0] = cnt + 1; out[1] = out[2] = 0; return; }
     out[0] = -1;
     out[1] = cnt + 1;
-    out[2] = cand_off[cur] + 4 + (int64_t)ld32(d, cand_off[cur]);
+    out[2] = cand_off[cur] + 4 + (int64_t)bam_block_size(d + cand_off[cur]);
 }
 
 struct BrRec {                                // a record as the emit kernel reads it
@@ -189,7 +185,7 @@ __device__ int64_t aux_next(const uint8_t *__restrict__ d, int64_t p, int64_t en
     case 'B': {
         if (v + 5 > end) return -1;
         const int sub = d[v];
-        const int64_t cnt = ld32(d, v + 1);
+        const int64_t cnt = ld_u32(d + v + 1);
         const int sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
         if (!sz) return -2;
         e = v + 5 + cnt * sz;
@@ -215,10 +211,10 @@ __device__ __forceinline__ int64_t aux_int(const uint8_t *__restrict__ d, int64_
     switch (ty) {
     case 'c': return (int8_t)d[v];
     case 'C': return d[v];
-    case 's': return (int16_t)ld16(d, v);
-    case 'S': return ld16(d, v);
-    case 'i': return (int32_t)ld32(d, v);
-    default:  return ld32(d, v);
+    case 's': return (int16_t)ld_u16(d + v);
+    case 'S': return ld_u16(d + v);
+    case 'i': return (int32_t)ld_u32(d + v);
+    default:  return ld_u32(d + v);
     }
 }
 __device__ __forceinline__ int dec_len(int64_t x) {
@@ -269,16 +265,17 @@ __global__ __launch_bounds__(256) void br_measure_kernel(const uint8_t *__restri
     for (int k = 0; k < levels; ++k)
         if ((r >> k) & 1) cur = up[(int64_t)k * stride + cur];
     const int64_t q = cand_off[cur];
-    const uint32_t block_size = ld32(d, q), l_name = d[q + 12], n_cig = ld16(d, q + 16), flag = ld16(d, q + 18);
-    const int32_t l_seq = (int32_t)ld32(d, q + 20);
+    const uint8_t *p = d + q;
+    const uint32_t block_size = bam_block_size(p), l_name = bam_l_name(p), n_cig = bam_n_cig(p), flag = bam_flag(p);
+    const int32_t l_seq = bam_l_seq(p);
     const bool kept = !(flag & 0x900);
     BrRec R;
-    R.name_at = q + 36; R.seq_at = q + 36 + l_name + 4 * (int64_t)n_cig; R.end = q + 4 + (int64_t)block_size;
+    R.name_at = q + kBamName; R.seq_at = q + bam_seq_at(l_name, n_cig); R.end = q + 4 + (int64_t)block_size;
     R.l_name = (int32_t)l_name - 1; R.l_seq = l_seq; R.flag = flag | (kept ? 1u << 16 : 0u); R.pad_ = 0;
     int l_comment = 0;
     if (kept) {
         unsigned long long err = 0;
-        const int64_t qual_at = R.seq_at + ((int64_t)l_seq + 1) / 2, aux_at = qual_at + l_seq;
+        const int64_t qual_at = q + bam_qual_at(l_name, n_cig, l_seq), aux_at = q + bam_aux_at(l_name, n_cig, l_seq);
         if (l_seq == 0) err = kErrLseq0;
         else {
             // the first kept record of either kind: the minimum settles with the first blocks, so look before the atomic (a stale

@@ -1,0 +1,41 @@
+// bam_rec.h — one BAM alignment record as the kernels read it: p points at its block_size, every field is little-endian
+// and no field is aligned (SAM specification, section 4.2).
+#pragma once
+#include "common.h"
+
+namespace bwams {
+
+constexpr int kGroup = 16;                    // lanes that share a record in the kernels that copy or sum over its bytes
+
+__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) {
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+// the fixed fields
+__device__ __forceinline__ uint32_t bam_block_size(const uint8_t *p) { return ld_u32(p); }       // the record without these four bytes
+__device__ __forceinline__ int32_t bam_ref_id(const uint8_t *p) { return (int32_t)ld_u32(p + 4); }
+__device__ __forceinline__ int32_t bam_pos(const uint8_t *p) { return (int32_t)ld_u32(p + 8); }
+__device__ __forceinline__ uint32_t bam_l_name(const uint8_t *p) { return p[12]; }               // with the NUL
+__device__ __forceinline__ uint32_t bam_mapq(const uint8_t *p) { return p[13]; }
+__device__ __forceinline__ uint32_t bam_n_cig(const uint8_t *p) { return ld_u16(p + 16); }
+__device__ __forceinline__ uint32_t bam_flag(const uint8_t *p) { return ld_u16(p + 18); }
+__device__ __forceinline__ int32_t bam_l_seq(const uint8_t *p) { return (int32_t)ld_u32(p + 20); }
+// where the variable-length fields start, as offsets from p
+constexpr int kBamName = 36;
+__device__ __forceinline__ int64_t bam_cigar_at(uint32_t l_name) { return kBamName + (int64_t)l_name; }
+__device__ __forceinline__ int64_t bam_seq_at(uint32_t l_name, uint32_t n_cig) { return bam_cigar_at(l_name) + 4 * (int64_t)n_cig; }
+__device__ __forceinline__ int64_t bam_qual_at(uint32_t l_name, uint32_t n_cig, int64_t l_seq) { return bam_seq_at(l_name, n_cig) + (l_seq + 1) / 2; }
+__device__ __forceinline__ int64_t bam_aux_at(uint32_t l_name, uint32_t n_cig, int64_t l_seq) { return bam_qual_at(l_name, n_cig, l_seq) + l_seq; }
+
+// reference bases the CIGAR operations first, first + stride, ... of c[0, n_cig) cover (M, D, N, =, X)
+__device__ __forceinline__ int64_t cigar_ref_len(const uint8_t *c, uint32_t n_cig, uint32_t first, uint32_t stride) {
+    int64_t rlen = 0;
+    for (uint32_t k = first; k < n_cig; k += stride) {
+        const uint32_t op = ld_u32(c + 4 * k), o = op & 15;
+        if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rlen += op >> 4;
+    }
+    return rlen;
+}
+
+}  // namespace bwams

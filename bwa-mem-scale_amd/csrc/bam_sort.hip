@@ -17,32 +17,19 @@
 #include <algorithm>
 #include <cstring>
 #include "common.h"
+#include "bam_rec.h"
 
 namespace bwams {
 namespace {
-
-constexpr int kGroup = 16;
-
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) {          // little-endian, any alignment
-    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
 
 __global__ void __launch_bounds__(256) bam_sort_key_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, uint32_t n_ref,
                                                            bwams_bam_coord_t *coord, uint64_t *dkey, uint32_t *idx) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
         const uint8_t *p = bam + rec_off[r];
-        const uint32_t block_size = ld_u32(p);
-        const int32_t rid = (int32_t)ld_u32(p + 4), pos = (int32_t)ld_u32(p + 8);
-        const uint32_t l_name = p[12];
-        const uint32_t n_cig = (uint32_t)p[16] | (uint32_t)p[17] << 8;
-        const uint32_t flag = (uint32_t)p[18] | (uint32_t)p[19] << 8;
-        int64_t rlen = 0;
-        const uint8_t *c = p + 36 + l_name;
-        for (uint32_t k = 0; k < n_cig; ++k) {
-            const uint32_t op = ld_u32(c + 4 * k);
-            const uint32_t o = op & 15;
-            if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rlen += op >> 4;
-        }
+        const uint32_t block_size = bam_block_size(p);
+        const int32_t rid = bam_ref_id(p), pos = bam_pos(p);
+        const uint32_t n_cig = bam_n_cig(p), flag = bam_flag(p);
+        const int64_t rlen = cigar_ref_len(p + bam_cigar_at(bam_l_name(p)), n_cig, 0, 1);
         const int64_t end = ((flag & 4) || n_cig == 0 || rlen == 0) ? (int64_t)pos + 1 : (int64_t)pos + rlen;
         const uint64_t low = (uint64_t)(uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1);
         bwams_bam_coord_t cd;

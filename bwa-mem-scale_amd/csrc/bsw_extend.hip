@@ -34,18 +34,13 @@ __host__ __device__ __forceinline__ size_t bsw_row_bytes(int qmax) {
     return (((size_t)(qmax + 1) * 8 + (size_t)qmax + 64 + 15) / 16) * 16;
 }
 
+// not wave_ops.h's scan_max: with the DPP form bsw_kernel's register counts change (90 -> 78 VGPRs, 85 -> 75 SGPRs), a rescheduling of its own
 __device__ __forceinline__ int wave_incl_prefix_max(int v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int t = __shfl_up(v, o);
         if (lane >= o) v = max(v, t);
     }
-    return v;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
     return v;
 }
 

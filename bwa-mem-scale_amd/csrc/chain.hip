@@ -83,21 +83,10 @@ struct RidCache { int64_t lo, hi; int rid; };
 __device__ __forceinline__ int pos2rid(const DevBns &b, int64_t pos_f, RidCache &rc) {
     if (pos_f >= b.l_pac) return -1;
     if (pos_f >= rc.lo && pos_f < rc.hi) return rc.rid;
-    int left = 0, mid = 0, right = b.n_seqs;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= b.contigs[mid].offset) {
-            if (mid == b.n_seqs - 1) break;
-            if (pos_f < b.contigs[mid + 1].offset) break;
-            left = mid + 1;
-        } else right = mid;
-    }
+    const int mid = pos2rid(b, pos_f);
     const int64_t off = b.contigs[mid].offset;
     if (pos_f >= off) { rc.lo = off; rc.hi = mid == b.n_seqs - 1 ? b.l_pac : b.contigs[mid + 1].offset; rc.rid = mid; }
     return mid;
-}
-__device__ __forceinline__ int64_t depos(const DevBns &b, int64_t pos) {
-    return pos >= b.l_pac ? (b.l_pac << 1) - 1 - pos : pos;
 }
 __device__ __forceinline__ int intv2rid(const DevBns &b, int64_t rb, int64_t re, RidCache &rc) {
     if (rb < b.l_pac && re > b.l_pac) return -2;
@@ -596,10 +585,6 @@ __device__ __forceinline__ bool chain_seed_one(const ChainArgs &A, const SeedCtx
         ++n_keys;
     }
     return true;
-}
-__device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
-    return (int64_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) |
-                     (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)v, l));
 }
 // the read's seeds [0, cnt), 64 per pass across its SMEMs sm[beg .. end); all 64 lanes call this.  Returns false when the read needs the B-tree.
 __device__ bool chain_seeds_batch(const ChainArgs &A, const SeedCtx &S, int &n_keys, const bwams_smem_t *sm, int64_t beg, int64_t end, int64_t base,

@@ -3,15 +3,9 @@
 #pragma once
 
 #include "common.h"
+#include "bns_dev.h"
 
 namespace bwams {
-
-// bntseq_t as the kernels see it
-struct DevBns {
-    const bwams_contig_t *contigs;
-    int32_t n_seqs;
-    int64_t l_pac;
-};
 
 // Scratch of the chaining kernel.  Every array except `nodes` and the per-read ones is indexed
 // like sa_coord (one slot per SA hit = per seed); a read owns the slice of its SMEMs' hits.

@@ -318,6 +318,8 @@ size_t bsw_list_bytes(int64_t n_tasks);          // scratch `list` of launch_bsw
 int bsw_lds_waves(int qmax);                     // waves per block of launch_bsw's one-task-per-wave kernel; 0: qmax does not fit
 void launch_emf_probe(const DevEmf &t, const uint8_t *enc, const int64_t *cum, int64_t nseq, uint32_t *out,
                       uint8_t *code, uint8_t *skip, DevCounters *ctr, hipStream_t st);
+// ksw_align2's xtra flags (ksw.h), carried in a task's h0 beside the 16-bit threshold
+constexpr int KSW_XBYTE = 0x10000, KSW_XSTOP = 0x20000, KSW_XSUBO = 0x40000, KSW_XSTART = 0x80000;
 constexpr int kKswMaxTarget = 20000;     // longest local-SW target: its row-maxima list must fit the LDS of a 4-wave block
 int launch_ksw(const bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint8_t *qer, const SwParams &prm,
                 int pmax, int tmax, void *out, DevCounters *ctr, int cu_count, hipStream_t st);

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "chain_kernels.h"
 #include "wave_ops.h"
+#include "ksw_global2_wave.h"
 #include "region_sort.h"
 
 namespace bwams {
@@ -20,7 +21,6 @@ namespace {
 constexpr int kLightN = 16;          // regions per read handled by a single lane (32: the lane tier was the stage's longest launch, 4.5 -> 3.9 ms)
 constexpr int kSmallN = 128, kMidN = 512;      // regions per read of the wave tier's smaller instances
 constexpr int kLdsN = 2048;          // sort records a wavefront keeps in LDS (largest instance of the wave tier)
-constexpr int MINUS_INF = -0x40000000;
 // DedupArgs::cnt (bwams_debug_dedup_counts, include/bwams.h): reads finished per tier, patch alignments per variant
 enum { kCntTriage = 0, kCntLane, kCntWaveSmall, kCntWaveMid, kCntWaveLarge, kCntOneLane, kCntShortcut, kCntHbm, kCntLds, kCntReg1, kCntReg2, kCntReg3,
        kCntReg4, kCntEarly };
@@ -35,16 +35,16 @@ __host__ __device__ constexpr size_t dd_lds_bytes(int cap, int max_read_len) {
 __device__ int global_score(const bwams_mem_opt_t &o, int qlen, const uint8_t *qseq, int qs, int tlen, const uint8_t *tseq, int ts,
                             int w, int2 *eh) {
     const int oe_del = o.o_del + o.e_del, oe_ins = o.o_ins + o.e_ins;
-    eh[0] = make_int2(0, MINUS_INF);
+    eh[0] = make_int2(0, kMinusInf);
     int j;
-    for (j = 1; j <= qlen && j <= w; ++j) eh[j] = make_int2(-(o.o_ins + o.e_ins * j), MINUS_INF);
-    for (; j <= qlen; ++j) eh[j] = make_int2(MINUS_INF, MINUS_INF);
+    for (j = 1; j <= qlen && j <= w; ++j) eh[j] = make_int2(-(o.o_ins + o.e_ins * j), kMinusInf);
+    for (; j <= qlen; ++j) eh[j] = make_int2(kMinusInf, kMinusInf);
     for (int i = 0; i < tlen; ++i) {
-        int f = MINUS_INF;
+        int f = kMinusInf;
         const int8_t *mrow = &o.mat[tseq[(int64_t)ts * i] * 5];
         const int beg = i > w ? i - w : 0;
         const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
-        int h1 = beg == 0 ? -(o.o_del + o.e_del * (i + 1)) : MINUS_INF;
+        int h1 = beg == 0 ? -(o.o_del + o.e_del * (i + 1)) : kMinusInf;
         // eight cells at a time: the row lives in HBM and a lane waits a full round trip per load, so the
         // loads of a block are issued together
         for (j = beg; j < end; j += 8) {
@@ -74,88 +74,30 @@ __device__ int global_score(const bwams_mem_opt_t &o, int qlen, const uint8_t *q
                 }
             }
         }
-        eh[end] = make_int2(h1, MINUS_INF);
+        eh[end] = make_int2(h1, kMinusInf);
     }
     return eh[qlen].x;
 }
 
 // The same alignment with the whole wavefront on a row (all 64 lanes call this with equal arguments): 64 columns per step, the (h, e) row
-// and the query in LDS, the row's target base handed round from a register (one load per 64 rows).  Within a row E and the diagonal term
-// come from the row above, and F — max over the columns to the left of (M - gap open) minus the extensions in between — is a prefix
-// maximum (ksw_global2 feeds F from M only, ksw.cpp:607-618), so the cells of a row are independent but for that scan: the scores are
-// the serial loop's, cell for cell.  Every patch candidate of a read with hundreds of overlapping regions goes through here; on one
-// lane with the row in HBM such a read held its wavefront for 0.4 s.
-__device__ __forceinline__ int dd_incl_max(int v) {
-    asm volatile("s_nop 4\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
-                 : "+v"(v));
-    return v;
-}
+// and the query in LDS, the row's target base handed round from a register (one load per 64 rows); the row itself is
+// ksw_global2_wave.h's, and the scores are the serial loop's, cell for cell.  Every patch candidate of a read with hundreds of
+// overlapping regions goes through here; on one lane with the row in HBM such a read held its wavefront for 0.4 s.
 __device__ int global_score_wave(const bwams_mem_opt_t &o, int qlen, const uint8_t *qseq, int qs, int tlen, const uint8_t *tseq, int ts,
                                  int w, int2 *eh, uint8_t *qbuf, int lane) {
     const int oe_del = o.o_del + o.e_del, oe_ins = o.o_ins + o.e_ins;
-    constexpr int kNeg = -0x30000000;                       // below every reachable score, above MINUS_INF - (what a row subtracts)
     for (int j = lane; j <= qlen; j += 64) {
-        eh[j] = j == 0 ? make_int2(0, MINUS_INF) : j <= w ? make_int2(-(o.o_ins + o.e_ins * j), MINUS_INF) : make_int2(MINUS_INF, MINUS_INF);
+        eh[j] = j == 0 ? make_int2(0, kMinusInf) : j <= w ? make_int2(-(o.o_ins + o.e_ins * j), kMinusInf) : make_int2(kMinusInf, kMinusInf);
         if (j < qlen) qbuf[j] = qseq[(int64_t)qs * j];
     }
     __syncthreads();
-    // the pair is the wave's: lengths and band in scalar registers (scalar row and chunk loops); cross-lane moves are DPP (the
-    // neighbour) and v_readlane (lane 63, the row's end, the row's target base), the matrix row is five bytes of one scalar
-    // — the changes that took mem_reg2aln's wave kernel from 167 to 60 instructions per row chunk (profiles/r03_notes.md 88)
+    // the pair is the wave's: lengths and band in scalar registers (scalar row and chunk loops), the row's target base a v_readlane
     qlen = __builtin_amdgcn_readfirstlane(qlen); tlen = __builtin_amdgcn_readfirstlane(tlen); w = __builtin_amdgcn_readfirstlane(w);
     int tv = 0;
     for (int i = 0; i < tlen; ++i) {
         if ((i & 63) == 0) tv = i + lane < tlen ? (int)tseq[(int64_t)ts * (i + lane)] : 4;
         const int tb = __builtin_amdgcn_readlane(tv, i & 63);
-        const int8_t *mrow = &o.mat[tb * 5];
-        const uint64_t mpk = (uint64_t)(uint8_t)mrow[0] | (uint64_t)(uint8_t)mrow[1] << 8 | (uint64_t)(uint8_t)mrow[2] << 16 |
-                             (uint64_t)(uint8_t)mrow[3] << 24 | (uint64_t)(uint8_t)mrow[4] << 32;
-        const int beg = i > w ? i - w : 0;
-        const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
-        const int h1_first = beg == 0 ? -(o.o_del + o.e_del * (i + 1)) : MINUS_INF;
-        int f_carry = MINUS_INF, h_carry = h1_first, h_end = h1_first;
-        for (int c0 = beg; c0 < end; c0 += 64) {
-            const int j = c0 + lane;
-            const bool act = j < end;
-            const int jj = act ? j : end - 1;
-            const int2 p = eh[jj];
-            int qb = qbuf[jj];
-            qb = qb > 4 ? 4 : qb;
-            const int m = p.x + (int)(int8_t)(uint8_t)(mpk >> (qb << 3));
-            int e = p.y;
-            const int t_ins = m - oe_ins;
-            const int g = act ? t_ins + j * o.e_ins : kNeg;
-            const int P = dd_incl_max(g);
-            const int Pex = lane_shr1(P, kNeg);            // lane 0: nothing to its left in this chunk
-            const int fc = f_carry - lane * o.e_ins;       // what the gap open before this chunk has become
-            const int fp = Pex - (j - 1) * o.e_ins;
-            const int f = fc > fp ? fc : fp;
-            int h = m >= e ? m : e;
-            h = h >= f ? h : f;
-            const int t = m - oe_del;
-            e -= o.e_del;
-            e = e > t ? e : t;
-            const int fn = f - o.e_ins;
-            const int hl = lane_shr1(h, h_carry);          // lane 0 takes the previous chunk's last h
-            if (act) eh[j] = make_int2(hl, e);
-            const int fnext = fn > t_ins ? fn : t_ins;
-            f_carry = __builtin_amdgcn_readlane(fnext, 63);
-            h_carry = __builtin_amdgcn_readlane(h, 63);
-            const int last = end - 1 - c0;                 // the row's last column, if it lies in this chunk
-            if (last < 64) h_end = __builtin_amdgcn_readlane(h, last);
-        }
-        if (lane == 0) eh[end] = make_int2(h_end, MINUS_INF);
+        ksw_global2_row_wave<false>(o, oe_del, oe_ins, ksw_mat_row(&o.mat[tb * 5]), i, w, qlen, eh, qbuf, lane, nullptr);
         __syncthreads();
     }
     return eh[qlen].x;
@@ -179,8 +121,8 @@ __device__ int global_score_wave_reg(const bwams_mem_opt_t &o, int qlen, const u
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int j = lane * NC + c;
-        h[c] = j == 0 ? 0 : (j <= w && j <= qlen) ? -(o.o_ins + e_ins * j) : MINUS_INF;
-        e[c] = MINUS_INF;
+        h[c] = j == 0 ? 0 : (j <= w && j <= qlen) ? -(o.o_ins + e_ins * j) : kMinusInf;
+        e[c] = kMinusInf;
         const int b = j < qlen ? (int)qseq[(int64_t)qs * j] : 4;
         qb[c] = (b > 4 ? 4 : b) << 3;
         je[c] = j * e_ins;
@@ -200,7 +142,7 @@ __device__ int global_score_wave_reg(const bwams_mem_opt_t &o, int qlen, const u
         const uint64_t mpk = tb == 0 ? mp[0] : tb == 1 ? mp[1] : tb == 2 ? mp[2] : tb == 3 ? mp[3] : mp[4];
         const int beg = i > w ? i - w : 0;
         const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
-        const int h1_first = beg == 0 ? -(o.o_del + e_del * (i + 1)) : MINUS_INF;
+        const int h1_first = beg == 0 ? -(o.o_del + e_del * (i + 1)) : kMinusInf;
         int m[NC], ti[NC], hv[NC];
         int loc = kNeg;
 #pragma unroll
@@ -210,7 +152,7 @@ __device__ int global_score_wave_reg(const bwams_mem_opt_t &o, int qlen, const u
             ti[c] = m[c] - oe_ins + je[c];                  // (M - gap open) + e_ins * column: what the prefix maximum runs over
             if (j >= beg && j < end) loc = loc > ti[c] ? loc : ti[c];
         }
-        int g = lane_shr1(dd_incl_max(loc), kNeg);         // the cells of the lanes to the left
+        int g = lane_shr1(scan_max(loc), kNeg);         // the cells of the lanes to the left
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int j = lane * NC + c;
@@ -219,7 +161,7 @@ __device__ int global_score_wave_reg(const bwams_mem_opt_t &o, int qlen, const u
             hv[c] = hh >= f ? hh : f;
             if (j >= beg && j < end) g = g > ti[c] ? g : ti[c];
         }
-        if ((i & 3) == 3 && need > MINUS_INF) {
+        if ((i & 3) == 3 && need > kMinusInf) {
             const int rows_left = tlen - 1 - i;
             int ub = kNeg;
 #pragma unroll
@@ -231,7 +173,7 @@ __device__ int global_score_wave_reg(const bwams_mem_opt_t &o, int qlen, const u
                                                              : o.a * cols_left - e_del * (rows_left - cols_left));
                 if (j >= beg && j < end) ub = ub > u ? ub : u;
             }
-            if (__builtin_amdgcn_readlane(dd_incl_max(ub), 63) < need) return MINUS_INF;
+            if (__builtin_amdgcn_readlane(scan_max(ub), 63) < need) return kMinusInf;
         }
         const int hv_left0 = lane_shr1(hv[NC - 1], 0);     // H of the cell left of this lane's first one
 #pragma unroll
@@ -242,7 +184,7 @@ __device__ int global_score_wave_reg(const bwams_mem_opt_t &o, int qlen, const u
             if (j >= beg && j < end) {
                 const int t = m[c] - oe_del, ee = e[c] - e_del;
                 e[c] = ee > t ? ee : t;
-            } else if (j == end) e[c] = MINUS_INF;
+            } else if (j == end) e[c] = kMinusInf;
         }
     }
     int last = 0;
@@ -315,7 +257,7 @@ __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_a
             const int q_s0 = patch_pred(b.qe - a.qb, (b.qe - b.qb) + (a.qe - a.qb), b.score + a.score);
             const int r_s0 = patch_pred(b.re - a.rb, (b.re - b.rb) + (a.re - a.rb), b.score + a.score);
             const int mx0 = q_s0 > r_s0 ? q_s0 : r_s0;
-            int need = MINUS_INF;
+            int need = kMinusInf;
             if (mx0 > 0) {
                 need = (int)((double)0.90f * (double)mx0);
                 while ((double)need / (double)mx0 < (double)0.90f) ++need;     // the smallest score the test accepts
@@ -343,7 +285,7 @@ __device__ int patch_reg(const DedupArgs &A, const uint8_t *query, const bwams_a
             atomicAdd(&A.cnt[route], 1ull);
             // global_score_wave_reg gave up.  A finished alignment never returns this value: the band is at least dl + 3, so the last
             // cell lies inside it and holds a reachable score (the tests pin it: no early exit is counted under BWAMS_DEDUP_SEQ=1)
-            if (score == MINUS_INF) atomicAdd(&A.cnt[kCntEarly], 1ull);
+            if (score == kMinusInf) atomicAdd(&A.cnt[kCntEarly], 1ull);
         }
     }
     const int q_s = patch_pred(b.qe - a.qb, (b.qe - b.qb) + (a.qe - a.qb), b.score + a.score);

@@ -26,13 +26,11 @@
 #include <algorithm>
 #include <climits>
 #include "common.h"
+#include "bam_rec.h"
+#include "wave_ops.h"
 
 namespace bwams {
 namespace {
-
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) {          // little-endian, any alignment
-    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
 
 unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
     int64_t g = (items + per_block - 1) / per_block;
@@ -44,8 +42,8 @@ __global__ void __launch_bounds__(256) depth_check_kernel(const uint8_t *bam, co
                                                           unsigned long long *bad) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
         const uint8_t *p = bam + rec_off[r];
-        const uint32_t l_name = p[12], n_cig = (uint32_t)p[16] | (uint32_t)p[17] << 8;
-        const uint8_t *c = p + 36 + l_name;
+        const uint32_t n_cig = bam_n_cig(p);
+        const uint8_t *c = p + bam_cigar_at(bam_l_name(p));
         bool any = false;
         for (uint32_t k = 0; k < n_cig; ++k) any |= (c[4 * k] & 15) > 8;
         if (any) atomicMin(bad, (unsigned long long)r);
@@ -89,13 +87,12 @@ __global__ void __launch_bounds__(256) depth_add_kernel(const uint8_t *bam, cons
         int64_t x = 0, base = 0, len_ref = 0;
         if (r < n_rec) {
             const uint8_t *p = bam + rec_off[r];
-            const int32_t rid = (int32_t)ld_u32(p + 4);
-            const uint32_t l_name = p[12], mapq = p[13], nc = (uint32_t)p[16] | (uint32_t)p[17] << 8;
-            const uint32_t flag = (uint32_t)p[18] | (uint32_t)p[19] << 8;
+            const int32_t rid = bam_ref_id(p);
+            const uint32_t mapq = bam_mapq(p), nc = bam_n_cig(p), flag = bam_flag(p);
             if (!(flag & f.exclude) && (int32_t)mapq >= f.min_mapq && rid >= 0 && rid < f.n_ref && nc > 0) {
                 n_cig = nc;
-                c = p + 36 + l_name;
-                x = (int32_t)ld_u32(p + 8);
+                c = p + bam_cigar_at(bam_l_name(p));
+                x = bam_pos(p);
                 base = slot_off[rid];
                 len_ref = slot_off[rid + 1] - base - 1;
             }
@@ -134,19 +131,6 @@ __global__ void __launch_bounds__(256) depth_add_kernel(const uint8_t *bam, cons
             emit(slots, b, -1, lane, combine != 0);
         }
     }
-}
-
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_xor((long long)v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int32_t wave_min(int32_t v) {
-    for (int d = 32; d; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int32_t wave_max(int32_t v) {
-    for (int d = 32; d; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
 }
 
 // the reference of slot s among [lo, hi]: the last r with slot_off[r] <= s

@@ -25,6 +25,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "wave_ops.h"
 
 namespace bwams {
 namespace {
@@ -136,11 +137,6 @@ struct BucketArgs {
 
 // lane = one sorted window; the lane at the head of a bucket's run does the bucket.  Counters and free-slot ranges are
 // handed out once per wavefront (a per-bucket atomic on one address would be two billion of them).
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1)
-        v += ((unsigned long long)(uint32_t)__shfl_down((int)(v >> 32), o) << 32 | (uint32_t)__shfl_down((int)v, o));
-    return v;
-}
 template <int PASS>
 __global__ __launch_bounds__(256) void emf_bucket_kernel(BucketArgs A) {
     const EmfBuild &B = A.B;

@@ -8,26 +8,13 @@
 // becomes a full-length mem_alnreg_t (score = l_seq * a).  One lane per read; a read's scratch is
 // sized by the length of its list (count -> scan -> fill + collapse -> scan -> emit).
 #include "common.h"
-#include "chain_kernels.h"
+#include "stage_state.h"
 
 namespace bwams {
 namespace {
 
 struct AlnP { int64_t loc, pos; int32_t rid; int32_t rev_alt; };        // mem_aln_perfect_t: is_rev bit 0, is_alt bit 1
 
-__device__ __forceinline__ int pos2rid(const DevBns &b, int64_t pos_f) {
-    int left = 0, mid = 0, right = b.n_seqs;
-    if (pos_f >= b.l_pac) return -1;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= b.contigs[mid].offset) {
-            if (mid == b.n_seqs - 1) break;
-            if (pos_f < b.contigs[mid + 1].offset) break;
-            left = mid + 1;
-        } else right = mid;
-    }
-    return mid;
-}
 __device__ __forceinline__ bool tail_matches(const DevEmf &t, uint32_t loc, const uint8_t *seed, bool is_rev, int len) {
     const int L = t.seed_len;
     len -= L;
@@ -129,12 +116,6 @@ __global__ void emfregs_fill_kernel(EmfRegArgs A, const int64_t *__restrict__ sc
     first_is_rev[r] = (uint8_t)(av[0].rev_alt & 1);
 }
 
-__global__ void emfregs_widen_kernel(const int32_t *a, int64_t n, int64_t *wide) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g > n) return;
-    wide[g] = g < n ? (int64_t)a[g] : 0;
-}
-
 // mem_perfect2reg (perfect_map.cpp:817-867)
 __global__ void emfregs_emit_kernel(EmfRegArgs A, const int64_t *__restrict__ scr_off, const int32_t *__restrict__ n_final,
                                     const int64_t *__restrict__ out_off, bwams_alnreg_t *out) {
@@ -192,7 +173,7 @@ void launch_emfregs_count(const EmfRegArgs &A, int64_t *wide, hipStream_t st) {
 void launch_emfregs_fill(const EmfRegArgs &A, const int64_t *scr_off, int32_t *n_final, uint8_t *first_is_rev, int64_t *wide,
                          hipStream_t st) {
     if (A.nseq > 0) emfregs_fill_kernel<<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A, scr_off, n_final, first_is_rev);
-    emfregs_widen_kernel<<<(unsigned)((A.nseq + 256) / 256), 256, 0, st>>>(n_final, A.nseq, wide);
+    launch_widen1(n_final, A.nseq, wide, st);
 }
 void launch_emfregs_emit(const EmfRegArgs &A, const int64_t *scr_off, const int32_t *n_final, const int64_t *out_off,
                          bwams_alnreg_t *out, hipStream_t st) {

@@ -28,20 +28,6 @@ __device__ __forceinline__ int cal_max_gap(const bwams_mem_opt_t &o, int qlen) {
     return l < (o.w << 1) ? l : (o.w << 1);
 }
 
-__device__ __forceinline__ int pos2rid(const DevBns &b, int64_t pos_f) {
-    int left = 0, mid = 0, right = b.n_seqs;
-    if (pos_f >= b.l_pac) return -1;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= b.contigs[mid].offset) {
-            if (mid == b.n_seqs - 1) break;
-            if (pos_f < b.contigs[mid + 1].offset) break;
-            left = mid + 1;
-        } else right = mid;
-    }
-    return mid;
-}
-
 __device__ __forceinline__ int seedcov(const bwams_alnreg_t &a, const bwams_chain_t &c, const bwams_chain_seed_t *seeds) {
     int cov = 0;
     for (int i = 0; i < c.n; ++i) {
@@ -192,9 +178,6 @@ __global__ void ext_widen_kernel(const int32_t *cnt, const int32_t *state, const
 // loads, in flight for the 64 slots of a wave together — and writes its SeqPair records; then the wave copies the bytes of one slot
 // after the other, the slot's fields broadcast from its lane.  (A wave per slot paid the chain of dependent loads once per slot:
 // 5.2 ms per step for 3.6 M tasks among 21.9 M slots.)
-__device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
-    return ((int64_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)v, src);
-}
 // lsrc / rsrc != nullptr: the tasks are extended IN PLACE (bwams_extend_run) — a task's sequences are where they lie, the read in the
 // chunk's base codes and the window in the resident .0123 text, read backwards for a left extension; what is written per task is the two
 // start offsets {query, target} and no byte is copied (the copies were 2.2 of the 3.9 ms this stage took per million reads).  The flat
@@ -516,10 +499,6 @@ __device__ __forceinline__ bool purge_keep_anyway_w(const bwams_chain_seed_t &s,
 // does; on a repeat-heavy genome (27 k reads per million beyond 128 regions) the middle class is what keeps enough wavefronts on them.
 constexpr int kSelCap[3] = {256, 640, 1280};
 constexpr int kSelUnroll = 6;            // regions of the bulk scan loaded together
-
-__device__ __forceinline__ int64_t readlane64(int64_t v, int j) {
-    return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, j);
-}
 
 // purge_class's first two returns (a purged region, a region that does not contain the seed) without a branch
 __device__ __forceinline__ bool sel_contains(const KReg &q, const bwams_chain_seed_t &s) {

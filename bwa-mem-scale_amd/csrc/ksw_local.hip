@@ -21,7 +21,6 @@ namespace bwams {
 namespace {
 
 constexpr int kKswWaves = 4;
-constexpr int KSW_XBYTE = 0x10000, KSW_XSTOP = 0x20000, KSW_XSUBO = 0x40000, KSW_XSTART = 0x80000;
 
 struct KswOut {
     int score, te, qe, score2, te2, tb, qb;

@@ -50,17 +50,13 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "common.h"
+#include "bam_rec.h"
 
 namespace bwams {
 namespace {
 
-constexpr int kGroup = 16;
 constexpr int kQualMin = 15, kScoreCap = 16383;
 constexpr int32_t kMaxRef = 1 << 30;                  // refIDs of the decision: [0, 2^30), so that ref << 33 and one more fit 64 bits
-
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) {          // little-endian, any alignment
-    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
 
 __device__ __forceinline__ uint32_t qual_sum4(uint32_t w, uint32_t keep) {   // the bytes of w >= 15 that `keep` (bit per byte) selects
     uint32_t s = 0;
@@ -77,10 +73,10 @@ __global__ void __launch_bounds__(256) md_head_kernel(const uint8_t *bam, const 
         uint32_t h = 1;
         if (r > 0) {
             const uint8_t *p = bam + rec_off[r - 1], *q = bam + rec_off[r];
-            const uint32_t l = p[12];
-            if (l == q[12]) {
+            const uint32_t l = bam_l_name(p);
+            if (l == bam_l_name(q)) {
                 uint32_t k = 0;
-                while (k < l && p[36 + k] == q[36 + k]) ++k;
+                while (k < l && p[kBamName + k] == q[kBamName + k]) ++k;
                 h = k < l;
             }
         }
@@ -95,20 +91,15 @@ __global__ void __launch_bounds__(256) md_rec_kernel(const uint8_t *bam, const i
     // every lane of a group runs the same number of iterations (r depends on the group only), so the shuffles below see all 16
     for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroup; r < n_rec; r += n_groups) {
         const uint8_t *p = bam + rec_off[r];
-        const int32_t rid = (int32_t)ld_u32(p + 4), pos = (int32_t)ld_u32(p + 8);
-        const uint32_t l_name = p[12];
-        const uint32_t n_cig = (uint32_t)p[16] | (uint32_t)p[17] << 8;
-        const uint32_t flag = (uint32_t)p[18] | (uint32_t)p[19] << 8;
-        const int64_t l_seq = (int32_t)ld_u32(p + 20);
+        const int32_t rid = bam_ref_id(p), pos = bam_pos(p);
+        const uint32_t l_name = bam_l_name(p), n_cig = bam_n_cig(p), flag = bam_flag(p);
+        const int64_t l_seq = bam_l_seq(p);
         const bool want = !(flag & 0x904);                     // a mapped primary: its coordinate and score
         int64_t rlen = 0, clip = 0;
         uint32_t score = 0;
         if (want) {
-            const uint8_t *c = p + 36 + l_name;
-            for (uint32_t k = g; k < n_cig; k += kGroup) {
-                const uint32_t op = ld_u32(c + 4 * k), o = op & 15;
-                if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rlen += op >> 4;
-            }
+            const uint8_t *c = p + bam_cigar_at(l_name);
+            rlen = cigar_ref_len(c, n_cig, g, kGroup);
             if (g == 0 && !(flag & 16)) {                    // forward: the S and H lengths before the first other op
                 for (uint32_t k = 0; k < n_cig; ++k) {
                     const uint32_t op = ld_u32(c + 4 * k), o = op & 15;
@@ -123,8 +114,8 @@ __global__ void __launch_bounds__(256) md_rec_kernel(const uint8_t *bam, const i
                     clip += op >> 4;
                 }
             }
-            const uint8_t *qs = c + 4 * (int64_t)n_cig + (l_seq + 1) / 2;
-            const int64_t n_q = std::min<int64_t>(l_seq, (p + 4 + ld_u32(p)) - qs);     // never past the record's block_size
+            const uint8_t *qs = p + bam_qual_at(l_name, n_cig, l_seq);
+            const int64_t n_q = std::min<int64_t>(l_seq, (p + 4 + bam_block_size(p)) - qs);     // never past the record's block_size
             if (n_q > 0 && qs[0] != 0xFF) {                   // QUAL present: aligned dwords over [qs, qs + n_q)
                 const uintptr_t a0 = reinterpret_cast<uintptr_t>(qs) & ~(uintptr_t)3;
                 const uintptr_t e = reinterpret_cast<uintptr_t>(qs) + (uintptr_t)n_q;
@@ -327,13 +318,13 @@ __global__ void __launch_bounds__(256) md_loc_kernel(const uint8_t *bam, const i
         while (r < r1 && (rec[r].flag & 0x900)) ++r;         // the first primary, else the first record
         if (r == r1) r = r0;
         const uint8_t *p = bam + rec_off[r];
-        const uint32_t l_name = p[12];
+        const uint32_t l_name = bam_l_name(p);
         bwams_dup_loc_t L;
         L.rg = -1; L.lib = G.n_lib - 1; L.tile = L.x = L.y = 0; L.has = 0;
         if (G.walk) {                                         // rule 9: the aux fields by their types, to the record's end
-            const int64_t n = (int64_t)ld_u32(p) + 4;         // the record with its block_size
-            const int64_t l_seq = (int32_t)ld_u32(p + 20);
-            int64_t a = 36 + (int64_t)l_name + 4 * (int64_t)((uint32_t)p[16] | (uint32_t)p[17] << 8) + (l_seq + 1) / 2 + l_seq;
+            const int64_t n = (int64_t)bam_block_size(p) + 4;         // the record with its block_size
+            const int64_t l_seq = bam_l_seq(p);
+            int64_t a = bam_aux_at(l_name, bam_n_cig(p), l_seq);
             bool ok = l_seq >= 0 && a <= n, found = false;
             int64_t v0 = 0, v1 = 0;                           // RG's value: p[v0, v1)
             while (ok && a < n) {
@@ -374,7 +365,7 @@ __global__ void __launch_bounds__(256) md_loc_kernel(const uint8_t *bam, const i
                 }
             }
         }
-        const uint8_t *s = p + 36;                            // rule 10: the name without its NUL
+        const uint8_t *s = p + kBamName;                            // rule 10: the name without its NUL
         const uint32_t n = l_name ? l_name - 1 : 0;
         uint32_t colons = 0;
         for (uint32_t k = 0; k < n; ++k) colons += s[k] == ':';

@@ -27,31 +27,10 @@
 namespace bwams {
 namespace {
 
-constexpr int KSW_XBYTE = 0x10000, KSW_XSUBO = 0x40000, KSW_XSTART = 0x80000;
-
 __device__ __forceinline__ uint64_t hash_64(uint64_t key) {          // utils.h:117-128
     key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
     key += (key << 3); key ^= (key >> 15); key += ~(key << 27); key ^= (key >> 31);
     return key;
-}
-__device__ __forceinline__ int infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist) {      // bwamem_pair.cpp:57-65
-    const int r1 = (b1 >= l_pac), r2 = (b2 >= l_pac);
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-__device__ __forceinline__ int pos2rid(const DevBns &b, int64_t pos_f) {                             // bntseq.cpp:397-413
-    if (pos_f >= b.l_pac) return -1;
-    int left = 0, mid = 0, right = b.n_seqs;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= b.contigs[mid].offset) {
-            if (mid == b.n_seqs - 1) break;
-            if (pos_f < b.contigs[mid + 1].offset) break;
-            left = mid + 1;
-        } else right = mid;
-    }
-    return mid;
 }
 __device__ __forceinline__ int is_alt(const bwams_alnreg_t &r) { return (r.n_comp_is_alt >> 30) & 3; }
 

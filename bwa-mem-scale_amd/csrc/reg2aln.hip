@@ -24,11 +24,10 @@
 #include "common.h"
 #include "chain_kernels.h"
 #include "wave_ops.h"
+#include "ksw_global2_wave.h"
 
 namespace bwams {
 namespace {
-
-constexpr int kMinusInf = -0x40000000;
 
 __device__ __forceinline__ int infer_bw(int l1, int l2, int score, int a, int q, int r) {
     if (l1 == l2 && l1 * a - score < (q + r - a) << 1) return 0;
@@ -45,21 +44,6 @@ __device__ __forceinline__ int64_t read_of_region(const int64_t *__restrict__ of
         if (off[mid] <= k) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-// bns_pos2rid (bntseq.cpp:397-411)
-__device__ __forceinline__ int pos2rid_f(const DevBns &b, int64_t pos_f) {
-    if (pos_f >= b.l_pac) return -1;
-    int left = 0, mid = 0, right = b.n_seqs;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= b.contigs[mid].offset) {
-            if (mid == b.n_seqs - 1) break;
-            if (pos_f < b.contigs[mid + 1].offset) break;
-            left = mid + 1;
-        } else right = mid;
-    }
-    return mid;
 }
 
 struct Seqs {                                        // the two sequences as bwa_gen_cigar2 aligns them
@@ -138,7 +122,7 @@ __device__ void finish_record(const RegAlnArgs &A, int64_t k, const bwams_alnreg
         if (clip3) cigar[n_cigar++] = (uint32_t)clip3 << 4 | 3;
     }
     bwams_aln_t a;
-    a.rid = pos2rid_f(A.bns, pos);
+    a.rid = pos2rid(A.bns, pos);
     a.pos = pos - (a.rid >= 0 ? A.bns.contigs[a.rid].offset : 0);
     a.flag = ar.secondary >= 0 ? 0x100 : 0;
     a.is_rev = is_rev;
@@ -400,27 +384,6 @@ __global__ __launch_bounds__(64) void aln_dp_kernel(RegAlnArgs A, int cls) {
 // direction matrix goes to HBM a byte per cell as before, the traceback runs once, on lane 0, after the retry loop has settled.
 constexpr int kWaveCols = 512;                        // query columns a wave's LDS row holds (4 KB)
 constexpr int kWaveTgt = 1024;                        // target bases staged in LDS (longer targets are read from HBM row by row)
-constexpr int kNegScan = -2000000000;
-
-// inclusive prefix maximum over the wavefront: four DPP steps inside each row of 16 lanes, then the row totals carried across with
-// row_bcast:15 (into rows 1 and 3) and row_bcast:31 (into rows 2 and 3).  A lane without a source keeps its value.  (Six
-// ds_bpermute shuffles, each waiting on the one before, were most of a row step's latency.)
-__device__ __forceinline__ int wave_incl_max(int v, int) {
-    asm volatile("s_nop 4\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_max_i32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
-                 : "+v"(v));
-    return v;
-}
 
 // the DP of ksw_global2 (ksw.cpp:588-637) for band w; returns the score, leaves the direction bytes in z
 __device__ int global2_dp_wave(const RegAlnArgs &A, const Seqs &S, int w, int2 *eh, const uint8_t *qs, const uint8_t *ts, uint32_t *z, int lane) {
@@ -436,55 +399,8 @@ __device__ int global2_dp_wave(const RegAlnArgs &A, const Seqs &S, int w, int2 *
     __syncthreads();
     for (int i = 0; i < tlen; ++i) {
         const int tb = __builtin_amdgcn_readfirstlane(ts ? (int)ts[i] : S.ra(i));
-        const int8_t *mrow = &o.mat[(tb > 4 ? 4 : tb) * 5];
-        // the row of the scoring matrix as five bytes of one scalar: a lane's score is a shift and a sign extension
-        const uint64_t mpk = (uint64_t)(uint8_t)mrow[0] | (uint64_t)(uint8_t)mrow[1] << 8 | (uint64_t)(uint8_t)mrow[2] << 16 |
-                             (uint64_t)(uint8_t)mrow[3] << 24 | (uint64_t)(uint8_t)mrow[4] << 32;
-        const int beg = i > w ? i - w : 0;
-        const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
-        const int h1_first = beg == 0 ? -(o.o_del + o.e_del * (i + 1)) : kMinusInf;
-        uint8_t *zi = reinterpret_cast<uint8_t *>(z + (size_t)i * zw);
-        int f_carry = kMinusInf, h_carry = h1_first, h_end = h1_first;
-        for (int c0 = beg; c0 < end; c0 += 64) {
-            // branch-free but for the two stores; lanes behind the row's end read its last column and are masked out of the scan.
-            // Cross-lane moves are DPP (the neighbour) and v_readlane (lane 63, the row's last column): no LDS permutes.
-            const int j = c0 + lane;
-            const bool act = j < end;
-            const int jj = act ? j : end - 1;
-            const int2 p = eh[jj];
-            int qb = qs[jj];
-            qb = qb > 4 ? 4 : qb;
-            const int m = p.x + (int)(int8_t)(uint8_t)(mpk >> (qb << 3));
-            int e = p.y;
-            const int t_ins = m - oe_ins;
-            const int g = act ? t_ins + j * o.e_ins : kNegScan;
-            const int P = wave_incl_max(g, lane);
-            const int Pex = lane_shr1(P, kNegScan);                        // lane 0: nothing to its left in this chunk
-            const int fc = f_carry - lane * o.e_ins;                       // what the gap open before this chunk has become
-            const int fp = Pex - (j - 1) * o.e_ins;
-            const int f = fc > fp ? fc : fp;
-            uint32_t d = m >= e ? 0u : 1u;
-            int h = m >= e ? m : e;
-            d = h >= f ? d : 2u;
-            h = h >= f ? h : f;
-            const int t = m - oe_del;
-            e -= o.e_del;
-            d |= e > t ? 1u << 2 : 0u;
-            e = e > t ? e : t;
-            const int fn = f - o.e_ins;
-            d |= fn > t_ins ? 2u << 4 : 0u;
-            const int hl = lane_shr1(h, h_carry);                          // lane 0 takes the previous chunk's last h
-            if (act) {
-                eh[j] = make_int2(hl, e);
-                zi[j - beg] = (uint8_t)d;
-            }
-            const int fnext = fn > t_ins ? fn : t_ins;
-            f_carry = __builtin_amdgcn_readlane(fnext, 63);
-            h_carry = __builtin_amdgcn_readlane(h, 63);
-            const int last = end - 1 - c0;                                 // the row's last column, if it lies in this chunk
-            if (last < 64) h_end = __builtin_amdgcn_readlane(h, last);
-        }
-        if (lane == 0) eh[end] = make_int2(h_end, kMinusInf);
+        ksw_global2_row_wave<true>(o, oe_del, oe_ins, ksw_mat_row(&o.mat[(tb > 4 ? 4 : tb) * 5]), i, w, qlen, eh, qs, lane,
+                                   reinterpret_cast<uint8_t *>(z + (size_t)i * zw));
         __syncthreads();
     }
     return eh[qlen].x;

@@ -396,14 +396,6 @@ __device__ __forceinline__ Mate mate_of(const Read &R, int k) {          // mem_
     return m;
 }
 
-// mem_infer_dir (bwamem_pair.cpp:57-65)
-__device__ __forceinline__ int infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist) {
-    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
 __device__ __forceinline__ int raw_mapq(int diff, int a) {               // bwamem_pair.cpp:432
 #pragma clang fp contract(off)
     return (int)(6.02 * diff / a + .499);

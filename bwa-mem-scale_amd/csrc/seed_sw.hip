@@ -8,32 +8,17 @@
 // semantics), an apply kernel compacts each chain's seed list in place, and the flat seed array is
 // re-packed so that a read's regions stay one per remaining seed.
 #include "common.h"
-#include "chain_kernels.h"
+#include "stage_state.h"
 
 namespace bwams {
 namespace {
 
 constexpr int MEM_SHORT_EXT = 50, MEM_SHORT_LEN = 200;
-constexpr int KSW_XSTART = 0x80000;
 
 __device__ __forceinline__ bool read_is_long(const bwams_mem_opt_t &o, int L, int *min_hsp) {
     const double min_l = o.min_chain_weight ? (double)(1.1f * (float)o.min_chain_weight) : (double)5.5f * log((double)L);
     *min_hsp = (int)((double)o.a * min_l + .499);
     return !(min_l > (double)(0.05f * (float)L));
-}
-
-__device__ __forceinline__ int pos2rid(const DevBns &b, int64_t pos_f) {
-    int left = 0, mid = 0, right = b.n_seqs;
-    if (pos_f >= b.l_pac) return -1;
-    while (left < right) {
-        mid = (left + right) >> 1;
-        if (pos_f >= b.contigs[mid].offset) {
-            if (mid == b.n_seqs - 1) break;
-            if (pos_f < b.contigs[mid + 1].offset) break;
-            left = mid + 1;
-        } else right = mid;
-    }
-    return mid;
 }
 
 // lane per chain: the SW window of each of its seeds (win[4 * slot] = qb, qe - qb, tlen; rb separately), or "no SW"
@@ -164,12 +149,6 @@ __global__ void seedsw_readoff_kernel(const int64_t *__restrict__ chain_off, con
     seed_off[r] = new_off[j < n_chains ? j : n_chains];
 }
 
-__global__ void widen1_kernel(const int32_t *a, int64_t n, int64_t *wide) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g > n) return;
-    wide[g] = g < n ? (int64_t)a[g] : 0;
-}
-
 }  // namespace
 
 void launch_seedsw_plan(const SeedSwArgs &A, int64_t *wide, hipStream_t st) {
@@ -191,7 +170,7 @@ void launch_seedsw_apply(const SeedSwArgs &A, const int64_t *offs, const bwams_k
                          hipStream_t st) {
     if (A.n_chains <= 0) return;
     seedsw_apply_kernel<<<(unsigned)((A.n_chains + 255) / 256), 256, 0, st>>>(A, offs, res, new_n);
-    widen1_kernel<<<(unsigned)((A.n_chains + 256) / 256), 256, 0, st>>>(new_n, A.n_chains, wide);
+    launch_widen1(new_n, A.n_chains, wide, st);
 }
 void launch_seedsw_repack(const SeedSwArgs &A, const int32_t *new_n, const int64_t *new_off, bwams_chain_seed_t *out,
                           const int64_t *chain_off, int64_t *seed_off, hipStream_t st) {

@@ -117,6 +117,7 @@ int check_opt(const bwams_mem_opt_t *o, const char *who);
 int dev_bns(bwams_index *ix, DevBns *out);                         // materialises the one-sequence default
 void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm);
 void sw_params(const bwams_sw_opt_t &o, SwParams *prm);
+void launch_widen1(const int32_t *a, int64_t n, int64_t *wide, hipStream_t st);                     // row a of n + 1 as int64, the last 0
 void launch_widen2(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide, hipStream_t st);   // rows a | b of n + 1 as int64, the last of each 0
 int scan_rows(bwams_batch *b, const int64_t *in, int64_t *out, int rows, int64_t n1);               // exclusive scan of each row of n1
 void stage_state_stats(const StageState *s, bwams_stats_t *out);   // timing and counts for bwams_batch_stats (api.hip)

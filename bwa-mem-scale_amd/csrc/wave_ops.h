@@ -1,4 +1,5 @@
-// wave_ops.h — cross-lane primitives of a 64-lane wavefront built on DPP (no LDS traffic).
+// wave_ops.h — cross-lane primitives of a 64-lane wavefront: DPP and v_readlane where they serve (no LDS traffic), ds_bpermute
+// shuffles (shfl64, wave_sum / wave_min / wave_max) where any lane may be the source.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,7 +17,7 @@ __device__ __forceinline__ int dppi(int old, int v) {
 // row_mask) are not written, i.e. keep their own value, so no identity constant is needed.  A VALU write followed
 // by a DPP read of the same register needs two wait states: the s_nop 1 in front of every step.
 __device__ __forceinline__ int scan_max(int v) {
-    asm("s_nop 4\n\t"         // also covers "VALU writes EXEC, then a DPP instruction" (5 wait states): the compiler cannot see into the asm
+    asm volatile("s_nop 4\n\t"         // also covers "VALU writes EXEC, then a DPP instruction" (5 wait states): the compiler cannot see into the asm
         "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\t"
         "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
@@ -33,6 +34,27 @@ __device__ __forceinline__ int scan_max(int v) {
 }
 __device__ __forceinline__ int lane_shr1(int v, int fill) { return dppi<0x138, 0xF, 0xF>(fill, v); }   // wave_shr:1
 
+// a 64-bit value of lane l (wave-uniform l: v_readlane) or of lane src (any src: ds_bpermute), as two 32-bit halves
+__device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
+    return (int64_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) |
+                     (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)v, l));
+}
+__device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
+    return ((int64_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)v, src);
+}
+// reductions over the 64 lanes, the result in every lane
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_xor((long long)v, d, 64);
+    return v;
+}
+__device__ __forceinline__ int32_t wave_min(int32_t v) {
+    for (int d = 32; d; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ int32_t wave_max(int32_t v) {
+    for (int d = 32; d; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
 
 // One value per wave from a global cursor: lane 0 advances it by `step`, every lane gets the old value.
 // Deliberately out of line.  Inlined into a `for (;;)` with a `continue`, the lane-0 branch around the
