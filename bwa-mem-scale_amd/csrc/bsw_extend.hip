@@ -659,6 +659,11 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
     int64_t pid = 0, pid_end = 0;
     bool exhausted = false;
     bool alive = false;
+    // the ticket in hand, staged when it is taken: lane k < kQuadChunk holds the descriptor of its k-th task (s_qh: qlen | h0 << 8 | the
+    // first target base << 24; s_w: the clamped band), a refilling quad fetches its own with ds_bpermute
+    int64_t pid0 = 0, s_qo = 0, s_to = 0;
+    int s_cur = 0, s_tlen = 0, s_w = 0;
+    uint32_t s_qh = 0u;
     int cur = 0, qlen = 0, tlen = 0, h0 = 0, w = 0, i = 0, beg = 0, end = 0;
     int mx = 0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0, tb_next = 4;
     const uint8_t *tr = ref;
@@ -668,60 +673,125 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
     int base = 0, h1 = 0, key = -1, hlast = -1, c_max = kPkNeg, c_h = 0;
     uint32_t nzl = 0u, nzf = 0u;
     uint2 tt = make_uint2(0u, 0u);
+#ifdef BWAMS_BSWDBG                 // wave-time of the refill branch and of the pass (printed by run_side under BWAMS_VERBOSE)
+    const unsigned long long T0 = __builtin_amdgcn_s_memtime();
+    unsigned long long t_refill = 0, t_pass = 0, n_events = 0, n_filled = 0, n_iter = 0;
+#endif
 
     for (;;) {
         const unsigned long long need_m = __ballot(!alive);
         if (need_m) {
+#ifdef BWAMS_BSWDBG
+            const unsigned long long Ta = __builtin_amdgcn_s_memtime();
+#endif
             if (pid >= pid_end && !exhausted) {
                 pid = (int64_t)wave_ticket(head, (unsigned long long)kQuadChunk);
                 pid_end = pid + kQuadChunk < n_list ? pid + kQuadChunk : n_list;
                 if (pid >= n_list) { exhausted = true; pid_end = pid; }
+                // one dependent chain of loads (list entry, task, its two source offsets, the first target base) for the ticket's
+                // sixteen tasks, and the band clamp with its two divisions once, sixteen lanes wide
+                pid0 = pid;
+                if (lane < kQuadChunk && pid + lane < pid_end) {
+                    s_cur = list[pid + lane];
+                    const bwams_seqpair_t *sp = &pairs[s_cur];
+                    const int l2 = sp->len2, hh0 = sp->h0;
+                    s_tlen = sp->len1;
+                    if (src) { const int64_t id = sp->id; s_qo = src[2 * id]; s_to = src[2 * id + 1]; }
+                    else { s_qo = (int64_t)sp->idq; s_to = (int64_t)sp->idr; }
+                    uint32_t tb = s_tlen > 0 ? (uint32_t)ref[s_to] : 4u;
+                    tb = tb > 4u ? 4u : tb;
+                    s_qh = (uint32_t)l2 | ((uint32_t)hh0 << 8) | (tb << 24);          // the class: qlen <= 191, 0 <= h0 < 2^14
+                    int ww = w0;
+                    int max_ins = (int)((double)(l2 * prm.max_sc + prm.end_bonus - o_ins) / e_ins + 1.);
+                    max_ins = max_ins > 1 ? max_ins : 1;
+                    ww = ww < max_ins ? ww : max_ins;
+                    int max_del = (int)((double)(l2 * prm.max_sc + prm.end_bonus - o_del) / e_del + 1.);
+                    max_del = max_del > 1 ? max_del : 1;
+                    s_w = ww < max_del ? ww : max_del;
+                }
             }
             const int avail = (int)(pid_end - pid);
             const int nq = __popcll(need_m & kLeaders);
             const int rank = __popcll(need_m & kLeaders & ((1ull << (q * LPT)) - 1ull));
-            if (!alive && rank < avail) {
-                cur = list[pid + rank];
-                const bwams_seqpair_t sp = pairs[cur];
-                qlen = sp.len2; tlen = sp.len1; h0 = sp.h0;
-                const uint8_t *tq = qer + (src ? src[2 * (int64_t)sp.id] : (int64_t)sp.idq);
-                tr = ref + (src ? src[2 * (int64_t)sp.id + 1] : (int64_t)sp.idr);
-                start_row = true;
-                for (int p = g; p <= (qlen >> 1); p += LPT) {      // row -1 of the DP and the query, a pair of columns per lane and step
-                    uint32_t hh = 0, ss = 0;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int c = 2 * p + k;
-                        int h = 0;
-                        if (c <= qlen) { h = h0; if (c >= 1) { h = h0 - oe_ins - (c - 1) * e_ins; h = h > 0 ? h : 0; } }
-                        uint32_t qb = c < qlen ? (uint32_t)tq[c * dir] : 4u;
-                        const uint32_t sel = qb < 4u ? 2u * qb : 0x0du;
-                        hh |= (uint32_t)h << (16 * k);
-                        ss |= sel << (8 * k);
+            if (avail > 0) {                                              // wave-uniform: nothing to hand out once the list has run dry
+                const bool take = !alive && rank < avail;
+                // every lane fetches (a bpermute reads nothing from a lane that is switched off), the taking quads keep
+                const int sk = take ? (int)(pid - pid0) + rank : 0;
+                const int f_cur = __shfl(s_cur, sk), f_tlen = __shfl(s_tlen, sk), f_w = __shfl(s_w, sk);
+                const uint32_t f_qh = (uint32_t)__shfl((int)s_qh, sk);
+                const int64_t f_qo = shfl64(s_qo, sk), f_to = shfl64(s_to, sk);
+                if (take) {
+                    cur = f_cur; qlen = (int)(f_qh & 0xffu); h0 = (int)((f_qh >> 8) & 0x3fffu); tlen = f_tlen; w = f_w;
+                    tr = ref + f_to;
+                    start_row = true;
+                    mx = h0; max_i = -1; max_j = -1; max_ie = -1; gscore = -1; max_off = 0;
+                    beg = 0; end = qlen; i = 0;
+                    alive = tlen > 0;
+                    if (!alive && g == 0) {
+                        bwams_seqpair_t *o = &pairs[cur];
+                        o->score = mx; o->qle = 0; o->tle = 0; o->gtle = 0; o->gscore = -1; o->max_off = 0;
                     }
-                    t_hp[p] = hh; t_ep[p] = 0u; t_sel[p] = (uint16_t)ss;
+                    tb_next = (int)(f_qh >> 24);
                 }
-                w = w0;
-                {
-                    int max_ins = (int)((double)(qlen * prm.max_sc + prm.end_bonus - o_ins) / e_ins + 1.);
-                    max_ins = max_ins > 1 ? max_ins : 1;
-                    w = w < max_ins ? w : max_ins;
-                    int max_del = (int)((double)(qlen * prm.max_sc + prm.end_bonus - o_del) / e_del + 1.);
-                    max_del = max_del > 1 ? max_del : 1;
-                    w = w < max_del ? w : max_del;
+                // row -1 of the DP and the query of every slot that took a task, one slot at a time with the whole wave: a lane writes one
+                // granule of four columns (two pairs), so a query of up to 255 bases is one trip and one memory round trip.  A granule inside
+                // the query is one 4-byte load at the task's own bytes (at any alignment, reversed for dir = -1); the granule the query ends
+                // in takes byte loads, so no load touches a byte that is not the task's
+                for (unsigned long long fill_m = __ballot(take) & kLeaders; fill_m; fill_m &= fill_m - 1ull) {
+                    const int sl = __ffsll((long long)fill_m) - 1;                // lane 0 of the slot
+                    const int f_qlen = __builtin_amdgcn_readlane(qlen, sl), f_h0 = __builtin_amdgcn_readlane(h0, sl);
+                    const uint8_t *const f_q = qer + readlane64(f_qo, sl);
+                    uint32_t *const f_hp = pk_lds + 16 + (size_t)((threadIdx.x >> 6) * TPW + (sl >> 2)) * (size_t)((5 * P) / 2 + 6);
+                    uint32_t *const f_ep = f_hp + P + 2;
+                    uint16_t *const f_sel = reinterpret_cast<uint16_t *>(f_ep + P + 2);
+                    const int c0 = 4 * lane, p_last = f_qlen >> 1;
+                    // every load is issued before the first of them is waited for: the values meet only behind the branches
+                    const bool full = c0 + 3 < f_qlen, edge = !full && c0 < f_qlen;
+                    uint32_t v = 0u, b0 = 4u, b1 = 4u, b2 = 4u;
+                    if (full) __builtin_memcpy(&v, dir > 0 ? f_q + c0 : f_q - c0 - 3, 4);
+                    if (edge) {                                                  // positions past the query's end read its last byte again
+                        const int last = f_qlen - 1;
+                        b0 = f_q[c0 * dir];
+                        b1 = f_q[(c0 + 1 < last ? c0 + 1 : last) * dir];
+                        b2 = f_q[(c0 + 2 < last ? c0 + 2 : last) * dir];
+                    }
+                    b1 = c0 + 1 < f_qlen ? b1 : 4u;
+                    b2 = c0 + 2 < f_qlen ? b2 : 4u;
+                    const uint32_t qw = full ? (dir > 0 ? v : __builtin_amdgcn_perm(v, v, 0x00010203u)) : (b0 | (b1 << 8) | (b2 << 16) | 0x04000000u);
+                    uint32_t hh[2] = {0u, 0u}, ss[2] = {0u, 0u};
+    #pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int c = c0 + k;
+                        int h = 0;
+                        if (c <= f_qlen) { h = f_h0; if (c >= 1) { h = f_h0 - oe_ins - (c - 1) * e_ins; h = h > 0 ? h : 0; } }
+                        const uint32_t qb = (qw >> (8 * k)) & 0xffu;
+                        const uint32_t sel = qb < 4u ? 2u * qb : 0x0du;
+                        hh[k >> 1] |= (uint32_t)h << (16 * (k & 1));
+                        ss[k >> 1] |= sel << (8 * (k & 1));
+                    }
+    #pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const int p = 2 * lane + k;
+                        if (p <= p_last) { f_hp[p] = hh[k]; f_ep[p] = 0u; f_sel[p] = (uint16_t)ss[k]; }
+                    }
                 }
-                mx = h0; max_i = -1; max_j = -1; max_ie = -1; gscore = -1; max_off = 0;
-                beg = 0; end = qlen; i = 0;
-                alive = tlen > 0;
-                if (!alive && g == 0) {
-                    bwams_seqpair_t *o = &pairs[cur];
-                    o->score = mx; o->qle = 0; o->tle = 0; o->gtle = 0; o->gscore = -1; o->max_off = 0;
-                }
-                tb_next = alive ? (int)tr[0] : 4;
+                // the lanes that wrote a row are not the quad that reads it: the writes are done before the pass below begins (the row is
+                // this wavefront's alone, so no barrier)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
             pid += nq < avail ? nq : avail;
+#ifdef BWAMS_BSWDBG
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            t_refill += __builtin_amdgcn_s_memtime() - Ta;
+            ++n_events; n_filled += (unsigned long long)(nq < avail ? nq : avail);
+#endif
             if (exhausted && !wave_any(alive)) break;
         }
+#ifdef BWAMS_BSWDBG
+        const unsigned long long Tb = __builtin_amdgcn_s_memtime();
+#endif
 
         // ---- one PASS (a window of 32 columns) of the current row of every live task.  The tasks of a wavefront do not wait for
         // each other at the end of a row: a task whose row needs a second window takes it in the next iteration while the others
@@ -936,7 +1006,19 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                 start_row = true;
             }
         }
+#ifdef BWAMS_BSWDBG
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        t_pass += __builtin_amdgcn_s_memtime() - Tb;
+        ++n_iter;
+#endif
     }
+#ifdef BWAMS_BSWDBG
+    if (lane == 0) {
+        unsigned long long *d = ctr->dbg + 40;
+        atomicAdd(&d[0], __builtin_amdgcn_s_memtime() - T0); atomicAdd(&d[1], t_refill); atomicAdd(&d[2], t_pass);
+        atomicAdd(&d[3], n_events); atomicAdd(&d[4], n_filled); atomicAdd(&d[5], n_iter); atomicAdd(&d[6], 1ull);
+    }
+#endif
     for (int o = 32; o > 0; o >>= 1) cells += ((unsigned long long)__shfl_down((unsigned)(cells >> 32), o) << 32) | (unsigned)__shfl_down((unsigned)cells, o);
     if (lane == 0 && cells) atomicAdd(&ctr->bsw_cells, cells);
 }
