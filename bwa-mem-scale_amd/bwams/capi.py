@@ -31,7 +31,7 @@ SYMBOLS = [
     "bwams_seed_upload", "bwams_seed_run", "bwams_seed_counts", "bwams_seed_fetch",
     "bwams_ert_from_host", "bwams_ert_open", "bwams_ert_close", "bwams_ert_bytes", "bwams_ert_set_fat", "bwams_seed_run_ert",
     "bwams_ert_build", "bwams_ert_info", "bwams_ert_fetch", "bwams_ert_save", "bwams_debug_sort", "bwams_debug_regs_upload", "bwams_debug_aln_lists",
-    "bwams_debug_ext_regs_upload", "bwams_debug_dedup_counts",
+    "bwams_debug_ext_regs_upload", "bwams_debug_dedup_counts", "bwams_debug_pair_regs_upload", "bwams_debug_pair_counts",
     "bwams_emf_build", "bwams_emf_info", "bwams_emf_table_fetch", "bwams_emf_save",
     "bwams_bsw_extend", "bwams_bsw_upload", "bwams_bsw_run", "bwams_bsw_fetch",
     "bwams_batch_stats", "bwams_batch_sync", "bwams_ksw_align",
@@ -877,6 +877,8 @@ def lib():
         L.bwams_debug_aln_lists.argtypes = [vp, vp]
         L.bwams_debug_ext_regs_upload.argtypes = [vp, vp, i64, vp, i64]
         L.bwams_debug_dedup_counts.argtypes = [vp, vp]
+        L.bwams_debug_pair_regs_upload.argtypes = [vp, vp, i64, vp, i64]
+        L.bwams_debug_pair_counts.argtypes = [vp, vp]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
         L.bwams_index_set_fma.argtypes = [vp, vp, C.c_int, vp, C.c_int]
         L.bwams_index_fetch_fma.argtypes = [vp, vp, vp]
@@ -1451,6 +1453,24 @@ class Batch:
         reg_off = np.ascontiguousarray(reg_off, np.int64)
         _chk(lib().bwams_debug_regs_upload(self.h, _p(regs), len(regs), _p(reg_off), len(reg_off) - 1), "bwams_debug_regs_upload")
         self._n_final = len(regs)
+
+    PAIR_COUNTS = ("post_lane", "post_wave", "post_one_lane", "post_ert", "sort_rank", "sort_net", "sort_intro", "inserted", "mark_lane",
+                   "mark_wave256", "mark_wave2048", "mark_one_lane", "mark_rank", "mark_net", "post_second")
+
+    def debug_pair_regs_upload(self, regs, reg_off):
+        """Test hook: debug_regs_upload for the pairing stage (pair_run, mark_primary_se, pair_fetch run on these regions); refuses
+        also a rid outside the sequences, a reference span that is empty or outside the text, a negative score."""
+        regs = np.ascontiguousarray(regs, ALNREG_DTYPE)
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        _chk(lib().bwams_debug_pair_regs_upload(self.h, _p(regs), len(regs), _p(reg_off), len(reg_off) - 1), "bwams_debug_pair_regs_upload")
+        self._n_final = len(regs)
+
+    def debug_pair_counts(self):
+        """Test hook: what the last pair_run / mark_primary_se under BWAMS_PAIR_COUNT=1 did, as a dict over PAIR_COUNTS (visits per
+        rescue route, sorts per path, regions inserted, reads per marking route; include/bwams.h)."""
+        cnt = np.zeros(len(self.PAIR_COUNTS), np.int64)
+        _chk(lib().bwams_debug_pair_counts(self.h, _p(cnt)), "bwams_debug_pair_counts")
+        return dict(zip(self.PAIR_COUNTS, cnt.tolist()))
 
     DEDUP_COUNTS = ("triage", "lane", "wave128", "wave512", "wave2048", "one_lane", "shortcut", "hbm", "lds", "reg1", "reg2", "reg3", "reg4", "early")
 

@@ -30,6 +30,7 @@ void knobs_reload() {
     k.ext_inplace = env_int("BWAMS_EXT_INPLACE", 1);
     k.dedup_seq = env_int("BWAMS_DEDUP_SEQ", 0) == 1;
     k.dedup_count = env_int("BWAMS_DEDUP_COUNT", 0) == 1;
+    k.pair_count = env_int("BWAMS_PAIR_COUNT", 0) == 1;
     k.pair_drop_plan = getenv("BWAMS_PAIR_DROP_PLAN") != nullptr;
     k.trace_pair = env_int("BWAMS_TRACE_PAIR", 0);
     k.bsw_pk = env_int("BWAMS_BSW_PK", 1);

@@ -1,7 +1,7 @@
 // api_regions.hip — C-ABI entry points of the stages that finish a chunk's regions (include/bwams.h): bwams_dedup_*
 // (mem_sort_dedup_patch), bwams_pair_* (mate rescue, mem_mark_primary_se, mem_pair), bwams_emf_regs_* (mem_perfect2reg and its
 // merge), bwams_pestat* (mem_pestat) and the test hooks bwams_debug_sort, bwams_debug_ext_regs_upload and
-// bwams_debug_dedup_counts, over dedup.hip, pair.hip, ksw_local.hip and emf_regs.hip.
+// bwams_debug_dedup_counts and bwams_debug_pair_counts, over dedup.hip, pair.hip, ksw_local.hip and emf_regs.hip.
 // No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <algorithm>
 #include <cmath>
@@ -250,6 +250,13 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     A.aoff = aoff; A.ooff = ooff; A.n_fin = s->pr.nfin.p; A.n_pri = s->pr.npri.p; A.n_sw = s->pr.nsw.p; A.full = s->pr.full.p; A.ctr = b->d_ctr.p;
     A.anchor = nullptr; A.slot_read = nullptr; A.n_slots = 0; A.task = nullptr; A.trb = nullptr; A.tl1 = nullptr; A.aln = nullptr; A.pool = nullptr;
     A.ord = nullptr; A.zbuf = nullptr; A.srt = nullptr; A.heavy = nullptr;
+    const bool count_pr = knobs().pair_count != 0;        // tests: reads per route, sorts per path (bwams_debug_pair_counts)
+    if (count_pr) {
+        BWAMS_HIP(s->pr.cnt.ensure_n((size_t)kPairCounts));
+        BWAMS_HIP(hipMemsetAsync(s->pr.cnt.p, 0, kPairCounts * sizeof(unsigned long long), st));
+    }
+    A.cnt = count_pr ? s->pr.cnt.p : nullptr;
+    s->pr.counted = false;
     BWAMS_HIP(hipEventRecord(s->ev[14], st));
     BWAMS_HIP(hipMemsetAsync(A.full, 0, (size_t)n1, st));
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->pair_full, 0, 2 * sizeof(unsigned long long), st));
@@ -347,8 +354,12 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     if (!single_end) launch_pair_pair(A, s->pr.ooff.p, s->pr.out.p, s->pr.res.p, st);
     PR_TRACE("pair done");
     BWAMS_HIP(hipEventRecord(s->ev[15], st));
+    unsigned long long cnt_pr[kPairCounts] = {};
+    if (count_pr) BWAMS_HIP(hipMemcpyAsync(cnt_pr, s->pr.cnt.p, sizeof cnt_pr, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
+    for (int i = 0; i < kPairCounts; ++i) s->pr.counts[i] = (int64_t)cnt_pr[i];
+    s->pr.counted = count_pr;
     s->pr.total = total;
     s->pr.single = single_end != 0;
     s->pr.done = true;
@@ -370,6 +381,17 @@ int bwams_pair_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, in
     if (reg_off) BWAMS_HIP(hipMemcpyAsync(reg_off, s->pr.ooff.p, (size_t)(s->ch.nseq + 1) * 8, hipMemcpyDeviceToHost, st));
     if (pairs && s->ch.nseq > 1 && !s->pr.single) BWAMS_HIP(hipMemcpyAsync(pairs, s->pr.res.p, (size_t)(s->ch.nseq / 2) * sizeof(bwams_pair_t), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
+    return BWAMS_OK;
+}
+
+/* Test hook: what the last bwams_pair_run counted (include/bwams.h). */
+int bwams_debug_pair_counts(bwams_batch_t *b, int64_t counts[15]) {
+    static_assert(kPairCounts == 15, "include/bwams.h documents 15 counters");
+    if (!b || !counts || !b->stages || !b->stages->pr.done || !b->stages->pr.counted) {
+        set_last_error("bwams_debug_pair_counts: no bwams_pair_run with BWAMS_PAIR_COUNT=1 on this batch");
+        return BWAMS_ERR_ARG;
+    }
+    for (int i = 0; i < kPairCounts; ++i) counts[i] = b->stages->pr.counts[i];
     return BWAMS_OK;
 }
 

@@ -1,5 +1,5 @@
 // api_sam.hip — C-ABI entry points of the SAM side (include/bwams.h): bwams_reg2aln_* (mem_reg2aln, the host's mem_approx_mapq_se),
-// the test hooks bwams_debug_regs_upload and bwams_debug_aln_lists, bwams_index_set_contig_names and _annos, bwams_sam_upload, _run,
+// the test hooks bwams_debug_regs_upload, bwams_debug_pair_regs_upload and bwams_debug_aln_lists, bwams_index_set_contig_names and _annos, bwams_sam_upload, _run,
 // _run_emf, _run_pe, _fetch and _fetch_bgzf, over reg2aln.hip and sam_text.hip.  No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <cmath>
 #include <cstring>
@@ -167,21 +167,23 @@ int bwams_reg2aln_fetch(bwams_batch_t *b, bwams_aln_t *aln, int64_t aln_cap, uin
     return BWAMS_OK;
 }
 
-/* Test hook: caller-given regions take the place of the de-duplication stage's final regions (include/bwams.h).  Only what
- * would make a kernel read outside the reads is refused; the reference side of a region is aln_plan_kernel's to judge. */
-int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
+/* Test hooks: caller-given regions take the place of the de-duplication stage's final regions (include/bwams.h).  Only what
+ * would make a kernel read outside the reads is refused; the reference side of a region is aln_plan_kernel's to judge.  for_pairing:
+ * also what would make a pairing kernel index outside the sequence table or compute on nonsense. */
+static int regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads, bool for_pairing) {
+    const std::string who = for_pairing ? "bwams_debug_pair_regs_upload" : "bwams_debug_regs_upload";
     if (!b || n_regs < 0 || n_reads < 0 || !reg_off || (n_regs && !regs)) return BWAMS_ERR_ARG;
     if (!b->d_cum.p || n_reads != b->nseq) {
-        set_last_error("bwams_debug_regs_upload: n_reads is not the number of reads of the last bwams_seed_upload");
+        set_last_error(who + ": n_reads is not the number of reads of the last bwams_seed_upload");
         return BWAMS_ERR_ARG;
     }
     if (reg_off[0] != 0 || reg_off[n_reads] != n_regs) {
-        set_last_error("bwams_debug_regs_upload: reg_off must run from 0 to n_regs");
+        set_last_error(who + ": reg_off must run from 0 to n_regs");
         return BWAMS_ERR_ARG;
     }
     for (int64_t r = 0; r < n_reads; ++r)
         if (reg_off[r + 1] < reg_off[r]) {
-            set_last_error("bwams_debug_regs_upload: reg_off decreases at read " + std::to_string(r));
+            set_last_error(who + ": reg_off decreases at read " + std::to_string(r));
             return BWAMS_ERR_ARG;
         }
     BWAMS_HIP(hipSetDevice(b->idx->device));
@@ -193,9 +195,24 @@ int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_
         const int64_t len = cum[(size_t)r + 1] - cum[(size_t)r];
         for (int64_t k = reg_off[r]; k < reg_off[r + 1]; ++k)
             if (regs[k].qb < 0 || regs[k].qe > len || regs[k].qb > regs[k].qe) {
-                set_last_error("bwams_debug_regs_upload: region " + std::to_string(k) + " has a query span outside its read");
+                set_last_error(who + ": region " + std::to_string(k) + " has a query span outside its read");
                 return BWAMS_ERR_ARG;
             }
+    }
+    if (for_pairing) {
+        DevBns bns;
+        if (int rc = dev_bns(b->idx, &bns)) return rc;
+        for (int64_t k = 0; k < n_regs; ++k) {
+            const bwams_alnreg_t &a = regs[k];
+            const char *why = nullptr;
+            if (a.rid < 0 || a.rid >= bns.n_seqs) why = " has rid outside [0, number of sequences)";
+            else if (a.rb < 0 || a.re <= a.rb || a.re > 2 * bns.l_pac) why = " has a reference span that is empty or outside the text";
+            else if (a.score < 0) why = " has a negative score";
+            if (why) {
+                set_last_error(who + ": region " + std::to_string(k) + why);
+                return BWAMS_ERR_ARG;
+            }
+        }
     }
     StageState *s;
     int rc = get_state(b, &s);
@@ -207,6 +224,12 @@ int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_
     BWAMS_HIP(hipStreamSynchronize(st));
     s->dd.n_final = n_regs; s->ch.nseq = n_reads; s->dd.done = true;
     return BWAMS_OK;
+}
+int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
+    return regs_upload(b, regs, n_regs, reg_off, n_reads, false);
+}
+int bwams_debug_pair_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
+    return regs_upload(b, regs, n_regs, reg_off, n_reads, true);
 }
 
 /* Test hook: the lengths of the four region lists of the last bwams_reg2aln_run (include/bwams.h). */

@@ -206,7 +206,10 @@ struct PairArgs {
     uint8_t *full;                 // per read: redo with every orientation planned
     int32_t *heavy;                // reads whose list mem_mark_primary_se handles with a wavefront
     DevCounters *ctr;
+    unsigned long long *cnt;       // BWAMS_PAIR_COUNT=1: kPairCounts words (bwams_debug_pair_counts, layout in include/bwams.h) through kernel instances
+                                   // of their own, else nullptr: a production launch holds no counting code
 };
+constexpr int kPairCounts = 15;
 void launch_pair_count(const PairArgs &A, int64_t *wide, hipStream_t st);
 void launch_pair_cap(const PairArgs &A, int64_t *wide, hipStream_t st);
 void launch_pair_slots(const PairArgs &A, hipStream_t st);

@@ -32,6 +32,7 @@ struct Knobs {
     int ext_inplace = 1;           // BWAMS_EXT_INPLACE=0: extension tasks copied into flat buffers
     int dedup_seq = 0;             // BWAMS_DEDUP_SEQ=1: every read through de-duplication's one-lane form
     int dedup_count = 0;           // BWAMS_DEDUP_COUNT=1: de-duplication counts its reads per tier and its patch alignments per variant (tests)
+    int pair_count = 0;            // BWAMS_PAIR_COUNT=1: the pairing stage counts its reads per route and its sorts per path (tests)
     int pair_drop_plan = 0;        // BWAMS_PAIR_DROP_PLAN: exercise mate rescue's second pass
     int trace_pair = 0;            // BWAMS_TRACE_PAIR: a synchronisation and a line per launch of the paired-end tail
     int bsw_pk = 1;                // BWAMS_BSW_PK=0: the 32-bit eight-task banded-SW kernel

@@ -164,6 +164,11 @@ __global__ __launch_bounds__(256) void pair_build_kernel(PairArgs A, const int64
 }
 
 // ---- post: lane per read ------------------------------------------------------------------------------------------
+// PairArgs::cnt (bwams_debug_pair_counts, include/bwams.h).  The kernels that take a list size for a route come in two instances:
+// COUNT = true counts into A.cnt, a production launch runs COUNT = false, which holds no counting code.
+enum { kCntPostLane, kCntPostWave, kCntPostOneLane, kCntPostErt, kCntSortRank, kCntSortNet, kCntSortIntro, kCntInserted, kCntMarkLane,
+       kCntMarkSmall, kCntMarkLarge, kCntMarkOneLane, kCntMarkRank, kCntMarkNet, kCntPostSecond };
+static_assert(kCntPostSecond + 1 == kPairCounts, "include/bwams.h documents the layout");
 // sort_alnreg_re (by_score = 0) / sort_alnreg_score (1) on the list ord[0, n) over pool: ksort.h's introsort
 __device__ void list_sort(const bwams_alnreg_t *pool, int32_t *ord, int n, SortRec *srt, int by_score) {
     if (n < 2) return;
@@ -304,6 +309,7 @@ __device__ int list_mark_primary(const PairArgs &A, bwams_alnreg_t *pool, int32_
 }
 
 // the whole rescue of read m's list by one lane, lists and sort records in HBM
+template <bool COUNT>
 __device__ void post_read_seq(const PairArgs &A, int64_t m) {
     const int64_t l_pac = A.bns.l_pac;
     const int64_t o0 = A.ooff[m];
@@ -379,6 +385,7 @@ __device__ void post_read_seq(const PairArgs &A, int64_t m) {
                         if (resort) list_sort(pool, ord, n + 1, srt, 0);
                     }
                     ++n; ++n_pool;
+                    if (COUNT) atomicAdd(&A.cnt[kCntInserted], 1ull);
                 }
                 ++cnt;
             }
@@ -405,13 +412,18 @@ constexpr int kPostLight = 16;       // pool slots (regions + room for rescued o
 constexpr int kPostLds = 1024;       // pool slots a wavefront keeps in LDS (a power of two: the bitonic sort pads to one)
 constexpr int kPostRankMax = 96;     // longer lists are sorted by the bitonic network, shorter ones by rank
 
+template <bool COUNT>
 __global__ __launch_bounds__(64) void pair_post_kernel(PairArgs A) {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= A.nseq) return;
     if (A.pass == 1 && !A.full[m]) return;                   // second pass: only the flagged reads
     // (the ERT variant of the procedure exists in its one-lane form only)
     if (!A.use_ert && A.ooff[m + 1] - A.ooff[m] > kPostLight) { A.heavy[atomicAdd(&A.ctr->pair_heavy, 1ull)] = (int32_t)m; return; }
-    post_read_seq(A, m);
+    post_read_seq<COUNT>(A, m);
+    if (COUNT) {
+        atomicAdd(&A.cnt[A.use_ert ? kCntPostErt : kCntPostLane], 1ull);
+        if (A.pass == 1) atomicAdd(&A.cnt[kCntPostSecond], 1ull);
+    }
 }
 
 // Long lists: a wavefront per read.  What the procedure reads of a region (rid, rb, re, qb, qe, score) lives in LDS,
@@ -421,6 +433,7 @@ __global__ __launch_bounds__(64) void pair_post_kernel(PairArgs A) {
 // give ksort.h's order whenever no two keys are equal; if a key repeats (identical hits) lane 0 runs the
 // operation-exact introsort instead.  Only the pairwise redundancy pass is sequential (lane 0, LDS).  The pool in
 // HBM is written once per region (the copy, a rescued region, the final n_comp); lanes exchange data through LDS only.
+template <bool COUNT>
 __global__ __launch_bounds__(64) void pair_post_wave_kernel(PairArgs A) {
     __shared__ int64_t l_rb[kPostLds], l_re[kPostLds], l_k64[kPostLds];
     __shared__ int32_t l_qb[kPostLds], l_qe[kPostLds], l_sc[kPostLds], l_rid[kPostLds], l_ncia[kPostLds];
@@ -437,8 +450,16 @@ __global__ __launch_bounds__(64) void pair_post_wave_kernel(PairArgs A) {
         const int64_t o0 = A.ooff[m];
         __syncthreads();
         if (A.ooff[m + 1] - o0 > kPostLds) {                 // beyond the LDS arrays: one lane, through HBM
-            if (lane == 0) post_read_seq(A, m);
+            if (lane == 0) {
+                post_read_seq<COUNT>(A, m);
+                if (COUNT) atomicAdd(&A.cnt[kCntPostOneLane], 1ull);
+                if (COUNT && A.pass == 1) atomicAdd(&A.cnt[kCntPostSecond], 1ull);
+            }
             continue;
+        }
+        if (COUNT && lane == 0) {
+            atomicAdd(&A.cnt[kCntPostWave], 1ull);
+            if (A.pass == 1) atomicAdd(&A.cnt[kCntPostSecond], 1ull);
         }
         bwams_alnreg_t *pool = A.pool + o0;
         SortRec *srt = reinterpret_cast<SortRec *>(A.srt) + o0;
@@ -538,6 +559,10 @@ __global__ __launch_bounds__(64) void pair_post_wave_kernel(PairArgs A) {
                 tie = tie || (__ballot(i < n && eq > 1) != 0);
             }
             __syncthreads();
+            if (COUNT && lane == 0) {
+                atomicAdd(&A.cnt[n > kPostRankMax ? kCntSortNet : kCntSortRank], 1ull);
+                if (tie) atomicAdd(&A.cnt[kCntSortIntro], 1ull);
+            }
             if (!tie) {
                 for (int i = lane; i < n; i += 64) l_ord[i] = l_tmp[i];
             } else {                                         // equal keys: ksort.h's introsort decides their order
@@ -634,6 +659,7 @@ __global__ __launch_bounds__(64) void pair_post_wave_kernel(PairArgs A) {
                         }
                         if (lane == 0) l_ord[at] = sl;
                         ++n; ++n_pool;
+                        if (COUNT && lane == 0) atomicAdd(&A.cnt[kCntInserted], 1ull);
                         __syncthreads();
                     }
                     ++cnt;
@@ -705,6 +731,7 @@ __global__ __launch_bounds__(64) void pair_post_wave_kernel(PairArgs A) {
 constexpr int kMarkLight = 24;       // regions a single lane handles
 constexpr int kMarkLdsMax = 2048, kMarkLdsSmall = 256;       // regions a wavefront keeps in LDS (68 B each): the two instances
 
+template <bool COUNT>
 __global__ __launch_bounds__(64) void pair_mark_kernel(PairArgs A) {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= A.nseq) return;
@@ -713,6 +740,7 @@ __global__ __launch_bounds__(64) void pair_mark_kernel(PairArgs A) {
     const int64_t o0 = A.ooff[m];
     const int64_t id = A.single_end ? A.id_base + m : (((A.id_base + (m >> 1)) << 1) | (m & 1));      // mem_reg2sam passes n_processed + i, mem_sam_pe id << 1 | end
     A.n_pri[m] = list_mark_primary(A, A.pool + o0, A.ord + o0, n, id, reinterpret_cast<SortRec *>(A.srt) + o0, A.zbuf + o0);
+    if (COUNT) atomicAdd(&A.cnt[kCntMarkLane], 1ull);
 }
 
 // The list is long: its two sorts dominate when one lane runs them through HBM.  Both compare keys that cannot tie,
@@ -723,7 +751,7 @@ __global__ __launch_bounds__(64) void pair_mark_kernel(PairArgs A) {
 // long lists, each with its own ticket counter; the largest also takes what is beyond its LDS (one lane, through HBM).
 // One 1024-entry instance kept three waves per CU busy with mostly short lists and sent the longest (> 1024 regions) to
 // a single lane: 11.3 ms for a chunk.
-template <int CAP, int LO>
+template <int CAP, int LO, bool COUNT>
 __global__ __launch_bounds__(64) void pair_mark_wave_kernel(PairArgs A, unsigned long long *ticket) {
     extern __shared__ __align__(16) unsigned char lds_mark[];
     uint64_t *l_hash = reinterpret_cast<uint64_t *>(lds_mark);
@@ -751,7 +779,12 @@ __global__ __launch_bounds__(64) void pair_mark_wave_kernel(PairArgs A, unsigned
         __syncthreads();
         if (n > kMarkLds) {                                  // beyond the LDS arrays: one lane, through HBM
             if (lane == 0) A.n_pri[m] = list_mark_primary(A, pool, ord, n, id, reinterpret_cast<SortRec *>(A.srt) + o0, A.zbuf + o0);
+            if (COUNT && lane == 0) atomicAdd(&A.cnt[kCntMarkOneLane], 1ull);
             continue;
+        }
+        if (COUNT && lane == 0) {
+            atomicAdd(&A.cnt[CAP == kMarkLdsSmall ? kCntMarkSmall : kCntMarkLarge], 1ull);
+            atomicAdd(&A.cnt[n > kPostRankMax ? kCntMarkNet : kCntMarkRank], 1ull);
         }
         int n_pri = 0;
         for (int ib = 0; ib < n; ib += 64) {
@@ -1041,18 +1074,29 @@ void launch_pair_build(const PairArgs &A, const int64_t *offs, bwams_seqpair_t *
     if (blocks > (int64_t)cu_count * 16) blocks = (int64_t)cu_count * 16;
     pair_build_kernel<<<(unsigned)blocks, 256, 0, st>>>(A, offs, pairs, tref, tqer);
 }
+// COUNT: the instances that count into A.cnt (bwams_debug_pair_counts); a production launch runs the ones without any counting code
+template <bool COUNT>
+static void launch_pair_post_t(const PairArgs &A, int cu_count, hipStream_t st) {
+    pair_post_kernel<COUNT><<<blocks_of(A.nseq, 64), 64, 0, st>>>(A);
+    pair_post_wave_kernel<COUNT><<<(unsigned)(cu_count * 2), 64, 0, st>>>(A);
+}
 void launch_pair_post(const PairArgs &A, int cu_count, hipStream_t st) {
     if (A.nseq <= 0) return;
-    pair_post_kernel<<<blocks_of(A.nseq, 64), 64, 0, st>>>(A);
-    pair_post_wave_kernel<<<(unsigned)(cu_count * 2), 64, 0, st>>>(A);
+    if (A.cnt) launch_pair_post_t<true>(A, cu_count, st);
+    else launch_pair_post_t<false>(A, cu_count, st);
+}
+template <bool COUNT>
+static void launch_pair_mark_t(const PairArgs &A, int cu_count, hipStream_t st) {
+    pair_mark_kernel<COUNT><<<blocks_of(A.nseq, 64), 64, 0, st>>>(A);
+    // per launch: the attribute belongs to the current device (a failure here surfaces as the launch error the caller checks)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pair_mark_wave_kernel<kMarkLdsMax, kMarkLdsSmall, COUNT>), hipFuncAttributeMaxDynamicSharedMemorySize, 68 * kMarkLdsMax);
+    pair_mark_wave_kernel<kMarkLdsMax, kMarkLdsSmall, COUNT><<<(unsigned)cu_count, 64, 68 * kMarkLdsMax, st>>>(A, &A.ctr->pair_ticket);
+    pair_mark_wave_kernel<kMarkLdsSmall, kMarkLight, COUNT><<<(unsigned)(cu_count * 8), 64, 68 * kMarkLdsSmall, st>>>(A, &A.ctr->pair_ticket2);
 }
 void launch_pair_mark(const PairArgs &A, int cu_count, hipStream_t st) {
     if (A.nseq <= 0) return;
-    pair_mark_kernel<<<blocks_of(A.nseq, 64), 64, 0, st>>>(A);
-    // per launch: the attribute belongs to the current device (a failure here surfaces as the launch error the caller checks)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pair_mark_wave_kernel<kMarkLdsMax, kMarkLdsSmall>), hipFuncAttributeMaxDynamicSharedMemorySize, 68 * kMarkLdsMax);
-    pair_mark_wave_kernel<kMarkLdsMax, kMarkLdsSmall><<<(unsigned)cu_count, 64, 68 * kMarkLdsMax, st>>>(A, &A.ctr->pair_ticket);
-    pair_mark_wave_kernel<kMarkLdsSmall, kMarkLight><<<(unsigned)(cu_count * 8), 64, 68 * kMarkLdsSmall, st>>>(A, &A.ctr->pair_ticket2);
+    if (A.cnt) launch_pair_mark_t<true>(A, cu_count, st);
+    else launch_pair_mark_t<false>(A, cu_count, st);
 }
 void launch_pair_widen(const PairArgs &A, int64_t *wide, hipStream_t st) {
     pair_widen_kernel<<<blocks_of(A.nseq + 1, 256), 256, 0, st>>>(A, wide);

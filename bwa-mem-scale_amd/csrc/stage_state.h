@@ -53,7 +53,9 @@ struct StageState {
         DevBuf<bwams_alnreg_t> pool, out;
         DevBuf<> srt;                        // 24-byte sort records (pair.hip)
         DevBuf<bwams_pair_t> res;
-        int64_t total = 0, tasks = 0, redone = 0; bool done = false, single = false;
+        DevBuf<unsigned long long> cnt;      // kPairCounts words, written only when a run counts (BWAMS_PAIR_COUNT=1)
+        int64_t counts[kPairCounts] = {};    // ... of the last run
+        int64_t total = 0, tasks = 0, redone = 0; bool done = false, single = false, counted = false;
     } pr;
     struct EmfRegStage {                     // mem_perfect2reg (+ mg_*: its merge into the final regions)
         DevBuf<int64_t> wide, off, ooff, mg_wide, mg_off;

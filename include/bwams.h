@@ -53,6 +53,7 @@ const char *bwams_last_error(void);
  *   BWAMS_DEDUP_SEQ=1, BWAMS_PAIR_DROP_PLAN, BWAMS_TRACE_PAIR   fallback paths forced by tests (tests/test_gpu_dedup_limits.py runs its batches under
  *     BWAMS_DEDUP_SEQ=1 as well); a line per launch of the paired-end tail
  *   BWAMS_DEDUP_COUNT=1   bwams_dedup_run counts its reads per tier and its patch alignments per variant (bwams_debug_dedup_counts)
+ *   BWAMS_PAIR_COUNT=1   bwams_pair_run counts its reads per route and its sorts per path (bwams_debug_pair_counts)
  *   BWAMS_DEPTH_COMBINE=0   the depth add issues one atomic per lane instead of folding equal slots inside a wave (tools/depth_rate.py)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
@@ -665,6 +666,27 @@ int bwams_debug_ext_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, in
  * row in LDS (queries of 256 bases and more), [9] .. [12] the wavefront with the row in registers, queries below 64, 128, 192
  * and 256 bases; [13] how many of [9] .. [12] the early exit ended. */
 int bwams_debug_dedup_counts(bwams_batch_t *b, int64_t counts[14]);
+
+/* Test hook (not part of the drop-in surface): bwams_debug_regs_upload for the pairing stage.  Called after bwams_seed_upload of
+ * the reads; bwams_pair_run, bwams_pair_run_sam (all flags, BWAMS_PAIR_SINGLE_END included) and bwams_pair_fetch then run on
+ * these regions as on real ones.  It does what bwams_debug_regs_upload does and refuses what that hook refuses; additionally it
+ * returns BWAMS_ERR_ARG, launches nothing and leaves the batch as it was when a region has rid outside [0, number of
+ * sequences), not 0 <= rb < re <= 2 l_pac, or score < 0: what would make a pairing kernel (or mem_pair itself) index outside the
+ * sequence table or compute on nonsense. */
+int bwams_debug_pair_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads);
+
+/* Test hook (not part of the drop-in surface): what the last bwams_pair_run / bwams_pair_run_sam on this batch did, when it ran
+ * with BWAMS_PAIR_COUNT=1 (BWAMS_ERR_ARG otherwise; a run without the variable launches kernel instances that hold no counting
+ * code).  Mate rescue, visits of a read's list per route (a read the second pass redoes is visited in both passes and counted in
+ * both; [14] says how many of the visits were the second pass's): counts[0] one lane (pool capacity = regions + 4 per anchor of
+ * the mate, up to 16), [1] a wavefront with the list in LDS (capacity up to 1024), [2] one lane inside the wave kernel (capacity
+ * above 1024), [3] the ERT variant (BWAMS_PAIR_USE_ERT: always one lane).  Sorts of the wave tier [1]: [4] by rank (lists up to
+ * 96), [5] by the bitonic network, [6] how many of [4] + [5] found equal keys and were ended by the operation-exact introsort.
+ * [7] regions inserted by the rescue, over all routes and visits.  mem_mark_primary_se, reads per route by their final region
+ * count: [8] one lane (up to 24), [9] the wave instance for (24, 256], [10] the one for (256, 2048], [11] one lane inside the
+ * latter (more than 2048); lists the wave instances ordered [12] by rank (up to 96), [13] by the network.  A no-rescue or
+ * single-end run still sends every read through [0] .. [3] (nothing to insert), so their sum is the read count of the first pass. */
+int bwams_debug_pair_counts(bwams_batch_t *b, int64_t counts[15]);
 
 /* Test hook (not part of the drop-in surface): how many regions the last bwams_reg2aln_run gave to each of its four
  * dynamic-programming launches.  counts[0]: lane per region with a 32-column ring in LDS; counts[1]: wave per region, bands
