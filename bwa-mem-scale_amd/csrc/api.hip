@@ -35,6 +35,7 @@ void knobs_reload() {
     k.trace_pair = env_int("BWAMS_TRACE_PAIR", 0);
     k.bsw_pk = env_int("BWAMS_BSW_PK", 1);
     k.chain_batch = env_int("BWAMS_CHAIN_BATCH", 1);
+    k.chain_count = env_int("BWAMS_CHAIN_COUNT", 0) == 1;
     k.depth_combine = env_int("BWAMS_DEPTH_COMBINE", 1);
     k.ert_ticket = env_int("BWAMS_ERT_TICKET", 1); k.ert_grid = env_int("BWAMS_ERT_GRID", -1); k.ert_fat = env_int("BWAMS_ERT_FAT", 1);
     g_knobs = k;

@@ -100,6 +100,7 @@ struct SeedView {
 static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedView &sv, int64_t *n_chains, int64_t *n_seeds);
 
 int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_chains, int64_t *n_seeds) {
+    if (b && b->stages) b->stages->ch.ran = false;       // bwams_debug_chain_counts reports the LAST run: a refused one has nothing to report
     if (!b || !b->sd.done || !b->sd.with_sa) {
         set_last_error("bwams_chain_run: run bwams_seed_run(with_sa = 1) first");
         return BWAMS_ERR_ARG;
@@ -115,6 +116,7 @@ int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_cha
 
 int bwams_chain_run_ert(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_ert_mem_t *mems, const int64_t *mem_off,
                         const uint64_t *hits, const int64_t *hit_off, int64_t *n_chains, int64_t *n_seeds) {
+    if (b && b->stages) b->stages->ch.ran = false;
     if (!b || b->nseq <= 0 || !mem_off || !hit_off) {
         set_last_error("bwams_chain_run_ert: upload the reads first (bwams_seed_upload) and pass the MEM / hit offsets");
         return BWAMS_ERR_ARG;
@@ -196,7 +198,15 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
     A.order = s->ch.ovals2.p; A.read_base = s->ch.read_base.p; A.frac_rep = s->ch.frac.p; A.ctr = b->d_ctr.p; A.seed_batch = knobs().chain_batch;
 
     BWAMS_HIP(hipEventRecord(s->ev[0], st));
-    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_redo, 0, 2 * sizeof(unsigned long long), st));
+    // chain_redo, chain_redo_ticket, (pair_heavy, pair_ticket: the pairing stage clears them before it uses them,) dbg[0 .. 19): the filter's
+    // size histogram and cycle counts, the two route counts of the counting instances and the sequential form's count, so that they are
+    // this run's (bwams_debug_chain_counts).  dbg is shared: the seeding stage's diagnostics use dbg[0 .. 19] and de-duplication's dbg[0 .. 19] as
+    // well, each cleared, filled and printed (BWAMS_VERBOSE) within its own run — chaining's filter added to dbg[0 .. 15] on top of whatever they
+    // left before this clear existed; nothing reads another stage's figures after a later stage has run.
+    static_assert(offsetof(DevCounters, dbg) == offsetof(DevCounters, chain_redo) + 4 * sizeof(unsigned long long), "one memset clears chain_redo .. dbg[18]");
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_redo, 0, 23 * sizeof(unsigned long long), st));
+    const bool count_ch = knobs().chain_count != 0;       // tests: reads per filter route, passes of chain_seeds_batch (bwams_debug_chain_counts)
+    if (count_ch) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg + 61, 0, 4 * sizeof(unsigned long long), st));
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_overflow, 0, 29 * sizeof(unsigned long long), st));   // overflow, longread, n_heavy, chain_class[10], chain_ticket[10], heavy_tickets[6]
     // mem_chain_seeds' loop guard `pos < num_smem - 1` (bwamem.cpp:819) makes a work item with exactly
     // one SMEM produce no chain at all
@@ -209,7 +219,7 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
         if ((rc = with_tmp(b, "bwams_chain_run: radix_sort_pairs_desc", [&](void *tmp, size_t &tb) {
                 return rocprim::radix_sort_pairs_desc(tmp, tb, s->ch.okeys.p, s->ch.okeys2.p, s->ch.ovals.p, s->ch.ovals2.p, (size_t)nseq, 0, 32, st);
             }))) return rc;
-        if (launch_chain(A, s->ch.okeys.p, b->cu_count, st, s->aux, s->fork, s->join)) {
+        if (launch_chain(A, s->ch.okeys.p, b->cu_count, st, s->aux, s->fork, s->join, count_ch)) {
             set_last_error("bwams_chain_run: stream fork/join failed");
             return BWAMS_ERR_DEVICE;
         }
@@ -229,22 +239,35 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
         const bool vb = knobs().verbose != 0;
         if (vb) {
             const unsigned long long *d = b->h_ctr.p->dbg;
-            fprintf(stderr, "[bwams_chain_run] filter wave tier: reads by chains <=32 %llu <=64 %llu <=128 %llu <=256 %llu <=512 %llu <=960 %llu more %llu; "
+            fprintf(stderr, "[bwams_chain_run] filter wave tier: reads by chains <=32 %llu <=64 %llu <=128 %llu <=256 %llu <=512 %llu <=960 %llu more %llu (+ %llu taken sequentially by one lane); "
                             "Mcycles: sequential(HBM) %.1f sort %.1f filter %.1f; chains %llu selected %llu; longest read: sort %.2f filter %.2f Mcycles, most chains %llu, most selected %llu\n",
-                    d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7] / 1e6, d[8] / 1e6, d[9] / 1e6, d[11], d[10], d[12] / 1e6, d[13] / 1e6, d[14], d[15]);
+                    d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[18], d[7] / 1e6, d[8] / 1e6, d[9] / 1e6, d[11], d[10], d[12] / 1e6, d[13] / 1e6, d[14], d[15]);
 #ifdef BWAMS_CHAINDBG
             static const char *cn[8] = {"XL", "L", "L2", "L1", "M2", "M", "M1", "S"};
             fprintf(stderr, "[bwams_chain_run] chaining wave tier, per class: reads / mean us / longest us / wave-ms:");
             for (int c = 0; c < 8; ++c) fprintf(stderr, "  %s %llu / %.0f / %.0f / %.1f", cn[c], d[32 + 3 * c], d[32 + 3 * c] ? d[33 + 3 * c] * 1e-2 / d[32 + 3 * c] : 0.0, d[34 + 3 * c] * 1e-2, d[33 + 3 * c] * 1e-5);
             fprintf(stderr, "\n");
-            fprintf(stderr, "[bwams_chain_run] wave tier phases, G cycles: preamble %.2f chaining %.2f weights+copy %.2f (sort %.2f filter %.2f: all reads); reads %llu seeds %llu; passes %llu settling %llu seeds (%llu new chains), %llu seeds one by one; pass parts, G cycles: batch prologue %.2f search %.2f record+test %.2f settle %.2f commit %.2f one-by-one %.2f\n",
-                    d[56] / 1e9, d[57] / 1e9, d[58] / 1e9, d[8] / 1e9, d[9] / 1e9, d[59], d[60], d[61], d[63], d[64], d[62], d[65] / 1e9, d[66] / 1e9, d[67] / 1e9, d[68] / 1e9, d[69] / 1e9, d[70] / 1e9);
+            fprintf(stderr, "[bwams_chain_run] wave tier phases, G cycles: preamble %.2f chaining %.2f weights+copy %.2f (sort %.2f filter %.2f: all reads); reads %llu seeds %llu; passes %llu settling %llu seeds (%llu new chains), %llu seeds one by one%s; pass parts, G cycles: batch prologue %.2f search %.2f record+test %.2f settle %.2f commit %.2f one-by-one %.2f\n",
+                    d[56] / 1e9, d[57] / 1e9, d[58] / 1e9, d[8] / 1e9, d[9] / 1e9, d[59], d[60], count_ch ? d[61] : 0ull, count_ch ? d[63] : 0ull,
+                    count_ch ? d[64] : 0ull, count_ch ? d[62] : 0ull, count_ch ? "" : " (these four are counted under BWAMS_CHAIN_COUNT=1 only)", d[65] / 1e9, d[66] / 1e9, d[67] / 1e9, d[68] / 1e9, d[69] / 1e9, d[70] / 1e9);
 #endif
         }
     }
     if (b->h_ctr.p->chain_overflow) {
         set_last_error("bwams_chain_run: internal B-tree node region exhausted");
         return BWAMS_ERR_CAPACITY;
+    }
+    {
+        const DevCounters *h = b->h_ctr.p;
+        int64_t *c = s->ch.counts;
+        for (int i = 0; i < 10; ++i) c[i] = (int64_t)h->chain_class[i];
+        c[10] = (int64_t)h->n_heavy; c[11] = (int64_t)h->chain_redo;
+        for (int i = 0; i < 7; ++i) c[12 + i] = (int64_t)h->dbg[i];
+        c[19] = (int64_t)h->dbg[18];
+        c[20] = count_ch ? (int64_t)h->dbg[16] : -1; c[21] = count_ch ? (int64_t)h->dbg[17] : -1;
+        c[22] = count_ch ? (int64_t)h->dbg[61] : -1; c[23] = count_ch ? (int64_t)h->dbg[63] : -1;
+        c[24] = count_ch ? (int64_t)h->dbg[64] : -1; c[25] = count_ch ? (int64_t)h->dbg[62] : -1;
+        s->ch.ran = true;
     }
     const bool has_long = b->h_ctr.p->chain_longread != 0;
     s->ch.n_redo = (int64_t)b->h_ctr.p->chain_redo;
@@ -275,6 +298,17 @@ int bwams_chain_fetch(bwams_batch_t *b, bwams_chain_t *chains, int64_t chain_cap
     if (s->ch.n_seeds) BWAMS_HIP(hipMemcpyAsync(seeds, s->ch.seeds.p, (size_t)s->ch.n_seeds * sizeof(bwams_chain_seed_t), hipMemcpyDeviceToHost, st));
     if (chain_off) BWAMS_HIP(hipMemcpyAsync(chain_off, s->ch.chain_off.p, (size_t)(s->ch.nseq + 1) * 8, hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
+    return BWAMS_OK;
+}
+
+/* Test hook: routes and passes of the last chaining run (include/bwams.h). */
+int bwams_debug_chain_counts(bwams_batch_t *b, int64_t counts[26]) {
+    static_assert(kChainCounts == 26, "include/bwams.h documents 26 counters");
+    if (!b || !counts || !b->stages || !b->stages->ch.done || !b->stages->ch.ran) {
+        set_last_error("bwams_debug_chain_counts: no bwams_chain_run / bwams_chain_run_ert on this batch");
+        return BWAMS_ERR_ARG;
+    }
+    for (int i = 0; i < kChainCounts; ++i) counts[i] = b->stages->ch.counts[i];
     return BWAMS_OK;
 }
 
@@ -322,7 +356,7 @@ int bwams_chain_upload(bwams_batch_t *b, const bwams_chain_t *chains, int64_t n_
     BWAMS_HIP(hipStreamSynchronize(st));
     delete[] soff;
     s->ch.n_chains = n_chains; s->ch.n_seeds = n_seeds; s->ch.nseq = nseq;
-    s->ch.done = true;
+    s->ch.done = true; s->ch.ran = false;
     return BWAMS_OK;
 }
 }  // extern "C"

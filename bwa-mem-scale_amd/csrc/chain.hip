@@ -432,6 +432,7 @@ __device__ __forceinline__ uint4 make_rec(const ChainArgs &A, const ChainRec &c,
     return make_uint4((uint32_t)c.first_qbeg, (uint32_t)(c.last_qbeg + c.last_len), w | alt, 0xffffffffu);
 }
 
+#ifndef BWAMS_CHAIN_COUNT_TU            // (chain_count.hip compiles this file for its counting instances only: see launch_chain)
 // ---- the chaining kernel: one lane per read --------------------------------------------------
 // lane per read: the read's slice of the sorted SMEM array and its seed count (the sort key that
 // groups reads of similar cost into the same wave)
@@ -465,6 +466,8 @@ __global__ void chain_count_kernel(ChainArgs A, uint32_t *keys, uint32_t *vals) 
         if (m && (threadIdx.x & 63) == 0) atomicAdd(&A.ctr->chain_class[c], (unsigned long long)__popcll(m));
     }
 }
+
+#endif
 
 // Chain one read.  `nl` lanes run this function in lockstep on the same read: 1 (a lane per read) or
 // 64 (a wave per read: every load is wave-uniform, i.e. one request; lane 0 performs the stores).
@@ -587,6 +590,8 @@ __device__ __forceinline__ bool chain_seed_one(const ChainArgs &A, const SeedCtx
     return true;
 }
 // the read's seeds [0, cnt), 64 per pass across its SMEMs sm[beg .. end); all 64 lanes call this.  Returns false when the read needs the B-tree.
+// COUNT: passes, seeds settled by passes, chains started by passes and seeds taken one by one go to ctr->dbg[61 .. 64] (bwams_debug_chain_counts)
+template <bool COUNT>
 __device__ bool chain_seeds_batch(const ChainArgs &A, const SeedCtx &S, int &n_keys, const bwams_smem_t *sm, int64_t beg, int64_t end, int64_t base,
                                   int32_t cnt, RidCache &rc, const WaveBns &wb, int lane) {
     enum { NONE = 0, NOOP = 1, MERGE = 2, NEW = 3, UNSETTLED = 4 };
@@ -652,9 +657,7 @@ __device__ bool chain_seeds_batch(const ChainArgs &A, const SeedCtx &S, int &n_k
                 if (!chain_seed_one(A, S, n_keys, gb + l0, readlane64(rbeg, l0), __builtin_amdgcn_readlane(rid, l0), __builtin_amdgcn_readlane(qbeg, l0),
                                     __builtin_amdgcn_readlane(slen, l0), lane)) return false;
                 if (lane == l0) pend = false;
-#ifdef BWAMS_CHAINDBG
-                if (lane == 0) atomicAdd(&A.ctr->dbg[62], 1ull);
-#endif
+                if constexpr (COUNT) { if (lane == 0) atomicAdd(&A.ctr->dbg[62], 1ull); }
                 --one_by_one;
                 TQ(5)
                 continue;
@@ -788,9 +791,10 @@ __device__ bool chain_seeds_batch(const ChainArgs &A, const SeedCtx &S, int &n_k
                 n_keys = n + m;
             }
             if (com) pend = false;
-#ifdef BWAMS_CHAINDBG
-            if (lane == 0) { atomicAdd(&A.ctr->dbg[61], 1ull); atomicAdd(&A.ctr->dbg[63], (unsigned long long)__popcll(__ballot(com))); atomicAdd(&A.ctr->dbg[64], (unsigned long long)__popcll(m_new)); }
-#endif
+            if constexpr (COUNT) {
+                const unsigned long long n_com = (unsigned long long)__popcll(__ballot(com));
+                if (lane == 0) { atomicAdd(&A.ctr->dbg[61], 1ull); atomicAdd(&A.ctr->dbg[63], n_com); atomicAdd(&A.ctr->dbg[64], (unsigned long long)__popcll(m_new)); }
+            }
             if (__popcll(__ballot(com)) <= 1) one_by_one = 8;
             if (S.crec_hbm) __threadfence_block();                            // the chain records of class XL are read back through L2
             TQ(4)
@@ -805,7 +809,9 @@ __device__ bool chain_seeds_batch(const ChainArgs &A, const SeedCtx &S, int &n_k
 __device__ void heavy_read(const ChainArgs &A, int64_t r, int64_t base, int n_chn, unsigned char *lds, int cap, int lane);
 __host__ __device__ constexpr size_t heavy_lds_bytes(int cap);
 // CONT = 0: kbtree (exact for any input); CONT = 1: sorted array, returns false when the read needs the B-tree
-template <bool LDS, int CONT = 0, bool CREC_HBM = false>
+// COUNT (BWAMS_CHAIN_COUNT=1, bwams_debug_chain_counts): the reads whose sort and filter run in the chaining wave's LDS go to ctr->dbg[16],
+// the reads a lane sorts and filters sequentially to ctr->dbg[17]; a launch without the variable runs the instances that hold no such code
+template <bool LDS, int CONT = 0, bool CREC_HBM = false, bool COUNT = false>
 __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int lane, int nl, Node *nodes, int32_t cap_nodes,
                                            ChainRec *crec_w, int32_t cap_chains) {
     const bool wr = lane == 0;
@@ -889,7 +895,7 @@ __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int la
             SeedCtx S;
             S.pos = pos; S.s_next = s_next; S.s_ql = s_ql; S.crec = crec; S.s_key = s_key; S.s_cid = s_cid; S.crec_hbm = CREC_HBM;
             int nk = 0;
-            if (!chain_seeds_batch(A, S, nk, sm, beg, end, base, cnt, rc, wb, lane)) return false;
+            if (!chain_seeds_batch<COUNT>(A, S, nk, sm, beg, end, base, cnt, rc, wb, lane)) return false;
             c.n_keys = nk;
         }
     }
@@ -1033,6 +1039,7 @@ __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int la
             if (cap_f >= 64 && n_chn <= cap_f) {
                 if (wr) A.n_chn[r] = n_chn;
                 __threadfence_block();          // crec_g, fl: written above by other lanes
+                if constexpr (COUNT) { if (wr) atomicAdd(&A.ctr->dbg[16], 1ull); }
                 heavy_read(A, r, base, n_chn, region, cap_f, lane);
                 return true;
             }
@@ -1045,6 +1052,7 @@ __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int la
         A.heavy[slot] = (int32_t)r;
         return true;
     }
+    if constexpr (COUNT) atomicAdd(&A.ctr->dbg[17], 1ull);
     ks_introsort(fl, n_chn, FltLt());
     uint4 *rec = A.f_rec + base;
     int32_t *kept = A.f_kept + base;
@@ -1059,16 +1067,18 @@ __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int la
 }
 
 // reads with few seeds: one lane per read, state in HBM scratch
+template <bool COUNT>
 __global__ __launch_bounds__(64) void chain_kernel(ChainArgs A, const uint32_t *__restrict__ n_seeds) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= A.nseq) return;
     if (n_seeds[r] > (uint32_t)kLaneSeeds) return;          // a wave kernel's
-    chain_read<false>(A, r, 0, 1, nullptr, 0, nullptr, 0);
+    chain_read<false, 0, false, COUNT>(A, r, 0, 1, nullptr, 0, nullptr, 0);
 }
 
 // reads with many seeds: one wave (= one block) per read, B-tree and chain records in LDS.  The reads
 // order[lo .. hi) (sorted by descending seed count, so a size class is a range) are handed out by ticket.
 // K = 0: no LDS (reads too large for a CU's LDS): state in HBM scratch.
+template <bool COUNT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void chain_wave_kernel(ChainArgs A, const unsigned long long *lo_p, const unsigned long long *hi_p,
                                                         unsigned long long *ticket, int K) {
     extern __shared__ __align__(16) unsigned char l_mem[];
@@ -1084,12 +1094,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         const unsigned long long tk0 = wall_clock64();
 #endif
         if (K < 0) {                 // class XL: ordered array of -K chains in LDS, chain records in HBM
-            if (!chain_read<true, 1, true>(A, r, lane, 64, reinterpret_cast<Node *>(l_mem), 0, nullptr, -K) && lane == 0)
+            if (!chain_read<true, 1, true, COUNT>(A, r, lane, 64, reinterpret_cast<Node *>(l_mem), 0, nullptr, -K) && lane == 0)
                 A.redo[atomicAdd(&A.ctr->chain_redo, 1ull)] = (int32_t)r;
         } else if (K) {
-            if (!chain_read<true, 1>(A, r, lane, 64, l_nodes, 0, l_crec, K) && lane == 0)
+            if (!chain_read<true, 1, false, COUNT>(A, r, lane, 64, l_nodes, 0, l_crec, K) && lane == 0)
                 A.redo[atomicAdd(&A.ctr->chain_redo, 1ull)] = (int32_t)r;
-        } else chain_read<false>(A, r, lane, 64, nullptr, 0, nullptr, 0);
+        } else chain_read<false, 0, false, COUNT>(A, r, lane, 64, nullptr, 0, nullptr, 0);
         __syncthreads();
 #ifdef BWAMS_CHAINDBG
         if (lane == 0) {
@@ -1102,13 +1112,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 }
 
 // reads whose chain positions repeat: again, with the B-tree (state in HBM scratch, wave per read)
+template <bool COUNT>
 __global__ __launch_bounds__(64) void chain_redo_kernel(ChainArgs A) {
     const int lane = threadIdx.x;
     const int64_t n = (int64_t)A.ctr->chain_redo;
     for (;;) {
         const int64_t t = (int64_t)wave_ticket(&A.ctr->chain_redo_ticket, 1ull);
         if (t >= n) break;
-        chain_read<false>(A, A.redo[t], lane, 64, nullptr, 0, nullptr, 0);
+        chain_read<false, 0, false, COUNT>(A, A.redo[t], lane, 64, nullptr, 0, nullptr, 0);
     }
 }
 
@@ -1303,7 +1314,7 @@ __global__ __launch_bounds__(64) void chain_heavy_kernel(ChainArgs A, const unsi
         if (n_chn > kLdsChains) {              // beyond the LDS budget: the sequential form, on lane 0
             const unsigned long long t_0 = __builtin_amdgcn_s_memtime();
             if (lane == 0) {
-                atomicAdd(&A.ctr->dbg[6], 1ull);
+                atomicAdd(&A.ctr->dbg[18], 1ull);            // a slot of its own: dbg[6] is heavy_read's bin for more than 960 chains
                 ks_introsort(fl, n_chn, FltLt());
                 for (int i = 0; i < n_chn; ++i) { rec[i] = make_rec(A, crec[fl[i].y], fl[i].x); kept[i] = 0; }
                 filter_seq(A.opt, n_chn, rec, kept, A.f_sel + base);
@@ -1316,6 +1327,7 @@ __global__ __launch_bounds__(64) void chain_heavy_kernel(ChainArgs A, const unsi
     }
 }
 
+#ifndef BWAMS_CHAIN_COUNT_TU
 // flat chain and seed records.  Sixteen lanes per read, a lane per kept chain (sixteen chains a trip): the chains' seed offsets are a
 // prefix sum of their seed counts inside the group, and every lane walks its own chain's seed list — a lane per read took the chains
 // one after the other, three dependent loads each before the first seed (1.8 ms per million reads; 4.4 on the grch38_like genome)
@@ -1401,8 +1413,11 @@ __global__ __launch_bounds__(64) void flt_sort_test_kernel(const uint2 *__restri
     for (int i = lane; i < n; i += 64) order[i] = (int32_t)l_a[i].y;
 }
 
+#endif
+
 }  // namespace
 
+#ifndef BWAMS_CHAIN_COUNT_TU
 size_t chain_node_bytes(int64_t n_sa, int64_t nseq) { return (size_t)((n_sa >> 1) + 2 * nseq + 4) * sizeof(Node); }
 size_t chain_rec_bytes(int64_t n_sa) { return (size_t)(n_sa > 0 ? n_sa : 1) * sizeof(ChainRec); }
 
@@ -1412,15 +1427,22 @@ void launch_chain_count(const ChainArgs &A, uint32_t *keys, uint32_t *vals, hipS
     if (A.n_smem > 0) chain_slice_kernel<<<(unsigned)((A.n_smem + 255) / 256), 256, 0, st>>>(A);
     chain_count_kernel<<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A, keys, vals);
 }
+#endif
 // The tiers are independent of each other: they run concurrently on the auxiliary streams (forked from
 // and joined back into the batch's stream), the filter of the many-chain reads after all of them.
-int launch_chain(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux,
-                 hipEvent_t fork, hipEvent_t *join) {
+// COUNT: the instances that count into ctr->dbg (bwams_debug_chain_counts); a production launch runs the ones without any counting code.
+// The counting instances are compiled in a translation unit of their own (chain_count.hip: this file again, under BWAMS_CHAIN_COUNT_TU):
+// beside them in ONE code object the compiler allocated the registers of chain_wave_kernel<false> and of the out-of-line heavy_read
+// differently, and the chain stage measured 0.2 ms per million reads slower than the parent's; alone, this object's kernels are the
+// parent's instruction for instruction.  chain_heavy_kernel has nothing conditional to count: the counting launch runs its own copy.
+template <bool COUNT>
+static int launch_chain_t(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux,
+                          hipEvent_t fork, hipEvent_t *join) {
     if (A.nseq <= 0) return 0;
     unsigned long long *cls = A.ctr->chain_class, *tk = A.ctr->chain_ticket;
     // the opt-in for more than 64 KB of dynamic LDS belongs to the CURRENT device: set per launch (a batch on a second GPU of the
     // process needs it too), and checked
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(chain_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(chain_wave_kernel<COUNT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_bytes_xl(kClassXL2)) != hipSuccess) return -1;
     if (hipEventRecord(fork, st) != hipSuccess) return -1;
     for (int i = 0; i < 7; ++i)
@@ -1433,26 +1455,26 @@ int launch_chain(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipS
     // class XL2 wants a whole CU's LDS per read: on the batch's own stream, which does not wait for the fork event, so that its blocks
     // are placed before the other classes' have filled every CU (behind them they found no CU free until the others drained: 42 ms on
     // the grch38_like genome for reads of ~2 ms each); blocks without a read leave at once
-    chain_wave_kernel<<<(unsigned)cu_count, 64, lds_bytes_xl(kClassXL2), st>>>(A, cls + 9, cls + 6, tk + 9, -kClassXL2);
-    chain_wave_kernel<<<(unsigned)(cu_count * 8), 64, 0, aux[0]>>>(A, nullptr, cls + 9, tk + 0, 0);
-    chain_wave_kernel<<<(unsigned)cu_count, 64, lds_bytes_xl(kClassXL), aux[0]>>>(A, cls + 6, cls + 0, tk + 6, -kClassXL);
-    chain_wave_kernel<<<(unsigned)cu_count, 64, lds_bytes(kClassL), aux[1]>>>(A, cls + 0, cls + 7, tk + 1, kClassL);
-    chain_wave_kernel<<<(unsigned)(cu_count * 2), 64, lds_bytes(kClassL2), aux[5]>>>(A, cls + 7, cls + 1, tk + 7, kClassL2);
-    chain_wave_kernel<<<(unsigned)(cu_count * 3), 64, lds_bytes(kClassL1), aux[2]>>>(A, cls + 1, cls + 8, tk + 2, kClassL1);
-    chain_wave_kernel<<<(unsigned)(cu_count * 4), 64, lds_bytes(kClassM2), aux[6]>>>(A, cls + 8, cls + 2, tk + 8, kClassM2);
-    chain_wave_kernel<<<(unsigned)(cu_count * 8), 64, lds_bytes(kClassM1), aux[2]>>>(A, cls + 3, cls + 4, tk + 4, kClassM1);
-    chain_wave_kernel<<<(unsigned)(cu_count * 12), 64, lds_bytes(kClassS), aux[3]>>>(A, cls + 4, cls + 5, tk + 5, kClassS);
+    chain_wave_kernel<COUNT><<<(unsigned)cu_count, 64, lds_bytes_xl(kClassXL2), st>>>(A, cls + 9, cls + 6, tk + 9, -kClassXL2);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 8), 64, 0, aux[0]>>>(A, nullptr, cls + 9, tk + 0, 0);
+    chain_wave_kernel<COUNT><<<(unsigned)cu_count, 64, lds_bytes_xl(kClassXL), aux[0]>>>(A, cls + 6, cls + 0, tk + 6, -kClassXL);
+    chain_wave_kernel<COUNT><<<(unsigned)cu_count, 64, lds_bytes(kClassL), aux[1]>>>(A, cls + 0, cls + 7, tk + 1, kClassL);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 2), 64, lds_bytes(kClassL2), aux[5]>>>(A, cls + 7, cls + 1, tk + 7, kClassL2);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 3), 64, lds_bytes(kClassL1), aux[2]>>>(A, cls + 1, cls + 8, tk + 2, kClassL1);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 4), 64, lds_bytes(kClassM2), aux[6]>>>(A, cls + 8, cls + 2, tk + 8, kClassM2);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 8), 64, lds_bytes(kClassM1), aux[2]>>>(A, cls + 3, cls + 4, tk + 4, kClassM1);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 12), 64, lds_bytes(kClassS), aux[3]>>>(A, cls + 4, cls + 5, tk + 5, kClassS);
     // (the lane tier on the batch's own stream behind class XL2 instead: 19.1 -> 20.3 ms on the uniform genome, 50 -> 54 on grch38_like)
-    chain_kernel<<<(unsigned)((A.nseq + 63) / 64), 64, 0, aux[1]>>>(A, n_seeds);
+    chain_kernel<COUNT><<<(unsigned)((A.nseq + 63) / 64), 64, 0, aux[1]>>>(A, n_seeds);
     // class M behind the lane tier (5 ms) rather than behind class L or S (kernel trace at GRCh38 size: L 8.9-10.3 ms + M 4.3-6.7 was
     // the stage's longest stream; S 7.8, L1 7.7 + M1 2.9, XL 0.9 + 7.2)
     // (round 4: on the stream of class L, the shortest; aux[4] shares a hardware queue with class S's stream, 16 ms on a repeat-rich genome)
-    chain_wave_kernel<<<(unsigned)(cu_count * 5), 64, lds_bytes(kClassM), aux[5]>>>(A, cls + 2, cls + 3, tk + 3, kClassM);
+    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 5), 64, lds_bytes(kClassM), aux[5]>>>(A, cls + 2, cls + 3, tk + 3, kClassM);
     for (int i = 0; i < 7; ++i) {
         if (hipEventRecord(join[i], aux[i]) != hipSuccess) return -1;
         if (hipStreamWaitEvent(st, join[i], 0) != hipSuccess) return -1;
     }
-    chain_redo_kernel<<<(unsigned)(cu_count * 2), 64, 0, st>>>(A);
+    chain_redo_kernel<COUNT><<<(unsigned)(cu_count * 2), 64, 0, st>>>(A);
     // the filter of the many-chain reads: three size classes, concurrently, the class of the longest reads first
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(chain_heavy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)heavy_lds_bytes(kHeavyCap[5])) != hipSuccess) return -1;
@@ -1478,6 +1500,16 @@ int launch_chain(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipS
     }
     return 0;
 }
+#ifdef BWAMS_CHAIN_COUNT_TU
+int launch_chain_counting(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join) {
+    return launch_chain_t<true>(A, n_seeds, cu_count, st, aux, fork, join);
+}
+#else
+int launch_chain_counting(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join);
+int launch_chain(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux,
+                 hipEvent_t fork, hipEvent_t *join, bool count) {
+    return count ? launch_chain_counting(A, n_seeds, cu_count, st, aux, fork, join) : launch_chain_t<false>(A, n_seeds, cu_count, st, aux, fork, join);
+}
 void launch_chain_emit(const ChainArgs &A, const int64_t *chain_off, const int64_t *seed_off, bwams_chain_t *chains,
                        bwams_chain_seed_t *seeds, hipStream_t st) {
     if (A.nseq <= 0) return;
@@ -1496,5 +1528,6 @@ int launch_flt_sort_test(const int64_t *w, int n, int mode, int32_t *order) {
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(order, d_ord.p, 4 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
 }
+#endif
 
 }  // namespace bwams

@@ -21,6 +21,8 @@ struct StageState {
         DevBuf<bwams_smem_t> et_smem;
         DevBuf<> et_srt;                     // 24-byte sort records (ert_chain.hip)
         int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_redo = 0; bool done = false;
+        int64_t counts[kChainCounts] = {};   // bwams_debug_chain_counts: of the last bwams_chain_run / _run_ert
+        bool ran = false;                    // ... there was one (bwams_chain_upload clears it)
     } ch;
     struct ExtStage {                        // chain -> alignment regions
         DevBuf<bwams_alnreg_t> regs; DevBuf<uint32_t> srt; DevBuf<int32_t> state, cur, lim;

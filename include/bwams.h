@@ -54,6 +54,7 @@ const char *bwams_last_error(void);
  *     BWAMS_DEDUP_SEQ=1 as well); a line per launch of the paired-end tail
  *   BWAMS_DEDUP_COUNT=1   bwams_dedup_run counts its reads per tier and its patch alignments per variant (bwams_debug_dedup_counts)
  *   BWAMS_PAIR_COUNT=1   bwams_pair_run counts its reads per route and its sorts per path (bwams_debug_pair_counts)
+ *   BWAMS_CHAIN_COUNT=1   bwams_chain_run / _run_ert count their reads per filter route and the passes of the wave tier (bwams_debug_chain_counts)
  *   BWAMS_DEPTH_COMBINE=0   the depth add issues one atomic per lane instead of folding equal slots inside a wave (tools/depth_rate.py)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
@@ -674,6 +675,20 @@ int bwams_debug_dedup_counts(bwams_batch_t *b, int64_t counts[14]);
  * sequences), not 0 <= rb < re <= 2 l_pac, or score < 0: what would make a pairing kernel (or mem_pair itself) index outside the
  * sequence table or compute on nonsense. */
 int bwams_debug_pair_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads);
+
+/* Test hook (not part of the drop-in surface): the routes the last bwams_chain_run / bwams_chain_run_ert on this batch sent its
+ * reads through (BWAMS_ERR_ARG when there was none, or bwams_chain_upload came after it).  Always: counts[0 .. 9] reads with more
+ * seeds than the limits of class L (1700), L1 (850), M (512), M1 (256), S (128), of the lane tier (32), of class XL (4096), L2
+ * (1275), M2 (665) and XL2 (13000) — seeds as chaining sees them, after the max_occ pick, skipped ones included; all ten stay 0
+ * in a 256-read block without a read beyond the lane tier; [10] reads handed to the many-chain filter kernel; [11] reads the
+ * ordered-array attempt gave up on (a chain position repeated: chained again with the B-tree); [12 .. 18] reads sorted and
+ * filtered by a whole wavefront, by chains at or above min_chain_weight: up to 32, 64, 128, 256, 512, 960, more; [19] reads
+ * beyond 3840 chains, which one lane of the filter kernel sorts and filters sequentially (not in [12 .. 18]).  Only when the run
+ * had BWAMS_CHAIN_COUNT=1 (-1 otherwise: a run without the variable launches kernel instances that hold no counting code): [20]
+ * reads whose sort and filter ran in the chaining wave's own LDS (part of [12 .. 18]); [21] reads one lane sorted and filtered
+ * sequentially at the end of chaining (at most 16 chains); the wave tier's 64-seed passes: [22] passes, [23] seeds they
+ * settled, [24] chains they started, [25] seeds taken one at a time instead.  A refused run leaves nothing to report. */
+int bwams_debug_chain_counts(bwams_batch_t *b, int64_t counts[26]);
 
 /* Test hook (not part of the drop-in surface): what the last bwams_pair_run / bwams_pair_run_sam on this batch did, when it ran
  * with BWAMS_PAIR_COUNT=1 (BWAMS_ERR_ARG otherwise; a run without the variable launches kernel instances that hold no counting

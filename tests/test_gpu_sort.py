@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from bwams import capi
+from chain_cases import antiquicksort as _antiquicksort      # the adversary against ksort.h's introsort, shared with the chaining cases
 from oracle import loader
 from util import toy
 
@@ -90,91 +91,6 @@ def test_chain_filter_sort_equals_ksort(ix):
             assert np.array_equal(got, want), (len(w), mode, w[:12], got[:12], want[:12])
         n_tied += len(w) > len(np.unique(w))
     assert n_tied > 100
-
-
-def _ks_introsort_trace(n, lt):
-    """ksort.h's introsort (src/ksort.h: ks_introsort) over the indices 0..n-1 with a caller-supplied `lt(i, j)` on ELEMENT ids;
-    returns True when the depth limit sent a range to the comb-sort fallback.  Used only to BUILD an adversarial input."""
-    a = list(range(n))
-    hit = [False]
-    if n < 1:
-        return False
-    if n == 2:
-        return False
-    d = 2
-    while (1 << d) < n:
-        d += 1
-    d <<= 1
-    stack, s, t = [], 0, n - 1
-    while True:
-        if s < t:
-            d -= 1
-            if d == 0:
-                hit[0] = True
-                t = s
-                continue
-            i, j = s, t
-            k = i + ((j - i) >> 1) + 1
-            if lt(a[k], a[i]):
-                if lt(a[k], a[j]):
-                    k = j
-            else:
-                k = i if lt(a[j], a[i]) else j
-            rp = a[k]
-            if k != t:
-                a[k], a[t] = a[t], a[k]
-            while True:
-                i += 1
-                while lt(a[i], rp):
-                    i += 1
-                j -= 1
-                while i <= j and lt(rp, a[j]):
-                    j -= 1
-                if j <= i:
-                    break
-                a[i], a[j] = a[j], a[i]
-            a[i], a[t] = a[t], a[i]
-            if i - s > t - i:
-                if i - s > 16:
-                    stack.append((s, i - 1, d))
-                s = i + 1 if t - i > 16 else t
-            else:
-                if t - i > 16:
-                    stack.append((i + 1, t, d))
-                t = i - 1 if i - s > 16 else s
-        else:
-            if not stack:
-                return hit[0]
-            s, t, d = stack.pop()
-
-
-def _antiquicksort(n):
-    """McIlroy's adversary ("A killer adversary for quicksort", 1999) against the introsort above: values are fixed only when
-    a comparison needs them, so that every pivot turns out to be among the smallest of its range.  -> keys (a permutation)."""
-    GAS = n
-    val = [GAS] * n
-    state = {"nsolid": 0, "cand": 0}
-
-    def lt(x, y):
-        if val[x] == GAS and val[y] == GAS:
-            if x == state["cand"]:
-                val[x] = state["nsolid"]
-            else:
-                val[y] = state["nsolid"]
-            state["nsolid"] += 1
-        if val[x] == GAS:
-            state["cand"] = x
-        elif val[y] == GAS:
-            state["cand"] = y
-        return val[x] < val[y]
-
-    hit = _ks_introsort_trace(n, lt)
-    rest = state["nsolid"]
-    for i in range(n):
-        if val[i] == GAS:
-            val[i] = rest
-            rest += 1
-    return np.array(val, np.int64), hit
 
 
 def test_depth_limit_fallback(ix):
