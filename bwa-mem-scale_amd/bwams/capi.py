@@ -62,6 +62,8 @@ SYMBOLS = [
     "bwams_depth_open", "bwams_depth_close", "bwams_depth_reset", "bwams_depth_add_batch", "bwams_depth_add_records", "bwams_depth_finish",
     "bwams_depth_summary", "bwams_depth_hist", "bwams_depth_windows", "bwams_depth_runs", "bwams_depth_fetch", "bwams_depth_text",
     "bwams_sorter_set_depth",
+    "bwams_pileup_open", "bwams_pileup_close", "bwams_pileup_reset", "bwams_pileup_add_batch", "bwams_pileup_add_records", "bwams_pileup_set_ref",
+    "bwams_pileup_set_ref_index", "bwams_pileup_fetch", "bwams_pileup_sites", "bwams_pileup_text", "bwams_pileup_info", "bwams_sorter_set_pileup",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -99,6 +101,10 @@ DUP_LIB_STATS_DTYPE = np.dtype([(n, "<i8") for n in ("unpaired_examined", "pairs
                                                      "estimated_library_size")] + [("percent_duplication", "<f8")])   # bwams_dup_lib_stats_t
 DEPTH_REF_DTYPE = np.dtype([("length", "<i8"), ("bases", "<i8"), ("min", "<i4"), ("max", "<i4")])         # bwams_depth_ref_t
 assert DEPTH_REF_DTYPE.itemsize == 24
+PILEUP_REGION_DTYPE = np.dtype([("ref", "<i4"), ("beg", "<i4"), ("end", "<i4")])                          # bwams_pileup_region_t
+PILEUP_SITE_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("kinds", "<u4"), ("depth", "<u4"),
+                              ("c", "<u4", (12,))])                                                      # bwams_pileup_site_t
+assert PILEUP_REGION_DTYPE.itemsize == 12 and PILEUP_SITE_DTYPE.itemsize == 68
 assert DUP_LOC_DTYPE.itemsize == 24 and DUP_LIB_STATS_DTYPE.itemsize == 72
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
@@ -475,6 +481,10 @@ class Sorter:
         """bwams_sorter_set_depth: close adds the merged stream, as written, to the handle; before the first put."""
         _chk(lib().bwams_sorter_set_depth(self.h, depth.h), "bwams_sorter_set_depth")
 
+    def set_pileup(self, pileup: "Pileup") -> None:
+        """bwams_sorter_set_pileup: close adds the merged stream, as written, to the handle; before the first put."""
+        _chk(lib().bwams_sorter_set_pileup(self.h, pileup.h), "bwams_sorter_set_pileup")
+
     def close3(self) -> SorterStats:
         """bwams_sorter_close3: close()'s stats, .dup, and rule 13's rows as .lib (DUP_LIB_STATS_DTYPE)."""
         st, dup = SorterStats(), DupStats()
@@ -583,6 +593,104 @@ class Depth:
         h, self.h = self.h, C.c_void_p()
         if h:
             _chk(lib().bwams_depth_close(h), "bwams_depth_close")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PileupOpt(C.Structure):
+    _fields_ = [("exclude", C.c_uint32), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("min_alt", C.c_int32),
+                ("min_permille", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PileupInfo(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("n_regions", C.c_int32), ("n_slots", C.c_int64), ("n_counted", C.c_int64), ("n_entries", C.c_int64),
+                ("n_direct", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
+
+
+class Pileup:
+    """Per-base allele counts over regions on one GPU (bwams_pileup_t): add, then fetch, sites or text at any time."""
+
+    def __init__(self, l_ref, regions=(), device: int = 0, exclude: int = 0x704, min_mapq: int = 0, min_baseq: int = 13, min_alt: int = 2,
+                 min_permille: int = 200):
+        self.h = C.c_void_p()
+        self.l_ref = np.ascontiguousarray(l_ref, np.int32)
+        reg = np.zeros(len(regions), PILEUP_REGION_DTYPE)
+        for k, (r, b, e) in enumerate(regions):
+            reg[k] = (r, b, e)
+        o = PileupOpt(exclude, min_mapq, min_baseq, min_alt, min_permille, 0)
+        _chk(lib().bwams_pileup_open(device, _p(self.l_ref), len(self.l_ref), _p(reg), len(reg), C.byref(o), C.byref(self.h)),
+             "bwams_pileup_open")
+        self.regions = [tuple(int(v) for v in r) for r in regions] or [(r, 0, int(n)) for r, n in enumerate(self.l_ref) if n > 0]
+
+    def add_batch(self, batch: "Batch") -> int:
+        """The batch's current BAM records, read in HBM; -> the records that counted."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_pileup_add_batch(self.h, batch.h, C.byref(n)), "bwams_pileup_add_batch")
+        return n.value
+
+    def add_records(self, records: bytes) -> int:
+        records = bytes(records)
+        n = C.c_int64(0)
+        _chk(lib().bwams_pileup_add_records(self.h, records, len(records), C.byref(n)), "bwams_pileup_add_records")
+        return n.value
+
+    def reset(self) -> None:
+        _chk(lib().bwams_pileup_reset(self.h), "bwams_pileup_reset")
+
+    def set_ref(self, region: int, codes) -> None:
+        """The reference codes (0..4) of one region, end - beg of them."""
+        r, b, e = self.regions[region]
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert len(codes) == e - b
+        _chk(lib().bwams_pileup_set_ref(self.h, region, _p(codes)), "bwams_pileup_set_ref")
+
+    def set_ref_index(self, index: "Index") -> None:
+        _chk(lib().bwams_pileup_set_ref_index(self.h, index.h), "bwams_pileup_set_ref_index")
+
+    def fetch(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:
+        """uint32[end - beg, 12]: the counters of positions [beg, end) of the region (default: all of it)."""
+        r, b, e = self.regions[region]
+        beg, end = b if beg is None else beg, e if end is None else end
+        out = np.zeros((max(end - beg, 1), 12), np.uint32)
+        _chk(lib().bwams_pileup_fetch(self.h, region, beg, end, _p(out)), "bwams_pileup_fetch")
+        return out[:max(end - beg, 0)]
+
+    def sites(self, min_alt: int = -1, min_permille: int = -1, cap: int | None = None) -> np.ndarray:
+        """PILEUP_SITE_DTYPE records of rule 8; cap: the array's size (default: asked for first).  .n_sites: found or needed."""
+        n = C.c_int64(0)
+        if cap is None:
+            _chk(lib().bwams_pileup_sites(self.h, min_alt, min_permille, None, 0, C.byref(n)), "bwams_pileup_sites")
+            cap = n.value
+        out = np.zeros(max(cap, 1), PILEUP_SITE_DTYPE)
+        rc = lib().bwams_pileup_sites(self.h, min_alt, min_permille, _p(out), cap, C.byref(n))
+        self.n_sites = n.value
+        _chk(rc, "bwams_pileup_sites")
+        return out[:n.value]
+
+    def text(self, names, min_alt: int = -1, min_permille: int = -1) -> str:
+        flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
+        n = C.c_int64(0)
+        rc = lib().bwams_pileup_text(self.h, flat, min_alt, min_permille, None, 0, C.byref(n))
+        if rc != -4:
+            _chk(rc, "bwams_pileup_text")
+        buf = C.create_string_buffer(max(n.value, 1))
+        _chk(lib().bwams_pileup_text(self.h, flat, min_alt, min_permille, buf, n.value, C.byref(n)), "bwams_pileup_text")
+        return buf.raw[:n.value].decode("latin-1")
+
+    def info(self) -> dict:
+        """bwams_pileup_info: tile, n_regions, n_slots, and of the last add n_counted, n_entries, n_direct, ms_check, ms_add."""
+        i = PileupInfo()
+        _chk(lib().bwams_pileup_info(self.h, C.byref(i)), "bwams_pileup_info")
+        return {k: getattr(i, k) for k, _ in PileupInfo._fields_}
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_pileup_close(h), "bwams_pileup_close")
 
     def __del__(self):
         try:
@@ -871,6 +979,18 @@ def lib():
         L.bwams_depth_fetch.argtypes = [vp, i32, i32, i32, vp]
         L.bwams_depth_text.argtypes = [vp, vp, i32, i32, vp, i64, vp]
         L.bwams_sorter_set_depth.argtypes = [vp, vp]
+        L.bwams_pileup_open.argtypes = [C.c_int, vp, i32, vp, i32, vp, vp]
+        L.bwams_pileup_close.argtypes = [vp]
+        L.bwams_pileup_reset.argtypes = [vp]
+        L.bwams_pileup_add_batch.argtypes = [vp, vp, vp]
+        L.bwams_pileup_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_pileup_set_ref.argtypes = [vp, i32, vp]
+        L.bwams_pileup_set_ref_index.argtypes = [vp, vp]
+        L.bwams_pileup_fetch.argtypes = [vp, i32, i32, i32, vp]
+        L.bwams_pileup_sites.argtypes = [vp, i32, i32, vp, i64, vp]
+        L.bwams_pileup_text.argtypes = [vp, vp, i32, i32, vp, i64, vp]
+        L.bwams_pileup_info.argtypes = [vp, vp]
+        L.bwams_sorter_set_pileup.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]

@@ -1,0 +1,157 @@
+"""Pileup restated in numpy: the yardstick of csrc/pileup.hip and host/pileup_text.cpp.
+
+The rules are numbered in include/bwams.h above bwams_pileup_open; the numbers below are theirs.  Pileup(l_ref, regions, ...)
+accumulates records (BAM records with their block_size, back to back, as bwams/bam.py builds them) into 12 counters per region
+position; fetch, sites and text return what the C-ABI's return.
+"""
+from __future__ import annotations
+
+import struct
+
+import numpy as np
+
+from bwams import bam
+
+DEFAULT_EXCLUDE = 0x704
+CHANNELS = ("A+", "C+", "G+", "T+", "A-", "C-", "G-", "T-", "N", "DEL", "INS")          # the live ones; channel 11 stays 0
+N, DEL, INS = 8, 9, 10
+KINDS = ("A", "C", "G", "T", "DEL", "INS")                                              # rule 8's bits 0..5
+SITE_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("kinds", "<u4"), ("depth", "<u4"), ("c", "<u4", (12,))])
+TEXT_HEADER = "chrom\tpos\tref\tdepth\t" + "\t".join(CHANNELS) + "\talt\n"
+_CHANNEL_OF_CODE = np.full(16, N, np.int64)                                             # rule 4: every code but 1 2 4 8 is N
+_CHANNEL_OF_CODE[[1, 2, 4, 8]] = [0, 1, 2, 3]
+_REF_OPS, _QUERY_OPS = (0, 2, 3, 7, 8), (0, 1, 4, 7, 8)
+
+
+class PileupRefusal(ValueError):
+    """Rule 3 (BWAMS_ERR_ARG); .record is the record's index in the call, .why "op", "length" or "bounds"."""
+
+    def __init__(self, record: int, why: str):
+        super().__init__(f"record {record}: {why}")
+        self.record, self.why = record, why
+
+
+def fields(rec: bytes):
+    """(refID, POS, MAPQ, FLAG, [(length, op)], l_seq, codes uint8[l_seq], qual uint8[l_seq]) of one record (block_size included)."""
+    refid, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiBBHHHi", rec, 4)
+    at = 36 + l_name
+    ops = struct.unpack_from("<%dI" % n_cig, rec, at)
+    at += 4 * n_cig
+    n = min(max(l_seq, 0), max(len(rec) - at, 0) * 2 // 3)                        # a record cut short: rule 3 refuses it when it counts
+    packed = np.frombuffer(rec, np.uint8, (n + 1) // 2, at)
+    codes = np.stack([packed >> 4, packed & 15], 1).reshape(-1)[:n]
+    qual = np.frombuffer(rec, np.uint8, n, at + (n + 1) // 2)
+    return refid, pos, mapq, flag, [(c >> 4, c & 15) for c in ops], l_seq, codes, qual
+
+
+class Pileup:
+    def __init__(self, l_ref, regions=(), exclude: int = DEFAULT_EXCLUDE, min_mapq: int = 0, min_baseq: int = 13, min_alt: int = 2,
+                 min_permille: int = 200):
+        self.l_ref = [int(x) for x in l_ref]
+        regions = [tuple(int(v) for v in r) for r in regions] or [(r, 0, n) for r, n in enumerate(self.l_ref) if n > 0]
+        for k, (r, b, e) in enumerate(regions):                                          # rule 1
+            assert 0 <= r < len(self.l_ref) and 0 <= b < e <= self.l_ref[r], (k, r, b, e)
+            assert k == 0 or (regions[k - 1][0], regions[k - 1][2]) <= (r, b), "sorted, no overlap"
+        self.regions = regions
+        self.off = np.concatenate([[0], np.cumsum([e - b for _, b, e in regions])]).astype(np.int64)
+        self.n_slots = int(self.off[-1])
+        self.slot = [np.full(n, -1, np.int64) for n in self.l_ref]                       # position -> slot, -1 outside every region
+        for k, (r, b, e) in enumerate(regions):
+            self.slot[r][b:e] = np.arange(self.off[k], self.off[k + 1])
+        self.exclude, self.min_mapq, self.min_baseq, self.min_alt, self.min_permille = exclude, min_mapq, min_baseq, min_alt, min_permille
+        self.ref = np.full(self.n_slots, 4, np.uint8)                                    # rule 7
+        self.reset()
+
+    def reset(self):                                                                     # rule 6
+        self.c = np.zeros((self.n_slots, 12), np.int64)
+
+    def counts(self, refid, mapq, flag, cigar, l_seq) -> bool:                           # rule 2
+        return (not flag & self.exclude and mapq >= self.min_mapq and 0 <= refid < len(self.l_ref) and len(cigar) > 0 and l_seq > 0)
+
+    def _put(self, refid, pos, channel):
+        """+1 at each (position, channel) whose position lies in a region (rule 4: the others are dropped one by one)"""
+        pos, channel = np.asarray(pos, np.int64), np.asarray(channel, np.int64)
+        ok = (pos >= 0) & (pos < self.l_ref[refid])
+        s = self.slot[refid][pos[ok]]
+        np.add.at(self.c, (s[s >= 0], channel[ok][s >= 0]), 1)
+
+    def add(self, records: bytes) -> int:
+        """Every record of `records`; -> the number that counted.  Check first, then add (rule 3)."""
+        recs = [fields(r) for r in bam.split_records(records)]
+        for k, (refid, _, mapq, flag, cigar, l_seq, codes, _) in enumerate(recs):
+            if any(op > 8 for _, op in cigar):
+                raise PileupRefusal(k, "op")
+            if self.counts(refid, mapq, flag, cigar, l_seq):
+                if sum(n for n, op in cigar if op in _QUERY_OPS) != l_seq:
+                    raise PileupRefusal(k, "length")
+                if len(codes) != l_seq:                                                  # SEQ or QUAL ends behind the record
+                    raise PileupRefusal(k, "bounds")
+        n_counted = 0
+        for refid, pos, mapq, flag, cigar, l_seq, codes, qual in recs:
+            if not self.counts(refid, mapq, flag, cigar, l_seq):
+                continue
+            n_counted += 1
+            strand = 4 if flag & 0x10 else 0
+            good = np.ones(l_seq, bool) if qual[0] == 0xFF else qual >= self.min_baseq   # rule 4: no qualities pass every min_baseq
+            x, q, seen_ref = pos, 0, False
+            for n, op in cigar:
+                if op in (0, 7, 8):
+                    ch = _CHANNEL_OF_CODE[codes[q:q + n]]
+                    ch = np.where(ch < 4, ch + strand, ch)
+                    g = good[q:q + n]
+                    self._put(refid, np.arange(x, x + n)[g], ch[g])
+                elif op == 2:
+                    lo, hi = max(x, 0), min(x + n, self.l_ref[refid])
+                    if lo < hi:
+                        self._put(refid, np.arange(lo, hi), np.full(hi - lo, DEL))
+                elif op == 1 and seen_ref:                                               # one per I op, at the position before it
+                    self._put(refid, [x - 1], [INS])
+                if op in _REF_OPS:
+                    x += n
+                    seen_ref = True
+                if op in _QUERY_OPS:
+                    q += n
+        return n_counted
+
+    def set_ref(self, region: int, codes):                                               # rule 7
+        r, b, e = self.regions[region]
+        codes = np.asarray(codes, np.uint8)
+        assert len(codes) == e - b and (codes <= 4).all()
+        self.ref[self.off[region]:self.off[region + 1]] = codes
+
+    def set_ref_genome(self, genome_by_ref):
+        """every region's bases from one code array per reference (what _set_ref_index gathers)"""
+        for k, (r, b, e) in enumerate(self.regions):
+            self.set_ref(k, np.minimum(np.asarray(genome_by_ref[r][b:e], np.uint8), 4))
+
+    def fetch(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:
+        r, b, e = self.regions[region]
+        beg, end = b if beg is None else beg, e if end is None else end
+        assert b <= beg <= end <= e
+        return self.c[self.off[region] + beg - b:self.off[region] + end - b].astype(np.uint32)
+
+    def sites(self, min_alt: int | None = None, min_permille: int | None = None) -> np.ndarray:      # rule 8
+        min_alt = self.min_alt if min_alt is None else min_alt
+        min_permille = self.min_permille if min_permille is None else min_permille
+        c = self.c
+        depth = c[:, :8].sum(1) + c[:, DEL]
+        allele = np.stack([c[:, 0] + c[:, 4], c[:, 1] + c[:, 5], c[:, 2] + c[:, 6], c[:, 3] + c[:, 7], c[:, DEL], c[:, INS]], 1)
+        cand = (allele >= min_alt) & (allele * 1000 >= min_permille * depth[:, None]) & (self.ref < 4)[:, None]
+        cand[:, :4] &= np.arange(4)[None, :] != self.ref[:, None]
+        kinds = (cand << np.arange(6)).sum(1)
+        at = np.flatnonzero(kinds)
+        out = np.zeros(len(at), SITE_DTYPE)
+        region = np.searchsorted(self.off, at, "right") - 1
+        out["region"] = region
+        out["pos"] = at - self.off[region] + np.array([b for _, b, _ in self.regions], np.int64)[region]
+        out["ref"], out["kinds"], out["depth"], out["c"] = self.ref[at], kinds[at], depth[at], c[at]
+        return out
+
+    def text(self, names, min_alt: int | None = None, min_permille: int | None = None) -> str:       # rule 9
+        names = [n.decode() if isinstance(n, bytes) else n for n in names]
+        rows = [TEXT_HEADER]
+        for s in self.sites(min_alt, min_permille):
+            alts = ",".join(k for bit, k in enumerate(KINDS) if int(s["kinds"]) >> bit & 1)
+            rows.append("%s\t%d\t%s\t%d\t%s\t%s\n" % (names[self.regions[int(s["region"])][0]], int(s["pos"]) + 1, "ACGTN"[int(s["ref"])],
+                                                     int(s["depth"]), "\t".join(str(int(v)) for v in s["c"][:11]), alts))
+        return "".join(rows)

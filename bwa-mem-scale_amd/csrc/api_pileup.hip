@@ -1,0 +1,408 @@
+// api_pileup.hip — C-ABI entry points of the pileup (include/bwams.h, "Pileup"): the handle over a list of regions, the adds from a
+// batch and from host records, the reference bases, and the queries, over pileup.hip; the text over host/pileup_text.cpp.
+// No CPU fallback: every entry point runs HIP kernels or returns an error.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+#include <rocprim/rocprim.hpp>
+
+#include "stage_state.h"
+#include "../host/pileup_host.h"
+
+using namespace bwams;
+
+struct bwams_pileup {
+    int device = 0, cu_count = 0;
+    hipStream_t stream = nullptr;
+    bwams_pileup_opt_t opt{};
+    std::vector<int32_t> l_ref;
+    std::vector<bwams_pileup_region_t> regions;
+    std::vector<int64_t> reg_off;                    // n_regions + 1: region k's first slot; the last is the number of slots
+    DevBuf<uint32_t> counts;                         // kPileupChannels per slot
+    DevBuf<uint8_t> ref;                             // rule 7: a code per slot
+    DevBuf<int32_t> d_beg, d_end, d_ref_first, d_reg_ref;
+    DevBuf<int64_t> d_off;
+    DevBuf<> tmp;                                    // rocPRIM temporary storage
+    DevBuf<uint8_t> recs;                            // bwams_pileup_add_records: the uploaded records and their offsets
+    DevBuf<int64_t> roff;
+    DevBuf<unsigned long long> flag;                 // [0..2] rule 3's first bad records, [3..5] the route counters of a piece
+    DevBuf<uint32_t> keys, keys2, vals, vals2, heads, n_heads;       // the (tile, record) entries of a piece, twice for the sort
+    DevBuf<uint8_t> route;
+    DevBuf<int64_t> sel, sel_cnt;                    // the queries' device results, kept between calls
+    DevBuf<bwams_pileup_site_t> d_sites;
+    DevBuf<int64_t> hole_off;                        // bwams_pileup_set_ref_index: the index's .amb holes
+    DevBuf<int32_t> hole_len;
+    int64_t n_added = 0;                             // records given so far (rule 6)
+    int64_t last[3] = {0, 0, 0};                     // of the last add: records counted, tile entries, records routed direct
+    float ms_check = 0, ms_add = 0;                  // ... and its device time, between the events below
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int32_t n_ref() const { return (int32_t)l_ref.size(); }
+    int32_t n_regions() const { return (int32_t)regions.size(); }
+    int64_t n_slots() const { return reg_off.back(); }
+    PileupRegions dev_regions() const { return PileupRegions{d_beg.p, d_end.p, d_ref_first.p, d_off.p}; }
+    ~bwams_pileup() {
+        (void)hipSetDevice(device);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace bwams {
+int pileup_device(const bwams_pileup *p) { return p->device; }
+const std::vector<int32_t> &pileup_l_ref(const bwams_pileup *p) { return p->l_ref; }
+}  // namespace bwams
+
+namespace {
+
+constexpr int64_t kPiece = 1 << 24;                  // records routed and sorted at a time: 32 bytes of scratch per record
+
+struct SiteCount {
+    PileupSiteTest f;
+    __host__ __device__ int64_t operator()(int64_t s) const { return f(s) ? 1 : 0; }
+};
+
+// check first, then add (rule 3): the records at dev_bam + dev_off[r]
+int pileup_add(bwams_pileup *p, const uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, int64_t *n_counted, const char *who) {
+    if (p->n_added + n_rec > 0x7FFFFFFFLL) {
+        set_last_error(std::string(who) + ": more than 2^31 - 1 records added in total");
+        return BWAMS_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = p->stream;
+    int64_t sum[3] = {0, 0, 0};
+    float ms = 0;
+    p->ms_check = p->ms_add = 0;
+    if (n_rec > 0) {
+        const PileupFilter f{p->opt.exclude, p->opt.min_mapq, p->n_ref()};
+        unsigned long long h[3] = {0, 0, 0};
+        BWAMS_HIP(hipMemsetAsync(p->flag.p, 0xFF, 24, st));
+        BWAMS_HIP(hipEventRecord(p->ev[0], st));
+        launch_pileup_check(dev_bam, dev_off, n_rec, f, p->flag.p, p->cu_count, st);
+        BWAMS_HIP(hipEventRecord(p->ev[1], st));
+        BWAMS_HIP(hipMemcpyAsync(h, p->flag.p, 24, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipStreamSynchronize(st));
+        BWAMS_HIP(hipGetLastError());
+        BWAMS_HIP(hipEventElapsedTime(&p->ms_check, p->ev[0], p->ev[1]));
+        const int first = (int)(std::min_element(h, h + 3) - h);         // the first bad record; a record is in one list only
+        if (h[first] != ~0ULL) {
+            static const char *const why[3] = {" has a CIGAR op code above 8", " has a CIGAR whose query length is not l_seq",
+                                               " ends inside its SEQ or QUAL"};
+            set_last_error(std::string(who) + ": record " + std::to_string(h[first]) + why[first]);
+            return BWAMS_ERR_ARG;
+        }
+        const int64_t n_tiles = (p->n_slots() + kPileupTile - 1) / kPileupTile;
+        const int tiled = knobs().pileup_tiled != 0 && n_tiles > 0;
+        unsigned bits = 1;
+        while ((1LL << bits) <= n_tiles) ++bits;                         // the keys are 0 .. n_tiles
+        const PileupRegions R = p->dev_regions();
+        const int64_t n_max = std::min(kPiece, n_rec);                   // every buffer for the largest piece before the first counter
+        BWAMS_HIP(p->route.ensure_n((size_t)n_max));                     // moves: an allocation that fails adds nothing
+        if (tiled) {
+            BWAMS_HIP(p->keys.ensure_n((size_t)(2 * n_max))); BWAMS_HIP(p->keys2.ensure_n((size_t)(2 * n_max)));
+            BWAMS_HIP(p->vals.ensure_n((size_t)(2 * n_max))); BWAMS_HIP(p->vals2.ensure_n((size_t)(2 * n_max)));
+            BWAMS_HIP(p->heads.ensure_n((size_t)std::min(2 * n_max, n_tiles)));
+            size_t tb = 0;                                               // the sort's temporary storage too
+            BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, p->keys.p, p->keys2.p, p->vals.p, p->vals2.p, (size_t)(2 * n_max), 0u, bits, st));
+            if (tb > p->tmp.cap || !p->tmp.p) BWAMS_HIP(p->tmp.alloc(std::max<size_t>(tb, 256)));
+        }
+        for (int64_t r0 = 0; r0 < n_rec; r0 += kPiece) {
+            const int64_t n = std::min(kPiece, n_rec - r0), n_ent = 2 * n;
+            if (tiled) BWAMS_HIP(hipMemsetAsync(p->n_heads.p, 0, 4, st));
+            BWAMS_HIP(hipMemsetAsync(p->flag.p + 3, 0, 24, st));
+            BWAMS_HIP(hipEventRecord(p->ev[0], st));
+            launch_pileup_route(dev_bam, dev_off + r0, n, f, R, (uint32_t)n_tiles, tiled, p->keys.p, p->vals.p, p->route.p, p->flag.p + 3,
+                                p->cu_count, st);
+            if (tiled) {
+                if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": radix_sort_pairs").c_str(), [&](void *tmp, size_t &tb) {
+                        return rocprim::radix_sort_pairs(tmp, tb, p->keys.p, p->keys2.p, p->vals.p, p->vals2.p, (size_t)n_ent, 0u, bits, st);
+                    })) return rc;
+                launch_pileup_tiles(dev_bam, dev_off + r0, R, p->opt.min_baseq, p->keys2.p, p->vals2.p, n_ent, (uint32_t)n_tiles, p->heads.p,
+                                    p->n_heads.p, p->n_slots(), p->counts.p, p->cu_count, st);
+            }
+            launch_pileup_direct(dev_bam, dev_off + r0, n, R, p->opt.min_baseq, p->route.p, p->counts.p, p->cu_count, st);
+            BWAMS_HIP(hipEventRecord(p->ev[1], st));
+            BWAMS_HIP(hipMemcpyAsync(h, p->flag.p + 3, 24, hipMemcpyDeviceToHost, st));
+            BWAMS_HIP(hipStreamSynchronize(st));
+            BWAMS_HIP(hipGetLastError());
+            BWAMS_HIP(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+            p->ms_add += ms;
+            for (int k = 0; k < 3; ++k) sum[k] += (int64_t)h[k];
+        }
+    }
+    p->n_added += n_rec;
+    std::copy(sum, sum + 3, p->last);
+    if (n_counted) *n_counted = sum[0];
+    return BWAMS_OK;
+}
+
+int thresholds(const bwams_pileup *p, int32_t min_alt, int32_t min_permille, const char *who, PileupSiteTest *t) {
+    if (min_alt < 0) min_alt = p->opt.min_alt;
+    if (min_permille < 0) min_permille = p->opt.min_permille;
+    if (min_alt < 1 || min_permille > 1000) {
+        set_last_error(std::string(who) + ": min_alt >= 1 and min_permille <= 1000 are required (negative: the handle's)");
+        return BWAMS_ERR_ARG;
+    }
+    *t = PileupSiteTest{p->counts.p, p->ref.p, (uint32_t)min_alt, (uint32_t)min_permille};
+    return BWAMS_OK;
+}
+
+// rule 8: the sites into host memory
+int pileup_sites(bwams_pileup *p, const PileupSiteTest &test, const char *who, bool count_only, int64_t cap, bwams_pileup_site_t *sites,
+                 std::vector<bwams_pileup_site_t> *own, int64_t *n_out) {
+    hipStream_t st = p->stream;
+    int64_t n_sites = 0;
+    const int64_t n_slots = p->n_slots();
+    rocprim::counting_iterator<int64_t> slot(0);
+    BWAMS_HIP(p->sel_cnt.ensure_n(8));
+    if (n_slots > 0) {
+        auto ones = rocprim::make_transform_iterator(slot, SiteCount{test});
+        if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": reduce").c_str(), [&](void *tmp, size_t &tb) {
+                return rocprim::reduce(tmp, tb, ones, p->sel_cnt.p, (int64_t)0, (size_t)n_slots, rocprim::plus<int64_t>(), st);
+            })) return rc;
+        BWAMS_HIP(hipMemcpyAsync(&n_sites, p->sel_cnt.p, 8, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipStreamSynchronize(st));
+    }
+    *n_out = n_sites;
+    if (count_only || n_sites == 0) return BWAMS_OK;
+    if (!own && cap < n_sites) {
+        set_last_error(std::string(who) + ": " + std::to_string(n_sites) + " sites do not fit a capacity of " + std::to_string(cap));
+        return BWAMS_ERR_CAPACITY;
+    }
+    BWAMS_HIP(p->sel.ensure_n((size_t)n_sites)); BWAMS_HIP(p->d_sites.ensure_n((size_t)n_sites));
+    if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": select").c_str(), [&](void *tmp, size_t &tb) {
+            return rocprim::select(tmp, tb, slot, p->sel.p, p->sel_cnt.p, (size_t)n_slots, test, st);
+        })) return rc;
+    launch_pileup_sites(test, p->dev_regions(), p->n_regions(), p->sel.p, n_sites, p->d_sites.p, p->cu_count, st);
+    if (own) { own->resize((size_t)n_sites); sites = own->data(); }
+    BWAMS_HIP(hipMemcpyAsync(sites, p->d_sites.p, (size_t)n_sites * sizeof(bwams_pileup_site_t), hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    BWAMS_HIP(hipGetLastError());
+    return BWAMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwams_pileup_region_t *regions, int32_t n_regions,
+                      const bwams_pileup_opt_t *opt, bwams_pileup_t **out) {
+    if (!out || n_ref < 0 || (n_ref && !l_ref) || n_regions < 0 || (n_regions && !regions) ||
+        (opt && (opt->exclude > 0xFFFFu || opt->reserved != 0 || opt->min_baseq < 0 || opt->min_baseq > 255 || opt->min_alt < 1 ||
+                 opt->min_permille < 0 || opt->min_permille > 1000))) {
+        set_last_error("bwams_pileup_open: n_ref >= 0 lengths, n_regions >= 0 regions, exclude within 16 bits, min_baseq in [0, 255], "
+                       "min_alt >= 1, min_permille in [0, 1000] and reserved == 0 are required");
+        return BWAMS_ERR_ARG;
+    }
+    *out = nullptr;
+    for (int32_t r = 0; r < n_ref; ++r)
+        if (l_ref[r] < 0) {
+            set_last_error("bwams_pileup_open: reference " + std::to_string(r) + " has a negative length");
+            return BWAMS_ERR_ARG;
+        }
+    for (int32_t k = 0; k < n_regions; ++k) {                            // rule 1
+        const bwams_pileup_region_t &g = regions[k];
+        const bool inside = g.ref >= 0 && g.ref < n_ref && g.beg >= 0 && g.beg < g.end && g.end <= l_ref[g.ref];
+        const bool ordered = k == 0 || regions[k - 1].ref < g.ref || (regions[k - 1].ref == g.ref && regions[k - 1].end <= g.beg);
+        if (!inside || !ordered) {
+            set_last_error("bwams_pileup_open: region " + std::to_string(k) +
+                           (inside ? " overlaps the one before it or is not in (ref, beg) order" : " is not 0 <= beg < end <= l_ref[ref]"));
+            return BWAMS_ERR_ARG;
+        }
+    }
+    if (int rc = check_device(device)) return rc;
+    BWAMS_HIP(hipSetDevice(device));
+    std::unique_ptr<bwams_pileup> p(new bwams_pileup());
+    p->device = device;
+    p->opt = opt ? *opt : bwams_pileup_opt_t{0x704, 0, 13, 2, 200, 0};
+    p->l_ref.assign(l_ref, l_ref + n_ref);
+    if (n_regions) p->regions.assign(regions, regions + n_regions);
+    else
+        for (int32_t r = 0; r < n_ref; ++r)
+            if (l_ref[r] > 0) p->regions.push_back(bwams_pileup_region_t{r, 0, l_ref[r]});
+    const size_t n_reg = p->regions.size();
+    std::vector<int32_t> beg(n_reg), end(n_reg), reg_ref(n_reg), ref_first((size_t)n_ref + 1, 0);
+    p->reg_off.assign(n_reg + 1, 0);
+    for (size_t k = 0; k < n_reg; ++k) {
+        const bwams_pileup_region_t &g = p->regions[k];
+        beg[k] = g.beg; end[k] = g.end; reg_ref[k] = g.ref;
+        p->reg_off[k + 1] = p->reg_off[k] + (g.end - g.beg);
+        ++ref_first[(size_t)g.ref + 1];
+    }
+    for (int32_t r = 0; r < n_ref; ++r) ref_first[(size_t)r + 1] += ref_first[(size_t)r];
+    BWAMS_HIP(hipDeviceGetAttribute(&p->cu_count, hipDeviceAttributeMultiprocessorCount, device));
+    BWAMS_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    for (hipEvent_t &e : p->ev) BWAMS_HIP(hipEventCreate(&e));
+    hipStream_t st = p->stream;
+    const size_t slots = (size_t)std::max<int64_t>(p->n_slots(), 1);
+    BWAMS_HIP(p->counts.alloc(slots * kPileupChannels * 4));            // rule 1: BWAMS_ERR_NOMEM when they do not fit
+    BWAMS_HIP(p->ref.alloc(slots));
+    BWAMS_HIP(p->d_beg.alloc(std::max<size_t>(n_reg, 1) * 4)); BWAMS_HIP(p->d_end.alloc(std::max<size_t>(n_reg, 1) * 4));
+    BWAMS_HIP(p->d_reg_ref.alloc(std::max<size_t>(n_reg, 1) * 4)); BWAMS_HIP(p->d_off.alloc((n_reg + 1) * 8));
+    BWAMS_HIP(p->d_ref_first.alloc(((size_t)n_ref + 1) * 4));
+    BWAMS_HIP(p->flag.alloc(6 * 8)); BWAMS_HIP(p->n_heads.alloc(4));
+    BWAMS_HIP(hipMemsetAsync(p->counts.p, 0, slots * kPileupChannels * 4, st));
+    BWAMS_HIP(hipMemsetAsync(p->ref.p, 4, slots, st));
+    if (n_reg) {
+        BWAMS_HIP(hipMemcpyAsync(p->d_beg.p, beg.data(), n_reg * 4, hipMemcpyHostToDevice, st));
+        BWAMS_HIP(hipMemcpyAsync(p->d_end.p, end.data(), n_reg * 4, hipMemcpyHostToDevice, st));
+        BWAMS_HIP(hipMemcpyAsync(p->d_reg_ref.p, reg_ref.data(), n_reg * 4, hipMemcpyHostToDevice, st));
+    }
+    BWAMS_HIP(hipMemcpyAsync(p->d_off.p, p->reg_off.data(), (n_reg + 1) * 8, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(p->d_ref_first.p, ref_first.data(), ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipStreamSynchronize(st));                                 // the host vectors above end here
+    *out = p.release();
+    return BWAMS_OK;
+}
+
+int bwams_pileup_close(bwams_pileup_t *p) {
+    delete p;
+    return BWAMS_OK;
+}
+
+int bwams_pileup_reset(bwams_pileup_t *p) {
+    if (!p) return BWAMS_ERR_ARG;
+    BWAMS_HIP(hipSetDevice(p->device));
+    BWAMS_HIP(hipMemsetAsync(p->counts.p, 0, (size_t)std::max<int64_t>(p->n_slots(), 1) * kPileupChannels * 4, p->stream));
+    BWAMS_HIP(hipStreamSynchronize(p->stream));
+    p->n_added = 0;
+    std::fill(p->last, p->last + 3, 0);
+    return BWAMS_OK;
+}
+
+int bwams_pileup_add_batch(bwams_pileup_t *p, bwams_batch_t *b, int64_t *n_counted) {
+    if (!p || !b || !b->stages || !b->stages->bm.done) {
+        set_last_error("bwams_pileup_add_batch: run bwams_bam_run or bwams_bam_upload first");
+        return BWAMS_ERR_ARG;
+    }
+    if (b->idx->device != p->device) {
+        set_last_error("bwams_pileup_add_batch: the handle is on device " + std::to_string(p->device) + ", the batch on device " +
+                       std::to_string(b->idx->device));
+        return BWAMS_ERR_ARG;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    BWAMS_HIP(hipStreamSynchronize(b->stream));              // the records may still be written by queued work
+    StageState *s = b->stages;
+    return pileup_add(p, s->bm.out.p, s->bm.roff.p, s->bm.nrec, n_counted, "bwams_pileup_add_batch");
+}
+
+int bwams_pileup_add_records(bwams_pileup_t *p, const void *bam, int64_t n_bytes, int64_t *n_counted) {
+    if (!p || n_bytes < 0 || (n_bytes && !bam)) {
+        set_last_error("bwams_pileup_add_records: a handle and host records are required");
+        return BWAMS_ERR_ARG;
+    }
+    std::vector<int64_t> off;
+    int32_t max_rid = -1;
+    if (int rc = bam_record_offsets("bwams_pileup_add_records", bam, n_bytes, &off, &max_rid)) return rc;
+    const int64_t n_rec = (int64_t)off.size() - 1;
+    BWAMS_HIP(hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    BWAMS_HIP(p->recs.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(p->roff.ensure_n((size_t)n_rec + 1));
+    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(p->recs.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(p->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here when the add returns early
+    return pileup_add(p, p->recs.p, p->roff.p, n_rec, n_counted, "bwams_pileup_add_records");
+}
+
+int bwams_pileup_set_ref(bwams_pileup_t *p, int32_t region, const uint8_t *codes) {
+    if (!p || region < 0 || region >= p->n_regions() || !codes) {
+        set_last_error("bwams_pileup_set_ref: a handle, a region in [0, n_regions) and its codes are required");
+        return BWAMS_ERR_ARG;
+    }
+    const int64_t n = p->reg_off[(size_t)region + 1] - p->reg_off[(size_t)region];
+    for (int64_t k = 0; k < n; ++k)
+        if (codes[k] > 4) {
+            set_last_error("bwams_pileup_set_ref: code " + std::to_string(k) + " is above 4");
+            return BWAMS_ERR_ARG;
+        }
+    BWAMS_HIP(hipSetDevice(p->device));
+    BWAMS_HIP(hipMemcpyAsync(p->ref.p + p->reg_off[(size_t)region], codes, (size_t)n, hipMemcpyHostToDevice, p->stream));
+    BWAMS_HIP(hipStreamSynchronize(p->stream));
+    return BWAMS_OK;
+}
+
+int bwams_pileup_set_ref_index(bwams_pileup_t *p, const bwams_index_t *ix) {
+    if (!p || !ix || ix->device != p->device || !ix->fmi.ref || !ix->d_contigs.p || ix->n_seqs != p->n_ref()) {
+        set_last_error("bwams_pileup_set_ref_index: an index on the handle's device with its .0123 and the handle's n_ref contigs is required");
+        return BWAMS_ERR_ARG;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    std::vector<bwams_contig_t> c((size_t)ix->n_seqs);
+    if (!c.empty()) BWAMS_HIP(hipMemcpy(c.data(), ix->d_contigs.p, c.size() * sizeof(bwams_contig_t), hipMemcpyDeviceToHost));
+    const int64_t l_pac = (ix->fmi.ref_seq_len - 1) / 2;                 // the forward strand of .0123, as bwams_index_set_contigs has it
+    for (size_t r = 0; r < c.size(); ++r)
+        if (c[r].len != p->l_ref[r] || c[r].offset < 0 || c[r].offset + c[r].len > l_pac) {
+            set_last_error("bwams_pileup_set_ref_index: contig " + std::to_string(r) + " has not the handle's length, or lies outside the index");
+            return BWAMS_ERR_ARG;
+        }
+    hipStream_t st = p->stream;
+    const BnsMeta *m = ix->bns;
+    const size_t n_holes = m ? m->hole_off.size() : 0;
+    if (n_holes) {                                                       // in the handle: nothing queued outlives its buffer
+        BWAMS_HIP(p->hole_off.ensure_n(n_holes)); BWAMS_HIP(p->hole_len.ensure_n(n_holes));
+        BWAMS_HIP(hipMemcpyAsync(p->hole_off.p, m->hole_off.data(), n_holes * 8, hipMemcpyHostToDevice, st));
+        BWAMS_HIP(hipMemcpyAsync(p->hole_len.p, m->hole_len.data(), n_holes * 4, hipMemcpyHostToDevice, st));
+    }
+    launch_pileup_ref(p->dev_regions(), p->n_regions(), p->d_reg_ref.p, p->n_slots(), ix->fmi.ref, ix->d_contigs.as<const bwams_contig_t>(),
+                      p->hole_off.p, p->hole_len.p, (int32_t)n_holes, p->ref.p, p->cu_count, st);
+    BWAMS_HIP(hipStreamSynchronize(st));
+    BWAMS_HIP(hipGetLastError());
+    return BWAMS_OK;
+}
+
+int bwams_pileup_fetch(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *counts) {
+    if (!p || region < 0 || region >= p->n_regions() || beg < p->regions[(size_t)region].beg || end < beg ||
+        end > p->regions[(size_t)region].end || (end > beg && !counts)) {
+        set_last_error("bwams_pileup_fetch: a region in [0, n_regions) and region.beg <= beg <= end <= region.end are required");
+        return BWAMS_ERR_ARG;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    if (end > beg) {
+        const int64_t first = p->reg_off[(size_t)region] + (beg - p->regions[(size_t)region].beg);
+        BWAMS_HIP(hipMemcpyAsync(counts, p->counts.p + first * kPileupChannels, (size_t)(end - beg) * kPileupChannels * 4,
+                                 hipMemcpyDeviceToHost, p->stream));
+        BWAMS_HIP(hipStreamSynchronize(p->stream));
+    }
+    return BWAMS_OK;
+}
+
+int bwams_pileup_sites(bwams_pileup_t *p, int32_t min_alt, int32_t min_permille, bwams_pileup_site_t *sites, int64_t cap, int64_t *n) {
+    if (!p || cap < 0) return BWAMS_ERR_ARG;
+    PileupSiteTest test;
+    if (int rc = thresholds(p, min_alt, min_permille, "bwams_pileup_sites", &test)) return rc;
+    BWAMS_HIP(hipSetDevice(p->device));
+    int64_t n_sites = 0;
+    const int rc = pileup_sites(p, test, "bwams_pileup_sites", !sites, cap, sites, nullptr, &n_sites);
+    if (n) *n = n_sites;
+    return rc;
+}
+
+int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int32_t min_permille, char *out, int64_t cap, int64_t *n) {
+    if (!p || (!names && p->n_ref())) {
+        set_last_error("bwams_pileup_text: a handle and the references' names are required");
+        return BWAMS_ERR_ARG;
+    }
+    PileupSiteTest test;
+    if (int rc = thresholds(p, min_alt, min_permille, "bwams_pileup_text", &test)) return rc;
+    BWAMS_HIP(hipSetDevice(p->device));
+    std::vector<bwams_pileup_site_t> sites;
+    int64_t n_sites = 0;
+    if (int rc = pileup_sites(p, test, "bwams_pileup_text", false, 0, nullptr, &sites, &n_sites)) return rc;
+    std::string text;
+    if (int rc = pileup_text_format(names, p->n_ref(), p->regions.data(), p->n_regions(), sites.data(), n_sites, &text)) return rc;
+    if (n) *n = (int64_t)text.size();
+    if (!out || cap < (int64_t)text.size()) {
+        set_last_error("bwams_pileup_text: the text needs " + std::to_string(text.size()) + " bytes");
+        return BWAMS_ERR_CAPACITY;
+    }
+    memcpy(out, text.data(), text.size());
+    return BWAMS_OK;
+}
+
+int bwams_pileup_info(const bwams_pileup_t *p, bwams_pileup_info_t *info) {
+    if (!p || !info) return BWAMS_ERR_ARG;
+    *info = bwams_pileup_info_t{kPileupTile, p->n_regions(), p->n_slots(), p->last[0], p->last[1], p->last[2], p->ms_check, p->ms_add};
+    return BWAMS_OK;
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@ struct Knobs {
     int chain_batch = 1;           // BWAMS_CHAIN_BATCH=0: chaining's wave tier takes one seed at a time (chain.hip: chain_seeds_batch)
     int ert_fat = 1;               // BWAMS_ERT_FAT=0: the ERT walk reads the reference's two tables only (no entry + tree-head table)
     int depth_combine = 1;         // BWAMS_DEPTH_COMBINE=0: the depth add issues one atomic per lane (no folding of equal slots inside a wave)
+    int pileup_tiled = 1;          // BWAMS_PILEUP_TILED=0: every record of a pileup add goes through the direct kernel (one global atomic per base)
     int ert_grid = -1, ert_ticket = 1;   // BWAMS_ERT_GRID (blocks per CU, 0 = one block per 256 bases) / BWAMS_ERT_TICKET=0 (round robin)
 };
 const Knobs &knobs();
@@ -285,6 +286,60 @@ void launch_depth_windows(const int32_t *slots, const int64_t *slot_off, int32_t
                           unsigned long long *sums, int cu_count, hipStream_t st);
 void launch_depth_hist(const int32_t *slots, int64_t lo, int64_t hi, int32_t n_bins, unsigned long long *hist, int cu_count, hipStream_t st);
 void launch_depth_gather(const int32_t *slots, int64_t base, const int32_t *start, int64_t n, int32_t *depth, int cu_count, hipStream_t st);
+
+// pileup.hip: per-base allele counts and candidate sites (rules in include/bwams.h above bwams_pileup_open).  counts: kPileupChannels
+// uint32 per slot, a slot per region position in region order.  check: bad[0] = min(bad[0], index of a record with an op code above
+// 8), bad[1] the same for a counted record whose CIGAR query length is not l_seq, bad[2] for one whose SEQ or QUAL ends behind it.  route: rule 2's filter and each record's way
+// (route[r]); tiled != 0 also writes the (tile, record) entries 2r and 2r + 1 into keys / vals, unused ones with the key n_tiles;
+// counts[0..2] += records counted, entries, records routed direct.  tiles: the entries sorted by key; heads (min(n_ent, n_tiles)
+// slots) and *n_heads (zeroed by the caller) are scratch.  direct: the records with route[r] == kPileupDirect.  sites: the site
+// records of the selected slots.  ref: rule 7's gather from an index (holes: the .amb holes, ascending, or none).
+constexpr int kPileupTile = 1024;        // positions of a tile: 12 channels x 1024 x 4 bytes = 48 KB of a workgroup's LDS
+constexpr int kPileupChannels = BWAMS_PILEUP_CHANNELS, kPileupN = BWAMS_PILEUP_N, kPileupDel = BWAMS_PILEUP_DEL, kPileupIns = BWAMS_PILEUP_INS;
+enum : uint8_t { kPileupSkip = 0, kPileupTiled = 1, kPileupDirect = 2 };
+struct PileupFilter {
+    uint32_t exclude;
+    int32_t min_mapq, n_ref;
+};
+struct PileupRegions {                   // device arrays: region k is [beg[k], end[k]) from slot off[k]; reference r's regions are [ref_first[r], ref_first[r + 1])
+    const int32_t *beg, *end, *ref_first;
+    const int64_t *off;
+};
+struct PileupSiteTest {                  // rule 8 at slot s: the candidate alleles' bits (0 = no site) and the depth
+    const uint32_t *counts;
+    const uint8_t *ref;
+    uint32_t min_alt, min_permille;
+    __host__ __device__ uint32_t kinds(int64_t s, uint32_t *depth) const {
+        const uint32_t *c = counts + s * kPileupChannels;
+        const uint32_t b = ref[s];
+        uint64_t d = c[kPileupDel];
+        for (int k = 0; k < 8; ++k) d += c[k];
+        *depth = (uint32_t)d;
+        if (b > 3) return 0;
+        uint32_t out = 0;
+        for (uint32_t a = 0; a < 6; ++a) {
+            const uint64_t n = a < 4 ? (uint64_t)c[a] + c[a + 4] : c[kPileupDel + (a - 4)];
+            if (a != b && n >= min_alt && n * 1000 >= (uint64_t)min_permille * d) out |= 1u << a;
+        }
+        return out;
+    }
+    __host__ __device__ bool operator()(int64_t s) const { uint32_t d; return kinds(s, &d) != 0; }
+};
+void launch_pileup_check(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, unsigned long long *bad,
+                         int cu_count, hipStream_t st);
+void launch_pileup_route(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, const PileupRegions &R,
+                         uint32_t n_tiles, int tiled, uint32_t *keys, uint32_t *vals, uint8_t *route, unsigned long long *counts,
+                         int cu_count, hipStream_t st);
+void launch_pileup_tiles(const uint8_t *bam, const int64_t *rec_off, const PileupRegions &R, int min_baseq, const uint32_t *keys,
+                         const uint32_t *vals, int64_t n_ent, uint32_t n_tiles, uint32_t *heads, uint32_t *n_heads, int64_t n_slots,
+                         uint32_t *counts, int cu_count, hipStream_t st);
+void launch_pileup_direct(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupRegions &R, int min_baseq,
+                          const uint8_t *route, uint32_t *counts, int cu_count, hipStream_t st);
+void launch_pileup_sites(const PileupSiteTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *slots, int64_t n,
+                         bwams_pileup_site_t *out, int cu_count, hipStream_t st);
+void launch_pileup_ref(const PileupRegions &R, int32_t n_regions, const int32_t *reg_ref, int64_t n_slots, const uint8_t *ref0123,
+                       const bwams_contig_t *contigs, const int64_t *hole_off, const int32_t *hole_len, int32_t n_holes, uint8_t *out,
+                       int cu_count, hipStream_t st);
 
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);

@@ -23,9 +23,9 @@
 // After bwams_sorter_set_markdup a put_batch runs bwams_bam_templates2 with the sorter's copy of the groups table and also keeps the
 // put's bwams_dup_loc_t per end and its two record-level counts per library; close3 hands ends and locs to bwams_dup_decide2 and adds
 // the puts' record-level counts to its rows.
-// After bwams_sorter_set_depth close also hands the merged stream, as written, to the depth handle: every flushed piece goes to
-// bwams_depth_add_records in whole records; the bytes of a record that the piece's end cuts wait in a carry buffer for the next piece, so
-// the record is added once, with its final flag, wherever the pieces cut.
+// After bwams_sorter_set_depth and / or bwams_sorter_set_pileup close also hands the merged stream, as written, to those handles: every
+// flushed piece goes to bwams_depth_add_records and bwams_pileup_add_records in whole records; the bytes of a record that the piece's
+// end cuts wait in a carry buffer for the next piece, so the record is added once, with its final flag, wherever the pieces cut.
 // Plain C++ over the C-ABI (no HIP header), like fastq_io.cpp.
 #include <fcntl.h>
 #include <unistd.h>
@@ -44,6 +44,7 @@
 
 #include "bwams.h"
 #include "depth_host.h"
+#include "pileup_host.h"
 #include "dup_groups.h"
 
 namespace {
@@ -236,6 +237,7 @@ struct bwams_sorter {
     bwams_dup_groups groups;
     bwams_dup_opt_t opt{};
     bwams_depth_t *depth = nullptr;                   // bwams_sorter_set_depth: close adds the merged stream to it (the caller's handle)
+    bwams_pileup_t *pileup = nullptr;                 // bwams_sorter_set_pileup: the same
     int64_t n_lib() const { return has_groups ? (int64_t)groups.libs.size() : 1; }
 };
 
@@ -475,6 +477,23 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d) {
     return BWAMS_OK;
 }
 
+int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p) {
+    const char *why = !s || !p ? "a sorter and a pileup handle are required"
+                      : bwams::pileup_device(p) != s->device ? "the pileup handle is on another device than the sorter"
+                      : bwams::pileup_l_ref(p) != s->l_ref ? "the pileup handle's reference lengths are not the sorter header's" : nullptr;
+    if (why) {
+        bwams::set_last_error(std::string("bwams_sorter_set_pileup: ") + why);
+        return BWAMS_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->any_put) {
+        bwams::set_last_error("bwams_sorter_set_pileup: called after the sorter's first put");
+        return BWAMS_ERR_ARG;
+    }
+    s->pileup = p;
+    return BWAMS_OK;
+}
+
 int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats, bwams_dup_lib_stats_t *lib_stats,
                         int64_t cap_lib) {
     if (!s) return BWAMS_ERR_ARG;
@@ -556,25 +575,32 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         std::vector<uint8_t> gz((size_t)bwams_deflate_bound(kPiece));
         std::vector<int64_t> sizes;
         int64_t fill = 0, flushed = 0;                                           // bytes in buf, record-stream bytes flushed
-        // set_depth: the stream up to depth_at is added; whole_end is the end of the last record copied whole and open_end that of
-        // the record being copied; carry holds stream bytes [depth_at, flushed) of the record that the last piece's end cut
-        int64_t depth_at = 0, whole_end = 0, open_end = 0, carry_end = 0;
+        // set_depth, set_pileup: the stream up to fed_at is handed on; whole_end is the end of the last record copied whole and open_end
+        // that of the record being copied; carry holds stream bytes [fed_at, flushed) of the record that the last piece's end cut
+        int64_t fed_at = 0, whole_end = 0, open_end = 0, carry_end = 0;
         std::vector<uint8_t> carry;
-        auto depth_add = [&]() -> int {
-            if (whole_end > depth_at) {
-                int64_t from = depth_at;
+        auto consume = [&](const uint8_t *recs, int64_t n_bytes) -> int {        // whole records, to every consumer the sorter has
+            if (s->depth)
+                if (int e = bwams_depth_add_records(s->depth, recs, n_bytes, nullptr)) return e;
+            if (s->pileup)
+                if (int e = bwams_pileup_add_records(s->pileup, recs, n_bytes, nullptr)) return e;
+            return BWAMS_OK;
+        };
+        auto feed = [&]() -> int {
+            if (whole_end > fed_at) {
+                int64_t from = fed_at;
                 if (from < flushed) {                                            // the cut record ends in this piece
                     carry.insert(carry.end(), buf.data(), buf.data() + (carry_end - flushed));
-                    if (int e = bwams_depth_add_records(s->depth, carry.data(), (int64_t)carry.size(), nullptr)) return e;
+                    if (int e = consume(carry.data(), (int64_t)carry.size())) return e;
                     carry.clear();
                     from = carry_end;
                 }
                 if (whole_end > from)
-                    if (int e = bwams_depth_add_records(s->depth, buf.data() + (from - flushed), whole_end - from, nullptr)) return e;
-                depth_at = whole_end;
+                    if (int e = consume(buf.data() + (from - flushed), whole_end - from)) return e;
+                fed_at = whole_end;
             }
-            if (flushed + fill > depth_at) {                                     // the piece ends inside a record
-                const int64_t from = std::max(depth_at, flushed);
+            if (flushed + fill > fed_at) {                                       // the piece ends inside a record
+                const int64_t from = std::max(fed_at, flushed);
                 carry.insert(carry.end(), buf.data() + (from - flushed), buf.data() + fill);
                 carry_end = open_end;
             }
@@ -582,8 +608,8 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         };
         auto flush = [&]() -> int {
             if (fill == 0) return BWAMS_OK;
-            if (s->depth)
-                if (int e = depth_add()) return e;
+            if (s->depth || s->pileup)
+                if (int e = feed()) return e;
             Clock::time_point t0 = Clock::now();
             int64_t got = 0;
             if (int e = bwams_deflater_run(s->def, buf.data(), fill, 0, gz.data(), (int64_t)gz.size(), 0, 0, &got, nullptr)) return e;

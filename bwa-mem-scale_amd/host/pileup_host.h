@@ -1,0 +1,20 @@
+// pileup_host.h — what the pileup handle (csrc/api_pileup.hip) shares with plain host code: the text of rule 9 (host/pileup_text.cpp,
+// which also builds alone: tools/pileup_text_check.cpp) and what the sorted BAM writer asks of a handle.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "bwams.h"
+
+namespace bwams {
+
+// Rule 9's text of n_sites sites.  names: the references' NUL-terminated names back to back (n_ref of them); regions: the handle's list.
+int pileup_text_format(const char *names, int32_t n_ref, const bwams_pileup_region_t *regions, int32_t n_regions,
+                       const bwams_pileup_site_t *sites, int64_t n_sites, std::string *out);    // BWAMS_OK, or BWAMS_ERR_ARG for a site outside the lists
+
+int pileup_device(const bwams_pileup *p);
+const std::vector<int32_t> &pileup_l_ref(const bwams_pileup *p);
+
+}  // namespace bwams

@@ -56,6 +56,7 @@ const char *bwams_last_error(void);
  *   BWAMS_PAIR_COUNT=1   bwams_pair_run counts its reads per route and its sorts per path (bwams_debug_pair_counts)
  *   BWAMS_CHAIN_COUNT=1   bwams_chain_run / _run_ert count their reads per filter route and the passes of the wave tier (bwams_debug_chain_counts)
  *   BWAMS_DEPTH_COMBINE=0   the depth add issues one atomic per lane instead of folding equal slots inside a wave (tools/depth_rate.py)
+ *   BWAMS_PILEUP_TILED=0    every record of a pileup add goes through the direct kernel, one global atomic per base (tools/pileup_rate.py)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
 int bwams_device_count(int *n);
@@ -1176,6 +1177,92 @@ int bwams_depth_runs(bwams_depth_t *d, int32_t ref, int32_t beg, int32_t end, in
 int bwams_depth_fetch(bwams_depth_t *d, int32_t ref, int32_t beg, int32_t end, int32_t *depth);
 int bwams_depth_text(bwams_depth_t *d, const char *names, int32_t what, int32_t arg, char *out, int64_t cap, int64_t *n);
 int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
+/* Pileup (csrc/pileup.hip, csrc/api_pileup.hip, host/pileup_text.cpp): per-base allele counts of SEQ and QUAL against the reference,
+ * accumulated on the device from a batch's BAM records, from host records, or from the sorted BAM writer's merged stream, and the
+ * candidate variant sites they give.  The rules are this library's own, modelled on the defaults of `samtools mpileup`; no byte
+ * parity with it is claimed.  bwams/pileup.py restates them in numpy and is what the tests compare against.
+ *  1. Regions.  The handle is opened over n_ref reference lengths and a list of regions (ref, beg, end) with
+ *     0 <= beg < end <= l_ref[ref], sorted by (ref, beg) and not overlapping (touching regions are allowed); anything else is
+ *     BWAMS_ERR_ARG.  An empty list means one region per reference of length > 0.  Counters exist only for region positions,
+ *     concatenated in region order: a slot per position.  A slot holds 12 uint32 channels: A+ C+ G+ T+ A- C- G- T- (+ forward, - when
+ *     FLAG has 0x10), then N, DEL, INS, and one reserved channel that stays 0.  That is 48 bytes per position (a human chromosome is
+ *     12 GB), so a whole genome does not fit beside an index and regions are how a caller walks it.  When the counters do not fit,
+ *     the open returns BWAMS_ERR_NOMEM.
+ *  2. Which records count.  Depth rule 2's filter: (FLAG & exclude) == 0 (default 0x704), MAPQ >= min_mapq (default 0),
+ *     0 <= refID < n_ref and n_cigar_op > 0; in addition l_seq > 0 (a record with SEQ `*` is skipped).  A record that does not count
+ *     is skipped; it does not refuse the call.
+ *  3. Validity.  All records of a call are checked before anything is added.  An op code above 8 is BWAMS_ERR_ARG, whether the filter
+ *     would let the record through or not, as in depth rule 3.  A record that passes rule 2's filter whose CIGAR query length (the
+ *     lengths of M I S = X) differs from l_seq, or whose SEQ or QUAL ends behind the record's block_size, is BWAMS_ERR_ARG too.
+ *     bwams_last_error names the first such record (the op code when one record has both).  Nothing of that call is added.
+ *  4. The walk from POS.  M, = and X: each base adds 1 to the channel of its 4-bit SEQ code and strand; codes 1, 2, 4 and 8 are A, C,
+ *     G and T, every other code, 0 (`=`) included, goes to N, which has no strand.  A base counts only if its quality is >=
+ *     min_baseq (default 13); a record without qualities (first QUAL byte 0xFF) passes every min_baseq.  D adds 1 to DEL at each
+ *     deleted position, with no quality test.  N advances without counting.  Every I op adds 1 to INS at the position before the
+ *     insertion, whatever its length and quality, and only when a reference-consuming op (M D N = X, of any length) precedes it in
+ *     that record: an insertion that opens the alignment is not counted.  S advances the query only; H and P do nothing.
+ *     Positions outside every region, below 0, or at or past the reference's end are dropped one by one: a record may span
+ *     several regions and the gaps between them.  Only the CIGAR field counts (no CG tag).
+ *  5. No mate-overlap correction, as depth rule 4: where two mates overlap, both count.
+ *  6. Accumulation.  The counters hold the sum over all adds, in any order, over any number of calls, modulo 2^32.  More than
+ *     2^31 - 1 records given in total (counted or not) is BWAMS_ERR_UNSUPPORTED, and nothing of that call is added; nor is anything
+ *     when an allocation of the add fails (BWAMS_ERR_NOMEM).  After BWAMS_ERR_DEVICE the counters are undefined until _reset.
+ *     There is no finish step: a query sees everything added before it.  _reset zeroes the counters (the reference bases stay).
+ *  7. Reference bases: one code 0..4 per slot (0..3 = A C G T, 4 = N), all 4 before the first _set_ref*.  They come from host codes
+ *     for one region (_set_ref; a code above 4 is BWAMS_ERR_ARG), or from an opened index (_set_ref_index), which gathers the
+ *     forward strand of the index's .0123 bytes on the device by the contig table; BWAMS_ERR_ARG when the index has no .0123 or no
+ *     contigs, is on another device, or when its contig lengths differ from l_ref.  For an index made from FASTA
+ *     (bwams_index_from_fasta*) the .amb holes become 4.  For ANY OTHER index the bases that the index holds in place of N stay:
+ *     such an index does not know where its Ns were.
+ *  8. Candidate sites.  At a slot with reference base b < 4, depth is the sum of the eight base channels plus DEL (N and INS are not
+ *     part of it).  An allele is one of the three bases other than b (both strands summed), DEL, or INS.  An allele is a candidate
+ *     when its count >= min_alt (default 2) and count * 1000 >= min_permille * depth (default 200), in integer arithmetic.  A slot
+ *     with at least one candidate allele is a site; a slot whose reference base is 4 is none.  bwams_pileup_sites returns the sites
+ *     of all regions in slot order as bwams_pileup_site_t records (include/bwams_types.h): region, pos, ref, kinds (bits 0-3: A C G T as
+ *     alternate alleles, bit 4: DEL, bit 5: INS), depth, c[12].  The sites are found with rocprim::select, as the depth runs are.
+ *  9. Text (bwams_pileup_text; names: n_ref names, each ending in NUL, back to back).  A header line, then a tab-separated row per
+ *     site: chrom, 1-based position, ref letter (ACGTN), depth, the eleven live channels in rule 1's order, and the candidate alleles
+ *     separated by commas in the order of rule 8's bits (A C G T DEL INS).  Reference c1 = ACGTACGT, one region over it, seven records
+ *     of quality 30: 8M ACGTACGT at 0; 8M ACTTACGT at 0, once forward and once with FLAG 0x10; 2M1D2M GTCG at 2, twice;
+ *     2M2I2M ACTTGT at 4, twice:
+ *       "chrom\tpos\tref\tdepth\tA+\tC+\tG+\tT+\tA-\tC-\tG-\tT-\tN\tDEL\tINS\talt\n"
+ *       "c1\t3\tG\t5\t0\t0\t3\t1\t0\t0\t0\t1\t0\t0\t0\tT\n" "c1\t5\tA\t7\t4\t0\t0\t0\t1\t0\t0\t0\t0\t2\t0\tDEL\n"
+ *       "c1\t6\tC\t7\t0\t6\t0\t0\t0\t1\t0\t0\t0\t0\t2\tINS\n"
+ *     VCF, genotype likelihoods and quality-weighted counts are out of scope: the sites and their counters are the interface for a
+ *     caller that wants them.
+ * bwams_pileup_open: a zeroed handle on `device` (opt may be NULL for the defaults; exclude above 0xFFFF, min_baseq outside [0, 255],
+ * min_alt < 1, min_permille outside [0, 1000], reserved != 0, n_ref < 0, a negative length or rule 1: BWAMS_ERR_ARG).  _close (NULL
+ * allowed).  _add_batch: the batch's current BAM records (bwams_bam_run / _upload left them, BWAMS_ERR_ARG before either), read in
+ * HBM; the batch must be on the handle's device; after bwams_bam_markdup the records carry 0x400, so duplicates drop out by rule 2.
+ * _add_records: host records bam[0, n_bytes), uploaded; their block_size chain is checked as bwams_bam_upload checks it
+ * (BWAMS_ERR_ARG).  *n_counted (may be NULL): the records of this call that rule 2 let through.
+ * _set_ref: the region's end - beg codes.  _fetch: the counters of positions [beg, end) of the region's reference, inside the region,
+ * 12 per position: for tests and small ranges.  _sites: *n (may be NULL) the number of sites, found or needed; sites may be NULL to
+ * ask for it; cap too small: BWAMS_ERR_CAPACITY.  min_alt and min_permille: rule 8's thresholds for this query, a negative value
+ * for the handle's.  _text: rule 9 into out[0, cap); *n: the bytes written, or needed with BWAMS_ERR_CAPACITY, as bwams_sam_header.
+ * _info: the positions of a tile of the add (below), the handle's regions and slots, and of the last add the records counted, the
+ * (tile, record) entries, the records routed direct and the device time: a test and measurement hook, like bwams_debug_chain_counts.
+ * An add cuts the slots into tiles.  A record whose slots lie in one or two tiles is counted in LDS by the workgroup that owns
+ * the tile and the tile is added to HBM once; a record that touches more tiles (a long read, an N skip) goes to a kernel that issues
+ * a global atomic per base, and so does every record under BWAMS_PILEUP_TILED=0 (the A/B baseline; the counters are the same).
+ * bwams_sorter_set_pileup: the conditions and guarantees of bwams_sorter_set_depth: before the sorter's first put (BWAMS_ERR_ARG later,
+ * for a handle on another device, or when the handle's lengths differ from the sorter header's); the close adds every record of the
+ * merged stream AS WRITTEN, after the merge has set or cleared 0x400, in whole records (one cut by a deflate piece's end is counted
+ * once); the file and the index are byte for byte what they are without the call; an add that fails ends the close with its error.
+ * A sorter may have a depth handle, a pileup handle, or both: both see the same whole records. */
+int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwams_pileup_region_t *regions, int32_t n_regions,
+                      const bwams_pileup_opt_t *opt, bwams_pileup_t **out);
+int bwams_pileup_close(bwams_pileup_t *p);
+int bwams_pileup_reset(bwams_pileup_t *p);
+int bwams_pileup_add_batch(bwams_pileup_t *p, bwams_batch_t *b, int64_t *n_counted);
+int bwams_pileup_add_records(bwams_pileup_t *p, const void *bam, int64_t n_bytes, int64_t *n_counted);
+int bwams_pileup_set_ref(bwams_pileup_t *p, int32_t region, const uint8_t *codes);
+int bwams_pileup_set_ref_index(bwams_pileup_t *p, const bwams_index_t *ix);
+int bwams_pileup_fetch(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *counts);
+int bwams_pileup_sites(bwams_pileup_t *p, int32_t min_alt, int32_t min_permille, bwams_pileup_site_t *sites, int64_t cap, int64_t *n);
+int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int32_t min_permille, char *out, int64_t cap, int64_t *n);
+int bwams_pileup_info(const bwams_pileup_t *p, bwams_pileup_info_t *info);
+int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -315,6 +315,49 @@ typedef struct bwams_depth_ref {
     int32_t min, max;
 } bwams_depth_ref_t;
 
+/* Pileup (include/bwams.h, "Pileup").  A pileup handle lives on one device. */
+typedef struct bwams_pileup bwams_pileup_t;
+
+/* Rule 1: positions [beg, end) of reference `ref`. */
+typedef struct bwams_pileup_region {
+    int32_t ref, beg, end;
+} bwams_pileup_region_t;
+
+/* Rule 2's filter, rule 4's base quality and rule 8's thresholds.  reserved must be 0.  A NULL pointer means
+ * {0x704, 0, 13, 2, 200, 0}. */
+typedef struct bwams_pileup_opt {
+    uint32_t exclude;
+    int32_t  min_mapq;
+    int32_t  min_baseq;          /* 0..255 */
+    int32_t  min_alt;            /* >= 1 */
+    int32_t  min_permille;       /* 0..1000 */
+    int32_t  reserved;
+} bwams_pileup_opt_t;
+
+/* The channels of a slot (rule 1), as indices into its 12 counters. */
+#define BWAMS_PILEUP_CHANNELS 12
+#define BWAMS_PILEUP_N   8
+#define BWAMS_PILEUP_DEL 9
+#define BWAMS_PILEUP_INS 10
+
+/* One candidate site (rule 8): the region's index in the handle's list, the position on the region's reference, the reference
+ * base (0..3), the candidate alleles (bits 0-3: A C G T, bit 4: DEL, bit 5: INS), rule 8's depth and the slot's counters. */
+typedef struct bwams_pileup_site {
+    int32_t  region, pos, ref;
+    uint32_t kinds, depth;
+    uint32_t c[BWAMS_PILEUP_CHANNELS];
+} bwams_pileup_site_t;
+
+/* bwams_pileup_info: the tile of the tiled path in positions, the handle's slots, and of the last add the records rule 2 let
+ * through, the (tile, record) entries of the tiled path and the records that went to the direct kernel.  ms_check and ms_add are
+ * for measurement only (tools/pileup_rate.py), nothing a caller should build on: the device time between events around rule 3's
+ * check and around everything from the routing to the last counter update. */
+typedef struct bwams_pileup_info {
+    int32_t tile, n_regions;
+    int64_t n_slots, n_counted, n_entries, n_direct;
+    float   ms_check, ms_add;
+} bwams_pileup_info_t;
+
 #ifdef __cplusplus
 }
 #endif
