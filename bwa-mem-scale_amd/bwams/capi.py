@@ -64,6 +64,8 @@ SYMBOLS = [
     "bwams_sorter_set_depth",
     "bwams_pileup_open", "bwams_pileup_close", "bwams_pileup_reset", "bwams_pileup_add_batch", "bwams_pileup_add_records", "bwams_pileup_set_ref",
     "bwams_pileup_set_ref_index", "bwams_pileup_fetch", "bwams_pileup_sites", "bwams_pileup_text", "bwams_pileup_info", "bwams_sorter_set_pileup",
+    "bwams_qc_open", "bwams_qc_close", "bwams_qc_reset", "bwams_qc_add_batch", "bwams_qc_add_records", "bwams_qc_summary", "bwams_qc_table",
+    "bwams_qc_text", "bwams_qc_info", "bwams_sorter_set_qc",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -485,6 +487,10 @@ class Sorter:
         """bwams_sorter_set_pileup: close adds the merged stream, as written, to the handle; before the first put."""
         _chk(lib().bwams_sorter_set_pileup(self.h, pileup.h), "bwams_sorter_set_pileup")
 
+    def set_qc(self, qc: "Qc") -> None:
+        """bwams_sorter_set_qc: close adds the merged stream, as written, to the handle; before the first put."""
+        _chk(lib().bwams_sorter_set_qc(self.h, qc.h), "bwams_sorter_set_qc")
+
     def close3(self) -> SorterStats:
         """bwams_sorter_close3: close()'s stats, .dup, and rule 13's rows as .lib (DUP_LIB_STATS_DTYPE)."""
         st, dup = SorterStats(), DupStats()
@@ -691,6 +697,85 @@ class Pileup:
         h, self.h = self.h, C.c_void_p()
         if h:
             _chk(lib().bwams_pileup_close(h), "bwams_pileup_close")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class QcOpt(C.Structure):
+    _fields_ = [("exclude", C.c_uint32), ("max_cycle", C.c_int32), ("max_isize", C.c_int32), ("reserved", C.c_int32)]
+
+
+class QcSummary(C.Structure):
+    _fields_ = [("flags", C.c_int64 * 16 * 2), ("scalars", C.c_int64 * 16)]
+
+
+class QcInfo(C.Structure):
+    _fields_ = [("isize_lds", C.c_int32), ("slice", C.c_int32), ("n_records", C.c_int64), ("n_counted", C.c_int64),
+                ("bases_over", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
+
+
+class Qc:
+    """Alignment QC on one GPU (bwams_qc_t): flag counts, insert sizes and per-cycle tables; add, then query at any time."""
+
+    def __init__(self, device: int = 0, exclude: int = 0x900, max_cycle: int = 512, max_isize: int = 8000):
+        self.h = C.c_void_p()
+        self.max_cycle, self.max_isize = max_cycle, max_isize
+        o = QcOpt(exclude, max_cycle, max_isize, 0)
+        _chk(lib().bwams_qc_open(device, C.byref(o), C.byref(self.h)), "bwams_qc_open")
+
+    def add_batch(self, batch: "Batch") -> int:
+        """The batch's current BAM records, read in HBM; -> the records that rule 3's filter let through."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_qc_add_batch(self.h, batch.h, C.byref(n)), "bwams_qc_add_batch")
+        return n.value
+
+    def add_records(self, records: bytes) -> int:
+        records = bytes(records)
+        n = C.c_int64(0)
+        _chk(lib().bwams_qc_add_records(self.h, records, len(records), C.byref(n)), "bwams_qc_add_records")
+        return n.value
+
+    def reset(self) -> None:
+        _chk(lib().bwams_qc_reset(self.h), "bwams_qc_reset")
+
+    def summary(self):
+        """(flags int64[2, 16], scalars int64[16]) of rules 2 and 5"""
+        s = QcSummary()
+        _chk(lib().bwams_qc_summary(self.h, C.byref(s)), "bwams_qc_summary")
+        return np.array(s.flags, np.int64).reshape(2, 16), np.array(s.scalars, np.int64)
+
+    def table(self, what: int) -> np.ndarray:
+        """int64, flat: table `what` of rule 4 (0 RL, 1 QUAL, 2 BASE, 3 MAPQ, 4 ISIZE, 5 INDEL)"""
+        n = C.c_int64(0)
+        _chk(lib().bwams_qc_table(self.h, what, None, 0, C.byref(n)), "bwams_qc_table")
+        out = np.zeros(n.value, np.int64)
+        _chk(lib().bwams_qc_table(self.h, what, _p(out), len(out), C.byref(n)), "bwams_qc_table")
+        return out
+
+    def text(self, what: int) -> str:
+        """bwams_qc_text: what = 0 the flagstat lines, 1 the stats sections."""
+        n = C.c_int64(0)
+        rc = lib().bwams_qc_text(self.h, what, None, 0, C.byref(n))
+        if rc != -4:
+            _chk(rc, "bwams_qc_text")
+        buf = C.create_string_buffer(max(n.value, 1))
+        _chk(lib().bwams_qc_text(self.h, what, buf, n.value, C.byref(n)), "bwams_qc_text")
+        return buf.raw[:n.value].decode("latin-1")
+
+    def info(self) -> dict:
+        """bwams_qc_info: isize_lds, slice, and of the last add n_records, n_counted, bases_over, ms_check, ms_add."""
+        i = QcInfo()
+        _chk(lib().bwams_qc_info(self.h, C.byref(i)), "bwams_qc_info")
+        return {k: getattr(i, k) for k, _ in QcInfo._fields_}
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_qc_close(h), "bwams_qc_close")
 
     def __del__(self):
         try:
@@ -991,6 +1076,16 @@ def lib():
         L.bwams_pileup_text.argtypes = [vp, vp, i32, i32, vp, i64, vp]
         L.bwams_pileup_info.argtypes = [vp, vp]
         L.bwams_sorter_set_pileup.argtypes = [vp, vp]
+        L.bwams_qc_open.argtypes = [C.c_int, vp, vp]
+        L.bwams_qc_close.argtypes = [vp]
+        L.bwams_qc_reset.argtypes = [vp]
+        L.bwams_qc_add_batch.argtypes = [vp, vp, vp]
+        L.bwams_qc_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_qc_summary.argtypes = [vp, vp]
+        L.bwams_qc_table.argtypes = [vp, i32, vp, i64, vp]
+        L.bwams_qc_text.argtypes = [vp, i32, vp, i64, vp]
+        L.bwams_qc_info.argtypes = [vp, vp]
+        L.bwams_sorter_set_qc.argtypes = [vp, vp]
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]

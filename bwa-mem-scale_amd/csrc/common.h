@@ -41,6 +41,7 @@ struct Knobs {
     int ert_fat = 1;               // BWAMS_ERT_FAT=0: the ERT walk reads the reference's two tables only (no entry + tree-head table)
     int depth_combine = 1;         // BWAMS_DEPTH_COMBINE=0: the depth add issues one atomic per lane (no folding of equal slots inside a wave)
     int pileup_tiled = 1;          // BWAMS_PILEUP_TILED=0: every record of a pileup add goes through the direct kernel (one global atomic per base)
+    int qc_lanes = 1;              // BWAMS_QC_LANES=0: the QC add's per-cycle tables come from the plain kernel (one global atomic per base and per quality)
     int ert_grid = -1, ert_ticket = 1;   // BWAMS_ERT_GRID (blocks per CU, 0 = one block per 256 bases) / BWAMS_ERT_TICKET=0 (round robin)
 };
 const Knobs &knobs();
@@ -340,6 +341,35 @@ void launch_pileup_sites(const PileupSiteTest &test, const PileupRegions &R, int
 void launch_pileup_ref(const PileupRegions &R, int32_t n_regions, const int32_t *reg_ref, int64_t n_slots, const uint8_t *ref0123,
                        const bwams_contig_t *contigs, const int64_t *hole_off, const int32_t *hole_len, int32_t n_holes, uint8_t *out,
                        int cu_count, hipStream_t st);
+
+// qc.hip: alignment QC (rules in include/bwams.h above bwams_qc_open).  All counters are one block of 64-bit words in HBM, laid out by
+// QcLayout: the flag counters, the scalars, then rule 4's six tables.  check: *bad = min(*bad, record << 3 | reason).  records: rules
+// 2-5 but tables b and c; lists[c * n_rec ..] gets the indices of class c's filtered-in records with l_seq > 0 and call[] (zeroed by
+// the caller) the two list lengths, the two largest l_seq, the records counted and the bases past max_cycle.  cycles: tables b and c
+// and the two quality scalars from the lists, by the lane-per-cycle kernel or (lanes == 0) the plain one.
+constexpr int kQcIsizeLds = 1024;        // ISIZE bins of a row counted in LDS by the record kernel; the bins from here on go by global atomics
+constexpr int kQcSlice = 1024;           // records of a list that one wave of the cycle kernel takes at a time
+enum { kQcBadBounds = 0, kQcBadOp = 1, kQcBadSeq = 2, kQcBadAux = 3 };
+enum { kQcCallList = 0, kQcCallMaxLen = 2, kQcCallCounted = 4, kQcCallOver = 5, kQcCallWords = 8 };
+struct QcLayout {                        // offsets in 64-bit words
+    int32_t max_cycle, max_isize;
+    uint32_t exclude;
+    __host__ __device__ int64_t flags() const { return 0; }
+    __host__ __device__ int64_t scalars() const { return 32; }
+    __host__ __device__ int64_t rl() const { return 48; }
+    __host__ __device__ int64_t qual() const { return rl() + 2 * ((int64_t)max_cycle + 1); }
+    __host__ __device__ int64_t base() const { return qual() + 2 * (int64_t)max_cycle * 64; }
+    __host__ __device__ int64_t mapq() const { return base() + 2 * (int64_t)max_cycle * 5; }
+    __host__ __device__ int64_t isize() const { return mapq() + 256; }
+    __host__ __device__ int64_t indel() const { return isize() + 3 * ((int64_t)max_isize + 1); }
+    __host__ __device__ int64_t words() const { return indel() + 2 * 65; }
+};
+void launch_qc_check(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, uint32_t exclude, unsigned long long *bad, int cu_count,
+                     hipStream_t st);
+void launch_qc_records(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const QcLayout &L, unsigned long long *counters,
+                       uint32_t *lists, unsigned long long *call, int cu_count, hipStream_t st);
+void launch_qc_cycles(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const QcLayout &L, unsigned long long *counters,
+                      const uint32_t *lists, const unsigned long long *call, int lanes, int cu_count, hipStream_t st);
 
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);

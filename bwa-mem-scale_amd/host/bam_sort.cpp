@@ -23,8 +23,8 @@
 // After bwams_sorter_set_markdup a put_batch runs bwams_bam_templates2 with the sorter's copy of the groups table and also keeps the
 // put's bwams_dup_loc_t per end and its two record-level counts per library; close3 hands ends and locs to bwams_dup_decide2 and adds
 // the puts' record-level counts to its rows.
-// After bwams_sorter_set_depth and / or bwams_sorter_set_pileup close also hands the merged stream, as written, to those handles: every
-// flushed piece goes to bwams_depth_add_records and bwams_pileup_add_records in whole records; the bytes of a record that the piece's
+// After bwams_sorter_set_depth, bwams_sorter_set_pileup and / or bwams_sorter_set_qc close also hands the merged stream, as written, to those
+// handles: every flushed piece goes to bwams_depth_add_records, bwams_pileup_add_records and bwams_qc_add_records in whole records; the bytes of a record that the piece's
 // end cuts wait in a carry buffer for the next piece, so the record is added once, with its final flag, wherever the pieces cut.
 // Plain C++ over the C-ABI (no HIP header), like fastq_io.cpp.
 #include <fcntl.h>
@@ -45,6 +45,7 @@
 #include "bwams.h"
 #include "depth_host.h"
 #include "pileup_host.h"
+#include "qc_host.h"
 #include "dup_groups.h"
 
 namespace {
@@ -238,6 +239,7 @@ struct bwams_sorter {
     bwams_dup_opt_t opt{};
     bwams_depth_t *depth = nullptr;                   // bwams_sorter_set_depth: close adds the merged stream to it (the caller's handle)
     bwams_pileup_t *pileup = nullptr;                 // bwams_sorter_set_pileup: the same
+    bwams_qc_t *qc = nullptr;                         // bwams_sorter_set_qc: the same
     int64_t n_lib() const { return has_groups ? (int64_t)groups.libs.size() : 1; }
 };
 
@@ -494,6 +496,22 @@ int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p) {
     return BWAMS_OK;
 }
 
+int bwams_sorter_set_qc(bwams_sorter_t *s, bwams_qc_t *q) {
+    const char *why = !s || !q ? "a sorter and a QC handle are required"
+                      : bwams::qc_device(q) != s->device ? "the QC handle is on another device than the sorter" : nullptr;
+    if (why) {
+        bwams::set_last_error(std::string("bwams_sorter_set_qc: ") + why);
+        return BWAMS_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->any_put) {
+        bwams::set_last_error("bwams_sorter_set_qc: called after the sorter's first put");
+        return BWAMS_ERR_ARG;
+    }
+    s->qc = q;
+    return BWAMS_OK;
+}
+
 int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats, bwams_dup_lib_stats_t *lib_stats,
                         int64_t cap_lib) {
     if (!s) return BWAMS_ERR_ARG;
@@ -575,7 +593,7 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         std::vector<uint8_t> gz((size_t)bwams_deflate_bound(kPiece));
         std::vector<int64_t> sizes;
         int64_t fill = 0, flushed = 0;                                           // bytes in buf, record-stream bytes flushed
-        // set_depth, set_pileup: the stream up to fed_at is handed on; whole_end is the end of the last record copied whole and open_end
+        // set_depth, set_pileup, set_qc: the stream up to fed_at is handed on; whole_end is the end of the last record copied whole and open_end
         // that of the record being copied; carry holds stream bytes [fed_at, flushed) of the record that the last piece's end cut
         int64_t fed_at = 0, whole_end = 0, open_end = 0, carry_end = 0;
         std::vector<uint8_t> carry;
@@ -584,6 +602,8 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
                 if (int e = bwams_depth_add_records(s->depth, recs, n_bytes, nullptr)) return e;
             if (s->pileup)
                 if (int e = bwams_pileup_add_records(s->pileup, recs, n_bytes, nullptr)) return e;
+            if (s->qc)
+                if (int e = bwams_qc_add_records(s->qc, recs, n_bytes, nullptr)) return e;
             return BWAMS_OK;
         };
         auto feed = [&]() -> int {
@@ -608,7 +628,7 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         };
         auto flush = [&]() -> int {
             if (fill == 0) return BWAMS_OK;
-            if (s->depth || s->pileup)
+            if (s->depth || s->pileup || s->qc)
                 if (int e = feed()) return e;
             Clock::time_point t0 = Clock::now();
             int64_t got = 0;

@@ -57,6 +57,7 @@ const char *bwams_last_error(void);
  *   BWAMS_CHAIN_COUNT=1   bwams_chain_run / _run_ert count their reads per filter route and the passes of the wave tier (bwams_debug_chain_counts)
  *   BWAMS_DEPTH_COMBINE=0   the depth add issues one atomic per lane instead of folding equal slots inside a wave (tools/depth_rate.py)
  *   BWAMS_PILEUP_TILED=0    every record of a pileup add goes through the direct kernel, one global atomic per base (tools/pileup_rate.py)
+ *   BWAMS_QC_LANES=0        the QC add's per-cycle tables come from the plain kernel, one global atomic per base and per quality (tools/qc_rate.py)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
 int bwams_device_count(int *n);
@@ -1263,6 +1264,121 @@ int bwams_pileup_sites(bwams_pileup_t *p, int32_t min_alt, int32_t min_permille,
 int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int32_t min_permille, char *out, int64_t cap, int64_t *n);
 int bwams_pileup_info(const bwams_pileup_t *p, bwams_pileup_info_t *info);
 int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p);
+/* Alignment QC (csrc/qc.hip, csrc/api_qc.hip, host/qc_text.cpp): the flag counts, insert sizes and per-cycle tables that a pipeline
+ * reads off a finished BAM, accumulated on the device from a batch's BAM records, from host records, or from the sorted BAM
+ * writer's merged stream.  Every value is an integer count.  The rules are this library's own, modelled on `samtools flagstat` and
+ * `samtools stats`; no byte parity with either is claimed.  bwams/qc.py restates them in numpy and is what the tests compare against.
+ *  1. Validity.  All records of a call are checked before anything is added.  For ANY record, whether rule 3's filter would count it
+ *     or not: l_seq < 0, or a CIGAR that ends behind the record's block_size (`bounds`); a CIGAR op code above 8 (`op`, as depth
+ *     rule 3).  For a record that passes rule 3's filter: SEQ or QUAL ending behind the record (`bounds`).  For a record that passes
+ *     the filter and is mapped (no 0x4): an aux area that cannot be walked (`aux`): a field whose type byte is not one of
+ *     A c C s S i I f Z H B, a B field whose subtype is not one of c C s S i I f, a field that runs past the record, or a Z or H field
+ *     with no NUL inside the record.  Any of these makes the call BWAMS_ERR_ARG; bwams_last_error names the first such record and
+ *     the reason; within one record the order is CIGAR bounds, op, SEQ / QUAL bounds, aux.  Nothing of the call is added.
+ *  2. Flag counters.  Every record is counted, with no filter, in class 0, or in class 1 when FLAG has 0x200 (QC-fail).  Sixteen per
+ *     class, in the order of the BWAMS_QC_FLAG_* indices: total; primary (neither 0x100 nor 0x800); secondary (0x100); supplementary
+ *     (0x800 without 0x100); duplicates (0x400); primary_duplicates; mapped (not 0x4); primary_mapped; and over PRIMARY records with
+ *     0x1: paired; read1 (0x40); read2 (0x80); properly_paired (0x2 and not 0x4); both_mapped (neither 0x4 nor 0x8); singletons (0x8
+ *     and not 0x4); mate_other_ref (both mapped and next_refID != refID); mate_other_ref_mapq5 (the same with MAPQ >= 5).
+ *  3. Filter.  Every table and scalar below takes only records with (FLAG & exclude) == 0; the default exclude, 0x900, counts each
+ *     read once.  A record's class is 1 when FLAG has 0x80 (last fragment), otherwise 0.  Cycles are numbered in the read's original
+ *     direction: for a record with 0x10, base i is cycle l_seq - 1 - i and the base is complemented.  Cycles at or past max_cycle are
+ *     dropped from tables b and c and counted in bases_over (once per base).
+ *  4. Tables, each a flat int64 array of the shape given (bwams_qc_table's `what`):
+ *     a. BWAMS_QC_TABLE_RL    [2][max_cycle + 1]: 1 at min(l_seq, max_cycle).
+ *     b. BWAMS_QC_TABLE_QUAL  [2][max_cycle][64]: 1 per base at min(quality, 63).  A record whose first QUAL byte is 0xFF adds nothing
+ *        here and, when l_seq > 0, 1 to no_qual.
+ *     c. BWAMS_QC_TABLE_BASE  [2][max_cycle][5]: A C G T N; the SEQ codes 1, 2, 4 and 8 are the bases, every other code is N.
+ *     d. BWAMS_QC_TABLE_MAPQ  [256]: over mapped records (not 0x4).
+ *     e. BWAMS_QC_TABLE_ISIZE [3][max_isize + 1], the rows inward, outward, other: over records with 0x1 and neither 0x4 nor 0x8, with
+ *        refID == next_refID >= 0 and TLEN > 0 (which counts a pair once); 1 at min(TLEN, max_isize).  The row is `other` when 0x10
+ *        and 0x20 are both set or both clear; otherwise, with POS <= next_pos, inward for a forward record and outward for a reverse
+ *        one, and with POS > next_pos the other way round.
+ *     f. BWAMS_QC_TABLE_INDEL [2][65], insertions then deletions: over mapped records, every I or D op of length n >= 1 adds 1 at
+ *        min(n, 64).
+ *  5. Scalars (the BWAMS_QC_* indices of bwams_qc_summary_t.scalars), under the same filter, every sum exact: reads; bases (the sum of
+ *     l_seq); mapped; bases_mapped (the lengths of M I = X ops of mapped records); clipped (the lengths of S ops of mapped records);
+ *     nm_sum and nm_missing over mapped records: NM is the first aux field tagged NM of type c C s S i or I with a value >= 0, and a
+ *     record with no such field adds 1 to nm_missing; qual_sum (unclamped) and qual_bases over the bases table b takes; bases_over;
+ *     no_qual.  The rest are reserved and stay 0.
+ *  6. Accumulation.  64-bit counters in HBM, summed over any number of adds in any order; more than 2^31 - 1 records in ONE call is
+ *     BWAMS_ERR_UNSUPPORTED with nothing added.  There is no finish step: a query sees everything added before it.  _reset zeroes.
+ *  7. Text (bwams_qc_text).  A ratio a / b below is (double)a / (double)b.
+ *     BWAMS_QC_TEXT_FLAGSTAT: sixteen lines "<class 0> + <class 1> <label>\n" in rule 2's order; a percentage is 100.0 * a / b printed
+ *       with %.2f%%, or N/A when b is 0: mapped over total, primary mapped over primary, properly paired and singletons over paired.
+ *       The example below:
+ *         "9 + 1 in total (QC-passed reads + QC-failed reads)\n" "8 + 1 primary\n" "0 + 0 secondary\n" "1 + 0 supplementary\n"
+ *         "0 + 1 duplicates\n" "0 + 1 primary duplicates\n" "8 + 1 mapped (88.89% : 100.00%)\n"
+ *         "7 + 1 primary mapped (87.50% : 100.00%)\n" "8 + 0 paired in sequencing\n" "5 + 0 read1\n" "3 + 0 read2\n"
+ *         "2 + 0 properly paired (25.00% : N/A)\n" "6 + 0 with itself and mate mapped\n" "1 + 0 singletons (12.50% : N/A)\n"
+ *         "2 + 0 with mate mapped to a different chr\n" "1 + 0 with mate mapped to a different chr (mapQ>=5)\n"
+ *     BWAMS_QC_TEXT_STATS: tab-separated lines, each tagged in its first column, in this order:
+ *       SN <name> <value>: the eleven scalars under rule 5's names, then error_rate = nm_sum / bases_mapped with %.6e (0 with no
+ *         mapped bases), average_quality = qual_sum / qual_bases with %.1f (0 with none), and insert_size_n, _mean, _sd, _median over
+ *         the bins BELOW max_isize of all three rows together: n the count, S1 the sum of x * c and S2 of x * x * c as exact
+ *         integers; mean S1 / n with %.1f; sd sqrt((double)(n * S2 - S1 * S1)) / (double)n with %.1f, the numerator formed in
+ *         128-bit integers before the one conversion (they hold it for any n up to 2^40); median the smallest x whose cumulative count reaches (n + 1) / 2 (integer
+ *         division); with n = 0 the three print 0.
+ *       RL <length> <class 0> <class 1>: the occupied lengths.
+ *       FFQ <cycle, from 1> <64 counts>: class 0's table b, a row per cycle up to its last occupied one; LFQ: class 1's.
+ *       GCC <cycle, from 1> <A C G T N of class 0> <A C G T N of class 1>: a row per cycle up to the last occupied one of either.
+ *       MAPQ <mapq> <count>, IS <size> <inward> <outward> <other>, ID <length> <insertions> <deletions>: the occupied rows.
+ *     Example, with opt {0x900, 64, 100, 0}; each record is (FLAG, refID, POS, MAPQ, next_refID, next_pos, TLEN, CIGAR, SEQ, QUAL, NM),
+ *     `-` for QUAL meaning 0xFF bytes and for NM no such field:
+ *       (99,0,10,60,0,110,104,4M,ACGT,[30,30,20,10],0)      (147,0,110,60,0,10,-104,2M1I2M,ACGTA,[40,40,30,20,10],1)
+ *       (73,0,50,30,0,50,0,1S3M,NACG,[2,30,30,30],1)        (133,0,50,0,0,50,0,*,TTT,[10,10,10],-)
+ *       (2064,0,200,5,-1,-1,0,2M2D1M2H,ACG,[30,30,30],2)    (1536,0,5,0,-1,-1,0,3M,GGG,-,0)
+ *       (81,0,300,60,0,340,42,2M,CC,[30,70],-)              (97,0,400,4,1,7,0,2M,AT,[30,30],0)
+ *       (161,1,7,9,0,400,0,2M,GG,[30,30],0)                 (65,0,500,60,0,520,22,2M,AA,[30,30],0)
+ *     flags {9,8,0,1,0,0,8,7,8,5,3,2,6,1,2,1} and {1,1,0,0,1,1,1,1,0,...}; the STATS text (a row's 64 counts shortened here to its
+ *     occupied bins as bin:count; tests/test_qc.py holds the text in full):
+ *       "SN\treads\t9\n" "SN\tbases\t27\n" "SN\tmapped\t8\n" "SN\tbases_mapped\t23\n" "SN\tclipped\t1\n" "SN\tnm_sum\t2\n"
+ *       "SN\tnm_missing\t1\n" "SN\tqual_sum\t632\n" "SN\tqual_bases\t24\n" "SN\tbases_over\t0\n" "SN\tno_qual\t1\n"
+ *       "SN\terror_rate\t8.695652e-02\n" "SN\taverage_quality\t26.3\n" "SN\tinsert_size_n\t2\n" "SN\tinsert_size_mean\t32.0\n"
+ *       "SN\tinsert_size_sd\t10.0\n" "SN\tinsert_size_median\t22\n" "RL\t2\t3\t1\n" "RL\t3\t1\t1\n" "RL\t4\t2\t0\n" "RL\t5\t0\t1\n"
+ *       FFQ 1 {2:1 30:3 63:1}  2 {30:5}  3 {20:1 30:1}  4 {10:1 30:1}       LFQ 1 {10:2 30:1}  2 {10:1 20:1 30:1}  3 {10:1 30:1}  4 {40:1}  5 {40:1}
+ *       "GCC\t1\t3\t0\t2\t0\t1\t0\t0\t1\t2\t0\n" "GCC\t2\t2\t1\t2\t1\t0\t1\t0\t1\t1\t0\n" "GCC\t3\t0\t1\t2\t0\t0\t0\t1\t0\t1\t0\n"
+ *       "GCC\t4\t0\t0\t1\t1\t0\t0\t0\t1\t0\t0\n" "GCC\t5\t0\t0\t0\t0\t0\t0\t0\t0\t1\t0\n"
+ *       "MAPQ\t0\t1\n" "MAPQ\t4\t1\n" "MAPQ\t9\t1\n" "MAPQ\t30\t1\n" "MAPQ\t60\t4\n"
+ *       "IS\t22\t0\t0\t1\n" "IS\t42\t0\t1\t0\n" "IS\t100\t1\t0\t0\n" "ID\t1\t1\t0\n"
+ * bwams_qc_open: a zeroed handle on `device`; no reference lengths are needed; opt may be NULL for the defaults; max_cycle not a
+ * multiple of 64 in [64, 4096], max_isize outside [1, 2^20], exclude above 0xFFFF or reserved != 0: BWAMS_ERR_ARG.  _close (NULL
+ * allowed).  _add_batch: the batch's current BAM records (bwams_bam_run / _upload left them, BWAMS_ERR_ARG before either), read in
+ * HBM; the batch must be on the handle's device.  _add_records: host records bam[0, n_bytes), uploaded; their block_size chain is
+ * checked as bwams_bam_upload checks it (BWAMS_ERR_ARG).  *n_counted (may be NULL): the records of this call that rule 3's filter
+ * let through.  _summary: rules 2 and 5.  _table: `what` of rule 4 into out[0, cap); *n (may be NULL) the number of int64 values,
+ * written or needed; out may be NULL to ask for it; cap too small: BWAMS_ERR_CAPACITY.  _text: `what` of rule 7 into out[0, cap); *n:
+ * the bytes written, or needed with BWAMS_ERR_CAPACITY, as bwams_pileup_text.  _info: a test and measurement hook, like
+ * bwams_pileup_info (include/bwams_types.h).
+ * An add runs three kernels.  qc_check_kernel: a lane per record, rule 1.  qc_record_kernel: a lane per record reads the head, walks
+ * the CIGAR and the aux fields; the flag counters, MAPQ, INDEL, RL and the ISIZE bins below isize_lds are counted in LDS and flushed
+ * once per workgroup; it also lists the filtered-in records per class.  qc_cycle_kernel: tables b and c without an atomic per base:
+ * a wave owns a class, a block of 64 cycles and a slice of the class's list, a lane one cycle, whose 64 quality bins are a row of
+ * LDS that no other lane touches.  Under BWAMS_QC_LANES=0 a plain kernel takes the listed records instead, with one global atomic
+ * per base and per quality (the A/B baseline; the counters are the same).
+ * bwams_sorter_set_qc: the conditions and guarantees of bwams_sorter_set_depth, without the length check (the handle has no
+ * references): before the sorter's first put (BWAMS_ERR_ARG later, or for a handle on another device); the close adds every record of
+ * the merged stream AS WRITTEN, after the merge has set or cleared 0x400, in whole records (one cut by a deflate piece's end is
+ * counted once); the file and the index are byte for byte what they are without the call; an add that fails ends the close with its
+ * error.  A sorter may have any of the depth, pileup and QC handles, alone or together: all see the same whole records. */
+#define BWAMS_QC_TABLE_RL 0
+#define BWAMS_QC_TABLE_QUAL 1
+#define BWAMS_QC_TABLE_BASE 2
+#define BWAMS_QC_TABLE_MAPQ 3
+#define BWAMS_QC_TABLE_ISIZE 4
+#define BWAMS_QC_TABLE_INDEL 5
+#define BWAMS_QC_TEXT_FLAGSTAT 0
+#define BWAMS_QC_TEXT_STATS 1
+int bwams_qc_open(int device, const bwams_qc_opt_t *opt, bwams_qc_t **out);
+int bwams_qc_close(bwams_qc_t *q);
+int bwams_qc_reset(bwams_qc_t *q);
+int bwams_qc_add_batch(bwams_qc_t *q, bwams_batch_t *b, int64_t *n_counted);
+int bwams_qc_add_records(bwams_qc_t *q, const void *bam, int64_t n_bytes, int64_t *n_counted);
+int bwams_qc_summary(bwams_qc_t *q, bwams_qc_summary_t *out);
+int bwams_qc_table(bwams_qc_t *q, int32_t what, int64_t *out, int64_t cap, int64_t *n);
+int bwams_qc_text(bwams_qc_t *q, int32_t what, char *out, int64_t cap, int64_t *n);
+int bwams_qc_info(const bwams_qc_t *q, bwams_qc_info_t *info);
+int bwams_sorter_set_qc(bwams_sorter_t *s, bwams_qc_t *q);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

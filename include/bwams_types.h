@@ -358,6 +358,62 @@ typedef struct bwams_pileup_info {
     float   ms_check, ms_add;
 } bwams_pileup_info_t;
 
+/* Alignment QC (include/bwams.h, "Alignment QC").  A QC handle lives on one device. */
+typedef struct bwams_qc bwams_qc_t;
+
+/* Rule 3's filter and the sizes of rule 4's tables: max_cycle a multiple of 64 in [64, 4096], max_isize in [1, 2^20].  reserved must
+ * be 0.  A NULL pointer means {0x900, 512, 8000, 0}. */
+typedef struct bwams_qc_opt {
+    uint32_t exclude;
+    int32_t  max_cycle;
+    int32_t  max_isize;
+    int32_t  reserved;
+} bwams_qc_opt_t;
+
+/* Rule 2's counters as indices into flags[class], rule 5's as indices into scalars. */
+#define BWAMS_QC_FLAG_TOTAL 0
+#define BWAMS_QC_FLAG_PRIMARY 1
+#define BWAMS_QC_FLAG_SECONDARY 2
+#define BWAMS_QC_FLAG_SUPPLEMENTARY 3
+#define BWAMS_QC_FLAG_DUPLICATES 4
+#define BWAMS_QC_FLAG_PRIMARY_DUPLICATES 5
+#define BWAMS_QC_FLAG_MAPPED 6
+#define BWAMS_QC_FLAG_PRIMARY_MAPPED 7
+#define BWAMS_QC_FLAG_PAIRED 8
+#define BWAMS_QC_FLAG_READ1 9
+#define BWAMS_QC_FLAG_READ2 10
+#define BWAMS_QC_FLAG_PROPERLY_PAIRED 11
+#define BWAMS_QC_FLAG_BOTH_MAPPED 12
+#define BWAMS_QC_FLAG_SINGLETONS 13
+#define BWAMS_QC_FLAG_MATE_OTHER_REF 14
+#define BWAMS_QC_FLAG_MATE_OTHER_REF_MAPQ5 15
+#define BWAMS_QC_READS 0
+#define BWAMS_QC_BASES 1
+#define BWAMS_QC_MAPPED 2
+#define BWAMS_QC_BASES_MAPPED 3
+#define BWAMS_QC_CLIPPED 4
+#define BWAMS_QC_NM_SUM 5
+#define BWAMS_QC_NM_MISSING 6
+#define BWAMS_QC_QUAL_SUM 7
+#define BWAMS_QC_QUAL_BASES 8
+#define BWAMS_QC_BASES_OVER 9
+#define BWAMS_QC_NO_QUAL 10
+
+/* flags[0]: records without FLAG 0x200, flags[1]: with it (rule 2); scalars: rule 5, entries 11..15 stay 0. */
+typedef struct bwams_qc_summary {
+    int64_t flags[2][16];
+    int64_t scalars[16];
+} bwams_qc_summary_t;
+
+/* bwams_qc_info: the ISIZE bins of a row that the record kernel counts in LDS, the records of a slice of the cycle kernel, and of the
+ * last add the records given, the records rule 3's filter let through and the bases past max_cycle.  ms_check and ms_add are for
+ * measurement only (tools/qc_rate.py): the device time between events around rule 1's check and around the kernels that count. */
+typedef struct bwams_qc_info {
+    int32_t isize_lds, slice;
+    int64_t n_records, n_counted, bases_over;
+    float   ms_check, ms_add;
+} bwams_qc_info_t;
+
 #ifdef __cplusplus
 }
 #endif
