@@ -66,6 +66,9 @@ SYMBOLS = [
     "bwams_pileup_set_ref_index", "bwams_pileup_fetch", "bwams_pileup_sites", "bwams_pileup_text", "bwams_pileup_info", "bwams_sorter_set_pileup",
     "bwams_qc_open", "bwams_qc_close", "bwams_qc_reset", "bwams_qc_add_batch", "bwams_qc_add_records", "bwams_qc_summary", "bwams_qc_table",
     "bwams_qc_text", "bwams_qc_info", "bwams_sorter_set_qc",
+    "bwams_recal_open", "bwams_recal_close", "bwams_recal_reset", "bwams_recal_add_batch", "bwams_recal_add_records", "bwams_recal_set_ref",
+    "bwams_recal_set_ref_index", "bwams_recal_add_known", "bwams_recal_table", "bwams_recal_text", "bwams_recal_info",
+    "bwams_sorter_set_recal", "bwams_dup_groups_rg_id",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -385,6 +388,10 @@ class DupGroups:
         name = lib().bwams_dup_groups_library(self.h, k)
         return None if name is None else name.decode("latin-1")
 
+    def rg_id(self, k: int):
+        name = lib().bwams_dup_groups_rg_id(self.h, k)
+        return None if name is None else name.decode("latin-1")
+
     @property
     def libraries(self) -> list:
         return [self.library(k) for k in range(self.n_lib)]
@@ -490,6 +497,10 @@ class Sorter:
     def set_qc(self, qc: "Qc") -> None:
         """bwams_sorter_set_qc: close adds the merged stream, as written, to the handle; before the first put."""
         _chk(lib().bwams_sorter_set_qc(self.h, qc.h), "bwams_sorter_set_qc")
+
+    def set_recal(self, recal: "Recal") -> None:
+        """bwams_sorter_set_recal: close adds the merged stream, as written, to the handle; before the first put."""
+        _chk(lib().bwams_sorter_set_recal(self.h, recal.h), "bwams_sorter_set_recal")
 
     def close3(self) -> SorterStats:
         """bwams_sorter_close3: close()'s stats, .dup, and rule 13's rows as .lib (DUP_LIB_STATS_DTYPE)."""
@@ -776,6 +787,98 @@ class Qc:
         h, self.h = self.h, C.c_void_p()
         if h:
             _chk(lib().bwams_qc_close(h), "bwams_qc_close")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RecalOpt(C.Structure):
+    _fields_ = [("exclude", C.c_uint32), ("min_mapq", C.c_int32), ("min_baseq", C.c_int32), ("max_cycle", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RecalInfo(C.Structure):
+    _fields_ = [("lds", C.c_int32), ("slice", C.c_int32), ("n_records", C.c_int64), ("n_counted", C.c_int64), ("n_bases", C.c_int64),
+                ("store_bytes", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
+
+
+RECAL_SITE_DTYPE = np.dtype([("ref", "<i4"), ("beg", "<i4"), ("end", "<i4")])
+
+
+class Recal:
+    """Base recalibration tables on one GPU (bwams_recal_t): set the reference and the known sites, add, then query at any time."""
+
+    def __init__(self, l_ref, groups=None, device: int = 0, exclude: int = 0x704, min_mapq: int = 1, min_baseq: int = 6,
+                 max_cycle: int = 500):
+        self.h = C.c_void_p()
+        self.l_ref = np.ascontiguousarray(l_ref, np.int32)
+        self.groups = groups                                                             # a DupGroups or None; names the text's rows
+        self.n_rg, self.max_cycle = (groups.n_rg if groups is not None else 0), max_cycle
+        o = RecalOpt(exclude, min_mapq, min_baseq, max_cycle, 0)
+        _chk(lib().bwams_recal_open(device, _p(self.l_ref), len(self.l_ref), _groups_h(groups), C.byref(o), C.byref(self.h)),
+             "bwams_recal_open")
+
+    def add_batch(self, batch: "Batch") -> int:
+        """The batch's current BAM records, read in HBM; -> the records that rule 4 let through."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_add_batch(self.h, batch.h, C.byref(n)), "bwams_recal_add_batch")
+        return n.value
+
+    def add_records(self, records: bytes) -> int:
+        records = bytes(records)
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_add_records(self.h, records, len(records), C.byref(n)), "bwams_recal_add_records")
+        return n.value
+
+    def reset(self) -> None:
+        _chk(lib().bwams_recal_reset(self.h), "bwams_recal_reset")
+
+    def set_ref(self, ref: int, codes) -> None:
+        """The codes (0..4) of one whole reference."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert len(codes) == self.l_ref[ref]
+        _chk(lib().bwams_recal_set_ref(self.h, ref, _p(codes)), "bwams_recal_set_ref")
+
+    def set_ref_index(self, index: "Index") -> None:
+        _chk(lib().bwams_recal_set_ref_index(self.h, index.h), "bwams_recal_set_ref_index")
+
+    def add_known(self, sites) -> None:
+        """Intervals (ref, beg, end) of known variation."""
+        a = np.zeros(len(sites), RECAL_SITE_DTYPE)
+        for k, (r, b, e) in enumerate(sites):
+            a[k] = (r, b, e)
+        _chk(lib().bwams_recal_add_known(self.h, _p(a), len(a)), "bwams_recal_add_known")
+
+    def table(self, what: int) -> np.ndarray:
+        """int64 pairs (observations, errors) in the shape of rule 6: 0 RG, 1 QUAL, 2 CYCLE, 3 CONTEXT"""
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_table(self.h, what, None, 0, C.byref(n)), "bwams_recal_table")
+        out = np.zeros(n.value, np.int64)
+        _chk(lib().bwams_recal_table(self.h, what, _p(out), len(out), C.byref(n)), "bwams_recal_table")
+        shape = [(), (94,), (94, 2 * self.max_cycle + 1), (94, 16)][what]
+        return out.reshape((self.n_rg + 1,) + shape + (2,))
+
+    def text(self) -> str:
+        n = C.c_int64(0)
+        rc = lib().bwams_recal_text(self.h, _groups_h(self.groups), None, 0, C.byref(n))
+        if rc != -4:
+            _chk(rc, "bwams_recal_text")
+        buf = C.create_string_buffer(max(n.value, 1))
+        _chk(lib().bwams_recal_text(self.h, _groups_h(self.groups), buf, n.value, C.byref(n)), "bwams_recal_text")
+        return buf.raw[:n.value].decode("latin-1")
+
+    def info(self) -> dict:
+        """bwams_recal_info: lds, slice, store_bytes, and of the last add n_records, n_counted, n_bases, ms_check, ms_add."""
+        i = RecalInfo()
+        _chk(lib().bwams_recal_info(self.h, C.byref(i)), "bwams_recal_info")
+        return {k: getattr(i, k) for k, _ in RecalInfo._fields_}
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_recal_close(h), "bwams_recal_close")
 
     def __del__(self):
         try:
@@ -1086,6 +1189,20 @@ def lib():
         L.bwams_qc_text.argtypes = [vp, i32, vp, i64, vp]
         L.bwams_qc_info.argtypes = [vp, vp]
         L.bwams_sorter_set_qc.argtypes = [vp, vp]
+        L.bwams_recal_open.argtypes = [C.c_int, vp, i32, vp, vp, vp]
+        L.bwams_recal_close.argtypes = [vp]
+        L.bwams_recal_reset.argtypes = [vp]
+        L.bwams_recal_add_batch.argtypes = [vp, vp, vp]
+        L.bwams_recal_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_recal_set_ref.argtypes = [vp, i32, vp]
+        L.bwams_recal_set_ref_index.argtypes = [vp, vp]
+        L.bwams_recal_add_known.argtypes = [vp, vp, i64]
+        L.bwams_recal_table.argtypes = [vp, i32, vp, i64, vp]
+        L.bwams_recal_text.argtypes = [vp, vp, vp, i64, vp]
+        L.bwams_recal_info.argtypes = [vp, vp]
+        L.bwams_sorter_set_recal.argtypes = [vp, vp]
+        L.bwams_dup_groups_rg_id.argtypes = [vp, i64]
+        L.bwams_dup_groups_rg_id.restype = C.c_char_p
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]
         L.bwams_reg2aln_fetch.argtypes = [vp, vp, i64, vp, i64, vp, i64]
         L.bwams_debug_regs_upload.argtypes = [vp, vp, i64, vp, i64]

@@ -39,6 +39,7 @@ void knobs_reload() {
     k.depth_combine = env_int("BWAMS_DEPTH_COMBINE", 1);
     k.pileup_tiled = env_int("BWAMS_PILEUP_TILED", 1);
     k.qc_lanes = env_int("BWAMS_QC_LANES", 1);
+    k.recal_lds = env_int("BWAMS_RECAL_LDS", 1);
     k.ert_ticket = env_int("BWAMS_ERT_TICKET", 1); k.ert_grid = env_int("BWAMS_ERT_GRID", -1); k.ert_fat = env_int("BWAMS_ERT_FAT", 1);
     g_knobs = k;
 }

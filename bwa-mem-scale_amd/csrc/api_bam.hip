@@ -39,6 +39,32 @@ int bam_record_offsets(const char *who, const void *bam, int64_t n_bytes, std::v
     }
     return BWAMS_OK;
 }
+// The groups table as the device reads it (MdGroupsDev): IDs sorted by bytes, uploaded into the caller's buffers (g null: no table).
+int groups_upload(DevBuf<uint8_t> &g_ids, DevBuf<int64_t> &g_off, DevBuf<int32_t> &g_ord, DevBuf<int32_t> &g_lib,
+                  const bwams_dup_groups_t *g, MdGroupsDev *G, hipStream_t st) {
+    memset(G, 0, sizeof *G);
+    G->n_lib = 1;
+    if (!g) return BWAMS_OK;
+    const size_t n = g->ids.size();
+    std::vector<int32_t> ord(n);
+    for (size_t k = 0; k < n; ++k) ord[k] = (int32_t)k;
+    std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return g->ids[(size_t)a] < g->ids[(size_t)b]; });   // by unsigned bytes
+    std::vector<int64_t> off(n + 1, 0);
+    std::string ids;
+    for (size_t k = 0; k < n; ++k) { ids += g->ids[(size_t)ord[k]]; off[k + 1] = (int64_t)ids.size(); }
+    BWAMS_HIP(g_ids.ensure_n(ids.size() + 1)); BWAMS_HIP(g_off.ensure_n(n + 1));
+    BWAMS_HIP(g_ord.ensure_n(n + 1)); BWAMS_HIP(g_lib.ensure_n(n + 1));
+    if (!ids.empty()) BWAMS_HIP(hipMemcpyAsync(g_ids.p, ids.data(), ids.size(), hipMemcpyHostToDevice, st));
+    BWAMS_HIP(hipMemcpyAsync(g_off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n) {
+        BWAMS_HIP(hipMemcpyAsync(g_ord.p, ord.data(), n * 4, hipMemcpyHostToDevice, st));
+        BWAMS_HIP(hipMemcpyAsync(g_lib.p, g->rg_lib.data(), n * 4, hipMemcpyHostToDevice, st));
+    }
+    BWAMS_HIP(hipStreamSynchronize(st));                       // the host vectors above end here
+    G->ids = g_ids.p; G->id_off = g_off.p; G->id_ord = g_ord.p; G->rg_lib = g_lib.p;
+    G->n_rg = (int32_t)n; G->n_lib = (int32_t)g->libs.size(); G->walk = 1;
+    return BWAMS_OK;
+}
 }  // namespace bwams
 
 extern "C" {
@@ -390,28 +416,7 @@ int bwams_dup_decide2(int device, const bwams_dup_end_t *ends, const bwams_dup_l
 
 // the groups table as md_loc_kernel reads it: IDs sorted by bytes, uploaded into the stage's buffers (null: no table)
 static int groups_upload(StageState *s, const bwams_dup_groups_t *g, MdGroupsDev *G, hipStream_t st) {
-    memset(G, 0, sizeof *G);
-    G->n_lib = 1;
-    if (!g) return BWAMS_OK;
-    const size_t n = g->ids.size();
-    std::vector<int32_t> ord(n);
-    for (size_t k = 0; k < n; ++k) ord[k] = (int32_t)k;
-    std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return g->ids[(size_t)a] < g->ids[(size_t)b]; });   // by unsigned bytes
-    std::vector<int64_t> off(n + 1, 0);
-    std::string ids;
-    for (size_t k = 0; k < n; ++k) { ids += g->ids[(size_t)ord[k]]; off[k + 1] = (int64_t)ids.size(); }
-    BWAMS_HIP(s->md.g_ids.ensure_n(ids.size() + 1)); BWAMS_HIP(s->md.g_off.ensure_n(n + 1));
-    BWAMS_HIP(s->md.g_ord.ensure_n(n + 1)); BWAMS_HIP(s->md.g_lib.ensure_n(n + 1));
-    if (!ids.empty()) BWAMS_HIP(hipMemcpyAsync(s->md.g_ids.p, ids.data(), ids.size(), hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(s->md.g_off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (n) {
-        BWAMS_HIP(hipMemcpyAsync(s->md.g_ord.p, ord.data(), n * 4, hipMemcpyHostToDevice, st));
-        BWAMS_HIP(hipMemcpyAsync(s->md.g_lib.p, g->rg_lib.data(), n * 4, hipMemcpyHostToDevice, st));
-    }
-    BWAMS_HIP(hipStreamSynchronize(st));                       // the host vectors above end here
-    G->ids = s->md.g_ids.p; G->id_off = s->md.g_off.p; G->id_ord = s->md.g_ord.p; G->rg_lib = s->md.g_lib.p;
-    G->n_rg = (int32_t)n; G->n_lib = (int32_t)g->libs.size(); G->walk = 1;
-    return BWAMS_OK;
+    return bwams::groups_upload(s->md.g_ids, s->md.g_off, s->md.g_ord, s->md.g_lib, g, G, st);
 }
 
 int bwams_bam_templates2(bwams_batch_t *b, const bwams_dup_groups_t *groups, int64_t *n_templates, int64_t *n_ends) {

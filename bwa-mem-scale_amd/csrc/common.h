@@ -42,6 +42,7 @@ struct Knobs {
     int depth_combine = 1;         // BWAMS_DEPTH_COMBINE=0: the depth add issues one atomic per lane (no folding of equal slots inside a wave)
     int pileup_tiled = 1;          // BWAMS_PILEUP_TILED=0: every record of a pileup add goes through the direct kernel (one global atomic per base)
     int qc_lanes = 1;              // BWAMS_QC_LANES=0: the QC add's per-cycle tables come from the plain kernel (one global atomic per base and per quality)
+    int recal_lds = 1;             // BWAMS_RECAL_LDS=0: the recalibration add counts through the plain kernel (one global atomic per update)
     int ert_grid = -1, ert_ticket = 1;   // BWAMS_ERT_GRID (blocks per CU, 0 = one block per 256 bases) / BWAMS_ERT_TICKET=0 (round robin)
 };
 const Knobs &knobs();
@@ -370,6 +371,59 @@ void launch_qc_records(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec
                        uint32_t *lists, unsigned long long *call, int cu_count, hipStream_t st);
 void launch_qc_cycles(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const QcLayout &L, unsigned long long *counters,
                       const uint32_t *lists, const unsigned long long *call, int lanes, int cu_count, hipStream_t st);
+
+// api_bam.hip: the groups table as the device reads it, uploaded into the caller's buffers (g null: no table, G->walk = 0)
+int groups_upload(DevBuf<uint8_t> &g_ids, DevBuf<int64_t> &g_off, DevBuf<int32_t> &g_ord, DevBuf<int32_t> &g_lib,
+                  const bwams_dup_groups_t *g, MdGroupsDev *G, hipStream_t st);
+
+// recal.hip: base recalibration tables (rules in include/bwams.h above bwams_recal_open).
+// The store: a nibble per reference position, bits 0-2 the reference code 0..4, bit 3 the known-site flag; eight nibbles to a 32-bit
+// word, nibble k of a word in bits 4k .. 4k + 3; reference r begins at word ref_word[r] (n_ref + 1 entries), so no word is shared by
+// two references.  The tables: one block of 64-bit words, a cell two of them (observations, errors), laid out by RecalLayout.
+// check: *bad = min(*bad, record << 3 | reason).  records: rule 4's filter and the read group of each record; key[r] = 2 * group +
+// (cycles negative), or n_keys for a record that does not count; call[] (zeroed by the caller) gets the records counted and, per key,
+// the largest l_seq (call + kRecalCallMaxLen).  After a sort by key: heads / items turn the sorted keys into the item table of the
+// base kernel; bases: the default path; plain: BWAMS_RECAL_LDS=0.
+constexpr int kRecalQuals = 94, kRecalContexts = 16;
+constexpr int kRecalSlice = 1024;        // records of one key that a workgroup of the base kernel counts in LDS before it flushes (below 65536: 16-bit cells)
+enum { kRecalBadOp = 0, kRecalBadLength = 1, kRecalBadBounds = 2, kRecalBadCycle = 3, kRecalBadAux = 4 };
+enum { kRecalCallCounted = 0, kRecalCallBases = 1, kRecalCallItems = 2, kRecalCallMaxLen = 4 };
+struct RecalLayout {                     // offsets in 64-bit words
+    int32_t n_rg, max_cycle;
+    __host__ __device__ int64_t rows() const { return (int64_t)n_rg + 1; }
+    __host__ __device__ int64_t cols() const { return 2 * (int64_t)max_cycle + 1; }
+    __host__ __device__ int64_t rg() const { return 0; }
+    __host__ __device__ int64_t qual() const { return 2 * rows(); }
+    __host__ __device__ int64_t cycle() const { return qual() + 2 * rows() * kRecalQuals; }
+    __host__ __device__ int64_t context() const { return cycle() + 2 * rows() * kRecalQuals * cols(); }
+    __host__ __device__ int64_t words() const { return context() + 2 * rows() * kRecalQuals * kRecalContexts; }
+};
+struct RecalStore {
+    const uint32_t *words;
+    const int64_t *ref_word;             // n_ref + 1
+    const int32_t *l_ref;
+};
+struct RecalFilter {
+    uint32_t exclude;
+    int32_t min_mapq, min_baseq, max_cycle, n_ref;
+};
+void launch_recal_check(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalFilter &f, int walk_aux, unsigned long long *bad,
+                        int cu_count, hipStream_t st);
+void launch_recal_records(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalFilter &f, const MdGroupsDev &G,
+                          uint32_t n_keys, uint32_t *keys, uint32_t *vals, unsigned long long *call, int cu_count, hipStream_t st);
+void launch_recal_items(const uint32_t *keys, int64_t n_rec, uint32_t n_keys, const unsigned long long *call_max_len, uint32_t *key_first,
+                        int64_t *item_first, unsigned long long *n_items, hipStream_t st);
+void launch_recal_bases(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalFilter &f, const RecalStore &S,
+                        const RecalLayout &L, const uint32_t *vals, uint32_t n_keys, const uint32_t *key_first, const int64_t *item_first,
+                        const unsigned long long *n_items, unsigned long long *tables, unsigned long long *call, int cu_count, hipStream_t st);
+void launch_recal_plain(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalFilter &f, const RecalStore &S,
+                        const RecalLayout &L, const uint32_t *keys, uint32_t n_keys, unsigned long long *tables, unsigned long long *call,
+                        int cu_count, hipStream_t st);
+void launch_recal_set_ref(uint32_t *words, int64_t first_word, const uint8_t *codes, int32_t l_ref, int cu_count, hipStream_t st);
+void launch_recal_ref_index(uint32_t *words, const int64_t *ref_word, int32_t n_ref, int64_t n_words, const uint8_t *ref0123,
+                            const bwams_contig_t *contigs, const int64_t *hole_off, const int32_t *hole_len, int32_t n_holes, int cu_count,
+                            hipStream_t st);
+void launch_recal_known(uint32_t *words, const int64_t *ref_word, const bwams_recal_site_t *sites, int64_t n, int cu_count, hipStream_t st);
 
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);

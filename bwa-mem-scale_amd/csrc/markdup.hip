@@ -51,6 +51,7 @@
 #include <rocprim/rocprim.hpp>
 #include "common.h"
 #include "bam_rec.h"
+#include "aux_rg.h"
 
 namespace bwams {
 namespace {
@@ -294,10 +295,6 @@ __global__ void __launch_bounds__(256) md_apply_kernel(uint8_t *bam, const int64
 
 // ---- rules 9-10: a template's read group, library and location, lane per template ----
 
-__device__ __forceinline__ int aux_size(uint32_t t) {        // bytes of a fixed-size aux value of type t, 0 for any other
-    return (t == 'A' || t == 'c' || t == 'C') ? 1 : (t == 's' || t == 'S') ? 2 : (t == 'i' || t == 'I' || t == 'f') ? 4 : 0;
-}
-
 // one field of a read name from s[at, n): an optional '-', then digits up to the first other byte; *ok cleared outside int32
 __device__ __forceinline__ int32_t name_value(const uint8_t *s, uint32_t at, uint32_t n, bool *ok) {
     const bool neg = at < n && s[at] == '-';
@@ -321,48 +318,14 @@ __global__ void __launch_bounds__(256) md_loc_kernel(const uint8_t *bam, const i
         const uint32_t l_name = bam_l_name(p);
         bwams_dup_loc_t L;
         L.rg = -1; L.lib = G.n_lib - 1; L.tile = L.x = L.y = 0; L.has = 0;
-        if (G.walk) {                                         // rule 9: the aux fields by their types, to the record's end
-            const int64_t n = (int64_t)bam_block_size(p) + 4;         // the record with its block_size
-            const int64_t l_seq = bam_l_seq(p);
-            int64_t a = bam_aux_at(l_name, bam_n_cig(p), l_seq);
-            bool ok = l_seq >= 0 && a <= n, found = false;
+        if (G.walk) {                                         // rule 9: the aux fields by their types, to the record's end (aux_rg.h)
+            bool found = false;
             int64_t v0 = 0, v1 = 0;                           // RG's value: p[v0, v1)
-            while (ok && a < n) {
-                if (a + 3 > n) { ok = false; break; }
-                const uint32_t c0 = p[a], c1 = p[a + 1], ty = p[a + 2];
-                a += 3;
-                if (ty == 'Z' || ty == 'H') {
-                    const int64_t s = a;
-                    while (a < n && p[a] != 0) ++a;
-                    if (a >= n) { ok = false; break; }
-                    if (ty == 'Z' && c0 == 'R' && c1 == 'G' && !found) { found = true; v0 = s; v1 = a; }
-                    ++a;
-                } else if (ty == 'B') {
-                    if (a + 5 > n) { ok = false; break; }
-                    const int sz = aux_size(p[a]);
-                    if (!sz || p[a] == 'A') { ok = false; break; }
-                    a += 5 + (int64_t)sz * (int64_t)ld_u32(p + a + 1);
-                } else {
-                    const int sz = aux_size(ty);
-                    if (!sz) { ok = false; break; }
-                    a += sz;
-                }
-                if (a > n) ok = false;
-            }
+            const bool ok = aux_first_rg(p, &found, &v0, &v1);
             if (!ok) atomicMin(bad, (unsigned long long)r);
             if (ok && found) {                                // the ID among the table's, sorted by bytes
-                int lo = 0, hi = G.n_rg;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    const uint8_t *id = G.ids + G.id_off[mid];
-                    const int64_t ln = G.id_off[mid + 1] - G.id_off[mid], lv = v1 - v0;
-                    int64_t k = 0;
-                    while (k < ln && k < lv && id[k] == p[v0 + k]) ++k;
-                    const int cmp = k < ln && k < lv ? (id[k] < p[v0 + k] ? -1 : 1) : ln < lv ? -1 : ln > lv ? 1 : 0;
-                    if (cmp == 0) { L.rg = G.id_ord[mid]; L.lib = G.rg_lib[L.rg]; break; }
-                    if (cmp < 0) lo = mid + 1;
-                    else hi = mid;
-                }
+                const int32_t rg = groups_find(G, p + v0, v1 - v0);
+                if (rg >= 0) { L.rg = rg; L.lib = G.rg_lib[rg]; }
             }
         }
         const uint8_t *s = p + kBamName;                            // rule 10: the name without its NUL

@@ -24,10 +24,11 @@
 //   pileup_site_*         rule 8's predicate over the slots (SiteTest, given to rocprim::reduce and rocprim::select by
 //                         api_pileup.hip) and the gather that fills the site records of the selected slots.
 //   pileup_ref_kernel     rule 7: a lane per slot copies the forward strand's .0123 code at contig offset + position; a position in one
-//                         of the .amb holes reads 4.
+//                         of the .amb holes reads 4 (ref_code_at, ref_gather.h).
 #include <algorithm>
 #include "common.h"
 #include "bam_rec.h"
+#include "ref_gather.h"
 #include "wave_ops.h"
 
 namespace bwams {
@@ -387,16 +388,7 @@ __global__ void __launch_bounds__(256) pileup_ref_kernel(PileupRegions R, int32_
             if (R.off[mid] <= s) lo = mid;
             else hi = mid - 1;
         }
-        const int64_t at = contigs[reg_ref[lo]].offset + R.beg[lo] + (s - R.off[lo]);
-        int32_t a = 0, b = n_holes;                                      // the holes that begin at or before `at`: [0, a)
-        while (a < b) {
-            const int32_t mid = a + (b - a) / 2;
-            if (hole_off[mid] <= at) a = mid + 1;
-            else b = mid;
-        }
-        const bool hole = a > 0 && at < hole_off[a - 1] + hole_len[a - 1];
-        const uint8_t code = ref0123[at];
-        out[s] = hole || code > 3 ? 4 : code;
+        out[s] = ref_code_at(ref0123, contigs[reg_ref[lo]].offset + R.beg[lo] + (s - R.off[lo]), hole_off, hole_len, n_holes);
     }
 }
 

@@ -27,6 +27,7 @@
 #include <algorithm>
 #include "common.h"
 #include "bam_rec.h"
+#include "aux_rg.h"
 #include "wave_ops.h"
 
 namespace bwams {
@@ -41,11 +42,6 @@ unsigned grid_of(int64_t items, int64_t per_block, int cu_count, int per_cu) {
 __device__ __forceinline__ int32_t bam_next_ref_id(const uint8_t *p) { return (int32_t)ld_u32(p + 24); }
 __device__ __forceinline__ int32_t bam_next_pos(const uint8_t *p) { return (int32_t)ld_u32(p + 28); }
 __device__ __forceinline__ int32_t bam_tlen(const uint8_t *p) { return (int32_t)ld_u32(p + 32); }
-
-// bytes of one value of aux type t (A c C s S i I f), 0 for any other
-__device__ __forceinline__ int aux_size(uint32_t t) {
-    return t == 'A' || t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : t == 'i' || t == 'I' || t == 'f' ? 4 : 0;
-}
 
 // Rule 1's walk over the aux area a[0, n) and rule 5's NM (-1: no such field); false when the area cannot be walked.
 __device__ __forceinline__ bool aux_walk(const uint8_t *a, int64_t n, int64_t *nm_out) {

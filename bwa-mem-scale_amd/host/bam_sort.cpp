@@ -23,8 +23,9 @@
 // After bwams_sorter_set_markdup a put_batch runs bwams_bam_templates2 with the sorter's copy of the groups table and also keeps the
 // put's bwams_dup_loc_t per end and its two record-level counts per library; close3 hands ends and locs to bwams_dup_decide2 and adds
 // the puts' record-level counts to its rows.
-// After bwams_sorter_set_depth, bwams_sorter_set_pileup and / or bwams_sorter_set_qc close also hands the merged stream, as written, to those
-// handles: every flushed piece goes to bwams_depth_add_records, bwams_pileup_add_records and bwams_qc_add_records in whole records; the bytes of a record that the piece's
+// After bwams_sorter_set_depth, _set_pileup, _set_qc and / or _set_recal close also hands the merged stream, as written, to those
+// handles: every flushed piece goes to bwams_depth_add_records, bwams_pileup_add_records, bwams_qc_add_records and
+// bwams_recal_add_records in whole records; the bytes of a record that the piece's
 // end cuts wait in a carry buffer for the next piece, so the record is added once, with its final flag, wherever the pieces cut.
 // Plain C++ over the C-ABI (no HIP header), like fastq_io.cpp.
 #include <fcntl.h>
@@ -46,6 +47,7 @@
 #include "depth_host.h"
 #include "pileup_host.h"
 #include "qc_host.h"
+#include "recal_host.h"
 #include "dup_groups.h"
 
 namespace {
@@ -240,6 +242,7 @@ struct bwams_sorter {
     bwams_depth_t *depth = nullptr;                   // bwams_sorter_set_depth: close adds the merged stream to it (the caller's handle)
     bwams_pileup_t *pileup = nullptr;                 // bwams_sorter_set_pileup: the same
     bwams_qc_t *qc = nullptr;                         // bwams_sorter_set_qc: the same
+    bwams_recal_t *recal = nullptr;                   // bwams_sorter_set_recal: the same
     int64_t n_lib() const { return has_groups ? (int64_t)groups.libs.size() : 1; }
 };
 
@@ -512,6 +515,23 @@ int bwams_sorter_set_qc(bwams_sorter_t *s, bwams_qc_t *q) {
     return BWAMS_OK;
 }
 
+int bwams_sorter_set_recal(bwams_sorter_t *s, bwams_recal_t *r) {
+    const char *why = !s || !r ? "a sorter and a recalibration handle are required"
+                      : bwams::recal_device(r) != s->device ? "the recalibration handle is on another device than the sorter"
+                      : bwams::recal_l_ref(r) != s->l_ref ? "the recalibration handle's reference lengths are not the sorter header's" : nullptr;
+    if (why) {
+        bwams::set_last_error(std::string("bwams_sorter_set_recal: ") + why);
+        return BWAMS_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->any_put) {
+        bwams::set_last_error("bwams_sorter_set_recal: called after the sorter's first put");
+        return BWAMS_ERR_ARG;
+    }
+    s->recal = r;
+    return BWAMS_OK;
+}
+
 int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats, bwams_dup_lib_stats_t *lib_stats,
                         int64_t cap_lib) {
     if (!s) return BWAMS_ERR_ARG;
@@ -593,7 +613,7 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         std::vector<uint8_t> gz((size_t)bwams_deflate_bound(kPiece));
         std::vector<int64_t> sizes;
         int64_t fill = 0, flushed = 0;                                           // bytes in buf, record-stream bytes flushed
-        // set_depth, set_pileup, set_qc: the stream up to fed_at is handed on; whole_end is the end of the last record copied whole and open_end
+        // set_depth, set_pileup, set_qc, set_recal: the stream up to fed_at is handed on; whole_end is the end of the last record copied whole and open_end
         // that of the record being copied; carry holds stream bytes [fed_at, flushed) of the record that the last piece's end cut
         int64_t fed_at = 0, whole_end = 0, open_end = 0, carry_end = 0;
         std::vector<uint8_t> carry;
@@ -604,6 +624,8 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
                 if (int e = bwams_pileup_add_records(s->pileup, recs, n_bytes, nullptr)) return e;
             if (s->qc)
                 if (int e = bwams_qc_add_records(s->qc, recs, n_bytes, nullptr)) return e;
+            if (s->recal)
+                if (int e = bwams_recal_add_records(s->recal, recs, n_bytes, nullptr)) return e;
             return BWAMS_OK;
         };
         auto feed = [&]() -> int {
@@ -628,7 +650,7 @@ int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_du
         };
         auto flush = [&]() -> int {
             if (fill == 0) return BWAMS_OK;
-            if (s->depth || s->pileup || s->qc)
+            if (s->depth || s->pileup || s->qc || s->recal)
                 if (int e = feed()) return e;
             Clock::time_point t0 = Clock::now();
             int64_t got = 0;

@@ -119,6 +119,10 @@ const char *bwams_dup_groups_library(const bwams_dup_groups_t *g, int64_t lib) {
     return lib >= 0 && lib < (int64_t)g->libs.size() ? g->libs[(size_t)lib].c_str() : nullptr;
 }
 
+const char *bwams_dup_groups_rg_id(const bwams_dup_groups_t *g, int64_t rg) {
+    return g && rg >= 0 && rg < (int64_t)g->ids.size() ? g->ids[(size_t)rg].c_str() : nullptr;
+}
+
 void bwams_dup_groups_destroy(bwams_dup_groups_t *g) { delete g; }
 
 int64_t bwams_dup_library_size(int64_t n, int64_t c) { return bwams::dup_library_size(n, c); }

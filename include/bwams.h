@@ -58,6 +58,7 @@ const char *bwams_last_error(void);
  *   BWAMS_DEPTH_COMBINE=0   the depth add issues one atomic per lane instead of folding equal slots inside a wave (tools/depth_rate.py)
  *   BWAMS_PILEUP_TILED=0    every record of a pileup add goes through the direct kernel, one global atomic per base (tools/pileup_rate.py)
  *   BWAMS_QC_LANES=0        the QC add's per-cycle tables come from the plain kernel, one global atomic per base and per quality (tools/qc_rate.py)
+ *   BWAMS_RECAL_LDS=0       the recalibration add counts through the plain kernel, one global atomic per update (tools/recal_rate.py)
  *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
 int bwams_debug_reload(void);
 int bwams_device_count(int *n);
@@ -1379,6 +1380,97 @@ int bwams_qc_table(bwams_qc_t *q, int32_t what, int64_t *out, int64_t cap, int64
 int bwams_qc_text(bwams_qc_t *q, int32_t what, char *out, int64_t cap, int64_t *n);
 int bwams_qc_info(const bwams_qc_t *q, bwams_qc_info_t *info);
 int bwams_sorter_set_qc(bwams_sorter_t *s, bwams_qc_t *q);
+/* Base recalibration tables (csrc/recal.hip, csrc/api_recal.hip, host/recal_text.cpp): the counting half of base quality score
+ * recalibration.  Every aligned base is compared with the reference and counted, as an observation and possibly as an error, per read
+ * group, reported quality, machine cycle and dinucleotide context; positions of known variation are left out.  Accumulated on the
+ * device from a batch's BAM records, from host records, or from the sorted BAM writer's merged stream.  Every value is an integer
+ * count.  The rules are this library's own, modelled on the defaults of GATK BaseRecalibrator for the base-substitution event; no byte
+ * parity with GATK's report is claimed.  bwams/recal.py restates them in numpy and is what the tests compare against.  The empirical
+ * quality and the rewriting of QUAL are out of scope.
+ *  1. Handle.  Opened on a device over n_ref reference lengths, an optional groups table (bwams_dup_groups_t; NULL: no read groups)
+ *     and options: exclude (default 0x704, within 16 bits), min_mapq (1), min_baseq (6, in [0, 93]), max_cycle (500, at least 1),
+ *     reserved (0).  Anything else, n_ref < 0 or a negative length is BWAMS_ERR_ARG.  The handle owns rule 6's four tables and a store
+ *     of one nibble per position of every reference: the reference code 0..4 in bits 0-2, the known-site flag in bit 3, eight
+ *     positions to a 32-bit word, every reference beginning a new word: l / 2 bytes for l positions (1.55 GB for GRCh38), so the
+ *     whole genome sits beside an index.  BWAMS_ERR_NOMEM when the store or the tables do not fit.
+ *  2. Reference.  Every code is 4 (N) until set.  _set_ref: host codes 0..4 for one whole reference (a code above 4: BWAMS_ERR_ARG,
+ *     nothing set).  _set_ref_index: gathered on the device from the forward strand of an opened index's .0123 by the contig table,
+ *     under the conditions of pileup rule 7 (BWAMS_ERR_ARG when the index has no .0123 or no contigs, is on another device, or its
+ *     contig lengths differ); the .amb holes of an index made from FASTA become 4.  Neither touches the flags.
+ *  3. Known sites.  _add_known takes n intervals (ref, beg, end) with 0 <= ref < n_ref and 0 <= beg < end <= l_ref[ref], in any order,
+ *     overlapping freely.  A bad interval is BWAMS_ERR_ARG, bwams_last_error names the first, and nothing of that call is set.  The
+ *     flags are the union over all calls.  _reset zeroes the tables and keeps the reference and the flags.
+ *  4. Which records count.  (FLAG & exclude) == 0, MAPQ >= min_mapq, 0 <= refID < n_ref, n_cigar_op > 0, l_seq > 0 and a first QUAL
+ *     byte other than 0xFF.  A record that fails is skipped, not refused.  Supplementary records count, as they do in GATK.
+ *  5. Validity.  All records of a call are checked before anything is added.  BWAMS_ERR_ARG, bwams_last_error naming the first such
+ *     record and its reason: an op code above 8, in ANY record (`op`); and for a record that passes rule 4, in this order: SEQ or QUAL
+ *     ending behind the record's block_size (`bounds`; this comes before rule 4's look at the first QUAL byte, which such a record
+ *     does not hold); a CIGAR query length (the lengths of M I S = X) other than l_seq (`length`); l_seq > max_cycle (`cycle`; GATK
+ *     throws here too); and, when the handle has a groups table, aux fields that do not chain to the record's end as markdup rule 9
+ *     walks them (`aux`).  Without a table the aux fields are not read.
+ *  6. Keys and tables.  Read group g: the ordinal in the table of the record's first RG:Z value; n_rg for a record without RG:Z or with
+ *     one the table does not hold; with no table n_rg = 0 and every record is in row 0.  Quality q = min(QUAL byte, 93).  Cycle of
+ *     SEQ index i (0-based in SEQ as stored; soft clips are part of SEQ, hard clips are not): c = i + 1, or c = l_seq - i with FLAG
+ *     0x10; negated when FLAG has both 0x1 and 0x80.  Context: two bases in sequencing order, (SEQ[i-1], SEQ[i]), or with 0x10
+ *     (complement of SEQ[i+1], complement of SEQ[i]); it exists only when the neighbour exists and both codes are among 1, 2, 4, 8
+ *     (the neighbour may lie in a clip or an insertion); the key is 4 * first + second with A C G T as 0..3.  Every cell of a
+ *     table is two int64, observations then errors:
+ *       BWAMS_RECAL_TABLE_RG      [n_rg + 1]
+ *       BWAMS_RECAL_TABLE_QUAL    [n_rg + 1][94]
+ *       BWAMS_RECAL_TABLE_CYCLE   [n_rg + 1][94][2 * max_cycle + 1], column c + max_cycle; the middle column stays 0
+ *       BWAMS_RECAL_TABLE_CONTEXT [n_rg + 1][94][16]
+ *  7. Which bases count.  A base is an observation when its op is M, = or X, its SEQ code is 1, 2, 4 or 8, its QUAL byte is at least
+ *     min_baseq, its position lies in [0, l_ref), the reference code there is below 4 and the known flag there is clear.  It is also
+ *     an error when it differs from the reference base.  A base without a context counts in the other three tables only.  I, D, N,
+ *     S, H and P only advance; insertion and deletion events are out of scope.
+ *     Example: reference c1 = ACGTACGT, one @RG ID:a; record 1: 8M ACGTACGT at 0, forward, quality 30, RG:Z:a; record 2: 8M ACTTACGT
+ *     at 0 with FLAG 0x10, quality 30, RG:Z:a (the machine read ACGTAAGT).  RG[a] = 16 observations, 1 error; CYCLE[a][30][cycle 6] =
+ *     2 observations, 1 error; CONTEXT[a][30][AA] = 1 observation, 1 error; no other error anywhere.  With position 2 flagged as
+ *     known the error and both observations at that position vanish.
+ *  8. Accumulation.  As pileup rule 6: the tables hold the sums over any number of adds in any order; there is no finish step; more
+ *     than 2^31 - 1 records given in total is BWAMS_ERR_UNSUPPORTED with nothing of that call added; after BWAMS_ERR_DEVICE the
+ *     tables are undefined until _reset.
+ *  9. Queries.  _table: table `what` of rule 6 as int64 pairs into out[0, cap); *n (may be NULL) the number of int64 values, written
+ *     or needed; out may be NULL to ask for it; cap too small: BWAMS_ERR_CAPACITY.  _info: a test and measurement hook
+ *     (bwams_recal_info_t, include/bwams_types.h).
+ * 10. Text.  _text writes tab-separated rows, only those with observations > 0, in table order:
+ *       "RG\t<id>\t<obs>\t<err>\n"  "QUAL\t<id>\t<q>\t<obs>\t<err>\n"  "CYCLE\t<id>\t<q>\t<cycle>\t<obs>\t<err>\n"
+ *       "CONTEXT\t<id>\t<q>\t<XY>\t<obs>\t<err>\n"
+ *     <id> is the read group's ID in `names`, a groups table with the handle's number of read groups (NULL for a handle opened
+ *     without one; anything else is BWAMS_ERR_ARG), and `*` for the last row.  The example gives "CONTEXT\ta\t30\tAA\t1\t1\n".  *n: the
+ *     bytes written, or needed with BWAMS_ERR_CAPACITY, as bwams_qc_text.
+ * bwams_recal_open, _close (NULL allowed), _reset, _add_batch and _add_records: as their bwams_pileup_ namesakes; the groups table is
+ * copied, the caller may destroy it.  *n_counted (may be NULL): the records of this call that rule 4 let through.
+ * An add checks (recal_check_kernel, a lane per record), finds each record's read group and lists the counted records by (read
+ * group, sign of the cycles) with a radix sort, and then counts without a global atomic per base: a workgroup of recal_base_kernel owns
+ * a read group, a block of 64 cycles and a slice of the group's records, a lane one cycle of a record; CYCLE and CONTEXT are counted
+ * in LDS and flushed once per workgroup and slice, QUAL and RG folded from CYCLE at the flush.  Under BWAMS_RECAL_LDS=0 a plain kernel
+ * takes the records instead, a lane per base and one global atomic per update (the A/B baseline; the tables are the same).
+ * bwams_sorter_set_recal: the conditions and guarantees of bwams_sorter_set_depth: before the sorter's first put (BWAMS_ERR_ARG later,
+ * for a handle on another device, or when the handle's lengths differ from the sorter header's); the close adds every record of the
+ * merged stream AS WRITTEN, after the merge has set or cleared 0x400, so duplicates drop out by `exclude`, in whole records (one cut
+ * by a deflate piece's end is counted once); the file and the index are byte for byte what they are without the call; an add that
+ * fails ends the close with its error.  A sorter may have any of the depth, pileup, QC and recalibration handles, alone or together.
+ * bwams_dup_groups_rg_id: the ID of read group rg of a groups table (NULL outside [0, n_rg) or without a table), as
+ * bwams_dup_groups_library gives a library's name. */
+#define BWAMS_RECAL_TABLE_RG 0
+#define BWAMS_RECAL_TABLE_QUAL 1
+#define BWAMS_RECAL_TABLE_CYCLE 2
+#define BWAMS_RECAL_TABLE_CONTEXT 3
+int bwams_recal_open(int device, const int32_t *l_ref, int32_t n_ref, const bwams_dup_groups_t *groups, const bwams_recal_opt_t *opt,
+                     bwams_recal_t **out);
+int bwams_recal_close(bwams_recal_t *r);
+int bwams_recal_reset(bwams_recal_t *r);
+int bwams_recal_add_batch(bwams_recal_t *r, bwams_batch_t *b, int64_t *n_counted);
+int bwams_recal_add_records(bwams_recal_t *r, const void *bam, int64_t n_bytes, int64_t *n_counted);
+int bwams_recal_set_ref(bwams_recal_t *r, int32_t ref, const uint8_t *codes);
+int bwams_recal_set_ref_index(bwams_recal_t *r, const bwams_index_t *ix);
+int bwams_recal_add_known(bwams_recal_t *r, const bwams_recal_site_t *sites, int64_t n);
+int bwams_recal_table(bwams_recal_t *r, int32_t what, int64_t *out, int64_t cap, int64_t *n);
+int bwams_recal_text(bwams_recal_t *r, const bwams_dup_groups_t *names, char *out, int64_t cap, int64_t *n);
+int bwams_recal_info(const bwams_recal_t *r, bwams_recal_info_t *info);
+int bwams_sorter_set_recal(bwams_sorter_t *s, bwams_recal_t *r);
+const char *bwams_dup_groups_rg_id(const bwams_dup_groups_t *g, int64_t rg);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

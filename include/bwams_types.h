@@ -414,6 +414,34 @@ typedef struct bwams_qc_info {
     float   ms_check, ms_add;
 } bwams_qc_info_t;
 
+/* Base recalibration tables (include/bwams.h, "Base recalibration tables").  A handle lives on one device. */
+typedef struct bwams_recal bwams_recal_t;
+
+/* Rule 1's options: exclude within 16 bits, min_baseq in [0, 93], max_cycle >= 1, reserved 0.  A NULL pointer means
+ * {0x704, 1, 6, 500, 0}. */
+typedef struct bwams_recal_opt {
+    uint32_t exclude;
+    int32_t  min_mapq;
+    int32_t  min_baseq;
+    int32_t  max_cycle;
+    int32_t  reserved;
+} bwams_recal_opt_t;
+
+/* One interval of known variation (rule 3): positions [beg, end) of reference ref, 0-based. */
+typedef struct bwams_recal_site {
+    int32_t ref, beg, end;
+} bwams_recal_site_t;
+
+/* bwams_recal_info: which path the last add took (1: the LDS kernel, 0: the plain one), the records of a slice of the LDS kernel, of
+ * the last add the records given, the records rule 4 let through and the bases rule 7 observed, and the bytes of the handle's
+ * per-position store.  ms_check and ms_add are for measurement only (tools/recal_rate.py): the device time between events around
+ * rule 5's check and around the kernels that count. */
+typedef struct bwams_recal_info {
+    int32_t lds, slice;
+    int64_t n_records, n_counted, n_bases, store_bytes;
+    float   ms_check, ms_add;
+} bwams_recal_info_t;
+
 #ifdef __cplusplus
 }
 #endif
