@@ -69,6 +69,8 @@ SYMBOLS = [
     "bwams_recal_open", "bwams_recal_close", "bwams_recal_reset", "bwams_recal_add_batch", "bwams_recal_add_records", "bwams_recal_set_ref",
     "bwams_recal_set_ref_index", "bwams_recal_add_known", "bwams_recal_table", "bwams_recal_text", "bwams_recal_info",
     "bwams_sorter_set_recal", "bwams_dup_groups_rg_id",
+    "bwams_recal_model_create", "bwams_recal_model_from", "bwams_recal_model_table", "bwams_recal_model_constants", "bwams_recal_model_destroy",
+    "bwams_recal_apply_open", "bwams_recal_apply_close", "bwams_recal_apply_records", "bwams_recal_apply_batch", "bwams_recal_apply_info",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -887,6 +889,102 @@ class Recal:
             pass
 
 
+class RecalModelOpt(C.Structure):
+    _fields_ = [("exclude", C.c_uint32), ("preserve_below", C.c_int32), ("max_q", C.c_int32), ("prior_obs", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RecalApplyInfo(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("n_rewritten", C.c_int64), ("model_bytes", C.c_int64), ("ms_check", C.c_float),
+                ("ms_apply", C.c_float)]
+
+
+def recal_model_constants():
+    """bwams_recal_model_constants: (S[1..60], P[0..93]) as the library holds them"""
+    s, p = np.zeros(60, np.int64), np.zeros(94, np.int64)
+    _chk(lib().bwams_recal_model_constants(_p(s), _p(p)), "bwams_recal_model_constants")
+    return s, p
+
+
+class RecalModel:
+    """The quality model of base recalibration (bwams_recal_model_t, a host object): RecalModel(tables, max_cycle) from the four
+    count tables in the shapes Recal.table gives, or RecalModel.of(recal) from a handle's tables."""
+
+    def __init__(self, tables, max_cycle: int, exclude: int = 0, preserve_below: int = 6, max_q: int = 60, prior_obs: int = 1024,
+                 _from: "Recal | None" = None):
+        self.h = C.c_void_p()
+        o = RecalModelOpt(exclude, preserve_below, max_q, prior_obs, 0)
+        if _from is not None:
+            _chk(lib().bwams_recal_model_from(_from.h, C.byref(o), C.byref(self.h)), "bwams_recal_model_from")
+            self.n_rg = _from.n_rg
+        else:
+            t = [np.ascontiguousarray(x, np.int64) for x in tables]
+            self.n_rg = t[0].shape[0] - 1
+            _chk(lib().bwams_recal_model_create(_p(t[0]), _p(t[1]), _p(t[2]), _p(t[3]), self.n_rg, max_cycle, C.byref(o), C.byref(self.h)),
+                 "bwams_recal_model_create")
+        self.max_cycle = max_cycle
+
+    @classmethod
+    def of(cls, recal: "Recal", **opt) -> "RecalModel":
+        return cls(None, recal.max_cycle, _from=recal, **opt)
+
+    def table(self, what: int) -> np.ndarray:
+        """int16: 0 RG [n_rg + 1][3] = (Qrep, QG, G), 1 QUAL B [n_rg + 1][94], 2 CYCLE DC [..][94][2 max_cycle + 1], 3 CONTEXT DX [..][94][16]"""
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_model_table(self.h, what, None, 0, C.byref(n)), "bwams_recal_model_table")
+        out = np.zeros(n.value, np.int16)
+        _chk(lib().bwams_recal_model_table(self.h, what, _p(out), len(out), C.byref(n)), "bwams_recal_model_table")
+        return out.reshape((self.n_rg + 1,) + [(3,), (94,), (94, 2 * self.max_cycle + 1), (94, 16)][what])
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_recal_model_destroy(h), "bwams_recal_model_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RecalApply:
+    """A model on one GPU (bwams_recal_apply_t): rewrites the QUAL bytes of host records or of a batch's BAM records."""
+
+    def __init__(self, model: RecalModel, groups=None, device: int = 0):
+        self.h = C.c_void_p()
+        _chk(lib().bwams_recal_apply_open(device, model.h, _groups_h(groups), C.byref(self.h)), "bwams_recal_apply_open")
+
+    def records(self, records: bytes):
+        """-> (the records with their new QUAL, the records rewritten)"""
+        buf = np.frombuffer(bytes(records), np.uint8).copy()
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_apply_records(self.h, _p(buf), len(buf), C.byref(n)), "bwams_recal_apply_records")
+        return buf.tobytes(), n.value
+
+    def batch(self, batch: "Batch") -> int:
+        """The batch's current BAM records, and their sorted copy when there is one, rewritten in HBM; -> the records rewritten."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_apply_batch(self.h, batch.h, C.byref(n)), "bwams_recal_apply_batch")
+        return n.value
+
+    def info(self) -> dict:
+        """bwams_recal_apply_info: model_bytes, and of the last apply n_records, n_rewritten, ms_check, ms_apply."""
+        i = RecalApplyInfo()
+        _chk(lib().bwams_recal_apply_info(self.h, C.byref(i)), "bwams_recal_apply_info")
+        return {k: getattr(i, k) for k, _ in RecalApplyInfo._fields_}
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(lib().bwams_recal_apply_close(h), "bwams_recal_apply_close")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Gunzipper:
     """Plain gzip inflated on one GPU (bwams_gunzip_t): one file, fed in order."""
 
@@ -1201,6 +1299,16 @@ def lib():
         L.bwams_recal_text.argtypes = [vp, vp, vp, i64, vp]
         L.bwams_recal_info.argtypes = [vp, vp]
         L.bwams_sorter_set_recal.argtypes = [vp, vp]
+        L.bwams_recal_model_create.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.bwams_recal_model_from.argtypes = [vp, vp, vp]
+        L.bwams_recal_model_table.argtypes = [vp, i32, vp, i64, vp]
+        L.bwams_recal_model_constants.argtypes = [vp, vp]
+        L.bwams_recal_model_destroy.argtypes = [vp]
+        L.bwams_recal_apply_open.argtypes = [C.c_int, vp, vp, vp]
+        L.bwams_recal_apply_close.argtypes = [vp]
+        L.bwams_recal_apply_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_recal_apply_batch.argtypes = [vp, vp, vp]
+        L.bwams_recal_apply_info.argtypes = [vp, vp]
         L.bwams_dup_groups_rg_id.argtypes = [vp, i64]
         L.bwams_dup_groups_rg_id.restype = C.c_char_p
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -28,6 +28,10 @@ __device__ __forceinline__ int64_t bam_seq_at(uint32_t l_name, uint32_t n_cig) {
 __device__ __forceinline__ int64_t bam_qual_at(uint32_t l_name, uint32_t n_cig, int64_t l_seq) { return bam_seq_at(l_name, n_cig) + (l_seq + 1) / 2; }
 __device__ __forceinline__ int64_t bam_aux_at(uint32_t l_name, uint32_t n_cig, int64_t l_seq) { return bam_qual_at(l_name, n_cig, l_seq) + l_seq; }
 
+// SEQ: the 4-bit code of base i; A C G T (codes 1 2 4 8) as 0..3, -1 for any other code
+__device__ __forceinline__ uint32_t seq_code(const uint8_t *seq, int32_t i) { return (seq[i >> 1] >> ((i & 1) ? 0 : 4)) & 15; }
+__device__ __forceinline__ int base_of_code(uint32_t code) { return code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1; }
+
 // reference bases the CIGAR operations first, first + stride, ... of c[0, n_cig) cover (M, D, N, =, X)
 __device__ __forceinline__ int64_t cigar_ref_len(const uint8_t *c, uint32_t n_cig, uint32_t first, uint32_t stride) {
     int64_t rlen = 0;

@@ -425,6 +425,25 @@ void launch_recal_ref_index(uint32_t *words, const int64_t *ref_word, int32_t n_
                             hipStream_t st);
 void launch_recal_known(uint32_t *words, const int64_t *ref_word, const bwams_recal_site_t *sites, int64_t n, int cu_count, hipStream_t st);
 
+// recal_apply.hip: the quality model applied to QUAL (rules A to C in include/bwams.h above bwams_recal_model_create).  The model on
+// the device: b[row] in [0, 93], dc[row * cols + column] and dx[row * 16 + context] in [-93, 60], row = group * 94 + quality, the
+// columns as RecalLayout's.  check: *bad = min(*bad, record << 3 | reason), the reasons kRecalBad* above.  records: key[r] = 2 * group
+// + (cycles negative), or n_keys for a record rule A leaves alone; *n_taken (zeroed by the caller) += the records with a key.
+// apply: rule C over the records with a key, a wave per record.
+struct RecalModelDev {
+    const uint8_t *b;
+    const int8_t *dc, *dx;
+    int32_t n_rg, max_cycle, preserve_below, max_q;
+    uint32_t exclude;
+    __host__ __device__ int64_t cols() const { return 2 * (int64_t)max_cycle + 1; }
+};
+void launch_recal_apply_check(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalModelDev &M, int walk_aux,
+                              unsigned long long *bad, int cu_count, hipStream_t st);
+void launch_recal_apply_records(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalModelDev &M, const MdGroupsDev &G,
+                                uint32_t n_keys, uint32_t *keys, unsigned long long *n_taken, int cu_count, hipStream_t st);
+void launch_recal_apply(uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const RecalModelDev &M, const uint32_t *keys, uint32_t n_keys,
+                        int cu_count, hipStream_t st);
+
 // deflate.hip: the device a deflater is bound to; bwams_deflater_run with its work ordered behind what `after` has queued so far
 int deflater_device(const bwams_deflater *d);
 int deflater_run_after(bwams_deflater *d, hipStream_t after, const void *in, int64_t n_bytes, int in_on_device, void *out, int64_t out_cap,

@@ -174,10 +174,6 @@ __device__ __forceinline__ RecalRec rec_of(const uint8_t *p, const RecalStore &S
     return v;
 }
 
-// A C G T as 0..3 of a 4-bit SEQ code, -1 for any other
-__device__ __forceinline__ int base_of_code(uint32_t code) { return code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1; }
-__device__ __forceinline__ uint32_t seq_code(const uint8_t *seq, int32_t i) { return (seq[i >> 1] >> ((i & 1) ? 0 : 4)) & 15; }
-
 // Rules 6 and 7 for SEQ index i of record v: false when the base is no observation; else its quality *q, its context *ctx (-1: none)
 // and whether it is an error.  The lane walks the CIGAR from its start to the op that holds i.
 __device__ __forceinline__ bool recal_base(const RecalStore &S, const RecalRec &v, int32_t i, int min_baseq, int *q, int *ctx, bool *err) {

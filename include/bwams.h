@@ -1386,7 +1386,8 @@ int bwams_sorter_set_qc(bwams_sorter_t *s, bwams_qc_t *q);
  * device from a batch's BAM records, from host records, or from the sorted BAM writer's merged stream.  Every value is an integer
  * count.  The rules are this library's own, modelled on the defaults of GATK BaseRecalibrator for the base-substitution event; no byte
  * parity with GATK's report is claimed.  bwams/recal.py restates them in numpy and is what the tests compare against.  The empirical
- * quality and the rewriting of QUAL are out of scope.
+ * quality and the rewriting of QUAL are not part of this handle: they are the model and the apply handle of "Applying base
+ * recalibration" below, which take these tables.
  *  1. Handle.  Opened on a device over n_ref reference lengths, an optional groups table (bwams_dup_groups_t; NULL: no read groups)
  *     and options: exclude (default 0x704, within 16 bits), min_mapq (1), min_baseq (6, in [0, 93]), max_cycle (500, at least 1),
  *     reserved (0).  Anything else, n_ref < 0 or a negative length is BWAMS_ERR_ARG.  The handle owns rule 6's four tables and a store
@@ -1471,6 +1472,78 @@ int bwams_recal_text(bwams_recal_t *r, const bwams_dup_groups_t *names, char *ou
 int bwams_recal_info(const bwams_recal_t *r, bwams_recal_info_t *info);
 int bwams_sorter_set_recal(bwams_sorter_t *s, bwams_recal_t *r);
 const char *bwams_dup_groups_rg_id(const bwams_dup_groups_t *g, int64_t rg);
+/* Applying base recalibration (host/recal_model.cpp, csrc/recal_apply.hip, csrc/api_recal_apply.hip): the other half of base quality
+ * score recalibration.  A quality model is made on the host from the four tables above, and an apply handle rewrites the QUAL bytes
+ * of BAM records on the device with it.  The flow has two passes: count (bwams_recal_add_*), then bwams_recal_model_from, then apply.
+ * The rules are this library's own, in the spirit of GATK's hierarchical model: read group, then reported quality, then cycle and
+ * context deltas, sparse cells shrunk towards their parent; no parity with GATK's output is claimed.  Every value is an exact
+ * integer: no floating point and no libm call stands between the tables and the new bytes.  bwams/recal_apply.py restates all of it
+ * in Python integers and numpy and is what the tests compare against.
+ * The model.
+ *   Constants, committed as literals in host/recal_model.cpp and returned by bwams_recal_model_constants (S[k] at S[k - 1]):
+ *     S[k], k = 1..60: the largest integer s with s^20 <= 2^320 * 10^(2k - 1), that is floor(2^16 * 10^((2k - 1) / 20));
+ *     P[q], q = 0..93: the largest integer p with p^10 * 10^q <= 2^400, that is floor(2^40 * 10^(-q / 10)).
+ *   phred(num, den, cap) = the number of k in 1..cap with num * S[k] <= den << 16: round(-10 log10(num / den)) clamped to [0, cap].
+ *   post(n, e, Qp) = phred((e << 40) + m * P[Qp], (n + m) << 40, max_q): the quality of a cell of n observations and e errors after
+ *     m = prior_obs pseudo-observations at the prior quality Qp in [0, 93].  post(0, 0, q) = min(q, max_q).
+ *   Options (bwams_recal_model_opt_t; NULL: {0, 6, 60, 1024, 0}): exclude within 16 bits, preserve_below in [0, 93], max_q in [1, 60],
+ *     prior_obs in [1, 2^20], reserved 0; anything else is BWAMS_ERR_ARG.  A negative count, a cell with more errors than
+ *     observations, or a count of 2^40 or more is BWAMS_ERR_UNSUPPORTED: below 2^40 every product above stays below 2^128.
+ *   Values, for each row g in [0, n_rg] (n_rg: the row of records without a known read group):
+ *     RG       with RG[g].obs > 0: E = sum over q of QUAL[g][q].obs * P[q]; Qrep[g] = phred(E, RG[g].obs << 40, max_q);
+ *              QG[g] = post(RG[g], Qrep[g]); G[g] = QG[g] - Qrep[g].  Otherwise Qrep = QG = -1 and G = 0.
+ *     QUAL     Qp = clamp(q + G[g], 0, 93); B[g][q] = post(QUAL[g][q], Qp) for a cell with observations, else Qp.
+ *     CYCLE    DC[g][q][c] = post(CYCLE[g][q][c], B[g][q]) - B[g][q] for a cell with observations, else 0;
+ *     CONTEXT  DX[g][q][x] likewise.  Every delta lies in [-93, 60].
+ *   Example: the tables of the example of recalibration rule 7, default options: Qrep[a] = 30, QG[a] = 27, G[a] = -3; B[a][30] = 25,
+ *   B[a][37] = 34 (no data), B[*][30] = 30; DC[a][30] is -1 at cycle 6 and DX[a][30] is -1 at AA, every other delta is 0.
+ *   bwams_recal_model_create takes the four tables as int64 pairs, laid out as bwams_recal_table returns them; _model_from fetches
+ *   them from a handle.  _model_table: `what` and the capacity protocol of bwams_recal_table, int16 values: RG [n_rg + 1][3] =
+ *   (Qrep, QG, G); QUAL B [n_rg + 1][94]; CYCLE DC [n_rg + 1][94][2 * max_cycle + 1]; CONTEXT DX [n_rg + 1][94][16].  _model_destroy:
+ *   NULL allowed.  A model is plain host memory and is not tied to a device.
+ * Applying it.  bwams_recal_apply_open copies the model (B and the deltas as bytes) and the groups table to a device; the model and
+ * the table may be destroyed afterwards.  groups may be NULL only for a model with n_rg = 0; a table whose number of read groups is
+ * not the model's is BWAMS_ERR_ARG.  _close: NULL allowed.
+ *  A. Which records are rewritten.  (FLAG & exclude) == 0, l_seq > 0 and a first QUAL byte other than 0xFF.  Unmapped records,
+ *     duplicates and secondary records are rewritten too, as in GATK; MAPQ, refID and the CIGAR's content are not looked at.  Every
+ *     other record stays byte for byte.
+ *  B. Validity.  All records of a call are checked before any byte is written; BWAMS_ERR_ARG, bwams_last_error naming the first bad
+ *     record and its reason, and the caller's bytes and the batch's records unchanged.  For a record that passes the FLAG and l_seq
+ *     conditions of A, in this order: SEQ or QUAL ending behind the record's block_size (`bounds`; before the look at the first QUAL
+ *     byte); l_seq > the model's max_cycle (`cycle`); and, with a groups table, aux fields that do not chain to the record's end
+ *     (`aux`).
+ *  C. Which bases.  A base whose QUAL byte is below preserve_below keeps it.  Every other base of a rewritten record gets
+ *     clamp(B[g][q] + DC[g][q][cycle] + DX[g][q][context], 1, max_q) with q = min(byte, 93) and g, cycle and context exactly as
+ *     recalibration rule 6 defines them; where that rule gives no context (the first base in sequencing order; a base whose own code
+ *     or whose neighbour's is not A, C, G or T) DX counts as 0.  The base's own SEQ code does not otherwise matter.  Nothing but QUAL
+ *     bytes changes and no record changes its size.  Applying twice is NOT idempotent: the second pass reads the first one's output
+ *     as reported qualities.
+ *     Example: on the two records of that example, record 1 becomes 25 everywhere but stored index 5 (cycle 6), which becomes 24;
+ *     record 2 becomes 25 everywhere but stored index 2 (its cycle 6, context AA), which becomes 23 = 25 - 1 - 1.  With a model of
+ *     all-zero tables every byte b >= 6 becomes min(b, 93, max_q): 200 becomes 60.
+ * bwams_recal_apply_records rewrites host records in place (their block_size chain is checked as bwams_recal_add_records checks it).
+ * bwams_recal_apply_batch rewrites the batch's BAM records where they lie (of bwams_bam_run or bwams_bam_upload; BWAMS_ERR_ARG
+ * before either), and their sorted copy when the current records have one, as bwams_bam_markdup does: bwams_bam_fetch, _fetch_bgzf,
+ * _sort and _sorted_fetch all see the new bytes.  The templates of bwams_bam_templates are outdated by it.  *n_rewritten (may be
+ * NULL): the records rule A took.
+ * The kernels: a check (a lane per record), a record kernel for the read group and the key 2 * group + (cycles negative), and
+ * recal_apply_kernel, a wave per rewritten record and a lane per base, the model's three values of a base by global loads (a model
+ * is some 30 KB a read group at 150 cycles and stays in cache) and one byte store.  A second rewrite kernel that staged the model's
+ * rows in LDS over records sorted by key was measured against it, was slower, and is not in the library.  _info: a
+ * test and measurement hook (bwams_recal_apply_info_t, include/bwams_types.h).
+ * Out of scope: applying inside the sorted BAM writer (its counting happens at close, so no model can exist before its stream is
+ * written); OQ tags; quantised output qualities; insertion and deletion events; a model read back from bwams_recal_text. */
+int bwams_recal_model_create(const int64_t *rg, const int64_t *qual, const int64_t *cycle, const int64_t *context, int32_t n_rg,
+                             int32_t max_cycle, const bwams_recal_model_opt_t *opt, bwams_recal_model_t **out);
+int bwams_recal_model_from(bwams_recal_t *r, const bwams_recal_model_opt_t *opt, bwams_recal_model_t **out);
+int bwams_recal_model_table(const bwams_recal_model_t *m, int32_t what, int16_t *out, int64_t cap, int64_t *n);
+int bwams_recal_model_constants(int64_t S[60], int64_t P[94]);
+int bwams_recal_model_destroy(bwams_recal_model_t *m);
+int bwams_recal_apply_open(int device, const bwams_recal_model_t *model, const bwams_dup_groups_t *groups, bwams_recal_apply_t **out);
+int bwams_recal_apply_close(bwams_recal_apply_t *a);
+int bwams_recal_apply_records(bwams_recal_apply_t *a, void *bam, int64_t n_bytes, int64_t *n_rewritten);
+int bwams_recal_apply_batch(bwams_recal_apply_t *a, bwams_batch_t *b, int64_t *n_rewritten);
+int bwams_recal_apply_info(const bwams_recal_apply_t *a, bwams_recal_apply_info_t *info);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -442,6 +442,29 @@ typedef struct bwams_recal_info {
     float   ms_check, ms_add;
 } bwams_recal_info_t;
 
+/* The quality model and its application (include/bwams.h, "Applying base recalibration").  A model is a host object; an apply handle
+ * lives on one device. */
+typedef struct bwams_recal_model bwams_recal_model_t;
+typedef struct bwams_recal_apply bwams_recal_apply_t;
+
+/* The model's options: exclude within 16 bits, preserve_below in [0, 93], max_q in [1, 60], prior_obs in [1, 2^20], reserved 0.  A
+ * NULL pointer means {0, 6, 60, 1024, 0}. */
+typedef struct bwams_recal_model_opt {
+    uint32_t exclude;
+    int32_t  preserve_below;
+    int32_t  max_q;
+    int32_t  prior_obs;
+    int32_t  reserved;
+} bwams_recal_model_opt_t;
+
+/* bwams_recal_apply_info: of the last apply the records given and the records rewritten, and the bytes of the model on the device.
+ * ms_check and ms_apply are for measurement only (tools/recal_apply_rate.py): the device time between events around rule B's check
+ * and around the kernels that rewrite (for a batch with a sorted copy: both rewrites). */
+typedef struct bwams_recal_apply_info {
+    int64_t n_records, n_rewritten, model_bytes;
+    float   ms_check, ms_apply;
+} bwams_recal_apply_info_t;
+
 #ifdef __cplusplus
 }
 #endif
