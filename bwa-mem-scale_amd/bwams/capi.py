@@ -444,17 +444,66 @@ def dup_library_size(n: int, c: int):
     return None if v < 0 else v
 
 
+def _text(fn, *args) -> str:
+    """The text of a library function whose last arguments are (out, cap, n): asked for its size with no buffer (BWAMS_ERR_CAPACITY
+    gives it), then for the text."""
+    n = C.c_int64(0)
+    rc = fn(*args, None, 0, C.byref(n))
+    if rc != -4:
+        _chk(rc, fn.__name__)
+    buf = C.create_string_buffer(max(n.value, 1))
+    _chk(fn(*args, buf, n.value, C.byref(n)), fn.__name__)
+    return buf.raw[:n.value].decode("latin-1")
+
+
 def dup_metrics_text(groups, lib_stats, comment: str = "") -> str:
     """Rule 15 (bwams_dup_metrics_text) of DUP_LIB_STATS_DTYPE rows."""
     rows = np.ascontiguousarray(lib_stats, DUP_LIB_STATS_DTYPE)
-    n = C.c_int64(0)
-    rc = lib().bwams_dup_metrics_text(_groups_h(groups), _p(rows), len(rows), comment.encode(), None, 0, C.byref(n))
-    if rc != -4:
-        _chk(rc, "bwams_dup_metrics_text")
-    buf = C.create_string_buffer(max(n.value, 1))
-    _chk(lib().bwams_dup_metrics_text(_groups_h(groups), _p(rows), len(rows), comment.encode(), buf, n.value, C.byref(n)),
-         "bwams_dup_metrics_text")
-    return buf.raw[:n.value].decode("latin-1")
+    return _text(lib().bwams_dup_metrics_text, _groups_h(groups), _p(rows), len(rows), comment.encode())
+
+
+class _Handle:
+    """A library handle in .h that the function named by _close gives back, once."""
+    _close = ""
+
+    def _call(self, name: str, *args) -> None:
+        _chk(getattr(lib(), name)(self.h, *args), name)
+
+    def _info(self, name: str, struct) -> dict:
+        i = struct()
+        self._call(name, C.byref(i))
+        return {k: getattr(i, k) for k, _ in struct._fields_}
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _chk(getattr(lib(), self._close)(h), self._close)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Consumer(_Handle):
+    """A handle that BAM records are added to, through the functions _prefix + "_add_batch", "_add_records" and "_reset"."""
+    _prefix = ""
+
+    def add_batch(self, batch: "Batch") -> int:
+        """The batch's current BAM records, read in HBM; -> the records that counted."""
+        n = C.c_int64(0)
+        self._call(self._prefix + "_add_batch", batch.h, C.byref(n))
+        return n.value
+
+    def add_records(self, records: bytes) -> int:
+        records = bytes(records)
+        n = C.c_int64(0)
+        self._call(self._prefix + "_add_records", records, len(records), C.byref(n))
+        return n.value
+
+    def reset(self) -> None:
+        self._call(self._prefix + "_reset")
 
 
 class SorterStats(C.Structure):
@@ -534,8 +583,9 @@ class DepthOpt(C.Structure):
     _fields_ = [("exclude", C.c_uint32), ("min_mapq", C.c_int32), ("count_deletions", C.c_int32), ("reserved", C.c_int32)]
 
 
-class Depth:
+class Depth(_Consumer):
     """Per-base depth of coverage on one GPU (bwams_depth_t): add, finish once, query."""
+    _prefix, _close = "bwams_depth", "bwams_depth_close"
 
     def __init__(self, l_ref, device: int = 0, exclude: int = 0x704, min_mapq: int = 0, count_deletions: bool = False):
         self.h = C.c_void_p()
@@ -543,24 +593,9 @@ class Depth:
         o = DepthOpt(exclude, min_mapq, int(count_deletions), 0)
         _chk(lib().bwams_depth_open(device, _p(self.l_ref), len(self.l_ref), C.byref(o), C.byref(self.h)), "bwams_depth_open")
 
-    def add_batch(self, batch: "Batch") -> int:
-        """The batch's current BAM records, read in HBM; -> the records that counted."""
-        n = C.c_int64(0)
-        _chk(lib().bwams_depth_add_batch(self.h, batch.h, C.byref(n)), "bwams_depth_add_batch")
-        return n.value
-
-    def add_records(self, records: bytes) -> int:
-        records = bytes(records)
-        n = C.c_int64(0)
-        _chk(lib().bwams_depth_add_records(self.h, records, len(records), C.byref(n)), "bwams_depth_add_records")
-        return n.value
-
     def finish(self) -> "Depth":
         _chk(lib().bwams_depth_finish(self.h), "bwams_depth_finish")
         return self
-
-    def reset(self) -> None:
-        _chk(lib().bwams_depth_reset(self.h), "bwams_depth_reset")
 
     def summary(self) -> np.ndarray:
         rows = np.zeros(len(self.l_ref), DEPTH_REF_DTYPE)
@@ -600,24 +635,7 @@ class Depth:
     def text(self, names, what: int, arg: int = 0) -> str:
         """bwams_depth_text: what = 0 summary, 1 distribution (arg: n_bins), 2 windows BED (arg: w)."""
         flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
-        n = C.c_int64(0)
-        rc = lib().bwams_depth_text(self.h, flat, what, arg, None, 0, C.byref(n))
-        if rc != -4:
-            _chk(rc, "bwams_depth_text")
-        buf = C.create_string_buffer(max(n.value, 1))
-        _chk(lib().bwams_depth_text(self.h, flat, what, arg, buf, n.value, C.byref(n)), "bwams_depth_text")
-        return buf.raw[:n.value].decode("latin-1")
-
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _chk(lib().bwams_depth_close(h), "bwams_depth_close")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _text(lib().bwams_depth_text, self.h, flat, what, arg)
 
 
 class PileupOpt(C.Structure):
@@ -630,8 +648,9 @@ class PileupInfo(C.Structure):
                 ("n_direct", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
 
 
-class Pileup:
+class Pileup(_Consumer):
     """Per-base allele counts over regions on one GPU (bwams_pileup_t): add, then fetch, sites or text at any time."""
+    _prefix, _close = "bwams_pileup", "bwams_pileup_close"
 
     def __init__(self, l_ref, regions=(), device: int = 0, exclude: int = 0x704, min_mapq: int = 0, min_baseq: int = 13, min_alt: int = 2,
                  min_permille: int = 200):
@@ -644,21 +663,6 @@ class Pileup:
         _chk(lib().bwams_pileup_open(device, _p(self.l_ref), len(self.l_ref), _p(reg), len(reg), C.byref(o), C.byref(self.h)),
              "bwams_pileup_open")
         self.regions = [tuple(int(v) for v in r) for r in regions] or [(r, 0, int(n)) for r, n in enumerate(self.l_ref) if n > 0]
-
-    def add_batch(self, batch: "Batch") -> int:
-        """The batch's current BAM records, read in HBM; -> the records that counted."""
-        n = C.c_int64(0)
-        _chk(lib().bwams_pileup_add_batch(self.h, batch.h, C.byref(n)), "bwams_pileup_add_batch")
-        return n.value
-
-    def add_records(self, records: bytes) -> int:
-        records = bytes(records)
-        n = C.c_int64(0)
-        _chk(lib().bwams_pileup_add_records(self.h, records, len(records), C.byref(n)), "bwams_pileup_add_records")
-        return n.value
-
-    def reset(self) -> None:
-        _chk(lib().bwams_pileup_reset(self.h), "bwams_pileup_reset")
 
     def set_ref(self, region: int, codes) -> None:
         """The reference codes (0..4) of one region, end - beg of them."""
@@ -692,30 +696,11 @@ class Pileup:
 
     def text(self, names, min_alt: int = -1, min_permille: int = -1) -> str:
         flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
-        n = C.c_int64(0)
-        rc = lib().bwams_pileup_text(self.h, flat, min_alt, min_permille, None, 0, C.byref(n))
-        if rc != -4:
-            _chk(rc, "bwams_pileup_text")
-        buf = C.create_string_buffer(max(n.value, 1))
-        _chk(lib().bwams_pileup_text(self.h, flat, min_alt, min_permille, buf, n.value, C.byref(n)), "bwams_pileup_text")
-        return buf.raw[:n.value].decode("latin-1")
+        return _text(lib().bwams_pileup_text, self.h, flat, min_alt, min_permille)
 
     def info(self) -> dict:
         """bwams_pileup_info: tile, n_regions, n_slots, and of the last add n_counted, n_entries, n_direct, ms_check, ms_add."""
-        i = PileupInfo()
-        _chk(lib().bwams_pileup_info(self.h, C.byref(i)), "bwams_pileup_info")
-        return {k: getattr(i, k) for k, _ in PileupInfo._fields_}
-
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _chk(lib().bwams_pileup_close(h), "bwams_pileup_close")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._info("bwams_pileup_info", PileupInfo)
 
 
 class QcOpt(C.Structure):
@@ -731,8 +716,9 @@ class QcInfo(C.Structure):
                 ("bases_over", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
 
 
-class Qc:
+class Qc(_Consumer):
     """Alignment QC on one GPU (bwams_qc_t): flag counts, insert sizes and per-cycle tables; add, then query at any time."""
+    _prefix, _close = "bwams_qc", "bwams_qc_close"
 
     def __init__(self, device: int = 0, exclude: int = 0x900, max_cycle: int = 512, max_isize: int = 8000):
         self.h = C.c_void_p()
@@ -742,18 +728,7 @@ class Qc:
 
     def add_batch(self, batch: "Batch") -> int:
         """The batch's current BAM records, read in HBM; -> the records that rule 3's filter let through."""
-        n = C.c_int64(0)
-        _chk(lib().bwams_qc_add_batch(self.h, batch.h, C.byref(n)), "bwams_qc_add_batch")
-        return n.value
-
-    def add_records(self, records: bytes) -> int:
-        records = bytes(records)
-        n = C.c_int64(0)
-        _chk(lib().bwams_qc_add_records(self.h, records, len(records), C.byref(n)), "bwams_qc_add_records")
-        return n.value
-
-    def reset(self) -> None:
-        _chk(lib().bwams_qc_reset(self.h), "bwams_qc_reset")
+        return super().add_batch(batch)
 
     def summary(self):
         """(flags int64[2, 16], scalars int64[16]) of rules 2 and 5"""
@@ -771,30 +746,11 @@ class Qc:
 
     def text(self, what: int) -> str:
         """bwams_qc_text: what = 0 the flagstat lines, 1 the stats sections."""
-        n = C.c_int64(0)
-        rc = lib().bwams_qc_text(self.h, what, None, 0, C.byref(n))
-        if rc != -4:
-            _chk(rc, "bwams_qc_text")
-        buf = C.create_string_buffer(max(n.value, 1))
-        _chk(lib().bwams_qc_text(self.h, what, buf, n.value, C.byref(n)), "bwams_qc_text")
-        return buf.raw[:n.value].decode("latin-1")
+        return _text(lib().bwams_qc_text, self.h, what)
 
     def info(self) -> dict:
         """bwams_qc_info: isize_lds, slice, and of the last add n_records, n_counted, bases_over, ms_check, ms_add."""
-        i = QcInfo()
-        _chk(lib().bwams_qc_info(self.h, C.byref(i)), "bwams_qc_info")
-        return {k: getattr(i, k) for k, _ in QcInfo._fields_}
-
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _chk(lib().bwams_qc_close(h), "bwams_qc_close")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._info("bwams_qc_info", QcInfo)
 
 
 class RecalOpt(C.Structure):
@@ -809,8 +765,9 @@ class RecalInfo(C.Structure):
 RECAL_SITE_DTYPE = np.dtype([("ref", "<i4"), ("beg", "<i4"), ("end", "<i4")])
 
 
-class Recal:
+class Recal(_Consumer):
     """Base recalibration tables on one GPU (bwams_recal_t): set the reference and the known sites, add, then query at any time."""
+    _prefix, _close = "bwams_recal", "bwams_recal_close"
 
     def __init__(self, l_ref, groups=None, device: int = 0, exclude: int = 0x704, min_mapq: int = 1, min_baseq: int = 6,
                  max_cycle: int = 500):
@@ -824,18 +781,7 @@ class Recal:
 
     def add_batch(self, batch: "Batch") -> int:
         """The batch's current BAM records, read in HBM; -> the records that rule 4 let through."""
-        n = C.c_int64(0)
-        _chk(lib().bwams_recal_add_batch(self.h, batch.h, C.byref(n)), "bwams_recal_add_batch")
-        return n.value
-
-    def add_records(self, records: bytes) -> int:
-        records = bytes(records)
-        n = C.c_int64(0)
-        _chk(lib().bwams_recal_add_records(self.h, records, len(records), C.byref(n)), "bwams_recal_add_records")
-        return n.value
-
-    def reset(self) -> None:
-        _chk(lib().bwams_recal_reset(self.h), "bwams_recal_reset")
+        return super().add_batch(batch)
 
     def set_ref(self, ref: int, codes) -> None:
         """The codes (0..4) of one whole reference."""
@@ -863,30 +809,11 @@ class Recal:
         return out.reshape((self.n_rg + 1,) + shape + (2,))
 
     def text(self) -> str:
-        n = C.c_int64(0)
-        rc = lib().bwams_recal_text(self.h, _groups_h(self.groups), None, 0, C.byref(n))
-        if rc != -4:
-            _chk(rc, "bwams_recal_text")
-        buf = C.create_string_buffer(max(n.value, 1))
-        _chk(lib().bwams_recal_text(self.h, _groups_h(self.groups), buf, n.value, C.byref(n)), "bwams_recal_text")
-        return buf.raw[:n.value].decode("latin-1")
+        return _text(lib().bwams_recal_text, self.h, _groups_h(self.groups))
 
     def info(self) -> dict:
         """bwams_recal_info: lds, slice, store_bytes, and of the last add n_records, n_counted, n_bases, ms_check, ms_add."""
-        i = RecalInfo()
-        _chk(lib().bwams_recal_info(self.h, C.byref(i)), "bwams_recal_info")
-        return {k: getattr(i, k) for k, _ in RecalInfo._fields_}
-
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _chk(lib().bwams_recal_close(h), "bwams_recal_close")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._info("bwams_recal_info", RecalInfo)
 
 
 class RecalModelOpt(C.Structure):
@@ -905,9 +832,10 @@ def recal_model_constants():
     return s, p
 
 
-class RecalModel:
+class RecalModel(_Handle):
     """The quality model of base recalibration (bwams_recal_model_t, a host object): RecalModel(tables, max_cycle) from the four
     count tables in the shapes Recal.table gives, or RecalModel.of(recal) from a handle's tables."""
+    _close = "bwams_recal_model_destroy"
 
     def __init__(self, tables, max_cycle: int, exclude: int = 0, preserve_below: int = 6, max_q: int = 60, prior_obs: int = 1024,
                  _from: "Recal | None" = None):
@@ -935,20 +863,10 @@ class RecalModel:
         _chk(lib().bwams_recal_model_table(self.h, what, _p(out), len(out), C.byref(n)), "bwams_recal_model_table")
         return out.reshape((self.n_rg + 1,) + [(3,), (94,), (94, 2 * self.max_cycle + 1), (94, 16)][what])
 
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _chk(lib().bwams_recal_model_destroy(h), "bwams_recal_model_destroy")
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RecalApply:
+class RecalApply(_Handle):
     """A model on one GPU (bwams_recal_apply_t): rewrites the QUAL bytes of host records or of a batch's BAM records."""
+    _close = "bwams_recal_apply_close"
 
     def __init__(self, model: RecalModel, groups=None, device: int = 0):
         self.h = C.c_void_p()
@@ -969,20 +887,7 @@ class RecalApply:
 
     def info(self) -> dict:
         """bwams_recal_apply_info: model_bytes, and of the last apply n_records, n_rewritten, ms_check, ms_apply."""
-        i = RecalApplyInfo()
-        _chk(lib().bwams_recal_apply_info(self.h, C.byref(i)), "bwams_recal_apply_info")
-        return {k: getattr(i, k) for k, _ in RecalApplyInfo._fields_}
-
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _chk(lib().bwams_recal_apply_close(h), "bwams_recal_apply_close")
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._info("bwams_recal_apply_info", RecalApplyInfo)
 
 
 class Gunzipper:

@@ -8,22 +8,18 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "stage_state.h"
+#include "rec_consumer.h"
 #include "../host/depth_host.h"
 
 using namespace bwams;
 
-struct bwams_depth {
-    int device = 0, cu_count = 0;
-    hipStream_t stream = nullptr;
+struct bwams_depth : RecConsumer {
     bwams_depth_opt_t opt{};
     std::vector<int32_t> l_ref;
     std::vector<int64_t> slot_off;                   // n_ref + 1: reference r's first slot; the last is the number of slots
     DevBuf<int32_t> slots;                           // differences until finished, depths after
     DevBuf<int64_t> d_slot_off;
     DevBuf<> tmp;                                    // rocPRIM temporary storage
-    DevBuf<uint8_t> recs;                            // bwams_depth_add_records: the uploaded records and their offsets
-    DevBuf<int64_t> roff;
     DevBuf<unsigned long long> flag;                 // [0] first record with a bad op code, [1] records counted
     DevBuf<unsigned long long> hist;                 // the queries' device results, kept between calls
     DevBuf<int64_t> run_cnt;
@@ -33,10 +29,7 @@ struct bwams_depth {
     std::vector<bwams_depth_ref_t> rows;             // rule 7, computed at the first query that needs it
     int32_t n_ref() const { return (int32_t)l_ref.size(); }
     int64_t n_slots() const { return slot_off.back(); }
-    ~bwams_depth() {
-        (void)hipSetDevice(device);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    const char *finished_text() const { return finished ? "the handle is finished (bwams_depth_reset starts it again)" : nullptr; }
 };
 
 namespace bwams {
@@ -64,8 +57,9 @@ int query_ready(const bwams_depth *d, const char *who) {
     return BWAMS_OK;
 }
 
-// check first, then add (rule 3): the records at dev_bam + dev_off[r]
-int depth_add(bwams_depth *d, const uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, int64_t *n_counted, const char *who) {
+// check first, then add (rule 3)
+int depth_add(bwams_depth *d, const DevRecords &R, int64_t *n_counted, const char *who) {
+    const int64_t n_rec = R.n_rec;
     if (d->n_added + n_rec > 0x7FFFFFFFLL) {
         set_last_error(std::string(who) + ": more than 2^31 - 1 records added in total");
         return BWAMS_ERR_UNSUPPORTED;
@@ -73,17 +67,15 @@ int depth_add(bwams_depth *d, const uint8_t *dev_bam, const int64_t *dev_off, in
     hipStream_t st = d->stream;
     unsigned long long h[2] = {~0ULL, 0};
     if (n_rec > 0) {
-        BWAMS_HIP(hipMemsetAsync(d->flag.p, 0xFF, 8, st));
+        float ms = 0;                                                    // the check's time: nothing asks for it
         BWAMS_HIP(hipMemsetAsync(d->flag.p + 1, 0, 8, st));
-        launch_depth_check(dev_bam, dev_off, n_rec, d->flag.p, d->cu_count, st);
-        BWAMS_HIP(hipMemcpyAsync(h, d->flag.p, 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
-        BWAMS_HIP(hipGetLastError());
+        if (int rc = consumer_check(d, d->flag.p, 1, h, &ms, [&] { launch_depth_check(R.bam, R.off, n_rec, d->flag.p, d->cu_count, st); }))
+            return rc;
         if (h[0] != ~0ULL) {
             set_last_error(std::string(who) + ": record " + std::to_string(h[0]) + " has a CIGAR op code above 8");
             return BWAMS_ERR_ARG;
         }
-        launch_depth_add(dev_bam, dev_off, n_rec, d->opt, d->n_ref(), d->d_slot_off.p, d->slots.p, d->flag.p + 1, knobs().depth_combine,
+        launch_depth_add(R.bam, R.off, n_rec, d->opt, d->n_ref(), d->d_slot_off.p, d->slots.p, d->flag.p + 1, knobs().depth_combine,
                          d->cu_count, st);
         BWAMS_HIP(hipMemcpyAsync(h + 1, d->flag.p + 1, 8, hipMemcpyDeviceToHost, st));
         BWAMS_HIP(hipStreamSynchronize(st));
@@ -147,16 +139,12 @@ int bwams_depth_open(int device, const int32_t *l_ref, int32_t n_ref, const bwam
             set_last_error("bwams_depth_open: reference " + std::to_string(r) + " has a negative length");
             return BWAMS_ERR_ARG;
         }
-    if (int rc = check_device(device)) return rc;
-    BWAMS_HIP(hipSetDevice(device));
     std::unique_ptr<bwams_depth> d(new bwams_depth());
-    d->device = device;
+    if (int rc = d->open(device)) return rc;
     d->opt = opt ? *opt : bwams_depth_opt_t{0x704, 0, 0, 0};
     d->l_ref.assign(l_ref, l_ref + n_ref);
     d->slot_off.assign((size_t)n_ref + 1, 0);
     for (int32_t r = 0; r < n_ref; ++r) d->slot_off[(size_t)r + 1] = d->slot_off[(size_t)r] + l_ref[r] + 1;
-    BWAMS_HIP(hipDeviceGetAttribute(&d->cu_count, hipDeviceAttributeMultiprocessorCount, device));
-    BWAMS_HIP(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     BWAMS_HIP(d->slots.alloc((size_t)std::max<int64_t>(d->n_slots(), 1) * 4));
     BWAMS_HIP(d->d_slot_off.alloc(((size_t)n_ref + 1) * 8));
     BWAMS_HIP(d->flag.alloc(16));
@@ -183,45 +171,15 @@ int bwams_depth_reset(bwams_depth_t *d) {
 }
 
 int bwams_depth_add_batch(bwams_depth_t *d, bwams_batch_t *b, int64_t *n_counted) {
-    if (!d || !b || !b->stages || !b->stages->bm.done) {
-        set_last_error("bwams_depth_add_batch: run bwams_bam_run or bwams_bam_upload first");
-        return BWAMS_ERR_ARG;
-    }
-    if (d->finished) {
-        set_last_error("bwams_depth_add_batch: the handle is finished (bwams_depth_reset starts it again)");
-        return BWAMS_ERR_ARG;
-    }
-    if (b->idx->device != d->device) {
-        set_last_error("bwams_depth_add_batch: the handle is on device " + std::to_string(d->device) + ", the batch on device " +
-                       std::to_string(b->idx->device));
-        return BWAMS_ERR_ARG;
-    }
-    BWAMS_HIP(hipSetDevice(d->device));
-    BWAMS_HIP(hipStreamSynchronize(b->stream));              // the records may still be written by queued work
-    StageState *s = b->stages;
-    return depth_add(d, s->bm.out.p, s->bm.roff.p, s->bm.nrec, n_counted, "bwams_depth_add_batch");
+    DevRecords R;
+    if (int rc = consumer_batch(d, b, "bwams_depth_add_batch", &R, d ? d->finished_text() : nullptr)) return rc;
+    return depth_add(d, R, n_counted, "bwams_depth_add_batch");
 }
 
 int bwams_depth_add_records(bwams_depth_t *d, const void *bam, int64_t n_bytes, int64_t *n_counted) {
-    if (!d || n_bytes < 0 || (n_bytes && !bam)) {
-        set_last_error("bwams_depth_add_records: a handle and host records are required");
-        return BWAMS_ERR_ARG;
-    }
-    if (d->finished) {
-        set_last_error("bwams_depth_add_records: the handle is finished (bwams_depth_reset starts it again)");
-        return BWAMS_ERR_ARG;
-    }
-    std::vector<int64_t> off;
-    int32_t max_rid = -1;
-    if (int rc = bam_record_offsets("bwams_depth_add_records", bam, n_bytes, &off, &max_rid)) return rc;
-    const int64_t n_rec = (int64_t)off.size() - 1;
-    BWAMS_HIP(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    BWAMS_HIP(d->recs.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(d->roff.ensure_n((size_t)n_rec + 1));
-    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(d->recs.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(d->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here when the add returns early
-    return depth_add(d, d->recs.p, d->roff.p, n_rec, n_counted, "bwams_depth_add_records");
+    DevRecords R;
+    if (int rc = consumer_records(d, bam, n_bytes, "bwams_depth_add_records", &R, d ? d->finished_text() : nullptr)) return rc;
+    return depth_add(d, R, n_counted, "bwams_depth_add_records");
 }
 
 int bwams_depth_finish(bwams_depth_t *d) {

@@ -7,14 +7,12 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "stage_state.h"
+#include "rec_consumer.h"
 #include "../host/pileup_host.h"
 
 using namespace bwams;
 
-struct bwams_pileup {
-    int device = 0, cu_count = 0;
-    hipStream_t stream = nullptr;
+struct bwams_pileup : RecConsumer {
     bwams_pileup_opt_t opt{};
     std::vector<int32_t> l_ref;
     std::vector<bwams_pileup_region_t> regions;
@@ -24,8 +22,6 @@ struct bwams_pileup {
     DevBuf<int32_t> d_beg, d_end, d_ref_first, d_reg_ref;
     DevBuf<int64_t> d_off;
     DevBuf<> tmp;                                    // rocPRIM temporary storage
-    DevBuf<uint8_t> recs;                            // bwams_pileup_add_records: the uploaded records and their offsets
-    DevBuf<int64_t> roff;
     DevBuf<unsigned long long> flag;                 // [0..2] rule 3's first bad records, [3..5] the route counters of a piece
     DevBuf<uint32_t> keys, keys2, vals, vals2, heads, n_heads;       // the (tile, record) entries of a piece, twice for the sort
     DevBuf<uint8_t> route;
@@ -35,18 +31,11 @@ struct bwams_pileup {
     DevBuf<int32_t> hole_len;
     int64_t n_added = 0;                             // records given so far (rule 6)
     int64_t last[3] = {0, 0, 0};                     // of the last add: records counted, tile entries, records routed direct
-    float ms_check = 0, ms_add = 0;                  // ... and its device time, between the events below
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms_check = 0, ms_add = 0;                  // ... and its device time
     int32_t n_ref() const { return (int32_t)l_ref.size(); }
     int32_t n_regions() const { return (int32_t)regions.size(); }
     int64_t n_slots() const { return reg_off.back(); }
     PileupRegions dev_regions() const { return PileupRegions{d_beg.p, d_end.p, d_ref_first.p, d_off.p}; }
-    ~bwams_pileup() {
-        (void)hipSetDevice(device);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace bwams {
@@ -63,27 +52,23 @@ struct SiteCount {
     __host__ __device__ int64_t operator()(int64_t s) const { return f(s) ? 1 : 0; }
 };
 
-// check first, then add (rule 3): the records at dev_bam + dev_off[r]
-int pileup_add(bwams_pileup *p, const uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, int64_t *n_counted, const char *who) {
+// check first, then add (rule 3)
+int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, const char *who) {
+    const uint8_t *dev_bam = recs.bam;
+    const int64_t *dev_off = recs.off;
+    const int64_t n_rec = recs.n_rec;
     if (p->n_added + n_rec > 0x7FFFFFFFLL) {
         set_last_error(std::string(who) + ": more than 2^31 - 1 records added in total");
         return BWAMS_ERR_UNSUPPORTED;
     }
     hipStream_t st = p->stream;
     int64_t sum[3] = {0, 0, 0};
-    float ms = 0;
     p->ms_check = p->ms_add = 0;
     if (n_rec > 0) {
         const PileupFilter f{p->opt.exclude, p->opt.min_mapq, p->n_ref()};
         unsigned long long h[3] = {0, 0, 0};
-        BWAMS_HIP(hipMemsetAsync(p->flag.p, 0xFF, 24, st));
-        BWAMS_HIP(hipEventRecord(p->ev[0], st));
-        launch_pileup_check(dev_bam, dev_off, n_rec, f, p->flag.p, p->cu_count, st);
-        BWAMS_HIP(hipEventRecord(p->ev[1], st));
-        BWAMS_HIP(hipMemcpyAsync(h, p->flag.p, 24, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
-        BWAMS_HIP(hipGetLastError());
-        BWAMS_HIP(hipEventElapsedTime(&p->ms_check, p->ev[0], p->ev[1]));
+        if (int rc = consumer_check(p, p->flag.p, 3, h, &p->ms_check,
+                                    [&] { launch_pileup_check(dev_bam, dev_off, n_rec, f, p->flag.p, p->cu_count, st); })) return rc;
         const int first = (int)(std::min_element(h, h + 3) - h);         // the first bad record; a record is in one list only
         if (h[first] != ~0ULL) {
             static const char *const why[3] = {" has a CIGAR op code above 8", " has a CIGAR whose query length is not l_seq",
@@ -109,24 +94,19 @@ int pileup_add(bwams_pileup *p, const uint8_t *dev_bam, const int64_t *dev_off, 
         for (int64_t r0 = 0; r0 < n_rec; r0 += kPiece) {
             const int64_t n = std::min(kPiece, n_rec - r0), n_ent = 2 * n;
             if (tiled) BWAMS_HIP(hipMemsetAsync(p->n_heads.p, 0, 4, st));
-            BWAMS_HIP(hipMemsetAsync(p->flag.p + 3, 0, 24, st));
-            BWAMS_HIP(hipEventRecord(p->ev[0], st));
-            launch_pileup_route(dev_bam, dev_off + r0, n, f, R, (uint32_t)n_tiles, tiled, p->keys.p, p->vals.p, p->route.p, p->flag.p + 3,
-                                p->cu_count, st);
-            if (tiled) {
-                if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": radix_sort_pairs").c_str(), [&](void *tmp, size_t &tb) {
-                        return rocprim::radix_sort_pairs(tmp, tb, p->keys.p, p->keys2.p, p->vals.p, p->vals2.p, (size_t)n_ent, 0u, bits, st);
-                    })) return rc;
-                launch_pileup_tiles(dev_bam, dev_off + r0, R, p->opt.min_baseq, p->keys2.p, p->vals2.p, n_ent, (uint32_t)n_tiles, p->heads.p,
-                                    p->n_heads.p, p->n_slots(), p->counts.p, p->cu_count, st);
-            }
-            launch_pileup_direct(dev_bam, dev_off + r0, n, R, p->opt.min_baseq, p->route.p, p->counts.p, p->cu_count, st);
-            BWAMS_HIP(hipEventRecord(p->ev[1], st));
-            BWAMS_HIP(hipMemcpyAsync(h, p->flag.p + 3, 24, hipMemcpyDeviceToHost, st));
-            BWAMS_HIP(hipStreamSynchronize(st));
-            BWAMS_HIP(hipGetLastError());
-            BWAMS_HIP(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
-            p->ms_add += ms;
+            if (int rc = consumer_piece(p, p->flag.p + 3, 3, h, &p->ms_add, [&]() -> int {
+                    launch_pileup_route(dev_bam, dev_off + r0, n, f, R, (uint32_t)n_tiles, tiled, p->keys.p, p->vals.p, p->route.p,
+                                        p->flag.p + 3, p->cu_count, st);
+                    if (tiled) {
+                        if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": radix_sort_pairs").c_str(), [&](void *tmp, size_t &tb) {
+                                return rocprim::radix_sort_pairs(tmp, tb, p->keys.p, p->keys2.p, p->vals.p, p->vals2.p, (size_t)n_ent, 0u, bits, st);
+                            })) return rc;
+                        launch_pileup_tiles(dev_bam, dev_off + r0, R, p->opt.min_baseq, p->keys2.p, p->vals2.p, n_ent, (uint32_t)n_tiles,
+                                            p->heads.p, p->n_heads.p, p->n_slots(), p->counts.p, p->cu_count, st);
+                    }
+                    launch_pileup_direct(dev_bam, dev_off + r0, n, R, p->opt.min_baseq, p->route.p, p->counts.p, p->cu_count, st);
+                    return BWAMS_OK;
+                })) return rc;
             for (int k = 0; k < 3; ++k) sum[k] += (int64_t)h[k];
         }
     }
@@ -210,10 +190,8 @@ int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwa
             return BWAMS_ERR_ARG;
         }
     }
-    if (int rc = check_device(device)) return rc;
-    BWAMS_HIP(hipSetDevice(device));
     std::unique_ptr<bwams_pileup> p(new bwams_pileup());
-    p->device = device;
+    if (int rc = p->open(device)) return rc;
     p->opt = opt ? *opt : bwams_pileup_opt_t{0x704, 0, 13, 2, 200, 0};
     p->l_ref.assign(l_ref, l_ref + n_ref);
     if (n_regions) p->regions.assign(regions, regions + n_regions);
@@ -230,9 +208,6 @@ int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwa
         ++ref_first[(size_t)g.ref + 1];
     }
     for (int32_t r = 0; r < n_ref; ++r) ref_first[(size_t)r + 1] += ref_first[(size_t)r];
-    BWAMS_HIP(hipDeviceGetAttribute(&p->cu_count, hipDeviceAttributeMultiprocessorCount, device));
-    BWAMS_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : p->ev) BWAMS_HIP(hipEventCreate(&e));
     hipStream_t st = p->stream;
     const size_t slots = (size_t)std::max<int64_t>(p->n_slots(), 1);
     BWAMS_HIP(p->counts.alloc(slots * kPileupChannels * 4));            // rule 1: BWAMS_ERR_NOMEM when they do not fit
@@ -271,37 +246,15 @@ int bwams_pileup_reset(bwams_pileup_t *p) {
 }
 
 int bwams_pileup_add_batch(bwams_pileup_t *p, bwams_batch_t *b, int64_t *n_counted) {
-    if (!p || !b || !b->stages || !b->stages->bm.done) {
-        set_last_error("bwams_pileup_add_batch: run bwams_bam_run or bwams_bam_upload first");
-        return BWAMS_ERR_ARG;
-    }
-    if (b->idx->device != p->device) {
-        set_last_error("bwams_pileup_add_batch: the handle is on device " + std::to_string(p->device) + ", the batch on device " +
-                       std::to_string(b->idx->device));
-        return BWAMS_ERR_ARG;
-    }
-    BWAMS_HIP(hipSetDevice(p->device));
-    BWAMS_HIP(hipStreamSynchronize(b->stream));              // the records may still be written by queued work
-    StageState *s = b->stages;
-    return pileup_add(p, s->bm.out.p, s->bm.roff.p, s->bm.nrec, n_counted, "bwams_pileup_add_batch");
+    DevRecords recs;
+    if (int rc = consumer_batch(p, b, "bwams_pileup_add_batch", &recs)) return rc;
+    return pileup_add(p, recs, n_counted, "bwams_pileup_add_batch");
 }
 
 int bwams_pileup_add_records(bwams_pileup_t *p, const void *bam, int64_t n_bytes, int64_t *n_counted) {
-    if (!p || n_bytes < 0 || (n_bytes && !bam)) {
-        set_last_error("bwams_pileup_add_records: a handle and host records are required");
-        return BWAMS_ERR_ARG;
-    }
-    std::vector<int64_t> off;
-    int32_t max_rid = -1;
-    if (int rc = bam_record_offsets("bwams_pileup_add_records", bam, n_bytes, &off, &max_rid)) return rc;
-    const int64_t n_rec = (int64_t)off.size() - 1;
-    BWAMS_HIP(hipSetDevice(p->device));
-    hipStream_t st = p->stream;
-    BWAMS_HIP(p->recs.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(p->roff.ensure_n((size_t)n_rec + 1));
-    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(p->recs.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(p->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here when the add returns early
-    return pileup_add(p, p->recs.p, p->roff.p, n_rec, n_counted, "bwams_pileup_add_records");
+    DevRecords recs;
+    if (int rc = consumer_records(p, bam, n_bytes, "bwams_pileup_add_records", &recs)) return rc;
+    return pileup_add(p, recs, n_counted, "bwams_pileup_add_records");
 }
 
 int bwams_pileup_set_ref(bwams_pileup_t *p, int32_t region, const uint8_t *codes) {

@@ -5,30 +5,19 @@
 #include <cstring>
 #include <memory>
 
-#include "stage_state.h"
+#include "rec_consumer.h"
 #include "../host/qc_host.h"
 
 using namespace bwams;
 
-struct bwams_qc {
-    int device = 0, cu_count = 0;
-    hipStream_t stream = nullptr;
+struct bwams_qc : RecConsumer {
     bwams_qc_opt_t opt{};
     QcLayout lay{};
     DevBuf<unsigned long long> counters;             // lay.words() of them (rule 6)
     DevBuf<unsigned long long> call;                 // [0] rule 1's first bad record, then kQcCallWords words of a piece
     DevBuf<uint32_t> lists;                          // the filtered-in records of a piece, a list per class
-    DevBuf<uint8_t> recs;                            // bwams_qc_add_records: the uploaded records and their offsets
-    DevBuf<int64_t> roff;
     int64_t last[3] = {0, 0, 0};                     // of the last add: records given, records counted, bases past max_cycle
-    float ms_check = 0, ms_add = 0;                  // ... and its device time, between the events below
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~bwams_qc() {
-        (void)hipSetDevice(device);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    float ms_check = 0, ms_add = 0;                  // ... and its device time
 };
 
 namespace bwams {
@@ -39,47 +28,36 @@ namespace {
 
 constexpr int64_t kPiece = 1 << 24;                  // records listed at a time: 8 bytes of scratch per record
 
-// check first, then add (rule 1): the records at dev_bam + dev_off[r]
-int qc_add(bwams_qc *q, const uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, int64_t *n_counted, const char *who) {
+// check first, then add (rule 1)
+int qc_add(bwams_qc *q, const DevRecords &R, int64_t *n_counted, const char *who) {
+    const int64_t n_rec = R.n_rec;
     if (n_rec > 0x7FFFFFFFLL) {
         set_last_error(std::string(who) + ": more than 2^31 - 1 records in one call");
         return BWAMS_ERR_UNSUPPORTED;
     }
     hipStream_t st = q->stream;
     int64_t counted = 0, over = 0;
-    float ms = 0;
     q->ms_check = q->ms_add = 0;
     if (n_rec > 0) {
         unsigned long long h[kQcCallWords];
-        BWAMS_HIP(hipMemsetAsync(q->call.p, 0xFF, 8, st));
-        BWAMS_HIP(hipEventRecord(q->ev[0], st));
-        launch_qc_check(dev_bam, dev_off, n_rec, q->opt.exclude, q->call.p, q->cu_count, st);
-        BWAMS_HIP(hipEventRecord(q->ev[1], st));
-        BWAMS_HIP(hipMemcpyAsync(h, q->call.p, 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
-        BWAMS_HIP(hipGetLastError());
-        BWAMS_HIP(hipEventElapsedTime(&q->ms_check, q->ev[0], q->ev[1]));
+        if (int rc = consumer_check(q, q->call.p, 1, h, &q->ms_check,
+                                    [&] { launch_qc_check(R.bam, R.off, n_rec, q->opt.exclude, q->call.p, q->cu_count, st); })) return rc;
         if (h[0] != ~0ULL) {
             static const char *const why[4] = {" has a negative l_seq or a CIGAR that ends behind the record (bounds)",
                                                " has a CIGAR op code above 8 (op)", " ends inside its SEQ or QUAL (bounds)",
                                                " has an aux area that cannot be walked (aux)"};
-            set_last_error(std::string(who) + ": record " + std::to_string(h[0] >> 3) + why[h[0] & 7]);
-            return BWAMS_ERR_ARG;
+            return consumer_refuse_packed(who, h[0], why);
         }
         BWAMS_HIP(q->lists.ensure_n((size_t)(2 * std::min(kPiece, n_rec))));     // before the first counter moves
         const int lanes = knobs().qc_lanes != 0;
         for (int64_t r0 = 0; r0 < n_rec; r0 += kPiece) {
             const int64_t n = std::min(kPiece, n_rec - r0);
-            BWAMS_HIP(hipMemsetAsync(q->call.p + 1, 0, kQcCallWords * 8, st));
-            BWAMS_HIP(hipEventRecord(q->ev[0], st));
-            launch_qc_records(dev_bam, dev_off + r0, n, q->lay, q->counters.p, q->lists.p, q->call.p + 1, q->cu_count, st);
-            launch_qc_cycles(dev_bam, dev_off + r0, n, q->lay, q->counters.p, q->lists.p, q->call.p + 1, lanes, q->cu_count, st);
-            BWAMS_HIP(hipEventRecord(q->ev[1], st));
-            BWAMS_HIP(hipMemcpyAsync(h, q->call.p + 1, kQcCallWords * 8, hipMemcpyDeviceToHost, st));
-            BWAMS_HIP(hipStreamSynchronize(st));
-            BWAMS_HIP(hipGetLastError());
-            BWAMS_HIP(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
-            q->ms_add += ms;
+            unsigned long long *call = q->call.p + 1;
+            if (int rc = consumer_piece(q, call, kQcCallWords, h, &q->ms_add, [&] {
+                    launch_qc_records(R.bam, R.off + r0, n, q->lay, q->counters.p, q->lists.p, call, q->cu_count, st);
+                    launch_qc_cycles(R.bam, R.off + r0, n, q->lay, q->counters.p, q->lists.p, call, lanes, q->cu_count, st);
+                    return BWAMS_OK;
+                })) return rc;
             counted += (int64_t)h[kQcCallCounted];
             over += (int64_t)h[kQcCallOver];
         }
@@ -119,15 +97,10 @@ int bwams_qc_open(int device, const bwams_qc_opt_t *opt, bwams_qc_t **out) {
         return BWAMS_ERR_ARG;
     }
     *out = nullptr;
-    if (int rc = check_device(device)) return rc;
-    BWAMS_HIP(hipSetDevice(device));
     std::unique_ptr<bwams_qc> q(new bwams_qc());
-    q->device = device;
+    if (int rc = q->open(device)) return rc;
     q->opt = opt ? *opt : bwams_qc_opt_t{0x900, 512, 8000, 0};
     q->lay = QcLayout{q->opt.max_cycle, q->opt.max_isize, q->opt.exclude};
-    BWAMS_HIP(hipDeviceGetAttribute(&q->cu_count, hipDeviceAttributeMultiprocessorCount, device));
-    BWAMS_HIP(hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : q->ev) BWAMS_HIP(hipEventCreate(&e));
     BWAMS_HIP(q->counters.alloc((size_t)q->lay.words() * 8));
     BWAMS_HIP(q->call.alloc((1 + kQcCallWords) * 8));
     BWAMS_HIP(hipMemsetAsync(q->counters.p, 0, (size_t)q->lay.words() * 8, q->stream));
@@ -151,37 +124,15 @@ int bwams_qc_reset(bwams_qc_t *q) {
 }
 
 int bwams_qc_add_batch(bwams_qc_t *q, bwams_batch_t *b, int64_t *n_counted) {
-    if (!q || !b || !b->stages || !b->stages->bm.done) {
-        set_last_error("bwams_qc_add_batch: run bwams_bam_run or bwams_bam_upload first");
-        return BWAMS_ERR_ARG;
-    }
-    if (b->idx->device != q->device) {
-        set_last_error("bwams_qc_add_batch: the handle is on device " + std::to_string(q->device) + ", the batch on device " +
-                       std::to_string(b->idx->device));
-        return BWAMS_ERR_ARG;
-    }
-    BWAMS_HIP(hipSetDevice(q->device));
-    BWAMS_HIP(hipStreamSynchronize(b->stream));              // the records may still be written by queued work
-    StageState *s = b->stages;
-    return qc_add(q, s->bm.out.p, s->bm.roff.p, s->bm.nrec, n_counted, "bwams_qc_add_batch");
+    DevRecords R;
+    if (int rc = consumer_batch(q, b, "bwams_qc_add_batch", &R)) return rc;
+    return qc_add(q, R, n_counted, "bwams_qc_add_batch");
 }
 
 int bwams_qc_add_records(bwams_qc_t *q, const void *bam, int64_t n_bytes, int64_t *n_counted) {
-    if (!q || n_bytes < 0 || (n_bytes && !bam)) {
-        set_last_error("bwams_qc_add_records: a handle and host records are required");
-        return BWAMS_ERR_ARG;
-    }
-    std::vector<int64_t> off;
-    int32_t max_rid = -1;
-    if (int rc = bam_record_offsets("bwams_qc_add_records", bam, n_bytes, &off, &max_rid)) return rc;
-    const int64_t n_rec = (int64_t)off.size() - 1;
-    BWAMS_HIP(hipSetDevice(q->device));
-    hipStream_t st = q->stream;
-    BWAMS_HIP(q->recs.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(q->roff.ensure_n((size_t)n_rec + 1));
-    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(q->recs.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(q->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here when the add returns early
-    return qc_add(q, q->recs.p, q->roff.p, n_rec, n_counted, "bwams_qc_add_records");
+    DevRecords R;
+    if (int rc = consumer_records(q, bam, n_bytes, "bwams_qc_add_records", &R)) return rc;
+    return qc_add(q, R, n_counted, "bwams_qc_add_records");
 }
 
 int bwams_qc_summary(bwams_qc_t *q, bwams_qc_summary_t *out) {

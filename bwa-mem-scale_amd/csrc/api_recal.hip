@@ -8,7 +8,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "stage_state.h"
+#include "rec_consumer.h"
 #include "../host/dup_groups.h"
 #include "../host/recal_host.h"
 
@@ -18,9 +18,7 @@ namespace {
 constexpr int kCallWords = 8;                        // a piece's words of bwams_recal::call behind the first (kRecalCall*)
 }
 
-struct bwams_recal {
-    int device = 0, cu_count = 0;
-    hipStream_t stream = nullptr;
+struct bwams_recal : RecConsumer {
     bwams_recal_opt_t opt{};
     std::vector<int32_t> l_ref;
     std::vector<int64_t> ref_word;                   // n_ref + 1: reference r's first word of the store; the last is the number of words
@@ -38,8 +36,6 @@ struct bwams_recal {
     DevBuf<uint32_t> keys, keys2, vals, vals2, key_first;        // the (key, record) entries of a piece, twice for the sort
     DevBuf<int64_t> item_first;
     DevBuf<> tmp;                                    // rocPRIM temporary storage
-    DevBuf<uint8_t> recs;                            // bwams_recal_add_records: the uploaded records and their offsets
-    DevBuf<int64_t> roff;
     DevBuf<uint8_t> codes;                           // bwams_recal_set_ref: the uploaded codes
     DevBuf<bwams_recal_site_t> sites;                // bwams_recal_add_known: the uploaded intervals
     DevBuf<int64_t> hole_off;                        // bwams_recal_set_ref_index: the index's .amb holes
@@ -47,19 +43,12 @@ struct bwams_recal {
     int64_t n_added = 0;                             // records given so far (rule 8)
     int64_t last[3] = {0, 0, 0};                     // of the last add: records given, records counted, bases observed
     int last_lds = 1;                                // ... the path it took
-    float ms_check = 0, ms_add = 0;                  // ... and its device time, between the events below
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms_check = 0, ms_add = 0;                  // ... and its device time
     int32_t n_ref() const { return (int32_t)l_ref.size(); }
     int64_t n_words() const { return ref_word.back(); }
     uint32_t n_keys() const { return 2u * (uint32_t)(lay.n_rg + 1); }
     RecalStore dev_store() const { return RecalStore{store.p, d_ref_word.p, d_l_ref.p}; }
     RecalFilter filter() const { return RecalFilter{opt.exclude, opt.min_mapq, opt.min_baseq, opt.max_cycle, n_ref()}; }
-    ~bwams_recal() {
-        (void)hipSetDevice(device);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace bwams {
@@ -71,15 +60,15 @@ namespace {
 
 constexpr int64_t kPiece = 1 << 24;                  // records keyed and sorted at a time: 16 bytes of scratch per record
 
-// check first, then add (rule 5): the records at dev_bam + dev_off[r]
-int recal_add(bwams_recal *r, const uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, int64_t *n_counted, const char *who) {
+// check first, then add (rule 5)
+int recal_add(bwams_recal *r, const DevRecords &R, int64_t *n_counted, const char *who) {
+    const int64_t n_rec = R.n_rec;
     if (r->n_added + n_rec > 0x7FFFFFFFLL) {
         set_last_error(std::string(who) + ": more than 2^31 - 1 records added in total");
         return BWAMS_ERR_UNSUPPORTED;
     }
     hipStream_t st = r->stream;
     int64_t counted = 0, bases = 0;
-    float ms = 0;
     r->ms_check = r->ms_add = 0;
     const int lds = knobs().recal_lds != 0;
     if (n_rec > 0) {
@@ -87,20 +76,13 @@ int recal_add(bwams_recal *r, const uint8_t *dev_bam, const int64_t *dev_off, in
         const RecalStore S = r->dev_store();
         const uint32_t n_keys = r->n_keys();
         unsigned long long h[kCallWords];
-        BWAMS_HIP(hipMemsetAsync(r->call.p, 0xFF, 8, st));
-        BWAMS_HIP(hipEventRecord(r->ev[0], st));
-        launch_recal_check(dev_bam, dev_off, n_rec, f, r->G.walk, r->call.p, r->cu_count, st);
-        BWAMS_HIP(hipEventRecord(r->ev[1], st));
-        BWAMS_HIP(hipMemcpyAsync(h, r->call.p, 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
-        BWAMS_HIP(hipGetLastError());
-        BWAMS_HIP(hipEventElapsedTime(&r->ms_check, r->ev[0], r->ev[1]));
+        if (int rc = consumer_check(r, r->call.p, 1, h, &r->ms_check,
+                                    [&] { launch_recal_check(R.bam, R.off, n_rec, f, r->G.walk, r->call.p, r->cu_count, st); })) return rc;
         if (h[0] != ~0ULL) {
             static const char *const why[5] = {" has a CIGAR op code above 8 (op)", " has a CIGAR whose query length is not l_seq (length)",
                                                " ends inside its SEQ or QUAL (bounds)", " is longer than max_cycle (cycle)",
                                                " has aux fields that do not chain to its end (aux)"};
-            set_last_error(std::string(who) + ": record " + std::to_string(h[0] >> 3) + why[h[0] & 7]);
-            return BWAMS_ERR_ARG;
+            return consumer_refuse_packed(who, h[0], why);
         }
         unsigned bits = 1;
         while ((1ULL << bits) <= n_keys) ++bits;                         // the keys are 0 .. n_keys
@@ -116,25 +98,21 @@ int recal_add(bwams_recal *r, const uint8_t *dev_bam, const int64_t *dev_off, in
         for (int64_t r0 = 0; r0 < n_rec; r0 += kPiece) {
             const int64_t n = std::min(kPiece, n_rec - r0);
             unsigned long long *call = r->call.p + 1;
-            BWAMS_HIP(hipMemsetAsync(call, 0, kCallWords * 8, st));
-            BWAMS_HIP(hipEventRecord(r->ev[0], st));
-            launch_recal_records(dev_bam, dev_off + r0, n, f, r->G, n_keys, r->keys.p, r->vals.p, call, r->cu_count, st);
-            if (lds) {
-                if (int rc = with_tmp(r->tmp, st, (std::string(who) + ": radix_sort_pairs").c_str(), [&](void *tmp, size_t &tb) {
-                        return rocprim::radix_sort_pairs(tmp, tb, r->keys.p, r->keys2.p, r->vals.p, r->vals2.p, (size_t)n, 0u, bits, st);
-                    })) return rc;
-                launch_recal_items(r->keys2.p, n, n_keys, call + kRecalCallMaxLen, r->key_first.p, r->item_first.p, call + kRecalCallItems, st);
-                launch_recal_bases(dev_bam, dev_off + r0, n, f, S, r->lay, r->vals2.p, n_keys, r->key_first.p, r->item_first.p,
-                                   call + kRecalCallItems, r->tables.p, call, r->cu_count, st);
-            } else {
-                launch_recal_plain(dev_bam, dev_off + r0, n, f, S, r->lay, r->keys.p, n_keys, r->tables.p, call, r->cu_count, st);
-            }
-            BWAMS_HIP(hipEventRecord(r->ev[1], st));
-            BWAMS_HIP(hipMemcpyAsync(h, call, kCallWords * 8, hipMemcpyDeviceToHost, st));
-            BWAMS_HIP(hipStreamSynchronize(st));
-            BWAMS_HIP(hipGetLastError());
-            BWAMS_HIP(hipEventElapsedTime(&ms, r->ev[0], r->ev[1]));
-            r->ms_add += ms;
+            if (int rc = consumer_piece(r, call, kCallWords, h, &r->ms_add, [&]() -> int {
+                    launch_recal_records(R.bam, R.off + r0, n, f, r->G, n_keys, r->keys.p, r->vals.p, call, r->cu_count, st);
+                    if (lds) {
+                        if (int rc = with_tmp(r->tmp, st, (std::string(who) + ": radix_sort_pairs").c_str(), [&](void *tmp, size_t &tb) {
+                                return rocprim::radix_sort_pairs(tmp, tb, r->keys.p, r->keys2.p, r->vals.p, r->vals2.p, (size_t)n, 0u, bits, st);
+                            })) return rc;
+                        launch_recal_items(r->keys2.p, n, n_keys, call + kRecalCallMaxLen, r->key_first.p, r->item_first.p,
+                                           call + kRecalCallItems, st);
+                        launch_recal_bases(R.bam, R.off + r0, n, f, S, r->lay, r->vals2.p, n_keys, r->key_first.p, r->item_first.p,
+                                           call + kRecalCallItems, r->tables.p, call, r->cu_count, st);
+                    } else {
+                        launch_recal_plain(R.bam, R.off + r0, n, f, S, r->lay, r->keys.p, n_keys, r->tables.p, call, r->cu_count, st);
+                    }
+                    return BWAMS_OK;
+                })) return rc;
             counted += (int64_t)h[kRecalCallCounted];
             bases += (int64_t)h[kRecalCallBases];
         }
@@ -177,19 +155,14 @@ int bwams_recal_open(int device, const int32_t *l_ref, int32_t n_ref, const bwam
         set_last_error("bwams_recal_open: more than 2^24 read groups");
         return BWAMS_ERR_UNSUPPORTED;
     }
-    if (int rc = check_device(device)) return rc;
-    BWAMS_HIP(hipSetDevice(device));
     std::unique_ptr<bwams_recal> r(new bwams_recal());
-    r->device = device;
+    if (int rc = r->open(device)) return rc;
     r->opt = opt ? *opt : bwams_recal_opt_t{0x704, 1, 6, 500, 0};
     r->l_ref.assign(l_ref, l_ref + n_ref);
     r->ref_word.assign((size_t)n_ref + 1, 0);
     for (int32_t k = 0; k < n_ref; ++k) r->ref_word[(size_t)k + 1] = r->ref_word[(size_t)k] + ((int64_t)l_ref[k] + 7) / 8;
     if (groups) r->ids = groups->ids;
     r->lay = RecalLayout{(int32_t)r->ids.size(), r->opt.max_cycle};
-    BWAMS_HIP(hipDeviceGetAttribute(&r->cu_count, hipDeviceAttributeMultiprocessorCount, device));
-    BWAMS_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : r->ev) BWAMS_HIP(hipEventCreate(&e));
     hipStream_t st = r->stream;
     const size_t words = (size_t)std::max<int64_t>(r->n_words(), 1), n_keys = r->n_keys();
     BWAMS_HIP(r->store.alloc(words * 4));                                // rule 1: BWAMS_ERR_NOMEM when they do not fit
@@ -223,37 +196,15 @@ int bwams_recal_reset(bwams_recal_t *r) {
 }
 
 int bwams_recal_add_batch(bwams_recal_t *r, bwams_batch_t *b, int64_t *n_counted) {
-    if (!r || !b || !b->stages || !b->stages->bm.done) {
-        set_last_error("bwams_recal_add_batch: run bwams_bam_run or bwams_bam_upload first");
-        return BWAMS_ERR_ARG;
-    }
-    if (b->idx->device != r->device) {
-        set_last_error("bwams_recal_add_batch: the handle is on device " + std::to_string(r->device) + ", the batch on device " +
-                       std::to_string(b->idx->device));
-        return BWAMS_ERR_ARG;
-    }
-    BWAMS_HIP(hipSetDevice(r->device));
-    BWAMS_HIP(hipStreamSynchronize(b->stream));              // the records may still be written by queued work
-    StageState *s = b->stages;
-    return recal_add(r, s->bm.out.p, s->bm.roff.p, s->bm.nrec, n_counted, "bwams_recal_add_batch");
+    DevRecords R;
+    if (int rc = consumer_batch(r, b, "bwams_recal_add_batch", &R)) return rc;
+    return recal_add(r, R, n_counted, "bwams_recal_add_batch");
 }
 
 int bwams_recal_add_records(bwams_recal_t *r, const void *bam, int64_t n_bytes, int64_t *n_counted) {
-    if (!r || n_bytes < 0 || (n_bytes && !bam)) {
-        set_last_error("bwams_recal_add_records: a handle and host records are required");
-        return BWAMS_ERR_ARG;
-    }
-    std::vector<int64_t> off;
-    int32_t max_rid = -1;
-    if (int rc = bam_record_offsets("bwams_recal_add_records", bam, n_bytes, &off, &max_rid)) return rc;
-    const int64_t n_rec = (int64_t)off.size() - 1;
-    BWAMS_HIP(hipSetDevice(r->device));
-    hipStream_t st = r->stream;
-    BWAMS_HIP(r->recs.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(r->roff.ensure_n((size_t)n_rec + 1));
-    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(r->recs.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(r->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here when the add returns early
-    return recal_add(r, r->recs.p, r->roff.p, n_rec, n_counted, "bwams_recal_add_records");
+    DevRecords R;
+    if (int rc = consumer_records(r, bam, n_bytes, "bwams_recal_add_records", &R)) return rc;
+    return recal_add(r, R, n_counted, "bwams_recal_add_records");
 }
 
 int bwams_recal_set_ref(bwams_recal_t *r, int32_t ref, const uint8_t *codes) {

@@ -6,15 +6,13 @@
 #include <cstring>
 #include <memory>
 
-#include "stage_state.h"
+#include "rec_consumer.h"
 #include "../host/dup_groups.h"
 #include "../host/recal_model_host.h"
 
 using namespace bwams;
 
-struct bwams_recal_apply {
-    int device = 0, cu_count = 0;
-    hipStream_t stream = nullptr;
+struct bwams_recal_apply : RecConsumer {
     int32_t n_rg = 0;
     RecalModelDev M{};
     MdGroupsDev G{};
@@ -25,71 +23,49 @@ struct bwams_recal_apply {
     DevBuf<int64_t> g_off;
     DevBuf<int32_t> g_ord, g_lib;
     DevBuf<uint32_t> keys;                           // the keys of a piece
-    DevBuf<uint8_t> recs;                            // bwams_recal_apply_records: the uploaded records and their offsets
-    DevBuf<int64_t> roff;
     int64_t model_bytes = 0;
     int64_t last[2] = {0, 0};                        // of the last apply: records given, records rewritten
-    float ms_check = 0, ms_apply = 0;                // ... and its device time, between the events below
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms_check = 0, ms_apply = 0;                // ... and its device time
     uint32_t n_keys() const { return 2u * (uint32_t)(n_rg + 1); }
-    ~bwams_recal_apply() {
-        (void)hipSetDevice(device);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
 
 constexpr int64_t kPiece = 1 << 24;                  // records keyed at a time: 4 bytes of scratch per record
 
-// rule B over the records at dev_bam + dev_off[r]: BWAMS_OK, or the refusal
-int apply_check(bwams_recal_apply *a, const uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, const char *who) {
+// rule B over the records: BWAMS_OK, or the refusal
+int apply_check(bwams_recal_apply *a, const DevRecords &R, const char *who) {
     hipStream_t st = a->stream;
     a->ms_check = 0;
-    if (n_rec <= 0) return BWAMS_OK;
+    if (R.n_rec <= 0) return BWAMS_OK;
     unsigned long long h = 0;
-    BWAMS_HIP(hipMemsetAsync(a->call.p, 0xFF, 8, st));
-    BWAMS_HIP(hipEventRecord(a->ev[0], st));
-    launch_recal_apply_check(dev_bam, dev_off, n_rec, a->M, a->G.walk, a->call.p, a->cu_count, st);
-    BWAMS_HIP(hipEventRecord(a->ev[1], st));
-    BWAMS_HIP(hipMemcpyAsync(&h, a->call.p, 8, hipMemcpyDeviceToHost, st));
-    BWAMS_HIP(hipStreamSynchronize(st));
-    BWAMS_HIP(hipGetLastError());
-    BWAMS_HIP(hipEventElapsedTime(&a->ms_check, a->ev[0], a->ev[1]));
-    if (h != ~0ULL) {
-        const unsigned why = (unsigned)(h & 7);
-        const char *text = why == kRecalBadBounds ? " ends inside its SEQ or QUAL (bounds)"
-                           : why == kRecalBadCycle ? " is longer than the model's max_cycle (cycle)"
-                                                   : " has aux fields that do not chain to its end (aux)";
-        set_last_error(std::string(who) + ": record " + std::to_string(h >> 3) + text);
-        return BWAMS_ERR_ARG;
+    if (int rc = consumer_check(a, a->call.p, 1, &h, &a->ms_check, [&] {
+            launch_recal_apply_check(R.bam, R.off, R.n_rec, a->M, a->G.walk, a->call.p, a->cu_count, st);
+        })) return rc;
+    if (h != ~0ULL) {                                                    // by kRecalBad*: rule B has neither of the first two
+        static const char *const why[5] = {"", "", " ends inside its SEQ or QUAL (bounds)", " is longer than the model's max_cycle (cycle)",
+                                           " has aux fields that do not chain to its end (aux)"};
+        return consumer_refuse_packed(who, h, why);
     }
     return BWAMS_OK;
 }
 
 // rule C over records that apply_check let through (these, or a copy of them in another order)
-int apply_rewrite(bwams_recal_apply *a, uint8_t *dev_bam, const int64_t *dev_off, int64_t n_rec, int64_t *n_rewritten) {
+int apply_rewrite(bwams_recal_apply *a, const DevRecords &R, int64_t *n_rewritten) {
     hipStream_t st = a->stream;
     const uint32_t n_keys = a->n_keys();
+    const int64_t n_rec = R.n_rec;
     int64_t rewritten = 0;
-    float ms = 0;
     a->ms_apply = 0;
     if (n_rec > 0) BWAMS_HIP(a->keys.ensure_n((size_t)std::min(kPiece, n_rec)));
     for (int64_t r0 = 0; r0 < n_rec; r0 += kPiece) {
         const int64_t n = std::min(kPiece, n_rec - r0);
         unsigned long long *n_taken = a->call.p + 1, h = 0;
-        BWAMS_HIP(hipMemsetAsync(n_taken, 0, 8, st));
-        BWAMS_HIP(hipEventRecord(a->ev[0], st));
-        launch_recal_apply_records(dev_bam, dev_off + r0, n, a->M, a->G, n_keys, a->keys.p, n_taken, a->cu_count, st);
-        launch_recal_apply(dev_bam, dev_off + r0, n, a->M, a->keys.p, n_keys, a->cu_count, st);
-        BWAMS_HIP(hipEventRecord(a->ev[1], st));
-        BWAMS_HIP(hipMemcpyAsync(&h, n_taken, 8, hipMemcpyDeviceToHost, st));
-        BWAMS_HIP(hipStreamSynchronize(st));
-        BWAMS_HIP(hipGetLastError());
-        BWAMS_HIP(hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
-        a->ms_apply += ms;
+        if (int rc = consumer_piece(a, n_taken, 1, &h, &a->ms_apply, [&] {
+                launch_recal_apply_records(R.bam, R.off + r0, n, a->M, a->G, n_keys, a->keys.p, n_taken, a->cu_count, st);
+                launch_recal_apply(R.bam, R.off + r0, n, a->M, a->keys.p, n_keys, a->cu_count, st);
+                return BWAMS_OK;
+            })) return rc;
         rewritten += (int64_t)h;
     }
     a->last[0] = n_rec; a->last[1] = rewritten;
@@ -184,14 +160,9 @@ int bwams_recal_apply_open(int device, const bwams_recal_model_t *m, const bwams
                        (groups ? std::to_string(groups->ids.size()) : std::string("is missing")));
         return BWAMS_ERR_ARG;
     }
-    if (int rc = check_device(device)) return rc;
-    BWAMS_HIP(hipSetDevice(device));
     std::unique_ptr<bwams_recal_apply> a(new bwams_recal_apply());
-    a->device = device;
+    if (int rc = a->open(device)) return rc;
     a->n_rg = m->n_rg;
-    BWAMS_HIP(hipDeviceGetAttribute(&a->cu_count, hipDeviceAttributeMultiprocessorCount, device));
-    BWAMS_HIP(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : a->ev) BWAMS_HIP(hipEventCreate(&e));
     hipStream_t st = a->stream;
     BWAMS_HIP(a->call.alloc(2 * 8));
     if (int rc = model_upload(a->b, m->b, st)) return rc;
@@ -211,48 +182,27 @@ int bwams_recal_apply_close(bwams_recal_apply_t *a) {
 }
 
 int bwams_recal_apply_records(bwams_recal_apply_t *a, void *bam, int64_t n_bytes, int64_t *n_rewritten) {
-    if (!a || n_bytes < 0 || (n_bytes && !bam)) {
-        set_last_error("bwams_recal_apply_records: a handle and host records are required");
-        return BWAMS_ERR_ARG;
-    }
-    std::vector<int64_t> off;
-    int32_t max_rid = -1;
-    if (int rc = bam_record_offsets("bwams_recal_apply_records", bam, n_bytes, &off, &max_rid)) return rc;
-    const int64_t n_rec = (int64_t)off.size() - 1;
-    BWAMS_HIP(hipSetDevice(a->device));
-    hipStream_t st = a->stream;
-    BWAMS_HIP(a->recs.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(a->roff.ensure_n((size_t)n_rec + 1));
-    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(a->recs.p, bam, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipMemcpyAsync(a->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-    BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here when the check returns early
-    if (int rc = apply_check(a, a->recs.p, a->roff.p, n_rec, "bwams_recal_apply_records")) return rc;
-    if (int rc = apply_rewrite(a, a->recs.p, a->roff.p, n_rec, n_rewritten)) return rc;
-    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(bam, a->recs.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
-    BWAMS_HIP(hipStreamSynchronize(st));
+    DevRecords R;
+    if (int rc = consumer_records(a, bam, n_bytes, "bwams_recal_apply_records", &R)) return rc;
+    if (int rc = apply_check(a, R, "bwams_recal_apply_records")) return rc;
+    if (int rc = apply_rewrite(a, R, n_rewritten)) return rc;
+    if (n_bytes) BWAMS_HIP(hipMemcpyAsync(bam, R.bam, (size_t)n_bytes, hipMemcpyDeviceToHost, a->stream));
+    BWAMS_HIP(hipStreamSynchronize(a->stream));
     return BWAMS_OK;
 }
 
 int bwams_recal_apply_batch(bwams_recal_apply_t *a, bwams_batch_t *b, int64_t *n_rewritten) {
-    if (!a || !b || !b->stages || !b->stages->bm.done) {
-        set_last_error("bwams_recal_apply_batch: run bwams_bam_run or bwams_bam_upload first");
-        return BWAMS_ERR_ARG;
-    }
-    if (b->idx->device != a->device) {
-        set_last_error("bwams_recal_apply_batch: the handle is on device " + std::to_string(a->device) + ", the batch on device " +
-                       std::to_string(b->idx->device));
-        return BWAMS_ERR_ARG;
-    }
-    BWAMS_HIP(hipSetDevice(a->device));
-    BWAMS_HIP(hipStreamSynchronize(b->stream));              // the records may still be written by queued work
-    StageState *s = b->stages;
-    if (int rc = apply_check(a, s->bm.out.p, s->bm.roff.p, s->bm.nrec, "bwams_recal_apply_batch")) return rc;
+    DevRecords R;
+    StageState *s = nullptr;
+    if (int rc = consumer_batch(a, b, "bwams_recal_apply_batch", &R, nullptr, &s)) return rc;
+    if (int rc = apply_check(a, R, "bwams_recal_apply_batch")) return rc;
     int64_t n = 0;
     float ms = 0;
     if (s->bs.done) {                                        // the sorted copy holds the same records: the check above covers it
-        if (int rc = apply_rewrite(a, s->bs.out.p, s->bs.off.p, s->bs.nrec, &n)) return rc;
+        if (int rc = apply_rewrite(a, DevRecords{s->bs.out.p, s->bs.off.p, s->bs.nrec}, &n)) return rc;
         ms = a->ms_apply;
     }
-    if (int rc = apply_rewrite(a, s->bm.out.p, s->bm.roff.p, s->bm.nrec, &n)) return rc;
+    if (int rc = apply_rewrite(a, R, &n)) return rc;
     a->ms_apply += ms;
     s->md.done = s->md.loc_done = false;                     // the templates' scores are sums of the old qualities
     if (n_rewritten) *n_rewritten = n;

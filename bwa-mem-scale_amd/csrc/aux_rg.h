@@ -1,6 +1,6 @@
 // aux_rg.h — a record's read group on the device (markdup rule 9, recalibration rule 6): the walk over the aux fields by their types to
 // the record's first RG:Z value, and that value's ordinal in the groups table (MdGroupsDev, common.h).  markdup.hip's md_loc_kernel
-// and recal.hip share them; qc.hip shares aux_size.
+// and recal.hip share them; recal.hip and recal_apply.hip share the key made of it; qc.hip shares aux_size.
 #pragma once
 #include "bam_rec.h"
 
@@ -61,6 +61,22 @@ __device__ __forceinline__ int32_t groups_find(const MdGroupsDev &G, const uint8
         else hi = mid;
     }
     return -1;
+}
+
+// The key that recalibration counts and rewrites the record at p under (rule 6): 2 * its read group's ordinal, the group after the
+// table's last when it has no RG:Z or one the table does not hold, + 1 for the second read of a pair (its cycles are negative).  The
+// aux fields were walked once already, by the check kernel.
+__device__ __forceinline__ uint32_t rg_key(const uint8_t *p, const MdGroupsDev &G) {
+    int32_t g = G.n_rg;
+    if (G.walk) {
+        bool found;
+        int64_t v0, v1;
+        if (aux_first_rg(p, &found, &v0, &v1) && found) {
+            const int32_t rg = groups_find(G, p + v0, v1 - v0);
+            if (rg >= 0) g = rg;
+        }
+    }
+    return 2u * (uint32_t)g + ((bam_flag(p) & 0x81) == 0x81 ? 1u : 0u);
 }
 
 }  // namespace bwams

@@ -323,12 +323,6 @@ __global__ void __launch_bounds__(256) bam_read_off_kernel(BamArgs A, int64_t *b
     }
 }
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * 16;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 }  // namespace
 
 void launch_bam_count(const BamArgs &A, int cu_count, hipStream_t st) {

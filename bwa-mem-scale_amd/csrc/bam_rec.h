@@ -21,6 +21,10 @@ __device__ __forceinline__ uint32_t bam_mapq(const uint8_t *p) { return p[13]; }
 __device__ __forceinline__ uint32_t bam_n_cig(const uint8_t *p) { return ld_u16(p + 16); }
 __device__ __forceinline__ uint32_t bam_flag(const uint8_t *p) { return ld_u16(p + 18); }
 __device__ __forceinline__ int32_t bam_l_seq(const uint8_t *p) { return (int32_t)ld_u32(p + 20); }
+__device__ __forceinline__ int32_t bam_next_ref_id(const uint8_t *p) { return (int32_t)ld_u32(p + 24); }
+__device__ __forceinline__ int32_t bam_next_pos(const uint8_t *p) { return (int32_t)ld_u32(p + 28); }
+__device__ __forceinline__ int32_t bam_tlen(const uint8_t *p) { return (int32_t)ld_u32(p + 32); }
+__device__ __forceinline__ int64_t bam_end(const uint8_t *p) { return 4 + (int64_t)bam_block_size(p); }   // the record's end, as an offset from p
 // where the variable-length fields start, as offsets from p
 constexpr int kBamName = 36;
 __device__ __forceinline__ int64_t bam_cigar_at(uint32_t l_name) { return kBamName + (int64_t)l_name; }
@@ -28,16 +32,26 @@ __device__ __forceinline__ int64_t bam_seq_at(uint32_t l_name, uint32_t n_cig) {
 __device__ __forceinline__ int64_t bam_qual_at(uint32_t l_name, uint32_t n_cig, int64_t l_seq) { return bam_seq_at(l_name, n_cig) + (l_seq + 1) / 2; }
 __device__ __forceinline__ int64_t bam_aux_at(uint32_t l_name, uint32_t n_cig, int64_t l_seq) { return bam_qual_at(l_name, n_cig, l_seq) + l_seq; }
 
+// QUAL is there: its first byte is not 0xFF (l_seq > 0)
+__device__ __forceinline__ bool bam_has_qual(const uint8_t *p, uint32_t l_name, uint32_t n_cig, int64_t l_seq) {
+    return p[bam_qual_at(l_name, n_cig, l_seq)] != 0xFF;
+}
+
 // SEQ: the 4-bit code of base i; A C G T (codes 1 2 4 8) as 0..3, -1 for any other code
 __device__ __forceinline__ uint32_t seq_code(const uint8_t *seq, int32_t i) { return (seq[i >> 1] >> ((i & 1) ? 0 : 4)) & 15; }
 __device__ __forceinline__ int base_of_code(uint32_t code) { return code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1; }
 
-// reference bases the CIGAR operations first, first + stride, ... of c[0, n_cig) cover (M, D, N, =, X)
+// CIGAR op codes: the ones that take reference positions (M D N = X), query bases (M I S = X), both as a match or mismatch (M = X)
+__device__ __forceinline__ bool op_takes_ref(uint32_t o) { return o == 0 || o == 2 || o == 3 || o == 7 || o == 8; }
+__device__ __forceinline__ bool op_takes_query(uint32_t o) { return o == 0 || o == 1 || o == 4 || o == 7 || o == 8; }
+__device__ __forceinline__ bool op_is_match(uint32_t o) { return o == 0 || o == 7 || o == 8; }
+
+// reference bases the CIGAR operations first, first + stride, ... of c[0, n_cig) cover
 __device__ __forceinline__ int64_t cigar_ref_len(const uint8_t *c, uint32_t n_cig, uint32_t first, uint32_t stride) {
     int64_t rlen = 0;
     for (uint32_t k = first; k < n_cig; k += stride) {
         const uint32_t op = ld_u32(c + 4 * k), o = op & 15;
-        if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rlen += op >> 4;
+        if (op_takes_ref(o)) rlen += op >> 4;
     }
     return rlen;
 }

@@ -83,12 +83,6 @@ __global__ void __launch_bounds__(256) bam_sort_gather_kernel(const uint8_t *src
     }
 }
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * 16;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 }  // namespace
 
 int bam_sort_bits(uint32_t n_ref) {                          // bits of the device key: POS + 1 and the strand, then refID in [0, n_ref]

@@ -272,6 +272,13 @@ void launch_md_gather32(const uint32_t *src, const uint32_t *idx, int64_t n, uin
 // the largest refID; BWAMS_ERR_ARG with `who` and the first bad record in the last error.
 int bam_record_offsets(const char *who, const void *bam, int64_t n_bytes, std::vector<int64_t> *offsets, int32_t *max_rid);
 
+// The grid of a grid-stride launch: a block per per_block items, at least one and at most per_cu for each compute unit.
+inline unsigned grid_of(int64_t items, int64_t per_block, int cu_count, int per_cu = 16) {
+    int64_t g = (items + per_block - 1) / per_block;
+    const int64_t cap = (int64_t)cu_count * per_cu;
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
 // depth.hip: depth of coverage (rules in include/bwams.h above bwams_depth_open).  slots: l_ref[r] + 1 int32 per reference from
 // slot_off[r] (n_ref + 1 entries, device); differences while records are added, depths after the scan.  check: *bad = min(*bad, index
 // of a record with an op code above 8).  add: rule 2's filter and rule 3's stretches of the records at bam + rec_off[r]; *n_counted +=
@@ -385,6 +392,8 @@ int groups_upload(DevBuf<uint8_t> &g_ids, DevBuf<int64_t> &g_off, DevBuf<int32_t
 // the largest l_seq (call + kRecalCallMaxLen).  After a sort by key: heads / items turn the sorted keys into the item table of the
 // base kernel; bases: the default path; plain: BWAMS_RECAL_LDS=0.
 constexpr int kRecalQuals = 94, kRecalContexts = 16;
+// rule 6's context of a base b behind its neighbour in sequencing order nb (both 0..3): as read, or complemented under FLAG 0x10
+__device__ __forceinline__ int recal_context(int nb, int b, bool rev) { return rev ? 4 * (3 - nb) + (3 - b) : 4 * nb + b; }
 constexpr int kRecalSlice = 1024;        // records of one key that a workgroup of the base kernel counts in LDS before it flushes (below 65536: 16-bit cells)
 enum { kRecalBadOp = 0, kRecalBadLength = 1, kRecalBadBounds = 2, kRecalBadCycle = 3, kRecalBadAux = 4 };
 enum { kRecalCallCounted = 0, kRecalCallBases = 1, kRecalCallItems = 2, kRecalCallMaxLen = 4 };

@@ -32,12 +32,6 @@
 namespace bwams {
 namespace {
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * 16;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 __global__ void __launch_bounds__(256) depth_check_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec,
                                                           unsigned long long *bad) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
@@ -107,7 +101,7 @@ __global__ void __launch_bounds__(256) depth_add_kernel(const uint8_t *bam, cons
                 const uint32_t op = ld_u32(c + 4 * k);
                 const uint32_t o = op & 15;
                 const int64_t len = op >> 4;
-                const bool covers = o == 0 || o == 7 || o == 8 || (o == 2 && f.count_deletions);
+                const bool covers = o == 0 || o == 7 || o == 8 || (o == 2 && f.count_deletions);     // spelled out: op_is_match here costs 45 instructions
                 if (covers) {
                     if (!open) { open = true; beg = x; }
                     x += len;

@@ -529,12 +529,6 @@ __global__ void __launch_bounds__(256) md_opt_mark_kernel(const bwams_dup_end_t 
     }
 }
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * 16;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 int bit_width(uint64_t x) {
     int w = 0;
     while (w < 64 && (x >> w) != 0) ++w;

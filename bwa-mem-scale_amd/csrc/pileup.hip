@@ -34,16 +34,6 @@
 namespace bwams {
 namespace {
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * 16;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
-__device__ __forceinline__ bool op_takes_ref(uint32_t o) { return o == 0 || o == 2 || o == 3 || o == 7 || o == 8; }
-__device__ __forceinline__ bool op_takes_query(uint32_t o) { return o == 0 || o == 1 || o == 4 || o == 7 || o == 8; }
-__device__ __forceinline__ bool op_is_match(uint32_t o) { return o == 0 || o == 7 || o == 8; }
-
 // rule 2, for a record at p
 __device__ __forceinline__ bool record_counts(const uint8_t *p, const PileupFilter &f) {
     const int32_t rid = bam_ref_id(p);
@@ -68,7 +58,7 @@ __global__ void __launch_bounds__(256) pileup_check_kernel(const uint8_t *bam, c
         if (!record_counts(p, f)) continue;
         const int64_t l_seq = bam_l_seq(p);
         if (qlen != l_seq) atomicMin(bad + 1, (unsigned long long)r);
-        else if (bam_aux_at(bam_l_name(p), n_cig, l_seq) > 4 + (int64_t)bam_block_size(p)) atomicMin(bad + 2, (unsigned long long)r);
+        else if (bam_aux_at(bam_l_name(p), n_cig, l_seq) > bam_end(p)) atomicMin(bad + 2, (unsigned long long)r);
     }
 }
 

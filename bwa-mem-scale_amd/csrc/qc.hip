@@ -33,16 +33,6 @@
 namespace bwams {
 namespace {
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count, int per_cu) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * per_cu;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
-__device__ __forceinline__ int32_t bam_next_ref_id(const uint8_t *p) { return (int32_t)ld_u32(p + 24); }
-__device__ __forceinline__ int32_t bam_next_pos(const uint8_t *p) { return (int32_t)ld_u32(p + 28); }
-__device__ __forceinline__ int32_t bam_tlen(const uint8_t *p) { return (int32_t)ld_u32(p + 32); }
-
 // Rule 1's walk over the aux area a[0, n) and rule 5's NM (-1: no such field); false when the area cannot be walked.
 __device__ __forceinline__ bool aux_walk(const uint8_t *a, int64_t n, int64_t *nm_out) {
     int64_t at = 0, nm = -1;
@@ -88,7 +78,7 @@ __global__ void __launch_bounds__(256) qc_check_kernel(const uint8_t *bam, const
                                                        unsigned long long *bad) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
         const uint8_t *p = bam + rec_off[r];
-        const int64_t end = 4 + (int64_t)bam_block_size(p), l_seq = bam_l_seq(p);
+        const int64_t end = bam_end(p), l_seq = bam_l_seq(p);
         const uint32_t n_cig = bam_n_cig(p), l_name = bam_l_name(p);
         int why = -1;
         if (l_seq < 0 || bam_seq_at(l_name, n_cig) > end) {
@@ -169,7 +159,7 @@ __global__ void __launch_bounds__(256) qc_record_kernel(const uint8_t *bam, cons
                     }
                     const int64_t aux_at = bam_aux_at(l_name, n_cig, l_seq);
                     int64_t nm = -1;
-                    aux_walk(p + aux_at, 4 + (int64_t)bam_block_size(p) - aux_at, &nm);          // rule 1 walked it already
+                    aux_walk(p + aux_at, bam_end(p) - aux_at, &nm);                              // rule 1 walked it already
                     if (nm < 0) ++nm_missing;
                     else nm_sum += nm;
                 }

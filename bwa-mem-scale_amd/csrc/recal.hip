@@ -35,16 +35,6 @@
 namespace bwams {
 namespace {
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count, int per_cu) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * per_cu;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
-__device__ __forceinline__ bool op_takes_ref(uint32_t o) { return o == 0 || o == 2 || o == 3 || o == 7 || o == 8; }
-__device__ __forceinline__ bool op_takes_query(uint32_t o) { return o == 0 || o == 1 || o == 4 || o == 7 || o == 8; }
-__device__ __forceinline__ bool op_is_match(uint32_t o) { return o == 0 || o == 7 || o == 8; }
-
 // rule 4 without its last test (the first QUAL byte), for a record at p
 __device__ __forceinline__ bool head_counts(const uint8_t *p, const RecalFilter &f) {
     const int32_t rid = bam_ref_id(p);
@@ -72,8 +62,8 @@ __global__ void __launch_bounds__(256) recal_check_kernel(const uint8_t *bam, co
             const int64_t l_seq = bam_l_seq(p);
             bool found;
             int64_t v0, v1;
-            if (bam_aux_at(l_name, n_cig, l_seq) > 4 + (int64_t)bam_block_size(p)) why = kRecalBadBounds;
-            else if (p[bam_qual_at(l_name, n_cig, l_seq)] == 0xFF) why = -1;                   // rule 4 skips it
+            if (bam_aux_at(l_name, n_cig, l_seq) > bam_end(p)) why = kRecalBadBounds;
+            else if (!bam_has_qual(p, l_name, n_cig, l_seq)) why = -1;                         // rule 4 skips it
             else if (qlen != l_seq) why = kRecalBadLength;
             else if (l_seq > f.max_cycle) why = kRecalBadCycle;
             else if (walk_aux && !aux_first_rg(p, &found, &v0, &v1)) why = kRecalBadAux;
@@ -93,21 +83,11 @@ __global__ void __launch_bounds__(256) recal_record_kernel(const uint8_t *bam, c
         int32_t len = 0;
         if (r < n_rec) {
             const uint8_t *p = bam + rec_off[r];
-            const uint32_t flag = bam_flag(p);
             const int32_t l_seq = bam_l_seq(p);
-            counted = head_counts(p, f) && p[bam_qual_at(bam_l_name(p), bam_n_cig(p), l_seq)] != 0xFF;
+            counted = head_counts(p, f) && bam_has_qual(p, bam_l_name(p), bam_n_cig(p), l_seq);
             uint32_t key = n_keys;
             if (counted) {
-                int32_t g = G.n_rg;                                      // rule 6: no RG:Z, or one the table does not hold
-                if (G.walk) {
-                    bool found;
-                    int64_t v0, v1;
-                    if (aux_first_rg(p, &found, &v0, &v1) && found) {    // rule 5 walked it already
-                        const int32_t rg = groups_find(G, p + v0, v1 - v0);
-                        if (rg >= 0) g = rg;
-                    }
-                }
-                key = 2u * (uint32_t)g + ((flag & 0x81) == 0x81 ? 1u : 0u);
+                key = rg_key(p, G);                                      // rule 6; rule 5 walked the aux fields already
                 len = l_seq;
             }
             keys[r] = key;
@@ -202,7 +182,7 @@ __device__ __forceinline__ bool recal_base(const RecalStore &S, const RecalRec &
     *q = (int)min(qual, (uint32_t)(kRecalQuals - 1));
     *err = (int)s != b;
     const int nb = base_of_code(ncode);
-    *ctx = nb < 0 ? -1 : v.rev ? 4 * (3 - nb) + (3 - b) : 4 * nb + b;
+    *ctx = nb < 0 ? -1 : recal_context(nb, b, v.rev);
     return true;
 }
 

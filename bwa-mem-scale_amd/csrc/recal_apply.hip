@@ -19,12 +19,6 @@
 namespace bwams {
 namespace {
 
-unsigned grid_of(int64_t items, int64_t per_block, int cu_count, int per_cu) {
-    int64_t g = (items + per_block - 1) / per_block;
-    const int64_t cap = (int64_t)cu_count * per_cu;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 // rule A without its last test (the first QUAL byte)
 __device__ __forceinline__ bool head_taken(const uint8_t *p, uint32_t exclude) { return !(bam_flag(p) & exclude) && bam_l_seq(p) > 0; }
 
@@ -38,8 +32,8 @@ __global__ void __launch_bounds__(256) recal_apply_check_kernel(const uint8_t *b
         int why = -1;
         bool found;
         int64_t v0, v1;
-        if (bam_aux_at(l_name, n_cig, l_seq) > 4 + (int64_t)bam_block_size(p)) why = kRecalBadBounds;
-        else if (p[bam_qual_at(l_name, n_cig, l_seq)] == 0xFF) why = -1;                           // rule A leaves it alone
+        if (bam_aux_at(l_name, n_cig, l_seq) > bam_end(p)) why = kRecalBadBounds;
+        else if (!bam_has_qual(p, l_name, n_cig, l_seq)) why = -1;                                 // rule A leaves it alone
         else if (l_seq > max_cycle) why = kRecalBadCycle;
         else if (walk_aux && !aux_first_rg(p, &found, &v0, &v1)) why = kRecalBadAux;
         if (why >= 0) atomicMin(bad, (unsigned long long)r << 3 | (unsigned)why);
@@ -54,21 +48,8 @@ __global__ void __launch_bounds__(256) recal_apply_record_kernel(const uint8_t *
         bool taken = false;
         if (r < n_rec) {
             const uint8_t *p = bam + rec_off[r];
-            taken = head_taken(p, exclude) && p[bam_qual_at(bam_l_name(p), bam_n_cig(p), bam_l_seq(p))] != 0xFF;
-            uint32_t key = n_keys;
-            if (taken) {
-                int32_t g = G.n_rg;                                      // no RG:Z, or one the table does not hold
-                if (G.walk) {
-                    bool found;
-                    int64_t v0, v1;
-                    if (aux_first_rg(p, &found, &v0, &v1) && found) {    // rule B walked it already
-                        const int32_t rg = groups_find(G, p + v0, v1 - v0);
-                        if (rg >= 0) g = rg;
-                    }
-                }
-                key = 2u * (uint32_t)g + ((bam_flag(p) & 0x81) == 0x81 ? 1u : 0u);
-            }
-            keys[r] = key;
+            taken = head_taken(p, exclude) && bam_has_qual(p, bam_l_name(p), bam_n_cig(p), bam_l_seq(p));
+            keys[r] = taken ? rg_key(p, G) : n_keys;                     // rule B walked the aux fields already
         }
         const uint64_t m = __ballot(taken);
         if (lane == 0 && m) atomicAdd(n_taken, (unsigned long long)__popcll((unsigned long long)m));
@@ -99,7 +80,7 @@ __global__ void __launch_bounds__(256) recal_apply_kernel(uint8_t *bam, const in
             const int32_t c = rev ? l_seq - i : i + 1;
             const int b = base_of_code(code), nb = base_of_code(ncode);  // recalibration rule 6's context, or none
             int v = (int)M.b[row] + M.dc[row * cols + ((key & 1) ? -c : c) + M.max_cycle];
-            if (b >= 0 && nb >= 0) v += M.dx[row * kRecalContexts + (rev ? 4 * (3 - nb) + (3 - b) : 4 * nb + b)];
+            if (b >= 0 && nb >= 0) v += M.dx[row * kRecalContexts + recal_context(nb, b, rev)];
             qual[i] = (uint8_t)(v < 1 ? 1 : v > M.max_q ? M.max_q : v);
         }
     }

@@ -329,6 +329,27 @@ bool member_sizes(const uint8_t *gz, int64_t n, std::vector<int64_t> *sizes) {
     return true;
 }
 
+// bwams_sorter_set_depth, _set_pileup, _set_qc, _set_recal: handle h, a `kind` handle in the texts, goes into *slot; device gives the
+// handle's, l_ref its reference lengths (null: it has none to compare)
+template <class H>
+int sorter_set(bwams_sorter_t *s, H *h, H *bwams_sorter::*slot, const char *who, const std::string &kind, int (*device)(const H *),
+               const std::vector<int32_t> &(*l_ref)(const H *)) {
+    const std::string why = !s || !h ? "a sorter and a " + kind + " handle are required"
+                            : device(h) != s->device ? "the " + kind + " handle is on another device than the sorter"
+                            : l_ref && l_ref(h) != s->l_ref ? "the " + kind + " handle's reference lengths are not the sorter header's" : "";
+    if (!why.empty()) {
+        bwams::set_last_error(std::string(who) + ": " + why);
+        return BWAMS_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->any_put) {
+        bwams::set_last_error(std::string(who) + ": called after the sorter's first put");
+        return BWAMS_ERR_ARG;
+    }
+    s->*slot = h;
+    return BWAMS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -466,70 +487,19 @@ int bwams_sorter_set_markdup(bwams_sorter_t *s, const bwams_dup_groups_t *groups
 }
 
 int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d) {
-    const char *why = !s || !d ? "a sorter and a depth handle are required"
-                      : bwams::depth_device(d) != s->device ? "the depth handle is on another device than the sorter"
-                      : bwams::depth_l_ref(d) != s->l_ref ? "the depth handle's reference lengths are not the sorter header's" : nullptr;
-    if (why) {
-        bwams::set_last_error(std::string("bwams_sorter_set_depth: ") + why);
-        return BWAMS_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->any_put) {
-        bwams::set_last_error("bwams_sorter_set_depth: called after the sorter's first put");
-        return BWAMS_ERR_ARG;
-    }
-    s->depth = d;
-    return BWAMS_OK;
+    return sorter_set(s, d, &bwams_sorter::depth, "bwams_sorter_set_depth", "depth", bwams::depth_device, bwams::depth_l_ref);
 }
 
 int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p) {
-    const char *why = !s || !p ? "a sorter and a pileup handle are required"
-                      : bwams::pileup_device(p) != s->device ? "the pileup handle is on another device than the sorter"
-                      : bwams::pileup_l_ref(p) != s->l_ref ? "the pileup handle's reference lengths are not the sorter header's" : nullptr;
-    if (why) {
-        bwams::set_last_error(std::string("bwams_sorter_set_pileup: ") + why);
-        return BWAMS_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->any_put) {
-        bwams::set_last_error("bwams_sorter_set_pileup: called after the sorter's first put");
-        return BWAMS_ERR_ARG;
-    }
-    s->pileup = p;
-    return BWAMS_OK;
+    return sorter_set(s, p, &bwams_sorter::pileup, "bwams_sorter_set_pileup", "pileup", bwams::pileup_device, bwams::pileup_l_ref);
 }
 
 int bwams_sorter_set_qc(bwams_sorter_t *s, bwams_qc_t *q) {
-    const char *why = !s || !q ? "a sorter and a QC handle are required"
-                      : bwams::qc_device(q) != s->device ? "the QC handle is on another device than the sorter" : nullptr;
-    if (why) {
-        bwams::set_last_error(std::string("bwams_sorter_set_qc: ") + why);
-        return BWAMS_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->any_put) {
-        bwams::set_last_error("bwams_sorter_set_qc: called after the sorter's first put");
-        return BWAMS_ERR_ARG;
-    }
-    s->qc = q;
-    return BWAMS_OK;
+    return sorter_set<bwams_qc_t>(s, q, &bwams_sorter::qc, "bwams_sorter_set_qc", "QC", bwams::qc_device, nullptr);
 }
 
 int bwams_sorter_set_recal(bwams_sorter_t *s, bwams_recal_t *r) {
-    const char *why = !s || !r ? "a sorter and a recalibration handle are required"
-                      : bwams::recal_device(r) != s->device ? "the recalibration handle is on another device than the sorter"
-                      : bwams::recal_l_ref(r) != s->l_ref ? "the recalibration handle's reference lengths are not the sorter header's" : nullptr;
-    if (why) {
-        bwams::set_last_error(std::string("bwams_sorter_set_recal: ") + why);
-        return BWAMS_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->any_put) {
-        bwams::set_last_error("bwams_sorter_set_recal: called after the sorter's first put");
-        return BWAMS_ERR_ARG;
-    }
-    s->recal = r;
-    return BWAMS_OK;
+    return sorter_set(s, r, &bwams_sorter::recal, "bwams_sorter_set_recal", "recalibration", bwams::recal_device, bwams::recal_l_ref);
 }
 
 int bwams_sorter_close3(bwams_sorter_t *s, bwams_sorter_stats_t *stats, bwams_dup_stats_t *dup_stats, bwams_dup_lib_stats_t *lib_stats,
