@@ -64,6 +64,7 @@ SYMBOLS = [
     "bwams_sorter_set_depth",
     "bwams_pileup_open", "bwams_pileup_close", "bwams_pileup_reset", "bwams_pileup_add_batch", "bwams_pileup_add_records", "bwams_pileup_set_ref",
     "bwams_pileup_set_ref_index", "bwams_pileup_fetch", "bwams_pileup_sites", "bwams_pileup_text", "bwams_pileup_info", "bwams_sorter_set_pileup",
+    "bwams_pileup_set_quality", "bwams_pileup_fetch_quality", "bwams_pileup_calls", "bwams_pileup_vcf",
     "bwams_qc_open", "bwams_qc_close", "bwams_qc_reset", "bwams_qc_add_batch", "bwams_qc_add_records", "bwams_qc_summary", "bwams_qc_table",
     "bwams_qc_text", "bwams_qc_info", "bwams_sorter_set_qc",
     "bwams_recal_open", "bwams_recal_close", "bwams_recal_reset", "bwams_recal_add_batch", "bwams_recal_add_records", "bwams_recal_set_ref",
@@ -111,7 +112,9 @@ assert DEPTH_REF_DTYPE.itemsize == 24
 PILEUP_REGION_DTYPE = np.dtype([("ref", "<i4"), ("beg", "<i4"), ("end", "<i4")])                          # bwams_pileup_region_t
 PILEUP_SITE_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("kinds", "<u4"), ("depth", "<u4"),
                               ("c", "<u4", (12,))])                                                      # bwams_pileup_site_t
-assert PILEUP_REGION_DTYPE.itemsize == 12 and PILEUP_SITE_DTYPE.itemsize == 68
+PILEUP_CALL_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("a1", "<i4"), ("a2", "<i4"), ("qual", "<i4"), ("gq", "<i4"),
+                              ("depth", "<u4"), ("n", "<u4", (4,)), ("pl", "<i4", (10,))])               # bwams_pileup_call_t
+assert PILEUP_REGION_DTYPE.itemsize == 12 and PILEUP_SITE_DTYPE.itemsize == 68 and PILEUP_CALL_DTYPE.itemsize == 88
 assert DUP_LOC_DTYPE.itemsize == 24 and DUP_LIB_STATS_DTYPE.itemsize == 72
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
@@ -643,6 +646,10 @@ class PileupOpt(C.Structure):
                 ("min_permille", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PileupGlOpt(C.Structure):
+    _fields_ = [("min_qual", C.c_int32), ("min_depth", C.c_int32), ("no_qual_q", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PileupInfo(C.Structure):
     _fields_ = [("tile", C.c_int32), ("n_regions", C.c_int32), ("n_slots", C.c_int64), ("n_counted", C.c_int64), ("n_entries", C.c_int64),
                 ("n_direct", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
@@ -697,6 +704,35 @@ class Pileup(_Consumer):
     def text(self, names, min_alt: int = -1, min_permille: int = -1) -> str:
         flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
         return _text(lib().bwams_pileup_text, self.h, flat, min_alt, min_permille)
+
+    def set_quality(self, min_qual: int = 20, min_depth: int = 1, no_qual_q: int = 30) -> None:
+        """bwams_pileup_set_quality: the quality plane beside the counters, zeroed; only while the counters are zero."""
+        o = PileupGlOpt(min_qual, min_depth, no_qual_q, 0)
+        _chk(lib().bwams_pileup_set_quality(self.h, C.byref(o)), "bwams_pileup_set_quality")
+
+    def fetch_quality(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:
+        """uint32[end - beg, 12]: the sums Q[A..T], HOM[A..T], HET[A..T] of positions [beg, end) of the region (default: all of it)."""
+        r, b, e = self.regions[region]
+        beg, end = b if beg is None else beg, e if end is None else end
+        out = np.zeros((max(end - beg, 1), 12), np.uint32)
+        _chk(lib().bwams_pileup_fetch_quality(self.h, region, beg, end, _p(out)), "bwams_pileup_fetch_quality")
+        return out[:max(end - beg, 0)]
+
+    def calls(self, min_qual: int = -1, min_depth: int = -1, cap: int | None = None) -> np.ndarray:
+        """PILEUP_CALL_DTYPE records of rule 13; cap: the array's size (default: asked for first).  .n_calls: found or needed."""
+        n = C.c_int64(0)
+        if cap is None:
+            _chk(lib().bwams_pileup_calls(self.h, min_qual, min_depth, None, 0, C.byref(n)), "bwams_pileup_calls")
+            cap = n.value
+        out = np.zeros(max(cap, 1), PILEUP_CALL_DTYPE)
+        rc = lib().bwams_pileup_calls(self.h, min_qual, min_depth, _p(out), cap, C.byref(n))
+        self.n_calls = n.value
+        _chk(rc, "bwams_pileup_calls")
+        return out[:n.value]
+
+    def vcf(self, names, sample, min_qual: int = -1, min_depth: int = -1) -> str:
+        flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
+        return _text(lib().bwams_pileup_vcf, self.h, flat, sample if isinstance(sample, bytes) else sample.encode(), min_qual, min_depth)
 
     def info(self) -> dict:
         """bwams_pileup_info: tile, n_regions, n_slots, and of the last add n_counted, n_entries, n_direct, ms_check, ms_add."""
@@ -1182,6 +1218,10 @@ def lib():
         L.bwams_pileup_text.argtypes = [vp, vp, i32, i32, vp, i64, vp]
         L.bwams_pileup_info.argtypes = [vp, vp]
         L.bwams_sorter_set_pileup.argtypes = [vp, vp]
+        L.bwams_pileup_set_quality.argtypes = [vp, vp]
+        L.bwams_pileup_fetch_quality.argtypes = [vp, i32, i32, i32, vp]
+        L.bwams_pileup_calls.argtypes = [vp, i32, i32, vp, i64, vp]
+        L.bwams_pileup_vcf.argtypes = [vp, vp, C.c_char_p, i32, i32, vp, i64, vp]
         L.bwams_qc_open.argtypes = [C.c_int, vp, vp]
         L.bwams_qc_close.argtypes = [vp]
         L.bwams_qc_reset.argtypes = [vp]

@@ -2,7 +2,9 @@
 
 The rules are numbered in include/bwams.h above bwams_pileup_open; the numbers below are theirs.  Pileup(l_ref, regions, ...)
 accumulates records (BAM records with their block_size, back to back, as bwams/bam.py builds them) into 12 counters per region
-position; fetch, sites and text return what the C-ABI's return.
+position; fetch, sites and text return what the C-ABI's return.  After set_quality the adds also keep rule 11's sums, 12 per position,
+and fetch_quality, calls and vcf restate rules 10 to 13 (csrc/pileup.hip's quality sinks and call kernel, host/pileup_vcf.cpp) in integer
+arithmetic alone.
 """
 from __future__ import annotations
 
@@ -21,6 +23,22 @@ TEXT_HEADER = "chrom\tpos\tref\tdepth\t" + "\t".join(CHANNELS) + "\talt\n"
 _CHANNEL_OF_CODE = np.full(16, N, np.int64)                                             # rule 4: every code but 1 2 4 8 is N
 _CHANNEL_OF_CODE[[1, 2, 4, 8]] = [0, 1, 2, 3]
 _REF_OPS, _QUERY_OPS = (0, 2, 3, 7, 8), (0, 1, 4, 7, 8)
+# Rule 12: the cost, in hundredths of a phred, of a base of effective quality GL_MIN_Q + k under a homozygous and under a heterozygous
+# genotype that holds it (csrc/common.h has the same numbers; tests/test_pileup_calls.py recomputes them); a mismatch costs 100 q + GL_MIS.
+GL_MIN_Q, GL_MAX_Q, GL_MIS = 4, 60, 477
+T_HOM = (220, 165, 126, 97, 75, 58, 46, 36, 28, 22, 18, 14, 11, 9, 7, 6, 4, 3, 3, 2, 2, 1, 1, 1, 1, 1) + (0,) * 31
+T_HET = (435, 404, 381, 363, 350, 339, 331, 325, 320, 316, 313, 310, 308, 307, 306, 305, 304, 303, 303, 302, 302, 302, 302, 302) + (301,) * 33
+Q, HOM, HET = 0, 4, 8                                                                   # rule 11: the sums of base b at these + b
+GENOTYPES = tuple((a1, a2) for a2 in range(4) for a1 in range(a2 + 1))                  # rule 13: index a2 (a2 + 1) / 2 + a1
+CALL_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("a1", "<i4"), ("a2", "<i4"), ("qual", "<i4"), ("gq", "<i4"),
+                       ("depth", "<u4"), ("n", "<u4", (4,)), ("pl", "<i4", (10,))])
+VCF_FIXED = ('##INFO=<ID=DP,Number=1,Type=Integer,Description="Bases counted">\n'
+             '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n'
+             '##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Bases counted per allele">\n'
+             '##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Bases counted">\n'
+             '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality">\n'
+             '##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Genotype costs in phred, the least at 0">\n'
+             "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t")
 
 
 class PileupRefusal(ValueError):
@@ -60,20 +78,36 @@ class Pileup:
             self.slot[r][b:e] = np.arange(self.off[k], self.off[k + 1])
         self.exclude, self.min_mapq, self.min_baseq, self.min_alt, self.min_permille = exclude, min_mapq, min_baseq, min_alt, min_permille
         self.ref = np.full(self.n_slots, 4, np.uint8)                                    # rule 7
+        self.q = None                                                                    # rule 11's plane: none before set_quality
         self.reset()
 
     def reset(self):                                                                     # rule 6
         self.c = np.zeros((self.n_slots, 12), np.int64)
+        if self.q is not None:
+            self.q = np.zeros((self.n_slots, 12), np.int64)
+
+    def set_quality(self, min_qual: int = 20, min_depth: int = 1, no_qual_q: int = 30):
+        """the quality plane, zeroed; only while the counters are zero (BWAMS_ERR_ARG otherwise)"""
+        assert min_qual >= 0 and min_depth >= 1 and 0 <= no_qual_q <= 93 and not self.c.any()
+        self.min_qual, self.min_depth, self.no_qual_q = min_qual, min_depth, no_qual_q
+        self.q = np.zeros((self.n_slots, 12), np.int64)
 
     def counts(self, refid, mapq, flag, cigar, l_seq) -> bool:                           # rule 2
         return (not flag & self.exclude and mapq >= self.min_mapq and 0 <= refid < len(self.l_ref) and len(cigar) > 0 and l_seq > 0)
 
-    def _put(self, refid, pos, channel):
-        """+1 at each (position, channel) whose position lies in a region (rule 4: the others are dropped one by one)"""
+    def _put(self, refid, pos, channel, qe=None):
+        """+1 at each (position, channel) whose position lies in a region (rule 4: the others are dropped one by one); with qe, rule
+        10's effective quality per position, rule 11's three sums of every base in one of the eight base channels too"""
         pos, channel = np.asarray(pos, np.int64), np.asarray(channel, np.int64)
         ok = (pos >= 0) & (pos < self.l_ref[refid])
         s = self.slot[refid][pos[ok]]
         np.add.at(self.c, (s[s >= 0], channel[ok][s >= 0]), 1)
+        if qe is not None:
+            s, channel, qe = s[s >= 0], channel[ok][s >= 0], np.asarray(qe, np.int64)[ok][s >= 0]
+            s, b, qe = s[channel < 8], channel[channel < 8] & 3, qe[channel < 8]
+            np.add.at(self.q, (s, Q + b), qe)
+            np.add.at(self.q, (s, HOM + b), np.asarray(T_HOM, np.int64)[qe - GL_MIN_Q])
+            np.add.at(self.q, (s, HET + b), np.asarray(T_HET, np.int64)[qe - GL_MIN_Q])
 
     def add(self, records: bytes) -> int:
         """Every record of `records`; -> the number that counted.  Check first, then add (rule 3)."""
@@ -93,13 +127,17 @@ class Pileup:
             n_counted += 1
             strand = 4 if flag & 0x10 else 0
             good = np.ones(l_seq, bool) if qual[0] == 0xFF else qual >= self.min_baseq   # rule 4: no qualities pass every min_baseq
+            qe = None
+            if self.q is not None:                                                       # rule 10
+                raw = np.full(l_seq, self.no_qual_q, np.int64) if qual[0] == 0xFF else qual.astype(np.int64)
+                qe = np.clip(np.minimum(raw, mapq), GL_MIN_Q, GL_MAX_Q)
             x, q, seen_ref = pos, 0, False
             for n, op in cigar:
                 if op in (0, 7, 8):
                     ch = _CHANNEL_OF_CODE[codes[q:q + n]]
                     ch = np.where(ch < 4, ch + strand, ch)
                     g = good[q:q + n]
-                    self._put(refid, np.arange(x, x + n)[g], ch[g])
+                    self._put(refid, np.arange(x, x + n)[g], ch[g], None if qe is None else qe[q:q + n][g])
                 elif op == 2:
                     lo, hi = max(x, 0), min(x + n, self.l_ref[refid])
                     if lo < hi:
@@ -154,4 +192,55 @@ class Pileup:
             alts = ",".join(k for bit, k in enumerate(KINDS) if int(s["kinds"]) >> bit & 1)
             rows.append("%s\t%d\t%s\t%d\t%s\t%s\n" % (names[self.regions[int(s["region"])][0]], int(s["pos"]) + 1, "ACGTN"[int(s["ref"])],
                                                      int(s["depth"]), "\t".join(str(int(v)) for v in s["c"][:11]), alts))
+        return "".join(rows)
+
+    def fetch_quality(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:      # rule 11
+        assert self.q is not None
+        r, b, e = self.regions[region]
+        beg, end = b if beg is None else beg, e if end is None else end
+        assert b <= beg <= end <= e
+        return self.q[self.off[region] + beg - b:self.off[region] + end - b].astype(np.uint32)
+
+    def genotypes(self) -> np.ndarray:
+        """rule 13 at every slot, CALL_DTYPE with region -1 where it does not apply: from the uint32 the device holds (the planes
+        modulo 2^32), in Python integers"""
+        assert self.q is not None
+        out = np.zeros(self.n_slots, CALL_DTYPE)
+        out["region"] = -1
+        c, q = self.c & 0xFFFFFFFF, self.q & 0xFFFFFFFF
+        region = np.searchsorted(self.off, np.arange(self.n_slots), "right") - 1
+        for s in np.flatnonzero((self.ref < 4) & (c[:, :8].sum(1) > 0)):
+            n = [int(c[s, b]) + int(c[s, b + 4]) for b in range(4)]
+            mis = [100 * int(q[s, Q + b]) + GL_MIS * n[b] for b in range(4)]
+            cost = [sum(mis[b] if b not in (a1, a2) else int(q[s, (HOM if a1 == a2 else HET) + b]) for b in range(4)) for a1, a2 in GENOTYPES]
+            best = cost.index(min(cost))                                                 # ties: the lowest g
+            pl = [min((x - cost[best] + 50) // 100, 2 ** 31 - 1) for x in cost]
+            r = int(self.ref[s])
+            k = int(region[s])
+            out[s] = (k, int(s - self.off[k]) + self.regions[k][1], r, GENOTYPES[best][0], GENOTYPES[best][1], pl[r * (r + 1) // 2 + r],
+                      min(99, min(x for g, x in enumerate(pl) if g != best)), sum(n) & 0xFFFFFFFF, [x & 0xFFFFFFFF for x in n], pl)
+        return out
+
+    def calls(self, min_qual: int | None = None, min_depth: int | None = None) -> np.ndarray:               # rule 13
+        min_qual = self.min_qual if min_qual is None else min_qual
+        min_depth = self.min_depth if min_depth is None else min_depth
+        g = self.genotypes()
+        depth = (self.c & 0xFFFFFFFF)[:, :8].sum(1)                                       # untruncated, as the device compares it
+        return g[(g["region"] >= 0) & (depth >= min_depth) & ((g["a1"] != g["ref"]) | (g["a2"] != g["ref"])) & (g["qual"] >= min_qual)]
+
+    def vcf(self, names, sample: str, min_qual: int | None = None, min_depth: int | None = None) -> str:
+        names = [n.decode() if isinstance(n, bytes) else n for n in names]
+        rows = ["##fileformat=VCFv4.2\n##source=bwams\n"]
+        rows += ["##contig=<ID=%s,length=%d>\n" % (n, l) for n, l in zip(names, self.l_ref)]
+        rows.append(VCF_FIXED + sample + "\n")
+        for x in self.calls(min_qual, min_depth):
+            r, a1, a2 = int(x["ref"]), int(x["a1"]), int(x["a2"])
+            alleles = [r] + [a for a in dict.fromkeys((a1, a2)) if a != r]               # REF, then the other alleles in base order
+            gt = sorted((alleles.index(a1), alleles.index(a2)))
+            pl = [int(x["pl"][max(alleles[i], alleles[j]) * (max(alleles[i], alleles[j]) + 1) // 2 + min(alleles[i], alleles[j])])
+                  for j in range(len(alleles)) for i in range(j + 1)]
+            rows.append("%s\t%d\t.\t%s\t%s\t%d\t.\tDP=%d\tGT:AD:DP:GQ:PL\t%d/%d:%s:%d:%d:%s\n" % (
+                names[self.regions[int(x["region"])][0]], int(x["pos"]) + 1, "ACGT"[r], ",".join("ACGT"[a] for a in alleles[1:]), int(x["qual"]),
+                int(x["depth"]), gt[0], gt[1], ",".join(str(int(x["n"][a])) for a in alleles), int(x["depth"]), int(x["gq"]),
+                ",".join(map(str, pl))))
         return "".join(rows)

@@ -1,5 +1,6 @@
 // api_pileup.hip — C-ABI entry points of the pileup (include/bwams.h, "Pileup"): the handle over a list of regions, the adds from a
-// batch and from host records, the reference bases, and the queries, over pileup.hip; the text over host/pileup_text.cpp.
+// batch and from host records, the reference bases, the quality plane, and the queries, over pileup.hip; the texts over
+// host/pileup_text.cpp and host/pileup_vcf.cpp.
 // No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <algorithm>
 #include <cstring>
@@ -18,6 +19,9 @@ struct bwams_pileup : RecConsumer {
     std::vector<bwams_pileup_region_t> regions;
     std::vector<int64_t> reg_off;                    // n_regions + 1: region k's first slot; the last is the number of slots
     DevBuf<uint32_t> counts;                         // kPileupChannels per slot
+    DevBuf<uint32_t> sums;                           // rule 11's plane, kPileupChannels per slot; none before bwams_pileup_set_quality
+    bwams_pileup_gl_opt_t gl{};
+    bool clean = true;                               // no add since the open or the last _reset: the counters are zero
     DevBuf<uint8_t> ref;                             // rule 7: a code per slot
     DevBuf<int32_t> d_beg, d_end, d_ref_first, d_reg_ref;
     DevBuf<int64_t> d_off;
@@ -27,6 +31,7 @@ struct bwams_pileup : RecConsumer {
     DevBuf<uint8_t> route;
     DevBuf<int64_t> sel, sel_cnt;                    // the queries' device results, kept between calls
     DevBuf<bwams_pileup_site_t> d_sites;
+    DevBuf<bwams_pileup_call_t> d_calls;
     DevBuf<int64_t> hole_off;                        // bwams_pileup_set_ref_index: the index's .amb holes
     DevBuf<int32_t> hole_len;
     int64_t n_added = 0;                             // records given so far (rule 6)
@@ -36,6 +41,8 @@ struct bwams_pileup : RecConsumer {
     int32_t n_regions() const { return (int32_t)regions.size(); }
     int64_t n_slots() const { return reg_off.back(); }
     PileupRegions dev_regions() const { return PileupRegions{d_beg.p, d_end.p, d_ref_first.p, d_off.p}; }
+    PileupQuality quality() const { return PileupQuality{sums.p, gl.no_qual_q}; }
+    size_t plane_bytes() const { return (size_t)std::max<int64_t>(n_slots(), 1) * kPileupChannels * 4; }
 };
 
 namespace bwams {
@@ -47,8 +54,8 @@ namespace {
 
 constexpr int64_t kPiece = 1 << 24;                  // records routed and sorted at a time: 32 bytes of scratch per record
 
-struct SiteCount {
-    PileupSiteTest f;
+template <class Test> struct SlotCount {             // 1 at a slot the test selects
+    Test f;
     __host__ __device__ int64_t operator()(int64_t s) const { return f(s) ? 1 : 0; }
 };
 
@@ -81,6 +88,7 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
         unsigned bits = 1;
         while ((1LL << bits) <= n_tiles) ++bits;                         // the keys are 0 .. n_tiles
         const PileupRegions R = p->dev_regions();
+        const PileupQuality Q = p->quality();
         const int64_t n_max = std::min(kPiece, n_rec);                   // every buffer for the largest piece before the first counter
         BWAMS_HIP(p->route.ensure_n((size_t)n_max));                     // moves: an allocation that fails adds nothing
         if (tiled) {
@@ -91,6 +99,7 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
             BWAMS_HIP(rocprim::radix_sort_pairs(nullptr, tb, p->keys.p, p->keys2.p, p->vals.p, p->vals2.p, (size_t)(2 * n_max), 0u, bits, st));
             if (tb > p->tmp.cap || !p->tmp.p) BWAMS_HIP(p->tmp.alloc(std::max<size_t>(tb, 256)));
         }
+        p->clean = false;
         for (int64_t r0 = 0; r0 < n_rec; r0 += kPiece) {
             const int64_t n = std::min(kPiece, n_rec - r0), n_ent = 2 * n;
             if (tiled) BWAMS_HIP(hipMemsetAsync(p->n_heads.p, 0, 4, st));
@@ -101,10 +110,13 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
                         if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": radix_sort_pairs").c_str(), [&](void *tmp, size_t &tb) {
                                 return rocprim::radix_sort_pairs(tmp, tb, p->keys.p, p->keys2.p, p->vals.p, p->vals2.p, (size_t)n_ent, 0u, bits, st);
                             })) return rc;
-                        launch_pileup_tiles(dev_bam, dev_off + r0, R, p->opt.min_baseq, p->keys2.p, p->vals2.p, n_ent, (uint32_t)n_tiles,
-                                            p->heads.p, p->n_heads.p, p->n_slots(), p->counts.p, p->cu_count, st);
+                        if (launch_pileup_tiles(dev_bam, dev_off + r0, R, p->opt.min_baseq, p->keys2.p, p->vals2.p, n_ent, (uint32_t)n_tiles,
+                                                p->heads.p, p->n_heads.p, p->n_slots(), p->counts.p, Q, p->cu_count, st)) {
+                            set_last_error(std::string(who) + ": the device refused the LDS of the quality tile");
+                            return BWAMS_ERR_DEVICE;
+                        }
                     }
-                    launch_pileup_direct(dev_bam, dev_off + r0, n, R, p->opt.min_baseq, p->route.p, p->counts.p, p->cu_count, st);
+                    launch_pileup_direct(dev_bam, dev_off + r0, n, R, p->opt.min_baseq, p->route.p, p->counts.p, Q, p->cu_count, st);
                     return BWAMS_OK;
                 })) return rc;
             for (int k = 0; k < 3; ++k) sum[k] += (int64_t)h[k];
@@ -127,16 +139,40 @@ int thresholds(const bwams_pileup *p, int32_t min_alt, int32_t min_permille, con
     return BWAMS_OK;
 }
 
-// rule 8: the sites into host memory
-int pileup_sites(bwams_pileup *p, const PileupSiteTest &test, const char *who, bool count_only, int64_t cap, bwams_pileup_site_t *sites,
-                 std::vector<bwams_pileup_site_t> *own, int64_t *n_out) {
+int call_thresholds(const bwams_pileup *p, int32_t min_qual, int32_t min_depth, const char *who, PileupCallTest *t) {
+    if (!p->sums.p) {
+        set_last_error(std::string(who) + ": the handle has no quality plane (bwams_pileup_set_quality)");
+        return BWAMS_ERR_ARG;
+    }
+    if (min_qual < 0) min_qual = p->gl.min_qual;
+    if (min_depth < 0) min_depth = p->gl.min_depth;
+    if (min_depth < 1) {
+        set_last_error(std::string(who) + ": min_depth >= 1 is required (negative: the handle's)");
+        return BWAMS_ERR_ARG;
+    }
+    *t = PileupCallTest{p->counts.p, p->sums.p, p->ref.p, min_qual, min_depth};
+    return BWAMS_OK;
+}
+
+void launch_records(const PileupSiteTest &test, bwams_pileup *p, int64_t n, bwams_pileup_site_t *out) {
+    launch_pileup_sites(test, p->dev_regions(), p->n_regions(), p->sel.p, n, out, p->cu_count, p->stream);
+}
+void launch_records(const PileupCallTest &test, bwams_pileup *p, int64_t n, bwams_pileup_call_t *out) {
+    launch_pileup_calls(test, p->dev_regions(), p->n_regions(), p->sel.p, n, out, p->cu_count, p->stream);
+}
+
+// rules 8 and 13: the slots that `test` selects, counted and selected in slot order, and their records (sites or calls; d_out: the
+// handle's device buffer for them) into host memory
+template <class Test, class Rec>
+int pileup_select(bwams_pileup *p, const Test &test, DevBuf<Rec> &d_out, const char *who, const char *what, bool count_only, int64_t cap,
+                  Rec *sites, std::vector<Rec> *own, int64_t *n_out) {
     hipStream_t st = p->stream;
     int64_t n_sites = 0;
     const int64_t n_slots = p->n_slots();
     rocprim::counting_iterator<int64_t> slot(0);
     BWAMS_HIP(p->sel_cnt.ensure_n(8));
     if (n_slots > 0) {
-        auto ones = rocprim::make_transform_iterator(slot, SiteCount{test});
+        auto ones = rocprim::make_transform_iterator(slot, SlotCount<Test>{test});
         if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": reduce").c_str(), [&](void *tmp, size_t &tb) {
                 return rocprim::reduce(tmp, tb, ones, p->sel_cnt.p, (int64_t)0, (size_t)n_slots, rocprim::plus<int64_t>(), st);
             })) return rc;
@@ -146,16 +182,16 @@ int pileup_sites(bwams_pileup *p, const PileupSiteTest &test, const char *who, b
     *n_out = n_sites;
     if (count_only || n_sites == 0) return BWAMS_OK;
     if (!own && cap < n_sites) {
-        set_last_error(std::string(who) + ": " + std::to_string(n_sites) + " sites do not fit a capacity of " + std::to_string(cap));
+        set_last_error(std::string(who) + ": " + std::to_string(n_sites) + " " + what + " do not fit a capacity of " + std::to_string(cap));
         return BWAMS_ERR_CAPACITY;
     }
-    BWAMS_HIP(p->sel.ensure_n((size_t)n_sites)); BWAMS_HIP(p->d_sites.ensure_n((size_t)n_sites));
+    BWAMS_HIP(p->sel.ensure_n((size_t)n_sites)); BWAMS_HIP(d_out.ensure_n((size_t)n_sites));
     if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": select").c_str(), [&](void *tmp, size_t &tb) {
             return rocprim::select(tmp, tb, slot, p->sel.p, p->sel_cnt.p, (size_t)n_slots, test, st);
         })) return rc;
-    launch_pileup_sites(test, p->dev_regions(), p->n_regions(), p->sel.p, n_sites, p->d_sites.p, p->cu_count, st);
+    launch_records(test, p, n_sites, d_out.p);
     if (own) { own->resize((size_t)n_sites); sites = own->data(); }
-    BWAMS_HIP(hipMemcpyAsync(sites, p->d_sites.p, (size_t)n_sites * sizeof(bwams_pileup_site_t), hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipMemcpyAsync(sites, d_out.p, (size_t)n_sites * sizeof(Rec), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
     return BWAMS_OK;
@@ -238,8 +274,10 @@ int bwams_pileup_close(bwams_pileup_t *p) {
 int bwams_pileup_reset(bwams_pileup_t *p) {
     if (!p) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(p->device));
-    BWAMS_HIP(hipMemsetAsync(p->counts.p, 0, (size_t)std::max<int64_t>(p->n_slots(), 1) * kPileupChannels * 4, p->stream));
+    BWAMS_HIP(hipMemsetAsync(p->counts.p, 0, p->plane_bytes(), p->stream));
+    if (p->sums.p) BWAMS_HIP(hipMemsetAsync(p->sums.p, 0, p->plane_bytes(), p->stream));
     BWAMS_HIP(hipStreamSynchronize(p->stream));
+    p->clean = true;
     p->n_added = 0;
     std::fill(p->last, p->last + 3, 0);
     return BWAMS_OK;
@@ -319,13 +357,84 @@ int bwams_pileup_fetch(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t e
     return BWAMS_OK;
 }
 
+int bwams_pileup_set_quality(bwams_pileup_t *p, const bwams_pileup_gl_opt_t *opt) {
+    const bwams_pileup_gl_opt_t o = opt ? *opt : bwams_pileup_gl_opt_t{20, 1, 30, 0};
+    if (!p || o.min_qual < 0 || o.min_depth < 1 || o.no_qual_q < 0 || o.no_qual_q > 93 || o.reserved != 0) {
+        set_last_error("bwams_pileup_set_quality: a handle, min_qual >= 0, min_depth >= 1, no_qual_q in [0, 93] and reserved == 0 are required");
+        return BWAMS_ERR_ARG;
+    }
+    if (!p->clean) {
+        set_last_error("bwams_pileup_set_quality: the counters are not zero: before the first add, or directly after bwams_pileup_reset");
+        return BWAMS_ERR_ARG;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    if (!p->sums.p) BWAMS_HIP(p->sums.alloc(p->plane_bytes()));         // BWAMS_ERR_NOMEM when the plane does not fit, as rule 1's counters
+    BWAMS_HIP(hipMemsetAsync(p->sums.p, 0, p->plane_bytes(), p->stream));
+    BWAMS_HIP(hipStreamSynchronize(p->stream));
+    p->gl = o;
+    return BWAMS_OK;
+}
+
+int bwams_pileup_fetch_quality(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *sums) {
+    if (!p || !p->sums.p || region < 0 || region >= p->n_regions() || beg < p->regions[(size_t)region].beg || end < beg ||
+        end > p->regions[(size_t)region].end || (end > beg && !sums)) {
+        set_last_error("bwams_pileup_fetch_quality: a handle with a quality plane, a region in [0, n_regions) and region.beg <= beg <= end <= "
+                       "region.end are required");
+        return BWAMS_ERR_ARG;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    if (end > beg) {
+        const int64_t first = p->reg_off[(size_t)region] + (beg - p->regions[(size_t)region].beg);
+        BWAMS_HIP(hipMemcpyAsync(sums, p->sums.p + first * kPileupChannels, (size_t)(end - beg) * kPileupChannels * 4, hipMemcpyDeviceToHost,
+                                 p->stream));
+        BWAMS_HIP(hipStreamSynchronize(p->stream));
+    }
+    return BWAMS_OK;
+}
+
+int bwams_pileup_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, bwams_pileup_call_t *calls, int64_t cap, int64_t *n) {
+    if (!p || cap < 0) return BWAMS_ERR_ARG;
+    PileupCallTest test;
+    if (int rc = call_thresholds(p, min_qual, min_depth, "bwams_pileup_calls", &test)) return rc;
+    BWAMS_HIP(hipSetDevice(p->device));
+    int64_t n_calls = 0;
+    const int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, test, p->d_calls, "bwams_pileup_calls", "calls", !calls, cap, calls, nullptr, &n_calls);
+    if (n) *n = n_calls;
+    return rc;
+}
+
+int bwams_pileup_vcf(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, char *out, int64_t cap,
+                     int64_t *n) {
+    if (!p || (!names && p->n_ref()) || !sample) {
+        set_last_error("bwams_pileup_vcf: a handle, the references' names and a sample name are required");
+        return BWAMS_ERR_ARG;
+    }
+    PileupCallTest test;
+    if (int rc = call_thresholds(p, min_qual, min_depth, "bwams_pileup_vcf", &test)) return rc;
+    BWAMS_HIP(hipSetDevice(p->device));
+    std::vector<bwams_pileup_call_t> calls;
+    int64_t n_calls = 0;
+    if (int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, test, p->d_calls, "bwams_pileup_vcf", "calls", false, 0, nullptr, &calls, &n_calls))
+        return rc;
+    std::string text;
+    if (int rc = pileup_vcf_format(names, p->l_ref.data(), p->n_ref(), p->regions.data(), p->n_regions(), sample, calls.data(), n_calls, &text))
+        return rc;
+    if (n) *n = (int64_t)text.size();
+    if (!out || cap < (int64_t)text.size()) {
+        set_last_error("bwams_pileup_vcf: the text needs " + std::to_string(text.size()) + " bytes");
+        return BWAMS_ERR_CAPACITY;
+    }
+    memcpy(out, text.data(), text.size());
+    return BWAMS_OK;
+}
+
 int bwams_pileup_sites(bwams_pileup_t *p, int32_t min_alt, int32_t min_permille, bwams_pileup_site_t *sites, int64_t cap, int64_t *n) {
     if (!p || cap < 0) return BWAMS_ERR_ARG;
     PileupSiteTest test;
     if (int rc = thresholds(p, min_alt, min_permille, "bwams_pileup_sites", &test)) return rc;
     BWAMS_HIP(hipSetDevice(p->device));
     int64_t n_sites = 0;
-    const int rc = pileup_sites(p, test, "bwams_pileup_sites", !sites, cap, sites, nullptr, &n_sites);
+    const int rc = pileup_select<PileupSiteTest, bwams_pileup_site_t>(p, test, p->d_sites, "bwams_pileup_sites", "sites", !sites, cap, sites, nullptr, &n_sites);
     if (n) *n = n_sites;
     return rc;
 }
@@ -340,7 +449,8 @@ int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int
     BWAMS_HIP(hipSetDevice(p->device));
     std::vector<bwams_pileup_site_t> sites;
     int64_t n_sites = 0;
-    if (int rc = pileup_sites(p, test, "bwams_pileup_text", false, 0, nullptr, &sites, &n_sites)) return rc;
+    if (int rc = pileup_select<PileupSiteTest, bwams_pileup_site_t>(p, test, p->d_sites, "bwams_pileup_text", "sites", false, 0, nullptr, &sites, &n_sites))
+        return rc;
     std::string text;
     if (int rc = pileup_text_format(names, p->n_ref(), p->regions.data(), p->n_regions(), sites.data(), n_sites, &text)) return rc;
     if (n) *n = (int64_t)text.size();

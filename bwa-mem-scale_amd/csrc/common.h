@@ -302,8 +302,8 @@ void launch_depth_gather(const int32_t *slots, int64_t base, const int32_t *star
 // (route[r]); tiled != 0 also writes the (tile, record) entries 2r and 2r + 1 into keys / vals, unused ones with the key n_tiles;
 // counts[0..2] += records counted, entries, records routed direct.  tiles: the entries sorted by key; heads (min(n_ent, n_tiles)
 // slots) and *n_heads (zeroed by the caller) are scratch.  direct: the records with route[r] == kPileupDirect.  sites: the site
-// records of the selected slots.  ref: rule 7's gather from an index (holes: the .amb holes, ascending, or none).
-constexpr int kPileupTile = 1024;        // positions of a tile: 12 channels x 1024 x 4 bytes = 48 KB of a workgroup's LDS
+// records of the selected slots, calls: rule 13's call records of the selected slots.  ref: rule 7's gather from an index (holes: the .amb holes, ascending, or none).
+constexpr int kPileupTile = 1024;        // positions of a tile: 12 channels x 1024 x 4 bytes = 48 KB of a workgroup's LDS; 96 KB with the quality plane
 constexpr int kPileupChannels = BWAMS_PILEUP_CHANNELS, kPileupN = BWAMS_PILEUP_N, kPileupDel = BWAMS_PILEUP_DEL, kPileupIns = BWAMS_PILEUP_INS;
 enum : uint8_t { kPileupSkip = 0, kPileupTiled = 1, kPileupDirect = 2 };
 struct PileupFilter {
@@ -334,16 +334,91 @@ struct PileupSiteTest {                  // rule 8 at slot s: the candidate alle
     }
     __host__ __device__ bool operator()(int64_t s) const { uint32_t d; return kinds(s, &d) != 0; }
 };
+// Rule 12's tables over the effective qualities kPileupGlMinQ .. kPileupGlMaxQ, in hundredths of a phred, and rule 13's mismatch cost
+// 100 q + kPileupGlMis.  bwams/pileup.py holds the same numbers; tests/test_pileup_calls.py recomputes both and reads these literals.
+constexpr int kPileupGlMinQ = 4, kPileupGlMaxQ = 60, kPileupGlMis = 477;
+__host__ __device__ __forceinline__ uint32_t pileup_gl_hom(int qe) {
+    constexpr uint16_t kPileupGlHom[kPileupGlMaxQ - kPileupGlMinQ + 1] = {
+        220, 165, 126, 97, 75, 58, 46, 36, 28, 22, 18, 14, 11, 9, 7, 6, 4, 3, 3, 2, 2, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+        0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return kPileupGlHom[qe - kPileupGlMinQ];
+}
+__host__ __device__ __forceinline__ uint32_t pileup_gl_het(int qe) {
+    constexpr uint16_t kPileupGlHet[kPileupGlMaxQ - kPileupGlMinQ + 1] = {
+        435, 404, 381, 363, 350, 339, 331, 325, 320, 316, 313, 310, 308, 307, 306, 305, 304, 303, 303, 302, 302, 302, 302, 302, 301, 301,
+        301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301, 301,
+        301, 301, 301, 301, 301, 301};
+    return kPileupGlHet[qe - kPileupGlMinQ];
+}
+// The quality plane (rule 11): kPileupChannels uint32 per slot beside the counters, Q[A..T], HOM[A..T], HET[A..T].  `quality` in the
+// launches below: the plane, or null for a handle without one (the count-only kernels run, as before the plane existed).
+struct PileupQuality {
+    uint32_t *sums;
+    int32_t no_qual_q;
+};
+struct PileupCallTest {                  // rule 13 at slot s
+    const uint32_t *counts, *sums;
+    const uint8_t *ref;
+    int32_t min_qual, min_depth;
+    // the slot's record but region and pos; false when rule 13 does not apply (reference base 4, or fewer than min_depth bases)
+    __host__ __device__ bool genotype(int64_t s, bwams_pileup_call_t *out) const {
+        const uint32_t *c = counts + s * kPileupChannels, *q = sums + s * kPileupChannels;
+        const int32_t r = ref[s];
+        uint64_t n[4], mis[4], depth = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            n[b] = (uint64_t)c[b] + c[b + 4];
+            mis[b] = 100 * (uint64_t)q[b] + (uint64_t)kPileupGlMis * n[b];
+            depth += n[b];
+        }
+        if (r > 3 || depth < (uint64_t)min_depth) return false;
+        uint64_t cost[10], least = ~0ULL, cost_rr = 0;                   // every loop unrolled: the arrays stay in registers
+        int best = 0;
+#pragma unroll
+        for (int a2 = 0; a2 < 4; ++a2)
+#pragma unroll
+            for (int a1 = 0; a1 <= a2; ++a1) {
+                const int g = a2 * (a2 + 1) / 2 + a1;
+                uint64_t x = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) x += b != a1 && b != a2 ? mis[b] : a1 == a2 ? q[BWAMS_PILEUP_HOM + b] : q[BWAMS_PILEUP_HET + b];
+                cost[g] = x;
+                if (x < least) { least = x; best = g; out->a1 = a1; out->a2 = a2; }    // ascending g: a tie stays with the lowest
+                if (a1 == r && a2 == r) cost_rr = x;
+            }
+        int32_t second = 0x7FFFFFFF;
+#pragma unroll
+        for (int g = 0; g < 10; ++g) {
+            const uint64_t pl = (cost[g] - least + 50) / 100;
+            out->pl[g] = pl > 0x7FFFFFFFULL ? 0x7FFFFFFF : (int32_t)pl;
+            if (g != best && out->pl[g] < second) second = out->pl[g];
+        }
+        const uint64_t pl_rr = (cost_rr - least + 50) / 100;
+        out->ref = r;
+        out->qual = pl_rr > 0x7FFFFFFFULL ? 0x7FFFFFFF : (int32_t)pl_rr;
+        out->gq = second < 99 ? second : 99;
+        out->depth = (uint32_t)depth;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) out->n[b] = (uint32_t)n[b];
+        return true;
+    }
+    __host__ __device__ bool operator()(int64_t s) const {
+        bwams_pileup_call_t x;
+        return genotype(s, &x) && !(x.a1 == x.ref && x.a2 == x.ref) && x.qual >= min_qual;
+    }
+};
 void launch_pileup_check(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, unsigned long long *bad,
                          int cu_count, hipStream_t st);
 void launch_pileup_route(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, const PileupRegions &R,
                          uint32_t n_tiles, int tiled, uint32_t *keys, uint32_t *vals, uint8_t *route, unsigned long long *counts,
                          int cu_count, hipStream_t st);
-void launch_pileup_tiles(const uint8_t *bam, const int64_t *rec_off, const PileupRegions &R, int min_baseq, const uint32_t *keys,
-                         const uint32_t *vals, int64_t n_ent, uint32_t n_tiles, uint32_t *heads, uint32_t *n_heads, int64_t n_slots,
-                         uint32_t *counts, int cu_count, hipStream_t st);
+int launch_pileup_tiles(const uint8_t *bam, const int64_t *rec_off, const PileupRegions &R, int min_baseq, const uint32_t *keys,
+                        const uint32_t *vals, int64_t n_ent, uint32_t n_tiles, uint32_t *heads, uint32_t *n_heads, int64_t n_slots,
+                        uint32_t *counts, const PileupQuality &quality, int cu_count, hipStream_t st);      // -1: the LDS of the quality tile was refused
 void launch_pileup_direct(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupRegions &R, int min_baseq,
-                          const uint8_t *route, uint32_t *counts, int cu_count, hipStream_t st);
+                          const uint8_t *route, uint32_t *counts, const PileupQuality &quality, int cu_count, hipStream_t st);
+void launch_pileup_calls(const PileupCallTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *slots, int64_t n,
+                         bwams_pileup_call_t *out, int cu_count, hipStream_t st);
 void launch_pileup_sites(const PileupSiteTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *slots, int64_t n,
                          bwams_pileup_site_t *out, int cu_count, hipStream_t st);
 void launch_pileup_ref(const PileupRegions &R, int32_t n_regions, const int32_t *reg_ref, int64_t n_slots, const uint8_t *ref0123,

@@ -1,4 +1,5 @@
-// pileup.hip — per-base allele counts and candidate sites (the rules are in include/bwams.h above bwams_pileup_open).
+// pileup.hip — per-base allele counts, candidate sites, quality sums and SNV calls (the rules are in include/bwams.h above
+// bwams_pileup_open).
 //
 // Layout: a slot per region position, the regions' slots back to back in region order (reg_off[k] is region k's first slot); a slot is
 // kPileupChannels uint32 counters (48 bytes), so slot s lives at counts + 12 * s.  ref_first[r] is the first region of reference r
@@ -21,6 +22,15 @@
 //                         end a thread per position adds the position's 12 counters to HBM with three 16-byte loads and stores when
 //                         one of them is not zero: a tile has one owner per launch, so no global atomic is issued.
 //   pileup_direct_kernel  a wave per record routed direct: the same walk with one global atomic per counted base.
+//   pileup_tile_quality_kernel, pileup_direct_quality_kernel
+//                         the same two for a handle with a quality plane (rules 10 and 11): a second plane of 12 uint32 per slot,
+//                         Q[A..T] HOM[A..T] HET[A..T], and a counted base adds four values, its count and the three sums of its
+//                         effective quality.  The tile holds both planes, 96 KB of dynamic LDS, so one workgroup is resident on a
+//                         CU; the flush writes the second plane as it writes the first.  The count-only kernels are instantiated
+//                         from the same walk with sinks that ignore the quality, and compile to what they were without it.
+//   pileup_call_kernel    rule 13: PileupCallTest (common.h) gives the genotype costs of a slot from the two planes in 64-bit
+//                         integers; api_pileup.hip counts and selects the calls with it as it does the sites, and this kernel
+//                         fills the call records of the selected slots.
 //   pileup_site_*         rule 8's predicate over the slots (SiteTest, given to rocprim::reduce and rocprim::select by
 //                         api_pileup.hip) and the gather that fills the site records of the selected slots.
 //   pileup_ref_kernel     rule 7: a lane per slot copies the forward strand's .0123 code at contig offset + position; a position in one
@@ -99,6 +109,7 @@ struct RecView {
     RegionCursor first;                    // the regions [first.ri, r_end) of its reference end above POS - 1
     int64_t pos;
     int strand;                            // 0, or 4 for FLAG 0x10
+    int mapq;                              // rule 10; only a quality sink reads it
     bool has_qual;
 };
 
@@ -112,6 +123,7 @@ __device__ __forceinline__ RecView view_of(const uint8_t *p, const PileupRegions
     v.qual = p + bam_qual_at(l_name, v.n_cig, v.l_seq);
     v.pos = bam_pos(p);
     v.strand = (bam_flag(p) & 0x10) ? 4 : 0;
+    v.mapq = bam_mapq(p);
     v.has_qual = v.qual[0] != 0xFF;
     const int32_t rid = bam_ref_id(p);
     v.r_end = R.ref_first[rid + 1];
@@ -153,7 +165,8 @@ __device__ __forceinline__ OpRound op_round(const RecView &v, uint32_t k0, int l
     return r;
 }
 
-// Rule 4 for one record by one wave: sink.add(slot, channel) for everything the record counts.  First the query bases, a lane per
+// Rule 4 for one record by one wave: sink.add(slot, channel, qe) for everything the record counts; qe is rule 10's effective quality of
+// a base in one of the eight base channels, worked out only for a sink with kQuality (0 otherwise).  First the query bases, a lane per
 // base in rounds of 64: a lane keeps the op that holds its base and the query and reference offsets of that op's start, and moves
 // them forward from round to round (its bases ascend).  Then the CIGAR ops, a lane per op in rounds of 64 (op_round): an I is counted
 // by its lane; when the record has a D, a second pass over the ops counts the positions of each D by the whole wave.
@@ -179,7 +192,10 @@ template <class Sink> __device__ __forceinline__ void walk_record(const PileupRe
         if (s < 0) continue;
         const uint32_t code = (two >> ((q & 1) ? 0 : 4)) & 15;
         const int base = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1;
-        sink.add(s, base < 0 ? kPileupN : base + v.strand);
+        int qe = 0;
+        if constexpr (Sink::kQuality)
+            qe = std::min(std::max(std::min(v.has_qual ? (int)qual : sink.no_qual_q, v.mapq), kPileupGlMinQ), kPileupGlMaxQ);
+        sink.add(s, base < 0 ? kPileupN : base + v.strand, qe);
     }
     int64_t x_carry = v.pos;
     bool seen_carry = false, any_del = false;
@@ -188,7 +204,7 @@ template <class Sink> __device__ __forceinline__ void walk_record(const PileupRe
         const OpRound r = op_round(v, k0, lane, x_carry, seen_carry);
         if (r.o == 1 && r.seen) {
             const int64_t s = slot_at(R, c, v.r_end, r.x - 1);
-            if (s >= 0) sink.add(s, kPileupIns);
+            if (s >= 0) sink.add(s, kPileupIns, 0);
         }
         any_del |= __ballot(r.o == 2) != 0;
     }
@@ -206,7 +222,7 @@ template <class Sink> __device__ __forceinline__ void walk_record(const PileupRe
             while (d_ri < v.r_end && (int64_t)R.end[d_ri] <= dx) ++d_ri;
             for (int32_t rj = d_ri; rj < v.r_end && (int64_t)R.beg[rj] < d_end; ++rj) {
                 const int64_t lo = std::max<int64_t>(dx, R.beg[rj]), hi = std::min<int64_t>(d_end, R.end[rj]);
-                for (int64_t y = lo + lane; y < hi; y += 64) sink.add(R.off[rj] + (y - R.beg[rj]), kPileupDel);
+                for (int64_t y = lo + lane; y < hi; y += 64) sink.add(R.off[rj] + (y - R.beg[rj]), kPileupDel, 0);
             }
         }
     }
@@ -291,29 +307,76 @@ __global__ void __launch_bounds__(256) pileup_heads_kernel(const uint32_t *keys,
 constexpr int kTileThreads = 1024;                                      // 16 waves a tile; two tiles a CU while the kernel stays at or under 64 VGPRs (make resource-usage)
 
 struct TileSink {                                                        // the workgroup's tile in LDS, channel-major
+    static constexpr bool kQuality = false;
     uint32_t *lds;
     int64_t first;                                                       // the tile's first slot
-    __device__ __forceinline__ void add(int64_t slot, int channel) {
+    __device__ __forceinline__ void add(int64_t slot, int channel, int) {
         const uint64_t at = (uint64_t)(slot - first);
         if (at < (uint64_t)kPileupTile) atomicAdd(lds + channel * kPileupTile + (int)at, 1u);
     }
 };
 
 struct DirectSink {
+    static constexpr bool kQuality = false;
     uint32_t *counts;
-    __device__ __forceinline__ void add(int64_t slot, int channel) { atomicAdd(counts + slot * kPileupChannels + channel, 1u); }
+    __device__ __forceinline__ void add(int64_t slot, int channel, int) { atomicAdd(counts + slot * kPileupChannels + channel, 1u); }
 };
 
-__global__ void __launch_bounds__(kTileThreads) pileup_tile_kernel(const uint8_t *bam, const int64_t *rec_off, PileupRegions R, int min_baseq,
-                                                          const uint32_t *keys, const uint32_t *vals, int64_t n_ent, const uint32_t *heads,
-                                                          const uint32_t *n_heads, int64_t n_slots, uint32_t *counts) {
-    __shared__ uint32_t lds[kPileupChannels * kPileupTile];
-    if (blockIdx.x >= *n_heads) return;
-    for (int i = threadIdx.x; i < kPileupChannels * kPileupTile; i += blockDim.x) lds[i] = 0;
+// The quality-on sinks (rule 11): a counted base adds four values, its count and Q, HOM and HET of its base, both strands together.
+struct TileQualitySink {                                                 // both planes of the tile in LDS: the counters' 12 channels, then the sums' 12
+    static constexpr bool kQuality = true;
+    uint32_t *lds;
+    int64_t first;
+    int no_qual_q;
+    __device__ __forceinline__ void add(int64_t slot, int channel, int qe) {
+        const uint64_t at = (uint64_t)(slot - first);
+        if (at >= (uint64_t)kPileupTile) return;
+        atomicAdd(lds + channel * kPileupTile + (int)at, 1u);
+        if (channel >= 8) return;
+        uint32_t *q = lds + (kPileupChannels + (channel & 3)) * kPileupTile + (int)at;
+        atomicAdd(q + BWAMS_PILEUP_Q * kPileupTile, (uint32_t)qe);
+        atomicAdd(q + BWAMS_PILEUP_HOM * kPileupTile, pileup_gl_hom(qe));
+        atomicAdd(q + BWAMS_PILEUP_HET * kPileupTile, pileup_gl_het(qe));
+    }
+};
+
+struct DirectQualitySink {
+    static constexpr bool kQuality = true;
+    uint32_t *counts, *sums;
+    int no_qual_q;
+    __device__ __forceinline__ void add(int64_t slot, int channel, int qe) {
+        atomicAdd(counts + slot * kPileupChannels + channel, 1u);
+        if (channel >= 8) return;
+        uint32_t *q = sums + slot * kPileupChannels + (channel & 3);
+        atomicAdd(q + BWAMS_PILEUP_Q, (uint32_t)qe);
+        atomicAdd(q + BWAMS_PILEUP_HOM, pileup_gl_hom(qe));
+        atomicAdd(q + BWAMS_PILEUP_HET, pileup_gl_het(qe));
+    }
+};
+
+// the slot's 12 values of one plane of the tile (lds: the plane's first channel) added to HBM at g, when one of them is not zero
+__device__ __forceinline__ void flush_slot(const uint32_t *lds, int i, uint32_t *g_slot) {
+    uint32_t c[kPileupChannels];
+    uint32_t any = 0;
+    for (int ch = 0; ch < kPileupChannels; ++ch) { c[ch] = lds[ch * kPileupTile + i]; any |= c[ch]; }
+    if (!any) return;
+    uint4 *g = reinterpret_cast<uint4 *>(g_slot);
+    for (int j = 0; j < kPileupChannels / 4; ++j) {
+        uint4 x = g[j];
+        x.x += c[4 * j]; x.y += c[4 * j + 1]; x.z += c[4 * j + 2]; x.w += c[4 * j + 3];
+        g[j] = x;
+    }
+}
+
+// A workgroup's tile: the planes of the sink (one, or the counters and the sums) zeroed in LDS, the tile's records walked, the planes
+// added to HBM.  sums: the quality plane in HBM, read only by a sink with kQuality.
+template <class Sink> __device__ __forceinline__ void tile_body(uint32_t *lds, Sink &sink, const uint8_t *bam, const int64_t *rec_off,
+                                                                const PileupRegions &R, int min_baseq, const uint32_t *keys,
+                                                                const uint32_t *vals, int64_t n_ent, int64_t head, uint32_t tile,
+                                                                int64_t n_slots, uint32_t *counts, uint32_t *sums) {
+    constexpr int kWords = (Sink::kQuality ? 2 : 1) * kPileupChannels * kPileupTile;
+    for (int i = threadIdx.x; i < kWords; i += blockDim.x) lds[i] = 0;
     __syncthreads();
-    const int64_t head = heads[blockIdx.x];
-    const uint32_t tile = keys[head];
-    TileSink sink{lds, (int64_t)tile * kPileupTile};
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
     for (int64_t e = head + wave; e < n_ent && keys[e] == tile; e += n_waves) {
         const RecView v = view_of(bam + rec_off[vals[e]], R);
@@ -323,17 +386,35 @@ __global__ void __launch_bounds__(kTileThreads) pileup_tile_kernel(const uint8_t
     for (int i = threadIdx.x; i < kPileupTile; i += blockDim.x) {
         const int64_t slot = sink.first + i;
         if (slot >= n_slots) break;
-        uint32_t c[kPileupChannels];
-        uint32_t any = 0;
-        for (int ch = 0; ch < kPileupChannels; ++ch) { c[ch] = lds[ch * kPileupTile + i]; any |= c[ch]; }
-        if (!any) continue;
-        uint4 *g = reinterpret_cast<uint4 *>(counts + slot * kPileupChannels);
-        for (int j = 0; j < kPileupChannels / 4; ++j) {
-            uint4 x = g[j];
-            x.x += c[4 * j]; x.y += c[4 * j + 1]; x.z += c[4 * j + 2]; x.w += c[4 * j + 3];
-            g[j] = x;
-        }
+        flush_slot(lds, i, counts + slot * kPileupChannels);
+        if constexpr (Sink::kQuality) flush_slot(lds + kPileupChannels * kPileupTile, i, sums + slot * kPileupChannels);
     }
+}
+
+__global__ void __launch_bounds__(kTileThreads) pileup_tile_kernel(const uint8_t *bam, const int64_t *rec_off, PileupRegions R, int min_baseq,
+                                                          const uint32_t *keys, const uint32_t *vals, int64_t n_ent, const uint32_t *heads,
+                                                          const uint32_t *n_heads, int64_t n_slots, uint32_t *counts) {
+    __shared__ uint32_t lds[kPileupChannels * kPileupTile];
+    if (blockIdx.x >= *n_heads) return;
+    const int64_t head = heads[blockIdx.x];
+    const uint32_t tile = keys[head];
+    TileSink sink{lds, (int64_t)tile * kPileupTile};
+    tile_body(lds, sink, bam, rec_off, R, min_baseq, keys, vals, n_ent, head, tile, n_slots, counts, nullptr);
+}
+
+// The tile with both planes: 2 x 12 channels x kPileupTile x 4 bytes = 96 KB, above the 64 KB a kernel may declare, so the LDS is
+// dynamic and the launch raises the kernel's maximum; one workgroup fits a CU.
+constexpr int kTileQualityLds = 2 * kPileupChannels * kPileupTile * 4;
+__global__ void __launch_bounds__(kTileThreads) pileup_tile_quality_kernel(const uint8_t *bam, const int64_t *rec_off, PileupRegions R,
+                                                                  int min_baseq, const uint32_t *keys, const uint32_t *vals, int64_t n_ent,
+                                                                  const uint32_t *heads, const uint32_t *n_heads, int64_t n_slots,
+                                                                  uint32_t *counts, PileupQuality quality) {
+    extern __shared__ __align__(16) uint32_t lds_both[];
+    if (blockIdx.x >= *n_heads) return;
+    const int64_t head = heads[blockIdx.x];
+    const uint32_t tile = keys[head];
+    TileQualitySink sink{lds_both, (int64_t)tile * kPileupTile, quality.no_qual_q};
+    tile_body(lds_both, sink, bam, rec_off, R, min_baseq, keys, vals, n_ent, head, tile, n_slots, counts, quality.sums);
 }
 
 __global__ void __launch_bounds__(256) pileup_direct_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, PileupRegions R,
@@ -348,16 +429,47 @@ __global__ void __launch_bounds__(256) pileup_direct_kernel(const uint8_t *bam, 
     }
 }
 
+__global__ void __launch_bounds__(256) pileup_direct_quality_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, PileupRegions R,
+                                                                    int min_baseq, const uint8_t *route, uint32_t *counts,
+                                                                    PileupQuality quality) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    DirectQualitySink sink{counts, quality.sums, quality.no_qual_q};
+    for (int64_t r = wave; r < n_rec; r += n_waves) {
+        if (route[r] != kPileupDirect) continue;
+        const RecView v = view_of(bam + rec_off[r], R);
+        walk_record(R, v, min_baseq, lane, sink);
+    }
+}
+
+// the region of slot s: the last whose first slot is at or before s
+__device__ __forceinline__ int32_t region_of_slot(const PileupRegions &R, int32_t n_regions, int64_t s) {
+    int32_t lo = 0, hi = n_regions - 1;
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo + 1) / 2;
+        if (R.off[mid] <= s) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) pileup_call_kernel(PileupCallTest test, PileupRegions R, int32_t n_regions, const int64_t *slots,
+                                                          int64_t n, bwams_pileup_call_t *out) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = slots[k];
+        bwams_pileup_call_t x;
+        test.genotype(s, &x);
+        x.region = region_of_slot(R, n_regions, s);
+        x.pos = (int32_t)(R.beg[x.region] + (s - R.off[x.region]));
+        out[k] = x;
+    }
+}
+
 __global__ void __launch_bounds__(256) pileup_site_kernel(PileupSiteTest test, PileupRegions R, int32_t n_regions, const int64_t *slots,
                                                           int64_t n, bwams_pileup_site_t *out) {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
         const int64_t s = slots[k];
-        int32_t lo = 0, hi = n_regions - 1;                              // the last region whose first slot is at or before s
-        while (lo < hi) {
-            const int32_t mid = lo + (hi - lo + 1) / 2;
-            if (R.off[mid] <= s) lo = mid;
-            else hi = mid - 1;
-        }
+        const int32_t lo = region_of_slot(R, n_regions, s);
         bwams_pileup_site_t x;
         x.region = lo;
         x.pos = (int32_t)(R.beg[lo] + (s - R.off[lo]));
@@ -372,12 +484,7 @@ __global__ void __launch_bounds__(256) pileup_ref_kernel(PileupRegions R, int32_
                                                          const uint8_t *ref0123, const bwams_contig_t *contigs, const int64_t *hole_off,
                                                          const int32_t *hole_len, int32_t n_holes, uint8_t *out) {
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n_slots; s += (int64_t)gridDim.x * blockDim.x) {
-        int32_t lo = 0, hi = n_regions - 1;
-        while (lo < hi) {
-            const int32_t mid = lo + (hi - lo + 1) / 2;
-            if (R.off[mid] <= s) lo = mid;
-            else hi = mid - 1;
-        }
+        const int32_t lo = region_of_slot(R, n_regions, s);
         out[s] = ref_code_at(ref0123, contigs[reg_ref[lo]].offset + R.beg[lo] + (s - R.off[lo]), hole_off, hole_len, n_holes);
     }
 }
@@ -396,19 +503,35 @@ void launch_pileup_route(const uint8_t *bam, const int64_t *rec_off, int64_t n_r
         pileup_route_kernel<<<grid_of(n_rec, 256, cu_count), 256, 0, st>>>(bam, rec_off, n_rec, f, R, n_tiles, tiled, keys, vals, route, counts);
 }
 
-void launch_pileup_tiles(const uint8_t *bam, const int64_t *rec_off, const PileupRegions &R, int min_baseq, const uint32_t *keys,
-                         const uint32_t *vals, int64_t n_ent, uint32_t n_tiles, uint32_t *heads, uint32_t *n_heads, int64_t n_slots,
-                         uint32_t *counts, int cu_count, hipStream_t st) {
-    if (n_ent <= 0) return;
+int launch_pileup_tiles(const uint8_t *bam, const int64_t *rec_off, const PileupRegions &R, int min_baseq, const uint32_t *keys,
+                        const uint32_t *vals, int64_t n_ent, uint32_t n_tiles, uint32_t *heads, uint32_t *n_heads, int64_t n_slots,
+                        uint32_t *counts, const PileupQuality &quality, int cu_count, hipStream_t st) {
+    if (n_ent <= 0) return 0;
+    // the opt-in for more than 64 KB of dynamic LDS belongs to the current device: set per launch, and checked, before anything is queued
+    if (quality.sums && hipFuncSetAttribute(reinterpret_cast<const void *>(pileup_tile_quality_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, kTileQualityLds) != hipSuccess) return -1;
     pileup_heads_kernel<<<grid_of(n_ent, 256, cu_count), 256, 0, st>>>(keys, n_ent, n_tiles, heads, n_heads);
     const unsigned grid = (unsigned)std::min<int64_t>(n_ent, n_tiles);   // no more tiles can be occupied; the blocks beyond *n_heads leave at once
-    pileup_tile_kernel<<<grid, kTileThreads, 0, st>>>(bam, rec_off, R, min_baseq, keys, vals, n_ent, heads, n_heads, n_slots, counts);
+    if (quality.sums)
+        pileup_tile_quality_kernel<<<grid, kTileThreads, kTileQualityLds, st>>>(bam, rec_off, R, min_baseq, keys, vals, n_ent, heads, n_heads,
+                                                                               n_slots, counts, quality);
+    else
+        pileup_tile_kernel<<<grid, kTileThreads, 0, st>>>(bam, rec_off, R, min_baseq, keys, vals, n_ent, heads, n_heads, n_slots, counts);
+    return 0;
 }
 
 void launch_pileup_direct(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupRegions &R, int min_baseq,
-                          const uint8_t *route, uint32_t *counts, int cu_count, hipStream_t st) {
-    if (n_rec > 0)
+                          const uint8_t *route, uint32_t *counts, const PileupQuality &quality, int cu_count, hipStream_t st) {
+    if (n_rec <= 0) return;
+    if (quality.sums)
+        pileup_direct_quality_kernel<<<grid_of(n_rec, 4, cu_count), 256, 0, st>>>(bam, rec_off, n_rec, R, min_baseq, route, counts, quality);
+    else
         pileup_direct_kernel<<<grid_of(n_rec, 4, cu_count), 256, 0, st>>>(bam, rec_off, n_rec, R, min_baseq, route, counts);
+}
+
+void launch_pileup_calls(const PileupCallTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *slots, int64_t n,
+                         bwams_pileup_call_t *out, int cu_count, hipStream_t st) {
+    if (n > 0) pileup_call_kernel<<<grid_of(n, 256, cu_count), 256, 0, st>>>(test, R, n_regions, slots, n, out);
 }
 
 void launch_pileup_sites(const PileupSiteTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *slots, int64_t n,

@@ -1179,7 +1179,7 @@ int bwams_depth_runs(bwams_depth_t *d, int32_t ref, int32_t beg, int32_t end, in
 int bwams_depth_fetch(bwams_depth_t *d, int32_t ref, int32_t beg, int32_t end, int32_t *depth);
 int bwams_depth_text(bwams_depth_t *d, const char *names, int32_t what, int32_t arg, char *out, int64_t cap, int64_t *n);
 int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
-/* Pileup (csrc/pileup.hip, csrc/api_pileup.hip, host/pileup_text.cpp): per-base allele counts of SEQ and QUAL against the reference,
+/* Pileup (csrc/pileup.hip, csrc/api_pileup.hip, host/pileup_text.cpp, host/pileup_vcf.cpp): per-base allele counts of SEQ and QUAL against the reference,
  * accumulated on the device from a batch's BAM records, from host records, or from the sorted BAM writer's merged stream, and the
  * candidate variant sites they give.  The rules are this library's own, modelled on the defaults of `samtools mpileup`; no byte
  * parity with it is claimed.  bwams/pileup.py restates them in numpy and is what the tests compare against.
@@ -1230,8 +1230,47 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  *       "chrom\tpos\tref\tdepth\tA+\tC+\tG+\tT+\tA-\tC-\tG-\tT-\tN\tDEL\tINS\talt\n"
  *       "c1\t3\tG\t5\t0\t0\t3\t1\t0\t0\t0\t1\t0\t0\t0\tT\n" "c1\t5\tA\t7\t4\t0\t0\t0\t1\t0\t0\t0\t0\t2\t0\tDEL\n"
  *       "c1\t6\tC\t7\t0\t6\t0\t0\t0\t1\t0\t0\t0\t0\t2\tINS\n"
- *     VCF, genotype likelihoods and quality-weighted counts are out of scope: the sites and their counters are the interface for a
- *     caller that wants them.
+ *     Quality-weighted sums, genotype costs, SNV calls and their VCF text are rules 10 to 13, for a handle with a quality plane.
+ *     Indel genotypes are out of scope: the sites and their counters are the interface for a caller that wants them.
+ * 10. Effective quality (a handle with a quality plane: bwams_pileup_set_quality).  A base that rule 4 counts in one of the eight base
+ *     channels has the effective quality qe = clamp(min(q, MAPQ), 4, 60), where q is its QUAL byte, or no_qual_q (default 30) for a
+ *     record whose first QUAL byte is 0xFF.  min_baseq is tested on the raw byte as in rule 4, before this.  N, DEL and INS add
+ *     nothing to the plane.
+ * 11. The sums.  The plane holds 12 uint32 per slot beside the counters (48 bytes more per position): for each base b of A C G T,
+ *     both strands together, Q[b] = sum of qe, HOM[b] = sum of T_HOM[qe] and HET[b] = sum of T_HET[qe], in the order Q[A..T],
+ *     HOM[A..T], HET[A..T] (BWAMS_PILEUP_Q, _HOM, _HET + b).  They accumulate as rule 6's counters do: any order, any number of
+ *     calls, modulo 2^32.  The largest addend is T_HET[4] = 435, so no sum wraps below a depth of 2^32 / 435, which lies above 2^22:
+ *     a caller with a depth above 2^22 gets what wrapped sums give (bwams/pileup.py wraps the same way).
+ * 12. The tables.  The unit is a hundredth of a phred: -1000 log10(p), rounded half to even, with e = 10^(-q / 10).  T_HOM[q] is
+ *     the cost of p = 1 - e, a base under a homozygous genotype of its own allele; T_HET[q] that of p = (1 - e) / 2 + e / 6, a base
+ *     under a heterozygous genotype that holds its allele.  A base under a genotype without its allele has p = e / 3, which costs
+ *     exactly 100 q + 477 for every integer q and needs no table.  For q = 4 .. 60:
+ *       T_HOM = 220 165 126 97 75 58 46 36 28 22 18 14 11 9 7 6 4 3 3 2 2 1 1 1 1 1, then 0 for q = 30 .. 60
+ *       T_HET = 435 404 381 363 350 339 331 325 320 316 313 310 308 307 306 305 304 303 303 302 302 302 302 302, then 301 for
+ *               q = 28 .. 60
+ *     (computed with 60 decimal digits; no entry lies within 0.002 of a rounding boundary).  csrc/common.h holds them as integer
+ *     literals, bwams/pileup.py restates them, and tests/test_pileup_calls.py recomputes both.  There is no floating point between
+ *     the records and a call.
+ * 13. Genotype costs and calls, at a slot whose reference base is r < 4 and whose base depth is at least min_depth (default 1).
+ *     n[b] is channel b plus channel b + 4; the base depth n = sum of n[b] leaves out DEL, N and INS; MIS[b] = 100 Q[b] + 477 n[b].
+ *     The ten diploid genotypes (a1 <= a2 by base code) have the index g = a2 (a2 + 1) / 2 + a1, VCF's order over A C G T:
+ *     AA AC CC AG CG GG AT CT GT TT.  cost(g) is the sum over the four bases b of HOM[b] when g is homozygous b b, of HET[b] when g
+ *     is heterozygous and b one of its alleles, and of MIS[b] when b is no allele of g, in uint64 from the uint32 sums.
+ *     pl[g] = (cost(g) - least cost + 50) / 100 by integer division, uncapped, as int32 saturating at 2^31 - 1.  The genotype is
+ *     the g of least cost, a tie going to the lowest g; qual = pl[g(r, r)]; gq = min(99, the least pl over the other nine
+ *     genotypes).  A slot is a CALL when its genotype is not (r, r) and qual >= min_qual (default 20).  There is no prior on
+ *     heterozygosity and no model of strand bias or of overlapping mates (rule 5): every base is an independent observation, and
+ *     min_qual is the caller's lever.  bwams_pileup_calls returns the calls of all regions in slot order as bwams_pileup_call_t
+ *     records (include/bwams_types.h): region, pos, ref, a1, a2, qual, gq, depth, n[4], pl[10]; they are counted and selected with
+ *     rocprim::reduce and rocprim::select, as the sites are.
+ *     VCF (bwams_pileup_vcf; names as in rule 9, sample: the name of the one sample column).  The header lines
+ *     ##fileformat=VCFv4.2, ##source=bwams, one ##contig=<ID=name,length=L> per reference, ##INFO DP (1, Integer), ##FORMAT GT (1,
+ *     String), AD (R, Integer), DP (1, Integer), GQ (1, Integer) and PL (G, Integer), and the #CHROM line; then a row per call.  ALT
+ *     is the genotype's alleles other than the reference, in base order, one or two; GT their indices (0 the reference, 1 and 2 the
+ *     ALTs) as a/b with a <= b; AD is n over REF and the ALTs; PL the pl of the genotypes over (REF, ALTs) in VCF's order, three
+ *     values or six.  Rule 9's seven records with MAPQ 60: slot 2 (reference G) has three G and two T of quality 30, so
+ *     cost(GG) = 2 * 3477 = 6954, cost(GT) = 5 * 301 = 1505 and cost(TT) = 3 * 3477 = 10431, pl is 54 / 0 / 89, and the only row is
+ *       "c1\t3\t.\tG\tT\t54\t.\tDP=5\tGT:AD:DP:GQ:PL\t0/1:3,2:5:54:54,0,89\n"
  * bwams_pileup_open: a zeroed handle on `device` (opt may be NULL for the defaults; exclude above 0xFFFF, min_baseq outside [0, 255],
  * min_alt < 1, min_permille outside [0, 1000], reserved != 0, n_ref < 0, a negative length or rule 1: BWAMS_ERR_ARG).  _close (NULL
  * allowed).  _add_batch: the batch's current BAM records (bwams_bam_run / _upload left them, BWAMS_ERR_ARG before either), read in
@@ -1242,16 +1281,27 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  * 12 per position: for tests and small ranges.  _sites: *n (may be NULL) the number of sites, found or needed; sites may be NULL to
  * ask for it; cap too small: BWAMS_ERR_CAPACITY.  min_alt and min_permille: rule 8's thresholds for this query, a negative value
  * for the handle's.  _text: rule 9 into out[0, cap); *n: the bytes written, or needed with BWAMS_ERR_CAPACITY, as bwams_sam_header.
+ * _set_quality: the quality plane of rules 10 to 13, allocated beside the counters and zeroed (opt may be NULL for {20, 1, 30, 0};
+ * min_qual < 0, min_depth < 1, no_qual_q outside [0, 93] or reserved != 0: BWAMS_ERR_ARG; BWAMS_ERR_NOMEM when the plane does not
+ * fit, as rule 1 has it for the counters).  It is legal only while the counters are zero, before the first add or directly after
+ * _reset (BWAMS_ERR_ARG otherwise); calling it again then replaces the options and zeroes the plane, which stays for the life of the
+ * handle; _reset zeroes both planes.  A handle on which it was never called behaves in every call as if the plane did not exist, and
+ * its adds run the count-only kernels.  _fetch_quality: the sums of positions [beg, end), 12 per position, as _fetch.  _calls: as
+ * _sites; min_qual and min_depth: rule 13's thresholds for this query, a negative value for the handle's (min_depth 0:
+ * BWAMS_ERR_ARG).  _vcf: rule 13's text into out[0, cap), as _text.  _fetch_quality, _calls and _vcf on a handle without a plane:
+ * BWAMS_ERR_ARG.
  * _info: the positions of a tile of the add (below), the handle's regions and slots, and of the last add the records counted, the
  * (tile, record) entries, the records routed direct and the device time: a test and measurement hook, like bwams_debug_chain_counts.
  * An add cuts the slots into tiles.  A record whose slots lie in one or two tiles is counted in LDS by the workgroup that owns
  * the tile and the tile is added to HBM once; a record that touches more tiles (a long read, an N skip) goes to a kernel that issues
  * a global atomic per base, and so does every record under BWAMS_PILEUP_TILED=0 (the A/B baseline; the counters are the same).
+ * With a quality plane a tile holds both planes and a counted base adds four values, in either kernel; the routing is the same.
  * bwams_sorter_set_pileup: the conditions and guarantees of bwams_sorter_set_depth: before the sorter's first put (BWAMS_ERR_ARG later,
  * for a handle on another device, or when the handle's lengths differ from the sorter header's); the close adds every record of the
  * merged stream AS WRITTEN, after the merge has set or cleared 0x400, in whole records (one cut by a deflate piece's end is counted
  * once); the file and the index are byte for byte what they are without the call; an add that fails ends the close with its error.
- * A sorter may have a depth handle, a pileup handle, or both: both see the same whole records. */
+ * A sorter may have a depth handle, a pileup handle, or both: both see the same whole records.  A handle with a quality plane set on
+ * a sorter receives the sums through the same add: the close leaves it ready for _calls and _vcf. */
 int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwams_pileup_region_t *regions, int32_t n_regions,
                       const bwams_pileup_opt_t *opt, bwams_pileup_t **out);
 int bwams_pileup_close(bwams_pileup_t *p);
@@ -1264,6 +1314,11 @@ int bwams_pileup_fetch(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t e
 int bwams_pileup_sites(bwams_pileup_t *p, int32_t min_alt, int32_t min_permille, bwams_pileup_site_t *sites, int64_t cap, int64_t *n);
 int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int32_t min_permille, char *out, int64_t cap, int64_t *n);
 int bwams_pileup_info(const bwams_pileup_t *p, bwams_pileup_info_t *info);
+int bwams_pileup_set_quality(bwams_pileup_t *p, const bwams_pileup_gl_opt_t *opt);
+int bwams_pileup_fetch_quality(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *sums);
+int bwams_pileup_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, bwams_pileup_call_t *calls, int64_t cap, int64_t *n);
+int bwams_pileup_vcf(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, char *out, int64_t cap,
+                     int64_t *n);
 int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p);
 /* Alignment QC (csrc/qc.hip, csrc/api_qc.hip, host/qc_text.cpp): the flag counts, insert sizes and per-cycle tables that a pipeline
  * reads off a finished BAM, accumulated on the device from a batch's BAM records, from host records, or from the sorted BAM

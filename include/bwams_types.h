@@ -348,6 +348,29 @@ typedef struct bwams_pileup_site {
     uint32_t c[BWAMS_PILEUP_CHANNELS];
 } bwams_pileup_site_t;
 
+/* Rules 10 and 13: the thresholds of a call and the quality of a record without qualities.  reserved must be 0.  A NULL pointer
+ * means {20, 1, 30, 0}. */
+typedef struct bwams_pileup_gl_opt {
+    int32_t min_qual;            /* >= 0 */
+    int32_t min_depth;           /* >= 1 */
+    int32_t no_qual_q;           /* 0..93 */
+    int32_t reserved;
+} bwams_pileup_gl_opt_t;
+
+/* The sums of a slot's quality plane (rule 11), as indices into its 12 values: Q, HOM and HET of base b at these + b. */
+#define BWAMS_PILEUP_Q   0
+#define BWAMS_PILEUP_HOM 4
+#define BWAMS_PILEUP_HET 8
+
+/* One SNV call (rule 13): the region's index in the handle's list, the position on the region's reference, the reference base
+ * (0..3), the genotype's alleles a1 <= a2 (0..3), QUAL, GQ, the base depth, n[b] of the four bases and the ten pl in VCF order. */
+typedef struct bwams_pileup_call {
+    int32_t  region, pos, ref, a1, a2, qual, gq;
+    uint32_t depth;
+    uint32_t n[4];
+    int32_t  pl[10];
+} bwams_pileup_call_t;
+
 /* bwams_pileup_info: the tile of the tiled path in positions, the handle's slots, and of the last add the records rule 2 let
  * through, the (tile, record) entries of the tiled path and the records that went to the direct kernel.  ms_check and ms_add are
  * for measurement only (tools/pileup_rate.py), nothing a caller should build on: the device time between events around rule 3's

@@ -8,6 +8,10 @@ bwams_pileup_add_records, whose kernels the library times between events (bwams_
 bwams_depth_add_records takes the same bytes; it has no events, so its row is the host clock around the call with the upload in it,
 next to the same clock around the pileup add: the kernels of the depth add come from a `rocprofv3 --kernel-trace --stats` run of
 this tool (--reps 2 is enough for that).  One JSON line per measurement on stdout.
+
+--quality: the same adds with the quality plane on (bwams_pileup_set_quality: four additions per counted base, both planes of a
+tile in LDS), tiled and direct, and then, in place of the depth add, bwams_pileup_calls over all the slots against a random
+reference: the host clock around the call that counts and the call that fetches.
 """
 from __future__ import annotations
 
@@ -55,6 +59,7 @@ def main():
     ap.add_argument("--mbp", type=float, default=50.0)
     ap.add_argument("--coverage", type=float, default=30.0)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--quality", action="store_true")
     a = ap.parse_args()
     l_ref = int(a.mbp * 1e6)
     n = int(l_ref * a.coverage / 150)
@@ -68,6 +73,8 @@ def main():
         os.environ["BWAMS_PILEUP_TILED"] = str(tiled)
         capi.debug_reload()
         p = capi.Pileup([l_ref])
+        if a.quality:
+            p.set_quality()
         cnt = C.c_int64(0)
         check, add, wall = [], [], []
         for rep in range(a.reps + 1):                                                       # the first is the warm-up
@@ -79,8 +86,24 @@ def main():
                 check.append(i["ms_check"]); add.append(i["ms_add"]); wall.append(w)
         total = [x + y for x, y in zip(check, add)]
         depth_at = int(p.fetch(0, l_ref // 2, l_ref // 2 + 1)[0, :8].sum())
+        if a.quality and not tiled:                                                         # the calls, once: the planes are the same either way
+            p.reset()
+            capi._chk(L.bwams_pileup_add_records(p.h, ptr, n_bytes, C.byref(cnt)), "bwams_pileup_add_records")
+            p.set_ref(0, np.random.default_rng(12).integers(0, 4, l_ref, dtype=np.uint8))
+            count, fetch = [], []
+            for rep in range(a.reps + 1):
+                t = time.perf_counter()
+                n_calls = C.c_int64(0)
+                capi._chk(L.bwams_pileup_calls(p.h, -1, -1, None, 0, C.byref(n_calls)), "bwams_pileup_calls")
+                t1 = time.perf_counter()
+                got = p.calls(cap=n_calls.value)
+                t2 = time.perf_counter()
+                if rep:
+                    count.append((t1 - t) * 1e3); fetch.append((t2 - t1) * 1e3)
+            print(json.dumps({"calls": len(got), "slots": l_ref, "count_ms": stats(count), "count_and_fetch_ms": stats(fetch),
+                              "slots_per_s": round(l_ref / float(np.median(count)) * 1e3)}), flush=True)
         p.close()
-        tag = "tiled" if tiled else "direct"
+        tag = ("quality_" if a.quality else "") + ("tiled" if tiled else "direct")
         out[tag] = float(np.median(total))
         print(json.dumps({"pileup": tag, "counted": cnt.value, "entries": i["n_entries"], "routed_direct": i["n_direct"],
                           "check_ms": stats(check), "add_ms": stats(add), "kernels_ms": stats(total), "call_ms": stats(wall),
@@ -89,6 +112,9 @@ def main():
                           "depth_mid": depth_at // (a.reps + 1)}), flush=True)
     del os.environ["BWAMS_PILEUP_TILED"]
     capi.debug_reload()
+    if a.quality:
+        print(json.dumps({"tiled_over_direct": round(out["quality_direct"] / out["quality_tiled"], 2)}), flush=True)
+        return
     d = capi.Depth([l_ref])
     wall = []
     for rep in range(a.reps + 1):
