@@ -240,7 +240,7 @@ int bwams_batch_stats(bwams_batch_t *b, bwams_stats_t *out) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, b->ev[a], b->ev[bb]) == hipSuccess) *dst = ms;
     };
-    if (b->sd.done) {
+    if (has(b, Product::seeds)) {
         el(b->kEvR1Start, b->kEvR1End, &s.ms_smem_r1);
         el(b->kEvR2Start, b->kEvR2End, &s.ms_smem_r2);
         el(b->kEvR3Start, b->kEvR3End, &s.ms_smem_r3);
@@ -256,7 +256,7 @@ int bwams_batch_stats(bwams_batch_t *b, bwams_stats_t *out) {
     s.ert_ref_bytes = (int64_t)c.ert_ref;
     s.emf_nodes = (int64_t)b->emf.emf_nodes;
     s.emf_cmp_bytes = (int64_t)b->emf.emf_cmp_bytes;
-    stage_state_stats(b->stages, &s);
+    stage_state_stats(b, &s);
     (void)hipGetLastError();
     *out = s;
     return BWAMS_OK;

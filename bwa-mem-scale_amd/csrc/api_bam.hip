@@ -71,7 +71,7 @@ extern "C" {
 /* ------------------------------------------------------------ BAM records (bam.hip) ---- */
 
 int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
-    if (!b || !b->stages || !b->stages->sm.done) {
+    if (!has(b, Product::sam)) {
         set_last_error("bwams_bam_run: run bwams_sam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -87,7 +87,7 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(ix->device));
     hipStream_t st = b->stream;
-    outdated(s, From::bam);
+    outdated(b, Product::bam);
     s->bm.nref = (uint32_t)ix->n_seqs;
     const int64_t nseq = s->sm.merged_n >= 0 ? s->sm.merged_n : s->ch.nseq;
     DevBuf<int64_t> ends;
@@ -99,9 +99,10 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     if (n_rec == 0) {                                         // no text (a chunk of no reads): no records
         BWAMS_HIP(hipMemsetAsync(s->bm.off.p, 0, (size_t)(nseq + 1) * 8, st));
         BWAMS_HIP(hipStreamSynchronize(st));
-        s->bm.bytes = 0; s->bm.nrec = 0; s->bm.nseq = nseq; s->bm.done = true;
+        s->bm.bytes = 0; s->bm.nrec = 0; s->bm.nseq = nseq;
         if (bam_bytes) *bam_bytes = 0;
         if (n_records) *n_records = 0;
+        produced(b, Product::bam);
         return BWAMS_OK;
     }
     BamArgs A;
@@ -131,14 +132,15 @@ int bwams_bam_run(bwams_batch_t *b, int64_t *bam_bytes, int64_t *n_records) {
     launch_bam_write(A, s->bm.off.p, b->cu_count, st);
     BWAMS_HIP(hipGetLastError());
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->bm.bytes = total; s->bm.nrec = n_rec; s->bm.nseq = nseq; s->bm.done = true;
+    s->bm.bytes = total; s->bm.nrec = n_rec; s->bm.nseq = nseq;
     if (bam_bytes) *bam_bytes = total;
     if (n_records) *n_records = n_rec;
+    produced(b, Product::bam);
     return BWAMS_OK;
 }
 
 int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off) {
-    if (!b || !b->stages || !b->stages->bm.done) {
+    if (!has(b, Product::bam)) {
         set_last_error("bwams_bam_fetch: run bwams_bam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -153,7 +155,7 @@ int bwams_bam_fetch(bwams_batch_t *b, void *bam, int64_t cap, int64_t *read_off)
 }
 
 int bwams_bam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out) {
-    if (!b || !d || !b->stages || !b->stages->bm.done) {
+    if (!d || !has(b, Product::bam)) {
         set_last_error("bwams_bam_fetch_bgzf: run bwams_bam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -182,7 +184,7 @@ int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t
     if (rc) return rc;
     hipStream_t st = b->stream;
     const int64_t n_rec = (int64_t)off.size() - 1;
-    outdated(s, From::bam);
+    outdated(b, Product::bam);
     BWAMS_HIP(hipStreamSynchronize(st));                     // the buffers below may still be read by queued work
     BWAMS_HIP(s->bm.out.ensure_n((size_t)n_bytes + 16)); BWAMS_HIP(s->bm.roff.ensure_n((size_t)(n_rec + 1)));
     BWAMS_HIP(s->bm.off.ensure_n((size_t)(n_rec + 1)));
@@ -190,18 +192,19 @@ int bwams_bam_upload(bwams_batch_t *b, const void *bam, int64_t n_bytes, int64_t
     BWAMS_HIP(hipMemcpyAsync(s->bm.roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipMemcpyAsync(s->bm.off.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->bm.bytes = n_bytes; s->bm.nrec = n_rec; s->bm.nseq = n_rec; s->bm.nref = (uint32_t)(max_rid + 1); s->bm.done = true;
+    s->bm.bytes = n_bytes; s->bm.nrec = n_rec; s->bm.nseq = n_rec; s->bm.nref = (uint32_t)(max_rid + 1);
     if (n_records) *n_records = n_rec;
+    produced(b, Product::bam);
     return BWAMS_OK;
 }
 
 int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records) {
-    if (!b || !b->stages || !b->stages->bm.done) {
+    if (!has(b, Product::bam)) {
         set_last_error("bwams_bam_sort: run bwams_bam_run or bwams_bam_upload first");
         return BWAMS_ERR_ARG;
     }
     StageState *s = b->stages;
-    if (s->bs.done) {
+    if (has(b, Product::sorted)) {
         if (n_records) *n_records = s->bs.nrec;
         return BWAMS_OK;
     }
@@ -232,13 +235,14 @@ int bwams_bam_sort(bwams_batch_t *b, int64_t *n_records) {
         BWAMS_HIP(hipGetLastError());
     }
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->bs.bytes = s->bm.bytes; s->bs.nrec = n; s->bs.done = true;
+    s->bs.bytes = s->bm.bytes; s->bs.nrec = n;
     if (n_records) *n_records = n;
+    produced(b, Product::sorted);
     return BWAMS_OK;
 }
 
 int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_coord_t *coords) {
-    if (!b || !b->stages || !b->stages->bm.done || !b->stages->bs.done) {
+    if (!has(b, Product::bam, Product::sorted)) {
         set_last_error("bwams_bam_sorted_fetch: run bwams_bam_sort first");
         return BWAMS_ERR_ARG;
     }
@@ -256,21 +260,20 @@ int bwams_bam_sorted_fetch(bwams_batch_t *b, void *bam, int64_t cap, bwams_bam_c
 /* ------------------------------------------------------------ duplicate marking (markdup.hip) ---- */
 
 int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends) {
-    if (!b || !b->stages || !b->stages->bm.done) {
+    if (!has(b, Product::bam)) {
         set_last_error("bwams_bam_templates: run bwams_bam_run or bwams_bam_upload first");
         return BWAMS_ERR_ARG;
     }
     StageState *s = b->stages;
-    if (!s->md.done) {
+    if (!has(b, Product::templates)) {                       // (and so no template_locs either: they go when the templates go)
         if (s->bm.nrec > 0xFFFFFFFFLL) {
             set_last_error("bwams_bam_templates: more than 2^32 - 1 records");
             return BWAMS_ERR_UNSUPPORTED;
         }
         BWAMS_HIP(hipSetDevice(b->idx->device));
         BWAMS_HIP(hipStreamSynchronize(b->stream));          // the buffers below may still be read by queued work
-        s->md.loc_done = false;
         if (int rc = md_templates(s->md.t, s->bm.out.p, s->bm.roff.p, s->bm.nrec, b->cu_count, b->stream)) return rc;
-        s->md.done = true;
+        produced(b, Product::templates);
     }
     if (n_templates) *n_templates = s->md.t.n_t;
     if (n_ends) *n_ends = s->md.t.n_e;
@@ -278,7 +281,7 @@ int bwams_bam_templates(bwams_batch_t *b, int64_t *n_templates, int64_t *n_ends)
 }
 
 int bwams_bam_templates_fetch(bwams_batch_t *b, bwams_dup_end_t *ends, int64_t cap, uint32_t *rec_tmpl, int32_t sorted) {
-    if (!b || !b->stages || !b->stages->bm.done || !b->stages->md.done || (sorted && !b->stages->bs.done)) {
+    if (!has(b, Product::bam, Product::templates) || (sorted && !has(b, Product::sorted))) {
         set_last_error("bwams_bam_templates_fetch: run bwams_bam_templates (and bwams_bam_sort for sorted = 1) on the current records first");
         return BWAMS_ERR_ARG;
     }
@@ -422,18 +425,18 @@ static int groups_upload(StageState *s, const bwams_dup_groups_t *g, MdGroupsDev
 int bwams_bam_templates2(bwams_batch_t *b, const bwams_dup_groups_t *groups, int64_t *n_templates, int64_t *n_ends) {
     if (int rc = bwams_bam_templates(b, n_templates, n_ends)) return rc;
     StageState *s = b->stages;
+    outdated(b, Product::template_locs);
     BWAMS_HIP(hipSetDevice(b->idx->device));
-    s->md.loc_done = false;
     MdGroupsDev G;
     if (int rc = groups_upload(s, groups, &G, b->stream)) return rc;
     if (int rc = md_locs(s->md.t, s->bm.out.p, s->bm.roff.p, s->bm.nrec, G, b->cu_count, b->stream)) return rc;
     s->md.n_lib = G.n_lib;
-    s->md.loc_done = true;
+    produced(b, Product::template_locs);
     return BWAMS_OK;
 }
 
 int bwams_bam_templates_fetch_loc(bwams_batch_t *b, bwams_dup_loc_t *loc, int64_t cap) {
-    if (!b || !b->stages || !b->stages->bm.done || !b->stages->md.done || !b->stages->md.loc_done) {
+    if (!has(b, Product::bam, Product::templates, Product::template_locs)) {
         set_last_error("bwams_bam_templates_fetch_loc: run bwams_bam_templates2 on the current records first");
         return BWAMS_ERR_ARG;
     }
@@ -447,18 +450,19 @@ int bwams_bam_templates_fetch_loc(bwams_batch_t *b, bwams_dup_loc_t *loc, int64_
 }
 
 int bwams_bam_lib_record_counts(bwams_batch_t *b, int64_t *secondary_or_supplementary, int64_t *unmapped, int64_t cap_lib) {
-    if (!b || !b->stages || !b->stages->bm.done || !b->stages->md.done) {
+    if (!has(b, Product::bam, Product::templates)) {
         set_last_error("bwams_bam_lib_record_counts: run bwams_bam_templates or _templates2 on the current records first");
         return BWAMS_ERR_ARG;
     }
     StageState *s = b->stages;
-    const int64_t n_lib = s->md.loc_done ? s->md.n_lib : 1;
+    const bool locs = has(b, Product::template_locs);
+    const int64_t n_lib = locs ? s->md.n_lib : 1;
     if (cap_lib < n_lib) return BWAMS_ERR_CAPACITY;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t q = b->stream;
     BWAMS_HIP(s->md.lib_counts.ensure_n((size_t)n_lib * 7));
     BWAMS_HIP(hipMemsetAsync(s->md.lib_counts.p, 0, (size_t)n_lib * 7 * 8, q));
-    launch_md_lib_recs(s->md.t, s->bm.nrec, s->md.loc_done && s->md.t.n_t ? s->md.t.tloc.as<const bwams_dup_loc_t>() : nullptr,
+    launch_md_lib_recs(s->md.t, s->bm.nrec, locs && s->md.t.n_t ? s->md.t.tloc.as<const bwams_dup_loc_t>() : nullptr,
                        (int)n_lib, s->md.lib_counts.p, b->cu_count, q);
     std::vector<unsigned long long> c((size_t)n_lib * 7);
     BWAMS_HIP(hipMemcpyAsync(c.data(), s->md.lib_counts.p, c.size() * 8, hipMemcpyDeviceToHost, q));
@@ -509,7 +513,7 @@ int bwams_bam_markdup2(bwams_batch_t *b, const bwams_dup_groups_t *groups, const
     const uint32_t *rt = s->md.t.rtmpl.as<const uint32_t>();
     const uint8_t *dup = s->md.dup.p;
     launch_md_apply(s->bm.out.p, s->bm.roff.p, nullptr, rt, dup, n, marked, b->cu_count, q);
-    if (s->bs.done)                                          // the sorted copy: record i is the unsorted record bs.idx2[i]
+    if (has(b, Product::sorted))                             // the sorted copy: record i is the unsorted record bs.idx2[i]
         launch_md_apply(s->bs.out.p, s->bs.off.p, s->bs.idx2.p, rt, dup, n, marked + 1, b->cu_count, q);
     std::vector<unsigned long long> c;
     if (lib_stats) {

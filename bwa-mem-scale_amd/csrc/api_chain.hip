@@ -101,7 +101,7 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
 
 int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_chains, int64_t *n_seeds) {
     if (b && b->stages) b->stages->ch.ran = false;       // bwams_debug_chain_counts reports the LAST run: a refused one has nothing to report
-    if (!b || !b->sd.done || !b->sd.with_sa) {
+    if (!has(b, Product::seeds) || !b->sd.with_sa) {
         set_last_error("bwams_chain_run: run bwams_seed_run(with_sa = 1) first");
         return BWAMS_ERR_ARG;
     }
@@ -117,7 +117,7 @@ int bwams_chain_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_cha
 int bwams_chain_run_ert(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_ert_mem_t *mems, const int64_t *mem_off,
                         const uint64_t *hits, const int64_t *hit_off, int64_t *n_chains, int64_t *n_seeds) {
     if (b && b->stages) b->stages->ch.ran = false;
-    if (!b || b->nseq <= 0 || !mem_off || !hit_off) {
+    if (!has(b, Product::reads) || b->nseq <= 0 || !mem_off || !hit_off) {
         set_last_error("bwams_chain_run_ert: upload the reads first (bwams_seed_upload) and pass the MEM / hit offsets");
         return BWAMS_ERR_ARG;
     }
@@ -175,7 +175,7 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
     BWAMS_HIP(hipSetDevice(b->idx->device));
     StageState *s;
     if ((rc = get_state(b, &s))) return rc;
-    outdated(s, From::chain);
+    outdated(b, Product::chains);
     hipStream_t st = b->stream;
     const int64_t nseq = b->nseq, n_sa = sv.n_sa, n1 = nseq + 1;
     const size_t ns = (size_t)(n_sa > 0 ? n_sa : 1);
@@ -277,16 +277,16 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
     if (has_long && tot[0] > 0 && (rc = flt_chained_seeds(b, s, opt, A.bns))) return rc;
     BWAMS_HIP(hipEventRecord(s->ev[1], st));
     BWAMS_HIP(hipGetLastError());
-    s->ch.done = true;
     s->opt = *opt;
     if (n_chains) *n_chains = s->ch.n_chains;
     if (n_seeds) *n_seeds = s->ch.n_seeds;
+    produced(b, Product::chains);
     return BWAMS_OK;
 }
 
 int bwams_chain_fetch(bwams_batch_t *b, bwams_chain_t *chains, int64_t chain_cap, bwams_chain_seed_t *seeds,
                       int64_t seed_cap, int64_t *chain_off) {
-    if (!b || !b->stages || !b->stages->ch.done) {
+    if (!has(b, Product::chains)) {
         set_last_error("bwams_chain_fetch: no chains on the device");
         return BWAMS_ERR_ARG;
     }
@@ -304,7 +304,7 @@ int bwams_chain_fetch(bwams_batch_t *b, bwams_chain_t *chains, int64_t chain_cap
 /* Test hook: routes and passes of the last chaining run (include/bwams.h). */
 int bwams_debug_chain_counts(bwams_batch_t *b, int64_t counts[26]) {
     static_assert(kChainCounts == 26, "include/bwams.h documents 26 counters");
-    if (!b || !counts || !b->stages || !b->stages->ch.done || !b->stages->ch.ran) {
+    if (!counts || !has(b, Product::chains) || !b->stages->ch.ran) {
         set_last_error("bwams_debug_chain_counts: no bwams_chain_run / bwams_chain_run_ert on this batch");
         return BWAMS_ERR_ARG;
     }
@@ -315,7 +315,7 @@ int bwams_debug_chain_counts(bwams_batch_t *b, int64_t counts[26]) {
 int bwams_chain_upload(bwams_batch_t *b, const bwams_chain_t *chains, int64_t n_chains, const bwams_chain_seed_t *seeds,
                        int64_t n_seeds, const int64_t *chain_off) {
     if (!b || !chain_off || n_chains < 0 || n_seeds < 0 || (n_chains && (!chains || !seeds))) return BWAMS_ERR_ARG;
-    if (b->nseq <= 0) {
+    if (!has(b, Product::reads) || b->nseq <= 0) {
         set_last_error("bwams_chain_upload: upload the reads first (bwams_seed_upload)");
         return BWAMS_ERR_ARG;
     }
@@ -345,7 +345,7 @@ int bwams_chain_upload(bwams_batch_t *b, const bwams_chain_t *chains, int64_t n_
     StageState *s;
     int rc = get_state(b, &s);
     if (rc) { delete[] soff; return rc; }
-    outdated(s, From::chain);
+    outdated(b, Product::chains);
     hipStream_t st = b->stream;
     BWAMS_HIP(s->ch.chain_off.ensure((size_t)n1 * 16)); BWAMS_HIP(s->ch.chains.ensure_n((size_t)(n_chains + 1)));
     BWAMS_HIP(s->ch.seeds.ensure_n((size_t)(n_seeds + 1)));
@@ -356,7 +356,8 @@ int bwams_chain_upload(bwams_batch_t *b, const bwams_chain_t *chains, int64_t n_
     BWAMS_HIP(hipStreamSynchronize(st));
     delete[] soff;
     s->ch.n_chains = n_chains; s->ch.n_seeds = n_seeds; s->ch.nseq = nseq;
-    s->ch.done = true; s->ch.ran = false;
+    s->ch.ran = false;
+    produced(b, Product::chains);
     return BWAMS_OK;
 }
 }  // extern "C"

@@ -91,7 +91,8 @@ static int emf_out_ensure(bwams_batch_t *b, int64_t nseq) {
 /* Resident form: probe the reads uploaded by bwams_seed_upload and set the batch's skip flags on the
  * device, so that the following bwams_seed_run leaves the matched reads out. */
 int bwams_emf_run(bwams_batch_t *b, bwams_emf_t *e) {
-    if (!b || !e || e->idx != b->idx) return BWAMS_ERR_ARG;
+    if (!b || !e || e->idx != b->idx || !has(b, Product::reads)) return BWAMS_ERR_ARG;
+    outdated(b, Product::probe);
     BWAMS_HIP(hipSetDevice(b->idx->device));
     const int64_t nseq = b->nseq;
     if (int rc = emf_out_ensure(b, nseq)) return rc;
@@ -107,11 +108,12 @@ int bwams_emf_run(bwams_batch_t *b, bwams_emf_t *e) {
     b->emf.emf_cmp_bytes = b->h_ctr.p->emf_cmp_bytes;
     BWAMS_HIP(hipGetLastError());
     b->has_skip = true;
+    produced(b, Product::probe);
     return BWAMS_OK;
 }
 
 int bwams_emf_fetch(bwams_batch_t *b, bwams_perfect_t *out, uint8_t *code) {
-    if (!b || !b->emf.d_emf_out.p) return BWAMS_ERR_ARG;
+    if (!has(b, Product::probe)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     if (b->nseq) {
         if (out) BWAMS_HIP(hipMemcpyAsync(out, b->emf.d_emf_out.p, (size_t)b->nseq * 8, hipMemcpyDeviceToHost, b->stream));
@@ -208,6 +210,9 @@ int bwams_emf_probe(bwams_batch_t *b, bwams_emf_t *e, const uint8_t *enc, const 
     }
     const int64_t nb = cum[nseq] - cum[0];
     if (cum[0] != 0 || nseq > b->max_reads || nb > b->max_bases) return BWAMS_ERR_CAPACITY;
+    // the caller's reads overwrite the resident ones and the probe's words, and nothing beside them is brought up to date: whatever
+    // follows needs a new bwams_seed_upload
+    outdated(b, Product::reads);
     BWAMS_HIP(hipSetDevice(b->idx->device));
     if (int rc = emf_out_ensure(b, nseq)) return rc;
     hipStream_t st = b->stream;
@@ -220,7 +225,6 @@ int bwams_emf_probe(bwams_batch_t *b, bwams_emf_t *e, const uint8_t *enc, const 
         BWAMS_HIP(hipMemcpyAsync(code, b->emf.d_emf_code.p, (size_t)nseq, hipMemcpyDeviceToHost, st));
     }
     BWAMS_HIP(hipStreamSynchronize(st));
-    b->sd.done = false;            // the resident reads were replaced
     return BWAMS_OK;
 }
 

@@ -113,7 +113,7 @@ static int ext_build_round(bwams_batch *b, StageState *s, const ExtArgs &A, int6
 }
 
 int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_left, int64_t *n_right) {
-    if (!b || !b->stages || !b->stages->ch.done) {
+    if (!has(b, Product::chains)) {
         set_last_error("bwams_extend_build: run bwams_chain_run (or bwams_chain_upload) first");
         return BWAMS_ERR_ARG;
     }
@@ -125,7 +125,7 @@ int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_
     if (rc) return rc;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     StageState *s = b->stages;
-    outdated(s, From::built);
+    outdated(b, Product::built);
     hipStream_t st = b->stream;
     ExtArgs A;
     BWAMS_HIP(hipEventRecord(s->ev[2], st));
@@ -134,10 +134,10 @@ int bwams_extend_build(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_
     if ((rc = ext_build_flat(b, s, A, nullptr, s->ch.n_seeds, tot))) return rc;
     BWAMS_HIP(hipEventRecord(s->ev[3], st));
     BWAMS_HIP(hipGetLastError());
-    s->ext.built = true;
     s->opt = *opt;
     if (n_left) *n_left = tot[0];
     if (n_right) *n_right = tot[3];
+    produced(b, Product::built);
     return BWAMS_OK;
 }
 
@@ -199,7 +199,7 @@ static int run_side(bwams_batch *b, StageState *s, const ExtArgs &A, int right, 
 // the next round's sizes — and once after the plan, once more when the rest is requested.  One list serves every
 // round: a round's build has consumed it before that round's selection, which alone appends, clears its cursor.
 int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !b->stages || !b->stages->ch.done) {
+    if (!has(b, Product::chains)) {
         set_last_error("bwams_extend_run: run bwams_chain_run (or bwams_chain_upload) first");
         return BWAMS_ERR_ARG;
     }
@@ -216,7 +216,7 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
     StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    outdated(s, From::built);
+    outdated(b, Product::built);                                // the run plans and builds its own tasks over the flat lists' buffers
     ExtArgs A;
     BWAMS_HIP(hipEventRecord(s->ev[10], st));
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->bsw_cells, 0, sizeof(unsigned long long), st));      // DP cells of this run, all rounds
@@ -271,14 +271,14 @@ int bwams_extend_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_re
     BWAMS_HIP(hipGetLastError());
     s->ext.n_rounds = round + 1;
     s->ext.n_left = tot_left; s->ext.n_right = tot_right;
-    s->ext.done = true;
     s->opt = *opt;
     if (n_regs) *n_regs = s->ch.n_seeds;
+    produced(b, Product::ext);
     return BWAMS_OK;
 }
 
 int bwams_extend_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off, int32_t *seed_aln) {
-    if (!b || !b->stages || !(b->stages->ext.done || b->stages->ext.built)) {
+    if (!has(b, Product::ext) && !has(b, Product::built)) {
         set_last_error("bwams_extend_fetch: no regions on the device");
         return BWAMS_ERR_ARG;
     }
@@ -298,7 +298,7 @@ int bwams_extend_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, 
 int bwams_extend_tasks_fetch(bwams_batch_t *b, int32_t side, bwams_seqpair_t *pairs, int64_t pair_cap, uint8_t *ref,
                              int64_t ref_cap, uint8_t *qer, int64_t qer_cap, int64_t *n_pairs, int64_t *ref_bytes,
                              int64_t *qer_bytes) {
-    if (!b || !b->stages || !(b->stages->ext.built || b->stages->ext.done) || (side != 0 && side != 1)) {
+    if ((!has(b, Product::built) && !has(b, Product::ext)) || (side != 0 && side != 1)) {
         set_last_error("bwams_extend_tasks_fetch: no task lists on the device");
         return BWAMS_ERR_ARG;
     }

@@ -43,8 +43,12 @@ static int process_stage2(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, 
 }
 
 static void process_empty(bwams_batch_t *b, int64_t *sam_bytes) {      // an empty chunk: no reads, no text
-    if (StageState *s = b->stages) { outdated(s, From::bam); s->sm.done = true; s->sm.bytes = 0; s->sm.nregs = 0; s->ch.nseq = 0; s->sm.merged_n = -1; }
+    outdated(b, Product::reads, false);                   // the chunk of no reads takes the resident chunk's place
     b->nseq = 0;
+    if (StageState *s = b->stages) {
+        s->sm.bytes = 0; s->sm.nregs = 0; s->ch.nseq = 0; s->sm.merged_n = -1;
+        produced(b, Product::sam);                        // its text, of no bytes, is there to fetch
+    }
     if (sam_bytes) *sam_bytes = 0;
 }
 
@@ -275,6 +279,7 @@ static int chunk_smart_decoded(bwams_batch_t *b, bwams_fastq_t *fq, int64_t n, b
     if (n_single) *n_single = (int64_t)ids[0].size();
     StageState *s;
     if ((rc = get_state(b, &s))) return rc;
+    outdated(b, Product::sam);                            // the last run's text makes way for the whole chunk's
     // every read's block back to its place in the chunk (ret->seqs[sep[k][i].id].sam = sep[k][i].sam)
     std::vector<int64_t> off((size_t)n + 1, 0);
     std::vector<int64_t> rank((size_t)n, 0);
@@ -297,9 +302,9 @@ static int chunk_smart_decoded(bwams_batch_t *b, bwams_fastq_t *fq, int64_t n, b
     if ((rc = segment_copy(mv, st))) return rc;
     BWAMS_HIP(hipMemcpyAsync(s->sm.off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    outdated(s, From::bam);
-    s->sm.bytes = total; s->sm.nregs = 0; s->sm.merged_n = n; s->sm.done = true;
+    s->sm.bytes = total; s->sm.nregs = 0; s->sm.merged_n = n;
     if (sam_bytes) *sam_bytes = total;
+    produced(b, Product::sam);
     return BWAMS_OK;
 }
 

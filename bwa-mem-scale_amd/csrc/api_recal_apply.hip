@@ -198,13 +198,13 @@ int bwams_recal_apply_batch(bwams_recal_apply_t *a, bwams_batch_t *b, int64_t *n
     if (int rc = apply_check(a, R, "bwams_recal_apply_batch")) return rc;
     int64_t n = 0;
     float ms = 0;
-    if (s->bs.done) {                                        // the sorted copy holds the same records: the check above covers it
+    outdated(b, Product::templates);                         // the templates' scores are sums of the old qualities
+    if (has(b, Product::sorted)) {                           // the sorted copy holds the same records: the check above covers it
         if (int rc = apply_rewrite(a, DevRecords{s->bs.out.p, s->bs.off.p, s->bs.nrec}, &n)) return rc;
         ms = a->ms_apply;
     }
     if (int rc = apply_rewrite(a, R, &n)) return rc;
     a->ms_apply += ms;
-    s->md.done = s->md.loc_done = false;                     // the templates' scores are sums of the old qualities
     if (n_rewritten) *n_rewritten = n;
     return BWAMS_OK;
 }

@@ -18,7 +18,7 @@ extern "C" {
 /* ---------------------------------------------- the tail of mem_kernel2_core ---- */
 
 int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !b->stages || !b->stages->ext.done) {
+    if (!has(b, Product::ext)) {
         set_last_error("bwams_dedup_run: run bwams_extend_run first");
         return BWAMS_ERR_ARG;
     }
@@ -27,7 +27,7 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
     StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    outdated(s, From::dedup);
+    outdated(b, Product::dedup);
     const int64_t N = s->ch.n_seeds, n1 = s->ch.nseq + 1;
     const int64_t L = b->max_read_len > 1 ? b->max_read_len : 1;
     // strips for the global alignment: as many lanes as 1 GiB of (h, e) rows allows, at most 64 Ki
@@ -94,13 +94,13 @@ int bwams_dedup_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int64_t *n_reg
                 d[15], d[16] / 1e6, d[17], d[18], d[19] / 1e6);
     }
     s->dd.n_final = total;
-    s->dd.done = true;
     if (n_regs) *n_regs = total;
+    produced(b, Product::dedup);
     return BWAMS_OK;
 }
 
 int bwams_dedup_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off) {
-    if (!b || !b->stages || !b->stages->dd.done) {
+    if (!has(b, Product::dedup)) {
         set_last_error("bwams_dedup_fetch: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
@@ -117,7 +117,7 @@ int bwams_dedup_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, i
 /* Test hook: what the last bwams_dedup_run counted (include/bwams.h). */
 int bwams_debug_dedup_counts(bwams_batch_t *b, int64_t counts[14]) {
     static_assert(kDedupCounts == 14, "include/bwams.h documents 14 counters");
-    if (!b || !counts || !b->stages || !b->stages->dd.done || !b->stages->dd.counted) {
+    if (!counts || !has(b, Product::dedup) || !b->stages->dd.counted) {
         set_last_error("bwams_debug_dedup_counts: no bwams_dedup_run with BWAMS_DEDUP_COUNT=1 on this batch");
         return BWAMS_ERR_ARG;
     }
@@ -129,7 +129,7 @@ int bwams_debug_dedup_counts(bwams_batch_t *b, int64_t counts[14]) {
  * kernel read outside the reads or the text, and the values on which mem_patch_reg itself divides by zero or converts NaN to int. */
 int bwams_debug_ext_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
     if (!b || n_regs < 0 || n_reads < 0 || !reg_off || (n_regs && !regs)) return BWAMS_ERR_ARG;
-    if (!b->d_cum.p || n_reads != b->nseq) {
+    if (!has(b, Product::reads) || n_reads != b->nseq) {
         set_last_error("bwams_debug_ext_regs_upload: n_reads is not the number of reads of the last bwams_seed_upload");
         return BWAMS_ERR_ARG;
     }
@@ -169,7 +169,8 @@ int bwams_debug_ext_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, in
     StageState *s;
     if ((rc = get_state(b, &s))) return rc;
     // the chains and seeds of an earlier run no longer belong to these regions: nothing may extend them again
-    outdated(s, From::chain); outdated(s, From::al); outdated(s, From::er); outdated(s, From::sam);
+    outdated(b, Product::chains);
+    outdated(b, Product::er);          // beside the graph, as before: regions given by hand are not to meet mem_perfect2reg's of an earlier run
     const int64_t n1 = n_reads + 1;
     BWAMS_HIP(s->ext.regs.ensure_n((size_t)n_regs + 1)); BWAMS_HIP(s->ch.chain_off.ensure((size_t)n1 * 16));
     BWAMS_HIP(s->ch.seeds.ensure_n((size_t)n_regs + 1));     // bwams_extend_fetch reads a word per region from here: zeros
@@ -180,7 +181,7 @@ int bwams_debug_ext_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, in
     BWAMS_HIP(hipStreamSynchronize(st));
     s->ch.n_chains = 0; s->ch.n_seeds = n_regs; s->ch.nseq = n_reads;
     s->ext.n_left = s->ext.n_right = 0; s->ext.tasks_inplace = true;      // no task lists belong to these regions: bwams_extend_tasks_fetch refuses
-    s->ext.done = true;
+    produced(b, Product::ext);
     return BWAMS_OK;
 }
 
@@ -212,7 +213,7 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     const int no_rescue = (flags & BWAMS_PAIR_NO_RESCUE) || single_end, use_ert = (flags & BWAMS_PAIR_USE_ERT) != 0;
     static const bwams_pestat_t no_pes[4] = {{0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}};
     if (single_end && !pes) pes = no_pes;
-    if (!b || !b->stages || !b->stages->dd.done) {
+    if (!has(b, Product::dedup)) {
         set_last_error("bwams_pair_run: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
@@ -232,7 +233,7 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     }
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    outdated(s, From::pair);
+    outdated(b, Product::pair);
     const int64_t nseq = s->ch.nseq, n1 = nseq + 1;
     BWAMS_HIP(s->pr.na.ensure_n((size_t)n1)); BWAMS_HIP(s->pr.wide.ensure_n((size_t)n1)); BWAMS_HIP(s->pr.offs.ensure((size_t)n1 * 16));
     BWAMS_HIP(s->pr.nfin.ensure_n((size_t)n1)); BWAMS_HIP(s->pr.npri.ensure_n((size_t)n1)); BWAMS_HIP(s->pr.nsw.ensure_n((size_t)n1));
@@ -362,14 +363,14 @@ static int pair_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwa
     s->pr.counted = count_pr;
     s->pr.total = total;
     s->pr.single = single_end != 0;
-    s->pr.done = true;
     if (n_regs) *n_regs = total;
     if (n_tasks) *n_tasks = s->pr.tasks;
+    produced(b, Product::pair);
     return BWAMS_OK;
 }
 
 int bwams_pair_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off, bwams_pair_t *pairs) {
-    if (!b || !b->stages || !b->stages->pr.done) {
+    if (!has(b, Product::pair)) {
         set_last_error("bwams_pair_fetch: run bwams_pair_run first");
         return BWAMS_ERR_ARG;
     }
@@ -387,7 +388,7 @@ int bwams_pair_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, in
 /* Test hook: what the last bwams_pair_run counted (include/bwams.h). */
 int bwams_debug_pair_counts(bwams_batch_t *b, int64_t counts[15]) {
     static_assert(kPairCounts == 15, "include/bwams.h documents 15 counters");
-    if (!b || !counts || !b->stages || !b->stages->pr.done || !b->stages->pr.counted) {
+    if (!counts || !has(b, Product::pair) || !b->stages->pr.counted) {
         set_last_error("bwams_debug_pair_counts: no bwams_pair_run with BWAMS_PAIR_COUNT=1 on this batch");
         return BWAMS_ERR_ARG;
     }
@@ -398,7 +399,7 @@ int bwams_debug_pair_counts(bwams_batch_t *b, int64_t counts[15]) {
 /* ------------------------------------------------------------ mem_perfect2reg ---- */
 
 int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *opt, int64_t *n_regs) {
-    if (!b || !e || !b->emf.d_emf_out.p || !b->emf.d_emf_code.p) {
+    if (!e || !has(b, Product::probe)) {
         set_last_error("bwams_emf_regs_run: run bwams_emf_run first");
         return BWAMS_ERR_ARG;
     }
@@ -407,7 +408,7 @@ int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *
     BWAMS_HIP(hipSetDevice(b->idx->device));
     StageState *s;
     if ((rc = get_state(b, &s))) return rc;
-    outdated(s, From::er);
+    outdated(b, Product::er);
     hipStream_t st = b->stream;
     const int64_t nseq = b->nseq, n1 = nseq + 1;
     BWAMS_HIP(s->er.wide.ensure_n((size_t)n1)); BWAMS_HIP(s->er.off.ensure_n((size_t)n1)); BWAMS_HIP(s->er.ooff.ensure_n((size_t)n1));
@@ -431,17 +432,19 @@ int bwams_emf_regs_run(bwams_batch_t *b, bwams_emf_t *e, const bwams_mem_opt_t *
     launch_emfregs_emit(A, s->er.off.p, s->er.n.p, s->er.ooff.p, s->er.out.p, st);
     BWAMS_HIP(hipGetLastError());
     s->er.total = total; s->er.nseq = nseq;
-    s->er.done = true;
     if (n_regs) *n_regs = total;
+    produced(b, Product::er);
     return BWAMS_OK;
 }
 
 int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
-    if (!b || !b->stages || !b->stages->er.done || !b->stages->dd.done || b->stages->er.nseq != b->stages->ch.nseq) {
+    if (!has(b, Product::er, Product::dedup)) {
         set_last_error("bwams_emf_regs_merge: run bwams_emf_regs_run and bwams_dedup_run of this chunk first");
         return BWAMS_ERR_ARG;
     }
     StageState *s = b->stages;
+    outdated(b, Product::dedup, false);                   // the final regions gain the merged ones where they lie
+    outdated(b, Product::er);                             // beside the graph: merged once, a second call would add them again
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
     const int64_t nseq = s->ch.nseq, n1 = nseq + 1;
@@ -457,14 +460,12 @@ int bwams_emf_regs_merge(bwams_batch_t *b, int64_t *n_regs) {
     std::swap(s->dd.out, s->er.mg_out);
     std::swap(s->dd.off, s->er.mg_off);
     s->dd.n_final = total;
-    outdated(s, From::er);                                // merged: a second call would add them again
-    outdated(s, From::pair); outdated(s, From::al); outdated(s, From::sam);
     if (n_regs) *n_regs = total;
     return BWAMS_OK;
 }
 
 int bwams_emf_regs_fetch(bwams_batch_t *b, bwams_alnreg_t *regs, int64_t reg_cap, int64_t *reg_off, uint8_t *first_is_rev) {
-    if (!b || !b->stages || !b->stages->er.done) {
+    if (!has(b, Product::er)) {
         set_last_error("bwams_emf_regs_fetch: run bwams_emf_regs_run first");
         return BWAMS_ERR_ARG;
     }
@@ -549,7 +550,7 @@ static void pestat_from_sorted(const unsigned long long *keys, size_t n, bwams_p
 }
 
 int bwams_pestat(bwams_batch_t *b, const bwams_mem_opt_t *opt, bwams_pestat_t pes[4]) {
-    if (!b || !b->stages || !b->stages->dd.done || !pes) {
+    if (!has(b, Product::dedup) || !pes) {
         set_last_error("bwams_pestat: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }
@@ -563,7 +564,7 @@ int bwams_pestat(bwams_batch_t *b, const bwams_mem_opt_t *opt, bwams_pestat_t pe
 }
 
 int bwams_pestat_keys(bwams_batch_t *b, const bwams_mem_opt_t *opt, uint64_t *keys_out, int64_t cap, int64_t *n_keys) {
-    if (!b || !b->stages || !b->stages->dd.done || !n_keys) {
+    if (!has(b, Product::dedup) || !n_keys) {
         set_last_error("bwams_pestat_keys: run bwams_dedup_run first");
         return BWAMS_ERR_ARG;
     }

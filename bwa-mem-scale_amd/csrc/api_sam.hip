@@ -41,7 +41,7 @@ static int approx_mapq_se(const bwams_mem_opt_t *opt, const bwams_alnreg_t *a) {
 
 static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t source, const uint8_t *only, int64_t *n_aln,
                         int64_t *n_cigar_ops, int64_t *md_bytes) {
-    if (!b || !b->stages || (source == 0 && !b->stages->dd.done) || (source == 1 && !b->stages->pr.done) || source < 0 || source > 1) {
+    if (source < 0 || source > 1 || !has(b, source ? Product::pair : Product::dedup)) {
         set_last_error("bwams_reg2aln_run: run bwams_dedup_run (source 0) or bwams_pair_run (source 1) first");
         return BWAMS_ERR_ARG;
     }
@@ -54,7 +54,7 @@ static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t so
     StageState *s = b->stages;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    outdated(s, From::al);
+    outdated(b, Product::al);
     const int64_t n = source ? s->pr.total : s->dd.n_final;
     RegAlnArgs A;
     memset(&A, 0, sizeof A);
@@ -99,11 +99,12 @@ static int reg2aln_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t so
         }
 #endif
     }
-    s->al.n = n; s->al.ncig = tot[0]; s->al.nmd = tot[1]; s->al.source = source; s->al.done = true;
+    s->al.n = n; s->al.ncig = tot[0]; s->al.nmd = tot[1]; s->al.source = source;
     s->opt = *opt;
     if (n_aln) *n_aln = n;
     if (n_cigar_ops) *n_cigar_ops = tot[0];
     if (md_bytes) *md_bytes = tot[1];
+    produced(b, Product::al);
     return BWAMS_OK;
 }
 
@@ -114,7 +115,7 @@ int bwams_reg2aln_run(bwams_batch_t *b, const bwams_mem_opt_t *opt, int32_t sour
 
 int bwams_reg2aln_run_sam(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_sam_opt_t *sopt, const bwams_pestat_t *pes,
                           int64_t *n_aln, int64_t *n_needed, int64_t *n_cigar_ops, int64_t *md_bytes) {
-    if (!b || !sopt || !b->stages || !b->stages->pr.done || b->stages->pr.single == (pes != nullptr)) {
+    if (!sopt || !has(b, Product::pair) || b->stages->pr.single == (pes != nullptr)) {
         set_last_error("bwams_reg2aln_run_sam: run bwams_pair_run first (BWAMS_PAIR_SINGLE_END and pes = NULL, or the paired-end form and its pes)");
         return BWAMS_ERR_ARG;
     }
@@ -145,7 +146,7 @@ int bwams_reg2aln_run_sam(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bw
 }
 
 int bwams_reg2aln_fetch(bwams_batch_t *b, bwams_aln_t *aln, int64_t aln_cap, uint32_t *cigar, int64_t cigar_cap, char *md, int64_t md_cap) {
-    if (!b || !b->stages || !b->stages->al.done) {
+    if (!has(b, Product::al)) {
         set_last_error("bwams_reg2aln_fetch: run bwams_reg2aln_run first");
         return BWAMS_ERR_ARG;
     }
@@ -173,7 +174,7 @@ int bwams_reg2aln_fetch(bwams_batch_t *b, bwams_aln_t *aln, int64_t aln_cap, uin
 static int regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads, bool for_pairing) {
     const std::string who = for_pairing ? "bwams_debug_pair_regs_upload" : "bwams_debug_regs_upload";
     if (!b || n_regs < 0 || n_reads < 0 || !reg_off || (n_regs && !regs)) return BWAMS_ERR_ARG;
-    if (!b->d_cum.p || n_reads != b->nseq) {
+    if (!has(b, Product::reads) || n_reads != b->nseq) {
         set_last_error(who + ": n_reads is not the number of reads of the last bwams_seed_upload");
         return BWAMS_ERR_ARG;
     }
@@ -217,12 +218,14 @@ static int regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_r
     StageState *s;
     int rc = get_state(b, &s);
     if (rc) return rc;
-    outdated(s, From::dedup); outdated(s, From::al); outdated(s, From::er); outdated(s, From::sam);
+    outdated(b, Product::dedup);
+    outdated(b, Product::er);          // beside the graph, as before: regions given by hand are not to meet mem_perfect2reg's of an earlier run
     BWAMS_HIP(s->dd.out.ensure_n((size_t)n_regs + 1)); BWAMS_HIP(s->dd.off.ensure_n((size_t)n_reads + 1));
     if (n_regs) BWAMS_HIP(hipMemcpyAsync(s->dd.out.p, regs, (size_t)n_regs * sizeof(bwams_alnreg_t), hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipMemcpyAsync(s->dd.off.p, reg_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));
-    s->dd.n_final = n_regs; s->ch.nseq = n_reads; s->dd.done = true;
+    s->dd.n_final = n_regs; s->ch.nseq = n_reads;
+    produced(b, Product::dedup);
     return BWAMS_OK;
 }
 int bwams_debug_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, int64_t n_regs, const int64_t *reg_off, int64_t n_reads) {
@@ -234,7 +237,7 @@ int bwams_debug_pair_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, i
 
 /* Test hook: the lengths of the four region lists of the last bwams_reg2aln_run (include/bwams.h). */
 int bwams_debug_aln_lists(bwams_batch_t *b, int64_t counts[4]) {
-    if (!b || !counts || !b->stages || !b->stages->al.done) {
+    if (!counts || !has(b, Product::al)) {
         set_last_error("bwams_debug_aln_lists: run bwams_reg2aln_run first");
         return BWAMS_ERR_ARG;
     }
@@ -298,7 +301,7 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
         set_last_error("bwams_sam_upload: names and their offsets are required; comments come with offsets");
         return BWAMS_ERR_ARG;
     }
-    if (b->nseq <= 0 || !b->d_cum.p) {
+    if (!has(b, Product::reads) || b->nseq <= 0) {
         set_last_error("bwams_sam_upload: upload the reads first (bwams_seed_upload)");
         return BWAMS_ERR_ARG;
     }
@@ -312,7 +315,7 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
         set_last_error("bwams_sam_upload: offsets start at 0");
         return BWAMS_ERR_ARG;
     }
-    outdated(s, From::sam_upload);
+    outdated(b, Product::names);
     BWAMS_HIP(s->sm.names.ensure_n((size_t)name_off[nseq] + 16)); BWAMS_HIP(s->sm.noff.ensure_n((size_t)n1));
     BWAMS_HIP(hipMemcpyAsync(s->sm.names.p, names, (size_t)name_off[nseq], hipMemcpyDefault, st));
     BWAMS_HIP(hipMemcpyAsync(s->sm.noff.p, name_off, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
@@ -329,21 +332,21 @@ int bwams_sam_upload(bwams_batch_t *b, const char *names, const int64_t *name_of
     }
     BWAMS_HIP(hipStreamSynchronize(st));
     s->sm.nseq = nseq;
-    s->sm.up = true;
+    produced(b, Product::names);
     return BWAMS_OK;
 }
 
 static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_sam_opt_t *sopt, const bwams_pestat_t *pes,
                         int64_t *sam_bytes, bwams_emf_t *emf = nullptr) {
     const bool pe = pes != nullptr;
-    if (!b || !sopt || !b->stages || !b->stages->al.done || b->stages->al.source != 1 || b->stages->pr.single == pe) {
+    if (!sopt || !has(b, Product::al) || b->stages->al.source != 1 || b->stages->pr.single == pe) {
         set_last_error(pe ? "bwams_sam_run_pe: run bwams_pair_run (paired-end) and bwams_reg2aln_run(source 1) first"
                           : "bwams_sam_run: run bwams_pair_run(BWAMS_PAIR_SINGLE_END) and bwams_reg2aln_run(source 1) first");
         return BWAMS_ERR_ARG;
     }
     StageState *s = b->stages;
     if (pe && (s->ch.nseq & 1)) return BWAMS_ERR_ARG;
-    if (!s->sm.up || s->sm.nseq != s->ch.nseq) {
+    if (!has(b, Product::names)) {
         set_last_error("bwams_sam_run: run bwams_sam_upload for this chunk first");
         return BWAMS_ERR_ARG;
     }
@@ -366,7 +369,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     if (!memchr(sopt->rg_id, 0, sizeof sopt->rg_id)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     hipStream_t st = b->stream;
-    outdated(s, From::sam); s->sm.merged_n = -1;
+    outdated(b, Product::sam); s->sm.merged_n = -1;
     const int64_t nseq = s->ch.nseq, n1 = nseq + 1, n = s->al.n;
     constexpr int kLogN = 1 << 16;
     if (!s->sm.log_ok) {                                   // log(i) with the C library's log, as the reference's host code computes it
@@ -387,7 +390,7 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     A.ctg_annos = b->idx->d_ctg_annos.as<const char>(); A.ctg_anno_off = b->idx->d_ctg_anno_off.as<const int32_t>(); A.opt = *opt; A.sopt = *sopt;
     A.logtab = s->sm.logtab.p; A.logtab_n = kLogN; A.coef_fac = opt->mapq_coef_len > 0 ? log((double)opt->mapq_coef_len) : 0.;
     if (emf) {
-        if (!s->er.done || s->er.nseq != nseq) {
+        if (!has(b, Product::er)) {
             set_last_error("bwams_sam_run_emf: run bwams_emf_run and bwams_emf_regs_run for this chunk first");
             return BWAMS_ERR_ARG;
         }
@@ -426,8 +429,9 @@ static int sam_run_impl(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwam
     launch_sam_text(A, true, b->cu_count, st);
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
-    s->sm.bytes = total; s->sm.nregs = n; s->sm.done = true;
+    s->sm.bytes = total; s->sm.nregs = n;
     if (sam_bytes) *sam_bytes = total;
+    produced(b, Product::sam);
     return BWAMS_OK;
 }
 
@@ -447,7 +451,7 @@ int bwams_sam_run_pe(bwams_batch_t *b, const bwams_mem_opt_t *opt, const bwams_s
 }
 
 int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off, int32_t *mapq, int64_t mapq_cap) {
-    if (!b || !b->stages || !b->stages->sm.done) {
+    if (!has(b, Product::sam)) {
         set_last_error("bwams_sam_fetch: run bwams_sam_run first");
         return BWAMS_ERR_ARG;
     }
@@ -464,7 +468,7 @@ int bwams_sam_fetch(bwams_batch_t *b, char *sam, int64_t cap, int64_t *read_off,
 }
 
 int bwams_sam_fetch_bgzf(bwams_batch_t *b, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out) {
-    if (!b || !d || !b->stages || !b->stages->sm.done) {
+    if (!d || !has(b, Product::sam)) {
         set_last_error("bwams_sam_fetch_bgzf: run bwams_sam_run first");
         return BWAMS_ERR_ARG;
     }

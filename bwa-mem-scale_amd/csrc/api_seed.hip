@@ -125,12 +125,12 @@ int bwams_seed_upload(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, 
         }
         if (l > mx) mx = (int)l;
     }
+    outdated(b, Product::reads);
     BWAMS_HIP(hipSetDevice(b->idx->device));
     b->nseq = nseq;
     b->nbases = nb;
     b->max_read_len = mx;
     b->has_skip = skip != nullptr;
-    b->sd.done = false;
     // enc may already live in this GPU's memory (a caller that keeps several chunks resident): the copy kind is inferred
     if (nb) BWAMS_HIP(hipMemcpyAsync(b->d_enc.p, enc, (size_t)nb, hipMemcpyDefault, b->stream));
     BWAMS_HIP(hipMemcpyAsync(b->d_cum.p, cum, (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, b->stream));
@@ -169,6 +169,7 @@ int bwams_seed_upload(bwams_batch_t *b, const uint8_t *enc, const int64_t *cum, 
         b->sd.bwd_items_cap = bi;
         b->sd.bwd_ent_cap = be;
     }
+    produced(b, Product::reads);
     return BWAMS_OK;
 }
 
@@ -304,7 +305,7 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     b->sd.n_pool_slots = n_slots;
     if (n > b->max_smem || n_slots > b->pool_cap) {
         set_last_error("SMEM pool overflow: need " + std::to_string(n) + " slots");
-        b->sd.done = true;
+        produced(b, Product::seeds);                           // the counts of an overflowing pass are there to read (bwams_seed_counts)
         return BWAMS_ERR_CAPACITY;
     }
     if (n_slots > 0)
@@ -317,19 +318,24 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
     }
     BWAMS_HIP(hipEventRecord(b->ev[b->kEvSeedEnd], st));
     BWAMS_HIP(hipGetLastError());
-    b->sd.done = true;
+    produced(b, Product::seeds);
     return BWAMS_OK;
 }
 
 int bwams_seed_run(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with_sa) {
     if (!b || !opt) return BWAMS_ERR_ARG;
+    if (!has(b, Product::reads)) {
+        set_last_error("bwams_seed_run: upload the reads first (bwams_seed_upload)");
+        return BWAMS_ERR_ARG;
+    }
+    outdated(b, Product::seeds);
     b->sd.last_opt = *opt;
     b->sd.ert = nullptr;
     return run_growing(b, [&] { return seed_run_once(b, opt, with_sa); });
 }
 
 int bwams_seed_counts(bwams_batch_t *b, int64_t *n_smem, int64_t *n_sa) {
-    if (!b || !b->sd.done) return BWAMS_ERR_ARG;
+    if (!has(b, Product::seeds)) return BWAMS_ERR_ARG;
     BWAMS_HIP(hipSetDevice(b->idx->device));
     BWAMS_HIP(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, sizeof(DevCounters), hipMemcpyDeviceToHost, b->stream));
     BWAMS_HIP(hipStreamSynchronize(b->stream));
@@ -363,7 +369,7 @@ int bwams_seed_counts(bwams_batch_t *b, int64_t *n_smem, int64_t *n_sa) {
 
 int bwams_seed_fetch(bwams_batch_t *b, bwams_smem_t *smem_out, int64_t smem_cap, int64_t *sa_coord,
                      int64_t sa_cap, int64_t *sa_off) {
-    if (!b || !b->sd.done) return BWAMS_ERR_ARG;
+    if (!has(b, Product::seeds)) return BWAMS_ERR_ARG;
     int64_t ns = 0, na = 0;
     int rc = bwams_seed_counts(b, &ns, &na);
     if (rc) return rc;
@@ -438,7 +444,7 @@ static int ert_run_once(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t
     b->sd.n_smem = n;
     if (n > b->max_smem || n > b->pool_cap) {
         set_last_error("SMEM pool overflow: need " + std::to_string(n) + " slots");
-        b->sd.done = true;
+        produced(b, Product::seeds);                           // as in seed_run_once
         return BWAMS_ERR_CAPACITY;
     }
     if (n > 0)
@@ -455,12 +461,16 @@ static int ert_run_once(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t
     launch_ert_clear(b->sd.d_sorted.p, n, st);
     BWAMS_HIP(hipEventRecord(b->ev[b->kEvSeedEnd], st));
     BWAMS_HIP(hipGetLastError());
-    b->sd.done = true;
+    produced(b, Product::seeds);
     return BWAMS_OK;
 }
 
 int bwams_seed_run_ert(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t *opt, int with_sa) {
     if (!b || !e || !opt) return BWAMS_ERR_ARG;
+    if (!has(b, Product::reads)) {
+        set_last_error("bwams_seed_run_ert: upload the reads first (bwams_seed_upload)");
+        return BWAMS_ERR_ARG;
+    }
     if (e->idx != b->idx) {
         set_last_error("bwams_seed_run_ert: table and batch belong to different indexes");
         return BWAMS_ERR_ARG;
@@ -475,6 +485,7 @@ int bwams_seed_run_ert(bwams_batch_t *b, bwams_ert_t *e, const bwams_seed_opt_t 
         set_last_error("bwams_seed_run_ert: a read is longer than the read length the ERT was built for");
         return BWAMS_ERR_UNSUPPORTED;
     }
+    outdated(b, Product::seeds);
     b->sd.last_opt = *opt;
     b->sd.ert = e;
     return run_growing(b, [&] { return ert_run_once(b, e, opt, with_sa, M); });

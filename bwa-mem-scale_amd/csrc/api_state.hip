@@ -1,5 +1,5 @@
 // api_state.hip — the stage state of a batch (stage_state.h) and what the entry-point files share: the per-device auxiliary
-// stream set, state creation (get_state) and release (stage_state_free), the invalidation function (outdated), check_opt, dev_bns,
+// stream set, state creation (get_state) and release (stage_state_free), check_opt, dev_bns,
 // sw_params, scan_rows with the widen kernels behind launch_widen1 / launch_widen2, and stage_state_stats for bwams_batch_stats.
 #include <cstring>
 #include <map>
@@ -80,20 +80,6 @@ int scan_rows(bwams_batch *b, const int64_t *in, int64_t *out, int rows, int64_t
     return BWAMS_OK;
 }
 
-void outdated(StageState *s, From first) {
-    switch (first) {
-    case From::chain: s->ch.done = false; [[fallthrough]];
-    case From::built: s->ext.built = s->ext.done = false; [[fallthrough]];
-    case From::dedup: s->dd.done = false; [[fallthrough]];
-    case From::pair: s->pr.done = false; break;
-    case From::al: s->al.done = false; break;
-    case From::er: s->er.done = false; break;
-    case From::sam_upload: s->sm.up = false; [[fallthrough]];
-    case From::sam: s->sm.done = false; [[fallthrough]];
-    case From::bam: s->bm.done = s->bs.done = s->md.done = false; break;
-    }
-}
-
 int get_state(bwams_batch *b, StageState **out) {
     if (!b->stages) {
         b->stages = new StageState();
@@ -148,7 +134,8 @@ template <class Opt> static void sw_fill(const Opt &o, int end_bonus, SwParams *
 void sw_params(const bwams_mem_opt_t &o, int end_bonus, SwParams *prm) { sw_fill(o, end_bonus, prm); }
 void sw_params(const bwams_sw_opt_t &o, SwParams *prm) { sw_fill(o, o.end_bonus, prm); }
 
-void stage_state_stats(const StageState *s, bwams_stats_t *out) {
+void stage_state_stats(const bwams_batch *b, bwams_stats_t *out) {
+    const StageState *s = b->stages;
     if (!s) return;
     out->n_chains = s->ch.n_chains; out->n_chain_seeds = s->ch.n_seeds; out->n_chain_redo = s->ch.n_redo;
     out->n_left = s->ext.n_left; out->n_right = s->ext.n_right;
@@ -159,15 +146,15 @@ void stage_state_stats(const StageState *s, bwams_stats_t *out) {
     };
     el(0, 1, &out->ms_chain);
     el(2, 3, &out->ms_ext_plan);
-    if (s->ext.done) {
+    if (has(b, Product::ext)) {
         el(4, 5, &out->ms_ext_left);
         el(6, 7, &out->ms_ext_right);
         el(8, 9, &out->ms_ext_purge);
         el(10, 11, &out->ms_ext_total);
         out->n_ext_rounds = s->ext.n_rounds;
     }
-    if (s->dd.done) { el(12, 13, &out->ms_dedup); out->n_final_regs = s->dd.n_final; }
-    if (s->pr.done) {
+    if (has(b, Product::dedup)) { el(12, 13, &out->ms_dedup); out->n_final_regs = s->dd.n_final; }
+    if (has(b, Product::pair)) {
         el(14, 15, &out->ms_pair);
         out->n_pair_tasks = s->pr.tasks; out->n_pair_redone = s->pr.redone; out->n_pair_regs = s->pr.total;
     }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/bwams.h"
+#include "stage_valid.h"
 
 namespace bwams {
 
@@ -668,6 +669,8 @@ struct bwams_batch {
     bool has_skip = false;
     int64_t nseq = 0, nbases = 0;
     int max_read_len = 0;
+    // which products are current (stage_valid.h; produced / outdated / has below).  A new batch holds the chunk of no reads.
+    uint32_t valid = bwams::bit(bwams::Product::reads);
     DevBuf<bwams::DevCounters> d_ctr;
     bwams::HostBuf<bwams::DevCounters> h_ctr;   // pinned host mirror
     DevBuf<> d_tmp;                      // rocPRIM temporary storage
@@ -697,7 +700,7 @@ struct bwams_batch {
         hipEvent_t seed_fork = nullptr, seed_join = nullptr;
         int64_t n_smem = 0, n_sa = 0;
         int64_t n_pool_slots = 0;        // SMEM pool slots the last seeding pass handed out (holes included)
-        bool done = false, with_sa = false;
+        bool with_sa = false;
         bwams_ert *ert = nullptr;        // the last seed run went over this ERT (nullptr: FM-index)
         bwams_seed_opt_t last_opt{};     // of the last seed run (a grown SA buffer re-runs the lookup)
     } sd;
@@ -728,6 +731,12 @@ struct bwams_batch {
 };
 
 namespace bwams {
+// The validity mask of a batch.  An entry point that replaces product p calls outdated(b, p) once, before it touches device memory,
+// and produced(b, p) as its last act; one that reads p refuses the call unless has(b, p).  self = false: p is changed where it
+// lies and stays valid, what was computed from it does not.
+inline void produced(bwams_batch *b, Product p) { b->valid |= bit(p); }
+inline void outdated(bwams_batch *b, Product p, bool self = true) { b->valid &= ~(kDerived.of[(int)p] | (self ? bit(p) : 0u)); }
+template <class... P> bool has(const bwams_batch *b, P... p) { return b && (b->valid & bits(p...)) == bits(p...); }   // a null batch has nothing
 int check_device(int device);                  // api.hip: the ordinal names a gfx950 device
 int tmp_reserve(bwams_batch *b, size_t &tb);   // grows b->d_tmp to tb bytes (the stream drained first) and sets tb to its size (api.hip)
 int alloc_smem_buffers(bwams_batch *b, int64_t max_smem);   // api_seed.hip: (re)allocates every buffer sized by max_smem

@@ -51,7 +51,7 @@ inline int consumer_refusal(const char *who, const std::string &what) {
 // before anything else is looked at (null: none).  *state: the batch's stages.
 inline int consumer_batch(const RecConsumer *c, bwams_batch *b, const char *who, DevRecords *out, const char *refuse = nullptr,
                           StageState **state = nullptr) {
-    if (!c || !b || !b->stages || !b->stages->bm.done) return consumer_refusal(who, "run bwams_bam_run or bwams_bam_upload first");
+    if (!c || !has(b, Product::bam)) return consumer_refusal(who, "run bwams_bam_run or bwams_bam_upload first");
     if (refuse) return consumer_refusal(who, refuse);
     if (b->idx->device != c->device)
         return consumer_refusal(who, "the handle is on device " + std::to_string(c->device) + ", the batch on device " +

@@ -1,6 +1,6 @@
 // stage_state.h — a batch's state behind seeding (bwams_batch::stages), one member per stage, and the host helpers the
 // entry-point files share (defined in api_state.hip).  A DevBuf<T> is read as T everywhere; a DevBuf<> holds several
-// rows or types and names its layout.
+// rows or types and names its layout.  Whether a stage's result is current is not kept here: bwams_batch::valid (stage_valid.h).
 #pragma once
 
 #include "chain_kernels.h"
@@ -20,7 +20,7 @@ struct StageState {
         DevBuf<bwams_ert_mem_t> et_mems; DevBuf<int64_t> et_moff, et_hoff, et_cnt, et_off, et_coord; DevBuf<uint64_t> et_hits;   // ERT mode input translation
         DevBuf<bwams_smem_t> et_smem;
         DevBuf<> et_srt;                     // 24-byte sort records (ert_chain.hip)
-        int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_redo = 0; bool done = false;
+        int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_redo = 0;
         int64_t counts[kChainCounts] = {};   // bwams_debug_chain_counts: of the last bwams_chain_run / _run_ert
         bool ran = false;                    // ... there was one (bwams_chain_upload clears it)
     } ch;
@@ -34,7 +34,7 @@ struct StageState {
         DevBuf<> lsrc, rsrc;                 // in place (bwams_extend_run): int64 {query, target} start offsets per task instead of copied bytes
         DevBuf<int32_t> req_list, rtask;     // bwams_extend_run: the slots requested for the next build (appended by whoever requests); per slot its right task
         int64_t n_left = 0, n_right = 0, lref_b = 0, lqer_b = 0, rref_b = 0, rqer_b = 0, n_retry_left = 0, n_retry_right = 0, n_rounds = 0;
-        bool tasks_inplace = false, built = false, done = false;
+        bool tasks_inplace = false;
     } ext;
     struct DedupStage {                      // mem_sort_dedup_patch, mem_pestat's keys
         DevBuf<bwams_alnreg_t> regs, out; DevBuf<int32_t> ord, nout, light;
@@ -44,7 +44,7 @@ struct StageState {
         DevBuf<int64_t> off; DevBuf<unsigned long long> pe_keys, pe_keys2;
         DevBuf<unsigned long long> cnt;      // kDedupCounts words, written only when a run counts (BWAMS_DEDUP_COUNT=1)
         int64_t counts[kDedupCounts] = {};   // ... of the last run
-        int64_t n_final = 0; bool done = false, counted = false;
+        int64_t n_final = 0; bool counted = false;
     } dd;
     struct PairStage {                       // mate rescue + mem_mark_primary_se + mem_pair
         DevBuf<int32_t> na, anchor, slot, task, tl1, ord, z, nfin, npri, nsw; DevBuf<int64_t> wide, trb, owide, ooff;
@@ -57,13 +57,13 @@ struct StageState {
         DevBuf<bwams_pair_t> res;
         DevBuf<unsigned long long> cnt;      // kPairCounts words, written only when a run counts (BWAMS_PAIR_COUNT=1)
         int64_t counts[kPairCounts] = {};    // ... of the last run
-        int64_t total = 0, tasks = 0, redone = 0; bool done = false, single = false, counted = false;
+        int64_t total = 0, tasks = 0, redone = 0; bool single = false, counted = false;
     } pr;
     struct EmfRegStage {                     // mem_perfect2reg (+ mg_*: its merge into the final regions)
         DevBuf<int64_t> wide, off, ooff, mg_wide, mg_off;
         DevBuf<> scr;                        // emfregs_scratch_bytes()
         DevBuf<int32_t> n; DevBuf<uint8_t> rev; DevBuf<bwams_alnreg_t> out, mg_out;
-        int64_t total = 0, nseq = 0; bool done = false;
+        int64_t total = 0, nseq = 0;
     } er;
     struct AlnStage {                        // mem_reg2aln
         DevBuf<int64_t> need, off; DevBuf<int32_t> cls; DevBuf<uint8_t> scr, only;
@@ -71,25 +71,24 @@ struct StageState {
         DevBuf<bwams_aln_t> rec;
         DevBuf<> wide, offs;                 // 2 int64 rows of n + 1: CIGAR operations | MD bytes
         DevBuf<uint32_t> cig; DevBuf<char> md; DevBuf<unsigned long long> cnt;
-        int64_t n = 0, ncig = 0, nmd = 0; int source = 0; bool done = false;
+        int64_t n = 0, ncig = 0, nmd = 0; int source = 0;
     } al;
     struct SamStage {                        // SAM text
         DevBuf<char> names, qual, comm, out; DevBuf<int64_t> noff, coff, len, off; DevBuf<int32_t> mapq; DevBuf<double> logtab;
         DevBuf<> bad;                        // 8 words: unsigned flags at 0 and 2, bwams_reg2aln_run_sam's int64 sum at 1
         int64_t bytes = 0, nseq = 0, nregs = 0;
         int64_t merged_n = -1;               // >= 0: out / off hold that many reads' text merged from two runs (bwams_process_chunk_smart)
-        bool up = false, has_qual = false, has_comm = false, done = false, log_ok = false;
+        bool has_qual = false, has_comm = false, log_ok = false;
     } sm;
     struct BamStage {                        // BAM records of the SAM text (bwams_bam_run) or uploaded (bwams_bam_upload)
         DevBuf<int64_t> size, roff, off; DevBuf<uint8_t> out; DevBuf<unsigned long long> bad;
         int64_t bytes = 0, nrec = 0, nseq = 0;
         uint32_t nref = 0;                   // refIDs lie in [-1, nref): the index's sequences, or what bwams_bam_upload found
-        bool done = false;
     } bm;
     struct BamSortStage {                    // the records sorted (bwams_bam_sort)
         DevBuf<uint8_t> out; DevBuf<bwams_bam_coord_t> coord, coord0; DevBuf<uint64_t> keys, keys2; DevBuf<uint32_t> idx, idx2;
         DevBuf<int64_t> size, off;
-        int64_t bytes = 0, nrec = 0; bool done = false;
+        int64_t bytes = 0, nrec = 0;
     } bs;
     struct MarkdupStage {
         MdTemplates t;                       // templates and ends of the current records (bwams_bam_templates)
@@ -97,8 +96,7 @@ struct StageState {
         DevBuf<uint8_t> dup; DevBuf<unsigned long long> cnt; DevBuf<uint32_t> sorted;
         DevBuf<uint8_t> optical, g_ids; DevBuf<unsigned long long> lib_counts;      // rule 12's marks, the groups table, rule 13's counts
         DevBuf<int64_t> g_off; DevBuf<int32_t> g_ord, g_lib;
-        int32_t n_lib = 1;                   // of the last bwams_bam_templates2
-        bool done = false, loc_done = false; // loc_done: t.tloc / t.locs hold the current templates' (bwams_bam_templates2)
+        int32_t n_lib = 1;                   // of the last bwams_bam_templates2 (Product::template_locs: t.tloc / t.locs hold the current templates')
     } md;
     DevBuf<int32_t> heavy;        // per read: the wave tier's read list of whichever stage runs (chaining, selection, de-duplication, pairing)
     bwams_mem_opt_t opt{};
@@ -109,13 +107,6 @@ struct StageState {
     hipEvent_t fork = nullptr, join[7] = {};
 };
 
-// What a stage's (re)run or upload outdates: the stage named and everything derived from it.  Two chains,
-//   chain -> built, ext -> dedup -> pair      and      sam_upload -> sam -> bam, its sort, its templates,
-// and two products nothing derives from in this sense (al, er).  Known gap: a new chain, extension, de-duplication or pairing run
-// does not outdate al or sam and what derives from them, so bwams_sam_fetch after a new bwams_chain_run returns the old text.
-enum class From { chain, built, dedup, pair, al, er, sam_upload, sam, bam };
-void outdated(StageState *s, From first);
-
 int get_state(bwams_batch *b, StageState **out);                  // creates b->stages at the first call
 int check_opt(const bwams_mem_opt_t *o, const char *who);
 int dev_bns(bwams_index *ix, DevBns *out);                         // materialises the one-sequence default
@@ -124,6 +115,6 @@ void sw_params(const bwams_sw_opt_t &o, SwParams *prm);
 void launch_widen1(const int32_t *a, int64_t n, int64_t *wide, hipStream_t st);                     // row a of n + 1 as int64, the last 0
 void launch_widen2(const int32_t *a, const int32_t *b, int64_t n, int64_t *wide, hipStream_t st);   // rows a | b of n + 1 as int64, the last of each 0
 int scan_rows(bwams_batch *b, const int64_t *in, int64_t *out, int rows, int64_t n1);               // exclusive scan of each row of n1
-void stage_state_stats(const StageState *s, bwams_stats_t *out);   // timing and counts for bwams_batch_stats (api.hip)
+void stage_state_stats(const bwams_batch *b, bwams_stats_t *out);  // timing and counts for bwams_batch_stats (api.hip)
 
 }  // namespace bwams

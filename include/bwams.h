@@ -229,7 +229,18 @@ int64_t bwams_index_bytes(const bwams_index_t *idx);
  * default: 24 SMEMs and 64 coordinates per read on average).  They are not limits: a chunk that
  * needs more makes the stage run a second time on grown buffers (the kernels keep counting when
  * a buffer is full).  The host buffers of bwams_seed_fmi / bwams_seed_fetch are the caller's and
- * still yield BWAMS_ERR_CAPACITY when too small. */
+ * still yield BWAMS_ERR_CAPACITY when too small.
+ *
+ * Order of calls on a batch.  A batch holds one chunk, and each stage's result is computed from earlier ones: the reads
+ * (bwams_seed_upload) -> seeds (bwams_seed_run / _run_ert) -> chains -> extension -> de-duplication -> pairing -> alignment records
+ * (bwams_reg2aln_run*) -> SAM text -> BAM records -> their sort and their templates; beside that line the names (bwams_sam_upload,
+ * after the reads, read by the text only) and the exact-match probe (bwams_emf_run, after the reads) with its regions
+ * (bwams_emf_regs_run, read by bwams_emf_regs_merge and bwams_sam_run_emf).  Running or uploading a stage again replaces its result
+ * and invalidates everything computed from it: a call that needs an invalidated result returns BWAMS_ERR_ARG with the text it has for
+ * a stage that never ran ("run ... first") until the stages between have run again, in order.  New reads (bwams_seed_upload, and
+ * bwams_emf_probe, which uploads reads of its own and so needs a bwams_seed_upload behind it) invalidate everything else the batch
+ * holds, BAM records of bwams_bam_upload included.  Results that do not derive from one another stay: a seed run keeps the probe,
+ * its regions and the names; new names keep the alignment records; bwams_bam_sort keeps the text.  A refused call changes nothing. */
 int bwams_batch_create(bwams_index_t *idx, int64_t max_reads, int64_t max_bases,
                        int64_t max_smem, int64_t max_sa, bwams_batch_t **out);
 int bwams_batch_destroy(bwams_batch_t *b);
