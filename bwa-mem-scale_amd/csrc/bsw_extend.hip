@@ -595,12 +595,20 @@ __device__ __forceinline__ uint32_t add(uint32_t a, uint32_t b) { uint32_t d; as
 __device__ __forceinline__ uint32_t sub(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_sub_i16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t max(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_max_i16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t max0(uint32_t a) { uint32_t d; asm("v_pk_max_i16 %0, %1, 0" : "=v"(d) : "v"(a)); return d; }
-__device__ __forceinline__ uint32_t minu(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_min_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+// The second operand WAVE-UNIFORM, read from a scalar register (a packed instruction takes one): a constant of the launch then costs
+// no vector register and no copy into one.  Only for values that are uniform by construction (kernel arguments and what is made of them)
+__device__ __forceinline__ uint32_t adds(uint32_t a, uint32_t s) { uint32_t d; asm("v_pk_add_u16 %0, %1, %2" : "=v"(d) : "v"(a), "s"(s)); return d; }
+__device__ __forceinline__ uint32_t subs(uint32_t a, uint32_t s) { uint32_t d; asm("v_pk_sub_i16 %0, %1, %2" : "=v"(d) : "v"(a), "s"(s)); return d; }
+// small constants in both halves: the inline constant's low half taken for both (op_sel_hi)
+__device__ __forceinline__ uint32_t add2(uint32_t a) { uint32_t d; asm("v_pk_add_u16 %0, %1, 2 op_sel_hi:[1,0]" : "=v"(d) : "v"(a)); return d; }
+__device__ __forceinline__ uint32_t min1(uint32_t a) { uint32_t d; asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(d) : "v"(a)); return d; }
 __device__ __forceinline__ uint32_t hi2(uint32_t a) { return __builtin_amdgcn_perm(a, a, 0x03020302u); }      // the high half in both halves
 __device__ __forceinline__ uint32_t lo2(uint32_t a) { return __builtin_amdgcn_perm(a, a, 0x01000100u); }      // the low half in both halves
-__device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }   // v_bfi_b32
-template <int CTRL> __device__ __forceinline__ int qdpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
+// (a & mask) | (b & ~mask) as the one instruction it is (written in C it compiles to three or four)
+__device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { uint32_t d; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(mask), "v"(a), "v"(b)); return d; }
+// quad_perm moves: every source lane exists, so bound_ctrl changes no value, and with it the move folds into the instruction that uses it
+template <int CTRL> __device__ __forceinline__ int qdpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
 __device__ __forceinline__ int quad_all_max(int v) {
     int t = qdpp<0xB1>(v);                       // quad_perm [1,0,3,2]
     v = v > t ? v : t;
@@ -650,7 +658,6 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                                  (uint32_t)(uint16_t)(int16_t)prm.mat[t * 5 + 2] | ((uint32_t)(uint16_t)(int16_t)prm.mat[t * 5 + 3] << 16));
     }
     __syncthreads();
-    const uint32_t ONE = 0x00010001u, TWO = 0x00020002u, C257 = 0x01010101u;
     const uint32_t OEI = (uint32_t)oe_ins * 0x10001u, OED = (uint32_t)oe_del * 0x10001u, EDX = (uint32_t)e_del * 0x10001u;
     const uint32_t E1X = (uint32_t)e_ins * 0x10001u, E2X = (uint32_t)(2 * e_ins) * 0x10001u;
     const uint32_t NEGP = (uint32_t)(uint16_t)(int16_t)kPkNeg * 0x10001u;
@@ -671,7 +678,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
     // the row in progress (a row may take several iterations: one per window of 32 columns)
     bool start_row = true, row = false;
     int base = 0, h1 = 0, key = -1, hlast = -1, c_max = kPkNeg, c_h = 0;
-    uint32_t nzl = 0u, nzf = 0u;
+    int nz_last = 0, nz_first = 256;           // of the row so far: its last column with a non-zero stored cell, plus one (0: none); its first (256: none)
     uint2 tt = make_uint2(0u, 0u);
 #ifdef BWAMS_BSWDBG                 // wave-time of the refill branch and of the pass (printed by run_side under BWAMS_VERBOSE)
     const unsigned long long T0 = __builtin_amdgcn_s_memtime();
@@ -796,6 +803,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
         // ---- one PASS (a window of 32 columns) of the current row of every live task.  The tasks of a wavefront do not wait for
         // each other at the end of a row: a task whose row needs a second window takes it in the next iteration while the others
         // are already on their next rows, so an iteration costs the same whether one task or all sixteen have a wide band.
+        asm volatile("; BSW_PK_PASS_BEGIN");                          // tools/isa_count.py counts between the two markers
         if (alive && start_row) {                                     // row prologue
             int tb = tb_next;
             tb = tb > 4 ? 4 : tb;
@@ -810,7 +818,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                 h1 = h1 < 0 ? 0 : h1;
             }
             row = beg < end;
-            key = -1; hlast = -1; nzl = 0u; nzf = 0u;
+            key = -1; hlast = -1; nz_last = 0; nz_first = 256;
             c_max = kPkNeg; c_h = 0;
             base = beg & ~3;
             start_row = false;
@@ -824,6 +832,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
             lo = lo < 0 ? 0 : (lo > 8 ? 8 : lo);
             hi = hi < 0 ? 0 : (hi > 8 ? 8 : hi);
             const uint32_t m8 = inr ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+            const uint32_t m8x = m8 | (m8 << 15);                     // bit k also at bit k + 15: an odd column's bit 16 above the even one's before it
             // the window starts at a multiple of FOUR columns (a band of the typical 23 columns then fits one window almost always;
             // at a multiple of eight a fifth of the rows needed a second one): the lane's eight columns are 8-byte aligned in the H and E
             // arrays, 4-byte aligned in the selector bytes.  Lanes without a live column read too (whatever lies there: it is masked)
@@ -841,25 +850,25 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
             JE[0] = (uint32_t)(jb * e_ins) * 0x10001u + ((uint32_t)e_ins << 16);
             JP[0] = (uint32_t)jb * 0x10001u + 0x00020001u;            // (j + 1, j + 2)
 #pragma unroll
-            for (int c = 1; c < 4; ++c) { JE[c] = pk::add(JE[c - 1], E2X); JP[c] = pk::add(JP[c - 1], TWO); }
+            for (int c = 1; c < 4; ++c) { JE[c] = pk::adds(JE[c - 1], E2X); JP[c] = pk::add2(JP[c - 1]); }
             // Stage by stage over the four pairs, not pair by pair: dependent packed (VOP3P) instructions need a wait state between them
             // (the compiler fills it with s_nop 0: 34 per window in the pair-by-pair order), and the four pairs are independent.
             uint32_t Hm[4], T1[4], T2[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const uint32_t blo = (uint32_t)__builtin_amdgcn_sbfe((int)m8, 2 * c, 1), bhi = (uint32_t)__builtin_amdgcn_sbfe((int)m8, 2 * c + 1, 1);
-                AM[c] = pk::bfi(0xffffu, blo, bhi);
+            for (int c = 0; c < 4; ++c) {                            // bits 2c and 2c + 1 of m8 at bits 15 and 31, then v_perm's sign selectors 8 and 9
+                const uint32_t x = m8x << (15 - 2 * c);
+                AM[c] = __builtin_amdgcn_perm(x, x, 0x09090808u);
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) { Hm[c] = hpv[c] & AM[c]; E[c] = epv[c] & AM[c]; }
 #pragma unroll
             for (int c = 0; c < 4; ++c) T1[c] = pk::add(Hm[c], __builtin_amdgcn_perm(tt.y, tt.x, slv[c]));
 #pragma unroll
-            for (int c = 0; c < 4; ++c) T2[c] = pk::minu(Hm[c], ONE);
+            for (int c = 0; c < 4; ++c) T2[c] = pk::min1(Hm[c]);
 #pragma unroll
             for (int c = 0; c < 4; ++c) M[c] = pk::mul(T1[c], T2[c]);                                   // M = H ? H + S : 0
 #pragma unroll
-            for (int c = 0; c < 4; ++c) T1[c] = pk::sub(M[c], OEI);
+            for (int c = 0; c < 4; ++c) T1[c] = pk::subs(M[c], OEI);
 #pragma unroll
             for (int c = 0; c < 4; ++c) T1[c] = pk::max0(T1[c]);
 #pragma unroll
@@ -884,11 +893,11 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
 #pragma unroll
             for (int c = 0; c < 4; ++c) F4[c] = __builtin_amdgcn_alignbit(PX[c], c ? PX[c - 1] : NEGP, 16);      // {prefix up to column j - 1}
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { F4[c] = pk::max(F4[c], Lexp); E2[c] = pk::sub(M[c], OED); }
+            for (int c = 0; c < 4; ++c) { F4[c] = pk::max(F4[c], Lexp); E2[c] = pk::subs(M[c], OED); }
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { F4[c] = pk::sub(F4[c], JE[c]); T1[c] = pk::sub(E[c], EDX); ME[c] = pk::max(M[c], E[c]); }
+            for (int c = 0; c < 4; ++c) { F4[c] = pk::sub(F4[c], JE[c]); T1[c] = pk::subs(E[c], EDX); ME[c] = pk::max(M[c], E[c]); }
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { F4[c] = pk::add(F4[c], E1X); E2[c] = pk::max(E2[c], T1[c]); }
+            for (int c = 0; c < 4; ++c) { F4[c] = pk::adds(F4[c], E1X); E2[c] = pk::max(E2[c], T1[c]); }
 #pragma unroll
             for (int c = 0; c < 4; ++c) { F4[c] = pk::max0(F4[c]); E2[c] = pk::max0(E2[c]); }                    // F = max(Pex - (j - 1) e_ins, 0)
 #pragma unroll
@@ -920,17 +929,22 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                 lkey = lkey > kk ? lkey : kk;
             }
             {
-                uint32_t NF[4], NA[4], NB[4];
+                // a bit per column of the window that is live and stores a non-zero H or E: per pair {0 | 1, 0 | 1}, the lane's eight as bits
+                // 0-7 (even columns from the low halves, odd ones from the high halves), the quad's 32 as one word, the same in its four lanes
+                uint32_t NF[4];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) NF[c] = (HL[c] | E2[c]) & AM[c];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) { NF[c] = pk::minu(NF[c], ONE); NB[c] = pk::sub(C257, JP[c]); }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { NA[c] = pk::mul(NF[c], JP[c]); NB[c] = pk::mul(NF[c], NB[c]); }
-                NA[0] = pk::max(NA[0], NA[1]); NA[2] = pk::max(NA[2], NA[3]); NB[0] = pk::max(NB[0], NB[1]); NB[2] = pk::max(NB[2], NB[3]);
-                NA[0] = pk::max(NA[0], NA[2]); NB[0] = pk::max(NB[0], NB[2]);
-                nzl = pk::max(nzl, NA[0]);
-                nzf = pk::max(nzf, NB[0]);
+                for (int c = 0; c < 4; ++c) NF[c] = pk::min1(NF[c]);
+                const uint32_t nx = NF[0] | (NF[1] << 2) | (NF[2] << 4) | (NF[3] << 6);
+                const int nl = (int)(((nx | (nx >> 15)) & 0xffu) << (8 * g));
+                int nw = nl | pk::qdpp<0xB1>(nl);
+                nw |= pk::qdpp<0x4E>(nw);
+                // windows come in ascending order: the last one with a bit set has the row's last such column, the first one its first
+                const bool any = nw != 0;
+                const int fc = any ? base + __builtin_ctz((unsigned)nw) : 256;
+                nz_last = any ? base + 32 - __builtin_clz((unsigned)nw) : nz_last;
+                nz_first = nz_first < fc ? nz_first : fc;
             }
             lkey = m8 ? lkey : -1;                                  // a lane without a live column contributes nothing
             key = key > lkey ? key : lkey;
@@ -956,9 +970,8 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
             }
             // ---- the end of a row
             const int rkey = pk::quad_all_max(key), rhl = pk::quad_all_max(hlast);
-            const int a_ = (int)(nzl & 0xffffu), b_ = (int)(nzl >> 16), c_ = (int)(nzf & 0xffffu), d_ = (int)(nzf >> 16);
-            int last_nz = pk::quad_all_max(a_ > b_ ? a_ : b_) - 1;      // -1: none
-            int first_nz = 256 - pk::quad_all_max(c_ > d_ ? c_ : d_);   // 256: none (beyond every column)
+            int last_nz = nz_last - 1;                                  // -1: none
+            int first_nz = nz_first;                                    // 256: none (beyond every column)
             if (alive && !more) {
                 if (row && h1 != 0) {                                    // column beg stores h1 (see above)
                     first_nz = first_nz < beg ? first_nz : beg;
@@ -973,28 +986,28 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                     max_ie = gscore > h1f ? max_ie : i;
                     gscore = gscore > h1f ? gscore : h1f;
                 }
-                bool fin = m == 0;
-                if (!fin) {
-                    if (m > mx) {
-                        mx = m; max_i = i; max_j = mj;
-                        int d = mj - i;
-                        d = d < 0 ? -d : d;
-                        max_off = max_off > d ? max_off : d;
-                    } else if (prm.zdrop > 0) {
-                        if (i - max_i > mj - max_j) fin = mx - m - ((i - max_i) - (mj - max_j)) * e_del > prm.zdrop;
-                        else fin = mx - m - ((mj - max_j) - (i - max_i)) * e_ins > prm.zdrop;
-                    }
+                // selects, not branches: mx, max_i, max_j and max_off stay in their registers.  m > mx >= 0 implies m != 0
+                const bool better = m > mx;
+                const int di = i - max_i, dj = mj - max_j;
+                const int zpen = di > dj ? (di - dj) * e_del : (dj - di) * e_ins;
+                bool fin = m == 0 || (!better && prm.zdrop > 0 && mx - m - zpen > prm.zdrop);
+                {
+                    int d = mj - i;
+                    d = d < 0 ? -d : d;
+                    d = max_off > d ? max_off : d;
+                    max_off = better ? d : max_off;
+                    max_i = better ? i : max_i;
+                    max_j = better ? mj : max_j;
+                    mx = better ? m : mx;
                 }
-                if (!fin) {
+                {                                                        // the next row's band; of no account when the task ends here
                     const int nbeg = first_nz < end ? first_nz : end;
-                    int jj;
-                    if (h1f != 0) jj = end;
-                    else if (last_nz >= nbeg) jj = last_nz;
-                    else jj = nbeg - 1;
+                    int jj = last_nz >= nbeg ? last_nz : nbeg - 1;
+                    jj = h1f != 0 ? end : jj;
                     beg = nbeg;
                     end = jj + 2 < qlen ? jj + 2 : qlen;
                     ++i;
-                    fin = i >= tlen;
+                    fin = fin || i >= tlen;
                 }
                 if (fin) {
                     if (g == 0) {
@@ -1006,6 +1019,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                 start_row = true;
             }
         }
+        asm volatile("; BSW_PK_PASS_END");
 #ifdef BWAMS_BSWDBG
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         t_pass += __builtin_amdgcn_s_memtime() - Tb;
