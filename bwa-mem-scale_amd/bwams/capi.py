@@ -65,6 +65,8 @@ SYMBOLS = [
     "bwams_pileup_open", "bwams_pileup_close", "bwams_pileup_reset", "bwams_pileup_add_batch", "bwams_pileup_add_records", "bwams_pileup_set_ref",
     "bwams_pileup_set_ref_index", "bwams_pileup_fetch", "bwams_pileup_sites", "bwams_pileup_text", "bwams_pileup_info", "bwams_sorter_set_pileup",
     "bwams_pileup_set_quality", "bwams_pileup_fetch_quality", "bwams_pileup_calls", "bwams_pileup_vcf",
+    "bwams_pileup_set_indels", "bwams_pileup_fetch_span", "bwams_pileup_indel_alleles", "bwams_pileup_indel_calls", "bwams_pileup_indel_vcf",
+    "bwams_pileup_vcf_all", "bwams_pileup_indel_info",
     "bwams_qc_open", "bwams_qc_close", "bwams_qc_reset", "bwams_qc_add_batch", "bwams_qc_add_records", "bwams_qc_summary", "bwams_qc_table",
     "bwams_qc_text", "bwams_qc_info", "bwams_sorter_set_qc",
     "bwams_recal_open", "bwams_recal_close", "bwams_recal_reset", "bwams_recal_add_batch", "bwams_recal_add_records", "bwams_recal_set_ref",
@@ -115,6 +117,12 @@ PILEUP_SITE_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"),
 PILEUP_CALL_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("a1", "<i4"), ("a2", "<i4"), ("qual", "<i4"), ("gq", "<i4"),
                               ("depth", "<u4"), ("n", "<u4", (4,)), ("pl", "<i4", (10,))])               # bwams_pileup_call_t
 assert PILEUP_REGION_DTYPE.itemsize == 12 and PILEUP_SITE_DTYPE.itemsize == 68 and PILEUP_CALL_DTYPE.itemsize == 88
+PILEUP_INDEL_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("type", "<i4"), ("len", "<i4"), ("reserved", "<i4"),
+                               ("seq", "<u8"), ("gt", "<i4"), ("qual", "<i4"), ("gq", "<i4"), ("depth", "<u4"), ("n_ref", "<u4"), ("n_alt", "<u4"),
+                               ("n_other", "<u4"), ("pl", "<i4", (3,)), ("del_ref", "u1", (32,))])       # bwams_pileup_indel_t
+PILEUP_INDEL_ALLELE_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("type", "<i4"), ("len", "<i4"), ("seq", "<u8"), ("n", "<u8"),
+                                      ("q", "<u8"), ("hom", "<u8"), ("het", "<u8")])                      # bwams_pileup_indel_allele_t
+assert PILEUP_INDEL_DTYPE.itemsize == 104 and PILEUP_INDEL_ALLELE_DTYPE.itemsize == 56
 assert DUP_LOC_DTYPE.itemsize == 24 and DUP_LIB_STATS_DTYPE.itemsize == 72
 assert CONTIG_DTYPE.itemsize == 16 and CHAIN_SEED_DTYPE.itemsize == 32 and CHAIN_DTYPE.itemsize == 48
 assert ALNREG_DTYPE.itemsize == 112
@@ -655,6 +663,14 @@ class PileupInfo(C.Structure):
                 ("n_direct", C.c_int64), ("ms_check", C.c_float), ("ms_add", C.c_float)]
 
 
+class PileupIndelOpt(C.Structure):
+    _fields_ = [("min_qual", C.c_int32), ("min_depth", C.c_int32), ("indel_q", C.c_int32), ("max_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PileupIndelInfo(C.Structure):
+    _fields_ = [("n_events", C.c_int64), ("cap_events", C.c_int64), ("n_appended", C.c_int64), ("ms_indel", C.c_float), ("reserved", C.c_int32)]
+
+
 class Pileup(_Consumer):
     """Per-base allele counts over regions on one GPU (bwams_pileup_t): add, then fetch, sites or text at any time."""
     _prefix, _close = "bwams_pileup", "bwams_pileup_close"
@@ -737,6 +753,57 @@ class Pileup(_Consumer):
     def info(self) -> dict:
         """bwams_pileup_info: tile, n_regions, n_slots, and of the last add n_counted, n_entries, n_direct, ms_check, ms_add."""
         return self._info("bwams_pileup_info", PileupInfo)
+
+    def set_indels(self, min_qual: int = 20, min_depth: int = 1, indel_q: int = 40, max_len: int = 32) -> None:
+        """bwams_pileup_set_indels: the indel store (rules 14 to 17), empty; only while the counters are zero."""
+        o = PileupIndelOpt(min_qual, min_depth, indel_q, max_len, 0)
+        _chk(lib().bwams_pileup_set_indels(self.h, C.byref(o)), "bwams_pileup_set_indels")
+
+    def fetch_span(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:
+        """uint32[end - beg, 4]: SPAN_N, SPAN_Q, SPAN_HOM, SPAN_HET of positions [beg, end) of the region (default: all of it)."""
+        r, b, e = self.regions[region]
+        beg, end = b if beg is None else beg, e if end is None else end
+        out = np.zeros((max(end - beg, 1), 4), np.uint32)
+        _chk(lib().bwams_pileup_fetch_span(self.h, region, beg, end, _p(out)), "bwams_pileup_fetch_span")
+        return out[:max(end - beg, 0)]
+
+    def indel_alleles(self, cap: int | None = None) -> np.ndarray:
+        """PILEUP_INDEL_ALLELE_DTYPE records of rule 17, every group; cap: the array's size (default: asked for first)."""
+        n = C.c_int64(0)
+        if cap is None:
+            _chk(lib().bwams_pileup_indel_alleles(self.h, None, 0, C.byref(n)), "bwams_pileup_indel_alleles")
+            cap = n.value
+        out = np.zeros(max(cap, 1), PILEUP_INDEL_ALLELE_DTYPE)
+        rc = lib().bwams_pileup_indel_alleles(self.h, _p(out), cap, C.byref(n))
+        self.n_alleles = n.value
+        _chk(rc, "bwams_pileup_indel_alleles")
+        return out[:n.value]
+
+    def indel_calls(self, min_qual: int = -1, min_depth: int = -1, cap: int | None = None) -> np.ndarray:
+        """PILEUP_INDEL_DTYPE records of rule 16; cap: the array's size (default: asked for first).  .n_indel_calls: found or needed."""
+        n = C.c_int64(0)
+        if cap is None:
+            _chk(lib().bwams_pileup_indel_calls(self.h, min_qual, min_depth, None, 0, C.byref(n)), "bwams_pileup_indel_calls")
+            cap = n.value
+        out = np.zeros(max(cap, 1), PILEUP_INDEL_DTYPE)
+        rc = lib().bwams_pileup_indel_calls(self.h, min_qual, min_depth, _p(out), cap, C.byref(n))
+        self.n_indel_calls = n.value
+        _chk(rc, "bwams_pileup_indel_calls")
+        return out[:n.value]
+
+    def indel_vcf(self, names, sample, min_qual: int = -1, min_depth: int = -1) -> str:
+        flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
+        return _text(lib().bwams_pileup_indel_vcf, self.h, flat, sample if isinstance(sample, bytes) else sample.encode(), min_qual, min_depth)
+
+    def vcf_all(self, names, sample, min_qual: int = -1, min_depth: int = -1, indel_min_qual: int = -1, indel_min_depth: int = -1) -> str:
+        """bwams_pileup_vcf_all: the SNV rows and the indel rows under one header; needs the quality plane and the indel store."""
+        flat = b"".join((n if isinstance(n, bytes) else n.encode()) + b"\0" for n in names)
+        return _text(lib().bwams_pileup_vcf_all, self.h, flat, sample if isinstance(sample, bytes) else sample.encode(), min_qual, min_depth,
+                     indel_min_qual, indel_min_depth)
+
+    def indel_info(self) -> dict:
+        """bwams_pileup_indel_info: n_events, cap_events, and of the last add n_appended and ms_indel."""
+        return self._info("bwams_pileup_indel_info", PileupIndelInfo)
 
 
 class QcOpt(C.Structure):
@@ -1222,6 +1289,13 @@ def lib():
         L.bwams_pileup_fetch_quality.argtypes = [vp, i32, i32, i32, vp]
         L.bwams_pileup_calls.argtypes = [vp, i32, i32, vp, i64, vp]
         L.bwams_pileup_vcf.argtypes = [vp, vp, C.c_char_p, i32, i32, vp, i64, vp]
+        L.bwams_pileup_set_indels.argtypes = [vp, vp]
+        L.bwams_pileup_fetch_span.argtypes = [vp, i32, i32, i32, vp]
+        L.bwams_pileup_indel_alleles.argtypes = [vp, vp, i64, vp]
+        L.bwams_pileup_indel_calls.argtypes = [vp, i32, i32, vp, i64, vp]
+        L.bwams_pileup_indel_vcf.argtypes = [vp, vp, C.c_char_p, i32, i32, vp, i64, vp]
+        L.bwams_pileup_vcf_all.argtypes = [vp, vp, C.c_char_p, i32, i32, i32, i32, vp, i64, vp]
+        L.bwams_pileup_indel_info.argtypes = [vp, vp]
         L.bwams_qc_open.argtypes = [C.c_int, vp, vp]
         L.bwams_qc_close.argtypes = [vp]
         L.bwams_qc_reset.argtypes = [vp]

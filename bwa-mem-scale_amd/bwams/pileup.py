@@ -4,7 +4,19 @@ The rules are numbered in include/bwams.h above bwams_pileup_open; the numbers b
 accumulates records (BAM records with their block_size, back to back, as bwams/bam.py builds them) into 12 counters per region
 position; fetch, sites and text return what the C-ABI's return.  After set_quality the adds also keep rule 11's sums, 12 per position,
 and fetch_quality, calls and vcf restate rules 10 to 13 (csrc/pileup.hip's quality sinks and call kernel, host/pileup_vcf.cpp) in integer
-arithmetic alone.
+arithmetic alone.  After set_indels the adds also keep rule 14's events and rule 15's span sums, and fetch_span, indel_alleles,
+indel_calls, indel_vcf and vcf_all restate rules 14 to 17 (csrc/pileup_indel.hip, host/pileup_indel_vcf.cpp):
+ 14. Every I or D op of a counted record that a reference-consuming op precedes is an event at the anchor, the position before the op;
+     dropped when the anchor has no slot.  (type, len, seq): 0 DEL, 1 INS, 2 OTHER; seq packs an insertion's bases 2 bits each, base j
+     at bits 2j.  OTHER, with len 0 and seq 0: longer than max_len, an inserted base that is not A C G T, or a deletion whose last
+     position is not in the anchor's region.  qe = clamp(min(MAPQ, indel_q), 4, 60).
+ 15. A counted record spans slot s when s and s + 1 lie in one maximal run of M/=/X ops; SPAN_N, SPAN_Q, SPAN_HOM, SPAN_HET get 1, qe,
+     T_HOM[qe], T_HET[qe], modulo 2^32.
+ 16. At a slot with reference base < 4 the events group by (type, len, seq); ALT is the type-0 or type-1 group of largest n, the first
+     in that order on a tie; cost(RR) = SPAN_HOM + MIS_ALT, cost(RA) = SPAN_HET + HET_ALT, cost(AA) = SPAN_MIS + HOM_ALT with
+     MIS = 100 Q + 477 n; pl, genotype, qual and gq as rule 13; depth = SPAN_N + n_ALT + n_other; a call when the genotype is not RR,
+     qual >= min_qual and depth >= min_depth.  No realignment, no left-normalisation, no model of repeats, strands or mate overlap.
+ 17. INDEL_DTYPE and INDEL_ALLELE_DTYPE records; the VCF rows with INFO DP=depth;INDEL, and vcf_all's merge, the SNV first at a slot.
 """
 from __future__ import annotations
 
@@ -39,6 +51,16 @@ VCF_FIXED = ('##INFO=<ID=DP,Number=1,Type=Integer,Description="Bases counted">\n
              '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality">\n'
              '##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Genotype costs in phred, the least at 0">\n'
              "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t")
+EV_DEL, EV_INS, EV_OTHER = 0, 1, 2                                                      # rule 14's types
+SPAN_N, SPAN_Q, SPAN_HOM, SPAN_HET = 0, 1, 2, 3                                         # rule 15's sums
+INDEL_MAX = 32
+INDEL_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("type", "<i4"), ("len", "<i4"), ("reserved", "<i4"), ("seq", "<u8"),
+                        ("gt", "<i4"), ("qual", "<i4"), ("gq", "<i4"), ("depth", "<u4"), ("n_ref", "<u4"), ("n_alt", "<u4"), ("n_other", "<u4"),
+                        ("pl", "<i4", (3,)), ("del_ref", "u1", (INDEL_MAX,))])          # bwams_pileup_indel_t
+INDEL_ALLELE_DTYPE = np.dtype([("region", "<i4"), ("pos", "<i4"), ("type", "<i4"), ("len", "<i4"), ("seq", "<u8"), ("n", "<u8"), ("q", "<u8"),
+                               ("hom", "<u8"), ("het", "<u8")])                          # bwams_pileup_indel_allele_t
+assert INDEL_DTYPE.itemsize == 104 and INDEL_ALLELE_DTYPE.itemsize == 56
+VCF_INDEL_LINE = '##INFO=<ID=INDEL,Number=0,Type=Flag,Description="An insertion or deletion, as the CIGARs give it">\n'
 
 
 class PileupRefusal(ValueError):
@@ -79,12 +101,66 @@ class Pileup:
         self.exclude, self.min_mapq, self.min_baseq, self.min_alt, self.min_permille = exclude, min_mapq, min_baseq, min_alt, min_permille
         self.ref = np.full(self.n_slots, 4, np.uint8)                                    # rule 7
         self.q = None                                                                    # rule 11's plane: none before set_quality
+        self.span = None                                                                 # rule 15's sums: none before set_indels
         self.reset()
 
     def reset(self):                                                                     # rule 6
         self.c = np.zeros((self.n_slots, 12), np.int64)
         if self.q is not None:
             self.q = np.zeros((self.n_slots, 12), np.int64)
+        if self.span is not None:
+            self.span = np.zeros((self.n_slots, 4), np.int64)
+            self.events = []                                                             # (slot, type, len, seq, qe, from an I op)
+
+    def set_indels(self, min_qual: int = 20, min_depth: int = 1, indel_q: int = 40, max_len: int = INDEL_MAX):
+        """the indel store, empty; only while the counters are zero (BWAMS_ERR_ARG otherwise)"""
+        assert min_qual >= 0 and min_depth >= 1 and 0 <= indel_q <= 93 and 1 <= max_len <= INDEL_MAX and not self.c.any()
+        assert self.n_slots < 2 ** 32
+        self.indel_min_qual, self.indel_min_depth, self.indel_q, self.max_len = min_qual, min_depth, indel_q, max_len
+        self.span = np.zeros((self.n_slots, 4), np.int64)
+        self.events = []
+
+    def _indels_of(self, refid, pos, mapq, cigar, codes):
+        """rules 14 and 15 for one counted record"""
+        qe = min(max(min(mapq, self.indel_q), GL_MIN_Q), GL_MAX_Q)
+        add = np.array([1, qe, T_HOM[qe - GL_MIN_Q], T_HET[qe - GL_MIN_Q]], np.int64)
+        slot, l_ref = self.slot[refid], self.l_ref[refid]
+        x, q, seen, run = pos, 0, False, None
+        runs = []
+        for n, op in cigar:
+            if op in (1, 2) and seen and 0 <= x - 1 < l_ref and slot[x - 1] >= 0:
+                s = int(slot[x - 1])
+                k = int(np.searchsorted(self.off, s, "right")) - 1                        # the anchor's region
+                kind, seq = (EV_INS, 0) if op == 1 else (EV_DEL, 0)
+                if n > self.max_len:
+                    kind = EV_OTHER
+                elif op == 2:
+                    if x + n - 1 >= self.regions[k][2]:
+                        kind = EV_OTHER
+                else:
+                    for j, code in enumerate(codes[q:q + n]):
+                        if _CHANNEL_OF_CODE[code] > 3:
+                            kind = EV_OTHER
+                            break
+                        seq |= int(_CHANNEL_OF_CODE[code]) << (2 * j)
+                self.events.append((s, kind, 0, 0, qe, op == 1) if kind == EV_OTHER else (s, kind, n, seq, qe, op == 1))
+            if op in (0, 7, 8):
+                run = [x, x + n] if run is None else [run[0], x + n]
+            elif run is not None:
+                runs.append(run)
+                run = None
+            if op in _REF_OPS:
+                x += n
+                seen = True
+            if op in _QUERY_OPS:
+                q += n
+        if run is not None:
+            runs.append(run)
+        for a, b in runs:                                                                # s and s + 1 in the run: s in [a, b - 1)
+            lo, hi = max(a, 0), min(b - 1, l_ref)
+            if lo < hi:
+                s = slot[lo:hi]
+                self.span[s[s >= 0]] += add
 
     def set_quality(self, min_qual: int = 20, min_depth: int = 1, no_qual_q: int = 30):
         """the quality plane, zeroed; only while the counters are zero (BWAMS_ERR_ARG otherwise)"""
@@ -149,6 +225,8 @@ class Pileup:
                     seen_ref = True
                 if op in _QUERY_OPS:
                     q += n
+            if self.span is not None:
+                self._indels_of(refid, pos, mapq, cigar, codes)
         return n_counted
 
     def set_ref(self, region: int, codes):                                               # rule 7
@@ -244,3 +322,98 @@ class Pileup:
                 int(x["depth"]), gt[0], gt[1], ",".join(str(int(x["n"][a])) for a in alleles), int(x["depth"]), int(x["gq"]),
                 ",".join(map(str, pl))))
         return "".join(rows)
+
+    def fetch_span(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:           # rule 15
+        assert self.span is not None
+        r, b, e = self.regions[region]
+        beg, end = b if beg is None else beg, e if end is None else end
+        assert b <= beg <= end <= e
+        return self.span[self.off[region] + beg - b:self.off[region] + end - b].astype(np.uint32)
+
+    def _place(self, s: int):
+        k = int(np.searchsorted(self.off, s, "right")) - 1
+        return k, int(s - self.off[k]) + self.regions[k][1]
+
+    def _groups(self):
+        """{slot: [((type, len, seq), [n, Q, HOM, HET]), ...] in rule 16's order}, the slots ascending"""
+        assert self.span is not None
+        g = {}
+        for s, kind, n, seq, qe, _ in self.events:
+            v = g.setdefault((s, kind, n, seq), [0, 0, 0, 0])
+            v[0] += 1; v[1] += qe; v[2] += T_HOM[qe - GL_MIN_Q]; v[3] += T_HET[qe - GL_MIN_Q]
+        by_slot = {}
+        for key in sorted(g):
+            by_slot.setdefault(key[0], []).append((key[1:], g[key]))
+        return by_slot
+
+    def indel_alleles(self) -> np.ndarray:                                               # rule 17: every group, OTHER included
+        rows = [(*self._place(s), kind, n, seq, *v) for s, groups in self._groups().items() for (kind, n, seq), v in groups]
+        out = np.zeros(len(rows), INDEL_ALLELE_DTYPE)
+        for i, row in enumerate(rows):
+            out[i] = row
+        return out
+
+    def indel_genotypes(self):
+        """rule 16 at every slot that has an ALT: [(INDEL_DTYPE record, depth untruncated, tie)], tie: another type-0 or type-1 group
+        has the ALT's n"""
+        out = []
+        span = self.span & 0xFFFFFFFF
+        for s, groups in self._groups().items():
+            r = int(self.ref[s])
+            cand = [(key, v) for key, v in groups if key[0] != EV_OTHER]
+            if r > 3 or not cand:
+                continue
+            n_alt = max(v[0] for _, v in cand)
+            (kind, n, seq), alt = next((key, v) for key, v in cand if v[0] == n_alt)      # a tie: the first in the order
+            total = sum(v[0] for _, v in groups)
+            sp = [int(x) for x in span[s]]
+            cost = [sp[SPAN_HOM] + 100 * alt[1] + GL_MIS * alt[0], sp[SPAN_HET] + alt[3], 100 * sp[SPAN_Q] + GL_MIS * sp[SPAN_N] + alt[2]]
+            best = cost.index(min(cost))
+            pl = [min((x - cost[best] + 50) // 100, 2 ** 31 - 1) for x in cost]
+            k, pos = self._place(s)
+            rec = np.zeros(1, INDEL_DTYPE)[0]
+            depth = sp[SPAN_N] + total
+            del_ref = np.zeros(INDEL_MAX, np.uint8)
+            if kind == EV_DEL:
+                del_ref[:n] = self.ref[s + 1:s + 1 + n]
+            rec["region"], rec["pos"], rec["ref"], rec["type"], rec["len"], rec["seq"], rec["gt"] = k, pos, r, kind, n, seq, best
+            rec["qual"], rec["gq"], rec["depth"] = pl[0], min(99, min(x for g, x in enumerate(pl) if g != best)), depth & 0xFFFFFFFF
+            rec["n_ref"], rec["n_alt"], rec["n_other"] = sp[SPAN_N], n_alt & 0xFFFFFFFF, (total - n_alt) & 0xFFFFFFFF
+            rec["pl"], rec["del_ref"] = pl, del_ref
+            out.append((rec, depth, sum(v[0] == n_alt for _, v in cand) > 1))
+        return out
+
+    def indel_calls(self, min_qual: int | None = None, min_depth: int | None = None) -> np.ndarray:         # rule 16
+        min_qual = self.indel_min_qual if min_qual is None else min_qual
+        min_depth = self.indel_min_depth if min_depth is None else min_depth
+        rows = [rec for rec, depth, _ in self.indel_genotypes() if rec["gt"] != 0 and rec["qual"] >= min_qual and depth >= min_depth]
+        return np.array(rows, INDEL_DTYPE) if rows else np.zeros(0, INDEL_DTYPE)
+
+    def _vcf_head(self, names, sample: str, indel: bool):
+        fixed = VCF_FIXED.split("\n", 1)
+        return (["##fileformat=VCFv4.2\n##source=bwams\n"] + ["##contig=<ID=%s,length=%d>\n" % (n, l) for n, l in zip(names, self.l_ref)] +
+                [fixed[0] + "\n" + (VCF_INDEL_LINE if indel else "") + fixed[1] + sample + "\n"])
+
+    def _indel_row(self, names, x) -> str:                                               # rule 17
+        r, n = "ACGT"[int(x["ref"])], int(x["len"])
+        if int(x["type"]) == EV_DEL:
+            ref, alt = r + "".join("ACGTN"[c] for c in x["del_ref"][:n]), r
+        else:
+            ref, alt = r, r + "".join("ACGT"[int(x["seq"]) >> (2 * j) & 3] for j in range(n))
+        return "%s\t%d\t.\t%s\t%s\t%d\t.\tDP=%d;INDEL\tGT:AD:DP:GQ:PL\t%s:%d,%d:%d:%d:%d,%d,%d\n" % (
+            names[self.regions[int(x["region"])][0]], int(x["pos"]) + 1, ref, alt, int(x["qual"]), int(x["depth"]),
+            "0/1" if int(x["gt"]) == 1 else "1/1", int(x["n_ref"]), int(x["n_alt"]), int(x["depth"]), int(x["gq"]), *map(int, x["pl"]))
+
+    def indel_vcf(self, names, sample: str, min_qual: int | None = None, min_depth: int | None = None) -> str:
+        names = [n.decode() if isinstance(n, bytes) else n for n in names]
+        return "".join(self._vcf_head(names, sample, True) + [self._indel_row(names, x) for x in self.indel_calls(min_qual, min_depth)])
+
+    def vcf_all(self, names, sample: str, min_qual: int | None = None, min_depth: int | None = None, indel_min_qual: int | None = None,
+                indel_min_depth: int | None = None) -> str:
+        """the SNV rows of vcf and the indel rows of indel_vcf under the header with the INDEL line, by (region, pos), the SNV first"""
+        assert self.q is not None and self.span is not None
+        names = [n.decode() if isinstance(n, bytes) else n for n in names]
+        snv_rows = self.vcf(names, sample, min_qual, min_depth).splitlines(True)[len(names) + 2 + VCF_FIXED.count("\n") + 1:]
+        rows = [((int(x["region"]), int(x["pos"]), 0), row) for x, row in zip(self.calls(min_qual, min_depth), snv_rows)]
+        rows += [((int(x["region"]), int(x["pos"]), 1), self._indel_row(names, x)) for x in self.indel_calls(indel_min_qual, indel_min_depth)]
+        return "".join(self._vcf_head(names, sample, True) + [row for _, row in sorted(rows)])

@@ -1,6 +1,6 @@
 // api_pileup.hip — C-ABI entry points of the pileup (include/bwams.h, "Pileup"): the handle over a list of regions, the adds from a
-// batch and from host records, the reference bases, the quality plane, and the queries, over pileup.hip; the texts over
-// host/pileup_text.cpp and host/pileup_vcf.cpp.
+// batch and from host records, the reference bases, the quality plane, the indel store, and the queries, over pileup.hip and
+// pileup_indel.hip; the texts over host/pileup_text.cpp, host/pileup_vcf.cpp and host/pileup_indel_vcf.cpp.
 // No CPU fallback: every entry point runs HIP kernels or returns an error.
 #include <algorithm>
 #include <cstring>
@@ -37,6 +37,22 @@ struct bwams_pileup : RecConsumer {
     int64_t n_added = 0;                             // records given so far (rule 6)
     int64_t last[3] = {0, 0, 0};                     // of the last add: records counted, tile entries, records routed direct
     float ms_check = 0, ms_add = 0;                  // ... and its device time
+    // The indel store (rules 14 to 17); none before bwams_pileup_set_indels.
+    bool indels = false;
+    bwams_pileup_indel_opt_t io{};
+    DevBuf<uint32_t> diff;                           // rule 15 as a difference array: four per entry, n_slots + 1 entries
+    DevBuf<PileupSpan> span;                         // its inclusive scan, made by the first query after an add
+    DevBuf<PileupEvKey> ev_keys, ev_sorted, grp_keys;        // the events as appended; sorted; one key per group
+    DevBuf<uint32_t> ev_qe, ev_qe_sorted;
+    DevBuf<PileupEvSums> grp_sums;
+    DevBuf<unsigned long long> ev_n;                 // [0] the events held, as the event pass counts on; [1] the count pass of an add
+    DevBuf<bwams_pileup_indel_allele_t> d_alleles;
+    DevBuf<bwams_pileup_indel_t> d_icalls;
+    int64_t n_events = 0, ev_cap = 0, n_appended = 0, n_groups = 0;
+    bool span_valid = false, groups_valid = false;   // span and the groups answer for everything added: an add or a _reset clears both
+    float ms_indel = 0;                              // the indel kernels of the last add
+    PileupIndelStore store(unsigned long long *n) const { return PileupIndelStore{diff.p, ev_keys.p, ev_qe.p, n, ev_cap, io.indel_q, io.max_len}; }
+    size_t diff_bytes() const { return ((size_t)n_slots() + 1) * 16; }
     int32_t n_ref() const { return (int32_t)l_ref.size(); }
     int32_t n_regions() const { return (int32_t)regions.size(); }
     int64_t n_slots() const { return reg_off.back(); }
@@ -58,6 +74,50 @@ template <class Test> struct SlotCount {             // 1 at a slot the test sel
     Test f;
     __host__ __device__ int64_t operator()(int64_t s) const { return f(s) ? 1 : 0; }
 };
+
+// launch() on the handle's stream between its two events, waited for; the device time is added to *ms
+template <class Launch> int timed(bwams_pileup *p, float *ms, Launch &&launch) {
+    hipStream_t st = p->stream;
+    float t = 0;
+    BWAMS_HIP(hipEventRecord(p->ev[0], st));
+    launch();
+    BWAMS_HIP(hipEventRecord(p->ev[1], st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    BWAMS_HIP(hipGetLastError());
+    BWAMS_HIP(hipEventElapsedTime(&t, p->ev[0], p->ev[1]));
+    *ms += t;
+    return BWAMS_OK;
+}
+
+// Rule 14's count pass: the events the records would append, and an event buffer that holds them beside the ones it has.  Nothing of
+// the handle has moved when this fails.
+int indel_reserve(bwams_pileup *p, const DevRecords &recs, const PileupFilter &f, int64_t *n_new) {
+    hipStream_t st = p->stream;
+    unsigned long long count = 0;
+    BWAMS_HIP(hipMemsetAsync(p->ev_n.p + 1, 0, 8, st));
+    if (int rc = timed(p, &p->ms_indel, [&] {
+            launch_pileup_indel_events(recs.bam, recs.off, recs.n_rec, f, p->dev_regions(), p->store(p->ev_n.p + 1), 0, p->cu_count, st);
+        })) return rc;
+    BWAMS_HIP(hipMemcpyAsync(&count, p->ev_n.p + 1, 8, hipMemcpyDeviceToHost, st));
+    BWAMS_HIP(hipStreamSynchronize(st));
+    const int64_t need = p->n_events + (int64_t)count;
+    if (need > p->ev_cap) {                                              // grow by half, keeping the events held
+        const int64_t cap = std::max<int64_t>(need + need / 2, 256);
+        DevBuf<PileupEvKey> keys;
+        DevBuf<uint32_t> qe;
+        BWAMS_HIP(keys.alloc((size_t)cap * sizeof(PileupEvKey))); BWAMS_HIP(qe.alloc((size_t)cap * 4));
+        if (p->n_events) {
+            BWAMS_HIP(hipMemcpyAsync(keys.p, p->ev_keys.p, (size_t)p->n_events * sizeof(PileupEvKey), hipMemcpyDeviceToDevice, st));
+            BWAMS_HIP(hipMemcpyAsync(qe.p, p->ev_qe.p, (size_t)p->n_events * 4, hipMemcpyDeviceToDevice, st));
+            BWAMS_HIP(hipStreamSynchronize(st));
+        }
+        p->ev_keys = std::move(keys);
+        p->ev_qe = std::move(qe);
+        p->ev_cap = cap;
+    }
+    *n_new = (int64_t)count;
+    return BWAMS_OK;
+}
 
 // check first, then add (rule 3)
 int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, const char *who) {
@@ -83,6 +143,11 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
             set_last_error(std::string(who) + ": record " + std::to_string(h[first]) + why[first]);
             return BWAMS_ERR_ARG;
         }
+        int64_t n_events_new = 0;
+        p->ms_indel = 0;
+        p->n_appended = 0;
+        if (p->indels)
+            if (int rc = indel_reserve(p, recs, f, &n_events_new)) return rc;
         const int64_t n_tiles = (p->n_slots() + kPileupTile - 1) / kPileupTile;
         const int tiled = knobs().pileup_tiled != 0 && n_tiles > 0;
         unsigned bits = 1;
@@ -121,6 +186,14 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
                 })) return rc;
             for (int k = 0; k < 3; ++k) sum[k] += (int64_t)h[k];
         }
+        if (p->indels) {                                                 // the events and the span runs of every record of the call
+            p->span_valid = p->groups_valid = false;
+            if (int rc = timed(p, &p->ms_indel, [&] {
+                    launch_pileup_indel_events(dev_bam, dev_off, n_rec, f, R, p->store(p->ev_n.p), 1, p->cu_count, st);
+                })) return rc;
+            p->n_events += n_events_new;
+            p->n_appended = n_events_new;
+        }
     }
     p->n_added += n_rec;
     std::copy(sum, sum + 3, p->last);
@@ -154,6 +227,68 @@ int call_thresholds(const bwams_pileup *p, int32_t min_qual, int32_t min_depth, 
     return BWAMS_OK;
 }
 
+// What an indel query reads, brought up to date with the adds (cached until the next add or _reset): rule 15's sums, the inclusive scan
+// of the difference array; with `groups`, rule 16's groups too: the events sorted by (slot, type, len, seq) and each run of one key
+// reduced to its n, Q, HOM and HET.  BWAMS_ERR_ARG on a handle without the store; the handle's device is current afterwards.
+int indel_prepare(bwams_pileup *p, const char *who, bool groups) {
+    if (!p->indels) {
+        set_last_error(std::string(who) + ": the handle has no indel store (bwams_pileup_set_indels)");
+        return BWAMS_ERR_ARG;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    hipStream_t st = p->stream;
+    if (!p->span_valid && p->n_slots() > 0) {
+        if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": inclusive_scan").c_str(), [&](void *tmp, size_t &tb) {
+                return rocprim::inclusive_scan(tmp, tb, p->diff.as<const PileupSpan>(), p->span.p, (size_t)p->n_slots(), rocprim::plus<PileupSpan>(), st);
+            })) return rc;
+        BWAMS_HIP(hipStreamSynchronize(st));
+    }
+    p->span_valid = true;
+    if (!groups || p->groups_valid) return BWAMS_OK;
+    const size_t n = (size_t)p->n_events;
+    int64_t n_groups = 0;
+    if (n > 0) {
+        BWAMS_HIP(p->ev_sorted.ensure_n(n)); BWAMS_HIP(p->ev_qe_sorted.ensure_n(n));
+        BWAMS_HIP(p->grp_keys.ensure_n(n)); BWAMS_HIP(p->grp_sums.ensure_n(n)); BWAMS_HIP(p->sel_cnt.ensure_n(8));
+        if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": merge_sort").c_str(), [&](void *tmp, size_t &tb) {
+                return rocprim::merge_sort(tmp, tb, p->ev_keys.p, p->ev_sorted.p, p->ev_qe.p, p->ev_qe_sorted.p, n, PileupEvLess(), st);
+            })) return rc;
+        auto shares = rocprim::make_transform_iterator(p->ev_qe_sorted.p, PileupEvSumsOf());
+        if (int rc = with_tmp(p->tmp, st, (std::string(who) + ": reduce_by_key").c_str(), [&](void *tmp, size_t &tb) {
+                return rocprim::reduce_by_key(tmp, tb, p->ev_sorted.p, shares, n, p->grp_keys.p, p->grp_sums.p, p->sel_cnt.p,
+                                              rocprim::plus<PileupEvSums>(), PileupEvEqual(), st);
+            })) return rc;
+        BWAMS_HIP(hipMemcpyAsync(&n_groups, p->sel_cnt.p, 8, hipMemcpyDeviceToHost, st));
+        BWAMS_HIP(hipStreamSynchronize(st));
+    }
+    p->n_groups = n_groups;
+    p->groups_valid = true;
+    return BWAMS_OK;
+}
+
+int indel_thresholds(bwams_pileup *p, int32_t min_qual, int32_t min_depth, const char *who, PileupIndelTest *t) {
+    if (int rc = indel_prepare(p, who, true)) return rc;
+    if (min_qual < 0) min_qual = p->io.min_qual;
+    if (min_depth < 0) min_depth = p->io.min_depth;
+    if (min_depth < 1) {
+        set_last_error(std::string(who) + ": min_depth >= 1 is required (negative: the handle's)");
+        return BWAMS_ERR_ARG;
+    }
+    *t = PileupIndelTest{p->grp_keys.p, p->grp_sums.p, p->n_groups, p->span.p, p->ref.p, min_qual, min_depth};
+    return BWAMS_OK;
+}
+
+// a text into out[0, cap): *n the bytes written, or needed with BWAMS_ERR_CAPACITY
+int text_out(const char *who, const std::string &text, char *out, int64_t cap, int64_t *n) {
+    if (n) *n = (int64_t)text.size();
+    if (!out || cap < (int64_t)text.size()) {
+        set_last_error(std::string(who) + ": the text needs " + std::to_string(text.size()) + " bytes");
+        return BWAMS_ERR_CAPACITY;
+    }
+    memcpy(out, text.data(), text.size());
+    return BWAMS_OK;
+}
+
 void launch_records(const PileupSiteTest &test, bwams_pileup *p, int64_t n, bwams_pileup_site_t *out) {
     launch_pileup_sites(test, p->dev_regions(), p->n_regions(), p->sel.p, n, out, p->cu_count, p->stream);
 }
@@ -161,14 +296,18 @@ void launch_records(const PileupCallTest &test, bwams_pileup *p, int64_t n, bwam
     launch_pileup_calls(test, p->dev_regions(), p->n_regions(), p->sel.p, n, out, p->cu_count, p->stream);
 }
 
-// rules 8 and 13: the slots that `test` selects, counted and selected in slot order, and their records (sites or calls; d_out: the
+void launch_records(const PileupIndelTest &test, bwams_pileup *p, int64_t n, bwams_pileup_indel_t *out) {
+    launch_pileup_indel_calls(test, p->dev_regions(), p->n_regions(), p->sel.p, n, out, p->cu_count, p->stream);
+}
+
+// rules 8, 13 and 16: the slots that `test` selects, counted and selected in slot order, and their records (sites or calls; d_out: the
 // handle's device buffer for them) into host memory
+// n_slots: the items `test` is asked about, 0 .. n_slots - 1 (the handle's slots, or rule 16's groups)
 template <class Test, class Rec>
 int pileup_select(bwams_pileup *p, const Test &test, DevBuf<Rec> &d_out, const char *who, const char *what, bool count_only, int64_t cap,
-                  Rec *sites, std::vector<Rec> *own, int64_t *n_out) {
+                  Rec *sites, std::vector<Rec> *own, int64_t *n_out, int64_t n_slots) {
     hipStream_t st = p->stream;
     int64_t n_sites = 0;
-    const int64_t n_slots = p->n_slots();
     rocprim::counting_iterator<int64_t> slot(0);
     BWAMS_HIP(p->sel_cnt.ensure_n(8));
     if (n_slots > 0) {
@@ -276,6 +415,12 @@ int bwams_pileup_reset(bwams_pileup_t *p) {
     BWAMS_HIP(hipSetDevice(p->device));
     BWAMS_HIP(hipMemsetAsync(p->counts.p, 0, p->plane_bytes(), p->stream));
     if (p->sums.p) BWAMS_HIP(hipMemsetAsync(p->sums.p, 0, p->plane_bytes(), p->stream));
+    if (p->indels) {
+        BWAMS_HIP(hipMemsetAsync(p->diff.p, 0, p->diff_bytes(), p->stream));
+        BWAMS_HIP(hipMemsetAsync(p->ev_n.p, 0, 16, p->stream));
+        p->n_events = p->n_appended = p->n_groups = 0;
+        p->span_valid = p->groups_valid = false;
+    }
     BWAMS_HIP(hipStreamSynchronize(p->stream));
     p->clean = true;
     p->n_added = 0;
@@ -398,7 +543,7 @@ int bwams_pileup_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, b
     if (int rc = call_thresholds(p, min_qual, min_depth, "bwams_pileup_calls", &test)) return rc;
     BWAMS_HIP(hipSetDevice(p->device));
     int64_t n_calls = 0;
-    const int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, test, p->d_calls, "bwams_pileup_calls", "calls", !calls, cap, calls, nullptr, &n_calls);
+    const int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, test, p->d_calls, "bwams_pileup_calls", "calls", !calls, cap, calls, nullptr, &n_calls, p->n_slots());
     if (n) *n = n_calls;
     return rc;
 }
@@ -414,7 +559,7 @@ int bwams_pileup_vcf(bwams_pileup_t *p, const char *names, const char *sample, i
     BWAMS_HIP(hipSetDevice(p->device));
     std::vector<bwams_pileup_call_t> calls;
     int64_t n_calls = 0;
-    if (int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, test, p->d_calls, "bwams_pileup_vcf", "calls", false, 0, nullptr, &calls, &n_calls))
+    if (int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, test, p->d_calls, "bwams_pileup_vcf", "calls", false, 0, nullptr, &calls, &n_calls, p->n_slots()))
         return rc;
     std::string text;
     if (int rc = pileup_vcf_format(names, p->l_ref.data(), p->n_ref(), p->regions.data(), p->n_regions(), sample, calls.data(), n_calls, &text))
@@ -434,7 +579,7 @@ int bwams_pileup_sites(bwams_pileup_t *p, int32_t min_alt, int32_t min_permille,
     if (int rc = thresholds(p, min_alt, min_permille, "bwams_pileup_sites", &test)) return rc;
     BWAMS_HIP(hipSetDevice(p->device));
     int64_t n_sites = 0;
-    const int rc = pileup_select<PileupSiteTest, bwams_pileup_site_t>(p, test, p->d_sites, "bwams_pileup_sites", "sites", !sites, cap, sites, nullptr, &n_sites);
+    const int rc = pileup_select<PileupSiteTest, bwams_pileup_site_t>(p, test, p->d_sites, "bwams_pileup_sites", "sites", !sites, cap, sites, nullptr, &n_sites, p->n_slots());
     if (n) *n = n_sites;
     return rc;
 }
@@ -449,7 +594,7 @@ int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int
     BWAMS_HIP(hipSetDevice(p->device));
     std::vector<bwams_pileup_site_t> sites;
     int64_t n_sites = 0;
-    if (int rc = pileup_select<PileupSiteTest, bwams_pileup_site_t>(p, test, p->d_sites, "bwams_pileup_text", "sites", false, 0, nullptr, &sites, &n_sites))
+    if (int rc = pileup_select<PileupSiteTest, bwams_pileup_site_t>(p, test, p->d_sites, "bwams_pileup_text", "sites", false, 0, nullptr, &sites, &n_sites, p->n_slots()))
         return rc;
     std::string text;
     if (int rc = pileup_text_format(names, p->n_ref(), p->regions.data(), p->n_regions(), sites.data(), n_sites, &text)) return rc;
@@ -459,6 +604,131 @@ int bwams_pileup_text(bwams_pileup_t *p, const char *names, int32_t min_alt, int
         return BWAMS_ERR_CAPACITY;
     }
     memcpy(out, text.data(), text.size());
+    return BWAMS_OK;
+}
+
+int bwams_pileup_set_indels(bwams_pileup_t *p, const bwams_pileup_indel_opt_t *opt) {
+    const bwams_pileup_indel_opt_t o = opt ? *opt : bwams_pileup_indel_opt_t{20, 1, 40, BWAMS_PILEUP_INDEL_MAX, 0};
+    if (!p || o.min_qual < 0 || o.min_depth < 1 || o.indel_q < 0 || o.indel_q > 93 || o.max_len < 1 || o.max_len > BWAMS_PILEUP_INDEL_MAX ||
+        o.reserved != 0) {
+        set_last_error("bwams_pileup_set_indels: a handle, min_qual >= 0, min_depth >= 1, indel_q in [0, 93], max_len in [1, 32] and reserved == 0 "
+                       "are required");
+        return BWAMS_ERR_ARG;
+    }
+    if (!p->clean) {
+        set_last_error("bwams_pileup_set_indels: the counters are not zero: before the first add, or directly after bwams_pileup_reset");
+        return BWAMS_ERR_ARG;
+    }
+    if (p->n_slots() >= (1LL << 32)) {
+        set_last_error("bwams_pileup_set_indels: an event's key holds a slot below 2^32; the handle has " + std::to_string(p->n_slots()));
+        return BWAMS_ERR_UNSUPPORTED;
+    }
+    BWAMS_HIP(hipSetDevice(p->device));
+    if (!p->diff.p) BWAMS_HIP(p->diff.alloc(p->diff_bytes()));           // BWAMS_ERR_NOMEM when the span sums do not fit
+    if (!p->span.p) BWAMS_HIP(p->span.alloc((size_t)std::max<int64_t>(p->n_slots(), 1) * sizeof(PileupSpan)));
+    if (!p->ev_n.p) BWAMS_HIP(p->ev_n.alloc(16));
+    BWAMS_HIP(hipMemsetAsync(p->diff.p, 0, p->diff_bytes(), p->stream));
+    BWAMS_HIP(hipMemsetAsync(p->ev_n.p, 0, 16, p->stream));
+    BWAMS_HIP(hipStreamSynchronize(p->stream));
+    p->n_events = p->n_appended = p->n_groups = 0;
+    p->span_valid = p->groups_valid = false;
+    p->io = o;
+    p->indels = true;
+    return BWAMS_OK;
+}
+
+int bwams_pileup_fetch_span(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *sums) {
+    if (!p || !p->indels || region < 0 || region >= p->n_regions() || beg < p->regions[(size_t)region].beg || end < beg ||
+        end > p->regions[(size_t)region].end || (end > beg && !sums)) {
+        set_last_error("bwams_pileup_fetch_span: a handle with an indel store, a region in [0, n_regions) and region.beg <= beg <= end <= "
+                       "region.end are required");
+        return BWAMS_ERR_ARG;
+    }
+    if (int rc = indel_prepare(p, "bwams_pileup_fetch_span", false)) return rc;
+    if (end > beg) {
+        const int64_t first = p->reg_off[(size_t)region] + (beg - p->regions[(size_t)region].beg);
+        BWAMS_HIP(hipMemcpyAsync(sums, p->span.p + first, (size_t)(end - beg) * sizeof(PileupSpan), hipMemcpyDeviceToHost, p->stream));
+        BWAMS_HIP(hipStreamSynchronize(p->stream));
+    }
+    return BWAMS_OK;
+}
+
+int bwams_pileup_indel_alleles(bwams_pileup_t *p, bwams_pileup_indel_allele_t *alleles, int64_t cap, int64_t *n) {
+    if (!p || cap < 0) return BWAMS_ERR_ARG;
+    if (int rc = indel_prepare(p, "bwams_pileup_indel_alleles", true)) return rc;
+    if (n) *n = p->n_groups;
+    if (!alleles || p->n_groups == 0) return BWAMS_OK;
+    if (cap < p->n_groups) {
+        set_last_error("bwams_pileup_indel_alleles: " + std::to_string(p->n_groups) + " alleles do not fit a capacity of " + std::to_string(cap));
+        return BWAMS_ERR_CAPACITY;
+    }
+    BWAMS_HIP(p->d_alleles.ensure_n((size_t)p->n_groups));
+    launch_pileup_indel_alleles(p->grp_keys.p, p->grp_sums.p, p->n_groups, p->dev_regions(), p->n_regions(), p->d_alleles.p, p->cu_count, p->stream);
+    BWAMS_HIP(hipMemcpyAsync(alleles, p->d_alleles.p, (size_t)p->n_groups * sizeof(bwams_pileup_indel_allele_t), hipMemcpyDeviceToHost, p->stream));
+    BWAMS_HIP(hipStreamSynchronize(p->stream));
+    BWAMS_HIP(hipGetLastError());
+    return BWAMS_OK;
+}
+
+int bwams_pileup_indel_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, bwams_pileup_indel_t *calls, int64_t cap, int64_t *n) {
+    if (!p || cap < 0) return BWAMS_ERR_ARG;
+    PileupIndelTest test;
+    if (int rc = indel_thresholds(p, min_qual, min_depth, "bwams_pileup_indel_calls", &test)) return rc;
+    int64_t n_calls = 0;
+    const int rc = pileup_select<PileupIndelTest, bwams_pileup_indel_t>(p, test, p->d_icalls, "bwams_pileup_indel_calls", "indel calls", !calls, cap,
+                                                                        calls, nullptr, &n_calls, p->n_groups);
+    if (n) *n = n_calls;
+    return rc;
+}
+
+int bwams_pileup_indel_vcf(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, char *out, int64_t cap,
+                           int64_t *n) {
+    if (!p || (!names && p->n_ref()) || !sample) {
+        set_last_error("bwams_pileup_indel_vcf: a handle, the references' names and a sample name are required");
+        return BWAMS_ERR_ARG;
+    }
+    PileupIndelTest test;
+    if (int rc = indel_thresholds(p, min_qual, min_depth, "bwams_pileup_indel_vcf", &test)) return rc;
+    std::vector<bwams_pileup_indel_t> indels;
+    int64_t n_indels = 0;
+    if (int rc = pileup_select<PileupIndelTest, bwams_pileup_indel_t>(p, test, p->d_icalls, "bwams_pileup_indel_vcf", "indel calls", false, 0, nullptr,
+                                                                      &indels, &n_indels, p->n_groups)) return rc;
+    std::string text;
+    if (int rc = pileup_indel_vcf_format(names, p->l_ref.data(), p->n_ref(), p->regions.data(), p->n_regions(), sample, nullptr, 0, indels.data(),
+                                         n_indels, &text)) return rc;
+    return text_out("bwams_pileup_indel_vcf", text, out, cap, n);
+}
+
+int bwams_pileup_vcf_all(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, int32_t indel_min_qual,
+                         int32_t indel_min_depth, char *out, int64_t cap, int64_t *n) {
+    if (!p || (!names && p->n_ref()) || !sample) {
+        set_last_error("bwams_pileup_vcf_all: a handle, the references' names and a sample name are required");
+        return BWAMS_ERR_ARG;
+    }
+    PileupCallTest snv_test;
+    PileupIndelTest test;
+    if (int rc = call_thresholds(p, min_qual, min_depth, "bwams_pileup_vcf_all", &snv_test)) return rc;
+    if (int rc = indel_thresholds(p, indel_min_qual, indel_min_depth, "bwams_pileup_vcf_all", &test)) return rc;
+    std::vector<bwams_pileup_call_t> snvs;
+    std::vector<bwams_pileup_indel_t> indels;
+    int64_t n_snvs = 0, n_indels = 0;
+    if (int rc = pileup_select<PileupCallTest, bwams_pileup_call_t>(p, snv_test, p->d_calls, "bwams_pileup_vcf_all", "calls", false, 0, nullptr, &snvs,
+                                                                    &n_snvs, p->n_slots())) return rc;
+    if (int rc = pileup_select<PileupIndelTest, bwams_pileup_indel_t>(p, test, p->d_icalls, "bwams_pileup_vcf_all", "indel calls", false, 0, nullptr,
+                                                                      &indels, &n_indels, p->n_groups)) return rc;
+    std::string text;
+    if (int rc = pileup_indel_vcf_format(names, p->l_ref.data(), p->n_ref(), p->regions.data(), p->n_regions(), sample, snvs.data(), n_snvs,
+                                         indels.data(), n_indels, &text)) return rc;
+    return text_out("bwams_pileup_vcf_all", text, out, cap, n);
+}
+
+int bwams_pileup_indel_info(const bwams_pileup_t *p, bwams_pileup_indel_info_t *info) {
+    if (!p || !info) return BWAMS_ERR_ARG;
+    if (!p->indels) {
+        set_last_error("bwams_pileup_indel_info: the handle has no indel store (bwams_pileup_set_indels)");
+        return BWAMS_ERR_ARG;
+    }
+    *info = bwams_pileup_indel_info_t{p->n_events, p->ev_cap, p->n_appended, p->ms_indel, 0};
     return BWAMS_OK;
 }
 

@@ -426,6 +426,104 @@ void launch_pileup_ref(const PileupRegions &R, int32_t n_regions, const int32_t 
                        const bwams_contig_t *contigs, const int64_t *hole_off, const int32_t *hole_len, int32_t n_holes, uint8_t *out,
                        int cu_count, hipStream_t st);
 
+// pileup_indel.hip: the indel store of a pileup handle (rules 14 to 17).  An event is a 16-byte key and its quality: k0 holds
+// slot << 8 | type << 6 | len and seq the packed bases, so the order by (k0, seq) is rule 16's order by (slot, type, len, seq).  diff:
+// rule 15's sums as a difference array, four uint32 per entry over n_slots + 1 entries; span: its inclusive scan, four per slot.
+struct PileupEvKey {
+    uint64_t k0, seq;
+    __host__ __device__ int64_t slot() const { return (int64_t)(k0 >> 8); }
+    __host__ __device__ int type() const { return (int)(k0 >> 6) & 3; }
+    __host__ __device__ int len() const { return (int)k0 & 63; }
+};
+struct PileupEvLess {
+    __host__ __device__ bool operator()(const PileupEvKey &a, const PileupEvKey &b) const { return a.k0 < b.k0 || (a.k0 == b.k0 && a.seq < b.seq); }
+};
+struct PileupEvEqual {
+    __host__ __device__ bool operator()(const PileupEvKey &a, const PileupEvKey &b) const { return a.k0 == b.k0 && a.seq == b.seq; }
+};
+struct PileupEvSums {                    // a group's n, Q, HOM and HET (rule 16)
+    uint64_t n, q, hom, het;
+    __host__ __device__ PileupEvSums operator+(const PileupEvSums &o) const { return PileupEvSums{n + o.n, q + o.q, hom + o.hom, het + o.het}; }
+};
+struct PileupEvSumsOf {                  // an event's share of its group, from its qe
+    __host__ __device__ PileupEvSums operator()(uint32_t qe) const { return PileupEvSums{1, qe, pileup_gl_hom((int)qe), pileup_gl_het((int)qe)}; }
+};
+struct PileupSpan {                      // SPAN_N, SPAN_Q, SPAN_HOM, SPAN_HET, modulo 2^32
+    uint32_t v[4];
+    __host__ __device__ PileupSpan operator+(const PileupSpan &o) const { return PileupSpan{{v[0] + o.v[0], v[1] + o.v[1], v[2] + o.v[2], v[3] + o.v[3]}}; }
+};
+struct PileupIndelStore {                // what the event kernels write: the difference array, the events from *n_events on (cap of them)
+    uint32_t *diff;
+    PileupEvKey *keys;
+    uint32_t *qe;
+    unsigned long long *n_events;
+    int64_t cap;
+    int32_t indel_q, max_len;
+};
+struct PileupIndelTest {                 // rule 16 over the sorted groups: group i is asked, and answers only as the first group of its slot
+    const PileupEvKey *keys;
+    const PileupEvSums *sums;
+    int64_t n_groups;
+    const PileupSpan *span;
+    const uint8_t *ref;
+    int32_t min_qual, min_depth;
+    // the slot's record but region, pos and del_ref; false when i is not the first group of its slot, or rule 16 gives no ALT there
+    __host__ __device__ bool genotype(int64_t i, bwams_pileup_indel_t *out, uint64_t *depth) const {
+        const int64_t s = keys[i].slot();
+        if (i > 0 && keys[i - 1].slot() == s) return false;
+        const int32_t r = ref[s];
+        if (r > 3) return false;
+        int64_t alt = -1;
+        uint64_t n_alt = 0, total = 0;
+        for (int64_t j = i; j < n_groups && keys[j].slot() == s; ++j) {
+            const uint64_t n = sums[j].n;
+            total += n;
+            if (keys[j].type() < BWAMS_PILEUP_EV_OTHER && n > n_alt) { alt = j; n_alt = n; }     // ascending order: a tie stays with the first
+        }
+        if (alt < 0) return false;
+        const PileupSpan sp = span[s];
+        const PileupEvSums a = sums[alt];
+        const uint64_t cost[3] = {(uint64_t)sp.v[BWAMS_PILEUP_SPAN_HOM] + 100 * a.q + (uint64_t)kPileupGlMis * a.n,
+                                  (uint64_t)sp.v[BWAMS_PILEUP_SPAN_HET] + a.het,
+                                  100 * (uint64_t)sp.v[BWAMS_PILEUP_SPAN_Q] + (uint64_t)kPileupGlMis * sp.v[BWAMS_PILEUP_SPAN_N] + a.hom};
+        const int best = cost[1] < cost[0] ? (cost[2] < cost[1] ? 2 : 1) : (cost[2] < cost[0] ? 2 : 0);
+        int32_t second = 0x7FFFFFFF;
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const uint64_t pl = (cost[g] - cost[best] + 50) / 100;
+            out->pl[g] = pl > 0x7FFFFFFFULL ? 0x7FFFFFFF : (int32_t)pl;
+            if (g != best && out->pl[g] < second) second = out->pl[g];
+        }
+        out->ref = r;
+        out->type = keys[alt].type();
+        out->len = keys[alt].len();
+        out->reserved = 0;
+        out->seq = keys[alt].seq;
+        out->gt = best;
+        out->qual = out->pl[0];
+        out->gq = second < 99 ? second : 99;
+        *depth = (uint64_t)sp.v[BWAMS_PILEUP_SPAN_N] + total;
+        out->depth = (uint32_t)*depth;
+        out->n_ref = sp.v[BWAMS_PILEUP_SPAN_N];
+        out->n_alt = (uint32_t)n_alt;
+        out->n_other = (uint32_t)(total - n_alt);
+        return true;
+    }
+    __host__ __device__ bool operator()(int64_t i) const {
+        bwams_pileup_indel_t x;
+        uint64_t depth;
+        return genotype(i, &x, &depth) && x.gt != 0 && x.qual >= min_qual && depth >= (uint64_t)min_depth;
+    }
+};
+// events: emit == 0 adds to *S.n_events the events the records would append and writes nothing else; emit != 0 appends them and adds
+// rule 15's runs to S.diff.  alleles and indel_calls: the records of the groups / of the selected first groups.
+void launch_pileup_indel_events(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, const PileupRegions &R,
+                                const PileupIndelStore &S, int emit, int cu_count, hipStream_t st);
+void launch_pileup_indel_alleles(const PileupEvKey *keys, const PileupEvSums *sums, int64_t n_groups, const PileupRegions &R, int32_t n_regions,
+                                 bwams_pileup_indel_allele_t *out, int cu_count, hipStream_t st);
+void launch_pileup_indel_calls(const PileupIndelTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *groups, int64_t n,
+                               bwams_pileup_indel_t *out, int cu_count, hipStream_t st);
+
 // qc.hip: alignment QC (rules in include/bwams.h above bwams_qc_open).  All counters are one block of 64-bit words in HBM, laid out by
 // QcLayout: the flag counters, the scalars, then rule 4's six tables.  check: *bad = min(*bad, record << 3 | reason).  records: rules
 // 2-5 but tables b and c; lists[c * n_rec ..] gets the indices of class c's filtered-in records with l_seq > 0 and call[] (zeroed by

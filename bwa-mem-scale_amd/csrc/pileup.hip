@@ -33,23 +33,18 @@
 //                         fills the call records of the selected slots.
 //   pileup_site_*         rule 8's predicate over the slots (SiteTest, given to rocprim::reduce and rocprim::select by
 //                         api_pileup.hip) and the gather that fills the site records of the selected slots.
+//   The indel store of rules 14 to 17 is pileup_indel.hip; pileup_dev.h holds what the two files share.
 //   pileup_ref_kernel     rule 7: a lane per slot copies the forward strand's .0123 code at contig offset + position; a position in one
 //                         of the .amb holes reads 4 (ref_code_at, ref_gather.h).
 #include <algorithm>
 #include "common.h"
 #include "bam_rec.h"
+#include "pileup_dev.h"
 #include "ref_gather.h"
 #include "wave_ops.h"
 
 namespace bwams {
 namespace {
-
-// rule 2, for a record at p
-__device__ __forceinline__ bool record_counts(const uint8_t *p, const PileupFilter &f) {
-    const int32_t rid = bam_ref_id(p);
-    return !(bam_flag(p) & f.exclude) && (int32_t)bam_mapq(p) >= f.min_mapq && rid >= 0 && rid < f.n_ref && bam_n_cig(p) > 0 &&
-           bam_l_seq(p) > 0;
-}
 
 __global__ void __launch_bounds__(256) pileup_check_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, PileupFilter f,
                                                            unsigned long long *bad) {
@@ -70,16 +65,6 @@ __global__ void __launch_bounds__(256) pileup_check_kernel(const uint8_t *bam, c
         if (qlen != l_seq) atomicMin(bad + 1, (unsigned long long)r);
         else if (bam_aux_at(bam_l_name(p), n_cig, l_seq) > bam_end(p)) atomicMin(bad + 2, (unsigned long long)r);
     }
-}
-
-// the first region of [lo, hi) whose end is above x (hi when there is none)
-__device__ __forceinline__ int32_t first_region_ending_above(const PileupRegions &R, int32_t lo, int32_t hi, int64_t x) {
-    while (lo < hi) {
-        const int32_t mid = lo + (hi - lo) / 2;
-        if ((int64_t)R.end[mid] > x) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
 }
 
 // A region held in registers: the usual record lies in one region, and its lanes then ask memory nothing to place a base.
@@ -440,17 +425,6 @@ __global__ void __launch_bounds__(256) pileup_direct_quality_kernel(const uint8_
         const RecView v = view_of(bam + rec_off[r], R);
         walk_record(R, v, min_baseq, lane, sink);
     }
-}
-
-// the region of slot s: the last whose first slot is at or before s
-__device__ __forceinline__ int32_t region_of_slot(const PileupRegions &R, int32_t n_regions, int64_t s) {
-    int32_t lo = 0, hi = n_regions - 1;
-    while (lo < hi) {
-        const int32_t mid = lo + (hi - lo + 1) / 2;
-        if (R.off[mid] <= s) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(256) pileup_call_kernel(PileupCallTest test, PileupRegions R, int32_t n_regions, const int64_t *slots,

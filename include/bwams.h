@@ -1242,7 +1242,7 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  *       "c1\t3\tG\t5\t0\t0\t3\t1\t0\t0\t0\t1\t0\t0\t0\tT\n" "c1\t5\tA\t7\t4\t0\t0\t0\t1\t0\t0\t0\t0\t2\t0\tDEL\n"
  *       "c1\t6\tC\t7\t0\t6\t0\t0\t0\t1\t0\t0\t0\t0\t2\tINS\n"
  *     Quality-weighted sums, genotype costs, SNV calls and their VCF text are rules 10 to 13, for a handle with a quality plane.
- *     Indel genotypes are out of scope: the sites and their counters are the interface for a caller that wants them.
+ *     Indel alleles, their genotypes and VCF rows are rules 14 to 17, for a handle with an indel store.
  * 10. Effective quality (a handle with a quality plane: bwams_pileup_set_quality).  A base that rule 4 counts in one of the eight base
  *     channels has the effective quality qe = clamp(min(q, MAPQ), 4, 60), where q is its QUAL byte, or no_qual_q (default 30) for a
  *     record whose first QUAL byte is 0xFF.  min_baseq is tested on the raw byte as in rule 4, before this.  N, DEL and INS add
@@ -1282,6 +1282,42 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  *     values or six.  Rule 9's seven records with MAPQ 60: slot 2 (reference G) has three G and two T of quality 30, so
  *     cost(GG) = 2 * 3477 = 6954, cost(GT) = 5 * 301 = 1505 and cost(TT) = 3 * 3477 = 10431, pl is 54 / 0 / 89, and the only row is
  *       "c1\t3\t.\tG\tT\t54\t.\tDP=5\tGT:AD:DP:GQ:PL\t0/1:3,2:5:54:54,0,89\n"
+ * 14. Events (a handle with an indel store: bwams_pileup_set_indels; the store is independent of the quality plane).  In each record
+ *     that rule 2 counts (rule 3 is checked for the whole call first), every I or D op that a reference-consuming op (M D N = X, of
+ *     any length) precedes gives one event at the ANCHOR, the reference position just before the op: rule 4's INS condition, for D
+ *     too.  An I or D that opens the alignment gives none; the DEL and INS channels are untouched by all of this.  An event whose
+ *     anchor is in no region slot is dropped.  An event has a type (0 DEL, 1 INS, 2 OTHER), a length and a sequence: for an insertion
+ *     the op's SEQ bases packed 2 bits each, base j at bits 2j and 2j + 1, codes 1 2 4 8 as 0 1 2 3, the bits above 2 len zero; 0
+ *     for a deletion.  An event becomes OTHER, with len 0 and seq 0, when its length exceeds max_len (1..32, default 32: what a
+ *     64-bit sequence word holds), when an inserted base is not A, C, G or T, or when it is a deletion whose last deleted position
+ *     is not in the anchor's region.  Its quality is qe = clamp(min(MAPQ, indel_q), 4, 60), indel_q in 0..93, default 40; base
+ *     qualities and min_baseq play no part.  Adjacent I and D ops give two events at one anchor.
+ * 15. Span sums (reference support).  A record that rule 2 counts SPANS slot s when positions s and s + 1 both lie inside one
+ *     maximal run of consecutive M/=/X ops of its CIGAR (any other op, of any length, ends a run); s + 1 may lie outside every
+ *     region.  Per slot four uint32 sums, SPAN_N, SPAN_Q, SPAN_HOM and SPAN_HET (BWAMS_PILEUP_SPAN_*), get 1, qe, T_HOM[qe] and
+ *     T_HET[qe] with rule 14's qe.  They accumulate as rule 6 has it, modulo 2^32.
+ * 16. Alleles and genotype, at a slot with reference base r < 4.  The events at the slot group by (type, len, seq); a group has n,
+ *     Q = sum of qe, HOM = sum of T_HOM[qe] and HET = sum of T_HET[qe], each in uint64.  The groups are ordered by (type, len, seq),
+ *     seq compared unsigned.  ALT is the type-0 or type-1 group with the largest n, a tie going to the first in that order; a slot
+ *     with no such group is no call.  n_other counts every other event at the slot.  MIS_x = 100 Q_x + 477 n_x.  In uint64:
+ *       cost(RR) = SPAN_HOM + MIS_ALT,  cost(RA) = SPAN_HET + HET_ALT,  cost(AA) = SPAN_MIS + HOM_ALT.
+ *     pl, the genotype, qual = pl[RR] and gq follow rule 13: + 50 then / 100, saturating int32, a tie to the lowest of RR RA AA,
+ *     gq = min(99, the least other pl).  depth = SPAN_N + n_ALT + n_other.  A slot is a CALL when the genotype is not RR, qual >=
+ *     min_qual (default 20) and depth >= min_depth (default 1).  Alleles are taken as the CIGARs give them: there is NO realignment,
+ *     NO left-normalisation and no model of homopolymers, tandem repeats, strands or mate overlap.  Two reads that place the same
+ *     deletion one base apart are two alleles at two slots.
+ * 17. Records and text.  bwams_pileup_indel_calls returns the calls in slot order as bwams_pileup_indel_t records (include/bwams_types.h):
+ *     region, pos (the anchor), ref, type, len, seq, gt (1 het, 2 hom-alt), qual, gq, depth, n_ref (SPAN_N), n_alt, n_other, pl[3],
+ *     del_ref[32] (the reference codes 0..4 of the deleted positions, 0 elsewhere).  bwams_pileup_indel_alleles returns EVERY group
+ *     of every slot, OTHER included and whatever the slot's reference base, in (slot, type, len, seq) order as
+ *     bwams_pileup_indel_allele_t: region, pos, type, len, seq, n, q, hom, het.  VCF rows: a deletion has REF = the anchor letter
+ *     plus the deleted letters (ACGTN) and ALT = the anchor letter; an insertion has REF = the anchor letter and ALT = the anchor
+ *     letter plus the sequence.  INFO is DP=depth;INDEL, FORMAT GT:AD:DP:GQ:PL, GT 0/1 or 1/1, AD n_ref,n_alt, three PL values.
+ *     Rule 9's seven records with MAPQ 60 and the default options: qe = 40, MIS = 4477 a read, HOM = 0 and HET = 301.  Slot 3 has
+ *     3 spanning reads and 2 deletions of 1: cost(RR) = 8954, cost(RA) = 3 * 301 + 2 * 301 = 1505, cost(AA) = 13431.  Slot 5 has 5
+ *     spanning reads and 2 insertions of TT: cost(RR) = 8954, cost(RA) = 2107, cost(AA) = 22385.  The two rows:
+ *       "c1\t4\t.\tTA\tT\t74\t.\tDP=5;INDEL\tGT:AD:DP:GQ:PL\t0/1:3,2:5:74:74,0,119\n"
+ *       "c1\t6\t.\tC\tCTT\t68\t.\tDP=7;INDEL\tGT:AD:DP:GQ:PL\t0/1:5,2:7:68:68,0,203\n"
  * bwams_pileup_open: a zeroed handle on `device` (opt may be NULL for the defaults; exclude above 0xFFFF, min_baseq outside [0, 255],
  * min_alt < 1, min_permille outside [0, 1000], reserved != 0, n_ref < 0, a negative length or rule 1: BWAMS_ERR_ARG).  _close (NULL
  * allowed).  _add_batch: the batch's current BAM records (bwams_bam_run / _upload left them, BWAMS_ERR_ARG before either), read in
@@ -1301,6 +1337,24 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  * _sites; min_qual and min_depth: rule 13's thresholds for this query, a negative value for the handle's (min_depth 0:
  * BWAMS_ERR_ARG).  _vcf: rule 13's text into out[0, cap), as _text.  _fetch_quality, _calls and _vcf on a handle without a plane:
  * BWAMS_ERR_ARG.
+ * _set_indels: the indel store of rules 14 to 17, independent of the quality plane: rule 15's sums (32 bytes more per position, the
+ * sums and their difference array) allocated and zeroed, and an empty event list (opt may be NULL for {20, 1, 40, 32, 0}; min_qual
+ * < 0, min_depth < 1, indel_q outside [0, 93], max_len outside [1, 32] or reserved != 0: BWAMS_ERR_ARG; BWAMS_ERR_UNSUPPORTED for a
+ * handle of 2^32 slots or more; BWAMS_ERR_NOMEM when the sums do not fit).  Legal only while the counters are zero, as _set_quality;
+ * calling it again then replaces the options, zeroes the sums and empties the events; _reset zeroes the sums and empties the events.
+ * A handle on which it was never called behaves in every call exactly as before, and its adds launch exactly the kernels they
+ * launched.  With the store, an add first counts the events its records give and grows the event buffer (16 bytes of key and 4 of
+ * quality per event, the events held kept) before any counter of the call moves: BWAMS_ERR_NOMEM there adds nothing.
+ * _fetch_span: rule 15's sums of positions [beg, end), four per position, as _fetch.  _indel_alleles and _indel_calls: as _sites
+ * (*n found or needed, a NULL array to ask, BWAMS_ERR_CAPACITY); min_qual and min_depth as in _calls, a negative value for the
+ * store's.  _indel_vcf: rule 13's header with the line ##INFO=<ID=INDEL,Number=0,Type=Flag,...> after DP, then rule 17's rows, as
+ * _text.  _vcf_all needs both the quality plane and the indel store (BWAMS_ERR_ARG otherwise): that same header, then the SNV rows
+ * of _vcf (min_qual, min_depth) and the indel rows (indel_min_qual, indel_min_depth) merged by position, the SNV first where both
+ * stand at one position; _vcf itself stays byte for byte what it is.  _indel_info: the events held, the capacity of their buffer in
+ * events, and of the last add the events appended and the device time of the indel kernels; a test and measurement hook.
+ * _fetch_span, _indel_alleles, _indel_calls, _indel_vcf, _vcf_all and _indel_info on a handle without the store: BWAMS_ERR_ARG.
+ * The queries sort the events with rocprim::merge_sort, reduce runs of one key with rocprim::reduce_by_key and scan the sums'
+ * difference array with rocprim::inclusive_scan; all three are cached until the next add or _reset.
  * _info: the positions of a tile of the add (below), the handle's regions and slots, and of the last add the records counted, the
  * (tile, record) entries, the records routed direct and the device time: a test and measurement hook, like bwams_debug_chain_counts.
  * An add cuts the slots into tiles.  A record whose slots lie in one or two tiles is counted in LDS by the workgroup that owns
@@ -1312,7 +1366,9 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  * merged stream AS WRITTEN, after the merge has set or cleared 0x400, in whole records (one cut by a deflate piece's end is counted
  * once); the file and the index are byte for byte what they are without the call; an add that fails ends the close with its error.
  * A sorter may have a depth handle, a pileup handle, or both: both see the same whole records.  A handle with a quality plane set on
- * a sorter receives the sums through the same add: the close leaves it ready for _calls and _vcf. */
+ * a sorter receives the sums through the same add: the close leaves it ready for _calls and _vcf.  A handle with an indel store set
+ * on a sorter receives the events and the span sums through that add too, with no further call: the close leaves it ready for
+ * _indel_calls and, with both, _vcf_all. */
 int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwams_pileup_region_t *regions, int32_t n_regions,
                       const bwams_pileup_opt_t *opt, bwams_pileup_t **out);
 int bwams_pileup_close(bwams_pileup_t *p);
@@ -1330,6 +1386,15 @@ int bwams_pileup_fetch_quality(bwams_pileup_t *p, int32_t region, int32_t beg, i
 int bwams_pileup_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, bwams_pileup_call_t *calls, int64_t cap, int64_t *n);
 int bwams_pileup_vcf(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, char *out, int64_t cap,
                      int64_t *n);
+int bwams_pileup_set_indels(bwams_pileup_t *p, const bwams_pileup_indel_opt_t *opt);
+int bwams_pileup_fetch_span(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *sums);
+int bwams_pileup_indel_alleles(bwams_pileup_t *p, bwams_pileup_indel_allele_t *alleles, int64_t cap, int64_t *n);
+int bwams_pileup_indel_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, bwams_pileup_indel_t *calls, int64_t cap, int64_t *n);
+int bwams_pileup_indel_vcf(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, char *out, int64_t cap,
+                           int64_t *n);
+int bwams_pileup_vcf_all(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, int32_t indel_min_qual,
+                         int32_t indel_min_depth, char *out, int64_t cap, int64_t *n);
+int bwams_pileup_indel_info(const bwams_pileup_t *p, bwams_pileup_indel_info_t *info);
 int bwams_sorter_set_pileup(bwams_sorter_t *s, bwams_pileup_t *p);
 /* Alignment QC (csrc/qc.hip, csrc/api_qc.hip, host/qc_text.cpp): the flag counts, insert sizes and per-cycle tables that a pipeline
  * reads off a finished BAM, accumulated on the device from a batch's BAM records, from host records, or from the sorted BAM

@@ -381,6 +381,54 @@ typedef struct bwams_pileup_info {
     float   ms_check, ms_add;
 } bwams_pileup_info_t;
 
+/* Rules 14 and 16: the thresholds of an indel call, the cap on an event's quality and the longest allele kept apart.  reserved must
+ * be 0.  A NULL pointer means {20, 1, 40, 32, 0}. */
+typedef struct bwams_pileup_indel_opt {
+    int32_t min_qual;            /* >= 0 */
+    int32_t min_depth;           /* >= 1 */
+    int32_t indel_q;             /* 0..93 */
+    int32_t max_len;             /* 1..32 */
+    int32_t reserved;
+} bwams_pileup_indel_opt_t;
+
+/* The type of an event (rule 14) and the four span sums of a slot (rule 15), as indices into its four values. */
+#define BWAMS_PILEUP_EV_DEL   0
+#define BWAMS_PILEUP_EV_INS   1
+#define BWAMS_PILEUP_EV_OTHER 2
+#define BWAMS_PILEUP_SPAN_N   0
+#define BWAMS_PILEUP_SPAN_Q   1
+#define BWAMS_PILEUP_SPAN_HOM 2
+#define BWAMS_PILEUP_SPAN_HET 3
+#define BWAMS_PILEUP_INDEL_MAX 32
+
+/* One indel call (rule 17): the region's index in the handle's list, the anchor's position on the region's reference, the anchor's
+ * reference base (0..3), the ALT allele (type 0 or 1, len, seq as rule 14 packs it; 0 for a deletion), gt (1 het, 2 hom-alt), QUAL,
+ * GQ, rule 16's depth, the spanning reads, the ALT's events and the other events, pl of RR RA AA, and for a deletion the reference
+ * codes 0..4 of the len deleted positions (0 elsewhere).  reserved is 0. */
+typedef struct bwams_pileup_indel {
+    int32_t  region, pos, ref, type, len, reserved;
+    uint64_t seq;
+    int32_t  gt, qual, gq;
+    uint32_t depth, n_ref, n_alt, n_other;
+    int32_t  pl[3];
+    uint8_t  del_ref[BWAMS_PILEUP_INDEL_MAX];
+} bwams_pileup_indel_t;
+
+/* One allele group of a slot (rule 16): the anchor, (type, len, seq), the events n and the sums of qe, T_HOM[qe] and T_HET[qe]. */
+typedef struct bwams_pileup_indel_allele {
+    int32_t  region, pos, type, len;
+    uint64_t seq;
+    uint64_t n, q, hom, het;
+} bwams_pileup_indel_allele_t;
+
+/* bwams_pileup_indel_info: the events held and the capacity of their buffer in events, and of the last add the events appended and
+ * the device time of the indel kernels (the count pass and the event pass); for tests and measurement only, as bwams_pileup_info. */
+typedef struct bwams_pileup_indel_info {
+    int64_t n_events, cap_events, n_appended;
+    float   ms_indel;
+    int32_t reserved;
+} bwams_pileup_indel_info_t;
+
 /* Alignment QC (include/bwams.h, "Alignment QC").  A QC handle lives on one device. */
 typedef struct bwams_qc bwams_qc_t;
 
