@@ -31,7 +31,7 @@ SYMBOLS = [
     "bwams_seed_upload", "bwams_seed_run", "bwams_seed_counts", "bwams_seed_fetch",
     "bwams_ert_from_host", "bwams_ert_open", "bwams_ert_close", "bwams_ert_bytes", "bwams_ert_set_fat", "bwams_seed_run_ert",
     "bwams_ert_build", "bwams_ert_info", "bwams_ert_fetch", "bwams_ert_save", "bwams_debug_sort", "bwams_debug_regs_upload", "bwams_debug_aln_lists",
-    "bwams_debug_ext_regs_upload", "bwams_debug_dedup_counts", "bwams_debug_pair_regs_upload", "bwams_debug_pair_counts", "bwams_debug_chain_counts",
+    "bwams_debug_ext_regs_upload", "bwams_debug_dedup_counts", "bwams_debug_pair_regs_upload", "bwams_debug_pair_counts", "bwams_debug_chain_counts", "bwams_debug_chain_lane_counts",
     "bwams_emf_build", "bwams_emf_info", "bwams_emf_table_fetch", "bwams_emf_save",
     "bwams_bsw_extend", "bwams_bsw_upload", "bwams_bsw_run", "bwams_bsw_fetch",
     "bwams_batch_stats", "bwams_batch_sync", "bwams_ksw_align",
@@ -1339,6 +1339,7 @@ def lib():
         L.bwams_debug_pair_regs_upload.argtypes = [vp, vp, i64, vp, i64]
         L.bwams_debug_pair_counts.argtypes = [vp, vp]
         L.bwams_debug_chain_counts.argtypes = [vp, vp]
+        L.bwams_debug_chain_lane_counts.argtypes = [vp, vp]
         L.bwams_index_build_fma.argtypes = [vp, C.c_int, C.c_int]
         L.bwams_index_set_fma.argtypes = [vp, vp, C.c_int, vp, C.c_int]
         L.bwams_index_fetch_fma.argtypes = [vp, vp, vp]
@@ -1943,6 +1944,13 @@ class Batch:
         cnt = np.zeros(len(self.CHAIN_COUNTS), np.int64)
         _chk(lib().bwams_debug_chain_counts(self.h, _p(cnt)), "bwams_debug_chain_counts")
         return dict(zip(self.CHAIN_COUNTS, cnt.tolist()))
+
+    def debug_chain_lane_counts(self):
+        """Test hook: (reads of the lane tier, those among them that gave the leaf form up) of the last chain_run /
+        chain_run_ert (include/bwams.h)."""
+        cnt = np.zeros(2, np.int64)
+        _chk(lib().bwams_debug_chain_lane_counts(self.h, _p(cnt)), "bwams_debug_chain_lane_counts")
+        return int(cnt[0]), int(cnt[1])
 
     DEDUP_COUNTS = ("triage", "lane", "wave128", "wave512", "wave2048", "one_lane", "shortcut", "hbm", "lds", "reg1", "reg2", "reg3", "reg4", "early")
 

@@ -208,6 +208,7 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
     const bool count_ch = knobs().chain_count != 0;       // tests: reads per filter route, passes of chain_seeds_batch (bwams_debug_chain_counts)
     if (count_ch) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg + 61, 0, 4 * sizeof(unsigned long long), st));
     BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_overflow, 0, 29 * sizeof(unsigned long long), st));   // overflow, longread, n_heavy, chain_class[10], chain_ticket[10], heavy_tickets[6]
+    BWAMS_HIP(hipMemsetAsync(&b->d_ctr.p->chain_lane_giveup, 0, sizeof(unsigned long long), st));
     // mem_chain_seeds' loop guard `pos < num_smem - 1` (bwamem.cpp:819) makes a work item with exactly
     // one SMEM produce no chain at all
     if ((sv.one_smem_quirk ? sv.n_smem <= 1 : sv.n_smem <= 0) || n_sa == 0) {
@@ -267,6 +268,9 @@ static int chain_common(bwams_batch *b, const bwams_mem_opt_t *opt, const SeedVi
         c[20] = count_ch ? (int64_t)h->dbg[16] : -1; c[21] = count_ch ? (int64_t)h->dbg[17] : -1;
         c[22] = count_ch ? (int64_t)h->dbg[61] : -1; c[23] = count_ch ? (int64_t)h->dbg[63] : -1;
         c[24] = count_ch ? (int64_t)h->dbg[64] : -1; c[25] = count_ch ? (int64_t)h->dbg[62] : -1;
+        const bool chained = !((sv.one_smem_quirk ? sv.n_smem <= 1 : sv.n_smem <= 0) || n_sa == 0);      // (else no kernel ran)
+        s->ch.lane_counts[0] = chained ? nseq - (int64_t)h->chain_class[5] : 0;
+        s->ch.lane_counts[1] = (int64_t)h->chain_lane_giveup;
         s->ch.ran = true;
     }
     const bool has_long = b->h_ctr.p->chain_longread != 0;
@@ -309,6 +313,16 @@ int bwams_debug_chain_counts(bwams_batch_t *b, int64_t counts[26]) {
         return BWAMS_ERR_ARG;
     }
     for (int i = 0; i < kChainCounts; ++i) counts[i] = b->stages->ch.counts[i];
+    return BWAMS_OK;
+}
+
+/* Test hook: the lane tier of the last chaining run (include/bwams.h). */
+int bwams_debug_chain_lane_counts(bwams_batch_t *b, int64_t counts[2]) {
+    if (!counts || !has(b, Product::chains) || !b->stages->ch.ran) {
+        set_last_error("bwams_debug_chain_lane_counts: no bwams_chain_run / bwams_chain_run_ert on this batch");
+        return BWAMS_ERR_ARG;
+    }
+    counts[0] = b->stages->ch.lane_counts[0]; counts[1] = b->stages->ch.lane_counts[1];
     return BWAMS_OK;
 }
 

@@ -9,8 +9,8 @@
 //
 // The work is sequential per read (each seed is tested against the chain found by an ordered
 // lookup; then the read's chains are sorted and filtered pairwise) and reads are independent.
-//   chain_kernel        one lane per read with few seeds: chaining, chain weights; for reads with
-//                       few chains also the sort and the filter.
+//   chain_lane_kernel   (chain_lane.hip) one lane per read with few seeds: chaining, chain weights, the sort
+//                       and the filter, on the chip while the read's tree is one leaf; else chain_read<false>.
 //   chain_wave_kernel   one wave per read with many seeds, heaviest reads first: the same code run
 //                       in lockstep by 64 lanes (uniform loads = one request; lane 0 stores), the
 //                       chain records and an ordered array of chain positions in LDS; a read in
@@ -36,6 +36,12 @@
 #include "chain_kernels.h"
 #include "wave_ops.h"
 #include "ksort.h"
+
+// chain_count.hip and chain_lane.hip compile this file once more, each for its own kernels: the stage's other kernels, its
+// launchers and host helpers are this translation unit's alone
+#if defined(BWAMS_CHAIN_COUNT_TU) || defined(BWAMS_CHAIN_LANE_TU)
+#define BWAMS_CHAIN_PART_TU
+#endif
 
 namespace bwams {
 namespace {
@@ -432,7 +438,7 @@ __device__ __forceinline__ uint4 make_rec(const ChainArgs &A, const ChainRec &c,
     return make_uint4((uint32_t)c.first_qbeg, (uint32_t)(c.last_qbeg + c.last_len), w | alt, 0xffffffffu);
 }
 
-#ifndef BWAMS_CHAIN_COUNT_TU            // (chain_count.hip compiles this file for its counting instances only: see launch_chain)
+#ifndef BWAMS_CHAIN_PART_TU             // (chain_count.hip compiles this file for its counting instances only: see launch_chain)
 // ---- the chaining kernel: one lane per read --------------------------------------------------
 // lane per read: the read's slice of the sorted SMEM array and its seed count (the sort key that
 // groups reads of similar cost into the same wave)
@@ -806,7 +812,7 @@ __device__ bool chain_seeds_batch(const ChainArgs &A, const SeedCtx &S, int &n_k
     return true;
 }
 
-__device__ void heavy_read(const ChainArgs &A, int64_t r, int64_t base, int n_chn, unsigned char *lds, int cap, int lane);
+[[maybe_unused]] __device__ void heavy_read(const ChainArgs &A, int64_t r, int64_t base, int n_chn, unsigned char *lds, int cap, int lane);
 __host__ __device__ constexpr size_t heavy_lds_bytes(int cap);
 // CONT = 0: kbtree (exact for any input); CONT = 1: sorted array, returns false when the read needs the B-tree
 // COUNT (BWAMS_CHAIN_COUNT=1, bwams_debug_chain_counts): the reads whose sort and filter run in the chaining wave's LDS go to ctr->dbg[16],
@@ -1066,15 +1072,8 @@ __device__ __forceinline__ bool chain_read(const ChainArgs &A, int64_t r, int la
     return true;
 }
 
-// reads with few seeds: one lane per read, state in HBM scratch
-template <bool COUNT>
-__global__ __launch_bounds__(64) void chain_kernel(ChainArgs A, const uint32_t *__restrict__ n_seeds) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= A.nseq) return;
-    if (n_seeds[r] > (uint32_t)kLaneSeeds) return;          // a wave kernel's
-    chain_read<false, 0, false, COUNT>(A, r, 0, 1, nullptr, 0, nullptr, 0);
-}
-
+// (reads with few seeds, one lane per read: chain_lane.hip, which compiles this file for chain_read<false> and its helpers alone)
+#ifndef BWAMS_CHAIN_LANE_TU
 // reads with many seeds: one wave (= one block) per read, B-tree and chain records in LDS.  The reads
 // order[lo .. hi) (sorted by descending seed count, so a size class is a range) are handed out by ticket.
 // K = 0: no LDS (reads too large for a CU's LDS): state in HBM scratch.
@@ -1327,7 +1326,8 @@ __global__ __launch_bounds__(64) void chain_heavy_kernel(ChainArgs A, const unsi
     }
 }
 
-#ifndef BWAMS_CHAIN_COUNT_TU
+#endif                                  // BWAMS_CHAIN_LANE_TU
+#ifndef BWAMS_CHAIN_PART_TU
 // flat chain and seed records.  Sixteen lanes per read, a lane per kept chain (sixteen chains a trip): the chains' seed offsets are a
 // prefix sum of their seed counts inside the group, and every lane walks its own chain's seed list — a lane per read took the chains
 // one after the other, three dependent loads each before the first seed (1.8 ms per million reads; 4.4 on the grch38_like genome)
@@ -1417,7 +1417,7 @@ __global__ __launch_bounds__(64) void flt_sort_test_kernel(const uint2 *__restri
 
 }  // namespace
 
-#ifndef BWAMS_CHAIN_COUNT_TU
+#ifndef BWAMS_CHAIN_PART_TU
 size_t chain_node_bytes(int64_t n_sa, int64_t nseq) { return (size_t)((n_sa >> 1) + 2 * nseq + 4) * sizeof(Node); }
 size_t chain_rec_bytes(int64_t n_sa) { return (size_t)(n_sa > 0 ? n_sa : 1) * sizeof(ChainRec); }
 
@@ -1428,6 +1428,7 @@ void launch_chain_count(const ChainArgs &A, uint32_t *keys, uint32_t *vals, hipS
     chain_count_kernel<<<(unsigned)((A.nseq + 255) / 256), 256, 0, st>>>(A, keys, vals);
 }
 #endif
+#ifndef BWAMS_CHAIN_LANE_TU
 // The tiers are independent of each other: they run concurrently on the auxiliary streams (forked from
 // and joined back into the batch's stream), the filter of the many-chain reads after all of them.
 // COUNT: the instances that count into ctr->dbg (bwams_debug_chain_counts); a production launch runs the ones without any counting code.
@@ -1465,7 +1466,7 @@ static int launch_chain_t(const ChainArgs &A, const uint32_t *n_seeds, int cu_co
     chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 8), 64, lds_bytes(kClassM1), aux[2]>>>(A, cls + 3, cls + 4, tk + 4, kClassM1);
     chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 12), 64, lds_bytes(kClassS), aux[3]>>>(A, cls + 4, cls + 5, tk + 5, kClassS);
     // (the lane tier on the batch's own stream behind class XL2 instead: 19.1 -> 20.3 ms on the uniform genome, 50 -> 54 on grch38_like)
-    chain_kernel<COUNT><<<(unsigned)((A.nseq + 63) / 64), 64, 0, aux[1]>>>(A, n_seeds);
+    launch_chain_lane(A, aux[1], COUNT);
     // class M behind the lane tier (5 ms) rather than behind class L or S (kernel trace at GRCh38 size: L 8.9-10.3 ms + M 4.3-6.7 was
     // the stage's longest stream; S 7.8, L1 7.7 + M1 2.9, XL 0.9 + 7.2)
     // (round 4: on the stream of class L, the shortest; aux[4] shares a hardware queue with class S's stream, 16 ms on a repeat-rich genome)
@@ -1529,5 +1530,6 @@ int launch_flt_sort_test(const int64_t *w, int n, int mode, int32_t *order) {
     return 0;
 }
 #endif
+#endif                                  // BWAMS_CHAIN_LANE_TU
 
 }  // namespace bwams

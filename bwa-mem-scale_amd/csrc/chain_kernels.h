@@ -45,6 +45,8 @@ size_t chain_rec_bytes(int64_t n_sa);
 void launch_chain_count(const ChainArgs &A, uint32_t *keys, uint32_t *vals, hipStream_t st);
 int launch_chain(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux,
                  hipEvent_t fork, hipEvent_t *join, bool count);      // count: the kernel instances that count routes and passes (chain.hip)
+// the lane tier (chain_lane.hip): the reads of at most kLaneSeeds seeds, A.order[ctr->chain_class[5] .. nseq), a lane each
+void launch_chain_lane(const ChainArgs &A, hipStream_t st, bool count);
 void launch_chain_emit(const ChainArgs &A, const int64_t *chain_off, const int64_t *seed_off, bwams_chain_t *chains,
                        bwams_chain_seed_t *seeds, hipStream_t st);
 // test hook (bwams_debug_sort, which = 2): the chain filter's sort of n <= 1024 weights on the current device

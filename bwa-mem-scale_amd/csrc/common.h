@@ -185,6 +185,7 @@ struct DevCounters {
     unsigned long long bwd_items, bwd_entries, bwd_ticket;   // SMEM search: backward phases handed to the wave kernel, their list entries, its work cursor
     unsigned long long bwd_items_s, bwd_ticket_s;            // ... the short lists (smem_bwd_group_kernel): slots handed out, work cursor
     unsigned long long pair_full, pair_fail;   // mate rescue: reads redone with every orientation planned; reads the second pass could not finish (never expected)
+    unsigned long long chain_lane_giveup;      // chaining: lane-tier reads that outgrew the leaf form and were chained again through the B-tree in HBM
 };
 
 struct StageState;                       // a batch's state behind seeding, stage by stage (stage_state.h)

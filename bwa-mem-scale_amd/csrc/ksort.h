@@ -33,12 +33,14 @@ template <class T, class LT> __device__ __forceinline__ void ks_combsort(T *a, i
     if (gap != 1) ks_insertsort(a, 0, n, lt);
 }
 // depth0 > 0 replaces the 2 ceil(log2 n) depth budget (tests reach the comb-sort fallback on any input with it)
-template <class T, class LT> __device__ __forceinline__ void ks_introsort(T *a, int n, LT lt, int depth0 = 0) {
+// STK: entries of the explicit stack.  Only a part of more than 16 elements is ever pushed, so a caller that knows n <= 17 passes 1
+// and keeps the three arrays (480 B per lane) out of scratch memory.
+template <int STK = 40, class T, class LT> __device__ __forceinline__ void ks_introsort(T *a, int n, LT lt, int depth0 = 0) {
     if (n < 1) return;
     if (n == 2) { if (lt(a[1], a[0])) { const T x = a[0]; a[0] = a[1]; a[1] = x; } return; }
     int d;
     for (d = 2; (1ul << d) < (unsigned long)n; ++d);
-    int stk_l[40], stk_r[40], stk_d[40], top = 0;
+    int stk_l[STK], stk_r[STK], stk_d[STK], top = 0;
     int s = 0, t = n - 1;
     d <<= 1;
     if (depth0 > 0) d = depth0;

@@ -22,6 +22,7 @@ struct StageState {
         DevBuf<> et_srt;                     // 24-byte sort records (ert_chain.hip)
         int64_t n_chains = 0, n_seeds = 0, nseq = 0, n_redo = 0;
         int64_t counts[kChainCounts] = {};   // bwams_debug_chain_counts: of the last bwams_chain_run / _run_ert
+        int64_t lane_counts[2] = {};         // bwams_debug_chain_lane_counts: reads of the lane tier, those that gave the leaf form up
         bool ran = false;                    // ... there was one (bwams_chain_upload clears it)
     } ch;
     struct ExtStage {                        // chain -> alignment regions

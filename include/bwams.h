@@ -704,6 +704,13 @@ int bwams_debug_pair_regs_upload(bwams_batch_t *b, const bwams_alnreg_t *regs, i
  * settled, [24] chains they started, [25] seeds taken one at a time instead.  A refused run leaves nothing to report. */
 int bwams_debug_chain_counts(bwams_batch_t *b, int64_t counts[26]);
 
+/* Test hook (not part of the drop-in surface): the lane tier of the last bwams_chain_run / bwams_chain_run_ert on this batch
+ * (BWAMS_ERR_ARG when bwams_debug_chain_counts would refuse).  counts[0]: reads of at most 32 seeds, the ones without a seed
+ * included — a lane each chains them with the B-tree's root leaf in registers and the chain records in LDS; counts[1]: those
+ * among them that needed a tenth chain, gave that form up and were chained again, from their first seed, with the B-tree in
+ * global memory.  Counted in every run. */
+int bwams_debug_chain_lane_counts(bwams_batch_t *b, int64_t counts[2]);
+
 /* Test hook (not part of the drop-in surface): what the last bwams_pair_run / bwams_pair_run_sam on this batch did, when it ran
  * with BWAMS_PAIR_COUNT=1 (BWAMS_ERR_ARG otherwise; a run without the variable launches kernel instances that hold no counting
  * code).  Mate rescue, visits of a read's list per route (a read the second pass redoes is visited in both passes and counted in

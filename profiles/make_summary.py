@@ -37,7 +37,7 @@ def short(k):
                       ("key_hist", "key_hist_kernel (index build)"), ("sa_sample", "sa_sample_kernel (index build)"),
                       ("chain_count", "chain_count_kernel"), ("chain_wave", "chain_wave_kernel (wave per read, LDS state; 6 size classes)"),
                       ("chain_heavy", "chain_heavy_kernel (sort + filter of many-chain reads)"),
-                      ("chain_emit", "chain_emit_kernel"), ("chain_kernel", "chain_kernel (lane per read)"),
+                      ("chain_emit", "chain_emit_kernel"), ("chain_kernel", "chain_kernel (lane per read)"), ("chain_lane", "chain_lane_kernel (lane per read, leaf on the chip)"),
                       ("ext_plan", "ext_plan_kernel"), ("ext_build", "ext_build_kernel (task construction)"),
                       ("ext_post", "ext_post_kernel"), ("ext_select_wave", "ext_select_wave_kernel (selection / purge, wave per read)"),
                       ("ext_select", "ext_select_kernel (selection / purge, lane per read)"),
