@@ -66,7 +66,7 @@ SYMBOLS = [
     "bwams_pileup_set_ref_index", "bwams_pileup_fetch", "bwams_pileup_sites", "bwams_pileup_text", "bwams_pileup_info", "bwams_sorter_set_pileup",
     "bwams_pileup_set_quality", "bwams_pileup_fetch_quality", "bwams_pileup_calls", "bwams_pileup_vcf",
     "bwams_pileup_set_indels", "bwams_pileup_fetch_span", "bwams_pileup_indel_alleles", "bwams_pileup_indel_calls", "bwams_pileup_indel_vcf",
-    "bwams_pileup_vcf_all", "bwams_pileup_indel_info",
+    "bwams_pileup_vcf_all", "bwams_pileup_indel_info", "bwams_pileup_set_indel_leftalign",
     "bwams_qc_open", "bwams_qc_close", "bwams_qc_reset", "bwams_qc_add_batch", "bwams_qc_add_records", "bwams_qc_summary", "bwams_qc_table",
     "bwams_qc_text", "bwams_qc_info", "bwams_sorter_set_qc",
     "bwams_recal_open", "bwams_recal_close", "bwams_recal_reset", "bwams_recal_add_batch", "bwams_recal_add_records", "bwams_recal_set_ref",
@@ -759,6 +759,10 @@ class Pileup(_Consumer):
         o = PileupIndelOpt(min_qual, min_depth, indel_q, max_len, 0)
         _chk(lib().bwams_pileup_set_indels(self.h, C.byref(o)), "bwams_pileup_set_indels")
 
+    def set_indel_leftalign(self, on: bool = True) -> None:
+        """bwams_pileup_set_indel_leftalign: rule 18 for the adds that follow; needs the store, zero counters, and the reference before the records."""
+        _chk(lib().bwams_pileup_set_indel_leftalign(self.h, int(on)), "bwams_pileup_set_indel_leftalign")
+
     def fetch_span(self, region: int, beg: int | None = None, end: int | None = None) -> np.ndarray:
         """uint32[end - beg, 4]: SPAN_N, SPAN_Q, SPAN_HOM, SPAN_HET of positions [beg, end) of the region (default: all of it)."""
         r, b, e = self.regions[region]
@@ -1290,6 +1294,7 @@ def lib():
         L.bwams_pileup_calls.argtypes = [vp, i32, i32, vp, i64, vp]
         L.bwams_pileup_vcf.argtypes = [vp, vp, C.c_char_p, i32, i32, vp, i64, vp]
         L.bwams_pileup_set_indels.argtypes = [vp, vp]
+        L.bwams_pileup_set_indel_leftalign.argtypes = [vp, i32]
         L.bwams_pileup_fetch_span.argtypes = [vp, i32, i32, i32, vp]
         L.bwams_pileup_indel_alleles.argtypes = [vp, vp, i64, vp]
         L.bwams_pileup_indel_calls.argtypes = [vp, i32, i32, vp, i64, vp]

@@ -15,8 +15,14 @@ indel_calls, indel_vcf and vcf_all restate rules 14 to 17 (csrc/pileup_indel.hip
  16. At a slot with reference base < 4 the events group by (type, len, seq); ALT is the type-0 or type-1 group of largest n, the first
      in that order on a tie; cost(RR) = SPAN_HOM + MIS_ALT, cost(RA) = SPAN_HET + HET_ALT, cost(AA) = SPAN_MIS + HOM_ALT with
      MIS = 100 Q + 477 n; pl, genotype, qual and gq as rule 13; depth = SPAN_N + n_ALT + n_other; a call when the genotype is not RR,
-     qual >= min_qual and depth >= min_depth.  No realignment, no left-normalisation, no model of repeats, strands or mate overlap.
+     qual >= min_qual and depth >= min_depth.  No realignment, no model of repeats, strands or mate overlap; the alleles are as the
+     CIGARs give them unless rule 18 is on.
  17. INDEL_DTYPE and INDEL_ALLELE_DTYPE records; the VCF rows with INFO DP=depth;INDEL, and vcf_all's merge, the SNV first at a slot.
+ 18. Left-alignment (set_indel_leftalign; the reference before the records).  A DEL or INS event (rule 14's type, taken first) of
+     length L >= 1 at anchor a in region [beg, end): X is the reference up to a, then the reference (DEL) or the inserted bases (INS);
+     k is the largest shift with a - j - 1 >= beg, X[a - j] == X[a + L - j] and neither an N, for every j < k.  The event is stored at
+     a - k, an insertion's sequence as X[a - k + 1 .. a - k + L].  When the op directly before the event's op is M, = or X, the record
+     does not span the slots of [a - k, a) that lie in that run.  Nothing else moves: not the DEL and INS channels, not an earlier run.
 """
 from __future__ import annotations
 
@@ -102,9 +108,12 @@ class Pileup:
         self.ref = np.full(self.n_slots, 4, np.uint8)                                    # rule 7
         self.q = None                                                                    # rule 11's plane: none before set_quality
         self.span = None                                                                 # rule 15's sums: none before set_indels
+        self.leftalign = False                                                           # rule 18: off before set_indel_leftalign
+        self.ref_set = [False] * len(regions)                                            # ... which wants every region's bases before an add
         self.reset()
 
     def reset(self):                                                                     # rule 6
+        self.dirty = False                                                               # an add since the open or the last reset
         self.c = np.zeros((self.n_slots, 12), np.int64)
         if self.q is not None:
             self.q = np.zeros((self.n_slots, 12), np.int64)
@@ -119,9 +128,27 @@ class Pileup:
         self.indel_min_qual, self.indel_min_depth, self.indel_q, self.max_len = min_qual, min_depth, indel_q, max_len
         self.span = np.zeros((self.n_slots, 4), np.int64)
         self.events = []
+        self.leftalign = False                                                           # the call replaces the store's options
+
+    def set_indel_leftalign(self, on: bool = True):
+        """rule 18 for the adds that follow; only on a handle with the store and while the counters are zero (BWAMS_ERR_ARG otherwise)"""
+        assert self.span is not None and not self.dirty and on in (0, 1)
+        self.leftalign = bool(on)
+
+    def _shift(self, s: int, beg_slot: int, is_ins: bool, n: int, seq: int):
+        """rule 18's k and the sequence at the new anchor, one base at a time; s: the anchor's slot, beg_slot: its region's first.
+        Inside a region the slots are the positions, so X is indexed by slot."""
+        def X(t):
+            return int(self.ref[t]) if t <= s or not is_ins else seq >> (2 * (t - s - 1)) & 3
+        k = 0
+        while s - k - 1 >= beg_slot and X(s - k) != 4 and X(s + n - k) != 4 and X(s - k) == X(s + n - k):
+            k += 1
+        if is_ins:
+            seq = sum(X(s - k + 1 + i) << (2 * i) for i in range(n))
+        return k, seq
 
     def _indels_of(self, refid, pos, mapq, cigar, codes):
-        """rules 14 and 15 for one counted record"""
+        """rules 14 and 15 for one counted record, and rule 18 on a left-aligning handle"""
         qe = min(max(min(mapq, self.indel_q), GL_MIN_Q), GL_MAX_Q)
         add = np.array([1, qe, T_HOM[qe - GL_MIN_Q], T_HET[qe - GL_MIN_Q]], np.int64)
         slot, l_ref = self.slot[refid], self.l_ref[refid]
@@ -143,6 +170,12 @@ class Pileup:
                             kind = EV_OTHER
                             break
                         seq |= int(_CHANNEL_OF_CODE[code]) << (2 * j)
+                if self.leftalign and kind != EV_OTHER and n > 0:                        # rule 18
+                    shift, seq = self._shift(s, int(self.off[k]), op == 1, n, seq)
+                    if run is not None:                                                  # the op before is M, = or X: its run ends at the anchor
+                        gone = max(min(shift, x - 1 - run[0]), 0)                        # [max(a - k, the run's first position), a)
+                        self.span[s - gone:s] -= add
+                    s -= shift
                 self.events.append((s, kind, 0, 0, qe, op == 1) if kind == EV_OTHER else (s, kind, n, seq, qe, op == 1))
             if op in (0, 7, 8):
                 run = [x, x + n] if run is None else [run[0], x + n]
@@ -187,6 +220,7 @@ class Pileup:
 
     def add(self, records: bytes) -> int:
         """Every record of `records`; -> the number that counted.  Check first, then add (rule 3)."""
+        assert not self.leftalign or all(self.ref_set), "rule 18: every region's reference before the records (BWAMS_ERR_ARG)"
         recs = [fields(r) for r in bam.split_records(records)]
         for k, (refid, _, mapq, flag, cigar, l_seq, codes, _) in enumerate(recs):
             if any(op > 8 for _, op in cigar):
@@ -197,6 +231,7 @@ class Pileup:
                 if len(codes) != l_seq:                                                  # SEQ or QUAL ends behind the record
                     raise PileupRefusal(k, "bounds")
         n_counted = 0
+        self.dirty = self.dirty or len(recs) > 0
         for refid, pos, mapq, flag, cigar, l_seq, codes, qual in recs:
             if not self.counts(refid, mapq, flag, cigar, l_seq):
                 continue
@@ -233,7 +268,9 @@ class Pileup:
         r, b, e = self.regions[region]
         codes = np.asarray(codes, np.uint8)
         assert len(codes) == e - b and (codes <= 4).all()
+        assert not (self.leftalign and self.dirty), "rule 18: the events held were aligned against the bases in place (BWAMS_ERR_ARG)"
         self.ref[self.off[region]:self.off[region + 1]] = codes
+        self.ref_set[region] = True
 
     def set_ref_genome(self, genome_by_ref):
         """every region's bases from one code array per reference (what _set_ref_index gathers)"""

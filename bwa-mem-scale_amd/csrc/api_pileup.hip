@@ -51,6 +51,11 @@ struct bwams_pileup : RecConsumer {
     int64_t n_events = 0, ev_cap = 0, n_appended = 0, n_groups = 0;
     bool span_valid = false, groups_valid = false;   // span and the groups answer for everything added: an add or a _reset clears both
     float ms_indel = 0;                              // the indel kernels of the last add
+    // Rule 18; off before bwams_pileup_set_indel_leftalign.
+    bool leftalign = false;
+    std::vector<uint8_t> ref_set;                    // per region: a _set_ref* has given its bases
+    DevBuf<uint32_t> ev_run;                         // transient, per event of an add: the slots below its anchor that the run ending there spans
+    bool ref_complete() const { return std::find(ref_set.begin(), ref_set.end(), 0) == ref_set.end(); }
     PileupIndelStore store(unsigned long long *n) const { return PileupIndelStore{diff.p, ev_keys.p, ev_qe.p, n, ev_cap, io.indel_q, io.max_len}; }
     size_t diff_bytes() const { return ((size_t)n_slots() + 1) * 16; }
     int32_t n_ref() const { return (int32_t)l_ref.size(); }
@@ -115,6 +120,7 @@ int indel_reserve(bwams_pileup *p, const DevRecords &recs, const PileupFilter &f
         p->ev_qe = std::move(qe);
         p->ev_cap = cap;
     }
+    if (p->leftalign) BWAMS_HIP(p->ev_run.ensure_n((size_t)(p->ev_cap - p->n_events)));       // a word for every event the buffer has room for
     *n_new = (int64_t)count;
     return BWAMS_OK;
 }
@@ -127,6 +133,10 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
     if (p->n_added + n_rec > 0x7FFFFFFFLL) {
         set_last_error(std::string(who) + ": more than 2^31 - 1 records added in total");
         return BWAMS_ERR_UNSUPPORTED;
+    }
+    if (p->leftalign && !p->ref_complete()) {                            // rule 18 shifts against the bases in place
+        set_last_error(std::string(who) + ": a left-aligning handle needs every region's reference bases (bwams_pileup_set_ref*) before the records");
+        return BWAMS_ERR_ARG;
     }
     hipStream_t st = p->stream;
     int64_t sum[3] = {0, 0, 0};
@@ -189,7 +199,13 @@ int pileup_add(bwams_pileup *p, const DevRecords &recs, int64_t *n_counted, cons
         if (p->indels) {                                                 // the events and the span runs of every record of the call
             p->span_valid = p->groups_valid = false;
             if (int rc = timed(p, &p->ms_indel, [&] {
-                    launch_pileup_indel_events(dev_bam, dev_off, n_rec, f, R, p->store(p->ev_n.p), 1, p->cu_count, st);
+                    if (!p->leftalign) {
+                        launch_pileup_indel_events(dev_bam, dev_off, n_rec, f, R, p->store(p->ev_n.p), 1, p->cu_count, st);
+                        return;
+                    }
+                    launch_pileup_indel_events_run(dev_bam, dev_off, n_rec, f, R, p->store(p->ev_n.p), p->ev_run.p, p->n_events, p->cu_count, st);
+                    launch_pileup_indel_align(R, p->n_regions(), p->ref.p, p->ev_keys.p + p->n_events, p->ev_qe.p + p->n_events, p->ev_run.p,
+                                              n_events_new, p->diff.p, p->cu_count, st);      // rule 18 over the events just appended
                 })) return rc;
             p->n_events += n_events_new;
             p->n_appended = n_events_new;
@@ -374,6 +390,7 @@ int bwams_pileup_open(int device, const int32_t *l_ref, int32_t n_ref, const bwa
         for (int32_t r = 0; r < n_ref; ++r)
             if (l_ref[r] > 0) p->regions.push_back(bwams_pileup_region_t{r, 0, l_ref[r]});
     const size_t n_reg = p->regions.size();
+    p->ref_set.assign(n_reg, 0);
     std::vector<int32_t> beg(n_reg), end(n_reg), reg_ref(n_reg), ref_first((size_t)n_ref + 1, 0);
     p->reg_off.assign(n_reg + 1, 0);
     for (size_t k = 0; k < n_reg; ++k) {
@@ -451,15 +468,24 @@ int bwams_pileup_set_ref(bwams_pileup_t *p, int32_t region, const uint8_t *codes
             set_last_error("bwams_pileup_set_ref: code " + std::to_string(k) + " is above 4");
             return BWAMS_ERR_ARG;
         }
+    if (p->leftalign && !p->clean) {                                     // rule 18: the events held were shifted against the bases in place
+        set_last_error("bwams_pileup_set_ref: a left-aligning handle takes its reference before the first add, or directly after bwams_pileup_reset");
+        return BWAMS_ERR_ARG;
+    }
     BWAMS_HIP(hipSetDevice(p->device));
     BWAMS_HIP(hipMemcpyAsync(p->ref.p + p->reg_off[(size_t)region], codes, (size_t)n, hipMemcpyHostToDevice, p->stream));
     BWAMS_HIP(hipStreamSynchronize(p->stream));
+    p->ref_set[(size_t)region] = 1;
     return BWAMS_OK;
 }
 
 int bwams_pileup_set_ref_index(bwams_pileup_t *p, const bwams_index_t *ix) {
     if (!p || !ix || ix->device != p->device || !ix->fmi.ref || !ix->d_contigs.p || ix->n_seqs != p->n_ref()) {
         set_last_error("bwams_pileup_set_ref_index: an index on the handle's device with its .0123 and the handle's n_ref contigs is required");
+        return BWAMS_ERR_ARG;
+    }
+    if (p->leftalign && !p->clean) {
+        set_last_error("bwams_pileup_set_ref_index: a left-aligning handle takes its reference before the first add, or directly after bwams_pileup_reset");
         return BWAMS_ERR_ARG;
     }
     BWAMS_HIP(hipSetDevice(p->device));
@@ -483,6 +509,7 @@ int bwams_pileup_set_ref_index(bwams_pileup_t *p, const bwams_index_t *ix) {
                       p->hole_off.p, p->hole_len.p, (int32_t)n_holes, p->ref.p, p->cu_count, st);
     BWAMS_HIP(hipStreamSynchronize(st));
     BWAMS_HIP(hipGetLastError());
+    std::fill(p->ref_set.begin(), p->ref_set.end(), 1);
     return BWAMS_OK;
 }
 
@@ -634,6 +661,20 @@ int bwams_pileup_set_indels(bwams_pileup_t *p, const bwams_pileup_indel_opt_t *o
     p->span_valid = p->groups_valid = false;
     p->io = o;
     p->indels = true;
+    p->leftalign = false;                                                // the call replaces the store's options
+    return BWAMS_OK;
+}
+
+int bwams_pileup_set_indel_leftalign(bwams_pileup_t *p, int32_t on) {
+    if (!p || !p->indels || (on != 0 && on != 1)) {
+        set_last_error("bwams_pileup_set_indel_leftalign: a handle with an indel store (bwams_pileup_set_indels) and on in {0, 1} are required");
+        return BWAMS_ERR_ARG;
+    }
+    if (!p->clean) {
+        set_last_error("bwams_pileup_set_indel_leftalign: the counters are not zero: before the first add, or directly after bwams_pileup_reset");
+        return BWAMS_ERR_ARG;
+    }
+    p->leftalign = on != 0;
     return BWAMS_OK;
 }
 

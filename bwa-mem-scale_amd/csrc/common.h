@@ -520,6 +520,13 @@ struct PileupIndelTest {                 // rule 16 over the sorted groups: grou
 // rule 15's runs to S.diff.  alleles and indel_calls: the records of the groups / of the selected first groups.
 void launch_pileup_indel_events(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, const PileupRegions &R,
                                 const PileupIndelStore &S, int emit, int cu_count, hipStream_t st);
+// rule 18: events_run is the emitting event pass that also writes run[e - first] for every event e it appends (S.cap - first words:
+// the slots below the anchor that the run of match ops ending there spans); align shifts the n events at keys / qe / run against
+// ref, rewrites their keys in place and corrects diff.
+void launch_pileup_indel_events_run(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, const PileupFilter &f, const PileupRegions &R,
+                                    const PileupIndelStore &S, uint32_t *run, int64_t first, int cu_count, hipStream_t st);
+void launch_pileup_indel_align(const PileupRegions &R, int32_t n_regions, const uint8_t *ref, PileupEvKey *keys, const uint32_t *qe,
+                               const uint32_t *run, int64_t n, uint32_t *diff, int cu_count, hipStream_t st);
 void launch_pileup_indel_alleles(const PileupEvKey *keys, const PileupEvSums *sums, int64_t n_groups, const PileupRegions &R, int32_t n_regions,
                                  bwams_pileup_indel_allele_t *out, int cu_count, hipStream_t st);
 void launch_pileup_indel_calls(const PileupIndelTest &test, const PileupRegions &R, int32_t n_regions, const int64_t *groups, int64_t n,

@@ -1310,9 +1310,11 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  *       cost(RR) = SPAN_HOM + MIS_ALT,  cost(RA) = SPAN_HET + HET_ALT,  cost(AA) = SPAN_MIS + HOM_ALT.
  *     pl, the genotype, qual = pl[RR] and gq follow rule 13: + 50 then / 100, saturating int32, a tie to the lowest of RR RA AA,
  *     gq = min(99, the least other pl).  depth = SPAN_N + n_ALT + n_other.  A slot is a CALL when the genotype is not RR, qual >=
- *     min_qual (default 20) and depth >= min_depth (default 1).  Alleles are taken as the CIGARs give them: there is NO realignment,
- *     NO left-normalisation and no model of homopolymers, tandem repeats, strands or mate overlap.  Two reads that place the same
- *     deletion one base apart are two alleles at two slots.
+ *     min_qual (default 20) and depth >= min_depth (default 1).  There is NO realignment and no model of homopolymers, tandem
+ *     repeats, strands or mate overlap.  Without rule 18 the alleles are taken as the CIGARs give them, and two reads that place the
+ *     same deletion one base apart are two alleles at two slots; with it they are one allele at the leftmost placement the
+ *     reference allows inside the region, and nothing more is done: reads are not aligned again, and two events that a read could
+ *     have expressed as one stay two.
  * 17. Records and text.  bwams_pileup_indel_calls returns the calls in slot order as bwams_pileup_indel_t records (include/bwams_types.h):
  *     region, pos (the anchor), ref, type, len, seq, gt (1 het, 2 hom-alt), qual, gq, depth, n_ref (SPAN_N), n_alt, n_other, pl[3],
  *     del_ref[32] (the reference codes 0..4 of the deleted positions, 0 elsewhere).  bwams_pileup_indel_alleles returns EVERY group
@@ -1325,6 +1327,33 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  *     spanning reads and 2 insertions of TT: cost(RR) = 8954, cost(RA) = 2107, cost(AA) = 22385.  The two rows:
  *       "c1\t4\t.\tTA\tT\t74\t.\tDP=5;INDEL\tGT:AD:DP:GQ:PL\t0/1:3,2:5:74:74,0,119\n"
  *       "c1\t6\t.\tC\tCTT\t68\t.\tDP=7;INDEL\tGT:AD:DP:GQ:PL\t0/1:5,2:7:68:68,0,203\n"
+ * 18. Left-alignment (a handle with an indel store on which bwams_pileup_set_indel_leftalign(p, 1) was called; every region's
+ *     reference bases must be in place before the records, see below).  Rule 14 classifies the event first, on the CIGAR's anchor.
+ *     An event of type DEL or INS (not OTHER) and length L >= 1 with anchor a in the region [beg, end) is then shifted.  Let X[p] be
+ *     the reference code at p for p <= a; for a deletion the reference code for p > a too; for an insertion X[a + 1 + i] is inserted
+ *     base i, i < L.  The shift k is the largest value such that for every j < k: a - j - 1 >= beg, X[a - j] == X[a + L - j], and
+ *     neither code is 4 (an N matches nothing, itself included).  The event is stored at a' = a - k with its type and length; an
+ *     insertion's sequence becomes X[a' + 1 .. a' + L], packed as rule 14 packs it (the inserted bases rotated by k modulo L).  An
+ *     event of length 0 and an OTHER event are stored as rule 14 has them.  The shift NEVER LEAVES THE ANCHOR'S REGION, even where
+ *     another region ends at beg: a region that begins inside a repeat gives that region's leftmost placement, not the genome's.
+ *     A shift that runs into an N ends with the N as the anchor (the test that fails is the one that reads it), where rule 16 makes
+ *     no call; the allele record still shows the event there.
+ *     Span sums: when the op directly before the event's op is M, = or X, that run of match ops ends at a, and the record does NOT
+ *     span the slots s with a' <= s < a that rule 15 gave it through that run; rule 15 holds everywhere else.  (Otherwise a read
+ *     whose deletion moved left would be reference support at the slot where it is now ALT.)  Only that run is clipped: an event
+ *     behind any other op (N, D, P, or the second of two adjacent I and D ops) clips nothing, and earlier runs of the record are
+ *     left alone even where the shift crosses them.  The sums stay modulo 2^32 and no sum goes below zero: what is taken back was
+ *     added by the same record.  The DEL and INS channels of rule 4 stay where the CIGAR put them.  Rules 16 and 17 are unchanged
+ *     and work on the shifted events; del_ref and the VCF's REF and ALT come from the shifted anchor.  This is the reference-only
+ *     normalisation of `bcftools norm` (Tan et al. 2015) applied to each event by itself: no realignment, no repeat model.
+ *     Rule 9's records do not move under it (c1 = ACGTACGT repeats nothing), and rule 17's two rows stand as they are:
+ *       "c1\t4\t.\tTA\tT\t74\t.\tDP=5;INDEL\tGT:AD:DP:GQ:PL\t0/1:3,2:5:74:74,0,119\n"
+ *       "c1\t6\t.\tC\tCTT\t68\t.\tDP=7;INDEL\tGT:AD:DP:GQ:PL\t0/1:5,2:7:68:68,0,203\n"
+ *     Reference c2 = TCAAAAGT, MAPQ 60, three records at 0: 8M; 5M1D2M, anchor 4, which moves by 3; 3M1D4M, anchor 2, which moves
+ *     by 1.  Both deletions are one allele at slot 1; the first read's span over 0..3 shrinks to slot 0, the second's over 0..1
+ *     too, and only the 8M read spans slot 1: cost(RR) = 8954, cost(RA) = 301 + 602, cost(AA) = 4477.  The one row (without the
+ *     rule: two rows of QUAL 36 at 3 and 5):
+ *       "c2\t2\t.\tCA\tC\t81\t.\tDP=3;INDEL\tGT:AD:DP:GQ:PL\t0/1:1,2:3:36:81,0,36\n"
  * bwams_pileup_open: a zeroed handle on `device` (opt may be NULL for the defaults; exclude above 0xFFFF, min_baseq outside [0, 255],
  * min_alt < 1, min_permille outside [0, 1000], reserved != 0, n_ref < 0, a negative length or rule 1: BWAMS_ERR_ARG).  _close (NULL
  * allowed).  _add_batch: the batch's current BAM records (bwams_bam_run / _upload left them, BWAMS_ERR_ARG before either), read in
@@ -1352,6 +1381,15 @@ int bwams_sorter_set_depth(bwams_sorter_t *s, bwams_depth_t *d);
  * A handle on which it was never called behaves in every call exactly as before, and its adds launch exactly the kernels they
  * launched.  With the store, an add first counts the events its records give and grows the event buffer (16 bytes of key and 4 of
  * quality per event, the events held kept) before any counter of the call moves: BWAMS_ERR_NOMEM there adds nothing.
+ * _set_indel_leftalign: rule 18 on (1) or off (0) for the adds that follow.  Legal only on a handle with an indel store and while the
+ * counters are zero, as _set_indels (BWAMS_ERR_ARG on a handle without the store, after an add, or for any other value of `on`);
+ * _set_indels called again turns it off, since that call replaces the store's options; _reset keeps it.  A handle on which it is
+ * off behaves, and launches, exactly as one that never made the call.  On a left-aligning handle the reference comes first: an add
+ * while any region has had neither _set_ref nor _set_ref_index is BWAMS_ERR_ARG, and nothing of that call is added; _set_ref and
+ * _set_ref_index after an add and before _reset are BWAMS_ERR_ARG, because the events held were shifted against the bases in
+ * place.  (Neither refusal exists on any other handle.)  Its adds run an event pass that also notes, in four transient bytes per
+ * event sized with the event buffer before anything moves, how far the match run before the event reaches, and then
+ * pileup_indel_align_kernel over the events of that add; _indel_info's ms_indel includes both.
  * _fetch_span: rule 15's sums of positions [beg, end), four per position, as _fetch.  _indel_alleles and _indel_calls: as _sites
  * (*n found or needed, a NULL array to ask, BWAMS_ERR_CAPACITY); min_qual and min_depth as in _calls, a negative value for the
  * store's.  _indel_vcf: rule 13's header with the line ##INFO=<ID=INDEL,Number=0,Type=Flag,...> after DP, then rule 17's rows, as
@@ -1394,6 +1432,7 @@ int bwams_pileup_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, b
 int bwams_pileup_vcf(bwams_pileup_t *p, const char *names, const char *sample, int32_t min_qual, int32_t min_depth, char *out, int64_t cap,
                      int64_t *n);
 int bwams_pileup_set_indels(bwams_pileup_t *p, const bwams_pileup_indel_opt_t *opt);
+int bwams_pileup_set_indel_leftalign(bwams_pileup_t *p, int32_t on);
 int bwams_pileup_fetch_span(bwams_pileup_t *p, int32_t region, int32_t beg, int32_t end, uint32_t *sums);
 int bwams_pileup_indel_alleles(bwams_pileup_t *p, bwams_pileup_indel_allele_t *alleles, int64_t cap, int64_t *n);
 int bwams_pileup_indel_calls(bwams_pileup_t *p, int32_t min_qual, int32_t min_depth, bwams_pileup_indel_t *calls, int64_t cap, int64_t *n);

@@ -19,6 +19,12 @@ time of the indel kernels alone (bwams_pileup_indel_info: ms_indel, the count pa
 then, three times after a reset and an add, the host clock around the first bwams_pileup_fetch_span (the scan of the span sums), the
 first bwams_pileup_indel_alleles that counts (the sort and the reduction of the events) and the bwams_pileup_indel_calls that counts
 (rule 16 over the groups), each of which finds the work of the one before it cached.
+
+--tracts (with --indels): the reference has a tract of 8 to 40 bases in every 256 positions, homopolymers and 2-mers by turns, and every
+record with an event is moved so that the event lies at a random place inside one: one base in a homopolymer, two in a 2-mer, an
+insertion repeating the tract.  The reference is set before the adds.  --leftalign (implies --tracts): the handle left-aligns
+(bwams_pileup_set_indel_leftalign), so ms_indel holds the event pass that notes the runs and the align kernel too; the two switches
+on the same input are the cost of rule 18.  The indel row also gives ms_indel as a share of all the add's kernels.
 """
 from __future__ import annotations
 
@@ -61,15 +67,35 @@ def records(n: int, l_ref: int, seed: int) -> np.ndarray:
     return rec
 
 
-def with_indels(rec: np.ndarray, share: float, seed: int) -> np.ndarray:
-    """the records back to back, `share` of them with 75M1I74M or 75M1D75M in place of 150M (three CIGAR words: 8 bytes more)"""
+TRACT_EVERY, TRACT_AT = 256, 64                       # --tracts: a tract in every 256 positions of the reference, from the 64th on
+
+
+def tract_reference(l_ref: int, seed: int):
+    """reference codes uint8[l_ref], random but for a tract of 8 to 40 bases in every block of TRACT_EVERY positions: a homopolymer in
+    the even blocks, a 2-mer in the odd ones -> (codes, the tracts' lengths, their two unit codes)"""
+    rng = np.random.default_rng(seed)
+    ref = rng.integers(0, 4, l_ref, dtype=np.uint8)
+    nb = l_ref // TRACT_EVERY
+    length = rng.integers(8, 41, nb)
+    u0 = rng.integers(0, 4, nb, dtype=np.uint8)
+    u1 = np.where(np.arange(nb) % 2 == 0, u0, (u0 + rng.integers(1, 4, nb, dtype=np.uint8)) % 4).astype(np.uint8)
+    for j in range(40):
+        m = np.flatnonzero(length > j)
+        ref[TRACT_EVERY * m + TRACT_AT + j] = (u1 if j % 2 else u0)[m]
+    return ref, length, np.stack([u0, u1], 1)
+
+
+def with_indels(rec: np.ndarray, share: float, seed: int, tracts=None) -> np.ndarray:
+    """the records back to back, `share` of them with 75M1I74M or 75M1D75M in place of 150M (three CIGAR words: 8 bytes more).
+    tracts (what tract_reference returns): each such record is moved so that its event lies at a random place inside the tract of
+    its block, one base in a homopolymer, two in a 2-mer, an insertion repeating the tract in phase: events that rule 18 can move"""
     rng = np.random.default_rng(seed)
     n = len(rec)
     kind, ins = rng.random(n) < share, rng.random(n) < 0.5
     off = np.concatenate([[0], np.cumsum(np.where(kind, 275, 267))])
     out = np.zeros(int(off[-1]), np.uint8)
-    cig_i = np.frombuffer(struct.pack("<III", 75 << 4, 1 << 4 | 1, 74 << 4), np.uint8)
-    cig_d = np.frombuffer(struct.pack("<III", 75 << 4, 1 << 4 | 2, 75 << 4), np.uint8)
+    cig = {(1, 1): (75, 1, 74), (0, 1): (75, 1, 75), (1, 2): (75, 2, 73), (0, 2): (75, 2, 75)}      # (insertion, length): the three ops
+    cig = {k: np.frombuffer(struct.pack("<III", a << 4, b << 4 | (1 if k[0] else 2), c << 4), np.uint8) for k, (a, b, c) in cig.items()}
     for k in range(0, n, 1 << 18):                                                          # in pieces: the scatter indices are 8 bytes a byte
         m = min(n, k + (1 << 18))
         plain, ind = np.flatnonzero(~kind[k:m]) + k, np.flatnonzero(kind[k:m]) + k
@@ -78,8 +104,21 @@ def with_indels(rec: np.ndarray, share: float, seed: int) -> np.ndarray:
         wide[:, :38] = rec[ind, :38]
         wide[:, 0:4] = np.frombuffer(struct.pack("<I", 271), np.uint8)
         wide[:, 16] = 3
-        wide[:, 38:50] = np.where(ins[ind, None], cig_i, cig_d)
+        wide[:, 38:50] = np.where(ins[ind, None], cig[1, 1], cig[0, 1])
         wide[:, 50:] = rec[ind, 42:]
+        if tracts is not None:
+            _, length, unit = tracts
+            pos = np.ascontiguousarray(wide[:, 8:12]).view("<i4")[:, 0]
+            blk = np.clip((pos + 74) // TRACT_EVERY, 1, len(length) - 2)
+            two = blk % 2 == 1
+            n_ev = np.where(two, 2, 1)
+            at = (rng.random(len(ind)) * (length[blk] - n_ev)).astype(np.int64)             # the anchor's place in the tract; the event ends inside it
+            wide[:, 8:12] = (TRACT_EVERY * blk + TRACT_AT + at - 74).astype("<i4").view(np.uint8).reshape(-1, 4)
+            wide[:, 38:50] = np.where(two[:, None], np.where(ins[ind, None], cig[1, 2], cig[0, 2]), wide[:, 38:50])
+            b0, b1 = unit[blk, (at + 1) % 2], unit[blk, (at + 2) % 2]                       # the tract's bases behind the anchor
+            i1, i2 = ins[ind], ins[ind] & two
+            wide[i1, 50 + 37] = (wide[i1, 50 + 37] & 0xF0) | (1 << b0[i1])                 # query base 75: the low nibble of SEQ byte 37
+            wide[i2, 50 + 38] = (wide[i2, 50 + 38] & 0x0F) | (16 << b1[i2])                # query base 76: the high nibble of byte 38
         out[(off[ind, None] + np.arange(275)).ravel()] = wide.ravel()
     return out
 
@@ -92,12 +131,17 @@ def main():
     ap.add_argument("--quality", action="store_true")
     ap.add_argument("--indels", action="store_true")
     ap.add_argument("--indel-share", type=float, default=0.1)
+    ap.add_argument("--tracts", action="store_true")
+    ap.add_argument("--leftalign", action="store_true")
     a = ap.parse_args()
+    if (a.tracts or a.leftalign) and not a.indels:
+        ap.error("--tracts and --leftalign go with --indels")
     l_ref = int(a.mbp * 1e6)
     n = int(l_ref * a.coverage / 150)
     rec = records(n, l_ref, 11)
+    tracts = tract_reference(l_ref, 12) if a.tracts or a.leftalign else None
     if a.indels:
-        rec = with_indels(rec, a.indel_share, 13)
+        rec = with_indels(rec, a.indel_share, 13, tracts)
     n_bytes = rec.nbytes
     ptr = rec.ctypes.data_as(C.c_void_p)
     L = capi.lib()
@@ -111,6 +155,10 @@ def main():
             p.set_quality()
         if a.indels:
             p.set_indels()
+        if a.leftalign:
+            p.set_indel_leftalign()
+        if tracts is not None:                                                              # rule 18 wants the reference before the records
+            p.set_ref(0, tracts[0])
         cnt = C.c_int64(0)
         check, add, wall, indel = [], [], [], []
         for rep in range(a.reps + 1):                                                       # the first is the warm-up
@@ -143,9 +191,12 @@ def main():
         if a.indels:
             ii = p.indel_info()
             print(json.dumps({"indel_kernels_ms": stats(indel), "events_appended": ii["n_appended"], "events_held": ii["n_events"],
-                              "event_capacity": ii["cap_events"]}), flush=True)
+                              "event_capacity": ii["cap_events"], "leftalign": bool(a.leftalign),
+                              "of_the_add_s_kernels_pct": round(100 * float(np.median(indel)) / (float(np.median(indel)) + float(np.median(total))), 1)}),
+                  flush=True)
         if a.indels and not tiled:                                                          # the queries: the store is the same either way
-            p.set_ref(0, np.random.default_rng(12).integers(0, 4, l_ref, dtype=np.uint8))
+            if tracts is None:
+                p.set_ref(0, np.random.default_rng(12).integers(0, 4, l_ref, dtype=np.uint8))
             scan, groups, calls = [], [], []
             n_out = C.c_int64(0)
             one = np.zeros(4, np.uint32)
