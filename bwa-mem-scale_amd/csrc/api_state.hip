@@ -10,13 +10,15 @@
 
 namespace bwams {
 
-// The auxiliary streams are ONE set per device, shared by its batches (reference-counted).  A batch of its own set made 9 streams per
-// batch; the runtime maps streams onto GPU_MAX_HW_QUEUES (8) hardware queues and a queue completes its packets in order, so with
-// three batches on a device (two chunks in flight + the caller's) a slot's copies landed behind another slot's kernels or not,
-// depending on the order in which the process had created its streams (bench.py: 4.5 .. 5.6 Mreads/s streaming in a process that had
-// created other batches before, 7.3 .. 7.6 in a fresh one).  Sharing is safe: every use is fork event -> launches -> join event, and
-// a stream is a total order.
-struct AuxSet { hipStream_t q[7] = {}; int refs = 0; };
+// The auxiliary streams are ONE set per device, shared by its batches (reference-counted).  A process gets four hardware queues
+// from the runtime (the library sets nothing); the runtime puts every new stream on the least used of them, and a queue completes
+// its packets in order.  A batch with a set of its own made nine streams per batch, and with three batches on a device (two chunks
+// in flight + the caller's) a slot's copies landed behind another slot's kernels or not, depending on the order in which the
+// process had created its streams (4.5 .. 5.6 Mreads/s streaming in a process that had created other batches before, 7.3 .. 7.6
+// in a fresh one).  The set holds what the widest stage forks onto (kAuxStreams: banded SW's four); a stage that wants an order
+// between two launches puts them on one stream and does not count on two streams sharing a queue.  Sharing is safe: every use is
+// fork event -> launches -> join event, and a stream is a total order.
+struct AuxSet { hipStream_t q[kAuxStreams] = {}; int refs = 0; };
 static std::mutex g_aux_mu;
 static std::map<int, AuxSet> g_aux;
 static int aux_acquire(int device, hipStream_t *out) {
@@ -25,7 +27,7 @@ static int aux_acquire(int device, hipStream_t *out) {
     if (a.refs == 0)
         for (auto &q : a.q) BWAMS_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
     ++a.refs;
-    for (int i = 0; i < 7; ++i) out[i] = a.q[i];
+    for (int i = 0; i < kAuxStreams; ++i) out[i] = a.q[i];
     return BWAMS_OK;
 }
 static void aux_release(int device) {

@@ -1429,8 +1429,73 @@ void launch_chain_count(const ChainArgs &A, uint32_t *keys, uint32_t *vals, hipS
 }
 #endif
 #ifndef BWAMS_CHAIN_LANE_TU
-// The tiers are independent of each other: they run concurrently on the auxiliary streams (forked from
-// and joined back into the batch's stream), the filter of the many-chain reads after all of them.
+// The launch plan.  The classes are independent of each other: they run concurrently on LANES, streams forked from the batch's
+// stream and joined back into it (one event out, one event per auxiliary lane back), and the filter of the many-chain reads follows
+// in a second fork-join round on the same lanes.  A lane is a total order and a hardware queue completes its launches in order, so
+// the plan says itself which launch waits for which; nothing is left to the streams that happen to share a queue
+// (profiles/chain_plan.md has the traces and the plans that lost).  A row: lane, position in the lane, what to launch, grid blocks
+// per CU.  Every class hands its reads out by ticket: the grid decides which block chains a read, not what a read produces.
+//
+// What the plan rests on:
+//   * A class's grid is what its LDS admits per CU, so any of L2, L1, M2, M and the lane tier alone fills every CU's LDS, and S at
+//     twelve per CU takes every wave slot (amdgpu_waves_per_eu(3, 3): twelve chaining waves a CU).  Classes XL2, XL and L want 156,
+//     49 and 102 KB on ONE CU for each of their few reads, which last milliseconds; behind a class that has filled the CUs their
+//     blocks wait until it drains (L 10.2 ms instead of 3.1 with S starting beside it; 8.4 with L2 at the fork; XL2 once 42 ms on
+//     the grch38_like genome).  So every lane BEGINS with one of them, or with the HBM tier, whose blocks find no read and leave
+//     within 60 us: by then the blocks of XL2, XL and L are placed.  Their blocks without a read leave at once.
+//   * There are three such beginnings, hence three lanes.  A fourth lane, begun by L2, measured slower (17.9 against 16.3 ms).
+//   * Behind the beginnings the LDS is the currency: the lanes are balanced by duration, longest first, and the lane tier, which
+//     runs best with the chip to itself, comes last on the lane of S, the class that leaves the most LDS free.
+//   * S at ten blocks per CU instead of twelve leaves two wave slots a CU to the classes beside it (16.5 -> 16.2 ms).
+enum : int8_t { kRunXL2, kRunHbm, kRunXL, kRunL, kRunL2, kRunL1, kRunM2, kRunM, kRunM1, kRunS, kRunLaneTier };
+struct PlanRow { int8_t lane, pos, run, per_cu; };
+// Lane 0 is the batch's stream, which does not wait for the fork event; lanes 1 and 2 are aux[0] and aux[2].  (A process has
+// four hardware queues and the runtime puts a new stream on the least used one; the null stream and the seeding's side stream hold
+// one each, and aux[0] and aux[1] come to share the fourth — kernel trace.  Two lanes on one queue are one lane.)
+constexpr int kLanes = 3;
+constexpr int kLaneAux[kLanes] = {-1, 0, 2};
+constexpr PlanRow kWavePlan[11] = {
+    {0, 0, kRunXL2, 1}, {0, 1, kRunXL, 1},  {0, 2, kRunL1, 3}, {0, 3, kRunM, 5},
+    {1, 0, kRunL, 1},   {1, 1, kRunM1, 8},  {1, 2, kRunL2, 2}, {1, 3, kRunM2, 4},
+    {2, 0, kRunHbm, 8}, {2, 1, kRunS, 10},  {2, 2, kRunLaneTier, 0}};
+// The filter of the many-chain reads; `run` is the class (kHeavyCap's index).  The class of the longest reads (a whole CU's LDS per
+// read, a few dozen reads per million) is first on the batch's stream for the reason XL2 is: behind the other classes its blocks
+// found no CU with 157 KB free until those drained (16.8 ms for 26 reads of ~4 ms).  A wave of this kernel runs on LDS latency,
+// so what a class's footprint leaves of a CU's occupancy is its speed: five classes below it, the large ones first on their lanes.
+constexpr PlanRow kHeavyPlan[6] = {{0, 0, 5, 1}, {0, 1, 1, 16}, {1, 0, 4, 4}, {1, 1, 2, 12}, {2, 0, 0, 24}, {2, 1, 3, 7}};
+// a wave class: its reads are order[chain_class[lo] .. chain_class[hi]) (lo < 0: from 0), its ticket, chain_wave_kernel's K
+struct WaveClass { int8_t lo, hi, ticket; int K; };
+constexpr WaveClass kWaveClass[10] = {{9, 6, 9, -kClassXL2}, {-1, 9, 0, 0},       {6, 0, 6, -kClassXL}, {0, 7, 1, kClassL},  {7, 1, 7, kClassL2},
+                                      {1, 8, 2, kClassL1},   {8, 2, 8, kClassM2}, {2, 3, 3, kClassM},   {3, 4, 4, kClassM1}, {4, 5, 5, kClassS}};
+constexpr size_t wave_class_lds(int K) { return K < 0 ? lds_bytes_xl(-K) : K > 0 ? lds_bytes(K) : 0; }
+template <int N> constexpr bool plan_ok(const PlanRow (&p)[N]) {   // rows lane by lane, positions counted from 0, every launch once
+    unsigned seen = 0;
+    for (int i = 0; i < N; ++i) {
+        const bool first = i == 0 || p[i - 1].lane != p[i].lane;
+        if (p[i].lane < 0 || p[i].lane >= kLanes || (i && p[i].lane < p[i - 1].lane)) return false;
+        if (p[i].pos != (first ? 0 : p[i - 1].pos + 1)) return false;
+        if (p[i].run < 0 || p[i].run >= N || (seen >> p[i].run & 1)) return false;
+        seen |= 1u << p[i].run;
+    }
+    return true;
+}
+static_assert(plan_ok(kWavePlan) && plan_ok(kHeavyPlan), "a plan lists every launch once, lane by lane");
+static_assert(kWavePlan[0].run == kRunXL2 && kHeavyPlan[0].run == 5, "the whole-CU classes go first on the batch's stream");
+
+static int lanes_fork(hipStream_t st, hipStream_t *aux, hipEvent_t fork) {
+    if (hipEventRecord(fork, st) != hipSuccess) return -1;
+    for (int l = 1; l < kLanes; ++l)
+        if (hipStreamWaitEvent(aux[kLaneAux[l]], fork, 0) != hipSuccess) return -1;
+    return 0;
+}
+static int lanes_join(hipStream_t st, hipStream_t *aux, hipEvent_t *join) {
+    for (int l = 1; l < kLanes; ++l) {
+        if (hipEventRecord(join[l - 1], aux[kLaneAux[l]]) != hipSuccess) return -1;
+        if (hipStreamWaitEvent(st, join[l - 1], 0) != hipSuccess) return -1;
+    }
+    return 0;
+}
+
 // COUNT: the instances that count into ctr->dbg (bwams_debug_chain_counts); a production launch runs the ones without any counting code.
 // The counting instances are compiled in a translation unit of their own (chain_count.hip: this file again, under BWAMS_CHAIN_COUNT_TU):
 // beside them in ONE code object the compiler allocated the registers of chain_wave_kernel<false> and of the out-of-line heavy_read
@@ -1445,61 +1510,25 @@ static int launch_chain_t(const ChainArgs &A, const uint32_t *n_seeds, int cu_co
     // process needs it too), and checked
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(chain_wave_kernel<COUNT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_bytes_xl(kClassXL2)) != hipSuccess) return -1;
-    if (hipEventRecord(fork, st) != hipSuccess) return -1;
-    for (int i = 0; i < 7; ++i)
-        if (hipStreamWaitEvent(aux[i], fork, 0) != hipSuccess) return -1;
-    // heaviest first: reads beyond the LDS budget (HBM state) and classes L, L1, then M, M1, S, then the lane tier
-    // (the reads beyond a CU's LDS keep their state in HBM: every step is a dependent L2 / HBM access, so they get many
-    // waves — no LDS limits them; at GRCh38 size, with max_occ hits per repeat SMEM, they were the stage's long pole on two)
-    // (class XL, round 2: the five reads per million beyond class L — 2915 seeds the longest — took 19.5 ms in the HBM tier and
-    // were the stage's long pole; with the ordered array in LDS only their chain records are in HBM)
-    // class XL2 wants a whole CU's LDS per read: on the batch's own stream, which does not wait for the fork event, so that its blocks
-    // are placed before the other classes' have filled every CU (behind them they found no CU free until the others drained: 42 ms on
-    // the grch38_like genome for reads of ~2 ms each); blocks without a read leave at once
-    chain_wave_kernel<COUNT><<<(unsigned)cu_count, 64, lds_bytes_xl(kClassXL2), st>>>(A, cls + 9, cls + 6, tk + 9, -kClassXL2);
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 8), 64, 0, aux[0]>>>(A, nullptr, cls + 9, tk + 0, 0);
-    chain_wave_kernel<COUNT><<<(unsigned)cu_count, 64, lds_bytes_xl(kClassXL), aux[0]>>>(A, cls + 6, cls + 0, tk + 6, -kClassXL);
-    chain_wave_kernel<COUNT><<<(unsigned)cu_count, 64, lds_bytes(kClassL), aux[1]>>>(A, cls + 0, cls + 7, tk + 1, kClassL);
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 2), 64, lds_bytes(kClassL2), aux[5]>>>(A, cls + 7, cls + 1, tk + 7, kClassL2);
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 3), 64, lds_bytes(kClassL1), aux[2]>>>(A, cls + 1, cls + 8, tk + 2, kClassL1);
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 4), 64, lds_bytes(kClassM2), aux[6]>>>(A, cls + 8, cls + 2, tk + 8, kClassM2);
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 8), 64, lds_bytes(kClassM1), aux[2]>>>(A, cls + 3, cls + 4, tk + 4, kClassM1);
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 12), 64, lds_bytes(kClassS), aux[3]>>>(A, cls + 4, cls + 5, tk + 5, kClassS);
-    // (the lane tier on the batch's own stream behind class XL2 instead: 19.1 -> 20.3 ms on the uniform genome, 50 -> 54 on grch38_like)
-    launch_chain_lane(A, aux[1], COUNT);
-    // class M behind the lane tier (5 ms) rather than behind class L or S (kernel trace at GRCh38 size: L 8.9-10.3 ms + M 4.3-6.7 was
-    // the stage's longest stream; S 7.8, L1 7.7 + M1 2.9, XL 0.9 + 7.2)
-    // (round 4: on the stream of class L, the shortest; aux[4] shares a hardware queue with class S's stream, 16 ms on a repeat-rich genome)
-    chain_wave_kernel<COUNT><<<(unsigned)(cu_count * 5), 64, lds_bytes(kClassM), aux[5]>>>(A, cls + 2, cls + 3, tk + 3, kClassM);
-    for (int i = 0; i < 7; ++i) {
-        if (hipEventRecord(join[i], aux[i]) != hipSuccess) return -1;
-        if (hipStreamWaitEvent(st, join[i], 0) != hipSuccess) return -1;
+    if (lanes_fork(st, aux, fork)) return -1;
+    for (const PlanRow &p : kWavePlan) {
+        const hipStream_t q = p.lane ? aux[kLaneAux[p.lane]] : st;
+        if (p.run == kRunLaneTier) {
+            launch_chain_lane(A, q, COUNT);
+            continue;
+        }
+        const WaveClass &c = kWaveClass[p.run];
+        chain_wave_kernel<COUNT><<<(unsigned)(cu_count * p.per_cu), 64, wave_class_lds(c.K), q>>>(A, c.lo < 0 ? nullptr : cls + c.lo, cls + c.hi, tk + c.ticket, c.K);
     }
+    if (lanes_join(st, aux, join)) return -1;
     chain_redo_kernel<COUNT><<<(unsigned)(cu_count * 2), 64, 0, st>>>(A);
-    // the filter of the many-chain reads: three size classes, concurrently, the class of the longest reads first
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(chain_heavy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)heavy_lds_bytes(kHeavyCap[5])) != hipSuccess) return -1;
-    if (hipEventRecord(fork, st) != hipSuccess) return -1;
-    for (int i = 0; i < 5; ++i)
-        if (hipStreamWaitEvent(aux[i], fork, 0) != hipSuccess) return -1;
-    unsigned long long *htk = A.ctr->heavy_tickets;
-    // The class of the longest reads (a whole CU's LDS per read, a few dozen reads per million) goes on the batch's own stream: it
-    // starts without waiting for the fork event, i.e. before the other classes' blocks have filled every CU's LDS — behind them
-    // (kernel trace) its blocks found no CU with 157 KB free until the other classes drained: 16.8 ms for 26 reads of ~4 ms.
-    // Its blocks without a read leave at once.
-    // (round 4: five classes instead of three — a wave of this kernel runs on LDS latency, so what a class's footprint leaves of a CU's
-    // occupancy is its speed: the 257..512-chain reads ran four to a CU under the 960 class's 39 KB)
-    chain_heavy_kernel<<<(unsigned)cu_count, 64, heavy_lds_bytes(kHeavyCap[5]), st>>>(A, &A.ctr->n_heavy, kHeavyCap[4], kHeavyCap[5], htk + 5);
-    chain_heavy_kernel<<<(unsigned)(cu_count * 4), 64, heavy_lds_bytes(kHeavyCap[4]), aux[1]>>>(A, &A.ctr->n_heavy, kHeavyCap[3], kHeavyCap[4], htk + 4);
-    chain_heavy_kernel<<<(unsigned)(cu_count * 7), 64, heavy_lds_bytes(kHeavyCap[3]), aux[2]>>>(A, &A.ctr->n_heavy, kHeavyCap[2], kHeavyCap[3], htk + 3);
-    chain_heavy_kernel<<<(unsigned)(cu_count * 12), 64, heavy_lds_bytes(kHeavyCap[2]), aux[0]>>>(A, &A.ctr->n_heavy, kHeavyCap[1], kHeavyCap[2], htk + 2);
-    chain_heavy_kernel<<<(unsigned)(cu_count * 16), 64, heavy_lds_bytes(kHeavyCap[1]), aux[3]>>>(A, &A.ctr->n_heavy, kHeavyCap[0], kHeavyCap[1], htk + 1);
-    chain_heavy_kernel<<<(unsigned)(cu_count * 24), 64, heavy_lds_bytes(kHeavyCap[0]), aux[4]>>>(A, &A.ctr->n_heavy, 0, kHeavyCap[0], htk + 0);
-    for (int i = 0; i < 5; ++i) {
-        if (hipEventRecord(join[i], aux[i]) != hipSuccess) return -1;
-        if (hipStreamWaitEvent(st, join[i], 0) != hipSuccess) return -1;
-    }
-    return 0;
+    if (lanes_fork(st, aux, fork)) return -1;
+    for (const PlanRow &p : kHeavyPlan)
+        chain_heavy_kernel<<<(unsigned)(cu_count * p.per_cu), 64, heavy_lds_bytes(kHeavyCap[p.run]), p.lane ? aux[kLaneAux[p.lane]] : st>>>(
+            A, &A.ctr->n_heavy, p.run ? kHeavyCap[p.run - 1] : 0, kHeavyCap[p.run], A.ctr->heavy_tickets + p.run);
+    return lanes_join(st, aux, join);
 }
 #ifdef BWAMS_CHAIN_COUNT_TU
 int launch_chain_counting(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join) {

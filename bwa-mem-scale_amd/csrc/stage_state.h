@@ -7,6 +7,9 @@
 
 namespace bwams {
 
+// Streams beside the batch's own that a stage forks its launches onto: banded SW uses all four (launch_bsw: five query-length
+// classes with the batch's stream), de-duplication three, chaining two (its plan: chain.hip), selection one.
+constexpr int kAuxStreams = 4;
 struct StageState {
     struct ChainStage {                      // chaining, mem_flt_chained_seeds (sw_*), the ERT input translation (et_*)
         DevBuf<int32_t> s_next, f_first, f_kept, f_sel; DevBuf<int2> s_ql; DevBuf<uint2> flt; DevBuf<uint4> f_rec;       // scratch per SA hit
@@ -103,9 +106,9 @@ struct StageState {
     bwams_mem_opt_t opt{};
     hipEvent_t ev[16] = {};       // 0-1 chain, 2-3 plan+build, 4-5 left, 6-7 right, 8-9 selection (first round each), 10-11 all rounds
     bool ev_ok = false;
-    hipStream_t aux[7] = {};      // the chaining tiers run concurrently (the device's shared set: api_state.hip)
+    hipStream_t aux[kAuxStreams] = {};   // the stages' concurrent launches (the device's shared set: api_state.hip)
     int aux_device = -1;
-    hipEvent_t fork = nullptr, join[7] = {};
+    hipEvent_t fork = nullptr, join[kAuxStreams] = {};
 };
 
 int get_state(bwams_batch *b, StageState **out);                  // creates b->stages at the first call
