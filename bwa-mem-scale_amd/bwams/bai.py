@@ -2,7 +2,19 @@
 
 build(bam_file) makes the index of a BGZF-compressed, coordinate-sorted BAM file byte for byte as bwams_sorter_close writes it;
 read(bai) parses an index; query(index, bam_file, tid, beg, end) returns the records the index's candidate chunks yield that overlap
-[beg, end) — what a region query of a BAM reader returns.
+[beg, end) — what a region query of a BAM reader returns; plan(index, regions) is the plan of such a query over several regions as
+bwams_bam_file_query makes it and bwams_bai_plan returns it (host/bam_query.cpp), walk(plan, bam_file, regions) the records it yields.
+
+The rules of a region query (include/bwams.h, "BAM file by region"):
+  1. a record overlaps region (ref, beg, end) when refID == ref, POS < end and bam.record_end > beg (overlapping);
+  2. regions (0 <= ref < n_ref, 0 <= beg < end, any order, overlapping or not) are sorted by (ref, beg) and merged per reference
+     where they overlap or touch; a record that overlaps several comes back once, and records come back in file order;
+  3. the plan: for every merged region the chunks of reg2bins(beg, end) — levels the coordinate overruns give no bin, pseudo-bin
+     37450 is never a source — that end past the linear index's offset of beg's 16 kb window (the window index clamped to the last
+     entry, an empty linear index gives 0), each start clipped to that offset; all of them sorted by virtual offset, and those that
+     touch or overlap merged into disjoint intervals;
+  4. no regions: the whole file, one interval from the first record to the end of the data, unplaced records included;
+  5. a chain of records starts at an interval's start and stops at its end offset.
 
 The rules (htslib's hts_idx_push / hts_idx_finish, with the choices spelled out):
   * a record's span is [max(POS, 0), max(end, that + 1)), end = bam.record_end; its bin is reg2bin of the span;
@@ -216,4 +228,60 @@ def overlapping(records: bytes, tid: int, beg: int, end: int) -> list[bytes]:
         refid, pos = struct.unpack_from("<ii", rec, 4)
         if refid == tid and pos < end and bam.record_end(rec) > beg:
             out.append(rec)
+    return out
+
+
+def merge_regions(regions) -> list[tuple[int, int, int]]:
+    """Rule 2: the regions sorted by (ref, beg) and merged per reference where they overlap or touch."""
+    out = []
+    for ref, beg, end in sorted((int(r), int(b), int(e)) for r, b, e in regions):
+        assert ref >= 0 and 0 <= beg < end, (ref, beg, end)
+        if out and out[-1][0] == ref and beg <= out[-1][2]:
+            out[-1][2] = max(out[-1][2], end)
+        else:
+            out.append([ref, beg, end])
+    return [tuple(x) for x in out]
+
+
+def _bins(beg: int, end: int):
+    """reg2bins(beg, end) with every level clipped to its own bins (a coordinate of 2^29 or more overruns the scheme)"""
+    yield 0
+    for shift, first, nxt in ((26, 1, 9), (23, 9, 73), (20, 73, 585), (17, 585, 4681), (14, 4681, 37449)):
+        yield from range(first + (beg >> shift), min(first + ((end - 1) >> shift), nxt - 1) + 1)
+
+
+def plan(index: dict, regions) -> list[tuple[int, int]]:
+    """Rule 3: the disjoint intervals (beg, end) of virtual offsets, ascending, that hold every record overlapping a region."""
+    chunks = []
+    for ref, beg, end in merge_regions(regions):
+        r = index["refs"][ref]
+        lin = r["lin"]
+        min_off = 0 if not lin else lin[min(beg >> 14, len(lin) - 1)]
+        for b in _bins(beg, end):
+            for cb, ce in r["bins"].get(b, ()):
+                if ce > min_off and max(cb, min_off) < ce:
+                    chunks.append((max(cb, min_off), ce))
+    out = []
+    for cb, ce in sorted(chunks):
+        if out and cb <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], ce)
+        else:
+            out.append([cb, ce])
+    return [tuple(c) for c in out]
+
+
+def walk(intervals, bam_file: bytes, regions) -> list[bytes]:
+    """The records a reader gets from a plan: every interval's chain from its start to its end offset, rule 1 against the regions."""
+    st = _Stream(bam_file)
+    merged = merge_regions(regions)
+    out = []
+    for vb, ve in intervals:
+        x, stop = st.at(vb), st.at(ve)
+        while x < stop:
+            (bs,) = struct.unpack_from("<I", st.data, x)
+            rec = st.data[x:x + 4 + bs]
+            refid, pos = struct.unpack_from("<ii", rec, 4)
+            if any(refid == ref and pos < end and bam.record_end(rec) > beg for ref, beg, end in merged):
+                out.append(rec)
+            x += 4 + bs
     return out

@@ -74,6 +74,9 @@ SYMBOLS = [
     "bwams_sorter_set_recal", "bwams_dup_groups_rg_id",
     "bwams_recal_model_create", "bwams_recal_model_from", "bwams_recal_model_table", "bwams_recal_model_constants", "bwams_recal_model_destroy",
     "bwams_recal_apply_open", "bwams_recal_apply_close", "bwams_recal_apply_records", "bwams_recal_apply_batch", "bwams_recal_apply_info",
+    "bwams_bam_file_open", "bwams_bam_file_header", "bwams_bam_file_refs", "bwams_bam_file_query", "bwams_bam_file_next", "bwams_bam_file_fetch",
+    "bwams_bam_file_info", "bwams_bam_file_close", "bwams_depth_add_file", "bwams_pileup_add_file", "bwams_qc_add_file", "bwams_recal_add_file",
+    "bwams_recal_apply_file", "bwams_bai_plan",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -511,6 +514,12 @@ class _Consumer(_Handle):
         records = bytes(records)
         n = C.c_int64(0)
         self._call(self._prefix + "_add_records", records, len(records), C.byref(n))
+        return n.value
+
+    def add_file(self, bam_file: "BamFile") -> int:
+        """The current piece of a BamFile, read in HBM; -> the records that counted."""
+        n = C.c_int64(0)
+        self._call(self._prefix + "_add_file", bam_file.h, C.byref(n))
         return n.value
 
     def reset(self) -> None:
@@ -992,9 +1001,102 @@ class RecalApply(_Handle):
         _chk(lib().bwams_recal_apply_batch(self.h, batch.h, C.byref(n)), "bwams_recal_apply_batch")
         return n.value
 
+    def file(self, bam_file: "BamFile") -> int:
+        """The current piece of a BamFile rewritten in HBM (BamFile.fetch then gives the new bytes); -> the records rewritten."""
+        n = C.c_int64(0)
+        _chk(lib().bwams_recal_apply_file(self.h, bam_file.h, C.byref(n)), "bwams_recal_apply_file")
+        return n.value
+
     def info(self) -> dict:
         """bwams_recal_apply_info: model_bytes, and of the last apply n_records, n_rewritten, ms_check, ms_apply."""
         return self._info("bwams_recal_apply_info", RecalApplyInfo)
+
+
+class BamFileInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("intervals", "members", "compressed_bytes", "inflated_bytes", "candidates", "records_seen",
+                                         "records_kept", "pieces", "carried")] + \
+               [(n, C.c_float) for n in ("ms_read", "ms_inflate", "ms_discover", "ms_select", "ms_gather")] + [("pad_", C.c_int32)]
+
+
+def _regions(regions):
+    a = np.zeros(len(regions), PILEUP_REGION_DTYPE)
+    for k, (r, b, e) in enumerate(regions):
+        a[k] = (r, b, e)
+    return a
+
+
+def bai_plan(bai: bytes, regions) -> list:
+    """bwams_bai_plan: rule 3's intervals [(beg, end), ...] of virtual offsets from the bytes of a BAI (host only)."""
+    bai = bytes(bai)
+    a = _regions(regions)
+    n = C.c_int64(0)
+    rc = lib().bwams_bai_plan(bai, len(bai), _p(a), len(a), None, None, 0, C.byref(n))
+    if rc != -4:
+        _chk(rc, "bwams_bai_plan")
+    b, e = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint64)
+    _chk(lib().bwams_bai_plan(bai, len(bai), _p(a), len(a), _p(b), _p(e), n.value, C.byref(n)), "bwams_bai_plan")
+    return [(int(x), int(y)) for x, y in zip(b[:n.value], e[:n.value])]
+
+
+class BamFile(_Handle):
+    """A coordinate-sorted BAM file read back by region on one GPU (bwams_bam_file_t): query, then next() until done; fetch() or a
+    consumer's add_file() takes the current piece."""
+    _close = "bwams_bam_file_close"
+
+    def __init__(self, path: str, bai_path: str | None = None, device: int = 0, piece_bytes: int = 0):
+        self.h = C.c_void_p()
+        _chk(lib().bwams_bam_file_open(path.encode(), bai_path.encode() if bai_path else None, device, piece_bytes, C.byref(self.h)),
+             "bwams_bam_file_open")
+        self.n_records = self.n_bytes = 0
+
+    def header(self) -> tuple[bytes, int]:
+        """(the header text, n_ref)"""
+        t, n, nr = C.c_void_p(), C.c_int64(0), C.c_int32(0)
+        self._call("bwams_bam_file_header", C.byref(t), C.byref(n), C.byref(nr))
+        return C.string_at(t, n.value) if n.value else b"", nr.value
+
+    def refs(self) -> np.ndarray:
+        """the references' lengths"""
+        out = np.zeros(max(self.header()[1], 1), np.int32)
+        self._call("bwams_bam_file_refs", _p(out), len(out))
+        return out[:self.header()[1]]
+
+    def query(self, regions=()) -> "BamFile":
+        """regions: (ref, beg, end) triples; none: the whole file"""
+        a = _regions(regions)
+        self._call("bwams_bam_file_query", _p(a), len(a))
+        return self
+
+    def next(self) -> bool:
+        """Makes the next piece current (.n_records, .n_bytes); -> done"""
+        n, nb, done = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._call("bwams_bam_file_next", C.byref(n), C.byref(nb), C.byref(done))
+        self.n_records, self.n_bytes = n.value, nb.value
+        return bool(done.value)
+
+    def fetch(self):
+        """-> (the current piece's records, their coords as BAM_COORD_DTYPE)"""
+        buf = np.zeros(max(self.n_bytes, 1), np.uint8)
+        coords = np.zeros(max(self.n_records, 1), BAM_COORD_DTYPE)
+        self._call("bwams_bam_file_fetch", _p(buf), self.n_bytes, _p(coords))
+        return buf[:self.n_bytes].tobytes(), coords[:self.n_records]
+
+    def pieces(self):
+        """Iterates over the query's pieces: each is current while the loop body runs."""
+        done = False
+        while not done:
+            done = self.next()
+            yield self
+
+    def read(self, regions=()):
+        """The whole query fetched: (records, coords)"""
+        self.query(regions)
+        got = [p.fetch() for p in self.pieces()]
+        return b"".join(r for r, _ in got), np.concatenate([c for _, c in got])
+
+    def info(self) -> dict:
+        """bwams_bam_file_info: the totals since the last query"""
+        return self._info("bwams_bam_file_info", BamFileInfo)
 
 
 class Gunzipper:
@@ -1333,6 +1435,17 @@ def lib():
         L.bwams_recal_apply_records.argtypes = [vp, vp, i64, vp]
         L.bwams_recal_apply_batch.argtypes = [vp, vp, vp]
         L.bwams_recal_apply_info.argtypes = [vp, vp]
+        L.bwams_bam_file_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int, i64, vp]
+        L.bwams_bam_file_header.argtypes = [vp, vp, vp, vp]
+        L.bwams_bam_file_refs.argtypes = [vp, vp, i32]
+        L.bwams_bam_file_query.argtypes = [vp, vp, i32]
+        L.bwams_bam_file_next.argtypes = [vp, vp, vp, vp]
+        L.bwams_bam_file_fetch.argtypes = [vp, vp, i64, vp]
+        L.bwams_bam_file_info.argtypes = [vp, vp]
+        L.bwams_bam_file_close.argtypes = [vp]
+        for name in ("bwams_depth_add_file", "bwams_pileup_add_file", "bwams_qc_add_file", "bwams_recal_add_file", "bwams_recal_apply_file"):
+            getattr(L, name).argtypes = [vp, vp, vp]
+        L.bwams_bai_plan.argtypes = [vp, i64, vp, i32, vp, vp, i64, vp]
         L.bwams_dup_groups_rg_id.argtypes = [vp, i64]
         L.bwams_dup_groups_rg_id.restype = C.c_char_p
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -182,6 +182,12 @@ int bwams_depth_add_records(bwams_depth_t *d, const void *bam, int64_t n_bytes, 
     return depth_add(d, R, n_counted, "bwams_depth_add_records");
 }
 
+int bwams_depth_add_file(bwams_depth_t *d, bwams_bam_file_t *f, int64_t *n_counted) {
+    DevRecords R;
+    if (int rc = consumer_file(d, f, "bwams_depth_add_file", &R, d ? d->finished_text() : nullptr)) return rc;
+    return depth_add(d, R, n_counted, "bwams_depth_add_file");
+}
+
 int bwams_depth_finish(bwams_depth_t *d) {
     if (!d) return BWAMS_ERR_ARG;
     if (d->finished) return BWAMS_OK;

@@ -457,6 +457,12 @@ int bwams_pileup_add_records(bwams_pileup_t *p, const void *bam, int64_t n_bytes
     return pileup_add(p, recs, n_counted, "bwams_pileup_add_records");
 }
 
+int bwams_pileup_add_file(bwams_pileup_t *p, bwams_bam_file_t *f, int64_t *n_counted) {
+    DevRecords recs;
+    if (int rc = consumer_file(p, f, "bwams_pileup_add_file", &recs)) return rc;
+    return pileup_add(p, recs, n_counted, "bwams_pileup_add_file");
+}
+
 int bwams_pileup_set_ref(bwams_pileup_t *p, int32_t region, const uint8_t *codes) {
     if (!p || region < 0 || region >= p->n_regions() || !codes) {
         set_last_error("bwams_pileup_set_ref: a handle, a region in [0, n_regions) and its codes are required");

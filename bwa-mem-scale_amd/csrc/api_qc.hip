@@ -135,6 +135,12 @@ int bwams_qc_add_records(bwams_qc_t *q, const void *bam, int64_t n_bytes, int64_
     return qc_add(q, R, n_counted, "bwams_qc_add_records");
 }
 
+int bwams_qc_add_file(bwams_qc_t *q, bwams_bam_file_t *f, int64_t *n_counted) {
+    DevRecords R;
+    if (int rc = consumer_file(q, f, "bwams_qc_add_file", &R)) return rc;
+    return qc_add(q, R, n_counted, "bwams_qc_add_file");
+}
+
 int bwams_qc_summary(bwams_qc_t *q, bwams_qc_summary_t *out) {
     if (!q || !out) return BWAMS_ERR_ARG;
     static_assert(sizeof(bwams_qc_summary_t) == 48 * 8, "the summary is the head of the counter block");

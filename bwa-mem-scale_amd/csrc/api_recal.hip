@@ -207,6 +207,12 @@ int bwams_recal_add_records(bwams_recal_t *r, const void *bam, int64_t n_bytes, 
     return recal_add(r, R, n_counted, "bwams_recal_add_records");
 }
 
+int bwams_recal_add_file(bwams_recal_t *r, bwams_bam_file_t *f, int64_t *n_counted) {
+    DevRecords R;
+    if (int rc = consumer_file(r, f, "bwams_recal_add_file", &R)) return rc;
+    return recal_add(r, R, n_counted, "bwams_recal_add_file");
+}
+
 int bwams_recal_set_ref(bwams_recal_t *r, int32_t ref, const uint8_t *codes) {
     if (!r || ref < 0 || ref >= r->n_ref() || (!codes && r->l_ref[(size_t)ref] > 0)) {
         set_last_error("bwams_recal_set_ref: a handle, a reference in [0, n_ref) and its codes are required");

@@ -191,6 +191,13 @@ int bwams_recal_apply_records(bwams_recal_apply_t *a, void *bam, int64_t n_bytes
     return BWAMS_OK;
 }
 
+int bwams_recal_apply_file(bwams_recal_apply_t *a, bwams_bam_file_t *f, int64_t *n_rewritten) {
+    DevRecords R;
+    if (int rc = consumer_file(a, f, "bwams_recal_apply_file", &R)) return rc;
+    if (int rc = apply_check(a, R, "bwams_recal_apply_file")) return rc;
+    return apply_rewrite(a, R, n_rewritten);
+}
+
 int bwams_recal_apply_batch(bwams_recal_apply_t *a, bwams_batch_t *b, int64_t *n_rewritten) {
     DevRecords R;
     StageState *s = nullptr;

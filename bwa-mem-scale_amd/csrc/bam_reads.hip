@@ -2,19 +2,9 @@
 // becomes in fastq.hip.  The reference reads FASTQ / FASTA only; the behaviour reproduced is `samtools fastq` (htslib's bam2fq) in
 // front of `bwa mem`, with the rules written out in include/bwams.h above bwams_bam_reads_decode and restated in bwams/bam_reads.py.
 //
-// Record discovery.  Where record k + 1 starts follows from record k's block_size, so the records are a linked list through the
-// bytes.  As for FASTQ records over several lines (fastq.hip), every position is parsed as if a record began there and the real
-// records are the chain of successors from byte 0, found by binary lifting — but over the few positions that can be a record at all:
-//   (1) br_filter_kernel: a lane per byte offset, the bytes staged through LDS in 16-byte loads, tests rule 1 (sizes consistent,
-//       the name's NUL in place, the end inside the buffer).  The wave's ballot is one word of a bitmap; its population count goes
-//       into a second array whose exclusive scan gives, for any offset q, "index of the candidate at q" in O(1).
-//   (2) br_succ_kernel: a lane per bitmap word lists its candidates' offsets and their successors — the candidate index at
-//       q + 4 + block_size, END when that is n_bytes, BAD when nothing well formed starts there.
-//   (3) br_double_kernel, ceil(log2(candidates)) + 1 levels; br_count_kernel (one lane) descends them from candidate 0: the number
-//       of records, or the ordinal and offset of the first position the chain reaches where no record starts.
-// Quality and aux bytes do give false candidates (a Z value may hold a whole record); the chain from byte 0 never visits them.
-// Scratch: 1/8 byte (bitmap) + 1/16 byte (ranks) per input byte, 8 + 4 * levels bytes per candidate — about 0.75 byte per input
-// byte for a million 150-base reads.
+// Record discovery: bam_discover.h (candidate filter, successors, binary lifting), shared with the region reader of bam_query.hip;
+// here the chain runs from byte 0 and must end at the end of the buffer.  Its scratch is about 0.75 byte per input byte for a million
+// 150-base reads.
 // Behind it: br_measure_kernel, a lane per record (its offset by lifting; FLAG, lengths, the aux walk, rules 4 and 6), four exclusive
 // scans, br_compact_kernel (the offsets of the kept reads), br_emit_kernel, 16 lanes per record: the packed SEQ in 4-byte loads, a
 // nibble to its code by shifts of a constant, qualities, names and comments lane by lane.
@@ -22,141 +12,20 @@
 // `levels` dependent 4-byte gathers per record are latency bound and small beside them.
 #include <algorithm>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <memory>
 #include <string>
 #include <vector>
-#include "common.h"
-#include "bam_rec.h"
+#include "bam_discover.h"
 
 namespace bwams {
 namespace {
 
-constexpr int kTile = 4096;                   // bytes per block of br_filter_kernel: 64 bitmap words
-constexpr int kHalo = 48;                     // a record's fixed part (36 bytes) behind the tile's last offset, in 16-byte pieces
 constexpr int kMaxTags = 32;
 
 struct Tags {                                 // the listed tags, by value in the kernel arguments
     int32_t n;
     uint8_t t[2 * kMaxTags];
 };
-
-// the aligned word w of the buffer (d is 16-byte aligned): one load when it lies inside [0, n), its bytes inside otherwise
-__device__ __forceinline__ uint32_t ld_word(const uint8_t *__restrict__ d, int64_t w, int64_t n) {
-    const int64_t p = w * 4;
-    if (p + 4 <= n) return *reinterpret_cast<const uint32_t *>(d + p);
-    uint32_t v = 0;
-    for (int k = 0; k < 4; ++k)
-        if (p + k < n) v |= (uint32_t)d[p + k] << (8 * k);
-    return v;
-}
-// the four bytes at p (any alignment), bytes outside [0, n) as zeros
-__device__ __forceinline__ uint32_t ld_wide(const uint8_t *__restrict__ d, int64_t p, int64_t n) {
-    const int64_t w = p >> 2;
-    const int sh = (int)(p & 3) * 8;
-    const uint32_t lo = ld_word(d, w, n);
-    if (!sh) return lo;
-    return lo >> sh | ld_word(d, w + 1, n) << (32 - sh);
-}
-
-// rule 1 at offset q from the fields of the fixed part: everything but the name's NUL
-__device__ __forceinline__ bool fixed_ok(int64_t q, int64_t n, uint32_t block_size, uint32_t l_name, uint32_t n_cig, int32_t l_seq) {
-    if (block_size < 32 || l_name < 1 || l_seq < 0) return false;
-    if (q + 4 + (int64_t)block_size > n) return false;
-    const int64_t need = bam_aux_at(l_name, n_cig, l_seq) - 4;
-    return need <= (int64_t)block_size;
-}
-
-// (1) a lane per offset.  Block b takes offsets [b * kTile, (b + 1) * kTile); bm: one bit per offset, cnt[w] = popcount(bm[w]).
-__global__ __launch_bounds__(256) void br_filter_kernel(const uint8_t *__restrict__ d, int64_t n, unsigned long long *__restrict__ bm,
-                                                        uint32_t *__restrict__ cnt) {
-    __shared__ uint32_t lds[(kTile + kHalo) / 4 + 1];
-    const int64_t t0 = (int64_t)blockIdx.x * kTile;
-    for (int piece = threadIdx.x; piece < (kTile + kHalo) / 16; piece += 256) {
-        const int64_t p = t0 + (int64_t)piece * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (p + 16 <= n) v = *reinterpret_cast<const uint4 *>(d + p);
-        else if (p < n) { v.x = ld_word(d, p >> 2, n); v.y = ld_word(d, (p >> 2) + 1, n); v.z = ld_word(d, (p >> 2) + 2, n); v.w = ld_word(d, (p >> 2) + 3, n); }
-        lds[piece * 4] = v.x; lds[piece * 4 + 1] = v.y; lds[piece * 4 + 2] = v.z; lds[piece * 4 + 3] = v.w;
-    }
-    if (threadIdx.x == 0) lds[(kTile + kHalo) / 4] = 0;
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = 0; k < kTile / 256; ++k) {
-        const int t = k * 256 + threadIdx.x;                     // consecutive lanes, consecutive offsets: four lanes share a word
-        const int64_t q = t0 + t;
-        const int sh = (t & 3) * 8, w = t >> 2;
-        auto u32_at = [&](int word) -> uint32_t {
-            const uint32_t lo = lds[word], hi = lds[word + 1];
-            return sh ? (lo >> sh | hi << (32 - sh)) : lo;
-        };
-        bool ok = false;
-        if (q + kBamName <= n) {
-            const uint32_t block_size = u32_at(w);
-            if (block_size >= 32 && q + 4 + (int64_t)block_size <= n) {
-                const uint32_t l_name = u32_at(w + 3) & 0xFF, n_cig = u32_at(w + 4) & 0xFFFF;
-                const int32_t l_seq = (int32_t)u32_at(w + 5);
-                ok = fixed_ok(q, n, block_size, l_name, n_cig, l_seq) && d[q + kBamName - 1 + l_name] == 0;     // the name's last byte: inside the record
-            }
-        }
-        const unsigned long long m = __ballot(ok);
-        if (lane == 0) {
-            const int64_t word = (t0 >> 6) + k * 4 + wave;
-            bm[word] = m;
-            cnt[word] = (uint32_t)__popcll(m);
-        }
-    }
-}
-
-// (2) a lane per bitmap word: offsets and successors of its candidates.  END = n_cand, BAD = n_cand + 1 (both map to themselves).
-__global__ __launch_bounds__(256) void br_succ_kernel(const uint8_t *__restrict__ d, int64_t n, const unsigned long long *__restrict__ bm,
-                                                      const uint32_t *__restrict__ rank, int64_t n_words, uint32_t n_cand,
-                                                      int64_t *__restrict__ cand_off, uint32_t *__restrict__ up0) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w == 0) { up0[n_cand] = n_cand; up0[n_cand + 1] = n_cand + 1; }
-    if (w >= n_words) return;
-    unsigned long long bits = bm[w];
-    uint32_t idx = rank[w];
-    while (bits) {
-        const int b = __ffsll((long long)bits) - 1;
-        bits &= bits - 1;
-        const int64_t q = w * 64 + b;
-        const int64_t q2 = q + 4 + (int64_t)bam_block_size(d + q);           // <= n: the filter saw to it
-        uint32_t nx = n_cand + 1;
-        if (q2 == n) nx = n_cand;
-        else {
-            const unsigned long long m = bm[q2 >> 6];
-            const int s = (int)(q2 & 63);
-            if ((m >> s) & 1) nx = rank[q2 >> 6] + (uint32_t)__popcll(m & ((1ull << s) - 1));
-        }
-        cand_off[idx] = q;
-        up0[idx] = nx;
-        ++idx;
-    }
-}
-
-// (3) up[k + 1] = up[k] o up[k]
-__global__ __launch_bounds__(256) void br_double_kernel(const uint32_t *__restrict__ a, uint32_t *__restrict__ b, int64_t n) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) b[j] = a[a[j]];
-}
-
-// one lane: out[0] = records of the chain from byte 0, or -1 with out[1] / out[2] = ordinal / offset of the first bad record
-__global__ void br_count_kernel(const uint8_t *__restrict__ d, const unsigned long long *__restrict__ bm, const uint32_t *__restrict__ up,
-                                int levels, uint32_t n_cand, const int64_t *__restrict__ cand_off, int64_t *__restrict__ out) {
-    if (!(bm[0] & 1)) { out[0] = -1; out[1] = 0; out[2] = 0; return; }
-    const int64_t stride = (int64_t)n_cand + 2;
-    uint32_t cur = 0;
-    int64_t cnt = 0;
-    for (int k = levels - 1; k >= 0; --k) {
-        const uint32_t nx = up[(int64_t)k * stride + cur];
-        if (nx < n_cand) { cur = nx; cnt += (int64_t)1 << k; }
-    }
-    if (up[cur] == n_cand) { out[0] = cnt + 1; out[1] = out[2] = 0; return; }
-    out[0] = -1;
-    out[1] = cnt + 1;
-    out[2] = cand_off[cur] + 4 + (int64_t)bam_block_size(d + cand_off[cur]);
-}
 
 struct BrRec {                                // a record as the emit kernel reads it
     int64_t name_at, seq_at, end;             // end: one past the record
@@ -260,11 +129,7 @@ __global__ __launch_bounds__(256) void br_measure_kernel(const uint8_t *__restri
     if (r > n_rec) return;
     const int64_t n1 = n_rec + 1;
     if (r == n_rec) { wide[r] = wide[n1 + r] = wide[2 * n1 + r] = wide[3 * n1 + r] = 0; return; }
-    const int64_t stride = (int64_t)n_cand + 2;
-    uint32_t cur = 0;
-    for (int k = 0; k < levels; ++k)
-        if ((r >> k) & 1) cur = up[(int64_t)k * stride + cur];
-    const int64_t q = cand_off[cur];
+    const int64_t q = cand_off[br_lift(up, levels, n_cand, 0, r)];
     const uint8_t *p = d + q;
     const uint32_t block_size = bam_block_size(p), l_name = bam_l_name(p), n_cig = bam_n_cig(p), flag = bam_flag(p);
     const int32_t l_seq = bam_l_seq(p);
@@ -439,12 +304,10 @@ int bwams_bam_reads_decode(int device, const void *bam, int64_t n_bytes, const c
     const bool on_dev = hipPointerGetAttributes(&attr, bam) == hipSuccess && attr.type == hipMemoryTypeDevice;
     (void)hipGetLastError();
     DevBuf<uint8_t> own;
-    DevBuf<unsigned long long> bm;
-    DevBuf<uint32_t> rank, up;
-    DevBuf<int64_t> cand_off, res, wide, offs, comp;
+    BrDiscover disc;
+    DevBuf<int64_t> wide, offs, comp;
     DevBuf<BrRec> recs;
     DevBuf<BrFlags> flags;
-    DevBuf<> scan_tmp;
     const uint8_t *d = static_cast<const uint8_t *>(bam);
     if (!on_dev || (reinterpret_cast<uintptr_t>(bam) & 15)) {
         BWAMS_HIP(own.alloc((size_t)n_bytes + 16));
@@ -452,45 +315,23 @@ int bwams_bam_reads_decode(int device, const void *bam, int64_t n_bytes, const c
         d = own.p;
     }
     BWAMS_HIP(hipEventRecord(evs.a, st));
-    // (1) the filter, the ranks
-    const int64_t n_tiles = (n_bytes + kTile - 1) / kTile, n_words = n_tiles * (kTile / 64);
-    BWAMS_HIP(bm.alloc((size_t)n_words * 8));
-    BWAMS_HIP(rank.alloc((size_t)(n_words + 1) * 4));
-    br_filter_kernel<<<(unsigned)n_tiles, 256, 0, st>>>(d, n_bytes, bm.p, rank.p);
-    BWAMS_HIP(hipMemsetAsync(rank.p + n_words, 0, 4, st));
-    {
-        size_t tb = 0;
-        BWAMS_HIP(rocprim::exclusive_scan(nullptr, tb, rank.p, rank.p, 0u, (size_t)(n_words + 1), rocprim::plus<uint32_t>(), st));
-        BWAMS_HIP(scan_tmp.alloc(tb + 16));
-        BWAMS_HIP(rocprim::exclusive_scan(scan_tmp.p, tb, rank.p, rank.p, 0u, (size_t)(n_words + 1), rocprim::plus<uint32_t>(), st));
-    }
-    uint32_t n_cand = 0;
-    BWAMS_HIP(hipMemcpyAsync(&n_cand, rank.p + n_words, 4, hipMemcpyDeviceToHost, st));
-    BWAMS_HIP(hipStreamSynchronize(st));
     auto bad_record = [&](int64_t ordinal, int64_t at) {
         set_last_error("bwams_bam_reads_decode: record " + std::to_string(ordinal) + " at byte " + std::to_string(at) +
                        " is not a well-formed BAM record inside the buffer (block_size, l_read_name, l_seq, the name's NUL), or the "
                        "records do not end at n_bytes");
         return BWAMS_ERR_ARG;
     };
-    if (n_cand == 0) return bad_record(0, 0);
-    // (2) successors, (3) lifting
-    int levels = 1;
-    while (((int64_t)1 << (levels - 1)) < (int64_t)n_cand) ++levels;
-    const int64_t stride = (int64_t)n_cand + 2;
-    BWAMS_HIP(cand_off.alloc((size_t)n_cand * 8));
-    BWAMS_HIP(up.alloc((size_t)levels * (size_t)stride * 4));
-    BWAMS_HIP(res.alloc(64));
-    br_succ_kernel<<<(unsigned)((n_words + 255) / 256), 256, 0, st>>>(d, n_bytes, bm.p, rank.p, n_words, n_cand, cand_off.p, up.p);
-    for (int k = 1; k < levels; ++k)
-        br_double_kernel<<<(unsigned)((stride + 255) / 256), 256, 0, st>>>(up.p + (int64_t)(k - 1) * stride, up.p + (int64_t)k * stride, stride);
-    br_count_kernel<<<1, 1, 0, st>>>(d, bm.p, up.p, levels, n_cand, cand_off.p, res.p);
-    int64_t h_res[3] = {0, 0, 0};
-    BWAMS_HIP(hipMemcpyAsync(h_res, res.p, 24, hipMemcpyDeviceToHost, st));
+    // the records: the chain from byte 0 must end at n_bytes
+    BrEnd ch;
+    if (int rc = disc.run(d, n_bytes, 0, n_bytes, st, &ch)) return rc;
     BWAMS_HIP(hipEventRecord(evs.b, st));
-    BWAMS_HIP(hipStreamSynchronize(st));
-    if (h_res[0] < 0) return bad_record(h_res[1], h_res[2]);
-    const int64_t n_rec = h_res[0], n1 = n_rec + 1;
+    if (ch.how != kBrStopped) return bad_record(ch.n_rec, ch.at);
+    const int64_t n_rec = ch.n_rec, n1 = n_rec + 1;
+    const uint32_t n_cand = disc.n_cand;
+    const int levels = disc.levels;
+    DevBuf<uint32_t> &up = disc.up;
+    DevBuf<int64_t> &cand_off = disc.cand_off;
+    DevBuf<> &scan_tmp = disc.scan_tmp;
     f->n_cand = n_cand;
     // measure, scans, the kept reads' offsets
     BWAMS_HIP(recs.alloc((size_t)n1 * sizeof(BrRec)));

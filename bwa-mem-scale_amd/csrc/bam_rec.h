@@ -56,4 +56,18 @@ __device__ __forceinline__ int64_t cigar_ref_len(const uint8_t *c, uint32_t n_ci
     return rlen;
 }
 
+
+// a record's place in coordinate order and the end reg2bin takes (bwams_bam_coord_t, include/bwams_types.h)
+__device__ __forceinline__ bwams_bam_coord_t bam_coord(const uint8_t *p) {
+    const int32_t rid = bam_ref_id(p), pos = bam_pos(p);
+    const uint32_t n_cig = bam_n_cig(p), flag = bam_flag(p);
+    const int64_t rlen = cigar_ref_len(p + bam_cigar_at(bam_l_name(p)), n_cig, 0, 1);
+    const int64_t end = ((flag & 4) || n_cig == 0 || rlen == 0) ? (int64_t)pos + 1 : (int64_t)pos + rlen;
+    bwams_bam_coord_t cd;
+    cd.key = (uint64_t)(uint32_t)rid << 32 | (uint64_t)(uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1);
+    cd.end = (int32_t)end;
+    cd.size = (int32_t)(bam_block_size(p) + 4);
+    return cd;
+}
+
 }  // namespace bwams

@@ -26,16 +26,9 @@ __global__ void __launch_bounds__(256) bam_sort_key_kernel(const uint8_t *bam, c
                                                            bwams_bam_coord_t *coord, uint64_t *dkey, uint32_t *idx) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
         const uint8_t *p = bam + rec_off[r];
-        const uint32_t block_size = bam_block_size(p);
-        const int32_t rid = bam_ref_id(p), pos = bam_pos(p);
-        const uint32_t n_cig = bam_n_cig(p), flag = bam_flag(p);
-        const int64_t rlen = cigar_ref_len(p + bam_cigar_at(bam_l_name(p)), n_cig, 0, 1);
-        const int64_t end = ((flag & 4) || n_cig == 0 || rlen == 0) ? (int64_t)pos + 1 : (int64_t)pos + rlen;
-        const uint64_t low = (uint64_t)(uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1);
-        bwams_bam_coord_t cd;
-        cd.key = (uint64_t)(uint32_t)rid << 32 | low;
-        cd.end = (int32_t)end;
-        cd.size = (int32_t)(block_size + 4);
+        const bwams_bam_coord_t cd = bam_coord(p);
+        const int32_t rid = (int32_t)(cd.key >> 32);
+        const uint64_t low = cd.key & 0xFFFFFFFFu;
         coord[r] = cd;
         dkey[r] = (uint64_t)(rid < 0 ? n_ref : (uint32_t)rid) << 32 | low;
         idx[r] = (uint32_t)r;

@@ -221,6 +221,27 @@ void launch_bam_sort_permute(const bwams_bam_coord_t *coord, const uint32_t *idx
 void launch_bam_sort_gather(const uint8_t *src, const int64_t *rec_off, const uint32_t *idx, const int64_t *new_off, int64_t n_rec,
                             uint8_t *dst, int cu_count, hipStream_t st);
 
+// bam_query.hip: one piece of a BAM file read by region (rules in include/bwams.h above bwams_bam_file_open).  d[0, n) holds whole
+// inflated members behind the carried bytes (16-byte aligned, 64 bytes of slack behind n); the record chain starts at `start` and
+// takes the records that begin below `stop`.  regions: rule 2's merged regions on the device, n_regions 0 keeps every record.  The
+// kept records go back to back into recs (with the 16 bytes of slack consumer_records documents), their offsets into roff
+// (n_kept + 1) and their coords into coords.  All on st, which is drained.
+struct BamQueryScratch;                  // the discovery's and the selection's device buffers
+BamQueryScratch *bam_query_scratch_new();
+void bam_query_scratch_free(BamQueryScratch *s);
+struct BamQueryResult {
+    int64_t n_rec, n_kept, kept_bytes, n_cand;
+    int64_t at;                          // behind the chain's last record
+    bool cut, bad;                       // at `at`: a record the end of the buffer cuts off / nothing well formed
+    int64_t cut_size;                    // the cut-off record's size when its block_size is there, else 0
+    int64_t bad_rec;                     // the first record with refID < -1 or POS outside [-1, 2^31 - 2], or -1
+    int64_t bad_rec_at;
+    float ms_discover, ms_select, ms_gather;
+};
+int bam_query_piece(BamQueryScratch *s, const uint8_t *d, int64_t n, int64_t start, int64_t stop, const bwams_pileup_region_t *regions,
+                    int32_t n_regions, DevBuf<uint8_t> &recs, DevBuf<int64_t> &roff, DevBuf<bwams_bam_coord_t> &coords, hipEvent_t ev[4],
+                    int cu_count, hipStream_t st, BamQueryResult *out);
+
 // markdup.hip: duplicate marking (rules in include/bwams.h above bwams_bam_templates).  md_templates groups n_rec records (at
 // bam + rec_off[r], 16 bytes of slack past the last) into templates: m.n_t templates, m.rtmpl[r] each record's, and the m.n_e ends
 // of the templates that have one, in template order, at m.ends; BWAMS_ERR_UNSUPPORTED (last error: the first record concerned) for

@@ -1,6 +1,6 @@
 // rec_consumer.h — what the handles that read BAM records on the device share (depth, pileup, QC, recalibration and its apply; host
-// only, for their api_*.hip): the base of the handle structs, the two ways to the records of an add (a batch's, in HBM; host
-// records, uploaded into the handle) with their refusals, and the timed sequences around a check kernel and around a piece's kernels.
+// only, for their api_*.hip): the base of the handle structs, the three ways to the records of an add (a batch's, in HBM; host
+// records, uploaded into the handle; the current piece of a BAM file read by region) with their refusals, and the timed sequences around a check kernel and around a piece's kernels.
 // A base struct and free functions: each *_add stays in its own file as check, size buffers, loop over pieces.
 #pragma once
 #include "stage_state.h"
@@ -81,6 +81,24 @@ inline int consumer_records(RecConsumer *c, const void *bam, int64_t n_bytes, co
     BWAMS_HIP(hipMemcpyAsync(c->roff.p, off.data(), (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
     BWAMS_HIP(hipStreamSynchronize(st));                     // the host vector above ends here
     *out = DevRecords{c->recs.p, c->roff.p, n_rec};
+    return BWAMS_OK;
+}
+
+// api_bam_file.hip: the current piece of f (refused with `who` and a text when it has none), the device and the stream of f
+int bam_file_piece(bwams_bam_file *f, const char *who, int *device, hipStream_t *stream, DevRecords *out);
+
+// The current piece of BAM file f for handle c (bwams_bam_file_next made it), with c's device current and what f has queued done.  The
+// records lie in f and stay until its next bwams_bam_file_next or _query.  refuse: as above.
+inline int consumer_file(const RecConsumer *c, bwams_bam_file *f, const char *who, DevRecords *out, const char *refuse = nullptr) {
+    if (!c || !f) return consumer_refusal(who, "a handle and a BAM file are required");
+    if (refuse) return consumer_refusal(who, refuse);
+    int device = 0;
+    hipStream_t stream = nullptr;
+    if (int rc = bam_file_piece(f, who, &device, &stream, out)) return rc;
+    if (device != c->device)
+        return consumer_refusal(who, "the handle is on device " + std::to_string(c->device) + ", the file on device " + std::to_string(device));
+    BWAMS_HIP(hipSetDevice(c->device));
+    BWAMS_HIP(hipStreamSynchronize(stream));
     return BWAMS_OK;
 }
 

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "bwams.h"
+#include "bam_query.h"
 
 namespace {
 
@@ -514,49 +515,22 @@ int bwams_reader_open_device2(const char *path, int device, int64_t chunk_bases,
     return BWAMS_OK;
 }
 
-// The BAM header block from the start of the stream: magic, l_text, text, n_ref, then l_name / name / l_ref per reference.  What was
-// inflated behind it becomes the reader's carry.
+// The BAM header block from the start of the stream (bam_header_read, host/bam_query.cpp: the parse a bwams_bam_file_t shares).  What
+// was inflated behind it becomes the reader's carry.
 static int bam_header_parse(bwams_reader *r) {
     std::vector<char> hb;
-    bool file_end = false;
-    auto need = [&](size_t n) -> int {                       // 0: hb holds n bytes
-        while (hb.size() < n) {
-            if (file_end) { r->err = "the file ends inside the BAM header"; return BWAMS_ERR_IO; }
-            const size_t have = hb.size();
-            const int64_t want = std::max<int64_t>(1 << 20, (int64_t)std::min<size_t>(n - have, (size_t)r->src->step));
-            hb.resize(have + (size_t)want);
-            std::string e_;
-            const int64_t got = r->src->read(hb.data() + have, want, e_);
+    bwams::BamHeader h;
+    const int rc = bwams::bam_header_read(
+        [r](char *dst, int64_t want, std::string &e) {
+            const int64_t got = r->src->read(dst, want, e);
             r->stats = r->src->st;
-            hb.resize(have + (size_t)std::max<int64_t>(got, 0));
-            if (got < 0) { r->err = e_; return (int)got; }
-            if (got == 0) file_end = true;
-        }
-        return BWAMS_OK;
-    };
-    auto i32 = [&](size_t at) {
-        const unsigned char *u = reinterpret_cast<const unsigned char *>(hb.data()) + at;
-        return (int32_t)((uint32_t)u[0] | (uint32_t)u[1] << 8 | (uint32_t)u[2] << 16 | (uint32_t)u[3] << 24);
-    };
-    if (int rc = need(4)) return rc;
-    if (memcmp(hb.data(), "BAM\1", 4) != 0) { r->err = "not a BAM file (no BAM\\1 magic)"; return BWAMS_ERR_UNSUPPORTED; }
-    if (int rc = need(8)) return rc;
-    const int64_t l_text = i32(4);
-    if (l_text < 0) { r->err = "BAM header: negative l_text"; return BWAMS_ERR_IO; }
-    if (int rc = need((size_t)(12 + l_text))) return rc;
-    r->bam_text.assign(hb.data() + 8, (size_t)l_text);
-    const int32_t n_ref = i32((size_t)(8 + l_text));
-    if (n_ref < 0) { r->err = "BAM header: negative n_ref"; return BWAMS_ERR_IO; }
-    size_t p = (size_t)(12 + l_text);
-    for (int32_t k = 0; k < n_ref; ++k) {
-        if (int rc = need(p + 4)) return rc;
-        const int64_t l_name = i32(p);
-        if (l_name < 1) { r->err = "BAM header: reference " + std::to_string(k) + " without a name"; return BWAMS_ERR_IO; }
-        if (int rc = need(p + 8 + (size_t)l_name)) return rc;
-        p += 8 + (size_t)l_name;
-    }
-    r->bam_n_ref = n_ref;
-    r->carry.assign(hb.begin() + (std::ptrdiff_t)p, hb.end());
+            return got;
+        },
+        r->src->step, &hb, &h, &r->err);
+    if (rc) return rc;
+    r->bam_text = h.text;
+    r->bam_n_ref = h.n_ref;
+    r->carry.assign(hb.begin() + (std::ptrdiff_t)h.end, hb.end());
     return BWAMS_OK;
 }
 

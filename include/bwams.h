@@ -1721,6 +1721,66 @@ int bwams_recal_apply_close(bwams_recal_apply_t *a);
 int bwams_recal_apply_records(bwams_recal_apply_t *a, void *bam, int64_t n_bytes, int64_t *n_rewritten);
 int bwams_recal_apply_batch(bwams_recal_apply_t *a, bwams_batch_t *b, int64_t *n_rewritten);
 int bwams_recal_apply_info(const bwams_recal_apply_t *a, bwams_recal_apply_info_t *info);
+
+/* ------------------------------------------------ BAM file by region ---- */
+
+/* A coordinate-sorted BAM file and its BAI (what bwams_sorter_close writes, or any other writer) read back as device records: the
+ * handle turns (file, index, regions) into pieces of records in HBM, which bwams_bam_file_fetch copies out and the five record
+ * consumers (depth, pileup, QC, recalibration and its apply) take where they lie.  bwams/bai.py restates the rules (overlapping,
+ * plan).  The file is untrusted input: everything below that can be wrong with it is an error return.
+ *  1. Overlap.  A record overlaps region (ref, beg, end) when its refID == ref, POS < end and its end > beg; the end is
+ *     bwams_bam_coord_t's: POS + the CIGAR's reference length, or POS + 1 for FLAG 0x4, no CIGAR or a reference length of 0.
+ *  2. Regions.  0 <= ref < n_ref and 0 <= beg < end each (BWAMS_ERR_ARG otherwise); in any order, overlapping or not.  They are
+ *     sorted by (ref, beg) and merged per reference where they overlap or touch before anything else, so a record that overlaps
+ *     several regions comes back once.  Records come back in file order.
+ *  3. Plan.  For every merged region: the chunks of the bins of reg2bins over [beg, end) (SAMv1 section 5.3; levels that the
+ *     coordinate overruns give no bin, and pseudo-bin 37450 is never a source of chunks) that end past the linear index's offset of
+ *     beg's 16 kb window (the window index clamped to the last entry; an empty linear index gives offset 0), each chunk's start
+ *     clipped to that offset.  The chunks of all regions are sorted by virtual offset and those that touch or overlap merged into
+ *     disjoint intervals.  bwams_bai_plan returns exactly these intervals from the bytes of a BAI (host only, no device; *n_chunks
+ *     their number, BWAMS_ERR_CAPACITY when cap is smaller; n_regions 0 gives none; n_ref is the index's).
+ *  4. Whole file (n_regions 0).  One interval from the first record behind the header to the end of the data; every record is kept,
+ *     unplaced ones (refID -1) included, and no index is needed.
+ *  5. Pieces.  Within an interval a piece is a run of whole BGZF members whose inflated size fits piece_bytes (0: 128 MiB; a piece
+ *     costs the inflater one call, so few large ones are faster; the handle holds some ten times piece_bytes of device memory).
+ *     Bytes behind the last whole record of a piece are carried, on the device, in front of the next piece of the same interval.  The
+ *     record chain of an interval's first piece starts at the in-block offset of the interval's start and stops at the interval's
+ *     end offset.  A piece may yield 0 records; *done is set together with the last piece, which may be empty.  A single record
+ *     larger than piece_bytes is BWAMS_ERR_CAPACITY, with its size in the text.
+ *  6. Refusals.  No index and n_regions > 0: BWAMS_ERR_ARG.  An index whose n_ref differs from the header's, or that is cut off:
+ *     BWAMS_ERR_IO at open.  A chunk that points past the file or not at a member, a member that fails CRC or ISIZE, a chain
+ *     that reaches a position where no well-formed record starts (rule 1 of bwams_bam_reads_decode; a record cut off by the end
+ *     of a piece is the carry, not an error, while members follow), a record with refID < -1 or POS outside [-1, 2^31 - 2]:
+ *     BWAMS_ERR_IO from bwams_bam_file_next, with the file offset of the piece and the record's ordinal in the query; the query is
+ *     over then.  _next, _fetch and the consumers' _file calls before _query, _fetch and those before the first _next, or any of
+ *     them after a _next that followed the last piece: BWAMS_ERR_ARG with a text.  A consumer on another device: refused as a
+ *     batch on another device is.
+ * bwams_bam_file_open: bai_path NULL takes <path>.bai when it can be read and no index otherwise.  _header and _refs: the header
+ * text (not NUL terminated; it lives as long as the handle), n_ref, and the references' lengths (cap >= n_ref).  _query starts a
+ * query and ends the one before; _next makes the next piece current (*n_records, *n_bytes: its kept records); _fetch copies the
+ * current piece's records (cap >= *n_bytes, BWAMS_ERR_CAPACITY otherwise) and, when coords is not NULL, their *n_records coords to
+ * the host.  The consumers' _add_file calls add the current piece exactly as their _add_records calls add host records, with the
+ * same checks and counts; bwams_recal_apply_file rewrites the piece where it lies, so that _fetch then returns the new bytes.  The
+ * piece stays current until the next _next or _query.  One caller at a time.
+ * The kernels: the record discovery of bwams_bam_reads_decode (csrc/bam_discover.h) from an offset to an offset; a select kernel, a
+ * lane per record, with the merged regions in LDS; two scans; the sorter's gather into the handle's record buffer.  _info: a test
+ * and measurement hook (bwams_bam_file_info_t, include/bwams_types.h).
+ * Out of scope: CRAM, CSI and tabix indexes, unsorted input beyond whole-file mode, several files merged, writing. */
+int bwams_bam_file_open(const char *path, const char *bai_path, int device, int64_t piece_bytes, bwams_bam_file_t **out);
+int bwams_bam_file_header(const bwams_bam_file_t *f, const char **text, int64_t *n_text, int32_t *n_ref);
+int bwams_bam_file_refs(const bwams_bam_file_t *f, int32_t *l_ref, int32_t cap);
+int bwams_bam_file_query(bwams_bam_file_t *f, const bwams_pileup_region_t *regions, int32_t n_regions);
+int bwams_bam_file_next(bwams_bam_file_t *f, int64_t *n_records, int64_t *n_bytes, int32_t *done);
+int bwams_bam_file_fetch(bwams_bam_file_t *f, void *bam, int64_t cap, bwams_bam_coord_t *coords);
+int bwams_bam_file_info(const bwams_bam_file_t *f, bwams_bam_file_info_t *info);
+int bwams_bam_file_close(bwams_bam_file_t *f);
+int bwams_depth_add_file(bwams_depth_t *d, bwams_bam_file_t *f, int64_t *n_counted);
+int bwams_pileup_add_file(bwams_pileup_t *p, bwams_bam_file_t *f, int64_t *n_counted);
+int bwams_qc_add_file(bwams_qc_t *q, bwams_bam_file_t *f, int64_t *n_counted);
+int bwams_recal_add_file(bwams_recal_t *r, bwams_bam_file_t *f, int64_t *n_counted);
+int bwams_recal_apply_file(bwams_recal_apply_t *a, bwams_bam_file_t *f, int64_t *n_rewritten);
+int bwams_bai_plan(const void *bai, int64_t n_bai, const bwams_pileup_region_t *regions, int32_t n_regions, uint64_t *chunk_beg,
+                   uint64_t *chunk_end, int64_t cap, int64_t *n_chunks);
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -536,6 +536,20 @@ typedef struct bwams_recal_apply_info {
     float   ms_check, ms_apply;
 } bwams_recal_apply_info_t;
 
+/* A BAM file read back by region (include/bwams.h, "BAM file by region").  A file handle lives on one device. */
+typedef struct bwams_bam_file bwams_bam_file_t;
+
+/* bwams_bam_file_info: totals since the last bwams_bam_file_query.  intervals: the plan's; members and compressed_bytes: what was
+ * read of the file and inflated to inflated_bytes; candidates: offsets that passed the discovery's filter; records_seen: records of
+ * the chains, records_kept: those rule 1 kept; pieces; carried: bytes moved in front of a next piece.  The times are for measurement
+ * only (tools/bam_query_rate.py): ms_read and ms_inflate by the host clock around pread and bwams_inflater_run, the others device
+ * time between events around the discovery, the select kernel with its scans, and the compaction with the gather. */
+typedef struct bwams_bam_file_info {
+    int64_t intervals, members, compressed_bytes, inflated_bytes, candidates, records_seen, records_kept, pieces, carried;
+    float   ms_read, ms_inflate, ms_discover, ms_select, ms_gather;
+    int32_t pad_;
+} bwams_bam_file_info_t;
+
 #ifdef __cplusplus
 }
 #endif
