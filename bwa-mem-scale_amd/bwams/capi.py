@@ -25,6 +25,7 @@ SEQPAIR_DTYPE = np.dtype([(n, "<i4") for n in
 SYMBOLS = [
     "bwams_strerror", "bwams_last_error", "bwams_device_count", "bwams_debug_reload",
     "bwams_index_open", "bwams_index_from_host", "bwams_index_from_device", "bwams_index_close",
+    "bwams_debug_sa_dense_state", "bwams_debug_sa_dense_fetch", "bwams_debug_sa_dense_release",
     "bwams_index_bytes", "bwams_index_build", "bwams_index_fetch", "bwams_index_save", "bwams_reg2aln_run", "bwams_reg2aln_run_sam", "bwams_reg2aln_fetch",
     "bwams_index_set_contig_names", "bwams_index_set_contig_annos", "bwams_sam_upload", "bwams_sam_run", "bwams_sam_run_pe", "bwams_sam_run_emf", "bwams_sam_fetch",
     "bwams_process_chunk", "bwams_process_chunk_smart", "bwams_process_chunk2", "bwams_emf_regs_merge", "bwams_fastq_decode", "bwams_fastq_info", "bwams_fastq_has_qual", "bwams_fastq_fetch", "bwams_fastq_to_batch", "bwams_fastq_to_batch_opt", "bwams_fastq_close", "bwams_batch_create", "bwams_batch_destroy", "bwams_seed_fmi",
@@ -1463,6 +1464,9 @@ def lib():
         L.bwams_index_fetch_fma.argtypes = [vp, vp, vp]
         L.bwams_index_bytes.restype = i64
         L.bwams_index_bytes.argtypes = [vp]
+        L.bwams_debug_sa_dense_state.argtypes = [vp, vp, vp, vp, vp]
+        L.bwams_debug_sa_dense_fetch.argtypes = [vp, vp, i64, vp]
+        L.bwams_debug_sa_dense_release.argtypes = [C.c_int, vp]
         L.bwams_batch_create.argtypes = [vp, i64, i64, i64, i64, vp]
         L.bwams_batch_destroy.argtypes = [vp]
         L.bwams_seed_fmi.argtypes = [vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]
@@ -1708,10 +1712,34 @@ class Index:
     def nbytes(self) -> int:
         return lib().bwams_index_bytes(self.h)
 
+    def sa_dense_state(self):
+        """(state, stride, bytes, build_ms) of the dense suffix-array table; state as SA_DENSE_STATES names it (test hook)"""
+        st, sr, nb, ms = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_float(0)
+        _chk(lib().bwams_debug_sa_dense_state(self.h, C.byref(st), C.byref(sr), C.byref(nb), C.byref(ms)), "bwams_debug_sa_dense_state")
+        return SA_DENSE_STATES[st.value], sr.value, nb.value, ms.value
+
+    def sa_dense_fetch(self) -> np.ndarray:
+        """the dense suffix-array table as uint64 entries: coordinate | sentinel << 40 | steps << 41 (test hook; small indexes)"""
+        n = C.c_int64(0)
+        _chk(lib().bwams_debug_sa_dense_fetch(self.h, None, 0, C.byref(n)), "bwams_debug_sa_dense_fetch")
+        out = np.zeros(n.value, np.uint64)
+        _chk(lib().bwams_debug_sa_dense_fetch(self.h, _p(out), len(out), C.byref(n)), "bwams_debug_sa_dense_fetch")
+        return out
+
     def close(self):
         if self.h:
             lib().bwams_index_close(self.h)
             self.h = None
+
+
+SA_DENSE_STATES = ("absent", "built", "refused", "yielded")
+
+
+def sa_dense_release(device: int = 0) -> int:
+    """what the library's allocator does when `device` is out of memory: every dense suffix-array table there is released (test hook)"""
+    n = C.c_int32(0)
+    _chk(lib().bwams_debug_sa_dense_release(device, C.byref(n)), "bwams_debug_sa_dense_release")
+    return n.value
 
 
 class Emf:

@@ -41,6 +41,10 @@ void knobs_reload() {
     k.qc_lanes = env_int("BWAMS_QC_LANES", 1);
     k.recal_lds = env_int("BWAMS_RECAL_LDS", 1);
     k.ert_ticket = env_int("BWAMS_ERT_TICKET", 1); k.ert_grid = env_int("BWAMS_ERT_GRID", -1); k.ert_fat = env_int("BWAMS_ERT_FAT", 1);
+    k.sa_dense = env_int("BWAMS_SA_DENSE", kSaDenseDefault);
+    if (k.sa_dense != 0 && k.sa_dense != 1 && k.sa_dense != 2 && k.sa_dense != 4) k.sa_dense = kSaDenseDefault;
+    { const char *mb = getenv("BWAMS_SA_DENSE_MAX_BYTES"); k.sa_dense_max_bytes = mb && *mb ? atoll(mb) : 0; }
+    k.sort_narrow = env_int("BWAMS_SORT_NARROW", 1);
     g_knobs = k;
 }
 const Knobs &knobs() {

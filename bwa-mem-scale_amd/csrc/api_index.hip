@@ -7,7 +7,101 @@
 namespace bwams {
 int fmi_build_device(bwams_index *ix, const uint8_t *d_fw, int64_t l_pac, int keep_ref, int64_t chunk_rows, int verbose,
                      bwams_build_stats_t *bs);                   // fmi_build.hip
+
+// Every live index, for sa_dense_release.  Lock order: g_ix_mu, then an index's sa_mu; nothing allocates under either but the
+// table's own build, which does not come back here (dev_malloc's may_yield = false).
+static std::mutex g_ix_mu;
+static std::vector<bwams_index *> g_ix;
 }
+
+bwams_index::bwams_index() {
+    std::lock_guard<std::mutex> reg(bwams::g_ix_mu);
+    bwams::g_ix.push_back(this);
+}
+bwams_index::~bwams_index() {
+    std::lock_guard<std::mutex> reg(bwams::g_ix_mu);
+    for (size_t i = 0; i < bwams::g_ix.size(); ++i)
+        if (bwams::g_ix[i] == this) { bwams::g_ix.erase(bwams::g_ix.begin() + i); break; }
+}
+
+namespace bwams {
+
+// The caller's current device is `device` (dev_malloc: the device it allocates on).  A lookup that reads a table was launched under
+// the shared lock, so once the exclusive lock is held every such launch is queued and the device synchronisation waits for it.
+int sa_dense_release(int device) {
+    int n = 0;
+    std::lock_guard<std::mutex> reg(g_ix_mu);
+    for (bwams_index *ix : g_ix) {
+        if (ix->device != device) continue;
+        std::unique_lock<std::shared_mutex> lock(ix->sa_mu);
+        if (ix->sa_state != BWAMS_SA_DENSE_BUILT) continue;
+        (void)hipDeviceSynchronize();
+        ix->d_sa_dense.release();
+        ix->sa_bytes = 0;
+        ix->sa_state = BWAMS_SA_DENSE_YIELDED;           // for the rest of the index's life: no rebuild, nothing thrashes
+        if (knobs().verbose) fprintf(stderr, "[sa_dense] device %d out of memory: the table of stride %d gave way\n", device, ix->sa_stride);
+        ++n;
+    }
+    return n;
+}
+
+// The table of ix, built at its first FM-index seeding that wants coordinates.  A table that is switched off, above the cap, not
+// allocatable or not representable leaves the index walking (state "refused"): no error.
+int sa_dense_ensure(bwams_index *ix, int cu_count, hipStream_t st) {
+    const Knobs &kn = knobs();
+    if (kn.sa_dense == 0) return BWAMS_OK;
+    {
+        std::shared_lock<std::shared_mutex> lock(ix->sa_mu);
+        if (ix->sa_state != BWAMS_SA_DENSE_ABSENT) return BWAMS_OK;
+    }
+    std::unique_lock<std::shared_mutex> lock(ix->sa_mu);
+    if (ix->sa_state != BWAMS_SA_DENSE_ABSENT) return BWAMS_OK;
+    const int stride = kn.sa_dense;
+    const int64_t n = sa_dense_entries(ix->fmi.ref_seq_len, stride), bytes = n * 8;
+    ix->sa_stride = stride;
+    if (kn.sa_dense_max_bytes > 0 && bytes > kn.sa_dense_max_bytes) {
+        ix->sa_state = BWAMS_SA_DENSE_REFUSED;
+        return BWAMS_OK;
+    }
+    DevBuf<> t;
+    if (t.alloc((size_t)bytes + 8, false) != hipSuccess) {            // + the build's flag word; never through the yielding path
+        (void)hipGetLastError();
+        ix->sa_state = BWAMS_SA_DENSE_REFUSED;
+        if (kn.verbose) fprintf(stderr, "[sa_dense] no room for %.1f GiB: the index keeps the walk\n", bytes / 1073741824.0);
+        return BWAMS_OK;
+    }
+    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(t.as<uint64_t>() + n), bad = 0;
+    hipEvent_t ev[2];
+    BWAMS_HIP(hipEventCreate(&ev[0]));
+    BWAMS_HIP(hipEventCreate(&ev[1]));
+    hipError_t e = hipMemsetAsync(d_bad, 0, 8, st);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) {
+        launch_sa_dense_build(ix->fmi, stride, n, t.as<uint64_t>(), d_bad, cu_count, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    BWAMS_HIP(e);
+    ix->sa_build_ms = ms;
+    if (bad) {
+        fprintf(stderr, "[sa_dense] a walk of this index does not fit the table's %d-bit step field: the index keeps the walk\n", kSaDenseStepBits);
+        ix->sa_state = BWAMS_SA_DENSE_REFUSED;
+        return BWAMS_OK;
+    }
+    ix->d_sa_dense = std::move(t);
+    ix->sa_bytes = bytes;
+    ix->sa_state = BWAMS_SA_DENSE_BUILT;
+    if (kn.verbose) fprintf(stderr, "[sa_dense] stride %d: %lld entries, %.2f GiB, built in %.1f ms\n", stride, (long long)n, bytes / 1073741824.0, ms);
+    return BWAMS_OK;
+}
+
+}  // namespace bwams
 
 using namespace bwams;
 
@@ -216,7 +310,43 @@ int bwams_index_close(bwams_index_t *ix) {
     return BWAMS_OK;
 }
 
+// the index's own arrays: what it derives at its first seeding (the search kernels' table, the dense suffix-array table) is not in
+// here — a fresh handle and a used one of the same index report the same (bwams_debug_sa_dense_state reports the dense table's bytes)
 int64_t bwams_index_bytes(const bwams_index_t *ix) { return ix ? ix->bytes : 0; }
+
+int bwams_debug_sa_dense_state(bwams_index_t *ix, int32_t *state, int32_t *stride, int64_t *bytes, float *build_ms) {
+    if (!ix) return BWAMS_ERR_ARG;
+    std::shared_lock<std::shared_mutex> lock(ix->sa_mu);
+    if (state) *state = ix->sa_state;
+    if (stride) *stride = ix->sa_stride;
+    if (bytes) *bytes = ix->sa_bytes.load();
+    if (build_ms) *build_ms = ix->sa_build_ms;
+    return BWAMS_OK;
+}
+
+int bwams_debug_sa_dense_fetch(bwams_index_t *ix, uint64_t *out, int64_t cap, int64_t *n) {
+    if (!ix || !n) return BWAMS_ERR_ARG;
+    BWAMS_HIP(hipSetDevice(ix->device));
+    std::shared_lock<std::shared_mutex> lock(ix->sa_mu);                // the table cannot give way under the copy
+    if (ix->sa_state != BWAMS_SA_DENSE_BUILT) {
+        set_last_error("bwams_debug_sa_dense_fetch: the index holds no dense table");
+        return BWAMS_ERR_ARG;
+    }
+    *n = sa_dense_entries(ix->fmi.ref_seq_len, ix->sa_stride);
+    if (!out) return BWAMS_OK;
+    if (cap < *n) return BWAMS_ERR_CAPACITY;
+    BWAMS_HIP(hipMemcpy(out, ix->d_sa_dense.p, (size_t)*n * 8, hipMemcpyDeviceToHost));
+    return BWAMS_OK;
+}
+
+int bwams_debug_sa_dense_release(int device, int32_t *n_released) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    BWAMS_HIP(hipSetDevice(device));
+    const int n = sa_dense_release(device);
+    if (n_released) *n_released = n;
+    return BWAMS_OK;
+}
 
 /* ------------------------------------------------------------------- FMA ---- */
 

@@ -50,21 +50,29 @@ namespace {
 int sort_pool(bwams_batch *b, const char *who, int64_t n_keys, int64_t n, int64_t *sa_cnt, int max_occ) {
     bwams_batch::Seed &sd = b->sd;
     hipStream_t st = b->stream;
-    // key = rid << 32 | m << 16 | n; chunk holes carry rid = nseq and sort behind every read
-    launch_make_keys(sd.d_pool.p, n_keys, sd.d_keys.p, sd.d_vals.p, (uint32_t)b->nseq, st);
+    // key = rid << 2w | m << w | n; chunk holes carry rid = nseq and sort behind every read.  m and n are positions in a read: w = 8
+    // when the batch's longest read has at most 255 bases (36 key bits for a chunk of 1 M 150-base reads, 52 with w = 16)
+    const int w = b->max_read_len <= 255 && knobs().sort_narrow ? 8 : 16;
+    launch_make_keys(sd.d_pool.p, n_keys, sd.d_keys.p, sd.d_vals.p, (uint32_t)b->nseq, w, st);
     int rid_bits = 1;
     while (((int64_t)1 << rid_bits) <= b->nseq) rid_bits++;
     if (int rc = with_tmp(b, who, [&](void *tmp, size_t &tb) {     // the temporary size depends on the size / bit range: ask for this call
-            return rocprim::radix_sort_pairs(tmp, tb, sd.d_keys.p, sd.d_keys2.p, sd.d_vals.p, sd.d_vals2.p, (size_t)n_keys, 0, 32 + rid_bits, st);
+            return rocprim::radix_sort_pairs(tmp, tb, sd.d_keys.p, sd.d_keys2.p, sd.d_vals.p, sd.d_vals2.p, (size_t)n_keys, 0, 2 * w + rid_bits, st);
         })) return rc;
     launch_gather_sorted(sd.d_pool.p, sd.d_vals2.p, n, sd.d_sorted.p, sa_cnt, max_occ, st);
     return BWAMS_OK;
 }
 
 // The lookups of the last pass' n sorted SMEMs, as the pass and the re-run behind a grown SA buffer (bwams_seed_counts) launch them
+// The index's dense table is read and the kernel that reads it launched under the shared lock: a release on another thread then
+// waits for this launch before it frees (api_index.hip: sa_dense_release).  Nothing allocates in here.
 void fm_lookup(bwams_batch *b, int64_t n) {
     bwams_batch::Seed &sd = b->sd;
-    launch_sa_lookup(b->idx->fmi, sd.d_sorted.p, n, sd.d_sa_off.p, sd.d_sa_coord.p, b->max_sa, sd.last_opt.max_occ, b->d_ctr.p, b->cu_count, b->stream);
+    bwams_index *ix = b->idx;
+    std::shared_lock<std::shared_mutex> lock(ix->sa_mu);
+    const bool use = ix->sa_state == BWAMS_SA_DENSE_BUILT && knobs().sa_dense != 0;
+    launch_sa_lookup(ix->fmi, sd.d_sorted.p, n, sd.d_sa_off.p, sd.d_sa_coord.p, b->max_sa, sd.last_opt.max_occ, b->d_ctr.p, b->cu_count, b->stream,
+                     use ? ix->d_sa_dense.as<const uint64_t>() : nullptr, ix->sa_stride);
 }
 void ert_locate(bwams_batch *b, int64_t n) {
     bwams_batch::Seed &sd = b->sd;
@@ -194,6 +202,9 @@ static int seed_run_once(bwams_batch_t *b, const bwams_seed_opt_t *opt, int with
         }
         cp2 = ix->d_cp2.as<const uint4>();
     }
+    // the lookup's dense table, the same way: once per index, at its first FM-index seeding that wants coordinates
+    if (with_sa)
+        if (int rc = sa_dense_ensure(b->idx, b->cu_count, st)) return rc;
     SeedLaunch a;
     a.fmi = b->idx->fmi;
     a.fmi.cp2 = cp2;

@@ -1,9 +1,11 @@
 // common.h — internal declarations shared by the HIP translation units.
 #pragma once
 
+#include <atomic>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <shared_mutex>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -21,8 +23,9 @@ void set_last_error(const std::string &s);
 // another chunk left dirty (a fresh process gets zeros).  tests: the whole `-m gpu` suite passes under it.
 // Debugging aids and A-B switches, all of them result-neutral: read from the environment ONCE (at the first call into the library; again
 // on bwams_debug_reload(), which the tests call after changing a variable) — never per call on the hot host path.  include/bwams.h lists them.
+constexpr int kSaDenseDefault = 1;       // profiles/sa_dense.md: the stride table
 struct Knobs {
-    int verbose = 0;               // BWAMS_VERBOSE: stage times and counters per run on stderr
+    int verbose = 0;              // BWAMS_VERBOSE: stage times and counters per run on stderr
     int debug = 0;                 // BWAMS_DEBUG: diagnostic ablations of the SMEM search (bit 0: no SMEM is written)
     int poison = 0;                // BWAMS_POISON: fresh device allocations are filled with 0xAB
     int bwd_min_list = 40, bwd_cols = 24, bwd_late_list = 8;                     // BWAMS_BWD_MIN_LIST / _COLS / _LATE_LIST   (fmi_seed.hip: bwd_hand_over)
@@ -45,13 +48,26 @@ struct Knobs {
     int qc_lanes = 1;              // BWAMS_QC_LANES=0: the QC add's per-cycle tables come from the plain kernel (one global atomic per base and per quality)
     int recal_lds = 1;             // BWAMS_RECAL_LDS=0: the recalibration add counts through the plain kernel (one global atomic per update)
     int ert_grid = -1, ert_ticket = 1;   // BWAMS_ERT_GRID (blocks per CU, 0 = one block per 256 bases) / BWAMS_ERT_TICKET=0 (round robin)
+    int sa_dense = kSaDenseDefault;      // BWAMS_SA_DENSE: stride of an index's dense suffix-array table, 1 / 2 / 4; 0 = never built, never read
+    int64_t sa_dense_max_bytes = 0;      // BWAMS_SA_DENSE_MAX_BYTES: a table above it is not built (0: no cap)
+    int sort_narrow = 1;                 // BWAMS_SORT_NARROW=0: the SMEM sort keys keep 16-bit position fields whatever the longest read
 };
 const Knobs &knobs();
 void knobs_reload();
 
-template <class T> static inline hipError_t dev_malloc(T **p, size_t bytes) {
+// The dense suffix-array tables are a cache that gives way (api_index.hip): every table of an index on `device` is released, for
+// good; returns how many were.  dev_malloc calls it when the device is out of memory; bwams_debug_sa_dense_release is the same call.
+int sa_dense_release(int device);
+
+// may_yield = false: the dense table's own allocation, which must not release the tables to make room for itself
+template <class T> static inline hipError_t dev_malloc(T **p, size_t bytes, bool may_yield = true) {
     const bool poison = knobs().poison != 0;
     hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
+    if (e == hipErrorOutOfMemory && may_yield) {
+        int dev = 0;
+        (void)hipGetLastError();
+        if (hipGetDevice(&dev) == hipSuccess && sa_dense_release(dev) > 0) e = hipMalloc(reinterpret_cast<void **>(p), bytes);
+    }
     if (e == hipSuccess && poison && bytes) {
         e = hipMemset(*p, 0xAB, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();     // hipMemset on the null stream does not order with non-blocking streams
@@ -78,9 +94,9 @@ template <class T = void, bool Host = false> struct Buf {
         p = nullptr;
         cap = 0;
     }
-    hipError_t alloc(size_t bytes) {
+    hipError_t alloc(size_t bytes, bool may_yield = true) {
         release();
-        hipError_t e = Host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : dev_malloc(&p, bytes);
+        hipError_t e = Host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : dev_malloc(&p, bytes, may_yield);
         cap = p ? bytes : 0;
         return e;
     }
@@ -745,6 +761,16 @@ struct bwams_index {
     bwams::DevBuf<> d_cp, d_ms, d_ls, d_ref;
     bwams::DevBuf<> d_cp2;                       // the search kernels' table derived from the CP_OCC array at the first FM-index seeding;
     std::mutex cp2_mu;                           // ... published under this lock once built, freed only by bwams_index_close
+    // The dense suffix-array table (fmi_kernels.h), built at the first FM-index seeding with coordinates and released, for good, when
+    // the device runs out of memory (DESIGN.md "The dense suffix-array table").  sa_mu guards the four fields: shared to read the
+    // pointer and launch the lookup that reads it, exclusive to build and to release.
+    bwams::DevBuf<> d_sa_dense;
+    std::shared_mutex sa_mu;
+    int sa_state = BWAMS_SA_DENSE_ABSENT, sa_stride = 0;
+    float sa_build_ms = 0;
+    std::atomic<int64_t> sa_bytes{0};            // the table's bytes while it is resident (bwams_debug_sa_dense_state)
+    bwams_index();                               // api_index.hip: every index is known to sa_dense_release while it lives
+    ~bwams_index();
     bwams::DevBuf<> d_all, d_last;               // FMA tables
     bwams::DevBuf<> d_contigs;                   // bwams_contig_t[n_seqs]; empty = one sequence [0, l_pac)
     int32_t n_seqs = 0;
@@ -758,6 +784,7 @@ struct bwams_index {
 
 namespace bwams {
 int bns_save(bwams_index *ix, const char *prefix);     // fasta_ref.hip: writes <prefix>.ann, .amb, .pac
+int sa_dense_ensure(bwams_index *ix, int cu_count, hipStream_t st);   // api_index.hip: builds ix's dense table unless it has a state already
 int bam_names_index(bwams_index *ix, const char *names, const int32_t *name_off, int32_t n);   // bam.hip, from set_contig_names
 }
 

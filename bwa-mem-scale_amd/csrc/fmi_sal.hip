@@ -11,6 +11,11 @@
 // Mapping: every lookup is an independent chain of at most 7 dependent block
 // reads, so one LANE per lookup; the owning SMEM is found by binary search in the
 // prefix offsets, which stay L2-resident.
+//
+// SA[row] depends on the index alone: with the index's dense table (one entry per
+// S-th row holding what the walk from that row produces, fmi_kernels.h) a lookup
+// walks only to the next multiple of S and reads the rest; both counters stay what
+// the reference walks.
 #include "fmi_kernels.h"
 
 namespace bwams {
@@ -20,10 +25,12 @@ __device__ __forceinline__ uint64_t mk64(uint32_t lo, uint32_t hi) {
     return (uint64_t)lo | ((uint64_t)hi << 32);
 }
 
+// S = 0: no table, every row walks to a sample of the index; S = 1, 2, 4: the dense table of that stride
+template <int S>
 __global__ __launch_bounds__(256) void sa_lookup_kernel(DevFmi f, const bwams_smem_t *__restrict__ sm,
                                                         int64_t n_smem, const int64_t *__restrict__ sa_off,
                                                         int64_t *__restrict__ coord, int64_t coord_cap,
-                                                        int max_occ, DevCounters *ctr) {
+                                                        int max_occ, DevCounters *ctr, const uint64_t *__restrict__ dense) {
     const int64_t total = sa_off[n_smem] < coord_cap ? sa_off[n_smem] : coord_cap;
     unsigned long long lf = 0;
     // The owner of position g is the last SMEM whose first position is <= g: a binary search over 9 M offsets, i.e. 23
@@ -78,32 +85,21 @@ __global__ __launch_bounds__(256) void sa_lookup_kernel(DevFmi f, const bwams_sm
         const int64_t k = sm[lo].k, s = sm[lo].s;
         const int64_t step = s > (int64_t)max_occ ? s / max_occ : 1;
         int64_t sp = k + (g - sa_off[lo]) * step;
-        int64_t off = 0, val = 0;
-        while (true) {
-            if ((sp & 7) == 0) {
-                val = ((int64_t)f.sa_ms[sp >> 3] << 32) + (int64_t)f.sa_ls[sp >> 3] + off;
-                break;
+        int64_t val;
+        if constexpr (S == 0) {
+            const SaWalk w = sa_walk<8>(f, sp);
+            val = w.sentinel ? 0 : sa_sample(f, w.sp) + (int64_t)w.steps;
+            lf += w.steps;
+        } else {
+            // at most S - 1 steps of its own, then the entry of the row reached: what the reference's walk from there produces
+            const SaWalk w = sa_walk<S>(f, sp);
+            uint64_t e = kSaDenseSentinel;
+            if (!w.sentinel) {
+                e = dense[S == 1 ? w.sp : S == 2 ? w.sp >> 1 : w.sp >> 2];
+                lf += e >> (kSaDenseCoordBits + 1);
             }
-            const uint4 *p = f.cp + ((sp >> 6) << 2);
-            // the whole block in one round trip: the count of the row's base would otherwise be a second, dependent load
-            const uint4 c01 = p[0], c23 = p[1], h01 = p[2], h23 = p[3];
-            const int sh = 63 - (int)(sp & 63);
-            const uint64_t h0 = mk64(h01.x, h01.y), h1 = mk64(h01.z, h01.w);
-            const uint64_t h2 = mk64(h23.x, h23.y), h3 = mk64(h23.z, h23.w);
-            int b = 4;
-            uint64_t hb = 0;
-            if ((h0 >> sh) & 1) { b = 0; hb = h0; }
-            else if ((h1 >> sh) & 1) { b = 1; hb = h1; }
-            else if ((h2 >> sh) & 1) { b = 2; hb = h2; }
-            else if ((h3 >> sh) & 1) { b = 3; hb = h3; }
-            if (b == 4) { val = 0; break; }
-            const int y = (int)(sp & 63);
-            const uint64_t mask = y ? (~0ull << (64 - y)) : 0ull;
-            const int64_t cnt = (int64_t)(b == 0 ? mk64(c01.x, c01.y) : b == 1 ? mk64(c01.z, c01.w) : b == 2 ? mk64(c23.x, c23.y) : mk64(c23.z, c23.w));
-            sp = (b == 0 ? f.count[0] : b == 1 ? f.count[1] : b == 2 ? f.count[2] : f.count[3]) + cnt +
-                 __popcll(hb & mask);
-            off++;
-            lf++;
+            val = (e & kSaDenseSentinel) ? 0 : (int64_t)(e & (kSaDenseSentinel - 1)) + (int64_t)w.steps;
+            lf += w.steps;
         }
         coord[g] = val;
     }
@@ -113,13 +109,34 @@ __global__ __launch_bounds__(256) void sa_lookup_kernel(DevFmi f, const bwams_sm
     if (blockIdx.x == 0 && threadIdx.x == 0) ctr->n_sa_lookups = (unsigned long long)sa_off[n_smem];
 }
 
+// One lane per entry: the present walk from row i * stride, packed
+__global__ __launch_bounds__(256) void sa_dense_build_kernel(DevFmi f, int stride, int64_t n, uint64_t *__restrict__ table,
+                                                             unsigned long long *bad) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const SaWalk w = sa_walk<8>(f, i * stride);
+        if (w.steps >> kSaDenseStepBits) *bad = 1;
+        const uint64_t c = w.sentinel ? kSaDenseSentinel : (uint64_t)(sa_sample(f, w.sp) + (int64_t)w.steps);
+        if (!w.sentinel && (c >> kSaDenseCoordBits)) *bad = 1;
+        table[i] = c | ((uint64_t)w.steps << (kSaDenseCoordBits + 1));
+    }
+}
+
 }  // namespace
 
 void launch_sa_lookup(const DevFmi &f, const bwams_smem_t *sorted, int64_t n_smem, const int64_t *sa_off,
                       int64_t *coord, int64_t coord_cap, int max_occ, DevCounters *ctr, int cu_count,
-                      hipStream_t st) {
+                      hipStream_t st, const uint64_t *dense, int stride) {
     if (n_smem <= 0) return;
-    sa_lookup_kernel<<<cu_count * 8, 256, 0, st>>>(f, sorted, n_smem, sa_off, coord, coord_cap, max_occ, ctr);
+    const unsigned grid = (unsigned)cu_count * 8;
+    if (!dense) sa_lookup_kernel<0><<<grid, 256, 0, st>>>(f, sorted, n_smem, sa_off, coord, coord_cap, max_occ, ctr, nullptr);
+    else if (stride == 1) sa_lookup_kernel<1><<<grid, 256, 0, st>>>(f, sorted, n_smem, sa_off, coord, coord_cap, max_occ, ctr, dense);
+    else if (stride == 2) sa_lookup_kernel<2><<<grid, 256, 0, st>>>(f, sorted, n_smem, sa_off, coord, coord_cap, max_occ, ctr, dense);
+    else sa_lookup_kernel<4><<<grid, 256, 0, st>>>(f, sorted, n_smem, sa_off, coord, coord_cap, max_occ, ctr, dense);
+}
+
+void launch_sa_dense_build(const DevFmi &f, int stride, int64_t n, uint64_t *table, unsigned long long *bad, int cu_count, hipStream_t st) {
+    if (n <= 0) return;
+    sa_dense_build_kernel<<<grid_of(n, 256, cu_count, 32), 256, 0, st>>>(f, stride, n, table, bad);
 }
 
 }  // namespace bwams

@@ -1459,14 +1459,15 @@ __global__ __launch_bounds__(kBlock) void seed_strategy_kernel(SeedLaunch a, int
     flush_counters(a.ctr, n_ext, n_blk, true);
 }
 
-// (rid, m, n) sort key of each pooled SMEM
+// (rid, m, n) sort key of each pooled SMEM: m and n in pos_bits bits each (8 when no read of the batch is longer than 255 bases, else 16)
 __global__ void make_keys_kernel(const bwams_smem_t *pool, int64_t n, uint64_t *keys, uint32_t *vals,
-                                 uint32_t hole_key_rid) {
+                                 uint32_t hole_key_rid, int pos_bits) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const bwams_smem_t s = pool[i];
         const uint32_t rid = s.rid == kHoleRid ? hole_key_rid : s.rid;     // holes behind every read
-        keys[i] = ((uint64_t)rid << 32) | ((uint64_t)(s.m & 0xffff) << 16) | (uint64_t)(s.n & 0xffff);
+        const uint32_t mask = (1u << pos_bits) - 1;
+        keys[i] = ((uint64_t)rid << (2 * pos_bits)) | ((uint64_t)(s.m & mask) << pos_bits) | (uint64_t)(s.n & mask);
         vals[i] = (uint32_t)i;
     }
 }
@@ -1563,9 +1564,9 @@ void launch_smem_round3(const SeedLaunch &a, int max_intv, int cu_count, hipStre
 }
 
 void launch_make_keys(const bwams_smem_t *pool, int64_t n, uint64_t *keys, uint32_t *vals, uint32_t hole_key_rid,
-                      hipStream_t st) {
+                      int pos_bits, hipStream_t st) {
     if (n <= 0) return;
-    make_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(pool, n, keys, vals, hole_key_rid);
+    make_keys_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(pool, n, keys, vals, hole_key_rid, pos_bits);
 }
 
 void launch_gather_sorted(const bwams_smem_t *pool, const uint32_t *order, int64_t n, bwams_smem_t *sorted,

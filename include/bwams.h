@@ -59,7 +59,11 @@ const char *bwams_last_error(void);
  *   BWAMS_PILEUP_TILED=0    every record of a pileup add goes through the direct kernel, one global atomic per base (tools/pileup_rate.py)
  *   BWAMS_QC_LANES=0        the QC add's per-cycle tables come from the plain kernel, one global atomic per base and per quality (tools/qc_rate.py)
  *   BWAMS_RECAL_LDS=0       the recalibration add counts through the plain kernel, one global atomic per update (tools/recal_rate.py)
- *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6) */
+ *   BWAMS_ERT_GRID, BWAMS_ERT_FAT=0, BWAMS_ERT_TICKET=0   ERT walk launch shape        BWAMS_HOST_THREADS   host threads of mem_process_seqs' staging (6)
+ *   BWAMS_SA_DENSE=0 / 1 / 2 / 4   stride of the dense suffix-array table an index derives at its first FM-index seeding with coordinates
+ *     (8 bytes for every stride-th row; the lookup then takes at most stride - 1 LF steps of its own); 0: never built, never read
+ *   BWAMS_SA_DENSE_MAX_BYTES   a table above it is not built and the index keeps the walk (default: no cap)
+ *   BWAMS_SORT_NARROW=0   the SMEM sort keys keep 16-bit position fields whatever the batch's longest read */
 int bwams_debug_reload(void);
 int bwams_device_count(int *n);
 
@@ -220,7 +224,27 @@ int bwams_deflater_destroy(bwams_deflater_t *d);
 int bwams_index_load_bns(bwams_index_t *idx, const char *prefix);
 
 int bwams_index_close(bwams_index_t *idx);
+/* Device bytes of the index's own arrays.  What it derives at its first seeding is not counted here: the same index reports the
+ * same number before and after (the dense suffix-array table's bytes: bwams_debug_sa_dense_state below). */
 int64_t bwams_index_bytes(const bwams_index_t *idx);
+
+/* The dense suffix-array table of an index: a cache derived from the index at its first bwams_seed_run with coordinates
+ * (BWAMS_SA_DENSE, BWAMS_SA_DENSE_MAX_BYTES above), one 64-bit entry for every row r with r % stride == 0: bits 0-39 the
+ * coordinate the reference's walk from r produces, bit 40 set when that walk meets the sentinel row (the lookup yields 0), bits
+ * 41-63 the LF steps of the walk.  When ANY device allocation of the library runs out of memory, the tables of the indexes on
+ * that device are released and the allocation is tried once more; a released index walks for the rest of its life.  Results and
+ * counters are the same in every state. */
+enum { BWAMS_SA_DENSE_ABSENT = 0,     /* not built (yet, or BWAMS_SA_DENSE=0) */
+       BWAMS_SA_DENSE_BUILT = 1,
+       BWAMS_SA_DENSE_REFUSED = 2,    /* above the cap, no room for it, or a walk too long for the step field: the index walks */
+       BWAMS_SA_DENSE_YIELDED = 3 };  /* released to make room: the index walks */
+/* Test hooks (not part of the drop-in surface).  _state: the state above, the stride (0 before a build was tried), the table's
+ * bytes while it is resident, the build kernel's time; any pointer may be null.  _fetch: *n = the table's entries, copied to out
+ * when out is given (cap entries; BWAMS_ERR_CAPACITY when too few); BWAMS_ERR_ARG unless the state is BUILT.  _release: the routine
+ * the allocator calls on out-of-memory, for `device`; *n_released = tables released. */
+int bwams_debug_sa_dense_state(bwams_index_t *idx, int32_t *state, int32_t *stride, int64_t *bytes, float *build_ms);
+int bwams_debug_sa_dense_fetch(bwams_index_t *idx, uint64_t *out, int64_t cap, int64_t *n);
+int bwams_debug_sa_dense_release(int device, int32_t *n_released);
 
 /* ---------------------------------------------------------------- batch ---- */
 
@@ -739,8 +763,9 @@ int bwams_debug_aln_lists(bwams_batch_t *b, int64_t counts[4]);
 typedef struct bwams_stats {
     int64_t n_ext;            /* backwardExt evaluations */
     int64_t n_ext_blocks;     /* CP_OCC blocks they touch: 1 when k and k+s share a block, else 2 */
-    int64_t n_sa_lookups;
-    int64_t n_lf_steps;
+    int64_t n_sa_lookups;     /* suffix-array rows looked up */
+    int64_t n_lf_steps;       /* LF steps the REFERENCE walks for them (to its 1/8 samples): the same number whether the lookup
+                                 walked them or read them from the index's dense table (BWAMS_SA_DENSE) */
     int64_t n_smem[3];        /* SMEMs from round 1, 2, 3 */
     int64_t bsw_cells;        /* DP cells evaluated by the last bsw run */
     int64_t n_ext_round[3];   /* n_ext split by round */
