@@ -78,6 +78,9 @@ SYMBOLS = [
     "bwams_bam_file_open", "bwams_bam_file_header", "bwams_bam_file_refs", "bwams_bam_file_query", "bwams_bam_file_next", "bwams_bam_file_fetch",
     "bwams_bam_file_info", "bwams_bam_file_close", "bwams_depth_add_file", "bwams_pileup_add_file", "bwams_qc_add_file", "bwams_recal_add_file",
     "bwams_recal_apply_file", "bwams_bai_plan",
+    "bwams_dupjoin_open", "bwams_dupjoin_reset", "bwams_dupjoin_close", "bwams_dupjoin_add_records", "bwams_dupjoin_add_file",
+    "bwams_dupjoin_finish", "bwams_dupjoin_fetch", "bwams_dupjoin_apply_records", "bwams_dupjoin_apply_file", "bwams_dupjoin_info",
+    "bwams_dupjoin_key", "bwams_bam_file_header_block",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -1056,6 +1059,12 @@ class BamFile(_Handle):
         self._call("bwams_bam_file_header", C.byref(t), C.byref(n), C.byref(nr))
         return C.string_at(t, n.value) if n.value else b"", nr.value
 
+    def header_block(self) -> bytes:
+        """the file's BAM header (magic to the last reference) as Sorter takes it"""
+        b, n = C.c_void_p(), C.c_int64(0)
+        self._call("bwams_bam_file_header_block", C.byref(b), C.byref(n))
+        return C.string_at(b, n.value) if n.value else b""
+
     def refs(self) -> np.ndarray:
         """the references' lengths"""
         out = np.zeros(max(self.header()[1], 1), np.int32)
@@ -1098,6 +1107,68 @@ class BamFile(_Handle):
     def info(self) -> dict:
         """bwams_bam_file_info: the totals since the last query"""
         return self._info("bwams_bam_file_info", BamFileInfo)
+
+
+class DupJoinInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("records", "templates", "ends", "adds", "applied", "hbm_bytes", "entry_bytes")] + \
+               [("state", C.c_int32), ("pad_", C.c_int32)] + \
+               [(n, C.c_float) for n in ("ms_add", "ms_sort", "ms_ends", "ms_decide", "ms_apply", "pad2_")]
+
+
+def dupjoin_key(name: bytes) -> tuple[int, int]:
+    """bwams_dupjoin_key: rule J1's (k0, k1) of a read name, computed by the library on the host"""
+    name = bytes(name)
+    key = (C.c_uint64 * 2)()
+    _chk(lib().bwams_dupjoin_key(name, len(name), key), "bwams_dupjoin_key")
+    return int(key[0]), int(key[1])
+
+
+class DupJoin(_Consumer):
+    """Duplicate marking of records that are not query-grouped (bwams_dupjoin_t): templates joined by name.  Pass 1: add_records /
+    add_file over every piece; finish(); pass 2: apply_records / apply_file over the same pieces in the same order."""
+    _close = "bwams_dupjoin_close"
+    _prefix = "bwams_dupjoin"
+
+    def __init__(self, groups=None, device: int = 0, distance: int = 0, max_set: int = 0, opt=True):
+        self.h = C.c_void_p()
+        o = _dup_opt(distance, max_set)
+        self.n_lib = groups.n_lib if groups is not None else 1
+        _chk(lib().bwams_dupjoin_open(device, _groups_h(groups), C.byref(o) if opt else None, C.byref(self.h)), "bwams_dupjoin_open")
+
+    def add_batch(self, batch: "Batch") -> int:
+        raise NotImplementedError("a batch's templates are adjacent: Batch.bam_markdup2 serves them")
+
+    def finish(self):
+        """-> (DupStats, rule 13's rows as DUP_LIB_STATS_DTYPE)"""
+        st = DupStats()
+        rows = np.zeros(self.n_lib, DUP_LIB_STATS_DTYPE)
+        self._call("bwams_dupjoin_finish", C.byref(st), _p(rows), len(rows))
+        return st, rows
+
+    def fetch(self):
+        """-> (ends: DUP_END_DTYPE, locs: DUP_LOC_DTYPE, rec_tmpl: uint32 by ordinal, dup, optical: uint8 per template)"""
+        i = self.info()
+        ends, locs = np.zeros(max(i["ends"], 1), DUP_END_DTYPE), np.zeros(max(i["ends"], 1), DUP_LOC_DTYPE)
+        rt = np.zeros(max(i["records"], 1), np.uint32)
+        dup, optical = np.zeros(max(i["templates"], 1), np.uint8), np.zeros(max(i["templates"], 1), np.uint8)
+        self._call("bwams_dupjoin_fetch", _p(ends), _p(locs), i["ends"], _p(rt), i["records"], _p(dup), _p(optical), i["templates"])
+        return ends[:i["ends"]], locs[:i["ends"]], rt[:i["records"]], dup[:i["templates"]], optical[:i["templates"]]
+
+    def apply_records(self, records: bytes):
+        """-> (the records of the next add with 0x400 set or cleared, the records marked)"""
+        buf = np.frombuffer(bytes(records), np.uint8).copy()
+        n = C.c_int64(0)
+        self._call("bwams_dupjoin_apply_records", _p(buf), len(buf), C.byref(n))
+        return buf.tobytes(), n.value
+
+    def apply_file(self, bam_file: "BamFile") -> int:
+        """Marks the BamFile's current piece where it lies; -> the records marked"""
+        n = C.c_int64(0)
+        self._call("bwams_dupjoin_apply_file", bam_file.h, C.byref(n))
+        return n.value
+
+    def info(self) -> dict:
+        return self._info("bwams_dupjoin_info", DupJoinInfo)
 
 
 class Gunzipper:
@@ -1447,6 +1518,18 @@ def lib():
         for name in ("bwams_depth_add_file", "bwams_pileup_add_file", "bwams_qc_add_file", "bwams_recal_add_file", "bwams_recal_apply_file"):
             getattr(L, name).argtypes = [vp, vp, vp]
         L.bwams_bai_plan.argtypes = [vp, i64, vp, i32, vp, vp, i64, vp]
+        L.bwams_bam_file_header_block.argtypes = [vp, vp, vp]
+        L.bwams_dupjoin_open.argtypes = [C.c_int, vp, vp, vp]
+        L.bwams_dupjoin_reset.argtypes = [vp]
+        L.bwams_dupjoin_close.argtypes = [vp]
+        L.bwams_dupjoin_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_dupjoin_add_file.argtypes = [vp, vp, vp]
+        L.bwams_dupjoin_finish.argtypes = [vp, vp, vp, i64]
+        L.bwams_dupjoin_fetch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64]
+        L.bwams_dupjoin_apply_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_dupjoin_apply_file.argtypes = [vp, vp, vp]
+        L.bwams_dupjoin_info.argtypes = [vp, vp]
+        L.bwams_dupjoin_key.argtypes = [C.c_char_p, i32, vp]
         L.bwams_dup_groups_rg_id.argtypes = [vp, i64]
         L.bwams_dup_groups_rg_id.restype = C.c_char_p
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -80,6 +80,37 @@ primary whose 0x1 differs from the template's first primary's, a mapped primary 
    line.  PERCENT_DUPLICATION is printed as %.6f; ESTIMATED_LIBRARY_SIZE is left empty when there is none.  Picard's histogram
    section is not written.
 
+Templates joined by name (bwams_dupjoin_t, csrc/dup_join.hip): duplicate marking of records that are not query-grouped, such as a
+coordinate-sorted BAM.  Rules 2 to 15 hold unchanged except where a rule below says otherwise.  "Add order" is the order of the adds,
+then record order within each; a record's ordinal is its 0-based place in add order.
+
+J1. Name key.  L = l_read_name - 1, the name without its NUL.  For each of two seeds S0 = 0x9e3779b97f4a7c15 and S1 =
+    0xc2b2ae3d27d4eb4f: h = S ^ L; then for i in [0, max(1, ceil(L / 8))): h = fmix64(h ^ w_i), where w_i is the name's bytes
+    [8i, 8i + 8) as a little-endian 64-bit word, zero-padded past L, and fmix64 is MurmurHash3's finalizer (h ^= h >> 33; h *=
+    0xff51afd7ed558ccd; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53; h ^= h >> 33; mod 2^64).  The key is (k0, k1).  Names of at most 8
+    bytes cannot collide within one length: one bijective step.
+J2. Template: all added records with equal (L, k0, k1), adjacent or not.  This replaces rule 1.  Its ordinal is its rank by the
+    ordinal of its first record.  Two different names with equal L and key would be taken for one template (among 2^32 names the
+    chance of any such pair is below 2^-65); the consequence is a wrong 0x400 or a refusal by rule 2.  More than 2^32 - 1 records
+    are refused.
+J3. The walk.  Rules 2 to 5 are applied to a template's records in ordinal order: "the earlier record" of rule 5 is the one with
+    the smaller ordinal, "the first record concerned" of rule 2 the smallest ordinal at which any template's walk meets a fault.
+    So two primaries of one segment that share a name are refused wherever they lie; the adjacent-run rule takes them for two
+    templates when they are apart.
+J4. Read group, library, location.  Rules 9 and 10 take the template's first primary in add order, or its first record when it has no
+    primary.  With a groups table every added record's aux fields are walked at the add; a record that does not chain refuses that
+    add (MarkdupRefusal with reason AUX, naming the smallest such ordinal), before rules 2-3 are looked at.  Without a table no aux
+    field is read.
+J5. Decision and tie-breaks.  Rule 6 and rules 11 to 13 apply; "earlier template" means the smaller template ordinal of J2.
+J6. Marking.  Rule 7 applies: every record of a duplicate template is marked, secondary, supplementary and unmapped-mate records
+    included, wherever they lie.  This is what the query-grouped path does, and more than Picard does on coordinate-sorted input.
+J7. Defined over what was added.  A paired primary whose mate was never added makes a fragment; the whole file is the intended input.
+J8. Pass 2 (the library only): apply call i takes the records of add i, checked by their count and two sums of their k0.
+J9. States (the library only): empty -> adding -> finished.
+
+name_key(name) -> (k0, k1); join(adds, table) -> (n_templates, ends, rec_tmpl by ordinal, locs parallel to ends, each template's
+library); mark_joined(adds, header_text, distance, max_set) -> (marked records per add, rule 8's counts, rule 13's rows).
+
 groups(header_text) -> Groups (rule 9); read_group(rec) -> the RG:Z value or None; location(name) -> (tile, x, y) or None;
 ends2(records, groups) -> ends' (n_templates, ends, rec_tmpl, locs, each template's library); decide2(ends, locs, n_templates, n_lib,
 distance, max_set) -> (dup, optical, per-library rows); mark2(runs, header_text, distance, max_set) -> (marked records per run,
@@ -526,3 +557,124 @@ def metrics_text(table: Groups | None, rows, comment: str = "") -> str:
         size = r["estimated_library_size"]
         out.append("\t".join([name] + [str(r[k]) for k in LIB_COUNTS] + ["%.6f" % r["percent_duplication"], "" if size < 0 else str(size)]))
     return "\n".join(out) + "\n\n"
+
+
+# ---- templates joined by name: rules J1-J9 ----
+
+JOIN_SEEDS = (0x9e3779b97f4a7c15, 0xc2b2ae3d27d4eb4f)
+_M64 = (1 << 64) - 1
+
+
+def _fmix64(h: int) -> int:
+    h ^= h >> 33
+    h = h * 0xff51afd7ed558ccd & _M64
+    h ^= h >> 33
+    h = h * 0xc4ceb9fe1a85ec53 & _M64
+    return h ^ h >> 33
+
+
+def name_key(name) -> tuple[int, int]:
+    """J1: (k0, k1) of a read name (bytes, without its NUL)."""
+    name = bytes(name)
+    out = []
+    for seed in JOIN_SEEDS:
+        h = seed ^ len(name)
+        for i in range(max(1, (len(name) + 7) // 8)):
+            h = _fmix64(h ^ int.from_bytes(name[8 * i:8 * i + 8], "little"))
+        out.append(h)
+    return out[0], out[1]
+
+
+def join(adds, table: Groups | None = None):
+    """J1-J4 over adds (records per add, in add order): (n_templates, the ends of the templates that have one in template order,
+    each record's template by ordinal, locs parallel to ends, each template's library), refusing with MarkdupRefusal."""
+    recs = []
+    for add in adds:
+        piece = _records(add)
+        if table:                                                    # J4: every record of the add is walked, and refuses that add
+            for k, r in enumerate(piece):
+                try:
+                    read_group(r)
+                except ValueError:
+                    raise MarkdupRefusal(len(recs) + k, AUX) from None
+        recs += piece
+    by_key = {}                                                      # J2: insertion order is the order of the first records
+    for o, r in enumerate(recs):
+        name = r[36:36 + max(r[12] - 1, 0)]
+        by_key.setdefault((len(name),) + name_key(name), []).append(o)
+    n_lib = table.n_lib if table else 1
+    out, rec_tmpl, faults, tloc = [], [0] * len(recs), [], []
+    for t, members in enumerate(by_key.values()):
+        seg, paired, fault = {}, None, None
+        for o in members:                                            # J3: rules 2-5 in ordinal order
+            rec_tmpl[o] = t
+            f = _flag(recs[o])
+            if fault or f & 0x900:
+                continue
+            p = f & 1
+            if paired is None:
+                paired = p
+            if p != paired:
+                fault = (o, 2)
+            elif p and bool(f & 0x40) == bool(f & 0x80):
+                fault = (o, 1)
+            else:
+                s = "only" if not p else "first" if f & 0x40 else "last"
+                if s in seg:
+                    fault = (o, 0)
+                elif not f & 4 and (struct.unpack_from("<i", recs[o], 4)[0] < 0 or not -(1 << 31) <= unclipped_5p(recs[o]) < 1 << 31):
+                    fault = (o, 3)
+                else:
+                    seg[s] = o
+        named = next((o for o in members if not _flag(recs[o]) & 0x900), members[0])      # J4
+        rg = -1
+        if table:
+            v = read_group(recs[named])
+            rg = table.ids.index(v) if v in table.ids else -1
+        at = location(recs[named][36:36 + max(recs[named][12] - 1, 0)])
+        tile, x, y = at if at else (0, 0, 0)
+        tloc.append(dict(lib=table.lib_of(rg) if table else n_lib - 1, rg=rg, tile=tile, x=x, y=y, has=int(at is not None)))
+        if fault:
+            faults.append(fault)
+            continue
+        mapped = {s: o for s, o in seg.items() if not _flag(recs[o]) & 4}
+
+        def half(o):
+            rec = recs[o]
+            return (struct.unpack_from("<i", rec, 4)[0], unclipped_5p(rec), _flag(rec) >> 4 & 1, score(rec))
+        if "first" in mapped and "last" in mapped:
+            e1, e2 = (half(o) for o in sorted((mapped["first"], mapped["last"])))
+            if (e2[0], e2[1]) < (e1[0], e1[1]):
+                e1, e2 = e2, e1
+            out.append(dict(tmpl=t, ref1=e1[0], pos1=e1[1], ref2=e2[0], pos2=e2[1], score=e1[3] + e2[3], strands=e1[2] | e2[2] << 1))
+        elif len(mapped) == 1:
+            e1 = half(next(iter(mapped.values())))
+            out.append(dict(tmpl=t, ref1=e1[0], pos1=e1[1], ref2=-1, pos2=0, score=e1[3], strands=e1[2]))
+    if faults:
+        raise MarkdupRefusal(*min(faults))
+    return len(by_key), out, rec_tmpl, [tloc[e["tmpl"]] for e in out], [t["lib"] for t in tloc]
+
+
+def mark_joined(adds, header_text=None, distance: int = 0, max_set: int = MAX_SET):
+    """J1-J7 over adds as one input: (marked records per add, rule 8's counts, rule 13's rows)."""
+    table = groups(header_text) if header_text is not None else None
+    n_lib = table.n_lib if table else 1
+    pieces = [_records(a) for a in adds]
+    n_t, es, rt, locs, tlib = join(pieces, table)
+    dup, _optical, rows = decide2(es, locs, n_t, n_lib, distance, max_set)
+    flat = [r for piece in pieces for r in piece]
+    for r, t in zip(flat, rt):
+        f = _flag(r)
+        if f & 4:
+            rows[tlib[t]]["unmapped"] += 1
+        elif f & 0x900:
+            rows[tlib[t]]["secondary_or_supplementary"] += 1
+    counts = dict(templates=n_t, records_marked=sum(dup[t] for t in rt))
+    for k in ("unpaired_examined", "unpaired_duplicates", "pairs_examined", "pair_duplicates"):
+        counts[k] = sum(r[k] for r in rows)
+    counts["percent_duplication"] = percent_duplication(counts)
+    out, base = [], 0
+    for piece in pieces:
+        out.append(b"".join(set_dup(r, dup[t]) for r, t in zip(piece, rt[base:base + len(piece)])))
+        base += len(piece)
+    return out, counts, rows

@@ -65,6 +65,35 @@ int groups_upload(DevBuf<uint8_t> &g_ids, DevBuf<int64_t> &g_off, DevBuf<int32_t
     G->n_rg = (int32_t)n; G->n_lib = (int32_t)g->libs.size(); G->walk = 1;
     return BWAMS_OK;
 }
+// the decision's counts (md_decide: pairs, pair duplicates, fragment duplicates) as the caller's statistics
+void dup_stats(bwams_dup_stats_t *st, int64_t n_t, int64_t n_e, const int64_t cnt[3], float ms) {
+    memset(st, 0, sizeof *st);
+    st->templates = n_t;
+    st->pairs_examined = cnt[0];
+    st->unpaired_examined = n_e - cnt[0];
+    st->pair_duplicates = cnt[1];
+    st->unpaired_duplicates = cnt[2];
+    st->ms_decide = ms;
+}
+
+// rule 13's rows from the device's counts (md_decide's and md_lib_recs': 7 words per library), rule 14 and the percentage added
+void lib_rows(bwams_dup_lib_stats_t *rows, int64_t n_lib, const unsigned long long *c) {
+    for (int64_t k = 0; k < n_lib; ++k, c += 7) {
+        bwams_dup_lib_stats_t &r = rows[k];
+        memset(&r, 0, sizeof r);
+        r.unpaired_examined = (int64_t)c[0]; r.pairs_examined = (int64_t)c[1]; r.unpaired_duplicates = (int64_t)c[2];
+        r.pair_duplicates = (int64_t)c[3]; r.pair_optical_duplicates = (int64_t)c[4]; r.secondary_or_supplementary = (int64_t)c[5];
+        r.unmapped = (int64_t)c[6];
+        dup_lib_finish(&r);
+    }
+}
+
+// opt as md_decide takes it: d (0: off) and the largest group examined; false for a negative value
+bool dup_opt_values(const bwams_dup_opt_t *opt, int64_t *d, int64_t *max_set) {
+    *d = opt ? opt->optical_distance : 0;
+    *max_set = opt && opt->max_optical_set ? opt->max_optical_set : 300000;
+    return *d >= 0 && *max_set > 0;
+}
 }  // namespace bwams
 
 extern "C" {
@@ -306,36 +335,6 @@ int bwams_bam_templates_fetch(bwams_batch_t *b, bwams_dup_end_t *ends, int64_t c
     return BWAMS_OK;
 }
 
-// the decision's counts (md_decide: pairs, pair duplicates, fragment duplicates) as the caller's statistics
-static void dup_stats(bwams_dup_stats_t *st, int64_t n_t, int64_t n_e, const int64_t cnt[3], float ms) {
-    memset(st, 0, sizeof *st);
-    st->templates = n_t;
-    st->pairs_examined = cnt[0];
-    st->unpaired_examined = n_e - cnt[0];
-    st->pair_duplicates = cnt[1];
-    st->unpaired_duplicates = cnt[2];
-    st->ms_decide = ms;
-}
-
-// rule 13's rows from the device's counts (md_decide's and md_lib_recs': 7 words per library), rule 14 and the percentage added
-static void lib_rows(bwams_dup_lib_stats_t *rows, int64_t n_lib, const unsigned long long *c) {
-    for (int64_t k = 0; k < n_lib; ++k, c += 7) {
-        bwams_dup_lib_stats_t &r = rows[k];
-        memset(&r, 0, sizeof r);
-        r.unpaired_examined = (int64_t)c[0]; r.pairs_examined = (int64_t)c[1]; r.unpaired_duplicates = (int64_t)c[2];
-        r.pair_duplicates = (int64_t)c[3]; r.pair_optical_duplicates = (int64_t)c[4]; r.secondary_or_supplementary = (int64_t)c[5];
-        r.unmapped = (int64_t)c[6];
-        dup_lib_finish(&r);
-    }
-}
-
-// opt as md_decide takes it: d (0: off) and the largest group examined; false for a negative value
-static bool opt_values(const bwams_dup_opt_t *opt, int64_t *d, int64_t *max_set) {
-    *d = opt ? opt->optical_distance : 0;
-    *max_set = opt && opt->max_optical_set ? opt->max_optical_set : 300000;
-    return *d >= 0 && *max_set > 0;
-}
-
 static int decide_host(int device, const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_ends, int64_t n_templates,
                        int64_t n_lib, const bwams_dup_opt_t *opt, uint8_t *dup, uint8_t *optical, bwams_dup_lib_stats_t *lib_stats,
                        int64_t cnt[3]) {
@@ -344,7 +343,7 @@ static int decide_host(int device, const bwams_dup_end_t *ends, const bwams_dup_
         set_last_error("bwams_dup_decide: host ends and a dup array of n_templates bytes are required");
         return BWAMS_ERR_ARG;
     }
-    if (n_lib < 1 || n_lib > 0x7FFFFFFF || !opt_values(opt, &d, &max_set)) {
+    if (n_lib < 1 || n_lib > 0x7FFFFFFF || !dup_opt_values(opt, &d, &max_set)) {
         set_last_error("bwams_dup_decide: n_lib >= 1, optical_distance >= 0 and max_optical_set >= 0 are required");
         return BWAMS_ERR_ARG;
     }
@@ -478,7 +477,7 @@ int bwams_bam_lib_record_counts(bwams_batch_t *b, int64_t *secondary_or_suppleme
 int bwams_bam_markdup2(bwams_batch_t *b, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt, bwams_dup_stats_t *st,
                        bwams_dup_lib_stats_t *lib_stats, int64_t cap_lib) {
     int64_t n_t = 0, n_e = 0, d = 0, max_set = 0;
-    if (!opt_values(opt, &d, &max_set)) {
+    if (!dup_opt_values(opt, &d, &max_set)) {
         set_last_error("bwams_bam_markdup2: optical_distance >= 0 and max_optical_set >= 0 are required");
         return BWAMS_ERR_ARG;
     }

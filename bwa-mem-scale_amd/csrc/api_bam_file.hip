@@ -101,6 +101,13 @@ int bwams_bam_file_header(const bwams_bam_file_t *f, const char **text, int64_t 
     return BWAMS_OK;
 }
 
+int bwams_bam_file_header_block(const bwams_bam_file_t *f, const void **block, int64_t *n) {
+    if (!f || !block || !n) return BWAMS_ERR_ARG;
+    *block = f->host.header_block.data();
+    *n = (int64_t)f->host.header_block.size();
+    return BWAMS_OK;
+}
+
 int bwams_bam_file_refs(const bwams_bam_file_t *f, int32_t *l_ref, int32_t cap) {
     if (!f || cap < 0 || (cap && !l_ref)) return BWAMS_ERR_ARG;
     if (cap < f->host.hdr.n_ref)

@@ -263,7 +263,7 @@ int bam_query_piece(BamQueryScratch *s, const uint8_t *d, int64_t n, int64_t sta
 // of the templates that have one, in template order, at m.ends; BWAMS_ERR_UNSUPPORTED (last error: the first record concerned) for
 // rules 2-3.  md_decide: rule 6 over device ends[0, n_e) into device dup[0, n_t) (zeroed first); counts = pairs, pair duplicates,
 // fragment duplicates.  launch_md_apply: FLAG 0x400 of the record at rec_off[i] from dup[rtmpl[perm ? perm[i] : i]] (*n_marked counts
-// the records set).  launch_md_gather32: dst[i] = src[idx[i]].
+// the records set).  launch_md_gather32 / _gather64: dst[i] = src[idx[i]].
 struct MdRec {                           // one record as the template kernel reads it
     int64_t c;                           // unclipped 5' coordinate of a mapped primary (rule 3), else 0
     int32_t rid;
@@ -305,6 +305,47 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
 void launch_md_apply(uint8_t *bam, const int64_t *rec_off, const uint32_t *perm, const uint32_t *rtmpl, const uint8_t *dup, int64_t n_rec,
                      unsigned long long *n_marked, int cu_count, hipStream_t st);
 void launch_md_gather32(const uint32_t *src, const uint32_t *idx, int64_t n, uint32_t *dst, int cu_count, hipStream_t st);
+void launch_md_gather64(const uint64_t *src, const uint32_t *idx, int64_t n, uint64_t *dst, int cu_count, hipStream_t st);
+const char *md_reason_text(int reason);  // the text of refusal reason 0-3 (rules 2-3) or 4 (rule 9's aux walk)
+
+// dup_join.hip: templates joined by read name (rules J1-J9 in include/bwams.h above bwams_dupjoin_open).  One entry per added record,
+// as arrays indexed by the record's ordinal: J1's key, L, the MdRec, and rules 9-10 of the record itself.
+struct DjEntries {
+    DevBuf<uint64_t> k0, k1;
+    DevBuf<uint8_t> len;
+    DevBuf<MdRec> rec;
+    DevBuf<bwams_dup_loc_t> loc;
+};
+constexpr int64_t kDjEntryBytes = 8 + 8 + 1 + (int64_t)sizeof(MdRec) + (int64_t)sizeof(bwams_dup_loc_t);      // 57 per record
+struct DjScratch {                       // of dj_join: freed with the entries
+    DevBuf<uint64_t> ka, kb;
+    DevBuf<uint32_t> i1, i2, first, tid, tstart;
+    DevBuf<uint8_t> head, has;
+    DevBuf<bwams_dup_end_t> tend;
+    DevBuf<unsigned long long> info;
+    DevBuf<> tmp;
+    void release() { ka.release(); kb.release(); i1.release(); i2.release(); first.release(); tid.release(); tstart.release();
+                     head.release(); has.release(); tend.release(); info.release(); tmp.release(); }
+};
+struct DjJoined {                        // what dj_join leaves: each record's template, the ends and their locs, each template's loc
+    DevBuf<uint32_t> rec_tmpl;
+    DevBuf<bwams_dup_end_t> ends;
+    DevBuf<bwams_dup_loc_t> locs, tloc;
+    int64_t n_t = 0, n_e = 0;
+};
+// The entries of the n records at bam + rec_off[r] into E's arrays from `base` on (room for base + n is the caller's).  call[0] +=
+// the sum of their k0 mod 2^64, call[1] += the sum of (2r + 1) * k0, call[2] = min(call[2], the ordinal of a record whose aux
+// fields do not chain) when G.walk.
+void launch_dj_entries(const uint8_t *bam, const int64_t *rec_off, int64_t n, int64_t base, const MdGroupsDev &G, DjEntries &E,
+                       unsigned long long *call, int cu_count, hipStream_t st);
+// J8's check: sum[0] and sum[1] += the two sums of k0 over the n records
+void launch_dj_key_sum(const uint8_t *bam, const int64_t *rec_off, int64_t n, unsigned long long *sum, int cu_count, hipStream_t st);
+// J2-J4 over entries [0, n): the sorts, the template ordinals, the walks and the ends.  BWAMS_ERR_UNSUPPORTED with `who`, the first
+// record concerned and the reason in the last error for rules 2-3.  ms: host-clock milliseconds of the sorts and of the rest.
+int dj_join(const DjEntries &E, int64_t n, DjScratch &S, DjJoined &J, const char *who, float ms[2], int cu_count, hipStream_t st);
+// rule 13's two record-level counts into counts[lib * 7 + 5 .. 6] and *n_marked += the records whose template is a duplicate
+void launch_dj_counts(const MdRec *rec, const uint32_t *rec_tmpl, const bwams_dup_loc_t *tloc, const uint8_t *dup, int64_t n, int n_lib,
+                      unsigned long long *counts, unsigned long long *n_marked, int cu_count, hipStream_t st);
 
 // api_bam.hip: the offsets of host BAM records bam[0, n_bytes) (n + 1 of them) from their block_size chain, with the checks of
 // bwams_bam_upload (every record whole, block_size >= 32, refID >= -1, POS in [-1, 2^31 - 2], name and CIGAR inside the record) and
@@ -601,6 +642,12 @@ void launch_qc_cycles(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec,
 // api_bam.hip: the groups table as the device reads it, uploaded into the caller's buffers (g null: no table, G->walk = 0)
 int groups_upload(DevBuf<uint8_t> &g_ids, DevBuf<int64_t> &g_off, DevBuf<int32_t> &g_ord, DevBuf<int32_t> &g_lib,
                   const bwams_dup_groups_t *g, MdGroupsDev *G, hipStream_t st);
+// api_bam.hip: md_decide's counts (pairs, pair duplicates, fragment duplicates) as bwams_dup_stats_t; rule 13's rows from the device's
+// counts (7 words per library), rule 14 and the percentage added; opt as md_decide takes it (d, 0: off; the largest group examined),
+// false for a negative value
+void dup_stats(bwams_dup_stats_t *st, int64_t n_t, int64_t n_e, const int64_t cnt[3], float ms);
+void lib_rows(bwams_dup_lib_stats_t *rows, int64_t n_lib, const unsigned long long *c);
+bool dup_opt_values(const bwams_dup_opt_t *opt, int64_t *d, int64_t *max_set);
 
 // recal.hip: base recalibration tables (rules in include/bwams.h above bwams_recal_open).
 // The store: a nibble per reference position, bits 0-2 the reference code 0..4, bit 3 the known-site flag; eight nibbles to a 32-bit

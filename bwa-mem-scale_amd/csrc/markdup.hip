@@ -50,24 +50,12 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "common.h"
-#include "bam_rec.h"
-#include "aux_rg.h"
+#include "markdup_dev.h"
 
 namespace bwams {
 namespace {
 
-constexpr int kQualMin = 15, kScoreCap = 16383;
 constexpr int32_t kMaxRef = 1 << 30;                  // refIDs of the decision: [0, 2^30), so that ref << 33 and one more fit 64 bits
-
-__device__ __forceinline__ uint32_t qual_sum4(uint32_t w, uint32_t keep) {   // the bytes of w >= 15 that `keep` (bit per byte) selects
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t q = (w >> (8 * k)) & 0xFF;
-        s += ((keep >> k) & 1) && q >= (uint32_t)kQualMin ? q : 0;
-    }
-    return s;
-}
 
 __global__ void __launch_bounds__(256) md_head_kernel(const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, uint32_t *head) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
@@ -91,113 +79,25 @@ __global__ void __launch_bounds__(256) md_rec_kernel(const uint8_t *bam, const i
     const int64_t n_groups = (int64_t)gridDim.x * (blockDim.x / kGroup);
     // every lane of a group runs the same number of iterations (r depends on the group only), so the shuffles below see all 16
     for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroup; r < n_rec; r += n_groups) {
-        const uint8_t *p = bam + rec_off[r];
-        const int32_t rid = bam_ref_id(p), pos = bam_pos(p);
-        const uint32_t l_name = bam_l_name(p), n_cig = bam_n_cig(p), flag = bam_flag(p);
-        const int64_t l_seq = bam_l_seq(p);
-        const bool want = !(flag & 0x904);                     // a mapped primary: its coordinate and score
-        int64_t rlen = 0, clip = 0;
-        uint32_t score = 0;
-        if (want) {
-            const uint8_t *c = p + bam_cigar_at(l_name);
-            rlen = cigar_ref_len(c, n_cig, g, kGroup);
-            if (g == 0 && !(flag & 16)) {                    // forward: the S and H lengths before the first other op
-                for (uint32_t k = 0; k < n_cig; ++k) {
-                    const uint32_t op = ld_u32(c + 4 * k), o = op & 15;
-                    if (o != 4 && o != 5) break;
-                    clip += op >> 4;
-                }
-            }
-            if (g == 1 && (flag & 16)) {                     // reverse: the S and H lengths after the last other op
-                for (uint32_t k = n_cig; k-- > 0;) {
-                    const uint32_t op = ld_u32(c + 4 * k), o = op & 15;
-                    if (o != 4 && o != 5) break;
-                    clip += op >> 4;
-                }
-            }
-            const uint8_t *qs = p + bam_qual_at(l_name, n_cig, l_seq);
-            const int64_t n_q = std::min<int64_t>(l_seq, (p + 4 + bam_block_size(p)) - qs);     // never past the record's block_size
-            if (n_q > 0 && qs[0] != 0xFF) {                   // QUAL present: aligned dwords over [qs, qs + n_q)
-                const uintptr_t a0 = reinterpret_cast<uintptr_t>(qs) & ~(uintptr_t)3;
-                const uintptr_t e = reinterpret_cast<uintptr_t>(qs) + (uintptr_t)n_q;
-                const int64_t n_dw = (int64_t)((e - a0 + 3) >> 2);
-                const uint32_t *w = reinterpret_cast<const uint32_t *>(a0);
-                for (int64_t k = g; k < n_dw; k += kGroup) {
-                    const uintptr_t at = a0 + 4 * (uintptr_t)k;
-                    uint32_t keep = 0xF;
-                    if (at < reinterpret_cast<uintptr_t>(qs)) keep &= 0xFu << (reinterpret_cast<uintptr_t>(qs) - at);
-                    if (at + 4 > e) keep &= 0xFu >> (at + 4 - e);
-                    score = min(score + qual_sum4(w[k], keep), (uint32_t)kScoreCap);
-                }
-            }
-        }
-#pragma unroll
-        for (int m = kGroup / 2; m > 0; m >>= 1) {
-            rlen += __shfl_xor(rlen, m, kGroup);
-            clip += __shfl_xor(clip, m, kGroup);
-            score += __shfl_xor(score, m, kGroup);
-        }
+        const MdRec m = md_rec_of(bam + rec_off[r], g);      // rules 3-4 (markdup_dev.h)
         if (g == 0) {
             const uint32_t t = tid[r] - 1;
             rtmpl[r] = t;
             if (head[r]) tstart[t] = (uint32_t)r;
-            MdRec m;
-            m.c = !want ? 0 : (flag & 16) ? (int64_t)pos + (rlen ? rlen : 1) - 1 + clip : (int64_t)pos - clip;
-            m.rid = rid;
-            m.flag = (uint16_t)flag;
-            m.score = (uint16_t)min(score, (uint32_t)kScoreCap);
             rec[r] = m;
         }
     }
 }
 
-// reasons of a refusal, in the low two bits of record << 2 | reason
-enum { kTwoPrimaries = 0, kSegmentBits = 1, kMixed = 2, kCoordinate = 3 };
-
 __global__ void __launch_bounds__(256) md_tmpl_kernel(const MdRec *rec, const uint32_t *tstart, int64_t n_t, int64_t n_rec,
                                                       bwams_dup_end_t *tend, uint8_t *has, unsigned long long *bad) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_t; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r0 = tstart[t], r1 = t + 1 < n_t ? (int64_t)tstart[t + 1] : n_rec;
-        int64_t only = -1, first = -1, last = -1;            // the primary of each segment
-        int paired = -1;
-        unsigned long long fault = ~0ULL;
-        for (int64_t r = r0; r < r1 && fault == ~0ULL; ++r) {
-            const uint32_t f = rec[r].flag;
-            if (f & 0x900) continue;
-            const int p = f & 1;
-            if (paired < 0) paired = p;
-            int64_t &seg = !p ? only : (f & 0x40) ? first : last;
-            if (p != paired) fault = (unsigned long long)r << 2 | kMixed;
-            else if (p && ((f >> 6) & 1) == ((f >> 7) & 1)) fault = (unsigned long long)r << 2 | kSegmentBits;
-            else if (seg >= 0) fault = (unsigned long long)r << 2 | kTwoPrimaries;
-            else if (!(f & 4) && (rec[r].rid < 0 || rec[r].c < -(1LL << 31) || rec[r].c >= (1LL << 31)))
-                fault = (unsigned long long)r << 2 | kCoordinate;
-            else seg = r;
-        }
-        uint8_t h = 0;
+        MdWalk w;                                            // rules 2-3 and 5 (markdup_dev.h)
+        for (int64_t r = r0; r < r1 && w.fault == ~0ULL; ++r) w.step(r, rec[r]);
+        if (w.fault != ~0ULL) atomicMin(bad, w.fault);
         bwams_dup_end_t e;
-        e.tmpl = t; e.ref2 = -1; e.pos2 = 0;
-        const bool m_only = only >= 0 && !(rec[only].flag & 4), m_first = first >= 0 && !(rec[first].flag & 4);
-        const bool m_last = last >= 0 && !(rec[last].flag & 4);
-        if (fault != ~0ULL) {
-            atomicMin(bad, fault);
-        } else if (m_first && m_last) {                      // a pair: end 1 the smaller (refID, coordinate), on a tie the earlier record
-            const int64_t a = min(first, last), b = max(first, last);
-            const MdRec A = rec[a], B = rec[b];
-            const bool swap = B.rid < A.rid || (B.rid == A.rid && B.c < A.c);
-            const MdRec E1 = swap ? B : A, E2 = swap ? A : B;
-            e.ref1 = E1.rid; e.pos1 = (int32_t)E1.c; e.ref2 = E2.rid; e.pos2 = (int32_t)E2.c;
-            e.score = (int32_t)E1.score + (int32_t)E2.score;
-            e.strands = (int32_t)((E1.flag >> 4) & 1) | (int32_t)((E2.flag >> 4) & 1) << 1;
-            h = 1;
-        } else if ((int)m_only + (int)m_first + (int)m_last == 1) {
-            const MdRec E1 = rec[m_only ? only : m_first ? first : last];
-            e.ref1 = E1.rid; e.pos1 = (int32_t)E1.c;
-            e.score = E1.score;
-            e.strands = (int32_t)((E1.flag >> 4) & 1);
-            h = 1;
-        }
-        if (!h) { e.ref1 = -1; e.pos1 = 0; e.score = 0; e.strands = 0; }
+        const uint8_t h = w.end(rec, t, &e) ? 1 : 0;
         tend[t] = e;
         has[t] = h;
     }
@@ -295,17 +195,6 @@ __global__ void __launch_bounds__(256) md_apply_kernel(uint8_t *bam, const int64
 
 // ---- rules 9-10: a template's read group, library and location, lane per template ----
 
-// one field of a read name from s[at, n): an optional '-', then digits up to the first other byte; *ok cleared outside int32
-__device__ __forceinline__ int32_t name_value(const uint8_t *s, uint32_t at, uint32_t n, bool *ok) {
-    const bool neg = at < n && s[at] == '-';
-    if (neg) ++at;
-    int64_t v = 0;
-    for (; at < n && s[at] >= '0' && s[at] <= '9'; ++at) v = min(v * 10 + (s[at] - '0'), (int64_t)1 << 40);
-    if (neg) v = -v;
-    if (v < -(1LL << 31) || v >= (1LL << 31)) *ok = false;
-    return (int32_t)v;
-}
-
 __global__ void __launch_bounds__(256) md_loc_kernel(const uint8_t *bam, const int64_t *rec_off, const MdRec *rec, const uint32_t *tstart,
                                                      int64_t n_t, int64_t n_rec, MdGroupsDev G, bwams_dup_loc_t *tloc,
                                                      unsigned long long *bad) {
@@ -314,69 +203,14 @@ __global__ void __launch_bounds__(256) md_loc_kernel(const uint8_t *bam, const i
         int64_t r = r0;
         while (r < r1 && (rec[r].flag & 0x900)) ++r;         // the first primary, else the first record
         if (r == r1) r = r0;
-        const uint8_t *p = bam + rec_off[r];
-        const uint32_t l_name = bam_l_name(p);
-        bwams_dup_loc_t L;
-        L.rg = -1; L.lib = G.n_lib - 1; L.tile = L.x = L.y = 0; L.has = 0;
-        if (G.walk) {                                         // rule 9: the aux fields by their types, to the record's end (aux_rg.h)
-            bool found = false;
-            int64_t v0 = 0, v1 = 0;                           // RG's value: p[v0, v1)
-            const bool ok = aux_first_rg(p, &found, &v0, &v1);
-            if (!ok) atomicMin(bad, (unsigned long long)r);
-            if (ok && found) {                                // the ID among the table's, sorted by bytes
-                const int32_t rg = groups_find(G, p + v0, v1 - v0);
-                if (rg >= 0) { L.rg = rg; L.lib = G.rg_lib[rg]; }
-            }
-        }
-        const uint8_t *s = p + kBamName;                            // rule 10: the name without its NUL
-        const uint32_t n = l_name ? l_name - 1 : 0;
-        uint32_t colons = 0;
-        for (uint32_t k = 0; k < n; ++k) colons += s[k] == ':';
-        const int first = colons == 4 ? 2 : (colons == 6 || colons == 7) ? 4 : -1;
-        if (first >= 0) {
-            uint32_t at = 0;
-            for (int f = 0; f < first; ++at) f += s[at] == ':';
-            bool ok = true;
-            int32_t v[3];
-#pragma unroll
-            for (int f = 0; f < 3; ++f) {
-                v[f] = name_value(s, at, n, &ok);
-                while (at < n && s[at] != ':') ++at;
-                ++at;
-            }
-            if (ok) { L.tile = v[0]; L.x = v[1]; L.y = v[2]; L.has = 1; }
-        }
+        bool ok;
+        const bwams_dup_loc_t L = md_loc_of(bam + rec_off[r], G, &ok);     // rules 9-10 (markdup_dev.h)
+        if (!ok) atomicMin(bad, (unsigned long long)r);
         tloc[t] = L;
     }
 }
 
-// ---- rule 13: counts per library.  counts[lib * kLibCounts + which]; a workgroup counts in LDS when the libraries fit ----
-
-constexpr int kLibCounts = 7, kLdsLibs = 64;
-enum { kUnpEx = 0, kPairEx = 1, kUnpDup = 2, kPairDup = 3, kOptical = 4, kSecSup = 5, kUnmapped = 6 };
-
-struct LibCounter {
-    unsigned int *lds;                                        // kLdsLibs * kLibCounts words, or null: straight to global memory
-    unsigned long long *out;
-    __device__ void init(unsigned int *sh, int n_lib, unsigned long long *counts) {
-        lds = n_lib <= kLdsLibs ? sh : nullptr;
-        out = counts;
-        if (lds) {
-            for (int k = threadIdx.x; k < n_lib * kLibCounts; k += blockDim.x) lds[k] = 0;
-            __syncthreads();
-        }
-    }
-    __device__ void add(int lib, int which) {
-        if (lds) atomicAdd(lds + lib * kLibCounts + which, 1u);
-        else atomicAdd(out + (int64_t)lib * kLibCounts + which, 1ULL);
-    }
-    __device__ void flush(int n_lib) {
-        if (!lds) return;
-        __syncthreads();
-        for (int k = threadIdx.x; k < n_lib * kLibCounts; k += blockDim.x)
-            if (lds[k]) atomicAdd(out + k, (unsigned long long)lds[k]);
-    }
-};
+// ---- rule 13: counts per library, through markdup_dev.h's LibCounter ----
 
 // lane per end: its template's kind and what the decision made of it, to the end's library (loc null: library 0)
 __global__ void __launch_bounds__(256) md_lib_ends_kernel(const bwams_dup_end_t *ends, const bwams_dup_loc_t *loc, int64_t n_e,
@@ -540,6 +374,8 @@ const char *kReason[4] = {"two primaries of one segment", "a paired primary with
 const char *kReasonAux = "aux fields do not chain to the record's end";
 
 }  // namespace
+
+const char *md_reason_text(int reason) { return reason >= 0 && reason < 4 ? kReason[reason] : kReasonAux; }
 
 int md_templates(MdTemplates &m, const uint8_t *bam, const int64_t *rec_off, int64_t n_rec, int cu_count, hipStream_t st) {
     m.n_t = m.n_e = 0;
@@ -742,6 +578,10 @@ int md_decide(MdDecide &w, const bwams_dup_end_t *ends, int64_t n_e, int64_t n_t
 void launch_md_apply(uint8_t *bam, const int64_t *rec_off, const uint32_t *perm, const uint32_t *rtmpl, const uint8_t *dup, int64_t n_rec,
                      unsigned long long *n_marked, int cu_count, hipStream_t st) {
     if (n_rec > 0) md_apply_kernel<<<grid_of(n_rec, 256, cu_count), 256, 0, st>>>(bam, rec_off, perm, rtmpl, dup, n_rec, n_marked);
+}
+
+void launch_md_gather64(const uint64_t *src, const uint32_t *idx, int64_t n, uint64_t *dst, int cu_count, hipStream_t st) {
+    if (n > 0) md_gather64_kernel<<<grid_of(n, 256, cu_count), 256, 0, st>>>(src, idx, n, dst);
 }
 
 void launch_md_gather32(const uint32_t *src, const uint32_t *idx, int64_t n, uint32_t *dst, int cu_count, hipStream_t st) {

@@ -59,6 +59,7 @@ struct BamFileHost {
     int fd = -1;
     int64_t file_size = 0;
     BamHeader hdr;
+    std::vector<char> header_block;  // the header as the file holds it, inflated: magic to the last reference's l_ref
     uint64_t first_voff = 0;         // the first record behind the header
     bool has_index = false;
     Bai bai;

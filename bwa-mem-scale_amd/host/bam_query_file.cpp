@@ -101,6 +101,7 @@ int BamFileHost::open(const char *path_, const char *bai_path, int device, int64
         },
         65536, &hb, &hdr, err);
     if (rc) return rc;
+    header_block.assign(hb.begin(), hb.begin() + (std::ptrdiff_t)hdr.end);
     // the first record: in the member that holds byte hdr.end, or at the start of the one behind the members read
     first_voff = (uint64_t)file_at << 16;
     for (size_t k = 0; k < coff.size(); ++k) {

@@ -1790,6 +1790,7 @@ int bwams_recal_apply_info(const bwams_recal_apply_t *a, bwams_recal_apply_info_
  * The kernels: the record discovery of bwams_bam_reads_decode (csrc/bam_discover.h) from an offset to an offset; a select kernel, a
  * lane per record, with the merged regions in LDS; two scans; the sorter's gather into the handle's record buffer.  _info: a test
  * and measurement hook (bwams_bam_file_info_t, include/bwams_types.h).
+ * A sixth consumer of the pieces is the join handle below: bwams_dupjoin_add_file and bwams_dupjoin_apply_file.
  * Out of scope: CRAM, CSI and tabix indexes, unsorted input beyond whole-file mode, several files merged, writing. */
 int bwams_bam_file_open(const char *path, const char *bai_path, int device, int64_t piece_bytes, bwams_bam_file_t **out);
 int bwams_bam_file_header(const bwams_bam_file_t *f, const char **text, int64_t *n_text, int32_t *n_ref);
@@ -1806,6 +1807,80 @@ int bwams_recal_add_file(bwams_recal_t *r, bwams_bam_file_t *f, int64_t *n_count
 int bwams_recal_apply_file(bwams_recal_apply_t *a, bwams_bam_file_t *f, int64_t *n_rewritten);
 int bwams_bai_plan(const void *bai, int64_t n_bai, const bwams_pileup_region_t *regions, int32_t n_regions, uint64_t *chunk_beg,
                    uint64_t *chunk_end, int64_t cap, int64_t *n_chunks);
+/* ------------------------------ Duplicate marking, templates joined by name ---- */
+
+/* Duplicate marking of records that are NOT query-grouped (csrc/dup_join.hip): a coordinate-sorted BAM of another aligner, of an older
+ * run, or one written without BWAMS_SORT_MARKDUP.  A sixth record consumer, bwams_dupjoin_t, on one device, used in two passes over
+ * the same records: pass 1 adds every piece and keeps a small entry per record in HBM; _finish joins the entries into templates by
+ * read name and decides; pass 2 sets or clears 0x400 in each piece where it lies.  After bwams_dupjoin_apply_file,
+ * bwams_bam_file_fetch returns the marked bytes and their coords, bwams_sorter_put takes them as they are, and the other consumers'
+ * _add_file on the same piece sees the marks.  bwams/markdup.py restates the rules (name_key, join, mark_joined).
+ * Rules 2 to 15 of "Duplicate marking" (above bwams_bam_templates) hold unchanged except where a rule below says otherwise.  "Add
+ * order" is the order of the _add_* calls, then record order within each; a record's ORDINAL is its 0-based place in add order.
+ *  J1. Name key.  L = l_read_name - 1, the name without its NUL.  For each of two seeds S0 = 0x9e3779b97f4a7c15 and S1 =
+ *      0xc2b2ae3d27d4eb4f: h = S ^ L; then for i in [0, max(1, ceil(L / 8))): h = fmix64(h ^ w_i), where w_i is the name's bytes
+ *      [8i, 8i + 8) as a little-endian 64-bit word, zero-padded past L, and fmix64 is MurmurHash3's finalizer (h ^= h >> 33; h *=
+ *      0xff51afd7ed558ccd; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53; h ^= h >> 33; mod 2^64).  The key is (k0, k1).  "r1" gives
+ *      (f725c5a0830ac16d, b55003a821483129).  Names of at most 8 bytes cannot collide within one length: one bijective step.
+ *  J2. Template: all added records with equal (L, k0, k1), adjacent or not.  This replaces rule 1.  Its ordinal is its rank by the
+ *      ordinal of its first record.  Two different names with equal L and key would be taken for one template (among 2^32 names
+ *      the chance of any such pair is below 2^-65, but the file is untrusted input and such names can be constructed): the
+ *      consequence is a wrong 0x400 or a refusal by rule 2, never an access out of bounds, since no index the kernels store through
+ *      depends on a name.  More than 2^32 - 1 records: BWAMS_ERR_UNSUPPORTED.
+ *  J3. The walk.  Rules 2 to 5 are applied to a template's records in ordinal order: "the earlier record" of rule 5 is the one with
+ *      the smaller ordinal, and "the first record concerned" of rule 2 is the smallest ordinal at which any template's walk meets a
+ *      fault.  Consequence: two primaries of one segment that share a name are refused wherever they lie (for example two
+ *      single-end reads of one name at two places of a sorted file), where the adjacent-run rule takes them for two templates when
+ *      they are apart.
+ *  J4. Read group, library, location.  Rules 9 and 10 take the template's first primary in add order, or its first record when it has
+ *      no primary.  With a groups table EVERY added record's aux fields are walked at the add (aux_first_rg), also those of records
+ *      rule 9 never names: a record that does not chain refuses that add with BWAMS_ERR_UNSUPPORTED and the fifth reason ("aux fields
+ *      do not chain to the record's end"), naming the smallest such ordinal, and the handle is left as it was before the add.
+ *      Without a table no aux field is read.
+ *  J5. Decision and tie-breaks.  Rule 6 and rules 11 to 13 apply, through the same kernels over device ends (no round trip of the
+ *      ends through the host).  "Earlier template" means the smaller template ordinal of J2.
+ *  J6. Marking.  Rule 7 applies: every record of a duplicate template is marked, secondary, supplementary and unmapped-mate records
+ *      included, wherever they lie in the file.  This is what the query-grouped path does; it is more than Picard does on
+ *      coordinate-sorted input, where records that are not primaries keep their flags.
+ *  J7. Defined over what was added.  A paired primary whose mate was never added makes a fragment, so a region query in pass 1 gives
+ *      marks that hold only for those records.  The whole file (n_regions 0) is the intended input.
+ *  J8. Pass 2.  Apply call i takes the records of add i.  Before any byte is written, a check kernel compares the piece's record
+ *      count, the sum mod 2^64 of its k0 and the sum of (2r + 1) * k0 over its records r = 0, 1, ... (a plain sum cannot see two
+ *      names exchanged) with what add i left; a mismatch is BWAMS_ERR_ARG with a text, nothing is written, and the same apply may be
+ *      tried again.
+ *  J9. States: empty -> adding -> finished.  BWAMS_ERR_ARG with a text for _add_* after _finish, for _apply_* or _fetch before it, for
+ *      an apply past the last add, and for a file on another device.  A refusal at _finish (rules 2 and 3) leaves the handle fit
+ *      only for _reset or _close.  _reset returns to empty and keeps the table and the options.
+ * Counts: bwams_dup_stats_t and the bwams_dup_lib_stats_t rows (may be NULL; cap_lib < n_lib: BWAMS_ERR_CAPACITY) come complete
+ * from _finish; records_marked is the number of records whose template is a duplicate, known before pass 2.
+ * bwams_dup_metrics_text takes the rows unchanged.
+ * bwams_dupjoin_open: groups (copied) and opt may both be NULL.  _add_records / _add_file: *n_added the records of the add; an add
+ * of no records is an add.  _fetch (after _finish): the ends and their locs (cap_ends), each record's template by ordinal (cap_rec),
+ * dup and optical per template (cap_tmpl); any pointer may be NULL; a capacity too small for a pointer given is
+ * BWAMS_ERR_CAPACITY.  _apply_records rewrites host records in place; _apply_file the file's current piece in HBM; *n_marked the
+ * records that now carry 0x400.  _key: J1 on the host (n in [0, 254]).  bwams_bam_file_header_block: the file's BAM header as
+ * bwams_sorter_open takes it (it lives as long as the file handle).
+ * Memory: 57 bytes of device memory per record while adding (the key 16, L 1, the coordinate, refID, FLAG and score 16, the
+ * record's library, read group and location 24), in arrays grown by half; _finish adds 33 bytes per record of sort scratch and rocPRIM's
+ * own, and frees all of it but 4 bytes per record (rec_tmpl) and 2 per template.  What does not fit is BWAMS_ERR_NOMEM with the size
+ * asked for.  _info: a test and measurement hook (bwams_dupjoin_info_t, include/bwams_types.h).
+ * Out of scope: batches (a batch's templates are adjacent: bwams_bam_markdup serves them); lifting bwams_sorter_put's refusal under
+ * BWAMS_SORT_MARKDUP (the follow-up this handle makes possible); storing names to verify keys; the DT tag, REMOVE_DUPLICATES, UMIs;
+ * several files merged. */
+int bwams_dupjoin_open(int device, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt, bwams_dupjoin_t **out);
+int bwams_dupjoin_reset(bwams_dupjoin_t *j);
+int bwams_dupjoin_close(bwams_dupjoin_t *j);
+int bwams_dupjoin_add_records(bwams_dupjoin_t *j, const void *bam, int64_t n_bytes, int64_t *n_added);
+int bwams_dupjoin_add_file(bwams_dupjoin_t *j, bwams_bam_file_t *f, int64_t *n_added);
+int bwams_dupjoin_finish(bwams_dupjoin_t *j, bwams_dup_stats_t *st, bwams_dup_lib_stats_t *lib_stats, int64_t cap_lib);
+int bwams_dupjoin_fetch(bwams_dupjoin_t *j, bwams_dup_end_t *ends, bwams_dup_loc_t *loc, int64_t cap_ends, uint32_t *rec_tmpl,
+                        int64_t cap_rec, uint8_t *dup, uint8_t *optical, int64_t cap_tmpl);
+int bwams_dupjoin_apply_records(bwams_dupjoin_t *j, void *bam, int64_t n_bytes, int64_t *n_marked);
+int bwams_dupjoin_apply_file(bwams_dupjoin_t *j, bwams_bam_file_t *f, int64_t *n_marked);
+int bwams_dupjoin_info(const bwams_dupjoin_t *j, bwams_dupjoin_info_t *info);
+int bwams_dupjoin_key(const void *name, int32_t n, uint64_t key[2]);
+int bwams_bam_file_header_block(const bwams_bam_file_t *f, const void **block, int64_t *n);
+
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

@@ -550,6 +550,21 @@ typedef struct bwams_bam_file_info {
     int32_t pad_;
 } bwams_bam_file_info_t;
 
+/* Duplicate marking with templates joined by name (include/bwams.h, above bwams_dupjoin_open).  A join handle lives on one device. */
+typedef struct bwams_dupjoin bwams_dupjoin_t;
+
+/* bwams_dupjoin_info: records added, templates and ends (after _finish), adds, applies done since _finish, the bytes of device memory
+ * the handle holds now (the entries while adding; rec_tmpl, dup, optical, the ends and their locs once finished; the upload buffer of
+ * the _records calls), the bytes an entry takes per record while adding (57), and the state (0 empty, 1 adding, 2 finished, 3
+ * refused at _finish).  The times are for measurement only (tools/dup_join_rate.py): ms_add and ms_apply device time between events
+ * around the kernels of all adds and of all applies; ms_sort, ms_ends and ms_decide the host clock around _finish's three sorts, its
+ * head flags to the selects, and md_decide with the counts. */
+typedef struct bwams_dupjoin_info {
+    int64_t records, templates, ends, adds, applied, hbm_bytes, entry_bytes;
+    int32_t state, pad_;
+    float   ms_add, ms_sort, ms_ends, ms_decide, ms_apply, pad2_;
+} bwams_dupjoin_info_t;
+
 #ifdef __cplusplus
 }
 #endif
