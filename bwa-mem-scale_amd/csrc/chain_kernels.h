@@ -1,5 +1,5 @@
 // chain_kernels.h — device-side argument blocks and launchers of the chaining and
-// chain-to-alignment stages (chain.hip, ext_aln.hip).
+// chain-to-alignment stages (chain.hip, chain_count.hip, chain_lane.hip, ext_aln.hip).
 #pragma once
 
 #include "common.h"
@@ -44,7 +44,10 @@ size_t chain_node_bytes(int64_t n_sa, int64_t nseq);
 size_t chain_rec_bytes(int64_t n_sa);
 void launch_chain_count(const ChainArgs &A, uint32_t *keys, uint32_t *vals, hipStream_t st);
 int launch_chain(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux,
-                 hipEvent_t fork, hipEvent_t *join, bool count);      // count: the kernel instances that count routes and passes (chain.hip)
+                 hipEvent_t fork, hipEvent_t *join, bool count);      // count: the kernel instances that count routes and passes (launch_chain_counting)
+// the launch plan (launch_chain_t, chain_wave.h) over those instances, which are chain_count.hip's code object
+int launch_chain_counting(const ChainArgs &A, const uint32_t *n_seeds, int cu_count, hipStream_t st, hipStream_t *aux,
+                          hipEvent_t fork, hipEvent_t *join);
 // the lane tier (chain_lane.hip): the reads of at most kLaneSeeds seeds, A.order[ctr->chain_class[5] .. nseq), a lane each
 void launch_chain_lane(const ChainArgs &A, hipStream_t st, bool count);
 void launch_chain_emit(const ChainArgs &A, const int64_t *chain_off, const int64_t *seed_off, bwams_chain_t *chains,

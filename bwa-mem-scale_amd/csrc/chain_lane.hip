@@ -1,10 +1,10 @@
 // chain_lane.hip — the lane tier of the chaining stage: one lane per read of at most kLaneSeeds seeds.
 //
-// chain.hip's chain_read<false> keeps a read's whole working state in the read's HBM scratch, a line per lane and access: every
+// chain_dev.h's chain_read<false> keeps a read's whole working state in the read's HBM scratch, a line per lane and access: every
 // lookup loads the root node again, every test_and_merge loads and stores a chain record, the sort and the filter walk small
 // arrays element by element.  A read of the lane tier has at most 32 seeds and nearly always a handful of chains, and while the
 // kbtree is ONE node — its root, a leaf of at most KB_MAXK = 9 keys — the same decisions can be taken with
-//   * the leaf in registers (NodeR and node_search / sel_key / sel_pos, chain.hip's own),
+//   * the leaf in registers (NodeR and node_search / sel_key / sel_pos, chain_dev.h's),
 //   * the chain records, the filter's {weight, id} pairs, its records and its kept / selected marks in LDS, a row per lane,
 // and every array the later kernels read (chain records, seed links, kept pairs, first shadowed chains, the per-read totals)
 // written once.  A read that needs a tenth chain gives up: its lane chains it again from its first seed with chain_read<false>,
@@ -12,10 +12,10 @@
 // takes too, so the rewritten seed links are a superset with the same values).
 // The reads come in the stage's descending seed-count order (A.order behind the wave tiers' range), so that a wavefront holds
 // reads of nearly the same length.
-// This file compiles chain.hip for chain_read<false> and its helpers only (chain.hip says what a second set of kernels inside
-// its own code object cost), as chain_count.hip does for the counting instances.
-#define BWAMS_CHAIN_LANE_TU
-#include "chain.hip"
+// This file compiles chain_dev.h alone, for chain_read<false> and its helpers: the lane tier is a code object of its own
+// (chain_wave.h, at launch_chain_t, says what a second set of kernels beside the wave tiers' cost), as chain_count.hip is for the
+// counting instances.
+#include "chain_dev.h"
 
 namespace bwams {
 namespace {
@@ -32,7 +32,7 @@ static_assert(sizeof(LeafLds) <= 48 * 1024, "three wavefronts of the lane tier p
 
 // One read on one lane while its kbtree is a single leaf.  Returns false when the read needs a tenth chain.
 // Every pointer into `S` is derived here from the __shared__ object and every helper is inlined, so that the accesses stay ds_*
-// instructions (chain.hip, at chain_read, says what a flat access costs).
+// instructions (chain_dev.h, at chain_read, says what a flat access costs).
 template <bool COUNT>
 __device__ __forceinline__ bool chain_read_leaf(const ChainArgs &A, int64_t r, LeafLds &S, int lane) {
     A.n_kept[r] = 0;

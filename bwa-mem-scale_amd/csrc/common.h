@@ -41,7 +41,7 @@ struct Knobs {
     int trace_pair = 0;            // BWAMS_TRACE_PAIR: a synchronisation and a line per launch of the paired-end tail
     int bsw_pk = 1;                // BWAMS_BSW_PK=0: the 32-bit eight-task banded-SW kernel
     int chain_count = 0;           // BWAMS_CHAIN_COUNT=1: chaining counts its filter routes and the passes of chain_seeds_batch (tests)
-    int chain_batch = 1;           // BWAMS_CHAIN_BATCH=0: chaining's wave tier takes one seed at a time (chain.hip: chain_seeds_batch)
+    int chain_batch = 1;           // BWAMS_CHAIN_BATCH=0: chaining's wave tier takes one seed at a time (chain_dev.h: chain_seeds_batch)
     int ert_fat = 1;               // BWAMS_ERT_FAT=0: the ERT walk reads the reference's two tables only (no entry + tree-head table)
     int depth_combine = 1;         // BWAMS_DEPTH_COMBINE=0: the depth add issues one atomic per lane (no folding of equal slots inside a wave)
     int pileup_tiled = 1;          // BWAMS_PILEUP_TILED=0: every record of a pileup add goes through the direct kernel (one global atomic per base)

@@ -2,7 +2,7 @@
 // final insertion sort; src/ksort.h there), operation by operation, over any record type T with a comparator LT: the sort
 // is unstable, so only the same sequence of comparisons and swaps leaves tied records in the reference's order.  Every
 // device sort is an instantiation of this file: the region sorts (region_sort.h, 24-byte SortRec) and the chain filter's
-// (chain.hip, uint2 {weight, id}).  Each form exists twice: sequential (one lane, HBM pointers) and whole-wavefront (LDS).
+// (chain_dev.h, uint2 {weight, id}).  Each form exists twice: sequential (one lane, HBM pointers) and whole-wavefront (LDS).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

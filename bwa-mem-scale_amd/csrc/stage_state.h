@@ -8,7 +8,7 @@
 namespace bwams {
 
 // Streams beside the batch's own that a stage forks its launches onto: banded SW uses all four (launch_bsw: five query-length
-// classes with the batch's stream), de-duplication three, chaining two (its plan: chain.hip), selection one.
+// classes with the batch's stream), de-duplication three, chaining two (its plan: chain_wave.h), selection one.
 constexpr int kAuxStreams = 4;
 struct StageState {
     struct ChainStage {                      // chaining, mem_flt_chained_seeds (sw_*), the ERT input translation (et_*)

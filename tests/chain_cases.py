@@ -14,9 +14,9 @@ Two building blocks make the chain count of a read exact whatever the options:
   * MEM k of a "ladder" starts at query k * STEP and hits every base position + k * STEP: seed k extends the chain of its base
     position (x = y = STEP) as long as the base positions are further apart than the ladder is long.
 
-`model` restates what decides a read's way through the kernels — the constants below are copied from chain.hip, and
-test_chain_cases.py checks that the file still holds them — from the inputs (seeds per read after mem_chain_new's stride pick)
-and from the oracle's chains before the filter (loader.chain_new_ert(do_flt=False): chains per read, repeated positions, and
+`model` restates what decides a read's way through the kernels — the constants below are copied from the chaining sources
+(chain_dev.h, chain_wave.h, chain.hip), and test_chain_cases.py checks that those still hold them, each in one file — from the
+inputs (seeds per read after mem_chain_new's stride pick) and from the oracle's chains before the filter (loader.chain_new_ert(do_flt=False): chains per read, repeated positions, and
 mem_chain_weight restated here).  It is written from the order of tests at the end of chain_read and in chain_heavy_kernel."""
 import functools
 import re
@@ -53,7 +53,7 @@ COUNT_KEYS = ("gt_L", "gt_L1", "gt_M", "gt_M1", "gt_S", "gt_lane", "gt_XL", "gt_
 
 
 def missing_constants(text):
-    """The entries of SOURCE_CONSTANTS that chain.hip's text no longer holds."""
+    """The entries of SOURCE_CONSTANTS that `text` (the chaining sources' text) does not hold."""
     return [c for c in SOURCE_CONSTANTS if not re.search(c, text)]
 
 

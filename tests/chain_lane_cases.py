@@ -1,6 +1,6 @@
 """Planted reads for the lane tier of the chaining stage (csrc/chain_lane.hip): reads of at most 32 seeds, which one lane chains
 with the B-tree's root leaf in registers and the chain records in LDS for as long as the read has at most nine chains, and which
-the same lane chains again through chain.hip's chain_read<false> when a tenth chain appears.  Built from tests/chain_cases.py's
+the same lane chains again through chain_dev.h's chain_read<false> when a tenth chain appears.  Built from tests/chain_cases.py's
 blocks; tests/test_chain_lane_cases.py proves under the oracle alone that every case has the property it is built for, and
 tests/test_gpu_chain_lane.py runs them through bwams_chain_run_ert.
 

@@ -1,4 +1,4 @@
-"""One batch for the launch plan of the chaining stage (launch_chain_t, csrc/chain.hip): every launch of the plan has a read
+"""One batch for the launch plan of the chaining stage (launch_chain_t, csrc/chain_wave.h): every launch of the plan has a read
 to chain at the same time, so that every lane and both fork-join rounds carry work.  Built from the planted-seed blocks of
 tests/chain_cases.py and tests/chain_lane_cases.py, default options; tests/test_chain_plan_cases.py proves under the oracle alone
 that the batch holds what this text says, tests/test_gpu_chain_plan.py runs it through bwams_chain_run_ert.

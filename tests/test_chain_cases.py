@@ -1,9 +1,10 @@
 """The planted chaining cases (tests/chain_cases.py) under the oracle alone: every case sits on the side of its limit that it was
-built for, the settling cases are decided by the rule they are named after, and the route model's constants are chain.hip's.
+built for, the settling cases are decided by the rule they are named after, and the route model's constants are the chaining sources'.
 Where the reference's kbtree.h / ksort.h are built (oracle/_ref/libref_chain.so), the reads in which tree shape and sort
 stability decide go through them as well."""
 import bisect
 import os
+import re
 
 import numpy as np
 import pytest
@@ -12,7 +13,8 @@ import chain_cases as cc
 from oracle import loader
 
 REF = loader.ref_chain_lib()
-CHAIN_HIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bwa-mem-scale_amd", "csrc", "chain.hip")
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bwa-mem-scale_amd", "csrc")
+CHAIN_SOURCES = ("chain_dev.h", "chain_wave.h", "chain.hip", "chain_lane.hip")
 
 
 def _reads(case):
@@ -26,8 +28,13 @@ def _chains_of(case, r, **kw):
 
 
 def test_model_constants_are_chain_hip_s():
-    with open(CHAIN_HIP) as f:
-        assert cc.missing_constants(f.read()) == []
+    texts = []
+    for name in CHAIN_SOURCES:
+        with open(os.path.join(CSRC, name)) as f:
+            texts.append(f.read())
+    assert cc.missing_constants("\n".join(texts)) == []
+    for c in cc.SOURCE_CONSTANTS:                                                # a constant defined in two files would be a bug
+        assert len([name for name, t in zip(CHAIN_SOURCES, texts) if re.search(c, t)]) == 1, c
     assert cc.missing_constants("constexpr int kLaneSeeds = 33;") != []
     assert [cc.cap_f("xl", cc.CLASS_XL), cc.cap_f("xl", cc.CLASS_XL2)] == [1197, 3803]
     assert all(cc.cap_f("lds", k) > k for k in cc.LDS_CLASSES)               # in the other classes the filter always fits

@@ -101,7 +101,7 @@ def _assert_chains(want, got):
 
 @pytest.mark.parametrize("batch", ["1", "0"])
 def test_chains_match_oracle(rep_toy, monkeypatch, batch):
-    """batch = 1 (default): the wave tier settles 64 seeds per pass (chain.hip: chain_seeds_batch); 0: one seed at a time."""
+    """batch = 1 (default): the wave tier settles 64 seeds per pass (chain_dev.h: chain_seeds_batch); 0: one seed at a time."""
     monkeypatch.setenv("BWAMS_CHAIN_BATCH", batch)
     capi.debug_reload()
     g, idx, ix = rep_toy

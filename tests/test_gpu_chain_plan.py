@@ -1,4 +1,4 @@
-"""The launch plan of the chaining stage (launch_chain_t, csrc/chain.hip) with every lane at work: the batch of
+"""The launch plan of the chaining stage (launch_chain_t, csrc/chain_wave.h) with every lane at work: the batch of
 tests/chain_plan_cases.py — a read at both seed-count limits of every wave class, lane-tier reads between them (one that needs
 a tenth chain, reads without a seed), a redo read and reads for two classes of the many-chain filter — through
 bwams_chain_run_ert against loader.chain_new_ert, every field of chains, seeds and chain_off, with the kernel instances a
