@@ -81,6 +81,8 @@ SYMBOLS = [
     "bwams_dupjoin_open", "bwams_dupjoin_reset", "bwams_dupjoin_close", "bwams_dupjoin_add_records", "bwams_dupjoin_add_file",
     "bwams_dupjoin_finish", "bwams_dupjoin_fetch", "bwams_dupjoin_apply_records", "bwams_dupjoin_apply_file", "bwams_dupjoin_info",
     "bwams_dupjoin_key", "bwams_bam_file_header_block",
+    "bwams_collate_open", "bwams_collate_reset", "bwams_collate_close", "bwams_collate_add_records", "bwams_collate_add_file",
+    "bwams_collate_finish", "bwams_collate_out", "bwams_collate_fetch", "bwams_collate_info",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -1171,6 +1173,61 @@ class DupJoin(_Consumer):
         return self._info("bwams_dupjoin_info", DupJoinInfo)
 
 
+class CollateOpt(C.Structure):
+    _fields_ = [("pool_bytes", C.c_int64), ("key_mask", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+class CollateOut(C.Structure):
+    _fields_ = [("pairs", C.c_void_p), ("pairs_bytes", C.c_int64), ("n_pairs", C.c_int64), ("singles", C.c_void_p),
+                ("singles_bytes", C.c_int64), ("n_singles", C.c_int64)]
+
+
+class CollateInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("records", "skipped", "pairs", "singles", "orphans", "pending", "pending_bytes", "pool_capacity",
+                                         "bytes_pooled", "compactions", "bytes_compacted", "max_run", "adds")] + \
+               [("state", C.c_int32), ("pad_", C.c_int32)] + \
+               [(n, C.c_float) for n in ("ms_entry", "ms_group", "ms_match", "ms_place", "ms_copy", "pad2_")]
+
+
+class Collate(_Consumer):
+    """A coordinate-sorted BAM collated by read name (bwams_collate_t): add_records / add_file per piece, each followed by out() or
+    fetch() for the pairs it completed and its singles; finish() leaves the orphans as the singles."""
+    _close = "bwams_collate_close"
+    _prefix = "bwams_collate"
+
+    def __init__(self, device: int = 0, pool_bytes: int = 0, key_mask: int = (1 << 64) - 1, opt=True):
+        self.h = C.c_void_p()
+        o = CollateOpt(pool_bytes, key_mask)
+        _chk(lib().bwams_collate_open(device, C.byref(o) if opt else None, C.byref(self.h)), "bwams_collate_open")
+
+    def add_batch(self, batch: "Batch") -> int:
+        raise NotImplementedError("a batch's records are grouped already")
+
+    def finish(self) -> int:
+        """-> the orphans, which out() and fetch() now give as the singles"""
+        n = C.c_int64(0)
+        self._call("bwams_collate_finish", C.byref(n))
+        return n.value
+
+    def out(self) -> CollateOut:
+        """The output of the last add or finish in device memory: .pairs and .singles are device addresses (None when empty),
+        valid until the next add, finish, reset or close.  (out.pairs, out.pairs_bytes) is what Batch.process_chunk_bam takes."""
+        o = CollateOut()
+        self._call("bwams_collate_out", C.byref(o))
+        return o
+
+    def fetch(self):
+        """-> (pairs: bytes, pair_off: int64[2 * n_pairs + 1], singles: bytes, single_off: int64[n_singles + 1])"""
+        o = self.out()
+        pairs, singles = np.zeros(max(o.pairs_bytes, 1), np.uint8), np.zeros(max(o.singles_bytes, 1), np.uint8)
+        poff, soff = np.zeros(2 * o.n_pairs + 1, np.int64), np.zeros(o.n_singles + 1, np.int64)
+        self._call("bwams_collate_fetch", _p(pairs), o.pairs_bytes, _p(poff), _p(singles), o.singles_bytes, _p(soff))
+        return pairs[:o.pairs_bytes].tobytes(), poff, singles[:o.singles_bytes].tobytes(), soff
+
+    def info(self) -> dict:
+        return self._info("bwams_collate_info", CollateInfo)
+
+
 class Gunzipper:
     """Plain gzip inflated on one GPU (bwams_gunzip_t): one file, fed in order."""
 
@@ -1530,6 +1587,15 @@ def lib():
         L.bwams_dupjoin_apply_file.argtypes = [vp, vp, vp]
         L.bwams_dupjoin_info.argtypes = [vp, vp]
         L.bwams_dupjoin_key.argtypes = [C.c_char_p, i32, vp]
+        L.bwams_collate_open.argtypes = [C.c_int, vp, vp]
+        L.bwams_collate_reset.argtypes = [vp]
+        L.bwams_collate_close.argtypes = [vp]
+        L.bwams_collate_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_collate_add_file.argtypes = [vp, vp, vp]
+        L.bwams_collate_finish.argtypes = [vp, vp]
+        L.bwams_collate_out.argtypes = [vp, vp]
+        L.bwams_collate_fetch.argtypes = [vp, vp, i64, vp, vp, i64, vp]
+        L.bwams_collate_info.argtypes = [vp, vp]
         L.bwams_dup_groups_rg_id.argtypes = [vp, i64]
         L.bwams_dup_groups_rg_id.restype = C.c_char_p
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -7,10 +7,8 @@
 //                           32 + bit_width(n_ref) bits instead of 64 (the published key keeps 0xFFFFFFFF);
 //   rocprim::radix_sort_pairs (device key, record index): stable, as the order needs;
 //   bam_sort_permute_kernel lane per sorted slot: the coord of its record, and its size for the exclusive scan (scan_rows);
-//   bam_sort_gather_kernel  sixteen lanes per record copy it from rec_off[idx[i]] to new_off[i]: its head bytes up to the next
-//                           16-byte boundary of the destination and its tail bytes one a lane; the body as aligned 16-byte stores,
-//                           each built from aligned dword loads of the source shifted into place (v_alignbyte), since records are
-//                           not 4-byte aligned in general.  Every byte is read once and written once.
+//   bam_sort_gather_kernel  sixteen lanes per record copy it from rec_off[idx[i]] to new_off[i] (rec_gather.h's copy_record: aligned
+//                           16-byte stores built from aligned dword loads).  Every byte is read once and written once.
 // A record's bytes are only written inside its own range, so the head and tail bytes, which share a dword with the next record,
 // never race.  The source buffer holds 16 bytes of slack past its last record (bwams_bam_run / _upload allocate it), so the
 // aligned loads that reach past a record's end stay in bounds.
@@ -18,6 +16,7 @@
 #include <cstring>
 #include "common.h"
 #include "bam_rec.h"
+#include "rec_gather.h"
 
 namespace bwams {
 namespace {
@@ -50,29 +49,7 @@ __global__ void __launch_bounds__(256) bam_sort_gather_kernel(const uint8_t *src
     const int64_t n_groups = (int64_t)gridDim.x * (blockDim.x / kGroup);
     for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroup; i < n_rec; i += n_groups) {
         const int64_t s = rec_off[idx[i]], d = new_off[i], n = new_off[i + 1] - d;
-        const int64_t head = std::min<int64_t>((16 - (d & 15)) & 15, n);
-        const int64_t body = (n - head) & ~(int64_t)15;
-        const int64_t tail = n - head - body;
-        if (g < head) dst[d + g] = src[s + g];
-        if (g < tail) dst[d + head + body + g] = src[s + head + body + g];
-        const int64_t s0 = s + head;                         // source of the body's first byte
-        const unsigned a = (unsigned)(s0 & 3);
-        const uint32_t *sw = reinterpret_cast<const uint32_t *>(src + (s0 - a));
-        uint4 *dw = reinterpret_cast<uint4 *>(dst + d + head);
-        for (int64_t k = g; k < body / 16; k += kGroup) {
-            const uint32_t *q = sw + 4 * k;
-            uint4 v;
-            if (a == 0) {
-                v.x = q[0]; v.y = q[1]; v.z = q[2]; v.w = q[3];
-            } else {
-                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4];
-                v.x = __builtin_amdgcn_alignbyte(w1, w0, a);
-                v.y = __builtin_amdgcn_alignbyte(w2, w1, a);
-                v.z = __builtin_amdgcn_alignbyte(w3, w2, a);
-                v.w = __builtin_amdgcn_alignbyte(w4, w3, a);
-            }
-            dw[k] = v;
-        }
+        copy_record(src + s, dst + d, n, g);
     }
 }
 

@@ -347,6 +347,56 @@ int dj_join(const DjEntries &E, int64_t n, DjScratch &S, DjJoined &J, const char
 void launch_dj_counts(const MdRec *rec, const uint32_t *rec_tmpl, const bwams_dup_loc_t *tloc, const uint8_t *dup, int64_t n, int n_lib,
                       unsigned long long *counts, unsigned long long *n_marked, int cu_count, hipStream_t st);
 
+// collate.hip: a coordinate-sorted BAM collated by read name (rules C1-C8 in include/bwams.h above bwams_collate_open).  An entry per
+// record that waits for its mate, as arrays in ordinal order: the masked key, where the record lies (the pool, or the piece during
+// an add), its ordinal, its size and its segment (2 first, 3 last).
+struct CoEntries {
+    DevBuf<uint64_t> key;
+    DevBuf<const uint8_t *> ptr;
+    DevBuf<int64_t> ord;
+    DevBuf<int32_t> size;
+    DevBuf<uint8_t> seg;
+};
+constexpr int64_t kCoEntryBytes = 8 + 8 + 8 + 4 + 1;       // 29 per waiting record
+struct CoEntryArrays {                   // the same, as the kernels take it
+    uint64_t *key;
+    const uint8_t **ptr;
+    int64_t *ord;
+    int32_t *size;
+    uint8_t *seg;
+};
+struct CoPlace {                         // what the scans add up: bytes and records
+    int64_t bytes, n;
+};
+// the call words of an add: the first-bad word (ordinal << 3 | reason), the longest run, the pool bytes that died, co_totals' eight
+enum { kCoCallBad = 0, kCoCallMaxRun, kCoCallDied, kCoCallWaitBytes, kCoCallWaitN, kCoCallOldBytes, kCoCallOldN, kCoCallPairBytes,
+       kCoCallPairN, kCoCallSingleBytes, kCoCallSingleN, kCoCallWords };
+enum { kCoReasonBits = 0, kCoReasonSegment = 1 };
+// entry: cls[r] (0 skipped, 1 single, 2 first, 3 last, 4 refused by C2), nkey[r] of the paired ones, paired[0, n] for the scan.
+// append: the paired records' entries at E[n_pend + place[r]], and idx[i] = i over all N.  match: fate and partner per entry (fate
+// zeroed by the caller).  place: the three scans' inputs (N + 1, N - n_pend + 1 and n + 1 slots).  totals: call[kCoCallWaitBytes ..].
+// pairs / singles: the copies with their record offsets.  pool: the waiting entries from `from` on copied to dst + (place - sub),
+// all waiting entries written to F (F.key null: none), rec_at (or null) the copied records' offsets.
+void launch_co_entry(const uint8_t *bam, const int64_t *rec_off, int64_t n, int64_t base, uint64_t mask, uint8_t *cls, uint64_t *nkey,
+                     uint32_t *paired, unsigned long long *call, int cu_count, hipStream_t st);
+int co_scan_u32(void *tmp, size_t &tmp_bytes, const uint32_t *in, uint32_t *out, int64_t n, hipStream_t st);
+int co_scan_place(void *tmp, size_t &tmp_bytes, const CoPlace *in, CoPlace *out, int64_t n, hipStream_t st);
+int co_sort(void *tmp, size_t &tmp_bytes, const uint64_t *key, uint64_t *skey, const uint32_t *idx, uint32_t *sidx, int64_t N, hipStream_t st);
+void launch_co_append(const uint8_t *bam, const int64_t *rec_off, int64_t n, int64_t base, const uint8_t *cls, const uint64_t *nkey,
+                      const uint32_t *place, int64_t n_pend, const CoEntryArrays &E, uint32_t *idx, int64_t N, int cu_count, hipStream_t st);
+void launch_co_match(const uint64_t *skey, const uint32_t *sidx, int64_t N, int64_t n_pend, const CoEntryArrays &E, uint8_t *fate,
+                     uint32_t *partner, unsigned long long *call, int cu_count, hipStream_t st);
+void launch_co_place(const uint8_t *fate, const uint32_t *partner, const int32_t *size, int64_t N, int64_t n_pend, const uint8_t *cls,
+                     const int64_t *rec_off, int64_t n, CoPlace *waits, CoPlace *pairs, CoPlace *singles, int cu_count, hipStream_t st);
+void launch_co_totals(const CoPlace *waits, const CoPlace *pairs, const CoPlace *singles, int64_t N, int64_t n_pend, int64_t n,
+                      unsigned long long *call, hipStream_t st);
+void launch_co_pairs(const CoEntryArrays &E, const uint8_t *fate, const uint32_t *partner, const CoPlace *at, int64_t n_pend, int64_t m,
+                     uint8_t *dst, int64_t *pair_off, int cu_count, hipStream_t st);
+void launch_co_singles(const uint8_t *bam, const int64_t *rec_off, const uint8_t *cls, const CoPlace *at, int64_t n, uint8_t *dst,
+                       int64_t *single_off, int cu_count, hipStream_t st);
+void launch_co_pool(const CoEntryArrays &E, const uint8_t *fate, const CoPlace *at, int64_t from, int64_t N, uint8_t *dst, int64_t sub,
+                    const CoEntryArrays &F, int64_t *rec_at, int cu_count, hipStream_t st);
+
 // api_bam.hip: the offsets of host BAM records bam[0, n_bytes) (n + 1 of them) from their block_size chain, with the checks of
 // bwams_bam_upload (every record whole, block_size >= 32, refID >= -1, POS in [-1, 2^31 - 2], name and CIGAR inside the record) and
 // the largest refID; BWAMS_ERR_ARG with `who` and the first bad record in the last error.

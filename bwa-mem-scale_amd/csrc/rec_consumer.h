@@ -1,4 +1,4 @@
-// rec_consumer.h — what the handles that read BAM records on the device share (depth, pileup, QC, recalibration and its apply, duplicate marking joined by name; host
+// rec_consumer.h — what the handles that read BAM records on the device share (depth, pileup, QC, recalibration and its apply, duplicate marking joined by name, collating by name; host
 // only, for their api_*.hip): the base of the handle structs, the three ways to the records of an add (a batch's, in HBM; host
 // records, uploaded into the handle; the current piece of a BAM file read by region) with their refusals, and the timed sequences around a check kernel and around a piece's kernels.
 // A base struct and free functions: each *_add stays in its own file as check, size buffers, loop over pieces.

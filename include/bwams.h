@@ -988,7 +988,8 @@ int bwams_process_chunk_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *e
 /* bwams_process_chunk / _chunk_smart with bwams_bam_reads_decode in place of bwams_fastq_decode: bam[0, n_bytes) are whole BAM records
  * (host or device memory, no header block), tags as for bwams_bam_reads_decode (the comments reach the SAM text only with
  * BWAMS_CHUNK_COPY_COMMENT).  With paired, kept reads 2k and 2k + 1 are the two ends, in file order — what `samtools fastq | bwa mem -p`
- * does; collating a coordinate-sorted BAM (`samtools collate`) is the caller's job.  Everything behind the decode is bwams_process_chunk's. */
+ * does; a coordinate-sorted BAM is collated first (`samtools collate`) by bwams_collate_t below, whose `pairs` output in device memory
+ * is such input.  Everything behind the decode is bwams_process_chunk's. */
 int bwams_process_chunk_bam(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
                             const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags, int32_t paired,
                             const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes);
@@ -1790,7 +1791,8 @@ int bwams_recal_apply_info(const bwams_recal_apply_t *a, bwams_recal_apply_info_
  * The kernels: the record discovery of bwams_bam_reads_decode (csrc/bam_discover.h) from an offset to an offset; a select kernel, a
  * lane per record, with the merged regions in LDS; two scans; the sorter's gather into the handle's record buffer.  _info: a test
  * and measurement hook (bwams_bam_file_info_t, include/bwams_types.h).
- * A sixth consumer of the pieces is the join handle below: bwams_dupjoin_add_file and bwams_dupjoin_apply_file.
+ * A sixth consumer of the pieces is the join handle below: bwams_dupjoin_add_file and bwams_dupjoin_apply_file; a seventh the
+ * collate handle behind it: bwams_collate_add_file.
  * Out of scope: CRAM, CSI and tabix indexes, unsorted input beyond whole-file mode, several files merged, writing. */
 int bwams_bam_file_open(const char *path, const char *bai_path, int device, int64_t piece_bytes, bwams_bam_file_t **out);
 int bwams_bam_file_header(const bwams_bam_file_t *f, const char **text, int64_t *n_text, int32_t *n_ref);
@@ -1880,6 +1882,72 @@ int bwams_dupjoin_apply_file(bwams_dupjoin_t *j, bwams_bam_file_t *f, int64_t *n
 int bwams_dupjoin_info(const bwams_dupjoin_t *j, bwams_dupjoin_info_t *info);
 int bwams_dupjoin_key(const void *name, int32_t n, uint64_t key[2]);
 int bwams_bam_file_header_block(const bwams_bam_file_t *f, const void **block, int64_t *n);
+
+/* ------------------------------ Collating a coordinate-sorted BAM by read name ---- */
+
+/* Re-aligning an existing BAM starts from a coordinate-sorted file, while a paired chunk of bwams_process_chunk_bam wants the two
+ * ends of a pair next to each other.  A seventh record consumer, bwams_collate_t, on one device, joins mates while the file streams
+ * through (csrc/collate.hip): each add gives back the pairs it completed and its single reads, and keeps only the records that still
+ * wait for their mate in device memory.  In a coordinate-sorted file most mates lie a few hundred bases apart, so that set stays
+ * small.  bwams/collate.py restates the rules with a dict.
+ * "Add order" and a record's 64-bit ORDINAL are as for bwams_dupjoin_t: the order of the _add_* calls, then record order within each;
+ * every added record has an ordinal, skipped ones included.  There is no 2^32 limit on ordinals.
+ *  C1. Kept records.  Records with FLAG 0x100 or 0x800 are skipped and counted; they never enter the pool.  This is rule 2 of
+ *      bwams_bam_reads_decode: they would not become reads anyway.
+ *  C2. Segment.  A kept record with 0x1 clear is SINGLE.  With 0x1 set it is FIRST when 0x40 is set and 0x80 clear, LAST when 0x80
+ *      is set and 0x40 clear; 0x1 with both or neither of 0x40 and 0x80 is refused (C6).
+ *  C3. The walk, defined sequentially; the device reproduces it exactly.  A table `pending` holds at most one record per name, a
+ *      name being its bytes without the NUL, compared byte for byte.  Kept records are taken in ordinal order.  A single is emitted at
+ *      once.  A paired record R whose name is not pending becomes pending.  When the name is pending with a record P of the other
+ *      segment, the pair (first, last) is emitted and the name leaves the table.  When P is of the same segment the add is refused
+ *      (C6).  A record whose name's pair was emitted before simply waits again and ends as an orphan: nothing remembers emitted names.
+ *  C4. Output of an add: two byte strings of whole records, each record byte for byte as it came in; no bit is set or cleared.
+ *      `pairs`: every pair this add completed, the first record then the last, in the order of the ordinals of the records that
+ *      completed them.  `singles`: the add's singles in ordinal order.  So any prefix of `pairs` that ends on a pair boundary is
+ *      input for bwams_process_chunk_bam with paired = 1, and `singles` with paired = 0.
+ *  C5. Finish.  _finish sets `pairs` to empty and `singles` to the pending records in ordinal order (the orphans); the table is
+ *      empty afterwards.  Then adds are refused with BWAMS_ERR_ARG and a text until _reset.  Over a whole run the outputs of all adds
+ *      and of the finish hold every kept record exactly once.
+ *  C6. Refusals.  BWAMS_ERR_UNSUPPORTED with the text "record K" and the reason, K being the smallest ordinal at which the sequential
+ *      walk meets a fault of C2 or C3, whichever rule it is.  The handle (pending set, counters, previous output) is left exactly as
+ *      before the add.  Malformed record chains are refused as the other consumers' _add_records refuse them, a file on another
+ *      device as their _add_file does.
+ *  C7. Keys are a device, not a rule.  The kernels group candidates by rule J1's k0; a pair is only made after the two names were
+ *      compared byte by byte, length included.  A key collision, which can be constructed in untrusted input, costs time (a run of
+ *      equal keys is walked in the square of its length) and never a wrong pair.  bwams_collate_opt_t.key_mask (default all ones) is
+ *      ANDed onto the key before grouping: a test hook that makes the collision path reachable; mask 0 puts every record into one run.
+ *  C8. Pool.  Pending records live in a device pool that grows on demand, in blocks that are never moved to grow: their bytes, and
+ *      an entry of 29 bytes each (masked key, address, ordinal, size, segment).  opt.pool_bytes > 0 caps the bytes of pending
+ *      records: an add after which more would wait is BWAMS_ERR_NOMEM with the size asked for in the text and leaves the handle as
+ *      before the add; so does a device allocation that fails.  An add moves pool bytes only when it compacts: the records still
+ *      waiting are copied into one fresh block and the old blocks are freed, which takes the live bytes once more for that moment.  It
+ *      compacts when the dead bytes exceed the live bytes, or when the pool's used bytes would otherwise pass the cap.  Without a
+ *      cap bytes_compacted <= bytes_pooled holds at all times: each pooled byte dies once, and a compaction moves fewer live bytes
+ *      than the dead bytes it retires.  Every buffer the copies read has the 16 bytes of slack behind it that bwams_bam_sort asks for.
+ * bwams_collate_open: opt may be NULL (no cap, every key bit); reserved != 0 or pool_bytes < 0 is BWAMS_ERR_ARG.  _reset returns to
+ * empty and keeps the options; _close takes NULL.  _add_records: host records; _add_file: the file's current piece, where it lies;
+ * *n_added the records of the add, skipped ones included; an add of no records is an add.  There is no _add_batch: a batch's records
+ * are grouped already.  _finish: *n_orphans.  _out: device pointers to the output of the last add or finish, valid until the next
+ * _add_*, _finish, _reset or _close; before any add the output is empty.  _fetch copies that output to the host: pairs and singles
+ * (their capacities in bytes), pair_off with 2 * n_pairs + 1 record offsets and single_off with n_singles + 1; any pointer may be
+ * NULL; a capacity too small for a pointer given is BWAMS_ERR_CAPACITY.  _info: a test and measurement hook (bwams_collate_info_t,
+ * include/bwams_types.h).
+ * Memory: the pending records' bytes, 29 bytes of entry each (twice while an add writes the next entries), the output of one add,
+ * and per add 49 bytes of scratch per record of the piece and 53 per entry sorted, pending ones included (85 for the piece's own
+ * paired records), kept between adds, beside rocPRIM's own.
+ * Out of scope: spilling the pool to host memory; a reader thread that collates (bwams_reader_open_bam stays as it is); name-sorted
+ * output (`samtools sort -n`); keeping secondary and supplementary records; several files merged; a device hash table in place of
+ * the sort (the follow-up if a measurement points at the sort). */
+int bwams_collate_open(int device, const bwams_collate_opt_t *opt, bwams_collate_t **out);
+int bwams_collate_reset(bwams_collate_t *c);
+int bwams_collate_close(bwams_collate_t *c);
+int bwams_collate_add_records(bwams_collate_t *c, const void *bam, int64_t n_bytes, int64_t *n_added);
+int bwams_collate_add_file(bwams_collate_t *c, bwams_bam_file_t *f, int64_t *n_added);
+int bwams_collate_finish(bwams_collate_t *c, int64_t *n_orphans);
+int bwams_collate_out(const bwams_collate_t *c, bwams_collate_out_t *out);
+int bwams_collate_fetch(bwams_collate_t *c, void *pairs, int64_t cap_pairs, int64_t *pair_off, void *singles, int64_t cap_singles,
+                        int64_t *single_off);
+int bwams_collate_info(const bwams_collate_t *c, bwams_collate_info_t *info);
 
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);

@@ -565,6 +565,39 @@ typedef struct bwams_dupjoin_info {
     float   ms_add, ms_sort, ms_ends, ms_decide, ms_apply, pad2_;
 } bwams_dupjoin_info_t;
 
+/* A coordinate-sorted BAM collated by read name (include/bwams.h, above bwams_collate_open).  A collate handle lives on one device. */
+typedef struct bwams_collate bwams_collate_t;
+
+/* bwams_collate_open's options.  pool_bytes: 0 = no cap, > 0 = the most bytes of waiting records the pool may hold (rule C8);
+ * key_mask: ANDed onto a name's key before grouping (rule C7; a test hook).  Without options: no cap, all ones. */
+typedef struct bwams_collate_opt {
+    int64_t  pool_bytes;
+    uint64_t key_mask;
+    uint32_t reserved[2];
+} bwams_collate_opt_t;
+
+/* bwams_collate_out: the output of the last add or finish in device memory (rule C4), whole records back to back. */
+typedef struct bwams_collate_out {
+    const void *pairs;
+    int64_t     pairs_bytes, n_pairs;
+    const void *singles;
+    int64_t     singles_bytes, n_singles;
+} bwams_collate_out_t;
+
+/* bwams_collate_info: totals since open or the last reset.  records: all added (= the next ordinal); skipped: rule C1's; pairs and
+ * singles: emitted by the adds; orphans: emitted by _finish; pending and pending_bytes: the records that wait now; pool_capacity:
+ * the bytes of the pool's blocks; bytes_pooled: record bytes ever put into the pool; compactions and bytes_compacted: rule C8;
+ * max_run: the longest run of equal masked keys the match kernel walked; adds: successful ones; state: 0 empty, 1 adding, 2
+ * finished.  The times are for measurement only (tools/collate_rate.py), device time between events over all adds: ms_entry the
+ * entry kernel, its scan and the append, ms_group the sort, ms_match the match kernel, ms_place the placement with its three
+ * scans, ms_copy the three copies. */
+typedef struct bwams_collate_info {
+    int64_t records, skipped, pairs, singles, orphans, pending, pending_bytes, pool_capacity, bytes_pooled, compactions, bytes_compacted,
+            max_run, adds;
+    int32_t state, pad_;
+    float   ms_entry, ms_group, ms_match, ms_place, ms_copy, pad2_;
+} bwams_collate_info_t;
+
 #ifdef __cplusplus
 }
 #endif
