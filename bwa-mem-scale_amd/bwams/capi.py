@@ -83,6 +83,8 @@ SYMBOLS = [
     "bwams_dupjoin_key", "bwams_bam_file_header_block",
     "bwams_collate_open", "bwams_collate_reset", "bwams_collate_close", "bwams_collate_add_records", "bwams_collate_add_file",
     "bwams_collate_finish", "bwams_collate_out", "bwams_collate_fetch", "bwams_collate_info",
+    "bwams_samview_open", "bwams_samview_close", "bwams_samview_add_records", "bwams_samview_add_batch", "bwams_samview_add_file",
+    "bwams_samview_out", "bwams_samview_fetch", "bwams_samview_fetch_bgzf", "bwams_samview_info", "bwams_fmt_float",
     "bwams_dedup_run", "bwams_dedup_fetch", "bwams_chain_run_ert", "bwams_pestat", "bwams_pestat_keys", "bwams_pestat_from_keys", "bwams_pair_run", "bwams_pair_run_sam", "bwams_pair_fetch", "bwams_emf_regs_run", "bwams_emf_regs_fetch",
 ]
 ERT_MEM_DTYPE = np.dtype([("forward", "u1"), ("pad_", "u1", (3,)), ("start", "<i4"), ("end", "<i4"), ("rc_start", "<i4"),
@@ -1228,6 +1230,71 @@ class Collate(_Consumer):
         return self._info("bwams_collate_info", CollateInfo)
 
 
+class SamViewOpt(C.Structure):
+    _fields_ = [("flag_require", C.c_uint32), ("flag_exclude", C.c_uint32), ("min_mapq", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class SamViewOut(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("n_bytes", C.c_int64), ("line_off", C.c_void_p), ("n_lines", C.c_int64), ("n_records", C.c_int64)]
+
+
+class SamViewInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("records", "lines", "filtered", "bytes", "adds")] + \
+               [(n, C.c_float) for n in ("ms_count", "ms_write")]
+
+
+class SamView(_Consumer):
+    """BAM records viewed as SAM text (bwams_samview_t): add_records / add_batch / add_file (-> the lines), each followed by out(),
+    fetch() or fetch_bgzf() for the lines of that add."""
+    _close = "bwams_samview_close"
+    _prefix = "bwams_samview"
+
+    def __init__(self, bam_header: bytes, device: int = 0, require: int = 0, exclude: int = 0, min_mapq: int = 0, reserved: int = 0,
+                 opt=True):
+        self.h = C.c_void_p()
+        hdr = bytes(bam_header)
+        o = SamViewOpt(require, exclude, min_mapq, reserved)
+        _chk(lib().bwams_samview_open(device, hdr, len(hdr), C.byref(o) if opt else None, C.byref(self.h)), "bwams_samview_open")
+
+    def reset(self) -> None:
+        raise NotImplementedError("a view keeps nothing between adds")
+
+    def out(self) -> SamViewOut:
+        """The lines of the last add in device memory: .text and .line_off are device addresses (.text None when empty), valid
+        until the next add or close."""
+        o = SamViewOut()
+        self._call("bwams_samview_out", C.byref(o))
+        return o
+
+    def fetch(self, cap: int | None = None):
+        """-> (text: bytes, line_off: int64[n_lines + 1]); cap: the capacity offered instead of the text's size"""
+        o = self.out()
+        text, off = np.zeros(max(o.n_bytes, 1), np.uint8), np.zeros(o.n_lines + 1, np.int64)
+        self._call("bwams_samview_fetch", _p(text), o.n_bytes if cap is None else cap, _p(off))
+        return text[:o.n_bytes].tobytes(), off
+
+    def fetch_bgzf(self, deflater: "Deflater", eof: bool = False) -> bytes:
+        """The lines of the last add as BGZF members, compressed on the device where they lie (bwams_samview_fetch_bgzf)."""
+        cap = deflate_bound(self.out().n_bytes)
+        buf = C.create_string_buffer(cap)
+        n = C.c_int64(0)
+        self._call("bwams_samview_fetch_bgzf", deflater.h, C.addressof(buf), cap, DEFLATE_EOF if eof else 0, C.byref(n))
+        return buf.raw[:n.value]
+
+    def info(self) -> dict:
+        return self._info("bwams_samview_info", SamViewInfo)
+
+
+def fmt_float(x) -> bytes:
+    """Rule V5 (bwams_fmt_float): the text of a float as "%g" prints it; x is a number, or an int taken as the float's 32 bits when
+    given as np.uint32.  No device is needed."""
+    v = np.array([x], np.uint32).view(np.float32) if isinstance(x, np.uint32) else np.array([x], np.float32)
+    buf = C.create_string_buffer(16)
+    n = C.c_int32(0)
+    _chk(lib().bwams_fmt_float(C.c_float.from_buffer_copy(v.tobytes()), buf, C.byref(n)), "bwams_fmt_float")
+    return buf.raw[:n.value]
+
+
 class Gunzipper:
     """Plain gzip inflated on one GPU (bwams_gunzip_t): one file, fed in order."""
 
@@ -1596,6 +1663,16 @@ def lib():
         L.bwams_collate_out.argtypes = [vp, vp]
         L.bwams_collate_fetch.argtypes = [vp, vp, i64, vp, vp, i64, vp]
         L.bwams_collate_info.argtypes = [vp, vp]
+        L.bwams_samview_open.argtypes = [C.c_int, vp, i64, vp, vp]
+        L.bwams_samview_close.argtypes = [vp]
+        L.bwams_samview_add_records.argtypes = [vp, vp, i64, vp]
+        L.bwams_samview_add_batch.argtypes = [vp, vp, vp]
+        L.bwams_samview_add_file.argtypes = [vp, vp, vp]
+        L.bwams_samview_out.argtypes = [vp, vp]
+        L.bwams_samview_fetch.argtypes = [vp, vp, i64, vp]
+        L.bwams_samview_fetch_bgzf.argtypes = [vp, vp, vp, i64, i32, vp]
+        L.bwams_samview_info.argtypes = [vp, vp]
+        L.bwams_fmt_float.argtypes = [C.c_float, vp, vp]
         L.bwams_dup_groups_rg_id.argtypes = [vp, i64]
         L.bwams_dup_groups_rg_id.restype = C.c_char_p
         L.bwams_reg2aln_run.argtypes = [vp, vp, i32, vp, vp, vp]

@@ -52,24 +52,6 @@ struct bwams_collate : RecConsumer {
 
 namespace {
 
-int no_memory(const char *who, size_t bytes, const char *what) {
-    (void)hipGetLastError();
-    set_last_error(std::string(who) + ": " + std::to_string(bytes) + " bytes of device memory for " + what + " could not be had");
-    return BWAMS_ERR_NOMEM;
-}
-
-// room for n elements; what b held is not kept, and b is left as it was when the memory cannot be had
-template <class T> int fresh(DevBuf<T> &b, size_t n, const char *who, const char *what) {
-    const size_t bytes = n * sizeof(T);
-    if (bytes <= b.cap) return BWAMS_OK;
-    DevBuf<T> nb;
-    const hipError_t e = nb.alloc(bytes + bytes / 8 + 4096);
-    if (e == hipErrorOutOfMemory) return no_memory(who, bytes, what);
-    BWAMS_HIP(e);
-    b = std::move(nb);
-    return BWAMS_OK;
-}
-
 // room for n elements, the first `have` kept
 template <class T> int grow_keep(DevBuf<T> &b, int64_t have, int64_t n, const char *who, hipStream_t st) {
     DevBuf<T> nb;
@@ -120,22 +102,6 @@ int refuse_finished(const char *who) {
 void set_output(bwams_collate *c, int64_t pb, int64_t np, int64_t sb, int64_t ns) {
     c->pairs_bytes = pb; c->n_pairs = np; c->singles_bytes = sb; c->n_singles = ns;
 }
-
-// An output buffer that is too small gets a replacement in `next`; nothing of the handle changes before commit.
-template <class T> struct Staged {
-    DevBuf<T> *cur;
-    DevBuf<T> next;
-    int stage(size_t n, const char *who, const char *what) {
-        const size_t bytes = n * sizeof(T);
-        if (bytes <= cur->cap) return BWAMS_OK;
-        const hipError_t e = next.alloc(bytes + bytes / 8 + 4096);
-        if (e == hipErrorOutOfMemory) return no_memory(who, bytes, what);
-        BWAMS_HIP(e);
-        return BWAMS_OK;
-    }
-    T *p() const { return next.p ? next.p : cur->p; }
-    void commit() { if (next.p) *cur = std::move(next); }
-};
 
 int co_add(bwams_collate *c, const DevRecords &R, int64_t *n_added, const char *who) {
     const int64_t n = R.n_rec, n_pend = c->n_pend, base = c->I.records;

@@ -397,6 +397,28 @@ void launch_co_singles(const uint8_t *bam, const int64_t *rec_off, const uint8_t
 void launch_co_pool(const CoEntryArrays &E, const uint8_t *fate, const CoPlace *at, int64_t from, int64_t N, uint8_t *dst, int64_t sub,
                     const CoEntryArrays &F, int64_t *rec_at, int cu_count, hipStream_t st);
 
+// samview.hip: BAM records as SAM lines (rules V1-V8 in include/bwams.h above bwams_samview_open).  The reference names lie back to
+// back without their NULs, name r being names[name_off[r], name_off[r + 1]).  count: size[r] = (the line's bytes, 1), or (0, 0) for
+// a record rule V2 filters or rule V6 refuses, size[n_rec] = (0, 0); *bad = min(*bad, r << 3 | reason - 1).  write: `at` is the
+// exclusive scan of size over its n_rec + 1 slots; the lines at text + at[r].bytes, line_off[at[r].n] = at[r].bytes, the end of
+// the last line from slot n_rec.
+struct SvArgs {
+    const uint8_t *bam;
+    const int64_t *rec_off;
+    int64_t n_rec;
+    const uint8_t *names;
+    const int64_t *name_off;
+    int32_t n_ref;
+    uint32_t require, exclude, min_mapq;
+    CoPlace *size;
+    const CoPlace *at;
+    uint8_t *text;
+    int64_t *line_off;
+    unsigned long long *bad;
+};
+void launch_samview_count(const SvArgs &A, int cu_count, hipStream_t st);
+void launch_samview_write(const SvArgs &A, int cu_count, hipStream_t st);
+
 // api_bam.hip: the offsets of host BAM records bam[0, n_bytes) (n + 1 of them) from their block_size chain, with the checks of
 // bwams_bam_upload (every record whole, block_size >= 32, refID >= -1, POS in [-1, 2^31 - 2], name and CIGAR inside the record) and
 // the largest refID; BWAMS_ERR_ARG with `who` and the first bad record in the last error.

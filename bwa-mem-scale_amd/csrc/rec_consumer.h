@@ -139,4 +139,39 @@ template <class Launch> int consumer_piece(RecConsumer *c, unsigned long long *d
     return BWAMS_OK;
 }
 
+// Device memory for a handle's buffers: a failed allocation is BWAMS_ERR_NOMEM with the size asked for, and leaves what was there.
+inline int no_memory(const char *who, size_t bytes, const char *what) {
+    (void)hipGetLastError();
+    set_last_error(std::string(who) + ": " + std::to_string(bytes) + " bytes of device memory for " + what + " could not be had");
+    return BWAMS_ERR_NOMEM;
+}
+
+// room for n elements; what b held is not kept, and b is left as it was when the memory cannot be had
+template <class T> int fresh(DevBuf<T> &b, size_t n, const char *who, const char *what) {
+    const size_t bytes = n * sizeof(T);
+    if (bytes <= b.cap) return BWAMS_OK;
+    DevBuf<T> nb;
+    const hipError_t e = nb.alloc(bytes + bytes / 8 + 4096);
+    if (e == hipErrorOutOfMemory) return no_memory(who, bytes, what);
+    BWAMS_HIP(e);
+    b = std::move(nb);
+    return BWAMS_OK;
+}
+
+// An output buffer that is too small gets a replacement in `next`; nothing of the handle changes before commit.
+template <class T> struct Staged {
+    DevBuf<T> *cur;
+    DevBuf<T> next;
+    int stage(size_t n, const char *who, const char *what) {
+        const size_t bytes = n * sizeof(T);
+        if (bytes <= cur->cap) return BWAMS_OK;
+        const hipError_t e = next.alloc(bytes + bytes / 8 + 4096);
+        if (e == hipErrorOutOfMemory) return no_memory(who, bytes, what);
+        BWAMS_HIP(e);
+        return BWAMS_OK;
+    }
+    T *p() const { return next.p ? next.p : cur->p; }
+    void commit() { if (next.p) *cur = std::move(next); }
+};
+
 }  // namespace bwams

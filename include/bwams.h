@@ -1949,6 +1949,69 @@ int bwams_collate_fetch(bwams_collate_t *c, void *pairs, int64_t cap_pairs, int6
                         int64_t *single_off);
 int bwams_collate_info(const bwams_collate_t *c, bwams_collate_info_t *info);
 
+/* ------------------------------ Viewing BAM records as SAM text ---- */
+
+/* The way back from BAM bytes to SAM text: `samtools view` on records that lie in device memory.  An eighth record consumer,
+ * bwams_samview_t, on one device (csrc/samview.hip, the inverse of csrc/bam.hip): each add of BAM records gives their SAM lines in
+ * device memory, to be fetched as text, compressed where they lie, or handed on by pointer.  bwams/samview.py restates the rules.
+ * The yardsticks are SAMv1 sections 1.4 and 4.2, htslib's sam_format1 rules as restated there, hand-written (record, line) pairs,
+ * and the round trip through this library's own encoder; nothing here was run against htslib.
+ *  V1. Output model, as bwams_collate_t's.  An add replaces the handle's output with the lines of that add's records, in record
+ *      order.  Each line ends in '\n'; line_off has n_lines + 1 entries.  The output stays valid until the next _add_* or _close;
+ *      before any add it is empty.  An add of no records is an add.  All offsets are 64-bit.
+ *  V2. Filter (`samtools view -f / -F / -q`).  A record gives a line iff (FLAG & flag_require) == flag_require, (FLAG &
+ *      flag_exclude) == 0 and MAPQ >= min_mapq.  Other records are counted as filtered and give no bytes.  *n_lines counts the lines.
+ *  V3. The eleven fields, tab separated.  QNAME: the l_read_name - 1 bytes as they are.  FLAG in decimal.  RNAME: the reference's
+ *      name, or `*` for refID -1.  POS + 1.  MAPQ.  CIGAR: <len><op> over MIDNSHP=X, or `*` for n_cigar_op == 0.  RNEXT: `*` for next
+ *      refID -1, `=` when equal to refID (and not -1), else the name.  PNEXT + 1.  TLEN, signed.  SEQ through =ACMGRSVTWYHKDBN, high
+ *      nibble first, or `*` for l_seq == 0.  QUAL + 33, or `*` when l_seq == 0 or the first quality byte is 0xFF.
+ *  V4. Aux fields, in record order, each behind a tab.  A gives TG:A:c.  c C s S i I all give TG:i:<decimal>.  Z and H give TG:Z: /
+ *      TG:H: and the bytes up to the NUL.  f gives TG:f: and rule V5.  B gives TG:B:<subtype>, then ,<value> per element, formatted by
+ *      the subtype's own rule; a count of 0 gives TG:B:c and nothing more.
+ *  V5. Floats.  The text is what C's "%g" gives for the value widened to double: six significant digits, round-half-even on the exact
+ *      value; trailing zeros and a bare point removed; scientific form d.ddddde±XX (at least two exponent digits) when the decimal
+ *      exponent is below -4 or at least 6; inf, -inf, nan, -nan (the sign bit, as glibc prints it), 0 and -0.  No floating-point
+ *      arithmetic computes it: csrc/fmt_g.h does it in integer arithmetic on the float's mantissa and exponent, for the kernels and
+ *      for bwams_fmt_float alike.  At most 13 bytes come out.
+ *  V6. Refusals.  The counting pass decides before a byte of output is written: BWAMS_ERR_UNSUPPORTED with "record K" and the reason,
+ *      K being the smallest 0-based ordinal within the add at which any of these holds:
+ *        1. refID or next refID outside [-1, n_ref);
+ *        2. l_read_name == 0, the name's last byte not NUL, or a NUL inside it;
+ *        3. a CIGAR op code above 8;
+ *        4. l_seq < 0, or name + CIGAR + SEQ + QUAL pass the record's end;
+ *        5. the aux fields do not chain to the record's end, exactly as the other consumers decide it (a type that is none of
+ *           A c C s S i I f Z H B, a B subtype that is none of c C s S i I f, a field past the end, a Z or H without its NUL): so
+ *           type `d` is refused here as everywhere else.
+ *      When several hold at record K the reason given is the first in the order 1, 4, 2, 3, 5: what 4 refuses cannot be read for
+ *      the others.  Filtered records are checked too.  A refused add leaves the handle's previous output and counters exactly as
+ *      they were.  Malformed record chains, a missing batch product, and a batch or file on another device are refused as the
+ *      other consumers refuse them (BWAMS_ERR_ARG).
+ *  V7. Nothing is interpreted.  Tabs or newlines inside a name or a Z value come out as they are; a CG:B:I long-CIGAR tag is
+ *      printed as a tag; the bin is ignored.
+ *  V8. Memory, all kept between adds and grown on demand: the output text, line_off, 32 bytes per record of an add (its size and
+ *      its place, as bytes and lines), rocPRIM's scan scratch, the reference names.  A failed allocation is BWAMS_ERR_NOMEM with
+ *      the size asked for and leaves the handle as before.
+ * bwams_samview_open: bam_header is a BAM header block (bwams_bam_header builds one, bwams_bam_file_header_block and
+ * bwams_sorter_open hand one over); the reference names and n_ref come from it and go to the device once.  A block that is cut off
+ * or has the wrong magic is BWAMS_ERR_ARG.  opt may be NULL (keep everything); reserved != 0 is BWAMS_ERR_ARG.  _close takes NULL.
+ * _add_records: host records; _add_batch: the batch's current BAM records; _add_file: the file's current piece; all where they
+ * lie.  _out: device pointers, rule V1.  _fetch copies text (cap bytes; too small is BWAMS_ERR_CAPACITY) and the n_lines + 1
+ * offsets to the host; either pointer may be NULL.  _fetch_bgzf is bwams_sam_fetch_bgzf for this text: the deflater reads the
+ * device text, same `flags`.  _info: a test and measurement hook.  bwams_fmt_float: rule V5 on the host, no device needed; out gets
+ * *n bytes and a NUL behind them.
+ * Out of scope: type `d`; expanding a CG tag into the CIGAR; region text parsing in C (regions stay bwams_pileup_region_t);
+ * `--rf` / `-G` / subsampling; a writer thread; CRAM; load balance for very long reads (one lane group owns a whole record). */
+int bwams_samview_open(int device, const void *bam_header, int64_t n_header, const bwams_samview_opt_t *opt, bwams_samview_t **out);
+int bwams_samview_close(bwams_samview_t *v);
+int bwams_samview_add_records(bwams_samview_t *v, const void *bam, int64_t n_bytes, int64_t *n_lines);
+int bwams_samview_add_batch(bwams_samview_t *v, bwams_batch_t *b, int64_t *n_lines);
+int bwams_samview_add_file(bwams_samview_t *v, bwams_bam_file_t *f, int64_t *n_lines);
+int bwams_samview_out(const bwams_samview_t *v, bwams_samview_out_t *out);
+int bwams_samview_fetch(bwams_samview_t *v, char *text, int64_t cap, int64_t *line_off);
+int bwams_samview_fetch_bgzf(bwams_samview_t *v, bwams_deflater_t *d, void *out, int64_t cap, int32_t flags, int64_t *n_out);
+int bwams_samview_info(const bwams_samview_t *v, bwams_samview_info_t *info);
+int bwams_fmt_float(float x, char out[16], int32_t *n);
+
 /* Page-locked host memory (hipHostMalloc) for the buffers that cross PCIe every chunk: reads, names and qualities up, SAM text down. */
 int bwams_host_alloc(size_t bytes, void **out);
 int bwams_host_free(void *p);

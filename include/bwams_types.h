@@ -598,6 +598,35 @@ typedef struct bwams_collate_info {
     float   ms_entry, ms_group, ms_match, ms_place, ms_copy, pad2_;
 } bwams_collate_info_t;
 
+/* BAM records viewed as SAM text (include/bwams.h, above bwams_samview_open).  A view handle lives on one device. */
+typedef struct bwams_samview bwams_samview_t;
+
+/* bwams_samview_open's options: rule V2's filter, `samtools view -f / -F / -q`.  Without options every record gives a line. */
+typedef struct bwams_samview_opt {
+    uint32_t flag_require, flag_exclude;
+    int32_t  min_mapq;
+    uint32_t reserved;
+} bwams_samview_opt_t;
+
+/* bwams_samview_out: the lines of the last add in device memory (rule V1).  line_off has n_lines + 1 entries, line k being
+ * text[line_off[k], line_off[k + 1]) with its newline; n_records: the records of that add, filtered ones included.  text is NULL
+ * when there are no bytes; line_off is never NULL. */
+typedef struct bwams_samview_out {
+    const char    *text;
+    int64_t        n_bytes;
+    const int64_t *line_off;
+    int64_t        n_lines, n_records;
+} bwams_samview_out_t;
+
+/* bwams_samview_info: totals since open over the successful adds.  records: all added; lines: the records that gave a line;
+ * filtered: those rule V2 dropped (records = lines + filtered); bytes: the text written; adds: successful ones.  The times are for
+ * measurement only (tools/samview_rate.py), device time between events over all adds: ms_count the counting pass with its scan,
+ * ms_write the writing pass. */
+typedef struct bwams_samview_info {
+    int64_t records, lines, filtered, bytes, adds;
+    float   ms_count, ms_write;
+} bwams_samview_info_t;
+
 #ifdef __cplusplus
 }
 #endif
