@@ -81,6 +81,7 @@ SYMBOLS = [
     "bwams_dupjoin_open", "bwams_dupjoin_reset", "bwams_dupjoin_close", "bwams_dupjoin_add_records", "bwams_dupjoin_add_file",
     "bwams_dupjoin_finish", "bwams_dupjoin_fetch", "bwams_dupjoin_apply_records", "bwams_dupjoin_apply_file", "bwams_dupjoin_info",
     "bwams_dupjoin_key", "bwams_bam_file_header_block",
+    "bwams_bam_file_open_merge", "bwams_bam_merge_info", "bwams_bam_header_merge",
     "bwams_collate_open", "bwams_collate_reset", "bwams_collate_close", "bwams_collate_add_records", "bwams_collate_add_file",
     "bwams_collate_finish", "bwams_collate_out", "bwams_collate_fetch", "bwams_collate_info",
     "bwams_samview_open", "bwams_samview_close", "bwams_samview_add_records", "bwams_samview_add_batch", "bwams_samview_add_file",
@@ -1026,6 +1027,30 @@ class BamFileInfo(C.Structure):
                [(n, C.c_float) for n in ("ms_read", "ms_inflate", "ms_discover", "ms_select", "ms_gather")] + [("pad_", C.c_int32)]
 
 
+class BamMergeOpt(C.Structure):
+    _fields_ = [("child_bytes", C.c_int64), ("reserved", C.c_int32), ("pad_", C.c_int32)]
+
+
+class BamMergeInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_files", "child_bytes", "rounds", "refills", "records", "bytes", "max_piece_records",
+                                         "max_piece_bytes", "max_window_left")] + [("pg_dropped", C.c_int32), ("pad_", C.c_int32)] + \
+               [(n, C.c_float) for n in ("ms_check", "ms_frontier", "ms_rank", "ms_scan", "ms_gather", "ms_refill")]
+
+
+def bam_header_merge(blocks) -> tuple[bytes, int]:
+    """bwams_bam_header_merge: (the merged BAM header block, the @PG lines dropped) of the files' header blocks (host only)."""
+    blocks = [bytes(b) for b in blocks]
+    ptr = (C.c_char_p * max(len(blocks), 1))(*blocks)
+    sizes = (C.c_int64 * max(len(blocks), 1))(*[len(b) for b in blocks])
+    n, dropped = C.c_int64(0), C.c_int32(0)
+    rc = lib().bwams_bam_header_merge(ptr, sizes, len(blocks), None, 0, C.byref(n), C.byref(dropped))
+    if rc != -4:
+        _chk(rc, "bwams_bam_header_merge")
+    out = C.create_string_buffer(max(n.value, 1))
+    _chk(lib().bwams_bam_header_merge(ptr, sizes, len(blocks), out, n.value, C.byref(n), C.byref(dropped)), "bwams_bam_header_merge")
+    return out.raw[:n.value], dropped.value
+
+
 def _regions(regions):
     a = np.zeros(len(regions), PILEUP_REGION_DTYPE)
     for k, (r, b, e) in enumerate(regions):
@@ -1056,6 +1081,27 @@ class BamFile(_Handle):
         _chk(lib().bwams_bam_file_open(path.encode(), bai_path.encode() if bai_path else None, device, piece_bytes, C.byref(self.h)),
              "bwams_bam_file_open")
         self.n_records = self.n_bytes = 0
+
+    @classmethod
+    def merge(cls, paths, bai_paths=None, device: int = 0, piece_bytes: int = 0, child_bytes: int = 0, reserved: int = 0) -> "BamFile":
+        """bwams_bam_file_open_merge: the coordinate-sorted files at `paths` as one record stream in coordinate order; every other
+        call is the same as on one file.  bai_paths: None, or a path or None per file."""
+        paths = [p.encode() for p in paths]
+        ptr = (C.c_char_p * max(len(paths), 1))(*paths)
+        bai = None
+        if bai_paths is not None:
+            bai = (C.c_char_p * max(len(paths), 1))(*[b.encode() if b else None for b in bai_paths])
+        opt = BamMergeOpt(child_bytes, reserved, 0)
+        f = cls.__new__(cls)
+        f.h = C.c_void_p()
+        f.n_records = f.n_bytes = 0
+        _chk(lib().bwams_bam_file_open_merge(ptr, bai, len(paths), device, piece_bytes, C.byref(opt) if child_bytes or reserved else None,
+                                             C.byref(f.h)), "bwams_bam_file_open_merge")
+        return f
+
+    def merge_info(self) -> dict:
+        """bwams_bam_merge_info: a merged handle's counts and stage times since the last query"""
+        return self._info("bwams_bam_merge_info", BamMergeInfo)
 
     def header(self) -> tuple[bytes, int]:
         """(the header text, n_ref)"""
@@ -1643,6 +1689,9 @@ def lib():
             getattr(L, name).argtypes = [vp, vp, vp]
         L.bwams_bai_plan.argtypes = [vp, i64, vp, i32, vp, vp, i64, vp]
         L.bwams_bam_file_header_block.argtypes = [vp, vp, vp]
+        L.bwams_bam_file_open_merge.argtypes = [vp, vp, i32, C.c_int, i64, vp, vp]
+        L.bwams_bam_merge_info.argtypes = [vp, vp]
+        L.bwams_bam_header_merge.argtypes = [vp, vp, i32, vp, i64, vp, vp]
         L.bwams_dupjoin_open.argtypes = [C.c_int, vp, vp, vp]
         L.bwams_dupjoin_reset.argtypes = [vp]
         L.bwams_dupjoin_close.argtypes = [vp]

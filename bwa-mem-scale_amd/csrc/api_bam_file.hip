@@ -2,12 +2,40 @@
 // query, the pieces and their fetch, over host/bam_query.h (header, index, plan, the file's members) and bam_query.hip (the records
 // of a piece found, selected and copied on the device); bwams_bai_plan, the plan alone.  The consumers reach the current piece
 // through consumer_file (rec_consumer.h).  No CPU fallback: the records are found and selected by HIP kernels or the call fails.
+// A handle of bwams_bam_file_open_merge is the same struct with a merge part: it owns a plain handle per file and its pieces are
+// rounds of bam_merge.hip's kernels over the children's current pieces (rules M1 to M9); bwams_bam_header_merge, the header alone.
+#include <chrono>
+#include <cstring>
 #include <memory>
+#include <thread>
 
 #include "rec_consumer.h"
 #include "../host/bam_query.h"
 
 using namespace bwams;
+
+struct bwams_bam_file;
+
+// The merge part of a handle that bwams_bam_file_open_merge made (rules M1 to M9): the children it owns, a cursor per child into the
+// child's current piece, and what a round's kernels need.  The merged piece itself goes to the handle's own recs / roff / coords.
+struct BamMerge {
+    std::vector<bwams_bam_file *> kids;
+    std::vector<std::string> names;                  // "file k (path): "
+    int64_t child_bytes = 0;
+    std::vector<int64_t> cur, seen;                  // of child j: its window starts at record cur[j] of its piece; records of the pieces before
+    std::vector<int32_t> parity;
+    HostBuf<BmChild> h_kids;
+    HostBuf<BmPlan> h_plan;
+    DevBuf<BmChild> d_kids;
+    DevBuf<BmPlan> d_plan;
+    DevBuf<uint64_t> last_key;                       // two words per child (bm_check_kernel)
+    DevBuf<const uint8_t *> src;                     // of each record of the piece
+    DevBuf<int64_t> size;
+    DevBuf<> tmp;                                    // the scan's
+    hipEvent_t ev[7] = {};                           // check, frontier | rank, scan, gather: the host reads the plan in between
+    bwams_bam_merge_info_t info{};
+    ~BamMerge();
+};
 
 struct bwams_bam_file {
     int device = 0, cu_count = 0;
@@ -26,7 +54,9 @@ struct bwams_bam_file {
     int64_t n_rec = 0, n_bytes = 0;
     enum State { kNoQuery, kQueried, kPiece, kLast, kConsumed } state = kNoQuery;
     bwams_bam_file_info_t info{};
+    std::unique_ptr<BamMerge> merge;                 // null: a plain handle
     ~bwams_bam_file() {
+        merge.reset();                               // the children first: each makes its own device current
         (void)hipSetDevice(device);
         bam_query_scratch_free(scratch);
         for (hipEvent_t e : ev)
@@ -51,6 +81,214 @@ const char *no_piece_text(const bwams_bam_file *f) {
 int fail(const char *who, int rc, const std::string &why) {
     set_last_error(std::string(who) + ": " + why);
     return rc;
+}
+
+// ---- several files merged (rules M1 to M9) ----
+
+constexpr int kRefillThreads = 16;       // children advanced at a time
+
+// the text a child's call left, without the entry point's name in front of it
+std::string child_text(const char *entry) {
+    std::string t = bwams_last_error();
+    const std::string head = std::string(entry) + ": ";
+    return t.compare(0, head.size(), head) == 0 ? t.substr(head.size()) : t;
+}
+
+// a HIP call's result as a return code, with the call's name and HIP's text as the last error (what BWAMS_HIP does, without its return)
+int hip_rc(hipError_t e, const char *what) {
+    if (e == hipSuccess) return BWAMS_OK;
+    set_last_error(std::string(what) + " -> " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? BWAMS_ERR_NOMEM : BWAMS_ERR_DEVICE;
+}
+
+bool kid_open(const bwams_bam_file *k) { return k->state == bwams_bam_file::kQueried || k->state == bwams_bam_file::kPiece; }
+int64_t kid_window(const BamMerge *m, size_t j) { return m->kids[j]->has_piece() ? m->kids[j]->n_rec - m->cur[j] : 0; }
+
+int merge_query(bwams_bam_file *f, const bwams_pileup_region_t *regions, int32_t n_regions) {
+    const char *who = "bwams_bam_file_query";
+    BamMerge *m = f->merge.get();
+    if (n_regions > 0)
+        for (size_t k = 0; k < m->kids.size(); ++k)
+            if (!m->kids[k]->host.has_index) return fail(who, BWAMS_ERR_ARG, m->names[k] + "a query with regions needs an index, and this file has none");
+    // Child 0 checks the regions for all (M2: one reference list), so a refusal by it leaves the last query's state as the plain
+    // handle's does.  From the first child that took the query on, the last query is gone: whatever fails then leaves no query.
+    auto no_query = [&](int rc) {
+        f->n_rec = f->n_bytes = 0;
+        f->state = bwams_bam_file::kNoQuery;
+        return rc;
+    };
+    for (size_t k = 0; k < m->kids.size(); ++k)
+        if (int rc = bwams_bam_file_query(m->kids[k], regions, n_regions)) {
+            fail(who, rc, m->names[k] + child_text(who));
+            return k ? no_query(rc) : rc;
+        }
+    if (int rc = hip_rc(hipSetDevice(f->device), "hipSetDevice")) return no_query(rc);
+    if (int rc = hip_rc(hipStreamSynchronize(f->stream), "hipStreamSynchronize")) return no_query(rc);
+    if (int rc = hip_rc(hipMemsetAsync(m->last_key.p, 0, m->last_key.cap, f->stream), "hipMemsetAsync")) return no_query(rc);
+    if (int rc = hip_rc(hipStreamSynchronize(f->stream), "hipStreamSynchronize")) return no_query(rc);
+    std::fill(m->cur.begin(), m->cur.end(), 0);
+    std::fill(m->seen.begin(), m->seen.end(), 0);
+    std::fill(m->parity.begin(), m->parity.end(), 0);
+    const bwams_bam_merge_info_t was = m->info;
+    m->info = bwams_bam_merge_info_t{};
+    m->info.n_files = was.n_files; m->info.child_bytes = was.child_bytes; m->info.pg_dropped = was.pg_dropped;
+    f->n_rec = f->n_bytes = 0;
+    f->state = bwams_bam_file::kQueried;
+    return BWAMS_OK;
+}
+
+// Rule M7's advance: every open child whose window is empty gets its next piece, again while pieces come back empty.  A thread per
+// child, kRefillThreads at a time; each child has its own stream, inflater and scratch, and what a child returns depends on that
+// child alone, so the threads decide nothing (rule M8).  refilled[j]: child j has a new piece.
+int merge_refill(bwams_bam_file *f, std::vector<char> *refilled, std::string *why) {
+    BamMerge *m = f->merge.get();
+    const size_t K = m->kids.size();
+    std::vector<size_t> need;
+    for (size_t j = 0; j < K; ++j)
+        if (kid_open(m->kids[j]) && kid_window(m, j) == 0) need.push_back(j);
+    if (need.empty()) return BWAMS_OK;
+    std::vector<int> rc(K, BWAMS_OK);
+    std::vector<int64_t> calls(K, 0);
+    std::vector<std::string> text(K);
+    auto advance = [&](size_t j) {
+        bwams_bam_file *k = m->kids[j];
+        do {
+            if (k->has_piece()) m->seen[j] += k->n_rec;
+            rc[j] = bwams_bam_file_next(k, nullptr, nullptr, nullptr);
+            if (rc[j]) { text[j] = child_text("bwams_bam_file_next"); return; }
+            calls[j] += 1;
+        } while (k->n_rec == 0 && kid_open(k));
+        m->cur[j] = 0;
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t at = 0; at < need.size(); at += kRefillThreads) {
+        const size_t end = std::min(need.size(), at + (size_t)kRefillThreads);
+        if (end - at == 1) { advance(need[at]); continue; }
+        std::vector<std::thread> pool;
+        for (size_t i = at; i < end; ++i) pool.emplace_back(advance, need[i]);
+        for (std::thread &t : pool) t.join();
+    }
+    m->info.ms_refill += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (size_t j : need) {
+        m->info.refills += calls[j];
+        (*refilled)[j] = 1;
+    }
+    for (size_t j : need)
+        if (rc[j]) { *why = m->names[j] + text[j]; return rc[j]; }
+    return BWAMS_OK;
+}
+
+// One round (rule M7): the next piece of the merged stream into f->recs / roff / coords.  *last: it is the query's last.
+int merge_round(bwams_bam_file *f, const char *who, bool *last) {
+    BamMerge *m = f->merge.get();
+    const size_t K = m->kids.size();
+    hipStream_t st = f->stream;
+    auto broken = [&](int rc, const std::string &why) {
+        f->state = bwams_bam_file::kConsumed;
+        return why.empty() ? rc : fail(who, rc, why);
+    };
+    std::vector<char> refilled(K, 0);
+    std::string why;
+    if (int rc = merge_refill(f, &refilled, &why)) return broken(rc, why);
+    auto failed = [&](int rc) { f->state = bwams_bam_file::kConsumed; return rc; };      // the text is set already
+#define BM_HIP(call) do { if (int rc_ = hip_rc(call, #call)) return failed(rc_); } while (0)
+    BM_HIP(hipSetDevice(f->device));                         // a child's call on this thread may have left another device current
+    bool any_open = false;
+    int64_t max_new = 0, room = 0;
+    for (size_t j = 0; j < K; ++j) {
+        bwams_bam_file *k = m->kids[j];
+        const bool fresh_piece = refilled[j] && k->n_rec > 0;
+        if (fresh_piece) m->parity[j] ^= 1;
+        BmChild &c = m->h_kids.p[j];
+        c = BmChild{k->coords.p, k->recs.p, k->roff.p, m->cur[j], k->has_piece() ? k->n_rec : 0, m->seen[j], kid_open(k) ? 1 : 0,
+                    fresh_piece ? 1 : 0, m->parity[j], 0};
+        any_open |= kid_open(k);
+        if (fresh_piece) max_new = std::max(max_new, k->n_rec);
+        if (k->has_piece()) room += k->n_bytes;
+    }
+    BM_HIP(hipMemcpyAsync(m->d_kids.p, m->h_kids.p, K * sizeof(BmChild), hipMemcpyHostToDevice, st));
+    BM_HIP(hipMemsetAsync(m->d_plan.p, 0xFF, sizeof(BmPlan), st));
+    BM_HIP(hipEventRecord(m->ev[0], st));
+    launch_bm_check(m->d_kids.p, (int)K, max_new, m->last_key.p, m->d_plan.p, f->cu_count, st);
+    BM_HIP(hipEventRecord(m->ev[1], st));
+    launch_bm_frontier(m->d_kids.p, (int)K, m->d_plan.p, st);
+    BM_HIP(hipEventRecord(m->ev[2], st));
+    BM_HIP(hipMemcpyAsync(m->h_plan.p, m->d_plan.p, sizeof(BmPlan), hipMemcpyDeviceToHost, st));
+    BM_HIP(hipStreamSynchronize(st));
+    BM_HIP(hipGetLastError());
+    const BmPlan &P = *m->h_plan.p;
+    for (size_t j = 0; j < K; ++j)
+        if (P.bad[j] != ~0ULL)                               // rule M5
+            return broken(BWAMS_ERR_IO, m->names[j] + "record " + std::to_string(P.bad[j]) + ": key below its predecessor's");
+    const int64_t total = P.total;
+    if (total < 0 || total >= ((int64_t)1 << 32)) return broken(BWAMS_ERR_UNSUPPORTED, "a merged piece of 2^32 records or more");
+    const size_t n1 = (size_t)total + 1;
+    if (int rc = fresh(m->src, n1, who, "a merged piece's source addresses")) return failed(rc);
+    if (int rc = fresh(m->size, n1, who, "a merged piece's record sizes")) return failed(rc);
+    if (int rc = fresh(f->roff, n1, who, "a merged piece's offsets")) return failed(rc);
+    if (int rc = fresh(f->coords, n1, who, "a merged piece's coords")) return failed(rc);
+    if (int rc = fresh(f->recs, (size_t)room + 16, who, "a merged piece's records")) return failed(rc);
+    int64_t n_bytes = 0;
+    if (total > 0) {
+        BM_HIP(hipEventRecord(m->ev[3], st));                // behind the plan's round trip and the allocations: the rank alone
+        launch_bm_rank(m->d_kids.p, (int)K, m->d_plan.p, total, m->src.p, m->size.p, f->coords.p, st);
+        BM_HIP(hipEventRecord(m->ev[4], st));
+        if (int rc = with_tmp(m->tmp, st, "bwams_bam_file_next: exclusive_scan", [&](void *tmp, size_t &tb) {
+                return bm_scan(tmp, tb, m->size.p, f->roff.p, (int64_t)n1, st);
+            })) return failed(rc);
+        BM_HIP(hipEventRecord(m->ev[5], st));
+        launch_bm_gather(m->src.p, f->roff.p, total, f->recs.p, f->cu_count, st);
+        BM_HIP(hipEventRecord(m->ev[6], st));
+        BM_HIP(hipMemcpyAsync(&n_bytes, f->roff.p + total, 8, hipMemcpyDeviceToHost, st));
+    } else {
+        BM_HIP(hipMemsetAsync(f->roff.p, 0, 8, st));
+    }
+    BM_HIP(hipStreamSynchronize(st));
+    BM_HIP(hipGetLastError());
+#undef BM_HIP
+    if (n_bytes < 0 || n_bytes > room) return broken(BWAMS_ERR_DEVICE, "a merged piece's size does not add up to its children's");
+    float t = 0;
+    bwams_bam_merge_info_t &I = m->info;
+    if (hipEventElapsedTime(&t, m->ev[0], m->ev[1]) == hipSuccess) I.ms_check += t;
+    if (hipEventElapsedTime(&t, m->ev[1], m->ev[2]) == hipSuccess) I.ms_frontier += t;
+    if (total > 0) {
+        if (hipEventElapsedTime(&t, m->ev[3], m->ev[4]) == hipSuccess) I.ms_rank += t;
+        if (hipEventElapsedTime(&t, m->ev[4], m->ev[5]) == hipSuccess) I.ms_scan += t;
+        if (hipEventElapsedTime(&t, m->ev[5], m->ev[6]) == hipSuccess) I.ms_gather += t;
+    }
+    for (size_t j = 0; j < K; ++j) {
+        m->cur[j] += P.count[j];
+        I.max_window_left = std::max(I.max_window_left, kid_window(m, j));
+    }
+    I.rounds += 1; I.records += total; I.bytes += n_bytes;
+    I.max_piece_records = std::max(I.max_piece_records, total);
+    I.max_piece_bytes = std::max(I.max_piece_bytes, n_bytes);
+    f->n_rec = total;
+    f->n_bytes = n_bytes;
+    *last = !any_open;
+    return BWAMS_OK;
+}
+
+}  // namespace
+
+BamMerge::~BamMerge() {
+    for (bwams_bam_file *k : kids) delete k;
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+}
+
+namespace {
+
+void sum_info(const BamMerge *m, bwams_bam_file_info_t *out) {
+    *out = bwams_bam_file_info_t{};
+    for (const bwams_bam_file *k : m->kids) {
+        const bwams_bam_file_info_t &i = k->info;
+        out->intervals += i.intervals; out->members += i.members; out->compressed_bytes += i.compressed_bytes;
+        out->inflated_bytes += i.inflated_bytes; out->candidates += i.candidates; out->records_seen += i.records_seen;
+        out->records_kept += i.records_kept; out->pieces += i.pieces; out->carried += i.carried;
+        out->ms_read += i.ms_read; out->ms_inflate += i.ms_inflate; out->ms_discover += i.ms_discover;
+        out->ms_select += i.ms_select; out->ms_gather += i.ms_gather;
+    }
 }
 
 }  // namespace
@@ -88,6 +326,84 @@ int bwams_bam_file_open(const char *path, const char *bai_path, int device, int6
     return BWAMS_OK;
 }
 
+int bwams_bam_file_open_merge(const char *const *paths, const char *const *bai_paths, int32_t n_files, int device, int64_t piece_bytes,
+                              const bwams_bam_merge_opt_t *opt, bwams_bam_file_t **out) {
+    const char *who = "bwams_bam_file_open_merge";
+    if (!paths || !out || n_files < 1 || n_files > kBmMaxFiles || piece_bytes < 0)
+        return fail(who, BWAMS_ERR_ARG, "paths, out, n_files in [1, 64] and piece_bytes of 0 or more are required");
+    *out = nullptr;
+    for (int32_t k = 0; k < n_files; ++k)
+        if (!paths[k]) return fail(who, BWAMS_ERR_ARG, "file " + std::to_string(k) + " has no path");
+    if (opt && (opt->reserved != 0 || opt->child_bytes < 0)) return fail(who, BWAMS_ERR_ARG, "opt->reserved must be 0 and opt->child_bytes 0 or more");
+    const int64_t child_bytes = opt && opt->child_bytes ? opt->child_bytes : ((piece_bytes ? piece_bytes : kDefaultPiece) / n_files) & ~(int64_t)0xFFFF;
+    if (child_bytes < 65536)
+        return fail(who, BWAMS_ERR_ARG, "a child piece of " + std::to_string(child_bytes) + " bytes is below 65536: " + std::to_string(n_files) +
+                                            " files need piece_bytes of at least " + std::to_string((int64_t)65536 * n_files));
+    if (int rc = check_device(device)) return rc;
+    BWAMS_HIP(hipSetDevice(device));
+    std::unique_ptr<bwams_bam_file> f(new bwams_bam_file());
+    f->device = device;
+    BWAMS_HIP(hipDeviceGetAttribute(&f->cu_count, hipDeviceAttributeMultiprocessorCount, device));
+    BWAMS_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    for (hipEvent_t &e : f->ev) BWAMS_HIP(hipEventCreate(&e));
+    f->merge.reset(new BamMerge());
+    BamMerge *m = f->merge.get();
+    for (hipEvent_t &e : m->ev) BWAMS_HIP(hipEventCreate(&e));
+    m->child_bytes = child_bytes;
+    for (int32_t k = 0; k < n_files; ++k) {
+        const std::string name = "file " + std::to_string(k) + " (" + paths[k] + "): ";
+        bwams_bam_file_t *kid = nullptr;
+        if (int rc = bwams_bam_file_open(paths[k], bai_paths ? bai_paths[k] : nullptr, device, child_bytes, &kid))
+            return fail(who, rc, name + child_text("bwams_bam_file_open"));
+        m->kids.push_back(kid);
+        m->names.push_back(name);
+    }
+    std::vector<const void *> blocks;
+    std::vector<int64_t> sizes;
+    for (const bwams_bam_file *k : m->kids) {
+        blocks.push_back(k->host.header_block.data());
+        sizes.push_back((int64_t)k->host.header_block.size());
+    }
+    std::string block, err;
+    if (int rc = bam_header_merge(blocks.data(), sizes.data(), n_files, &block, &m->info.pg_dropped, &err)) return fail(who, rc, err);
+    int32_t l_text = 0;
+    memcpy(&l_text, block.data() + 4, 4);
+    f->host.path = "the merge of " + std::to_string(n_files) + " files";
+    f->host.header_block.assign(block.begin(), block.end());
+    f->host.hdr.text.assign(block, 8, (size_t)l_text);
+    f->host.hdr.n_ref = m->kids[0]->host.hdr.n_ref;
+    f->host.hdr.l_ref = m->kids[0]->host.hdr.l_ref;
+    m->info.n_files = n_files;
+    m->info.child_bytes = child_bytes;
+    m->cur.assign((size_t)n_files, 0); m->seen.assign((size_t)n_files, 0); m->parity.assign((size_t)n_files, 0);
+    BWAMS_HIP(hipSetDevice(device));
+    BWAMS_HIP(m->h_kids.alloc(kBmMaxFiles * sizeof(BmChild))); BWAMS_HIP(m->h_plan.alloc(sizeof(BmPlan)));
+    BWAMS_HIP(m->d_kids.alloc(kBmMaxFiles * sizeof(BmChild))); BWAMS_HIP(m->d_plan.alloc(sizeof(BmPlan)));
+    BWAMS_HIP(m->last_key.alloc(2 * kBmMaxFiles * sizeof(uint64_t)));
+    BWAMS_HIP(f->roff.ensure_n(1)); BWAMS_HIP(f->recs.ensure_n(16));
+    *out = f.release();
+    return BWAMS_OK;
+}
+
+int bwams_bam_merge_info(const bwams_bam_file_t *f, bwams_bam_merge_info_t *info) {
+    if (!f || !info) return BWAMS_ERR_ARG;
+    if (!f->merge) return fail("bwams_bam_merge_info", BWAMS_ERR_ARG, "the handle is a plain one: bwams_bam_file_open_merge makes a merged one");
+    *info = f->merge->info;
+    return BWAMS_OK;
+}
+
+int bwams_bam_header_merge(const void *const *blocks, const int64_t *n_block, int32_t n_files, void *out, int64_t cap, int64_t *n_out,
+                           int32_t *pg_dropped) {
+    const char *who = "bwams_bam_header_merge";
+    std::string block, err;
+    if (int rc = bam_header_merge(blocks, n_block, n_files, &block, pg_dropped, &err)) return fail(who, rc, err);
+    if (n_out) *n_out = (int64_t)block.size();
+    if (cap < (int64_t)block.size() || !out)
+        return fail(who, BWAMS_ERR_CAPACITY, std::to_string(block.size()) + " bytes of header do not fit a capacity of " + std::to_string(cap));
+    memcpy(out, block.data(), block.size());
+    return BWAMS_OK;
+}
+
 int bwams_bam_file_close(bwams_bam_file_t *f) {
     delete f;
     return BWAMS_OK;
@@ -119,6 +435,7 @@ int bwams_bam_file_refs(const bwams_bam_file_t *f, int32_t *l_ref, int32_t cap) 
 int bwams_bam_file_query(bwams_bam_file_t *f, const bwams_pileup_region_t *regions, int32_t n_regions) {
     const char *who = "bwams_bam_file_query";
     if (!f) return fail(who, BWAMS_ERR_ARG, "a handle is required");
+    if (f->merge) return merge_query(f, regions, n_regions);
     std::vector<bwams_pileup_region_t> merged;
     std::string err;
     if (int rc = f->host.query(regions, n_regions, &merged, &err)) return fail(who, rc, err);      // a refused query leaves the last one's state
@@ -154,6 +471,15 @@ int bwams_bam_file_next(bwams_bam_file_t *f, int64_t *n_records, int64_t *n_byte
         return fail(who, rc, why);
     };
     f->n_rec = f->n_bytes = 0;
+    if (f->merge) {                                          // a round over the children's windows (rule M7)
+        bool last = false;
+        if (int rc = merge_round(f, who, &last)) return rc;
+        f->state = last ? bwams_bam_file::kLast : bwams_bam_file::kPiece;
+        if (n_records) *n_records = f->n_rec;
+        if (n_bytes) *n_bytes = f->n_bytes;
+        if (done) *done = last ? 1 : 0;
+        return BWAMS_OK;
+    }
     BamQueryResult R{};
     bool last = true;
     if (f->host.exhausted()) {                               // a plan without intervals: one empty piece
@@ -221,7 +547,8 @@ int bwams_bam_file_fetch(bwams_bam_file_t *f, void *bam, int64_t cap, bwams_bam_
 
 int bwams_bam_file_info(const bwams_bam_file_t *f, bwams_bam_file_info_t *info) {
     if (!f || !info) return BWAMS_ERR_ARG;
-    *info = f->info;
+    if (f->merge) sum_info(f->merge.get(), info);
+    else *info = f->info;
     return BWAMS_OK;
 }
 

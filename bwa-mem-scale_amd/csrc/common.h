@@ -258,6 +258,35 @@ int bam_query_piece(BamQueryScratch *s, const uint8_t *d, int64_t n, int64_t sta
                     int32_t n_regions, DevBuf<uint8_t> &recs, DevBuf<int64_t> &roff, DevBuf<bwams_bam_coord_t> &coords, hipEvent_t ev[4],
                     int cu_count, hipStream_t st, BamQueryResult *out);
 
+// bam_merge.hip: one round of several BAM files merged (rules M4 to M8 in include/bwams.h above bwams_bam_file_open_merge).  A child
+// is described by where its handle left its current piece; the plan is what the frontier kernel decides and the host reads once a
+// round.  check: plan->bad[j] = min(it, the ordinal of a record of child j's new piece whose key is below its predecessor's), and
+// last_key[2j + parity] = the piece's last key (two words per child; all zero when a query begins).  frontier: count, base, total.
+// rank: for each of the `total` emitted records, at its place in the piece, its source address, size and coord; size[total] = 0.
+// bm_scan: the sizes' exclusive scan (total + 1 entries).  gather: the records into dst, which holds 16 bytes of slack as every source does.
+constexpr int kBmMaxFiles = 64;          // a lane of the frontier kernel's one wave per file
+struct BmChild {
+    const bwams_bam_coord_t *coords;     // of its current piece, as are recs and roff
+    const uint8_t *recs;
+    const int64_t *roff;
+    int64_t cur, n;                      // the window: records [cur, n)
+    int64_t seen;                        // the ordinal of the piece's record 0 among the child's records of this query
+    int32_t open, refilled;              // pieces to come; the piece is new in this round
+    int32_t parity, pad_;                // the word of last_key that this piece writes
+};
+struct BmPlan {
+    int64_t count[kBmMaxFiles], base[kBmMaxFiles], total;
+    uint64_t frontier;
+    int32_t i_star, any_open;
+    unsigned long long bad[kBmMaxFiles];
+};
+void launch_bm_check(const BmChild *kids, int n_kids, int64_t max_n, uint64_t *last_key, BmPlan *plan, int cu_count, hipStream_t st);
+void launch_bm_frontier(const BmChild *kids, int n_kids, BmPlan *plan, hipStream_t st);
+void launch_bm_rank(const BmChild *kids, int n_kids, const BmPlan *plan, int64_t total, const uint8_t **src, int64_t *size,
+                    bwams_bam_coord_t *coords, hipStream_t st);
+hipError_t bm_scan(void *tmp, size_t &tmp_bytes, const int64_t *size, int64_t *roff, int64_t n1, hipStream_t st);
+void launch_bm_gather(const uint8_t *const *src, const int64_t *roff, int64_t n, uint8_t *dst, int cu_count, hipStream_t st);
+
 // markdup.hip: duplicate marking (rules in include/bwams.h above bwams_bam_templates).  md_templates groups n_rec records (at
 // bam + rec_off[r], 16 bytes of slack past the last) into templates: m.n_t templates, m.rtmpl[r] each record's, and the m.n_e ends
 // of the templates that have one, in template order, at m.ends; BWAMS_ERR_UNSUPPORTED (last error: the first record concerned) for

@@ -81,4 +81,11 @@ struct BamFileHost {
     int next_piece(void *dev_out, BamPiece *p, std::string *err);
 };
 
+// host/bam_merge_header.cpp: the header block of n_files files merged (include/bwams.h, above bwams_bam_file_open_merge, rules M2 and
+// M3) from their header blocks (magic to the last reference's l_ref; bytes behind that are not looked at).  *pg_dropped (may be
+// null): the @PG lines M3 dropped.  BWAMS_ERR_ARG for a block that is cut off or has the wrong magic, BWAMS_ERR_UNSUPPORTED for
+// reference lists that differ and for an @RG ID taken with other bytes; the text in *err.
+int bam_header_merge(const void *const *blocks, const int64_t *n_block, int32_t n_files, std::string *out, int32_t *pg_dropped,
+                     std::string *err);
+
 }  // namespace bwams

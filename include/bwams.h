@@ -1793,7 +1793,11 @@ int bwams_recal_apply_info(const bwams_recal_apply_t *a, bwams_recal_apply_info_
  * and measurement hook (bwams_bam_file_info_t, include/bwams_types.h).
  * A sixth consumer of the pieces is the join handle below: bwams_dupjoin_add_file and bwams_dupjoin_apply_file; a seventh the
  * collate handle behind it: bwams_collate_add_file.
- * Out of scope: CRAM, CSI and tabix indexes, unsorted input beyond whole-file mode, several files merged, writing. */
+ * An eighth is the SAM view (bwams_samview_add_file).  Several files as one stream: bwams_bam_file_open_merge below, whose handle
+ * every call here takes unchanged.
+ * Out of scope: CRAM, CSI and tabix indexes, unsorted input beyond whole-file mode, writing; of the merge: renaming @RG IDs that
+ * collide, files whose reference lists differ, prefetching a child's next piece while the current round merges, one inflater call
+ * over members of several files, a writer that takes an ordered stream directly (bwams_sorter_put merges its runs once more). */
 int bwams_bam_file_open(const char *path, const char *bai_path, int device, int64_t piece_bytes, bwams_bam_file_t **out);
 int bwams_bam_file_header(const bwams_bam_file_t *f, const char **text, int64_t *n_text, int32_t *n_ref);
 int bwams_bam_file_refs(const bwams_bam_file_t *f, int32_t *l_ref, int32_t cap);
@@ -1809,6 +1813,65 @@ int bwams_recal_add_file(bwams_recal_t *r, bwams_bam_file_t *f, int64_t *n_count
 int bwams_recal_apply_file(bwams_recal_apply_t *a, bwams_bam_file_t *f, int64_t *n_rewritten);
 int bwams_bai_plan(const void *bai, int64_t n_bai, const bwams_pileup_region_t *regions, int32_t n_regions, uint64_t *chunk_beg,
                    uint64_t *chunk_end, int64_t cap, int64_t *n_chunks);
+
+/* Several coordinate-sorted BAM files (a sample's lanes, flow cells, the shards bwams_writer_* and bwams_multi_* write) merged as one
+ * record stream, what `samtools merge` gives: bwams_bam_file_open_merge returns a bwams_bam_file_t that is the merge of n_files files.
+ * Each child file is inflated and its records are found in HBM as above; HIP kernels (csrc/bam_merge.hip) merge the children's
+ * pieces into pieces in coordinate order, which _query / _next / _fetch, the eight _add_file calls, bwams_recal_apply_file and
+ * bwams_dupjoin_apply_file take as they take one file's.  _header, _header_block and _refs give the merged header, _info the sums
+ * over the children, _close closes them.  bwams/merge.py restates the rules (merge_records, merge_header, rounds).
+ *  M1. Inputs.  n_files in [1, 64] (a lane of one wave per file), every path given; BWAMS_ERR_ARG otherwise.  bai_paths may be
+ *      NULL and so may each entry: bwams_bam_file_open's rule per file.  The handle opens and owns its children on `device`, each
+ *      with piece size child_bytes: opt->child_bytes, or with 0 / opt NULL piece_bytes / n_files rounded down to a multiple of 65536
+ *      (piece_bytes 0: 128 MiB).  child_bytes below 65536: BWAMS_ERR_ARG, the text giving the smallest piece_bytes that would do.
+ *      opt->reserved != 0: BWAMS_ERR_ARG.  A child that cannot be opened: that child's code, "file k (path): " before its text.
+ *  M2. References.  Every file must have file 0's n_ref and per reference the same name bytes and length: BWAMS_ERR_UNSUPPORTED at
+ *      open otherwise, naming the file, the reference's ordinal and what differs.  No refID is ever rewritten.
+ *  M3. Header text (bwams_bam_header_merge, host only, host/bam_merge_header.cpp).  A text's lines end at '\n'; NUL padding behind
+ *      the text and empty lines are no lines; every line is written with its '\n'.  The @HD line and all @SQ lines come from file 0
+ *      as they are (those of the other files are not looked at: M2 compares the binary lists).  Then, for file 0, 1, ...: every other
+ *      line in file order that is not byte-equal to a line already taken.  An @RG line whose ID equals an ID already taken, with
+ *      other bytes: BWAMS_ERR_UNSUPPORTED naming both files and the ID (samtools merge renames the ID and rewrites RG:Z; silently
+ *      changing library membership is worse than refusing).  An @PG line in that situation is dropped and counted in *pg_dropped
+ *      (two lanes through one pipeline always collide here, and the ID that records may name still exists).  The block written is a
+ *      BAM header block as bwams_bam_file_header_block gives it: magic, l_text, text, n_ref, file 0's references.  *n_out: its size,
+ *      BWAMS_ERR_CAPACITY when cap is smaller (bwams_bai_plan's convention).  A block that is cut off or has another magic:
+ *      BWAMS_ERR_ARG, naming the file.  Bytes behind a block's last reference are not looked at.
+ *  M4. Order.  The merged stream of the whole file holds every record of every file once, that of a query every kept record once,
+ *      ordered by (bwams_bam_coord_t.key, file index, ordinal within the file), each record byte for byte and with its coord: what
+ *      bwams_sorter_close gives when file k is put as the run with seq = k.
+ *  M5. Sorted input is checked, not assumed.  A file's kept records must have non-decreasing keys, also across its pieces.  The
+ *      first violation ends the query with BWAMS_ERR_IO from _next: "file k (path): record r: key below its predecessor's", r the
+ *      ordinal among that file's kept records of this query (when several files break the rule in one round: the lowest file).
+ *  M6. Query.  _query passes the same regions to every child.  n_regions > 0 with a child that has no index: BWAMS_ERR_ARG naming
+ *      the file.  Bad regions are refused by file 0 for all and leave the last query's state, as on one file; a query that a
+ *      later file refuses (an I/O error) comes back with the file prefix and leaves the handle without a query.  A child's error
+ *      from _next comes back with the file prefix and ends the query.  Rule 6's refusals by state hold
+ *      with the same texts.
+ *  M7. Rounds, defined so that the output cannot depend on timing.  Each child has a WINDOW, the not yet emitted tail of its current
+ *      piece, and is OPEN while it has pieces to come.  Before a round every open child with an empty window is advanced, again
+ *      while its pieces come back empty.  L_j: the key of the last record in open child j's window; F = min L_j; i* the smallest j
+ *      with L_j = F.  Child j emits its window's records with key < F and, when j <= i*, those with key = F.  With no open child
+ *      every window is emitted whole, and that round's piece is the last.  The emitted records in M4's order are the handle's next
+ *      piece; it may be empty.  Why j <= i*: an open child j < i* has L_j > F, so all its records of key F are in its window, and
+ *      a closed child's are too; child i* empties its window in every round, so a run of equal keys longer than a piece (all
+ *      unplaced reads of a file share one key) makes progress.
+ *  M8. Pieces are a function of the input: their boundaries depend only on the files' bytes, the query and child_bytes, so two
+ *      queries give the same pieces (rule J8 of the join holds in pass 2).  A piece holds at most the sum of the children's current
+ *      pieces, each at most 2 x child_bytes (carry plus inflated); the output buffers grow on demand, and a failed allocation is
+ *      BWAMS_ERR_NOMEM with the size asked for and ends the query.  The children that need a piece in one round are advanced
+ *      concurrently, a host thread each and at most 16 at a time (each child has its own stream and inflater), which decides nothing.
+ *  M9. bwams_bam_merge_info (bwams_bam_merge_info_t, include/bwams_types.h): a test and measurement hook; on a plain handle
+ *      BWAMS_ERR_ARG.
+ * The kernels of a round, on the handle's stream, the children read in place: bm_check (M5, a lane per record of a new piece),
+ * bm_frontier (one wave, a lane per child: F, i*, each child's emit count by binary search, a wave prefix sum), bm_rank (a lane per
+ * emitted record: its place from K - 1 binary searches over the other children's keys), one rocPRIM scan of the sizes, bm_gather
+ * (kGroup lanes per record from K source buffers). */
+int bwams_bam_file_open_merge(const char *const *paths, const char *const *bai_paths, int32_t n_files, int device, int64_t piece_bytes,
+                              const bwams_bam_merge_opt_t *opt, bwams_bam_file_t **out);
+int bwams_bam_merge_info(const bwams_bam_file_t *f, bwams_bam_merge_info_t *info);
+int bwams_bam_header_merge(const void *const *blocks, const int64_t *n_block, int32_t n_files, void *out, int64_t cap, int64_t *n_out,
+                           int32_t *pg_dropped);
 /* ------------------------------ Duplicate marking, templates joined by name ---- */
 
 /* Duplicate marking of records that are NOT query-grouped (csrc/dup_join.hip): a coordinate-sorted BAM of another aligner, of an older
@@ -1867,8 +1930,9 @@ int bwams_bai_plan(const void *bai, int64_t n_bai, const bwams_pileup_region_t *
  * own, and frees all of it but 4 bytes per record (rec_tmpl) and 2 per template.  What does not fit is BWAMS_ERR_NOMEM with the size
  * asked for.  _info: a test and measurement hook (bwams_dupjoin_info_t, include/bwams_types.h).
  * Out of scope: batches (a batch's templates are adjacent: bwams_bam_markdup serves them); lifting bwams_sorter_put's refusal under
- * BWAMS_SORT_MARKDUP (the follow-up this handle makes possible); storing names to verify keys; the DT tag, REMOVE_DUPLICATES, UMIs;
- * several files merged. */
+ * BWAMS_SORT_MARKDUP (the follow-up this handle makes possible); storing names to verify keys; the DT tag, REMOVE_DUPLICATES, UMIs.
+ * Several files (the lanes of a library): both passes over a handle of bwams_bam_file_open_merge, whose pieces are the same in
+ * both (rule M8), so that J8 holds. */
 int bwams_dupjoin_open(int device, const bwams_dup_groups_t *groups, const bwams_dup_opt_t *opt, bwams_dupjoin_t **out);
 int bwams_dupjoin_reset(bwams_dupjoin_t *j);
 int bwams_dupjoin_close(bwams_dupjoin_t *j);
@@ -1936,7 +2000,7 @@ int bwams_bam_file_header_block(const bwams_bam_file_t *f, const void **block, i
  * and per add 49 bytes of scratch per record of the piece and 53 per entry sorted, pending ones included (85 for the piece's own
  * paired records), kept between adds, beside rocPRIM's own.
  * Out of scope: spilling the pool to host memory; a reader thread that collates (bwams_reader_open_bam stays as it is); name-sorted
- * output (`samtools sort -n`); keeping secondary and supplementary records; several files merged; a device hash table in place of
+ * output (`samtools sort -n`); keeping secondary and supplementary records; a device hash table in place of
  * the sort (the follow-up if a measurement points at the sort). */
 int bwams_collate_open(int device, const bwams_collate_opt_t *opt, bwams_collate_t **out);
 int bwams_collate_reset(bwams_collate_t *c);

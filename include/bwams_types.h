@@ -550,6 +550,25 @@ typedef struct bwams_bam_file_info {
     int32_t pad_;
 } bwams_bam_file_info_t;
 
+/* bwams_bam_file_open_merge's options (include/bwams.h, rule M1).  child_bytes: the piece size of every child, 0 = piece_bytes /
+ * n_files rounded down to a multiple of 65536; reserved must be 0.  Without options: child_bytes 0. */
+typedef struct bwams_bam_merge_opt {
+    int64_t child_bytes;
+    int32_t reserved, pad_;
+} bwams_bam_merge_opt_t;
+
+/* bwams_bam_merge_info (rule M9): n_files and child_bytes of the handle; since the last bwams_bam_file_query the rounds, the refills
+ * (successful bwams_bam_file_next calls on children), the records and bytes emitted, the largest piece in records and in bytes, and
+ * the most records any child's window held unemitted after a round; pg_dropped: the @PG lines rule M3 dropped at open.  The times
+ * are for measurement only (tools/bam_merge_rate.py): device time between events around the check, frontier, rank, scan and gather
+ * of all rounds (the host's read of the plan and the growth of the output buffers, between frontier and rank, are in none of them),
+ * and ms_refill by the host clock around the children's bwams_bam_file_next calls. */
+typedef struct bwams_bam_merge_info {
+    int64_t n_files, child_bytes, rounds, refills, records, bytes, max_piece_records, max_piece_bytes, max_window_left;
+    int32_t pg_dropped, pad_;
+    float   ms_check, ms_frontier, ms_rank, ms_scan, ms_gather, ms_refill;
+} bwams_bam_merge_info_t;
+
 /* Duplicate marking with templates joined by name (include/bwams.h, above bwams_dupjoin_open).  A join handle lives on one device. */
 typedef struct bwams_dupjoin bwams_dupjoin_t;
 
