@@ -34,6 +34,7 @@ void knobs_reload() {
     k.pair_drop_plan = getenv("BWAMS_PAIR_DROP_PLAN") != nullptr;
     k.trace_pair = env_int("BWAMS_TRACE_PAIR", 0);
     k.bsw_pk = env_int("BWAMS_BSW_PK", 1);
+    k.bsw_early = env_int("BWAMS_BSW_EARLY", -1);
     k.chain_batch = env_int("BWAMS_CHAIN_BATCH", 1);
     k.chain_count = env_int("BWAMS_CHAIN_COUNT", 0) == 1;
     k.depth_combine = env_int("BWAMS_DEPTH_COMBINE", 1);

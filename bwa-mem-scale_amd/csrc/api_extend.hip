@@ -161,8 +161,9 @@ static int run_side(bwams_batch *b, StageState *s, const ExtArgs &A, int right, 
     if (bsw_list_bytes(n) > b->sw.d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(st));   // the last launch may still read the lists
     BWAMS_HIP(b->sw.d_bsw_list.ensure(bsw_list_bytes(n), bsw_list_bytes(n + n / 4 + 1024)));
     const bool verbose_bsw = knobs().verbose != 0;
-    if (verbose_bsw) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg + 40, 0, 8 * sizeof(unsigned long long), st));
-    if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr.p, b->cu_count, st, b->sw.d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) {
+    const bool early = knobs().bsw_early != 0;          // a task stops once no later row can change its result (BWAMS_BSW_EARLY=0: every row)
+    if (verbose_bsw) BWAMS_HIP(hipMemsetAsync(b->d_ctr.p->dbg + 40, 0, 10 * sizeof(unsigned long long), st));
+    if (int lrc = launch_bsw(pairs, n, ref, qer, A.opt.w, prm, qmax, b->d_ctr.p, b->cu_count, st, b->sw.d_bsw_list.p, s->aux, s->fork, s->join, src, dir, early)) {
         set_last_error(lrc == -2 ? "banded SW: a query longer than ~18000 bases does not fit the LDS kernel" : "banded SW: stream fork/join failed");
         return lrc == -2 ? BWAMS_ERR_UNSUPPORTED : BWAMS_ERR_DEVICE;
     }
@@ -170,16 +171,16 @@ static int run_side(bwams_batch *b, StageState *s, const ExtArgs &A, int right, 
     BWAMS_HIP(hipMemcpyAsync(h_nretry, d_nretry, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     BWAMS_HIP(hipStreamSynchronize(st));
     if (verbose_bsw) {               // filled only by a build of bsw_extend.hip with -DBWAMS_BSWDBG
-        unsigned long long d[8];
+        unsigned long long d[10];
         BWAMS_HIP(hipMemcpy(d, b->d_ctr.p->dbg + 40, sizeof d, hipMemcpyDeviceToHost));
         if (d[6])
             fprintf(stderr, "[run_side] bsw_pk_kernel, %s, %lld tasks: %llu waves, Mticks of wave-time %.2f, in the refill branch %.2f (%.1f %%), in the pass %.2f; "
-                            "%llu refill events, %llu slots filled, %llu iterations\n",
-                    right ? "right" : "left", (long long)n, d[6], d[0] / 1e6, d[1] / 1e6, 100. * (double)d[1] / (double)d[0], d[2] / 1e6, d[3], d[4], d[5]);
+                            "%llu refill events, %llu slots filled, %llu iterations, %llu rows, %llu tasks ended early\n",
+                    right ? "right" : "left", (long long)n, d[6], d[0] / 1e6, d[1] / 1e6, 100. * (double)d[1] / (double)d[0], d[2] / 1e6, d[3], d[4], d[5], d[7], d[8]);
     }
     const unsigned long long nr = *h_nretry;
     if (nr) {
-        if (launch_bsw(s->ext.retry.p, (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr.p, b->cu_count, st, b->sw.d_bsw_list.p, s->aux, s->fork, s->join, src, dir)) return BWAMS_ERR_DEVICE;
+        if (launch_bsw(s->ext.retry.p, (int64_t)nr, ref, qer, A.opt.w << 1, prm, qmax, b->d_ctr.p, b->cu_count, st, b->sw.d_bsw_list.p, s->aux, s->fork, s->join, src, dir, early)) return BWAMS_ERR_DEVICE;
         launch_ext_post(A, right, s->ext.retry.p, (int64_t)nr, A.opt.w << 1, 1, nullptr, d_nretry, rp, st);
     }
     *n_retry_out += (int64_t)nr;

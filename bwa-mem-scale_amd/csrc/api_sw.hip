@@ -55,7 +55,8 @@ int bwams_bsw_run(bwams_batch_t *b, int32_t w, const bwams_sw_opt_t *o) {
     if (list_bytes > b->sw.d_bsw_list.cap) BWAMS_HIP(hipStreamSynchronize(b->stream));     // the last launch may still read the lists
     BWAMS_HIP(b->sw.d_bsw_list.ensure(list_bytes, bsw_list_bytes(b->sw.n_pairs + b->sw.n_pairs / 4 + 1024)));
     BWAMS_HIP(hipEventRecord(b->ev[b->kEvBswStart], b->stream));
-    if (launch_bsw(b->sw.d_pairs.p, b->sw.n_pairs, b->sw.d_ref.p, b->sw.d_qer.p, w, prm, b->sw.max_qlen, b->d_ctr.p, b->cu_count, b->stream, b->sw.d_bsw_list.p)) {
+    if (launch_bsw(b->sw.d_pairs.p, b->sw.n_pairs, b->sw.d_ref.p, b->sw.d_qer.p, w, prm, b->sw.max_qlen, b->d_ctr.p, b->cu_count, b->stream, b->sw.d_bsw_list.p,
+                   nullptr, nullptr, nullptr, nullptr, 1, knobs().bsw_early == 1)) {     // the early exit only on request: bsw_cells is the full walk's otherwise
         set_last_error("bwams_bsw_run: a query longer than ~18000 bases does not fit the LDS kernel");
         return BWAMS_ERR_UNSUPPORTED;
     }

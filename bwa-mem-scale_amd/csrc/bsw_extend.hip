@@ -596,6 +596,7 @@ __device__ __forceinline__ uint32_t sub(uint32_t a, uint32_t b) { uint32_t d; as
 __device__ __forceinline__ uint32_t max(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_max_i16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 __device__ __forceinline__ uint32_t max0(uint32_t a) { uint32_t d; asm("v_pk_max_i16 %0, %1, 0" : "=v"(d) : "v"(a)); return d; }
 __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+__device__ __forceinline__ uint32_t mad(uint32_t a, uint32_t b, uint32_t c) { uint32_t d; asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 // The second operand WAVE-UNIFORM, read from a scalar register (a packed instruction takes one): a constant of the launch then costs
 // no vector register and no copy into one.  Only for values that are uniform by construction (kernel arguments and what is made of them)
 __device__ __forceinline__ uint32_t adds(uint32_t a, uint32_t s) { uint32_t d; asm("v_pk_add_u16 %0, %1, %2" : "=v"(d) : "v"(a), "s"(s)); return d; }
@@ -621,6 +622,10 @@ constexpr int kPkNeg = -16384;
 #ifndef BWAMS_PK_WAVES
 #define BWAMS_PK_WAVES 2
 #endif
+#ifndef BWAMS_BSW_EARLY_FORM
+#define BWAMS_BSW_EARLY_FORM 1
+#endif
+constexpr int kPkEarlyForm = BWAMS_BSW_EARLY_FORM;   // how often the early exit is tested: 1 after every row, 2 after every fourth (the A-B of profiles/bsw_early_exit.md)
 constexpr int kPkWaves = BWAMS_PK_WAVES;      // wavefronts per workgroup: LDS is handed out per workgroup, small ones pack a CU better
 
 __host__ __device__ __forceinline__ bool bsw_pk_eligible(const SwParams &prm) {
@@ -630,7 +635,19 @@ __host__ __device__ __forceinline__ bool bsw_pk_eligible(const SwParams &prm) {
            prm.o_del >= 0 && prm.o_del + prm.e_del < 8000;
 }
 
-__global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
+// EARLY: the early exit ("BSW kernel: the early exit").  After a completed row nothing a later row computes can exceed
+//     P = max over the stored columns of  H(i, j) + a (qlen - 1 - j)  and  E(i + 1, j) + a (qlen - 1 - j)  (non-zero cells only)
+//         and h1 + a qlen for the first-column value h1 of a row that starts at column 0
+// (a = max_sc: only a diagonal step gains, at most a, and uses up a column; a zero cell is no source; the band clip and the trim only
+// take cells away).  When P <= max and P < gscore the six outputs are final and the task ends there, exactly as a row maximum of 0
+// ends it.  H(i, j) is what the row stores as column j + 1's diagonal source, so H and E of a column share one remainder and the
+// potentials come from the pass's packed Hn and E2 registers.  The rule needs every stored cell to the right of the row's band to
+// be zero: zr is a column beyond which that holds (stale cells lie there only from row -1 or where the w clip cut the band), set
+// to the trim's last non-zero column after every row whose end reaches it.  It starts at qlen, not at row -1's last positive column:
+// the rule cannot fire before gscore is set, which takes a row with end == qlen >= either, and from that row on the two agree.
+// 0: none of it (the instance is the kernel without the rule); 1: tested after every row; 2: after the rows with (i & 3) == 3.
+template <int EARLY>
+__global__ __launch_bounds__(kPkWaves * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void bsw_pk_kernel(      // four waves per SIMD: 128 VGPRs
     bwams_seqpair_t *__restrict__ pairs, const int32_t *__restrict__ list, const unsigned long long *n_list_p,
     const uint8_t *__restrict__ ref, const uint8_t *__restrict__ qer, int w0, SwParams prm, DevCounters *ctr, unsigned long long *head,
     int cols, const int64_t *__restrict__ src, int dir) {
@@ -680,9 +697,11 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
     int base = 0, h1 = 0, key = -1, hlast = -1, c_max = kPkNeg, c_h = 0;
     int nz_last = 0, nz_first = 256;           // of the row so far: its last column with a non-zero stored cell, plus one (0: none); its first (256: none)
     uint2 tt = make_uint2(0u, 0u);
+    int zr = 0;                                // EARLY: every stored cell of a column beyond zr is zero
+    uint32_t pot = 0u;                         // EARLY: of the row so far, the largest potential of a stored cell (two 16-bit halves)
 #ifdef BWAMS_BSWDBG                 // wave-time of the refill branch and of the pass (printed by run_side under BWAMS_VERBOSE)
     const unsigned long long T0 = __builtin_amdgcn_s_memtime();
-    unsigned long long t_refill = 0, t_pass = 0, n_events = 0, n_filled = 0, n_iter = 0;
+    unsigned long long t_refill = 0, t_pass = 0, n_events = 0, n_filled = 0, n_iter = 0, n_rows = 0, n_rule = 0;
 #endif
 
     for (;;) {
@@ -733,6 +752,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                     start_row = true;
                     mx = h0; max_i = -1; max_j = -1; max_ie = -1; gscore = -1; max_off = 0;
                     beg = 0; end = qlen; i = 0;
+                    if constexpr (EARLY != 0) zr = qlen;
                     alive = tlen > 0;
                     if (!alive && g == 0) {
                         bwams_seqpair_t *o = &pairs[cur];
@@ -820,6 +840,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
             row = beg < end;
             key = -1; hlast = -1; nz_last = 0; nz_first = 256;
             c_max = kPkNeg; c_h = 0;
+            if constexpr (EARLY != 0) pot = 0u;
             base = beg & ~3;
             start_row = false;
         }
@@ -921,6 +942,22 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
             // key = H << 8 | (j + 1), one v_perm per column: the bytes {index, H low, H high, 0}.  A dead column contributes
             // (0 << 8 | j + 1) < 256: below every live key of a row whose maximum is positive, and the column of the maximum is
             // not read when the maximum is 0
+            if constexpr (EARLY != 0) {
+                // per pair the remainders a (qlen - 1 - j) of its two columns; X = max(H, E) of the live columns (E2 of a dead column is 0),
+                // X ? X + remainder : 0 as one multiply-add with min(X, 1); below 2^14, as every score of the class
+                const uint32_t A2X = (uint32_t)(2 * prm.max_sc) * 0x10001u;
+                uint32_t RM[4], X[4], T[4];
+                RM[0] = pk::lo2((uint32_t)__mul24(qlen - 1 - jb, prm.max_sc)) - ((uint32_t)prm.max_sc << 16);
+#pragma unroll
+                for (int c = 1; c < 4; ++c) RM[c] = pk::subs(RM[c - 1], A2X);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) X[c] = pk::max(Hn[c] & AM[c], E2[c]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) T[c] = pk::min1(X[c]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) X[c] = pk::mad(T[c], RM[c], X[c]);
+                pot = pk::max(pot, pk::max(pk::max(X[0], X[1]), pk::max(X[2], X[3])));
+            }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const uint32_t ha = Hn[c] & AM[c];
@@ -970,6 +1007,11 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
             }
             // ---- the end of a row
             const int rkey = pk::quad_all_max(key), rhl = pk::quad_all_max(hlast);
+            int rpot = 0;
+            if constexpr (EARLY != 0) {
+                const int a = (int)(pot & 0xffffu), b = (int)(pot >> 16);
+                rpot = pk::quad_all_max(a > b ? a : b);
+            }
             int last_nz = nz_last - 1;                                  // -1: none
             int first_nz = nz_first;                                    // 256: none (beyond every column)
             if (alive && !more) {
@@ -1004,6 +1046,23 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
                     const int nbeg = first_nz < end ? first_nz : end;
                     int jj = last_nz >= nbeg ? last_nz : nbeg - 1;
                     jj = h1f != 0 ? end : jj;
+                    if constexpr (EARLY != 0) {
+                        // column beg of a row that starts at column 0 stores h1, the source of column 0's cell in the next row (next
+                        // row's own first-column value is smaller)
+                        int P = h1 + __mul24(qlen, prm.max_sc);
+                        P = h1 > 0 ? P : 0;
+                        P = P > rpot ? P : rpot;
+                        const bool tail_known = end >= zr;                    // nothing alive to the right of this row's band
+                        zr = tail_known ? jj : zr;
+                        const bool ends = tail_known && P <= mx && P < gscore && (EARLY == 1 || (i & 3) == 3);
+#ifdef BWAMS_BSWDBG
+                        if (g == 0 && ends && !fin && i + 1 < tlen) ++n_rule;
+#endif
+                        fin = fin || ends;
+                    }
+#ifdef BWAMS_BSWDBG
+                    if (g == 0) ++n_rows;
+#endif
                     beg = nbeg;
                     end = jj + 2 < qlen ? jj + 2 : qlen;
                     ++i;
@@ -1032,6 +1091,7 @@ __global__ __launch_bounds__(kPkWaves * 64) void bsw_pk_kernel(
         atomicAdd(&d[0], __builtin_amdgcn_s_memtime() - T0); atomicAdd(&d[1], t_refill); atomicAdd(&d[2], t_pass);
         atomicAdd(&d[3], n_events); atomicAdd(&d[4], n_filled); atomicAdd(&d[5], n_iter); atomicAdd(&d[6], 1ull);
     }
+    if (g == 0 && n_rows) { atomicAdd(&ctr->dbg[47], n_rows); atomicAdd(&ctr->dbg[48], n_rule); }     // rows walked, tasks the rule ended
 #endif
     for (int o = 32; o > 0; o >>= 1) cells += ((unsigned long long)__shfl_down((unsigned)(cells >> 32), o) << 32) | (unsigned)__shfl_down((unsigned)cells, o);
     if (lane == 0 && cells) atomicAdd(&ctr->bsw_cells, cells);
@@ -1049,7 +1109,7 @@ __global__ void bsw_reset_kernel(DevCounters *ctr) {
 // streams they run concurrently, the classes of the longest queries first.  `list` holds kNumBswClass * n task indices.
 int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint8_t *qer, int w, const SwParams &prm, int qmax,
                DevCounters *ctr, int cu_count, hipStream_t st, int32_t *list, hipStream_t *aux, hipEvent_t fork, hipEvent_t *join,
-               const int64_t *src, int dir) {
+               const int64_t *src, int dir, bool early) {
     bsw_reset_kernel<<<1, 1, 0, st>>>(ctr);
     if (n <= 0) return 0;
     bsw_classify_kernel<<<(unsigned)((n + 1023) / 1024), 1024, 0, st>>>(pairs, n, prm.max_sc, list, ctr->bsw_cls_cnt);
@@ -1078,7 +1138,8 @@ int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint
         if (dev < 0 || dev >= 64 || !done[dev]) {
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_qwin_kernel<kBswLpt, kBswWin>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)((size_t)kWavesPerBlock * (64 / kBswLpt) * 192 * 4)) != hipSuccess) return -1;
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_pk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds(192)) != hipSuccess) return -1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_pk_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds(192)) != hipSuccess) return -1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(bsw_pk_kernel<kPkEarlyForm>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk_lds(192)) != hipSuccess) return -1;
             if (dev >= 0 && dev < 64) done[dev] = true;
         }
     }
@@ -1089,8 +1150,10 @@ int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint
     if (pk_env && bsw_pk_eligible(prm)) {
         static const int kCols[5] = {32, 64, 96, 144, 192};
         const unsigned Bp = (unsigned)((int64_t)B * kWavesPerBlock / kPkWaves);
+        // the early exit rests on a positive best score per column; the 32-bit kernels below walk every row whatever the setting
+        auto *const kern = early && prm.max_sc > 0 ? bsw_pk_kernel<kPkEarlyForm> : bsw_pk_kernel<0>;
         for (int c = 4; c >= 0; --c)
-            bsw_pk_kernel<<<Bp, kPkWaves * 64, pk_lds(kCols[c]), q[c]>>>(pairs, list + (int64_t)c * n, cnt + c, ref, qer, w, prm, ctr, hd + c, kCols[c], src, dir);
+            kern<<<Bp, kPkWaves * 64, pk_lds(kCols[c]), q[c]>>>(pairs, list + (int64_t)c * n, cnt + c, ref, qer, w, prm, ctr, hd + c, kCols[c], src, dir);
     } else {
     bsw_qwin_kernel<kBswLpt, kBswWin><<<B, T, (size_t)kWavesPerBlock * (64 / kBswLpt) * 192 * 4, q[4]>>>(pairs, list + 4 * n, cnt + 4, ref, qer, w, prm, ctr, hd + 4, 192, src, dir);
     bsw_qwin_kernel<kBswLpt, kBswWin><<<B, T, (size_t)kWavesPerBlock * (64 / kBswLpt) * 144 * 4, q[3]>>>(pairs, list + 3 * n, cnt + 3, ref, qer, w, prm, ctr, hd + 3, 144, src, dir);

@@ -40,6 +40,8 @@ struct Knobs {
     int pair_drop_plan = 0;        // BWAMS_PAIR_DROP_PLAN: exercise mate rescue's second pass
     int trace_pair = 0;            // BWAMS_TRACE_PAIR: a synchronisation and a line per launch of the paired-end tail
     int bsw_pk = 1;                // BWAMS_BSW_PK=0: the 32-bit eight-task banded-SW kernel
+    int bsw_early = -1;            // BWAMS_BSW_EARLY: the packed kernel's early exit.  Unset: on in bwams_extend_run, off in bwams_bsw_run (whose
+                                   // bsw_cells the tests pin to the cells of the full walk); 0: off in both; 1: on in both
     int chain_count = 0;           // BWAMS_CHAIN_COUNT=1: chaining counts its filter routes and the passes of chain_seeds_batch (tests)
     int chain_batch = 1;           // BWAMS_CHAIN_BATCH=0: chaining's wave tier takes one seed at a time (chain_dev.h: chain_seeds_batch)
     int ert_fat = 1;               // BWAMS_ERT_FAT=0: the ERT walk reads the reference's two tables only (no entry + tree-head table)
@@ -849,7 +851,7 @@ struct BwdItem {
 
 int launch_bsw(bwams_seqpair_t *pairs, int64_t n, const uint8_t *ref, const uint8_t *qer, int w, const SwParams &prm, int qmax,
                DevCounters *ctr, int cu_count, hipStream_t st, int32_t *list, hipStream_t *aux = nullptr, hipEvent_t fork = nullptr,
-               hipEvent_t *join = nullptr, const int64_t *src = nullptr, int dir = 1);
+               hipEvent_t *join = nullptr, const int64_t *src = nullptr, int dir = 1, bool early = false);   // early: bsw_pk_kernel's early exit
 size_t bsw_list_bytes(int64_t n_tasks);          // scratch `list` of launch_bsw
 int bsw_lds_waves(int qmax);                     // waves per block of launch_bsw's one-task-per-wave kernel; 0: qmax does not fit
 void launch_emf_probe(const DevEmf &t, const uint8_t *enc, const int64_t *cum, int64_t nseq, uint32_t *out,

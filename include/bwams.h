@@ -767,7 +767,9 @@ typedef struct bwams_stats {
     int64_t n_lf_steps;       /* LF steps the REFERENCE walks for them (to its 1/8 samples): the same number whether the lookup
                                  walked them or read them from the index's dense table (BWAMS_SA_DENSE) */
     int64_t n_smem[3];        /* SMEMs from round 1, 2, 3 */
-    int64_t bsw_cells;        /* DP cells evaluated by the last bsw run */
+    int64_t bsw_cells;        /* DP cells actually computed by the last bsw run.  With the packed kernel's early exit (on in bwams_extend_run
+                                 unless BWAMS_BSW_EARLY=0; in bwams_bsw_run only with BWAMS_BSW_EARLY=1) a task stops once no later row can
+                                 change its six outputs, so the count lies below that of scalarBandedSWA's full walk */
     int64_t n_ext_round[3];   /* n_ext split by round */
     int64_t n_blk_round[3];   /* n_ext_blocks split by round */
     float   ms_smem_r1, ms_smem_r2, ms_smem_r3, ms_sort, ms_sal, ms_seed_total;
