@@ -58,6 +58,7 @@ SYMBOLS = [
     "bwams_dup_library_size", "bwams_dup_metrics_text", "bwams_sorter_set_markdup", "bwams_sorter_close3",
     "bwams_bam_reads_decode", "bwams_bam_reads_info", "bwams_process_chunk_bam", "bwams_process_chunk_bam_smart",
     "bwams_reader_open_bam", "bwams_reader_bam_header",
+    "bwams_trim_opt_default", "bwams_fastq_trim", "bwams_fastq_text", "bwams_fastq_text_fetch", "bwams_process_chunk_decoded",
     "bwams_process_reads_upload", "bwams_process_reads_stage1_run", "bwams_batch_device", "bwams_multi_upload", "bwams_multi_compute",
     "bwams_shard_bounds", "bwams_multi_create", "bwams_multi_process_reads", "bwams_multi_fetch", "bwams_multi_error", "bwams_multi_destroy",
     "bwams_depth_open", "bwams_depth_close", "bwams_depth_reset", "bwams_depth_add_batch", "bwams_depth_add_records", "bwams_depth_finish",
@@ -212,10 +213,67 @@ class Fastq:
         _chk(lib().bwams_fastq_to_batch(self.h, batch.h), "bwams_fastq_to_batch")
         batch._nseq = self.n_reads
 
+    def trim(self, opt: "TrimOpt | None" = None, paired: bool = False, report: bool = True):
+        """bwams_fastq_trim -> (the trimmed chunk, a new Fastq; the report (TRIM_READ_DTYPE) or None; the stats as trim.stats_of's dict).
+        This chunk is left as it is."""
+        opt = opt if opt is not None else trim_opt()
+        g = Fastq(None)
+        rep = np.zeros(self.n_reads, TRIM_READ_DTYPE) if report else None
+        st = TrimStats()
+        _chk(lib().bwams_fastq_trim(self.h, C.byref(opt), 1 if paired else 0, C.byref(g.h), _p(rep) if report and self.n_reads else None,
+                                    C.byref(st)), "bwams_fastq_trim")
+        g.n_reads, g.n_bases = st.reads_out, st.bases_out
+        return g, rep, st.as_dict()
+
+    def text(self, with_comment: bool = True, fetch: bool = True):
+        """bwams_fastq_text: the chunk as FASTQ (or FASTA) text -> bytes, or (device address, n_bytes) with fetch=False; the device
+        text lives until the next call or close()."""
+        d, n = C.c_void_p(), C.c_int64(0)
+        _chk(lib().bwams_fastq_text(self.h, 1 if with_comment else 0, C.byref(d), C.byref(n)), "bwams_fastq_text")
+        if not fetch:
+            return d.value, n.value
+        buf = np.zeros(max(n.value, 1), np.uint8)
+        _chk(lib().bwams_fastq_text_fetch(self.h, _p(buf), n.value), "bwams_fastq_text_fetch")
+        return bytes(buf[:n.value])
+
     def close(self):
         if self.h:
             lib().bwams_fastq_close(self.h)
             self.h = C.c_void_p()
+
+
+TRIM_READ_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("insert", "<i4"), ("reason", "u1"), ("steps", "u1"), ("pad_", "u1", (2,)),
+                            ("removed", "<i4", (6,))])                                                   # bwams_trim_read_t
+assert TRIM_READ_DTYPE.itemsize == 40
+
+
+class TrimOpt(C.Structure):
+    """bwams_trim_opt_t (trim_opt() gives the defaults)"""
+    _fields_ = [(n, C.c_int32) for n in ("trim_front", "trim_tail", "cut_front", "cut_tail", "cut_window", "cut_quality", "overlap",
+                                         "overlap_min", "overlap_max_diff", "overlap_diff_pct", "adapter_min_match", "adapter_mismatch_per",
+                                         "max_len", "min_len", "n_limit", "qual_floor", "low_qual_pct")] + \
+               [("adapter1", C.c_char * 129), ("adapter2", C.c_char * 129), ("pad_", C.c_char * 2)]
+
+
+class TrimStats(C.Structure):
+    """bwams_trim_stats_t"""
+    _fields_ = [(n, C.c_int64) for n in ("reads_in", "bases_in", "reads_out", "bases_out", "pairs_insert", "pairs_skipped")] + \
+               [("step_reads", C.c_int64 * 6), ("step_bases", C.c_int64 * 6), ("dropped", C.c_int64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {n: (list(getattr(self, n)) if n in ("step_reads", "step_bases", "dropped") else getattr(self, n)) for n, _ in self._fields_}
+
+
+def trim_opt(like=None, **kw) -> TrimOpt:
+    """bwams_trim_opt_default, then the fields of `like` (any object with TrimOpt's fields, such as trim.Opt), then the keywords"""
+    o = TrimOpt()
+    _chk(lib().bwams_trim_opt_default(C.byref(o)), "bwams_trim_opt_default")
+    for n, _ in TrimOpt._fields_[:-1]:
+        if like is not None:
+            setattr(o, n, getattr(like, n))
+        if n in kw:
+            setattr(o, n, kw[n])
+    return o
 
 
 class SamOpt(C.Structure):
@@ -1566,6 +1624,11 @@ def lib():
         L.bwams_bam_reads_info.argtypes = [vp, vp, vp, vp, vp]
         L.bwams_process_chunk_bam.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, C.c_char_p, i32, vp, i64, i32, vp, vp]
         L.bwams_process_chunk_bam_smart.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, C.c_char_p, vp, i64, i32, vp, vp, vp]
+        L.bwams_trim_opt_default.argtypes = [vp]
+        L.bwams_fastq_trim.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.bwams_fastq_text.argtypes = [vp, i32, vp, vp]
+        L.bwams_fastq_text_fetch.argtypes = [vp, vp, i64]
+        L.bwams_process_chunk_decoded.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, i32, vp, vp]
         L.bwams_deflate_bound.restype = i64
         L.bwams_deflate_bound.argtypes = [i64]
         L.bwams_deflater_create.argtypes = [C.c_int, i64, vp]
@@ -2505,6 +2568,25 @@ class Batch:
         _chk(lib().bwams_process_chunk_bam(self.h, emf.h if emf is not None else None, ert.h if ert is not None else None, C.byref(seed_opt),
                                            C.byref(opt), C.byref(sopt), src, nbytes, tags or None, 1 if paired else 0, pp, n_processed,
                                            flags | (0x100 if copy_comment else 0), C.byref(n), C.byref(nb)), "bwams_process_chunk_bam")
+        self._nseq, self._sam_bytes = n.value, nb.value
+        if not fetch:
+            return nb.value
+        text, off, _ = self.sam_fetch()
+        return text, off
+
+    def process_chunk_decoded(self, fq: "Fastq", paired: bool = False, emf=None, ert=None, seed_opt=None, opt: MemOpt | None = None, sopt=None,
+                              pes=None, n_processed: int = 0, flags: int = 0, copy_comment: bool = False, fetch: bool = True):
+        """bwams_process_chunk_decoded: process_chunk for a chunk already decoded (and perhaps trimmed); fq is consumed ->
+        (SAM text, read_off), or the byte count with fetch=False."""
+        seed_opt = seed_opt or default_seed_opt()
+        opt = opt or default_mem_opt()
+        sopt = sopt or default_sam_opt()
+        n, nb = C.c_int64(0), C.c_int64(0)
+        pp = _p(np.ascontiguousarray(pes, PESTAT_DTYPE)) if pes is not None else None
+        h, fq.h = fq.h, C.c_void_p()
+        _chk(lib().bwams_process_chunk_decoded(self.h, emf.h if emf is not None else None, ert.h if ert is not None else None, C.byref(seed_opt),
+                                               C.byref(opt), C.byref(sopt), h, 1 if paired else 0, pp, n_processed,
+                                               flags | (0x100 if copy_comment else 0), C.byref(n), C.byref(nb)), "bwams_process_chunk_decoded")
         self._nseq, self._sam_bytes = n.value, nb.value
         if not fetch:
             return nb.value

@@ -200,6 +200,19 @@ int bwams_process_chunk(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, co
     return chunk_decoded("bwams_process_chunk", b, fq, n, emf, ert, so, mo, sam_opt, paired, pes0, n_processed, flags, n_reads, sam_bytes);
 }
 
+// The same chunk already decoded (and perhaps trimmed: api_trim.hip) by the caller
+int bwams_process_chunk_decoded(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                                const bwams_sam_opt_t *sam_opt, bwams_fastq_t *fq, int32_t paired, const bwams_pestat_t *pes0,
+                                int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes) {
+    if (!b || !so || !mo || !sam_opt || !fq || (paired != 0 && paired != 1) || fq->device != b->idx->device) {
+        bwams_fastq_close(fq);
+        set_last_error("bwams_process_chunk_decoded: batch, options and a chunk decoded on the batch's device are required; paired is 0 or 1");
+        return BWAMS_ERR_ARG;
+    }
+    return chunk_decoded("bwams_process_chunk_decoded", b, fq, fq->n_reads, emf, ert, so, mo, sam_opt, paired, pes0, n_processed, flags, n_reads,
+                         sam_bytes);
+}
+
 // The same chunk given as BAM records (bam_reads.hip decodes them to the same handle)
 int bwams_process_chunk_bam(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
                             const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags, int32_t paired,

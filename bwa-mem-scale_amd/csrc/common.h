@@ -869,6 +869,32 @@ int segment_copy(const std::vector<SegMove> &moves, hipStream_t st);
 // into *ends (allocated here: n_nl + 16 slots)
 int line_ends(const char *d_text, int64_t n_bytes, hipStream_t st, DevBuf<int64_t> *ends, int64_t *n_nl);
 
+// trim.hip: read trimming (rules T1 to T9 above bwams_fastq_trim in include/bwams.h).  TrimParams: the options in kernel form, the two
+// adapters as bit planes (bit k of a_lo / a_hi[which][k / 64] = the low / high bit of letter k's code).  TrimArrays: a decoded
+// chunk's arrays, the offsets in device memory too.  reads: report[i] for every read.  widths: wide[row * (n + 1) + i], rows = name
+// bytes, comment bytes, bases that read i brings to the new chunk; gather: the kept reads to offs = the exclusive scans of those rows.
+struct TrimParams {
+    int32_t trim_front, trim_tail, cut_front, cut_tail, cut_window, cut_quality, overlap, overlap_min, overlap_max_diff, overlap_diff_pct,
+        adapter_min_match, adapter_mismatch_per, max_len, min_len, n_limit, qual_floor, low_qual_pct;
+    int32_t paired, has_qual;
+    int32_t a_len[2];
+    unsigned long long a_lo[2][2], a_hi[2][2];
+};
+struct TrimArrays {
+    uint8_t *enc;
+    char *qual, *names, *comments;       // qual: nullptr for a chunk without qualities
+    const int64_t *cum, *name_off, *comment_off;
+};
+void launch_trim_reads(const uint8_t *enc, const char *qual, const int64_t *cum, int64_t n_reads, const TrimParams &P, bwams_trim_read_t *report,
+                       hipStream_t st);
+void launch_trim_widths(const bwams_trim_read_t *report, const int64_t *name_off, const int64_t *comment_off, int64_t n, int64_t *wide,
+                        hipStream_t st);
+void launch_trim_gather(const bwams_trim_read_t *report, int64_t n, const TrimArrays &in, const int64_t *offs, const TrimArrays &out,
+                        hipStream_t st);
+// a decoded chunk as FASTQ text: wide[i] = the bytes of read i's record (0 at i = n), emit to off = their exclusive scan
+void launch_fastq_text_widths(const TrimArrays &in, int64_t n, int with_comment, int64_t *wide, hipStream_t st);
+void launch_fastq_text_emit(const TrimArrays &in, int64_t n, int with_comment, const int64_t *off, char *text, hipStream_t st);
+
 // The reference metadata of an index made from FASTA (fasta_ref.hip): what bns_fasta2bntseq keeps and bns_dump writes.
 struct BnsMeta {
     int64_t l_pac = 0;
@@ -892,9 +918,11 @@ struct bwams_fastq {
     bool has_qual = true;                                  // false: FASTA text, or BAM records without qualities
     float ms_discover = 0;                                 // bam_reads.hip: the part of ms spent finding the records,
     int64_t n_cand = 0, n_records = 0;                     // the offsets that passed its filter, the records (skipped ones included)
+    bwams::DevBuf<char> d_text;                            // api_trim.hip: the chunk as FASTQ text (bwams_fastq_text), text_bytes of it
+    int64_t text_bytes = -1;                               // -1: no text yet
     // a decode that fails half way (an allocation, a kernel) drops the handle: whatever it had allocated goes with it
     ~bwams_fastq() {
-        if (d_enc.p || d_qual.p || d_names.p || d_comments.p) (void)hipSetDevice(device);
+        if (d_enc.p || d_qual.p || d_names.p || d_comments.p || d_text.p) (void)hipSetDevice(device);
     }
 };
 namespace bwams {

@@ -32,6 +32,17 @@ __device__ __forceinline__ int scan_max(int v) {
         : "+v"(v));
     return v;
 }
+// inclusive prefix sum over the 64 lanes, the same six DPP steps through the builtin (the compiler pads its hazards): a lane without
+// a valid source, or outside row_mask, adds 0
+__device__ __forceinline__ int scan_add(int v) {
+    v += dppi<0x111, 0xF, 0xF>(0, v);      // row_shr:1
+    v += dppi<0x112, 0xF, 0xF>(0, v);      // row_shr:2
+    v += dppi<0x114, 0xF, 0xF>(0, v);      // row_shr:4
+    v += dppi<0x118, 0xF, 0xF>(0, v);      // row_shr:8
+    v += dppi<0x142, 0xA, 0xF>(0, v);      // row_bcast:15 into rows 1 and 3
+    v += dppi<0x143, 0xC, 0xF>(0, v);      // row_bcast:31 into rows 2 and 3
+    return v;
+}
 __device__ __forceinline__ int lane_shr1(int v, int fill) { return dppi<0x138, 0xF, 0xF>(fill, v); }   // wave_shr:1
 
 // a 64-bit value of lane l (wave-uniform l: v_readlane) or of lane src (any src: ds_bpermute), as two 32-bit halves

@@ -648,6 +648,84 @@ int bwams_bam_reads_decode(int device, const void *bam, int64_t n_bytes, const c
                            int64_t *n_bases, int64_t *n_records);
 int bwams_bam_reads_info(const bwams_fastq_t *f, float *ms_discover, float *ms_emit, int64_t *n_candidates, int64_t *n_records);
 
+/* ------------------------------------------------------------- read trimming ---- *
+ * A decoded chunk in, an ordinary decoded chunk out (csrc/trim.hip): adapter read-through, low-quality ends and reads not worth
+ * mapping leave the chunk before it reaches the batch.  `in` is left untouched; *out is a bwams_fastq_t like any other
+ * (bwams_fastq_info / _has_qual / _fetch / _to_batch / _to_batch_opt / _text / _close work on it unchanged; the `ms` of bwams_fastq_info
+ * is the device time of the trim's kernels and scans, without the report's copy to the host between them).  Names and comments of
+ * the kept reads are copied byte for byte, in input order; has_qual is that of `in`.  The model is fastp's defaults, but no parity
+ * with any tool's output is claimed: bwams/trim.py restates the rules, and the device's arrays, report and stats equal it entry for
+ * entry.
+ * A read is codes c[0, n) and qualities q[i] = byte - 33 (0 when the byte is below 33); code 4 is N.  With paired, reads 2k and 2k + 1
+ * are the two ends.  The steps run in this order on the current read, each on what the one before left:
+ *  T1 fixed.  trim_front bases leave the 5' end, trim_tail the 3' end; nothing left: the read is empty.
+ *  T2 quality windows (a chunk with qualities, n > 0).  w = min(cut_window, n), S(i, j) the sum of q over [i, j).  cut_front: s is the
+ *     smallest s in [0, n - w] with S(s, s + w) >= w * cut_quality; none: the read is empty; otherwise s advances while q[s] <
+ *     cut_quality and the read becomes [s, n).  cut_tail, after cut_front and with w taken anew: e is the largest e in [w, n] with
+ *     S(e - w, e) >= w * cut_quality; none: empty; otherwise e falls while q[e - 1] < cut_quality and the read becomes [0, e).
+ *  T3 overlap (paired, overlap != 0, both ends at most BWAMS_TRIM_OVERLAP_MAX_LEN long; a longer pair skips T3 and is counted).
+ *     a = end 1 (n1 bases), b = the reverse complement of end 2 (n2 bases; 4 stays 4).  A candidate insert length I pairs a[i] with
+ *     b[i + n2 - I] for i in [lo, hi), lo = max(0, I - n2), hi = min(n1, I), ov = hi - lo; a position is a mismatch when the codes
+ *     differ or either is 4, d counts them.  I passes when ov >= overlap_min, d <= overlap_max_diff and 100 d <= overlap_diff_pct * ov.
+ *     Of all I in [overlap_min, n1 + n2 - overlap_min] the LARGEST that passes is the pair's insert; each end is cut to min(n, I)
+ *     (nothing is cut when I is at least both lengths: the insert still counts as found).
+ *  T4 adapter by sequence: a single read, and each end of a pair for which T3 found no insert (off, skipped, or no I passed), against
+ *     adapter1 (end 1, single reads) or adapter2 (end 2); an empty adapter: no step.  With the adapter A of m letters, for p from 0 to
+ *     n - adapter_min_match: cmp = min(n - p, m), d = #{k < cmp: c[p + k] != A[k] or c[p + k] == 4}; the smallest p with
+ *     d * adapter_mismatch_per <= cmp cuts the read to p bases.
+ *  T5 max_len > 0: n = min(n, max_len).
+ *  T6 filters, per end, the first that fails being the end's reason: LEN n < min_len; N more than n_limit bases of code 4; QUAL (with
+ *     qualities) 100 * #{q < qual_floor} > low_qual_pct * n.  A single read that fails is dropped; a pair is dropped when either end
+ *     fails, and an end that itself passes gets the reason MATE.
+ *  T7 report, one entry per read of `in`: start / len, what T1-T5 left, in the input read's coordinates (a dropped read's too; an
+ *     empty read has len 0); insert, T3's I or 0 (both ends carry it); reason; removed[k], the bases step k took from this read (k:
+ *     BWAMS_TRIM_STEP_*), and steps, bit k set when removed[k] > 0, BWAMS_TRIM_STEP_SKIPPED on both ends of a pair that skipped T3.
+ *  T8 stats: every number is a function of the report (and the input lengths): pairs_insert counts the pairs with insert > 0,
+ *     pairs_skipped those with BWAMS_TRIM_STEP_SKIPPED, step_reads[k] / step_bases[k] the reads with removed[k] > 0 and the sum of
+ *     removed[k], dropped[r - 1] the reads with reason r.
+ *  T9 refusals, before anything is allocated: BWAMS_ERR_ARG, bwams_last_error naming the field, for an option outside its range (the
+ *     counts and limits are >= 0, cut_window is in 1..64, overlap_min / adapter_min_match / adapter_mismatch_per / min_len are >= 1),
+ *     an adapter with a letter other than A, C, G, T or without a NUL in its 129 bytes, or paired with an odd number of reads.  A
+ *     chunk from which nothing survives gives a valid chunk of 0 reads.  With every step off and filters that pass everything
+ *     (min_len 1: an empty read never survives), *out equals `in` array for array.
+ * Not built: adapter auto-detection, base correction inside the overlap, polyG / polyX tails, UMIs, fixed trims per end, chunks that
+ * mix single reads and pairs (`mem -p` smart pairing), and the compiled mem_process_seqs() path (it returns one text per input read). */
+#define BWAMS_TRIM_OVERLAP_MAX_LEN 1024
+enum { BWAMS_TRIM_KEPT = 0, BWAMS_TRIM_LEN = 1, BWAMS_TRIM_N = 2, BWAMS_TRIM_QUAL = 3, BWAMS_TRIM_MATE = 4 };
+enum { BWAMS_TRIM_STEP_FIXED = 0, BWAMS_TRIM_STEP_CUT_FRONT = 1, BWAMS_TRIM_STEP_CUT_TAIL = 2, BWAMS_TRIM_STEP_OVERLAP = 3,
+       BWAMS_TRIM_STEP_ADAPTER = 4, BWAMS_TRIM_STEP_MAX_LEN = 5, BWAMS_TRIM_N_STEPS = 6 };
+#define BWAMS_TRIM_STEP_SKIPPED 0x40
+typedef struct bwams_trim_opt {
+    int32_t trim_front, trim_tail;                                         /* T1: 0, 0 */
+    int32_t cut_front, cut_tail, cut_window, cut_quality;                  /* T2: 0, 1, 4, 20 */
+    int32_t overlap, overlap_min, overlap_max_diff, overlap_diff_pct;      /* T3: 1, 30, 5, 20 */
+    int32_t adapter_min_match, adapter_mismatch_per;                       /* T4: 4, 8 */
+    int32_t max_len;                                                       /* T5: 0 = none */
+    int32_t min_len, n_limit, qual_floor, low_qual_pct;                    /* T6: 15, 5, 15, 40 */
+    char adapter1[129], adapter2[129];                                     /* T4: NUL-terminated, A / C / G / T, empty = none */
+    char pad_[2];
+} bwams_trim_opt_t;                                                        /* 328 bytes */
+typedef struct bwams_trim_read {
+    int32_t start, len, insert;
+    uint8_t reason, steps, pad_[2];
+    int32_t removed[BWAMS_TRIM_N_STEPS];
+} bwams_trim_read_t;                                                       /* 40 bytes */
+typedef struct bwams_trim_stats {
+    int64_t reads_in, bases_in, reads_out, bases_out, pairs_insert, pairs_skipped;
+    int64_t step_reads[BWAMS_TRIM_N_STEPS], step_bases[BWAMS_TRIM_N_STEPS];
+    int64_t dropped[4];                                                    /* LEN, N, QUAL, MATE */
+} bwams_trim_stats_t;                                                      /* 176 bytes */
+int bwams_trim_opt_default(bwams_trim_opt_t *o);
+int bwams_fastq_trim(bwams_fastq_t *in, const bwams_trim_opt_t *opt, int32_t paired, bwams_fastq_t **out,
+                     bwams_trim_read_t *report /* n_reads(in) entries or NULL */, bwams_trim_stats_t *stats /* or NULL */);
+/* A decoded chunk as FASTQ text (`fastp -o`), in device memory owned by the handle until it is closed (a second call replaces the
+ * first call's text): with qualities "@name[ comment]\nSEQ\n+\nQUAL\n" per read, without them ">name[ comment]\nSEQ\n"; the codes
+ * 0..4 become ACGTN; the comment (with_comment != 0 and the read has one) follows one space.  Names are written as held: the "/1" and
+ * "/2" suffixes that bwams_fastq_decode removed do not come back.  bwams_fastq_text_fetch copies the last text to the host
+ * (BWAMS_ERR_CAPACITY when cap is below its size, BWAMS_ERR_ARG without a text). */
+int bwams_fastq_text(bwams_fastq_t *f, int32_t with_comment, const char **d_text, int64_t *n_bytes);
+int bwams_fastq_text_fetch(bwams_fastq_t *f, char *out, int64_t cap);
+
 /* ----------------------------------------------------------- mate rescue ---- */
 
 /* Local Smith-Waterman of mate rescue over n tasks: out[i] = ksw_align2(len2, qer + idq,
@@ -999,6 +1077,13 @@ int bwams_process_chunk_bam_smart(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_
                                   const bwams_sam_opt_t *sam_opt, const void *bam, int64_t n_bytes, const char *tags,
                                   const bwams_pestat_t *pes0, int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *n_single,
                                   int64_t *sam_bytes);
+/* bwams_process_chunk behind its decode, for a chunk the caller decoded (bwams_fastq_decode, bwams_bam_reads_decode) and perhaps
+ * trimmed (bwams_fastq_trim): decode, then trim, then map.  fq is consumed: closed here whatever the outcome.  paired is 0 or 1 (no
+ * smart pairing of a decoded chunk).  *n_reads: the reads of fq.  n_processed counts the reads that reached the mapper before this
+ * chunk: after trimming, the KEPT reads of the chunks before (the reads the text numbers), not the reads of the input files. */
+int bwams_process_chunk_decoded(bwams_batch_t *b, bwams_emf_t *emf, bwams_ert_t *ert, const bwams_seed_opt_t *so, const bwams_mem_opt_t *mo,
+                                const bwams_sam_opt_t *sam_opt, bwams_fastq_t *fq /* consumed */, int32_t paired, const bwams_pestat_t *pes0,
+                                int64_t n_processed, int32_t flags, int64_t *n_reads, int64_t *sam_bytes);
 
 /* mem_process_seqs (src/bwamem.cpp:1850-1903) for a chunk that arrives the way the reference hands it over: parsed records (bseq1_t:
  * name, comment, seq, qual — src/bwa.h:76-86), here as flat arrays — enc_qdb / cum_len as bwams_seed_upload takes them, names (NUL
